@@ -11,6 +11,11 @@ from the two are comparable (last row):
 * three report lines: `average reward`, `reward stds`, `rewards` (:61-63);
 * defaults `--env-name point --policy-name ppo` (:68-69).
 
+`--robots N` runs the same protocol for max(N, epochs) robots at once on the device goal environment (the kinematic
+stand-in stepped by the engine, no time limit, reset on goal): ONE engine call instead of one `predict` round trip per robot
+and step.  Each robot is one epoch: the `rewards` line lists max(N, epochs) figures.  Without `--robots` the script runs the
+host loop above, exactly as before.
+
 GUI rendering, the 5 ms sleep that paces the Bullet GUI and video recording (:24-33, :48-52) need the real MuJoCo / Bullet
 simulators; the kinematic stand-in robots have nothing to draw, so `--no-gui` / `--video-path` are accepted and ignored.
 """
@@ -52,6 +57,21 @@ def simulate(env_name, policy_name="ppo", epochs=5, no_gui=True, video_path=None
     return rewards
 
 
+def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None, seed=0):
+    """The protocol of `simulate` for max(robots, epochs) robots in one device evaluation (PPOEngine.evaluate_goal_env)."""
+    from mobrob_amd import load_policy
+    from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
+    policy = load_policy(env_name, policy_name) if policy is None else policy
+    n = max(int(robots), int(epochs))
+    env = DeviceGoalVecEnv.for_robot(env_name, n, time_limit=0, seed=seed, terminate_on_goal=True)
+    r = env.evaluate(policy.engine, n_robots=n, max_steps=STEPS_PER_EPOCH, episodes=0, deterministic=True)
+    rewards = [float(x) for x in r["reward_sum"]]
+    print(f"average reward: {np.mean(rewards)}")
+    print(f"reward stds: {np.std(rewards)}")
+    print(f"rewards: {rewards}")
+    return rewards
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--env-name", type=str, default="point")
@@ -59,5 +79,10 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--no-gui", action="store_true", default=False)
     ap.add_argument("--video-path", type=str, default=None)
+    ap.add_argument("--robots", type=int, default=None,
+                    help="evaluate max(ROBOTS, epochs) robots at once on the device (one engine call)")
     a = ap.parse_args()
+    if a.robots is not None:
+        simulate_device(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, robots=a.robots)
+        sys.exit(0)
     simulate(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, no_gui=a.no_gui, video_path=a.video_path)

@@ -423,6 +423,49 @@ int mobrob_ppo_fetch_step_stats(mobrob_ppo_engine_t* e, float* out, int32_t max_
 int mobrob_ppo_predict(mobrob_ppo_engine_t* e, const float* obs, int32_t n, int32_t deterministic,
                        const float* eps /* n*A or NULL */, float* actions_clipped, float* values);
 
+/* ---- evaluation: SB3 evaluate_policy / examples/control.py:36-46 on the device goal environment ----------------------
+ * n_robots independent robots of the goal environment above, driven by the CURRENT policy, all on the device:
+ *   start     every robot starts from a fresh reset -- pose from init_space, new goal (reference examples/control.py:37).
+ *   stepping  action, then the env step of mobrob_ppo_collect_goal_env (src/mobrob/envs/wrapper.py:156-171); on termination
+ *             (goal reached and terminate_on_goal) or truncation (env->time_limit steps; 0 = no limit, the control.py protocol)
+ *             the robot resets (wrapper.py:173-201, control.py:41-44): a robot that reached its goal keeps its pose (lazy reset).
+ *   actions   deterministic = 1: clip(mean) (policy.predict(obs, deterministic=True), control.py:39); 0: clip(mean + exp(log_std)
+ *             N(0,1)) from the evaluation's stream (refused for use_sde).
+ *   robot_out [n_robots][4] doubles: reward sum over all steps run, steps run, episodes finished, goals reached.  Rewards are
+ *             summed in float64, as SB3's evaluate_policy (`current_rewards += rewards`) and control.py (`cum_reward += r`) do.
+ *   episodes  0: every robot runs exactly max_steps steps (control.py).  > 0: the total number of episodes (SB3 n_eval_episodes);
+ *             robot i finishes quota[i] episodes -- or, with quota = NULL, SB3's split (episodes + i) / n_robots
+ *             (evaluate_policy's episode_count_targets) -- and idles afterwards (max_steps still bounds it).  Needs
+ *             time_limit > 0 (MOBROB_ERR_INVALID otherwise: such a run might never finish).
+ *   episode_out [n_robots][max_i quota[i]][3] doubles, or NULL: (return, length, success) of the first quota[i] episodes of
+ *             robot i, in order; success = the episode ended inside the reach radius (wrapper.py:203-207).  Records beyond an
+ *             unfinished quota are zero.
+ *   trace_out [trace_steps][trace_robots][9 + obs_dim + act_dim + 4] floats, or NULL (tests: teacher forcing): per step and robot
+ *             pos[3] vel[3] goal[3] BEFORE the step, the observation the policy saw, the action applied, the reward, and the
+ *             flags reached, terminated, truncated (1.0 / 0.0).  Rows of robots that idle are zero.
+ *   streams   the evaluation's own Philox streams (stream constants of its own, key = seed; counter = (robot, component, step)):
+ *             it never reads nor advances the engine's draw counter, env step base, env state, episode statistics / records,
+ *             rollout, training or gSDE buffers -- evaluating between any two calls leaves training bit-identical.
+ *   ordering  enqueued on the engine's stream (it sees the parameters of any pending train_enqueue); reads the flat f32
+ *             parameter vector; returns after the results are copied out.  Its device buffers are allocated on first use, grown
+ *             when needed and freed by mobrob_ppo_destroy; they are outside the engine's arena (mobrob_ppo_device_bytes and
+ *             mobrob_ppo_create_in_arena are unchanged).
+ *   kernels   2x64 tanh engines of the fused family: ONE persistent launch (k_eval64_goal); every other engine: the engine's
+ *             forward plus one kernel per step (k_eval_goal_step).  MOBROB_EVAL_PERSISTENT=0 forces the per-step path.
+ * Returns 1 when the persistent kernel ran, 0 for the per-step path, or a negative error. */
+typedef struct mobrob_eval_spec {
+  int32_t n_robots;        /* >= 1, independent of the engine's n_envs                                        */
+  int32_t max_steps;       /* hard bound on steps per robot                                                   */
+  int32_t episodes;        /* 0: run every robot for exactly max_steps (control.py protocol);
+                              > 0: episode quota (SB3 evaluate_policy), robot idles after its share            */
+  int32_t deterministic;   /* 1: clip(mean); 0: mean + exp(log_std) * N(0,1), clipped (refused for use_sde)      */
+  uint64_t seed;           /* Philox key of the evaluation streams                                            */
+  int32_t trace_robots, trace_steps;   /* optional teacher-forcing trace of the first robots / steps (tests)    */
+} mobrob_eval_spec_t;
+int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                                 const int32_t* quota /* [n_robots] or NULL */, double* robot_out /* [n_robots][4] */,
+                                 double* episode_out /* [n_robots][max quota][3] or NULL */, float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

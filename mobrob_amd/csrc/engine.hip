@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <climits>
 #include <cstring>
 #include <ctime>
 #include <cstdlib>
@@ -48,6 +49,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_fused.h"
 #include "fused_dispatch.h"
 #include "kernels_env.h"
+#include "kernels_eval.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -255,6 +257,9 @@ struct mobrob_ppo_engine {
   bool plan_only = false;  // sizing pass: count bytes, touch no device
   std::vector<NormChunk> chunk_table;
   FusedState fused;
+  // policy evaluation (mobrob_ppo_evaluate_goal_env): one hipMalloc of its own, outside the arena, grown on demand
+  char* eval_buf = nullptr;
+  size_t eval_bytes = 0;
 };
 
 namespace {
@@ -1219,6 +1224,7 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   }
   for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
   for (void* p : e->allocs) (void)hipFree(p);
+  if (e->eval_buf) (void)hipFree(e->eval_buf);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3207,6 +3213,109 @@ int mobrob_ppo_predict(mobrob_ppo_engine_t* e, const float* obs, int32_t n, int3
     HIPC(hipStreamSynchronize(e->stream));
   }
   return MOBROB_OK;
+}
+
+// ---- policy evaluation: evaluate_policy / examples/control.py on the device ---------------------------------------------
+int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                                 const int32_t* quota, double* robot_out, double* episode_out, float* trace_out) {
+  if (!e || !env || !spec || !robot_out) return fail(MOBROB_ERR_INVALID, "evaluate: null argument");
+  const int N = spec->n_robots;
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "evaluate: n_robots must be >= 1");
+  if (spec->max_steps < 1) return fail(MOBROB_ERR_INVALID, "evaluate: max_steps must be >= 1");
+  if (spec->episodes < 0) return fail(MOBROB_ERR_INVALID, "evaluate: episodes must be >= 0");
+  if (env->pos_dim < 1 || env->pos_dim > 3 || 3 * env->pos_dim > e->D)
+    return fail(MOBROB_ERR_INVALID, "evaluate: pos_dim must be 1..3 and 3*pos_dim <= obs_dim");
+  if (e->A > 32) return fail(MOBROB_ERR_INVALID, "evaluate: act_dim must be <= 32");
+  if (env->time_limit < 0) return fail(MOBROB_ERR_INVALID, "evaluate: time_limit must be >= 0 (0: none)");
+  if (spec->episodes > 0 && env->time_limit == 0)
+    return fail(MOBROB_ERR_INVALID, "evaluate: an episode quota needs a time limit (the run might never finish)");
+  if (!spec->deterministic && e->sde)
+    return fail(MOBROB_ERR_INVALID, "evaluate: stochastic actions of a use_sde policy are not supported (deterministic only)");
+  const bool tracing = trace_out && spec->trace_robots > 0 && spec->trace_steps > 0;
+  if (tracing && (spec->trace_robots > N || spec->trace_steps > spec->max_steps))
+    return fail(MOBROB_ERR_INVALID, "evaluate: trace_robots <= n_robots and trace_steps <= max_steps");
+  std::vector<int32_t> q(N);
+  int maxq = 0;
+  for (int i = 0; i < N; ++i) {
+    q[i] = quota ? quota[i] : (spec->episodes > 0 ? (int32_t)(((int64_t)spec->episodes + i) / N) : 0);
+    if (q[i] < 0) return fail(MOBROB_ERR_INVALID, "evaluate: negative quota");
+    maxq = std::max(maxq, (int)q[i]);
+  }
+  // ---- buffers (outside the arena: device_bytes / create_in_arena are unchanged) ----
+  const int Dp = e->Dp, Ap = e->Ap, A = e->A, D = e->D;
+  const int tw = 9 + D + A + kEvalTraceFlags;
+  const size_t n_tr = tracing ? (size_t)spec->trace_steps * spec->trace_robots * tw : 1;
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t b_out = al((size_t)N * 4 * 8), b_ep = al(std::max<size_t>((size_t)N * maxq * 3, 1) * 8), b_q = al((size_t)N * 4),
+               b_tr = al(n_tr * 4), b_st = al((size_t)N * kGoalStateFloats * 4), b_er = al((size_t)N * 8),
+               b_obs = al((size_t)cdiv(N, 256) * 256 * Dp * 4), b_mu = al((size_t)cdiv(N, 256) * 256 * Ap * 4);   // whole 256-row tiles
+  const size_t need = b_out + b_ep + b_q + b_tr + b_st + b_er + b_obs + b_mu;
+  if (need > e->eval_bytes) {
+    HIPC(hipStreamSynchronize(e->stream));
+    if (e->eval_buf) HIPC(hipFree(e->eval_buf));
+    e->eval_buf = nullptr;
+    e->eval_bytes = 0;
+    HIPC(hipMalloc(reinterpret_cast<void**>(&e->eval_buf), need));
+    e->eval_bytes = need;
+  }
+  char* cur = e->eval_buf;
+  auto take = [&](size_t b) { char* r = cur; cur += b; return r; };
+  EvalArgs a{};
+  a.robot_out = reinterpret_cast<double*>(take(b_out));
+  a.ep_out = reinterpret_cast<double*>(take(b_ep));
+  int* q_dev = reinterpret_cast<int*>(take(b_q));
+  float* tr_dev = reinterpret_cast<float*>(take(b_tr));
+  a.st = reinterpret_cast<float*>(take(b_st));
+  a.ep_ret = reinterpret_cast<double*>(take(b_er));
+  a.obs = reinterpret_cast<float*>(take(b_obs));
+  float* mu = reinterpret_cast<float*>(take(b_mu));
+  a.mu = mu;
+  a.quota = q_dev;
+  a.trace = tracing ? tr_dev : nullptr;
+  a.trace_robots = tracing ? spec->trace_robots : 0;
+  a.trace_steps = tracing ? spec->trace_steps : 0;
+  GoalEnvParams& g = a.p;
+  g.P = env->pos_dim; g.terminate_on_goal = env->terminate_on_goal != 0;
+  g.time_limit = env->time_limit > 0 ? env->time_limit : INT_MAX;   // control.py: no time limit
+  g.dt = env->dt; g.extent = env->extent; g.reach = env->reach_radius; g.bonus = env->goal_bonus;
+  g.extra_bonus = env->extra_bonus; g.noise = env->obs_noise;
+  for (int j = 0; j < 3; ++j)
+    for (int k = 0; k < 32; ++k) g.mix[j][k] = (j < env->pos_dim && k < A) ? env->mix[j][k] : 0.f;
+  a.N = N; a.D = D; a.Dp = Dp; a.A = A; a.Ap = Ap;
+  a.episodes = spec->episodes; a.deterministic = spec->deterministic != 0; a.maxq = maxq;
+  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
+  const uint64_t key = spec->seed ^ kEvalKeyMix;
+  a.k0 = (uint32_t)key; a.k1 = (uint32_t)(key >> 32);
+  a.log_std = Pp(e, T_LOGSTD);
+  HIPC(hipMemcpyAsync(q_dev, q.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  if (tracing) HIPC(hipMemsetAsync(tr_dev, 0, n_tr * 4, e->stream));
+  if (maxq > 0) HIPC(hipMemsetAsync(a.ep_out, 0, (size_t)N * maxq * 3 * 8, e->stream));
+  // a robot finishes an episode at least every time_limit steps: with a quota, the run is over after maxq * time_limit steps
+  int steps = spec->max_steps;
+  if (spec->episodes > 0) steps = (int)std::min<int64_t>(steps, (int64_t)maxq * env->time_limit);
+  const char* pe = getenv("MOBROB_EVAL_PERSISTENT");   // 0: the per-step path on every engine (A/B, tests); read per call
+  const bool persistent = e->fused.enabled && e->fused.H == 64 && !(pe && atoi(pe) == 0);
+  if (persistent) {
+    Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
+    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_eval64_goal<DPc>), dim3(cdiv(N, 16)), dim3(64), eval64_lds_bytes(Dp), e->stream, a, W, steps));
+    HIPC(hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(k_eval_goal_init, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, a);
+    for (int t = 0; t < steps; ++t) {
+      for (int s = 0; s < N; s += e->rows_max) {
+        const int c = std::min(e->rows_max, N - s);
+        forward(e, a.obs + (size_t)s * Dp, c, true, mu + (size_t)s * Ap, false, nullptr);
+      }
+      hipLaunchKernelGGL(k_eval_goal_step, dim3(cdiv(N, 256)), dim3(256), 256 * 33 * sizeof(float), e->stream, a, t);
+    }
+    HIPC(hipGetLastError());
+  }
+  HIPC(hipMemcpyAsync(robot_out, a.robot_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (episode_out && maxq > 0)
+    HIPC(hipMemcpyAsync(episode_out, a.ep_out, (size_t)N * maxq * 3 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (tracing) HIPC(hipMemcpyAsync(trace_out, tr_dev, n_tr * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return persistent ? 1 : 0;
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -1,0 +1,314 @@
+// Batched on-device policy evaluation of the goal environment (mobrob_ppo_evaluate_goal_env): SB3's evaluate_policy and the
+// protocol of the reference examples/control.py:36-46 for thousands of robots at once.
+//
+// The environment rules are the device functions of kernels_env.h, used unchanged (goal_advance, goal_reset, goal_features), so an
+// evaluated robot steps exactly like a training environment.  Randomness comes from streams of the evaluation's own (new stream
+// constants, keyed by the caller's seed; counter = (robot, component, step)): nothing here reads or advances a training counter.
+//
+//   k_eval_goal_init   fresh reset of every robot (control.py:37), first observation          (per-step path, one launch)
+//   k_eval_goal_step   clip / sample, env.step, reset, accounting, records, trace, next obs    (per-step path, one launch per step;
+//                      the actor mean comes from the engine's forward() into the evaluation's own buffers)
+//   k_eval64_goal<DP>  the whole evaluation in one launch for 2x64 tanh actors: one wave per 16-robot tile, the actor in LDS,
+//                      the forward on the f32 16x16x4 MFMA, the tile's state in registers / LDS through the step loop
+#pragma once
+#include "kernels_fused.h"
+#include "kernels_env.h"
+
+namespace mobrob {
+
+constexpr uint32_t kStreamEvalObs = 0x45564F31u;   // 'EVO1' observation noise
+constexpr uint32_t kStreamEvalAct = 0x45564131u;   // 'EVA1' action noise (deterministic = 0)
+constexpr uint64_t kEvalKeyMix = 0x9E6C63D0676A9A99ull;   // the reset stream's key (goal_reset's constant is the env's own)
+constexpr int kEvalTraceFlags = 4;                  // reward, reached, term, tr
+
+struct EvalArgs {
+  GoalEnvParams p;            // time_limit 0 (none) already mapped to INT_MAX
+  int N, D, Dp, A, Ap;
+  int episodes, deterministic, maxq;
+  float lo, hi;
+  uint32_t k0, k1;            // Philox key of the evaluation streams
+  const int* quota;           // [N] episodes to record (and, with episodes > 0, to finish before idling)
+  const float* log_std;       // [A] (deterministic = 0)
+  double* robot_out;          // [N][4] reward sum, steps run, episodes finished, goals reached
+  double* ep_out;             // [N][maxq][3] return, length, success
+  float* trace;               // [trace_steps][trace_robots][9 + D + A + 4] or null
+  int trace_robots, trace_steps;
+  // per-step path state
+  float* st;                  // [N][kGoalStateFloats]
+  double* ep_ret;             // [N] float64 return of the running episode
+  float* obs;                 // [N][Dp] observation the next step acts on
+  const float* mu;            // [N][Ap] actor mean of those observations
+};
+
+__device__ __forceinline__ int eval_trace_width(const EvalArgs& a) { return 9 + a.D + a.A + kEvalTraceFlags; }
+
+// observation chunk c (features 4c .. 4c + 3) of state g, seen before step `step`
+__device__ __forceinline__ f32x4 eval_features(const GoalState& g, const EvalArgs& a, int n, int c, uint32_t step) {
+  float z[4] = {0.f, 0.f, 0.f, 0.f};
+  if (a.p.noise != 0.f) box_muller4(philox4x32_10((uint32_t)n, (uint32_t)c, step, kStreamEvalObs, a.k0, a.k1), z);
+  return goal_features(g, a.p.P, a.D, c, z, a.p.noise);
+}
+
+__device__ __forceinline__ void eval_reset0(GoalState& g, const EvalArgs& a, int n) {
+  g = GoalState{};
+  goal_reset(g, a.p, false, (uint32_t)n, 0xFFFFFFFFu, a.k0, a.k1);
+}
+
+// action k of robot n at step t from the actor mean m: clip(mean), or clip(mean + exp(log_std) z) with z from the eval stream
+__device__ __forceinline__ void eval_actions(const EvalArgs& a, int n, int t, const float* m, float* act) {
+  for (int g4 = 0; 4 * g4 < a.A; ++g4) {
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!a.deterministic) box_muller4(philox4x32_10((uint32_t)n, (uint32_t)g4, (uint32_t)t, kStreamEvalAct, a.k0, a.k1), z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = 4 * g4 + j;
+      if (k < a.A) {
+        float v = m[k];
+        if (!a.deterministic) v = __fmaf_rn(expf(a.log_std[k]), z[j], v);
+        act[k] = fminf(fmaxf(v, a.lo), a.hi);
+      }
+    }
+  }
+}
+
+// per-robot accounting of one evaluation
+struct EvalRobot {
+  double ret_sum, ep_ret;
+  int steps, eps, goals, quota;
+};
+
+// one step of robot n at step t: trace (state before the step, observation, action), env.step, float64 accounting, episode
+// record, reset.  Returns whether the robot is still active afterwards.  obs_row: the D observation features it acted on.
+__device__ __forceinline__ bool eval_env_step(GoalState& g, EvalRobot& R, const EvalArgs& a, int n, int t, const float* act,
+                                              const float* obs_row) {
+  float* tr_row = nullptr;
+  if (a.trace && n < a.trace_robots && t < a.trace_steps) {
+    tr_row = a.trace + ((size_t)t * a.trace_robots + n) * eval_trace_width(a);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { tr_row[j] = g.pos[j]; tr_row[3 + j] = g.vel[j]; tr_row[6 + j] = g.goal[j]; }
+    for (int f = 0; f < a.D; ++f) tr_row[9 + f] = obs_row[f];
+    for (int k = 0; k < a.A; ++k) tr_row[9 + a.D + k] = act[k];
+  }
+  const GoalOutcome o = goal_advance(g, a.p, act, a.A);
+  R.steps += 1;
+  R.ret_sum += (double)o.reward;
+  R.ep_ret += (double)o.reward;
+  if (o.reached) R.goals += 1;
+  if (tr_row) {
+    float* f = tr_row + 9 + a.D + a.A;
+    f[0] = o.reward; f[1] = o.reached ? 1.f : 0.f; f[2] = o.term ? 1.f : 0.f; f[3] = o.tr ? 1.f : 0.f;
+  }
+  if (o.done) {
+    if (R.eps < R.quota) {
+      double* r = a.ep_out + ((size_t)n * a.maxq + R.eps) * 3;
+      r[0] = R.ep_ret; r[1] = (double)g.ep_len; r[2] = o.reached ? 1.0 : 0.0;
+    }
+    R.eps += 1;
+    R.ep_ret = 0.0;
+    goal_reset(g, a.p, o.reached, (uint32_t)n, (uint32_t)t, a.k0, a.k1);
+  }
+  return a.episodes == 0 || R.eps < R.quota;
+}
+
+__device__ __forceinline__ void eval_robot_out(const EvalArgs& a, int n, const EvalRobot& R) {
+  double* o = a.robot_out + (size_t)n * 4;
+  o[0] = R.ret_sum; o[1] = (double)R.steps; o[2] = (double)R.eps; o[3] = (double)R.goals;
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-step path
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_eval_goal_init(EvalArgs a) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= a.N) return;
+  GoalState g;
+  eval_reset0(g, a, n);
+  goal_store(a.st + (size_t)n * kGoalStateFloats, g);
+  a.ep_ret[n] = 0.0;
+  eval_robot_out(a, n, EvalRobot{0.0, 0.0, 0, 0, 0, 0});
+  for (int c = 0; c < a.Dp / 4; ++c) reinterpret_cast<f32x4*>(a.obs)[(size_t)n * (a.Dp / 4) + c] = eval_features(g, a, n, c, 0u);
+}
+
+__global__ __launch_bounds__(256) void k_eval_goal_step(EvalArgs a, int t) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= a.N) return;
+  double* o = a.robot_out + (size_t)n * 4;
+  EvalRobot R{o[0], a.ep_ret[n], (int)o[1], (int)o[2], (int)o[3], a.quota[n]};
+  if (a.episodes > 0 && R.eps >= R.quota) return;   // idle: quota met
+  GoalState g = goal_load(a.st + (size_t)n * kGoalStateFloats);
+  float* act = &lds[threadIdx.x * 33];   // [256][33]: the thread's clipped actions (LDS, not a dynamically indexed register array)
+  eval_actions(a, n, t, a.mu + (size_t)n * a.Ap, act);
+  (void)eval_env_step(g, R, a, n, t, act, a.obs + (size_t)n * a.Dp);
+  goal_store(a.st + (size_t)n * kGoalStateFloats, g);
+  a.ep_ret[n] = R.ep_ret;
+  eval_robot_out(a, n, R);
+  for (int c = 0; c < a.Dp / 4; ++c)
+    reinterpret_cast<f32x4*>(a.obs)[(size_t)n * (a.Dp / 4) + c] = eval_features(g, a, n, c, (uint32_t)t + 1u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_eval64_goal<DP>: the persistent path for 2x64 tanh actors (every reference config).
+//
+// One workgroup = ONE wave = one tile of 16 robots, so every barrier of the step loop is a single-wave s_barrier and the exit test
+// (a ballot of the tile's active robots) is uniform across the workgroup.  The actor (~40 KB at DP = 64) is copied from the flat
+// parameter vector into LDS once, in the B-fragment order of v_mfma_f32_16x16x4_f32 (lane l of k-step s holds W[col + (l & 15)]
+// [4 s + (l >> 4)]: one conflict-free ds_read_b32 per MFMA).  Per step: observation tile -> LDS (goal_features), layer 1 (DP / 4
+// k-steps x 4 independent 16-column accumulators), layer 2 (16 x 4), head (16 x 1 or 2), each a chain of 40-cycle dependent MFMAs
+// with 4 (2) chains in flight; the env phase (clip / sample, goal_advance, goal_reset, float64 accounting, records) runs on the
+// tile's 16 lanes, the robots' GoalState and accumulators stay in those lanes' registers for the whole launch.
+// ------------------------------------------------------------------------------------------------
+struct Eval64Net {
+  const float *W1, *b1, *W2, *b2, *W3, *b3;   // canonical SB3 tensors (pi.0, pi.2, action_net), row-major [out][in]
+};
+template <int DP>
+struct LayEval64 {
+  static constexpr int KS1 = DP / 4, LDX = DP + 4, LDH = 68, LDM = 36;
+  static constexpr int W1 = 0;                    // [4 col blocks][KS1][64 lanes]
+  static constexpr int W2 = W1 + 4 * KS1 * 64;    // [4][16][64]
+  static constexpr int W3 = W2 + 4 * 16 * 64;     // [2][16][64]
+  static constexpr int B1 = W3 + 2 * 16 * 64;     // [64]
+  static constexpr int B2 = B1 + 64;              // [64]
+  static constexpr int B3 = B2 + 64;              // [32]
+  static constexpr int X = B3 + 32;               // [16][LDX]
+  static constexpr int H1 = X + 16 * LDX;         // [16][LDH]
+  static constexpr int H2 = H1 + 16 * LDH;        // [16][LDH]
+  static constexpr int MU = H2 + 16 * LDH;        // [16][LDM]
+  static constexpr int ST = MU + 16 * LDM;        // [16][12] robot state for the observation phase
+  static constexpr int END = ST + 16 * 12;
+};
+inline size_t eval64_lds_bytes(int Dp) {
+  switch (Dp) {
+    case 16: return LayEval64<16>::END * sizeof(float);
+    case 32: return LayEval64<32>::END * sizeof(float);
+    case 48: return LayEval64<48>::END * sizeof(float);
+    default: return LayEval64<64>::END * sizeof(float);
+  }
+}
+
+__device__ __forceinline__ void eval64_state_lds(float* s, const GoalState& g) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { s[j] = g.pos[j]; s[3 + j] = g.vel[j]; s[6 + j] = g.goal[j]; }
+}
+
+template <int DP>
+__global__ __launch_bounds__(64) void k_eval64_goal(EvalArgs a, Eval64Net W, int max_steps) {
+  using L = LayEval64<DP>;
+  constexpr int KS1 = L::KS1, per = DP / 4;
+  const int lane = threadIdx.x;
+  const int r16 = lane & 15, q = lane >> 4;
+  const int row0 = blockIdx.x * 16;
+  const int D = a.D, A = a.A;
+  // ---- the actor -> LDS in fragment order (zero beyond D / A) ----
+  for (int i = lane; i < 4 * KS1 * 64; i += 64) {
+    const int l = i & 63, ks = (i >> 6) % KS1, cb = (i >> 6) / KS1;
+    const int k = 4 * ks + (l >> 4);
+    lds[L::W1 + i] = k < D ? W.W1[(size_t)(16 * cb + (l & 15)) * D + k] : 0.f;
+  }
+  for (int i = lane; i < 4 * 16 * 64; i += 64) {
+    const int l = i & 63, ks = (i >> 6) & 15, cb = i >> 10;
+    lds[L::W2 + i] = W.W2[(16 * cb + (l & 15)) * 64 + 4 * ks + (l >> 4)];
+  }
+  for (int i = lane; i < 2 * 16 * 64; i += 64) {
+    const int l = i & 63, ks = (i >> 6) & 15, nb = i >> 10;
+    const int col = 16 * nb + (l & 15);
+    lds[L::W3 + i] = col < A ? W.W3[col * 64 + 4 * ks + (l >> 4)] : 0.f;
+  }
+  lds[L::B1 + lane] = W.b1[lane];
+  lds[L::B2 + lane] = W.b2[lane];
+  if (lane < 32) lds[L::B3 + lane] = lane < A ? W.b3[lane] : 0.f;
+  for (int i = lane; i < 16 * L::LDX; i += 64) lds[L::X + i] = 0.f;
+  // ---- fresh reset of the tile's robots (lanes 0..15 own robot row0 + lane) ----
+  const int n = row0 + r16;
+  const bool mine = lane < 16 && n < a.N;
+  GoalState g{};
+  EvalRobot R{0.0, 0.0, 0, 0, 0, 0};
+  bool active = false;
+  if (mine) {
+    eval_reset0(g, a, n);
+    R.quota = a.quota[n];
+    active = a.episodes == 0 || R.quota > 0;
+    eval64_state_lds(&lds[L::ST + 12 * r16], g);
+  }
+  __syncthreads();
+  const bool wide_head = A > 16;
+  for (int t = 0; t < max_steps; ++t) {
+    if (__ballot(active) == 0ull) break;   // one wave per workgroup: uniform
+    // ---- observation tile: lane (r16, q) builds chunks q, q + 4, ... of robot r16 ----
+    if (row0 + r16 < a.N) {
+      GoalState gs{};
+      const float* s = &lds[L::ST + 12 * r16];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { gs.pos[j] = s[j]; gs.vel[j] = s[3 + j]; gs.goal[j] = s[6 + j]; }
+      for (int c = q; c < per; c += 4)
+        *reinterpret_cast<f32x4*>(&lds[L::X + r16 * L::LDX + 4 * c]) = eval_features(gs, a, row0 + r16, c, (uint32_t)t);
+    }
+    __syncthreads();
+    // ---- layer 1: h1 = tanh(W1 x + b1), four 16-column accumulators ----
+    {
+      f32x4 c[4];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) { const float b = lds[L::B1 + 16 * cb + r16]; c[cb] = f32x4{b, b, b, b}; }
+#pragma unroll
+      for (int ks = 0; ks < KS1; ++ks) {
+        const float x = lds[L::X + r16 * L::LDX + 4 * ks + q];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) c[cb] = MFMA16(x, lds[L::W1 + (cb * KS1 + ks) * 64 + lane], c[cb]);
+      }
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lds[L::H1 + (4 * q + i) * L::LDH + 16 * cb + r16] = fast_tanh(c[cb][i]);
+    }
+    __syncthreads();
+    // ---- layer 2 ----
+    {
+      f32x4 c[4];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) { const float b = lds[L::B2 + 16 * cb + r16]; c[cb] = f32x4{b, b, b, b}; }
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) {
+        const float x = lds[L::H1 + r16 * L::LDH + 4 * ks + q];
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) c[cb] = MFMA16(x, lds[L::W2 + (cb * 16 + ks) * 64 + lane], c[cb]);
+      }
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lds[L::H2 + (4 * q + i) * L::LDH + 16 * cb + r16] = fast_tanh(c[cb][i]);
+    }
+    __syncthreads();
+    // ---- head: mean = W3 h2 + b3 (one or two 16-column blocks) ----
+    {
+      const float b0 = lds[L::B3 + r16], b1 = lds[L::B3 + 16 + r16];
+      f32x4 c0 = f32x4{b0, b0, b0, b0}, c1 = f32x4{b1, b1, b1, b1};
+      if (wide_head) {
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {
+          const float x = lds[L::H2 + r16 * L::LDH + 4 * ks + q];
+          c0 = MFMA16(x, lds[L::W3 + ks * 64 + lane], c0);
+          c1 = MFMA16(x, lds[L::W3 + (16 + ks) * 64 + lane], c1);
+        }
+      } else {
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) c0 = MFMA16(lds[L::H2 + r16 * L::LDH + 4 * ks + q], lds[L::W3 + ks * 64 + lane], c0);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        lds[L::MU + (4 * q + i) * L::LDM + r16] = c0[i];
+        lds[L::MU + (4 * q + i) * L::LDM + 16 + r16] = c1[i];
+      }
+    }
+    __syncthreads();
+    // ---- env phase: the tile's 16 lanes ----
+    if (mine && active) {
+      float* act = &lds[L::MU + r16 * L::LDM];   // the mean row becomes the applied action in place
+      eval_actions(a, n, t, act, act);
+      active = eval_env_step(g, R, a, n, t, act, &lds[L::X + r16 * L::LDX]);
+      eval64_state_lds(&lds[L::ST + 12 * r16], g);
+    }
+    __syncthreads();
+  }
+  if (mine) eval_robot_out(a, n, R);
+}
+
+}  // namespace mobrob

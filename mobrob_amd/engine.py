@@ -7,7 +7,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from ._lib import BUF, Config, DroneParams, EpisodeStats, GoalEnv, TrainStats, check
+from ._lib import BUF, Config, DroneParams, EpisodeStats, EvalSpec, GoalEnv, TrainStats, check
 
 F32 = np.float32
 STAT_KEYS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
@@ -334,6 +334,64 @@ class PPOEngine:
             for k in range(mix.shape[1]):
                 g.mix[j][k] = float(mix[j, k])
         check(self.lib.mobrob_ppo_collect_goal_env(self._h, C.byref(g)))
+
+    def _goal_env_struct(self, pos_dim, mix, time_limit, terminate_on_goal, dt, extent, reach_radius, goal_bonus, extra_bonus,
+                         obs_noise):
+        g = GoalEnv()
+        g.pos_dim, g.terminate_on_goal, g.time_limit = int(pos_dim), int(bool(terminate_on_goal)), int(time_limit)
+        g.dt, g.extent, g.reach_radius = float(dt), float(extent), float(reach_radius)
+        g.goal_bonus, g.extra_bonus, g.obs_noise = float(goal_bonus), float(extra_bonus), float(obs_noise)
+        mix = np.asarray(mix, F32)
+        if mix.shape != (int(pos_dim), self.A):
+            raise ValueError(f"mix must be [{int(pos_dim)}, {self.A}], got {mix.shape}")
+        for j in range(mix.shape[0]):
+            for k in range(mix.shape[1]):
+                g.mix[j][k] = float(mix[j, k])
+        return g
+
+    def evaluate_goal_env(self, pos_dim, mix, time_limit=0, terminate_on_goal=True, dt=0.05, extent=3.0, reach_radius=0.3,
+                          goal_bonus=5.0, extra_bonus=0.0, obs_noise=0.1, *, n_robots, max_steps=1000, episodes=0, quota=None,
+                          deterministic=True, seed=0, trace=None):
+        """The current policy on `n_robots` fresh robots of the device goal environment (mobrob_ppo_evaluate_goal_env).
+        time_limit 0: no limit (examples/control.py).  episodes > 0: SB3 evaluate_policy's quota of finished episodes, split
+        (episodes + i) // n_robots unless `quota` ([n_robots] ints) is given.  trace = (robots, steps): teacher-forcing trace.
+        Returns a dict of NumPy arrays: reward_sum, steps, episodes, goals ([n_robots]); episode_returns, episode_lengths,
+        episode_success ([n_robots][max quota], NaN past an unfinished quota); trace ([steps][robots][9 + D + A + 4]) and
+        `persistent` (which kernel path ran)."""
+        n = int(n_robots)
+        if self.use_sde and not deterministic:
+            raise ValueError("evaluate_goal_env: stochastic actions of a use_sde (gSDE) policy are not supported; use deterministic=True")
+        g = self._goal_env_struct(pos_dim, mix, time_limit, terminate_on_goal, dt, extent, reach_radius, goal_bonus, extra_bonus,
+                                  obs_noise)
+        sp = EvalSpec()
+        sp.n_robots, sp.max_steps, sp.episodes, sp.deterministic = n, int(max_steps), int(episodes), int(bool(deterministic))
+        sp.seed = int(seed) & (2 ** 64 - 1)
+        tr_r, tr_s = (0, 0) if trace is None else (int(trace[0]), int(trace[1]))
+        sp.trace_robots, sp.trace_steps = tr_r, tr_s
+        if quota is not None:
+            q = np.ascontiguousarray(quota, dtype=np.int32)
+            if q.shape != (max(n, 0),):
+                raise ValueError(f"quota must have shape ({n},), got {q.shape}")
+        elif int(episodes) > 0 and n > 0:
+            q = ((int(episodes) + np.arange(n)) // n).astype(np.int32)
+        else:
+            q = np.zeros(max(n, 0), np.int32)
+        maxq = int(q.max()) if q.size else 0
+        robot = np.zeros((max(n, 1), 4), np.float64)
+        ep = np.zeros((max(n, 1), max(maxq, 1), 3), np.float64)
+        tr = np.zeros((max(tr_s, 1), max(tr_r, 1), 9 + self.D + self.A + 4), F32) if trace is not None else None
+        dp = C.POINTER(C.c_double)
+        r = check(self.lib.mobrob_ppo_evaluate_goal_env(self._h, C.byref(g), C.byref(sp), q.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         robot.ctypes.data_as(dp), ep.ctypes.data_as(dp), _fp(tr)))
+        ep = ep[:, :maxq]
+        done = np.arange(maxq)[None, :] < np.minimum(robot[:, 2:3], q[:, None])
+        out = {"reward_sum": robot[:, 0], "steps": robot[:, 1].astype(np.int64), "episodes": robot[:, 2].astype(np.int64),
+               "goals": robot[:, 3].astype(np.int64), "quota": q,
+               "episode_returns": np.where(done, ep[:, :, 0], np.nan), "episode_lengths": np.where(done, ep[:, :, 1], np.nan),
+               "episode_success": np.where(done, ep[:, :, 2], np.nan), "persistent": bool(r == 1)}
+        if tr is not None:
+            out["trace"] = tr
+        return out
 
     def episode_stats(self, reset=True):
         """Episodes finished by the goal environment since the counters were last reset."""

@@ -200,6 +200,23 @@ class DeviceGoalVecEnv(VecEnvBase):
         engine.collect_goal_env(self.pos_dim, self.mix, self.time_limit, self.terminate_on_goal, dt=self.dt,
                                 extent=self.extent, extra_bonus=self.extra_bonus)
 
+    def evaluate(self, engine, n_robots=None, max_steps=None, episodes=0, quota=None, deterministic=True, seed=None,
+                 trace=None):
+        """The engine's current policy on fresh robots of this task (PPOEngine.evaluate_goal_env with this env's mix, dt,
+        extent, extra_bonus and time_limit).  n_robots defaults to num_envs; with a quota (`episodes` > 0 or `quota`)
+        max_steps defaults to the bound max quota x time_limit, else to time_limit; seed defaults to the env's seed."""
+        n = self.num_envs if n_robots is None else int(n_robots)
+        if max_steps is None:
+            if quota is not None or episodes > 0:
+                q = np.asarray(quota) if quota is not None else (int(episodes) + np.arange(n)) // n
+                max_steps = max(int(q.max()) if q.size else 1, 1) * max(self.time_limit, 1)
+            else:
+                max_steps = self.time_limit
+        return engine.evaluate_goal_env(self.pos_dim, self.mix, self.time_limit, self.terminate_on_goal, dt=self.dt,
+                                        extent=self.extent, extra_bonus=self.extra_bonus, n_robots=n, max_steps=int(max_steps),
+                                        episodes=episodes, quota=quota, deterministic=deterministic,
+                                        seed=(self._seed or 0) if seed is None else seed, trace=trace)
+
     def seed(self, seed=None):
         self._seed = seed
 

@@ -90,6 +90,106 @@ class CheckpointCallback(BaseCallback):
         return True
 
 
+class EvalCallback(BaseCallback):
+    """SB3 2.0's EvalCallback: every `eval_freq` calls of on_step, `n_eval_episodes` episodes of the current policy on
+    `eval_env` (evaluation.evaluate_episodes: one device launch for a DeviceGoalVecEnv, SB3's host loop otherwise).
+    `<log_path>/evaluations.npz` holds timesteps, results, ep_lengths (and successes when the env reports them);
+    `<best_model_save_path>/best_model.zip` is the policy of the best mean reward so far; eval/mean_reward,
+    eval/mean_ep_length and eval/success_rate go into the next log dump.  The device rollout replays its on_step calls after
+    the launch, so an evaluation runs between collect and train: the parameters SB3 evaluates at that step."""
+
+    def __init__(self, eval_env, callback_on_new_best=None, callback_after_eval=None, n_eval_episodes: int = 5,
+                 eval_freq: int = 10000, log_path=None, best_model_save_path=None, deterministic: bool = True,
+                 render: bool = False, verbose: int = 1, warn: bool = True):
+        super().__init__(verbose)
+        self.eval_env, self.n_eval_episodes, self.eval_freq = eval_env, int(n_eval_episodes), int(eval_freq)
+        self.callback_on_new_best, self.callback = callback_on_new_best, callback_after_eval
+        for c in (callback_on_new_best, callback_after_eval):
+            if c is not None:
+                c.parent = self
+        self.deterministic, self.render, self.warn = deterministic, render, warn
+        self.best_mean_reward, self.last_mean_reward = -np.inf, -np.inf
+        self.best_model_save_path = best_model_save_path
+        self.log_path = os.path.join(log_path, "evaluations") if log_path is not None else None
+        self.evaluations_results, self.evaluations_timesteps, self.evaluations_length = [], [], []
+        self.evaluations_successes = []
+        self.evaluate_fn = None   # (model, env, n_episodes, deterministic) -> (returns, lengths, successes); None: evaluate_episodes
+
+    def init_callback(self, model):
+        if getattr(model, "world_size", 1) > 1:
+            raise ValueError("EvalCallback: data-parallel training (world_size > 1) is not supported -- evaluate on one rank "
+                             "after learn() instead")
+        super().init_callback(model)
+        if self.best_model_save_path is not None:
+            os.makedirs(self.best_model_save_path, exist_ok=True)
+        if self.log_path is not None:
+            os.makedirs(os.path.dirname(self.log_path), exist_ok=True)
+        for c in (self.callback_on_new_best, self.callback):
+            if c is not None:
+                c.init_callback(model)
+
+    def _evaluate(self):
+        if self.evaluate_fn is not None:
+            return self.evaluate_fn(self.model, self.eval_env, self.n_eval_episodes, self.deterministic)
+        from ..evaluation import evaluate_episodes
+        return evaluate_episodes(self.model, self.eval_env, self.n_eval_episodes, self.deterministic, render=self.render)
+
+    def _on_step(self) -> bool:
+        go_on = True
+        if self.eval_freq > 0 and self.n_calls % self.eval_freq == 0:
+            rewards, lengths, successes = self._evaluate()
+            if self.log_path is not None:
+                self.evaluations_timesteps.append(self.num_timesteps)
+                self.evaluations_results.append(list(rewards))
+                self.evaluations_length.append(list(lengths))
+                kw = {}
+                if len(successes) > 0:
+                    self.evaluations_successes.append(list(successes))
+                    kw = dict(successes=self.evaluations_successes)
+                np.savez(self.log_path, timesteps=self.evaluations_timesteps, results=self.evaluations_results,
+                         ep_lengths=self.evaluations_length, **kw)
+            mean_reward, std_reward = float(np.mean(rewards)), float(np.std(rewards))
+            mean_len, std_len = float(np.mean(lengths)), float(np.std(lengths))
+            self.last_mean_reward = mean_reward
+            if self.verbose >= 1:
+                print(f"Eval num_timesteps={self.num_timesteps}, episode_reward={mean_reward:.2f} +/- {std_reward:.2f}")
+                print(f"Episode length: {mean_len:.2f} +/- {std_len:.2f}")
+            self.model._record("eval/mean_reward", mean_reward)
+            self.model._record("eval/mean_ep_length", mean_len)
+            if len(successes) > 0:
+                rate = float(np.mean(successes))
+                if self.verbose >= 1:
+                    print(f"Success rate: {100 * rate:.2f}%")
+                self.model._record("eval/success_rate", rate)
+            if mean_reward > self.best_mean_reward:
+                if self.verbose >= 1:
+                    print("New best mean reward!")
+                if self.best_model_save_path is not None:
+                    self.model.save(os.path.join(self.best_model_save_path, "best_model"))
+                self.best_mean_reward = mean_reward
+                if self.callback_on_new_best is not None:
+                    go_on = self.callback_on_new_best.on_step()
+            if self.callback is not None:
+                go_on = self.callback.on_step() and go_on
+        return go_on
+
+
+class StopTrainingOnRewardThreshold(BaseCallback):
+    """SB3's callback_on_new_best that stops learn() once the parent EvalCallback's best mean reward reaches the threshold."""
+
+    def __init__(self, reward_threshold: float, verbose: int = 0):
+        super().__init__(verbose)
+        self.reward_threshold, self.parent = float(reward_threshold), None
+
+    def _on_step(self) -> bool:
+        assert self.parent is not None, "StopTrainingOnRewardThreshold must be used with an EvalCallback"
+        go_on = bool(self.parent.best_mean_reward < self.reward_threshold)
+        if self.verbose >= 1 and not go_on:
+            print(f"Stopping training because the mean reward {self.parent.best_mean_reward:.2f} "
+                  f"is above the threshold {self.reward_threshold}")
+        return go_on
+
+
 class _CallbackList(BaseCallback):
     def __init__(self, cbs):
         super().__init__()
@@ -469,6 +569,7 @@ class PPO:
         return stats
 
     _tb = None   # event-file writer of the learn() call in progress (tensorboard_log)
+    _records = OrderedDict()   # scalars callbacks recorded for the next log dump (replaced, never mutated, at class level)
 
     def learn(self, total_timesteps, callback=None, log_interval=1, tb_log_name="PPO", reset_num_timesteps=True,
               progress_bar=False):
@@ -567,6 +668,8 @@ class PPO:
                  ("train/value_loss", stats["value_loss"])]
         if self.clip_range_vf is not None and not callable(self.clip_range_vf):
             rows.append(("train/clip_range_vf", float(self.clip_range_vf)))
+        rows += list(self._records.items())   # what callbacks recorded since the last dump (EvalCallback's eval/*)
+        self._records = OrderedDict()
         if self._tb is not None:   # SB3 keeps these three out of the event file (logger.record(..., exclude="tensorboard"))
             skip = ("time/iterations", "time/time_elapsed", "time/total_timesteps")
             self._tb.add_scalars([(k, v) for k, v in rows if k not in skip], self.num_timesteps)
@@ -578,6 +681,12 @@ class PPO:
         for k, v in rows:
             print(f"| {k:<{w}} | {v:<13.6g} |" if isinstance(v, float) else f"| {k:<{w}} | {v:<13} |")
         print("-" * (w + 20), flush=True)
+
+    def _record(self, key, value):
+        """SB3 logger.record: a scalar for the next log dump (stdout table and event file)."""
+        if "_records" not in self.__dict__:
+            self._records = OrderedDict()
+        self._records[key] = value
 
     # ---------------------------------------------------------------------------------------------
     def _hyper(self):
