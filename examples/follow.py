@@ -1,0 +1,55 @@
+#!/usr/bin/env python3
+"""Drive a trained goal-conditioned policy along a planner's waypoints and report whether, and when, the robots get there.
+
+    python examples/follow.py --env-name point --policy-name ppo --waypoints path.npy --robots 4096
+
+`--waypoints FILE.npy` holds `[K][P]` positions (the same path for every robot) or `[n][K][P]` (one path per robot, n = --robots).
+Each robot starts at rest at a position drawn from the environment's start region (`--seed`) and follows its waypoints in
+order: a waypoint counts as reached after the step that ends inside the reach radius, and the next one becomes the goal
+(mobrob_amd.waypoints).  The checkpoint is loaded as examples/control.py loads it (data/policies/<env>-<policy>.zip).
+
+By default all robots run in ONE device call (DeviceGoalVecEnv, the kinematic stand-in stepped by the engine); `--host` runs
+the same semantics as a Python loop over `get_env(...)` with one `predict` per robot and step.  Three report lines: the success
+rate (all waypoints reached), the mean number of waypoints reached, and the mean arrival step of the last waypoint over the
+robots that reached it (nan if none did).
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None):
+    from mobrob_amd import load_policy
+    from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
+    from mobrob_amd.envs.wrapper import ROBOT_DIMS, KinematicSim
+    from mobrob_amd.waypoints import follow_waypoints
+    policy = load_policy(env_name, policy_name) if policy is None else policy
+    d, a, p = ROBOT_DIMS[env_name]
+    extent = KinematicSim(d, a, p).extent
+    start = np.random.default_rng(seed).uniform(-extent / 2, extent / 2, (int(robots), p))   # the env's init_space
+    env = env_name if host else DeviceGoalVecEnv.for_robot(env_name, int(robots), time_limit=0, seed=seed)
+    r = follow_waypoints(policy, env, start, waypoints, max_steps=max_steps, deterministic=True, seed=seed)
+    K = r["arrival"].shape[1]
+    done = r["reached"] == K
+    last = r["arrival"][done, K - 1]
+    print(f"success rate: {float(np.mean(done))}")
+    print(f"mean waypoints reached: {float(np.mean(r['reached']))}")
+    print(f"mean arrival step of the last waypoint: {float(np.mean(last)) if last.size else float('nan')}")
+    return r
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env-name", type=str, default="point")
+    ap.add_argument("--policy-name", type=str, default="ppo")
+    ap.add_argument("--waypoints", type=str, required=True, help="[K][P] or [n][K][P] positions (.npy)")
+    ap.add_argument("--robots", type=int, default=1)
+    ap.add_argument("--max-steps", type=int, default=1000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--host", action="store_true", default=False, help="the Python loop over get_env instead of one device call")
+    args = ap.parse_args()
+    follow(args.env_name, args.policy_name, np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed)

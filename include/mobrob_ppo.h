@@ -466,6 +466,45 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
                                  const int32_t* quota /* [n_robots] or NULL */, double* robot_out /* [n_robots][4] */,
                                  double* episode_out /* [n_robots][max quota][3] or NULL */, float* trace_out /* or NULL */);
 
+/* ---- waypoint following: the trained policy as a low-level tracker of given goal sequences (planner waypoints) ------------
+ * n_robots independent robots of the goal environment above, driven by the CURRENT policy along goals given by the caller instead
+ * of goals drawn from the RNG.  Per robot i (the host loop of mobrob_amd/waypoints.py states the same thing on EnvWrapper):
+ *   start     at rest on start[i], goal waypoints[i][0] (EnvWrapper.reset(init_pos=start); set_goal(wp[0])).
+ *   stepping  action, then the env step of mobrob_ppo_collect_goal_env with NO time limit and NO reset (env->time_limit and
+ *             env->terminate_on_goal play no part).  After the step, if the robot is inside the reach radius (tested once per
+ *             step, after the step: a robot starting inside the radius of wp[0] counts after its first step), arrival[i][k] =
+ *             t + 1 and waypoint k + 1 becomes the goal (pose and velocity kept; progress is measured against the goal in force).
+ *             At most one waypoint advances per step.  After its last waypoint the robot has finished and idles.
+ *   n_waypoints [n_robots] counts (0 .. max_waypoints), or NULL = max_waypoints each.  A robot with 0 waypoints runs no step.
+ *             Waypoints outside the arena's +-extent are allowed (unreachable); non-finite starts or waypoints are refused.
+ *   arrival   [n_robots][max_waypoints] int32: arrival step (1-based) of each waypoint, -1 = not reached.
+ *   robot_out [n_robots][4] doubles: reward sum (float64, reach bonus included), steps run, waypoints reached, final distance to
+ *             the waypoint in force (NaN for a robot without waypoints).
+ *   path_out  [max_steps / path_stride + 1][n_robots][pos_dim] floats, or NULL (path_stride 0: none): record r is the position
+ *             after r * path_stride steps (record 0 = start); a robot that has finished repeats its last position.
+ *   trace_out as mobrob_ppo_evaluate_goal_env's, the four flags being: reward, reached, index of the waypoint in force before
+ *             the step, finished after the step.  Rows of robots that have finished are zero.
+ *   actions, streams, ordering, buffers and kernels: as mobrob_ppo_evaluate_goal_env (the evaluation's Philox streams keyed by
+ *             seed; nothing of the training state is read or advanced).  2x64 tanh engines of the fused family: ONE persistent
+ *             launch (k_follow64_goal); every other engine: forward plus one kernel per step.  MOBROB_EVAL_PERSISTENT=0 forces
+ *             the per-step path.
+ * MOBROB_ERR_INVALID before any launch for: a count outside 0 .. max_waypoints, max_waypoints < 1, a pos_dim / act_dim that
+ * evaluate refuses, max_steps < 1, path_stride < 0, a trace larger than the run, stochastic actions of a use_sde engine, non-finite
+ * starts or (used) waypoints.  Returns 1 when the persistent kernel ran, 0 for the per-step path, or a negative error. */
+typedef struct mobrob_follow_spec {
+  int32_t n_robots;        /* >= 1                                                                            */
+  int32_t max_waypoints;   /* K >= 1: the row stride of waypoints / arrival                                   */
+  int32_t max_steps;       /* steps per robot at most                                                         */
+  int32_t deterministic;   /* 1: clip(mean); 0: mean + exp(log_std) * N(0,1), clipped (refused for use_sde)      */
+  uint64_t seed;           /* Philox key of the evaluation streams                                            */
+  int32_t path_stride;     /* 0: no path; > 0: a path record every path_stride steps                          */
+  int32_t trace_robots, trace_steps;   /* optional teacher-forcing trace of the first robots / steps (tests)    */
+} mobrob_follow_spec_t;
+int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                const float* start /* [n][pos_dim] */, const float* waypoints /* [n][K][pos_dim] */,
+                                const int32_t* n_waypoints /* [n] or NULL = K */, int32_t* arrival /* [n][K], -1 = not reached */,
+                                double* robot_out /* [n][4] */, float* path_out /* or NULL */, float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

@@ -66,6 +66,11 @@ class EvalSpec(C.Structure):  # mobrob_eval_spec_t
                 ("seed", C.c_uint64), ("trace_robots", C.c_int32), ("trace_steps", C.c_int32)]
 
 
+class FollowSpec(C.Structure):  # mobrob_follow_spec_t
+    _fields_ = [("n_robots", C.c_int32), ("max_waypoints", C.c_int32), ("max_steps", C.c_int32), ("deterministic", C.c_int32),
+                ("seed", C.c_uint64), ("path_stride", C.c_int32), ("trace_robots", C.c_int32), ("trace_steps", C.c_int32)]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -127,6 +132,8 @@ SYMBOLS = {
     "mobrob_ppo_predict": (C.c_int, [_P, _F, C.c_int32, C.c_int32, _F, _F, _F]),
     "mobrob_ppo_evaluate_goal_env": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(EvalSpec), C.POINTER(C.c_int32),
                                                C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
+    "mobrob_ppo_follow_waypoints": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), _F, _F, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_double), _F, _F]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

@@ -50,6 +50,7 @@ inline void poison_lds(hipStream_t st) {
 #include "fused_dispatch.h"
 #include "kernels_env.h"
 #include "kernels_eval.h"
+#include "kernels_follow.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -3216,6 +3217,29 @@ int mobrob_ppo_predict(mobrob_ppo_engine_t* e, const float* obs, int32_t n, int3
 }
 
 // ---- policy evaluation: evaluate_policy / examples/control.py on the device ---------------------------------------------
+// the evaluation's device buffer (evaluate and follow_waypoints): grown to `need` bytes, outside the arena, freed by destroy
+static int grow_eval_buf(mobrob_ppo_engine_t* e, size_t need) {
+  if (need > e->eval_bytes) {
+    HIPC(hipStreamSynchronize(e->stream));
+    if (e->eval_buf) HIPC(hipFree(e->eval_buf));
+    e->eval_buf = nullptr;
+    e->eval_bytes = 0;
+    HIPC(hipMalloc(reinterpret_cast<void**>(&e->eval_buf), need));
+    e->eval_bytes = need;
+  }
+  return MOBROB_OK;
+}
+
+static GoalEnvParams eval_env_params(const mobrob_goal_env_t* env, int A, bool terminate_on_goal, int time_limit) {
+  GoalEnvParams g{};
+  g.P = env->pos_dim; g.terminate_on_goal = terminate_on_goal; g.time_limit = time_limit;
+  g.dt = env->dt; g.extent = env->extent; g.reach = env->reach_radius; g.bonus = env->goal_bonus;
+  g.extra_bonus = env->extra_bonus; g.noise = env->obs_noise;
+  for (int j = 0; j < 3; ++j)
+    for (int k = 0; k < 32; ++k) g.mix[j][k] = (j < env->pos_dim && k < A) ? env->mix[j][k] : 0.f;
+  return g;
+}
+
 int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
                                  const int32_t* quota, double* robot_out, double* episode_out, float* trace_out) {
   if (!e || !env || !spec || !robot_out) return fail(MOBROB_ERR_INVALID, "evaluate: null argument");
@@ -3250,14 +3274,7 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
                b_tr = al(n_tr * 4), b_st = al((size_t)N * kGoalStateFloats * 4), b_er = al((size_t)N * 8),
                b_obs = al((size_t)cdiv(N, 256) * 256 * Dp * 4), b_mu = al((size_t)cdiv(N, 256) * 256 * Ap * 4);   // whole 256-row tiles
   const size_t need = b_out + b_ep + b_q + b_tr + b_st + b_er + b_obs + b_mu;
-  if (need > e->eval_bytes) {
-    HIPC(hipStreamSynchronize(e->stream));
-    if (e->eval_buf) HIPC(hipFree(e->eval_buf));
-    e->eval_buf = nullptr;
-    e->eval_bytes = 0;
-    HIPC(hipMalloc(reinterpret_cast<void**>(&e->eval_buf), need));
-    e->eval_bytes = need;
-  }
+  if (const int rc = grow_eval_buf(e, need)) return rc;
   char* cur = e->eval_buf;
   auto take = [&](size_t b) { char* r = cur; cur += b; return r; };
   EvalArgs a{};
@@ -3274,13 +3291,7 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
   a.trace = tracing ? tr_dev : nullptr;
   a.trace_robots = tracing ? spec->trace_robots : 0;
   a.trace_steps = tracing ? spec->trace_steps : 0;
-  GoalEnvParams& g = a.p;
-  g.P = env->pos_dim; g.terminate_on_goal = env->terminate_on_goal != 0;
-  g.time_limit = env->time_limit > 0 ? env->time_limit : INT_MAX;   // control.py: no time limit
-  g.dt = env->dt; g.extent = env->extent; g.reach = env->reach_radius; g.bonus = env->goal_bonus;
-  g.extra_bonus = env->extra_bonus; g.noise = env->obs_noise;
-  for (int j = 0; j < 3; ++j)
-    for (int k = 0; k < 32; ++k) g.mix[j][k] = (j < env->pos_dim && k < A) ? env->mix[j][k] : 0.f;
+  a.p = eval_env_params(env, A, env->terminate_on_goal != 0, env->time_limit > 0 ? env->time_limit : INT_MAX);   // control.py: no limit
   a.N = N; a.D = D; a.Dp = Dp; a.A = A; a.Ap = Ap;
   a.episodes = spec->episodes; a.deterministic = spec->deterministic != 0; a.maxq = maxq;
   a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
@@ -3313,6 +3324,106 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
   HIPC(hipMemcpyAsync(robot_out, a.robot_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
   if (episode_out && maxq > 0)
     HIPC(hipMemcpyAsync(episode_out, a.ep_out, (size_t)N * maxq * 3 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (tracing) HIPC(hipMemcpyAsync(trace_out, tr_dev, n_tr * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return persistent ? 1 : 0;
+}
+
+// ---- waypoint following: the policy as a tracker of given goal sequences ------------------------------------------------
+int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
+                                double* robot_out, float* path_out, float* trace_out) {
+  if (!e || !env || !spec || !start || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
+  const int N = spec->n_robots, K = spec->max_waypoints, P = env->pos_dim;
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "follow: n_robots must be >= 1");
+  if (K < 1) return fail(MOBROB_ERR_INVALID, "follow: max_waypoints must be >= 1");
+  if (spec->max_steps < 1) return fail(MOBROB_ERR_INVALID, "follow: max_steps must be >= 1");
+  if (spec->path_stride < 0) return fail(MOBROB_ERR_INVALID, "follow: path_stride must be >= 0 (0: no path)");
+  if (P < 1 || P > 3 || 3 * P > e->D) return fail(MOBROB_ERR_INVALID, "follow: pos_dim must be 1..3 and 3*pos_dim <= obs_dim");
+  if (e->A > 32) return fail(MOBROB_ERR_INVALID, "follow: act_dim must be <= 32");
+  if (!spec->deterministic && e->sde)
+    return fail(MOBROB_ERR_INVALID, "follow: stochastic actions of a use_sde policy are not supported (deterministic only)");
+  if (spec->trace_robots < 0 || spec->trace_steps < 0) return fail(MOBROB_ERR_INVALID, "follow: negative trace size");
+  const bool tracing = trace_out && spec->trace_robots > 0 && spec->trace_steps > 0;
+  if (tracing && (spec->trace_robots > N || spec->trace_steps > spec->max_steps))
+    return fail(MOBROB_ERR_INVALID, "follow: trace_robots <= n_robots and trace_steps <= max_steps");
+  std::vector<int32_t> nw(N);
+  for (int i = 0; i < N; ++i) {
+    nw[i] = n_waypoints ? n_waypoints[i] : K;
+    if (nw[i] < 0 || nw[i] > K) return fail(MOBROB_ERR_INVALID, "follow: n_waypoints[%d] = %d outside 0 .. %d", i, nw[i], K);
+    for (int j = 0; j < P; ++j)
+      if (!std::isfinite(start[(size_t)i * P + j])) return fail(MOBROB_ERR_INVALID, "follow: start of robot %d is not finite", i);
+    for (int k = 0; k < nw[i]; ++k)
+      for (int j = 0; j < P; ++j)
+        if (!std::isfinite(waypoints[((size_t)i * K + k) * P + j]))
+          return fail(MOBROB_ERR_INVALID, "follow: waypoint %d of robot %d is not finite", k, i);
+  }
+  // ---- buffers: the evaluation's (outside the arena) ----
+  const int Dp = e->Dp, Ap = e->Ap, A = e->A, D = e->D;
+  const bool pathing = path_out && spec->path_stride > 0;
+  const size_t n_rec = pathing ? (size_t)(spec->max_steps / spec->path_stride + 1) : 0;
+  const int tw = 9 + D + A + kEvalTraceFlags;
+  const size_t n_tr = tracing ? (size_t)spec->trace_steps * spec->trace_robots * tw : 1;
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t b_out = al((size_t)N * 4 * 8), b_arr = al((size_t)N * K * 4), b_start = al((size_t)N * P * 4),
+               b_wp = al((size_t)N * K * P * 4), b_nw = al((size_t)N * 4), b_path = al(std::max<size_t>(n_rec * N * P, 1) * 4),
+               b_tr = al(n_tr * 4), b_st = al((size_t)N * kGoalStateFloats * 4),
+               b_obs = al((size_t)cdiv(N, 256) * 256 * Dp * 4), b_mu = al((size_t)cdiv(N, 256) * 256 * Ap * 4);   // whole 256-row tiles
+  if (const int rc = grow_eval_buf(e, b_out + b_arr + b_start + b_wp + b_nw + b_path + b_tr + b_st + b_obs + b_mu)) return rc;
+  char* cur = e->eval_buf;
+  auto take = [&](size_t b) { char* r = cur; cur += b; return r; };
+  FollowArgs f{};
+  EvalArgs& a = f.e;
+  a.robot_out = reinterpret_cast<double*>(take(b_out));
+  f.arrival = reinterpret_cast<int*>(take(b_arr));
+  float* start_dev = reinterpret_cast<float*>(take(b_start));
+  float* wp_dev = reinterpret_cast<float*>(take(b_wp));
+  int* nw_dev = reinterpret_cast<int*>(take(b_nw));
+  float* path_dev = reinterpret_cast<float*>(take(b_path));
+  float* tr_dev = reinterpret_cast<float*>(take(b_tr));
+  a.st = reinterpret_cast<float*>(take(b_st));
+  a.obs = reinterpret_cast<float*>(take(b_obs));
+  float* mu = reinterpret_cast<float*>(take(b_mu));
+  a.mu = mu;
+  a.trace = tracing ? tr_dev : nullptr;
+  a.trace_robots = tracing ? spec->trace_robots : 0;
+  a.trace_steps = tracing ? spec->trace_steps : 0;
+  a.p = eval_env_params(env, A, false, INT_MAX);   // no termination, no time limit: the robot only stops at its last waypoint
+  a.N = N; a.D = D; a.Dp = Dp; a.A = A; a.Ap = Ap;
+  a.deterministic = spec->deterministic != 0;
+  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
+  const uint64_t key = spec->seed ^ kEvalKeyMix;
+  a.k0 = (uint32_t)key; a.k1 = (uint32_t)(key >> 32);
+  a.log_std = Pp(e, T_LOGSTD);
+  f.K = K; f.max_steps = spec->max_steps; f.path_stride = pathing ? spec->path_stride : 0;
+  f.start = start_dev; f.wp = wp_dev; f.nwp = nw_dev;
+  f.path = pathing ? path_dev : nullptr;
+  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(wp_dev, waypoints, (size_t)N * K * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(nw_dev, nw.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemsetAsync(f.arrival, 0xFF, (size_t)N * K * 4, e->stream));   // -1: not reached
+  if (tracing) HIPC(hipMemsetAsync(tr_dev, 0, n_tr * 4, e->stream));
+  const char* pe = getenv("MOBROB_EVAL_PERSISTENT");   // 0: the per-step path on every engine (A/B, tests); read per call
+  const bool persistent = e->fused.enabled && e->fused.H == 64 && !(pe && atoi(pe) == 0);
+  if (persistent) {
+    Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
+    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_follow64_goal<DPc>), dim3(cdiv(N, 16)), dim3(64), eval64_lds_bytes(Dp), e->stream, f, W));
+    HIPC(hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(k_follow_goal_init, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, f);
+    for (int t = 0; t < spec->max_steps; ++t) {
+      for (int s = 0; s < N; s += e->rows_max) {
+        const int c = std::min(e->rows_max, N - s);
+        forward(e, a.obs + (size_t)s * Dp, c, true, mu + (size_t)s * Ap, false, nullptr);
+      }
+      hipLaunchKernelGGL(k_follow_goal_step, dim3(cdiv(N, 256)), dim3(256), 256 * 33 * sizeof(float), e->stream, f, t);
+    }
+    hipLaunchKernelGGL(k_follow_goal_fin, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, f);
+    HIPC(hipGetLastError());
+  }
+  HIPC(hipMemcpyAsync(robot_out, a.robot_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(arrival, f.arrival, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
+  if (pathing) HIPC(hipMemcpyAsync(path_out, path_dev, n_rec * N * P * 4, hipMemcpyDeviceToHost, e->stream));
   if (tracing) HIPC(hipMemcpyAsync(trace_out, tr_dev, n_tr * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return persistent ? 1 : 0;

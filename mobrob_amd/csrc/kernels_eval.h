@@ -190,6 +190,109 @@ __device__ __forceinline__ void eval64_state_lds(float* s, const GoalState& g) {
   for (int j = 0; j < 3; ++j) { s[j] = g.pos[j]; s[3 + j] = g.vel[j]; s[6 + j] = g.goal[j]; }
 }
 
+// k_eval64_goal's tile phases as functions, for k_follow64_goal (kernels_follow.h).  k_eval64_goal keeps its own inline copy, so
+// that its code is the one its measurements and tests were taken on.
+//
+// the actor -> LDS in fragment order (zero beyond D / A), its biases, and a zeroed observation tile
+template <int DP>
+__device__ __forceinline__ void eval64_load_actor(const Eval64Net& W, int D, int A, int lane) {
+  using L = LayEval64<DP>;
+  constexpr int KS1 = L::KS1;
+  for (int i = lane; i < 4 * KS1 * 64; i += 64) {
+    const int l = i & 63, ks = (i >> 6) % KS1, cb = (i >> 6) / KS1;
+    const int k = 4 * ks + (l >> 4);
+    lds[L::W1 + i] = k < D ? W.W1[(size_t)(16 * cb + (l & 15)) * D + k] : 0.f;
+  }
+  for (int i = lane; i < 4 * 16 * 64; i += 64) {
+    const int l = i & 63, ks = (i >> 6) & 15, cb = i >> 10;
+    lds[L::W2 + i] = W.W2[(16 * cb + (l & 15)) * 64 + 4 * ks + (l >> 4)];
+  }
+  for (int i = lane; i < 2 * 16 * 64; i += 64) {
+    const int l = i & 63, ks = (i >> 6) & 15, nb = i >> 10;
+    const int col = 16 * nb + (l & 15);
+    lds[L::W3 + i] = col < A ? W.W3[col * 64 + 4 * ks + (l >> 4)] : 0.f;
+  }
+  lds[L::B1 + lane] = W.b1[lane];
+  lds[L::B2 + lane] = W.b2[lane];
+  if (lane < 32) lds[L::B3 + lane] = lane < A ? W.b3[lane] : 0.f;
+  for (int i = lane; i < 16 * L::LDX; i += 64) lds[L::X + i] = 0.f;
+}
+
+// one step of the tile's actor: observation tile (goal_features of the robots' LDS state rows + the evaluation's noise, 64 lanes),
+// layer 1, layer 2, head; the 16 mean rows land in L::MU.  Every phase ends with the (single-wave) barrier.
+template <int DP>
+__device__ __forceinline__ void eval64_actor_step(const EvalArgs& a, int row0, int t, int lane, bool wide_head) {
+  using L = LayEval64<DP>;
+  constexpr int KS1 = L::KS1, per = DP / 4;
+  const int r16 = lane & 15, q = lane >> 4;
+  // ---- observation tile: lane (r16, q) builds chunks q, q + 4, ... of robot r16 ----
+  if (row0 + r16 < a.N) {
+    GoalState gs{};
+    const float* s = &lds[L::ST + 12 * r16];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { gs.pos[j] = s[j]; gs.vel[j] = s[3 + j]; gs.goal[j] = s[6 + j]; }
+    for (int c = q; c < per; c += 4)
+      *reinterpret_cast<f32x4*>(&lds[L::X + r16 * L::LDX + 4 * c]) = eval_features(gs, a, row0 + r16, c, (uint32_t)t);
+  }
+  __syncthreads();
+  // ---- layer 1: h1 = tanh(W1 x + b1), four 16-column accumulators ----
+  {
+    f32x4 c[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) { const float b = lds[L::B1 + 16 * cb + r16]; c[cb] = f32x4{b, b, b, b}; }
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) {
+      const float x = lds[L::X + r16 * L::LDX + 4 * ks + q];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) c[cb] = MFMA16(x, lds[L::W1 + (cb * KS1 + ks) * 64 + lane], c[cb]);
+    }
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) lds[L::H1 + (4 * q + i) * L::LDH + 16 * cb + r16] = fast_tanh(c[cb][i]);
+  }
+  __syncthreads();
+  // ---- layer 2 ----
+  {
+    f32x4 c[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) { const float b = lds[L::B2 + 16 * cb + r16]; c[cb] = f32x4{b, b, b, b}; }
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+      const float x = lds[L::H1 + r16 * L::LDH + 4 * ks + q];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) c[cb] = MFMA16(x, lds[L::W2 + (cb * 16 + ks) * 64 + lane], c[cb]);
+    }
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) lds[L::H2 + (4 * q + i) * L::LDH + 16 * cb + r16] = fast_tanh(c[cb][i]);
+  }
+  __syncthreads();
+  // ---- head: mean = W3 h2 + b3 (one or two 16-column blocks) ----
+  {
+    const float b0 = lds[L::B3 + r16], b1 = lds[L::B3 + 16 + r16];
+    f32x4 c0 = f32x4{b0, b0, b0, b0}, c1 = f32x4{b1, b1, b1, b1};
+    if (wide_head) {
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) {
+        const float x = lds[L::H2 + r16 * L::LDH + 4 * ks + q];
+        c0 = MFMA16(x, lds[L::W3 + ks * 64 + lane], c0);
+        c1 = MFMA16(x, lds[L::W3 + (16 + ks) * 64 + lane], c1);
+      }
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) c0 = MFMA16(lds[L::H2 + r16 * L::LDH + 4 * ks + q], lds[L::W3 + ks * 64 + lane], c0);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      lds[L::MU + (4 * q + i) * L::LDM + r16] = c0[i];
+      lds[L::MU + (4 * q + i) * L::LDM + 16 + r16] = c1[i];
+    }
+  }
+  __syncthreads();
+}
+
 template <int DP>
 __global__ __launch_bounds__(64) void k_eval64_goal(EvalArgs a, Eval64Net W, int max_steps) {
   using L = LayEval64<DP>;

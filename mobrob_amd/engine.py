@@ -7,7 +7,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from ._lib import BUF, Config, DroneParams, EpisodeStats, EvalSpec, GoalEnv, TrainStats, check
+from ._lib import BUF, Config, DroneParams, EpisodeStats, EvalSpec, FollowSpec, GoalEnv, TrainStats, check
 
 F32 = np.float32
 STAT_KEYS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
@@ -391,6 +391,40 @@ class PPOEngine:
                "episode_success": np.where(done, ep[:, :, 2], np.nan), "persistent": bool(r == 1)}
         if tr is not None:
             out["trace"] = tr
+        return out
+
+    def follow_waypoints(self, pos_dim, mix, dt=0.05, extent=3.0, reach_radius=0.3, goal_bonus=5.0, extra_bonus=0.0,
+                         obs_noise=0.1, *, start, waypoints, n_waypoints=None, max_steps=1000, deterministic=True, seed=0,
+                         path_stride=0, trace=None):
+        """The current policy as a tracker of given goal sequences (mobrob_ppo_follow_waypoints): robot i starts at rest on
+        start[i] ([n][P]) and follows waypoints[i][:n_waypoints[i]] (waypoints [n][K][P], or [K][P] for all robots; n_waypoints
+        None = K each), no time limit, no reset.  path_stride > 0 records positions; trace = (robots, steps): teacher-forcing
+        trace.  Returns the dict of mobrob_amd.waypoints (arrival, reached, steps, reward_sum, final_distance, path, trace,
+        persistent)."""
+        from .waypoints import follow_inputs
+        s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
+        n, K, P = wp.shape
+        if self.use_sde and not deterministic:
+            raise ValueError("follow_waypoints: stochastic actions of a use_sde (gSDE) policy are not supported; use deterministic=True")
+        g = self._goal_env_struct(pos_dim, mix, 0, False, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise)
+        sp = FollowSpec()
+        sp.n_robots, sp.max_waypoints, sp.max_steps, sp.deterministic = n, K, int(max_steps), int(bool(deterministic))
+        sp.seed = int(seed) & (2 ** 64 - 1)
+        sp.path_stride = int(path_stride)
+        tr_r, tr_s = (0, 0) if trace is None else (int(trace[0]), int(trace[1]))
+        sp.trace_robots, sp.trace_steps = tr_r, tr_s
+        arrival = np.empty((n, K), np.int32)
+        robot = np.zeros((n, 4), np.float64)
+        path = np.zeros((int(max_steps) // int(path_stride) + 1, n, P), F32) if int(path_stride) > 0 and int(max_steps) > 0 else None
+        tr = np.zeros((max(tr_s, 1), max(tr_r, 1), 9 + self.D + self.A + 4), F32) if trace is not None else None
+        i32 = C.POINTER(C.c_int32)
+        r = check(self.lib.mobrob_ppo_follow_waypoints(self._h, C.byref(g), C.byref(sp), _fp(s), _fp(wp), nw.ctypes.data_as(i32),
+                                                        arrival.ctypes.data_as(i32), robot.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        _fp(path), _fp(tr)))
+        out = {"arrival": arrival.astype(np.int64), "reached": robot[:, 2].astype(np.int64), "steps": robot[:, 1].astype(np.int64),
+               "reward_sum": robot[:, 0], "final_distance": robot[:, 3], "trace": tr, "persistent": bool(r == 1)}
+        if path is not None:
+            out["path"] = path
         return out
 
     def episode_stats(self, reset=True):

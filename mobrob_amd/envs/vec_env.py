@@ -217,6 +217,15 @@ class DeviceGoalVecEnv(VecEnvBase):
                                         episodes=episodes, quota=quota, deterministic=deterministic,
                                         seed=(self._seed or 0) if seed is None else seed, trace=trace)
 
+    def follow(self, engine, start, waypoints, n_waypoints=None, max_steps=1000, deterministic=True, seed=None, path_stride=0,
+               trace=None):
+        """The engine's current policy following given waypoints on this task (PPOEngine.follow_waypoints with this env's mix,
+        dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed."""
+        return engine.follow_waypoints(self.pos_dim, self.mix, dt=self.dt, extent=self.extent, extra_bonus=self.extra_bonus,
+                                       start=start, waypoints=waypoints, n_waypoints=n_waypoints, max_steps=int(max_steps),
+                                       deterministic=deterministic, seed=(self._seed or 0) if seed is None else seed,
+                                       path_stride=path_stride, trace=trace)
+
     def seed(self, seed=None):
         self._seed = seed
 
