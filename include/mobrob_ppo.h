@@ -450,8 +450,8 @@ int mobrob_ppo_predict(mobrob_ppo_engine_t* e, const float* obs, int32_t n, int3
  *             parameter vector; returns after the results are copied out.  Its device buffers are allocated on first use, grown
  *             when needed and freed by mobrob_ppo_destroy; they are outside the engine's arena (mobrob_ppo_device_bytes and
  *             mobrob_ppo_create_in_arena are unchanged).
- *   kernels   2x64 tanh engines of the fused family: ONE persistent launch (k_eval64_goal); every other engine: the engine's
- *             forward plus one kernel per step (k_eval_goal_step).  MOBROB_EVAL_PERSISTENT=0 forces the per-step path.
+ *   kernels   2x64 tanh engines of the fused family: ONE persistent launch (k_goal64_tile); every other engine: the engine's
+ *             forward plus one kernel per step (k_goal_task_step).  MOBROB_EVAL_PERSISTENT=0 forces the per-step path.
  * Returns 1 when the persistent kernel ran, 0 for the per-step path, or a negative error. */
 typedef struct mobrob_eval_spec {
   int32_t n_robots;        /* >= 1, independent of the engine's n_envs                                        */
@@ -486,7 +486,7 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
  *             the step, finished after the step.  Rows of robots that have finished are zero.
  *   actions, streams, ordering, buffers and kernels: as mobrob_ppo_evaluate_goal_env (the evaluation's Philox streams keyed by
  *             seed; nothing of the training state is read or advanced).  2x64 tanh engines of the fused family: ONE persistent
- *             launch (k_follow64_goal); every other engine: forward plus one kernel per step.  MOBROB_EVAL_PERSISTENT=0 forces
+ *             launch (k_goal64_tile); every other engine: forward plus one kernel per step.  MOBROB_EVAL_PERSISTENT=0 forces
  *             the per-step path.
  * MOBROB_ERR_INVALID before any launch for: a count outside 0 .. max_waypoints, max_waypoints < 1, a pos_dim / act_dim that
  * evaluate refuses, max_steps < 1, path_stride < 0, a trace larger than the run, stochastic actions of a use_sde engine, non-finite

@@ -3240,24 +3240,123 @@ static GoalEnvParams eval_env_params(const mobrob_goal_env_t* env, int A, bool t
   return g;
 }
 
+extern "C++" {   // templates: C++ linkage inside the C-ABI block
+// what evaluate and follow_waypoints take alike from their specs; `who` prefixes their error messages
+struct EvalCall {
+  const char* who;
+  int N, max_steps, deterministic;
+  uint64_t seed;
+  int trace_robots, trace_steps;
+  float* trace_out;
+  bool tracing() const { return trace_out && trace_robots > 0 && trace_steps > 0; }
+};
+
+// the checks both entry points make, in two groups (evaluate has checks of its own between them)
+static int eval_check_dims(const mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const char* who) {
+  if (env->pos_dim < 1 || env->pos_dim > 3 || 3 * env->pos_dim > e->D)
+    return fail(MOBROB_ERR_INVALID, "%s: pos_dim must be 1..3 and 3*pos_dim <= obs_dim", who);
+  if (e->A > 32) return fail(MOBROB_ERR_INVALID, "%s: act_dim must be <= 32", who);
+  return MOBROB_OK;
+}
+static int eval_check_actions_trace(const mobrob_ppo_engine_t* e, const EvalCall& c) {
+  if (!c.deterministic && e->sde)
+    return fail(MOBROB_ERR_INVALID, "%s: stochastic actions of a use_sde policy are not supported (deterministic only)", c.who);
+  if (c.tracing() && (c.trace_robots > c.N || c.trace_steps > c.max_steps))
+    return fail(MOBROB_ERR_INVALID, "%s: trace_robots <= n_robots and trace_steps <= max_steps", c.who);
+  return MOBROB_OK;
+}
+
+// eval_buf's regions, described once: add() every region while sizing, at() the same offsets once the buffer is grown
+struct EvalCarve {
+  size_t total = 0;
+  size_t add(size_t bytes) {
+    const size_t off = total;
+    total += (bytes + 255) / 256 * 256;
+    return off;
+  }
+};
+template <class T>
+static T* eval_at(const mobrob_ppo_engine_t* e, size_t off) { return reinterpret_cast<T*>(e->eval_buf + off); }
+
+// The common part of a call: adds the shared regions (robot_out, trace, st, obs, mu) to the task's own in `carve`, grows eval_buf
+// (outside the arena: device_bytes / create_in_arena are unchanged), fills the fields of `a` that do not depend on the task and
+// zeroes the trace.
+static int eval_prepare(mobrob_ppo_engine_t* e, const EvalCall& c, const GoalEnvParams& p, EvalCarve& carve, EvalArgs& a) {
+  const int N = c.N, Dp = e->Dp, Ap = e->Ap;
+  const bool tracing = c.tracing();
+  const size_t n_tr = tracing ? (size_t)c.trace_steps * c.trace_robots * (9 + e->D + e->A + kEvalTraceFlags) : 1;
+  const size_t o_out = carve.add((size_t)N * 4 * 8), o_tr = carve.add(n_tr * 4), o_st = carve.add((size_t)N * kGoalStateFloats * 4),
+               o_obs = carve.add((size_t)cdiv(N, 256) * 256 * Dp * 4), o_mu = carve.add((size_t)cdiv(N, 256) * 256 * Ap * 4);   // whole 256-row tiles
+  if (const int rc = grow_eval_buf(e, carve.total)) return rc;
+  a.robot_out = eval_at<double>(e, o_out);
+  a.st = eval_at<float>(e, o_st);
+  a.obs = eval_at<float>(e, o_obs);
+  a.mu = eval_at<float>(e, o_mu);
+  a.trace = tracing ? eval_at<float>(e, o_tr) : nullptr;
+  a.trace_robots = tracing ? c.trace_robots : 0;
+  a.trace_steps = tracing ? c.trace_steps : 0;
+  a.p = p;
+  a.N = N; a.D = e->D; a.Dp = Dp; a.A = e->A; a.Ap = Ap;
+  a.deterministic = c.deterministic != 0;
+  a.max_steps = c.max_steps;
+  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
+  const uint64_t key = c.seed ^ kEvalKeyMix;
+  a.k0 = (uint32_t)key; a.k1 = (uint32_t)(key >> 32);
+  a.log_std = Pp(e, T_LOGSTD);
+  if (tracing) HIPC(hipMemsetAsync(a.trace, 0, n_tr * 4, e->stream));
+  return MOBROB_OK;
+}
+
+// Runs the task for a.max_steps steps: k_goal64_tile on 2x64 tanh engines of the fused family (returns 1), else the per-step path
+// (returns 0): the engine's forward() in rows_max chunks + the step kernel per step, then the task's `fin` kernel if it has one.
+template <class Task>
+static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, void (*fin)(typename Task::Args)) {
+  const EvalArgs& a = Task::eval(args);
+  const int N = a.N;
+  const char* pe = getenv("MOBROB_EVAL_PERSISTENT");   // 0: the per-step path on every engine (A/B, tests); read per call
+  const bool persistent = e->fused.enabled && e->fused.H == 64 && !(pe && atoi(pe) == 0);
+  if (persistent) {
+    Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
+    FUSED_DISPATCH_DP(a.Dp, hipLaunchKernelGGL((k_goal64_tile<DPc, Task>), dim3(cdiv(N, 16)), dim3(64), eval64_lds_bytes(a.Dp), e->stream, args, W));
+  } else {
+    hipLaunchKernelGGL(k_goal_task_init<Task>, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, args);
+    for (int t = 0; t < a.max_steps; ++t) {
+      for (int s = 0; s < N; s += e->rows_max) {
+        const int c = std::min(e->rows_max, N - s);
+        forward(e, a.obs + (size_t)s * a.Dp, c, true, a.mu + (size_t)s * a.Ap, false, nullptr);
+      }
+      hipLaunchKernelGGL(k_goal_task_step<Task>, dim3(cdiv(N, 256)), dim3(256), 256 * 33 * sizeof(float), e->stream, args, t);
+    }
+    if (fin) hipLaunchKernelGGL(fin, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, args);
+  }
+  HIPC(hipGetLastError());
+  return persistent ? 1 : 0;
+}
+
+// robot_out and the trace back to the caller; returns `ran` (eval_run's) once everything enqueued on the stream is done
+static int eval_copy_back(mobrob_ppo_engine_t* e, const EvalCall& c, const EvalArgs& a, double* robot_out, int ran) {
+  HIPC(hipMemcpyAsync(robot_out, a.robot_out, (size_t)a.N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (a.trace)
+    HIPC(hipMemcpyAsync(c.trace_out, a.trace, (size_t)a.trace_steps * a.trace_robots * (9 + a.D + a.A + kEvalTraceFlags) * 4,
+                        hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return ran;
+}
+}  // extern "C++"
+
 int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
                                  const int32_t* quota, double* robot_out, double* episode_out, float* trace_out) {
   if (!e || !env || !spec || !robot_out) return fail(MOBROB_ERR_INVALID, "evaluate: null argument");
-  const int N = spec->n_robots;
+  const EvalCall c{"evaluate", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
+  const int N = c.N;
   if (N < 1) return fail(MOBROB_ERR_INVALID, "evaluate: n_robots must be >= 1");
   if (spec->max_steps < 1) return fail(MOBROB_ERR_INVALID, "evaluate: max_steps must be >= 1");
   if (spec->episodes < 0) return fail(MOBROB_ERR_INVALID, "evaluate: episodes must be >= 0");
-  if (env->pos_dim < 1 || env->pos_dim > 3 || 3 * env->pos_dim > e->D)
-    return fail(MOBROB_ERR_INVALID, "evaluate: pos_dim must be 1..3 and 3*pos_dim <= obs_dim");
-  if (e->A > 32) return fail(MOBROB_ERR_INVALID, "evaluate: act_dim must be <= 32");
+  if (const int rc = eval_check_dims(e, env, c.who)) return rc;
   if (env->time_limit < 0) return fail(MOBROB_ERR_INVALID, "evaluate: time_limit must be >= 0 (0: none)");
   if (spec->episodes > 0 && env->time_limit == 0)
     return fail(MOBROB_ERR_INVALID, "evaluate: an episode quota needs a time limit (the run might never finish)");
-  if (!spec->deterministic && e->sde)
-    return fail(MOBROB_ERR_INVALID, "evaluate: stochastic actions of a use_sde policy are not supported (deterministic only)");
-  const bool tracing = trace_out && spec->trace_robots > 0 && spec->trace_steps > 0;
-  if (tracing && (spec->trace_robots > N || spec->trace_steps > spec->max_steps))
-    return fail(MOBROB_ERR_INVALID, "evaluate: trace_robots <= n_robots and trace_steps <= max_steps");
+  if (const int rc = eval_check_actions_trace(e, c)) return rc;
   std::vector<int32_t> q(N);
   int maxq = 0;
   for (int i = 0; i < N; ++i) {
@@ -3265,68 +3364,25 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
     if (q[i] < 0) return fail(MOBROB_ERR_INVALID, "evaluate: negative quota");
     maxq = std::max(maxq, (int)q[i]);
   }
-  // ---- buffers (outside the arena: device_bytes / create_in_arena are unchanged) ----
-  const int Dp = e->Dp, Ap = e->Ap, A = e->A, D = e->D;
-  const int tw = 9 + D + A + kEvalTraceFlags;
-  const size_t n_tr = tracing ? (size_t)spec->trace_steps * spec->trace_robots * tw : 1;
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_out = al((size_t)N * 4 * 8), b_ep = al(std::max<size_t>((size_t)N * maxq * 3, 1) * 8), b_q = al((size_t)N * 4),
-               b_tr = al(n_tr * 4), b_st = al((size_t)N * kGoalStateFloats * 4), b_er = al((size_t)N * 8),
-               b_obs = al((size_t)cdiv(N, 256) * 256 * Dp * 4), b_mu = al((size_t)cdiv(N, 256) * 256 * Ap * 4);   // whole 256-row tiles
-  const size_t need = b_out + b_ep + b_q + b_tr + b_st + b_er + b_obs + b_mu;
-  if (const int rc = grow_eval_buf(e, need)) return rc;
-  char* cur = e->eval_buf;
-  auto take = [&](size_t b) { char* r = cur; cur += b; return r; };
+  EvalCarve carve;
+  const size_t o_ep = carve.add(std::max<size_t>((size_t)N * maxq * 3, 1) * 8), o_q = carve.add((size_t)N * 4), o_er = carve.add((size_t)N * 8);
   EvalArgs a{};
-  a.robot_out = reinterpret_cast<double*>(take(b_out));
-  a.ep_out = reinterpret_cast<double*>(take(b_ep));
-  int* q_dev = reinterpret_cast<int*>(take(b_q));
-  float* tr_dev = reinterpret_cast<float*>(take(b_tr));
-  a.st = reinterpret_cast<float*>(take(b_st));
-  a.ep_ret = reinterpret_cast<double*>(take(b_er));
-  a.obs = reinterpret_cast<float*>(take(b_obs));
-  float* mu = reinterpret_cast<float*>(take(b_mu));
-  a.mu = mu;
+  const GoalEnvParams p = eval_env_params(env, e->A, env->terminate_on_goal != 0, env->time_limit > 0 ? env->time_limit : INT_MAX);   // control.py: no limit
+  if (const int rc = eval_prepare(e, c, p, carve, a)) return rc;
+  int* q_dev = eval_at<int>(e, o_q);
+  a.ep_out = eval_at<double>(e, o_ep);
+  a.ep_ret = eval_at<double>(e, o_er);
   a.quota = q_dev;
-  a.trace = tracing ? tr_dev : nullptr;
-  a.trace_robots = tracing ? spec->trace_robots : 0;
-  a.trace_steps = tracing ? spec->trace_steps : 0;
-  a.p = eval_env_params(env, A, env->terminate_on_goal != 0, env->time_limit > 0 ? env->time_limit : INT_MAX);   // control.py: no limit
-  a.N = N; a.D = D; a.Dp = Dp; a.A = A; a.Ap = Ap;
-  a.episodes = spec->episodes; a.deterministic = spec->deterministic != 0; a.maxq = maxq;
-  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
-  const uint64_t key = spec->seed ^ kEvalKeyMix;
-  a.k0 = (uint32_t)key; a.k1 = (uint32_t)(key >> 32);
-  a.log_std = Pp(e, T_LOGSTD);
-  HIPC(hipMemcpyAsync(q_dev, q.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
-  if (tracing) HIPC(hipMemsetAsync(tr_dev, 0, n_tr * 4, e->stream));
-  if (maxq > 0) HIPC(hipMemsetAsync(a.ep_out, 0, (size_t)N * maxq * 3 * 8, e->stream));
+  a.episodes = spec->episodes; a.maxq = maxq;
   // a robot finishes an episode at least every time_limit steps: with a quota, the run is over after maxq * time_limit steps
-  int steps = spec->max_steps;
-  if (spec->episodes > 0) steps = (int)std::min<int64_t>(steps, (int64_t)maxq * env->time_limit);
-  const char* pe = getenv("MOBROB_EVAL_PERSISTENT");   // 0: the per-step path on every engine (A/B, tests); read per call
-  const bool persistent = e->fused.enabled && e->fused.H == 64 && !(pe && atoi(pe) == 0);
-  if (persistent) {
-    Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
-    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_eval64_goal<DPc>), dim3(cdiv(N, 16)), dim3(64), eval64_lds_bytes(Dp), e->stream, a, W, steps));
-    HIPC(hipGetLastError());
-  } else {
-    hipLaunchKernelGGL(k_eval_goal_init, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, a);
-    for (int t = 0; t < steps; ++t) {
-      for (int s = 0; s < N; s += e->rows_max) {
-        const int c = std::min(e->rows_max, N - s);
-        forward(e, a.obs + (size_t)s * Dp, c, true, mu + (size_t)s * Ap, false, nullptr);
-      }
-      hipLaunchKernelGGL(k_eval_goal_step, dim3(cdiv(N, 256)), dim3(256), 256 * 33 * sizeof(float), e->stream, a, t);
-    }
-    HIPC(hipGetLastError());
-  }
-  HIPC(hipMemcpyAsync(robot_out, a.robot_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (spec->episodes > 0) a.max_steps = (int)std::min<int64_t>(a.max_steps, (int64_t)maxq * env->time_limit);
+  HIPC(hipMemcpyAsync(q_dev, q.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  if (maxq > 0) HIPC(hipMemsetAsync(a.ep_out, 0, (size_t)N * maxq * 3 * 8, e->stream));
+  const int ran = eval_run<EvalTask>(e, a, nullptr);
+  if (ran < 0) return ran;
   if (episode_out && maxq > 0)
     HIPC(hipMemcpyAsync(episode_out, a.ep_out, (size_t)N * maxq * 3 * 8, hipMemcpyDeviceToHost, e->stream));
-  if (tracing) HIPC(hipMemcpyAsync(trace_out, tr_dev, n_tr * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPC(hipStreamSynchronize(e->stream));
-  return persistent ? 1 : 0;
+  return eval_copy_back(e, c, a, robot_out, ran);
 }
 
 // ---- waypoint following: the policy as a tracker of given goal sequences ------------------------------------------------
@@ -3334,19 +3390,16 @@ int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t*
                                 const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
                                 double* robot_out, float* path_out, float* trace_out) {
   if (!e || !env || !spec || !start || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
-  const int N = spec->n_robots, K = spec->max_waypoints, P = env->pos_dim;
+  const EvalCall c{"follow", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
+  const int N = c.N, K = spec->max_waypoints, P = env->pos_dim;
   if (N < 1) return fail(MOBROB_ERR_INVALID, "follow: n_robots must be >= 1");
   if (K < 1) return fail(MOBROB_ERR_INVALID, "follow: max_waypoints must be >= 1");
   if (spec->max_steps < 1) return fail(MOBROB_ERR_INVALID, "follow: max_steps must be >= 1");
   if (spec->path_stride < 0) return fail(MOBROB_ERR_INVALID, "follow: path_stride must be >= 0 (0: no path)");
-  if (P < 1 || P > 3 || 3 * P > e->D) return fail(MOBROB_ERR_INVALID, "follow: pos_dim must be 1..3 and 3*pos_dim <= obs_dim");
-  if (e->A > 32) return fail(MOBROB_ERR_INVALID, "follow: act_dim must be <= 32");
-  if (!spec->deterministic && e->sde)
-    return fail(MOBROB_ERR_INVALID, "follow: stochastic actions of a use_sde policy are not supported (deterministic only)");
+  if (const int rc = eval_check_dims(e, env, c.who)) return rc;
+  // (a negative trace size is never `tracing`, so the shared trace-bounds check cannot fire in its place)
+  if (const int rc = eval_check_actions_trace(e, c)) return rc;
   if (spec->trace_robots < 0 || spec->trace_steps < 0) return fail(MOBROB_ERR_INVALID, "follow: negative trace size");
-  const bool tracing = trace_out && spec->trace_robots > 0 && spec->trace_steps > 0;
-  if (tracing && (spec->trace_robots > N || spec->trace_steps > spec->max_steps))
-    return fail(MOBROB_ERR_INVALID, "follow: trace_robots <= n_robots and trace_steps <= max_steps");
   std::vector<int32_t> nw(N);
   for (int i = 0; i < N; ++i) {
     nw[i] = n_waypoints ? n_waypoints[i] : K;
@@ -3358,75 +3411,31 @@ int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t*
         if (!std::isfinite(waypoints[((size_t)i * K + k) * P + j]))
           return fail(MOBROB_ERR_INVALID, "follow: waypoint %d of robot %d is not finite", k, i);
   }
-  // ---- buffers: the evaluation's (outside the arena) ----
-  const int Dp = e->Dp, Ap = e->Ap, A = e->A, D = e->D;
   const bool pathing = path_out && spec->path_stride > 0;
   const size_t n_rec = pathing ? (size_t)(spec->max_steps / spec->path_stride + 1) : 0;
-  const int tw = 9 + D + A + kEvalTraceFlags;
-  const size_t n_tr = tracing ? (size_t)spec->trace_steps * spec->trace_robots * tw : 1;
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_out = al((size_t)N * 4 * 8), b_arr = al((size_t)N * K * 4), b_start = al((size_t)N * P * 4),
-               b_wp = al((size_t)N * K * P * 4), b_nw = al((size_t)N * 4), b_path = al(std::max<size_t>(n_rec * N * P, 1) * 4),
-               b_tr = al(n_tr * 4), b_st = al((size_t)N * kGoalStateFloats * 4),
-               b_obs = al((size_t)cdiv(N, 256) * 256 * Dp * 4), b_mu = al((size_t)cdiv(N, 256) * 256 * Ap * 4);   // whole 256-row tiles
-  if (const int rc = grow_eval_buf(e, b_out + b_arr + b_start + b_wp + b_nw + b_path + b_tr + b_st + b_obs + b_mu)) return rc;
-  char* cur = e->eval_buf;
-  auto take = [&](size_t b) { char* r = cur; cur += b; return r; };
+  EvalCarve carve;
+  const size_t o_arr = carve.add((size_t)N * K * 4), o_start = carve.add((size_t)N * P * 4), o_wp = carve.add((size_t)N * K * P * 4),
+               o_nw = carve.add((size_t)N * 4), o_path = carve.add(std::max<size_t>(n_rec * N * P, 1) * 4);
   FollowArgs f{};
-  EvalArgs& a = f.e;
-  a.robot_out = reinterpret_cast<double*>(take(b_out));
-  f.arrival = reinterpret_cast<int*>(take(b_arr));
-  float* start_dev = reinterpret_cast<float*>(take(b_start));
-  float* wp_dev = reinterpret_cast<float*>(take(b_wp));
-  int* nw_dev = reinterpret_cast<int*>(take(b_nw));
-  float* path_dev = reinterpret_cast<float*>(take(b_path));
-  float* tr_dev = reinterpret_cast<float*>(take(b_tr));
-  a.st = reinterpret_cast<float*>(take(b_st));
-  a.obs = reinterpret_cast<float*>(take(b_obs));
-  float* mu = reinterpret_cast<float*>(take(b_mu));
-  a.mu = mu;
-  a.trace = tracing ? tr_dev : nullptr;
-  a.trace_robots = tracing ? spec->trace_robots : 0;
-  a.trace_steps = tracing ? spec->trace_steps : 0;
-  a.p = eval_env_params(env, A, false, INT_MAX);   // no termination, no time limit: the robot only stops at its last waypoint
-  a.N = N; a.D = D; a.Dp = Dp; a.A = A; a.Ap = Ap;
-  a.deterministic = spec->deterministic != 0;
-  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
-  const uint64_t key = spec->seed ^ kEvalKeyMix;
-  a.k0 = (uint32_t)key; a.k1 = (uint32_t)(key >> 32);
-  a.log_std = Pp(e, T_LOGSTD);
-  f.K = K; f.max_steps = spec->max_steps; f.path_stride = pathing ? spec->path_stride : 0;
+  // no termination, no time limit: the robot only stops at its last waypoint
+  if (const int rc = eval_prepare(e, c, eval_env_params(env, e->A, false, INT_MAX), carve, f.e)) return rc;
+  float* start_dev = eval_at<float>(e, o_start);
+  float* wp_dev = eval_at<float>(e, o_wp);
+  int* nw_dev = eval_at<int>(e, o_nw);
+  float* path_dev = eval_at<float>(e, o_path);
+  f.arrival = eval_at<int>(e, o_arr);
+  f.K = K; f.path_stride = pathing ? spec->path_stride : 0;
   f.start = start_dev; f.wp = wp_dev; f.nwp = nw_dev;
   f.path = pathing ? path_dev : nullptr;
   HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(wp_dev, waypoints, (size_t)N * K * P * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(nw_dev, nw.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemsetAsync(f.arrival, 0xFF, (size_t)N * K * 4, e->stream));   // -1: not reached
-  if (tracing) HIPC(hipMemsetAsync(tr_dev, 0, n_tr * 4, e->stream));
-  const char* pe = getenv("MOBROB_EVAL_PERSISTENT");   // 0: the per-step path on every engine (A/B, tests); read per call
-  const bool persistent = e->fused.enabled && e->fused.H == 64 && !(pe && atoi(pe) == 0);
-  if (persistent) {
-    Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
-    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_follow64_goal<DPc>), dim3(cdiv(N, 16)), dim3(64), eval64_lds_bytes(Dp), e->stream, f, W));
-    HIPC(hipGetLastError());
-  } else {
-    hipLaunchKernelGGL(k_follow_goal_init, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, f);
-    for (int t = 0; t < spec->max_steps; ++t) {
-      for (int s = 0; s < N; s += e->rows_max) {
-        const int c = std::min(e->rows_max, N - s);
-        forward(e, a.obs + (size_t)s * Dp, c, true, mu + (size_t)s * Ap, false, nullptr);
-      }
-      hipLaunchKernelGGL(k_follow_goal_step, dim3(cdiv(N, 256)), dim3(256), 256 * 33 * sizeof(float), e->stream, f, t);
-    }
-    hipLaunchKernelGGL(k_follow_goal_fin, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, f);
-    HIPC(hipGetLastError());
-  }
-  HIPC(hipMemcpyAsync(robot_out, a.robot_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
+  const int ran = eval_run<FollowTask>(e, f, k_follow_goal_fin);
+  if (ran < 0) return ran;
   HIPC(hipMemcpyAsync(arrival, f.arrival, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
   if (pathing) HIPC(hipMemcpyAsync(path_out, path_dev, n_rec * N * P * 4, hipMemcpyDeviceToHost, e->stream));
-  if (tracing) HIPC(hipMemcpyAsync(trace_out, tr_dev, n_tr * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPC(hipStreamSynchronize(e->stream));
-  return persistent ? 1 : 0;
+  return eval_copy_back(e, c, f.e, robot_out, ran);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -7,11 +7,10 @@
 // kept; goal_advance measures progress against the goal in force).  At most one waypoint advances per step; after the last one the
 // robot idles.  Observation noise and sampled actions come from the evaluation's streams (kernels_eval.h), keyed by the seed.
 //
-//   k_follow_goal_init  start state, first observation                                        (per-step path, one launch)
-//   k_follow_goal_step  clip / sample, env.step, waypoint bookkeeping, path, trace, next obs    (per-step path, one launch per step)
+// FollowTask plugs these rules into the task kernels of kernels_eval.h (k_goal_task_init / k_goal_task_step on the per-step path,
+// k_goal64_tile for 2x64 tanh actors: the exit ballot is over the tile's unfinished robots).  One kernel is the task's own:
+//
 //   k_follow_goal_fin   robot_out and the path records of robots that finished early           (per-step path, one launch)
-//   k_follow64_goal<DP> everything in one launch for 2x64 tanh actors: k_eval64_goal's tile (eval64_load_actor /
-//                       eval64_actor_step) with the follow env phase; the exit ballot is over the tile's unfinished robots
 #pragma once
 #include "kernels_eval.h"
 
@@ -21,7 +20,7 @@ struct FollowArgs {
   EvalArgs e;          // env parameters (no time limit, terminate_on_goal 0), dims, streams, trace and per-step buffers;
                        // e.robot_out [N][4]: reward sum, steps run, waypoints reached, final distance to the waypoint in force
   int K;               // waypoint row stride
-  int max_steps, path_stride;
+  int path_stride;     // e.max_steps is the run's step cap
   const float* start;  // [N][P]
   const float* wp;     // [N][K][P]
   const int* nwp;      // [N] waypoints of robot n (<= K)
@@ -68,14 +67,7 @@ __device__ __forceinline__ void follow_start(GoalState& g, FollowRobot& R, const
 __device__ __forceinline__ bool follow_env_step(GoalState& g, FollowRobot& R, const FollowArgs& f, int n, int t, const float* act,
                                                 const float* obs_row) {
   const EvalArgs& a = f.e;
-  float* tr_row = nullptr;
-  if (a.trace && n < a.trace_robots && t < a.trace_steps) {
-    tr_row = a.trace + ((size_t)t * a.trace_robots + n) * eval_trace_width(a);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { tr_row[j] = g.pos[j]; tr_row[3 + j] = g.vel[j]; tr_row[6 + j] = g.goal[j]; }
-    for (int c = 0; c < a.D; ++c) tr_row[9 + c] = obs_row[c];
-    for (int k = 0; k < a.A; ++k) tr_row[9 + a.D + k] = act[k];
-  }
+  float* fl = eval_trace_row(g, a, n, t, act, obs_row);
   const int k_before = R.k;
   const GoalOutcome o = goal_advance(g, a.p, act, a.A);
   R.steps += 1;
@@ -86,8 +78,7 @@ __device__ __forceinline__ bool follow_env_step(GoalState& g, FollowRobot& R, co
     if (R.k < R.nwp) follow_set_goal(g, f, n, R.k);
   }
   const bool going = R.k < R.nwp;
-  if (tr_row) {
-    float* fl = tr_row + 9 + a.D + a.A;
+  if (fl) {
     fl[0] = o.reward; fl[1] = o.reached ? 1.f : 0.f; fl[2] = (float)k_before; fl[3] = going ? 0.f : 1.f;
   }
   if (f.path && (t + 1) % f.path_stride == 0) follow_path_store(f, (t + 1) / f.path_stride, n, g);
@@ -100,7 +91,7 @@ __device__ __forceinline__ void follow_finish(const FollowArgs& f, int n, const 
   o[0] = R.ret_sum; o[1] = (double)R.steps; o[2] = (double)R.k;
   o[3] = R.nwp > 0 ? (double)goal_dist(g.goal, g.pos, f.e.p.P) : __longlong_as_double(0x7FF8000000000000ll);
   if (f.path)
-    for (int r = R.steps / f.path_stride + 1; r <= f.max_steps / f.path_stride; ++r) follow_path_store(f, r, n, g);
+    for (int r = R.steps / f.path_stride + 1; r <= f.e.max_steps / f.path_stride; ++r) follow_path_store(f, r, n, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -115,79 +106,26 @@ __device__ __forceinline__ void follow_robot_store(const FollowArgs& f, int n, c
   o[0] = R.ret_sum; o[1] = (double)R.steps; o[2] = (double)R.k;
 }
 
-__global__ __launch_bounds__(256) void k_follow_goal_init(FollowArgs f) {
-  const EvalArgs& a = f.e;
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= a.N) return;
-  GoalState g;
-  FollowRobot R;
-  follow_start(g, R, f, n);
-  goal_store(a.st + (size_t)n * kGoalStateFloats, g);
-  follow_robot_store(f, n, R);
-  for (int c = 0; c < a.Dp / 4; ++c) reinterpret_cast<f32x4*>(a.obs)[(size_t)n * (a.Dp / 4) + c] = eval_features(g, a, n, c, 0u);
-}
-
-__global__ __launch_bounds__(256) void k_follow_goal_step(FollowArgs f, int t) {
-  const EvalArgs& a = f.e;
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= a.N) return;
-  FollowRobot R = follow_robot_load(f, n);
-  if (R.k >= R.nwp) return;   // finished: idles
-  GoalState g = goal_load(a.st + (size_t)n * kGoalStateFloats);
-  float* act = &lds[threadIdx.x * 33];   // [256][33]: the thread's clipped actions (LDS, not a dynamically indexed register array)
-  eval_actions(a, n, t, a.mu + (size_t)n * a.Ap, act);
-  (void)follow_env_step(g, R, f, n, t, act, a.obs + (size_t)n * a.Dp);
-  goal_store(a.st + (size_t)n * kGoalStateFloats, g);
-  follow_robot_store(f, n, R);
-  for (int c = 0; c < a.Dp / 4; ++c)
-    reinterpret_cast<f32x4*>(a.obs)[(size_t)n * (a.Dp / 4) + c] = eval_features(g, a, n, c, (uint32_t)t + 1u);
-}
+// waypoint following as a task
+struct FollowTask {
+  using Args = FollowArgs;
+  using Robot = FollowRobot;
+  static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& f) { return f.e; }
+  static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& f, int n) { follow_start(g, R, f, n); }
+  static __device__ __forceinline__ bool active(const Args&, const Robot& R) { return R.k < R.nwp; }
+  static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& f, int n, int t, const float* act,
+                                              const float* obs_row) {
+    return follow_env_step(g, R, f, n, t, act, obs_row);
+  }
+  static __device__ __forceinline__ void finish(const Args& f, int n, const Robot& R, const GoalState& g) { follow_finish(f, n, R, g); }
+  static __device__ __forceinline__ Robot load(const Args& f, int n) { return follow_robot_load(f, n); }
+  static __device__ __forceinline__ void store(const Args& f, int n, const Robot& R) { follow_robot_store(f, n, R); }
+};
 
 __global__ __launch_bounds__(256) void k_follow_goal_fin(FollowArgs f) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= f.e.N) return;
   follow_finish(f, n, follow_robot_load(f, n), goal_load(f.e.st + (size_t)n * kGoalStateFloats));
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_follow64_goal<DP>: the persistent path for 2x64 tanh actors.  k_eval64_goal's tile (one wave, 16 robots, the actor in LDS in
-// 16x16x4 fragment order, the forward of eval64_actor_step); what differs is the start (from `start` / wp[0] instead of
-// eval_reset0), the env phase (follow_env_step: no reset; arrival, next waypoint from global memory) and the exit ballot (over the
-// tile's unfinished robots).
-// ------------------------------------------------------------------------------------------------
-template <int DP>
-__global__ __launch_bounds__(64) void k_follow64_goal(FollowArgs f, Eval64Net W) {
-  using L = LayEval64<DP>;
-  const EvalArgs& a = f.e;
-  const int lane = threadIdx.x;
-  const int r16 = lane & 15;
-  const int row0 = blockIdx.x * 16;
-  eval64_load_actor<DP>(W, a.D, a.A, lane);
-  const int n = row0 + r16;
-  const bool mine = lane < 16 && n < a.N;
-  GoalState g{};
-  FollowRobot R{0.0, 0, 0, 0};
-  bool going = false;
-  if (mine) {
-    follow_start(g, R, f, n);
-    going = R.k < R.nwp;
-    eval64_state_lds(&lds[L::ST + 12 * r16], g);
-  }
-  __syncthreads();
-  const bool wide_head = a.A > 16;
-  for (int t = 0; t < f.max_steps; ++t) {
-    if (__ballot(going) == 0ull) break;   // one wave per workgroup: uniform
-    eval64_actor_step<DP>(a, row0, t, lane, wide_head);
-    // ---- env phase: the tile's 16 lanes ----
-    if (mine && going) {
-      float* act = &lds[L::MU + r16 * L::LDM];   // the mean row becomes the applied action in place
-      eval_actions(a, n, t, act, act);
-      going = follow_env_step(g, R, f, n, t, act, &lds[L::X + r16 * L::LDX]);
-      eval64_state_lds(&lds[L::ST + 12 * r16], g);
-    }
-    __syncthreads();
-  }
-  if (mine) follow_finish(f, n, R, g);
 }
 
 }  // namespace mobrob

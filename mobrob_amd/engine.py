@@ -349,6 +349,22 @@ class PPOEngine:
                 g.mix[j][k] = float(mix[j, k])
         return g
 
+    def _eval_spec_common(self, what, sp, max_steps, deterministic, seed, trace):
+        """What evaluate_goal_env and follow_waypoints fill alike in their spec (max_steps, deterministic, seed, trace sizes), after
+        refusing sampled actions of a gSDE policy.  Returns the trace buffer, or None without a trace."""
+        if self.use_sde and not deterministic:
+            raise ValueError(f"{what}: stochastic actions of a use_sde (gSDE) policy are not supported; use deterministic=True")
+        sp.max_steps, sp.deterministic, sp.seed = int(max_steps), int(bool(deterministic)), int(seed) & (2 ** 64 - 1)
+        sp.trace_robots, sp.trace_steps = (0, 0) if trace is None else (int(trace[0]), int(trace[1]))
+        if trace is None:
+            return None
+        return np.zeros((max(sp.trace_steps, 1), max(sp.trace_robots, 1), 9 + self.D + self.A + 4), F32)
+
+    @staticmethod
+    def _eval_result(robot, r):
+        """The keys both calls return from robot_out's first two columns and the C call's return value."""
+        return {"reward_sum": robot[:, 0], "steps": robot[:, 1].astype(np.int64), "persistent": bool(r == 1)}
+
     def evaluate_goal_env(self, pos_dim, mix, time_limit=0, terminate_on_goal=True, dt=0.05, extent=3.0, reach_radius=0.3,
                           goal_bonus=5.0, extra_bonus=0.0, obs_noise=0.1, *, n_robots, max_steps=1000, episodes=0, quota=None,
                           deterministic=True, seed=0, trace=None):
@@ -359,15 +375,11 @@ class PPOEngine:
         episode_success ([n_robots][max quota], NaN past an unfinished quota); trace ([steps][robots][9 + D + A + 4]) and
         `persistent` (which kernel path ran)."""
         n = int(n_robots)
-        if self.use_sde and not deterministic:
-            raise ValueError("evaluate_goal_env: stochastic actions of a use_sde (gSDE) policy are not supported; use deterministic=True")
+        sp = EvalSpec()
+        tr = self._eval_spec_common("evaluate_goal_env", sp, max_steps, deterministic, seed, trace)
         g = self._goal_env_struct(pos_dim, mix, time_limit, terminate_on_goal, dt, extent, reach_radius, goal_bonus, extra_bonus,
                                   obs_noise)
-        sp = EvalSpec()
-        sp.n_robots, sp.max_steps, sp.episodes, sp.deterministic = n, int(max_steps), int(episodes), int(bool(deterministic))
-        sp.seed = int(seed) & (2 ** 64 - 1)
-        tr_r, tr_s = (0, 0) if trace is None else (int(trace[0]), int(trace[1]))
-        sp.trace_robots, sp.trace_steps = tr_r, tr_s
+        sp.n_robots, sp.episodes = n, int(episodes)
         if quota is not None:
             q = np.ascontiguousarray(quota, dtype=np.int32)
             if q.shape != (max(n, 0),):
@@ -379,16 +391,15 @@ class PPOEngine:
         maxq = int(q.max()) if q.size else 0
         robot = np.zeros((max(n, 1), 4), np.float64)
         ep = np.zeros((max(n, 1), max(maxq, 1), 3), np.float64)
-        tr = np.zeros((max(tr_s, 1), max(tr_r, 1), 9 + self.D + self.A + 4), F32) if trace is not None else None
         dp = C.POINTER(C.c_double)
         r = check(self.lib.mobrob_ppo_evaluate_goal_env(self._h, C.byref(g), C.byref(sp), q.ctypes.data_as(C.POINTER(C.c_int32)),
                                                          robot.ctypes.data_as(dp), ep.ctypes.data_as(dp), _fp(tr)))
         ep = ep[:, :maxq]
         done = np.arange(maxq)[None, :] < np.minimum(robot[:, 2:3], q[:, None])
-        out = {"reward_sum": robot[:, 0], "steps": robot[:, 1].astype(np.int64), "episodes": robot[:, 2].astype(np.int64),
-               "goals": robot[:, 3].astype(np.int64), "quota": q,
-               "episode_returns": np.where(done, ep[:, :, 0], np.nan), "episode_lengths": np.where(done, ep[:, :, 1], np.nan),
-               "episode_success": np.where(done, ep[:, :, 2], np.nan), "persistent": bool(r == 1)}
+        out = self._eval_result(robot, r)
+        out.update({"episodes": robot[:, 2].astype(np.int64), "goals": robot[:, 3].astype(np.int64), "quota": q,
+                    "episode_returns": np.where(done, ep[:, :, 0], np.nan), "episode_lengths": np.where(done, ep[:, :, 1], np.nan),
+                    "episode_success": np.where(done, ep[:, :, 2], np.nan)})
         if tr is not None:
             out["trace"] = tr
         return out
@@ -404,25 +415,20 @@ class PPOEngine:
         from .waypoints import follow_inputs
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
         n, K, P = wp.shape
-        if self.use_sde and not deterministic:
-            raise ValueError("follow_waypoints: stochastic actions of a use_sde (gSDE) policy are not supported; use deterministic=True")
-        g = self._goal_env_struct(pos_dim, mix, 0, False, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise)
         sp = FollowSpec()
-        sp.n_robots, sp.max_waypoints, sp.max_steps, sp.deterministic = n, K, int(max_steps), int(bool(deterministic))
-        sp.seed = int(seed) & (2 ** 64 - 1)
-        sp.path_stride = int(path_stride)
-        tr_r, tr_s = (0, 0) if trace is None else (int(trace[0]), int(trace[1]))
-        sp.trace_robots, sp.trace_steps = tr_r, tr_s
+        tr = self._eval_spec_common("follow_waypoints", sp, max_steps, deterministic, seed, trace)
+        g = self._goal_env_struct(pos_dim, mix, 0, False, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise)
+        sp.n_robots, sp.max_waypoints, sp.path_stride = n, K, int(path_stride)
         arrival = np.empty((n, K), np.int32)
         robot = np.zeros((n, 4), np.float64)
         path = np.zeros((int(max_steps) // int(path_stride) + 1, n, P), F32) if int(path_stride) > 0 and int(max_steps) > 0 else None
-        tr = np.zeros((max(tr_s, 1), max(tr_r, 1), 9 + self.D + self.A + 4), F32) if trace is not None else None
         i32 = C.POINTER(C.c_int32)
         r = check(self.lib.mobrob_ppo_follow_waypoints(self._h, C.byref(g), C.byref(sp), _fp(s), _fp(wp), nw.ctypes.data_as(i32),
                                                         arrival.ctypes.data_as(i32), robot.ctypes.data_as(C.POINTER(C.c_double)),
                                                         _fp(path), _fp(tr)))
-        out = {"arrival": arrival.astype(np.int64), "reached": robot[:, 2].astype(np.int64), "steps": robot[:, 1].astype(np.int64),
-               "reward_sum": robot[:, 0], "final_distance": robot[:, 3], "trace": tr, "persistent": bool(r == 1)}
+        out = self._eval_result(robot, r)
+        out.update({"arrival": arrival.astype(np.int64), "reached": robot[:, 2].astype(np.int64), "final_distance": robot[:, 3],
+                    "trace": tr})
         if path is not None:
             out["path"] = path
         return out

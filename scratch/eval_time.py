@@ -42,7 +42,7 @@ def main():
                     help="write DATA_DIR/policies/doggo-ppo.zip (reference doggo weights, tests/golden) for examples/control.py and exit")
     a = ap.parse_args()
     if a.make_checkpoint:
-        from tests.test_eval_gpu import _write_checkpoint
+        from tests.util import _write_checkpoint
         _write_checkpoint(a.make_checkpoint, "doggo")
         return
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
@@ -56,13 +56,13 @@ def main():
     e64 = engine(64)
     os.environ.pop("MOBROB_EVAL_PERSISTENT", None)
     tp, rp = timed(e64, env, a.robots, a.steps, a.runs, a.warmup)
-    rows.append(("doggo 2x64 persistent (k_eval64_goal)", tp, rp))
+    rows.append(("doggo 2x64 persistent (k_goal64_tile<EvalTask>)", tp, rp))
     os.environ["MOBROB_EVAL_PERSISTENT"] = "0"
     ts, rs = timed(e64, env, a.robots, a.steps, a.runs, a.warmup)
-    rows.append(("doggo 2x64 per-step (fused forward + k_eval_goal_step)", ts, rs))
+    rows.append(("doggo 2x64 per-step (fused forward + k_goal_task_step)", ts, rs))
     e256 = engine(256)
     t2, r2 = timed(e256, env, a.robots, a.steps, a.runs, a.warmup)
-    rows.append(("doggo 2x256 per-step (x3 forward + k_eval_goal_step)", t2, r2))
+    rows.append(("doggo 2x256 per-step (x3 forward + k_goal_task_step)", t2, r2))
     os.environ.pop("MOBROB_EVAL_PERSISTENT", None)
     print(f"{a.robots} robots x {a.steps} steps, control.py protocol (no time limit, reset on goal), median of {a.runs} after {a.warmup} warm-up")
     for name, t, r in rows:

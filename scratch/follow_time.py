@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Wall time of one device waypoint-following call (mobrob_ppo_follow_waypoints) of 4096 robots x 1000 steps at doggo 2x64:
-the persistent kernel (k_follow64_goal), the per-step path (MOBROB_EVAL_PERSISTENT=0) and, for comparison at the same shape,
-one evaluation (k_eval64_goal, control.py protocol).  The host loop (mobrob_amd.waypoints, one predict per robot and step) runs
+the persistent kernel (k_goal64_tile<FollowTask>), the per-step path (MOBROB_EVAL_PERSISTENT=0) and, for comparison at the same shape,
+one evaluation (k_goal64_tile<EvalTask>, control.py protocol).  The host loop (mobrob_amd.waypoints, one predict per robot and step) runs
 for --host-robots robots and is extrapolated to 4096 (labelled as such).  Every robot follows a 4-corner square far enough from
 its start that no robot finishes early with this untrained actor, so every call runs the full 1000 steps.  The calls are
 synchronous (they return after the results are copied out); median of --runs after --warmup.
@@ -59,12 +59,12 @@ def main():
     rows = []
     os.environ.pop("MOBROB_EVAL_PERSISTENT", None)
     tp, rp = timed(follow, a.runs, a.warmup)
-    rows.append(("follow, persistent (k_follow64_goal)", tp, rp))
+    rows.append(("follow, persistent (k_goal64_tile<FollowTask>)", tp, rp))
     te, re_ = timed(lambda: env.evaluate(e64, n_robots=a.robots, max_steps=a.steps, episodes=0, seed=1), a.runs, a.warmup)
-    rows.append(("evaluate, persistent (k_eval64_goal), same shape", te, re_))
+    rows.append(("evaluate, persistent (k_goal64_tile<EvalTask>), same shape", te, re_))
     os.environ["MOBROB_EVAL_PERSISTENT"] = "0"
     ts, rs = timed(follow, max(1, a.runs // 2), 1)
-    rows.append(("follow, per-step (fused forward + k_follow_goal_step)", ts, rs))
+    rows.append(("follow, per-step (fused forward + k_goal_task_step)", ts, rs))
     os.environ.pop("MOBROB_EVAL_PERSISTENT", None)
 
     class _Predict:   # the same engine behind PPO.predict's call shape

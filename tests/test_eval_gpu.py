@@ -8,55 +8,11 @@ import pytest
 
 from oracle import ppo_oracle as O
 from tests.eval_model import goal_advance, trace_fields
+from tests.util import EVAL_CASES as CASES, EVAL_IDS as IDS, _engine, _env, _go_to_goal_params, _snapshot, _write_checkpoint, persistent_env  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# (name, robot, engine kwargs, MOBROB_EVAL_PERSISTENT, persistent path expected)
-CASES = [
-    ("doggo64", "doggo", dict(pi=(64, 64), vf=(64, 64)), None, True),
-    ("point64", "point", dict(pi=(64, 64), vf=(64, 64)), None, True),
-    ("doggo256", "doggo", dict(pi=(256, 256), vf=(256, 256)), None, False),
-    ("elu3x32", "point", dict(pi=(32, 32, 32), vf=(32, 32, 32), activation="elu"), None, False),
-    ("sde64", "point", dict(pi=(64, 64), vf=(64, 64), use_sde=True), None, False),
-    ("doggo64_perstep", "doggo", dict(pi=(64, 64), vf=(64, 64)), "0", False),
-]
-IDS = [c[0] for c in CASES]
-
-
-@pytest.fixture
-def persistent_env(monkeypatch):
-    def set_(v):
-        if v is None:
-            monkeypatch.delenv("MOBROB_EVAL_PERSISTENT", raising=False)
-        else:
-            monkeypatch.setenv("MOBROB_EVAL_PERSISTENT", v)
-    return set_
-
-
-def _engine(robot, kw, n_envs=16, seed=3, scale=1.0):
-    from mobrob_amd.engine import PPOEngine
-    from mobrob_amd.envs.wrapper import ROBOT_DIMS
-    D, A, _ = ROBOT_DIMS[robot]
-    e = PPOEngine(obs_dim=D, act_dim=A, n_envs=n_envs, n_steps=16, batch_size=64, n_epochs=2, seed=seed, **kw)
-    rng = np.random.default_rng(seed)
-    p = e.get_params()
-    for k, v in p.items():
-        if k == "log_std":
-            p[k] = np.full_like(v, -0.5)
-        elif v.ndim == 2:
-            p[k] = (scale * rng.standard_normal(v.shape) / np.sqrt(v.shape[1])).astype(np.float32)
-        else:
-            p[k] = (0.1 * rng.standard_normal(v.shape)).astype(np.float32)
-    e.set_params(p)
-    return e, p
-
-
-def _env(robot, n, tl, seed=5):
-    from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
-    return DeviceGoalVecEnv.for_robot(robot, n, time_limit=tl, seed=seed)
-
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_teacher_forced_trace(case, persistent_env):
@@ -165,17 +121,6 @@ def test_determinism(case, persistent_env):
     e.close()
 
 
-def _snapshot(e):
-    s = {k: e.read(k) for k in ("obs", "actions", "rewards", "values", "log_probs", "episode_starts")}
-    m, v, step = e.get_optimizer_state()
-    s["params"], s["m"], s["v"], s["step"] = e.get_flat_params(), e.flatten(m), e.flatten(v), step
-    st = e.episode_stats(reset=False)
-    s["stats_counts"] = np.array([st["episodes"], st["goals"]])
-    s["stats_means"] = np.array([st["ep_rew_mean"], st["ep_len_mean"]])
-    s["env_state"] = e.read("env_state")
-    return s
-
-
 @pytest.mark.parametrize("case", [CASES[0], CASES[3], CASES[4], CASES[2]], ids=["fused64", "generic_elu", "generic_sde", "x3_256"])
 def test_evaluation_does_not_interfere_with_training(case, persistent_env):
     name, robot, kw, pe, _ = case
@@ -230,29 +175,6 @@ def test_persistent_and_per_step_paths_agree(persistent_env):
     e.close()
 
 
-def _go_to_goal_params(e, env, zero=False):
-    """A near-linear tanh actor: h1 = tanh(s * unit), h2 = tanh(h1), mean = pinv(mix) . unit (times a gain)."""
-    p = e.get_params()
-    for k in p:
-        p[k] = np.zeros_like(p[k])
-    P = env.pos_dim
-    s = 0.1
-    W1 = np.zeros_like(p["mlp_extractor.policy_net.0.weight"])
-    W2 = np.zeros_like(p["mlp_extractor.policy_net.2.weight"])
-    for j in range(P):
-        W1[j, j] = s
-        W2[j, j] = 1.0
-    p["mlp_extractor.policy_net.0.weight"] = W1
-    p["mlp_extractor.policy_net.2.weight"] = W2
-    Wa = np.zeros_like(p["action_net.weight"])
-    if not zero:   # command mix . a = unit vector to the goal (speed 1)
-        gain = 1.0 / np.tanh(np.tanh(s))
-        Wa[:, :P] = (gain * np.linalg.pinv(env.mix.astype(np.float64))).astype(np.float32)
-    p["action_net.weight"] = Wa
-    p["log_std"] = np.full_like(p["log_std"], -1.0)
-    e.set_params(p)
-
-
 def test_a_policy_that_solves_the_task_scores_as_one():
     from mobrob_amd.evaluation import evaluate_episodes, evaluate_policy
     from mobrob_amd.envs.vec_env import HostVecEnv, make_vec_env
@@ -304,16 +226,6 @@ def test_eval_callback_end_to_end(tmp_path):
     cb2 = EvalCallback(eval_env, callback_on_new_best=stop, n_eval_episodes=4, eval_freq=32, verbose=0)
     model2.learn(total_timesteps=16 * 32 * 10, callback=cb2)
     assert model2.num_timesteps == 16 * 32 < 16 * 32 * 10
-
-
-def _write_checkpoint(data_dir, robot):
-    """data/policies/<robot>-ppo.zip with the reference checkpoint's weights (tests/golden/<robot>.npz)."""
-    from mobrob_amd.rl_control.ppo import PPO
-    from tests.util import golden_params, load_golden
-    model = PPO(env=_env(robot, 16, tl=1000), n_steps=16, batch_size=64, seed=0)
-    model.engine.set_params(golden_params(load_golden(robot)))
-    os.makedirs(os.path.join(data_dir, "policies"), exist_ok=True)
-    model.save(os.path.join(data_dir, "policies", f"{robot}-ppo.zip"))
 
 
 def test_control_cli_robots(tmp_path):

@@ -3,6 +3,7 @@ import os
 from collections import OrderedDict
 
 import numpy as np
+import pytest
 
 from oracle import ppo_oracle as O
 
@@ -112,3 +113,93 @@ def sde_case(name):
     h = O.Hyper(clip_range=clip, ent_coef=ent, vf_coef=vfc, max_grad_norm=mgn, learning_rate=lr, adam_eps=eps, activation=act,
                 batch_size=100, n_epochs=1, use_sde=True, sde_use_expln=bool(c["use_expln"]))
     return c, act, pi, vf, p, h
+
+
+# ---- GPU tests of the evaluation family (test_eval_gpu.py, test_follow_gpu.py) ----
+# (name, robot, engine kwargs, MOBROB_EVAL_PERSISTENT, persistent path expected)
+EVAL_CASES = [
+    ("doggo64", "doggo", dict(pi=(64, 64), vf=(64, 64)), None, True),
+    ("point64", "point", dict(pi=(64, 64), vf=(64, 64)), None, True),
+    ("doggo256", "doggo", dict(pi=(256, 256), vf=(256, 256)), None, False),
+    ("elu3x32", "point", dict(pi=(32, 32, 32), vf=(32, 32, 32), activation="elu"), None, False),
+    ("sde64", "point", dict(pi=(64, 64), vf=(64, 64), use_sde=True), None, False),
+    ("doggo64_perstep", "doggo", dict(pi=(64, 64), vf=(64, 64)), "0", False),
+]
+EVAL_IDS = [c[0] for c in EVAL_CASES]
+
+
+@pytest.fixture
+def persistent_env(monkeypatch):
+    def set_(v):
+        if v is None:
+            monkeypatch.delenv("MOBROB_EVAL_PERSISTENT", raising=False)
+        else:
+            monkeypatch.setenv("MOBROB_EVAL_PERSISTENT", v)
+    return set_
+
+
+def _engine(robot, kw, n_envs=16, seed=3, scale=1.0):
+    from mobrob_amd.engine import PPOEngine
+    from mobrob_amd.envs.wrapper import ROBOT_DIMS
+    D, A, _ = ROBOT_DIMS[robot]
+    e = PPOEngine(obs_dim=D, act_dim=A, n_envs=n_envs, n_steps=16, batch_size=64, n_epochs=2, seed=seed, **kw)
+    rng = np.random.default_rng(seed)
+    p = e.get_params()
+    for k, v in p.items():
+        if k == "log_std":
+            p[k] = np.full_like(v, -0.5)
+        elif v.ndim == 2:
+            p[k] = (scale * rng.standard_normal(v.shape) / np.sqrt(v.shape[1])).astype(np.float32)
+        else:
+            p[k] = (0.1 * rng.standard_normal(v.shape)).astype(np.float32)
+    e.set_params(p)
+    return e, p
+
+
+def _env(robot, n, tl=0, seed=5):
+    from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
+    return DeviceGoalVecEnv.for_robot(robot, n, time_limit=tl, seed=seed)
+
+
+def _snapshot(e, stats=True):
+    s = {k: e.read(k) for k in ("obs", "actions", "rewards", "values", "log_probs", "episode_starts")}
+    m, v, step = e.get_optimizer_state()
+    s["params"], s["m"], s["v"], s["step"] = e.get_flat_params(), e.flatten(m), e.flatten(v), step
+    if stats:
+        st = e.episode_stats(reset=False)
+        s["stats_counts"] = np.array([st["episodes"], st["goals"]])
+        s["stats_means"] = np.array([st["ep_rew_mean"], st["ep_len_mean"]])
+    s["env_state"] = e.read("env_state")
+    return s
+
+
+def _go_to_goal_params(e, env, zero=False):
+    """A near-linear tanh actor: h1 = tanh(s * unit), h2 = tanh(h1), mean = pinv(mix) . unit (times a gain)."""
+    p = e.get_params()
+    for k in p:
+        p[k] = np.zeros_like(p[k])
+    P = env.pos_dim
+    s = 0.1
+    W1 = np.zeros_like(p["mlp_extractor.policy_net.0.weight"])
+    W2 = np.zeros_like(p["mlp_extractor.policy_net.2.weight"])
+    for j in range(P):
+        W1[j, j] = s
+        W2[j, j] = 1.0
+    p["mlp_extractor.policy_net.0.weight"] = W1
+    p["mlp_extractor.policy_net.2.weight"] = W2
+    Wa = np.zeros_like(p["action_net.weight"])
+    if not zero:   # command mix . a = unit vector to the goal (speed 1)
+        gain = 1.0 / np.tanh(np.tanh(s))
+        Wa[:, :P] = (gain * np.linalg.pinv(env.mix.astype(np.float64))).astype(np.float32)
+    p["action_net.weight"] = Wa
+    p["log_std"] = np.full_like(p["log_std"], -1.0)
+    e.set_params(p)
+
+
+def _write_checkpoint(data_dir, robot):
+    """data/policies/<robot>-ppo.zip with the reference checkpoint's weights (tests/golden/<robot>.npz)."""
+    from mobrob_amd.rl_control.ppo import PPO
+    model = PPO(env=_env(robot, 16, tl=1000), n_steps=16, batch_size=64, seed=0)
+    model.engine.set_params(golden_params(load_golden(robot)))
+    os.makedirs(os.path.join(data_dir, "policies"), exist_ok=True)
+    model.save(os.path.join(data_dir, "policies", f"{robot}-ppo.zip"))
