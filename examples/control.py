@@ -14,7 +14,8 @@ from the two are comparable (last row):
 `--robots N` runs the same protocol for max(N, epochs) robots at once on the device goal environment (the kinematic
 stand-in stepped by the engine, no time limit, reset on goal): ONE engine call instead of one `predict` round trip per robot
 and step.  Each robot is one epoch: the `rewards` line lists max(N, epochs) figures.  Without `--robots` the script runs the
-host loop above, exactly as before.
+host loop above, exactly as before.  With `--robots`, `--hazards FILE.npy` ([M][2] hazard centres, radius 0.3, the reference
+Engine's shaped hazard cost) adds three lines: the mean cost per robot, the violation rate and the minimum clearance.
 
 GUI rendering, the 5 ms sleep that paces the Bullet GUI and video recording (:24-33, :48-52) need the real MuJoCo / Bullet
 simulators; the kinematic stand-in robots have nothing to draw, so `--no-gui` / `--video-path` are accepted and ignored.
@@ -57,18 +58,24 @@ def simulate(env_name, policy_name="ppo", epochs=5, no_gui=True, video_path=None
     return rewards
 
 
-def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None, seed=0):
+def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None, seed=0, hazards=None):
     """The protocol of `simulate` for max(robots, epochs) robots in one device evaluation (PPOEngine.evaluate_goal_env)."""
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
     policy = load_policy(env_name, policy_name) if policy is None else policy
     n = max(int(robots), int(epochs))
     env = DeviceGoalVecEnv.for_robot(env_name, n, time_limit=0, seed=seed, terminate_on_goal=True)
-    r = env.evaluate(policy.engine, n_robots=n, max_steps=STEPS_PER_EPOCH, episodes=0, deterministic=True)
+    from mobrob_amd.envs.goal_rules import Hazards
+    hz = None if hazards is None else Hazards(hazards, indicator=False)
+    r = env.evaluate(policy.engine, n_robots=n, max_steps=STEPS_PER_EPOCH, episodes=0, deterministic=True, hazards=hz)
     rewards = [float(x) for x in r["reward_sum"]]
     print(f"average reward: {np.mean(rewards)}")
     print(f"reward stds: {np.std(rewards)}")
     print(f"rewards: {rewards}")
+    if hz is not None:
+        print(f"mean hazard cost: {float(np.mean(r['cost_sum']))}")
+        print(f"violation rate: {float(np.mean(r['violation_steps'] > 0))}")
+        print(f"minimum clearance: {float(np.min(r['min_clearance']))}")
     return rewards
 
 
@@ -81,8 +88,12 @@ if __name__ == "__main__":
     ap.add_argument("--video-path", type=str, default=None)
     ap.add_argument("--robots", type=int, default=None,
                     help="evaluate max(ROBOTS, epochs) robots at once on the device (one engine call)")
+    ap.add_argument("--hazards", type=str, default=None, help="[M][2] hazard centres (.npy), with --robots: report hazard costs")
     a = ap.parse_args()
+    if a.hazards is not None and a.robots is None:
+        ap.error("--hazards needs --robots (the device evaluation)")
     if a.robots is not None:
-        simulate_device(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, robots=a.robots)
+        simulate_device(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, robots=a.robots,
+                        hazards=None if a.hazards is None else np.load(a.hazards))
         sys.exit(0)
     simulate(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, no_gui=a.no_gui, video_path=a.video_path)

@@ -12,6 +12,10 @@ By default all robots run in ONE device call (DeviceGoalVecEnv, the kinematic st
 the same semantics as a Python loop over `get_env(...)` with one `predict` per robot and step.  Three report lines: the success
 rate (all waypoints reached), the mean number of waypoints reached, and the mean arrival step of the last waypoint over the
 robots that reached it (nan if none did).
+
+`--hazards FILE.npy` ([M][2] hazard centres; `--hazard-size R`, default 0.3) adds the reference Engine's hazard cost (shaped,
+coefficient 1) and three more lines: the mean cost per robot, the violation rate (robots that entered a hazard) and the minimum
+clearance (distance to the nearest hazard boundary) over all robots and steps.
 """
 import argparse
 import os
@@ -22,9 +26,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None):
+def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None):
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
+    from mobrob_amd.envs.goal_rules import Hazards
     from mobrob_amd.envs.wrapper import ROBOT_DIMS, KinematicSim
     from mobrob_amd.waypoints import follow_waypoints
     policy = load_policy(env_name, policy_name) if policy is None else policy
@@ -32,14 +37,24 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     extent = KinematicSim(d, a, p).extent
     start = np.random.default_rng(seed).uniform(-extent / 2, extent / 2, (int(robots), p))   # the env's init_space
     env = env_name if host else DeviceGoalVecEnv.for_robot(env_name, int(robots), time_limit=0, seed=seed)
-    r = follow_waypoints(policy, env, start, waypoints, max_steps=max_steps, deterministic=True, seed=seed)
+    hz = None if hazards is None else Hazards(hazards[0], hazards[1], indicator=False)
+    r = follow_waypoints(policy, env, start, waypoints, max_steps=max_steps, deterministic=True, seed=seed, hazards=hz)
     K = r["arrival"].shape[1]
     done = r["reached"] == K
     last = r["arrival"][done, K - 1]
     print(f"success rate: {float(np.mean(done))}")
     print(f"mean waypoints reached: {float(np.mean(r['reached']))}")
     print(f"mean arrival step of the last waypoint: {float(np.mean(last)) if last.size else float('nan')}")
+    if hz is not None:
+        report_hazards(r)
     return r
+
+
+def report_hazards(r):
+    """The three hazard lines: mean cost per robot, violation rate (robots with a step of cost > 0), minimum clearance."""
+    print(f"mean hazard cost: {float(np.mean(r['cost_sum']))}")
+    print(f"violation rate: {float(np.mean(r['violation_steps'] > 0))}")
+    print(f"minimum clearance: {float(np.nanmin(r['min_clearance'])) if np.any(r['steps'] > 0) else float('nan')}")
 
 
 if __name__ == "__main__":
@@ -51,5 +66,8 @@ if __name__ == "__main__":
     ap.add_argument("--max-steps", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--host", action="store_true", default=False, help="the Python loop over get_env instead of one device call")
+    ap.add_argument("--hazards", type=str, default=None, help="[M][2] hazard centres (.npy): report hazard costs")
+    ap.add_argument("--hazard-size", type=float, default=0.3, help="hazard radius (hazards_size)")
     args = ap.parse_args()
-    follow(args.env_name, args.policy_name, np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed)
+    follow(args.env_name, args.policy_name, np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed,
+           hazards=None if args.hazards is None else (np.load(args.hazards), args.hazard_size))

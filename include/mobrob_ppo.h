@@ -505,6 +505,48 @@ int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t*
                                 const int32_t* n_waypoints /* [n] or NULL = K */, int32_t* arrival /* [n][K], -1 = not reached */,
                                 double* robot_out /* [n][4] */, float* path_out /* or NULL */, float* trace_out /* or NULL */);
 
+/* ---- hazard costs: the reference Engine's constrain_hazards rule on evaluation and waypoint following ----------------------
+ * Hazards are circles on the floor (vertical cylinders; src/mobrob/envs/mujoco_robots/robots/engine.py: config :230-244, rule
+ * :1329-1345, dist_xy :1037-1043).  After every env step, at the robot's new position p (before any reset), over the hazards
+ * (x, y, r) of the robot's scene:
+ *   d_h = |p_xy - h_xy| (x and y only, every robot, the 3-D drone included); cost = sum over d_h <= r_h of cost * (r_h - d_h);
+ *   indicator: cost = (cost > 0).  A hazard exactly on whose boundary the robot stands contributes 0.  clearance = min_h (d_h - r_h),
+ *   +inf for an empty scene.  The cost never changes dynamics, reward, reaching, termination or reset.
+ *   Distances are float32 with a correctly rounded sqrt; the step cost is summed in float over four partial sums (hazards
+ *   h = q mod 4) combined as (p0 + p1) + (p2 + p3), the same bits on both kernel paths.
+ * mobrob_ppo_evaluate_goal_env_hazards / mobrob_ppo_follow_waypoints_hazards return what their counterparts return, in the same
+ * arrays with the same meaning, streams and checks, and in addition:
+ *   hazard_out [n_robots][4] doubles: cost summed in float64 over the steps run, steps with cost > 0, the first such step
+ *             (1-based, as arrival) or -1, minimum clearance over every post-step position (+inf for an empty scene, NaN for a
+ *             robot that ran no step).
+ *   episode_cost_out [n_robots][max quota] doubles, or NULL (evaluate only): the cost of each recorded episode, beside episode_out.
+ *   trace_out the counterpart's row plus two floats, the step's cost and clearance: width 9 + obs_dim + act_dim + 4 + 2.
+ *   kernels   k_goal64_tile<DP, HazardTask<...>> (the check on all 64 lanes: four per robot; a shared scene staged in LDS) or the
+ *             per-step path with k_goal_task_step<HazardTask<...>>.  max_hazards = 0 gives exactly the counterpart's results plus
+ *             zero costs.
+ * MOBROB_ERR_INVALID before any launch, besides the counterpart's checks, for: n_scenes < 1, max_hazards outside 0 .. 1024, a count
+ * outside 0 .. max_hazards, scene NULL with n_scenes > 1, a scene entry outside 0 .. n_scenes - 1, a non-finite coordinate or
+ * radius, a negative radius, a cost that is negative or not finite. */
+typedef struct mobrob_hazards {
+  int32_t n_scenes;          /* S >= 1                                                  */
+  int32_t max_hazards;       /* M, row stride, 0 .. 1024                                */
+  const float* hazards;      /* [S][M][3]: x, y, radius (radius >= 0, finite)           */
+  const int32_t* n_hazards;  /* [S] counts 0 .. M, or NULL = M                          */
+  const int32_t* scene;      /* [n_robots] scene of each robot, or NULL (needs S == 1)  */
+  float cost;                /* hazards_cost, >= 0                                      */
+  int32_t indicator;         /* constrain_indicator                                     */
+} mobrob_hazards_t;
+int mobrob_ppo_evaluate_goal_env_hazards(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                                         const mobrob_hazards_t* hz, const int32_t* quota /* [n_robots] or NULL */,
+                                         double* robot_out /* [n_robots][4] */, double* episode_out /* or NULL */,
+                                         double* hazard_out /* [n_robots][4] */, double* episode_cost_out /* or NULL */,
+                                         float* trace_out /* or NULL */);
+int mobrob_ppo_follow_waypoints_hazards(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                        const mobrob_hazards_t* hz, const float* start /* [n][pos_dim] */,
+                                        const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                        int32_t* arrival /* [n][K] */, double* robot_out /* [n][4] */,
+                                        double* hazard_out /* [n][4] */, float* path_out /* or NULL */, float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

@@ -71,6 +71,12 @@ class FollowSpec(C.Structure):  # mobrob_follow_spec_t
                 ("seed", C.c_uint64), ("path_stride", C.c_int32), ("trace_robots", C.c_int32), ("trace_steps", C.c_int32)]
 
 
+class HazardsC(C.Structure):  # mobrob_hazards_t
+    _fields_ = [("n_scenes", C.c_int32), ("max_hazards", C.c_int32), ("hazards", C.POINTER(C.c_float)),
+                ("n_hazards", C.POINTER(C.c_int32)), ("scene", C.POINTER(C.c_int32)), ("cost", C.c_float),
+                ("indicator", C.c_int32)]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -134,6 +140,12 @@ SYMBOLS = {
                                                C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
     "mobrob_ppo_follow_waypoints": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), _F, _F, C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32), C.POINTER(C.c_double), _F, _F]),
+    "mobrob_ppo_evaluate_goal_env_hazards": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(EvalSpec), C.POINTER(HazardsC),
+                                                       C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
+    "mobrob_ppo_follow_waypoints_hazards": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), C.POINTER(HazardsC), _F, _F,
+                                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double), _F, _F]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

@@ -51,6 +51,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_env.h"
 #include "kernels_eval.h"
 #include "kernels_follow.h"
+#include "kernels_hazard.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -3248,7 +3249,9 @@ struct EvalCall {
   uint64_t seed;
   int trace_robots, trace_steps;
   float* trace_out;
+  int trace_extra = 0;        // columns a wrapping task adds to each trace row (hazards: 2)
   bool tracing() const { return trace_out && trace_robots > 0 && trace_steps > 0; }
+  size_t trace_floats() const { return (size_t)trace_steps * trace_robots; }
 };
 
 // the checks both entry points make, in two groups (evaluate has checks of its own between them)
@@ -3284,7 +3287,7 @@ static T* eval_at(const mobrob_ppo_engine_t* e, size_t off) { return reinterpret
 static int eval_prepare(mobrob_ppo_engine_t* e, const EvalCall& c, const GoalEnvParams& p, EvalCarve& carve, EvalArgs& a) {
   const int N = c.N, Dp = e->Dp, Ap = e->Ap;
   const bool tracing = c.tracing();
-  const size_t n_tr = tracing ? (size_t)c.trace_steps * c.trace_robots * (9 + e->D + e->A + kEvalTraceFlags) : 1;
+  const size_t n_tr = tracing ? c.trace_floats() * (9 + e->D + e->A + kEvalTraceFlags + c.trace_extra) : 1;
   const size_t o_out = carve.add((size_t)N * 4 * 8), o_tr = carve.add(n_tr * 4), o_st = carve.add((size_t)N * kGoalStateFloats * 4),
                o_obs = carve.add((size_t)cdiv(N, 256) * 256 * Dp * 4), o_mu = carve.add((size_t)cdiv(N, 256) * 256 * Ap * 4);   // whole 256-row tiles
   if (const int rc = grow_eval_buf(e, carve.total)) return rc;
@@ -3317,7 +3320,9 @@ static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, voi
   const bool persistent = e->fused.enabled && e->fused.H == 64 && !(pe && atoi(pe) == 0);
   if (persistent) {
     Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
-    FUSED_DISPATCH_DP(a.Dp, hipLaunchKernelGGL((k_goal64_tile<DPc, Task>), dim3(cdiv(N, 16)), dim3(64), eval64_lds_bytes(a.Dp), e->stream, args, W));
+    size_t lds_bytes = eval64_lds_bytes(a.Dp);
+    if constexpr (Task::kWide) lds_bytes += Task::tile_lds_bytes(args);
+    FUSED_DISPATCH_DP(a.Dp, hipLaunchKernelGGL((k_goal64_tile<DPc, Task>), dim3(cdiv(N, 16)), dim3(64), lds_bytes, e->stream, args, W));
   } else {
     hipLaunchKernelGGL(k_goal_task_init<Task>, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, args);
     for (int t = 0; t < a.max_steps; ++t) {
@@ -3337,17 +3342,79 @@ static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, voi
 static int eval_copy_back(mobrob_ppo_engine_t* e, const EvalCall& c, const EvalArgs& a, double* robot_out, int ran) {
   HIPC(hipMemcpyAsync(robot_out, a.robot_out, (size_t)a.N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
   if (a.trace)
-    HIPC(hipMemcpyAsync(c.trace_out, a.trace, (size_t)a.trace_steps * a.trace_robots * (9 + a.D + a.A + kEvalTraceFlags) * 4,
+    HIPC(hipMemcpyAsync(c.trace_out, a.trace, c.trace_floats() * (9 + a.D + a.A + kEvalTraceFlags + c.trace_extra) * 4,
                         hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return ran;
 }
+
+// ---- hazards (the *_hazards entry points): checks, regions of eval_buf, upload ----
+struct HazardIO {
+  const mobrob_hazards_t* hz;
+  double* hazard_out;         // [N][4]
+  double* episode_cost_out;   // [N][max quota] or null (evaluate)
+};
+struct HazardCarve {
+  size_t hz, nhz, scene, out, acc;
+  std::vector<int32_t> counts;   // [S], n_hazards or M each
+};
+static int hazard_check(const mobrob_hazards_t* hz, int N, const char* who, std::vector<int32_t>& counts) {
+  const int S = hz->n_scenes, M = hz->max_hazards;
+  if (S < 1) return fail(MOBROB_ERR_INVALID, "%s: hazards: n_scenes must be >= 1", who);
+  if (M < 0 || M > kHazardMax) return fail(MOBROB_ERR_INVALID, "%s: hazards: max_hazards must lie in 0 .. %d", who, kHazardMax);
+  if (M > 0 && !hz->hazards) return fail(MOBROB_ERR_INVALID, "%s: hazards: null hazard table", who);
+  if (!hz->scene && S > 1) return fail(MOBROB_ERR_INVALID, "%s: hazards: %d scenes need a scene index per robot", who, S);
+  if (!(std::isfinite(hz->cost) && hz->cost >= 0.f)) return fail(MOBROB_ERR_INVALID, "%s: hazards: cost must be finite and >= 0", who);
+  counts.assign(S, M);
+  for (int s = 0; s < S; ++s) {
+    if (hz->n_hazards) counts[s] = hz->n_hazards[s];
+    if (counts[s] < 0 || counts[s] > M)
+      return fail(MOBROB_ERR_INVALID, "%s: hazards: n_hazards[%d] = %d outside 0 .. %d", who, s, counts[s], M);
+    for (int i = 0; i < counts[s]; ++i) {
+      const float* h = hz->hazards + ((size_t)s * M + i) * 3;
+      if (!(std::isfinite(h[0]) && std::isfinite(h[1]) && std::isfinite(h[2]) && h[2] >= 0.f))
+        return fail(MOBROB_ERR_INVALID, "%s: hazards: hazard %d of scene %d is not finite or has a negative radius", who, i, s);
+    }
+  }
+  if (hz->scene)
+    for (int i = 0; i < N; ++i)
+      if (hz->scene[i] < 0 || hz->scene[i] >= S)
+        return fail(MOBROB_ERR_INVALID, "%s: hazards: scene[%d] = %d outside 0 .. %d", who, i, hz->scene[i], S - 1);
+  return MOBROB_OK;
+}
+static void hazard_carve(EvalCarve& carve, const mobrob_hazards_t* hz, int N, HazardCarve& hc) {
+  hc.hz = carve.add(std::max<size_t>((size_t)hz->n_scenes * hz->max_hazards * 3, 1) * 4);
+  hc.nhz = carve.add((size_t)hz->n_scenes * 4);
+  hc.scene = carve.add((size_t)N * 4);
+  hc.out = carve.add((size_t)N * 4 * 8);
+  hc.acc = carve.add((size_t)N * 8);
+}
+// the hazard fields of `h` (after eval_prepare grew eval_buf); hazard_out is written by the task itself
+template <class BaseArgs>
+static int hazard_fill(mobrob_ppo_engine_t* e, const mobrob_hazards_t* hz, int N, const HazardCarve& hc, HazardArgs<BaseArgs>& h) {
+  const size_t nf = (size_t)hz->n_scenes * hz->max_hazards * 3;
+  h.hz = eval_at<float>(e, hc.hz);
+  h.nhz = eval_at<int>(e, hc.nhz);
+  h.scene = hz->scene ? eval_at<int>(e, hc.scene) : nullptr;
+  h.M = hz->max_hazards;
+  h.coef = hz->cost;
+  h.indicator = hz->indicator != 0;
+  h.hazard_out = eval_at<double>(e, hc.out);
+  h.ep_acc = eval_at<double>(e, hc.acc);
+  h.ep_cost = nullptr;
+  if (nf) HIPC(hipMemcpyAsync(const_cast<float*>(h.hz), hz->hazards, nf * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(const_cast<int*>(h.nhz), hc.counts.data(), (size_t)hz->n_scenes * 4, hipMemcpyHostToDevice, e->stream));
+  if (hz->scene) HIPC(hipMemcpyAsync(const_cast<int*>(h.scene), hz->scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  return MOBROB_OK;
+}
 }  // extern "C++"
 
-int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
-                                 const int32_t* quota, double* robot_out, double* episode_out, float* trace_out) {
+// evaluate, with hazards when `hio` is not null (mobrob_ppo_evaluate_goal_env_hazards)
+static int evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                             const int32_t* quota, double* robot_out, double* episode_out, float* trace_out, const HazardIO* hio) {
   if (!e || !env || !spec || !robot_out) return fail(MOBROB_ERR_INVALID, "evaluate: null argument");
-  const EvalCall c{"evaluate", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
+  EvalCall c{"evaluate", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
+  if (hio) c.trace_extra = kHazardTraceExtra;
   const int N = c.N;
   if (N < 1) return fail(MOBROB_ERR_INVALID, "evaluate: n_robots must be >= 1");
   if (spec->max_steps < 1) return fail(MOBROB_ERR_INVALID, "evaluate: max_steps must be >= 1");
@@ -3364,9 +3431,18 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
     if (q[i] < 0) return fail(MOBROB_ERR_INVALID, "evaluate: negative quota");
     maxq = std::max(maxq, (int)q[i]);
   }
+  HazardCarve hc;
+  if (hio)
+    if (const int rc = hazard_check(hio->hz, N, c.who, hc.counts)) return rc;
   EvalCarve carve;
   const size_t o_ep = carve.add(std::max<size_t>((size_t)N * maxq * 3, 1) * 8), o_q = carve.add((size_t)N * 4), o_er = carve.add((size_t)N * 8);
-  EvalArgs a{};
+  size_t o_ec = 0;
+  if (hio) {
+    hazard_carve(carve, hio->hz, N, hc);
+    o_ec = carve.add(std::max<size_t>((size_t)N * maxq, 1) * 8);
+  }
+  HazardArgs<EvalArgs> h{};
+  EvalArgs& a = h.b;
   const GoalEnvParams p = eval_env_params(env, e->A, env->terminate_on_goal != 0, env->time_limit > 0 ? env->time_limit : INT_MAX);   // control.py: no limit
   if (const int rc = eval_prepare(e, c, p, carve, a)) return rc;
   int* q_dev = eval_at<int>(e, o_q);
@@ -3378,19 +3454,44 @@ int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t
   if (spec->episodes > 0) a.max_steps = (int)std::min<int64_t>(a.max_steps, (int64_t)maxq * env->time_limit);
   HIPC(hipMemcpyAsync(q_dev, q.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
   if (maxq > 0) HIPC(hipMemsetAsync(a.ep_out, 0, (size_t)N * maxq * 3 * 8, e->stream));
-  const int ran = eval_run<EvalTask>(e, a, nullptr);
+  if (hio) {
+    if (const int rc = hazard_fill(e, hio->hz, N, hc, h)) return rc;
+    h.ep_cost = eval_at<double>(e, o_ec);
+    if (maxq > 0) HIPC(hipMemsetAsync(h.ep_cost, 0, (size_t)N * maxq * 8, e->stream));
+  }
+  const int ran = hio ? eval_run<HazardEvalTask>(e, h, nullptr) : eval_run<EvalTask>(e, a, nullptr);
   if (ran < 0) return ran;
   if (episode_out && maxq > 0)
     HIPC(hipMemcpyAsync(episode_out, a.ep_out, (size_t)N * maxq * 3 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (hio) {
+    HIPC(hipMemcpyAsync(hio->hazard_out, h.hazard_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
+    if (hio->episode_cost_out && maxq > 0)
+      HIPC(hipMemcpyAsync(hio->episode_cost_out, h.ep_cost, (size_t)N * maxq * 8, hipMemcpyDeviceToHost, e->stream));
+  }
   return eval_copy_back(e, c, a, robot_out, ran);
 }
 
+int mobrob_ppo_evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                                 const int32_t* quota, double* robot_out, double* episode_out, float* trace_out) {
+  return evaluate_goal_env(e, env, spec, quota, robot_out, episode_out, trace_out, nullptr);
+}
+
+int mobrob_ppo_evaluate_goal_env_hazards(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                                         const mobrob_hazards_t* hz, const int32_t* quota, double* robot_out, double* episode_out,
+                                         double* hazard_out, double* episode_cost_out, float* trace_out) {
+  if (!hz || !hazard_out) return fail(MOBROB_ERR_INVALID, "evaluate: null argument");
+  const HazardIO hio{hz, hazard_out, episode_cost_out};
+  return evaluate_goal_env(e, env, spec, quota, robot_out, episode_out, trace_out, &hio);
+}
+
 // ---- waypoint following: the policy as a tracker of given goal sequences ------------------------------------------------
-int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
-                                const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
-                                double* robot_out, float* path_out, float* trace_out) {
+// follow, with hazards when `hio` is not null (mobrob_ppo_follow_waypoints_hazards)
+static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                            const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
+                            double* robot_out, float* path_out, float* trace_out, const HazardIO* hio) {
   if (!e || !env || !spec || !start || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
-  const EvalCall c{"follow", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
+  EvalCall c{"follow", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
+  if (hio) c.trace_extra = kHazardTraceExtra;
   const int N = c.N, K = spec->max_waypoints, P = env->pos_dim;
   if (N < 1) return fail(MOBROB_ERR_INVALID, "follow: n_robots must be >= 1");
   if (K < 1) return fail(MOBROB_ERR_INVALID, "follow: max_waypoints must be >= 1");
@@ -3411,12 +3512,17 @@ int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t*
         if (!std::isfinite(waypoints[((size_t)i * K + k) * P + j]))
           return fail(MOBROB_ERR_INVALID, "follow: waypoint %d of robot %d is not finite", k, i);
   }
+  HazardCarve hc;
+  if (hio)
+    if (const int rc = hazard_check(hio->hz, N, c.who, hc.counts)) return rc;
   const bool pathing = path_out && spec->path_stride > 0;
   const size_t n_rec = pathing ? (size_t)(spec->max_steps / spec->path_stride + 1) : 0;
   EvalCarve carve;
   const size_t o_arr = carve.add((size_t)N * K * 4), o_start = carve.add((size_t)N * P * 4), o_wp = carve.add((size_t)N * K * P * 4),
                o_nw = carve.add((size_t)N * 4), o_path = carve.add(std::max<size_t>(n_rec * N * P, 1) * 4);
-  FollowArgs f{};
+  if (hio) hazard_carve(carve, hio->hz, N, hc);
+  HazardArgs<FollowArgs> h{};
+  FollowArgs& f = h.b;
   // no termination, no time limit: the robot only stops at its last waypoint
   if (const int rc = eval_prepare(e, c, eval_env_params(env, e->A, false, INT_MAX), carve, f.e)) return rc;
   float* start_dev = eval_at<float>(e, o_start);
@@ -3431,11 +3537,29 @@ int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t*
   HIPC(hipMemcpyAsync(wp_dev, waypoints, (size_t)N * K * P * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(nw_dev, nw.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemsetAsync(f.arrival, 0xFF, (size_t)N * K * 4, e->stream));   // -1: not reached
-  const int ran = eval_run<FollowTask>(e, f, k_follow_goal_fin);
+  if (hio)
+    if (const int rc = hazard_fill(e, hio->hz, N, hc, h)) return rc;
+  const int ran = hio ? eval_run<HazardFollowTask>(e, h, k_hazard_follow_fin) : eval_run<FollowTask>(e, f, k_follow_goal_fin);
   if (ran < 0) return ran;
   HIPC(hipMemcpyAsync(arrival, f.arrival, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
   if (pathing) HIPC(hipMemcpyAsync(path_out, path_dev, n_rec * N * P * 4, hipMemcpyDeviceToHost, e->stream));
+  if (hio) HIPC(hipMemcpyAsync(hio->hazard_out, h.hazard_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
   return eval_copy_back(e, c, f.e, robot_out, ran);
+}
+
+int mobrob_ppo_follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
+                                double* robot_out, float* path_out, float* trace_out) {
+  return follow_waypoints(e, env, spec, start, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out, nullptr);
+}
+
+int mobrob_ppo_follow_waypoints_hazards(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                        const mobrob_hazards_t* hz, const float* start, const float* waypoints,
+                                        const int32_t* n_waypoints, int32_t* arrival, double* robot_out, double* hazard_out,
+                                        float* path_out, float* trace_out) {
+  if (!hz || !hazard_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
+  const HazardIO hio{hz, hazard_out, nullptr};
+  return follow_waypoints(e, env, spec, start, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out, &hio);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -46,7 +46,9 @@ struct EvalArgs {
   float* mu;                  // [N][Ap] actor mean of those observations (written by the engine's forward())
 };
 
-__device__ __forceinline__ int eval_trace_width(const EvalArgs& a) { return 9 + a.D + a.A + kEvalTraceFlags; }
+// XT: extra columns a wrapping task appends to every row (kernels_hazard.h)
+template <int XT = 0>
+__device__ __forceinline__ int eval_trace_width(const EvalArgs& a) { return 9 + a.D + a.A + kEvalTraceFlags + XT; }
 
 // observation chunk c (features 4c .. 4c + 3) of state g, seen before step `step`
 __device__ __forceinline__ f32x4 eval_features(const GoalState& g, const EvalArgs& a, int n, int c, uint32_t step) {
@@ -62,10 +64,11 @@ __device__ __forceinline__ void eval_obs_store(const GoalState& g, const EvalArg
 
 // the trace row of robot n at step t: state before the step, observation, action.  Returns the row's four task-specific flag
 // floats for the caller to fill after the step, or null when (n, t) is not traced.
+template <int XT = 0>
 __device__ __forceinline__ float* eval_trace_row(const GoalState& g, const EvalArgs& a, int n, int t, const float* act,
                                                  const float* obs_row) {
   if (!(a.trace && n < a.trace_robots && t < a.trace_steps)) return nullptr;
-  float* tr_row = a.trace + ((size_t)t * a.trace_robots + n) * eval_trace_width(a);
+  float* tr_row = a.trace + ((size_t)t * a.trace_robots + n) * eval_trace_width<XT>(a);
 #pragma unroll
   for (int j = 0; j < 3; ++j) { tr_row[j] = g.pos[j]; tr_row[3 + j] = g.vel[j]; tr_row[6 + j] = g.goal[j]; }
   for (int f = 0; f < a.D; ++f) tr_row[9 + f] = obs_row[f];
@@ -102,11 +105,14 @@ struct EvalRobot {
 };
 
 // one step of robot n at step t: trace (state before the step, observation, action), env.step, float64 accounting, episode
-// record, reset.  Returns whether the robot is still active afterwards.  obs_row: the D observation features it acted on.
+// record, reset.  Returns whether the robot is still active afterwards.  obs_row: the D observation features it acted on;
+// post: if not null, receives x, y after the env step and before any reset.
+template <int XT = 0>
 __device__ __forceinline__ bool eval_env_step(GoalState& g, EvalRobot& R, const EvalArgs& a, int n, int t, const float* act,
-                                              const float* obs_row) {
-  float* f = eval_trace_row(g, a, n, t, act, obs_row);
+                                              const float* obs_row, float* post = nullptr) {
+  float* f = eval_trace_row<XT>(g, a, n, t, act, obs_row);
   const GoalOutcome o = goal_advance(g, a.p, act, a.A);
+  if (post) { post[0] = g.pos[0]; post[1] = g.pos[1]; }
   R.steps += 1;
   R.ret_sum += (double)o.reward;
   R.ep_ret += (double)o.reward;
@@ -141,11 +147,17 @@ struct EvalTask {
     eval_reset0(g, a, n);
     R = Robot{0.0, 0.0, 0, 0, 0, a.quota[n]};
   }
+  static constexpr bool kWide = false;   // k_goal64_tile: step runs on the robot's lane only
   static __device__ __forceinline__ bool active(const Args& a, const Robot& R) { return a.episodes == 0 || R.eps < R.quota; }
+  // XT / post: for a wrapping task (kernels_hazard.h): trace row width + XT, the post-step x, y
+  template <int XT = 0>
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
-                                              const float* obs_row) {
-    return eval_env_step(g, R, a, n, t, act, obs_row);
+                                              const float* obs_row, float* post = nullptr) {
+    return eval_env_step<XT>(g, R, a, n, t, act, obs_row, post);
   }
+  static __device__ __forceinline__ int episodes(const Robot& R) { return R.eps; }
+  static __device__ __forceinline__ int steps(const Robot& R) { return R.steps; }
+  static __device__ __forceinline__ bool recorded(const Robot& R, int e) { return e < R.quota; }
   static __device__ __forceinline__ void finish(const Args& a, int n, const Robot& R, const GoalState&) { eval_robot_out(a, n, R); }
   static __device__ __forceinline__ Robot load(const Args& a, int n) {
     const double* o = a.robot_out + (size_t)n * 4;
@@ -342,6 +354,7 @@ __global__ __launch_bounds__(64) void k_goal64_tile(typename Task::Args args, Ev
   const int r16 = lane & 15;
   const int row0 = blockIdx.x * 16;
   eval64_load_actor<DP>(W, a.D, a.A, lane);
+  if constexpr (Task::kWide) Task::stage(args, &lds[L::END + 32], lane);   // after [16][2] post-step positions at L::END
   // ---- start state of the tile's robots (lanes 0..15 own robot row0 + lane) ----
   const int n = row0 + r16;
   const bool mine = lane < 16 && n < a.N;
@@ -358,6 +371,20 @@ __global__ __launch_bounds__(64) void k_goal64_tile(typename Task::Args args, Ev
   for (int t = 0; t < a.max_steps; ++t) {
     if (__ballot(active) == 0ull) break;   // one wave per workgroup: uniform
     eval64_actor_step<DP>(a, row0, t, lane, wide_head);
+    if constexpr (Task::kWide) {
+      // ---- env phase on the tile's 16 lanes, then the task's wide phase on all 64 (robot lane & 15 stepped: bit of `stepping`) ----
+      const uint64_t stepping = __ballot(mine && active);
+      int e0 = 0;
+      if (mine && active) {
+        float* act = &lds[L::MU + r16 * L::LDM];
+        eval_actions(a, n, t, act, act);
+        active = Task::step_lane(g, R, args, n, t, act, &lds[L::X + r16 * L::LDX], &lds[L::END + 2 * r16], e0);
+        eval64_state_lds(&lds[L::ST + 12 * r16], g);
+      }
+      __syncthreads();
+      Task::after_step(args, R, n, t, lane, (stepping >> r16) & 1ull, e0, &lds[L::END], &lds[L::END + 32]);
+      __syncthreads();
+    } else {
     // ---- env phase: the tile's 16 lanes ----
     if (mine && active) {
       float* act = &lds[L::MU + r16 * L::LDM];   // the mean row becomes the applied action in place
@@ -366,6 +393,7 @@ __global__ __launch_bounds__(64) void k_goal64_tile(typename Task::Args args, Ev
       eval64_state_lds(&lds[L::ST + 12 * r16], g);
     }
     __syncthreads();
+    }
   }
   if (mine) Task::finish(args, n, R, g);
 }

@@ -63,13 +63,16 @@ __device__ __forceinline__ void follow_start(GoalState& g, FollowRobot& R, const
 }
 
 // step t of robot n (unfinished: R.k < R.nwp): trace (state before the step, observation, action), env.step, float64 reward sum,
-// arrival and the next waypoint, path record.  Returns whether the robot is still unfinished afterwards.
+// arrival and the next waypoint, path record.  Returns whether the robot is still unfinished afterwards.  XT / post: as
+// eval_env_step's.
+template <int XT = 0>
 __device__ __forceinline__ bool follow_env_step(GoalState& g, FollowRobot& R, const FollowArgs& f, int n, int t, const float* act,
-                                                const float* obs_row) {
+                                                const float* obs_row, float* post = nullptr) {
   const EvalArgs& a = f.e;
-  float* fl = eval_trace_row(g, a, n, t, act, obs_row);
+  float* fl = eval_trace_row<XT>(g, a, n, t, act, obs_row);
   const int k_before = R.k;
   const GoalOutcome o = goal_advance(g, a.p, act, a.A);
+  if (post) { post[0] = g.pos[0]; post[1] = g.pos[1]; }
   R.steps += 1;
   R.ret_sum += (double)o.reward;
   if (o.reached) {
@@ -112,11 +115,16 @@ struct FollowTask {
   using Robot = FollowRobot;
   static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& f) { return f.e; }
   static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& f, int n) { follow_start(g, R, f, n); }
+  static constexpr bool kWide = false;
   static __device__ __forceinline__ bool active(const Args&, const Robot& R) { return R.k < R.nwp; }
+  template <int XT = 0>
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& f, int n, int t, const float* act,
-                                              const float* obs_row) {
-    return follow_env_step(g, R, f, n, t, act, obs_row);
+                                              const float* obs_row, float* post = nullptr) {
+    return follow_env_step<XT>(g, R, f, n, t, act, obs_row, post);
   }
+  static __device__ __forceinline__ int episodes(const Robot&) { return 0; }   // no episodes: no reset
+  static __device__ __forceinline__ int steps(const Robot& R) { return R.steps; }
+  static __device__ __forceinline__ bool recorded(const Robot&, int) { return false; }
   static __device__ __forceinline__ void finish(const Args& f, int n, const Robot& R, const GoalState& g) { follow_finish(f, n, R, g); }
   static __device__ __forceinline__ Robot load(const Args& f, int n) { return follow_robot_load(f, n); }
   static __device__ __forceinline__ void store(const Args& f, int n, const Robot& R) { follow_robot_store(f, n, R); }

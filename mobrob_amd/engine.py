@@ -7,7 +7,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from ._lib import BUF, Config, DroneParams, EpisodeStats, EvalSpec, FollowSpec, GoalEnv, TrainStats, check
+from ._lib import BUF, Config, DroneParams, EpisodeStats, EvalSpec, FollowSpec, GoalEnv, HazardsC, TrainStats, check
 
 F32 = np.float32
 STAT_KEYS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
@@ -349,7 +349,28 @@ class PPOEngine:
                 g.mix[j][k] = float(mix[j, k])
         return g
 
-    def _eval_spec_common(self, what, sp, max_steps, deterministic, seed, trace):
+    @staticmethod
+    def _hazards_struct(hazards, n):
+        """mobrob_hazards_t of a goal_rules.Hazards for n robots, and the arrays it points into (kept alive by the caller)."""
+        from .envs.goal_rules import Hazards
+        if not isinstance(hazards, Hazards):
+            raise TypeError(f"hazards must be a mobrob_amd.envs.goal_rules.Hazards, not {type(hazards).__name__}")
+        hazards.check_robots(n)
+        keep = (hazards.table, hazards.counts, hazards.scene)
+        h = HazardsC()
+        h.n_scenes, h.max_hazards = hazards.n_scenes, hazards.max_hazards
+        h.hazards, h.n_hazards = _fp(hazards.table), hazards.counts.ctypes.data_as(C.POINTER(C.c_int32))
+        h.scene = None if hazards.scene is None else hazards.scene.ctypes.data_as(C.POINTER(C.c_int32))
+        h.cost, h.indicator = hazards.cost, int(hazards.indicator)
+        return h, keep
+
+    @staticmethod
+    def _hazard_result(hz):
+        """The keys hazard_out adds to both calls' dicts."""
+        return {"cost_sum": hz[:, 0], "violation_steps": hz[:, 1].astype(np.int64), "first_violation": hz[:, 2].astype(np.int64),
+                "min_clearance": hz[:, 3]}
+
+    def _eval_spec_common(self, what, sp, max_steps, deterministic, seed, trace, trace_extra=0):
         """What evaluate_goal_env and follow_waypoints fill alike in their spec (max_steps, deterministic, seed, trace sizes), after
         refusing sampled actions of a gSDE policy.  Returns the trace buffer, or None without a trace."""
         if self.use_sde and not deterministic:
@@ -358,7 +379,7 @@ class PPOEngine:
         sp.trace_robots, sp.trace_steps = (0, 0) if trace is None else (int(trace[0]), int(trace[1]))
         if trace is None:
             return None
-        return np.zeros((max(sp.trace_steps, 1), max(sp.trace_robots, 1), 9 + self.D + self.A + 4), F32)
+        return np.zeros((max(sp.trace_steps, 1), max(sp.trace_robots, 1), 9 + self.D + self.A + 4 + trace_extra), F32)
 
     @staticmethod
     def _eval_result(robot, r):
@@ -367,16 +388,18 @@ class PPOEngine:
 
     def evaluate_goal_env(self, pos_dim, mix, time_limit=0, terminate_on_goal=True, dt=0.05, extent=3.0, reach_radius=0.3,
                           goal_bonus=5.0, extra_bonus=0.0, obs_noise=0.1, *, n_robots, max_steps=1000, episodes=0, quota=None,
-                          deterministic=True, seed=0, trace=None):
+                          deterministic=True, seed=0, trace=None, hazards=None):
         """The current policy on `n_robots` fresh robots of the device goal environment (mobrob_ppo_evaluate_goal_env).
         time_limit 0: no limit (examples/control.py).  episodes > 0: SB3 evaluate_policy's quota of finished episodes, split
         (episodes + i) // n_robots unless `quota` ([n_robots] ints) is given.  trace = (robots, steps): teacher-forcing trace.
         Returns a dict of NumPy arrays: reward_sum, steps, episodes, goals ([n_robots]); episode_returns, episode_lengths,
         episode_success ([n_robots][max quota], NaN past an unfinished quota); trace ([steps][robots][9 + D + A + 4]) and
-        `persistent` (which kernel path ran)."""
+        `persistent` (which kernel path ran).  hazards: a goal_rules.Hazards -> mobrob_ppo_evaluate_goal_env_hazards, adding
+        cost_sum, violation_steps, first_violation, min_clearance ([n_robots]) and episode_cost ([n_robots][max quota], NaN
+        past an unfinished quota); trace rows then end in the step's cost and clearance."""
         n = int(n_robots)
         sp = EvalSpec()
-        tr = self._eval_spec_common("evaluate_goal_env", sp, max_steps, deterministic, seed, trace)
+        tr = self._eval_spec_common("evaluate_goal_env", sp, max_steps, deterministic, seed, trace, 0 if hazards is None else 2)
         g = self._goal_env_struct(pos_dim, mix, time_limit, terminate_on_goal, dt, extent, reach_radius, goal_bonus, extra_bonus,
                                   obs_noise)
         sp.n_robots, sp.episodes = n, int(episodes)
@@ -392,43 +415,63 @@ class PPOEngine:
         robot = np.zeros((max(n, 1), 4), np.float64)
         ep = np.zeros((max(n, 1), max(maxq, 1), 3), np.float64)
         dp = C.POINTER(C.c_double)
-        r = check(self.lib.mobrob_ppo_evaluate_goal_env(self._h, C.byref(g), C.byref(sp), q.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                         robot.ctypes.data_as(dp), ep.ctypes.data_as(dp), _fp(tr)))
+        if hazards is None:
+            r = check(self.lib.mobrob_ppo_evaluate_goal_env(self._h, C.byref(g), C.byref(sp), q.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                             robot.ctypes.data_as(dp), ep.ctypes.data_as(dp), _fp(tr)))
+        else:
+            h, _keep = self._hazards_struct(hazards, n)
+            hz = np.zeros((max(n, 1), 4), np.float64)
+            ec = np.zeros((max(n, 1), max(maxq, 1)), np.float64)
+            r = check(self.lib.mobrob_ppo_evaluate_goal_env_hazards(
+                self._h, C.byref(g), C.byref(sp), C.byref(h), q.ctypes.data_as(C.POINTER(C.c_int32)), robot.ctypes.data_as(dp),
+                ep.ctypes.data_as(dp), hz.ctypes.data_as(dp), ec.ctypes.data_as(dp), _fp(tr)))
         ep = ep[:, :maxq]
         done = np.arange(maxq)[None, :] < np.minimum(robot[:, 2:3], q[:, None])
         out = self._eval_result(robot, r)
         out.update({"episodes": robot[:, 2].astype(np.int64), "goals": robot[:, 3].astype(np.int64), "quota": q,
                     "episode_returns": np.where(done, ep[:, :, 0], np.nan), "episode_lengths": np.where(done, ep[:, :, 1], np.nan),
                     "episode_success": np.where(done, ep[:, :, 2], np.nan)})
+        if hazards is not None:
+            out.update(self._hazard_result(hz))
+            out["episode_cost"] = np.where(done, ec[:, :maxq], np.nan)
         if tr is not None:
             out["trace"] = tr
         return out
 
     def follow_waypoints(self, pos_dim, mix, dt=0.05, extent=3.0, reach_radius=0.3, goal_bonus=5.0, extra_bonus=0.0,
                          obs_noise=0.1, *, start, waypoints, n_waypoints=None, max_steps=1000, deterministic=True, seed=0,
-                         path_stride=0, trace=None):
+                         path_stride=0, trace=None, hazards=None):
         """The current policy as a tracker of given goal sequences (mobrob_ppo_follow_waypoints): robot i starts at rest on
         start[i] ([n][P]) and follows waypoints[i][:n_waypoints[i]] (waypoints [n][K][P], or [K][P] for all robots; n_waypoints
         None = K each), no time limit, no reset.  path_stride > 0 records positions; trace = (robots, steps): teacher-forcing
         trace.  Returns the dict of mobrob_amd.waypoints (arrival, reached, steps, reward_sum, final_distance, path, trace,
-        persistent)."""
+        persistent).  hazards: a goal_rules.Hazards -> mobrob_ppo_follow_waypoints_hazards, adding cost_sum, violation_steps,
+        first_violation, min_clearance; trace rows then end in the step's cost and clearance."""
         from .waypoints import follow_inputs
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
         n, K, P = wp.shape
         sp = FollowSpec()
-        tr = self._eval_spec_common("follow_waypoints", sp, max_steps, deterministic, seed, trace)
+        tr = self._eval_spec_common("follow_waypoints", sp, max_steps, deterministic, seed, trace, 0 if hazards is None else 2)
         g = self._goal_env_struct(pos_dim, mix, 0, False, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise)
         sp.n_robots, sp.max_waypoints, sp.path_stride = n, K, int(path_stride)
         arrival = np.empty((n, K), np.int32)
         robot = np.zeros((n, 4), np.float64)
         path = np.zeros((int(max_steps) // int(path_stride) + 1, n, P), F32) if int(path_stride) > 0 and int(max_steps) > 0 else None
-        i32 = C.POINTER(C.c_int32)
-        r = check(self.lib.mobrob_ppo_follow_waypoints(self._h, C.byref(g), C.byref(sp), _fp(s), _fp(wp), nw.ctypes.data_as(i32),
-                                                        arrival.ctypes.data_as(i32), robot.ctypes.data_as(C.POINTER(C.c_double)),
-                                                        _fp(path), _fp(tr)))
+        i32, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        if hazards is None:
+            r = check(self.lib.mobrob_ppo_follow_waypoints(self._h, C.byref(g), C.byref(sp), _fp(s), _fp(wp), nw.ctypes.data_as(i32),
+                                                            arrival.ctypes.data_as(i32), robot.ctypes.data_as(dp), _fp(path), _fp(tr)))
+        else:
+            h, _keep = self._hazards_struct(hazards, n)
+            hz = np.zeros((n, 4), np.float64)
+            r = check(self.lib.mobrob_ppo_follow_waypoints_hazards(
+                self._h, C.byref(g), C.byref(sp), C.byref(h), _fp(s), _fp(wp), nw.ctypes.data_as(i32), arrival.ctypes.data_as(i32),
+                robot.ctypes.data_as(dp), hz.ctypes.data_as(dp), _fp(path), _fp(tr)))
         out = self._eval_result(robot, r)
         out.update({"arrival": arrival.astype(np.int64), "reached": robot[:, 2].astype(np.int64), "final_distance": robot[:, 3],
                     "trace": tr})
+        if hazards is not None:
+            out.update(self._hazard_result(hz))
         if path is not None:
             out["path"] = path
         return out

@@ -201,10 +201,11 @@ class DeviceGoalVecEnv(VecEnvBase):
                                 extent=self.extent, extra_bonus=self.extra_bonus)
 
     def evaluate(self, engine, n_robots=None, max_steps=None, episodes=0, quota=None, deterministic=True, seed=None,
-                 trace=None):
+                 trace=None, hazards=None):
         """The engine's current policy on fresh robots of this task (PPOEngine.evaluate_goal_env with this env's mix, dt,
         extent, extra_bonus and time_limit).  n_robots defaults to num_envs; with a quota (`episodes` > 0 or `quota`)
-        max_steps defaults to the bound max quota x time_limit, else to time_limit; seed defaults to the env's seed."""
+        max_steps defaults to the bound max quota x time_limit, else to time_limit; seed defaults to the env's seed.
+        hazards: a goal_rules.Hazards (hazard costs, see PPOEngine.evaluate_goal_env)."""
         n = self.num_envs if n_robots is None else int(n_robots)
         if max_steps is None:
             if quota is not None or episodes > 0:
@@ -215,16 +216,16 @@ class DeviceGoalVecEnv(VecEnvBase):
         return engine.evaluate_goal_env(self.pos_dim, self.mix, self.time_limit, self.terminate_on_goal, dt=self.dt,
                                         extent=self.extent, extra_bonus=self.extra_bonus, n_robots=n, max_steps=int(max_steps),
                                         episodes=episodes, quota=quota, deterministic=deterministic,
-                                        seed=(self._seed or 0) if seed is None else seed, trace=trace)
+                                        seed=(self._seed or 0) if seed is None else seed, trace=trace, hazards=hazards)
 
     def follow(self, engine, start, waypoints, n_waypoints=None, max_steps=1000, deterministic=True, seed=None, path_stride=0,
-               trace=None):
+               trace=None, hazards=None):
         """The engine's current policy following given waypoints on this task (PPOEngine.follow_waypoints with this env's mix,
-        dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed."""
+        dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed.  hazards: a goal_rules.Hazards."""
         return engine.follow_waypoints(self.pos_dim, self.mix, dt=self.dt, extent=self.extent, extra_bonus=self.extra_bonus,
                                        start=start, waypoints=waypoints, n_waypoints=n_waypoints, max_steps=int(max_steps),
                                        deterministic=deterministic, seed=(self._seed or 0) if seed is None else seed,
-                                       path_stride=path_stride, trace=trace)
+                                       path_stride=path_stride, trace=trace, hazards=hazards)
 
     def seed(self, seed=None):
         self._seed = seed

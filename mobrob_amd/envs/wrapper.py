@@ -196,7 +196,19 @@ class EnvWrapper(ABC):
         obs, _, _, truncated, info = self.env.step(action)
         reward = self.reward_fn()
         terminated = bool(rules.episode_over(self.reached(), self.terminate_on_goal))
+        hz = getattr(self, "_hazards", None)
+        if hz is not None:   # the reference Engine.step: info.update(self.cost()) -- only hazards are constrained here
+            cost, _ = rules.hazard_cost(self.get_pos(), hz.rows(), hz.cost, hz.indicator)
+            info = dict(info)
+            info["cost_hazards"] = info["cost"] = float(cost)
         return obs, reward, terminated, truncated, info
+
+    def set_hazards(self, locations, size=rules.HAZARDS_SIZE, cost=rules.HAZARDS_COST, indicator=True):
+        """Hazards on the floor (reference Engine: hazards_locations / hazards_size / hazards_cost / constrain_indicator):
+        locations [M, 2], size a radius or [M].  Every step then adds info["cost_hazards"] and info["cost"]
+        (goal_rules.hazard_cost at the position after the step).  None removes them.  Dynamics, reward and episodes are
+        unchanged: a robot passes through a hazard and is charged for it."""
+        self._hazards = None if locations is None else rules.Hazards(locations, size, cost, indicator)
 
     def reset(self, init_pos=None, *args, **kwargs):
         seed = kwargs.pop("seed", None)

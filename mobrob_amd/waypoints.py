@@ -19,6 +19,10 @@ Returned dict (NumPy arrays; n robots, K waypoint slots, P position dimensions):
   path [R][n][P]   with path_stride > 0: position after r * path_stride steps (record 0 = start; finished robots stay put)
   trace            the device path's teacher-forcing trace when asked for, else None
   persistent       which device kernel path ran (None on the host)
+With `hazards` (a goal_rules.Hazards), also the hazard costs of every step (the reference Engine's constrain_hazards rule at the
+position after the step; on the host: info["cost"] of EnvWrapper.step with set_hazards):
+  cost_sum [n] float64 sum of the step costs;  violation_steps [n] steps with cost > 0;  first_violation [n] the first such step
+  (1-based), -1 = none;  min_clearance [n] smallest (distance - radius) after a step (+inf without hazards, NaN without steps)
 """
 from __future__ import annotations
 
@@ -58,9 +62,14 @@ def follow_inputs(start, waypoints, n_waypoints=None, pos_dim=None):
     return np.ascontiguousarray(start, np.float32), np.ascontiguousarray(wp, np.float32), nw
 
 
-def _host_follow(model, make_env, start, wp, nw, max_steps, deterministic, seed, path_stride):
+def _host_follow(model, make_env, start, wp, nw, max_steps, deterministic, seed, path_stride, hazards=None):
     """The semantics, one robot after another on EnvWrapper's public API (make_env(i) -> the robot's env)."""
+    from .envs.goal_rules import hazard_cost
     n, K, P = wp.shape
+    if hazards is not None:
+        hazards.check_robots(n)
+    cost_sum, viol = np.zeros(n), np.zeros(n, np.int64)
+    first, min_clear = np.full(n, -1, np.int64), np.full(n, np.nan)
     arrival = np.full((n, K), -1, np.int64)
     reached, steps = np.zeros(n, np.int64), np.zeros(n, np.int64)
     reward_sum, final_distance = np.zeros(n), np.full(n, np.nan)
@@ -71,6 +80,10 @@ def _host_follow(model, make_env, start, wp, nw, max_steps, deterministic, seed,
             path[0, i] = pos
         if nw[i] > 0:
             env = make_env(i)
+            if hazards is not None:
+                rows = hazards.rows(i)
+                env.set_hazards(rows[:, :2], rows[:, 2], hazards.cost, hazards.indicator)
+                min_clear[i] = np.inf
             if seed is not None:
                 env.seed(int(seed) + i)
             env.env.reset()                            # the simulator at rest: every robot starts with zero velocity
@@ -80,10 +93,16 @@ def _host_follow(model, make_env, start, wp, nw, max_steps, deterministic, seed,
             k = 0
             for t in range(max_steps):
                 a, _ = model.predict(obs, deterministic=deterministic)
-                obs, r, _, _, _ = env.step(a)
+                obs, r, _, _, info = env.step(a)
                 reward_sum[i] += float(r)
                 steps[i] = t + 1
                 pos = np.asarray(env.get_pos(), np.float64)[:P]
+                if hazards is not None:
+                    cost_sum[i] += info["cost"]
+                    if info["cost"] > 0:
+                        viol[i] += 1
+                        first[i] = t + 1 if first[i] < 0 else first[i]
+                    min_clear[i] = min(min_clear[i], hazard_cost(pos, rows)[1])
                 if path is not None and (t + 1) % path_stride == 0:
                     path[(t + 1) // path_stride, i] = pos
                 if env.reached():
@@ -95,21 +114,25 @@ def _host_follow(model, make_env, start, wp, nw, max_steps, deterministic, seed,
                     obs = env.get_obs()
             reached[i] = k
             final_distance[i] = float(np.linalg.norm(np.asarray(env.get_goal(), np.float64)[:P] - pos))
+            if hazards is not None:
+                env.set_hazards(None)
         if path is not None:
             path[steps[i] // path_stride + 1:, i] = pos
     out = {"arrival": arrival, "reached": reached, "steps": steps, "reward_sum": reward_sum, "final_distance": final_distance,
            "trace": None, "persistent": None}
+    if hazards is not None:
+        out.update({"cost_sum": cost_sum, "violation_steps": viol, "first_violation": first, "min_clearance": min_clear})
     if path is not None:
         out["path"] = path
     return out
 
 
 def follow_waypoints(model, env, start, waypoints, n_waypoints=None, *, max_steps=1000, deterministic=True, seed=0,
-                     path_stride=0):
+                     path_stride=0, hazards=None):
     """Every robot i follows waypoints[i][:n_waypoints[i]] from start[i] under `model` (a PPO, or for the host path anything
     with `.predict`).  `env`: a DeviceGoalVecEnv (device path), an EnvWrapper, or an env name for `get_env` (host path; a
     fresh environment per robot for a name, the given one reused robot after robot otherwise).  Returns the dict described in
-    the module docstring."""
+    the module docstring.  hazards: a goal_rules.Hazards (hazard costs, see the module docstring)."""
     from .envs.vec_env import DeviceGoalVecEnv
     from .envs.wrapper import EnvWrapper, TimeLimit, get_env
     max_steps, path_stride = int(max_steps), int(path_stride)
@@ -117,7 +140,7 @@ def follow_waypoints(model, env, start, waypoints, n_waypoints=None, *, max_step
         raise ValueError("max_steps must be >= 1 and path_stride >= 0")
     if isinstance(env, DeviceGoalVecEnv):
         return env.follow(getattr(model, "engine", model), start, waypoints, n_waypoints, max_steps=max_steps,
-                          deterministic=deterministic, seed=seed, path_stride=path_stride)
+                          deterministic=deterministic, seed=seed, path_stride=path_stride, hazards=hazards)
     if isinstance(env, str):
         name = env
 
@@ -134,4 +157,4 @@ def follow_waypoints(model, env, start, waypoints, n_waypoints=None, *, max_step
         def make_env(i):
             return env
     s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
-    return _host_follow(model, make_env, s, wp, nw, max_steps, deterministic, seed, path_stride)
+    return _host_follow(model, make_env, s, wp, nw, max_steps, deterministic, seed, path_stride, hazards)
