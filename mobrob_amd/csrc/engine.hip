@@ -88,6 +88,10 @@ int fail(int code, const char* fmt, ...) {
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int rup(int a, int b) { return cdiv(a, b) * b; }
 
+// an environment variable as a number, `dflt` when it is not set (a switch that only asks "is it set" keeps its getenv)
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+inline double env_double(const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; }
+
 struct ProfSpan {
   hipEvent_t a, b;
   int id;
@@ -345,7 +349,7 @@ void launch_gemm_tiles(mobrob_ppo_engine* e, const GemmOp& a, const GemmOp* b) {
   // (weights): with the waves side by side along N the block fetches its A rows ONCE (L1 / one XCD's L2) where four column blocks
   // scattered over the chip fetched them four times -- at 65 536 x 256 x 256 that was 268 MB through L2 per launch against 67.
   // Only where the column tiles fill the four waves; the weight-gradient GEMM (both operands tall) keeps them stacked along M.
-  static const bool wn_on = getenv("MOBROB_GEMM_WN") == nullptr || atoi(getenv("MOBROB_GEMM_WN")) != 0;
+  static const bool wn_on = env_int("MOBROB_GEMM_WN", 1) != 0;
   GemmArgs ga = a.g, gb = b ? b->g : a.g;
   int gx = 1, gy = 1;
   for (GemmArgs* g : {&ga, &gb}) {
@@ -414,7 +418,7 @@ void launch_multi(mobrob_ppo_engine* e, const GemmOp* const* ops, int n) {
 // the j-th GEMMs of both networks go out pairwise where they are of the same kind (they always are at equal depths; the tails of
 // unequal depths, and a head opposite a hidden layer, go alone).  MOBROB_GEMM_PAIR=0: one launch per GEMM; =1: pairs only.
 void run_queues(mobrob_ppo_engine* e, const GemmQueue& qa, const GemmQueue& qb, int width) {
-  static const int pairing = getenv("MOBROB_GEMM_PAIR") == nullptr ? 2 : atoi(getenv("MOBROB_GEMM_PAIR"));
+  static const int pairing = env_int("MOBROB_GEMM_PAIR", 2);
   const size_t n = std::max(qa.size(), qb.size());
   for (size_t j0 = 0; j0 < n; j0 += width) {
     const GemmOp* st[4];
@@ -862,8 +866,7 @@ bool is_pinned(const void* p) {
 // nothing about an [N][D] array).
 const char* served_buffer_problem(const void* p, size_t bytes) {
   if (!p || bytes == 0) return "a null or empty buffer";
-  const char* hc = getenv("HIP_HOST_COHERENT");
-  const bool default_noncoherent = hc != nullptr && atoi(hc) == 0;
+  const bool default_noncoherent = env_int("HIP_HOST_COHERENT", 1) == 0;
   const char* ends[2] = {static_cast<const char*>(p), static_cast<const char*>(p) + bytes - 1};
   for (const char* q : ends) {
     hipPointerAttribute_t at;
@@ -1125,11 +1128,11 @@ int engine_create(const mobrob_ppo_config_t* cfg, void* arena, size_t arena_byte
   CHK(check_device(cfg));
   auto* e = new mobrob_ppo_engine();
   *out = e;  // so that destroy() can clean up after a partial failure
-  if (const char* v = getenv("MOBROB_ROLLOUT64_TILE_MAX")) e->rollout64_tile_max = atoi(v);  // 0: one-wave kernel only
-  if (const char* v = getenv("MOBROB_PAIR64_MIN_TILES")) e->pair64_min_tiles = atoi(v);  // 0: block kernel for large minibatches
-  if (const char* v = getenv("MOBROB_SPLIT64_MAX_TILES")) e->split64_max_tiles = atoi(v);  // 0: block kernel only (A/B, tests)
-  if (const char* v = getenv("MOBROB_EPOCH_KERNEL")) e->epoch_kernel_on = atoi(v) != 0;     // 0: three launches per optimizer step, always
-  if (const char* v = getenv("MOBROB_GEMM_TILES")) e->gemm_tiles = atoi(v);                 // generic chain: tiles per wave (launch_gemm)
+  e->rollout64_tile_max = env_int("MOBROB_ROLLOUT64_TILE_MAX", e->rollout64_tile_max);  // 0: one-wave kernel only
+  e->pair64_min_tiles = env_int("MOBROB_PAIR64_MIN_TILES", e->pair64_min_tiles);  // 0: block kernel for large minibatches
+  e->split64_max_tiles = env_int("MOBROB_SPLIT64_MAX_TILES", e->split64_max_tiles);  // 0: block kernel only (A/B, tests)
+  e->epoch_kernel_on = env_int("MOBROB_EPOCH_KERNEL", e->epoch_kernel_on) != 0; // 0: three launches per optimizer step, always
+  e->gemm_tiles = env_int("MOBROB_GEMM_TILES", e->gemm_tiles); // generic chain: tiles per wave (launch_gemm)
   CHK(engine_dims(e, cfg));
   HIPC(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   e->own_stream = true;
@@ -1357,29 +1360,43 @@ int mobrob_ppo_act(mobrob_ppo_engine_t* e, const float* obs, const float* eps, f
   return MOBROB_OK;
 }
 
+namespace {
+// does any of the rows [r0, r0 + n) end in a time-limit truncation the caller sent the terminal observation of?
+bool any_truncated(const uint8_t* truncated, const float* terminal_obs, int r0, int n) {
+  bool any = false;
+  if (truncated && terminal_obs)
+    for (int i = r0; i < r0 + n; ++i) any |= truncated[i] != 0;
+  return any;
+}
+// rollout_buffer.add of step e->t on the compute stream: V(terminal_obs) of the truncated rows (term_obs / trunc_dev already hold
+// them), rewards (+ bootstrap) and episode starts into the slot, then the step's dones become the next step's episode starts.
+// rew / dones: device-readable -- the caller's pinned buffers, or rew_tmp / dones_u8
+void store_step(mobrob_ppo_engine* e, const float* rew, const uint8_t* dones, bool any_trunc) {
+  const size_t o = (size_t)e->t * e->N;
+  if (any_trunc) value_flagged(e, e->term_obs, e->trunc_dev, e->term_val);
+  hipLaunchKernelGGL(k_store_step, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, rew, e->prev_dones,
+                     any_trunc ? e->trunc_dev : nullptr, e->term_val, (float)e->cfg.gamma, e->N, e->rewards + o, e->es + o);
+  hipLaunchKernelGGL(k_u8_to_f32, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, dones, e->prev_dones, e->N);
+}
+}  // namespace
+
 int mobrob_ppo_store(mobrob_ppo_engine_t* e, const float* rewards, const uint8_t* dones, const uint8_t* truncated,
                      const float* terminal_obs) {
   if (!e || !rewards || !dones) return fail(MOBROB_ERR_INVALID, "store: null argument");
   if (e->t >= e->T) return fail(MOBROB_ERR_STATE, "store: rollout buffer full");
   CHK(streamer_init(e));
   const size_t N = e->N, D = e->D;
+  const bool any_trunc = any_truncated(truncated, terminal_obs, 0, e->N);
   if (is_pinned(rewards) && is_pinned(dones) && (!truncated || is_pinned(truncated)) &&
       (!terminal_obs || is_pinned(terminal_obs))) {
     // Pinned fast path: the kernels read the caller's buffers in place.  The caller may overwrite them only after
     // the next act() has returned (act synchronises the compute stream) -- the order every rollout loop has.
-    bool any = false;
-    if (truncated && terminal_obs)
-      for (size_t i = 0; i < N; ++i) any |= truncated[i] != 0;
-    if (any) {
+    if (any_trunc) {
       hipLaunchKernelGGL(k_pull_rows, dim3(cdiv((int)(N * e->Dp), 256)), dim3(256), 0, e->stream, terminal_obs, e->term_obs,
                          (int)N, (int)D, e->Dp);
       HIPC(hipMemcpyAsync(e->trunc_dev, truncated, N, hipMemcpyHostToDevice, e->stream));
-      value_flagged(e, e->term_obs, e->trunc_dev, e->term_val);
     }
-    hipLaunchKernelGGL(k_store_step, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, rewards, e->prev_dones,
-                       any ? e->trunc_dev : nullptr, e->term_val, (float)e->cfg.gamma, e->N,
-                       e->rewards + (size_t)e->t * N, e->es + (size_t)e->t * N);
-    hipLaunchKernelGGL(k_u8_to_f32, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, dones, e->prev_dones, e->N);
+    store_step(e, rewards, dones, any_trunc);
     HIPC(hipGetLastError());
     e->t++;
     return MOBROB_OK;
@@ -1392,9 +1409,6 @@ int mobrob_ppo_store(mobrob_ppo_engine_t* e, const float* rewards, const uint8_t
   memcpy(st.dones, dones, N);
   HIPC(hipMemcpyAsync(e->rew_tmp, st.rew, N * 4, hipMemcpyHostToDevice, e->cstream));
   HIPC(hipMemcpyAsync(e->dones_u8, st.dones, N, hipMemcpyHostToDevice, e->cstream));
-  bool any_trunc = false;
-  if (truncated && terminal_obs)
-    for (size_t i = 0; i < N; ++i) any_trunc |= truncated[i] != 0;
   if (any_trunc) {
     memcpy(st.trunc, truncated, N);
     memcpy(st.term, terminal_obs, N * D * 4);
@@ -1403,11 +1417,7 @@ int mobrob_ppo_store(mobrob_ppo_engine_t* e, const float* rewards, const uint8_t
   }
   HIPC(hipEventRecord(e->ev_store, e->cstream));
   HIPC(hipStreamWaitEvent(e->stream, e->ev_store, 0));
-  if (any_trunc) value_flagged(e, e->term_obs, e->trunc_dev, e->term_val);
-  hipLaunchKernelGGL(k_store_step, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, e->rew_tmp, e->prev_dones,
-                     any_trunc ? e->trunc_dev : nullptr, e->term_val, (float)e->cfg.gamma, e->N,
-                     e->rewards + (size_t)e->t * N, e->es + (size_t)e->t * N);
-  hipLaunchKernelGGL(k_u8_to_f32, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, e->dones_u8, e->prev_dones, e->N);
+  store_step(e, e->rew_tmp, e->dones_u8, any_trunc);
   // the next step's H2D of rew_tmp/dones_u8 must not overtake these kernels
   HIPC(hipEventRecord(e->ev_k, e->stream));
   HIPC(hipStreamWaitEvent(e->cstream, e->ev_k, 0));
@@ -1470,9 +1480,7 @@ int mobrob_ppo_store_part(mobrob_ppo_engine_t* e, int32_t part, int32_t nparts, 
   if (!is_pinned_cached(e, rewards) || !is_pinned_cached(e, dones) || (truncated && !is_pinned_cached(e, truncated)) ||
       (terminal_obs && !is_pinned_cached(e, terminal_obs)) || (next_obs && !is_pinned_cached(e, next_obs)))
     return fail(MOBROB_ERR_INVALID, "store_part needs device-visible pinned buffers (mobrob_ppo_host_alloc)");
-  bool any = false;
-  if (truncated && terminal_obs)
-    for (int i = r0; i < r0 + n; ++i) any |= truncated[i] != 0;
+  const bool any = any_truncated(truncated, terminal_obs, r0, n);
   const size_t o = (size_t)t * e->N + r0;
   StorePullArgs a{};
   a.rew_in = rewards + r0; a.dones = dones + r0;
@@ -1495,10 +1503,523 @@ int mobrob_ppo_store_part(mobrob_ppo_engine_t* e, int32_t part, int32_t nparts, 
   return MOBROB_OK;
 }
 
+int mobrob_ppo_finish_rollout(mobrob_ppo_engine_t* e, const float* last_obs, const uint8_t* dones) {
+  if (!e || !last_obs || !dones) return fail(MOBROB_ERR_INVALID, "finish_rollout: null argument");
+  if (e->t != e->T) return fail(MOBROB_ERR_STATE, "finish_rollout: %d of %d steps stored", e->t, e->T);
+  CHK(streamer_init(e));
+  const size_t N = e->N;
+  auto& st = e->stage[e->stage_i];
+  float* slot = e->obs + (size_t)e->T * N * e->Dp;
+  const float* src = stage_in(last_obs, st.obs, N * e->D);
+  CHK(upload_obs_on(e, e->cstream, src, slot, e->N));
+  memcpy(st.dones, dones, N);
+  HIPC(hipMemcpyAsync(e->dones_u8, st.dones, N, hipMemcpyHostToDevice, e->cstream));
+  HIPC(hipEventRecord(e->ev_in, e->cstream));
+  HIPC(hipStreamWaitEvent(e->stream, e->ev_in, 0));
+  hipLaunchKernelGGL(k_u8_to_f32, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, e->dones_u8, e->last_dones, e->N);
+  forward(e, slot, e->N, false, nullptr, true, e->last_values);
+  run_gae(e);
+  HIPC(hipStreamSynchronize(e->stream));
+  e->rollout_ready = true; e->train_rec_valid = false;
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_compute_gae(mobrob_ppo_engine_t* e) {
+  if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
+  run_gae(e);
+  HIPC(hipStreamSynchronize(e->stream));
+  e->rollout_ready = true; e->train_rec_valid = false;
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_x3_mode(const mobrob_ppo_engine_t* e) {
+  if (!e || !e->fused.enabled || e->fused.net[0].W2x == nullptr) return 0;
+  return 1 | (e->fused.train_x3 ? 2 : 0) | (e->fused.train_x3 && e->fused.train_chain ? 4 : 0);
+}
+
+int mobrob_ppo_update_mode(const mobrob_ppo_engine_t* e) { return e ? e->last_update_mode : 0; }
+
+int mobrob_ppo_explained_variance(mobrob_ppo_engine_t* e, double* out) {
+  if (!e || !out) return fail(MOBROB_ERR_INVALID, "explained_variance: null argument");
+  if (!e->rollout_ready) return fail(MOBROB_ERR_STATE, "explained_variance: rollout not finished");
+  const int n = e->N * e->T;
+  hipLaunchKernelGGL(k_explained_variance_partials, dim3(kEvBlocks), dim3(256), 0, e->stream, e->values, e->ret, n, e->expvar_part);
+  double part[kEvBlocks * 4];
+  HIPC(hipMemcpyAsync(part, e->expvar_part, sizeof part, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = 0; b < kEvBlocks; ++b)
+    for (int k = 0; k < 4; ++k) s[k] += part[b * 4 + k];
+  const double var_y = s[1] / n - (s[0] / n) * (s[0] / n), var_d = s[3] / n - (s[2] / n) * (s[2] / n);
+  *out = var_y > 0.0 ? 1.0 - var_d / var_y : NAN;  // SB3: nan when the returns do not vary
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_mark_rollout_ready(mobrob_ppo_engine_t* e) {
+  if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
+  e->rollout_ready = true; e->train_rec_valid = false;
+  e->t = e->T;
+  return MOBROB_OK;
+}
+
 namespace {
-// defined behind the device-rollout code it shares (enqueue of the persistent kernel's chunks and the overlapped value passes)
+// enqueue one whole device-resident rollout (T steps + last values + GAE) on the engine stream
+uint64_t env_seed_of(const mobrob_ppo_engine* e) {
+  return e->cfg.seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(e->cfg.rank + 1));
+}
+
+// One persistent launch for all T steps (policy forward + sample + env + store), then the value network over all
+// stored observations in one batched pass, then GAE (kernels_rollout.h).
+bool rollout_persistent_ok(const mobrob_ppo_engine* e) {
+  return e->cfg.rollout_persistent && e->fused.enabled;  // both fused widths (256: kernels_rollout.h top, 64: bottom)
+}
+// side stream and events of the overlapped value pass: created OUTSIDE any stream capture (resource creation is
+// not a capturable operation)
+int rollout_side_stream_init(mobrob_ppo_engine* e) {
+  if (!e->vstream) {
+    HIPC(hipStreamCreateWithFlags(&e->vstream, hipStreamNonBlocking));
+    HIPC(hipEventCreateWithFlags(&e->ev_vdone, hipEventDisableTiming));
+  }
+  while ((int)e->ev_chunks.size() < e->T / 16 + 2) {  // chunks are >= 16 steps
+    hipEvent_t ev;
+    HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    e->ev_chunks.push_back(ev);
+  }
+  return MOBROB_OK;
+}
+
+// ---- the persistent rollout kernels in chunks: device rollouts and the served host rollout (collect_host_served) ----
+// What a device rollout and a served one pass the kernel alike: the policy's packs, the sampling constants, the value network of
+// the time-limit bootstrap, the dims and every arena pointer.  The caller adds its kind, counters and environment.
+RolloutArgs rollout_args(mobrob_ppo_engine* e) {
+  RolloutArgs a{};
+  a.pi = e->fused.net[0];
+  a.log_std = Pp(e, T_LOGSTD); a.seed = eps_seed(e);
+  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
+  a.bt = BootArgs{Pp(e, T_VW1), Pp(e, T_VB1), Pp(e, T_VW2), Pp(e, T_VB2), Pp(e, T_VW), Pp(e, T_VB), e->G1, e->G2,
+                  (float)e->cfg.gamma, e->term_val};  // (fused path: two tanh layers)
+  a.N = e->N; a.D = e->D; a.A = e->A;
+  a.obs = e->obs; a.actions = e->actions; a.logp = e->logp; a.rewards = e->rewards; a.es = e->es;
+  a.term_obs = e->term_obs; a.trunc = e->trunc_dev; a.clip_act = e->clip_act;
+  a.ep_len = e->ep_len; a.prev_dones = e->prev_dones; a.gstate = e->gstate[0]; a.ep_stats = e->ep_stats;
+  return a;
+}
+
+bool wide_nets(const mobrob_ppo_engine* e) { return e->fused.H == FH; }  // of a fused engine: 256-wide, else 64-wide
+// 64-wide: one workgroup per 32-env tile (k_rollout64_tile) while every tile gets a CU of its own, else the one-wave kernel
+bool rollout64_tile_kernel(const mobrob_ppo_engine* e) { return cdiv(e->N, 32) <= e->rollout64_tile_max; }
+// x3 engines: the eight-wave form with W2's leading pieces stationary in registers (kernels_rollout.h, S8);
+// MOBROB_ROLLOUT_S8=0 keeps the four-wave form (A/B and the bit-equality test of the two)
+bool rollout_s8(const mobrob_ppo_engine* e) {
+  static const bool s8_on = !kRolloutStationary && env_int("MOBROB_ROLLOUT_S8", 1) != 0;
+  return s8_on && e->fused.net[0].W2x != nullptr;
+}
+
+// A rollout of <= 192 tiles (32 envs each, one workgroup, ~100 KB of LDS at 256 wide) leaves CUs idle for thousands of dependent
+// steps: it is cut into chunks, and the observations of a finished chunk are valued on the side stream, behind an event, while the
+// next chunk rolls out.  64-wide: the tile kernel only, and only when the value pass is more than a few launches' worth of work.
+// vgrid_max: workgroups of a side-stream value pass (256-wide), what the rollout leaves free.
+struct ChunkPlan {
+  bool overlap;
+  int chunk, vgrid_max;
+};
+ChunkPlan chunk_plan(bool wide, int tiles, bool tile_kernel, int T, int N) {
+  const bool overlap = tiles <= 192 && (wide || (tile_kernel && (size_t)T * N >= ((size_t)1 << 18)));  // otherwise the rollout itself fills the device
+  return ChunkPlan{overlap, overlap ? std::max(16, cdiv(T, 20)) : T, overlap ? std::max(32, 256 - tiles) : 256};
+}
+
+// steps [a.t0, a.t1) of the rollout on the compute stream: the one place that picks the kernel
+void launch_rollout_kernel(mobrob_ppo_engine* e, const RolloutArgs& a) {
+  const int Dp = e->Dp, tiles = cdiv(a.N, 32);
+  if (!wide_nets(e)) {  // 64-wide nets (kernels_rollout.h, bottom half)
+    if (a.kind == 3) {  // (served: within the tile kernel's range, collect_host_served)
+      FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout64_tile<DPc, 3>), dim3(tiles), dim3(256), rollout64_tile_lds_bytes(Dp, true), e->stream, a));
+    } else if (rollout64_tile_kernel(e)) {
+      FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout64_tile<DPc>), dim3(tiles), dim3(256), rollout64_tile_lds_bytes(Dp), e->stream, a));
+    } else {
+      const int nwv = rollout64_waves(Dp);
+      FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout64_persistent<DPc>), dim3(cdiv(tiles, nwv)), dim3(nwv * 64), rollout64_lds_bytes(Dp), e->stream, a));
+    }
+    return;
+  }
+  const bool s8 = a.kind == 3 || rollout_s8(e);  // (served: eight-wave x3 engines only, collect_host_served)
+  const dim3 grid(tiles), block(kRolloutThreads);
+  const size_t lds = rollout_lds_bytes(Dp, s8);
+  if (a.kind == 3) {
+    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 3, true>), grid, block, lds, e->stream, a));
+  } else if (s8 && a.kind == 1) {
+    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 1, true>), grid, block, lds, e->stream, a));
+  } else if (s8) {
+    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 2, true>), grid, block, lds, e->stream, a));
+  } else if (a.kind == 1) {
+    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 1>), grid, block, lds, e->stream, a));
+  } else {
+    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 2>), grid, block, lds, e->stream, a));
+  }
+}
+
+// V of the stored observation rows [r0, r1) into values[r0, r1) on stream `st`; grid_max caps the 256-wide kernel's workgroups
+void value_rows(mobrob_ppo_engine* e, hipStream_t st, int r0, int r1, int grid_max) {
+  const int Dp = e->Dp;
+  if (!wide_nets(e)) {
+    fused_forward(e->fused, e->obs + (size_t)r0 * Dp, r1 - r0, false, nullptr, e->Ap, true, e->values + r0, st);
+    return;
+  }
+  FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_value_batch<DPc>), dim3(std::min(grid_max, cdiv(r1 - r0, FR))), dim3(FTHREADS),
+                                           e->fused.lds_bytes, st, e->fused.net[1], e->obs + (size_t)r0 * Dp, r1 - r0, e->values + r0));
+}
+
+// The T steps as chunks of the plan on the compute stream; V of every chunk but the last on the side stream (chunk_plan).
+int enqueue_rollout_chunks(mobrob_ppo_engine* e, RolloutArgs& a, const ChunkPlan& pl) {
+  const int N = e->N, T = e->T;
+  ProfScope ps(e, MOBROB_K_ENV);
+  for (int t0 = 0; t0 < T; t0 += pl.chunk) {
+    a.t0 = t0; a.t1 = std::min(T, t0 + pl.chunk);
+    launch_rollout_kernel(e, a);
+    if (pl.overlap && a.t1 < T) {  // observations [t0, t1) are final: value them on the side stream
+      hipEvent_t ev = e->ev_chunks[t0 / pl.chunk];
+      HIPC(hipEventRecord(ev, e->stream));
+      HIPC(hipStreamWaitEvent(e->vstream, ev, 0));
+      value_rows(e, e->vstream, t0 * N, a.t1 * N, pl.vgrid_max);
+    }
+  }
+  return MOBROB_OK;
+}
+// ... and V of what the side stream did not take, rows up to rows_end, on the compute stream (the rollout is over: the whole
+// device), which then waits for the side stream.  rows_end: (T + 1) N for a device rollout (obs[T] is the last observation and
+// values[T N ..] = last_values), T N for a served one (V(last_obs) is finish_rollout's).
+int value_rollout_tail(mobrob_ppo_engine* e, const ChunkPlan& pl, int rows_end) {
+  ProfScope ps(e, MOBROB_K_ACT);
+  const int done_rows = pl.overlap ? ((e->T - 1) / pl.chunk) * pl.chunk * e->N : 0;
+  value_rows(e, e->stream, done_rows, rows_end, 256);
+  if (pl.overlap && done_rows > 0) {  // join the side stream before GAE
+    HIPC(hipEventRecord(e->ev_vdone, e->vstream));
+    HIPC(hipStreamWaitEvent(e->stream, e->ev_vdone, 0));
+  }
+  return MOBROB_OK;
+}
+
+// Behind the last step of a device rollout: the device-resident counters move on by the T steps taken, and the dones the last
+// step left are the rollout's last_dones.  (What follows -- V(last_obs), then run_gae -- differs per caller and keeps its place
+// in the launch order.)
+int end_device_steps(mobrob_ppo_engine* e) {
+  hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(64), 0, e->stream, e->ctr_dev, (uint32_t)e->T, (uint32_t)e->T);
+  HIPC(hipMemcpyAsync(e->last_dones, e->prev_dones, (size_t)e->N * 4, hipMemcpyDeviceToDevice, e->stream));
+  return MOBROB_OK;
+}
+
+int enqueue_rollout_persistent(mobrob_ppo_engine* e, const mobrob_ppo_engine::RolloutSpec& sp) {
+  const int N = e->N, T = e->T;
+  const size_t slot = (size_t)N * e->Dp;
+  HIPC(hipMemcpyAsync(e->obs, e->obs + (size_t)T * slot, slot * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (wide_nets(e) && !e->fused.train_x3) pack_x3_all(e);  // otherwise every optimizer step (apply_adam) and set_params keep the x3 packs current
+  RolloutArgs a = rollout_args(e);
+  a.kind = sp.kind; a.env_seed = env_seed_of(e); a.draw_base = e->ctr_dev; a.step_base = e->ctr_dev + 1;
+  a.p_term = sp.p_term; a.time_limit = sp.time_limit; a.goal = sp.goal;
+  const ChunkPlan pl = chunk_plan(wide_nets(e), cdiv(N, 32), rollout64_tile_kernel(e), T, N);
+  CHK(enqueue_rollout_chunks(e, a, pl));
+  CHK(end_device_steps(e));
+  CHK(value_rollout_tail(e, pl, (T + 1) * N));
+  run_gae(e);
+  return MOBROB_OK;
+}
+
+int enqueue_rollout(mobrob_ppo_engine* e, const mobrob_ppo_engine::RolloutSpec& sp) {
+  if (rollout_persistent_ok(e)) return enqueue_rollout_persistent(e, sp);
+  const int N = e->N, Dp = e->Dp, per = Dp / 4;
+  const size_t slot = (size_t)N * Dp;
+  const uint64_t env_seed = env_seed_of(e);
+  // the previous rollout's last observation is this rollout's first
+  HIPC(hipMemcpyAsync(e->obs, e->obs + (size_t)e->T * slot, slot * 4, hipMemcpyDeviceToDevice, e->stream));
+  const BootNetArgs bt = boot_args(e);
+  const size_t sm = env_step_lds_bytes(Dp, value_net_width_sum(e));
+  for (int t = 0; t < e->T; ++t) {
+    act_slot(e, t, nullptr, true);
+    {
+      ProfScope ps(e, MOBROB_K_ENV);
+      // env step + rollout_buffer.add scalars + time-limit bootstrap of the (rare) truncated rows in one launch
+      if (sp.kind == 1) {
+        hipLaunchKernelGGL(k_env_step_store, dim3(cdiv(N * per, 256)), dim3(256), sm, e->stream, env_seed, (uint32_t)t,
+                           e->ctr_dev + 1, N, e->D, Dp, sp.p_term, sp.time_limit, e->ep_len, e->ep_len2,
+                           e->obs + (size_t)(t + 1) * slot, e->term_obs, e->prev_dones, e->dones_tmp, e->trunc_dev,
+                           e->rewards + (size_t)t * N, e->es + (size_t)t * N, bt);
+        std::swap(e->ep_len, e->ep_len2);
+      } else {
+        GoalEnvArgs g{};
+        g.seed = env_seed; g.step_rel = (uint32_t)t; g.step_base = e->ctr_dev + 1;
+        g.N = N; g.D = e->D; g.Dp = Dp; g.A = e->A; g.p = sp.goal;
+        g.act = e->clip_act; g.st_in = e->gstate[0]; g.st_out = e->gstate[1];
+        g.obs_next = e->obs + (size_t)(t + 1) * slot; g.term_obs = e->term_obs;
+        g.prev_dones = e->prev_dones; g.next_dones = e->dones_tmp; g.trunc = e->trunc_dev;
+        g.rew_out = e->rewards + (size_t)t * N; g.es_out = e->es + (size_t)t * N; g.ep_stats = e->ep_stats;
+        hipLaunchKernelGGL(k_goal_env_step_store, dim3(cdiv(N * per, 256)), dim3(256), sm, e->stream, g, bt);
+        std::swap(e->gstate[0], e->gstate[1]);
+      }
+    }
+    std::swap(e->prev_dones, e->dones_tmp);
+  }
+  CHK(end_device_steps(e));
+  forward(e, e->obs + (size_t)e->T * slot, N, false, nullptr, true, e->last_values);
+  run_gae(e);
+  return MOBROB_OK;
+}
+
+// device-resident rollout of either env kind: (re)start the env if needed, then replay / enqueue the T-step loop
+int collect_device(mobrob_ppo_engine* e, const mobrob_ppo_engine::RolloutSpec& sp) {
+  const int N = e->N, Dp = e->Dp, per = Dp / 4;
+  const size_t slot = (size_t)N * Dp;
+  if (e->env_started != sp.kind) {
+    float* last = e->obs + (size_t)e->T * slot;  // reset writes the "previous last observation"
+    if (sp.kind == 1) {
+      hipLaunchKernelGGL(k_env_reset, dim3(cdiv(N * per, 256)), dim3(256), 0, e->stream, env_seed_of(e), N, e->D, Dp, last,
+                         e->ep_len);
+    } else {
+      hipLaunchKernelGGL(k_goal_env_reset, dim3(cdiv(N * per, 256)), dim3(256), 0, e->stream, env_seed_of(e), N, e->D, Dp,
+                         sp.goal, e->gstate[0], last);
+      HIPC(hipMemsetAsync(e->ep_stats, 0, kEpStatsDoubles * sizeof(double), e->stream));
+      e->ep_ring_read = 0;
+    }
+    std::vector<float> ones(N, 1.0f);  // a fresh env starts every episode: `_last_episode_starts` all True
+    HIPC(hipMemcpyAsync(e->prev_dones, ones.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipStreamSynchronize(e->stream));
+    e->env_started = sp.kind;
+  }
+  e->rollout_ready = false; e->train_rec_valid = false;
+  if (rollout_persistent_ok(e)) CHK(rollout_side_stream_init(e));
+  // Graph replay: every kernel argument of the T-step loop is fixed (slot pointers, ping-pong buffers with even T,
+  // counters relative to device-resident bases), so the loop is captured once and replayed per rollout.
+  // The persistent path is ~45 launches on two streams: enqueued eagerly (the launches hide behind the 18 ms of
+  // GPU work; a captured multi-stream graph was both slower to launch and, after many capture / destroy cycles in
+  // one process, crashed inside the runtime).  Only the per-step path (thousands of launches) is replayed as a graph.
+  bool use_graph = e->cfg.rollout_graph && e->T % 2 == 0 && !rollout_persistent_ok(e);
+  if (use_graph && (e->ro_exec == nullptr || memcmp(&e->ro_spec, &sp, sizeof sp) != 0)) {
+    HIPC(hipStreamSynchronize(e->stream));  // never destroy an executable graph that may still be running
+    if (e->ro_exec) { (void)hipGraphExecDestroy(e->ro_exec); e->ro_exec = nullptr; }
+    if (e->ro_graph) { (void)hipGraphDestroy(e->ro_graph); e->ro_graph = nullptr; }
+    const bool prof = e->prof_on;
+    e->prof_on = false;  // event records cannot be part of the captured graph
+    hipError_t be = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal);
+    if (be != hipSuccess) {  // e.g. a stream that does not support capture: run eagerly from now on
+      (void)hipGetLastError();
+      e->prof_on = prof;
+      e->cfg.rollout_graph = 0;
+      use_graph = false;
+    } else {
+      const int rc = enqueue_rollout(e, sp);
+      hipError_t ce = hipStreamEndCapture(e->stream, &e->ro_graph);
+      e->prof_on = prof;
+      if (rc != MOBROB_OK) return rc;
+      if (ce != hipSuccess) return fail(MOBROB_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+      HIPC(hipGraphInstantiate(&e->ro_exec, e->ro_graph, nullptr, nullptr, 0));
+      memcpy(&e->ro_spec, &sp, sizeof sp);
+    }
+  }
+  if (!use_graph) {
+    CHK(enqueue_rollout(e, sp));
+  } else {
+    ProfScope ps(e, MOBROB_K_ACT);  // with graph replay the ACT scope covers the whole rollout (forward+env+GAE)
+    HIPC(hipGraphLaunch(e->ro_exec, e->stream));
+  }
+  HIPC(hipGetLastError());
+  e->t = e->T;
+  e->rollout_ready = true; e->train_rec_valid = false;
+  return MOBROB_OK;
+}
+
+// Host environments SERVED by the persistent rollout kernel (round 5; kernels_rollout.h, KIND 3).  The launch-per-step collector above
+// pays, per row range and step, two kernel launches, an event, the event's completion latency and the weight stream of a fresh
+// k_fused_act -- 74 - 76 us of GPU-side time per vector step of 4096 envs against 10 us for the same arithmetic inside the device
+// rollout.  Here the device rollout's own kernel runs the policy (weights stationary, S8) and its env phase is the host's: a
+// workgroup writes its rows' clipped actions into the caller's pinned buffer, raises its flag word in pinned memory and polls the
+// host's word for its row range; the host waits for the flags of a range, steps it, raises its word.  No HIP call inside the step
+// loop.  Same Philox counters, same forward / sampling / storage / bootstrap code as the device rollout; against the launch-per-step
+// collector the buffers agree to float32 rounding (its k_fused_act runs the policy on the f32 pipe, the rollout kernel on the bf16
+// pipe with split operands: the same relation the device rollout has to its per-step form), what the kernel only moves -- clipped
+// actions to the host, rewards / observations from it -- is exact (tests/test_engine_gpu.py::test_served_host_rollout_...).
+// Conditions (else *served stays false and the caller runs the launch-per-step loop): 256-wide x3 engine with the eight-wave rollout
+// kernel, or (round 6) a 64-wide engine within the tile kernel's range (k_rollout64_tile<.., 3>: the shape of every reference config);
+// whole 32-row tiles per row range, every workgroup resident at once (tiles <= CUs: a waiting workgroup never yields its CU),
+// coherent pinned buffers (served_buffer_problem), no announced co-tenant of the device.  MOBROB_COLLECT_SERVER=0 switches it off; MOBROB_SERVER_TIMEOUT_S (default 60) bounds every wait on either side.
 int collect_host_served(mobrob_ppo_engine* e, mobrob_env_step_range_fn step_range, void* env, int nparts, float* obs,
-                        float* actions_clipped, float* rewards, uint8_t* dones, uint8_t* truncated, float* terminal_obs, bool* served);
+                        float* actions_clipped, float* rewards, uint8_t* dones, uint8_t* truncated, float* terminal_obs, bool* served) {
+  *served = false;
+  const int mode = env_int("MOBROB_COLLECT_SERVER", 1);   // 0 off, 1 when possible, 2 required (tests); read per rollout
+  const int N = e->N, T = e->T, Dp = e->Dp;
+  const int rblocks = cdiv(N, 32);
+  if (mode == 0) return MOBROB_OK;
+  const char* why = nullptr;
+  int cus = 0;
+  const bool wide = e->fused.enabled && wide_nets(e);   // 256-wide: k_rollout_persistent<.., 3, S8>; 64-wide: k_rollout64_tile<.., 3>
+  if (!rollout_persistent_ok(e)) why = "the fused persistent rollout kernels are off for this engine";
+  else if (wide && !rollout_s8(e)) why = "not a 256-wide x3 engine with the eight-wave rollout kernel";
+  else if (!wide && (e->fused.H != GH || !rollout64_tile_kernel(e))) why = "not a 64-wide engine within the tile kernel's range";
+  else if (getenv("MOBROB_COLLECT_TIMING") || env_int("MOBROB_COLLECT_THREADS", 0) != 0) why = "an instrumented / threaded collector was asked for";
+  // a 32-row tile must not straddle two row ranges; ONE range takes any number of environments (the reference YAMLs: 2 - 16, half a tile)
+  else if (nparts < 1 || nparts > MOBROB_MAX_PARTS || (nparts > 1 && (N % nparts != 0 || (N / nparts) % 32 != 0))) why = "row ranges are not whole 32-row tiles";
+  else if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device_id) != hipSuccess || rblocks > cus) why = "more tiles than compute units";
+  // Other tenants of the device that this process cannot count: ranks rehearsing data parallelism on ONE device, a CU mask.  Every
+  // workgroup of a served rollout must be resident at once (a waiting workgroup never yields its CU), so with them the launch-per-step
+  // collector -- which always works -- is the one that runs.  (A tenant nobody announced is caught by the residency check below.)
+  else if (env_int("MOBROB_DP_SAME_DEVICE", 0) != 0 && e->cfg.world_size > 1) why = "several data-parallel ranks share this device (MOBROB_DP_SAME_DEVICE)";
+  else if (getenv("HSA_CU_MASK") || getenv("ROC_GLOBAL_CU_MASK")) why = "a compute-unit mask is set (HSA_CU_MASK / ROC_GLOBAL_CU_MASK)";
+  else {
+    const size_t N_ = (size_t)N;
+    const struct { const void* p; size_t bytes; } bufs[6] = {{obs, N_ * e->D * 4}, {actions_clipped, N_ * e->A * 4}, {rewards, N_ * 4},
+                                                              {dones, N_}, {truncated, N_}, {terminal_obs, N_ * e->D * 4}};
+    for (const auto& b : bufs)
+      if (!why) why = served_buffer_problem(b.p, b.bytes);
+  }
+  // Every workgroup of a served rollout must be resident at once, and it keeps its compute unit until the host has stepped all n_steps:
+  // engines of ONE process that collect at the same time (a fleet's threads) share a DEVICE's compute units through that device's
+  // counter -- the one that does not fit takes the launch-per-step path instead of queueing behind a kernel that waits for a host.
+  constexpr int kLeaseDevices = 64;
+  static std::atomic<int> cus_serving[kLeaseDevices];   // zero-initialised (static storage)
+  std::atomic<int>& dev_lease = cus_serving[(unsigned)e->cfg.device_id % kLeaseDevices];
+  struct Lease {
+    std::atomic<int>& c; int n; bool held;
+    ~Lease() { if (held) c.fetch_sub(n); }
+  } lease{dev_lease, rblocks, false};
+  if (!why) {
+    if (dev_lease.fetch_add(rblocks) + rblocks > cus) { dev_lease.fetch_sub(rblocks); why = "the device's compute units are serving another engine's rollout"; }
+    else lease.held = true;
+  }
+  if (why) return mode == 2 ? fail(MOBROB_ERR_STATE, "collect_host: MOBROB_COLLECT_SERVER=2 but %s", why) : MOBROB_OK;
+  CHK(rollout_side_stream_init(e));
+  CHK(streamer_init(e));
+  constexpr int kHostWords = 16 * MOBROB_MAX_PARTS;
+  constexpr int kStampWords = 64 * 8 * 2;   // -DMOBROB_SERVE_STAMPS builds: 64 steps x 8 stamps (long long) of workgroup 0
+  const int fb = (rblocks + 15) / 16 * 16;
+  if (!e->srv_flags || e->srv_blocks < fb) {
+    if (e->srv_flags) (void)hipHostFree(e->srv_flags);
+    e->srv_flags = nullptr;
+    HIPC(hipHostMalloc((void**)&e->srv_flags, (size_t)(fb + kHostWords + 16 + kStampWords) * sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
+    e->srv_blocks = fb;
+  }
+  if (!e->srv_abort) HIPC(hipMalloc((void**)&e->srv_abort, 256));   // abort word | one 8-byte relay word per row range
+  unsigned* gpu_flag = e->srv_flags;
+  unsigned* host_flag = e->srv_flags + e->srv_blocks;
+  int* err_word = reinterpret_cast<int*>(host_flag + kHostWords);
+  memset(e->srv_flags, 0, (size_t)(e->srv_blocks + kHostWords + 16 + kStampWords) * sizeof(unsigned));
+  HIPC(hipMemsetAsync(e->srv_abort, 0, 256, e->stream));
+  const double timeout_s = env_double("MOBROB_SERVER_TIMEOUT_S", 60.0);
+
+  // slot 0 <- the environments' current observations (the kernel reads its first tile from the slot, like the device rollout)
+  hipLaunchKernelGGL(k_pull_rows, dim3(cdiv(N * Dp, 256)), dim3(256), 0, e->stream, obs, e->obs, N, e->D, Dp);
+  if (wide && !e->fused.train_x3) pack_x3_all(e);
+  RolloutArgs a = rollout_args(e);
+  a.kind = 3; a.draw0 = e->draw_ro0;   // (host-side draw counter; no env seed, no device step counter)
+  a.clip_act = actions_clipped;        // (the caller's pinned buffer)
+  a.h_obs = obs; a.h_rew = rewards; a.h_done = dones; a.h_trunc = truncated; a.h_term = terminal_obs;
+  a.h_gpu_flag = gpu_flag; a.h_host_flag = host_flag; a.h_error = err_word; a.abort_dev = e->srv_abort;
+  a.rows_per_part = N / nparts; a.timeout_ticks = (long long)(timeout_s * 1e8);
+  if (!wide)   // the served tile kernel's dynamic LDS exceeds 64 KB at 64 observation columns (per device and cheap: set per rollout)
+    FUSED_DISPATCH_DP(Dp, HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout64_tile<DPc, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)rollout64_tile_lds_bytes(Dp, true))));
+
+  // From the first KIND-3 launch on, EVERY way out of this function but the normal one tells the (possibly resident, possibly
+  // waiting) workgroups to stop first: they would otherwise spin for the whole timeout and the next synchronising call with them.
+  // The normal way out disarms it: the host has published step T of every row range, so nothing is left waiting.
+  struct StopServing {
+    mobrob_ppo_engine* e; unsigned* host_flag; int nparts; bool armed;
+    ~StopServing() {
+      if (!armed) return;
+      for (int p = 0; p < nparts; ++p) __atomic_store_n(reinterpret_cast<unsigned long long*>(&host_flag[16 * p]), 0xFFFFFFFFull, __ATOMIC_RELEASE);
+      (void)hipStreamSynchronize(e->stream);
+      (void)hipStreamSynchronize(e->vstream);
+    }
+  } stop{e, host_flag, nparts, true};
+  // chunks of the step loop on the compute stream, V(obs) of a finished chunk on the side stream: the device rollouts' path
+  const ChunkPlan pl = chunk_plan(wide, rblocks, true, T, N);   // (64-wide: within the tile kernel's range, checked above)
+  CHK(enqueue_rollout_chunks(e, a, pl));
+  CHK(value_rollout_tail(e, pl, T * N));   // V(last_obs) is finish_rollout's
+  HIPC(hipGetLastError());
+
+  // ---- the host's side of the step loop: wait for the flags of a row range, step it, raise the range's word ----
+  auto now_s = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
+  const int bpp = nparts == 1 ? rblocks : (N / nparts) / 32;   // workgroups per row range
+  {
+    // Residency check, before the environment is touched: the clipped actions of step 0 of EVERY workgroup within a short bound
+    // (MOBROB_SERVER_RESIDENCY_S, default 2 s; a resident workgroup needs ~25 us).  A workgroup that is not resident -- another
+    // process on the device, a CU mask nobody announced -- would leave the resident ones waiting for the host while the host waits
+    // for it: instead of stalling for the whole timeout and failing the rollout, the launches are told to stop and the caller runs
+    // the launch-per-step collector from the untouched rollout state (nothing has been stepped, no counter has moved).
+    const double bound = env_double("MOBROB_SERVER_RESIDENCY_S", 2.0);
+    const double r0 = now_s();
+    bool all_resident = false;
+    for (unsigned spins = 0; bound > 0.0; ++spins) {   // (a bound <= 0 always misses: how the tests reach the fallback below)
+      int b = 0;
+      while (b < rblocks && __atomic_load_n(&gpu_flag[b], __ATOMIC_ACQUIRE) >= 1u) ++b;
+      if (b == rblocks) { all_resident = true; break; }
+      __builtin_ia32_pause();
+      if ((spins & 0x3FFu) == 0x3FFu && (__atomic_load_n(err_word, __ATOMIC_ACQUIRE) != 0 || now_s() - r0 > bound)) break;
+    }
+    if (!all_resident) {   // (`stop` tells the launches to stop)
+      if (mode == 2) return fail(MOBROB_ERR_STATE, "collect_host: MOBROB_COLLECT_SERVER=2 but not every workgroup of the rollout kernel became resident within %.1f s (another tenant on the device?)", bound);
+      return MOBROB_OK;   // *served is false: the caller's launch-per-step loop takes over
+    }
+  }
+  const bool timing = getenv("MOBROB_SERVER_TIMING") != nullptr;   // per-step split of the host thread's time (stderr)
+  double tw = 0, te = 0;
+  for (int t = 0; t < T; ++t) {
+    for (int p = 0; p < nparts; ++p) {
+      const unsigned want = (unsigned)(t + 1);
+      double t_wait = -1.0;
+      const double c0 = timing ? now_s() : 0;
+      for (int b = p * bpp; b < (p + 1) * bpp; ++b) {
+        unsigned spins = 0;
+        while (__atomic_load_n(&gpu_flag[b], __ATOMIC_ACQUIRE) < want) {
+          __builtin_ia32_pause();
+          if ((++spins & 0xFFFFu) == 0) {   // every ~65 k polls: the device gave up, or nothing moved for the whole timeout
+            if (__atomic_load_n(err_word, __ATOMIC_ACQUIRE) != 0)
+              return fail(MOBROB_ERR_STATE, "collect_host: the rollout kernel gave up waiting for the host at step %d", *err_word - 1);
+            const double tn = now_s();
+            if (t_wait < 0) t_wait = tn;
+            if (tn - t_wait > timeout_s)
+              return fail(MOBROB_ERR_HIP, "collect_host: no actions from the device for %.0f s (step %d, row range %d)", timeout_s, t, p);
+          }
+        }
+      }
+      const int r0 = p * (N / nparts);
+      const double c1 = timing ? now_s() : 0;
+      const int32_t ntrunc = step_range(env, r0, r0 + N / nparts, actions_clipped, obs, rewards, dones, truncated, terminal_obs);
+      if (ntrunc < 0) return fail(MOBROB_ERR_STATE, "collect_host: the environment's step_range returned %d", ntrunc);
+      __atomic_store_n(reinterpret_cast<unsigned long long*>(&host_flag[16 * p]), ((unsigned long long)(unsigned)ntrunc << 32) | want, __ATOMIC_RELEASE);
+      if (timing) { tw += c1 - c0; te += now_s() - c1; }
+    }
+  }
+  stop.armed = false;   // the normal way out: every step of every row range has been published
+#ifdef MOBROB_SERVE_STAMPS
+  if (timing) {
+    (void)hipStreamSynchronize(e->stream);
+    const long long* st = reinterpret_cast<const long long*>(err_word + 16);
+    double d[8] = {0};
+    int n = 0;
+    for (int t = 8; t + 1 < 64 && t + 1 < T; ++t, ++n) {
+      d[0] += st[8 * t + 1] - st[8 * t + 0];        // publish -> host word seen
+      d[1] += st[8 * t + 2] - st[8 * t + 1];        // barrier (4b)
+      d[2] += st[8 * t + 3] - st[8 * t + 2];        // pull (this wave)
+      d[3] += st[8 * t + 4] - st[8 * t + 3];        // barrier (4c)
+      d[4] += st[8 * t + 5] - st[8 * t + 4];        // env phase + state update
+      d[5] += st[8 * (t + 1) + 6] - st[8 * t + 5];  // layers, head, sampling (next step)
+      d[6] += st[8 * (t + 1) + 7] - st[8 * (t + 1) + 6];  // drain of the action stores
+      d[7] += st[8 * (t + 1) + 0] - st[8 * (t + 1) + 7];  // barrier (4)
+    }
+    fprintf(stderr, "[served stamps, workgroup 0, us] wait for host %.2f | (4b) %.2f | pull %.2f | (4c) %.2f | env+state %.2f | policy %.2f | drain %.2f | (4) %.2f\n",
+            d[0] / n / 100, d[1] / n / 100, d[2] / n / 100, d[3] / n / 100, d[4] / n / 100, d[5] / n / 100, d[6] / n / 100, d[7] / n / 100);
+  }
+#endif
+  if (timing)
+    fprintf(stderr, "[collect_host served] per step: waiting for the device %.1f us, env %.1f us (%d row ranges)\n", 1e6 * tw / T, 1e6 * te / T, nparts);
+  e->t = T;
+  e->nparts = nparts;
+  for (int p = 0; p < nparts; ++p) { e->part_act_t[p] = e->part_store_t[p] = T; e->part_obs_t[p] = T; }
+  if (e->draw_counter < e->draw_ro0 + (uint32_t)T) e->draw_counter = e->draw_ro0 + (uint32_t)T;
+  *served = true;
+  const int rc = mobrob_ppo_finish_rollout(e, obs, dones);   // last observations / dones, V(last_obs), GAE; synchronises the stream
+  if (rc == MOBROB_OK && __atomic_load_n(err_word, __ATOMIC_ACQUIRE) != 0)
+    return fail(MOBROB_ERR_STATE, "collect_host: the rollout kernel gave up waiting for the host at step %d", *err_word - 1);
+  return rc;
+}
 }  // namespace
 
 // The whole pipelined rollout in one call: rollout_begin, n_steps x nparts x (wait_part, env step of the range,
@@ -1525,7 +2046,7 @@ int mobrob_ppo_collect_host(mobrob_ppo_engine_t* e, mobrob_env_step_range_fn ste
   // is the single-thread loop's bit for bit.  MEASURED (whole iteration, same box, alternating): 198.2 / 198.9 ms single thread,
   // 200.0 - 203.4 ms with the driver thread (16, 15 or 14 env threads): what bounds a part's cycle is sim -> launch latency -> two small
   // kernels -> sim, and the spinning driver takes a core from the simulator's team.  Kept for hosts with cores to spare; off by default.
-  const bool threaded = nparts >= 2 && !timing && getenv("MOBROB_COLLECT_THREADS") && atoi(getenv("MOBROB_COLLECT_THREADS")) != 0;
+  const bool threaded = nparts >= 2 && !timing && env_int("MOBROB_COLLECT_THREADS", 0) != 0;
   if (threaded) {
     struct Shared {
       std::atomic<int> ready[MOBROB_MAX_PARTS];     // acts of part p the GPU has finished (actions of step ready - 1 are in host memory)
@@ -1617,564 +2138,6 @@ int mobrob_ppo_collect_host(mobrob_ppo_engine_t* e, mobrob_env_step_range_fn ste
             tq / e->T, nparts);
   return mobrob_ppo_finish_rollout(e, obs, dones);
 }
-
-int mobrob_ppo_finish_rollout(mobrob_ppo_engine_t* e, const float* last_obs, const uint8_t* dones) {
-  if (!e || !last_obs || !dones) return fail(MOBROB_ERR_INVALID, "finish_rollout: null argument");
-  if (e->t != e->T) return fail(MOBROB_ERR_STATE, "finish_rollout: %d of %d steps stored", e->t, e->T);
-  CHK(streamer_init(e));
-  const size_t N = e->N;
-  auto& st = e->stage[e->stage_i];
-  float* slot = e->obs + (size_t)e->T * N * e->Dp;
-  const float* src = stage_in(last_obs, st.obs, N * e->D);
-  CHK(upload_obs_on(e, e->cstream, src, slot, e->N));
-  memcpy(st.dones, dones, N);
-  HIPC(hipMemcpyAsync(e->dones_u8, st.dones, N, hipMemcpyHostToDevice, e->cstream));
-  HIPC(hipEventRecord(e->ev_in, e->cstream));
-  HIPC(hipStreamWaitEvent(e->stream, e->ev_in, 0));
-  hipLaunchKernelGGL(k_u8_to_f32, dim3(cdiv(e->N, 256)), dim3(256), 0, e->stream, e->dones_u8, e->last_dones, e->N);
-  forward(e, slot, e->N, false, nullptr, true, e->last_values);
-  run_gae(e);
-  HIPC(hipStreamSynchronize(e->stream));
-  e->rollout_ready = true; e->train_rec_valid = false;
-  return MOBROB_OK;
-}
-
-int mobrob_ppo_compute_gae(mobrob_ppo_engine_t* e) {
-  if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
-  run_gae(e);
-  HIPC(hipStreamSynchronize(e->stream));
-  e->rollout_ready = true; e->train_rec_valid = false;
-  return MOBROB_OK;
-}
-
-int mobrob_ppo_x3_mode(const mobrob_ppo_engine_t* e) {
-  if (!e || !e->fused.enabled || e->fused.net[0].W2x == nullptr) return 0;
-  return 1 | (e->fused.train_x3 ? 2 : 0) | (e->fused.train_x3 && e->fused.train_chain ? 4 : 0);
-}
-
-int mobrob_ppo_update_mode(const mobrob_ppo_engine_t* e) { return e ? e->last_update_mode : 0; }
-
-int mobrob_ppo_explained_variance(mobrob_ppo_engine_t* e, double* out) {
-  if (!e || !out) return fail(MOBROB_ERR_INVALID, "explained_variance: null argument");
-  if (!e->rollout_ready) return fail(MOBROB_ERR_STATE, "explained_variance: rollout not finished");
-  const int n = e->N * e->T;
-  hipLaunchKernelGGL(k_explained_variance_partials, dim3(kEvBlocks), dim3(256), 0, e->stream, e->values, e->ret, n, e->expvar_part);
-  double part[kEvBlocks * 4];
-  HIPC(hipMemcpyAsync(part, e->expvar_part, sizeof part, hipMemcpyDeviceToHost, e->stream));
-  HIPC(hipStreamSynchronize(e->stream));
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int b = 0; b < kEvBlocks; ++b)
-    for (int k = 0; k < 4; ++k) s[k] += part[b * 4 + k];
-  const double var_y = s[1] / n - (s[0] / n) * (s[0] / n), var_d = s[3] / n - (s[2] / n) * (s[2] / n);
-  *out = var_y > 0.0 ? 1.0 - var_d / var_y : NAN;  // SB3: nan when the returns do not vary
-  return MOBROB_OK;
-}
-
-int mobrob_ppo_mark_rollout_ready(mobrob_ppo_engine_t* e) {
-  if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
-  e->rollout_ready = true; e->train_rec_valid = false;
-  e->t = e->T;
-  return MOBROB_OK;
-}
-
-namespace {
-// enqueue one whole device-resident rollout (T steps + last values + GAE) on the engine stream
-uint64_t env_seed_of(const mobrob_ppo_engine* e) {
-  return e->cfg.seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(e->cfg.rank + 1));
-}
-
-// One persistent launch for all T steps (policy forward + sample + env + store), then the value network over all
-// stored observations in one batched pass, then GAE (kernels_rollout.h).
-bool rollout_persistent_ok(const mobrob_ppo_engine* e) {
-  return e->cfg.rollout_persistent && e->fused.enabled;  // both fused widths (256: kernels_rollout.h top, 64: bottom)
-}
-// side stream and events of the overlapped value pass: created OUTSIDE any stream capture (resource creation is
-// not a capturable operation)
-int rollout_side_stream_init(mobrob_ppo_engine* e) {
-  if (!e->vstream) {
-    HIPC(hipStreamCreateWithFlags(&e->vstream, hipStreamNonBlocking));
-    HIPC(hipEventCreateWithFlags(&e->ev_vdone, hipEventDisableTiming));
-  }
-  while ((int)e->ev_chunks.size() < e->T / 16 + 2) {  // chunks are >= 16 steps
-    hipEvent_t ev;
-    HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    e->ev_chunks.push_back(ev);
-  }
-  return MOBROB_OK;
-}
-
-int enqueue_rollout_persistent(mobrob_ppo_engine* e, const mobrob_ppo_engine::RolloutSpec& sp) {
-  const int N = e->N, Dp = e->Dp, T = e->T;
-  const size_t slot = (size_t)N * Dp;
-  HIPC(hipMemcpyAsync(e->obs, e->obs + (size_t)T * slot, slot * 4, hipMemcpyDeviceToDevice, e->stream));
-  RolloutArgs a{};
-  a.pi = e->fused.net[0];
-  a.log_std = Pp(e, T_LOGSTD); a.seed = eps_seed(e); a.draw_base = e->ctr_dev;
-  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
-  a.kind = sp.kind; a.env_seed = env_seed_of(e); a.step_base = e->ctr_dev + 1;
-  a.p_term = sp.p_term; a.time_limit = sp.time_limit; a.goal = sp.goal;
-  a.bt = BootArgs{Pp(e, T_VW1), Pp(e, T_VB1), Pp(e, T_VW2), Pp(e, T_VB2), Pp(e, T_VW), Pp(e, T_VB), e->G1, e->G2,
-                  (float)e->cfg.gamma, e->term_val};  // (fused path: two tanh layers)
-  a.N = N; a.D = e->D; a.A = e->A;
-  a.obs = e->obs; a.actions = e->actions; a.logp = e->logp; a.rewards = e->rewards; a.es = e->es;
-  a.term_obs = e->term_obs; a.trunc = e->trunc_dev; a.clip_act = e->clip_act;
-  a.ep_len = e->ep_len; a.prev_dones = e->prev_dones; a.gstate = e->gstate[0]; a.ep_stats = e->ep_stats;
-  if (e->fused.H == GH) {  // 64-wide nets (kernels_rollout.h, bottom half)
-    const int nwv = rollout64_waves(Dp);
-    const int tiles = cdiv(N, 32);
-    const bool tile_kernel = tiles <= e->rollout64_tile_max;  // one workgroup per tile while every tile gets a CU of its own
-    // A rollout of <= 192 tiles leaves CUs idle for thousands of dependent steps: like the 256-wide path, cut it into chunks
-    // and value the observations of a finished chunk on the side stream while the next chunk rolls out.  Worth the extra
-    // launches only when the value pass is more than a few launches' worth of work.
-    const bool overlap = tile_kernel && tiles <= 192 && (size_t)T * N >= ((size_t)1 << 18);
-    const int chunk = overlap ? std::max(16, cdiv(T, 20)) : T;
-    {
-      ProfScope ps(e, MOBROB_K_ENV);
-      for (int t0 = 0; t0 < T; t0 += chunk) {
-        a.t0 = t0; a.t1 = std::min(T, t0 + chunk);
-        if (tile_kernel) {
-          FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout64_tile<DPc>), dim3(tiles), dim3(256), rollout64_tile_lds_bytes(Dp),
-                                                   e->stream, a));
-        } else {
-          FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout64_persistent<DPc>), dim3(cdiv(tiles, nwv)), dim3(nwv * 64),
-                                                   rollout64_lds_bytes(Dp), e->stream, a));
-        }
-        if (overlap && a.t1 < T) {  // observations [t0, t1) are final
-          hipEvent_t ev = e->ev_chunks[t0 / chunk];
-          HIPC(hipEventRecord(ev, e->stream));
-          HIPC(hipStreamWaitEvent(e->vstream, ev, 0));
-          fused_forward(e->fused, e->obs + (size_t)t0 * N * Dp, (a.t1 - t0) * N, false, nullptr, e->Ap, true, e->values + (size_t)t0 * N,
-                        e->vstream);
-        }
-      }
-    }
-    hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(64), 0, e->stream, e->ctr_dev, (uint32_t)T, (uint32_t)T);
-    HIPC(hipMemcpyAsync(e->last_dones, e->prev_dones, (size_t)N * 4, hipMemcpyDeviceToDevice, e->stream));
-    {
-      ProfScope ps(e, MOBROB_K_ACT);  // V of the last chunk and V(last_obs) (obs[T]; values[T*N..] = last_values)
-      const int done_rows = overlap ? ((T - 1) / chunk) * chunk * N : 0;
-      forward(e, e->obs + (size_t)done_rows * Dp, (T + 1) * N - done_rows, false, nullptr, true, e->values + done_rows);
-      if (overlap && done_rows > 0) {  // join the side stream before GAE
-        HIPC(hipEventRecord(e->ev_vdone, e->vstream));
-        HIPC(hipStreamWaitEvent(e->stream, e->ev_vdone, 0));
-      }
-    }
-    run_gae(e);
-    return MOBROB_OK;
-  }
-  // The rollout blocks (32 envs each, ~100 KB of LDS) leave CUs idle when N < 32 * 256; the value pass of the steps
-  // already finished runs there at the same time: the rollout is cut into chunks, chunk c's value pass is enqueued
-  // on a second stream behind an event and overlaps the rollout of chunk c+1.
-  if (!e->fused.train_x3) pack_x3_all(e);  // otherwise every optimizer step (apply_adam) and set_params keep the x3 packs current
-  const int rblocks = cdiv(N, 32);
-  const bool overlap = rblocks <= 192;                      // otherwise the rollout itself fills the device
-  const int chunk = overlap ? std::max(16, cdiv(T, 20)) : T;
-  const int vgrid_max = overlap ? std::max(32, 256 - rblocks) : 256;
-  auto value_pass = [&](hipStream_t st, int r0, int r1, int grid_max) {  // rows [r0, r1) of obs -> values
-    FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_value_batch<DPc>), dim3(std::min(grid_max, cdiv(r1 - r0, FR))),
-                                             dim3(FTHREADS), e->fused.lds_bytes, st, e->fused.net[1],
-                                             e->obs + (size_t)r0 * Dp, r1 - r0, e->values + r0));
-  };
-  {
-    ProfScope ps(e, MOBROB_K_ENV);
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-      a.t0 = t0; a.t1 = std::min(T, t0 + chunk);
-      // x3 engines: the eight-wave form with W2's leading pieces stationary in registers (kernels_rollout.h, S8);
-      // MOBROB_ROLLOUT_S8=0 keeps the four-wave form (A/B and the bit-equality test of the two)
-      static const bool s8_on = !kRolloutStationary && !(getenv("MOBROB_ROLLOUT_S8") && atoi(getenv("MOBROB_ROLLOUT_S8")) == 0);
-      const bool s8 = s8_on && a.pi.W2x != nullptr;
-      if (s8 && a.kind == 1) {
-        FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 1, true>), dim3(rblocks), dim3(kRolloutThreads),
-                                                 rollout_lds_bytes(Dp, true), e->stream, a));
-      } else if (s8) {
-        FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 2, true>), dim3(rblocks), dim3(kRolloutThreads),
-                                                 rollout_lds_bytes(Dp, true), e->stream, a));
-      } else if (a.kind == 1) {
-        FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 1>), dim3(rblocks), dim3(kRolloutThreads),
-                                                 rollout_lds_bytes(Dp), e->stream, a));
-      } else {
-        FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 2>), dim3(rblocks), dim3(kRolloutThreads),
-                                                 rollout_lds_bytes(Dp), e->stream, a));
-      }
-      if (overlap && a.t1 < T) {  // observations [t0, t1) are final: value them on the side stream
-        hipEvent_t ev = e->ev_chunks[t0 / chunk];
-        HIPC(hipEventRecord(ev, e->stream));
-        HIPC(hipStreamWaitEvent(e->vstream, ev, 0));
-        value_pass(e->vstream, t0 * N, a.t1 * N, vgrid_max);
-      }
-    }
-  }
-  hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(64), 0, e->stream, e->ctr_dev, (uint32_t)T, (uint32_t)T);
-  HIPC(hipMemcpyAsync(e->last_dones, e->prev_dones, (size_t)N * 4, hipMemcpyDeviceToDevice, e->stream));
-  {
-    ProfScope ps(e, MOBROB_K_ACT);  // V of the last chunk and V(last_obs) (obs[T]; values[T*N..] = last_values)
-    const int done_rows = overlap ? ((T - 1) / chunk) * chunk * N : 0;
-    value_pass(e->stream, done_rows, (T + 1) * N, 256);  // the rollout is over: the whole device
-    if (overlap && done_rows > 0) {  // join the side stream before GAE
-      HIPC(hipEventRecord(e->ev_vdone, e->vstream));
-      HIPC(hipStreamWaitEvent(e->stream, e->ev_vdone, 0));
-    }
-  }
-  run_gae(e);
-  return MOBROB_OK;
-}
-
-int enqueue_rollout(mobrob_ppo_engine* e, const mobrob_ppo_engine::RolloutSpec& sp) {
-  if (rollout_persistent_ok(e)) return enqueue_rollout_persistent(e, sp);
-  const int N = e->N, Dp = e->Dp, per = Dp / 4;
-  const size_t slot = (size_t)N * Dp;
-  const uint64_t env_seed = env_seed_of(e);
-  // the previous rollout's last observation is this rollout's first
-  HIPC(hipMemcpyAsync(e->obs, e->obs + (size_t)e->T * slot, slot * 4, hipMemcpyDeviceToDevice, e->stream));
-  const BootNetArgs bt = boot_args(e);
-  const size_t sm = env_step_lds_bytes(Dp, value_net_width_sum(e));
-  for (int t = 0; t < e->T; ++t) {
-    act_slot(e, t, nullptr, true);
-    {
-      ProfScope ps(e, MOBROB_K_ENV);
-      // env step + rollout_buffer.add scalars + time-limit bootstrap of the (rare) truncated rows in one launch
-      if (sp.kind == 1) {
-        hipLaunchKernelGGL(k_env_step_store, dim3(cdiv(N * per, 256)), dim3(256), sm, e->stream, env_seed, (uint32_t)t,
-                           e->ctr_dev + 1, N, e->D, Dp, sp.p_term, sp.time_limit, e->ep_len, e->ep_len2,
-                           e->obs + (size_t)(t + 1) * slot, e->term_obs, e->prev_dones, e->dones_tmp, e->trunc_dev,
-                           e->rewards + (size_t)t * N, e->es + (size_t)t * N, bt);
-        std::swap(e->ep_len, e->ep_len2);
-      } else {
-        GoalEnvArgs g{};
-        g.seed = env_seed; g.step_rel = (uint32_t)t; g.step_base = e->ctr_dev + 1;
-        g.N = N; g.D = e->D; g.Dp = Dp; g.A = e->A; g.p = sp.goal;
-        g.act = e->clip_act; g.st_in = e->gstate[0]; g.st_out = e->gstate[1];
-        g.obs_next = e->obs + (size_t)(t + 1) * slot; g.term_obs = e->term_obs;
-        g.prev_dones = e->prev_dones; g.next_dones = e->dones_tmp; g.trunc = e->trunc_dev;
-        g.rew_out = e->rewards + (size_t)t * N; g.es_out = e->es + (size_t)t * N; g.ep_stats = e->ep_stats;
-        hipLaunchKernelGGL(k_goal_env_step_store, dim3(cdiv(N * per, 256)), dim3(256), sm, e->stream, g, bt);
-        std::swap(e->gstate[0], e->gstate[1]);
-      }
-    }
-    std::swap(e->prev_dones, e->dones_tmp);
-  }
-  hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(64), 0, e->stream, e->ctr_dev, (uint32_t)e->T, (uint32_t)e->T);
-  HIPC(hipMemcpyAsync(e->last_dones, e->prev_dones, (size_t)N * 4, hipMemcpyDeviceToDevice, e->stream));
-  forward(e, e->obs + (size_t)e->T * slot, N, false, nullptr, true, e->last_values);
-  run_gae(e);
-  return MOBROB_OK;
-}
-
-// device-resident rollout of either env kind: (re)start the env if needed, then replay / enqueue the T-step loop
-int collect_device(mobrob_ppo_engine* e, const mobrob_ppo_engine::RolloutSpec& sp) {
-  const int N = e->N, Dp = e->Dp, per = Dp / 4;
-  const size_t slot = (size_t)N * Dp;
-  if (e->env_started != sp.kind) {
-    float* last = e->obs + (size_t)e->T * slot;  // reset writes the "previous last observation"
-    if (sp.kind == 1) {
-      hipLaunchKernelGGL(k_env_reset, dim3(cdiv(N * per, 256)), dim3(256), 0, e->stream, env_seed_of(e), N, e->D, Dp, last,
-                         e->ep_len);
-    } else {
-      hipLaunchKernelGGL(k_goal_env_reset, dim3(cdiv(N * per, 256)), dim3(256), 0, e->stream, env_seed_of(e), N, e->D, Dp,
-                         sp.goal, e->gstate[0], last);
-      HIPC(hipMemsetAsync(e->ep_stats, 0, kEpStatsDoubles * sizeof(double), e->stream));
-      e->ep_ring_read = 0;
-    }
-    std::vector<float> ones(N, 1.0f);  // a fresh env starts every episode: `_last_episode_starts` all True
-    HIPC(hipMemcpyAsync(e->prev_dones, ones.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
-    HIPC(hipStreamSynchronize(e->stream));
-    e->env_started = sp.kind;
-  }
-  e->rollout_ready = false; e->train_rec_valid = false;
-  if (rollout_persistent_ok(e)) CHK(rollout_side_stream_init(e));
-  // Graph replay: every kernel argument of the T-step loop is fixed (slot pointers, ping-pong buffers with even T,
-  // counters relative to device-resident bases), so the loop is captured once and replayed per rollout.
-  // The persistent path is ~45 launches on two streams: enqueued eagerly (the launches hide behind the 18 ms of
-  // GPU work; a captured multi-stream graph was both slower to launch and, after many capture / destroy cycles in
-  // one process, crashed inside the runtime).  Only the per-step path (thousands of launches) is replayed as a graph.
-  const bool use_graph = e->cfg.rollout_graph && e->T % 2 == 0 && !rollout_persistent_ok(e);
-  if (!use_graph) {
-    CHK(enqueue_rollout(e, sp));
-  } else {
-    if (e->ro_exec == nullptr || memcmp(&e->ro_spec, &sp, sizeof sp) != 0) {
-      HIPC(hipStreamSynchronize(e->stream));  // never destroy an executable graph that may still be running
-      if (e->ro_exec) { (void)hipGraphExecDestroy(e->ro_exec); e->ro_exec = nullptr; }
-      if (e->ro_graph) { (void)hipGraphDestroy(e->ro_graph); e->ro_graph = nullptr; }
-      const bool prof = e->prof_on;
-      e->prof_on = false;  // event records cannot be part of the captured graph
-      hipError_t be = hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal);
-      if (be != hipSuccess) {  // e.g. a stream that does not support capture: run eagerly from now on
-        (void)hipGetLastError();
-        e->prof_on = prof;
-        e->cfg.rollout_graph = 0;
-        CHK(enqueue_rollout(e, sp));
-        HIPC(hipGetLastError());
-        e->t = e->T;
-        e->rollout_ready = true; e->train_rec_valid = false;
-        return MOBROB_OK;
-      }
-      const int rc = enqueue_rollout(e, sp);
-      hipError_t ce = hipStreamEndCapture(e->stream, &e->ro_graph);
-      e->prof_on = prof;
-      if (rc != MOBROB_OK) return rc;
-      if (ce != hipSuccess) return fail(MOBROB_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-      HIPC(hipGraphInstantiate(&e->ro_exec, e->ro_graph, nullptr, nullptr, 0));
-      memcpy(&e->ro_spec, &sp, sizeof sp);
-    }
-    ProfScope ps(e, MOBROB_K_ACT);  // with graph replay the ACT scope covers the whole rollout (forward+env+GAE)
-    HIPC(hipGraphLaunch(e->ro_exec, e->stream));
-  }
-  HIPC(hipGetLastError());
-  e->t = e->T;
-  e->rollout_ready = true; e->train_rec_valid = false;
-  return MOBROB_OK;
-}
-
-// Host environments SERVED by the persistent rollout kernel (round 5; kernels_rollout.h, KIND 3).  The launch-per-step collector above
-// pays, per row range and step, two kernel launches, an event, the event's completion latency and the weight stream of a fresh
-// k_fused_act -- 74 - 76 us of GPU-side time per vector step of 4096 envs against 10 us for the same arithmetic inside the device
-// rollout.  Here the device rollout's own kernel runs the policy (weights stationary, S8) and its env phase is the host's: a
-// workgroup writes its rows' clipped actions into the caller's pinned buffer, raises its flag word in pinned memory and polls the
-// host's word for its row range; the host waits for the flags of a range, steps it, raises its word.  No HIP call inside the step
-// loop.  Same Philox counters, same forward / sampling / storage / bootstrap code as the device rollout; against the launch-per-step
-// collector the buffers agree to float32 rounding (its k_fused_act runs the policy on the f32 pipe, the rollout kernel on the bf16
-// pipe with split operands: the same relation the device rollout has to its per-step form), what the kernel only moves -- clipped
-// actions to the host, rewards / observations from it -- is exact (tests/test_engine_gpu.py::test_served_host_rollout_...).
-// Conditions (else *served stays false and the caller runs the launch-per-step loop): 256-wide x3 engine with the eight-wave rollout
-// kernel, or (round 6) a 64-wide engine within the tile kernel's range (k_rollout64_tile<.., 3>: the shape of every reference config);
-// whole 32-row tiles per row range, every workgroup resident at once (tiles <= CUs: a waiting workgroup never yields its CU),
-// coherent pinned buffers (served_buffer_problem), no announced co-tenant of the device.  MOBROB_COLLECT_SERVER=0 switches it off; MOBROB_SERVER_TIMEOUT_S (default 60) bounds every wait on either side.
-int collect_host_served(mobrob_ppo_engine* e, mobrob_env_step_range_fn step_range, void* env, int nparts, float* obs,
-                        float* actions_clipped, float* rewards, uint8_t* dones, uint8_t* truncated, float* terminal_obs, bool* served) {
-  *served = false;
-  const int mode = getenv("MOBROB_COLLECT_SERVER") ? atoi(getenv("MOBROB_COLLECT_SERVER")) : 1;   // 0 off, 1 when possible, 2 required (tests); read per rollout
-  static const bool s8_on = !kRolloutStationary && !(getenv("MOBROB_ROLLOUT_S8") && atoi(getenv("MOBROB_ROLLOUT_S8")) == 0);
-  const int N = e->N, T = e->T, Dp = e->Dp;
-  const int rblocks = cdiv(N, 32);
-  if (mode == 0) return MOBROB_OK;
-  const char* why = nullptr;
-  int cus = 0;
-  const bool wide = e->fused.enabled && e->fused.H == FH;   // 256-wide: k_rollout_persistent<.., 3, S8>; 64-wide: k_rollout64_tile<.., 3>
-  if (!rollout_persistent_ok(e)) why = "the fused persistent rollout kernels are off for this engine";
-  else if (wide && (!s8_on || e->fused.net[0].W2x == nullptr)) why = "not a 256-wide x3 engine with the eight-wave rollout kernel";
-  else if (!wide && (e->fused.H != GH || rblocks > e->rollout64_tile_max)) why = "not a 64-wide engine within the tile kernel's range";
-  else if (getenv("MOBROB_COLLECT_TIMING") || (getenv("MOBROB_COLLECT_THREADS") && atoi(getenv("MOBROB_COLLECT_THREADS")) != 0)) why = "an instrumented / threaded collector was asked for";
-  // a 32-row tile must not straddle two row ranges; ONE range takes any number of environments (the reference YAMLs: 2 - 16, half a tile)
-  else if (nparts < 1 || nparts > MOBROB_MAX_PARTS || (nparts > 1 && (N % nparts != 0 || (N / nparts) % 32 != 0))) why = "row ranges are not whole 32-row tiles";
-  else if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device_id) != hipSuccess || rblocks > cus) why = "more tiles than compute units";
-  // Other tenants of the device that this process cannot count: ranks rehearsing data parallelism on ONE device, a CU mask.  Every
-  // workgroup of a served rollout must be resident at once (a waiting workgroup never yields its CU), so with them the launch-per-step
-  // collector -- which always works -- is the one that runs.  (A tenant nobody announced is caught by the residency check below.)
-  else if (getenv("MOBROB_DP_SAME_DEVICE") && atoi(getenv("MOBROB_DP_SAME_DEVICE")) != 0 && e->cfg.world_size > 1) why = "several data-parallel ranks share this device (MOBROB_DP_SAME_DEVICE)";
-  else if (getenv("HSA_CU_MASK") || getenv("ROC_GLOBAL_CU_MASK")) why = "a compute-unit mask is set (HSA_CU_MASK / ROC_GLOBAL_CU_MASK)";
-  else {
-    const size_t N_ = (size_t)N;
-    const struct { const void* p; size_t bytes; } bufs[6] = {{obs, N_ * e->D * 4}, {actions_clipped, N_ * e->A * 4}, {rewards, N_ * 4},
-                                                              {dones, N_}, {truncated, N_}, {terminal_obs, N_ * e->D * 4}};
-    for (const auto& b : bufs)
-      if (!why) why = served_buffer_problem(b.p, b.bytes);
-  }
-  // Every workgroup of a served rollout must be resident at once, and it keeps its compute unit until the host has stepped all n_steps:
-  // engines of ONE process that collect at the same time (a fleet's threads) share a DEVICE's compute units through that device's
-  // counter -- the one that does not fit takes the launch-per-step path instead of queueing behind a kernel that waits for a host.
-  constexpr int kLeaseDevices = 64;
-  static std::atomic<int> cus_serving[kLeaseDevices];   // zero-initialised (static storage)
-  std::atomic<int>& dev_lease = cus_serving[(unsigned)e->cfg.device_id % kLeaseDevices];
-  struct Lease {
-    std::atomic<int>& c; int n; bool held;
-    ~Lease() { if (held) c.fetch_sub(n); }
-  } lease{dev_lease, rblocks, false};
-  if (!why) {
-    if (dev_lease.fetch_add(rblocks) + rblocks > cus) { dev_lease.fetch_sub(rblocks); why = "the device's compute units are serving another engine's rollout"; }
-    else lease.held = true;
-  }
-  if (why) return mode == 2 ? fail(MOBROB_ERR_STATE, "collect_host: MOBROB_COLLECT_SERVER=2 but %s", why) : MOBROB_OK;
-  CHK(rollout_side_stream_init(e));
-  CHK(streamer_init(e));
-  constexpr int kHostWords = 16 * MOBROB_MAX_PARTS;
-  constexpr int kStampWords = 64 * 8 * 2;   // -DMOBROB_SERVE_STAMPS builds: 64 steps x 8 stamps (long long) of workgroup 0
-  const int fb = (rblocks + 15) / 16 * 16;
-  if (!e->srv_flags || e->srv_blocks < fb) {
-    if (e->srv_flags) (void)hipHostFree(e->srv_flags);
-    e->srv_flags = nullptr;
-    HIPC(hipHostMalloc((void**)&e->srv_flags, (size_t)(fb + kHostWords + 16 + kStampWords) * sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
-    e->srv_blocks = fb;
-  }
-  if (!e->srv_abort) HIPC(hipMalloc((void**)&e->srv_abort, 256));   // abort word | one 8-byte relay word per row range
-  unsigned* gpu_flag = e->srv_flags;
-  unsigned* host_flag = e->srv_flags + e->srv_blocks;
-  int* err_word = reinterpret_cast<int*>(host_flag + kHostWords);
-  memset(e->srv_flags, 0, (size_t)(e->srv_blocks + kHostWords + 16 + kStampWords) * sizeof(unsigned));
-  HIPC(hipMemsetAsync(e->srv_abort, 0, 256, e->stream));
-  const double timeout_s = getenv("MOBROB_SERVER_TIMEOUT_S") ? atof(getenv("MOBROB_SERVER_TIMEOUT_S")) : 60.0;
-
-  // slot 0 <- the environments' current observations (the kernel reads its first tile from the slot, like the device rollout)
-  hipLaunchKernelGGL(k_pull_rows, dim3(cdiv(N * Dp, 256)), dim3(256), 0, e->stream, obs, e->obs, N, e->D, Dp);
-  if (wide && !e->fused.train_x3) pack_x3_all(e);
-  RolloutArgs a{};
-  a.pi = e->fused.net[0];
-  a.log_std = Pp(e, T_LOGSTD); a.seed = eps_seed(e); a.draw_base = nullptr; a.draw0 = e->draw_ro0;
-  a.lo = (float)e->cfg.action_low; a.hi = (float)e->cfg.action_high;
-  a.kind = 3; a.env_seed = 0; a.step_base = nullptr;
-  a.bt = BootArgs{Pp(e, T_VW1), Pp(e, T_VB1), Pp(e, T_VW2), Pp(e, T_VB2), Pp(e, T_VW), Pp(e, T_VB), e->G1, e->G2,
-                  (float)e->cfg.gamma, e->term_val};
-  a.N = N; a.D = e->D; a.A = e->A;
-  a.obs = e->obs; a.actions = e->actions; a.logp = e->logp; a.rewards = e->rewards; a.es = e->es;
-  a.term_obs = e->term_obs; a.trunc = e->trunc_dev; a.clip_act = actions_clipped;   // (the caller's pinned buffer)
-  a.ep_len = e->ep_len; a.prev_dones = e->prev_dones; a.gstate = e->gstate[0]; a.ep_stats = e->ep_stats;
-  a.h_obs = obs; a.h_rew = rewards; a.h_done = dones; a.h_trunc = truncated; a.h_term = terminal_obs;
-  a.h_gpu_flag = gpu_flag; a.h_host_flag = host_flag; a.h_error = err_word; a.abort_dev = e->srv_abort;
-  a.rows_per_part = N / nparts; a.timeout_ticks = (long long)(timeout_s * 1e8);
-
-  // From the first KIND-3 launch on, EVERY way out of this function that is not the normal one tells the (possibly resident, possibly
-  // waiting) workgroups to stop first: they would otherwise spin for the whole timeout and the next synchronising call with them.
-  auto give_up = [&](void) {
-    for (int p = 0; p < nparts; ++p) __atomic_store_n(reinterpret_cast<unsigned long long*>(&host_flag[16 * p]), 0xFFFFFFFFull, __ATOMIC_RELEASE);
-    (void)hipStreamSynchronize(e->stream);
-    (void)hipStreamSynchronize(e->vstream);
-  };
-#define SRV_HIPC(expr)                                                                                          \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) {                                                                                     \
-      give_up();                                                                                                \
-      return fail(MOBROB_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-    }                                                                                                           \
-  } while (0)
-  // chunks of the step loop on the compute stream, V(obs) of a finished chunk on the side stream (as enqueue_rollout_persistent)
-  const bool overlap = wide ? rblocks <= 192 : (rblocks <= 192 && (size_t)T * N >= ((size_t)1 << 18));   // (the device rollouts' rules)
-  const int chunk = overlap ? std::max(16, cdiv(T, 20)) : T;
-  const int vgrid_max = overlap ? std::max(32, 256 - rblocks) : 256;
-  auto value_pass = [&](hipStream_t st, int r0, int r1, int grid_max) {
-    if (wide) {
-      FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_value_batch<DPc>), dim3(std::min(grid_max, cdiv(r1 - r0, FR))), dim3(FTHREADS),
-                                               e->fused.lds_bytes, st, e->fused.net[1], e->obs + (size_t)r0 * Dp, r1 - r0, e->values + r0));
-    } else {
-      fused_forward(e->fused, e->obs + (size_t)r0 * Dp, r1 - r0, false, nullptr, e->Ap, true, e->values + r0, st);
-    }
-  };
-  if (!wide)   // the served tile kernel's dynamic LDS exceeds 64 KB at 64 observation columns (per device and cheap: set per rollout)
-    FUSED_DISPATCH_DP(Dp, HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout64_tile<DPc, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)rollout64_tile_lds_bytes(Dp, true))));
-  {
-    ProfScope ps(e, MOBROB_K_ENV);
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-      a.t0 = t0; a.t1 = std::min(T, t0 + chunk);
-      if (wide) {
-        FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout_persistent<DPc, 3, true>), dim3(rblocks), dim3(kRolloutThreads),
-                                                 rollout_lds_bytes(Dp, true), e->stream, a));
-      } else {
-        FUSED_DISPATCH_DP(Dp, hipLaunchKernelGGL((k_rollout64_tile<DPc, 3>), dim3(rblocks), dim3(256), rollout64_tile_lds_bytes(Dp, true), e->stream, a));
-      }
-      if (overlap && a.t1 < T) {
-        hipEvent_t ev = e->ev_chunks[t0 / chunk];
-        SRV_HIPC(hipEventRecord(ev, e->stream));
-        SRV_HIPC(hipStreamWaitEvent(e->vstream, ev, 0));
-        value_pass(e->vstream, t0 * N, a.t1 * N, vgrid_max);
-      }
-    }
-  }
-  {
-    ProfScope ps(e, MOBROB_K_ACT);   // V of the last chunk (V(last_obs) is finish_rollout's)
-    const int done_rows = overlap ? ((T - 1) / chunk) * chunk * N : 0;
-    value_pass(e->stream, done_rows, T * N, 256);
-    if (overlap && done_rows > 0) {
-      SRV_HIPC(hipEventRecord(e->ev_vdone, e->vstream));
-      SRV_HIPC(hipStreamWaitEvent(e->stream, e->ev_vdone, 0));
-    }
-  }
-  SRV_HIPC(hipGetLastError());
-#undef SRV_HIPC
-
-  // ---- the host's side of the step loop: wait for the flags of a row range, step it, raise the range's word ----
-  auto now_s = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-  const int bpp = nparts == 1 ? rblocks : (N / nparts) / 32;   // workgroups per row range
-  {
-    // Residency check, before the environment is touched: the clipped actions of step 0 of EVERY workgroup within a short bound
-    // (MOBROB_SERVER_RESIDENCY_S, default 2 s; a resident workgroup needs ~25 us).  A workgroup that is not resident -- another
-    // process on the device, a CU mask nobody announced -- would leave the resident ones waiting for the host while the host waits
-    // for it: instead of stalling for the whole timeout and failing the rollout, the launches are told to stop and the caller runs
-    // the launch-per-step collector from the untouched rollout state (nothing has been stepped, no counter has moved).
-    const double bound = getenv("MOBROB_SERVER_RESIDENCY_S") ? atof(getenv("MOBROB_SERVER_RESIDENCY_S")) : 2.0;
-    const double r0 = now_s();
-    bool all_resident = false;
-    for (unsigned spins = 0; bound > 0.0; ++spins) {   // (a bound <= 0 always misses: how the tests reach the fallback below)
-      int b = 0;
-      while (b < rblocks && __atomic_load_n(&gpu_flag[b], __ATOMIC_ACQUIRE) >= 1u) ++b;
-      if (b == rblocks) { all_resident = true; break; }
-      __builtin_ia32_pause();
-      if ((spins & 0x3FFu) == 0x3FFu && (__atomic_load_n(err_word, __ATOMIC_ACQUIRE) != 0 || now_s() - r0 > bound)) break;
-    }
-    if (!all_resident) {
-      give_up();
-      if (mode == 2) return fail(MOBROB_ERR_STATE, "collect_host: MOBROB_COLLECT_SERVER=2 but not every workgroup of the rollout kernel became resident within %.1f s (another tenant on the device?)", bound);
-      return MOBROB_OK;   // *served is false: the caller's launch-per-step loop takes over
-    }
-  }
-  const bool timing = getenv("MOBROB_SERVER_TIMING") != nullptr;   // per-step split of the host thread's time (stderr)
-  double tw = 0, te = 0;
-  for (int t = 0; t < T; ++t) {
-    for (int p = 0; p < nparts; ++p) {
-      const unsigned want = (unsigned)(t + 1);
-      double t_wait = -1.0;
-      const double c0 = timing ? now_s() : 0;
-      for (int b = p * bpp; b < (p + 1) * bpp; ++b) {
-        unsigned spins = 0;
-        while (__atomic_load_n(&gpu_flag[b], __ATOMIC_ACQUIRE) < want) {
-          __builtin_ia32_pause();
-          if ((++spins & 0xFFFFu) == 0) {   // every ~65 k polls: the device gave up, or nothing moved for the whole timeout
-            if (__atomic_load_n(err_word, __ATOMIC_ACQUIRE) != 0) {
-              give_up();
-              return fail(MOBROB_ERR_STATE, "collect_host: the rollout kernel gave up waiting for the host at step %d", *err_word - 1);
-            }
-            const double tn = now_s();
-            if (t_wait < 0) t_wait = tn;
-            if (tn - t_wait > timeout_s) {
-              give_up();
-              return fail(MOBROB_ERR_HIP, "collect_host: no actions from the device for %.0f s (step %d, row range %d)", timeout_s, t, p);
-            }
-          }
-        }
-      }
-      const int r0 = p * (N / nparts);
-      const double c1 = timing ? now_s() : 0;
-      const int32_t ntrunc = step_range(env, r0, r0 + N / nparts, actions_clipped, obs, rewards, dones, truncated, terminal_obs);
-      if (ntrunc < 0) {
-        give_up();
-        return fail(MOBROB_ERR_STATE, "collect_host: the environment's step_range returned %d", ntrunc);
-      }
-      __atomic_store_n(reinterpret_cast<unsigned long long*>(&host_flag[16 * p]), ((unsigned long long)(unsigned)ntrunc << 32) | want, __ATOMIC_RELEASE);
-      if (timing) { tw += c1 - c0; te += now_s() - c1; }
-    }
-  }
-#ifdef MOBROB_SERVE_STAMPS
-  if (timing) {
-    (void)hipStreamSynchronize(e->stream);
-    const long long* st = reinterpret_cast<const long long*>(err_word + 16);
-    double d[8] = {0};
-    int n = 0;
-    for (int t = 8; t + 1 < 64 && t + 1 < T; ++t, ++n) {
-      d[0] += st[8 * t + 1] - st[8 * t + 0];        // publish -> host word seen
-      d[1] += st[8 * t + 2] - st[8 * t + 1];        // barrier (4b)
-      d[2] += st[8 * t + 3] - st[8 * t + 2];        // pull (this wave)
-      d[3] += st[8 * t + 4] - st[8 * t + 3];        // barrier (4c)
-      d[4] += st[8 * t + 5] - st[8 * t + 4];        // env phase + state update
-      d[5] += st[8 * (t + 1) + 6] - st[8 * t + 5];  // layers, head, sampling (next step)
-      d[6] += st[8 * (t + 1) + 7] - st[8 * (t + 1) + 6];  // drain of the action stores
-      d[7] += st[8 * (t + 1) + 0] - st[8 * (t + 1) + 7];  // barrier (4)
-    }
-    fprintf(stderr, "[served stamps, workgroup 0, us] wait for host %.2f | (4b) %.2f | pull %.2f | (4c) %.2f | env+state %.2f | policy %.2f | drain %.2f | (4) %.2f\n",
-            d[0] / n / 100, d[1] / n / 100, d[2] / n / 100, d[3] / n / 100, d[4] / n / 100, d[5] / n / 100, d[6] / n / 100, d[7] / n / 100);
-  }
-#endif
-  if (timing)
-    fprintf(stderr, "[collect_host served] per step: waiting for the device %.1f us, env %.1f us (%d row ranges)\n", 1e6 * tw / T, 1e6 * te / T, nparts);
-  e->t = T;
-  e->nparts = nparts;
-  for (int p = 0; p < nparts; ++p) { e->part_act_t[p] = e->part_store_t[p] = T; e->part_obs_t[p] = T; }
-  if (e->draw_counter < e->draw_ro0 + (uint32_t)T) e->draw_counter = e->draw_ro0 + (uint32_t)T;
-  *served = true;
-  const int rc = mobrob_ppo_finish_rollout(e, obs, dones);   // last observations / dones, V(last_obs), GAE; synchronises the stream
-  if (rc == MOBROB_OK && __atomic_load_n(err_word, __ATOMIC_ACQUIRE) != 0)
-    return fail(MOBROB_ERR_STATE, "collect_host: the rollout kernel gave up waiting for the host at step %d", *err_word - 1);
-  return rc;
-}
-}  // namespace
 
 int mobrob_ppo_collect_synthetic(mobrob_ppo_engine_t* e, float p_term, int32_t time_limit) {
   if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
@@ -2686,7 +2649,7 @@ int oneshot_all_reduce(mobrob_ppo_engine* e, void* buf, size_t count, int dtype)
     a.peer_flags[r] = reinterpret_cast<const unsigned long long*>(o.peer[r] + 2 * o.payload);
   }
   a.world = o.world; a.rank = o.rank; a.bytes = bytes; a.seq = o.seq; a.error = o.error; a.timeout_ticks = o.timeout_ticks;
-  a.fence_form = getenv("MOBROB_ONESHOT_FENCE") != nullptr && atoi(getenv("MOBROB_ONESHOT_FENCE")) != 0;
+  a.fence_form = env_int("MOBROB_ONESHOT_FENCE", 0) != 0;
   const int chunks = cdiv((int)bytes, kOneShotChunkBytes);
   if (dtype == 1) hipLaunchKernelGGL(k_oneshot_allreduce<double>, dim3(chunks), dim3(256), 0, e->stream, a);
   else hipLaunchKernelGGL(k_oneshot_allreduce<float>, dim3(chunks), dim3(256), 0, e->stream, a);
@@ -2812,7 +2775,7 @@ int launch_epoch_kernel(mobrob_ppo_engine* e, int ep, int G) {
   ea.total = total; ea.bl = e->Bl; ea.nmb = nmb; ea.world = e->cfg.world_size;
   ea.step_consts = e->epoch_consts; ea.stats_idx = e->epoch_idx; ea.stats = e->stats;
   ea.barrier = e->epoch_bar; ea.error_host = e->epoch_err_host;
-  const double timeout_s = getenv("MOBROB_EPOCH_TIMEOUT_S") ? atof(getenv("MOBROB_EPOCH_TIMEOUT_S")) : 10.0;
+  const double timeout_s = env_double("MOBROB_EPOCH_TIMEOUT_S", 10.0);
   ea.timeout_ticks = (long long)(timeout_s * 1e8);
   void* kargs[1] = {&ea};
   {
@@ -3316,8 +3279,8 @@ template <class Task>
 static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, void (*fin)(typename Task::Args)) {
   const EvalArgs& a = Task::eval(args);
   const int N = a.N;
-  const char* pe = getenv("MOBROB_EVAL_PERSISTENT");   // 0: the per-step path on every engine (A/B, tests); read per call
-  const bool persistent = e->fused.enabled && e->fused.H == 64 && !(pe && atoi(pe) == 0);
+  // MOBROB_EVAL_PERSISTENT=0: the per-step path on every engine (A/B, tests); read per call
+  const bool persistent = e->fused.enabled && e->fused.H == 64 && env_int("MOBROB_EVAL_PERSISTENT", 1) != 0;
   if (persistent) {
     Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
     size_t lds_bytes = eval64_lds_bytes(a.Dp);

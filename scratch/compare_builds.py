@@ -6,7 +6,15 @@
     MOBROB_EVAL_PERSISTENT=0), deterministic and sampled actions, obs_noise 0 and 0.1, 37 robots (not a multiple of 16), an
     episode quota under a time limit and the no-limit protocol, waypoint lists of which some finish early; plus a 2x256 doggo
     engine (per-step path only).
-    python scratch/compare_builds.py /path/to/old.so /path/to/new.so   (the two children run one after the other)"""
+  rollout leg: the raw bytes of every rollout buffer (obs, actions, rewards, episode_starts, values, log_probs, advantages, returns,
+    last_values, last_dones, clipped_actions; host rollouts also the caller's clipped actions) after one and after two consecutive
+    collections, for every way a rollout is enqueued: device rollouts (synthetic source and goal env) on the 64-wide tile kernel
+    without and with the overlapped value pass, the one-wave kernel (MOBROB_ROLLOUT64_TILE_MAX=0), the 256-wide kernel with and
+    without overlap, n_steps that the chunk length does not divide, the per-step path eager and graph-replayed; host rollouts of
+    the native C env served by the rollout kernel (both widths, one and two row ranges) and through the launch-per-step collector
+    (MOBROB_COLLECT_SERVER=0); act / store with pinned and with ordinary buffers (truncations in every rollout).  A second child
+    per library runs the 256-wide device rollouts with MOBROB_ROLLOUT_S8=0 (the four-wave kernel; read once per process).
+    python scratch/compare_builds.py /path/to/old.so /path/to/new.so   (the children run one after the other)"""
 import os, subprocess, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -72,7 +80,128 @@ def eval_follow_legs(out):
         e.close()
 
 
-if len(sys.argv) == 3 and sys.argv[1] == "--run":
+ROLLOUT_KEYS = ("obs", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns", "last_values",
+                "last_dones", "clipped_actions")
+
+
+def rollout_digest(e, extra=None):
+    import hashlib
+    h = hashlib.sha256()
+    for k in ROLLOUT_KEYS:
+        h.update(e.read(k).tobytes())
+    if extra is not None:
+        h.update(extra.tobytes())
+    return h.hexdigest()[:16]
+
+
+def rollout_legs(out, s8_off):
+    """s8_off: the child runs under MOBROB_ROLLOUT_S8=0 -- only the configurations that kernel choice touches (256-wide, persistent)."""
+    import numpy as np
+    from mobrob_amd.engine import PPOEngine
+    from mobrob_amd.envs.native_env import NativeGoalVecEnv
+    from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
+    from mobrob_amd.rl_control.init import orthogonal_policy_init
+    from oracle import ppo_oracle as O
+    tag0 = "rollout S8=0 | " if s8_off else "rollout | "
+
+    def engine(robot, H, N, T, **kw):
+        D, A, _ = ROBOT_DIMS[robot]
+        e = PPOEngine(obs_dim=D, act_dim=A, n_envs=N, n_steps=T, batch_size=N, n_epochs=1, pi=(H, H), vf=(H, H), seed=5, **kw)
+        e.set_params(orthogonal_policy_init(D, A, (H, H), (H, H), 0))
+        return e
+
+    from mobrob_amd.envs.wrapper import ROBOT_DIMS
+    # ---- device rollouts: (name, robot, H, N, T, environment at engine_create, engine keywords)
+    dev = [("256 S8 overlap", "doggo", 256, 512, 64, {}, {}),
+           ("256 overlap, chunk does not divide T", "doggo", 256, 512, 72, {}, {}),
+           ("256 no overlap (193 tiles)", "car", 256, 193 * 32, 8, {}, {}),
+           ("256 Dp 48 (x3 packs rebuilt per rollout)", "turtlebot3", 256, 128, 40, {}, {}),
+           ("256 Dp 16 one chunk", "point", 256, 64, 12, {}, {})]
+    if not s8_off:
+        dev += [("64 tile no overlap", "point", 64, 256, 64, {}, {}),
+                ("64 tile overlap", "point", 64, 1024, 256, {}, {}),
+                ("64 tile overlap, chunk does not divide T", "turtlebot3", 64, 1024, 260, {}, {}),
+                ("64 one-wave kernel", "car", 64, 256, 64, {"MOBROB_ROLLOUT64_TILE_MAX": "0"}, {}),
+                ("64 per-step graph", "point", 64, 64, 16, {}, dict(rollout_persistent=False)),
+                ("64 per-step eager", "point", 64, 64, 16, {}, dict(rollout_persistent=False, rollout_graph=False)),
+                ("256 per-step graph", "doggo", 256, 64, 16, {}, dict(rollout_persistent=False)),
+                ("256 per-step eager", "doggo", 256, 64, 16, {}, dict(rollout_persistent=False, rollout_graph=False)),
+                ("48 generic per-step graph", "car", 48, 64, 16, {}, {}),
+                ("48 generic per-step eager", "car", 48, 64, 16, {}, dict(rollout_graph=False))]
+    for name, robot, H, N, T, env_vars, kw in dev:
+        for source in ("synthetic", "goal"):
+            os.environ.update(env_vars)
+            try:
+                e = engine(robot, H, N, T, **kw)
+            finally:
+                for k in env_vars:
+                    os.environ.pop(k, None)
+            genv = DeviceGoalVecEnv.for_robot(robot, N, time_limit=30, seed=5)
+            for i in (1, 2):
+                if source == "synthetic":
+                    e.collect_synthetic(p_term=0.02, time_limit=40)
+                else:
+                    genv.collect(e)
+                e.synchronize()
+                out[f"{tag0}{name} | {source} | after {i}"] = rollout_digest(e)
+            e.close()
+    if s8_off:   # (the served collector exists for the eight-wave kernel only)
+        return
+    # ---- host rollouts of the native C env: served by the rollout kernel (2: or fail) and launch-per-step (0)
+    host = [("256", "doggo", 256, 128, 37, 1), ("256", "doggo", 256, 128, 37, 2), ("256 Dp 48", "turtlebot3", 256, 192, 40, 2),
+            ("64", "doggo", 64, 128, 37, 1), ("64", "point", 64, 128, 37, 2), ("64 overlap", "point", 64, 1024, 256, 2)]
+    for name, robot, H, N, T, parts in host:
+        for mode in ("2", "0"):
+            e = engine(robot, H, N, T)
+            D, A = e.D, e.A
+            env = NativeGoalVecEnv.for_robot(robot, N, time_limit=5, seed=7)
+            b = dict(obs=e.pinned((N, D)), clip=e.pinned((N, A)), rew=e.pinned((N,)), done=e.pinned((N,), np.uint8),
+                     trunc=e.pinned((N,), np.uint8), term=e.pinned((N, D)))
+            env.use_buffers(obs=b["obs"], rewards=b["rew"], dones=b["done"], truncated=b["trunc"], terminal_obs=b["term"])
+            env.reset()
+            os.environ["MOBROB_COLLECT_SERVER"] = mode
+            os.environ["MOBROB_SERVER_TIMEOUT_S"] = "10"
+            try:
+                for i in (1, 2):
+                    e.rollout_begin()
+                    e.part_pipeline(parts, b["obs"], b["clip"], b["rew"], b["done"], b["trunc"], b["term"]).collect(env.step_range_fn, env.handle)
+                    out[f"{tag0}host {name} {robot} {parts} range(s) | {'served' if mode == '2' else 'launch-per-step'} | after {i}"] = rollout_digest(e, b["clip"])
+            finally:
+                os.environ.pop("MOBROB_COLLECT_SERVER", None)
+                os.environ.pop("MOBROB_SERVER_TIMEOUT_S", None)
+            env.close()
+            e.close()
+    # ---- act / store per step, pinned and ordinary buffers, a time limit of 5 steps (truncated rows with a bootstrap)
+    for H in (64, 256):
+        for pinned in (True, False):
+            D, A, N, T = 14, 2, 6, 12
+            e = engine("point", H, N, T)
+            env = O.NumpySyntheticVecEnv(N, D, A, p_term=0.1, time_limit=5, seed=3)
+            mk = e.pinned if pinned else (lambda shape, dtype=np.float32: np.zeros(shape, dtype))
+            b = dict(obs=mk((N, D)), clip=mk((N, A)), rew=mk((N,)), done=mk((N,), np.uint8), trunc=mk((N,), np.uint8), term=mk((N, D)))
+            b["obs"][:] = env.reset()
+            saw_trunc = False
+            for i in (1, 2):
+                e.rollout_begin()
+                for t in range(T):
+                    e.act(b["obs"], None, out_clipped=b["clip"], want_all=False)
+                    obs, rew, done, trunc, term = env.step(b["clip"].copy())
+                    b["obs"][:], b["rew"][:], b["done"][:], b["trunc"][:], b["term"][:] = obs, rew, done, trunc, term
+                    saw_trunc |= bool(trunc.any())
+                    e.store(b["rew"], b["done"], b["trunc"], b["term"])
+                e.finish_rollout(b["obs"], b["done"])
+                assert saw_trunc
+                out[f"{tag0}act/store 2x{H} {'pinned' if pinned else 'ordinary'} buffers | after {i}"] = rollout_digest(e, b["clip"])
+            e.close()
+
+
+if len(sys.argv) >= 3 and sys.argv[1] == "--run-s8off":
+    from mobrob_amd import _lib
+    _lib.LIB_PATH = sys.argv[2]
+    out = {}
+    rollout_legs(out, True)
+    print(json.dumps(out))
+elif len(sys.argv) == 3 and sys.argv[1] == "--run":
     import numpy as np, hashlib
     from mobrob_amd import _lib
     _lib.LIB_PATH = sys.argv[2]
@@ -91,17 +220,21 @@ if len(sys.argv) == 3 and sys.argv[1] == "--run":
             h.update(m[k].tobytes()); h.update(v[k].tobytes())
         out[f"{D}x{A}x{H}"] = [h.hexdigest()[:16], step, repr(st["grad_norm"]), repr(st["loss"])]
         e.close()
+    rollout_legs(out, False)
     eval_follow_legs(out)
     print(json.dumps(out))
 else:
     res = []
     for p in sys.argv[1:3]:   # one process at a time; a child that fails ends the comparison
-        c = subprocess.run([sys.executable, __file__, "--run", p], capture_output=True, text=True)
-        if c.returncode != 0:
-            sys.exit(f"{p}: exit status {c.returncode}\n{c.stderr[-4000:]}")
-        res.append(json.loads(c.stdout.strip().splitlines()[-1]))
+        r = {}
+        for leg, env in (("--run", {}), ("--run-s8off", {"MOBROB_ROLLOUT_S8": "0"})):
+            c = subprocess.run([sys.executable, __file__, leg, p], capture_output=True, text=True, env={**os.environ, **env})
+            if c.returncode != 0:
+                sys.exit(f"{p} ({leg}): exit status {c.returncode}\n{c.stderr[-4000:]}")
+            r.update(json.loads(c.stdout.strip().splitlines()[-1]))
+        res.append(r)
     for k in res[0]:
-        print(f"{k:<62}", "IDENTICAL" if res[0][k] == res[1][k] else "DIFFERENT", res[0][k], res[1][k])
+        print(f"{k:<86}", "IDENTICAL" if res[0][k] == res[1][k] else "DIFFERENT", res[0][k], res[1][k])
     bad = [k for k in res[0] if res[0][k] != res[1][k]]
     print(f"{len(res[0]) - len(bad)} of {len(res[0])} identical")
     sys.exit(1 if bad else 0)
