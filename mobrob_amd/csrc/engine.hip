@@ -88,9 +88,11 @@ int fail(int code, const char* fmt, ...) {
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int rup(int a, int b) { return cdiv(a, b) * b; }
 
-// an environment variable as a number, `dflt` when it is not set (a switch that only asks "is it set" keeps its getenv)
+// an environment variable as a number, `dflt` when it is not set
 inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 inline double env_double(const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; }
+// MOBROB_NO_X3, MOBROB_NO_TRAIN_X3, MOBROB_NO_CHAIN, MOBROB_NO_NORM_RECORDS switch their feature off by being PRESENT: any value, "0" included
+inline bool env_switched_off(const char* name) { return getenv(name) != nullptr; }
 
 struct ProfSpan {
   hipEvent_t a, b;
@@ -653,18 +655,55 @@ int upload_obs(mobrob_ppo_engine* e, const float* host, float* dev_rows, int row
   return MOBROB_OK;
 }
 
-int fused_init(mobrob_ppo_engine* e) {
+// ---- the update's argument structs: one filler each for what does not change from minibatch to minibatch (the callers add rows /
+// count / advstat / inv_bg, the slab count and group, b_local, stats_row) ----
+template <class Args>   // the loss hyper-parameters, which FusedTrainArgs, Fused64TrainArgs and LossArgs name alike
+void fill_loss_hyper(const mobrob_ppo_engine* e, Args& a) {
+  a.log_std = e->params + e->offs[T_LOGSTD]; a.normalize = e->cfg.normalize_advantage;
+  a.clip = (float)e->cfg.clip_range; a.vf_coef = (float)e->cfg.vf_coef; a.ent_coef = (float)e->cfg.ent_coef; a.clip_vf = (float)e->clip_vf;
+}
+Fused64TrainArgs train64_args(const mobrob_ppo_engine* e) {
+  const FusedState& f = e->fused;
+  Fused64TrainArgs a{};
+  for (int n = 0; n < 2; ++n) { a.net[n] = f.net[n]; a.wpack[n] = reinterpret_cast<const float*>(f.net[n].W1f); }
+  a.obs = e->obs; a.actions = e->actions; a.A = e->A; a.old_logp = e->logp; a.adv = e->adv; a.ret = e->ret; a.old_values = e->values;
+  fill_loss_hyper(e, a);
+  a.slabs = f.slabs; a.sums = e->grads + e->P; a.stamps = f.stamps;
+  return a;
+}
+FusedTrainArgs train256_args(const mobrob_ppo_engine* e) {
+  const FusedState& f = e->fused;
+  FusedTrainArgs a{};
+  a.net[0] = f.net[0]; a.net[1] = f.net[1];
+  a.obs = e->obs; a.Dp = e->Dp; a.A = e->A; a.rec = f.train_rec; a.RW = train_rec_width(e->A);
+  fill_loss_hyper(e, a);
+  a.slabs = f.slabs; a.slab_floats = f.slab_floats; a.sums = e->grads + e->P; a.stamps = f.stamps;
+  return a;
+}
+template <class Args>   // what SlabReduceArgs and Slab64ReduceArgs name alike
+Args reduce_args(const mobrob_ppo_engine* e) {
+  Args s{};
+  s.slabs = e->fused.slabs; s.grads = e->grads; s.P = e->P;
+  for (int i = 0; i < 14; ++i) s.offs[i] = e->offs[i];
+  s.D = e->D; s.A = e->A; s.ent_coef = (float)e->cfg.ent_coef; s.sums = e->grads + e->P;
+  s.rec_sum = e->use_norm_records ? e->norm_rec_sum : nullptr; s.rec_t = e->norm_rec_t;   // (inside train_loop with records on)
+  return s;
+}
+Slab64ReduceArgs slab64_reduce_args(const mobrob_ppo_engine* e) { return reduce_args<Slab64ReduceArgs>(e); }
+SlabReduceArgs slab_reduce_args(const mobrob_ppo_engine* e) {
+  SlabReduceArgs s = reduce_args<SlabReduceArgs>(e);
+  s.slab_floats = e->fused.slab_floats; s.Dp = e->Dp; s.h16 = e->A <= 16;
+  return s;
+}
+StatsArgs stats_args(const mobrob_ppo_engine* e) {
+  StatsArgs st{};
+  st.loss_sums = e->grads + e->P; st.log_std = e->params + e->offs[T_LOGSTD]; st.n_act = e->A; st.sde = e->sde;
+  st.ent_coef = (float)e->cfg.ent_coef; st.vf_coef = (float)e->cfg.vf_coef;
+  return st;
+}
+// fused_init, step 1: the f32 weight packs of both networks, one allocation carved per network
+int fused_carve_packs(mobrob_ppo_engine* e) {
   FusedState& f = e->fused;
-  // (every fused kernel's epilogue is tanh: ReLU networks run the generic GEMM chain)
-  f.enabled = e->cfg.fast_kernels && e->cfg.activation == MOBROB_ACT_TANH && e->Lp == 2 && e->Lv == 2 && !e->sde &&
-              fused_shape_ok(e->D, e->A, e->H1, e->H2, e->G1, e->G2);   // (other depths: generic GEMM chain)
-  if (!f.enabled) return MOBROB_OK;
-  f.D = e->D; f.Dp = e->Dp; f.A = e->A; f.H = e->H1;
-  if ((uint64_t)(e->T + 1) * e->N * e->Dp * 4ull >= (1ull << 32) || (uint64_t)e->T * e->N * e->A * 4ull >= (1ull << 32) ||
-      (uint64_t)e->T * e->N * train_rec_width(e->A) * 4ull >= (1ull << 32)) {
-    f.enabled = false;  // the fused kernels address rollout rows and training records with 32-bit byte offsets
-    return MOBROB_OK;
-  }
   const int H = f.H;
   const size_t nW1 = (size_t)(H / 32) * (e->Dp / 8) * 256, nW2 = (size_t)(H / 32) * (H / 8) * 256;
   const size_t nW3f = (size_t)(H / 8) * 256, nW3b = (size_t)(H / 32) * 4 * 256;
@@ -672,7 +711,7 @@ int fused_init(mobrob_ppo_engine* e) {
   const size_t per_net = nW1 + 2 * nW2 + nW3f + nW3h + nW3b + 2 * H;
   f.packed_floats = 2 * per_net;
   CHK(dalloc(e, &f.packed, f.packed_floats));
-  const int bias_ids[2][3] = {{T_PB1, T_PB2, T_AB}, {T_VB1, T_VB2, T_VB}};
+  const int head_bias[2] = {T_AB, T_VB};
   for (int n = 0; n < 2; ++n) {
     float* p = f.packed + n * per_net;
     f.net[n].W1f = reinterpret_cast<const f32x4*>(p); p += nW1;
@@ -683,11 +722,17 @@ int fused_init(mobrob_ppo_engine* e) {
     f.net[n].b1s = p; p += H;
     f.net[n].b2s = p; p += H;
     f.net[n].W3h = reinterpret_cast<const f32x4*>(p); p += nW3h;  // last: the H = 64 kernels mirror [W1f, b2s] as one block
-    f.net[n].b3 = e->params + e->offs[bias_ids[n][2]];
+    f.net[n].b3 = e->params + e->offs[head_bias[n]];
     f.net[n].head = n == 0 ? e->A : 1;
     f.net[n].W1x = nullptr; f.net[n].W2x = nullptr; f.net[n].W2bx = nullptr;
     f.net[n].W1c = nullptr; f.net[n].W2c = nullptr; f.net[n].W2bc = nullptr; f.net[n].W3c = nullptr; f.net[n].W3bc = nullptr;
   }
+  return MOBROB_OK;
+}
+// step 2, in arena order: gradient slabs; the epoch kernel's buffers (64 wide) or the x3 / chain packs and the training records (256 wide); stamps
+int fused_alloc_buffers(mobrob_ppo_engine* e) {
+  FusedState& f = e->fused;
+  const int H = f.H;
   f.max_grid = 256;
   if (H == 64) {
     f.slab_floats = s64_size();
@@ -704,20 +749,18 @@ int fused_init(mobrob_ppo_engine* e) {
   } else {
     f.slab_floats = slab_size(e->Dp);
     CHK(dalloc(e, &f.slabs, (size_t)f.max_grid * f.slab_floats));
-    if (e->cfg.forward_x3 && e->cfg.activation == MOBROB_ACT_TANH && getenv("MOBROB_NO_X3") == nullptr) {
+    if (e->cfg.forward_x3 && e->cfg.activation == MOBROB_ACT_TANH && !env_switched_off("MOBROB_NO_X3")) {
       // x3 packs of the hidden layers of both networks (kernels_fused.h, gemm_x3_r32): rebuilt at the start of every rollout
       for (int n = 0; n < 2; ++n) {
-        unsigned* w1 = nullptr; unsigned* w2 = nullptr;
+        unsigned* w1 = nullptr; unsigned* w2 = nullptr; unsigned* w2b = nullptr;
         CHK(dalloc(e, &w1, (size_t)(H / 32) * (e->Dp / 16) * 192 * 4));
         CHK(dalloc(e, &w2, (size_t)(H / 32) * (H / 16) * 192 * 4));
-        f.net[n].W1x = w1; f.net[n].W2x = w2;
-        unsigned* w2b = nullptr;
         CHK(dalloc(e, &w2b, (size_t)(H / 32) * (H / 16) * 192 * 4));
-        f.net[n].W2bx = w2b;
+        f.net[n].W1x = w1; f.net[n].W2x = w2; f.net[n].W2bx = w2b;
       }
-      f.train_x3 = e->A <= 16 && e->Dp != 48 && getenv("MOBROB_NO_TRAIN_X3") == nullptr;
+      f.train_x3 = e->A <= 16 && e->Dp != 48 && !env_switched_off("MOBROB_NO_TRAIN_X3");
       // the register-chained gradient kernel (kernels_chain.h) takes the same shapes; MOBROB_NO_CHAIN=1 keeps k_fused_train<.., X3>
-      f.train_chain = f.train_x3 && getenv("MOBROB_NO_CHAIN") == nullptr;
+      f.train_chain = f.train_x3 && !env_switched_off("MOBROB_NO_CHAIN");
       if (f.train_chain) {
         const int K1 = (e->Dp + 31) / 32;
         for (int n = 0; n < 2; ++n) {
@@ -736,118 +779,184 @@ int fused_init(mobrob_ppo_engine* e) {
     f.lds_bytes = fused_lds_bytes(e->Dp);
     f.lds_act_bytes = fused_lds_act_bytes(e->Dp);
   }
-  CHK(dalloc(e, &f.stamps, 32));
-  if (!e->plan_only) HIPC(fused_set_lds_attr(f));
-  {  // norm-record tables: which (network, block, slot) of the reduction kernel holds which tensor -- emulated here
-    // exactly as block_norm_records forms them (per wave: tensors by first occurrence; adjacent equal ones merge)
-    const int nb = cdiv(f.slab_floats, 256);
-    CHK(dalloc(e, &e->norm_rec_sum, (size_t)2 * nb * kNormRec));
-    CHK(dalloc(e, &e->norm_rec_t, (size_t)2 * nb * kNormRec));
-    CHK(dalloc(e, &e->fold_idx_dev, (size_t)2 * nb * kNormRec));
-    SlabReduceArgs s256{};
-    Slab64ReduceArgs s64{};
-    for (int i = 0; i < 14; ++i) { s256.offs[i] = e->offs[i]; s64.offs[i] = e->offs[i]; }
-    s256.D = e->D; s256.Dp = e->Dp; s256.A = e->A; s256.h16 = e->A <= 16; s256.P = e->P; s256.slab_floats = f.slab_floats;
-    s64.D = e->D; s64.A = e->A; s64.P = e->P;
-    std::vector<std::vector<int>> per_tensor(13);
-    for (int net = 0; net < 2; ++net)
-      for (int b = 0; b < nb; ++b) {
-        std::vector<int> recs;  // tensors of this block's records, in order
-        for (int w = 0; w < 4; ++w) {
-          std::vector<int> wave;
-          for (int l = 0; l < 64; ++l) {
-            const int p = b * 256 + w * 64 + l;
-            const int dst = p < f.slab_floats ? (H == 64 ? slab64_to_canonical(s64, net, p) : slab_to_canonical(s256, net, p)) : -1;
-            const int t = tensor_of_canonical(e->offs, e->P, dst);
-            if (t >= 0 && std::find(wave.begin(), wave.end(), t) == wave.end()) wave.push_back(t);
-          }
-          for (int t : wave)
-            if (recs.empty() || recs.back() != t) recs.push_back(t);
+  return dalloc(e, &f.stamps, 32);
+}
+// step 3: the norm-record tables -- which (network, block, slot) of the reduction kernel holds which tensor, emulated here exactly
+// as block_norm_records forms them (per wave: tensors by first occurrence; adjacent equal ones merge)
+int build_norm_record_tables(mobrob_ppo_engine* e) {
+  const FusedState& f = e->fused;
+  const int nb = cdiv(f.slab_floats, 256);
+  CHK(dalloc(e, &e->norm_rec_sum, (size_t)2 * nb * kNormRec));
+  CHK(dalloc(e, &e->norm_rec_t, (size_t)2 * nb * kNormRec));
+  CHK(dalloc(e, &e->fold_idx_dev, (size_t)2 * nb * kNormRec));
+  const SlabReduceArgs s256 = slab_reduce_args(e);
+  const Slab64ReduceArgs s64 = slab64_reduce_args(e);
+  std::vector<std::vector<int>> per_tensor(13);
+  for (int net = 0; net < 2; ++net)
+    for (int b = 0; b < nb; ++b) {
+      std::vector<int> recs;  // tensors of this block's records, in order
+      for (int w = 0; w < 4; ++w) {
+        std::vector<int> wave;
+        for (int l = 0; l < 64; ++l) {
+          const int p = b * 256 + w * 64 + l;
+          const int dst = p < f.slab_floats ? (f.H == 64 ? slab64_to_canonical(s64, net, p) : slab_to_canonical(s256, net, p)) : -1;
+          const int t = tensor_of_canonical(e->offs, e->P, dst);
+          if (t >= 0 && std::find(wave.begin(), wave.end(), t) == wave.end()) wave.push_back(t);
         }
-        if ((int)recs.size() > kNormRec) return fail(MOBROB_ERR_INVALID, "norm record table: %zu tensors in one reduction block", recs.size());
-        for (size_t k = 0; k < recs.size(); ++k) per_tensor[recs[k]].push_back((net * nb + b) * kNormRec + (int)k);
+        for (int t : wave)
+          if (recs.empty() || recs.back() != t) recs.push_back(t);
       }
-    std::vector<int> fold;
-    for (int t = 0; t < 13; ++t) {
-      e->fold_start[t] = (int)fold.size();
-      fold.insert(fold.end(), per_tensor[t].begin(), per_tensor[t].end());
+      if ((int)recs.size() > kNormRec) return fail(MOBROB_ERR_INVALID, "norm record table: %zu tensors in one reduction block", recs.size());
+      for (size_t k = 0; k < recs.size(); ++k) per_tensor[recs[k]].push_back((net * nb + b) * kNormRec + (int)k);
     }
-    e->fold_start[13] = (int)fold.size();
-    if (fold.size() > 1024) return fail(MOBROB_ERR_INVALID, "norm record table too large (%zu)", fold.size());
-    if (!e->plan_only)
-      HIPC(hipMemcpyAsync(e->fold_idx_dev, fold.data(), fold.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    if (!e->plan_only) HIPC(hipStreamSynchronize(e->stream));
+  std::vector<int> fold;
+  for (int t = 0; t < 13; ++t) {
+    e->fold_start[t] = (int)fold.size();
+    fold.insert(fold.end(), per_tensor[t].begin(), per_tensor[t].end());
   }
+  e->fold_start[13] = (int)fold.size();
+  if (fold.size() > 1024) return fail(MOBROB_ERR_INVALID, "norm record table too large (%zu)", fold.size());
+  if (!e->plan_only)
+    HIPC(hipMemcpyAsync(e->fold_idx_dev, fold.data(), fold.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  if (!e->plan_only) HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
 }
 
+int fused_init(mobrob_ppo_engine* e) {
+  FusedState& f = e->fused;
+  // (every fused kernel's epilogue is tanh: ReLU networks run the generic GEMM chain)
+  f.enabled = e->cfg.fast_kernels && e->cfg.activation == MOBROB_ACT_TANH && e->Lp == 2 && e->Lv == 2 && !e->sde &&
+              fused_shape_ok(e->D, e->A, e->H1, e->H2, e->G1, e->G2);   // (other depths: generic GEMM chain)
+  if (!f.enabled) return MOBROB_OK;
+  f.D = e->D; f.Dp = e->Dp; f.A = e->A; f.H = e->H1;
+  if ((uint64_t)(e->T + 1) * e->N * e->Dp * 4ull >= (1ull << 32) || (uint64_t)e->T * e->N * e->A * 4ull >= (1ull << 32) ||
+      (uint64_t)e->T * e->N * train_rec_width(e->A) * 4ull >= (1ull << 32)) {
+    f.enabled = false;  // the fused kernels address rollout rows and training records with 32-bit byte offsets
+    return MOBROB_OK;
+  }
+  CHK(fused_carve_packs(e));
+  CHK(fused_alloc_buffers(e));
+  if (!e->plan_only) HIPC(fused_set_lds_attr(f));
+  return build_norm_record_tables(e);
+}
+// Which 64-wide gradient kernel a minibatch of B rows takes and how its slabs are reduced: decided here and nowhere else
+// (fused64_minibatch_grad launches from it; epoch_kernel_eligible asks it about the largest minibatch of an epoch).
+struct Grad64Plan {
+  int ntiles, grid;    // 32-row tiles; k_fused64_train's workgroups (g_train_waves one-tile waves each, both networks)
+  bool split;          // small: one workgroup per (tile, network) (kernels_split64.h); its per-tile slabs are folded in groups of g_train_waves
+                       // tiles, which reproduces the block kernel bit for bit as long as that kernel would have given every wave at most one tile
+  bool pair;           // large: persistent two-wave workgroups, four per CU (kernels_pair64.h); one slab per workgroup of two pairs
+  int nseq, nbseq;     // k_pair64_train: tile sequences, and workgroups per network
+  int nblocks, group;  // the reduction's slab count and fold group (Slab64ReduceArgs)
+  bool wide;           // k_slab64_reduce_wide: more than 128 slabs per network
+};
+Grad64Plan grad64_plan(const mobrob_ppo_engine* e, int B) {
+  const FusedState& f = e->fused;
+  const int tw = g_train_waves(e->Dp);
+  Grad64Plan p{};
+  p.ntiles = cdiv(B, GR);
+  p.grid = 2 * std::min(f.max_grid / 2, cdiv(p.ntiles, tw));
+  p.split = p.ntiles <= e->split64_max_tiles && 2 * p.ntiles <= f.max_grid && p.ntiles <= (p.grid / 2) * tw;
+  p.pair = !p.split && e->pair64_min_tiles > 0 && p.ntiles >= e->pair64_min_tiles;
+  p.nseq = std::min(p.ntiles, f.pair_nseq_max); p.nbseq = (p.nseq + 1) / 2;
+  p.nblocks = p.split ? 2 * p.ntiles : (p.pair ? 2 * p.nbseq : p.grid); p.group = p.split ? tw : 1;
+  p.wide = p.pair && p.nbseq > 128;
+  return p;
+}
 // 64-wide networks: one independent wave per 32-row tile (kernels_fused64.h)
 void fused64_minibatch_grad(mobrob_ppo_engine* e, int mb, int start, int B, float inv_bg) {
   FusedState& f = e->fused;
-  Fused64TrainArgs a{};
-  a.net[0] = f.net[0]; a.net[1] = f.net[1];
-  a.obs = e->obs; a.actions = e->actions; a.A = e->A; a.old_logp = e->logp; a.adv = e->adv; a.ret = e->ret;
-  a.rows = e->rows + start; a.count = B; a.log_std = e->params + e->offs[T_LOGSTD];
-  a.advstat = e->advstat + 4 * (size_t)mb; a.normalize = e->cfg.normalize_advantage;
-  a.clip = (float)e->cfg.clip_range; a.vf_coef = (float)e->cfg.vf_coef; a.ent_coef = (float)e->cfg.ent_coef;
-  a.clip_vf = (float)e->clip_vf; a.old_values = e->values;
-  a.inv_bg = inv_bg; a.slabs = f.slabs; a.sums = e->grads + e->P; a.stamps = f.stamps;
-  const int ntiles = cdiv(B, GR);
-  const int grid = 2 * std::min(f.max_grid / 2, cdiv(ntiles, g_train_waves(e->Dp)));
-  a.wpack[0] = reinterpret_cast<const float*>(f.net[0].W1f);
-  a.wpack[1] = reinterpret_cast<const float*>(f.net[1].W1f);
-  // Small minibatches: one workgroup per tile (kernels_split64.h); its per-tile slabs are folded in groups of
-  // g_train_waves tiles, which reproduces the block kernel bit for bit as long as that kernel would have given every
-  // wave at most one tile.
-  const bool split = ntiles <= e->split64_max_tiles && 2 * ntiles <= f.max_grid && ntiles <= (grid / 2) * g_train_waves(e->Dp);
-  // Large minibatches: persistent two-wave workgroups, four per CU (kernels_pair64.h); one slab per workgroup.
-  const bool pair = !split && e->pair64_min_tiles > 0 && ntiles >= e->pair64_min_tiles;
-  const int nseq = std::min(ntiles, f.pair_nseq_max);
+  const Grad64Plan pl = grad64_plan(e, B);
+  Fused64TrainArgs a = train64_args(e);
+  a.rows = e->rows + start; a.count = B; a.advstat = e->advstat + 4 * (size_t)mb; a.inv_bg = inv_bg;
   {
     ProfScope ps(e, MOBROB_K_TRAIN_GRAD);
-    if (split) split64_launch_train(f, a, ntiles, e->stream);
-    else if (pair) pair64_launch_train(f, a, nseq, e->stream);
-    else fused64_launch_train(f, a, grid, e->stream);
+    if (pl.split) split64_launch_train(f, a, pl.ntiles, e->stream);
+    else if (pl.pair) pair64_launch_train(f, a, pl.nseq, pl.nbseq, e->stream);
+    else fused64_launch_train(f, a, pl.grid, e->stream);
   }
   ProfScope pr(e, MOBROB_K_GRAD_REDUCE);
-  Slab64ReduceArgs s{};
-  const int nbseq = (nseq + 1) / 2;  // k_pair64_train: one slab per workgroup of two pairs
-  s.slabs = f.slabs; s.nblocks = split ? 2 * ntiles : (pair ? 2 * nbseq : grid); s.group = split ? g_train_waves(e->Dp) : 1; s.grads = e->grads; s.P = e->P;
-  for (int i = 0; i < 14; ++i) s.offs[i] = e->offs[i];
-  s.D = e->D; s.A = e->A; s.ent_coef = (float)e->cfg.ent_coef; s.b_local = (float)B; s.inv_bg = inv_bg;
-  s.sums = e->grads + e->P;
-  s.rec_sum = e->use_norm_records ? e->norm_rec_sum : nullptr; s.rec_t = e->norm_rec_t;
-  if (pair && nbseq > 128) hipLaunchKernelGGL(k_slab64_reduce_wide, dim3(cdiv(s64_size(), 256), 2), dim3(1024), 0, e->stream, s);
+  Slab64ReduceArgs s = slab64_reduce_args(e);
+  s.nblocks = pl.nblocks; s.group = pl.group; s.b_local = (float)B; s.inv_bg = inv_bg;
+  if (pl.wide) hipLaunchKernelGGL(k_slab64_reduce_wide, dim3(cdiv(s64_size(), 256), 2), dim3(1024), 0, e->stream, s);
   else hipLaunchKernelGGL(k_slab64_reduce, dim3(cdiv(s64_size(), 256), 2), dim3(256), 0, e->stream, s);
+}
+
+// The training records (kernels_fused.h) are packed once per rollout: every call that can change actions / values /
+// log-probs / advantages / returns clears train_rec_valid (rollouts, GAE, write_buffer); a caller that obtained a device
+// pointer to one of them (buffer_info) can write without the engine seeing it, so from then on they are re-packed before
+// every gradient launch.
+void ensure_train_records(mobrob_ppo_engine* e) {
+  if (!e->fused.train_rec || (e->train_rec_valid && !e->train_rec_external)) return;
+  TrainRecArgs r{};
+  r.actions = e->actions; r.old_logp = e->logp; r.adv = e->adv; r.ret = e->ret; r.values = e->values;
+  r.A = e->A; r.RW = train_rec_width(e->A); r.rows = e->N * e->T; r.rec = e->fused.train_rec;
+  const long long items = (long long)r.rows * (r.RW / 4);
+  hipLaunchKernelGGL(k_build_train_records, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, e->stream, r);
+  e->train_rec_valid = true;
 }
 
 // fused minibatch gradient: one persistent kernel + the deterministic slab reduction
 void fused_minibatch_grad(mobrob_ppo_engine* e, int mb, int start, int B, float inv_bg) {
   FusedState& f = e->fused;
-  FusedTrainArgs a{};
-  a.net[0] = f.net[0]; a.net[1] = f.net[1];
-  a.obs = e->obs; a.Dp = e->Dp; a.A = e->A; a.rec = f.train_rec; a.RW = train_rec_width(e->A);
-  a.rows = e->rows + start; a.count = B; a.log_std = e->params + e->offs[T_LOGSTD];
-  a.advstat = e->advstat + 4 * (size_t)mb; a.normalize = e->cfg.normalize_advantage;
-  a.clip = (float)e->cfg.clip_range; a.vf_coef = (float)e->cfg.vf_coef; a.ent_coef = (float)e->cfg.ent_coef;
-  a.clip_vf = (float)e->clip_vf;
-  a.inv_bg = inv_bg; a.slabs = f.slabs; a.slab_floats = f.slab_floats; a.sums = e->grads + e->P;
-  a.stamps = f.stamps;
-  const int ntiles = cdiv(B, FR);
-  const int grid = 2 * std::min(f.max_grid / 2, ntiles);
+  ensure_train_records(e);
+  FusedTrainArgs a = train256_args(e);
+  a.rows = e->rows + start; a.count = B; a.advstat = e->advstat + 4 * (size_t)mb; a.inv_bg = inv_bg;
+  const int grid = 2 * std::min(f.max_grid / 2, cdiv(B, FR));
   // the 8 loss accumulators behind the gradient vector were zeroed by the previous k_adam_pack (or at allocation)
   {
     ProfScope ps(e, MOBROB_K_TRAIN_GRAD);
     fused_launch_train(f, a, grid, e->stream);
   }
   ProfScope pr(e, MOBROB_K_GRAD_REDUCE);
-  SlabReduceArgs s{};
-  s.slabs = f.slabs; s.slab_floats = f.slab_floats; s.nslabs = grid; s.grads = e->grads; s.P = e->P;
-  for (int i = 0; i < 14; ++i) s.offs[i] = e->offs[i];
-  s.D = e->D; s.Dp = e->Dp; s.A = e->A; s.h16 = e->A <= 16; s.ent_coef = (float)e->cfg.ent_coef; s.b_local = (float)B; s.inv_bg = inv_bg;
-  s.sums = e->grads + e->P;
-  s.rec_sum = e->use_norm_records ? e->norm_rec_sum : nullptr; s.rec_t = e->norm_rec_t;
+  SlabReduceArgs s = slab_reduce_args(e);
+  s.nslabs = grid; s.b_local = (float)B; s.inv_bg = inv_bg;
   hipLaunchKernelGGL(k_slab_reduce, dim3(cdiv(f.slab_floats, 256), 2), dim3(256), 0, e->stream, s);
+}
+
+// generic GEMM chain: gather, forward, loss, backward of both networks (kernels_generic.h)
+void generic_minibatch_grad(mobrob_ppo_engine* e, int mb, int start, int B, float inv_bg) {
+  ProfScope ps(e, MOBROB_K_TRAIN_GRAD);
+  // (the gather also zeroes the gradient vector + loss sums and the gSDE GEMM's output: everything this step adds into with atomics)
+  hipLaunchKernelGGL(k_gather, dim3(cdiv(B * (e->Dp / 4), 256)), dim3(256), 0, e->stream, e->rows + start, B, e->obs, e->Dp,
+                     e->actions, e->A, e->logp, e->adv, e->ret, e->Xg, e->actg, e->lpg, e->advg, e->retg, e->values,
+                     e->clip_vf >= 0.0 ? e->oldvg : (float*)nullptr, e->grads, e->P + 8, e->sde ? e->sde_graw : (float*)nullptr,
+                     e->sde ? e->HL * e->A : 0);
+  forward_generic(e, e->Xg, B, true, e->mu, true, e->vout, true);
+  LossArgs L{};
+  L.mu = e->mu; L.ldmu = e->Ap; L.v = e->vout; L.actions = e->actg; L.old_logp = e->lpg; L.adv = e->advg;
+  L.ret = e->retg; L.advstat = e->advstat + 4 * (size_t)mb; L.B = B; L.A = e->A;
+  fill_loss_hyper(e, L);
+  L.old_v = e->oldvg; L.inv_bg = inv_bg; L.dmu = e->dmu; L.lddmu = e->Ap; L.dv = e->dv; L.lddv = 8;
+  L.sums = e->grads + e->P; L.g_log_std = Gp(e, T_LOGSTD); L.g_b_action = Gp(e, T_AB); L.g_b_value = Gp(e, T_VB);
+  if (e->sde) {
+    sde_variance(e, B, true, e->sde_lat2);   // (log_std moved in the previous optimizer step; latent^2 for the gradient GEMM on the way)
+    L.lat = e->hp[e->Lp - 1]; L.HL = e->HL; L.var = e->sde_var; L.ldvar = e->Ap; L.gsig = e->sde_gsig; L.ldg = e->Ap;
+  }
+  // (the padding columns of dmu / dv -- K padding of the NN GEMMs -- are zeroed by k_loss itself)
+  hipLaunchKernelGGL(k_loss, dim3(cdiv(B, 256)), dim3(256), loss_lds_bytes(e->A), e->stream, L);
+  if (e->sde) {   // g_log_std = 2 std (d std / d log_std) * ((latent^2)^T . gsig) (summed over the actions without full_std): the entropy term is inside gsig
+    linear_bwd_weight(e, e->sde_lat2, e->HL, e->sde_gsig, e->Ap, e->sde_graw, e->A, e->HL, e->A, B);
+    hipLaunchKernelGGL(k_sde_scale_grad, dim3(cdiv(e->HL * e->A, 256)), dim3(256), 0, e->stream, Gp(e, T_LOGSTD), e->sde_graw, Pp(e, T_LOGSTD), e->HL,
+                       e->A, e->sde_mode);
+  }   // (state-independent log_std: its entropy term is added by k_loss)
+  // backward of both networks, last hidden layer first: dW of the layer above, then dz of this layer (dtanh / dReLU + bias sums)
+  GemmQueue qp, qv;
+  auto backward = [&](GemmQueue* q, int L, const int* Hw, float* const* h, float* const* dz, const float* dhead, int ldd, const float* headWp,
+                      int head_rows, int head_pad, int t_headW, const int* tW, const int* tB) {
+    const int HLw = Hw[L - 1];
+    linear_bwd_weight(e, dhead, ldd, h[L - 1], HLw, Gp(e, t_headW), HLw, head_rows, HLw, B, q);
+    linear_bwd_input(e, dhead, ldd, headWp, HLw, h[L - 1], HLw, dz[L - 1], HLw, Gp(e, tB[L - 1]), B, HLw, head_pad, q);
+    for (int l = L - 1; l >= 1; --l) {
+      linear_bwd_weight(e, dz[l], Hw[l], h[l - 1], Hw[l - 1], Gp(e, tW[l]), Hw[l - 1], Hw[l], Hw[l - 1], B, q);
+      linear_bwd_input(e, dz[l], Hw[l], Pp(e, tW[l]), Hw[l - 1], h[l - 1], Hw[l - 1], dz[l - 1], Hw[l - 1], Gp(e, tB[l - 1]), B, Hw[l - 1], Hw[l], q);
+    }
+    linear_bwd_weight(e, dz[0], Hw[0], e->Xg, e->Dp, Gp(e, tW[0]), e->D, Hw[0], e->D, B, q);
+  };
+  // both networks' chains alternate weight-gradient and input-gradient GEMMs from the head down: queued, then launched pairwise
+  backward(&qp, e->Lp, e->Hp, e->hp, e->dzp, e->dmu, e->Ap, e->aWp, e->A, e->Ap, T_AW, e->tPW, e->tPB);
+  backward(&qv, e->Lv, e->Hv, e->hv, e->dzv, e->dv, 8, e->vWp, 1, 8, T_VW, e->tVW, e->tVB);
+  run_queues(e, qp, qv, 2);
 }
 
 // ---- rollout streamer --------------------------------------------------------------------------------
@@ -2266,20 +2375,6 @@ int mobrob_ctrl_drone_pid(mobrob_ppo_engine_t* e, int32_t n, int32_t dev_ptrs, c
 // ---- update ----------------------------------------------------------------------------------------
 int mobrob_ppo_num_minibatches(const mobrob_ppo_engine_t* e) { return e ? e->nmb : -1; }
 
-// The training records (kernels_fused.h) are packed once per rollout: every call that can change actions / values /
-// log-probs / advantages / returns clears train_rec_valid (rollouts, GAE, write_buffer); a caller that obtained a device
-// pointer to one of them (buffer_info) can write without the engine seeing it, so from then on they are re-packed before
-// every gradient launch.
-static void ensure_train_records(mobrob_ppo_engine* e) {
-  if (!e->fused.train_rec || (e->train_rec_valid && !e->train_rec_external)) return;
-  TrainRecArgs r{};
-  r.actions = e->actions; r.old_logp = e->logp; r.adv = e->adv; r.ret = e->ret; r.values = e->values;
-  r.A = e->A; r.RW = train_rec_width(e->A); r.rows = e->N * e->T; r.rec = e->fused.train_rec;
-  const long long items = (long long)r.rows * (r.RW / 4);
-  hipLaunchKernelGGL(k_build_train_records, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, e->stream, r);
-  e->train_rec_valid = true;
-}
-
 int mobrob_ppo_epoch_begin(mobrob_ppo_engine_t* e, const int64_t* perm) {
   if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
   if (!e->rollout_ready) return fail(MOBROB_ERR_STATE, "epoch_begin: rollout not finished (finish_rollout / collect first)");
@@ -2332,65 +2427,12 @@ int mobrob_ppo_minibatch_grad(mobrob_ppo_engine_t* e, int32_t mb) {
   if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
   if (!e->epoch_open) return fail(MOBROB_ERR_STATE, "minibatch_grad before epoch_begin");
   if (mb < 0 || mb >= e->nmb) return fail(MOBROB_ERR_INVALID, "minibatch %d out of range [0,%d)", mb, e->nmb);
-  const int total = e->N * e->T;
-  const int start = mb * e->Bl;
-  const int B = std::min(e->Bl, total - start);
+  const int start = mb * e->Bl, B = std::min(e->Bl, e->N * e->T - start);
   const float inv_bg = 1.0f / (float)((int64_t)B * e->cfg.world_size);
   e->cur_count = B;
-  if (e->fused.enabled) {
-    if (e->fused.H == 64) fused64_minibatch_grad(e, mb, start, B, inv_bg);
-    else {
-      ensure_train_records(e);
-      fused_minibatch_grad(e, mb, start, B, inv_bg);
-    }
-    HIPC(hipGetLastError());
-    e->grad_pending = true;
-    return MOBROB_OK;
-  }
-  ProfScope ps(e, MOBROB_K_TRAIN_GRAD);
-  float* sums = e->grads + e->P;
-  const int per = e->Dp / 4;
-  // (the gather also zeroes the gradient vector + loss sums and the gSDE GEMM's output: everything this step adds into with atomics)
-  hipLaunchKernelGGL(k_gather, dim3(cdiv(B * per, 256)), dim3(256), 0, e->stream, e->rows + start, B, e->obs, e->Dp,
-                     e->actions, e->A, e->logp, e->adv, e->ret, e->Xg, e->actg, e->lpg, e->advg, e->retg, e->values,
-                     e->clip_vf >= 0.0 ? e->oldvg : (float*)nullptr, e->grads, e->P + 8, e->sde ? e->sde_graw : (float*)nullptr,
-                     e->sde ? e->HL * e->A : 0);
-  forward_generic(e, e->Xg, B, true, e->mu, true, e->vout, true);
-  LossArgs L{};
-  L.mu = e->mu; L.ldmu = e->Ap; L.v = e->vout; L.actions = e->actg; L.old_logp = e->lpg; L.adv = e->advg;
-  L.ret = e->retg; L.log_std = Pp(e, T_LOGSTD); L.advstat = e->advstat + 4 * (size_t)mb; L.B = B; L.A = e->A;
-  L.normalize = e->cfg.normalize_advantage; L.clip = (float)e->cfg.clip_range; L.vf_coef = (float)e->cfg.vf_coef;
-  L.clip_vf = (float)e->clip_vf; L.old_v = e->oldvg;
-  L.ent_coef = (float)e->cfg.ent_coef; L.inv_bg = inv_bg; L.dmu = e->dmu; L.lddmu = e->Ap; L.dv = e->dv; L.lddv = 8;
-  L.sums = sums; L.g_log_std = Gp(e, T_LOGSTD); L.g_b_action = Gp(e, T_AB); L.g_b_value = Gp(e, T_VB);
-  if (e->sde) {
-    sde_variance(e, B, true, e->sde_lat2);   // (log_std moved in the previous optimizer step; latent^2 for the gradient GEMM on the way)
-    L.lat = e->hp[e->Lp - 1]; L.HL = e->HL; L.var = e->sde_var; L.ldvar = e->Ap; L.gsig = e->sde_gsig; L.ldg = e->Ap;
-  }
-  // (the padding columns of dmu / dv -- K padding of the NN GEMMs -- are zeroed by k_loss itself)
-  hipLaunchKernelGGL(k_loss, dim3(cdiv(B, 256)), dim3(256), loss_lds_bytes(e->A), e->stream, L);
-  if (e->sde) {   // g_log_std = 2 std (d std / d log_std) * ((latent^2)^T . gsig) (summed over the actions without full_std): the entropy term is inside gsig
-    linear_bwd_weight(e, e->sde_lat2, e->HL, e->sde_gsig, e->Ap, e->sde_graw, e->A, e->HL, e->A, B);
-    hipLaunchKernelGGL(k_sde_scale_grad, dim3(cdiv(e->HL * e->A, 256)), dim3(256), 0, e->stream, Gp(e, T_LOGSTD), e->sde_graw, Pp(e, T_LOGSTD), e->HL,
-                       e->A, e->sde_mode);
-  }   // (state-independent log_std: its entropy term is added by k_loss)
-  // backward of both networks, last hidden layer first: dW of the layer above, then dz of this layer (dtanh / dReLU + bias sums)
-  GemmQueue qp, qv;
-  auto backward = [&](GemmQueue* q, int L, const int* Hw, float* const* h, float* const* dz, const float* dhead, int ldd, const float* headWp,
-                      int head_rows, int head_pad, int t_headW, const int* tW, const int* tB) {
-    const int HLw = Hw[L - 1];
-    linear_bwd_weight(e, dhead, ldd, h[L - 1], HLw, Gp(e, t_headW), HLw, head_rows, HLw, B, q);
-    linear_bwd_input(e, dhead, ldd, headWp, HLw, h[L - 1], HLw, dz[L - 1], HLw, Gp(e, tB[L - 1]), B, HLw, head_pad, q);
-    for (int l = L - 1; l >= 1; --l) {
-      linear_bwd_weight(e, dz[l], Hw[l], h[l - 1], Hw[l - 1], Gp(e, tW[l]), Hw[l - 1], Hw[l], Hw[l - 1], B, q);
-      linear_bwd_input(e, dz[l], Hw[l], Pp(e, tW[l]), Hw[l - 1], h[l - 1], Hw[l - 1], dz[l - 1], Hw[l - 1], Gp(e, tB[l - 1]), B, Hw[l - 1], Hw[l], q);
-    }
-    linear_bwd_weight(e, dz[0], Hw[0], e->Xg, e->Dp, Gp(e, tW[0]), e->D, Hw[0], e->D, B, q);
-  };
-  // both networks' chains alternate weight-gradient and input-gradient GEMMs from the head down: queued, then launched pairwise
-  backward(&qp, e->Lp, e->Hp, e->hp, e->dzp, e->dmu, e->Ap, e->aWp, e->A, e->Ap, T_AW, e->tPW, e->tPB);
-  backward(&qv, e->Lv, e->Hv, e->hv, e->dzv, e->dv, 8, e->vWp, 1, 8, T_VW, e->tVW, e->tVB);
-  run_queues(e, qp, qv, 2);
+  if (!e->fused.enabled) generic_minibatch_grad(e, mb, start, B, inv_bg);
+  else if (e->fused.H == 64) fused64_minibatch_grad(e, mb, start, B, inv_bg);
+  else fused_minibatch_grad(e, mb, start, B, inv_bg);
   HIPC(hipGetLastError());
   e->grad_pending = true;
   return MOBROB_OK;
@@ -2401,6 +2443,10 @@ namespace {
 void fill_adam_pack_args(mobrob_ppo_engine* e, AdamPackArgs& a) {
   a.p = e->params; a.g = e->grads; a.m = e->m; a.v = e->v; a.P = e->P;
   a.chunks = e->chunks_dev; a.partial = e->chunk_partial; a.nchunks = e->nchunks;
+  if (e->use_norm_records) {   // inside train_loop: the reduction kernel left the norm records, k_adam_pack folds them
+    a.partial = e->norm_rec_sum; a.fold_idx = e->fold_idx_dev;
+    for (int i = 0; i <= kMaxTensors; ++i) a.fold_start[i] = e->fold_start[i];
+  }
   a.max_norm = (float)e->cfg.max_grad_norm; a.beta1 = (float)e->cfg.adam_beta1; a.beta2 = (float)e->cfg.adam_beta2;
   a.eps = (float)e->cfg.adam_eps;
   for (int i = 0; i <= kMaxTensors; ++i) a.offs[i] = e->offs[i];
@@ -2436,41 +2482,36 @@ void fill_adam_pack_args(mobrob_ppo_engine* e, AdamPackArgs& a) {
 }  // namespace
 
 namespace {
-struct ApplyCtx { float* stats_row; bool records; };
+// The optimizer's step counter moves here only: Adam's bias corrections of the step that begins, formed in float64 and rounded once.
+struct AdamStep { float step_size, bc2_sqrt; };
+AdamStep next_adam_step(mobrob_ppo_engine* e) {
+  e->adam_step++;
+  const double bc1 = 1.0 - std::pow(e->cfg.adam_beta1, (double)e->adam_step), bc2 = 1.0 - std::pow(e->cfg.adam_beta2, (double)e->adam_step);
+  return {(float)(e->cfg.learning_rate / bc1), (float)std::sqrt(bc2)};
+}
+// the row of the statistics ring the step that begins logs into (the oldest rows are dropped if nobody fetched them)
+int next_stats_row(mobrob_ppo_engine* e) {
+  if (e->stats_n >= e->stats_cap) e->stats_n = 0;
+  return e->stats_n++;
+}
 // first half of an optimizer step: loss statistics + per-tensor sums of squares of the (reduced) gradient
-int apply_norms(mobrob_ppo_engine* e, ApplyCtx& c) {
-  if (e->stats_n >= e->stats_cap) e->stats_n = 0;  // ring: oldest rows are dropped if nobody fetched them
-  c.stats_row = e->stats + (size_t)e->stats_n * 8;
-  e->stats_n++;
-  StatsArgs st{};
-  st.stats_row = c.stats_row; st.loss_sums = e->grads + e->P; st.log_std = Pp(e, T_LOGSTD);
-  st.ent_coef = (float)e->cfg.ent_coef; st.vf_coef = (float)e->cfg.vf_coef;
-  st.inv_bg = 1.0f / (float)((int64_t)e->cur_count * e->cfg.world_size); st.n_act = e->A; st.sde = e->sde;
-  c.records = e->use_norm_records && e->fused.enabled;  // the reduction kernel of this step left the norm records
-  if (!c.records)
+StatsArgs apply_norms(mobrob_ppo_engine* e) {
+  StatsArgs st = stats_args(e);
+  st.stats_row = e->stats + (size_t)next_stats_row(e) * 8;
+  st.inv_bg = 1.0f / (float)((int64_t)e->cur_count * e->cfg.world_size);
+  if (!e->use_norm_records)  // (on: the reduction kernel of this step left the norm records)
     hipLaunchKernelGGL(k_sqnorm_chunks, dim3(e->nchunks), dim3(256), 0, e->stream, e->grads, e->chunks_dev,
                        e->chunk_partial, st);
-  return MOBROB_OK;
+  return st;
 }
 // second half: clip coefficient, Adam, re-pack
-int apply_adam(mobrob_ppo_engine* e, const ApplyCtx& c) {
-  e->adam_step++;
-  const double b1 = e->cfg.adam_beta1, b2 = e->cfg.adam_beta2;
-  const double bc1 = 1.0 - std::pow(b1, (double)e->adam_step);
-  const double bc2 = 1.0 - std::pow(b2, (double)e->adam_step);
+int apply_adam(mobrob_ppo_engine* e, const StatsArgs& st) {
+  const AdamStep step = next_adam_step(e);
   AdamPackArgs a{};
   fill_adam_pack_args(e, a);
-  a.step_size = (float)(e->cfg.learning_rate / bc1);
-  a.bc2_sqrt = (float)std::sqrt(bc2);
-  if (c.records) {
-    StatsArgs st{};
-    st.stats_row = c.stats_row; st.loss_sums = e->grads + e->P; st.log_std = Pp(e, T_LOGSTD);
-    st.ent_coef = (float)e->cfg.ent_coef; st.vf_coef = (float)e->cfg.vf_coef;
-    st.inv_bg = 1.0f / (float)((int64_t)e->cur_count * e->cfg.world_size); st.n_act = e->A;
-    a.partial = e->norm_rec_sum; a.fold_idx = e->fold_idx_dev; a.st = st;
-    for (int i = 0; i <= kMaxTensors; ++i) a.fold_start[i] = e->fold_start[i];
-  }
-  a.stats_row = c.stats_row;
+  a.step_size = step.step_size; a.bc2_sqrt = step.bc2_sqrt;
+  if (e->use_norm_records) a.st = st;   // k_adam_pack logs the step's statistics itself (a fused engine: st.sde is 0)
+  a.stats_row = st.stats_row;
   a.loss_sums_zero = e->fused.enabled ? e->grads + e->P : nullptr;
   hipLaunchKernelGGL(k_adam_pack, dim3(cdiv(e->P, 256)), dim3(256), 0, e->stream, a);
   HIPC(hipGetLastError());
@@ -2487,23 +2528,22 @@ namespace {
 int apply_checked(mobrob_ppo_engine* e, int32_t* stopped) {
   *stopped = 0;
   ProfScope ps(e, MOBROB_K_APPLY);
-  ApplyCtx c{};
-  CHK(apply_norms(e, c));
+  const StatsArgs st = apply_norms(e);
   if (e->target_kl > 0.0) {
     float approx_kl = 0.f;
-    HIPC(hipMemcpyAsync(&approx_kl, c.stats_row + 4, sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipMemcpyAsync(&approx_kl, st.stats_row + 4, sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIPC(hipStreamSynchronize(e->stream));
     if ((double)approx_kl > 1.5 * e->target_kl) {
       *stopped = 1;
       e->grad_pending = false;
       // the row of the dropped step carries its losses (SB3 appends them before the check) but no gradient norm:
       // all-ones bits = NaN, skipped by the averages
-      HIPC(hipMemsetAsync(c.stats_row + 6, 0xFF, sizeof(float), e->stream));
+      HIPC(hipMemsetAsync(st.stats_row + 6, 0xFF, sizeof(float), e->stream));
       if (e->fused.enabled) HIPC(hipMemsetAsync(e->grads + e->P, 0, 8 * sizeof(float), e->stream));  // what k_adam_pack would have re-zeroed
       return MOBROB_OK;
     }
   }
-  return apply_adam(e, c);
+  return apply_adam(e, st);
 }
 }  // namespace
 
@@ -2688,34 +2728,35 @@ int dp_all_reduce(mobrob_ppo_engine* e, void* buf, size_t count, int dtype, mobr
 
 namespace {
 // ---- one co-operative launch per epoch (kernels_epoch64.h) ----
+// The norm records (kernels_fused.h: block_norm_records): the reduction kernel leaves per-block (tensor, sum of squares) records and
+// k_adam_pack folds them with four wave reductions, so no k_sqnorm_chunks launch.  Never under data parallel: the records are norms of
+// the LOCAL gradient, the clip needs those of the summed one.  Never with target_kl (its stop sits between the two).  Asked once per train().
+// (Why wave reductions: at 2x256 the table has 712 records; one serial chain per tensor in every k_adam_pack block cost 12.9 instead of 11.4 ms per iteration.)
+bool norm_records_wanted(const mobrob_ppo_engine* e, bool dp) {
+  return !dp && e->fused.enabled && e->target_kl <= 0.0 && !env_switched_off("MOBROB_NO_NORM_RECORDS");
+}
 // Eligible: single rank, 64-wide fused engine, every minibatch of the epoch small enough for the split-tile gradient kernel
-// (fused64_minibatch_grad's `split`), norm records in use (no target_kl: its stop needs a host read per step), only the dominant
-// kernel bracketed when profiling, grid <= compute units.  *grid_out: workgroups of the launch.
-bool epoch_kernel_eligible(mobrob_ppo_engine* e, bool dp, int* grid_out) {
+// (Grad64Plan::split of the largest one), norm records in use (`records`: norm_records_wanted), only the dominant kernel bracketed
+// when profiling, grid <= compute units.  *launch (meaningful after `true` only): workgroups of the launch, the reduction's fold group.
+struct EpochLaunch { int grid = 0, group = 0; };
+bool epoch_kernel_eligible(const mobrob_ppo_engine* e, bool dp, bool records, EpochLaunch* launch) {
   static_assert(kEpochRedBlocks * 256 >= 10 * 1024 + 200 && (kEpochRedBlocks - 1) * 256 < 10 * 1024 + 200, "kEpochRedBlocks = ceil(s64_size() / 256)");
   const FusedState& f = e->fused;
   if (dp || e->cfg.world_size != 1 || !e->epoch_kernel_on || !f.enabled || f.H != GH || e->epoch_bar == nullptr) return false;
-  if (e->target_kl > 0.0 || !e->use_norm_records || kEpochRedBlocks != cdiv(s64_size(), 256)) return false;
+  if (e->target_kl > 0.0 || !records || kEpochRedBlocks != cdiv(s64_size(), 256)) return false;
   if (e->prof_on && (e->prof_mask & ((1u << MOBROB_K_GRAD_REDUCE) | (1u << MOBROB_K_APPLY))) != 0) return false;   // --phases: the per-step launches are what gets bracketed
-  const int total = e->N * e->T;
-  const int ntiles = cdiv(std::min(e->Bl, total), GR);
-  const int grid = 2 * std::min(f.max_grid / 2, cdiv(ntiles, g_train_waves(e->Dp)));
-  const bool split = ntiles <= e->split64_max_tiles && 2 * ntiles <= f.max_grid && ntiles <= (grid / 2) * g_train_waves(e->Dp);
-  if (!split) return false;
+  const Grad64Plan pl = grad64_plan(e, std::min(e->Bl, e->N * e->T));
+  if (!pl.split) return false;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device_id) != hipSuccess) return false;
-  const int G = std::max(2 * ntiles, 2 * kEpochRedBlocks);
-  if (G > cus) return false;
-  *grid_out = G;
-  return true;
+  launch->grid = std::max(2 * pl.ntiles, 2 * kEpochRedBlocks); launch->group = pl.group;
+  return launch->grid <= cus;
 }
 constexpr size_t kEpochLdsBytes = 84 * 1024;   // more than half of a CU's 160 KB: one workgroup per CU (the residency the hand-offs were validated in)
 
-int launch_epoch_kernel(mobrob_ppo_engine* e, int ep, int G) {
-  FusedState& f = e->fused;
+int launch_epoch_kernel(mobrob_ppo_engine* e, int ep, const EpochLaunch& launch) {
+  if (!e->use_norm_records) return fail(MOBROB_ERR_STATE, "k_epoch64 outside train_loop's norm-record scope");   // the fillers below read the flag
   const int total = e->N * e->T, nmb = e->nmb;
-  // per-step constants of this epoch: Adam's bias corrections in float64 exactly as apply_adam forms them, and the statistics rows the
-  // steps log into (apply_norms' ring)
   const size_t slot_bytes = (size_t)nmb * 12;
   if (!e->epoch_stage) {
     HIPC(hipHostMalloc((void**)&e->epoch_stage, slot_bytes * (size_t)std::max(1, e->cfg.n_epochs), hipHostMallocDefault));
@@ -2727,56 +2768,28 @@ int launch_epoch_kernel(mobrob_ppo_engine* e, int ep, int G) {
   char* slot = e->epoch_stage + slot_bytes * (size_t)(ep % std::max(1, e->cfg.n_epochs));
   float* consts = reinterpret_cast<float*>(slot);
   int* idx = reinterpret_cast<int*>(slot + (size_t)nmb * 8);
-  const double b1 = e->cfg.adam_beta1, b2 = e->cfg.adam_beta2;
+  // per-step constants of this epoch: Adam's bias corrections and the statistics rows, advanced as apply_adam / apply_norms advance them
   for (int mb = 0; mb < nmb; ++mb) {
-    e->adam_step++;
-    consts[2 * mb] = (float)(e->cfg.learning_rate / (1.0 - std::pow(b1, (double)e->adam_step)));
-    consts[2 * mb + 1] = (float)std::sqrt(1.0 - std::pow(b2, (double)e->adam_step));
-    if (e->stats_n >= e->stats_cap) e->stats_n = 0;
-    idx[mb] = e->stats_n++;
+    const AdamStep step = next_adam_step(e);
+    consts[2 * mb] = step.step_size; consts[2 * mb + 1] = step.bc2_sqrt;
+    idx[mb] = next_stats_row(e);
   }
   HIPC(hipMemcpyAsync(e->epoch_consts, consts, (size_t)nmb * 8, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(e->epoch_idx, idx, (size_t)nmb * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipEventRecord(e->epoch_ev, e->stream));
   HIPC(hipMemsetAsync(e->epoch_bar, 0, 1024 * sizeof(unsigned), e->stream));
-
-  Epoch64Args ea{};
-  {  // gradient phase (fused64_minibatch_grad)
-    Fused64TrainArgs& a = ea.tr;
-    a.net[0] = f.net[0]; a.net[1] = f.net[1];
-    a.obs = e->obs; a.actions = e->actions; a.A = e->A; a.old_logp = e->logp; a.adv = e->adv; a.ret = e->ret;
-    a.log_std = e->params + e->offs[T_LOGSTD];
-    a.normalize = e->cfg.normalize_advantage;
-    a.clip = (float)e->cfg.clip_range; a.vf_coef = (float)e->cfg.vf_coef; a.ent_coef = (float)e->cfg.ent_coef;
-    a.clip_vf = (float)e->clip_vf; a.old_values = e->values;
-    a.slabs = f.slabs; a.sums = e->grads + e->P; a.stamps = f.stamps;
-    a.wpack[0] = reinterpret_cast<const float*>(f.net[0].W1f);
-    a.wpack[1] = reinterpret_cast<const float*>(f.net[1].W1f);
-  }
-  {  // reduction phase
-    Slab64ReduceArgs& r = ea.rd;
-    r.slabs = f.slabs; r.group = g_train_waves(e->Dp); r.grads = e->grads; r.P = e->P;
-    for (int i = 0; i < 14; ++i) r.offs[i] = e->offs[i];
-    r.D = e->D; r.A = e->A; r.ent_coef = (float)e->cfg.ent_coef;
-    r.sums = e->grads + e->P;
-    r.rec_sum = e->norm_rec_sum; r.rec_t = e->norm_rec_t;
-  }
-  {  // clip + Adam + packs (apply_adam with the norm records)
-    AdamPackArgs& a = ea.ad;
-    fill_adam_pack_args(e, a);
-    StatsArgs st{};
-    st.loss_sums = e->grads + e->P; st.log_std = Pp(e, T_LOGSTD);
-    st.ent_coef = (float)e->cfg.ent_coef; st.vf_coef = (float)e->cfg.vf_coef; st.n_act = e->A;
-    a.partial = e->norm_rec_sum; a.fold_idx = e->fold_idx_dev; a.st = st;
-    for (int i = 0; i <= kMaxTensors; ++i) a.fold_start[i] = e->fold_start[i];
-    a.loss_sums_zero = e->grads + e->P;
-  }
+  Epoch64Args ea{};   // the three phases take the arguments of the three launches; what varies per minibatch is derived in the kernel
+  ea.tr = train64_args(e);
+  ea.rd = slab64_reduce_args(e);
+  ea.rd.group = launch.group;   // (rec_sum is set: eligibility needs the norm records, and train_loop has switched them on)
+  fill_adam_pack_args(e, ea.ad);
+  ea.ad.st = stats_args(e);
+  ea.ad.loss_sums_zero = e->grads + e->P;
   ea.rows = e->rows; ea.advstat = e->advstat;
   ea.total = total; ea.bl = e->Bl; ea.nmb = nmb; ea.world = e->cfg.world_size;
   ea.step_consts = e->epoch_consts; ea.stats_idx = e->epoch_idx; ea.stats = e->stats;
   ea.barrier = e->epoch_bar; ea.error_host = e->epoch_err_host;
-  const double timeout_s = env_double("MOBROB_EPOCH_TIMEOUT_S", 10.0);
-  ea.timeout_ticks = (long long)(timeout_s * 1e8);
+  ea.timeout_ticks = (long long)(env_double("MOBROB_EPOCH_TIMEOUT_S", 10.0) * 1e8);
   void* kargs[1] = {&ea};
   {
     ProfScope ps(e, MOBROB_K_TRAIN_GRAD);   // the whole epoch: gradient, reduction and Adam phases are one launch
@@ -2784,9 +2797,9 @@ int launch_epoch_kernel(mobrob_ppo_engine* e, int ep, int G) {
     FUSED_DISPATCH_DP(e->Dp, FUSED64_DISPATCH_NJ(e->A, {
       const void* fn = reinterpret_cast<const void*>(k_epoch64<DPc, NJc>);
       le = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEpochLdsBytes);
-      if (le == hipSuccess) le = hipLaunchCooperativeKernel(fn, dim3(G), dim3(256), kargs, (unsigned)kEpochLdsBytes, e->stream);
+      if (le == hipSuccess) le = hipLaunchCooperativeKernel(fn, dim3(launch.grid), dim3(256), kargs, (unsigned)kEpochLdsBytes, e->stream);
     }));
-    if (le != hipSuccess) return fail(MOBROB_ERR_HIP, "k_epoch64 launch (%d workgroups): %s", G, hipGetErrorString(le));
+    if (le != hipSuccess) return fail(MOBROB_ERR_HIP, "k_epoch64 launch (%d workgroups): %s", launch.grid, hipGetErrorString(le));
   }
   e->cur_count = std::min(e->Bl, total - (nmb - 1) * e->Bl);
   e->grad_pending = false;
@@ -2797,23 +2810,21 @@ int launch_epoch_kernel(mobrob_ppo_engine* e, int ep, int G) {
 // PPO.train() [SB3 ppo/ppo.py], single rank (dp == false) or data parallel (dp == true: the advantage statistics are
 // all-reduced once per epoch, the gradient TOGETHER WITH the eight loss sums behind it once per optimizer step, so the
 // logged statistics and the target_kl decision are those of the union minibatch on every rank alike).
-int train_loop(mobrob_ppo_engine* e, const int64_t* perms, bool dp, mobrob_allreduce_fn fn, void* ctx) {
+int train_loop(mobrob_ppo_engine* e, const int64_t* perms, bool dp, bool records, mobrob_allreduce_fn fn, void* ctx) {
+  if (!dp && e->cfg.world_size != 1)
+    return fail(MOBROB_ERR_STATE, "mobrob_ppo_train is the single-rank loop; data-parallel ranks call mobrob_ppo_train_dp "
+                                  "(or drive epoch_begin/minibatch_grad/[all-reduce]/minibatch_apply)");
   const size_t total = (size_t)e->N * e->T;
   e->stats_n = 0;
   const bool kl = e->target_kl > 0.0;
   e->last_epochs_started = 0; e->last_stopped_early = 0; e->last_steps_applied = 0;
-  // The reduction kernel leaves per-block (tensor, sum of squares) records and k_adam_pack folds them: no
-  // k_sqnorm_chunks launch.  (Round 2 had this for 64-wide nets only: at 2x256 the table has 712 records and the fold
-  // was one serial chain per tensor in every k_adam_pack block, 12.9 instead of 11.4 ms per iteration; the fold is now
-  // four wave reductions.)  Never under data parallel: the records are norms of the LOCAL gradient, the clip needs
-  // those of the summed one.
-  struct RecordsOn {  // nothing can touch the gradient between reduction and clip inside this loop
+  struct RecordsOn {  // `records` = norm_records_wanted: nothing can touch the gradient between reduction and clip inside this loop
     mobrob_ppo_engine* e;
-    RecordsOn(mobrob_ppo_engine* e_, bool dp_) : e(e_) { e->use_norm_records = !dp_ && e->fused.enabled && e->target_kl <= 0.0 && getenv("MOBROB_NO_NORM_RECORDS") == nullptr; }
+    RecordsOn(mobrob_ppo_engine* e_, bool on) : e(e_) { e->use_norm_records = on; }
     ~RecordsOn() { e->use_norm_records = false; }
-  } records_on(e, dp);
-  int epoch_grid = 0;
-  const bool epoch_kernel = epoch_kernel_eligible(e, dp, &epoch_grid);
+  } records_on(e, records);
+  EpochLaunch epoch_launch;
+  const bool epoch_kernel = epoch_kernel_eligible(e, dp, records, &epoch_launch);
   e->last_update_mode = epoch_kernel ? 1 : 0;
   for (int ep = 0; ep < e->cfg.n_epochs; ++ep) {
     CHK(mobrob_ppo_epoch_begin(e, perms ? perms + (size_t)ep * total : nullptr));
@@ -2822,7 +2833,7 @@ int train_loop(mobrob_ppo_engine* e, const int64_t* perms, bool dp, mobrob_allre
     e->last_epochs_started = ep + 1;
     if (ep == e->cfg.n_epochs - 1 || kl) e->stats_n = 0;  // the rows kept are those of the last epoch that ran
     if (epoch_kernel) {   // all optimizer steps of the epoch in ONE co-operative launch (kernels_epoch64.h): same arithmetic, same bits
-      CHK(launch_epoch_kernel(e, ep, epoch_grid));
+      CHK(launch_epoch_kernel(e, ep, epoch_launch));
       continue;
     }
     for (int mb = 0; mb < e->nmb && !e->last_stopped_early; ++mb) {
@@ -2843,16 +2854,22 @@ int train_loop(mobrob_ppo_engine* e, const int64_t* perms, bool dp, mobrob_allre
   e->epoch_open = false;
   return MOBROB_OK;
 }
+// parameters and both Adam moments into epoch_snap ([3][P]), or back (`restore`)
+int copy_optimizer_state(mobrob_ppo_engine* e, bool restore) {
+  float* const live[3] = {e->params, e->m, e->v};
+  for (int i = 0; i < 3; ++i) {
+    float* const snap = e->epoch_snap + (size_t)i * e->P;
+    HIPC(hipMemcpyAsync(restore ? live[i] : snap, restore ? snap : live[i], (size_t)e->P * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  }
+  return MOBROB_OK;
+}
 }  // namespace
 
 extern "C" {
 
 int mobrob_ppo_train_enqueue(mobrob_ppo_engine_t* e, const int64_t* perms) {
   if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
-  if (e->cfg.world_size != 1)
-    return fail(MOBROB_ERR_STATE, "mobrob_ppo_train is the single-rank loop; data-parallel ranks call mobrob_ppo_train_dp "
-                                  "(or drive epoch_begin/minibatch_grad/[all-reduce]/minibatch_apply)");
-  return train_loop(e, perms, false, nullptr, nullptr);
+  return train_loop(e, perms, false, norm_records_wanted(e, false), nullptr, nullptr);
 }
 
 int mobrob_ppo_comm_unique_id(uint8_t* out128) {
@@ -2972,7 +2989,7 @@ int mobrob_ppo_train_dp(mobrob_ppo_engine_t* e, const int64_t* perms, mobrob_all
   if (!e) return fail(MOBROB_ERR_INVALID, "null engine");
   if (!fn && !e->comm && !e->oneshot.ready)
     return fail(MOBROB_ERR_STATE, "train_dp: no communicator (mobrob_ppo_comm_init), no one-shot exchange (mobrob_ppo_oneshot_open) and no all-reduce callback");
-  CHK(train_loop(e, perms, true, fn, ctx));
+  CHK(train_loop(e, perms, true, norm_records_wanted(e, true), fn, ctx));
   if (!fn && e->oneshot.ready) {
     // A one-shot message whose peer never published leaves this rank's gradient LOCAL: such a step must not pass as a data-parallel
     // one.  The update is awaited here and the error word turned into a failure of this call (the caller ends the job).
@@ -3080,41 +3097,24 @@ int mobrob_ppo_train(mobrob_ppo_engine_t* e, const int64_t* perms, mobrob_ppo_tr
   // the state is restored and the whole update runs again as three launches per step -- the same bits, never a failed or half-applied
   // train().  The engine then keeps the three launches (mobrob_ppo_update_mode reports it).  (mobrob_ppo_train_enqueue has no such
   // retry: it returns before the outcome is known; there the abort fails the next synchronising call.)
-  int grid_unused = 0;
-  struct RecordsProbe {   // eligibility as train_loop will see it (it switches use_norm_records on for the loop's duration)
-    mobrob_ppo_engine* e; bool old;
-    explicit RecordsProbe(mobrob_ppo_engine* e_) : e(e_), old(e_->use_norm_records) { e->use_norm_records = e->fused.enabled && e->target_kl <= 0.0 && getenv("MOBROB_NO_NORM_RECORDS") == nullptr; }
-    ~RecordsProbe() { e->use_norm_records = old; }
-  };
-  bool snap = false;
-  {
-    RecordsProbe rp(e);
-    snap = e->cfg.world_size == 1 && e->epoch_snap != nullptr && epoch_kernel_eligible(e, false, &grid_unused);
-  }
-  const int64_t adam_step0 = e->adam_step;
-  const uint64_t perm_counter0 = e->perm_counter;
-  if (snap) {
-    const size_t pb = (size_t)e->P * sizeof(float);
-    HIPC(hipMemcpyAsync(e->epoch_snap, e->params, pb, hipMemcpyDeviceToDevice, e->stream));
-    HIPC(hipMemcpyAsync(e->epoch_snap + e->P, e->m, pb, hipMemcpyDeviceToDevice, e->stream));
-    HIPC(hipMemcpyAsync(e->epoch_snap + 2 * (size_t)e->P, e->v, pb, hipMemcpyDeviceToDevice, e->stream));
-  }
-  CHK(mobrob_ppo_train_enqueue(e, perms));
+  const bool records = norm_records_wanted(e, false);
+  EpochLaunch launch_unused;
+  const bool snap = e->cfg.world_size == 1 && e->epoch_snap != nullptr && epoch_kernel_eligible(e, false, records, &launch_unused);
+  const int64_t adam_step0 = e->adam_step; const uint64_t perm_counter0 = e->perm_counter;
+  if (snap) CHK(copy_optimizer_state(e, false));
+  CHK(train_loop(e, perms, false, records, nullptr, nullptr));
   if (snap && (e->last_update_mode & 1)) {
     HIPC(hipStreamSynchronize(e->stream));
     if (e->epoch_err_host && *(volatile int*)e->epoch_err_host != 0) {
       *(volatile int*)e->epoch_err_host = 0;
       fprintf(stderr, "[mobrob_ppo] the co-operative epoch kernel gave up at a grid barrier (workgroups not resident together: other spinning tenants "
                       "on the device?); the update is re-run as three launches per optimizer step and this engine keeps that form\n");
-      const size_t pb = (size_t)e->P * sizeof(float);
-      HIPC(hipMemcpyAsync(e->params, e->epoch_snap, pb, hipMemcpyDeviceToDevice, e->stream));
-      HIPC(hipMemcpyAsync(e->m, e->epoch_snap + e->P, pb, hipMemcpyDeviceToDevice, e->stream));
-      HIPC(hipMemcpyAsync(e->v, e->epoch_snap + 2 * (size_t)e->P, pb, hipMemcpyDeviceToDevice, e->stream));
+      CHK(copy_optimizer_state(e, true));
       HIPC(hipMemsetAsync(e->grads + e->P, 0, 8 * sizeof(float), e->stream));
       repack(e);   // every weight pack from the restored parameters
       e->adam_step = adam_step0; e->perm_counter = perm_counter0;   // (the same permutations again; the parity of the max-|adv| words simply goes on)
       e->epoch_kernel_on = false;
-      CHK(mobrob_ppo_train_enqueue(e, perms));
+      CHK(train_loop(e, perms, false, records, nullptr, nullptr));
     }
   }
   if (st) {

@@ -64,51 +64,50 @@ inline void split64_launch_train(FusedState& f, Fused64TrainArgs& a, int ntiles,
   FUSED_DISPATCH_DP(f.Dp, FUSED64_DISPATCH_NJ(f.A, hipLaunchKernelGGL((k_split64_train<DPc, NJc>), dim3(2 * ntiles), dim3(256), split64_lds_bytes(f.Dp), st, a)));
 }
 // persistent two-wave workgroups, four per CU: large minibatches (kernels_pair64.h)
-inline void pair64_launch_train(FusedState& f, Fused64TrainArgs& a, int nseq, hipStream_t st) {
-  const int nbseq = (nseq + 1) / 2;  // two pairs (tile sequences) per workgroup
-  const int grid = 16 * ((nbseq + 7) / 8);
+inline void pair64_launch_train(FusedState& f, Fused64TrainArgs& a, int nseq, int nbseq, hipStream_t st) {
+  const int grid = 16 * ((nbseq + 7) / 8);  // nbseq workgroups per network (two tile sequences each), in groups of 8 + 8
   FUSED_DISPATCH_DP(f.Dp, FUSED64_DISPATCH_NJ(f.A, hipLaunchKernelGGL((k_pair64_train<DPc, NJc>), dim3(grid), dim3(256), pair64_lds_bytes(f.Dp), st, a, nseq)));
 }
-inline hipError_t fused_set_lds_attr(FusedState& f) {
-  hipError_t e = hipSuccess;
-  if (f.H == 64) {
-    FUSED_DISPATCH_DP(f.Dp, {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fused64_train<DPc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fused64_act<DPc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_act_bytes);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout64_persistent<DPc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rollout64_lds_bytes(f.Dp));
-      if (e == hipSuccess)
-        FUSED64_DISPATCH_NJ(f.A, e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_pair64_train<DPc, NJc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair64_lds_bytes(f.Dp)));
-    });
-  } else {
-    FUSED_DISPATCH_DP(f.Dp, {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fused_train<DPc, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fused_train<DPc, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes);
-      if (e == hipSuccess && f.train_x3)
-        FUSED_DISPATCH_DP_X3(f.Dp, e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fused_train<DPc, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes));
-      if (e == hipSuccess && f.train_chain)
-        FUSED_DISPATCH_DP_X3(f.Dp, e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain_train<DPc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_chain_bytes));
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fused_act<DPc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_act_bytes);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout_persistent<DPc, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rollout_lds_bytes(f.Dp));
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout_persistent<DPc, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rollout_lds_bytes(f.Dp));
-      if (!kRolloutStationary) {
-        if (e == hipSuccess)
-          e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout_persistent<DPc, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rollout_lds_bytes(f.Dp, true));
-        if (e == hipSuccess)
-          e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout_persistent<DPc, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rollout_lds_bytes(f.Dp, true));
-        if (e == hipSuccess)
-          e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout_persistent<DPc, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rollout_lds_bytes(f.Dp, true));
-      }
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_value_batch<DPc>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes);
-    });
+// Dynamic LDS above the default limit has to be announced per kernel.  One entry per kernel an engine of this shape can launch
+// (fn == nullptr: not with this engine's switches); set in order, the first error is kept.
+struct LdsAttr { const void* fn; size_t bytes; };
+template <class K>
+inline LdsAttr lds_attr(K* kernel, size_t bytes, bool on = true) { return {on ? reinterpret_cast<const void*>(kernel) : nullptr, bytes}; }
+template <size_t N>
+inline hipError_t set_lds_attrs(const LdsAttr (&attrs)[N]) {
+  for (const LdsAttr& a : attrs) {
+    const hipError_t e = a.fn ? hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.bytes) : hipSuccess;
+    if (e != hipSuccess) return e;
   }
-  return e;
+  return hipSuccess;
+}
+template <int DPc>
+inline hipError_t fused64_set_lds_attr(FusedState& f) {
+  const void* pair = nullptr;
+  FUSED64_DISPATCH_NJ(f.A, pair = reinterpret_cast<const void*>(k_pair64_train<DPc, NJc>));
+  const LdsAttr attrs[] = {lds_attr(k_fused64_train<DPc>, f.lds_bytes), lds_attr(k_fused64_act<DPc>, f.lds_act_bytes),
+                           lds_attr(k_rollout64_persistent<DPc>, rollout64_lds_bytes(f.Dp)), {pair, pair64_lds_bytes(f.Dp)}};
+  return set_lds_attrs(attrs);
+}
+template <int DPc>
+inline hipError_t fused256_set_lds_attr(FusedState& f) {
+  constexpr int DPx = DPc == 48 ? 64 : DPc;   // FUSED_DISPATCH_DP_X3: no x3 / chain kernel at 48 columns (train_x3 is off there)
+  const size_t ro = rollout_lds_bytes(f.Dp), ro_s8 = rollout_lds_bytes(f.Dp, true);
+  const LdsAttr attrs[] = {lds_attr(k_fused_train<DPc, false>, f.lds_bytes), lds_attr(k_fused_train<DPc, true>, f.lds_bytes),
+                           lds_attr(k_fused_train<DPx, true, true>, f.lds_bytes, f.train_x3),
+                           lds_attr(k_chain_train<DPx>, f.lds_chain_bytes, f.train_chain),
+                           lds_attr(k_fused_act<DPc>, f.lds_act_bytes),
+                           lds_attr(k_rollout_persistent<DPc, 1>, ro), lds_attr(k_rollout_persistent<DPc, 2>, ro),
+                           lds_attr(k_rollout_persistent<DPc, 1, true>, ro_s8, !kRolloutStationary),
+                           lds_attr(k_rollout_persistent<DPc, 2, true>, ro_s8, !kRolloutStationary),
+                           lds_attr(k_rollout_persistent<DPc, 3, true>, ro_s8, !kRolloutStationary),
+                           lds_attr(k_value_batch<DPc>, f.lds_bytes)};
+  return set_lds_attrs(attrs);
+}
+inline hipError_t fused_set_lds_attr(FusedState& f) {
+  if (f.H == 64) { FUSED_DISPATCH_DP(f.Dp, return fused64_set_lds_attr<DPc>(f)); }
+  else { FUSED_DISPATCH_DP(f.Dp, return fused256_set_lds_attr<DPc>(f)); }
+  return hipSuccess;
 }
 
 }  // namespace mobrob

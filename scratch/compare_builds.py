@@ -1,5 +1,10 @@
 """Bit-level comparison of two builds of libmobrob_ppo.so on the same inputs (refactoring check).
-  training leg: three PPO iterations on three shapes, then parameters / Adam moments / step statistics must be identical.
+  training leg: three PPO iterations on three shapes, then parameters / Adam moments / step statistics must be identical (the
+    2x48 shape runs the generic chain, whose float atomics differ between two runs of one build: reported, not judged), and
+    train_legs: every host path of the update -- 2x256 chain kernel (two Dp), MOBROB_NO_CHAIN, MOBROB_NO_X3, Dp 48, A > 16; 2x64
+    epoch kernel, three launches, block kernel, pair kernel with the narrow and the wide reduce; on both widths target_kl (early
+    stop asserted), clip_range_vf, normalize_advantage off, MOBROB_NO_NORM_RECORDS, caller permutations, a short last minibatch
+    and the step-wise driver -- hashing parameters, moments, adam_step, statistics rows, update_mode and last_train_info.
   evaluation and follow legs: every array evaluate_goal_env / follow_waypoints return (reward sums, steps, episode records,
     arrivals, final distance, path, trace; raw bytes, so NaN payloads count) for one robot per DP instantiation of the tile kernel
     (point 16, car 32, turtlebot3 48, doggo 64, and drone: 16 with the two-block head) on both paths (default and
@@ -195,6 +200,86 @@ def rollout_legs(out, s8_off):
             e.close()
 
 
+def train_legs(out):
+    """Every host path of the optimizer update.  Per case: two collect_synthetic + train iterations of three epochs, then the raw
+    bytes of parameters, both Adam moments, adam_step, the step-statistics rows, update_mode and last_train_info.  Environment
+    switches are set before the engine is created and removed afterwards (they are read at creation or once per train())."""
+    import ctypes as C
+    import hashlib
+    import numpy as np
+    from mobrob_amd._lib import check
+    from mobrob_amd.engine import PPOEngine
+    from mobrob_amd.rl_control.init import orthogonal_policy_init
+    W256 = dict(D=58, A=12, H=256, N=128, T=32, B=1024)   # chain kernel, Dp 64
+    W64 = dict(D=14, A=2, H=64, N=64, T=32, B=512)        # split kernel (16 tiles), three launches per step or k_epoch64
+    REF = dict(D=58, A=12, H=64, N=16, T=125, B=100)      # reference-YAML-like: batch 100 = four tiles -> k_epoch64
+    cases = [("256 chain Dp 64", W256, dict(x3=7)),
+             ("256 chain Dp 32", dict(W256, D=26, A=2), dict(x3=7)),
+             ("256 MOBROB_NO_CHAIN", W256, dict(env={"MOBROB_NO_CHAIN": "1"}, x3=3)),
+             ("256 MOBROB_NO_X3", W256, dict(env={"MOBROB_NO_X3": "1"}, x3=0)),
+             ("256 Dp 48", dict(W256, D=40, A=2), dict(x3=1)),
+             ("256 A 20", dict(W256, A=20), dict(x3=1)),
+             ("64 epoch kernel", REF, dict(mode=1)),
+             ("64 epoch_kernel=0", REF, dict(hyper=dict(epoch_kernel=0), mode=0)),
+             ("64 block kernel", dict(W64, N=256, T=64, B=2048), dict(env={"MOBROB_SPLIT64_MAX_TILES": "0"}, mode=0, kernel="block")),
+             ("64 pair, narrow reduce", dict(W64, N=512, T=32, B=4096), dict(mode=0, kernel="pair")),
+             ("64 pair, wide reduce (256 slabs per network)", dict(W64, N=1024, T=32, B=16384), dict(mode=0, kernel="wide"))]
+    for w, base in (("256", W256), ("64", W64), ("64 ref", REF)):
+        cases += [(f"{w} target_kl early stop", base, dict(hyper=dict(target_kl=1e-5), stop=True)),
+                  (f"{w} clip_range_vf", base, dict(hyper=dict(clip_range_vf=0.2))),
+                  (f"{w} normalize_advantage off", base, dict(kw=dict(normalize_advantage=False))),
+                  (f"{w} MOBROB_NO_NORM_RECORDS", base, dict(env={"MOBROB_NO_NORM_RECORDS": "1"}, mode=0)),
+                  (f"{w} caller permutations", base, dict(perms=True)),
+                  (f"{w} short last minibatch", dict(base, B=base["B"] * 3 // 5), {}),
+                  (f"{w} step-wise driver", base, dict(stepwise=True))]
+    for name, s, o in cases:
+        if "kernel" in o:   # the engine's rule (grad64_plan; defaults: split up to 64 tiles, pair from 65, 4 pairs x 256 CUs / 2 sequences)
+            ntiles = -(-s["B"] // 32)
+            nbseq = (min(ntiles, 512) + 1) // 2
+            split = "MOBROB_SPLIT64_MAX_TILES" not in o.get("env", {}) and ntiles <= 64
+            want = "split" if split else "block" if ntiles < 65 else "wide" if nbseq > 128 else "pair"
+            assert want == o["kernel"], (name, want)
+        env_vars = o.get("env", {})
+        os.environ.update(env_vars)
+        try:
+            e = PPOEngine(obs_dim=s["D"], act_dim=s["A"], n_envs=s["N"], n_steps=s["T"], batch_size=s["B"], n_epochs=3,
+                          pi=(s["H"], s["H"]), vf=(s["H"], s["H"]), ent_coef=0.01, seed=5, **o.get("kw", {}))
+            e.set_params(orthogonal_policy_init(s["D"], s["A"], (s["H"], s["H"]), (s["H"], s["H"]), 0))
+            e.set_hyper(**o.get("hyper", {}))
+            if "x3" in o:
+                assert e.x3_mode() == o["x3"], (name, e.x3_mode())
+            total, rng = s["N"] * s["T"], np.random.default_rng(11)
+            assert (total % s["B"] != 0) == ("short" in name)
+            h = hashlib.sha256()
+            for _ in range(2):
+                e.collect_synthetic(p_term=0.02, time_limit=40)
+                if o.get("stepwise"):
+                    for _ep in range(3):
+                        e.epoch_begin()
+                        for mb in range(e.n_minibatches):
+                            e.minibatch_grad(mb)
+                            e.minibatch_apply()
+                else:
+                    perms = np.stack([rng.permutation(total) for _ in range(3)]).astype(np.int64) if o.get("perms") else None
+                    check(e.lib.mobrob_ppo_train(e._h, perms.ctypes.data_as(C.POINTER(C.c_int64)) if perms is not None else None, None))
+                h.update(e.fetch_step_stats().tobytes())   # (train() with a statistics struct would have consumed the rows)
+                if "mode" in o:
+                    assert e.update_mode() == o["mode"], (name, e.update_mode())
+            info = e.last_train_info()
+            if o.get("stop"):
+                assert info[1], (name, info)
+            m, v, step = e.get_optimizer_state()
+            h.update(e.get_flat_params().tobytes())
+            for k in sorted(m):
+                h.update(m[k].tobytes()); h.update(v[k].tobytes())
+            h.update(repr((step, e.update_mode(), info)).encode())
+            out[f"train | {name}"] = [h.hexdigest()[:16], step, e.update_mode(), list(info)]
+            e.close()
+        finally:
+            for k in env_vars:
+                os.environ.pop(k, None)
+
+
 if len(sys.argv) >= 3 and sys.argv[1] == "--run-s8off":
     from mobrob_amd import _lib
     _lib.LIB_PATH = sys.argv[2]
@@ -220,6 +305,7 @@ elif len(sys.argv) == 3 and sys.argv[1] == "--run":
             h.update(m[k].tobytes()); h.update(v[k].tobytes())
         out[f"{D}x{A}x{H}"] = [h.hexdigest()[:16], step, repr(st["grad_norm"]), repr(st["loss"])]
         e.close()
+    train_legs(out)
     rollout_legs(out, False)
     eval_follow_legs(out)
     print(json.dumps(out))
@@ -233,8 +319,10 @@ else:
                 sys.exit(f"{p} ({leg}): exit status {c.returncode}\n{c.stderr[-4000:]}")
             r.update(json.loads(c.stdout.strip().splitlines()[-1]))
         res.append(r)
+    # the generic chain (float atomics in its minibatch sums) differs between two runs of ONE build: reported, not judged
+    unjudged = ("26x2x48",)
     for k in res[0]:
-        print(f"{k:<86}", "IDENTICAL" if res[0][k] == res[1][k] else "DIFFERENT", res[0][k], res[1][k])
-    bad = [k for k in res[0] if res[0][k] != res[1][k]]
-    print(f"{len(res[0]) - len(bad)} of {len(res[0])} identical")
+        print(f"{k:<86}", "IDENTICAL" if res[0][k] == res[1][k] else "DIFFERENT", res[0][k], res[1][k], "(not judged)" if k in unjudged else "")
+    bad = [k for k in res[0] if res[0][k] != res[1][k] and k not in unjudged]
+    print(f"{len(res[0]) - len(unjudged) - len(bad)} of {len(res[0]) - len(unjudged)} judged rows identical")
     sys.exit(1 if bad else 0)
