@@ -547,6 +547,53 @@ int mobrob_ppo_follow_waypoints_hazards(mobrob_ppo_engine_t* e, const mobrob_goa
                                         int32_t* arrival /* [n][K] */, double* robot_out /* [n][4] */,
                                         double* hazard_out /* [n][4] */, float* path_out /* or NULL */, float* trace_out /* or NULL */);
 
+/* ---- resumable waypoint following: a RUN of calls with carried state, leg budgets and replanning between calls ----------------
+ * A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue (the loops around
+ * the tracker in the reference's planners; the tracker itself is examples/control.py:36-46, EnvWrapper.set_goal / reached
+ * wrapper.py:203-214).  mobrob_ppo_follow_waypoints_resume is mobrob_ppo_follow_waypoints (with hazards when hz is not NULL) as
+ * ONE CALL OF A RUN: a sequence of calls over the same n_robots with the same seed, call c covering the global steps
+ * step0 .. step0 + max_steps - 1 (the host loop of mobrob_amd/waypoints.py states the same thing on EnvWrapper).
+ *   streams   every Philox draw (observation noise, action noise) is keyed by (robot, GLOBAL step); arrival steps and a first
+ *             violation step are global and 1-based.
+ *   carried   per robot, read at entry and continued (never re-summed), written at exit:
+ *               resume->state [n][6] floats: position, velocity (unused components zero);
+ *               robot_out [n][0..2]: float64 reward sum, steps run, waypoints reached = the index k of the waypoint in force
+ *               ([3], the final distance, is output only);  arrival [n][K];  resume->leg_used [n]: steps spent on the waypoint in
+ *               force;  with hazards, hazard_out [n][4].
+ *   goal      at entry the goal in force is waypoints[n][k] (the last waypoint for a finished robot).
+ *   budget    leg_steps = 0: none.  Otherwise, after a step: on arrival (arrival[k] = g + 1, k += 1, next waypoint) leg_used = 0,
+ *             else leg_used += 1.  A robot is active iff k < n_waypoints[n] and (leg_steps == 0 or leg_used < leg_steps).
+ *             Without a budget nothing is counted (leg_used stays 0), and leg_used must lie in 0 .. leg_steps at entry: a run
+ *             that used a budget goes on without one (leg_steps = 0) only after the caller has zeroed leg_used.
+ *   status    resume->status [n], written at exit: 0 going (the call's step cap ended it), 1 finished, 2 stalled (budget spent),
+ *             3 no waypoints.
+ *   replan    between calls the caller may replace any robot's waypoint row and count; it then sets that robot's reached count to
+ *             0, its arrival row to -1 and leg_used to 0.  Everything else is carried.
+ *   local     path_out and trace_out are the call's own: path record 0 is the position at entry, trace rows are indexed by the
+ *             call's step, the waypoint flag holds k as carried; the rows of idle (finished, stalled) robots are zero.
+ * Two invariants: a run started with step0 = 0, state = (start, 0), zeroed robot_out, arrival = -1, leg_used = 0, leg_steps = 0
+ * (and hazard_out = 0, 0, -1, NaN) returns the bits of mobrob_ppo_follow_waypoints(_hazards) in every output; and one call of T
+ * steps and any chain of calls of T1 + T2 + ... = T steps handing the carried arrays on unchanged end with bit-identical carried
+ * arrays on the same kernel path (k_goal64_tile<DP, ResumeFollowTask> / HazardTask<ResumeFollowTask>, or the per-step kernels).
+ * MOBROB_ERR_INVALID before any launch or copy (the in/out arrays stay as given), besides the counterpart's checks, for: a NULL
+ * resume / state / leg_used / status, hazard_out NULL unless hz is, step0 < 0 or step0 + max_steps beyond int32, leg_steps < 0, a
+ * non-finite state, leg_used outside 0 .. leg_steps, a reached count outside 0 .. n_waypoints[n], a non-finite carried reward
+ * sum, carried steps outside 0 .. INT32_MAX - max_steps, a carried hazard record no call returns.  The counts that travel as
+ * float64 (steps run, reached count, violation steps, first violation) must be whole numbers: a fraction is refused. */
+typedef struct mobrob_follow_resume {
+  int32_t step0;       /* global step of this call's step 0, >= 0                 */
+  int32_t leg_steps;   /* step budget per waypoint, 0 = none                      */
+  float* state;        /* [n][6] position, velocity: in / out                     */
+  int32_t* leg_used;   /* [n] steps spent on the waypoint in force: in / out      */
+  int32_t* status;     /* [n] out: 0 going, 1 finished, 2 stalled, 3 no waypoints */
+} mobrob_follow_resume_t;
+int mobrob_ppo_follow_waypoints_resume(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                       const mobrob_hazards_t* hz /* or NULL */, const mobrob_follow_resume_t* resume,
+                                       const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                       int32_t* arrival /* [n][K] in / out */, double* robot_out /* [n][4] in / out */,
+                                       double* hazard_out /* [n][4] in / out, NULL iff hz is */, float* path_out /* or NULL */,
+                                       float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

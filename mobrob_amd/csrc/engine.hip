@@ -3448,11 +3448,43 @@ int mobrob_ppo_evaluate_goal_env_hazards(mobrob_ppo_engine_t* e, const mobrob_go
 }
 
 // ---- waypoint following: the policy as a tracker of given goal sequences ------------------------------------------------
-// follow, with hazards when `hio` is not null (mobrob_ppo_follow_waypoints_hazards)
+// what a call of a resumable run carries in besides arrival / robot_out / hazard_out: refused before any launch or copy
+static int follow_resume_check(const mobrob_follow_resume_t* rs, const mobrob_follow_spec_t* spec, const std::vector<int32_t>& nw,
+                               const double* robot_out, const double* hazard_out) {
+  const int N = spec->n_robots;
+  if (!rs->state || !rs->leg_used || !rs->status) return fail(MOBROB_ERR_INVALID, "follow: resume: null argument");
+  if (rs->step0 < 0 || (int64_t)rs->step0 + spec->max_steps > INT_MAX)
+    return fail(MOBROB_ERR_INVALID, "follow: resume: step0 must be >= 0 and step0 + max_steps fit an int32");
+  if (rs->leg_steps < 0) return fail(MOBROB_ERR_INVALID, "follow: resume: leg_steps must be >= 0 (0: no budget)");
+  for (int i = 0; i < N; ++i) {
+    for (int j = 0; j < 6; ++j)
+      if (!std::isfinite(rs->state[(size_t)i * 6 + j])) return fail(MOBROB_ERR_INVALID, "follow: resume: state of robot %d is not finite", i);
+    if (rs->leg_used[i] < 0 || rs->leg_used[i] > rs->leg_steps)
+      return fail(MOBROB_ERR_INVALID, "follow: resume: leg_used[%d] = %d outside 0 .. %d", i, rs->leg_used[i], rs->leg_steps);
+    const double* o = robot_out + (size_t)i * 4;
+    if (!std::isfinite(o[0])) return fail(MOBROB_ERR_INVALID, "follow: resume: reward sum of robot %d is not finite", i);
+    // the counts travel as float64 and are read back as int32: a value that is not a whole number is refused, not truncated
+    if (!(o[1] >= 0.0 && o[1] <= (double)(INT_MAX - spec->max_steps) && o[1] == std::floor(o[1])))
+      return fail(MOBROB_ERR_INVALID, "follow: resume: steps run of robot %d not a whole number in 0 .. INT_MAX - max_steps", i);
+    if (!(o[2] >= 0.0 && o[2] <= (double)nw[i] && o[2] == std::floor(o[2])))
+      return fail(MOBROB_ERR_INVALID, "follow: resume: waypoints reached of robot %d not a whole number in 0 .. %d", i, nw[i]);
+    if (hazard_out) {
+      const double* h = hazard_out + (size_t)i * 4;
+      if (!(std::isfinite(h[0]) && h[1] >= 0.0 && h[1] <= o[1] && h[1] == std::floor(h[1]) && h[2] >= -1.0 &&
+            h[2] <= (double)INT_MAX && h[2] == std::floor(h[2])))
+        return fail(MOBROB_ERR_INVALID, "follow: resume: carried hazard record of robot %d is not one a call returns", i);
+    }
+  }
+  return MOBROB_OK;
+}
+
+// follow, with hazards when `hio` is not null (mobrob_ppo_follow_waypoints_hazards); one call of a resumable run when `rs` is not
+// null (mobrob_ppo_follow_waypoints_resume: no `start`, arrival / robot_out / hazard_out in and out)
 static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
                             const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
-                            double* robot_out, float* path_out, float* trace_out, const HazardIO* hio) {
-  if (!e || !env || !spec || !start || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
+                            double* robot_out, float* path_out, float* trace_out, const HazardIO* hio,
+                            const mobrob_follow_resume_t* rs = nullptr) {
+  if (!e || !env || !spec || (!start && !rs) || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
   EvalCall c{"follow", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
   if (hio) c.trace_extra = kHazardTraceExtra;
   const int N = c.N, K = spec->max_waypoints, P = env->pos_dim;
@@ -3468,7 +3500,7 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   for (int i = 0; i < N; ++i) {
     nw[i] = n_waypoints ? n_waypoints[i] : K;
     if (nw[i] < 0 || nw[i] > K) return fail(MOBROB_ERR_INVALID, "follow: n_waypoints[%d] = %d outside 0 .. %d", i, nw[i], K);
-    for (int j = 0; j < P; ++j)
+    for (int j = 0; start && j < P; ++j)   // (a call of a run has no start: its state is checked by follow_resume_check)
       if (!std::isfinite(start[(size_t)i * P + j])) return fail(MOBROB_ERR_INVALID, "follow: start of robot %d is not finite", i);
     for (int k = 0; k < nw[i]; ++k)
       for (int j = 0; j < P; ++j)
@@ -3478,14 +3510,19 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   HazardCarve hc;
   if (hio)
     if (const int rc = hazard_check(hio->hz, N, c.who, hc.counts)) return rc;
+  if (rs)
+    if (const int rc = follow_resume_check(rs, spec, nw, robot_out, hio ? hio->hazard_out : nullptr)) return rc;
   const bool pathing = path_out && spec->path_stride > 0;
   const size_t n_rec = pathing ? (size_t)(spec->max_steps / spec->path_stride + 1) : 0;
   EvalCarve carve;
   const size_t o_arr = carve.add((size_t)N * K * 4), o_start = carve.add((size_t)N * P * 4), o_wp = carve.add((size_t)N * K * P * 4),
                o_nw = carve.add((size_t)N * 4), o_path = carve.add(std::max<size_t>(n_rec * N * P, 1) * 4);
   if (hio) hazard_carve(carve, hio->hz, N, hc);
+  const size_t o_state = carve.add(rs ? (size_t)N * 6 * 4 : 0), o_leg = carve.add(rs ? (size_t)N * 4 : 0),
+               o_status = carve.add(rs ? (size_t)N * 4 : 0), o_entry = carve.add(rs ? (size_t)N * 4 : 0);
   HazardArgs<FollowArgs> h{};
-  FollowArgs& f = h.b;
+  HazardArgs<ResumeArgs> hr{};   // the resumable task's arguments: its FollowArgs is the one filled below
+  FollowArgs& f = rs ? hr.b.f : h.b;
   // no termination, no time limit: the robot only stops at its last waypoint
   if (const int rc = eval_prepare(e, c, eval_env_params(env, e->A, false, INT_MAX), carve, f.e)) return rc;
   float* start_dev = eval_at<float>(e, o_start);
@@ -3494,19 +3531,46 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   float* path_dev = eval_at<float>(e, o_path);
   f.arrival = eval_at<int>(e, o_arr);
   f.K = K; f.path_stride = pathing ? spec->path_stride : 0;
-  f.start = start_dev; f.wp = wp_dev; f.nwp = nw_dev;
+  f.start = rs ? nullptr : start_dev; f.wp = wp_dev; f.nwp = nw_dev;
   f.path = pathing ? path_dev : nullptr;
-  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  if (!rs) HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(wp_dev, waypoints, (size_t)N * K * P * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(nw_dev, nw.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
-  HIPC(hipMemsetAsync(f.arrival, 0xFF, (size_t)N * K * 4, e->stream));   // -1: not reached
-  if (hio)
-    if (const int rc = hazard_fill(e, hio->hz, N, hc, h)) return rc;
-  const int ran = hio ? eval_run<HazardFollowTask>(e, h, k_hazard_follow_fin) : eval_run<FollowTask>(e, f, k_follow_goal_fin);
+  int ran;
+  double* hazard_dev = nullptr;
+  if (!rs) {
+    HIPC(hipMemsetAsync(f.arrival, 0xFF, (size_t)N * K * 4, e->stream));   // -1: not reached
+    if (hio)
+      if (const int rc = hazard_fill(e, hio->hz, N, hc, h)) return rc;
+    hazard_dev = h.hazard_out;
+    ran = hio ? eval_run<HazardFollowTask>(e, h, k_hazard_follow_fin) : eval_run<FollowTask>(e, f, k_follow_goal_fin);
+  } else {
+    // the run so far: arrival rows, accumulators, state
+    ResumeArgs& r = hr.b;
+    r.step0 = rs->step0; r.leg_steps = rs->leg_steps;
+    r.state = eval_at<float>(e, o_state); r.leg_used = eval_at<int>(e, o_leg);
+    r.status = eval_at<int>(e, o_status); r.entry_steps = eval_at<int>(e, o_entry);
+    HIPC(hipMemcpyAsync(f.arrival, arrival, (size_t)N * K * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(f.e.robot_out, robot_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(r.state, rs->state, (size_t)N * 6 * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(r.leg_used, rs->leg_used, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+    if (hio) {
+      if (const int rc = hazard_fill(e, hio->hz, N, hc, hr)) return rc;
+      HIPC(hipMemcpyAsync(hr.hazard_out, hio->hazard_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
+    }
+    hazard_dev = hr.hazard_out;
+    ran = hio ? eval_run<HazardTask<ResumeFollowTask>>(e, hr, k_goal_task_fin<HazardTask<ResumeFollowTask>>)
+              : eval_run<ResumeFollowTask>(e, r, k_goal_task_fin<ResumeFollowTask>);
+    if (ran >= 0) {
+      HIPC(hipMemcpyAsync(rs->state, r.state, (size_t)N * 6 * 4, hipMemcpyDeviceToHost, e->stream));
+      HIPC(hipMemcpyAsync(rs->leg_used, r.leg_used, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+      HIPC(hipMemcpyAsync(rs->status, r.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+  }
   if (ran < 0) return ran;
   HIPC(hipMemcpyAsync(arrival, f.arrival, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
   if (pathing) HIPC(hipMemcpyAsync(path_out, path_dev, n_rec * N * P * 4, hipMemcpyDeviceToHost, e->stream));
-  if (hio) HIPC(hipMemcpyAsync(hio->hazard_out, h.hazard_out, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
+  if (hio) HIPC(hipMemcpyAsync(hio->hazard_out, hazard_dev, (size_t)N * 4 * 8, hipMemcpyDeviceToHost, e->stream));
   return eval_copy_back(e, c, f.e, robot_out, ran);
 }
 
@@ -3523,6 +3587,16 @@ int mobrob_ppo_follow_waypoints_hazards(mobrob_ppo_engine_t* e, const mobrob_goa
   if (!hz || !hazard_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
   const HazardIO hio{hz, hazard_out, nullptr};
   return follow_waypoints(e, env, spec, start, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out, &hio);
+}
+
+int mobrob_ppo_follow_waypoints_resume(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                       const mobrob_hazards_t* hz, const mobrob_follow_resume_t* resume, const float* waypoints,
+                                       const int32_t* n_waypoints, int32_t* arrival, double* robot_out, double* hazard_out,
+                                       float* path_out, float* trace_out) {
+  if (!resume || (hz == nullptr) != (hazard_out == nullptr)) return fail(MOBROB_ERR_INVALID, "follow: resume: null argument");
+  const HazardIO hio{hz, hazard_out, nullptr};
+  return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
+                          hz ? &hio : nullptr, resume);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

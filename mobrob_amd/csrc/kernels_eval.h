@@ -148,6 +148,7 @@ struct EvalTask {
     R = Robot{0.0, 0.0, 0, 0, 0, a.quota[n]};
   }
   static constexpr bool kWide = false;   // k_goal64_tile: step runs on the robot's lane only
+  static constexpr bool kResume = false;   // the launch's step 0 is the streams' step 0 (task_step0 below)
   static __device__ __forceinline__ bool active(const Args& a, const Robot& R) { return a.episodes == 0 || R.eps < R.quota; }
   // XT / post: for a wrapping task (kernels_hazard.h): trace row width + XT, the post-step x, y
   template <int XT = 0>
@@ -169,6 +170,14 @@ struct EvalTask {
   }
 };
 
+// the global step of the launch's step 0: the observation and action streams are keyed by (robot, task_step0 + t).  A task of a
+// run that spans several calls (kResume: ResumeFollowTask, kernels_follow.h) names it; for every other task it is the constant 0
+template <class Task>
+__device__ __forceinline__ int task_step0(const typename Task::Args& args) {
+  if constexpr (Task::kResume) return Task::step0(args);
+  else return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // per-step path: robot state in st, the task's accumulators wherever Task::store keeps them between launches
 // ------------------------------------------------------------------------------------------------
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(256) void k_goal_task_init(typename Task::Args args
   Task::start(g, R, args, n);
   goal_store(a.st + (size_t)n * kGoalStateFloats, g);
   Task::store(args, n, R);
-  eval_obs_store(g, a, n, 0u);
+  eval_obs_store(g, a, n, (uint32_t)task_step0<Task>(args));
 }
 
 template <class Task>
@@ -194,11 +203,21 @@ __global__ __launch_bounds__(256) void k_goal_task_step(typename Task::Args args
   if (!Task::active(args, R)) return;   // idles: quota met / last waypoint reached
   GoalState g = goal_load(a.st + (size_t)n * kGoalStateFloats);
   float* act = &lds[threadIdx.x * 33];   // [256][33]: the thread's clipped actions (LDS, not a dynamically indexed register array)
-  eval_actions(a, n, t, a.mu + (size_t)n * a.Ap, act);
+  const int g0 = task_step0<Task>(args);
+  eval_actions(a, n, g0 + t, a.mu + (size_t)n * a.Ap, act);
   (void)Task::step(g, R, args, n, t, act, a.obs + (size_t)n * a.Dp);
   goal_store(a.st + (size_t)n * kGoalStateFloats, g);
   Task::store(args, n, R);
-  eval_obs_store(g, a, n, (uint32_t)t + 1u);
+  eval_obs_store(g, a, n, (uint32_t)(g0 + t) + 1u);
+}
+
+// the task's finish for every robot, from what the last step stored (a resumable task: robot_out, carried state, status, path)
+template <class Task>
+__global__ __launch_bounds__(256) void k_goal_task_fin(typename Task::Args args) {
+  const EvalArgs& a = Task::eval(args);
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= a.N) return;
+  Task::finish(args, n, Task::load(args, n), goal_load(a.st + (size_t)n * kGoalStateFloats));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -368,16 +387,17 @@ __global__ __launch_bounds__(64) void k_goal64_tile(typename Task::Args args, Ev
   }
   __syncthreads();
   const bool wide_head = a.A > 16;
+  const int g0 = task_step0<Task>(args);   // t: step of this launch (trace, path); g0 + t: step of the streams
   for (int t = 0; t < a.max_steps; ++t) {
     if (__ballot(active) == 0ull) break;   // one wave per workgroup: uniform
-    eval64_actor_step<DP>(a, row0, t, lane, wide_head);
+    eval64_actor_step<DP>(a, row0, g0 + t, lane, wide_head);
     if constexpr (Task::kWide) {
       // ---- env phase on the tile's 16 lanes, then the task's wide phase on all 64 (robot lane & 15 stepped: bit of `stepping`) ----
       const uint64_t stepping = __ballot(mine && active);
       int e0 = 0;
       if (mine && active) {
         float* act = &lds[L::MU + r16 * L::LDM];
-        eval_actions(a, n, t, act, act);
+        eval_actions(a, n, g0 + t, act, act);
         active = Task::step_lane(g, R, args, n, t, act, &lds[L::X + r16 * L::LDX], &lds[L::END + 2 * r16], e0);
         eval64_state_lds(&lds[L::ST + 12 * r16], g);
       }
@@ -388,7 +408,7 @@ __global__ __launch_bounds__(64) void k_goal64_tile(typename Task::Args args, Ev
     // ---- env phase: the tile's 16 lanes ----
     if (mine && active) {
       float* act = &lds[L::MU + r16 * L::LDM];   // the mean row becomes the applied action in place
-      eval_actions(a, n, t, act, act);
+      eval_actions(a, n, g0 + t, act, act);
       active = Task::step(g, R, args, n, t, act, &lds[L::X + r16 * L::LDX]);
       eval64_state_lds(&lds[L::ST + 12 * r16], g);
     }

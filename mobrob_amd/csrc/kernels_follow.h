@@ -11,6 +11,12 @@
 // k_goal64_tile for 2x64 tanh actors: the exit ballot is over the tile's unfinished robots).  One kernel is the task's own:
 //
 //   k_follow_goal_fin   robot_out and the path records of robots that finished early           (per-step path, one launch)
+//
+// ResumeFollowTask (mobrob_ppo_follow_waypoints_resume) is the same rules as one call of a RUN: a sequence of calls over the same
+// robots and seed, call c covering global steps step0 .. step0 + max_steps - 1.  The robot's position, velocity, reward sum, steps,
+// waypoint index, arrival row and `leg_used` (steps spent on the waypoint in force) are read at entry and continued, the streams
+// and the arrival steps use the global step, and a leg budget (leg_steps > 0) idles a robot that has spent it.  Path and trace
+// stay local to the call.  A run split into calls gives the bits of one call (every carried value is continued, never re-summed).
 #pragma once
 #include "kernels_eval.h"
 
@@ -64,10 +70,10 @@ __device__ __forceinline__ void follow_start(GoalState& g, FollowRobot& R, const
 
 // step t of robot n (unfinished: R.k < R.nwp): trace (state before the step, observation, action), env.step, float64 reward sum,
 // arrival and the next waypoint, path record.  Returns whether the robot is still unfinished afterwards.  XT / post: as
-// eval_env_step's.
+// eval_env_step's.  g0: the global step of the call's step 0 (a resumed run; arrival steps are global, trace and path local).
 template <int XT = 0>
 __device__ __forceinline__ bool follow_env_step(GoalState& g, FollowRobot& R, const FollowArgs& f, int n, int t, const float* act,
-                                                const float* obs_row, float* post = nullptr) {
+                                                const float* obs_row, float* post = nullptr, int g0 = 0) {
   const EvalArgs& a = f.e;
   float* fl = eval_trace_row<XT>(g, a, n, t, act, obs_row);
   const int k_before = R.k;
@@ -76,7 +82,7 @@ __device__ __forceinline__ bool follow_env_step(GoalState& g, FollowRobot& R, co
   R.steps += 1;
   R.ret_sum += (double)o.reward;
   if (o.reached) {
-    f.arrival[(size_t)n * f.K + R.k] = t + 1;
+    f.arrival[(size_t)n * f.K + R.k] = g0 + t + 1;
     R.k += 1;
     if (R.k < R.nwp) follow_set_goal(g, f, n, R.k);
   }
@@ -88,13 +94,15 @@ __device__ __forceinline__ bool follow_env_step(GoalState& g, FollowRobot& R, co
   return going;
 }
 
-// robot_out, and the path records after the robot's last step (a robot that finished early stays where it is)
-__device__ __forceinline__ void follow_finish(const FollowArgs& f, int n, const FollowRobot& R, const GoalState& g) {
+// robot_out, and the path records after the robot's last step (a robot that finished early stays where it is).  entry_steps:
+// R.steps at the call's entry (a resumed run: the path is the call's own)
+__device__ __forceinline__ void follow_finish(const FollowArgs& f, int n, const FollowRobot& R, const GoalState& g,
+                                              int entry_steps = 0) {
   double* o = f.e.robot_out + (size_t)n * 4;
   o[0] = R.ret_sum; o[1] = (double)R.steps; o[2] = (double)R.k;
   o[3] = R.nwp > 0 ? (double)goal_dist(g.goal, g.pos, f.e.p.P) : __longlong_as_double(0x7FF8000000000000ll);
   if (f.path)
-    for (int r = R.steps / f.path_stride + 1; r <= f.e.max_steps / f.path_stride; ++r) follow_path_store(f, r, n, g);
+    for (int r = (R.steps - entry_steps) / f.path_stride + 1; r <= f.e.max_steps / f.path_stride; ++r) follow_path_store(f, r, n, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -116,6 +124,7 @@ struct FollowTask {
   static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& f) { return f.e; }
   static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& f, int n) { follow_start(g, R, f, n); }
   static constexpr bool kWide = false;
+  static constexpr bool kResume = false;
   static __device__ __forceinline__ bool active(const Args&, const Robot& R) { return R.k < R.nwp; }
   template <int XT = 0>
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& f, int n, int t, const float* act,
@@ -135,5 +144,89 @@ __global__ __launch_bounds__(256) void k_follow_goal_fin(FollowArgs f) {
   if (n >= f.e.N) return;
   follow_finish(f, n, follow_robot_load(f, n), goal_load(f.e.st + (size_t)n * kGoalStateFloats));
 }
+
+// ------------------------------------------------------------------------------------------------
+// one call of a resumable run
+// ------------------------------------------------------------------------------------------------
+constexpr int kFollowGoing = 0, kFollowFinished = 1, kFollowStalled = 2, kFollowNoWaypoints = 3;   // status at exit
+
+struct ResumeArgs {
+  FollowArgs f;        // f.start is unused; f.e.robot_out [N][0..2] and f.arrival hold the run's values at entry
+  int step0;           // global step of the call's step 0
+  int leg_steps;       // step budget per waypoint, 0 = none
+  float* state;        // [N][6] position, velocity: in / out
+  int* leg_used;       // [N] steps spent on the waypoint in force: in / out
+  int* status;         // [N] out
+  int* entry_steps;    // [N] steps run at entry (per-step path: kept for the finish kernel's path records)
+};
+
+struct ResumeRobot {
+  FollowRobot b;
+  int leg_used, entry_steps;
+};
+
+struct ResumeFollowTask {
+  using Args = ResumeArgs;
+  using Robot = ResumeRobot;
+  static constexpr bool kWide = false;
+  static constexpr bool kResume = true;
+  static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& a) { return a.f.e; }
+  static __device__ __forceinline__ int step0(const Args& a) { return a.step0; }
+  // the carried robot: pose and velocity from `state`, accumulators from robot_out, goal = the waypoint in force (a finished
+  // robot keeps its last waypoint, one without waypoints its position, as after follow_start / follow_env_step); path record 0
+  static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& a, int n) {
+    const FollowArgs& f = a.f;
+    // GoalState.ep_len / ep_ret are NOT carried: they restart at 0 every call.  Nothing reads them here (no time limit, no episode
+    // output); a task that gives following a time limit must carry them as well, or a split run differs from the unsplit one
+    g = GoalState{};
+    R.b = follow_robot_load(f, n);
+    R.leg_used = a.leg_used[n];
+    R.entry_steps = R.b.steps;
+    const float* s = a.state + (size_t)n * 6;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      g.pos[j] = j < f.e.p.P ? s[j] : 0.f;
+      g.vel[j] = j < f.e.p.P ? s[3 + j] : 0.f;
+    }
+    if (R.b.nwp > 0) {
+      follow_set_goal(g, f, n, R.b.k < R.b.nwp ? R.b.k : R.b.nwp - 1);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) g.goal[j] = g.pos[j];
+    }
+    if (f.path) follow_path_store(f, 0, n, g);
+  }
+  static __device__ __forceinline__ bool active(const Args& a, const Robot& R) {
+    return R.b.k < R.b.nwp && (a.leg_steps == 0 || R.leg_used < a.leg_steps);
+  }
+  template <int XT = 0>
+  static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
+                                              const float* obs_row, float* post = nullptr) {
+    const int k0 = R.b.k;
+    (void)follow_env_step<XT>(g, R.b, a.f, n, t, act, obs_row, post, a.step0);
+    R.leg_used = (R.b.k != k0 || a.leg_steps == 0) ? 0 : R.leg_used + 1;   // an arrival starts the next leg; no budget, no count
+    return active(a, R);
+  }
+  static __device__ __forceinline__ int episodes(const Robot&) { return 0; }
+  static __device__ __forceinline__ int steps(const Robot& R) { return R.b.steps; }
+  static __device__ __forceinline__ bool recorded(const Robot&, int) { return false; }
+  static __device__ __forceinline__ void finish(const Args& a, int n, const Robot& R, const GoalState& g) {
+    follow_finish(a.f, n, R.b, g, R.entry_steps);
+    float* s = a.state + (size_t)n * 6;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { s[j] = g.pos[j]; s[3 + j] = g.vel[j]; }
+    a.leg_used[n] = R.leg_used;
+    a.status[n] = R.b.nwp == 0 ? kFollowNoWaypoints : R.b.k >= R.b.nwp ? kFollowFinished
+                  : (a.leg_steps > 0 && R.leg_used >= a.leg_steps) ? kFollowStalled : kFollowGoing;
+  }
+  static __device__ __forceinline__ Robot load(const Args& a, int n) {
+    return Robot{follow_robot_load(a.f, n), a.leg_used[n], a.entry_steps[n]};
+  }
+  static __device__ __forceinline__ void store(const Args& a, int n, const Robot& R) {
+    follow_robot_store(a.f, n, R.b);
+    a.leg_used[n] = R.leg_used;
+    a.entry_steps[n] = R.entry_steps;
+  }
+};
 
 }  // namespace mobrob

@@ -62,6 +62,8 @@ struct HazardTask {
     float min_clear;
   };
   static constexpr bool kWide = true;   // k_goal64_tile: the check runs on all 64 lanes (step_lane + after_step below)
+  static constexpr bool kResume = Base::kResume;   // a resumable base: accumulators continue from hazard_out, global steps
+  static __device__ __forceinline__ int step0(const Args& h) { return task_step0<Base>(h.b); }
 
   static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& h) { return Base::eval(h.b); }
   // LDS of k_goal64_tile beyond LayEval64::END: [16][2] post-step positions, then a shared scene
@@ -79,7 +81,7 @@ struct HazardTask {
     R.ep_cost += (double)cost;
     if (cost > 0.f) {
       R.viol += 1;
-      if (R.first < 0) R.first = t + 1;
+      if (R.first < 0) R.first = task_step0<Base>(h.b) + t + 1;
     }
     R.min_clear = fminf(R.min_clear, clear);
     if (Base::episodes(R.b) != e0) {   // the step ended an episode: its cost includes this step's
@@ -96,6 +98,7 @@ struct HazardTask {
   static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& h, int n) {
     Base::start(g, R.b, h.b, n);
     R.cost_sum = 0.0; R.ep_cost = 0.0; R.viol = 0; R.first = -1; R.min_clear = __builtin_inff();
+    if constexpr (kResume) hazard_load(h, n, R);   // the run's accumulators so far
   }
   static __device__ __forceinline__ bool active(const Args& h, const Robot& R) { return Base::active(h.b, R.b); }
 
@@ -156,12 +159,16 @@ struct HazardTask {
     Base::finish(h.b, n, R.b, g);
     hazard_store(h, n, R);
   }
-  static __device__ __forceinline__ Robot load(const Args& h, int n) {
-    Robot R;
-    R.b = Base::load(h.b, n);
+  // R's accumulators from hazard_out (R.b loaded)
+  static __device__ __forceinline__ void hazard_load(const Args& h, int n, Robot& R) {
     const double* o = h.hazard_out + (size_t)n * 4;
     R.cost_sum = o[0]; R.viol = (int)o[1]; R.first = (int)o[2];
     R.min_clear = Base::steps(R.b) > 0 ? (float)o[3] : __builtin_inff();
+  }
+  static __device__ __forceinline__ Robot load(const Args& h, int n) {
+    Robot R;
+    R.b = Base::load(h.b, n);
+    hazard_load(h, n, R);
     R.ep_cost = h.ep_acc[n];
     return R;
   }

@@ -439,15 +439,29 @@ class PPOEngine:
         return out
 
     def follow_waypoints(self, pos_dim, mix, dt=0.05, extent=3.0, reach_radius=0.3, goal_bonus=5.0, extra_bonus=0.0,
-                         obs_noise=0.1, *, start, waypoints, n_waypoints=None, max_steps=1000, deterministic=True, seed=0,
-                         path_stride=0, trace=None, hazards=None):
+                         obs_noise=0.1, *, start=None, waypoints=None, n_waypoints=None, max_steps=1000, deterministic=True, seed=0,
+                         path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0):
         """The current policy as a tracker of given goal sequences (mobrob_ppo_follow_waypoints): robot i starts at rest on
         start[i] ([n][P]) and follows waypoints[i][:n_waypoints[i]] (waypoints [n][K][P], or [K][P] for all robots; n_waypoints
         None = K each), no time limit, no reset.  path_stride > 0 records positions; trace = (robots, steps): teacher-forcing
         trace.  Returns the dict of mobrob_amd.waypoints (arrival, reached, steps, reward_sum, final_distance, path, trace,
         persistent).  hazards: a goal_rules.Hazards -> mobrob_ppo_follow_waypoints_hazards, adding cost_sum, violation_steps,
-        first_violation, min_clearance; trace rows then end in the step's cost and clearance."""
-        from .waypoints import follow_inputs
+        first_violation, min_clearance; trace rows then end in the step's cost and clearance.
+        resume: a waypoints.FollowState -> mobrob_ppo_follow_waypoints_resume, one call of the run the state is in (start,
+        waypoints and n_waypoints must be None: the state holds them); leg_steps: step budget per waypoint (0: none).  With
+        `leg_steps` alone the call starts a run.  Such a call adds `state` (the FollowState after the call; the one given is left
+        as it was) and `status` [n] to the dict; steps, reached, reward_sum and the hazard sums are the run's, path and trace the
+        call's."""
+        from .waypoints import FollowState, follow_inputs
+        if resume is not None or int(leg_steps) != 0:
+            if resume is None:
+                resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim)
+            elif not (start is None and waypoints is None and n_waypoints is None):
+                raise ValueError("follow_waypoints: a resumed call takes its robots and waypoints from `resume`")
+            return self._follow_resume(pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, resume,
+                                       int(leg_steps), max_steps, deterministic, seed, path_stride, trace, hazards)
+        if start is None or waypoints is None:
+            raise ValueError("follow_waypoints: start and waypoints are needed unless `resume` continues a run")
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
         n, K, P = wp.shape
         sp = FollowSpec()
@@ -472,6 +486,53 @@ class PPOEngine:
                     "trace": tr})
         if hazards is not None:
             out.update(self._hazard_result(hz))
+        if path is not None:
+            out["path"] = path
+        return out
+
+    def _follow_resume(self, pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, state, leg_steps,
+                       max_steps, deterministic, seed, path_stride, trace, hazards):
+        """One call of a run (mobrob_ppo_follow_waypoints_resume) on a copy of `state`."""
+        from ._lib import FollowResume
+        from .waypoints import FollowState
+        if not isinstance(state, FollowState):
+            raise TypeError(f"follow_waypoints: resume must be a FollowState, not {type(state).__name__}")
+        if (state.hazard is None) != (hazards is None):
+            raise ValueError("follow_waypoints: a run has hazards in every call or in none (FollowState(..., hazards=True))")
+        st = state.copy()
+        n, K, P = st.waypoints.shape
+        if P != int(pos_dim):
+            raise ValueError(f"follow_waypoints: the state has {P} position dimensions, the environment {int(pos_dim)}")
+        st.state, st.waypoints = np.ascontiguousarray(st.state, F32), np.ascontiguousarray(st.waypoints, F32)
+        st.robot = np.ascontiguousarray(st.robot, np.float64)
+        st.arrival, st.n_waypoints, st.leg_used, st.status = (np.ascontiguousarray(x, np.int32) for x in
+                                                             (st.arrival, st.n_waypoints, st.leg_used, st.status))
+        if st.hazard is not None:
+            st.hazard = np.ascontiguousarray(st.hazard, np.float64)
+        if st.state.shape != (n, 6) or st.robot.shape != (n, 4) or st.arrival.shape != (n, K) or st.leg_used.shape != (n,):
+            raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
+        sp = FollowSpec()
+        tr = self._eval_spec_common("follow_waypoints", sp, max_steps, deterministic, seed, trace, 0 if hazards is None else 2)
+        g = self._goal_env_struct(pos_dim, mix, 0, False, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise)
+        sp.n_robots, sp.max_waypoints, sp.path_stride = n, K, int(path_stride)
+        path = np.zeros((int(max_steps) // int(path_stride) + 1, n, P), F32) if int(path_stride) > 0 and int(max_steps) > 0 else None
+        i32, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        rs = FollowResume()
+        if not (-2 ** 31 <= int(st.step0) < 2 ** 31 and -2 ** 31 <= int(leg_steps) < 2 ** 31):
+            raise ValueError("follow_waypoints: step0 and leg_steps must fit an int32")
+        rs.step0, rs.leg_steps = int(st.step0), int(leg_steps)
+        rs.state, rs.leg_used, rs.status = _fp(st.state), st.leg_used.ctypes.data_as(i32), st.status.ctypes.data_as(i32)
+        h, _keep = (None, None) if hazards is None else self._hazards_struct(hazards, n)
+        r = check(self.lib.mobrob_ppo_follow_waypoints_resume(
+            self._h, C.byref(g), C.byref(sp), None if h is None else C.byref(h), C.byref(rs), _fp(st.waypoints),
+            st.n_waypoints.ctypes.data_as(i32), st.arrival.ctypes.data_as(i32), st.robot.ctypes.data_as(dp),
+            None if h is None else st.hazard.ctypes.data_as(dp), _fp(path), _fp(tr)))
+        st.step0 += int(max_steps)
+        out = self._eval_result(st.robot.copy(), r)
+        out.update({"arrival": st.arrival.astype(np.int64), "reached": st.reached, "final_distance": st.robot[:, 3].copy(),
+                    "trace": tr, "state": st, "status": st.status.copy()})
+        if hazards is not None:
+            out.update(self._hazard_result(st.hazard.copy()))
         if path is not None:
             out["path"] = path
         return out

@@ -218,14 +218,16 @@ class DeviceGoalVecEnv(VecEnvBase):
                                         episodes=episodes, quota=quota, deterministic=deterministic,
                                         seed=(self._seed or 0) if seed is None else seed, trace=trace, hazards=hazards)
 
-    def follow(self, engine, start, waypoints, n_waypoints=None, max_steps=1000, deterministic=True, seed=None, path_stride=0,
-               trace=None, hazards=None):
+    def follow(self, engine, start=None, waypoints=None, n_waypoints=None, max_steps=1000, deterministic=True, seed=None,
+               path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0):
         """The engine's current policy following given waypoints on this task (PPOEngine.follow_waypoints with this env's mix,
-        dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed.  hazards: a goal_rules.Hazards."""
+        dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed.  hazards: a goal_rules.Hazards.
+        resume: a waypoints.FollowState (this call continues that run; no start / waypoints then); leg_steps: step budget per
+        waypoint.  Either makes the call return `state` and `status` as well."""
         return engine.follow_waypoints(self.pos_dim, self.mix, dt=self.dt, extent=self.extent, extra_bonus=self.extra_bonus,
                                        start=start, waypoints=waypoints, n_waypoints=n_waypoints, max_steps=int(max_steps),
                                        deterministic=deterministic, seed=(self._seed or 0) if seed is None else seed,
-                                       path_stride=path_stride, trace=trace, hazards=hazards)
+                                       path_stride=path_stride, trace=trace, hazards=hazards, resume=resume, leg_steps=leg_steps)
 
     def seed(self, seed=None):
         self._seed = seed

@@ -23,6 +23,23 @@ With `hazards` (a goal_rules.Hazards), also the hazard costs of every step (the 
 position after the step; on the host: info["cost"] of EnvWrapper.step with set_hazards):
   cost_sum [n] float64 sum of the step costs;  violation_steps [n] steps with cost > 0;  first_violation [n] the first such step
   (1-based), -1 = none;  min_clearance [n] smallest (distance - radius) after a step (+inf without hazards, NaN without steps)
+
+Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
+sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
+into the next call) and `status`, and takes the previous call's `state=`.  Call c covers the global steps step0 .. step0 +
+max_steps - 1:
+  * observation and action noise are drawn per (robot, global step); arrival steps (and first_violation) are global, 1-based;
+  * position, velocity, reward sum, steps, waypoints reached (= the index k of the waypoint in force), the arrival row,
+    `leg_used` (steps spent on the waypoint in force) and the hazard sums are read at entry and continued, never re-summed: a
+    run split into calls ends exactly where one long call ends;
+  * leg budget `leg_steps` (0: none, leg_used stays 0): after a step, an arrival sets leg_used = 0, any other step adds 1 to it;
+    a robot is active while k < its count and (leg_steps == 0 or leg_used < leg_steps);
+  * status [n] at the end of the call: 0 going (the call's step cap ended it), 1 finished, 2 stalled (budget spent), 3 no
+    waypoints;
+  * between calls `state.replan(rows, waypoints)` gives robots new waypoints: reached = 0, arrival row = -1, leg_used = 0,
+    everything else carried;
+  * `path` and `trace` are the call's own: record 0 is the position at entry, `steps`, `reached`, `reward_sum` are the run's.
+`follow_with_replanning` is that loop with a planner callback.
 """
 from __future__ import annotations
 
@@ -62,85 +79,204 @@ def follow_inputs(start, waypoints, n_waypoints=None, pos_dim=None):
     return np.ascontiguousarray(start, np.float32), np.ascontiguousarray(wp, np.float32), nw
 
 
-def _host_follow(model, make_env, start, wp, nw, max_steps, deterministic, seed, path_stride, hazards=None):
-    """The semantics, one robot after another on EnvWrapper's public API (make_env(i) -> the robot's env)."""
+GOING, FINISHED, STALLED, NO_WAYPOINTS = 0, 1, 2, 3   # status of a robot at the end of a call
+
+
+class FollowState:
+    """What the robots of a run carry from one call into the next (see the module docstring), and the next call's `step0`.
+      state [n][6]      position, velocity (unused components zero): float32 from the device, float64 from the host loop
+      robot [n][4]      float64 reward sum, steps run, waypoints reached (= index of the waypoint in force), final distance (out only)
+      arrival [n][K]    int32 global arrival steps, -1 = not reached;  leg_used [n] int32;  status [n] int32 (of the last call)
+      hazard [n][4]     float64 cost sum, violation steps, first violation, min clearance -- or None without hazards
+      waypoints [n][K][P] float32, n_waypoints [n] int32: the rows in force (changed by `replan` only)"""
+
+    def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None):
+        s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
+        n, K, P = wp.shape
+        self.waypoints, self.n_waypoints, self.step0 = wp, nw, 0
+        self.state = np.zeros((n, 6), np.float32)
+        self.state[:, :P] = s
+        self.robot = np.zeros((n, 4), np.float64)
+        self.arrival = np.full((n, K), -1, np.int32)
+        self.leg_used, self.status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.hazard = np.tile(np.array([0.0, 0.0, -1.0, np.nan]), (n, 1)) if hazards else None
+
+    def copy(self):
+        c = object.__new__(FollowState)
+        c.__dict__ = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self.__dict__.items()}
+        return c
+
+    @property
+    def n_robots(self):
+        return self.waypoints.shape[0]
+
+    @property
+    def positions(self):
+        """[n][P] where the robots are"""
+        return self.state[:, :self.waypoints.shape[2]]
+
+    @property
+    def reached(self):
+        return self.robot[:, 2].astype(np.int64)
+
+    def replan(self, rows, waypoints, n_waypoints=None):
+        """New waypoints for the robots `rows` ([m] indices): waypoints [m][K'][P] or [K'][P] (the same for each), counts
+        n_waypoints [m] (None: K' each).  Those robots start over on their new rows -- reached = 0, arrival = -1, leg_used = 0 --
+        and keep position, velocity, reward sum, steps run and hazard sums.  K grows when K' is larger."""
+        rows = np.atleast_1d(np.asarray(rows))
+        if rows.size == 0:
+            return self
+        if rows.ndim != 1 or not np.issubdtype(rows.dtype, np.integer) or (rows.size and (rows.min() < 0 or rows.max() >= self.n_robots)):
+            raise ValueError(f"replan: rows must be robot indices in 0 .. {self.n_robots - 1}")
+        if len(np.unique(rows)) != len(rows):
+            raise ValueError("replan: a robot is listed twice")
+        n, K, P = self.waypoints.shape
+        _, wp, nw = follow_inputs(np.zeros((len(rows), P)), waypoints, n_waypoints, P)
+        K2 = wp.shape[1]
+        if K2 > K:
+            self.waypoints = np.concatenate([self.waypoints, np.zeros((n, K2 - K, P), np.float32)], axis=1)
+            self.arrival = np.concatenate([self.arrival, np.full((n, K2 - K), -1, np.int32)], axis=1)
+        self.waypoints[rows] = 0.0
+        self.waypoints[rows, :K2] = wp
+        self.n_waypoints[rows] = nw
+        self.arrival[rows] = -1
+        self.robot[rows, 2] = 0.0
+        self.leg_used[rows] = 0
+        return self
+
+
+def _check_run(state, leg_steps, max_steps, hazards):
+    """The run's values a call is given, checked as the engine checks them (ValueError)."""
+    leg_steps = int(leg_steps)
+    if leg_steps < 0:
+        raise ValueError("leg_steps must be >= 0 (0: no budget)")
+    if not isinstance(state, FollowState):
+        raise TypeError(f"state must be a FollowState, not {type(state).__name__}")
+    if state.step0 < 0 or state.step0 + int(max_steps) > 2 ** 31 - 1:
+        raise ValueError("state.step0 must be >= 0 and step0 + max_steps fit an int32")
+    if (state.hazard is None) != (hazards is None):
+        raise ValueError("a run has hazards in every call or in none (FollowState(..., hazards=True))")
+    if not np.all(np.isfinite(state.state)) or not np.all(np.isfinite(state.robot[:, 0])):
+        raise ValueError("state holds non-finite positions, velocities or reward sums")
+    if np.any(state.leg_used < 0) or np.any(state.leg_used > leg_steps):
+        raise ValueError(f"state.leg_used must lie in 0 .. {leg_steps}")
+    if np.any(state.robot[:, 2] < 0) or np.any(state.robot[:, 2] > state.n_waypoints):
+        raise ValueError("state: waypoints reached must lie in 0 .. n_waypoints")
+    return leg_steps
+
+
+def _status(k, nw, leg_used, leg_steps):
+    return NO_WAYPOINTS if nw == 0 else FINISHED if k >= nw else STALLED if leg_steps > 0 and leg_used >= leg_steps else GOING
+
+
+def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards=None, leg_steps=0):
+    """The semantics, one robot after another on EnvWrapper's public API (make_env(i) -> the robot's env): one call of the run
+    `state` is in (a fresh FollowState: the robots at rest on their starts).  Returns the dict and the state after the call.
+    The simulator's noise is seeded per (robot, global step), so a run split into calls draws what one long call draws."""
     from .envs.goal_rules import hazard_cost
+    st = state.copy()
+    st.state = st.state.astype(np.float64)              # the host simulator's own precision, carried exactly
+    wp, nw, step0 = st.waypoints, st.n_waypoints, st.step0
     n, K, P = wp.shape
     if hazards is not None:
         hazards.check_robots(n)
-    cost_sum, viol = np.zeros(n), np.zeros(n, np.int64)
-    first, min_clear = np.full(n, -1, np.int64), np.full(n, np.nan)
-    arrival = np.full((n, K), -1, np.int64)
-    reached, steps = np.zeros(n, np.int64), np.zeros(n, np.int64)
-    reward_sum, final_distance = np.zeros(n), np.full(n, np.nan)
+    final_distance = np.full(n, np.nan)
     path = np.zeros((max_steps // path_stride + 1, n, P), np.float32) if path_stride > 0 else None
+    key = None if seed is None else int(seed) & (2 ** 64 - 1)
     for i in range(n):
-        pos = start[i].astype(np.float64)
+        pos, vel = st.state[i, :P].copy(), st.state[i, 3:3 + P].copy()
+        k, leg_used, ran = int(st.robot[i, 2]), int(st.leg_used[i]), 0
         if path is not None:
             path[0, i] = pos
-        if nw[i] > 0:
+        if k < nw[i] and (leg_steps == 0 or leg_used < leg_steps):
             env = make_env(i)
             if hazards is not None:
                 rows = hazards.rows(i)
                 env.set_hazards(rows[:, :2], rows[:, 2], hazards.cost, hazards.indicator)
-                min_clear[i] = np.inf
             if seed is not None:
                 env.seed(int(seed) + i)
-            env.env.reset()                            # the simulator at rest: every robot starts with zero velocity
-            obs, _ = env.reset(init_pos=start[i])
-            env.set_goal(wp[i, 0])
-            obs = env.get_obs()
-            k = 0
+            env.env.reset()                            # the simulator at rest ...
+            env.reset(init_pos=pos)
+            if np.any(vel != 0.0):                     # ... then moving as the robot was when the last call ended
+                if not hasattr(env.env, "vel"):
+                    raise TypeError("resuming a moving robot needs a simulator whose velocity can be set (env.env.vel)")
+                env.env.vel = vel.copy()
+            env.set_goal(wp[i, k])
             for t in range(max_steps):
+                g = step0 + t                          # the global step
+                if key is not None:
+                    env.env.seed([key, i, g])
+                obs = env.get_obs()
                 a, _ = model.predict(obs, deterministic=deterministic)
-                obs, r, _, _, info = env.step(a)
-                reward_sum[i] += float(r)
-                steps[i] = t + 1
+                _, r, _, _, info = env.step(a)
+                st.robot[i, 0] += float(r)
+                st.robot[i, 1] += 1
+                ran = t + 1
                 pos = np.asarray(env.get_pos(), np.float64)[:P]
                 if hazards is not None:
-                    cost_sum[i] += info["cost"]
+                    h = st.hazard[i]
+                    h[0] += info["cost"]
                     if info["cost"] > 0:
-                        viol[i] += 1
-                        first[i] = t + 1 if first[i] < 0 else first[i]
-                    min_clear[i] = min(min_clear[i], hazard_cost(pos, rows)[1])
+                        h[1] += 1
+                        h[2] = g + 1 if h[2] < 0 else h[2]
+                    h[3] = min(np.inf if np.isnan(h[3]) else h[3], hazard_cost(pos, rows)[1])
                 if path is not None and (t + 1) % path_stride == 0:
                     path[(t + 1) // path_stride, i] = pos
                 if env.reached():
-                    arrival[i, k] = t + 1
-                    k += 1
+                    st.arrival[i, k] = g + 1
+                    k, leg_used = k + 1, 0
                     if k == nw[i]:
                         break
                     env.set_goal(wp[i, k])
-                    obs = env.get_obs()
-            reached[i] = k
-            final_distance[i] = float(np.linalg.norm(np.asarray(env.get_goal(), np.float64)[:P] - pos))
+                elif leg_steps > 0:
+                    leg_used += 1
+                    if leg_used >= leg_steps:
+                        break
+            vel = np.asarray(getattr(env.env, "vel", np.zeros(P)), np.float64)[:P]
             if hazards is not None:
                 env.set_hazards(None)
+        if nw[i] > 0:
+            final_distance[i] = float(np.linalg.norm(wp[i, min(k, nw[i] - 1)].astype(np.float64) - pos))
+        st.state[i, :P], st.state[i, 3:3 + P] = pos, vel
+        st.robot[i, 2], st.robot[i, 3], st.leg_used[i] = k, final_distance[i], leg_used
+        st.status[i] = _status(k, nw[i], leg_used, leg_steps)
         if path is not None:
-            path[steps[i] // path_stride + 1:, i] = pos
-    out = {"arrival": arrival, "reached": reached, "steps": steps, "reward_sum": reward_sum, "final_distance": final_distance,
-           "trace": None, "persistent": None}
+            path[ran // path_stride + 1:, i] = pos
+    st.step0 = step0 + max_steps
+    out = {"arrival": st.arrival.astype(np.int64), "reached": st.reached, "steps": st.robot[:, 1].astype(np.int64),
+           "reward_sum": st.robot[:, 0].copy(), "final_distance": final_distance, "trace": None, "persistent": None,
+           "state": st, "status": st.status.copy()}
     if hazards is not None:
-        out.update({"cost_sum": cost_sum, "violation_steps": viol, "first_violation": first, "min_clearance": min_clear})
+        out.update({"cost_sum": st.hazard[:, 0].copy(), "violation_steps": st.hazard[:, 1].astype(np.int64),
+                    "first_violation": st.hazard[:, 2].astype(np.int64), "min_clearance": st.hazard[:, 3].copy()})
     if path is not None:
         out["path"] = path
     return out
 
 
-def follow_waypoints(model, env, start, waypoints, n_waypoints=None, *, max_steps=1000, deterministic=True, seed=0,
-                     path_stride=0, hazards=None):
+def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *, max_steps=1000, deterministic=True, seed=0,
+                     path_stride=0, hazards=None, state=None, leg_steps=0):
     """Every robot i follows waypoints[i][:n_waypoints[i]] from start[i] under `model` (a PPO, or for the host path anything
     with `.predict`).  `env`: a DeviceGoalVecEnv (device path), an EnvWrapper, or an env name for `get_env` (host path; a
     fresh environment per robot for a name, the given one reused robot after robot otherwise).  Returns the dict described in
-    the module docstring.  hazards: a goal_rules.Hazards (hazard costs, see the module docstring)."""
+    the module docstring.  hazards: a goal_rules.Hazards (hazard costs, see the module docstring).
+    state: the `state` a previous call returned -- this call continues that run (start / waypoints / n_waypoints must then be
+    None: the robots are where they were, on the waypoints the state holds).  leg_steps: step budget per waypoint (0: none)."""
     from .envs.vec_env import DeviceGoalVecEnv
     from .envs.wrapper import EnvWrapper, TimeLimit, get_env
     max_steps, path_stride = int(max_steps), int(path_stride)
     if max_steps < 1 or path_stride < 0:
         raise ValueError("max_steps must be >= 1 and path_stride >= 0")
+    if state is not None and not (start is None and waypoints is None and n_waypoints is None):
+        raise ValueError("a resumed call takes its robots and waypoints from `state` (new waypoints: state.replan)")
+    if state is None and (start is None or waypoints is None):
+        raise ValueError("start and waypoints are needed unless `state` continues a run")
     if isinstance(env, DeviceGoalVecEnv):
-        return env.follow(getattr(model, "engine", model), start, waypoints, n_waypoints, max_steps=max_steps,
-                          deterministic=deterministic, seed=seed, path_stride=path_stride, hazards=hazards)
+        if state is None:
+            state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim)
+        _check_run(state, leg_steps, max_steps, hazards)
+        return env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
+                          path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps)
     if isinstance(env, str):
         name = env
 
@@ -156,5 +292,37 @@ def follow_waypoints(model, env, start, waypoints, n_waypoints=None, *, max_step
 
         def make_env(i):
             return env
-    s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
-    return _host_follow(model, make_env, s, wp, nw, max_steps, deterministic, seed, path_stride, hazards)
+    if state is None:
+        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim)
+    elif isinstance(state, FollowState) and state.waypoints.shape[2] != pos_dim:
+        raise ValueError(f"state has {state.waypoints.shape[2]} position dimensions, the environment {pos_dim}")
+    leg_steps = _check_run(state, leg_steps, max_steps, hazards)
+    return _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps)
+
+
+def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, rounds, leg_steps=0, n_waypoints=None,
+                           deterministic=True, seed=0, hazards=None):
+    """A planner's loop around the tracker: `rounds` calls of `horizon` steps each, one run (see the module docstring).  After
+    every round but the last, `planner(positions [n][P], status [n], reached [n])` returns {robot index: new waypoints [k][P]}
+    (or None / {} for no change), applied through FollowState.replan.  The loop ends early once no robot is going or stalled
+    and the planner changes nothing.  Returns the last call's dict plus `round_status` [rounds run][n]."""
+    horizon, rounds = int(horizon), int(rounds)
+    if horizon < 1 or rounds < 1:
+        raise ValueError("horizon and rounds must be >= 1")
+    out, state, statuses = None, None, []
+    for r in range(rounds):
+        first = state is None
+        out = follow_waypoints(model, env, start if first else None, waypoints if first else None, n_waypoints if first else None,
+                               max_steps=horizon, deterministic=deterministic, seed=seed, hazards=hazards, state=state,
+                               leg_steps=leg_steps)
+        state = out["state"]
+        statuses.append(out["status"].copy())
+        if r + 1 == rounds:
+            break
+        plan = planner(np.array(state.positions), out["status"].copy(), out["reached"].copy()) or {}
+        for robot, w in plan.items():
+            state.replan([int(robot)], np.asarray(w, np.float64)[None])
+        if not plan and not np.any((out["status"] == GOING) | (out["status"] == STALLED)):
+            break
+    out["round_status"] = np.stack(statuses)
+    return out
