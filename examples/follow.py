@@ -17,6 +17,10 @@ robots that reached it (nan if none did).
 coefficient 1) and three more lines: the mean cost per robot, the violation rate (robots that entered a hazard) and the minimum
 clearance (distance to the nearest hazard boundary) over all robots and steps.
 
+`--hazard-frames FILE.npy` ([F][M][3]: x, y, radius of M hazards in F frames) makes the hazards move instead: frame
+min(g // N, F - 1) is in force at step g with `--frame-steps N` (default 1), frame (g // N) % F with `--hazard-loop`.  It
+replaces --hazards / --hazard-size, reports the same three lines and works with --horizon / --leg-steps (g is the run's step).
+
 `--horizon H` runs the same job the way a planner would drive it: a chain of calls of H steps each (the last one shorter if H
 does not divide --max-steps), every call continuing from the state the previous one returned.  The report is exactly the single
 call's.  `--leg-steps B` gives every waypoint a budget of B steps: a robot that has spent it without arriving stalls (and would
@@ -47,11 +51,11 @@ def check_chain(max_steps, horizon, leg_steps):
 
 
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
-           horizon=None, leg_steps=0):
+           horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False):
     calls = check_chain(max_steps, horizon, leg_steps)
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
-    from mobrob_amd.envs.goal_rules import Hazards
+    from mobrob_amd.envs.goal_rules import Hazards, MovingHazards
     from mobrob_amd.envs.wrapper import ROBOT_DIMS, KinematicSim
     from mobrob_amd.waypoints import follow_waypoints
     policy = load_policy(env_name, policy_name) if policy is None else policy
@@ -60,6 +64,13 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     start = np.random.default_rng(seed).uniform(-extent / 2, extent / 2, (int(robots), p))   # the env's init_space
     env = env_name if host else DeviceGoalVecEnv.for_robot(env_name, int(robots), time_limit=0, seed=seed)
     hz = None if hazards is None else Hazards(hazards[0], hazards[1], indicator=False)
+    if hazard_frames is not None:
+        if hazards is not None:
+            raise ValueError("--hazards and --hazard-frames exclude each other")
+        fr = np.asarray(hazard_frames, np.float64)
+        if fr.ndim != 3 or fr.shape[2] != 3:
+            raise ValueError(f"--hazard-frames must hold [F][M][3] (x, y, radius), got shape {fr.shape}")
+        hz = MovingHazards(fr[:, :, :2], fr[None, :, :, 2], frame_steps=int(frame_steps), loop=bool(hazard_loop), indicator=False)
     r = follow_waypoints(policy, env, start, waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
                          leg_steps=leg_steps)
     for steps in calls[1:]:                                # the run, continued call after call
@@ -96,6 +107,9 @@ if __name__ == "__main__":
     ap.add_argument("--host", action="store_true", default=False, help="the Python loop over get_env instead of one device call")
     ap.add_argument("--hazards", type=str, default=None, help="[M][2] hazard centres (.npy): report hazard costs")
     ap.add_argument("--hazard-size", type=float, default=0.3, help="hazard radius (hazards_size)")
+    ap.add_argument("--hazard-frames", type=str, default=None, help="[F][M][3] x, y, radius per frame (.npy): moving hazards")
+    ap.add_argument("--frame-steps", type=int, default=1, help="steps per hazard frame")
+    ap.add_argument("--hazard-loop", action="store_true", default=False, help="start over after the last frame (else hold it)")
     ap.add_argument("--horizon", type=int, default=None, help="run as a chain of calls of this many steps (a planner's rounds)")
     ap.add_argument("--leg-steps", type=int, default=0, help="step budget per waypoint; a robot that spends it stalls (0: none)")
     args = ap.parse_args()
@@ -105,4 +119,5 @@ if __name__ == "__main__":
         ap.error(str(ex))
     follow(args.env_name, args.policy_name, np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed,
            hazards=None if args.hazards is None else (np.load(args.hazards), args.hazard_size), horizon=args.horizon,
-           leg_steps=args.leg_steps)
+           leg_steps=args.leg_steps, hazard_frames=None if args.hazard_frames is None else np.load(args.hazard_frames),
+           frame_steps=args.frame_steps, hazard_loop=args.hazard_loop)

@@ -594,6 +594,50 @@ int mobrob_ppo_follow_waypoints_resume(mobrob_ppo_engine_t* e, const mobrob_goal
                                        double* hazard_out /* [n][4] in / out, NULL iff hz is */, float* path_out /* or NULL */,
                                        float* trace_out /* or NULL */);
 
+/* ---- moving hazards: time-indexed hazard frames on evaluation and waypoint following --------------------------------------------
+ * The hazards of mobrob_hazards_t with a time axis: every scene is n_frames FRAMES of max_hazards rows, hazards
+ * [S][n_frames][M][3].  The check after a robot's step with 0-based GLOBAL step number g (rule, sums, trace columns, hazard_out,
+ * episode_cost_out exactly as for the *_hazards calls) reads the frame
+ *     f(g) = min(g / frame_steps, n_frames - 1)   (loop = 0: hold the last frame)     f(g) = (g / frame_steps) % n_frames  (loop = 1)
+ * with g = step0 + t in a waypoint-following run (t: the call's step; step0 = 0 without `resume`) and g = t in an evaluation (the
+ * clock is the call's: an episode reset does not reset it).  Frames are piecewise constant, nothing is interpolated; n_hazards is
+ * per scene, the same in every frame.  n_frames = 1 gives the bits of the *_hazards call on the same scene in every output.
+ * mobrob_ppo_follow_waypoints_hazard_frames is mobrob_ppo_follow_waypoints_hazards when resume is NULL (start given, arrival /
+ * robot_out / hazard_out out only) and one call of a run with hazards as mobrob_ppo_follow_waypoints_resume when it is not (start
+ * ignored): the invariants of a run hold with frames, since f depends on the global step alone.
+ *   kernels   k_goal64_tile<DP, FrameHazardTask<...>>: one frame of a shared scene resident in LDS, replaced by all 64 lanes when
+ *             f changes; per-robot scenes and the per-step path (k_goal_task_step<FrameHazardTask<...>>) read the frame from
+ *             global memory.
+ * MOBROB_ERR_INVALID before any launch or copy, besides every check of the counterpart (those of mobrob_hazards_t on every
+ * frame included), for: n_frames < 1, frame_steps < 1, a table of n_scenes * n_frames * max_hazards * 12 bytes above
+ * MOBROB_HAZARD_FRAMES_MAX_BYTES. */
+#define MOBROB_HAZARD_FRAMES_MAX_BYTES (64u << 20)
+typedef struct mobrob_hazard_frames {
+  int32_t n_scenes;          /* S >= 1                                                        */
+  int32_t max_hazards;       /* M, row stride, 0 .. 1024                                      */
+  const float* hazards;      /* [S][n_frames][M][3]: x, y, radius (radius >= 0, finite)       */
+  const int32_t* n_hazards;  /* [S] counts 0 .. M (every frame of the scene), or NULL = M     */
+  const int32_t* scene;      /* [n_robots] scene of each robot, or NULL (needs S == 1)        */
+  float cost;                /* hazards_cost, >= 0                                            */
+  int32_t indicator;         /* constrain_indicator                                           */
+  int32_t n_frames;          /* F >= 1                                                        */
+  int32_t frame_steps;       /* steps per frame, >= 1                                         */
+  int32_t loop;              /* after the last frame: 0 hold it, 1 start over                 */
+} mobrob_hazard_frames_t;
+int mobrob_ppo_evaluate_goal_env_hazard_frames(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                                               const mobrob_hazard_frames_t* hz, const int32_t* quota /* [n_robots] or NULL */,
+                                               double* robot_out /* [n_robots][4] */, double* episode_out /* or NULL */,
+                                               double* hazard_out /* [n_robots][4] */, double* episode_cost_out /* or NULL */,
+                                               float* trace_out /* or NULL */);
+int mobrob_ppo_follow_waypoints_hazard_frames(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                              const mobrob_hazard_frames_t* hz, const mobrob_follow_resume_t* resume /* or NULL */,
+                                              const float* start /* [n][pos_dim]; unused with resume */,
+                                              const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                              int32_t* arrival /* [n][K] (in / out with resume) */,
+                                              double* robot_out /* [n][4] (in / out with resume) */,
+                                              double* hazard_out /* [n][4] (in / out with resume) */, float* path_out /* or NULL */,
+                                              float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

@@ -77,6 +77,10 @@ class HazardsC(C.Structure):  # mobrob_hazards_t
                 ("indicator", C.c_int32)]
 
 
+class HazardFramesC(C.Structure):  # mobrob_hazard_frames_t
+    _fields_ = HazardsC._fields_ + [("n_frames", C.c_int32), ("frame_steps", C.c_int32), ("loop", C.c_int32)]
+
+
 class FollowResume(C.Structure):  # mobrob_follow_resume_t
     _fields_ = [("step0", C.c_int32), ("leg_steps", C.c_int32), ("state", C.POINTER(C.c_float)),
                 ("leg_used", C.POINTER(C.c_int32)), ("status", C.POINTER(C.c_int32))]
@@ -154,6 +158,12 @@ SYMBOLS = {
     "mobrob_ppo_follow_waypoints_resume": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), C.POINTER(HazardsC),
                                                      C.POINTER(FollowResume), _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                      C.POINTER(C.c_double), C.POINTER(C.c_double), _F, _F]),
+    "mobrob_ppo_evaluate_goal_env_hazard_frames": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(EvalSpec), C.POINTER(HazardFramesC),
+                                                             C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                             C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
+    "mobrob_ppo_follow_waypoints_hazard_frames": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), C.POINTER(HazardFramesC),
+                                                            C.POINTER(FollowResume), _F, _F, C.POINTER(C.c_int32),
+                                                            C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), _F, _F]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

@@ -3316,15 +3316,30 @@ struct HazardIO {
   const mobrob_hazards_t* hz;
   double* hazard_out;         // [N][4]
   double* episode_cost_out;   // [N][max quota] or null (evaluate)
+  // the *_hazard_frames entry points: hz->hazards is [S][F][M][3].  frames = 0: a static scene, its own single frame
+  int frames = 0, F = 1, frame_steps = 1, loop = 0;
 };
+// the static fields of a mobrob_hazard_frames_t as a mobrob_hazards_t, and its time axis
+static HazardIO hazard_frames_io(const mobrob_hazard_frames_t* hf, mobrob_hazards_t& view, double* hazard_out, double* episode_cost_out) {
+  view = mobrob_hazards_t{hf->n_scenes, hf->max_hazards, hf->hazards, hf->n_hazards, hf->scene, hf->cost, hf->indicator};
+  return HazardIO{&view, hazard_out, episode_cost_out, 1, hf->n_frames, hf->frame_steps, hf->loop != 0};
+}
 struct HazardCarve {
   size_t hz, nhz, scene, out, acc;
   std::vector<int32_t> counts;   // [S], n_hazards or M each
 };
-static int hazard_check(const mobrob_hazards_t* hz, int N, const char* who, std::vector<int32_t>& counts) {
-  const int S = hz->n_scenes, M = hz->max_hazards;
+static int hazard_check(const HazardIO& hio, int N, const char* who, std::vector<int32_t>& counts) {
+  const mobrob_hazards_t* hz = hio.hz;
+  const int S = hz->n_scenes, M = hz->max_hazards, F = hio.F;
   if (S < 1) return fail(MOBROB_ERR_INVALID, "%s: hazards: n_scenes must be >= 1", who);
   if (M < 0 || M > kHazardMax) return fail(MOBROB_ERR_INVALID, "%s: hazards: max_hazards must lie in 0 .. %d", who, kHazardMax);
+  if (hio.frames) {
+    if (F < 1) return fail(MOBROB_ERR_INVALID, "%s: hazard frames: n_frames must be >= 1", who);
+    if (hio.frame_steps < 1) return fail(MOBROB_ERR_INVALID, "%s: hazard frames: frame_steps must be >= 1", who);
+    if ((uint64_t)S * (uint64_t)F * (uint64_t)M * 12u > MOBROB_HAZARD_FRAMES_MAX_BYTES)
+      return fail(MOBROB_ERR_INVALID, "%s: hazard frames: %d scenes x %d frames x %d hazards x 12 bytes exceed the cap of %u bytes (64 MiB)",
+                  who, S, F, M, (unsigned)MOBROB_HAZARD_FRAMES_MAX_BYTES);
+  }
   if (M > 0 && !hz->hazards) return fail(MOBROB_ERR_INVALID, "%s: hazards: null hazard table", who);
   if (!hz->scene && S > 1) return fail(MOBROB_ERR_INVALID, "%s: hazards: %d scenes need a scene index per robot", who, S);
   if (!(std::isfinite(hz->cost) && hz->cost >= 0.f)) return fail(MOBROB_ERR_INVALID, "%s: hazards: cost must be finite and >= 0", who);
@@ -3333,10 +3348,12 @@ static int hazard_check(const mobrob_hazards_t* hz, int N, const char* who, std:
     if (hz->n_hazards) counts[s] = hz->n_hazards[s];
     if (counts[s] < 0 || counts[s] > M)
       return fail(MOBROB_ERR_INVALID, "%s: hazards: n_hazards[%d] = %d outside 0 .. %d", who, s, counts[s], M);
-    for (int i = 0; i < counts[s]; ++i) {
-      const float* h = hz->hazards + ((size_t)s * M + i) * 3;
+    for (size_t i = 0; i < (size_t)F * M; ++i) {   // every frame's rows in use
+      if ((int)(i % M) >= counts[s]) continue;
+      const float* h = hz->hazards + ((size_t)s * F * M + i) * 3;
       if (!(std::isfinite(h[0]) && std::isfinite(h[1]) && std::isfinite(h[2]) && h[2] >= 0.f))
-        return fail(MOBROB_ERR_INVALID, "%s: hazards: hazard %d of scene %d is not finite or has a negative radius", who, i, s);
+        return fail(MOBROB_ERR_INVALID, "%s: hazards: hazard %d of scene %d (frame %d) is not finite or has a negative radius", who,
+                    (int)(i % M), s, (int)(i / M));
     }
   }
   if (hz->scene)
@@ -3345,8 +3362,9 @@ static int hazard_check(const mobrob_hazards_t* hz, int N, const char* who, std:
         return fail(MOBROB_ERR_INVALID, "%s: hazards: scene[%d] = %d outside 0 .. %d", who, i, hz->scene[i], S - 1);
   return MOBROB_OK;
 }
-static void hazard_carve(EvalCarve& carve, const mobrob_hazards_t* hz, int N, HazardCarve& hc) {
-  hc.hz = carve.add(std::max<size_t>((size_t)hz->n_scenes * hz->max_hazards * 3, 1) * 4);
+static void hazard_carve(EvalCarve& carve, const HazardIO& hio, int N, HazardCarve& hc) {
+  const mobrob_hazards_t* hz = hio.hz;
+  hc.hz = carve.add(std::max<size_t>((size_t)hz->n_scenes * hio.F * hz->max_hazards * 3, 1) * 4);
   hc.nhz = carve.add((size_t)hz->n_scenes * 4);
   hc.scene = carve.add((size_t)N * 4);
   hc.out = carve.add((size_t)N * 4 * 8);
@@ -3354,8 +3372,9 @@ static void hazard_carve(EvalCarve& carve, const mobrob_hazards_t* hz, int N, Ha
 }
 // the hazard fields of `h` (after eval_prepare grew eval_buf); hazard_out is written by the task itself
 template <class BaseArgs>
-static int hazard_fill(mobrob_ppo_engine_t* e, const mobrob_hazards_t* hz, int N, const HazardCarve& hc, HazardArgs<BaseArgs>& h) {
-  const size_t nf = (size_t)hz->n_scenes * hz->max_hazards * 3;
+static int hazard_fill(mobrob_ppo_engine_t* e, const HazardIO& hio, int N, const HazardCarve& hc, HazardArgs<BaseArgs>& h) {
+  const mobrob_hazards_t* hz = hio.hz;
+  const size_t nf = (size_t)hz->n_scenes * hio.F * hz->max_hazards * 3;
   h.hz = eval_at<float>(e, hc.hz);
   h.nhz = eval_at<int>(e, hc.nhz);
   h.scene = hz->scene ? eval_at<int>(e, hc.scene) : nullptr;
@@ -3369,6 +3388,11 @@ static int hazard_fill(mobrob_ppo_engine_t* e, const mobrob_hazards_t* hz, int N
   HIPC(hipMemcpyAsync(const_cast<int*>(h.nhz), hc.counts.data(), (size_t)hz->n_scenes * 4, hipMemcpyHostToDevice, e->stream));
   if (hz->scene) HIPC(hipMemcpyAsync(const_cast<int*>(h.scene), hz->scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
   return MOBROB_OK;
+}
+// the time axis of the frames task around the filled static arguments
+template <class BaseArgs>
+static void hazard_fill_frames(const HazardIO& hio, FrameHazardArgs<BaseArgs>& hf) {
+  hf.F = hio.F; hf.frame_steps = hio.frame_steps; hf.loop = hio.loop;
 }
 }  // extern "C++"
 
@@ -3396,15 +3420,16 @@ static int evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* en
   }
   HazardCarve hc;
   if (hio)
-    if (const int rc = hazard_check(hio->hz, N, c.who, hc.counts)) return rc;
+    if (const int rc = hazard_check(*hio, N, c.who, hc.counts)) return rc;
   EvalCarve carve;
   const size_t o_ep = carve.add(std::max<size_t>((size_t)N * maxq * 3, 1) * 8), o_q = carve.add((size_t)N * 4), o_er = carve.add((size_t)N * 8);
   size_t o_ec = 0;
   if (hio) {
-    hazard_carve(carve, hio->hz, N, hc);
+    hazard_carve(carve, *hio, N, hc);
     o_ec = carve.add(std::max<size_t>((size_t)N * maxq, 1) * 8);
   }
-  HazardArgs<EvalArgs> h{};
+  FrameHazardArgs<EvalArgs> hf{};   // the frames task's arguments: its HazardArgs / EvalArgs are the ones filled below
+  HazardArgs<EvalArgs>& h = hf.h;
   EvalArgs& a = h.b;
   const GoalEnvParams p = eval_env_params(env, e->A, env->terminate_on_goal != 0, env->time_limit > 0 ? env->time_limit : INT_MAX);   // control.py: no limit
   if (const int rc = eval_prepare(e, c, p, carve, a)) return rc;
@@ -3418,11 +3443,13 @@ static int evaluate_goal_env(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* en
   HIPC(hipMemcpyAsync(q_dev, q.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
   if (maxq > 0) HIPC(hipMemsetAsync(a.ep_out, 0, (size_t)N * maxq * 3 * 8, e->stream));
   if (hio) {
-    if (const int rc = hazard_fill(e, hio->hz, N, hc, h)) return rc;
+    if (const int rc = hazard_fill(e, *hio, N, hc, h)) return rc;
+    hazard_fill_frames(*hio, hf);
     h.ep_cost = eval_at<double>(e, o_ec);
     if (maxq > 0) HIPC(hipMemsetAsync(h.ep_cost, 0, (size_t)N * maxq * 8, e->stream));
   }
-  const int ran = hio ? eval_run<HazardEvalTask>(e, h, nullptr) : eval_run<EvalTask>(e, a, nullptr);
+  const int ran = !hio ? eval_run<EvalTask>(e, a, nullptr)
+                  : hio->frames ? eval_run<FrameHazardTask<EvalTask>>(e, hf, nullptr) : eval_run<HazardEvalTask>(e, h, nullptr);
   if (ran < 0) return ran;
   if (episode_out && maxq > 0)
     HIPC(hipMemcpyAsync(episode_out, a.ep_out, (size_t)N * maxq * 3 * 8, hipMemcpyDeviceToHost, e->stream));
@@ -3444,6 +3471,15 @@ int mobrob_ppo_evaluate_goal_env_hazards(mobrob_ppo_engine_t* e, const mobrob_go
                                          double* hazard_out, double* episode_cost_out, float* trace_out) {
   if (!hz || !hazard_out) return fail(MOBROB_ERR_INVALID, "evaluate: null argument");
   const HazardIO hio{hz, hazard_out, episode_cost_out};
+  return evaluate_goal_env(e, env, spec, quota, robot_out, episode_out, trace_out, &hio);
+}
+
+int mobrob_ppo_evaluate_goal_env_hazard_frames(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_eval_spec_t* spec,
+                                               const mobrob_hazard_frames_t* hz, const int32_t* quota, double* robot_out,
+                                               double* episode_out, double* hazard_out, double* episode_cost_out, float* trace_out) {
+  if (!hz || !hazard_out) return fail(MOBROB_ERR_INVALID, "evaluate: null argument");
+  mobrob_hazards_t view;
+  const HazardIO hio = hazard_frames_io(hz, view, hazard_out, episode_cost_out);
   return evaluate_goal_env(e, env, spec, quota, robot_out, episode_out, trace_out, &hio);
 }
 
@@ -3509,7 +3545,7 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   }
   HazardCarve hc;
   if (hio)
-    if (const int rc = hazard_check(hio->hz, N, c.who, hc.counts)) return rc;
+    if (const int rc = hazard_check(*hio, N, c.who, hc.counts)) return rc;
   if (rs)
     if (const int rc = follow_resume_check(rs, spec, nw, robot_out, hio ? hio->hazard_out : nullptr)) return rc;
   const bool pathing = path_out && spec->path_stride > 0;
@@ -3517,11 +3553,13 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   EvalCarve carve;
   const size_t o_arr = carve.add((size_t)N * K * 4), o_start = carve.add((size_t)N * P * 4), o_wp = carve.add((size_t)N * K * P * 4),
                o_nw = carve.add((size_t)N * 4), o_path = carve.add(std::max<size_t>(n_rec * N * P, 1) * 4);
-  if (hio) hazard_carve(carve, hio->hz, N, hc);
+  if (hio) hazard_carve(carve, *hio, N, hc);
   const size_t o_state = carve.add(rs ? (size_t)N * 6 * 4 : 0), o_leg = carve.add(rs ? (size_t)N * 4 : 0),
                o_status = carve.add(rs ? (size_t)N * 4 : 0), o_entry = carve.add(rs ? (size_t)N * 4 : 0);
-  HazardArgs<FollowArgs> h{};
-  HazardArgs<ResumeArgs> hr{};   // the resumable task's arguments: its FollowArgs is the one filled below
+  FrameHazardArgs<FollowArgs> hf{};    // the frames tasks' arguments hold the static tasks'
+  FrameHazardArgs<ResumeArgs> hrf{};
+  HazardArgs<FollowArgs>& h = hf.h;
+  HazardArgs<ResumeArgs>& hr = hrf.h;   // the resumable task's arguments: its FollowArgs is the one filled below
   FollowArgs& f = rs ? hr.b.f : h.b;
   // no termination, no time limit: the robot only stops at its last waypoint
   if (const int rc = eval_prepare(e, c, eval_env_params(env, e->A, false, INT_MAX), carve, f.e)) return rc;
@@ -3540,10 +3578,14 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   double* hazard_dev = nullptr;
   if (!rs) {
     HIPC(hipMemsetAsync(f.arrival, 0xFF, (size_t)N * K * 4, e->stream));   // -1: not reached
-    if (hio)
-      if (const int rc = hazard_fill(e, hio->hz, N, hc, h)) return rc;
+    if (hio) {
+      if (const int rc = hazard_fill(e, *hio, N, hc, h)) return rc;
+      hazard_fill_frames(*hio, hf);
+    }
     hazard_dev = h.hazard_out;
-    ran = hio ? eval_run<HazardFollowTask>(e, h, k_hazard_follow_fin) : eval_run<FollowTask>(e, f, k_follow_goal_fin);
+    ran = !hio ? eval_run<FollowTask>(e, f, k_follow_goal_fin)
+          : hio->frames ? eval_run<FrameHazardTask<FollowTask>>(e, hf, k_goal_task_fin<FrameHazardTask<FollowTask>>)
+                        : eval_run<HazardFollowTask>(e, h, k_hazard_follow_fin);
   } else {
     // the run so far: arrival rows, accumulators, state
     ResumeArgs& r = hr.b;
@@ -3555,12 +3597,14 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     HIPC(hipMemcpyAsync(r.state, rs->state, (size_t)N * 6 * 4, hipMemcpyHostToDevice, e->stream));
     HIPC(hipMemcpyAsync(r.leg_used, rs->leg_used, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
     if (hio) {
-      if (const int rc = hazard_fill(e, hio->hz, N, hc, hr)) return rc;
+      if (const int rc = hazard_fill(e, *hio, N, hc, hr)) return rc;
+      hazard_fill_frames(*hio, hrf);
       HIPC(hipMemcpyAsync(hr.hazard_out, hio->hazard_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
     }
     hazard_dev = hr.hazard_out;
-    ran = hio ? eval_run<HazardTask<ResumeFollowTask>>(e, hr, k_goal_task_fin<HazardTask<ResumeFollowTask>>)
-              : eval_run<ResumeFollowTask>(e, r, k_goal_task_fin<ResumeFollowTask>);
+    ran = !hio ? eval_run<ResumeFollowTask>(e, r, k_goal_task_fin<ResumeFollowTask>)
+          : hio->frames ? eval_run<FrameHazardTask<ResumeFollowTask>>(e, hrf, k_goal_task_fin<FrameHazardTask<ResumeFollowTask>>)
+                        : eval_run<HazardTask<ResumeFollowTask>>(e, hr, k_goal_task_fin<HazardTask<ResumeFollowTask>>);
     if (ran >= 0) {
       HIPC(hipMemcpyAsync(rs->state, r.state, (size_t)N * 6 * 4, hipMemcpyDeviceToHost, e->stream));
       HIPC(hipMemcpyAsync(rs->leg_used, r.leg_used, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
@@ -3597,6 +3641,17 @@ int mobrob_ppo_follow_waypoints_resume(mobrob_ppo_engine_t* e, const mobrob_goal
   const HazardIO hio{hz, hazard_out, nullptr};
   return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
                           hz ? &hio : nullptr, resume);
+}
+
+int mobrob_ppo_follow_waypoints_hazard_frames(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                              const mobrob_hazard_frames_t* hz, const mobrob_follow_resume_t* resume, const float* start,
+                                              const float* waypoints, const int32_t* n_waypoints, int32_t* arrival, double* robot_out,
+                                              double* hazard_out, float* path_out, float* trace_out) {
+  if (!hz || !hazard_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
+  mobrob_hazards_t view;
+  const HazardIO hio = hazard_frames_io(hz, view, hazard_out, nullptr);
+  return follow_waypoints(e, env, spec, resume ? nullptr : start, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out, &hio,
+                          resume);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

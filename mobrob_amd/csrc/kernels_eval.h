@@ -149,6 +149,7 @@ struct EvalTask {
   }
   static constexpr bool kWide = false;   // k_goal64_tile: step runs on the robot's lane only
   static constexpr bool kResume = false;   // the launch's step 0 is the streams' step 0 (task_step0 below)
+  static constexpr bool kFrames = false;   // k_goal64_tile: nothing to restage between steps (kernels_hazard.h: FrameHazardTask)
   static __device__ __forceinline__ bool active(const Args& a, const Robot& R) { return a.episodes == 0 || R.eps < R.quota; }
   // XT / post: for a wrapping task (kernels_hazard.h): trace row width + XT, the post-step x, y
   template <int XT = 0>
@@ -388,8 +389,19 @@ __global__ __launch_bounds__(64) void k_goal64_tile(typename Task::Args args, Ev
   __syncthreads();
   const bool wide_head = a.A > 16;
   const int g0 = task_step0<Task>(args);   // t: step of this launch (trace, path); g0 + t: step of the streams
+  [[maybe_unused]] int staged = 0;         // kFrames: the frame of the shared scene resident in LDS (Task::stage: the first used)
+  if constexpr (Task::kFrames) staged = Task::frame(args, g0);
   for (int t = 0; t < a.max_steps; ++t) {
     if (__ballot(active) == 0ull) break;   // one wave per workgroup: uniform
+    if constexpr (Task::kFrames) {
+      // a new frame (uniform: it depends on g0 + t alone) replaces the resident one before the env phase; the previous step's
+      // reads ended at its closing barrier, and the actor step's barriers stand between these writes and after_step's reads
+      const int f = Task::frame(args, g0 + t);
+      if (f != staged) {
+        Task::stage_frame(args, &lds[L::END + 32], lane, f);
+        staged = f;
+      }
+    }
     eval64_actor_step<DP>(a, row0, g0 + t, lane, wide_head);
     if constexpr (Task::kWide) {
       // ---- env phase on the tile's 16 lanes, then the task's wide phase on all 64 (robot lane & 15 stepped: bit of `stepping`) ----

@@ -125,6 +125,7 @@ struct FollowTask {
   static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& f, int n) { follow_start(g, R, f, n); }
   static constexpr bool kWide = false;
   static constexpr bool kResume = false;
+  static constexpr bool kFrames = false;
   static __device__ __forceinline__ bool active(const Args&, const Robot& R) { return R.k < R.nwp; }
   template <int XT = 0>
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& f, int n, int t, const float* act,
@@ -170,6 +171,7 @@ struct ResumeFollowTask {
   using Robot = ResumeRobot;
   static constexpr bool kWide = false;
   static constexpr bool kResume = true;
+  static constexpr bool kFrames = false;
   static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& a) { return a.f.e; }
   static __device__ __forceinline__ int step0(const Args& a) { return a.step0; }
   // the carried robot: pose and velocity from `state`, accumulators from robot_out, goal = the waypoint in force (a finished

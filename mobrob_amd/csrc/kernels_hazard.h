@@ -63,16 +63,18 @@ struct HazardTask {
   };
   static constexpr bool kWide = true;   // k_goal64_tile: the check runs on all 64 lanes (step_lane + after_step below)
   static constexpr bool kResume = Base::kResume;   // a resumable base: accumulators continue from hazard_out, global steps
+  static constexpr bool kFrames = false;           // one scene for the whole run (FrameHazardTask below: a frame per step)
   static __device__ __forceinline__ int step0(const Args& h) { return task_step0<Base>(h.b); }
 
   static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& h) { return Base::eval(h.b); }
   // LDS of k_goal64_tile beyond LayEval64::END: [16][2] post-step positions, then a shared scene
   static size_t tile_lds_bytes(const Args& h) { return (size_t)(32 + (h.scene ? 0 : 3 * h.M)) * sizeof(float); }
 
-  static __device__ __forceinline__ const float* scene_of(const Args& h, int n, int& count) {
+  // F, f (here and below): frames per scene and the frame in force (FrameHazardTask); a static scene is its only frame
+  static __device__ __forceinline__ const float* scene_of(const Args& h, int n, int& count, int F = 1, int f = 0) {
     const int s = h.scene ? h.scene[n] : 0;
     count = h.nhz[s];
-    return h.hz + (size_t)s * h.M * 3;
+    return h.hz + ((size_t)s * F + f) * h.M * 3;
   }
 
   // the step's cost / clearance -> accumulators, episode record, trace columns.  e0: the base's episodes before the step.
@@ -104,12 +106,12 @@ struct HazardTask {
 
   // the whole step in one thread (per-step path): the four partial sums in turn
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& h, int n, int t, const float* act,
-                                              const float* obs_row) {
+                                              const float* obs_row, int F = 1, int f = 0) {
     float post[2];
     const int e0 = Base::episodes(R.b);
     const bool going = Base::template step<kHazardTraceExtra>(g, R.b, h.b, n, t, act, obs_row, post);
     int m;
-    const float* hs = scene_of(h, n, m);
+    const float* hs = scene_of(h, n, m, F, f);
     float c[4], cl[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) hazard_partial(hs, m, q, post[0], post[1], c[q], cl[q]);
@@ -120,9 +122,9 @@ struct HazardTask {
 
   // ---- k_goal64_tile: Base::step on the robot's lane (post-step position -> LDS), then after_step on all 64 lanes ----
   // hz_lds: the shared scene (scene == null) staged in LDS by `stage`; xy: [16][2] post-step positions in LDS
-  static __device__ __forceinline__ void stage(const Args& h, float* hz_lds, int lane) {
+  static __device__ __forceinline__ void stage(const Args& h, float* hz_lds, int lane, int f = 0) {
     if (!h.scene)
-      for (int i = lane; i < 3 * h.nhz[0]; i += 64) hz_lds[i] = h.hz[i];
+      for (int i = lane; i < 3 * h.nhz[0]; i += 64) hz_lds[i] = h.hz[(size_t)f * h.M * 3 + i];
   }
   static __device__ __forceinline__ bool step_lane(GoalState& g, Robot& R, const Args& h, int n, int t, const float* act,
                                                    const float* obs_row, float* xy, int& e0) {
@@ -131,12 +133,12 @@ struct HazardTask {
   }
   // every lane: quarter q = lane >> 4 of robot r16 = lane & 15 (if it stepped); lane r16 < 16 accounts the combined result
   static __device__ __forceinline__ void after_step(const Args& h, Robot& R, int n, int t, int lane, bool stepped, int e0,
-                                                    const float* xy, const float* hz_lds) {
+                                                    const float* xy, const float* hz_lds, int F = 1, int f = 0) {
     const int r16 = lane & 15, q = lane >> 4;
     float c = 0.f, cl = __builtin_inff();
     if (stepped) {
       int m;
-      const float* hs = scene_of(h, n, m);
+      const float* hs = scene_of(h, n, m, F, f);
       hazard_partial(h.scene ? hs : hz_lds, m, q, xy[2 * r16], xy[2 * r16 + 1], c, cl);
     }
     // lanes r16, r16 + 16, r16 + 32, r16 + 48 hold quarters 0..3: (p0 + p1) + (p2 + p3), the same sum on every one of them
@@ -181,6 +183,65 @@ struct HazardTask {
 
 using HazardEvalTask = HazardTask<EvalTask>;
 using HazardFollowTask = HazardTask<FollowTask>;
+
+// ------------------------------------------------------------------------------------------------
+// Moving hazards (mobrob_ppo_evaluate_goal_env_hazard_frames / mobrob_ppo_follow_waypoints_hazard_frames): every scene is F
+// frames, hz [S][F][M][3], and the check after the step with global number g = task_step0 + t reads the frame
+//   f(g) = min(g / frame_steps, F - 1)  (hold the last frame)   or, with loop,   f(g) = (g / frame_steps) % F
+// (goal_rules.MovingHazards.frame_index).  Frames are piecewise constant: no interpolation, so the check at a frame is exactly
+// the static task's, on the same lanes in the same order.  f depends on g alone, hence it is uniform over a wave.
+// FrameHazardTask<Base> is HazardTask<Base> with that frame chosen per step: accumulators, trace columns, hazard_out, ep_cost
+// are HazardTask's.  k_goal64_tile keeps ONE frame of a shared scene in LDS (tile_lds_bytes is HazardTask's) and restages it
+// when f changes (kFrames); per-robot scenes and the per-step path read the frame from global memory.
+// ------------------------------------------------------------------------------------------------
+template <class BaseArgs>
+struct FrameHazardArgs {
+  HazardArgs<BaseArgs> h;  // h.hz: [S][F][M][3]; every other field as for the static task
+  int F;                   // frames per scene, >= 1
+  int frame_steps;         // steps per frame, >= 1
+  int loop;                // after the last frame: 0 hold it, 1 start over
+};
+
+template <class Base>
+struct FrameHazardTask {
+  using H = HazardTask<Base>;
+  using Args = FrameHazardArgs<typename Base::Args>;
+  using Robot = typename H::Robot;
+  static constexpr bool kWide = true;
+  static constexpr bool kResume = Base::kResume;
+  static constexpr bool kFrames = true;   // k_goal64_tile: restage the shared scene whenever frame(g0 + t) changes
+  static __device__ __forceinline__ int step0(const Args& a) { return H::step0(a.h); }
+  static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& a) { return H::eval(a.h); }
+  static size_t tile_lds_bytes(const Args& a) { return H::tile_lds_bytes(a.h); }   // one frame resident
+
+  // the frame in force at the check after the step with global number g
+  static __device__ __forceinline__ int frame(const Args& a, int g) {
+    const int k = g / a.frame_steps;
+    return a.loop ? k % a.F : min(k, a.F - 1);
+  }
+  static __device__ __forceinline__ int frame_at(const Args& a, int t) { return frame(a, task_step0<Base>(a.h.b) + t); }
+
+  static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& a, int n) { H::start(g, R, a.h, n); }
+  static __device__ __forceinline__ bool active(const Args& a, const Robot& R) { return H::active(a.h, R); }
+  static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
+                                              const float* obs_row) {
+    return H::step(g, R, a.h, n, t, act, obs_row, a.F, frame_at(a, t));
+  }
+  // ---- k_goal64_tile: `stage` before the loop = the first frame used; stage_frame when the frame changes ----
+  static __device__ __forceinline__ void stage_frame(const Args& a, float* hz_lds, int lane, int f) { H::stage(a.h, hz_lds, lane, f); }
+  static __device__ __forceinline__ void stage(const Args& a, float* hz_lds, int lane) { stage_frame(a, hz_lds, lane, frame_at(a, 0)); }
+  static __device__ __forceinline__ bool step_lane(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
+                                                   const float* obs_row, float* xy, int& e0) {
+    return H::step_lane(g, R, a.h, n, t, act, obs_row, xy, e0);
+  }
+  static __device__ __forceinline__ void after_step(const Args& a, Robot& R, int n, int t, int lane, bool stepped, int e0,
+                                                    const float* xy, const float* hz_lds) {
+    H::after_step(a.h, R, n, t, lane, stepped, e0, xy, hz_lds, a.F, frame_at(a, t));
+  }
+  static __device__ __forceinline__ void finish(const Args& a, int n, const Robot& R, const GoalState& g) { H::finish(a.h, n, R, g); }
+  static __device__ __forceinline__ Robot load(const Args& a, int n) { return H::load(a.h, n); }
+  static __device__ __forceinline__ void store(const Args& a, int n, const Robot& R) { H::store(a.h, n, R); }
+};
 
 // robot_out and the path records of robots that finished early (per-step path; hazard_out is current after every step)
 __global__ __launch_bounds__(256) void k_hazard_follow_fin(HazardArgs<FollowArgs> h) {

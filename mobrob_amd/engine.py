@@ -7,7 +7,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from ._lib import BUF, Config, DroneParams, EpisodeStats, EvalSpec, FollowSpec, GoalEnv, HazardsC, TrainStats, check
+from ._lib import BUF, Config, DroneParams, EpisodeStats, EvalSpec, FollowSpec, GoalEnv, HazardFramesC, HazardsC, TrainStats, check
 
 F32 = np.float32
 STAT_KEYS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm")
@@ -351,13 +351,18 @@ class PPOEngine:
 
     @staticmethod
     def _hazards_struct(hazards, n):
-        """mobrob_hazards_t of a goal_rules.Hazards for n robots, and the arrays it points into (kept alive by the caller)."""
-        from .envs.goal_rules import Hazards
-        if not isinstance(hazards, Hazards):
-            raise TypeError(f"hazards must be a mobrob_amd.envs.goal_rules.Hazards, not {type(hazards).__name__}")
+        """mobrob_hazards_t of a goal_rules.Hazards (mobrob_hazard_frames_t of a goal_rules.MovingHazards) for n robots, and the
+        arrays it points into (kept alive by the caller)."""
+        from .envs.goal_rules import Hazards, MovingHazards
+        if not isinstance(hazards, (Hazards, MovingHazards)):
+            raise TypeError(f"hazards must be a mobrob_amd.envs.goal_rules.Hazards or MovingHazards, not {type(hazards).__name__}")
         hazards.check_robots(n)
         keep = (hazards.table, hazards.counts, hazards.scene)
-        h = HazardsC()
+        if isinstance(hazards, MovingHazards):
+            h = HazardFramesC()
+            h.n_frames, h.frame_steps, h.loop = hazards.n_frames, hazards.frame_steps, int(hazards.loop)
+        else:
+            h = HazardsC()
         h.n_scenes, h.max_hazards = hazards.n_scenes, hazards.max_hazards
         h.hazards, h.n_hazards = _fp(hazards.table), hazards.counts.ctypes.data_as(C.POINTER(C.c_int32))
         h.scene = None if hazards.scene is None else hazards.scene.ctypes.data_as(C.POINTER(C.c_int32))
@@ -396,7 +401,8 @@ class PPOEngine:
         episode_success ([n_robots][max quota], NaN past an unfinished quota); trace ([steps][robots][9 + D + A + 4]) and
         `persistent` (which kernel path ran).  hazards: a goal_rules.Hazards -> mobrob_ppo_evaluate_goal_env_hazards, adding
         cost_sum, violation_steps, first_violation, min_clearance ([n_robots]) and episode_cost ([n_robots][max quota], NaN
-        past an unfinished quota); trace rows then end in the step's cost and clearance."""
+        past an unfinished quota); trace rows then end in the step's cost and clearance.  A goal_rules.MovingHazards ->
+        mobrob_ppo_evaluate_goal_env_hazard_frames: the same keys, the check after the call's step t on frame f(t)."""
         n = int(n_robots)
         sp = EvalSpec()
         tr = self._eval_spec_common("evaluate_goal_env", sp, max_steps, deterministic, seed, trace, 0 if hazards is None else 2)
@@ -422,7 +428,9 @@ class PPOEngine:
             h, _keep = self._hazards_struct(hazards, n)
             hz = np.zeros((max(n, 1), 4), np.float64)
             ec = np.zeros((max(n, 1), max(maxq, 1)), np.float64)
-            r = check(self.lib.mobrob_ppo_evaluate_goal_env_hazards(
+            call = (self.lib.mobrob_ppo_evaluate_goal_env_hazard_frames if isinstance(h, HazardFramesC)
+                    else self.lib.mobrob_ppo_evaluate_goal_env_hazards)
+            r = check(call(
                 self._h, C.byref(g), C.byref(sp), C.byref(h), q.ctypes.data_as(C.POINTER(C.c_int32)), robot.ctypes.data_as(dp),
                 ep.ctypes.data_as(dp), hz.ctypes.data_as(dp), ec.ctypes.data_as(dp), _fp(tr)))
         ep = ep[:, :maxq]
@@ -446,7 +454,8 @@ class PPOEngine:
         None = K each), no time limit, no reset.  path_stride > 0 records positions; trace = (robots, steps): teacher-forcing
         trace.  Returns the dict of mobrob_amd.waypoints (arrival, reached, steps, reward_sum, final_distance, path, trace,
         persistent).  hazards: a goal_rules.Hazards -> mobrob_ppo_follow_waypoints_hazards, adding cost_sum, violation_steps,
-        first_violation, min_clearance; trace rows then end in the step's cost and clearance.
+        first_violation, min_clearance; trace rows then end in the step's cost and clearance.  A goal_rules.MovingHazards ->
+        mobrob_ppo_follow_waypoints_hazard_frames (with or without `resume`): the check after global step g on frame f(g).
         resume: a waypoints.FollowState -> mobrob_ppo_follow_waypoints_resume, one call of the run the state is in (start,
         waypoints and n_waypoints must be None: the state holds them); leg_steps: step budget per waypoint (0: none).  With
         `leg_steps` alone the call starts a run.  Such a call adds `state` (the FollowState after the call; the one given is left
@@ -478,9 +487,12 @@ class PPOEngine:
         else:
             h, _keep = self._hazards_struct(hazards, n)
             hz = np.zeros((n, 4), np.float64)
-            r = check(self.lib.mobrob_ppo_follow_waypoints_hazards(
-                self._h, C.byref(g), C.byref(sp), C.byref(h), _fp(s), _fp(wp), nw.ctypes.data_as(i32), arrival.ctypes.data_as(i32),
-                robot.ctypes.data_as(dp), hz.ctypes.data_as(dp), _fp(path), _fp(tr)))
+            tail = (_fp(s), _fp(wp), nw.ctypes.data_as(i32), arrival.ctypes.data_as(i32), robot.ctypes.data_as(dp),
+                    hz.ctypes.data_as(dp), _fp(path), _fp(tr))
+            if isinstance(h, HazardFramesC):
+                r = check(self.lib.mobrob_ppo_follow_waypoints_hazard_frames(self._h, C.byref(g), C.byref(sp), C.byref(h), None, *tail))
+            else:
+                r = check(self.lib.mobrob_ppo_follow_waypoints_hazards(self._h, C.byref(g), C.byref(sp), C.byref(h), *tail))
         out = self._eval_result(robot, r)
         out.update({"arrival": arrival.astype(np.int64), "reached": robot[:, 2].astype(np.int64), "final_distance": robot[:, 3],
                     "trace": tr})
@@ -492,7 +504,8 @@ class PPOEngine:
 
     def _follow_resume(self, pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, state, leg_steps,
                        max_steps, deterministic, seed, path_stride, trace, hazards):
-        """One call of a run (mobrob_ppo_follow_waypoints_resume) on a copy of `state`."""
+        """One call of a run (mobrob_ppo_follow_waypoints_resume; with a MovingHazards mobrob_ppo_follow_waypoints_hazard_frames)
+        on a copy of `state`."""
         from ._lib import FollowResume
         from .waypoints import FollowState
         if not isinstance(state, FollowState):
@@ -523,10 +536,14 @@ class PPOEngine:
         rs.step0, rs.leg_steps = int(st.step0), int(leg_steps)
         rs.state, rs.leg_used, rs.status = _fp(st.state), st.leg_used.ctypes.data_as(i32), st.status.ctypes.data_as(i32)
         h, _keep = (None, None) if hazards is None else self._hazards_struct(hazards, n)
-        r = check(self.lib.mobrob_ppo_follow_waypoints_resume(
-            self._h, C.byref(g), C.byref(sp), None if h is None else C.byref(h), C.byref(rs), _fp(st.waypoints),
-            st.n_waypoints.ctypes.data_as(i32), st.arrival.ctypes.data_as(i32), st.robot.ctypes.data_as(dp),
-            None if h is None else st.hazard.ctypes.data_as(dp), _fp(path), _fp(tr)))
+        tail = (_fp(st.waypoints), st.n_waypoints.ctypes.data_as(i32), st.arrival.ctypes.data_as(i32), st.robot.ctypes.data_as(dp),
+                None if h is None else st.hazard.ctypes.data_as(dp), _fp(path), _fp(tr))
+        if isinstance(h, HazardFramesC):
+            r = check(self.lib.mobrob_ppo_follow_waypoints_hazard_frames(self._h, C.byref(g), C.byref(sp), C.byref(h), C.byref(rs),
+                                                                         None, *tail))
+        else:
+            r = check(self.lib.mobrob_ppo_follow_waypoints_resume(self._h, C.byref(g), C.byref(sp), None if h is None else C.byref(h),
+                                                                  C.byref(rs), *tail))
         st.step0 += int(max_steps)
         out = self._eval_result(st.robot.copy(), r)
         out.update({"arrival": st.arrival.astype(np.int64), "reached": st.reached, "final_distance": st.robot[:, 3].copy(),

@@ -140,3 +140,111 @@ class Hazards:
     def check_robots(self, n):
         if self.scene is not None and self.scene.shape != (n,):
             raise ValueError(f"hazard scene must have {n} entries, one per robot, got {self.scene.shape[0]}")
+
+
+HAZARD_FRAMES_MAX_BYTES = 64 << 20   # cap on a MovingHazards table (S * F * M * 12 bytes); the engine refuses a larger one too
+
+
+class MovingHazards:
+    """Hazards that move: `Hazards` plus a time axis of F piecewise-constant FRAMES.  `locations` [F, M, 2] (one scene) or
+    [S, F, M, 2], `size` a scalar, [M], [S, M] or [S, F, M]; `frame_steps` >= 1 steps per frame; `loop`: wrap around after the
+    last frame instead of holding it; `counts` [S] (constant over the frames), `scene`, `cost`, `indicator` as for `Hazards`.
+    The table is float32 [S, F, M, 3].  Checked on construction (ValueError).
+
+    Time: the check after a robot's step with 0-based GLOBAL step number g uses frame
+        f(g) = min(g // frame_steps, F - 1)   (hold the last frame)        or, with loop,   f(g) = (g // frame_steps) % F.
+    In a waypoint-following run g = step0 + t; in an evaluation g = t, the step of the call (episode resets do not reset the
+    clock).  Cost and clearance at that frame are `hazard_cost` of the frame's rows: nothing is interpolated."""
+
+    def __init__(self, locations, size=HAZARDS_SIZE, frame_steps=1, loop=False, cost=HAZARDS_COST, indicator=True, counts=None,
+                 scene=None):
+        loc = np.asarray(locations, np.float64)
+        if loc.ndim == 3:
+            loc = loc[None]
+        if loc.ndim != 4 or loc.shape[3] != 2:
+            raise ValueError(f"moving hazard locations must be [F, M, 2] or [S, F, M, 2], got shape {np.shape(locations)}")
+        S, F, M = loc.shape[:3]
+        if S < 1:
+            raise ValueError("hazards need at least one scene")
+        if F < 1:
+            raise ValueError("moving hazards need at least one frame")
+        if M > HAZARDS_MAX:
+            raise ValueError(f"at most {HAZARDS_MAX} hazards per scene, got {M}")
+        if S * F * M * 12 > HAZARD_FRAMES_MAX_BYTES:
+            raise ValueError(f"hazard frames of {S} x {F} x {M} x 12 bytes exceed the cap of {HAZARD_FRAMES_MAX_BYTES} bytes "
+                             f"({HAZARD_FRAMES_MAX_BYTES >> 20} MiB)")
+        if isinstance(frame_steps, bool) or not isinstance(frame_steps, (int, np.integer)) or frame_steps < 1:
+            raise ValueError(f"frame_steps must be an integer >= 1, got {frame_steps!r}")
+        if frame_steps > 2 ** 31 - 1:
+            raise ValueError("frame_steps must fit an int32")
+        rad = np.asarray(size, np.float64)
+        if rad.shape not in ((), (M,), (S, M), (S, F, M)):
+            raise ValueError(f"hazard size must be a scalar, [{M}], [{S}, {M}] or [{S}, {F}, {M}], got shape {rad.shape}")
+        rad = np.broadcast_to(rad[:, None, :] if rad.shape == (S, M) else rad, (S, F, M))
+        if not (np.all(np.isfinite(loc)) and np.all(np.isfinite(rad))):
+            raise ValueError("hazard locations and sizes must be finite")
+        if np.any(rad < 0):
+            raise ValueError("hazard sizes must be >= 0")
+        static = Hazards(np.zeros((S, M, 2)), 0.0, cost, indicator, counts, scene)   # cost, counts and scene: Hazards' checks
+        self.table = np.ascontiguousarray(np.concatenate([loc, rad[..., None]], axis=-1), np.float32)   # [S, F, M, 3]
+        self.counts, self.scene, self.cost, self.indicator = static.counts, static.scene, static.cost, static.indicator
+        self.frame_steps, self.loop = int(frame_steps), bool(loop)
+
+    @property
+    def n_scenes(self):
+        return self.table.shape[0]
+
+    @property
+    def n_frames(self):
+        return self.table.shape[1]
+
+    @property
+    def max_hazards(self):
+        return self.table.shape[2]
+
+    def frame_index(self, step):
+        """The frame in force at the check after the step with 0-based global number `step`."""
+        step = int(step)
+        if step < 0:
+            raise ValueError("step must be >= 0")
+        k = step // self.frame_steps
+        return k % self.n_frames if self.loop else min(k, self.n_frames - 1)
+
+    def rows(self, robot=0, step=0):
+        """[m, 3] (x, y, radius) float64 of the hazards robot `robot` sees at the check after global step `step` (the float32
+        values the device uses)."""
+        s = 0 if self.scene is None else int(self.scene[robot])
+        return self.table[s, self.frame_index(step), : self.counts[s]].astype(np.float64)
+
+    check_robots = Hazards.check_robots
+
+    @staticmethod
+    def circling_offsets(travel, n_frames, dt, phase0=0.0):
+        """[n_frames, 2] float64: the reference Engine's gremlin motion (engine.py set_mocaps, gremlins_travel): at simulation
+        time phi the gremlin sits at travel * (sin phi, cos phi); frame j is taken at phi = phase0 + j * dt."""
+        out = np.zeros((int(n_frames), 2))
+        for j in range(int(n_frames)):
+            phase = float(phase0 + j * dt)
+            out[j] = np.array([np.sin(phase), np.cos(phase)]) * travel
+        return out
+
+    @classmethod
+    def circling(cls, centres, travel=0.3, size=0.1, n_frames=1, dt=0.05, phase0=0.0, **kwargs):
+        """Hazards circling as the reference's gremlins do: frame j holds centres + circling_offsets(...)[j], computed in
+        float64 and stored as float32.  centres [M, 2] or [S, M, 2]; travel: the circle's radius (gremlins_travel 0.3), size
+        the hazard radius (gremlins_size 0.1), dt the simulation time per frame (with frame_steps = 1: the env's dt).  With
+        n_frames * dt = 2 pi and loop=True the motion is periodic.  The offset rule is the reference's (pinned by
+        tests/golden/gremlin_cases.npz); adding a placement centre to it is this project's: the reference moves a mocap body
+        whose pose MuJoCo composes with the placement.  kwargs: frame_steps, loop, cost, indicator, counts, scene."""
+        c = np.asarray(centres, np.float64)
+        if c.ndim == 2:
+            c = c[None]
+        if c.ndim != 3 or c.shape[2] != 2:
+            raise ValueError(f"centres must be [M, 2] or [S, M, 2], got shape {np.shape(centres)}")
+        if int(n_frames) < 1:
+            raise ValueError("moving hazards need at least one frame")
+        if not (np.isfinite(travel) and np.isfinite(dt) and np.isfinite(phase0)):
+            raise ValueError("travel, dt and phase0 must be finite")
+        off = cls.circling_offsets(float(travel), n_frames, float(dt), float(phase0))
+        loc = c[:, None, :, :] + off[None, :, None, :]
+        return cls(loc if np.ndim(centres) == 3 else loc[0], size, **kwargs)

@@ -205,7 +205,7 @@ class DeviceGoalVecEnv(VecEnvBase):
         """The engine's current policy on fresh robots of this task (PPOEngine.evaluate_goal_env with this env's mix, dt,
         extent, extra_bonus and time_limit).  n_robots defaults to num_envs; with a quota (`episodes` > 0 or `quota`)
         max_steps defaults to the bound max quota x time_limit, else to time_limit; seed defaults to the env's seed.
-        hazards: a goal_rules.Hazards (hazard costs, see PPOEngine.evaluate_goal_env)."""
+        hazards: a goal_rules.Hazards or MovingHazards (hazard costs, see PPOEngine.evaluate_goal_env)."""
         n = self.num_envs if n_robots is None else int(n_robots)
         if max_steps is None:
             if quota is not None or episodes > 0:
@@ -221,7 +221,8 @@ class DeviceGoalVecEnv(VecEnvBase):
     def follow(self, engine, start=None, waypoints=None, n_waypoints=None, max_steps=1000, deterministic=True, seed=None,
                path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0):
         """The engine's current policy following given waypoints on this task (PPOEngine.follow_waypoints with this env's mix,
-        dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed.  hazards: a goal_rules.Hazards.
+        dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed.  hazards: a goal_rules.Hazards or
+        MovingHazards (frames indexed by the run's global step).
         resume: a waypoints.FollowState (this call continues that run; no start / waypoints then); leg_steps: step budget per
         waypoint.  Either makes the call return `state` and `status` as well."""
         return engine.follow_waypoints(self.pos_dim, self.mix, dt=self.dt, extent=self.extent, extra_bonus=self.extra_bonus,

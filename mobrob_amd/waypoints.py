@@ -23,6 +23,9 @@ With `hazards` (a goal_rules.Hazards), also the hazard costs of every step (the 
 position after the step; on the host: info["cost"] of EnvWrapper.step with set_hazards):
   cost_sum [n] float64 sum of the step costs;  violation_steps [n] steps with cost > 0;  first_violation [n] the first such step
   (1-based), -1 = none;  min_clearance [n] smallest (distance - radius) after a step (+inf without hazards, NaN without steps)
+`hazards` may be a goal_rules.MovingHazards: F frames of hazards, `frame_steps` steps each.  The check after the step with
+0-based global number g -- g = step0 + t, t the step of the call; g = t in a one-shot call -- reads frame f(g) =
+min(g // frame_steps, F - 1), or (g // frame_steps) % F with loop=True.  The host loop sets the frame's rows before that step.
 
 Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
 sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
@@ -39,7 +42,10 @@ max_steps - 1:
   * between calls `state.replan(rows, waypoints)` gives robots new waypoints: reached = 0, arrival row = -1, leg_used = 0,
     everything else carried;
   * `path` and `trace` are the call's own: record 0 is the position at entry, `steps`, `reached`, `reward_sum` are the run's.
-`follow_with_replanning` is that loop with a planner callback.
+`follow_with_replanning` is that loop with a planner callback.  g is a property of the run, not of the call: with moving
+hazards step g sees the same frame in one long call and in any chain of calls, so the split changes nothing here either.  A
+planner that holds the `state` a call returned asks `hazards.rows(i, state.step0)` for the scene robot i meets at the next
+call's first step (in `follow_with_replanning`, after round r of `horizon` steps, that step is (r + 1) * horizon).
 """
 from __future__ import annotations
 
@@ -173,13 +179,14 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
     """The semantics, one robot after another on EnvWrapper's public API (make_env(i) -> the robot's env): one call of the run
     `state` is in (a fresh FollowState: the robots at rest on their starts).  Returns the dict and the state after the call.
     The simulator's noise is seeded per (robot, global step), so a run split into calls draws what one long call draws."""
-    from .envs.goal_rules import hazard_cost
+    from .envs.goal_rules import MovingHazards, hazard_cost
     st = state.copy()
     st.state = st.state.astype(np.float64)              # the host simulator's own precision, carried exactly
     wp, nw, step0 = st.waypoints, st.n_waypoints, st.step0
     n, K, P = wp.shape
     if hazards is not None:
         hazards.check_robots(n)
+    moving = isinstance(hazards, MovingHazards)
     final_distance = np.full(n, np.nan)
     path = np.zeros((max_steps // path_stride + 1, n, P), np.float32) if path_stride > 0 else None
     key = None if seed is None else int(seed) & (2 ** 64 - 1)
@@ -190,7 +197,7 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
             path[0, i] = pos
         if k < nw[i] and (leg_steps == 0 or leg_used < leg_steps):
             env = make_env(i)
-            if hazards is not None:
+            if hazards is not None and not moving:
                 rows = hazards.rows(i)
                 env.set_hazards(rows[:, :2], rows[:, 2], hazards.cost, hazards.indicator)
             if seed is not None:
@@ -204,6 +211,9 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
             env.set_goal(wp[i, k])
             for t in range(max_steps):
                 g = step0 + t                          # the global step
+                if moving:                             # the frame in force at the check after this step
+                    rows = hazards.rows(i, g)
+                    env.set_hazards(rows[:, :2], rows[:, 2], hazards.cost, hazards.indicator)
                 if key is not None:
                     env.env.seed([key, i, g])
                 obs = env.get_obs()
@@ -259,7 +269,7 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
     """Every robot i follows waypoints[i][:n_waypoints[i]] from start[i] under `model` (a PPO, or for the host path anything
     with `.predict`).  `env`: a DeviceGoalVecEnv (device path), an EnvWrapper, or an env name for `get_env` (host path; a
     fresh environment per robot for a name, the given one reused robot after robot otherwise).  Returns the dict described in
-    the module docstring.  hazards: a goal_rules.Hazards (hazard costs, see the module docstring).
+    the module docstring.  hazards: a goal_rules.Hazards or MovingHazards (hazard costs, see the module docstring).
     state: the `state` a previous call returned -- this call continues that run (start / waypoints / n_waypoints must then be
     None: the robots are where they were, on the waypoints the state holds).  leg_steps: step budget per waypoint (0: none)."""
     from .envs.vec_env import DeviceGoalVecEnv
