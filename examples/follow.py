@@ -51,11 +51,11 @@ def check_chain(max_steps, horizon, leg_steps):
 
 
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
-           horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False):
+           horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3):
     calls = check_chain(max_steps, horizon, leg_steps)
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
-    from mobrob_amd.envs.goal_rules import Hazards, MovingHazards
+    from mobrob_amd.envs.goal_rules import Hazards, MovingHazards, Teams
     from mobrob_amd.envs.wrapper import ROBOT_DIMS, KinematicSim
     from mobrob_amd.waypoints import follow_waypoints
     policy = load_policy(env_name, policy_name) if policy is None else policy
@@ -71,11 +71,12 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         if fr.ndim != 3 or fr.shape[2] != 3:
             raise ValueError(f"--hazard-frames must hold [F][M][3] (x, y, radius), got shape {fr.shape}")
         hz = MovingHazards(fr[:, :, :2], fr[None, :, :, 2], frame_steps=int(frame_steps), loop=bool(hazard_loop), indicator=False)
+    teams = None if team_size is None else Teams(int(team_size), float(separation))   # (a ValueError names what is wrong)
     r = follow_waypoints(policy, env, start, waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
-                         leg_steps=leg_steps)
+                         leg_steps=leg_steps, teams=teams)
     for steps in calls[1:]:                                # the run, continued call after call
         r = follow_waypoints(policy, env, max_steps=steps, deterministic=True, seed=seed, hazards=hz, state=r["state"],
-                             leg_steps=leg_steps)
+                             leg_steps=leg_steps, teams=teams)
     K = r["arrival"].shape[1]
     done = r["reached"] == K
     last = r["arrival"][done, K - 1]
@@ -86,6 +87,8 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         print(f"stalled rate: {float(np.mean(r['status'] == 2))}")
     if hz is not None:
         report_hazards(r)
+    if teams is not None:
+        report_teams(r)
     return r
 
 
@@ -94,6 +97,15 @@ def report_hazards(r):
     print(f"mean hazard cost: {float(np.mean(r['cost_sum']))}")
     print(f"violation rate: {float(np.mean(r['violation_steps'] > 0))}")
     print(f"minimum clearance: {float(np.nanmin(r['min_clearance'])) if np.any(r['steps'] > 0) else float('nan')}")
+
+
+def report_teams(r):
+    """The three team lines: mean separation cost per robot, conflict rate (robots with a step of cost > 0), minimum clearance
+    to a team-mate."""
+    clear = r["min_team_clearance"]
+    print(f"mean team cost: {float(np.mean(r['team_cost_sum']))}")
+    print(f"conflict rate: {float(np.mean(r['conflict_steps'] > 0))}")
+    print(f"minimum team clearance: {float(np.nanmin(clear)) if np.any(~np.isnan(clear)) else float('nan')}")
 
 
 if __name__ == "__main__":
@@ -112,6 +124,8 @@ if __name__ == "__main__":
     ap.add_argument("--hazard-loop", action="store_true", default=False, help="start over after the last frame (else hold it)")
     ap.add_argument("--horizon", type=int, default=None, help="run as a chain of calls of this many steps (a planner's rounds)")
     ap.add_argument("--leg-steps", type=int, default=0, help="step budget per waypoint; a robot that spends it stalls (0: none)")
+    ap.add_argument("--team-size", type=int, default=None, help="teams of this many consecutive robots (1, 2, 4, 8, 16): report separation costs")
+    ap.add_argument("--separation", type=float, default=0.3, help="distance team-mates must keep")
     args = ap.parse_args()
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
@@ -120,4 +134,4 @@ if __name__ == "__main__":
     follow(args.env_name, args.policy_name, np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed,
            hazards=None if args.hazards is None else (np.load(args.hazards), args.hazard_size), horizon=args.horizon,
            leg_steps=args.leg_steps, hazard_frames=None if args.hazard_frames is None else np.load(args.hazard_frames),
-           frame_steps=args.frame_steps, hazard_loop=args.hazard_loop)
+           frame_steps=args.frame_steps, hazard_loop=args.hazard_loop, team_size=args.team_size, separation=args.separation)

@@ -638,6 +638,48 @@ int mobrob_ppo_follow_waypoints_hazard_frames(mobrob_ppo_engine_t* e, const mobr
                                               double* hazard_out /* [n][4] (in / out with resume) */, float* path_out /* or NULL */,
                                               float* trace_out /* or NULL */);
 
+/* ---- robot teams: pairwise separation costs in waypoint-following runs -------------------------------------------------------
+ * One call of a run (mobrob_ppo_follow_waypoints_resume; with hz its hazards, with hzf mobrob_ppo_follow_waypoints_hazard_frames'
+ * moving hazards; not both) whose robots are partitioned into TEAMS of team_size consecutive robots: team of robot n = n /
+ * team_size, team-local index m = n % team_size.  team_size is 1, 2, 4, 8 or 16 and divides n_robots, so a team never straddles a
+ * 16-robot tile; robots of different teams never see each other.  The rule (mobrob_amd/envs/goal_rules.py: team_cost): after the
+ * step with 0-based global number g, for every robot i that stepped in it, with p the post-step positions -- x and y only, as for
+ * hazards, for drones too -- and the team-mates j != i, a mate that did not step (finished, stalled, without waypoints, parked in
+ * an earlier call) counting where it stands:
+ *     d_ij = |p_i - p_j|  (float32, correctly rounded)      cost_i = cost * sum over d_ij <= separation of (separation - d_ij)
+ *     indicator: cost_i = (cost_i > 0)      clear_i = min_j (d_ij - separation)  (+inf alone)      partner_i = the j attaining it
+ * (equal clearances: the lowest j).  d_ij == separation contributes exactly 0 and is no conflict.  The float32 sum runs over four
+ * partial sums -- quarter q: the members m = q, q + 4, ... except i -- combined as (p0 + p1) + (p2 + p3), cost applied once
+ * afterwards; the minimum over the same quarters and exchanges.  A robot accounts only for steps in which it stepped itself.
+ *   team_out  [n][5] float64, in / out, carried like hazard_out: sum of the step costs, steps with cost > 0, the first such step
+ *             (global, 1-based, -1 = none), the minimum of clear_i over the run (NaN: no step run yet in the run; +inf with
+ *             team_size 1), the partner's global index at that minimum (the first attainment is kept; -1 = none).  A run starts
+ *             from 0, 0, -1, NaN, -1.
+ * Nothing else changes: dynamics, rewards, arrivals, status, hazard_out, path and trace (rows of the underlying call, same width)
+ * are the bits of the call without teams, and a run split into calls ends with the team_out of one long call.
+ *   kernels   k_goal64_tile<DP, TeamTask<...>>: every robot's carried position seeds the tile's [16][2] xy block before the step
+ *             loop, the check runs on all 64 lanes as (robot, quarter) after the env phase.  Per-step path: k_team_step after every
+ *             k_goal_task_step, one thread per robot, the same order of operations, hence the same bits.
+ * MOBROB_ERR_INVALID before any launch or copy, besides every check of the underlying run call, for: team_size outside {1, 2, 4,
+ * 8, 16}, n_robots % team_size != 0, separation or cost negative or non-finite, a NULL resume, teams or team_out, both hz and hzf,
+ * a carried team record no call returns (a sum that is negative or not finite, counts that are not whole, negative or above the
+ * steps run, a first step that is not whole, < -1 or > step0, a partner that is neither -1 nor another member of the robot's team,
+ * a clearance that is not NaN with zero steps run or NaN with steps run). */
+typedef struct mobrob_teams {
+  int32_t team_size;   /* 1, 2, 4, 8 or 16; divides n_robots */
+  float separation;    /* >= 0, finite                       */
+  float cost;          /* >= 0, finite                       */
+  int32_t indicator;   /* cost_i = (cost_i > 0)              */
+} mobrob_teams_t;
+int mobrob_ppo_follow_waypoints_teams(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                      const mobrob_hazards_t* hz /* or NULL */, const mobrob_hazard_frames_t* hzf /* or NULL; not both */,
+                                      const mobrob_follow_resume_t* resume, const mobrob_teams_t* teams,
+                                      const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                      int32_t* arrival /* [n][K] in / out */, double* robot_out /* [n][4] in / out */,
+                                      double* hazard_out /* [n][4] in / out, NULL iff no hazards */,
+                                      double* team_out /* [n][5] in / out */, float* path_out /* or NULL */,
+                                      float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

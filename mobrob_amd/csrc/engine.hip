@@ -52,6 +52,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_eval.h"
 #include "kernels_follow.h"
 #include "kernels_hazard.h"
+#include "kernels_team.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -3294,6 +3295,8 @@ static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, voi
         forward(e, a.obs + (size_t)s * a.Dp, c, true, a.mu + (size_t)s * a.Ap, false, nullptr);
       }
       hipLaunchKernelGGL(k_goal_task_step<Task>, dim3(cdiv(N, 256)), dim3(256), 256 * 33 * sizeof(float), e->stream, args, t);
+      if constexpr (task_teams<Task>)   // the team check needs every mate's post-step position: a launch of its own
+        hipLaunchKernelGGL(k_team_step<typename Task::TeamBase>, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, args, t);
     }
     if (fin) hipLaunchKernelGGL(fin, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, args);
   }
@@ -3393,6 +3396,44 @@ static int hazard_fill(mobrob_ppo_engine_t* e, const HazardIO& hio, int N, const
 template <class BaseArgs>
 static void hazard_fill_frames(const HazardIO& hio, FrameHazardArgs<BaseArgs>& hf) {
   hf.F = hio.F; hf.frame_steps = hio.frame_steps; hf.loop = hio.loop;
+}
+
+// ---- teams (mobrob_ppo_follow_waypoints_teams): checks, the run of a base task wrapped in TeamTask ----
+struct TeamIO {
+  const mobrob_teams_t* tm;
+  double* team_out;           // [N][5] in / out
+};
+struct TeamFill {             // the team fields of TeamArgs (after eval_prepare grew eval_buf)
+  int team_size;
+  float sep, coef;
+  int indicator;
+  double* out;
+  int* stepped;
+};
+static int team_check(const TeamIO& tio, int N, int step0, const double* robot_out) {
+  const mobrob_teams_t* tm = tio.tm;
+  const int ts = tm->team_size;
+  if (ts != 1 && ts != 2 && ts != 4 && ts != 8 && ts != 16) return fail(MOBROB_ERR_INVALID, "follow: teams: team_size must be 1, 2, 4, 8 or 16");
+  if (N % ts != 0) return fail(MOBROB_ERR_INVALID, "follow: teams: n_robots = %d is not a multiple of team_size = %d", N, ts);
+  if (!(std::isfinite(tm->separation) && tm->separation >= 0.f)) return fail(MOBROB_ERR_INVALID, "follow: teams: separation must be finite and >= 0");
+  if (!(std::isfinite(tm->cost) && tm->cost >= 0.f)) return fail(MOBROB_ERR_INVALID, "follow: teams: cost must be finite and >= 0");
+  for (int i = 0; i < N; ++i) {
+    const double* o = tio.team_out + (size_t)i * 5;
+    const double steps = robot_out[(size_t)i * 4 + 1];
+    const bool sums = std::isfinite(o[0]) && o[0] >= 0.0 && o[1] >= 0.0 && o[1] <= steps && o[1] == std::floor(o[1]);
+    const bool first = o[2] >= -1.0 && o[2] <= (double)step0 && o[2] == std::floor(o[2]);
+    const bool partner = o[4] == -1.0 || (o[4] == std::floor(o[4]) && o[4] >= (double)(i - i % ts) && o[4] < (double)(i - i % ts + ts) &&
+                                          o[4] != (double)i);
+    const bool clear = std::isnan(o[3]) == (steps == 0.0);
+    if (!(sums && first && partner && clear))
+      return fail(MOBROB_ERR_INVALID, "follow: teams: carried team record of robot %d is not one a call returns", i);
+  }
+  return MOBROB_OK;
+}
+template <class Base>
+static int team_run(mobrob_ppo_engine_t* e, const typename Base::Args& b, const TeamFill& t) {
+  const TeamArgs<typename Base::Args> a{b, t.team_size, t.sep, t.coef, t.indicator, t.out, t.stepped};
+  return eval_run<TeamTask<Base>>(e, a, k_goal_task_fin<TeamTask<Base>>);
 }
 }  // extern "C++"
 
@@ -3515,11 +3556,12 @@ static int follow_resume_check(const mobrob_follow_resume_t* rs, const mobrob_fo
 }
 
 // follow, with hazards when `hio` is not null (mobrob_ppo_follow_waypoints_hazards); one call of a resumable run when `rs` is not
-// null (mobrob_ppo_follow_waypoints_resume: no `start`, arrival / robot_out / hazard_out in and out)
+// null (mobrob_ppo_follow_waypoints_resume: no `start`, arrival / robot_out / hazard_out in and out), with teams when `tio` is not
+// null (mobrob_ppo_follow_waypoints_teams: a call of a run, team_out in and out)
 static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
                             const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
                             double* robot_out, float* path_out, float* trace_out, const HazardIO* hio,
-                            const mobrob_follow_resume_t* rs = nullptr) {
+                            const mobrob_follow_resume_t* rs = nullptr, const TeamIO* tio = nullptr) {
   if (!e || !env || !spec || (!start && !rs) || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
   EvalCall c{"follow", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
   if (hio) c.trace_extra = kHazardTraceExtra;
@@ -3548,6 +3590,8 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     if (const int rc = hazard_check(*hio, N, c.who, hc.counts)) return rc;
   if (rs)
     if (const int rc = follow_resume_check(rs, spec, nw, robot_out, hio ? hio->hazard_out : nullptr)) return rc;
+  if (tio)   // (only with rs: the entry point refuses a call without it)
+    if (const int rc = team_check(*tio, N, rs->step0, robot_out)) return rc;
   const bool pathing = path_out && spec->path_stride > 0;
   const size_t n_rec = pathing ? (size_t)(spec->max_steps / spec->path_stride + 1) : 0;
   EvalCarve carve;
@@ -3555,7 +3599,8 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
                o_nw = carve.add((size_t)N * 4), o_path = carve.add(std::max<size_t>(n_rec * N * P, 1) * 4);
   if (hio) hazard_carve(carve, *hio, N, hc);
   const size_t o_state = carve.add(rs ? (size_t)N * 6 * 4 : 0), o_leg = carve.add(rs ? (size_t)N * 4 : 0),
-               o_status = carve.add(rs ? (size_t)N * 4 : 0), o_entry = carve.add(rs ? (size_t)N * 4 : 0);
+               o_status = carve.add(rs ? (size_t)N * 4 : 0), o_entry = carve.add(rs ? (size_t)N * 4 : 0),
+               o_team = carve.add(tio ? (size_t)N * 5 * 8 : 0), o_stepped = carve.add(tio ? (size_t)N * 4 : 0);
   FrameHazardArgs<FollowArgs> hf{};    // the frames tasks' arguments hold the static tasks'
   FrameHazardArgs<ResumeArgs> hrf{};
   HazardArgs<FollowArgs>& h = hf.h;
@@ -3602,6 +3647,14 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
       HIPC(hipMemcpyAsync(hr.hazard_out, hio->hazard_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
     }
     hazard_dev = hr.hazard_out;
+    if (tio) {
+      const TeamFill tf{tio->tm->team_size, tio->tm->separation, tio->tm->cost, tio->tm->indicator != 0, eval_at<double>(e, o_team),
+                        eval_at<int>(e, o_stepped)};
+      HIPC(hipMemcpyAsync(tf.out, tio->team_out, (size_t)N * 5 * 8, hipMemcpyHostToDevice, e->stream));
+      ran = !hio ? team_run<ResumeFollowTask>(e, r, tf)
+            : hio->frames ? team_run<FrameHazardTask<ResumeFollowTask>>(e, hrf, tf) : team_run<HazardTask<ResumeFollowTask>>(e, hr, tf);
+      if (ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
+    } else
     ran = !hio ? eval_run<ResumeFollowTask>(e, r, k_goal_task_fin<ResumeFollowTask>)
           : hio->frames ? eval_run<FrameHazardTask<ResumeFollowTask>>(e, hrf, k_goal_task_fin<FrameHazardTask<ResumeFollowTask>>)
                         : eval_run<HazardTask<ResumeFollowTask>>(e, hr, k_goal_task_fin<HazardTask<ResumeFollowTask>>);
@@ -3652,6 +3705,20 @@ int mobrob_ppo_follow_waypoints_hazard_frames(mobrob_ppo_engine_t* e, const mobr
   const HazardIO hio = hazard_frames_io(hz, view, hazard_out, nullptr);
   return follow_waypoints(e, env, spec, resume ? nullptr : start, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out, &hio,
                           resume);
+}
+
+int mobrob_ppo_follow_waypoints_teams(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                      const mobrob_hazards_t* hz, const mobrob_hazard_frames_t* hzf, const mobrob_follow_resume_t* resume,
+                                      const mobrob_teams_t* teams, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
+                                      double* robot_out, double* hazard_out, double* team_out, float* path_out, float* trace_out) {
+  if (!resume || !teams || !team_out) return fail(MOBROB_ERR_INVALID, "follow: teams: null argument");
+  if (hz && hzf) return fail(MOBROB_ERR_INVALID, "follow: teams: static hazards or hazard frames, not both");
+  if ((hz || hzf) != (hazard_out != nullptr)) return fail(MOBROB_ERR_INVALID, "follow: teams: hazard_out is needed with hazards, and only then");
+  const TeamIO tio{teams, team_out};
+  mobrob_hazards_t view;
+  const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
+  return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
+                          (hz || hzf) ? &hio : nullptr, resume, &tio);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 //   k_goal64_tile<DP, Task>  the whole run in one launch for 2x64 tanh actors: one wave per 16-robot tile, the actor in LDS,
 //                            the forward on the f32 16x16x4 MFMA, the tile's state in registers / LDS through the step loop
 #pragma once
+#include <type_traits>
 #include "kernels_fused.h"
 #include "kernels_env.h"
 
@@ -178,6 +179,13 @@ __device__ __forceinline__ int task_step0(const typename Task::Args& args) {
   if constexpr (Task::kResume) return Task::step0(args);
   else return 0;
 }
+
+// a task that checks robots against their team-mates (kernels_team.h: TeamTask names its TeamBase): k_goal64_tile seeds the xy
+// block with every robot's carried position (Task::place), the per-step path launches k_team_step after every step kernel
+template <class Task, class = void>
+constexpr bool task_teams = false;
+template <class Task>
+constexpr bool task_teams<Task, std::void_t<typename Task::TeamBase>> = true;
 
 // ------------------------------------------------------------------------------------------------
 // per-step path: robot state in st, the task's accumulators wherever Task::store keeps them between launches
@@ -385,6 +393,7 @@ __global__ __launch_bounds__(64) void k_goal64_tile(typename Task::Args args, Ev
     Task::start(g, R, args, n);
     active = Task::active(args, R);
     eval64_state_lds(&lds[L::ST + 12 * r16], g);
+    if constexpr (task_teams<Task>) Task::place(g, &lds[L::END + 2 * r16]);
   }
   __syncthreads();
   const bool wide_head = a.A > 16;

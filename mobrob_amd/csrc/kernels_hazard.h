@@ -103,6 +103,7 @@ struct HazardTask {
     if constexpr (kResume) hazard_load(h, n, R);   // the run's accumulators so far
   }
   static __device__ __forceinline__ bool active(const Args& h, const Robot& R) { return Base::active(h.b, R.b); }
+  static __device__ __forceinline__ int steps(const Robot& R) { return Base::steps(R.b); }   // for a wrapping task (kernels_team.h)
 
   // the whole step in one thread (per-step path): the four partial sums in turn
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& h, int n, int t, const float* act,
@@ -223,6 +224,7 @@ struct FrameHazardTask {
 
   static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& a, int n) { H::start(g, R, a.h, n); }
   static __device__ __forceinline__ bool active(const Args& a, const Robot& R) { return H::active(a.h, R); }
+  static __device__ __forceinline__ int steps(const Robot& R) { return H::steps(R); }
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
                                               const float* obs_row) {
     return H::step(g, R, a.h, n, t, act, obs_row, a.F, frame_at(a, t));

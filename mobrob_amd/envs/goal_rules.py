@@ -248,3 +248,102 @@ class MovingHazards:
         off = cls.circling_offsets(float(travel), n_frames, float(dt), float(phase0))
         loc = c[:, None, :, :] + off[None, :, None, :]
         return cls(loc if np.ndim(centres) == 3 else loc[0], size, **kwargs)
+
+
+# ---- teams: pairwise separation costs between the robots of a waypoint-following run.  This project's own rule (the reference
+# has one robot per world); it is stated here once and the device (csrc/kernels_team.h) and the host loop are held to it.
+TEAM_SIZES = (1, 2, 4, 8, 16)   # they divide 16: a team never straddles a tile of the device kernel
+TEAM_START = (0.0, 0.0, -1.0, np.nan, -1.0)   # a robot's team record before its first step
+
+
+class Teams:
+    """Robots partitioned into teams of `size` consecutive robots (team of robot n: n // size, team-local index n % size) that
+    must keep `separation` apart: `cost` per unit of intrusion, `indicator`: a step's cost is 1 if there is any.  Robots of
+    different teams never see each other.  Checked on construction (ValueError)."""
+
+    def __init__(self, size, separation, cost=1.0, indicator=False):
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or int(size) not in TEAM_SIZES:
+            raise ValueError(f"team size must be one of {TEAM_SIZES}, got {size!r}")
+        separation, cost = float(separation), float(cost)
+        if not np.isfinite(separation) or separation < 0:
+            raise ValueError(f"team separation must be finite and >= 0, got {separation}")
+        if not np.isfinite(cost) or cost < 0:
+            raise ValueError(f"team cost must be finite and >= 0, got {cost}")
+        self.size, self.indicator = int(size), bool(indicator)
+        self.separation, self.cost = float(np.float32(separation)), float(np.float32(cost))   # the float32 values every path uses
+
+    def check_robots(self, n):
+        if int(n) % self.size != 0:
+            raise ValueError(f"{int(n)} robots do not split into teams of {self.size}")
+
+
+def team_cost(pos_xy, stepped, separation, coef=1.0, indicator=False):
+    """The team check of ONE step: pos_xy [..., G, 2] the post-step x, y of the G members of a team (a member that did not step:
+    where it stands), stepped [..., G] who stepped -> (cost [..., G] float32, clear [..., G] float32, partner_local [..., G]
+    int64) for the members that stepped; the others get 0, +inf, -1 and account nothing.  Leading dimensions are teams (or
+    steps) handled alike.  For member i and its mates j != i:
+        d_ij = |p_i - p_j|      cost_i = coef * sum over d_ij <= separation of (separation - d_ij)      indicator: cost_i > 0
+        clear_i = min_j (d_ij - separation)  (+inf alone)      partner_i = the j attaining it (equal clearances: the lowest j)
+    in float32, every operation rounded on its own, in the device's order: four partial sums, quarter q over the members
+    m = q, q + 4, ... except i, combined as (p0 + p1) + (p2 + p3), coef applied once afterwards; the (clearance, partner) minimum
+    over the same quarters and exchanges, the smaller clearance winning and equal clearances going to the smaller index.
+    d_ij == separation contributes exactly 0."""
+    f32 = np.float32
+    p = np.asarray(pos_xy, f32)
+    stepped = np.asarray(stepped, bool)
+    G = p.shape[-2]
+    if p.shape[-1] != 2 or stepped.shape != p.shape[:-1]:
+        raise ValueError(f"pos_xy must be [..., G, 2] and stepped [..., G], got {p.shape} and {stepped.shape}")
+    sep, lead = f32(separation), p.shape[:-2]
+    me = np.arange(G)
+    part, clear, partner = np.zeros((4,) + lead + (G,), f32), np.full((4,) + lead + (G,), np.inf, f32), np.full((4,) + lead + (G,), -1)
+    for m in range(G):
+        q = m % 4
+        dx, dy = p[..., :, 0] - p[..., m:m + 1, 0], p[..., :, 1] - p[..., m:m + 1, 1]
+        d = np.sqrt(dx * dx + dy * dy)                                    # float32 throughout: each operation correctly rounded
+        other = me != m
+        part[q] = np.where(other & (d <= sep), part[q] + (sep - d), part[q])
+        cl = d - sep
+        closer = other & (cl < clear[q])                                  # ascending m: equal clearances keep the lower index
+        clear[q], partner[q] = np.where(closer, cl, clear[q]), np.where(closer, m, partner[q])
+
+    def closer_of(a, b):
+        (ca, pa), (cb, pb) = a, b
+        take = (cb < ca) | ((cb == ca) & (pb < pa))
+        return np.where(take, cb, ca), np.where(take, pb, pa)
+    total = f32(coef) * ((part[0] + part[1]) + (part[2] + part[3]))
+    cl, pt = closer_of(closer_of((clear[0], partner[0]), (clear[1], partner[1])), closer_of((clear[2], partner[2]), (clear[3], partner[3])))
+    if indicator:
+        total = (total > 0).astype(f32)
+    return (np.where(stepped, total, f32(0)), np.where(stepped, cl, f32(np.inf)).astype(f32), np.where(stepped, pt, -1).astype(np.int64))
+
+
+def team_fold(record, pos_xy, stepped, teams, step0=0):
+    """The carried team record after the steps step0 .. step0 + T - 1: record [n][5] float64 (sum of step costs, steps with
+    cost > 0, the first such step as a global 1-based number or -1, the minimum clearance over the run -- NaN before the robot's
+    first step, +inf in a team of one --, the partner's global index at that minimum, first attainment kept, or -1), pos_xy
+    [T][n][2] the positions after each step (a robot that did not step: where it stands), stepped [T][n].  Returns a new
+    [n][5]; a robot accounts only for the steps in which it stepped itself."""
+    rec = np.array(record, np.float64)
+    pos = np.asarray(pos_xy, np.float32)
+    stepped = np.asarray(stepped, bool)
+    T, n = stepped.shape
+    teams.check_robots(n)
+    if rec.shape != (n, 5) or pos.shape != (T, n, 2):
+        raise ValueError(f"record must be [{n}][5] and pos_xy [{T}][{n}][2], got {rec.shape} and {pos.shape}")
+    G = teams.size
+    cost, clear, partner = team_cost(pos.reshape(T, n // G, G, 2), stepped.reshape(T, n // G, G), teams.separation, teams.cost,
+                                     teams.indicator)
+    cost, clear = cost.reshape(T, n).astype(np.float64), clear.reshape(T, n).astype(np.float64)
+    partner = np.where(partner < 0, -1, partner + (np.arange(n // G) * G)[None, :, None]).reshape(T, n)
+    for t in range(T):
+        s = stepped[t]
+        rec[:, 0] += np.where(s, cost[t], 0.0)                            # float64, one step after the other
+        hit = s & (cost[t] > 0)
+        rec[:, 1] += hit
+        rec[:, 2] = np.where(hit & (rec[:, 2] < 0), step0 + t + 1, rec[:, 2])
+        best = np.where(np.isnan(rec[:, 3]), np.inf, rec[:, 3])
+        closer = s & (clear[t] < best)
+        rec[:, 3] = np.where(s, np.where(closer, clear[t], best), rec[:, 3])
+        rec[:, 4] = np.where(closer, partner[t], rec[:, 4])
+    return rec
