@@ -25,6 +25,12 @@ replaces --hazards / --hazard-size, reports the same three lines and works with 
 does not divide --max-steps), every call continuing from the state the previous one returned.  The report is exactly the single
 call's.  `--leg-steps B` gives every waypoint a budget of B steps: a robot that has spent it without arriving stalls (and would
 be the planner's to replan); a fourth line then reports the rate of stalled robots.
+
+`--release FILE.npy` ([K] or [n][K] integers) times the waypoints: waypoint k may not become a robot's goal before the global step
+release[k]; until then the robot holds at the previous waypoint (its start for k = 0) under the policy.  `--stagger S` is the
+shorthand for delays: robot m of a team (robot i without --team-size) gets every waypoint released m * S steps later.  Two lines
+report the mean hold steps per robot and the largest drift from an anchor while holding.  With --team-size, a stagger of the
+time a robot needs to clear a crossing is the one-line demonstration that delays remove team conflicts.
 """
 import argparse
 import os
@@ -51,11 +57,12 @@ def check_chain(max_steps, horizon, leg_steps):
 
 
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
-           horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3):
+           horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
+           release=None, stagger=0):
     calls = check_chain(max_steps, horizon, leg_steps)
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
-    from mobrob_amd.envs.goal_rules import Hazards, MovingHazards, Teams
+    from mobrob_amd.envs.goal_rules import Hazards, MovingHazards, Schedule, Teams
     from mobrob_amd.envs.wrapper import ROBOT_DIMS, KinematicSim
     from mobrob_amd.waypoints import follow_waypoints
     policy = load_policy(env_name, policy_name) if policy is None else policy
@@ -72,11 +79,12 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             raise ValueError(f"--hazard-frames must hold [F][M][3] (x, y, radius), got shape {fr.shape}")
         hz = MovingHazards(fr[:, :, :2], fr[None, :, :, 2], frame_steps=int(frame_steps), loop=bool(hazard_loop), indicator=False)
     teams = None if team_size is None else Teams(int(team_size), float(separation))   # (a ValueError names what is wrong)
+    schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
     r = follow_waypoints(policy, env, start, waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
-                         leg_steps=leg_steps, teams=teams)
+                         leg_steps=leg_steps, teams=teams, schedule=schedule)
     for steps in calls[1:]:                                # the run, continued call after call
         r = follow_waypoints(policy, env, max_steps=steps, deterministic=True, seed=seed, hazards=hz, state=r["state"],
-                             leg_steps=leg_steps, teams=teams)
+                             leg_steps=leg_steps, teams=teams, schedule=schedule)
     K = r["arrival"].shape[1]
     done = r["reached"] == K
     last = r["arrival"][done, K - 1]
@@ -89,7 +97,26 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         report_hazards(r)
     if teams is not None:
         report_teams(r)
+    if schedule is not None:
+        print(f"mean hold steps: {float(np.mean(r['hold_steps']))}")
+        print(f"maximum hold drift: {float(np.nanmax(r['hold_drift'])) if np.any(r['hold_steps'] > 0) else float('nan')}")
     return r
+
+
+def make_schedule(release, stagger, n, K, team_size=None):
+    """--release / --stagger -> a Schedule, or None without either: release [K] or [n][K] (None: zeros) plus m * stagger for
+    robot m of its team (robot i without teams)"""
+    from mobrob_amd.envs.goal_rules import Schedule
+    if release is None and not stagger:
+        return None
+    if int(stagger) < 0:
+        raise ValueError("--stagger must be >= 0")
+    rel = np.zeros((n, K), np.int64) if release is None else np.asarray(release)
+    if not np.issubdtype(rel.dtype, np.integer):
+        raise ValueError("--release must hold integers")
+    rel = np.broadcast_to(rel, (n, rel.shape[-1])) if rel.ndim == 1 else rel
+    member = np.arange(n) % int(team_size) if team_size else np.arange(n)
+    return Schedule(rel + int(stagger) * member[:, None])
 
 
 def report_hazards(r):
@@ -126,6 +153,8 @@ if __name__ == "__main__":
     ap.add_argument("--leg-steps", type=int, default=0, help="step budget per waypoint; a robot that spends it stalls (0: none)")
     ap.add_argument("--team-size", type=int, default=None, help="teams of this many consecutive robots (1, 2, 4, 8, 16): report separation costs")
     ap.add_argument("--separation", type=float, default=0.3, help="distance team-mates must keep")
+    ap.add_argument("--release", type=str, default=None, help="[K] or [n][K] release steps of the waypoints (.npy, integers)")
+    ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
     args = ap.parse_args()
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
@@ -134,4 +163,5 @@ if __name__ == "__main__":
     follow(args.env_name, args.policy_name, np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed,
            hazards=None if args.hazards is None else (np.load(args.hazards), args.hazard_size), horizon=args.horizon,
            leg_steps=args.leg_steps, hazard_frames=None if args.hazard_frames is None else np.load(args.hazard_frames),
-           frame_steps=args.frame_steps, hazard_loop=args.hazard_loop, team_size=args.team_size, separation=args.separation)
+           frame_steps=args.frame_steps, hazard_loop=args.hazard_loop, team_size=args.team_size, separation=args.separation,
+           release=None if args.release is None else np.load(args.release), stagger=args.stagger)

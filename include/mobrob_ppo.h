@@ -680,6 +680,41 @@ int mobrob_ppo_follow_waypoints_teams(mobrob_ppo_engine_t* e, const mobrob_goal_
                                       double* team_out /* [n][5] in / out */, float* path_out /* or NULL */,
                                       float* trace_out /* or NULL */);
 
+/* ---- timed waypoints: release steps and holds in waypoint-following runs ---------------------------------------------------------
+ * One call of a run (mobrob_ppo_follow_waypoints_teams, with `teams` optional: NULL = no teams, and team_out is then NULL) whose
+ * waypoints carry RELEASE STEPS.  The rule (mobrob_amd/envs/goal_rules.py: Schedule): waypoint k of robot n may not be the goal in
+ * force in a step whose 0-based global number g is below release[n][k]; until then the robot HOLDS at its anchor -- the previous
+ * waypoint, home[n] for k = 0 -- under the policy.  k keeps its meaning (waypoints reached = index of the waypoint the robot is
+ * on) and the goal used in global step g is a pure function of (k, g), so nothing new is carried for it:
+ *     hold(k, g) = k < n_waypoints[n] and g < release[n][k]        goal(k, g) = hold ? anchor(k) : waypoint k (the last one for
+ *     k >= n_waypoints[n], as without a schedule)
+ * set for g = step0 at entry and for g + 1 at the end of step g, after any arrival.  A hold step (hold at the step's entry) runs the
+ * env step against the anchor and counts in `steps run`; path, trace, hazard and team checks run as on any step.  It ignores the
+ * reach test (no arrival), adds nothing to the reward sum, leaves leg_used as it is, and its trace flags are 0, 0, k, idle.
+ *   sched_out [n][2] float64, in / out, carried like hazard_out: hold steps run; the largest distance to the anchor after a hold
+ *             step (float32, widened; NaN while no hold step was run).  A run starts from 0, NaN.
+ * robot_out[n][3] is the distance to the waypoint the robot is on, released or not.  With every release 0 every output is the
+ * bits of the call without a schedule and sched_out stays 0, NaN; a run split into calls ends with the arrays of one long call.
+ *   kernels   the task kernels of the run calls with ScheduledFollowTask in ResumeFollowTask's place (csrc/kernels_follow.h).
+ * MOBROB_ERR_INVALID before any launch or copy, the in / out arrays left as given, besides every check of the underlying call, for:
+ * a NULL schedule, release, home or sched_out, team_out without teams or teams without team_out, a negative release among
+ * k < n_waypoints[n], a non-finite home, a carried sched_out[n][0] that is not a whole number in 0 .. steps run, sched_out[n][1]
+ * negative or infinite, NaN with [0] > 0, or not NaN with [0] == 0. */
+typedef struct mobrob_follow_schedule {
+  const int32_t* release;   /* [n][K] first global step in which waypoint k may be the goal in force, >= 0 */
+  const float* home;        /* [n][pos_dim] anchor of waypoint 0, finite                                  */
+} mobrob_follow_schedule_t;
+int mobrob_ppo_follow_waypoints_scheduled(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                          const mobrob_hazards_t* hz /* or NULL */, const mobrob_hazard_frames_t* hzf /* or NULL; not both */,
+                                          const mobrob_follow_resume_t* resume, const mobrob_teams_t* teams /* or NULL */,
+                                          const mobrob_follow_schedule_t* schedule,
+                                          const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                          int32_t* arrival /* [n][K] in / out */, double* robot_out /* [n][4] in / out */,
+                                          double* hazard_out /* [n][4] in / out, NULL iff no hazards */,
+                                          double* team_out /* [n][5] in / out, NULL iff no teams */,
+                                          double* sched_out /* [n][2] in / out */, float* path_out /* or NULL */,
+                                          float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

@@ -90,6 +90,10 @@ class TeamsC(C.Structure):  # mobrob_teams_t
     _fields_ = [("team_size", C.c_int32), ("separation", C.c_float), ("cost", C.c_float), ("indicator", C.c_int32)]
 
 
+class FollowScheduleC(C.Structure):  # mobrob_follow_schedule_t
+    _fields_ = [("release", C.POINTER(C.c_int32)), ("home", C.POINTER(C.c_float))]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -172,6 +176,11 @@ SYMBOLS = {
                                                     C.POINTER(HazardFramesC), C.POINTER(FollowResume), C.POINTER(TeamsC), _F,
                                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), _F, _F]),
+    "mobrob_ppo_follow_waypoints_scheduled": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), C.POINTER(HazardsC),
+                                                        C.POINTER(HazardFramesC), C.POINTER(FollowResume), C.POINTER(TeamsC),
+                                                        C.POINTER(FollowScheduleC), _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                        C.POINTER(C.c_double), _F, _F]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

@@ -3435,6 +3435,54 @@ static int team_run(mobrob_ppo_engine_t* e, const typename Base::Args& b, const 
   const TeamArgs<typename Base::Args> a{b, t.team_size, t.sep, t.coef, t.indicator, t.out, t.stepped};
   return eval_run<TeamTask<Base>>(e, a, k_goal_task_fin<TeamTask<Base>>);
 }
+
+// ---- timed waypoints (mobrob_ppo_follow_waypoints_scheduled): checks of the schedule and of the carried record ----
+struct SchedIO {
+  const mobrob_follow_schedule_t* sc;
+  double* sched_out;          // [N][2] in / out
+};
+static int sched_check(const SchedIO& sio, int N, int K, int P, const std::vector<int32_t>& nw, const double* robot_out) {
+  const mobrob_follow_schedule_t* sc = sio.sc;
+  if (!sc->release || !sc->home) return fail(MOBROB_ERR_INVALID, "follow: schedule: null argument");
+  for (int i = 0; i < N; ++i) {
+    for (int k = 0; k < nw[i]; ++k)
+      if (sc->release[(size_t)i * K + k] < 0)
+        return fail(MOBROB_ERR_INVALID, "follow: schedule: release step of waypoint %d of robot %d is negative", k, i);
+    for (int j = 0; j < P; ++j)
+      if (!std::isfinite(sc->home[(size_t)i * P + j])) return fail(MOBROB_ERR_INVALID, "follow: schedule: home of robot %d is not finite", i);
+    const double* o = sio.sched_out + (size_t)i * 2;
+    const double steps = robot_out[(size_t)i * 4 + 1];
+    const bool count = o[0] >= 0.0 && o[0] <= steps && o[0] == std::floor(o[0]);
+    const bool drift = std::isnan(o[1]) ? o[0] == 0.0 : (o[0] > 0.0 && o[1] >= 0.0 && std::isfinite(o[1]));
+    if (!(count && drift))
+      return fail(MOBROB_ERR_INVALID, "follow: schedule: carried hold record of robot %d is not one a call returns", i);
+  }
+  return MOBROB_OK;
+}
+
+// One call of a run on the resumable task Base (ResumeFollowTask, ScheduledFollowTask), filled in hf.h.b: with hazards when
+// `hio`, with teams when `tio`.  Uploads the carried hazard and team records, runs, and downloads the team record.
+template <class Base>
+static int resume_run(mobrob_ppo_engine_t* e, int N, const HazardIO* hio, const HazardCarve& hc, const TeamIO* tio, const TeamFill& tf,
+                      FrameHazardArgs<typename Base::Args>& hf, double*& hazard_dev) {
+  HazardArgs<typename Base::Args>& h = hf.h;
+  if (hio) {
+    if (const int rc = hazard_fill(e, *hio, N, hc, h)) return rc;
+    hazard_fill_frames(*hio, hf);
+    HIPC(hipMemcpyAsync(h.hazard_out, hio->hazard_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
+  }
+  hazard_dev = h.hazard_out;
+  if (tio) {
+    HIPC(hipMemcpyAsync(tf.out, tio->team_out, (size_t)N * 5 * 8, hipMemcpyHostToDevice, e->stream));
+    const int ran = !hio ? team_run<Base>(e, h.b, tf)
+                    : hio->frames ? team_run<FrameHazardTask<Base>>(e, hf, tf) : team_run<HazardTask<Base>>(e, h, tf);
+    if (ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
+    return ran;
+  }
+  return !hio ? eval_run<Base>(e, h.b, k_goal_task_fin<Base>)
+         : hio->frames ? eval_run<FrameHazardTask<Base>>(e, hf, k_goal_task_fin<FrameHazardTask<Base>>)
+                       : eval_run<HazardTask<Base>>(e, h, k_goal_task_fin<HazardTask<Base>>);
+}
 }  // extern "C++"
 
 // evaluate, with hazards when `hio` is not null (mobrob_ppo_evaluate_goal_env_hazards)
@@ -3557,11 +3605,12 @@ static int follow_resume_check(const mobrob_follow_resume_t* rs, const mobrob_fo
 
 // follow, with hazards when `hio` is not null (mobrob_ppo_follow_waypoints_hazards); one call of a resumable run when `rs` is not
 // null (mobrob_ppo_follow_waypoints_resume: no `start`, arrival / robot_out / hazard_out in and out), with teams when `tio` is not
-// null (mobrob_ppo_follow_waypoints_teams: a call of a run, team_out in and out)
+// null (mobrob_ppo_follow_waypoints_teams: a call of a run, team_out in and out), with timed waypoints when `sio` is not null
+// (mobrob_ppo_follow_waypoints_scheduled: ScheduledFollowTask in ResumeFollowTask's place, sched_out in and out)
 static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
                             const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
                             double* robot_out, float* path_out, float* trace_out, const HazardIO* hio,
-                            const mobrob_follow_resume_t* rs = nullptr, const TeamIO* tio = nullptr) {
+                            const mobrob_follow_resume_t* rs = nullptr, const TeamIO* tio = nullptr, const SchedIO* sio = nullptr) {
   if (!e || !env || !spec || (!start && !rs) || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
   EvalCall c{"follow", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
   if (hio) c.trace_extra = kHazardTraceExtra;
@@ -3592,6 +3641,8 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     if (const int rc = follow_resume_check(rs, spec, nw, robot_out, hio ? hio->hazard_out : nullptr)) return rc;
   if (tio)   // (only with rs: the entry point refuses a call without it)
     if (const int rc = team_check(*tio, N, rs->step0, robot_out)) return rc;
+  if (sio)   // (only with rs, likewise)
+    if (const int rc = sched_check(*sio, N, K, P, nw, robot_out)) return rc;
   const bool pathing = path_out && spec->path_stride > 0;
   const size_t n_rec = pathing ? (size_t)(spec->max_steps / spec->path_stride + 1) : 0;
   EvalCarve carve;
@@ -3600,12 +3651,16 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   if (hio) hazard_carve(carve, *hio, N, hc);
   const size_t o_state = carve.add(rs ? (size_t)N * 6 * 4 : 0), o_leg = carve.add(rs ? (size_t)N * 4 : 0),
                o_status = carve.add(rs ? (size_t)N * 4 : 0), o_entry = carve.add(rs ? (size_t)N * 4 : 0),
-               o_team = carve.add(tio ? (size_t)N * 5 * 8 : 0), o_stepped = carve.add(tio ? (size_t)N * 4 : 0);
+               o_team = carve.add(tio ? (size_t)N * 5 * 8 : 0), o_stepped = carve.add(tio ? (size_t)N * 4 : 0),
+               o_rel = carve.add(sio ? (size_t)N * K * 4 : 0), o_home = carve.add(sio ? (size_t)N * P * 4 : 0),
+               o_sched = carve.add(sio ? (size_t)N * 2 * 8 : 0);
   FrameHazardArgs<FollowArgs> hf{};    // the frames tasks' arguments hold the static tasks'
   FrameHazardArgs<ResumeArgs> hrf{};
+  FrameHazardArgs<ScheduledArgs> hsf{};
   HazardArgs<FollowArgs>& h = hf.h;
-  HazardArgs<ResumeArgs>& hr = hrf.h;   // the resumable task's arguments: its FollowArgs is the one filled below
-  FollowArgs& f = rs ? hr.b.f : h.b;
+  // the resumable task's arguments (the scheduled task holds them in turn): its FollowArgs is the one filled below
+  ResumeArgs& r = sio ? hsf.h.b.r : hrf.h.b;
+  FollowArgs& f = rs ? r.f : h.b;
   // no termination, no time limit: the robot only stops at its last waypoint
   if (const int rc = eval_prepare(e, c, eval_env_params(env, e->A, false, INT_MAX), carve, f.e)) return rc;
   float* start_dev = eval_at<float>(e, o_start);
@@ -3633,7 +3688,6 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
                         : eval_run<HazardFollowTask>(e, h, k_hazard_follow_fin);
   } else {
     // the run so far: arrival rows, accumulators, state
-    ResumeArgs& r = hr.b;
     r.step0 = rs->step0; r.leg_steps = rs->leg_steps;
     r.state = eval_at<float>(e, o_state); r.leg_used = eval_at<int>(e, o_leg);
     r.status = eval_at<int>(e, o_status); r.entry_steps = eval_at<int>(e, o_entry);
@@ -3641,23 +3695,23 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     HIPC(hipMemcpyAsync(f.e.robot_out, robot_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
     HIPC(hipMemcpyAsync(r.state, rs->state, (size_t)N * 6 * 4, hipMemcpyHostToDevice, e->stream));
     HIPC(hipMemcpyAsync(r.leg_used, rs->leg_used, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
-    if (hio) {
-      if (const int rc = hazard_fill(e, *hio, N, hc, hr)) return rc;
-      hazard_fill_frames(*hio, hrf);
-      HIPC(hipMemcpyAsync(hr.hazard_out, hio->hazard_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
+    TeamFill tf{};
+    if (tio)
+      tf = TeamFill{tio->tm->team_size, tio->tm->separation, tio->tm->cost, tio->tm->indicator != 0, eval_at<double>(e, o_team),
+                    eval_at<int>(e, o_stepped)};
+    if (sio) {
+      ScheduledArgs& sa = hsf.h.b;
+      int* rel_dev = eval_at<int>(e, o_rel);
+      float* home_dev = eval_at<float>(e, o_home);
+      sa.release = rel_dev; sa.home = home_dev; sa.sched_out = eval_at<double>(e, o_sched);
+      HIPC(hipMemcpyAsync(rel_dev, sio->sc->release, (size_t)N * K * 4, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(home_dev, sio->sc->home, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(sa.sched_out, sio->sched_out, (size_t)N * 2 * 8, hipMemcpyHostToDevice, e->stream));
+      ran = resume_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, hsf, hazard_dev);
+      if (ran >= 0) HIPC(hipMemcpyAsync(sio->sched_out, sa.sched_out, (size_t)N * 2 * 8, hipMemcpyDeviceToHost, e->stream));
+    } else {
+      ran = resume_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, hrf, hazard_dev);
     }
-    hazard_dev = hr.hazard_out;
-    if (tio) {
-      const TeamFill tf{tio->tm->team_size, tio->tm->separation, tio->tm->cost, tio->tm->indicator != 0, eval_at<double>(e, o_team),
-                        eval_at<int>(e, o_stepped)};
-      HIPC(hipMemcpyAsync(tf.out, tio->team_out, (size_t)N * 5 * 8, hipMemcpyHostToDevice, e->stream));
-      ran = !hio ? team_run<ResumeFollowTask>(e, r, tf)
-            : hio->frames ? team_run<FrameHazardTask<ResumeFollowTask>>(e, hrf, tf) : team_run<HazardTask<ResumeFollowTask>>(e, hr, tf);
-      if (ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
-    } else
-    ran = !hio ? eval_run<ResumeFollowTask>(e, r, k_goal_task_fin<ResumeFollowTask>)
-          : hio->frames ? eval_run<FrameHazardTask<ResumeFollowTask>>(e, hrf, k_goal_task_fin<FrameHazardTask<ResumeFollowTask>>)
-                        : eval_run<HazardTask<ResumeFollowTask>>(e, hr, k_goal_task_fin<HazardTask<ResumeFollowTask>>);
     if (ran >= 0) {
       HIPC(hipMemcpyAsync(rs->state, r.state, (size_t)N * 6 * 4, hipMemcpyDeviceToHost, e->stream));
       HIPC(hipMemcpyAsync(rs->leg_used, r.leg_used, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
@@ -3719,6 +3773,24 @@ int mobrob_ppo_follow_waypoints_teams(mobrob_ppo_engine_t* e, const mobrob_goal_
   const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
   return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
                           (hz || hzf) ? &hio : nullptr, resume, &tio);
+}
+
+int mobrob_ppo_follow_waypoints_scheduled(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                          const mobrob_hazards_t* hz, const mobrob_hazard_frames_t* hzf,
+                                          const mobrob_follow_resume_t* resume, const mobrob_teams_t* teams,
+                                          const mobrob_follow_schedule_t* schedule, const float* waypoints, const int32_t* n_waypoints,
+                                          int32_t* arrival, double* robot_out, double* hazard_out, double* team_out, double* sched_out,
+                                          float* path_out, float* trace_out) {
+  if (!resume || !schedule || !sched_out) return fail(MOBROB_ERR_INVALID, "follow: schedule: null argument");
+  if ((teams != nullptr) != (team_out != nullptr)) return fail(MOBROB_ERR_INVALID, "follow: schedule: team_out is needed with teams, and only then");
+  if (hz && hzf) return fail(MOBROB_ERR_INVALID, "follow: schedule: static hazards or hazard frames, not both");
+  if ((hz || hzf) != (hazard_out != nullptr)) return fail(MOBROB_ERR_INVALID, "follow: schedule: hazard_out is needed with hazards, and only then");
+  const TeamIO tio{teams, team_out};
+  const SchedIO sio{schedule, sched_out};
+  mobrob_hazards_t view;
+  const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
+  return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
+                          (hz || hzf) ? &hio : nullptr, resume, teams ? &tio : nullptr, &sio);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

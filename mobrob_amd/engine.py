@@ -448,7 +448,7 @@ class PPOEngine:
 
     def follow_waypoints(self, pos_dim, mix, dt=0.05, extent=3.0, reach_radius=0.3, goal_bonus=5.0, extra_bonus=0.0,
                          obs_noise=0.1, *, start=None, waypoints=None, n_waypoints=None, max_steps=1000, deterministic=True, seed=0,
-                         path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0, teams=None):
+                         path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0, teams=None, schedule=None):
         """The current policy as a tracker of given goal sequences (mobrob_ppo_follow_waypoints): robot i starts at rest on
         start[i] ([n][P]) and follows waypoints[i][:n_waypoints[i]] (waypoints [n][K][P], or [K][P] for all robots; n_waypoints
         None = K each), no time limit, no reset.  path_stride > 0 records positions; trace = (robots, steps): teacher-forcing
@@ -461,15 +461,18 @@ class PPOEngine:
         `leg_steps` alone the call starts a run.  Such a call adds `state` (the FollowState after the call; the one given is left
         as it was) and `status` [n] to the dict; steps, reached, reward_sum and the hazard sums are the run's, path and trace the
         call's.  teams: a goal_rules.Teams -> mobrob_ppo_follow_waypoints_teams (always a call of a run; without `resume` its
-        first), adding team_cost_sum, conflict_steps, first_conflict, min_team_clearance, closest_partner and `state.team`."""
+        first), adding team_cost_sum, conflict_steps, first_conflict, min_team_clearance, closest_partner and `state.team`.
+        schedule: a goal_rules.Schedule -> mobrob_ppo_follow_waypoints_scheduled (always a call of a run; without `resume` its
+        first: the state then takes release and home from it; with `resume` the state's are in force), adding hold_steps,
+        hold_drift, lateness and `state.sched`; trace rows of hold steps carry the flags 0, 0."""
         from .waypoints import FollowState, follow_inputs
-        if resume is not None or int(leg_steps) != 0 or teams is not None:
+        if resume is not None or int(leg_steps) != 0 or teams is not None or schedule is not None:
             if resume is None:
-                resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None)
+                resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule)
             elif not (start is None and waypoints is None and n_waypoints is None):
                 raise ValueError("follow_waypoints: a resumed call takes its robots and waypoints from `resume`")
             return self._follow_resume(pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, resume,
-                                       int(leg_steps), max_steps, deterministic, seed, path_stride, trace, hazards, teams)
+                                       int(leg_steps), max_steps, deterministic, seed, path_stride, trace, hazards, teams, schedule)
         if start is None or waypoints is None:
             raise ValueError("follow_waypoints: start and waypoints are needed unless `resume` continues a run")
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
@@ -504,12 +507,12 @@ class PPOEngine:
         return out
 
     def _follow_resume(self, pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, state, leg_steps,
-                       max_steps, deterministic, seed, path_stride, trace, hazards, teams=None):
+                       max_steps, deterministic, seed, path_stride, trace, hazards, teams=None, schedule=None):
         """One call of a run (mobrob_ppo_follow_waypoints_resume; with a MovingHazards mobrob_ppo_follow_waypoints_hazard_frames;
-        with teams mobrob_ppo_follow_waypoints_teams) on a copy of `state`."""
-        from ._lib import FollowResume, TeamsC
-        from .envs.goal_rules import Teams
-        from .waypoints import FollowState, team_result
+        with teams mobrob_ppo_follow_waypoints_teams; with a schedule mobrob_ppo_follow_waypoints_scheduled) on a copy of `state`."""
+        from ._lib import FollowResume, FollowScheduleC, TeamsC
+        from .envs.goal_rules import Schedule, Teams
+        from .waypoints import FollowState, schedule_result, team_result
         if not isinstance(state, FollowState):
             raise TypeError(f"follow_waypoints: resume must be a FollowState, not {type(state).__name__}")
         if (state.hazard is None) != (hazards is None):
@@ -520,6 +523,10 @@ class PPOEngine:
             if not isinstance(teams, Teams):
                 raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
             teams.check_robots(state.n_robots)
+        if (getattr(state, "release", None) is None) != (schedule is None):
+            raise ValueError("follow_waypoints: a run has a schedule in every call or in none (FollowState(..., schedule=Schedule))")
+        if schedule is not None and not isinstance(schedule, Schedule):
+            raise TypeError(f"schedule must be a mobrob_amd.envs.goal_rules.Schedule, not {type(schedule).__name__}")
         st = state.copy()
         n, K, P = st.waypoints.shape
         if P != int(pos_dim):
@@ -533,6 +540,11 @@ class PPOEngine:
         if teams is not None:
             st.team = np.ascontiguousarray(st.team, np.float64)
             if st.team.shape != (n, 5):
+                raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
+        if schedule is not None:
+            st.release, st.home = np.ascontiguousarray(st.release, np.int32), np.ascontiguousarray(st.home, F32)
+            st.sched = np.ascontiguousarray(st.sched, np.float64)
+            if st.release.shape != (n, K) or st.home.shape != (n, P) or st.sched.shape != (n, 2):
                 raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
         if st.state.shape != (n, 6) or st.robot.shape != (n, 4) or st.arrival.shape != (n, K) or st.leg_used.shape != (n,):
             raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
@@ -550,10 +562,19 @@ class PPOEngine:
         h, _keep = (None, None) if hazards is None else self._hazards_struct(hazards, n)
         tail = (_fp(st.waypoints), st.n_waypoints.ctypes.data_as(i32), st.arrival.ctypes.data_as(i32), st.robot.ctypes.data_as(dp),
                 None if h is None else st.hazard.ctypes.data_as(dp), _fp(path), _fp(tr))
+        tm = None
         if teams is not None:
             tm = TeamsC()
             tm.team_size, tm.separation, tm.cost, tm.indicator = teams.size, teams.separation, teams.cost, int(teams.indicator)
-            frames = isinstance(h, HazardFramesC)
+        frames = isinstance(h, HazardFramesC)
+        if schedule is not None:
+            sc = FollowScheduleC()
+            sc.release, sc.home = st.release.ctypes.data_as(i32), _fp(st.home)
+            r = check(self.lib.mobrob_ppo_follow_waypoints_scheduled(
+                self._h, C.byref(g), C.byref(sp), None if h is None or frames else C.byref(h), C.byref(h) if frames else None,
+                C.byref(rs), None if tm is None else C.byref(tm), C.byref(sc), *tail[:5],
+                None if tm is None else st.team.ctypes.data_as(dp), st.sched.ctypes.data_as(dp), *tail[5:]))
+        elif teams is not None:
             r = check(self.lib.mobrob_ppo_follow_waypoints_teams(
                 self._h, C.byref(g), C.byref(sp), None if h is None or frames else C.byref(h), C.byref(h) if frames else None,
                 C.byref(rs), C.byref(tm), *tail[:5], st.team.ctypes.data_as(dp), *tail[5:]))
@@ -571,6 +592,8 @@ class PPOEngine:
             out.update(self._hazard_result(st.hazard.copy()))
         if teams is not None:
             out.update(team_result(st.team))
+        if schedule is not None:
+            out.update(schedule_result(st))
         if path is not None:
             out["path"] = path
         return out

@@ -347,3 +347,115 @@ def team_fold(record, pos_xy, stepped, teams, step0=0):
         rec[:, 3] = np.where(s, np.where(closer, clear[t], best), rec[:, 3])
         rec[:, 4] = np.where(closer, partner[t], rec[:, 4])
     return rec
+
+
+# ---- timed waypoints: release steps and holds in a waypoint-following run.  This project's own rule; it is stated here once and
+# the device (csrc/kernels_follow.h: ScheduledFollowTask) and the host loop are held to it.
+SCHED_START = (0.0, np.nan)   # a robot's hold record before its first hold step
+
+
+class Schedule:
+    """Release steps for the waypoints of a run: `release` [n][K] (or [K], the same for every robot) integers >= 0, `home` [n][P]
+    finite (None: the robots' starts, filled in by FollowState).  Waypoint k of robot i may not be the goal in force in a step
+    whose 0-based GLOBAL number g is below release[i][k]; until then the robot holds at its anchor, under the policy:
+        holding(k, g) = k < n_waypoints[i] and g < release[i][k]
+        anchor(k)     = waypoints[i][k - 1] if k > 0 else home[i]
+        goal(k, g)    = anchor(k) if holding(k, g) else waypoints[i][min(k, n_waypoints[i] - 1)]
+    k is the robot's count of waypoints reached (the index of the waypoint it is on), so the goal of a step is a pure function of
+    (k, g) and nothing is carried for it.  A release earlier than its predecessor's never holds.  Checked on construction
+    (ValueError); entries past a robot's waypoint count are ignored."""
+
+    def __init__(self, release, home=None):
+        rel = np.asarray(release)
+        if rel.ndim not in (1, 2) or rel.size == 0 or not np.issubdtype(rel.dtype, np.integer) or rel.dtype == bool:
+            raise ValueError(f"release must be integers of shape [K] or [n, K], got {rel.dtype} of shape {rel.shape}")
+        if np.any(rel < 0) or np.any(rel > 2 ** 31 - 1):
+            raise ValueError("release steps must lie in 0 .. 2^31 - 1")
+        self.release = np.ascontiguousarray(rel, np.int32)
+        self.home = None
+        if home is not None:
+            h = np.asarray(home, np.float64)
+            if h.ndim != 2 or not np.all(np.isfinite(h)):
+                raise ValueError(f"home must be finite of shape [n, pos_dim], got shape {h.shape}")
+            self.home = np.ascontiguousarray(h, np.float32)
+
+    def for_robots(self, n, K, start=None):
+        """-> (release [n][K] int32, home [n][P] float32) for a run of n robots with K waypoint slots; a missing home is `start`"""
+        rel = self.release
+        if rel.ndim == 1:
+            rel = np.broadcast_to(rel, (n, rel.shape[0]))
+        if rel.shape[0] != n or rel.shape[1] > K:
+            raise ValueError(f"release must be [{n}, K'] or [K'] with K' <= {K}, got shape {self.release.shape}")
+        out = np.zeros((n, K), np.int32)
+        out[:, :rel.shape[1]] = rel
+        home = self.home if self.home is not None else start
+        if home is None or np.shape(home)[0] != n:
+            raise ValueError(f"home must have {n} rows, one per robot")
+        return out, np.ascontiguousarray(home, np.float32)
+
+    @staticmethod
+    def holding(release, n_waypoints, k, step):
+        """[n] bool: does robot i, on waypoint k[i], hold in the step with global number `step` ([n] or a scalar)?"""
+        release, nw, k = np.asarray(release), np.asarray(n_waypoints), np.asarray(k)
+        kk = np.minimum(k, release.shape[1] - 1)
+        return (k < nw) & (np.asarray(step) < release[np.arange(len(k)), kk])
+
+    @staticmethod
+    def goal(release, home, waypoints, n_waypoints, k, step):
+        """[n][P]: the goal in force of every robot in the step with global number `step` (a robot without waypoints: NaN)"""
+        wp, nw, k = np.asarray(waypoints), np.asarray(n_waypoints), np.asarray(k)
+        rows = np.arange(len(k))
+        hold = Schedule.holding(release, nw, k, step)
+        on = wp[rows, np.clip(np.minimum(k, nw - 1), 0, None)]
+        anchor = np.where((k > 0)[:, None], wp[rows, np.clip(k - 1, 0, None)], np.asarray(home, wp.dtype))
+        out = np.where(hold[:, None], anchor, on)
+        return np.where((nw > 0)[:, None], out, np.nan)
+
+    @staticmethod
+    def lateness(release, arrival):
+        """[n][K] float64: arrival[k] - release[k] (global steps; an arrival is 1-based, so a robot released at g that needs one
+        step is 1 late), NaN where the waypoint was not reached"""
+        arrival = np.asarray(arrival)
+        return np.where(arrival > 0, arrival.astype(np.float64) - np.asarray(release, np.float64), np.nan)
+
+
+def _fma32(a, b, c):
+    """float32 fma(a, b, c), correctly rounded: the product is exact in float64, the float64 sum is rounded to odd (TwoSum tells
+    which way the exact value lies), and the final rounding to float32 is then the one of the exact value"""
+    p, c = np.asarray(a, np.float32).astype(np.float64) * np.asarray(b, np.float32).astype(np.float64), np.asarray(c, np.float32).astype(np.float64)
+    s = p + c
+    v = s - p
+    err = (p - (s - v)) + (c - v)
+    even = (np.ascontiguousarray(s).view(np.int64) & 1) == 0
+    s = np.where((err != 0) & even, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def goal_distance32(goal, pos):
+    """The device's goal_dist (csrc/kernels_env.h) bit for bit: float32 differences, the squares summed by fused multiply-adds in
+    component order, the root taken in float64 and rounded once: [..., p], [..., p] -> [...] float32"""
+    d = np.asarray(goal, np.float32) - np.asarray(pos, np.float32)
+    s = np.zeros(d.shape[:-1], np.float32)
+    for j in range(d.shape[-1]):
+        s = _fma32(d[..., j], d[..., j], s)
+    return np.sqrt(s.astype(np.float64)).astype(np.float32)
+
+
+def schedule_fold(record, anchor, pos, held):
+    """The carried hold record after the steps of a call: record [n][2] float64 (hold steps run, the largest distance to the
+    anchor after a hold step -- NaN before the first), anchor [T][n][P] the goal in force in each step, pos [T][n][P] the
+    positions after it (float32: the device's), held [T][n] the robot's hold steps.  Returns a new [n][2]: the count continued,
+    the maximum of goal_distance32 taken in float32 step after step and widened."""
+    rec = np.array(record, np.float64)
+    held = np.asarray(held, bool)
+    T, n = held.shape
+    anchor, pos = np.asarray(anchor, np.float32), np.asarray(pos, np.float32)
+    if rec.shape != (n, 2) or anchor.shape != pos.shape or pos.shape[:2] != (T, n):
+        raise ValueError(f"record must be [{n}][2], anchor and pos [{T}][{n}][P], got {rec.shape}, {anchor.shape} and {pos.shape}")
+    for t in range(T):
+        h = held[t]
+        d = goal_distance32(anchor[t], pos[t]).astype(np.float64)
+        best = np.where(np.isnan(rec[:, 1]), 0.0, rec[:, 1])
+        rec[:, 0] += h
+        rec[:, 1] = np.where(h, np.maximum(best, d), rec[:, 1])
+    return rec

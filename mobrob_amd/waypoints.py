@@ -37,6 +37,18 @@ in an earlier call) counts where it stands; robots of different teams never see 
 A robot accounts only for the steps in which it stepped itself, so a pair is symmetric only while both move: a parked robot
 charges the one that passes it, not itself.  The cost changes nothing else.  A call with teams is always a call of a run.
 
+With `schedule` (a goal_rules.Schedule) the waypoints are TIMED: waypoint k of robot i may not be the goal in force in a step whose
+0-based global number g is below release[i][k].  Until then the robot HOLDS at its anchor -- the previous waypoint, `home[i]` (its
+start unless given) for k = 0 -- under the policy: it is stepped, observed, path-recorded, hazard- and team-checked as on any step
+and counts in `steps`, but a hold step (holding at the step's entry) ignores the reach test, adds nothing to reward_sum and leaves
+leg_used as it is.  The goal of step g is a pure function of (k, g), k the waypoints reached: anchor while g < release[i][k], else
+waypoint k; it is set before the observation of step g is taken.  The dict gains
+  hold_steps [n] hold steps run;  hold_drift [n] the largest distance to the anchor after a hold step (NaN: none);
+  lateness [n][K] arrival - release in global steps (NaN: not reached)
+and `state.sched` carries the first two.  final_distance is then the distance to the waypoint the robot is on, released or not.
+A call with a schedule is always a call of a run; the state holds `release` and `home` (changed by `replan` only), so on a
+continued call `schedule=` only says that the run is scheduled.  With every release 0 nothing differs from the run without.
+
 Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
 sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
 into the next call) and `status`, and takes the previous call's `state=`.  Call c covers the global steps step0 .. step0 +
@@ -105,9 +117,10 @@ class FollowState:
       arrival [n][K]    int32 global arrival steps, -1 = not reached;  leg_used [n] int32;  status [n] int32 (of the last call)
       hazard [n][4]     float64 cost sum, violation steps, first violation, min clearance -- or None without hazards
       team [n][5]       float64 team cost sum, conflict steps, first conflict, min clearance to a mate, that mate -- or None
+      release [n][K] int32, home [n][P] float32, sched [n][2] float64 hold steps, hold drift -- or None without a schedule
       waypoints [n][K][P] float32, n_waypoints [n] int32: the rows in force (changed by `replan` only)"""
 
-    def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False):
+    def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False, schedule=None):
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
         n, K, P = wp.shape
         self.waypoints, self.n_waypoints, self.step0 = wp, nw, 0
@@ -118,6 +131,16 @@ class FollowState:
         self.leg_used, self.status = np.zeros(n, np.int32), np.zeros(n, np.int32)
         self.hazard = np.tile(np.array([0.0, 0.0, -1.0, np.nan]), (n, 1)) if hazards else None
         self.team = np.tile(np.array([0.0, 0.0, -1.0, np.nan, -1.0]), (n, 1)) if teams else None
+        self.release = self.home = self.sched = None
+        if schedule is not None:
+            from .envs.goal_rules import SCHED_START, Schedule
+            if not isinstance(schedule, Schedule):
+                raise TypeError(f"schedule must be a mobrob_amd.envs.goal_rules.Schedule, not {type(schedule).__name__}")
+            self.release, self.home = schedule.for_robots(n, K, s)
+            if self.home.shape != (n, P):
+                raise ValueError(f"schedule: home must be [{n}, {P}], got shape {self.home.shape}")
+            self.release, self.home = self.release.copy(), self.home.copy()
+            self.sched = np.tile(np.array(SCHED_START), (n, 1))
 
     def copy(self):
         c = object.__new__(FollowState)
@@ -137,10 +160,12 @@ class FollowState:
     def reached(self):
         return self.robot[:, 2].astype(np.int64)
 
-    def replan(self, rows, waypoints, n_waypoints=None):
+    def replan(self, rows, waypoints, n_waypoints=None, release=None):
         """New waypoints for the robots `rows` ([m] indices): waypoints [m][K'][P] or [K'][P] (the same for each), counts
         n_waypoints [m] (None: K' each).  Those robots start over on their new rows -- reached = 0, arrival = -1, leg_used = 0 --
-        and keep position, velocity, reward sum, steps run, hazard sums and team sums.  K grows when K' is larger."""
+        and keep position, velocity, reward sum, steps run, hazard sums and team sums.  K grows when K' is larger.
+        In a scheduled run the replanned rows get `release` ([m][K'] or [K'] global steps; None: 0, released at once), their
+        `home` becomes where they are, and the hold record is carried.  `release` on a run without a schedule is refused."""
         rows = np.atleast_1d(np.asarray(rows))
         if rows.size == 0:
             return self
@@ -151,6 +176,14 @@ class FollowState:
         n, K, P = self.waypoints.shape
         _, wp, nw = follow_inputs(np.zeros((len(rows), P)), waypoints, n_waypoints, P)
         K2 = wp.shape[1]
+        scheduled = getattr(self, "release", None) is not None
+        if release is not None:
+            if not scheduled:
+                raise ValueError("replan: release steps need a run with a schedule (FollowState(..., schedule=Schedule))")
+            from .envs.goal_rules import Schedule
+            rel = Schedule(release).for_robots(len(rows), K2, np.zeros((len(rows), P)))[0]
+        if scheduled and K2 > K:
+            self.release = np.concatenate([self.release, np.zeros((n, K2 - K), np.int32)], axis=1)
         if K2 > K:
             self.waypoints = np.concatenate([self.waypoints, np.zeros((n, K2 - K, P), np.float32)], axis=1)
             self.arrival = np.concatenate([self.arrival, np.full((n, K2 - K), -1, np.int32)], axis=1)
@@ -160,10 +193,15 @@ class FollowState:
         self.arrival[rows] = -1
         self.robot[rows, 2] = 0.0
         self.leg_used[rows] = 0
+        if scheduled:
+            self.release[rows] = 0
+            if release is not None:
+                self.release[rows, :K2] = rel
+            self.home[rows] = self.state[rows, :P]
         return self
 
 
-def _check_run(state, leg_steps, max_steps, hazards, teams=None):
+def _check_run(state, leg_steps, max_steps, hazards, teams=None, schedule=None):
     """The run's values a call is given, checked as the engine checks them (ValueError)."""
     leg_steps = int(leg_steps)
     if leg_steps < 0:
@@ -181,6 +219,18 @@ def _check_run(state, leg_steps, max_steps, hazards, teams=None):
         if not isinstance(teams, Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
         teams.check_robots(state.n_robots)
+    if (getattr(state, "release", None) is None) != (schedule is None):
+        raise ValueError("a run has a schedule in every call or in none (FollowState(..., schedule=Schedule))")
+    if schedule is not None:
+        n, K, P = state.waypoints.shape
+        if state.release.shape != (n, K) or state.home.shape != (n, P) or state.sched.shape != (n, 2):
+            raise ValueError("state: release, home and sched do not fit the waypoints")
+        if np.any(state.release[np.arange(K)[None, :] < state.n_waypoints[:, None]] < 0) or not np.all(np.isfinite(state.home)):
+            raise ValueError("state: release steps must be >= 0 and home finite")
+        sc = state.sched
+        if (np.any(sc[:, 0] < 0) or np.any(sc[:, 0] > state.robot[:, 1]) or np.any(sc[:, 0] != np.floor(sc[:, 0]))
+                or np.any(np.isnan(sc[:, 1]) != (sc[:, 0] == 0)) or np.any(sc[:, 1] < 0) or np.any(np.isinf(sc[:, 1]))):
+            raise ValueError("state.sched is not a hold record a call returns")
     if not np.all(np.isfinite(state.state)) or not np.all(np.isfinite(state.robot[:, 0])):
         raise ValueError("state holds non-finite positions, velocities or reward sums")
     if np.any(state.leg_used < 0) or np.any(state.leg_used > leg_steps):
@@ -194,14 +244,18 @@ def _status(k, nw, leg_used, leg_steps):
     return NO_WAYPOINTS if nw == 0 else FINISHED if k >= nw else STALLED if leg_steps > 0 and leg_used >= leg_steps else GOING
 
 
-def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards=None, leg_steps=0, teams=None):
+def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards=None, leg_steps=0, teams=None,
+                 schedule=None):
     """The semantics, one robot after another on EnvWrapper's public API (make_env(i) -> the robot's env): one call of the run
     `state` is in (a fresh FollowState: the robots at rest on their starts).  Returns the dict and the state after the call.
     The simulator's noise is seeded per (robot, global step), so a run split into calls draws what one long call draws.
     With `teams` the loop stays robot after robot and keeps every robot's position after each step of the call (where it stands,
     for a step it did not take) and who stepped; after the last robot goal_rules.team_fold applies the rule.  The cost never feeds
-    back into a robot's motion, so this equals stepping the robots in lockstep exactly."""
-    from .envs.goal_rules import MovingHazards, hazard_cost, team_fold
+    back into a robot's motion, so this equals stepping the robots in lockstep exactly.
+    With `schedule` (the state holds release and home) the goal of every step is set per the rule before the step's observation
+    is taken, a hold step skips the reward sum, the arrival and the leg count, and goal_rules.schedule_fold folds the hold
+    record from the anchors and the float32 positions after the hold steps."""
+    from .envs.goal_rules import MovingHazards, hazard_cost, schedule_fold, team_fold
     st = state.copy()
     st.state = st.state.astype(np.float64)              # the host simulator's own precision, carried exactly
     wp, nw, step0 = st.waypoints, st.n_waypoints, st.step0
@@ -215,6 +269,14 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
     if teams is not None:
         team_xy, team_stepped = np.zeros((max_steps, n, 2)), np.zeros((max_steps, n), bool)
         team_xy[:, :, :min(P, 2)] = st.state[None, :, :min(P, 2)]
+    if schedule is not None:
+        rel, home = st.release, st.home
+        held, held_anchor, held_pos = np.zeros((max_steps, n), bool), np.zeros((max_steps, n, P), np.float32), np.zeros((max_steps, n, P), np.float32)
+
+    def goal_of(i, k, g):                                # -> (the goal in force of robot i, on waypoint k, in global step g; holding?)
+        if schedule is not None and k < nw[i] and g < rel[i, k]:
+            return (wp[i, k - 1] if k > 0 else home[i]), True
+        return wp[i, k], False
     for i in range(n):
         pos, vel = st.state[i, :P].copy(), st.state[i, 3:3 + P].copy()
         k, leg_used, ran = int(st.robot[i, 2]), int(st.leg_used[i]), 0
@@ -233,7 +295,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
                 if not hasattr(env.env, "vel"):
                     raise TypeError("resuming a moving robot needs a simulator whose velocity can be set (env.env.vel)")
                 env.env.vel = vel.copy()
-            env.set_goal(wp[i, k])
+            goal, hold = goal_of(i, k, step0)
+            env.set_goal(goal)
             for t in range(max_steps):
                 g = step0 + t                          # the global step
                 if moving:                             # the frame in force at the check after this step
@@ -244,7 +307,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
                 obs = env.get_obs()
                 a, _ = model.predict(obs, deterministic=deterministic)
                 _, r, _, _, info = env.step(a)
-                st.robot[i, 0] += float(r)
+                if not hold:                           # a hold step's reward is progress towards a place the robot waits at
+                    st.robot[i, 0] += float(r)
                 st.robot[i, 1] += 1
                 ran = t + 1
                 pos = np.asarray(env.get_pos(), np.float64)[:P]
@@ -259,16 +323,21 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
                     h[3] = min(np.inf if np.isnan(h[3]) else h[3], hazard_cost(pos, rows)[1])
                 if path is not None and (t + 1) % path_stride == 0:
                     path[(t + 1) // path_stride, i] = pos
-                if env.reached():
+                if hold:                               # no arrival, and waiting is not charged to the leg
+                    held[t, i], held_anchor[t, i], held_pos[t, i] = True, goal, pos
+                elif env.reached():
                     st.arrival[i, k] = g + 1
                     k, leg_used = k + 1, 0
                     if k == nw[i]:
                         break
-                    env.set_goal(wp[i, k])
                 elif leg_steps > 0:
                     leg_used += 1
                     if leg_used >= leg_steps:
                         break
+                nxt, hold = goal_of(i, k, g + 1)       # the goal of the next step, set before its observation is taken
+                if nxt is not goal and not np.array_equal(nxt, goal):
+                    env.set_goal(nxt)
+                goal = nxt
             vel = np.asarray(getattr(env.env, "vel", np.zeros(P)), np.float64)[:P]
             if hazards is not None:
                 env.set_hazards(None)
@@ -281,6 +350,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
             path[ran // path_stride + 1:, i] = pos
     if teams is not None:
         st.team = team_fold(st.team, team_xy, team_stepped, teams, step0)
+    if schedule is not None:
+        st.sched = schedule_fold(st.sched, held_anchor, held_pos, held)
     st.step0 = step0 + max_steps
     out = {"arrival": st.arrival.astype(np.int64), "reached": st.reached, "steps": st.robot[:, 1].astype(np.int64),
            "reward_sum": st.robot[:, 0].copy(), "final_distance": final_distance, "trace": None, "persistent": None,
@@ -290,9 +361,18 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
                     "first_violation": st.hazard[:, 2].astype(np.int64), "min_clearance": st.hazard[:, 3].copy()})
     if teams is not None:
         out.update(team_result(st.team))
+    if schedule is not None:
+        out.update(schedule_result(st))
     if path is not None:
         out["path"] = path
     return out
+
+
+def schedule_result(state):
+    """The keys a scheduled run adds to a call's dict, from the state after the call."""
+    from .envs.goal_rules import Schedule
+    return {"hold_steps": state.sched[:, 0].astype(np.int64), "hold_drift": state.sched[:, 1].copy(),
+            "lateness": Schedule.lateness(state.release, state.arrival)}
 
 
 def team_result(team):
@@ -302,14 +382,16 @@ def team_result(team):
 
 
 def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *, max_steps=1000, deterministic=True, seed=0,
-                     path_stride=0, hazards=None, state=None, leg_steps=0, teams=None):
+                     path_stride=0, hazards=None, state=None, leg_steps=0, teams=None, schedule=None):
     """Every robot i follows waypoints[i][:n_waypoints[i]] from start[i] under `model` (a PPO, or for the host path anything
     with `.predict`).  `env`: a DeviceGoalVecEnv (device path), an EnvWrapper, or an env name for `get_env` (host path; a
     fresh environment per robot for a name, the given one reused robot after robot otherwise).  Returns the dict described in
     the module docstring.  hazards: a goal_rules.Hazards or MovingHazards (hazard costs, see the module docstring).
     state: the `state` a previous call returned -- this call continues that run (start / waypoints / n_waypoints must then be
     None: the robots are where they were, on the waypoints the state holds).  leg_steps: step budget per waypoint (0: none).
-    teams: a goal_rules.Teams (separation costs between team-mates, see the module docstring)."""
+    teams: a goal_rules.Teams (separation costs between team-mates, see the module docstring).
+    schedule: a goal_rules.Schedule (release steps and holds, see the module docstring); with `state`, which holds the release
+    steps in force, it only says that the run is scheduled."""
     from .envs.vec_env import DeviceGoalVecEnv
     from .envs.wrapper import EnvWrapper, TimeLimit, get_env
     max_steps, path_stride = int(max_steps), int(path_stride)
@@ -321,10 +403,11 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         raise ValueError("start and waypoints are needed unless `state` continues a run")
     if isinstance(env, DeviceGoalVecEnv):
         if state is None:
-            state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams is not None)
-        _check_run(state, leg_steps, max_steps, hazards, teams)
+            state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams is not None, schedule)
+        _check_run(state, leg_steps, max_steps, hazards, teams, schedule)
         return env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
-                          path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps, teams=teams)
+                          path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps, teams=teams,
+                          schedule=schedule)
     if isinstance(env, str):
         name = env
 
@@ -341,20 +424,21 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         def make_env(i):
             return env
     if state is None:
-        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None)
+        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule)
     elif isinstance(state, FollowState) and state.waypoints.shape[2] != pos_dim:
         raise ValueError(f"state has {state.waypoints.shape[2]} position dimensions, the environment {pos_dim}")
-    leg_steps = _check_run(state, leg_steps, max_steps, hazards, teams)
-    return _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps, teams)
+    leg_steps = _check_run(state, leg_steps, max_steps, hazards, teams, schedule)
+    return _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps, teams, schedule)
 
 
 def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, rounds, leg_steps=0, n_waypoints=None,
-                           deterministic=True, seed=0, hazards=None, teams=None):
+                           deterministic=True, seed=0, hazards=None, teams=None, schedule=None):
     """A planner's loop around the tracker: `rounds` calls of `horizon` steps each, one run (see the module docstring).  After
     every round but the last, `planner(positions [n][P], status [n], reached [n])` returns {robot index: new waypoints [k][P]}
     (or None / {} for no change), applied through FollowState.replan.  The loop ends early once no robot is going or stalled
     and the planner changes nothing.  Returns the last call's dict plus `round_status` [rounds run][n].  teams: a
-    goal_rules.Teams; the planner callback is unchanged (the team sums are in the returned dict and in its `state`)."""
+    goal_rules.Teams; the planner callback is unchanged (the team sums are in the returned dict and in its `state`).  schedule: a
+    goal_rules.Schedule; a planner that returns {robot: (waypoints, release)} gives the new waypoints release steps (global)."""
     horizon, rounds = int(horizon), int(rounds)
     if horizon < 1 or rounds < 1:
         raise ValueError("horizon and rounds must be >= 1")
@@ -363,14 +447,17 @@ def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, ro
         first = state is None
         out = follow_waypoints(model, env, start if first else None, waypoints if first else None, n_waypoints if first else None,
                                max_steps=horizon, deterministic=deterministic, seed=seed, hazards=hazards, state=state,
-                               leg_steps=leg_steps, teams=teams)
+                               leg_steps=leg_steps, teams=teams, schedule=schedule)
         state = out["state"]
         statuses.append(out["status"].copy())
         if r + 1 == rounds:
             break
         plan = planner(np.array(state.positions), out["status"].copy(), out["reached"].copy()) or {}
         for robot, w in plan.items():
-            state.replan([int(robot)], np.asarray(w, np.float64)[None])
+            if schedule is not None and isinstance(w, tuple):
+                state.replan([int(robot)], np.asarray(w[0], np.float64)[None], release=np.asarray(w[1])[None])
+            else:
+                state.replan([int(robot)], np.asarray(w, np.float64)[None])
         if not plan and not np.any((out["status"] == GOING) | (out["status"] == STALLED)):
             break
     out["round_status"] = np.stack(statuses)
