@@ -31,6 +31,11 @@ release[k]; until then the robot holds at the previous waypoint (its start for k
 shorthand for delays: robot m of a team (robot i without --team-size) gets every waypoint released m * S steps later.  Two lines
 report the mean hold steps per robot and the largest drift from an anchor while holding.  With --team-size, a stagger of the
 time a robot needs to clear a crossing is the one-line demonstration that delays remove team conflicts.
+
+`--walls FILE.npy` ([M][4]: centre x, y and half extents hx, hy of M axis-aligned boxes) checks every step against walls:
+contact of the robot's footprint (`--robot-radius R`, default 0.1) and crossing of the step's segment, which also sees a step that
+jumps a thin wall.  `--arena` adds the reference's turtlebot3 enclosure (four boxes, 2.98 m outside, 0.265 m thick).  Three lines
+report the contact rate, the crossing rate (robots with such a step) and the minimum clearance to a wall.  Walls block nothing.
 """
 import argparse
 import os
@@ -58,11 +63,11 @@ def check_chain(max_steps, horizon, leg_steps):
 
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
-           release=None, stagger=0):
+           release=None, stagger=0, walls=None, arena=False, robot_radius=0.1):
     calls = check_chain(max_steps, horizon, leg_steps)
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
-    from mobrob_amd.envs.goal_rules import Hazards, MovingHazards, Schedule, Teams
+    from mobrob_amd.envs.goal_rules import Hazards, MovingHazards, Schedule, Teams, Walls
     from mobrob_amd.envs.wrapper import ROBOT_DIMS, KinematicSim
     from mobrob_amd.waypoints import follow_waypoints
     policy = load_policy(env_name, policy_name) if policy is None else policy
@@ -80,11 +85,17 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         hz = MovingHazards(fr[:, :, :2], fr[None, :, :, 2], frame_steps=int(frame_steps), loop=bool(hazard_loop), indicator=False)
     teams = None if team_size is None else Teams(int(team_size), float(separation))   # (a ValueError names what is wrong)
     schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
+    wl = None
+    if walls is not None or arena:
+        boxes = np.zeros((0, 4)) if walls is None else np.asarray(walls, np.float64)
+        if boxes.ndim != 2 or boxes.shape[1] != 4:
+            raise ValueError(f"--walls must hold [M][4] (cx, cy, hx, hy), got shape {boxes.shape}")
+        wl = Walls(np.concatenate([boxes, Walls.enclosure()]) if arena else boxes, radius=float(robot_radius), indicator=False)
     r = follow_waypoints(policy, env, start, waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
-                         leg_steps=leg_steps, teams=teams, schedule=schedule)
+                         leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
     for steps in calls[1:]:                                # the run, continued call after call
         r = follow_waypoints(policy, env, max_steps=steps, deterministic=True, seed=seed, hazards=hz, state=r["state"],
-                             leg_steps=leg_steps, teams=teams, schedule=schedule)
+                             leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
     K = r["arrival"].shape[1]
     done = r["reached"] == K
     last = r["arrival"][done, K - 1]
@@ -100,6 +111,11 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     if schedule is not None:
         print(f"mean hold steps: {float(np.mean(r['hold_steps']))}")
         print(f"maximum hold drift: {float(np.nanmax(r['hold_drift'])) if np.any(r['hold_steps'] > 0) else float('nan')}")
+    if wl is not None:
+        clear = r["min_wall_clearance"]
+        print(f"wall contact rate: {float(np.mean(r['contact_steps'] > 0))}")
+        print(f"wall crossing rate: {float(np.mean(r['crossing_steps'] > 0))}")
+        print(f"minimum wall clearance: {float(np.nanmin(clear)) if np.any(~np.isnan(clear)) else float('nan')}")
     return r
 
 
@@ -154,6 +170,9 @@ if __name__ == "__main__":
     ap.add_argument("--team-size", type=int, default=None, help="teams of this many consecutive robots (1, 2, 4, 8, 16): report separation costs")
     ap.add_argument("--separation", type=float, default=0.3, help="distance team-mates must keep")
     ap.add_argument("--release", type=str, default=None, help="[K] or [n][K] release steps of the waypoints (.npy, integers)")
+    ap.add_argument("--walls", type=str, default=None, help="[M][4] boxes cx, cy, hx, hy (.npy): report wall contacts and crossings")
+    ap.add_argument("--arena", action="store_true", default=False, help="add the reference's turtlebot3 enclosure to the walls")
+    ap.add_argument("--robot-radius", type=float, default=0.1, help="the robot's footprint for wall contact")
     ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
     args = ap.parse_args()
     try:
@@ -164,4 +183,5 @@ if __name__ == "__main__":
            hazards=None if args.hazards is None else (np.load(args.hazards), args.hazard_size), horizon=args.horizon,
            leg_steps=args.leg_steps, hazard_frames=None if args.hazard_frames is None else np.load(args.hazard_frames),
            frame_steps=args.frame_steps, hazard_loop=args.hazard_loop, team_size=args.team_size, separation=args.separation,
-           release=None if args.release is None else np.load(args.release), stagger=args.stagger)
+           release=None if args.release is None else np.load(args.release), stagger=args.stagger,
+           walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius)

@@ -715,6 +715,55 @@ int mobrob_ppo_follow_waypoints_scheduled(mobrob_ppo_engine_t* e, const mobrob_g
                                           double* sched_out /* [n][2] in / out */, float* path_out /* or NULL */,
                                           float* trace_out /* or NULL */);
 
+/* ---- walls: box contact and crossing checks in waypoint-following runs -----------------------------------------------------------
+ * One call of a run (mobrob_ppo_follow_waypoints_scheduled, with `teams` and `schedule` optional: NULL = none, and team_out /
+ * sched_out are then NULL) whose robots are checked against WALLS: axis-aligned boxes (cx, cy, hx, hy), hx, hy >= 0 half extents,
+ * up to 1024 per scene, shared or per robot by a scene index exactly as mobrob_hazards_t.  The check is observational: dynamics,
+ * rewards, arrivals, status, hazard_out, team_out, sched_out, path and trace are the bits of the call without walls.  The rule
+ * (mobrob_amd/envs/goal_rules.py: wall_check): after the step with 0-based global number g a robot that stepped has pre-step xy a
+ * and post-step xy p (x and y only, for drones too; a is where the previous step ended, or the carried position).  In float32,
+ * every operation rounded on its own:
+ *     qx = |px - cx| - hx    qy = |py - cy| - hy    sdf = sqrt(max(qx, 0)^2 + max(qy, 0)^2) + min(max(qx, qy), 0)
+ *     contact: sdf <= radius adds (radius - sdf) to the step's sum; clear_w = sdf - radius; sdf == radius adds exactly 0
+ *     mx = 0.5 (ax + px) - cx, my likewise, ex = 0.5 (px - ax), ey = 0.5 (py - ay)
+ *     hit_w = not(|mx| > hx + |ex| or |my| > hy + |ey| or |mx ey - my ex| > hx |ey| + hy |ex|)   (segment against the closed box)
+ * The sum runs over four partial sums -- quarter q: walls q, q + 4, ... -- combined as (p0 + p1) + (p2 + p3), `cost` applied once
+ * afterwards (indicator: cost > 0); the (clearance, wall) minimum over the same quarters and exchanges, the smaller clearance
+ * winning, then the smaller index; the crossing flag is the OR over all walls.
+ *   wall_out  [n][7] float64, in / out, carried like hazard_out: cost sum, contact steps (cost > 0), first contact step (global,
+ *             1-based, -1 = none), minimum clearance (NaN: no step run yet in the run; +inf without walls), the wall's index at
+ *             that minimum (first attainment; -1 = none), crossing steps, first crossing step.  A run starts from 0, 0, -1, NaN,
+ *             -1, 0, -1; a run split into calls ends with the wall_out of one long call.
+ *   kernels   k_goal64_tile<DP, WallTask<...>>: the robot lane keeps its pre-step xy in a second [16][2] LDS block, the check runs
+ *             on all 64 lanes as (robot, quarter), a shared scene is staged in LDS (16 bytes a wall).  Per-step path: the same
+ *             operations in one thread inside k_goal_task_step<WallTask<...>>.  Evaluation takes no walls: resets teleport.
+ * MOBROB_ERR_INVALID before any launch or copy, the in / out arrays left as given, besides every check of the underlying call,
+ * for: a NULL resume, walls or wall_out, team_out / sched_out / hazard_out without their argument or the reverse, n_scenes < 1,
+ * max_walls outside 0 .. 1024, a NULL box table with max_walls > 0, several scenes without a scene index, a scene index or a count
+ * out of range, a box in use that is not finite or has a negative half extent, radius or cost negative or non-finite, a carried
+ * wall record no call returns, a scene whose tile would need more LDS than the device allows a workgroup. */
+typedef struct mobrob_walls {
+  int32_t n_scenes;          /* S >= 1                                                  */
+  int32_t max_walls;         /* M, row stride, 0 .. 1024                                */
+  const float* boxes;        /* [S][M][4]: cx, cy, hx, hy (hx, hy >= 0, finite)         */
+  const int32_t* n_walls;    /* [S] counts 0 .. M, or NULL = M                          */
+  const int32_t* scene;      /* [n_robots] scene of each robot, or NULL (needs S == 1)  */
+  float radius;              /* the robot's footprint, >= 0                             */
+  float cost;                /* cost per unit of intrusion, >= 0                        */
+  int32_t indicator;         /* a step's cost is (cost > 0)                             */
+} mobrob_walls_t;
+int mobrob_ppo_follow_waypoints_walls(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                      const mobrob_hazards_t* hz /* or NULL */, const mobrob_hazard_frames_t* hzf /* or NULL; not both */,
+                                      const mobrob_follow_resume_t* resume, const mobrob_teams_t* teams /* or NULL */,
+                                      const mobrob_follow_schedule_t* schedule /* or NULL */, const mobrob_walls_t* walls,
+                                      const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                      int32_t* arrival /* [n][K] in / out */, double* robot_out /* [n][4] in / out */,
+                                      double* hazard_out /* [n][4] in / out, NULL iff no hazards */,
+                                      double* team_out /* [n][5] in / out, NULL iff no teams */,
+                                      double* sched_out /* [n][2] in / out, NULL iff no schedule */,
+                                      double* wall_out /* [n][7] in / out */, float* path_out /* or NULL */,
+                                      float* trace_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

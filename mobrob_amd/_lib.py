@@ -94,6 +94,12 @@ class FollowScheduleC(C.Structure):  # mobrob_follow_schedule_t
     _fields_ = [("release", C.POINTER(C.c_int32)), ("home", C.POINTER(C.c_float))]
 
 
+class WallsC(C.Structure):  # mobrob_walls_t
+    _fields_ = [("n_scenes", C.c_int32), ("max_walls", C.c_int32), ("boxes", C.POINTER(C.c_float)),
+                ("n_walls", C.POINTER(C.c_int32)), ("scene", C.POINTER(C.c_int32)), ("radius", C.c_float), ("cost", C.c_float),
+                ("indicator", C.c_int32)]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -181,6 +187,11 @@ SYMBOLS = {
                                                         C.POINTER(FollowScheduleC), _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                         C.POINTER(C.c_double), _F, _F]),
+    "mobrob_ppo_follow_waypoints_walls": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), C.POINTER(HazardsC),
+                                                    C.POINTER(HazardFramesC), C.POINTER(FollowResume), C.POINTER(TeamsC),
+                                                    C.POINTER(FollowScheduleC), C.POINTER(WallsC), _F, C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _F, _F]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

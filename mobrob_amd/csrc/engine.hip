@@ -53,6 +53,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_follow.h"
 #include "kernels_hazard.h"
 #include "kernels_team.h"
+#include "kernels_wall.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -3460,11 +3461,79 @@ static int sched_check(const SchedIO& sio, int N, int K, int P, const std::vecto
   return MOBROB_OK;
 }
 
+// ---- walls (mobrob_ppo_follow_waypoints_walls): checks of the scene and of the carried record, the run of a task wrapped in WallTask ----
+struct WallIO {
+  const mobrob_walls_t* wl;
+  double* wall_out;           // [N][7] in / out
+};
+struct WallFill {             // the wall fields of WallArgs (after eval_prepare grew eval_buf)
+  const float* boxes;
+  const int* nwall;
+  const int* scene;
+  int M;
+  float radius, coef;
+  int indicator;
+  double* out;
+};
+static int wall_check(const WallIO& wio, int N, int step0, const double* robot_out, std::vector<int32_t>& counts) {
+  const mobrob_walls_t* wl = wio.wl;
+  const int S = wl->n_scenes, M = wl->max_walls;
+  if (S < 1) return fail(MOBROB_ERR_INVALID, "follow: walls: n_scenes must be >= 1");
+  if (M < 0 || M > kWallMax) return fail(MOBROB_ERR_INVALID, "follow: walls: max_walls must lie in 0 .. %d", kWallMax);
+  if (M > 0 && !wl->boxes) return fail(MOBROB_ERR_INVALID, "follow: walls: null box table");
+  if (!wl->scene && S > 1) return fail(MOBROB_ERR_INVALID, "follow: walls: %d scenes need a scene index per robot", S);
+  if (!(std::isfinite(wl->radius) && wl->radius >= 0.f)) return fail(MOBROB_ERR_INVALID, "follow: walls: radius must be finite and >= 0");
+  if (!(std::isfinite(wl->cost) && wl->cost >= 0.f)) return fail(MOBROB_ERR_INVALID, "follow: walls: cost must be finite and >= 0");
+  counts.assign(S, M);
+  for (int s = 0; s < S; ++s) {
+    if (wl->n_walls) counts[s] = wl->n_walls[s];
+    if (counts[s] < 0 || counts[s] > M) return fail(MOBROB_ERR_INVALID, "follow: walls: n_walls[%d] = %d outside 0 .. %d", s, counts[s], M);
+    for (int i = 0; i < counts[s]; ++i) {
+      const float* b = wl->boxes + ((size_t)s * M + i) * 4;
+      if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]) && b[2] >= 0.f && b[3] >= 0.f))
+        return fail(MOBROB_ERR_INVALID, "follow: walls: box %d of scene %d is not finite or has a negative half extent", i, s);
+    }
+  }
+  if (wl->scene)
+    for (int i = 0; i < N; ++i)
+      if (wl->scene[i] < 0 || wl->scene[i] >= S)
+        return fail(MOBROB_ERR_INVALID, "follow: walls: scene[%d] = %d outside 0 .. %d", i, wl->scene[i], S - 1);
+  for (int i = 0; i < N; ++i) {
+    const double* o = wio.wall_out + (size_t)i * 7;
+    const double steps = robot_out[(size_t)i * 4 + 1];
+    const int m = counts[wl->scene ? wl->scene[i] : 0];
+    const auto count = [&](double v) { return v >= 0.0 && v <= steps && v == std::floor(v); };
+    const auto first = [&](double v) { return v >= -1.0 && v <= (double)step0 && v == std::floor(v); };
+    const bool sums = std::isfinite(o[0]) && o[0] >= 0.0 && count(o[1]) && count(o[5]) && first(o[2]) && first(o[6]);
+    const bool wall = o[4] == -1.0 || (o[4] == std::floor(o[4]) && o[4] >= 0.0 && o[4] < (double)m);
+    const bool clear = std::isnan(o[3]) == (steps == 0.0);
+    if (!(sums && wall && clear))
+      return fail(MOBROB_ERR_INVALID, "follow: walls: carried wall record of robot %d is not one a call returns", i);
+  }
+  return MOBROB_OK;
+}
+
+// the task Task with teams when `tio`, else on its own
+template <class Task>
+static int run_with_teams(mobrob_ppo_engine_t* e, const typename Task::Args& a, const TeamIO* tio, const TeamFill& tf) {
+  return tio ? team_run<Task>(e, a, tf) : eval_run<Task>(e, a, k_goal_task_fin<Task>);
+}
+// ... wrapped in WallTask when `wio` (pre_off: where the tile's pre-step block starts, after everything the wrapped task keeps in LDS)
+template <class Task>
+static int run_with_walls(mobrob_ppo_engine_t* e, const typename Task::Args& a, const WallIO* wio, const WallFill& wf, const TeamIO* tio,
+                          const TeamFill& tf) {
+  if (!wio) return run_with_teams<Task>(e, a, tio, tf);
+  const WallArgs<typename Task::Args> w{a, wf.boxes, wf.nwall, wf.scene, wf.M, wf.radius, wf.coef, wf.indicator,
+                                        (int)WallTask<Task>::base_lds_floats(a), wf.out};
+  return run_with_teams<WallTask<Task>>(e, w, tio, tf);
+}
+
 // One call of a run on the resumable task Base (ResumeFollowTask, ScheduledFollowTask), filled in hf.h.b: with hazards when
-// `hio`, with teams when `tio`.  Uploads the carried hazard and team records, runs, and downloads the team record.
+// `hio`, with walls when `wio`, with teams when `tio`.  Uploads the carried hazard and team records, runs, and downloads the team
+// record (the wall record is the caller's to move: its buffers are filled before the call).
 template <class Base>
 static int resume_run(mobrob_ppo_engine_t* e, int N, const HazardIO* hio, const HazardCarve& hc, const TeamIO* tio, const TeamFill& tf,
-                      FrameHazardArgs<typename Base::Args>& hf, double*& hazard_dev) {
+                      FrameHazardArgs<typename Base::Args>& hf, double*& hazard_dev, const WallIO* wio, const WallFill& wf) {
   HazardArgs<typename Base::Args>& h = hf.h;
   if (hio) {
     if (const int rc = hazard_fill(e, *hio, N, hc, h)) return rc;
@@ -3472,16 +3541,12 @@ static int resume_run(mobrob_ppo_engine_t* e, int N, const HazardIO* hio, const 
     HIPC(hipMemcpyAsync(h.hazard_out, hio->hazard_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
   }
   hazard_dev = h.hazard_out;
-  if (tio) {
-    HIPC(hipMemcpyAsync(tf.out, tio->team_out, (size_t)N * 5 * 8, hipMemcpyHostToDevice, e->stream));
-    const int ran = !hio ? team_run<Base>(e, h.b, tf)
-                    : hio->frames ? team_run<FrameHazardTask<Base>>(e, hf, tf) : team_run<HazardTask<Base>>(e, h, tf);
-    if (ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
-    return ran;
-  }
-  return !hio ? eval_run<Base>(e, h.b, k_goal_task_fin<Base>)
-         : hio->frames ? eval_run<FrameHazardTask<Base>>(e, hf, k_goal_task_fin<FrameHazardTask<Base>>)
-                       : eval_run<HazardTask<Base>>(e, h, k_goal_task_fin<HazardTask<Base>>);
+  if (tio) HIPC(hipMemcpyAsync(tf.out, tio->team_out, (size_t)N * 5 * 8, hipMemcpyHostToDevice, e->stream));
+  const int ran = !hio ? run_with_walls<Base>(e, h.b, wio, wf, tio, tf)
+                  : hio->frames ? run_with_walls<FrameHazardTask<Base>>(e, hf, wio, wf, tio, tf)
+                                : run_with_walls<HazardTask<Base>>(e, h, wio, wf, tio, tf);
+  if (tio && ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
+  return ran;
 }
 }  // extern "C++"
 
@@ -3606,11 +3671,13 @@ static int follow_resume_check(const mobrob_follow_resume_t* rs, const mobrob_fo
 // follow, with hazards when `hio` is not null (mobrob_ppo_follow_waypoints_hazards); one call of a resumable run when `rs` is not
 // null (mobrob_ppo_follow_waypoints_resume: no `start`, arrival / robot_out / hazard_out in and out), with teams when `tio` is not
 // null (mobrob_ppo_follow_waypoints_teams: a call of a run, team_out in and out), with timed waypoints when `sio` is not null
-// (mobrob_ppo_follow_waypoints_scheduled: ScheduledFollowTask in ResumeFollowTask's place, sched_out in and out)
+// (mobrob_ppo_follow_waypoints_scheduled: ScheduledFollowTask in ResumeFollowTask's place, sched_out in and out), with walls when
+// `wio` is not null (mobrob_ppo_follow_waypoints_walls: WallTask around the run's task, wall_out in and out)
 static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
                             const float* start, const float* waypoints, const int32_t* n_waypoints, int32_t* arrival,
                             double* robot_out, float* path_out, float* trace_out, const HazardIO* hio,
-                            const mobrob_follow_resume_t* rs = nullptr, const TeamIO* tio = nullptr, const SchedIO* sio = nullptr) {
+                            const mobrob_follow_resume_t* rs = nullptr, const TeamIO* tio = nullptr, const SchedIO* sio = nullptr,
+                            const WallIO* wio = nullptr) {
   if (!e || !env || !spec || (!start && !rs) || !waypoints || !arrival || !robot_out) return fail(MOBROB_ERR_INVALID, "follow: null argument");
   EvalCall c{"follow", spec->n_robots, spec->max_steps, spec->deterministic, spec->seed, spec->trace_robots, spec->trace_steps, trace_out};
   if (hio) c.trace_extra = kHazardTraceExtra;
@@ -3643,6 +3710,19 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     if (const int rc = team_check(*tio, N, rs->step0, robot_out)) return rc;
   if (sio)   // (only with rs, likewise)
     if (const int rc = sched_check(*sio, N, K, P, nw, robot_out)) return rc;
+  std::vector<int32_t> wall_counts;
+  if (wio) {   // (only with rs, likewise)
+    if (const int rc = wall_check(*wio, N, rs->step0, robot_out, wall_counts)) return rc;
+    if (e->fused.enabled && e->fused.H == 64) {   // the tile kernel's LDS: actor, the hazards' blocks, the walls' blocks
+      const size_t hz_floats = hio ? 32 + (hio->hz->scene ? 0 : 3 * (size_t)hio->hz->max_hazards) : 32;
+      const size_t tile = eval64_lds_bytes(e->Dp) + (hz_floats + 32 + (wio->wl->scene ? 0 : 4 * (size_t)wio->wl->max_walls)) * sizeof(float);
+      int limit = 0;
+      if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+      if (tile > (size_t)limit)
+        return fail(MOBROB_ERR_INVALID, "follow: walls: the tile kernel needs %zu bytes of LDS with this scene, the device allows %d per workgroup",
+                    tile, limit);
+    }
+  }
   const bool pathing = path_out && spec->path_stride > 0;
   const size_t n_rec = pathing ? (size_t)(spec->max_steps / spec->path_stride + 1) : 0;
   EvalCarve carve;
@@ -3653,7 +3733,10 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
                o_status = carve.add(rs ? (size_t)N * 4 : 0), o_entry = carve.add(rs ? (size_t)N * 4 : 0),
                o_team = carve.add(tio ? (size_t)N * 5 * 8 : 0), o_stepped = carve.add(tio ? (size_t)N * 4 : 0),
                o_rel = carve.add(sio ? (size_t)N * K * 4 : 0), o_home = carve.add(sio ? (size_t)N * P * 4 : 0),
-               o_sched = carve.add(sio ? (size_t)N * 2 * 8 : 0);
+               o_sched = carve.add(sio ? (size_t)N * 2 * 8 : 0),
+               o_wbox = carve.add(wio ? std::max<size_t>((size_t)wio->wl->n_scenes * wio->wl->max_walls * 4, 1) * 4 : 0),
+               o_wcnt = carve.add(wio ? (size_t)wio->wl->n_scenes * 4 : 0), o_wscene = carve.add(wio ? (size_t)N * 4 : 0),
+               o_wout = carve.add(wio ? (size_t)N * 7 * 8 : 0);
   FrameHazardArgs<FollowArgs> hf{};    // the frames tasks' arguments hold the static tasks'
   FrameHazardArgs<ResumeArgs> hrf{};
   FrameHazardArgs<ScheduledArgs> hsf{};
@@ -3699,6 +3782,19 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     if (tio)
       tf = TeamFill{tio->tm->team_size, tio->tm->separation, tio->tm->cost, tio->tm->indicator != 0, eval_at<double>(e, o_team),
                     eval_at<int>(e, o_stepped)};
+    WallFill wf{};
+    if (wio) {
+      const mobrob_walls_t* wl = wio->wl;
+      const size_t nb = (size_t)wl->n_scenes * wl->max_walls * 4;
+      float* box_dev = eval_at<float>(e, o_wbox);
+      int* cnt_dev = eval_at<int>(e, o_wcnt);
+      int* scene_dev = wl->scene ? eval_at<int>(e, o_wscene) : nullptr;
+      wf = WallFill{box_dev, cnt_dev, scene_dev, wl->max_walls, wl->radius, wl->cost, wl->indicator != 0, eval_at<double>(e, o_wout)};
+      if (nb) HIPC(hipMemcpyAsync(box_dev, wl->boxes, nb * 4, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(cnt_dev, wall_counts.data(), (size_t)wl->n_scenes * 4, hipMemcpyHostToDevice, e->stream));
+      if (wl->scene) HIPC(hipMemcpyAsync(scene_dev, wl->scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(wf.out, wio->wall_out, (size_t)N * 7 * 8, hipMemcpyHostToDevice, e->stream));
+    }
     if (sio) {
       ScheduledArgs& sa = hsf.h.b;
       int* rel_dev = eval_at<int>(e, o_rel);
@@ -3707,15 +3803,16 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
       HIPC(hipMemcpyAsync(rel_dev, sio->sc->release, (size_t)N * K * 4, hipMemcpyHostToDevice, e->stream));
       HIPC(hipMemcpyAsync(home_dev, sio->sc->home, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
       HIPC(hipMemcpyAsync(sa.sched_out, sio->sched_out, (size_t)N * 2 * 8, hipMemcpyHostToDevice, e->stream));
-      ran = resume_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, hsf, hazard_dev);
+      ran = resume_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, hsf, hazard_dev, wio, wf);
       if (ran >= 0) HIPC(hipMemcpyAsync(sio->sched_out, sa.sched_out, (size_t)N * 2 * 8, hipMemcpyDeviceToHost, e->stream));
     } else {
-      ran = resume_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, hrf, hazard_dev);
+      ran = resume_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, hrf, hazard_dev, wio, wf);
     }
     if (ran >= 0) {
       HIPC(hipMemcpyAsync(rs->state, r.state, (size_t)N * 6 * 4, hipMemcpyDeviceToHost, e->stream));
       HIPC(hipMemcpyAsync(rs->leg_used, r.leg_used, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
       HIPC(hipMemcpyAsync(rs->status, r.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+      if (wio) HIPC(hipMemcpyAsync(wio->wall_out, wf.out, (size_t)N * 7 * 8, hipMemcpyDeviceToHost, e->stream));
     }
   }
   if (ran < 0) return ran;
@@ -3791,6 +3888,27 @@ int mobrob_ppo_follow_waypoints_scheduled(mobrob_ppo_engine_t* e, const mobrob_g
   const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
   return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
                           (hz || hzf) ? &hio : nullptr, resume, teams ? &tio : nullptr, &sio);
+}
+
+int mobrob_ppo_follow_waypoints_walls(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                      const mobrob_hazards_t* hz, const mobrob_hazard_frames_t* hzf, const mobrob_follow_resume_t* resume,
+                                      const mobrob_teams_t* teams, const mobrob_follow_schedule_t* schedule, const mobrob_walls_t* walls,
+                                      const float* waypoints, const int32_t* n_waypoints, int32_t* arrival, double* robot_out,
+                                      double* hazard_out, double* team_out, double* sched_out, double* wall_out, float* path_out,
+                                      float* trace_out) {
+  if (!resume || !walls || !wall_out) return fail(MOBROB_ERR_INVALID, "follow: walls: null argument (a call with walls is a call of a run)");
+  if ((teams != nullptr) != (team_out != nullptr)) return fail(MOBROB_ERR_INVALID, "follow: walls: team_out is needed with teams, and only then");
+  if ((schedule != nullptr) != (sched_out != nullptr))
+    return fail(MOBROB_ERR_INVALID, "follow: walls: sched_out is needed with a schedule, and only then");
+  if (hz && hzf) return fail(MOBROB_ERR_INVALID, "follow: walls: static hazards or hazard frames, not both");
+  if ((hz || hzf) != (hazard_out != nullptr)) return fail(MOBROB_ERR_INVALID, "follow: walls: hazard_out is needed with hazards, and only then");
+  const TeamIO tio{teams, team_out};
+  const SchedIO sio{schedule, sched_out};
+  const WallIO wio{walls, wall_out};
+  mobrob_hazards_t view;
+  const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
+  return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
+                          (hz || hzf) ? &hio : nullptr, resume, teams ? &tio : nullptr, schedule ? &sio : nullptr, &wio);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -1,0 +1,221 @@
+// Walls (mobrob_ppo_follow_waypoints_walls): axis-aligned boxes in waypoint-following runs, checked for contact and for crossing.
+//
+// The rule, stated once in array form in mobrob_amd/envs/goal_rules.py (wall_check): a scene is up to 1024 walls (cx, cy, hx, hy)
+// with half extents hx, hy >= 0; after the step with global number g a robot that stepped has pre-step xy a and post-step xy p
+// (x and y only, as for hazards; runs have no resets, so a is where the previous step ended).  In float, every operation rounded
+// on its own, no fma:
+//   qx = |px - cx| - hx,  qy = |py - cy| - hy,  sdf = sqrt(max(qx, 0)^2 + max(qy, 0)^2) + min(max(qx, qy), 0)
+//   contact: sdf <= radius adds (radius - sdf) to the step's sum;  clear_w = sdf - radius
+//   mx = 0.5 (ax + px) - cx,  my likewise,  ex = 0.5 (px - ax),  ey = 0.5 (py - ay)
+//   hit_w = not(|mx| > hx + |ex|  or  |my| > hy + |ey|  or  |mx ey - my ex| > hx |ey| + hy |ex|)     (segment against closed box)
+// The sum runs over four partial sums (walls w = q, q + 4, ... for quarter q) combined as (p0 + p1) + (p2 + p3), the coefficient
+// applied once afterwards; the (clearance, wall) minimum over the same quarters and the same two exchanges (team_closer's rule);
+// the crossing flag is the OR over all walls.  Nothing the wrapped task computes changes.
+//
+// WallTask<Base> wraps a task of a RUN (ResumeFollowTask, ScheduledFollowTask, plain or under HazardTask<> / FrameHazardTask<>) and
+// offers what TeamTask expects of a base.  Its Robot adds the accumulators of wall_out [N][7] (float64 cost sum, contact steps,
+// first contact step (global, 1-based, -1: none), minimum clearance (NaN: no step run, +inf: no walls), the wall at that minimum
+// (first attainment, -1: none), crossing steps, first crossing step), read at entry and continued like hazard_out.
+#pragma once
+#include "kernels_team.h"
+
+namespace mobrob {
+
+constexpr int kWallMax = 1024;   // walls per scene at most (a shared scene: 16 KB of LDS)
+
+template <class BaseArgs>
+struct WallArgs {
+  BaseArgs b;              // the wrapped task's arguments
+  const float* boxes;      // [S][M][4] cx, cy, hx, hy
+  const int* nwall;        // [S] walls of each scene (<= M)
+  const int* scene;        // [N] scene of each robot, or null (S == 1)
+  int M;                   // row stride of boxes
+  float radius, coef;      // the robot's footprint, cost coefficient
+  int indicator;
+  int pre_off;             // k_goal64_tile: floats from the [16][2] post-step block to the pre-step block (the base's LDS floats)
+  double* wall_out;        // [N][7] in / out; per-step path: live state between the launches
+};
+
+struct WallAcc {
+  double cost_sum;
+  int contacts, first, wall, crossings, first_cross;
+  float min_clear;
+};
+
+// one quarter's partial (unscaled) cost, (clearance, wall) and crossing flag: walls q, q + 4, ... of the scene `w` (m of them) for
+// the step from (ax, ay) to (px, py).  Products that feed a sum are pinned (kernels_env.h: rounded), as in team_partial.
+__device__ __forceinline__ void wall_partial(const float* w, int m, int q, float ax, float ay, float px, float py, float radius,
+                                             float& cost, float& clear, int& wall, bool& hit) {
+  cost = 0.f;
+  clear = __builtin_inff();
+  wall = -1;
+  hit = false;
+  const float ex = rounded(__fmul_rn(0.5f, __fsub_rn(px, ax))), ey = rounded(__fmul_rn(0.5f, __fsub_rn(py, ay)));
+  const float sx = rounded(__fmul_rn(0.5f, __fadd_rn(ax, px))), sy = rounded(__fmul_rn(0.5f, __fadd_rn(ay, py)));
+  const float aex = fabsf(ex), aey = fabsf(ey);
+  for (int i = q; i < m; i += 4) {
+    const float cx = w[4 * i], cy = w[4 * i + 1], hx = w[4 * i + 2], hy = w[4 * i + 3];
+    const float qx = __fsub_rn(fabsf(__fsub_rn(px, cx)), hx), qy = __fsub_rn(fabsf(__fsub_rn(py, cy)), hy);
+    const float ox = fmaxf(qx, 0.f), oy = fmaxf(qy, 0.f);
+    const float out = sqrtf(__fadd_rn(rounded(__fmul_rn(ox, ox)), rounded(__fmul_rn(oy, oy))));   // sqrtf: correctly rounded
+    const float sdf = __fadd_rn(out, fminf(fmaxf(qx, qy), 0.f));
+    if (sdf <= radius) cost = __fadd_rn(cost, __fsub_rn(radius, sdf));
+    const float cl = __fsub_rn(sdf, radius);
+    if (cl < clear) { clear = cl; wall = i; }   // ascending i: equal clearances keep the lower index
+    // the segment against the closed box: three separating axes, no division
+    const float mx = __fsub_rn(sx, cx), my = __fsub_rn(sy, cy);
+    const float cross = fabsf(__fsub_rn(rounded(__fmul_rn(mx, ey)), rounded(__fmul_rn(my, ex))));
+    const float reach = __fadd_rn(rounded(__fmul_rn(hx, aey)), rounded(__fmul_rn(hy, aex)));
+    if (!(fabsf(mx) > __fadd_rn(hx, aex) || fabsf(my) > __fadd_rn(hy, aey) || cross > reach)) hit = true;
+  }
+}
+
+// the step's cost / clearance / wall / crossing -> the accumulators.  g1: the step's global 1-based number
+__device__ __forceinline__ void wall_account(WallAcc& W, float coef, int indicator, int g1, float sum, float clear, int wall, bool hit) {
+  const float s = __fmul_rn(coef, sum);
+  const float cost = indicator ? (s > 0.f ? 1.f : 0.f) : s;
+  W.cost_sum += (double)cost;
+  if (cost > 0.f) {
+    W.contacts += 1;
+    if (W.first < 0) W.first = g1;
+  }
+  if (clear < W.min_clear) { W.min_clear = clear; W.wall = wall; }   // strict: the first attainment is kept
+  if (hit) {
+    W.crossings += 1;
+    if (W.first_cross < 0) W.first_cross = g1;
+  }
+}
+
+// steps: the steps the robot has run in the RUN (0: nothing measured yet, clearance NaN <-> +inf)
+__device__ __forceinline__ WallAcc wall_load(const double* o, int steps) {
+  return WallAcc{o[0], (int)o[1], (int)o[2], (int)o[4], (int)o[5], (int)o[6], steps > 0 ? (float)o[3] : __builtin_inff()};
+}
+__device__ __forceinline__ void wall_store(double* o, const WallAcc& W, int steps) {
+  o[0] = W.cost_sum; o[1] = (double)W.contacts; o[2] = (double)W.first;
+  o[3] = steps > 0 ? (double)W.min_clear : __longlong_as_double(0x7FF8000000000000ll);   // NaN: no step run
+  o[4] = (double)W.wall; o[5] = (double)W.crossings; o[6] = (double)W.first_cross;
+}
+
+template <class Base>
+struct WallTask {
+  static_assert(Base::kResume, "walls are a property of a run: the wrapped task must be resumable");
+  using Args = WallArgs<typename Base::Args>;
+  struct Robot {
+    typename Base::Robot b;
+    WallAcc wall;
+  };
+  static constexpr bool kWide = true;
+  static constexpr bool kResume = true;
+  static constexpr bool kFrames = Base::kFrames;
+  static __device__ __forceinline__ int step0(const Args& a) { return Base::step0(a.b); }
+  static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& a) { return Base::eval(a.b); }
+  // floats of k_goal64_tile's LDS the base uses beyond LayEval64::END: its [16][2] post-step block and its shared scene (a base
+  // that is not wide has neither: the post-step block is added here).  The host fills Args::pre_off with it.
+  static size_t base_lds_floats(const typename Base::Args& b) {
+    if constexpr (Base::kWide) return Base::tile_lds_bytes(b) / sizeof(float);
+    else return 32;
+  }
+  // ... then the [16][2] pre-step block and a shared wall scene
+  static size_t tile_lds_bytes(const Args& a) { return ((size_t)a.pre_off + 32 + (a.scene ? 0 : 4 * (size_t)a.M)) * sizeof(float); }
+
+  static __device__ __forceinline__ const float* scene_of(const Args& a, int n, int& count) {
+    const int s = a.scene ? a.scene[n] : 0;
+    count = a.nwall[s];
+    return a.boxes + (size_t)s * a.M * 4;
+  }
+
+  static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& a, int n) {
+    Base::start(g, R.b, a.b, n);
+    R.wall = wall_load(a.wall_out + (size_t)n * 7, Base::steps(R.b));
+  }
+  static __device__ __forceinline__ bool active(const Args& a, const Robot& R) { return Base::active(a.b, R.b); }
+  static __device__ __forceinline__ int steps(const Robot& R) { return Base::steps(R.b); }   // for a wrapping task (kernels_team.h)
+
+  // the whole step in one thread (per-step path): the position before the base's step, the four quarters in turn afterwards, in
+  // the tile's order.  A run has no reset, so g.pos after the step is the post-step position the base's wide phase sees.
+  static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
+                                              const float* obs_row) {
+    const float ax = g.pos[0], ay = g.pos[1];
+    bool going;
+    if constexpr (Base::kWide) going = Base::step(g, R.b, a.b, n, t, act, obs_row);
+    else going = Base::template step<0>(g, R.b, a.b, n, t, act, obs_row);
+    int m;
+    const float* ws = scene_of(a, n, m);
+    float c[4], cl[4];
+    int wi[4];
+    bool hit[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) wall_partial(ws, m, q, ax, ay, g.pos[0], g.pos[1], a.radius, c[q], cl[q], wi[q], hit[q]);
+    team_closer(cl[0], wi[0], cl[1], wi[1]);
+    team_closer(cl[2], wi[2], cl[3], wi[3]);
+    team_closer(cl[0], wi[0], cl[2], wi[2]);
+    wall_account(R.wall, a.coef, a.indicator, Base::step0(a.b) + t + 1, __fadd_rn(__fadd_rn(c[0], c[1]), __fadd_rn(c[2], c[3])), cl[0],
+                 wi[0], hit[0] || hit[1] || hit[2] || hit[3]);
+    return going;
+  }
+
+  // ---- k_goal64_tile ----
+  // LDS beyond LayEval64::END: [16][2] post-step xy | the base's scene | [16][2] pre-step xy | a shared wall scene.  hz_lds is the
+  // base's scene (32 floats after the post-step block), xy the post-step block (step_lane: the robot's row of it).
+  static __device__ __forceinline__ int frame(const Args& a, int g) { return Base::frame(a.b, g); }   // kFrames only
+  static __device__ __forceinline__ void stage_frame(const Args& a, float* hz_lds, int lane, int f) { Base::stage_frame(a.b, hz_lds, lane, f); }
+  static __device__ __forceinline__ void stage(const Args& a, float* hz_lds, int lane) {
+    if constexpr (Base::kWide) Base::stage(a.b, hz_lds, lane);
+    if (!a.scene) {
+      float* wl = hz_lds + a.pre_off;   // = post-step block + pre_off + 32
+      for (int i = lane; i < 4 * a.nwall[0]; i += 64) wl[i] = a.boxes[i];
+    }
+  }
+  static __device__ __forceinline__ bool step_lane(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
+                                                   const float* obs_row, float* xy, int& e0) {
+    float* pre = xy + a.pre_off;   // the robot's row of the pre-step block
+    pre[0] = g.pos[0]; pre[1] = g.pos[1];
+    if constexpr (Base::kWide) return Base::step_lane(g, R.b, a.b, n, t, act, obs_row, xy, e0);
+    else return Base::template step<0>(g, R.b, a.b, n, t, act, obs_row, xy);
+  }
+  // every lane: the base's wide phase, then quarter q = lane >> 4 of robot r16 = lane & 15 against its scene.
+  // Barriers: none of its own.  The pre-step row is written where the post-step row is, on the robot's lane in the env phase, and
+  // read here: the kernel's barrier before after_step orders this step's writes of both blocks before these reads, its barrier
+  // after after_step orders these reads before the next step's writes.  The wall scene is written once, before the barrier that
+  // follows the start state, and only read afterwards; a restaged hazard frame touches the base's scene alone.
+  static __device__ __forceinline__ void after_step(const Args& a, Robot& R, int n, int t, int lane, bool stepped, int e0,
+                                                    const float* xy, const float* hz_lds) {
+    if constexpr (Base::kWide) Base::after_step(a.b, R.b, n, t, lane, stepped, e0, xy, hz_lds);
+    const int r16 = lane & 15, q = lane >> 4;
+    const float* pre = xy + a.pre_off;
+    float c = 0.f, cl = __builtin_inff();
+    int wi = -1;
+    bool hit = false;
+    if (stepped) {
+      int m;
+      const float* ws = scene_of(a, n, m);
+      wall_partial(a.scene ? ws : pre + 32, m, q, pre[2 * r16], pre[2 * r16 + 1], xy[2 * r16], xy[2 * r16 + 1], a.radius, c, cl, wi, hit);
+    }
+    // lanes r16, r16 + 16, r16 + 32, r16 + 48 hold quarters 0..3: (p0 + p1) + (p2 + p3), the same two exchanges for the minimum and the flag
+    const float c01 = __fadd_rn(c, __shfl_xor(c, 16, 64));
+    const float cs = __fadd_rn(c01, __shfl_xor(c01, 32, 64));
+    team_closer(cl, wi, __shfl_xor(cl, 16, 64), __shfl_xor(wi, 16, 64));
+    team_closer(cl, wi, __shfl_xor(cl, 32, 64), __shfl_xor(wi, 32, 64));
+    int h = hit ? 1 : 0;
+    h |= __shfl_xor(h, 16, 64);
+    h |= __shfl_xor(h, 32, 64);
+    if (lane < 16 && stepped) wall_account(R.wall, a.coef, a.indicator, Base::step0(a.b) + t + 1, cs, cl, wi, h != 0);
+  }
+
+  static __device__ __forceinline__ void finish(const Args& a, int n, const Robot& R, const GoalState& g) {
+    Base::finish(a.b, n, R.b, g);
+    wall_store(a.wall_out + (size_t)n * 7, R.wall, Base::steps(R.b));
+  }
+  static __device__ __forceinline__ Robot load(const Args& a, int n) {
+    Robot R;
+    R.b = Base::load(a.b, n);
+    R.wall = wall_load(a.wall_out + (size_t)n * 7, Base::steps(R.b));
+    return R;
+  }
+  static __device__ __forceinline__ void store(const Args& a, int n, const Robot& R) {
+    Base::store(a.b, n, R.b);
+    wall_store(a.wall_out + (size_t)n * 7, R.wall, Base::steps(R.b));
+  }
+};
+
+}  // namespace mobrob

@@ -393,7 +393,7 @@ class PPOEngine:
 
     def evaluate_goal_env(self, pos_dim, mix, time_limit=0, terminate_on_goal=True, dt=0.05, extent=3.0, reach_radius=0.3,
                           goal_bonus=5.0, extra_bonus=0.0, obs_noise=0.1, *, n_robots, max_steps=1000, episodes=0, quota=None,
-                          deterministic=True, seed=0, trace=None, hazards=None):
+                          deterministic=True, seed=0, trace=None, hazards=None, walls=None):
         """The current policy on `n_robots` fresh robots of the device goal environment (mobrob_ppo_evaluate_goal_env).
         time_limit 0: no limit (examples/control.py).  episodes > 0: SB3 evaluate_policy's quota of finished episodes, split
         (episodes + i) // n_robots unless `quota` ([n_robots] ints) is given.  trace = (robots, steps): teacher-forcing trace.
@@ -402,7 +402,11 @@ class PPOEngine:
         `persistent` (which kernel path ran).  hazards: a goal_rules.Hazards -> mobrob_ppo_evaluate_goal_env_hazards, adding
         cost_sum, violation_steps, first_violation, min_clearance ([n_robots]) and episode_cost ([n_robots][max quota], NaN
         past an unfinished quota); trace rows then end in the step's cost and clearance.  A goal_rules.MovingHazards ->
-        mobrob_ppo_evaluate_goal_env_hazard_frames: the same keys, the check after the call's step t on frame f(t)."""
+        mobrob_ppo_evaluate_goal_env_hazard_frames: the same keys, the check after the call's step t on frame f(t).
+        walls: refused (ValueError) -- an evaluation resets robots by teleporting them, and a swept segment across a reset has
+        no meaning; walls belong to waypoint-following runs (follow_waypoints(walls=))."""
+        if walls is not None:
+            raise ValueError("evaluate: walls: an evaluation takes no walls (resets teleport robots); use follow_waypoints(walls=)")
         n = int(n_robots)
         sp = EvalSpec()
         tr = self._eval_spec_common("evaluate_goal_env", sp, max_steps, deterministic, seed, trace, 0 if hazards is None else 2)
@@ -448,7 +452,8 @@ class PPOEngine:
 
     def follow_waypoints(self, pos_dim, mix, dt=0.05, extent=3.0, reach_radius=0.3, goal_bonus=5.0, extra_bonus=0.0,
                          obs_noise=0.1, *, start=None, waypoints=None, n_waypoints=None, max_steps=1000, deterministic=True, seed=0,
-                         path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0, teams=None, schedule=None):
+                         path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0, teams=None, schedule=None,
+                         walls=None):
         """The current policy as a tracker of given goal sequences (mobrob_ppo_follow_waypoints): robot i starts at rest on
         start[i] ([n][P]) and follows waypoints[i][:n_waypoints[i]] (waypoints [n][K][P], or [K][P] for all robots; n_waypoints
         None = K each), no time limit, no reset.  path_stride > 0 records positions; trace = (robots, steps): teacher-forcing
@@ -464,15 +469,20 @@ class PPOEngine:
         first), adding team_cost_sum, conflict_steps, first_conflict, min_team_clearance, closest_partner and `state.team`.
         schedule: a goal_rules.Schedule -> mobrob_ppo_follow_waypoints_scheduled (always a call of a run; without `resume` its
         first: the state then takes release and home from it; with `resume` the state's are in force), adding hold_steps,
-        hold_drift, lateness and `state.sched`; trace rows of hold steps carry the flags 0, 0."""
+        hold_drift, lateness and `state.sched`; trace rows of hold steps carry the flags 0, 0.
+        walls: a goal_rules.Walls -> mobrob_ppo_follow_waypoints_walls (always a call of a run; without `resume` its first),
+        adding the keys of waypoints.wall_result (wall_cost_sum, contact_steps, first_contact, min_wall_clearance, closest_wall,
+        crossing_steps, first_crossing) and `state.wall`; nothing else the call returns changes."""
         from .waypoints import FollowState, follow_inputs
-        if resume is not None or int(leg_steps) != 0 or teams is not None or schedule is not None:
+        if resume is not None or int(leg_steps) != 0 or teams is not None or schedule is not None or walls is not None:
             if resume is None:
-                resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule)
+                resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule,
+                                     walls is not None)
             elif not (start is None and waypoints is None and n_waypoints is None):
                 raise ValueError("follow_waypoints: a resumed call takes its robots and waypoints from `resume`")
             return self._follow_resume(pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, resume,
-                                       int(leg_steps), max_steps, deterministic, seed, path_stride, trace, hazards, teams, schedule)
+                                       int(leg_steps), max_steps, deterministic, seed, path_stride, trace, hazards, teams, schedule,
+                                       walls)
         if start is None or waypoints is None:
             raise ValueError("follow_waypoints: start and waypoints are needed unless `resume` continues a run")
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
@@ -507,12 +517,13 @@ class PPOEngine:
         return out
 
     def _follow_resume(self, pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, state, leg_steps,
-                       max_steps, deterministic, seed, path_stride, trace, hazards, teams=None, schedule=None):
+                       max_steps, deterministic, seed, path_stride, trace, hazards, teams=None, schedule=None, walls=None):
         """One call of a run (mobrob_ppo_follow_waypoints_resume; with a MovingHazards mobrob_ppo_follow_waypoints_hazard_frames;
-        with teams mobrob_ppo_follow_waypoints_teams; with a schedule mobrob_ppo_follow_waypoints_scheduled) on a copy of `state`."""
-        from ._lib import FollowResume, FollowScheduleC, TeamsC
-        from .envs.goal_rules import Schedule, Teams
-        from .waypoints import FollowState, schedule_result, team_result
+        with teams mobrob_ppo_follow_waypoints_teams; with a schedule mobrob_ppo_follow_waypoints_scheduled; with walls
+        mobrob_ppo_follow_waypoints_walls) on a copy of `state`."""
+        from ._lib import FollowResume, FollowScheduleC, TeamsC, WallsC
+        from .envs.goal_rules import Schedule, Teams, Walls
+        from .waypoints import FollowState, schedule_result, team_result, wall_result
         if not isinstance(state, FollowState):
             raise TypeError(f"follow_waypoints: resume must be a FollowState, not {type(state).__name__}")
         if (state.hazard is None) != (hazards is None):
@@ -527,6 +538,12 @@ class PPOEngine:
             raise ValueError("follow_waypoints: a run has a schedule in every call or in none (FollowState(..., schedule=Schedule))")
         if schedule is not None and not isinstance(schedule, Schedule):
             raise TypeError(f"schedule must be a mobrob_amd.envs.goal_rules.Schedule, not {type(schedule).__name__}")
+        if (getattr(state, "wall", None) is None) != (walls is None):
+            raise ValueError("follow_waypoints: a run has walls in every call or in none (FollowState(..., walls=True))")
+        if walls is not None:
+            if not isinstance(walls, Walls):
+                raise TypeError(f"walls must be a mobrob_amd.envs.goal_rules.Walls, not {type(walls).__name__}")
+            walls.check_robots(state.n_robots)
         st = state.copy()
         n, K, P = st.waypoints.shape
         if P != int(pos_dim):
@@ -545,6 +562,10 @@ class PPOEngine:
             st.release, st.home = np.ascontiguousarray(st.release, np.int32), np.ascontiguousarray(st.home, F32)
             st.sched = np.ascontiguousarray(st.sched, np.float64)
             if st.release.shape != (n, K) or st.home.shape != (n, P) or st.sched.shape != (n, 2):
+                raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
+        if walls is not None:
+            st.wall = np.ascontiguousarray(st.wall, np.float64)
+            if st.wall.shape != (n, 7):
                 raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
         if st.state.shape != (n, 6) or st.robot.shape != (n, 4) or st.arrival.shape != (n, K) or st.leg_used.shape != (n,):
             raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
@@ -567,9 +588,22 @@ class PPOEngine:
             tm = TeamsC()
             tm.team_size, tm.separation, tm.cost, tm.indicator = teams.size, teams.separation, teams.cost, int(teams.indicator)
         frames = isinstance(h, HazardFramesC)
+        sc = None
         if schedule is not None:
             sc = FollowScheduleC()
             sc.release, sc.home = st.release.ctypes.data_as(i32), _fp(st.home)
+        if walls is not None:
+            wl = WallsC()
+            wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+            wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
+            wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
+            wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
+            r = check(self.lib.mobrob_ppo_follow_waypoints_walls(
+                self._h, C.byref(g), C.byref(sp), None if h is None or frames else C.byref(h), C.byref(h) if frames else None,
+                C.byref(rs), None if tm is None else C.byref(tm), None if sc is None else C.byref(sc), C.byref(wl), *tail[:5],
+                None if tm is None else st.team.ctypes.data_as(dp), None if sc is None else st.sched.ctypes.data_as(dp),
+                st.wall.ctypes.data_as(dp), *tail[5:]))
+        elif schedule is not None:
             r = check(self.lib.mobrob_ppo_follow_waypoints_scheduled(
                 self._h, C.byref(g), C.byref(sp), None if h is None or frames else C.byref(h), C.byref(h) if frames else None,
                 C.byref(rs), None if tm is None else C.byref(tm), C.byref(sc), *tail[:5],
@@ -594,6 +628,8 @@ class PPOEngine:
             out.update(team_result(st.team))
         if schedule is not None:
             out.update(schedule_result(st))
+        if walls is not None:
+            out.update(wall_result(st))
         if path is not None:
             out["path"] = path
         return out

@@ -459,3 +459,177 @@ def schedule_fold(record, anchor, pos, held):
         rec[:, 0] += h
         rec[:, 1] = np.where(h, np.maximum(best, d), rec[:, 1])
     return rec
+
+
+# ---- walls: axis-aligned boxes in a waypoint-following run, checked for contact and for crossing.  The boxes are the reference's
+# (its turtlebot3 arena is four of them, its Engine takes walls_locations / walls_size with rot 0); the checks are this project's
+# own rule, stated here once, and the device (csrc/kernels_wall.h) and the host loop are held to it.
+WALLS_MAX = 1024         # walls per scene the device path takes
+WALL_START = (0.0, 0.0, -1.0, np.nan, -1.0, 0.0, -1.0)   # a robot's wall record before its first step
+ARENA_LENGTH, ARENA_THICK = 2.42 + 0.28 * 2, 0.265       # the reference's turtlebot3 enclosure
+
+
+class Walls:
+    """A wall layout: `boxes` [M, 4] (one scene) or [S, M, 4] (scenes) rows (cx, cy, hx, hy) -- centre and half extents, hx, hy
+    >= 0 --, `counts` [S] walls in use per scene (None: all M), `scene` [n] scene of each robot (None: S must be 1), `radius` the
+    robot's footprint, `cost` per unit of intrusion and `indicator` (a step's cost is 1 if there is any).  Only x and y count,
+    for every robot.  Checked on construction (ValueError)."""
+
+    def __init__(self, boxes, counts=None, scene=None, radius=0.0, cost=1.0, indicator=True):
+        bx = np.asarray(boxes, np.float64)
+        if bx.size == 0 and bx.ndim < 2:
+            bx = bx.reshape(0, 4)
+        if bx.ndim == 2:
+            bx = bx[None]
+        if bx.ndim != 3 or bx.shape[2] != 4:
+            raise ValueError(f"wall boxes must be [M, 4] or [S, M, 4], got shape {np.shape(boxes)}")
+        S, M = bx.shape[:2]
+        if S < 1:
+            raise ValueError("walls need at least one scene")
+        if M > WALLS_MAX:
+            raise ValueError(f"at most {WALLS_MAX} walls per scene, got {M}")
+        if not np.all(np.isfinite(bx)):
+            raise ValueError("wall boxes must be finite")
+        if np.any(bx[..., 2:] < 0):
+            raise ValueError("wall half extents must be >= 0")
+        radius, cost = float(radius), float(cost)
+        if not np.isfinite(radius) or radius < 0:
+            raise ValueError(f"robot radius must be finite and >= 0, got {radius}")
+        if not np.isfinite(cost) or cost < 0:
+            raise ValueError(f"wall cost must be finite and >= 0, got {cost}")
+        if counts is None:
+            cnt = np.full(S, M, np.int32)
+        else:
+            cnt = np.asarray(counts)
+            if cnt.shape != (S,) or not np.issubdtype(cnt.dtype, np.integer) or np.any(cnt < 0) or np.any(cnt > M):
+                raise ValueError(f"wall counts must be {S} integers in 0 .. {M}")
+            cnt = cnt.astype(np.int32)
+        if scene is None:
+            if S != 1:
+                raise ValueError(f"{S} wall scenes need a scene index per robot")
+            sc = None
+        else:
+            sc = np.asarray(scene)
+            if sc.ndim != 1 or not np.issubdtype(sc.dtype, np.integer) or np.any(sc < 0) or np.any(sc >= S):
+                raise ValueError(f"wall scene indices must be integers in 0 .. {S - 1}")
+            sc = sc.astype(np.int32)
+        self.table = np.ascontiguousarray(bx, np.float32)   # [S, M, 4]
+        self.counts, self.scene, self.indicator = cnt, sc, bool(indicator)
+        self.radius, self.cost = float(np.float32(radius)), float(np.float32(cost))   # the float32 values every path uses
+
+    @property
+    def n_scenes(self):
+        return self.table.shape[0]
+
+    @property
+    def max_walls(self):
+        return self.table.shape[1]
+
+    def rows(self, robot=0):
+        """[m, 4] float32 (cx, cy, hx, hy) of the walls robot `robot` sees"""
+        s = 0 if self.scene is None else int(self.scene[robot])
+        return self.table[s, : self.counts[s]]
+
+    def check_robots(self, n):
+        if self.scene is not None and self.scene.shape != (n,):
+            raise ValueError(f"wall scene must have {n} entries, one per robot, got {self.scene.shape[0]}")
+
+    @staticmethod
+    def enclosure(length=ARENA_LENGTH, thick=ARENA_THICK, centre=(0.0, 0.0)):
+        """[4, 4] float64 boxes of a square enclosure of outer side `length` and wall thickness `thick` around `centre`, laid out
+        as the reference's arena is (pinned by tests/golden/wall_cases.npz): four equal bars in a pinwheel, each reaching from one
+        outer corner to the inner face of the next bar.  With r = (length - thick) / 2 and h = thick / 2 the bars sit at (-h, r),
+        (r, h), (h, -r), (-r, -h) with half extents (r, h), (h, r), (r, h), (h, r)."""
+        length, thick = float(length), float(thick)
+        if not (np.isfinite(length) and np.isfinite(thick) and 0 <= thick <= length):
+            raise ValueError(f"an enclosure needs 0 <= thick <= length, got length {length}, thick {thick}")
+        cx, cy = (float(c) for c in centre)
+        r, h = (length - thick) / 2, thick / 2
+        return np.array([[cx - h, cy + r, r, h], [cx + r, cy + h, h, r], [cx + h, cy - r, r, h], [cx - r, cy - h, h, r]], np.float64)
+
+
+def wall_check(pre_xy, post_xy, boxes, radius=0.0, coef=1.0, indicator=True, counts=None):
+    """The wall check of ONE step: pre_xy, post_xy [..., 2] the x, y before and after the step, boxes [M, 4] rows (cx, cy, hx, hy)
+    or [..., M, 4] per position, counts [...] walls in use (None: all M) -> (cost [...] float32, clear [...] float32, wall [...]
+    int64, hit [...] bool).  With a the pre-step and p the post-step position, per wall w:
+        qx = |px - cx| - hx     qy = |py - cy| - hy     sdf = sqrt(max(qx, 0)^2 + max(qy, 0)^2) + min(max(qx, qy), 0)
+        contact: sdf <= radius adds (radius - sdf) to the step's sum;  clear_w = sdf - radius
+        mx = 0.5 (ax + px) - cx,  my likewise;  ex = 0.5 (px - ax),  ey = 0.5 (py - ay)
+        hit_w = not(|mx| > hx + |ex|  or  |my| > hy + |ey|  or  |mx ey - my ex| > hx |ey| + hy |ex|)
+    -- the separating-axis test of the segment a p against the closed box, without a division; with a == p it is "p in the closed
+    box".  Everything is float32, every operation rounded on its own, in the device's order: four partial sums, quarter q over
+    the walls q, q + 4, ..., combined as (p0 + p1) + (p2 + p3), coef applied once afterwards (indicator: cost > 0); the
+    (clearance, wall) minimum over the same quarters and exchanges, the smaller clearance winning and equal clearances going to
+    the smaller index (+inf and -1 without walls); hit is the OR over all walls.  sdf == radius contributes exactly 0."""
+    f32 = np.float32
+    a, p = np.asarray(pre_xy, f32), np.asarray(post_xy, f32)
+    if a.shape != p.shape or p.shape[-1:] != (2,):
+        raise ValueError(f"pre_xy and post_xy must both be [..., 2], got {a.shape} and {p.shape}")
+    bx = np.asarray(boxes, f32)
+    bx = bx.reshape(bx.shape[:-1] + (4,)) if bx.size else np.zeros((0, 4), f32)
+    lead, M = p.shape[:-1], bx.shape[-2]
+    used = np.full(lead, M) if counts is None else np.broadcast_to(np.asarray(counts), lead)
+    rad, half, zero = f32(radius), f32(0.5), f32(0)
+    ax, ay, px, py = a[..., 0], a[..., 1], p[..., 0], p[..., 1]
+    ex, ey = half * (px - ax), half * (py - ay)
+    sx, sy = half * (ax + px), half * (ay + py)
+    aex, aey = np.abs(ex), np.abs(ey)
+    part, clear = np.zeros((4,) + lead, f32), np.full((4,) + lead, np.inf, f32)
+    wall, hit = np.full((4,) + lead, -1), np.zeros(lead, bool)
+    for w in range(M):
+        q = w % 4
+        on = w < used
+        cx, cy, hx, hy = (bx[..., w, j] for j in range(4))
+        qx, qy = np.abs(px - cx) - hx, np.abs(py - cy) - hy
+        ox, oy = np.maximum(qx, zero), np.maximum(qy, zero)
+        sdf = np.sqrt(ox * ox + oy * oy) + np.minimum(np.maximum(qx, qy), zero)   # float32 throughout: each operation correctly rounded
+        part[q] = np.where(on & (sdf <= rad), part[q] + (rad - sdf), part[q])
+        cl = sdf - rad
+        closer = on & (cl < clear[q])                                             # ascending w: equal clearances keep the lower index
+        clear[q], wall[q] = np.where(closer, cl, clear[q]), np.where(closer, w, wall[q])
+        mx, my = sx - cx, sy - cy
+        apart = (np.abs(mx) > hx + aex) | (np.abs(my) > hy + aey) | (np.abs(mx * ey - my * ex) > hx * aey + hy * aex)
+        hit = hit | (on & ~apart)
+
+    def closer_of(u, v):
+        (cu, wu), (cv, wv) = u, v
+        take = (cv < cu) | ((cv == cu) & (wv < wu))
+        return np.where(take, cv, cu), np.where(take, wv, wu)
+    total = f32(coef) * ((part[0] + part[1]) + (part[2] + part[3]))
+    cl, wi = closer_of(closer_of((clear[0], wall[0]), (clear[1], wall[1])), closer_of((clear[2], wall[2]), (clear[3], wall[3])))
+    if indicator:
+        total = (total > 0).astype(f32)
+    return np.asarray(total, f32), np.asarray(cl, f32), np.asarray(wi, np.int64), np.asarray(hit, bool)
+
+
+def wall_fold(record, pre_xy, post_xy, stepped, walls, step0=0):
+    """The carried wall record after the steps step0 .. step0 + T - 1: record [n][7] float64 (sum of step costs, contact steps
+    (cost > 0), the first such step as a global 1-based number or -1, the minimum clearance over the run -- NaN before the
+    robot's first step, +inf without walls --, the wall's index at that minimum, first attainment kept, or -1, crossing steps,
+    the first crossing step or -1), pre_xy / post_xy [T][n][2] the positions before and after each step, stepped [T][n], walls
+    a Walls.  Returns a new [n][7]; a robot accounts only for the steps in which it stepped."""
+    rec = np.array(record, np.float64)
+    pre, post = np.asarray(pre_xy, np.float32), np.asarray(post_xy, np.float32)
+    stepped = np.asarray(stepped, bool)
+    T, n = stepped.shape
+    walls.check_robots(n)
+    if rec.shape != (n, 7) or pre.shape != (T, n, 2) or post.shape != (T, n, 2):
+        raise ValueError(f"record must be [{n}][7] and pre_xy, post_xy [{T}][{n}][2], got {rec.shape}, {pre.shape} and {post.shape}")
+    sc = np.zeros(n, np.int64) if walls.scene is None else walls.scene.astype(np.int64)
+    boxes, counts = walls.table[sc], walls.counts[sc]                             # [n, M, 4], [n]
+    for t in range(T):
+        s = stepped[t]
+        cost, clear, wall, hit = wall_check(pre[t], post[t], boxes, walls.radius, walls.cost, walls.indicator, counts)
+        cost, clear = cost.astype(np.float64), clear.astype(np.float64)
+        rec[:, 0] += np.where(s, cost, 0.0)                                       # float64, one step after the other
+        touch = s & (cost > 0)
+        rec[:, 1] += touch
+        rec[:, 2] = np.where(touch & (rec[:, 2] < 0), step0 + t + 1, rec[:, 2])
+        best = np.where(np.isnan(rec[:, 3]), np.inf, rec[:, 3])
+        closer = s & (clear < best)
+        rec[:, 3] = np.where(s, np.where(closer, clear, best), rec[:, 3])
+        rec[:, 4] = np.where(closer, wall, rec[:, 4])
+        cross = s & hit
+        rec[:, 5] += cross
+        rec[:, 6] = np.where(cross & (rec[:, 6] < 0), step0 + t + 1, rec[:, 6])
+    return rec

@@ -219,18 +219,19 @@ class DeviceGoalVecEnv(VecEnvBase):
                                         seed=(self._seed or 0) if seed is None else seed, trace=trace, hazards=hazards)
 
     def follow(self, engine, start=None, waypoints=None, n_waypoints=None, max_steps=1000, deterministic=True, seed=None,
-               path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0, teams=None, schedule=None):
+               path_stride=0, trace=None, hazards=None, resume=None, leg_steps=0, teams=None, schedule=None, walls=None):
         """The engine's current policy following given waypoints on this task (PPOEngine.follow_waypoints with this env's mix,
         dt, extent and extra_bonus; no time limit, no reset).  seed defaults to the env's seed.  hazards: a goal_rules.Hazards or
         MovingHazards (frames indexed by the run's global step).
         resume: a waypoints.FollowState (this call continues that run; no start / waypoints then); leg_steps: step budget per
         waypoint.  teams: a goal_rules.Teams (separation costs between team-mates).  schedule: a goal_rules.Schedule (release
-        steps and holds).  Any of the four makes the call a call of a run: it returns `state` and `status` as well."""
+        steps and holds).  walls: a goal_rules.Walls (box contact and crossing checks).  Any of the five makes the call a call of a
+        run: it returns `state` and `status` as well."""
         return engine.follow_waypoints(self.pos_dim, self.mix, dt=self.dt, extent=self.extent, extra_bonus=self.extra_bonus,
                                        start=start, waypoints=waypoints, n_waypoints=n_waypoints, max_steps=int(max_steps),
                                        deterministic=deterministic, seed=(self._seed or 0) if seed is None else seed,
                                        path_stride=path_stride, trace=trace, hazards=hazards, resume=resume, leg_steps=leg_steps,
-                                       teams=teams, schedule=schedule)
+                                       teams=teams, schedule=schedule, walls=walls)
 
     def seed(self, seed=None):
         self._seed = seed

@@ -49,6 +49,16 @@ and `state.sched` carries the first two.  final_distance is then the distance to
 A call with a schedule is always a call of a run; the state holds `release` and `home` (changed by `replan` only), so on a
 continued call `schedule=` only says that the run is scheduled.  With every release 0 nothing differs from the run without.
 
+With `walls` (a goal_rules.Walls) every robot that stepped is checked against the axis-aligned boxes of its scene after the step
+(goal_rules.wall_check states the rule; x and y only): CONTACT -- the signed distance of the post-step position to each box against
+the robot radius -- and CROSSING -- the segment from the pre-step to the post-step position against each closed box, which catches
+a step that jumps a thin wall or clips a corner.  Walls are observational: nothing is blocked or deflected.  The dict gains
+  wall_cost_sum [n] float64 sum of the step costs;  contact_steps [n] steps with cost > 0;  first_contact [n] the first such step
+  (global, 1-based), -1 = none;  min_wall_clearance [n] smallest (signed distance - radius) after a step (+inf without walls, NaN
+  without steps);  closest_wall [n] the wall's index at that minimum (-1 = none);  crossing_steps [n] steps whose segment met a
+  box;  first_crossing [n] the first such step, -1 = none
+and `state.wall` carries the seven.  A call with walls is always a call of a run; `replan` leaves the wall record alone.
+
 Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
 sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
 into the next call) and `status`, and takes the previous call's `state=`.  Call c covers the global steps step0 .. step0 +
@@ -118,9 +128,11 @@ class FollowState:
       hazard [n][4]     float64 cost sum, violation steps, first violation, min clearance -- or None without hazards
       team [n][5]       float64 team cost sum, conflict steps, first conflict, min clearance to a mate, that mate -- or None
       release [n][K] int32, home [n][P] float32, sched [n][2] float64 hold steps, hold drift -- or None without a schedule
+      wall [n][7]       float64 wall cost sum, contact steps, first contact, min clearance, that wall, crossing steps, first
+                        crossing -- or None without walls
       waypoints [n][K][P] float32, n_waypoints [n] int32: the rows in force (changed by `replan` only)"""
 
-    def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False, schedule=None):
+    def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False, schedule=None, walls=False):
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
         n, K, P = wp.shape
         self.waypoints, self.n_waypoints, self.step0 = wp, nw, 0
@@ -131,6 +143,10 @@ class FollowState:
         self.leg_used, self.status = np.zeros(n, np.int32), np.zeros(n, np.int32)
         self.hazard = np.tile(np.array([0.0, 0.0, -1.0, np.nan]), (n, 1)) if hazards else None
         self.team = np.tile(np.array([0.0, 0.0, -1.0, np.nan, -1.0]), (n, 1)) if teams else None
+        self.wall = None
+        if walls:
+            from .envs.goal_rules import WALL_START
+            self.wall = np.tile(np.array(WALL_START), (n, 1))
         self.release = self.home = self.sched = None
         if schedule is not None:
             from .envs.goal_rules import SCHED_START, Schedule
@@ -163,7 +179,7 @@ class FollowState:
     def replan(self, rows, waypoints, n_waypoints=None, release=None):
         """New waypoints for the robots `rows` ([m] indices): waypoints [m][K'][P] or [K'][P] (the same for each), counts
         n_waypoints [m] (None: K' each).  Those robots start over on their new rows -- reached = 0, arrival = -1, leg_used = 0 --
-        and keep position, velocity, reward sum, steps run, hazard sums and team sums.  K grows when K' is larger.
+        and keep position, velocity, reward sum, steps run, hazard sums, team sums and the wall record.  K grows when K' is larger.
         In a scheduled run the replanned rows get `release` ([m][K'] or [K'] global steps; None: 0, released at once), their
         `home` becomes where they are, and the hold record is carried.  `release` on a run without a schedule is refused."""
         rows = np.atleast_1d(np.asarray(rows))
@@ -201,7 +217,7 @@ class FollowState:
         return self
 
 
-def _check_run(state, leg_steps, max_steps, hazards, teams=None, schedule=None):
+def _check_run(state, leg_steps, max_steps, hazards, teams=None, schedule=None, walls=None):
     """The run's values a call is given, checked as the engine checks them (ValueError)."""
     leg_steps = int(leg_steps)
     if leg_steps < 0:
@@ -219,6 +235,15 @@ def _check_run(state, leg_steps, max_steps, hazards, teams=None, schedule=None):
         if not isinstance(teams, Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
         teams.check_robots(state.n_robots)
+    if (getattr(state, "wall", None) is None) != (walls is None):
+        raise ValueError("a run has walls in every call or in none (FollowState(..., walls=True))")
+    if walls is not None:
+        from .envs.goal_rules import Walls
+        if not isinstance(walls, Walls):
+            raise TypeError(f"walls must be a mobrob_amd.envs.goal_rules.Walls, not {type(walls).__name__}")
+        walls.check_robots(state.n_robots)
+        if np.shape(state.wall) != (state.n_robots, 7):
+            raise ValueError("state.wall must be [n_robots][7]")
     if (getattr(state, "release", None) is None) != (schedule is None):
         raise ValueError("a run has a schedule in every call or in none (FollowState(..., schedule=Schedule))")
     if schedule is not None:
@@ -245,7 +270,7 @@ def _status(k, nw, leg_used, leg_steps):
 
 
 def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards=None, leg_steps=0, teams=None,
-                 schedule=None):
+                 schedule=None, walls=None):
     """The semantics, one robot after another on EnvWrapper's public API (make_env(i) -> the robot's env): one call of the run
     `state` is in (a fresh FollowState: the robots at rest on their starts).  Returns the dict and the state after the call.
     The simulator's noise is seeded per (robot, global step), so a run split into calls draws what one long call draws.
@@ -254,8 +279,10 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
     back into a robot's motion, so this equals stepping the robots in lockstep exactly.
     With `schedule` (the state holds release and home) the goal of every step is set per the rule before the step's observation
     is taken, a hold step skips the reward sum, the arrival and the leg count, and goal_rules.schedule_fold folds the hold
-    record from the anchors and the float32 positions after the hold steps."""
-    from .envs.goal_rules import MovingHazards, hazard_cost, schedule_fold, team_fold
+    record from the anchors and the float32 positions after the hold steps.
+    With `walls` every step's float32 x, y before and after it are kept and goal_rules.wall_fold applies wall_check per step after
+    the last robot."""
+    from .envs.goal_rules import MovingHazards, hazard_cost, schedule_fold, team_fold, wall_fold
     st = state.copy()
     st.state = st.state.astype(np.float64)              # the host simulator's own precision, carried exactly
     wp, nw, step0 = st.waypoints, st.n_waypoints, st.step0
@@ -269,6 +296,9 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
     if teams is not None:
         team_xy, team_stepped = np.zeros((max_steps, n, 2)), np.zeros((max_steps, n), bool)
         team_xy[:, :, :min(P, 2)] = st.state[None, :, :min(P, 2)]
+    if walls is not None:
+        wall_pre, wall_post = np.zeros((max_steps, n, 2), np.float32), np.zeros((max_steps, n, 2), np.float32)
+        wall_stepped = np.zeros((max_steps, n), bool)
     if schedule is not None:
         rel, home = st.release, st.home
         held, held_anchor, held_pos = np.zeros((max_steps, n), bool), np.zeros((max_steps, n, P), np.float32), np.zeros((max_steps, n, P), np.float32)
@@ -306,6 +336,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
                     env.env.seed([key, i, g])
                 obs = env.get_obs()
                 a, _ = model.predict(obs, deterministic=deterministic)
+                if walls is not None:
+                    wall_pre[t, i, :min(P, 2)] = pos[:2]
                 _, r, _, _, info = env.step(a)
                 if not hold:                           # a hold step's reward is progress towards a place the robot waits at
                     st.robot[i, 0] += float(r)
@@ -314,6 +346,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
                 pos = np.asarray(env.get_pos(), np.float64)[:P]
                 if teams is not None:
                     team_xy[t:, i, :min(P, 2)], team_stepped[t, i] = pos[:2], True
+                if walls is not None:
+                    wall_post[t, i, :min(P, 2)], wall_stepped[t, i] = pos[:2], True
                 if hazards is not None:
                     h = st.hazard[i]
                     h[0] += info["cost"]
@@ -352,6 +386,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
         st.team = team_fold(st.team, team_xy, team_stepped, teams, step0)
     if schedule is not None:
         st.sched = schedule_fold(st.sched, held_anchor, held_pos, held)
+    if walls is not None:
+        st.wall = wall_fold(st.wall, wall_pre, wall_post, wall_stepped, walls, step0)
     st.step0 = step0 + max_steps
     out = {"arrival": st.arrival.astype(np.int64), "reached": st.reached, "steps": st.robot[:, 1].astype(np.int64),
            "reward_sum": st.robot[:, 0].copy(), "final_distance": final_distance, "trace": None, "persistent": None,
@@ -363,9 +399,19 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
         out.update(team_result(st.team))
     if schedule is not None:
         out.update(schedule_result(st))
+    if walls is not None:
+        out.update(wall_result(st))
     if path is not None:
         out["path"] = path
     return out
+
+
+def wall_result(state):
+    """The keys a run with walls adds to a call's dict, from the state after the call (state.wall [n][7])."""
+    w = state.wall
+    return {"wall_cost_sum": w[:, 0].copy(), "contact_steps": w[:, 1].astype(np.int64), "first_contact": w[:, 2].astype(np.int64),
+            "min_wall_clearance": w[:, 3].copy(), "closest_wall": w[:, 4].astype(np.int64), "crossing_steps": w[:, 5].astype(np.int64),
+            "first_crossing": w[:, 6].astype(np.int64)}
 
 
 def schedule_result(state):
@@ -382,7 +428,7 @@ def team_result(team):
 
 
 def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *, max_steps=1000, deterministic=True, seed=0,
-                     path_stride=0, hazards=None, state=None, leg_steps=0, teams=None, schedule=None):
+                     path_stride=0, hazards=None, state=None, leg_steps=0, teams=None, schedule=None, walls=None):
     """Every robot i follows waypoints[i][:n_waypoints[i]] from start[i] under `model` (a PPO, or for the host path anything
     with `.predict`).  `env`: a DeviceGoalVecEnv (device path), an EnvWrapper, or an env name for `get_env` (host path; a
     fresh environment per robot for a name, the given one reused robot after robot otherwise).  Returns the dict described in
@@ -391,7 +437,8 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
     None: the robots are where they were, on the waypoints the state holds).  leg_steps: step budget per waypoint (0: none).
     teams: a goal_rules.Teams (separation costs between team-mates, see the module docstring).
     schedule: a goal_rules.Schedule (release steps and holds, see the module docstring); with `state`, which holds the release
-    steps in force, it only says that the run is scheduled."""
+    steps in force, it only says that the run is scheduled.
+    walls: a goal_rules.Walls (box contact and crossing checks, see the module docstring)."""
     from .envs.vec_env import DeviceGoalVecEnv
     from .envs.wrapper import EnvWrapper, TimeLimit, get_env
     max_steps, path_stride = int(max_steps), int(path_stride)
@@ -403,11 +450,12 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         raise ValueError("start and waypoints are needed unless `state` continues a run")
     if isinstance(env, DeviceGoalVecEnv):
         if state is None:
-            state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams is not None, schedule)
-        _check_run(state, leg_steps, max_steps, hazards, teams, schedule)
+            state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams is not None, schedule,
+                                walls is not None)
+        _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
         return env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
                           path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps, teams=teams,
-                          schedule=schedule)
+                          schedule=schedule, walls=walls)
     if isinstance(env, str):
         name = env
 
@@ -424,21 +472,23 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         def make_env(i):
             return env
     if state is None:
-        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule)
+        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule, walls is not None)
     elif isinstance(state, FollowState) and state.waypoints.shape[2] != pos_dim:
         raise ValueError(f"state has {state.waypoints.shape[2]} position dimensions, the environment {pos_dim}")
-    leg_steps = _check_run(state, leg_steps, max_steps, hazards, teams, schedule)
-    return _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps, teams, schedule)
+    leg_steps = _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
+    return _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps, teams, schedule,
+                        walls)
 
 
 def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, rounds, leg_steps=0, n_waypoints=None,
-                           deterministic=True, seed=0, hazards=None, teams=None, schedule=None):
+                           deterministic=True, seed=0, hazards=None, teams=None, schedule=None, walls=None):
     """A planner's loop around the tracker: `rounds` calls of `horizon` steps each, one run (see the module docstring).  After
     every round but the last, `planner(positions [n][P], status [n], reached [n])` returns {robot index: new waypoints [k][P]}
     (or None / {} for no change), applied through FollowState.replan.  The loop ends early once no robot is going or stalled
     and the planner changes nothing.  Returns the last call's dict plus `round_status` [rounds run][n].  teams: a
     goal_rules.Teams; the planner callback is unchanged (the team sums are in the returned dict and in its `state`).  schedule: a
-    goal_rules.Schedule; a planner that returns {robot: (waypoints, release)} gives the new waypoints release steps (global)."""
+    goal_rules.Schedule; a planner that returns {robot: (waypoints, release)} gives the new waypoints release steps (global).
+    walls: a goal_rules.Walls; replanning leaves the wall record alone."""
     horizon, rounds = int(horizon), int(rounds)
     if horizon < 1 or rounds < 1:
         raise ValueError("horizon and rounds must be >= 1")
@@ -447,7 +497,7 @@ def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, ro
         first = state is None
         out = follow_waypoints(model, env, start if first else None, waypoints if first else None, n_waypoints if first else None,
                                max_steps=horizon, deterministic=deterministic, seed=seed, hazards=hazards, state=state,
-                               leg_steps=leg_steps, teams=teams, schedule=schedule)
+                               leg_steps=leg_steps, teams=teams, schedule=schedule, walls=walls)
         state = out["state"]
         statuses.append(out["status"].copy())
         if r + 1 == rounds:
