@@ -36,6 +36,12 @@ time a robot needs to clear a crossing is the one-line demonstration that delays
 contact of the robot's footprint (`--robot-radius R`, default 0.1) and crossing of the step's segment, which also sees a step that
 jumps a thin wall.  `--arena` adds the reference's turtlebot3 enclosure (four boxes, 2.98 m outside, 0.265 m thick).  Three lines
 report the contact rate, the crossing rate (robots with such a step) and the minimum clearance to a wall.  Walls block nothing.
+
+`--goal X,Y` (X,Y,Z for a drone) PLANS the waypoints instead of reading them: a grid of `--plan-cells` (32, 64, 128; default 64)
+cells a side over the arena, blocked where --walls / --arena / --hazards are (mobrob_amd.planning.GridPlanner), one path per robot
+from its start to the goal.  It excludes --waypoints.  A first line reports the rate of robots with a plan; the others count a
+robot without one as not successful.  With --horizon and --leg-steps a stalled robot is planned again from where it stands between
+the calls (the planner's callback).  Moving hazards are reported, not planned around.
 """
 import argparse
 import os
@@ -63,8 +69,10 @@ def check_chain(max_steps, horizon, leg_steps):
 
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
-           release=None, stagger=0, walls=None, arena=False, robot_radius=0.1):
+           release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64):
     calls = check_chain(max_steps, horizon, leg_steps)
+    if (goal is None) == (waypoints is None):
+        raise ValueError("give --waypoints or --goal, not both")
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
     from mobrob_amd.envs.goal_rules import Hazards, MovingHazards, Schedule, Teams, Walls
@@ -84,21 +92,36 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             raise ValueError(f"--hazard-frames must hold [F][M][3] (x, y, radius), got shape {fr.shape}")
         hz = MovingHazards(fr[:, :, :2], fr[None, :, :, 2], frame_steps=int(frame_steps), loop=bool(hazard_loop), indicator=False)
     teams = None if team_size is None else Teams(int(team_size), float(separation))   # (a ValueError names what is wrong)
-    schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
     wl = None
     if walls is not None or arena:
         boxes = np.zeros((0, 4)) if walls is None else np.asarray(walls, np.float64)
         if boxes.ndim != 2 or boxes.shape[1] != 4:
             raise ValueError(f"--walls must hold [M][4] (cx, cy, hx, hy), got shape {boxes.shape}")
         wl = Walls(np.concatenate([boxes, Walls.enclosure()]) if arena else boxes, radius=float(robot_radius), indicator=False)
-    r = follow_waypoints(policy, env, start, waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
+    n_waypoints = replan = None
+    if goal is not None:
+        from mobrob_amd.planning import GridPlanner
+        goal = np.asarray(goal, np.float64).reshape(-1)
+        if goal.shape != (p,) or p < 2:
+            raise ValueError(f"--goal must hold {p} coordinates of a robot that moves in x and y, got {goal.size}")
+        goals = np.tile(goal, (int(robots), 1))
+        planner = GridPlanner(env, walls=wl, hazards=hz if isinstance(hz, Hazards) else None, cells=int(plan_cells), engine=policy)
+        plan = planner.plan(start, goals, grow=True)
+        waypoints, n_waypoints = plan["waypoints"], plan["n_waypoints"]
+        replan = planner.callback(goals) if int(leg_steps) > 0 else None
+        print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
+    schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
+    r = follow_waypoints(policy, env, start, waypoints, n_waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
                          leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
     for steps in calls[1:]:                                # the run, continued call after call
+        if replan is not None:                             # a stalled robot is planned again from where it stands
+            for robot, w in replan(np.array(r["state"].positions), r["status"], r["reached"]).items():
+                r["state"].replan([robot], np.asarray(w, np.float64)[None])
         r = follow_waypoints(policy, env, max_steps=steps, deterministic=True, seed=seed, hazards=hz, state=r["state"],
                              leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
     K = r["arrival"].shape[1]
-    done = r["reached"] == K
-    last = r["arrival"][done, K - 1]
+    done = r["reached"] == (K if goal is None else np.where(r["state"].n_waypoints > 0, r["state"].n_waypoints, -1))
+    last = r["arrival"][done, (K if goal is None else r["state"].n_waypoints[done]) - 1]
     print(f"success rate: {float(np.mean(done))}")
     print(f"mean waypoints reached: {float(np.mean(r['reached']))}")
     print(f"mean arrival step of the last waypoint: {float(np.mean(last)) if last.size else float('nan')}")
@@ -155,7 +178,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--env-name", type=str, default="point")
     ap.add_argument("--policy-name", type=str, default="ppo")
-    ap.add_argument("--waypoints", type=str, required=True, help="[K][P] or [n][K][P] positions (.npy)")
+    ap.add_argument("--waypoints", type=str, default=None, help="[K][P] or [n][K][P] positions (.npy)")
+    ap.add_argument("--goal", type=str, default=None, help="x,y (x,y,z): plan the waypoints to this goal instead of --waypoints")
+    ap.add_argument("--plan-cells", type=int, default=64, help="grid cells a side of the planner (32, 64, 128)")
     ap.add_argument("--robots", type=int, default=1)
     ap.add_argument("--max-steps", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
@@ -175,13 +200,16 @@ if __name__ == "__main__":
     ap.add_argument("--robot-radius", type=float, default=0.1, help="the robot's footprint for wall contact")
     ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
     args = ap.parse_args()
+    if (args.waypoints is None) == (args.goal is None):
+        ap.error("give --waypoints or --goal, not both")
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
     except ValueError as ex:
         ap.error(str(ex))
-    follow(args.env_name, args.policy_name, np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed,
+    follow(args.env_name, args.policy_name, None if args.waypoints is None else np.load(args.waypoints), args.robots, args.max_steps, args.host, args.seed,
            hazards=None if args.hazards is None else (np.load(args.hazards), args.hazard_size), horizon=args.horizon,
            leg_steps=args.leg_steps, hazard_frames=None if args.hazard_frames is None else np.load(args.hazard_frames),
            frame_steps=args.frame_steps, hazard_loop=args.hazard_loop, team_size=args.team_size, separation=args.separation,
            release=None if args.release is None else np.load(args.release), stagger=args.stagger,
-           walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius)
+           walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius,
+           goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells)

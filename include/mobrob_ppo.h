@@ -764,6 +764,57 @@ int mobrob_ppo_follow_waypoints_walls(mobrob_ppo_engine_t* e, const mobrob_goal_
                                       double* wall_out /* [n][7] in / out */, float* path_out /* or NULL */,
                                       float* trace_out /* or NULL */);
 
+/* ---- grid planner: walls and hazards to waypoints ---------------------------------------------------------------------------
+ * Plans waypoints for n_robots robots at once on a grid of cells x cells (32, 64 or 128) over [-extent, extent]^2, x and y only, from
+ * the scenes of `walls` and / or `hazards` (neither: an empty grid).  The rule is stated once in mobrob_amd/envs/goal_rules.py
+ * (GridSpec, grid_occupancy, grid_field, grid_path) and the device reproduces it bit for bit: a cell is blocked when its centre has
+ * the walls' signed distance <= inflate to a wall, or lies within radius + inflate of a hazard (equality blocks); the field of a
+ * (scene, goal cell) is the cost-to-go over eight-connected moves (5 orthogonal, 7 diagonal, no corner cutting), -1 where blocked or
+ * unreachable; a robot's path descends its field, the previous direction first, else the lowest of E, N, W, S, NE, NW, SW, SE, and
+ * its waypoints are the centres of the cells where the direction changes, then the goal itself (z of every waypoint: the goal's).
+ * h = 2 extent / cells and inv_h = cells / (2 extent) are computed once by the caller, as floats; host and device use those two.
+ * Robots that share a scene and a goal cell share a FIELD: the caller lists the n_fields distinct (scene, goal cell) pairs and gives
+ * every robot the index of its own.  With walls and hazards both, the two must agree on n_scenes and on the scene of every robot.
+ *   outputs   waypoints_out [n][K][pos_dim] (the first min(count, K), the other slots 0), n_waypoints_out [n] = min(count, K),
+ *             count_out [n] waypoints of the full path, cost_out [n] the field at the start cell (-1: unreachable), status_out [n]:
+ *             0 planned; 1 unreachable (start or goal cell blocked, or no path; count 0); 2 truncated (count > K); 3 a loop of the
+ *             device ran into its bound of cells * cells sweeps or steps (count 0).  Optional copies: occupancy_out [S][G][G] (1
+ *             blocked; row iy, column ix), field_out [F][G][G], sweeps_out [F] (relaxation sweeps run, -1: bound hit).
+ *   reuse     fields_id_out receives an id > 0 of the occupancy and the fields this call computed; they stay resident until the next
+ *             computing call.  A call with spec->reuse_id equal to it (same cells, n_scenes, n_fields) runs the path kernel alone on
+ *             them -- a replanning round: new starts, the same goals; walls, hazards, field_goal_cell and field_scene are then unused
+ *             but for the scene index per robot.  A stale id is MOBROB_ERR_STATE.
+ *   kernels   k_plan_occupancy (a thread per scene and cell, the scene staged in LDS), k_plan_field (a workgroup per field, the field
+ *             and a byte of moves per cell in dynamic LDS -- 5 bytes a cell, 80 KB at 128 cells --, in-place relaxation sweeps until
+ *             a workgroup-wide "nothing changed"), k_plan_path (a thread per robot).  Runs on the engine's stream, in buffers of its
+ *             own outside the arena; nothing a training step reads or writes is touched.
+ * MOBROB_ERR_INVALID before any launch or copy for: a NULL argument, n_robots < 1, pos_dim not 2 or 3, cells not 32 / 64 / 128,
+ * max_waypoints < 1, n_fields outside 1 .. n_robots, extent, h, inv_h not finite and > 0 or h * inv_h not 1 within 1e-5, inflate
+ * negative or non-finite, n_scenes not the scenes' own, a scene that the walls / hazards calls would refuse (radius and costs
+ * aside), walls and hazards that disagree on a robot's scene, a non-finite start or goal, field_of outside 0 .. n_fields - 1, a
+ * field's scene or goal cell out of range, a robot whose scene or goal cell is not its field's, a field too large for the
+ * device's LDS per workgroup. */
+typedef struct mobrob_plan_spec {
+  int32_t n_robots;       /* n >= 1                                                   */
+  int32_t pos_dim;        /* 2 or 3                                                   */
+  int32_t cells;          /* G: 32, 64 or 128                                         */
+  int32_t max_waypoints;  /* K >= 1                                                   */
+  int32_t n_scenes;       /* S: the walls' / hazards' n_scenes, 1 without both        */
+  int32_t n_fields;       /* F distinct (scene, goal cell) pairs, 1 .. n              */
+  float extent;           /* the grid covers [-extent, extent]^2                      */
+  float h, inv_h;         /* float(2 extent / G), float(G / (2 extent))               */
+  float inflate;          /* clearance of a blocked cell's centre, >= 0               */
+  int64_t reuse_id;       /* 0: compute occupancy and fields; else a fields_id_out    */
+} mobrob_plan_spec_t;
+int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                         const mobrob_hazards_t* hazards /* or NULL */, const float* start /* [n][pos_dim] */,
+                         const float* goal /* [n][pos_dim] */, const int32_t* field_of /* [n] index into the fields */,
+                         const int32_t* field_goal_cell /* [F] iy * G + ix */, const int32_t* field_scene /* [F] */,
+                         float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */,
+                         int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */, uint8_t* occupancy_out /* [S][G][G] or NULL */,
+                         int32_t* field_out /* [F][G][G] or NULL */, int32_t* sweeps_out /* [F] or NULL */,
+                         int64_t* fields_id_out /* or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

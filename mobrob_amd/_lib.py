@@ -100,6 +100,12 @@ class WallsC(C.Structure):  # mobrob_walls_t
                 ("indicator", C.c_int32)]
 
 
+class PlanSpec(C.Structure):  # mobrob_plan_spec_t
+    _fields_ = [("n_robots", C.c_int32), ("pos_dim", C.c_int32), ("cells", C.c_int32), ("max_waypoints", C.c_int32),
+                ("n_scenes", C.c_int32), ("n_fields", C.c_int32), ("extent", C.c_float), ("h", C.c_float), ("inv_h", C.c_float),
+                ("inflate", C.c_float), ("reuse_id", C.c_int64)]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -192,6 +198,10 @@ SYMBOLS = {
                                                     C.POINTER(FollowScheduleC), C.POINTER(WallsC), _F, C.POINTER(C.c_int32),
                                                     C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _F, _F]),
+    "mobrob_ppo_plan_grid": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardsC), _F, _F, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _U8, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       _I64]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

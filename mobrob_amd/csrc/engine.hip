@@ -54,6 +54,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_hazard.h"
 #include "kernels_team.h"
 #include "kernels_wall.h"
+#include "kernels_plan.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -270,6 +271,15 @@ struct mobrob_ppo_engine {
   // policy evaluation (mobrob_ppo_evaluate_goal_env): one hipMalloc of its own, outside the arena, grown on demand
   char* eval_buf = nullptr;
   size_t eval_bytes = 0;
+  // grid planner (mobrob_ppo_plan_grid): two allocations of its own, outside the arena, grown on demand.  plan_fields holds what
+  // a replanning round reuses (occupancy, fields, their scenes, goal cells and sweep counts), plan_buf a call's inputs and outputs
+  char* plan_fields = nullptr;
+  char* plan_buf = nullptr;
+  size_t plan_fields_bytes = 0, plan_bytes = 0;
+  int64_t plan_id = 0;                // id of the resident fields, 0: none
+  int plan_G = 0, plan_S = 0, plan_F = 0;
+  std::vector<int32_t> plan_field_scene, plan_field_goal;   // the resident fields' (scene, goal cell)
+  bool plan_lds_set = false;          // k_plan_field's dynamic-LDS attribute is raised once
 };
 
 namespace {
@@ -1341,6 +1351,8 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->eval_buf) (void)hipFree(e->eval_buf);
+  if (e->plan_fields) (void)hipFree(e->plan_fields);
+  if (e->plan_buf) (void)hipFree(e->plan_buf);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3909,6 +3921,213 @@ int mobrob_ppo_follow_waypoints_walls(mobrob_ppo_engine_t* e, const mobrob_goal_
   const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
   return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
                           (hz || hzf) ? &hio : nullptr, resume, teams ? &tio : nullptr, schedule ? &sio : nullptr, &wio);
+}
+
+// ---- grid planner (mobrob_ppo_plan_grid): walls and hazards to waypoints ---------------------------------------------------
+// one of the planner's two device buffers, grown to `need` bytes (outside the arena, freed by destroy)
+static int grow_plan_buf(mobrob_ppo_engine_t* e, char*& buf, size_t& bytes, size_t need) {
+  if (need > bytes) {
+    HIPC(hipStreamSynchronize(e->stream));
+    if (buf) HIPC(hipFree(buf));
+    buf = nullptr;
+    bytes = 0;
+    HIPC(hipMalloc(reinterpret_cast<void**>(&buf), need));
+    bytes = need;
+  }
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                         const float* start, const float* goal, const int32_t* field_of, const int32_t* field_goal_cell,
+                         const int32_t* field_scene, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
+                         int32_t* status_out, int32_t* cost_out, uint8_t* occupancy_out, int32_t* field_out, int32_t* sweeps_out,
+                         int64_t* fields_id_out) {
+  if (!e || !spec || !start || !goal || !field_of || !waypoints_out || !n_waypoints_out || !count_out || !status_out || !cost_out)
+    return fail(MOBROB_ERR_INVALID, "plan: null argument");
+  const bool reuse = spec->reuse_id != 0;
+  if (!reuse && (!field_goal_cell || !field_scene)) return fail(MOBROB_ERR_INVALID, "plan: null argument");
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "plan: n_robots must be >= 1");
+  if (P != 2 && P != 3) return fail(MOBROB_ERR_INVALID, "plan: pos_dim must be 2 or 3 (the grid is x and y)");
+  if (G != 32 && G != 64 && G != 128) return fail(MOBROB_ERR_INVALID, "plan: cells must be 32, 64 or 128, got %d", G);
+  if (K < 1) return fail(MOBROB_ERR_INVALID, "plan: max_waypoints must be >= 1");
+  if (F < 1 || F > N) return fail(MOBROB_ERR_INVALID, "plan: n_fields = %d outside 1 .. n_robots = %d", F, N);
+  if (!(std::isfinite(spec->extent) && spec->extent > 0.f && std::isfinite(spec->h) && spec->h > 0.f && std::isfinite(spec->inv_h) &&
+        spec->inv_h > 0.f && std::fabs((double)spec->h * (double)spec->inv_h - 1.0) <= 1e-5))
+    return fail(MOBROB_ERR_INVALID, "plan: extent, h and inv_h must be finite and > 0 with h * inv_h = 1");
+  if (!(std::isfinite(spec->inflate) && spec->inflate >= 0.f)) return fail(MOBROB_ERR_INVALID, "plan: inflate must be finite and >= 0");
+  if ((int64_t)N * K * P > INT_MAX) return fail(MOBROB_ERR_INVALID, "plan: n_robots * max_waypoints * pos_dim must fit an int32");
+  const int cells = G * G;
+  if (S != (walls ? walls->n_scenes : hz ? hz->n_scenes : 1) || (walls && hz && walls->n_scenes != hz->n_scenes))
+    return fail(MOBROB_ERR_INVALID, "plan: n_scenes = %d is not the scenes' own (walls %d, hazards %d)", S, walls ? walls->n_scenes : -1,
+                hz ? hz->n_scenes : -1);
+  // the scenes, by the checks of the calls that take them (the walls' radius and the costs play no part here)
+  std::vector<int32_t> wall_counts, hz_counts;
+  if (walls) {
+    const int M = walls->max_walls;
+    if (S < 1) return fail(MOBROB_ERR_INVALID, "plan: walls: n_scenes must be >= 1");
+    if (M < 0 || M > kWallMax) return fail(MOBROB_ERR_INVALID, "plan: walls: max_walls must lie in 0 .. %d", kWallMax);
+    if (M > 0 && !walls->boxes) return fail(MOBROB_ERR_INVALID, "plan: walls: null box table");
+    if (!walls->scene && S > 1) return fail(MOBROB_ERR_INVALID, "plan: walls: %d scenes need a scene index per robot", S);
+    wall_counts.assign(S, M);
+    for (int s = 0; s < S; ++s) {
+      if (walls->n_walls) wall_counts[s] = walls->n_walls[s];
+      if (wall_counts[s] < 0 || wall_counts[s] > M)
+        return fail(MOBROB_ERR_INVALID, "plan: walls: n_walls[%d] = %d outside 0 .. %d", s, wall_counts[s], M);
+      for (int i = 0; i < wall_counts[s]; ++i) {
+        const float* b = walls->boxes + ((size_t)s * M + i) * 4;
+        if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]) && b[2] >= 0.f && b[3] >= 0.f))
+          return fail(MOBROB_ERR_INVALID, "plan: walls: box %d of scene %d is not finite or has a negative half extent", i, s);
+      }
+    }
+    if (walls->scene)
+      for (int i = 0; i < N; ++i)
+        if (walls->scene[i] < 0 || walls->scene[i] >= S)
+          return fail(MOBROB_ERR_INVALID, "plan: walls: scene[%d] = %d outside 0 .. %d", i, walls->scene[i], S - 1);
+  }
+  if (hz) {
+    mobrob_hazards_t view = *hz;
+    view.cost = 0.f;   // (unused here: not refused)
+    const HazardIO hio{&view, nullptr, nullptr};
+    if (const int rc = hazard_check(hio, N, "plan", hz_counts)) return rc;
+  }
+  if (walls && hz) {
+    if ((walls->scene != nullptr) != (hz->scene != nullptr))
+      return fail(MOBROB_ERR_INVALID, "plan: walls and hazards must agree on the scene index per robot");
+    for (int i = 0; walls->scene && i < N; ++i)
+      if (walls->scene[i] != hz->scene[i])
+        return fail(MOBROB_ERR_INVALID, "plan: walls and hazards disagree on the scene of robot %d (%d and %d)", i, walls->scene[i], hz->scene[i]);
+  }
+  const int32_t* scene = walls ? walls->scene : hz ? hz->scene : nullptr;
+  if (reuse) {
+    if (spec->reuse_id != e->plan_id || e->plan_id == 0)
+      return fail(MOBROB_ERR_STATE, "plan: the fields of id %lld are no longer resident (resident: %lld)", (long long)spec->reuse_id,
+                  (long long)e->plan_id);
+    if (G != e->plan_G || S != e->plan_S || F != e->plan_F)
+      return fail(MOBROB_ERR_INVALID, "plan: reuse: cells, n_scenes, n_fields = %d, %d, %d are not the resident fields' %d, %d, %d", G, S, F,
+                  e->plan_G, e->plan_S, e->plan_F);
+    field_goal_cell = e->plan_field_goal.data();
+    field_scene = e->plan_field_scene.data();
+  } else {
+    for (int f = 0; f < F; ++f) {
+      if (field_scene[f] < 0 || field_scene[f] >= S)
+        return fail(MOBROB_ERR_INVALID, "plan: field_scene[%d] = %d outside 0 .. %d", f, field_scene[f], S - 1);
+      if (field_goal_cell[f] < 0 || field_goal_cell[f] >= cells)
+        return fail(MOBROB_ERR_INVALID, "plan: field_goal_cell[%d] = %d outside 0 .. %d", f, field_goal_cell[f], cells - 1);
+    }
+  }
+  const auto cell_of = [&](float x) {   // plan_cell's arithmetic (kernels_plan.h); volatile: the sum is rounded to float before the product
+    volatile float sum = x + spec->extent;
+    volatile float c = sum * spec->inv_h;
+    return (int)std::fmin(std::fmax(std::floor((float)c), 0.f), (float)(G - 1));
+  };
+  for (int i = 0; i < N; ++i) {
+    for (int j = 0; j < P; ++j)
+      if (!std::isfinite(start[(size_t)i * P + j]) || !std::isfinite(goal[(size_t)i * P + j]))
+        return fail(MOBROB_ERR_INVALID, "plan: start or goal of robot %d is not finite", i);
+    const int f = field_of[i];
+    if (f < 0 || f >= F) return fail(MOBROB_ERR_INVALID, "plan: field_of[%d] = %d outside 0 .. %d", i, f, F - 1);
+    if (field_scene[f] != (scene ? scene[i] : 0))
+      return fail(MOBROB_ERR_INVALID, "plan: robot %d is in scene %d, its field %d in scene %d", i, scene ? scene[i] : 0, f, field_scene[f]);
+    const int gc = cell_of(goal[(size_t)i * P + 1]) * G + cell_of(goal[(size_t)i * P]);
+    if (gc != field_goal_cell[f])
+      return fail(MOBROB_ERR_INVALID, "plan: the goal of robot %d lies in cell %d, its field %d has goal cell %d", i, gc, f, field_goal_cell[f]);
+  }
+  const size_t field_lds = plan_field_lds_bytes(G);
+  const int Mw = walls ? walls->max_walls : 0, Mh = hz ? hz->max_hazards : 0;
+  if (!reuse) {   // the per-workgroup LDS limit, as the tile kernels' scenes are checked
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+    if (field_lds > (size_t)limit)
+      return fail(MOBROB_ERR_INVALID, "plan: k_plan_field needs %zu bytes of LDS at %d cells, the device allows %d per workgroup", field_lds, G, limit);
+  }
+  // the resident part: occupancy | field | field_goal | field_scene | sweeps
+  EvalCarve keep;
+  const size_t o_occ = keep.add((size_t)S * cells), o_field = keep.add((size_t)F * cells * 4), o_fgoal = keep.add((size_t)F * 4),
+               o_fscene = keep.add((size_t)F * 4), o_sweeps = keep.add((size_t)F * 4);
+  // the call's part
+  EvalCarve call;
+  const size_t o_start = call.add((size_t)N * P * 4), o_goal = call.add((size_t)N * P * 4), o_fof = call.add((size_t)N * 4),
+               o_wp = call.add((size_t)N * K * P * 4), o_nwp = call.add((size_t)N * 4), o_count = call.add((size_t)N * 4),
+               o_status = call.add((size_t)N * 4), o_cost = call.add((size_t)N * 4),
+               o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
+               o_hz = call.add(std::max<size_t>((size_t)S * Mh * 3, 1) * 4), o_nhz = call.add((size_t)S * 4);
+  if (!reuse) {
+    e->plan_id = 0;   // whatever was resident is gone from here on
+    if (const int rc = grow_plan_buf(e, e->plan_fields, e->plan_fields_bytes, keep.total)) return rc;
+  }
+  if (const int rc = grow_plan_buf(e, e->plan_buf, e->plan_bytes, call.total)) return rc;
+  const auto kept = [&](size_t off) { return e->plan_fields + off; };
+  const auto mine = [&](size_t off) { return e->plan_buf + off; };
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(kept(o_occ));
+  int* field_dev = reinterpret_cast<int*>(kept(o_field));
+  int* fgoal_dev = reinterpret_cast<int*>(kept(o_fgoal));
+  int* fscene_dev = reinterpret_cast<int*>(kept(o_fscene));
+  int* sweeps_dev = reinterpret_cast<int*>(kept(o_sweeps));
+  const PlanGrid grid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  if (!reuse) {
+    PlanOccArgs oa{};
+    oa.g = grid; oa.Mw = Mw; oa.Mh = Mh; oa.occ = occ_dev;
+    if (walls) {
+      float* box_dev = reinterpret_cast<float*>(mine(o_box));
+      int* cnt_dev = reinterpret_cast<int*>(mine(o_nwall));
+      if ((size_t)S * Mw) HIPC(hipMemcpyAsync(box_dev, walls->boxes, (size_t)S * Mw * 16, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(cnt_dev, wall_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+      oa.boxes = box_dev; oa.nwall = cnt_dev;
+    }
+    if (hz) {
+      float* hz_dev = reinterpret_cast<float*>(mine(o_hz));
+      int* cnt_dev = reinterpret_cast<int*>(mine(o_nhz));
+      if ((size_t)S * Mh) HIPC(hipMemcpyAsync(hz_dev, hz->hazards, (size_t)S * Mh * 12, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(cnt_dev, hz_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+      oa.hz = hz_dev; oa.nhz = cnt_dev;
+    }
+    HIPC(hipMemcpyAsync(fgoal_dev, field_goal_cell, (size_t)F * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(fscene_dev, field_scene, (size_t)F * 4, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_plan_occupancy, dim3(cdiv(cells, 256), S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
+    if (!e->plan_lds_set) {   // 80 KB at 128 cells: above the 64 KB a kernel gets without asking
+      HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_field), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)plan_field_lds_bytes(128)));
+      e->plan_lds_set = true;
+    }
+    const PlanFieldArgs fa{G, occ_dev, fgoal_dev, fscene_dev, field_dev, sweeps_dev};
+    hipLaunchKernelGGL(k_plan_field, dim3(F), dim3(kPlanFieldThreads), field_lds, e->stream, fa);
+    HIPC(hipGetLastError());
+  }
+  PlanPathArgs pa{};
+  pa.g = grid; pa.N = N; pa.K = K; pa.P = P;
+  float* start_dev = reinterpret_cast<float*>(mine(o_start));
+  float* goal_dev = reinterpret_cast<float*>(mine(o_goal));
+  int* fof_dev = reinterpret_cast<int*>(mine(o_fof));
+  pa.start = start_dev; pa.goal = goal_dev; pa.field_of = fof_dev;
+  pa.field_scene = fscene_dev; pa.sweeps = sweeps_dev; pa.occ = occ_dev; pa.field = field_dev;
+  pa.wp = reinterpret_cast<float*>(mine(o_wp));
+  pa.nwp = reinterpret_cast<int*>(mine(o_nwp)); pa.count = reinterpret_cast<int*>(mine(o_count));
+  pa.status = reinterpret_cast<int*>(mine(o_status)); pa.cost = reinterpret_cast<int*>(mine(o_cost));
+  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(goal_dev, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(fof_dev, field_of, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
+  hipLaunchKernelGGL(k_plan_path, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, pa);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  if (occupancy_out) HIPC(hipMemcpyAsync(occupancy_out, occ_dev, (size_t)S * cells, hipMemcpyDeviceToHost, e->stream));
+  if (field_out) HIPC(hipMemcpyAsync(field_out, field_dev, (size_t)F * cells * 4, hipMemcpyDeviceToHost, e->stream));
+  if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, sweeps_dev, (size_t)F * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  if (!reuse) {   // resident from here on
+    static int64_t next_id = 0;
+    e->plan_id = ++next_id;
+    e->plan_G = G; e->plan_S = S; e->plan_F = F;
+    e->plan_field_goal.assign(field_goal_cell, field_goal_cell + F);
+    e->plan_field_scene.assign(field_scene, field_scene + F);
+  }
+  if (fields_id_out) *fields_id_out = e->plan_id;
+  return MOBROB_OK;
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -1,0 +1,229 @@
+// Grid planner (mobrob_ppo_plan_grid): walls and hazards to waypoints, for all robots in one call.
+//
+// The rule, stated once in array form in mobrob_amd/envs/goal_rules.py (GridSpec, grid_occupancy, grid_field, grid_path): a grid of
+// G x G cells (G = 32, 64, 128) over [-extent, extent]^2, x and y only.  The host hands down extent, h = 2 extent / G and inv_h =
+// G / (2 extent) as floats; in float, every operation rounded on its own, no fma:
+//   cell of x:   clamp(floor((x + extent) * inv_h), 0, G - 1)          centre of cell i:   -extent + (i + 0.5) * h
+//   blocked:     wall_sdf(centre, wall) <= inflate for a wall of the scene (kernels_wall.h: the walls' own arithmetic), or
+//                sqrt(dx^2 + dy^2) <= radius_k + inflate for a hazard k of the scene (team_partial's distance).  Equality blocks.
+//   field:       the cost-to-go to the goal cell over eight-connected moves, 5 orthogonal and 7 diagonal, a diagonal only where both
+//                orthogonal cells at the corner are free; -1: blocked or unreachable.  It is the unique fixed point of
+//                d[c] = min(d[nb] + w), d[goal] = 0, so the order of the relaxations does not show in it.
+//   path:        from the start's cell to a neighbour with d[nb] + w == d[c], the previous direction first, else the lowest of E, N,
+//                W, S, NE, NW, SW, SE; a cell's centre is a waypoint where the direction changes; the last waypoint is the goal.
+// Three kernels: k_plan_occupancy (a thread per scene and cell), k_plan_field (a workgroup per distinct (scene, goal cell), the
+// field in LDS, sweeps of in-place relaxations until a workgroup-wide "nothing changed", at most G * G of them), k_plan_path (a
+// thread per robot, at most G * G steps).  A loop that runs into its bound reports status 3; nothing here can spin.
+#pragma once
+#include "kernels_wall.h"
+
+namespace mobrob {
+
+constexpr int kPlanInf = 0x3FFFFFFF;   // "no path yet" inside k_plan_field (any sum of a path's costs stays far below it)
+constexpr int kPlanFieldThreads = 1024;
+// status of a robot's plan
+constexpr int kPlanned = 0, kPlanUnreachable = 1, kPlanTruncated = 2, kPlanUnconverged = 3;
+
+struct PlanGrid {
+  int G;                   // cells per side
+  float extent, h, inv_h;  // the host's floats
+  float inflate;
+};
+
+__device__ __forceinline__ int plan_cell(const PlanGrid& g, float x) {
+  const float c = floorf(__fmul_rn(__fadd_rn(x, g.extent), g.inv_h));
+  return (int)fminf(fmaxf(c, 0.f), (float)(g.G - 1));
+}
+__device__ __forceinline__ float plan_centre(const PlanGrid& g, int i) {
+  return __fadd_rn(-g.extent, rounded(__fmul_rn(__fadd_rn((float)i, 0.5f), g.h)));
+}
+// move k of E, N, W, S, NE, NW, SW, SE
+__device__ __forceinline__ int plan_dx(int k) { return k == 0 || k == 4 || k == 7 ? 1 : (k == 1 || k == 3 ? 0 : -1); }
+__device__ __forceinline__ int plan_dy(int k) { return k == 1 || k == 4 || k == 5 ? 1 : (k == 0 || k == 2 ? 0 : -1); }
+
+// the moves a robot in the free cell (ix, iy) may make, bit k for move k: target in the grid and free, a diagonal only with both
+// orthogonal cells at the corner free
+template <class Occ>
+__device__ __forceinline__ unsigned plan_moves(const Occ* occ, int G, int ix, int iy) {
+  unsigned free4 = 0;   // E, N, W, S
+  if (ix + 1 < G && !occ[iy * G + ix + 1]) free4 |= 1u;
+  if (iy + 1 < G && !occ[(iy + 1) * G + ix]) free4 |= 2u;
+  if (ix > 0 && !occ[iy * G + ix - 1]) free4 |= 4u;
+  if (iy > 0 && !occ[(iy - 1) * G + ix]) free4 |= 8u;
+  unsigned m = free4;
+  if ((free4 & 3u) == 3u && !occ[(iy + 1) * G + ix + 1]) m |= 16u;     // NE: E and N free
+  if ((free4 & 6u) == 6u && !occ[(iy + 1) * G + ix - 1]) m |= 32u;     // NW: N and W
+  if ((free4 & 12u) == 12u && !occ[(iy - 1) * G + ix - 1]) m |= 64u;   // SW: W and S
+  if ((free4 & 9u) == 9u && !occ[(iy - 1) * G + ix + 1]) m |= 128u;    // SE: S and E
+  return m;
+}
+
+struct PlanOccArgs {
+  PlanGrid g;
+  const float* boxes;   // [S][Mw][4]
+  const int* nwall;     // [S]
+  int Mw;
+  const float* hz;      // [S][Mh][3]
+  const int* nhz;       // [S]
+  int Mh;
+  unsigned char* occ;   // [S][G][G] out: 1 blocked
+};
+
+// grid (cdiv(G * G, 256), S), 256 threads, LDS 4 Mw + 3 Mh floats: the scene's walls and hazards, staged once per workgroup (at
+// the caps of 1024 rows each that is 28 KB: a scene always fits)
+__global__ __launch_bounds__(256) void k_plan_occupancy(PlanOccArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float plan_scene_lds[];
+  const int s = blockIdx.y, G = a.g.G;
+  const int mw = a.nwall ? a.nwall[s] : 0, mh = a.nhz ? a.nhz[s] : 0;
+  float* wl = plan_scene_lds;
+  float* hl = plan_scene_lds + 4 * a.Mw;
+  for (int i = threadIdx.x; i < 4 * mw; i += 256) wl[i] = a.boxes[(size_t)s * a.Mw * 4 + i];
+  for (int i = threadIdx.x; i < 3 * mh; i += 256) hl[i] = a.hz[(size_t)s * a.Mh * 3 + i];
+  __syncthreads();
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= G * G) return;
+  const float px = plan_centre(a.g, c % G), py = plan_centre(a.g, c / G);
+  bool blocked = false;
+  for (int i = 0; i < mw; ++i)
+    if (wall_sdf(px, py, wl[4 * i], wl[4 * i + 1], wl[4 * i + 2], wl[4 * i + 3]) <= a.g.inflate) blocked = true;
+  for (int i = 0; i < mh; ++i) {
+    const float dx = __fsub_rn(px, hl[3 * i]), dy = __fsub_rn(py, hl[3 * i + 1]);
+    const float d = sqrtf(__fadd_rn(rounded(__fmul_rn(dx, dx)), rounded(__fmul_rn(dy, dy))));   // sqrtf: correctly rounded
+    if (d <= __fadd_rn(hl[3 * i + 2], a.g.inflate)) blocked = true;
+  }
+  a.occ[(size_t)s * G * G + c] = blocked ? 1 : 0;
+}
+
+struct PlanFieldArgs {
+  int G;
+  const unsigned char* occ;   // [S][G][G]
+  const int* field_goal;      // [F] goal cell
+  const int* field_scene;     // [F]
+  int* field;                 // [F][G][G] out: cost-to-go, -1 blocked or unreachable
+  int* sweeps;                // [F] out: sweeps run (the last one changed nothing), -1: the bound of G * G was hit
+};
+
+// LDS bytes of k_plan_field: the field, then one byte of moves per cell
+inline size_t plan_field_lds_bytes(int G) { return (size_t)G * G * (sizeof(int) + 1); }
+
+// One workgroup per field, 1024 threads, cell c on thread c % 1024.  The relaxations are IN PLACE: every value ever stored in d is
+// the cost of a real path to the goal and values only decrease, so a neighbour's value read while its owner replaces it is an upper
+// bound either way, and a sweep that changes nothing has found the fixed point.  A cell is read and written as one aligned 32-bit
+// LDS word.  Blocked cells have no moves and stay at kPlanInf.
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_field(PlanFieldArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int plan_field_lds[];
+  const int f = blockIdx.x, G = a.G, cells = G * G, tid = threadIdx.x;
+  int* d = plan_field_lds;
+  unsigned char* moves = reinterpret_cast<unsigned char*>(plan_field_lds + cells);
+  const unsigned char* occ = a.occ + (size_t)a.field_scene[f] * cells;
+  const int goal = a.field_goal[f];
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    const bool blocked = occ[c] != 0;
+    moves[c] = blocked ? 0 : (unsigned char)plan_moves(occ, G, c % G, c / G);
+    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
+  }
+  __syncthreads();
+  int sweeps = -1;
+  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
+    int changed = 0;
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      const unsigned m = moves[c];
+      if (m == 0 || c == goal) continue;
+      const int cur = d[c];
+      int best = cur;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (m & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
+      if (best < cur) { d[c] = best; changed = 1; }
+    }
+    __syncthreads();   // this sweep's stores before the next sweep's loads
+    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
+  }
+  int* out = a.field + (size_t)f * cells;
+  for (int c = tid; c < cells; c += kPlanFieldThreads) out[c] = d[c] >= kPlanInf ? -1 : d[c];
+  if (tid == 0) a.sweeps[f] = sweeps;
+}
+
+struct PlanPathArgs {
+  PlanGrid g;
+  int N, K, P;
+  const float* start;         // [N][P]
+  const float* goal;          // [N][P]
+  const int* field_of;        // [N]
+  const int* field_scene;     // [F]
+  const int* sweeps;          // [F] k_plan_field's: -1 = that field did not converge
+  const unsigned char* occ;   // [S][G][G]
+  const int* field;           // [F][G][G]
+  float* wp;                  // [N][K][P] out (zeroed by the host)
+  int* nwp;                   // [N] out: min(count, K)
+  int* count;                 // [N] out: waypoints of the full path
+  int* status;                // [N] out
+  int* cost;                  // [N] out: d[start cell], -1 unreachable
+};
+
+// one thread per robot: the walk of goal_rules.grid_path on its field in global memory
+__global__ __launch_bounds__(256) void k_plan_path(PlanPathArgs a) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= a.N) return;
+  const int G = a.g.G, cells = G * G, P = a.P, K = a.K;
+  const int f = a.field_of[n];
+  const unsigned char* occ = a.occ + (size_t)a.field_scene[f] * cells;
+  const int* d = a.field + (size_t)f * cells;
+  const float* s = a.start + (size_t)n * P;
+  const float* gl = a.goal + (size_t)n * P;
+  float* wp = a.wp + (size_t)n * K * P;
+  int ix = plan_cell(a.g, s[0]), iy = plan_cell(a.g, s[1]);
+  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
+  int count = 0, status = kPlanned, cost = -1;
+  if (a.sweeps[f] < 0) {
+    status = kPlanUnconverged;
+  } else if (occ[iy * G + ix] || occ[gy * G + gx] || d[iy * G + ix] < 0) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d[iy * G + ix];
+    int prev = -1, steps = 0;
+    while (ix != gx || iy != gy) {
+      if (++steps > cells) { status = kPlanUnconverged; break; }
+      const unsigned m = plan_moves(occ, G, ix, iy);
+      const int dc = d[iy * G + ix];
+      int dir = -1;
+      for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
+        if (!(m & (1u << k))) continue;
+        const int dn = d[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
+        if (dn >= 0 && dn + (k < 4 ? 5 : 7) == dc) dir = k;
+      }
+      if (prev >= 0 && (m & (1u << prev))) {   // the previous direction first
+        const int dn = d[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
+        if (dn >= 0 && dn + (prev < 4 ? 5 : 7) == dc) dir = prev;
+      }
+      if (dir < 0) { status = kPlanUnconverged; break; }   // not a cost-to-go field: cannot happen after a converged k_plan_field
+      if (prev >= 0 && dir != prev) {
+        if (count < K) {
+          wp[count * P] = plan_centre(a.g, ix);
+          wp[count * P + 1] = plan_centre(a.g, iy);
+          if (P == 3) wp[count * P + 2] = gl[2];
+        }
+        ++count;
+      }
+      ix += plan_dx(dir); iy += plan_dy(dir);
+      prev = dir;
+    }
+    if (status == kPlanned) {
+      if (count < K)
+        for (int j = 0; j < P; ++j) wp[count * P + j] = gl[j];
+      ++count;
+      if (count > K) status = kPlanTruncated;
+    }
+  }
+  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
+    for (int j = 0; j < min(count, K) * P; ++j) wp[j] = 0.f;
+    count = 0;
+    cost = -1;
+  }
+  a.nwp[n] = min(count, K);
+  a.count[n] = count;
+  a.status[n] = status;
+  a.cost[n] = cost;
+}
+
+}  // namespace mobrob

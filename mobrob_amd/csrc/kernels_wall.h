@@ -42,6 +42,15 @@ struct WallAcc {
   float min_clear;
 };
 
+// signed distance of (px, py) to the box (cx, cy, hx, hy): the rule's sdf, every operation rounded on its own (also the grid
+// planner's blocked test, kernels_plan.h)
+__device__ __forceinline__ float wall_sdf(float px, float py, float cx, float cy, float hx, float hy) {
+  const float qx = __fsub_rn(fabsf(__fsub_rn(px, cx)), hx), qy = __fsub_rn(fabsf(__fsub_rn(py, cy)), hy);
+  const float ox = fmaxf(qx, 0.f), oy = fmaxf(qy, 0.f);
+  const float out = sqrtf(__fadd_rn(rounded(__fmul_rn(ox, ox)), rounded(__fmul_rn(oy, oy))));   // sqrtf: correctly rounded
+  return __fadd_rn(out, fminf(fmaxf(qx, qy), 0.f));
+}
+
 // one quarter's partial (unscaled) cost, (clearance, wall) and crossing flag: walls q, q + 4, ... of the scene `w` (m of them) for
 // the step from (ax, ay) to (px, py).  Products that feed a sum are pinned (kernels_env.h: rounded), as in team_partial.
 __device__ __forceinline__ void wall_partial(const float* w, int m, int q, float ax, float ay, float px, float py, float radius,
@@ -55,10 +64,7 @@ __device__ __forceinline__ void wall_partial(const float* w, int m, int q, float
   const float aex = fabsf(ex), aey = fabsf(ey);
   for (int i = q; i < m; i += 4) {
     const float cx = w[4 * i], cy = w[4 * i + 1], hx = w[4 * i + 2], hy = w[4 * i + 3];
-    const float qx = __fsub_rn(fabsf(__fsub_rn(px, cx)), hx), qy = __fsub_rn(fabsf(__fsub_rn(py, cy)), hy);
-    const float ox = fmaxf(qx, 0.f), oy = fmaxf(qy, 0.f);
-    const float out = sqrtf(__fadd_rn(rounded(__fmul_rn(ox, ox)), rounded(__fmul_rn(oy, oy))));   // sqrtf: correctly rounded
-    const float sdf = __fadd_rn(out, fminf(fmaxf(qx, qy), 0.f));
+    const float sdf = wall_sdf(px, py, cx, cy, hx, hy);
     if (sdf <= radius) cost = __fadd_rn(cost, __fsub_rn(radius, sdf));
     const float cl = __fsub_rn(sdf, radius);
     if (cl < clear) { clear = cl; wall = i; }   // ascending i: equal clearances keep the lower index

@@ -634,6 +634,71 @@ class PPOEngine:
             out["path"] = path
         return out
 
+    def plan_grid(self, spec, walls=None, hazards=None, *, start, goal, max_waypoints=16, want_occupancy=False, want_fields=False,
+                  reuse=None):
+        """Waypoints for every robot from a grid over the scene (mobrob_ppo_plan_grid; the rule: goal_rules.grid_occupancy /
+        grid_field / grid_path, reproduced bit for bit).  spec: a goal_rules.GridSpec; walls / hazards: a goal_rules.Walls /
+        Hazards or None; start, goal [n][P] (P = 2 or 3).  Robots that share a scene and a goal cell share a field (deduplicated
+        here with NumPy).  Returns a dict: waypoints [n][K][P] float32, n_waypoints, count, status (goal_rules.PLANNED,
+        UNREACHABLE, TRUNCATED, UNCONVERGED), cost [n] int32, field_of [n], field_goal_cell [F], field_scene [F], sweeps [F] (the
+        relaxation sweeps of each field; None on a reused call), fields_id, and on request occupancy bool [S][G][G] and fields int32
+        [F][G][G].  reuse: the dict a previous call returned -- its fields are still on the device (same scene, same goal cells:
+        ValueError otherwise) and only the paths are walked again."""
+        from ._lib import PlanSpec, WallsC
+        from .envs.goal_rules import GridSpec, plan_fields, plan_scene
+        if not isinstance(spec, GridSpec):
+            raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.GridSpec, not {type(spec).__name__}")
+        start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
+        if goal.ndim != 2 or goal.shape[0] < 1 or goal.shape[1] not in (2, 3) or start.shape != goal.shape:
+            raise ValueError(f"plan: start and goal must both be [n_robots, 2 or 3], got shapes {start.shape} and {goal.shape}")
+        if not (np.all(np.isfinite(start)) and np.all(np.isfinite(goal))):
+            raise ValueError("plan: start and goal must be finite")
+        n, P = goal.shape
+        K = int(max_waypoints)
+        if K < 1:
+            raise ValueError("plan: max_waypoints must be >= 1")
+        S, scene = plan_scene(walls, hazards)
+        for sc in (walls, hazards):
+            if sc is not None:
+                sc.check_robots(n)
+        start, goal = np.ascontiguousarray(start, F32), np.ascontiguousarray(goal, F32)
+        field_of, fcell, fscene = plan_fields(spec, None, scene, goal)
+        if reuse is not None and not (np.array_equal(reuse["field_goal_cell"], fcell) and np.array_equal(reuse["field_scene"], fscene)):
+            raise ValueError("plan: reuse: the goal cells or scenes are not those of the fields to reuse")
+        Fn, G = len(fcell), spec.cells
+        i32 = C.POINTER(C.c_int32)
+        sp = PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_scenes, sp.n_fields = n, P, G, K, S, Fn
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(spec.extent), float(spec.h), float(spec.inv_h), float(spec.inflate_for(walls))
+        sp.reuse_id = 0 if reuse is None else int(reuse["fields_id"])
+        wl = None
+        if walls is not None:
+            wl = WallsC()
+            wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+            wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
+            wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
+            wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
+        h, _keep = (None, None) if hazards is None else self._hazards_struct(hazards, n)
+        wp = np.zeros((n, K, P), F32)
+        nwp, count, status, cost = (np.zeros(n, np.int32) for _ in range(4))
+        occ = np.zeros((S, G, G), np.uint8) if want_occupancy else None
+        fields = np.zeros((Fn, G, G), np.int32) if want_fields else None
+        sweeps = np.zeros(Fn, np.int32) if reuse is None else None
+        fid = C.c_int64(0)
+        check(self.lib.mobrob_ppo_plan_grid(
+            self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None else C.byref(h), _fp(start), _fp(goal),
+            field_of.ctypes.data_as(i32), fcell.ctypes.data_as(i32), fscene.ctypes.data_as(i32), _fp(wp), nwp.ctypes.data_as(i32),
+            count.ctypes.data_as(i32), status.ctypes.data_as(i32), cost.ctypes.data_as(i32),
+            None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), None if fields is None else fields.ctypes.data_as(i32),
+            None if sweeps is None else sweeps.ctypes.data_as(i32), C.byref(fid)))
+        out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "field_of": field_of,
+               "field_goal_cell": fcell, "field_scene": fscene, "sweeps": sweeps, "fields_id": int(fid.value)}
+        if occ is not None:
+            out["occupancy"] = occ.astype(bool)
+        if fields is not None:
+            out["fields"] = fields
+        return out
+
     def episode_stats(self, reset=True):
         """Episodes finished by the goal environment since the counters were last reset."""
         st = EpisodeStats()

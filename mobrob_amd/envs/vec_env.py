@@ -233,6 +233,13 @@ class DeviceGoalVecEnv(VecEnvBase):
                                        path_stride=path_stride, trace=trace, hazards=hazards, resume=resume, leg_steps=leg_steps,
                                        teams=teams, schedule=schedule, walls=walls)
 
+    def plan(self, engine, spec, walls=None, hazards=None, *, start, goal, max_waypoints=16, **kwargs):
+        """Waypoints for every robot from a grid over the scene (PPOEngine.plan_grid); start and goal [n][pos_dim] of this task.
+        kwargs: want_occupancy, want_fields, reuse."""
+        if np.ndim(goal) != 2 or np.shape(goal)[1] != self.pos_dim:
+            raise ValueError(f"plan: goal must be [n_robots, {self.pos_dim}], got shape {np.shape(goal)}")
+        return engine.plan_grid(spec, walls, hazards, start=start, goal=goal, max_waypoints=max_waypoints, **kwargs)
+
     def seed(self, seed=None):
         self._seed = seed
 

@@ -1,0 +1,126 @@
+"""Grid planner: from an arena described with `goal_rules.Walls` / `goal_rules.Hazards` and a goal per robot to the waypoints the
+tracker (`mobrob_amd.waypoints`) follows.
+
+    planner = GridPlanner(env, walls=W, hazards=H, cells=64)
+    plan = planner.plan(start, goal)                          # all robots in one device call
+    follow_with_replanning(model, env, start, plan["waypoints"], planner.callback(goal), n_waypoints=plan["n_waypoints"], ...)
+
+The rule -- grid, blocked cells, cost-to-go field, path, waypoints -- is stated once in NumPy (goal_rules.GridSpec, grid_occupancy,
+grid_field, grid_path).  Two paths, one meaning, bit for bit:
+  * device: `env` is a `DeviceGoalVecEnv` and `engine` a PPOEngine (or a PPO that has one): mobrob_ppo_plan_grid, three kernels.
+  * host: `env` is an `EnvWrapper` or an env name: the NumPy rule itself (as `_host_follow` serves following).
+Static scenes only: moving hazards, team-mates and any-angle smoothing are not planned for."""
+from __future__ import annotations
+
+import numpy as np
+
+from .envs import goal_rules as rules
+
+
+class GridPlanner:
+    """A planner over one scene.  env: a DeviceGoalVecEnv (device path; `engine`: the PPOEngine or PPO to run on), or an env name
+    / EnvWrapper (host path, the NumPy rule).  walls / hazards: goal_rules.Walls / Hazards or None; cells: 32, 64 or 128 per side
+    over the env's [-extent, extent]^2; inflate: clearance of a blocked cell's centre (None: the walls' radius + one cell);
+    max_waypoints: the K slots of a plan."""
+
+    def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None):
+        from .envs.vec_env import DeviceGoalVecEnv
+        rules.plan_scene(walls, hazards)
+        self.walls, self.hazards, self.K = walls, hazards, int(max_waypoints)
+        if self.K < 1:
+            raise ValueError("max_waypoints must be >= 1")
+        self.device = isinstance(env, DeviceGoalVecEnv)
+        if self.device:
+            self.engine = getattr(engine, "engine", engine)
+            if self.engine is None:
+                raise ValueError("GridPlanner on a DeviceGoalVecEnv needs engine= (the PPOEngine, or the PPO that owns one)")
+            self.env, self.pos_dim, env_extent = env, env.pos_dim, env.extent
+        else:
+            from .envs.wrapper import EnvWrapper, TimeLimit, get_env
+            if isinstance(env, str):
+                env = get_env(env, terminate_on_goal=False)
+            while isinstance(env, TimeLimit):
+                env = env.env
+            if not isinstance(env, EnvWrapper):
+                raise TypeError(f"GridPlanner: env must be a DeviceGoalVecEnv, an EnvWrapper or an env name, not {type(env).__name__}")
+            self.engine, self.env, self.pos_dim = None, env, len(env.get_pos())
+            env_extent = getattr(env.env, "extent", None)
+        if extent is None:
+            extent = env_extent
+        if extent is None:
+            raise ValueError("GridPlanner: this environment has no extent; give extent=")
+        if self.pos_dim not in (2, 3):
+            raise ValueError(f"GridPlanner: the grid is x and y; the environment has {self.pos_dim} position dimension(s)")
+        self.spec = rules.GridSpec(extent, cells, inflate)
+        self._kept = None        # the latest full plan: its goal cells, scenes and (device: resident, host: arrays) fields
+
+    def _check(self, start, goal):
+        start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
+        if goal.ndim != 2 or goal.shape[1] != self.pos_dim or start.shape != goal.shape:
+            raise ValueError(f"plan: start and goal must both be [n_robots, {self.pos_dim}], got shapes {start.shape} and {goal.shape}")
+        if not (np.all(np.isfinite(start)) and np.all(np.isfinite(goal))):
+            raise ValueError("plan: start and goal must be finite")
+        for sc in (self.walls, self.hazards):
+            if sc is not None:
+                sc.check_robots(goal.shape[0])
+        return start.astype(np.float32), goal.astype(np.float32)
+
+    def _plan(self, start, goal, K, want_occupancy, want_fields):
+        """One call.  The fields of the previous call are reused when this call's (scene, goal cell) list is the same."""
+        _, scene = rules.plan_scene(self.walls, self.hazards)
+        _, fcell, fscene = rules.plan_fields(self.spec, None, scene, goal)
+        kept = self._kept
+        same = kept is not None and np.array_equal(kept["field_goal_cell"], fcell) and np.array_equal(kept["field_scene"], fscene)
+        if self.device:
+            reuse = kept if same and not (want_occupancy or want_fields) and kept["fields_id"] == getattr(self.engine, "_plan_resident", None) else None
+            out = self.engine.plan_grid(self.spec, self.walls, self.hazards, start=start, goal=goal, max_waypoints=K,
+                                        want_occupancy=want_occupancy, want_fields=want_fields, reuse=reuse)
+            self.engine._plan_resident = out["fields_id"]
+            out["fields_reused"] = reuse is not None
+            if reuse is not None:
+                out["sweeps"] = kept["sweeps"]
+        else:
+            out = rules.grid_plan(self.spec, self.walls, self.hazards, start, goal, K, kept["occupancy"] if same else None,
+                                  kept["fields"] if same else None)
+            out["fields_reused"] = bool(same)
+        self._kept = out
+        return out
+
+    def plan(self, start, goal, *, grow=False, want_occupancy=False, want_fields=False):
+        """start, goal [n][P] -> dict: waypoints [n][K][P] float32 (z: the goal's), n_waypoints [n] (= min(count, K)), count [n]
+        waypoints of the full path, status [n] (goal_rules.PLANNED 0, UNREACHABLE 1, TRUNCATED 2; UNCONVERGED 3: a device loop hit
+        its bound), cost [n] int32 (-1: unreachable), cost_distance [n] float64 = cost * h / 5 (NaN: unreachable), field_of [n],
+        field_goal_cell [F], field_scene [F]; with want_occupancy / want_fields also occupancy bool [S][G][G] / fields int32
+        [F][G][G].  grow: when a robot's path was truncated, plan again with K = count.max() (this call only)."""
+        start, goal = self._check(start, goal)
+        out = self._plan(start, goal, self.K, want_occupancy, want_fields)
+        if grow and np.any(out["status"] == rules.TRUNCATED):
+            out = self._plan(start, goal, int(out["count"].max()), want_occupancy, want_fields)
+        res = {k: out[k] for k in ("waypoints", "n_waypoints", "count", "status", "cost", "field_of", "field_goal_cell", "field_scene",
+                                   "fields_reused")}
+        res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
+        if want_occupancy:
+            res["occupancy"] = out["occupancy"]
+        if want_fields:
+            res["fields"] = out["fields"]
+        if out.get("sweeps") is not None:
+            res["sweeps"] = out["sweeps"]
+        return res
+
+    def callback(self, goal):
+        """The `planner(positions, status, reached)` of waypoints.follow_with_replanning for the goals `goal` [n][P]: every
+        STALLED robot is planned again from where it stands -- all robots in one call, so the fields of the unchanged goals are
+        reused and only the paths are walked -- and gets {robot: waypoints[:count]}; robots whose plan is not PLANNED (unreachable
+        from there, or longer than max_waypoints) are left alone.  `callback.last` holds the latest plan (None before the first)."""
+        from .waypoints import STALLED
+        goal = np.asarray(goal, np.float64)
+
+        def planner(positions, status, reached):
+            stalled = np.nonzero(np.asarray(status) == STALLED)[0]
+            if stalled.size == 0:
+                return {}
+            plan = self.plan(positions, goal)
+            planner.last = plan
+            return {int(i): plan["waypoints"][i, :plan["n_waypoints"][i]].copy() for i in stalled if plan["status"][i] == rules.PLANNED}
+        planner.last = None
+        return planner

@@ -1,0 +1,222 @@
+"""GPU: the grid planner on the device (mobrob_ppo_plan_grid: k_plan_occupancy, k_plan_field, k_plan_path) against the NumPy rule
+(goal_rules.grid_plan), BIT FOR BIT: bool occupancy, int32 fields, float32 waypoints compared as uint32, counts, statuses, costs.
+Nothing here has a tolerance: the rule fixes every float32 operation and the field is the unique fixed point of its relaxation."""
+import numpy as np
+import pytest
+
+from mobrob_amd.envs import goal_rules as R
+from mobrob_amd.envs.goal_rules import GridSpec, Hazards, Walls, grid_plan
+from mobrob_amd.planning import GridPlanner
+from mobrob_amd.waypoints import STALLED, follow_with_replanning
+from tests.plan_scenes import EXTENT, INFLATE, SCENE0, arena, robots33, serpentine, three_hazards, two_scenes
+from tests.util import _engine, _env, _snapshot, golden_params, load_golden
+
+pytestmark = pytest.mark.gpu
+KW = dict(pi=(64, 64), vf=(64, 64))
+
+
+@pytest.fixture(scope="module")
+def engine():
+    e, _ = _engine("point", KW)
+    yield e
+    e.close()
+
+
+def same(dev, ref, keys=("waypoints", "n_waypoints", "count", "status", "cost", "occupancy", "fields", "field_of", "field_goal_cell", "field_scene")):
+    for k in keys:
+        assert dev[k].dtype == ref[k].dtype and dev[k].shape == ref[k].shape, (k, dev[k].dtype, dev[k].shape, ref[k].dtype, ref[k].shape)
+        bad = np.flatnonzero(dev[k].ravel() != ref[k].ravel()) if k != "waypoints" else \
+            np.flatnonzero(np.ascontiguousarray(dev[k]).view(np.uint32).ravel() != np.ascontiguousarray(ref[k]).view(np.uint32).ravel())
+        assert bad.size == 0, f"{k}: {bad.size} of {dev[k].size} entries differ, first at {bad[:5]}"
+    assert not np.any(dev["status"] == R.UNCONVERGED)
+
+
+@pytest.mark.parametrize("scene_kind", ["walls", "walls_hazards", "hazards", "empty"])
+def test_g32_two_scenes_33_robots_7_goals(engine, scene_kind):
+    scene, start, goal = robots33()
+    walls = two_scenes(scene) if scene_kind.startswith("walls") else None
+    hazards = three_hazards(scene) if "hazards" in scene_kind else None
+    if scene_kind == "empty":
+        hazards = Hazards(np.zeros((0, 2)))                                     # M = 0: an empty grid through the hazards' path
+    spec = GridSpec(EXTENT, 32, INFLATE if walls is not None else None)           # without walls: the default inflate (one cell)
+    ref = grid_plan(spec, walls, hazards, start, goal, 4)
+    dev = engine.plan_grid(spec, walls, hazards, start=start, goal=goal, max_waypoints=4, want_occupancy=True, want_fields=True)
+    same(dev, ref)
+    assert len(ref["field_goal_cell"]) == (14 if scene_kind != "empty" else 7) < 33
+    assert np.all((dev["sweeps"] >= 1) & (dev["sweeps"] <= 32 * 32))
+    if scene_kind == "walls":                                                   # the rule alone yields every status but 3
+        assert set(ref["status"].tolist()) == {R.PLANNED, R.UNREACHABLE, R.TRUNCATED}
+    if scene_kind == "empty":
+        assert not dev["occupancy"].any() and np.all(dev["status"] == R.PLANNED)
+        none = engine.plan_grid(spec, None, None, start=start, goal=goal, max_waypoints=4, want_occupancy=True, want_fields=True)
+        same(none, ref)
+
+
+def test_g128_four_fields_uses_the_large_lds_path(engine):
+    rng = np.random.default_rng(5)
+    walls = Walls(SCENE0, radius=0.05)
+    goals = np.array([(1.2, 1.2), (-1.2, -1.2), (1.2, -1.3), (-0.3, 1.3)], np.float32)     # the third lies in the sealed pocket
+    start = rng.uniform(-1.5, 1.5, (9, 2)).astype(np.float32)
+    goal = goals[np.arange(9) % 4]
+    spec = GridSpec(EXTENT, 128)                                                 # default inflate: radius + h
+    ref = grid_plan(spec, walls, None, start, goal, 12)
+    dev = engine.plan_grid(spec, walls, None, start=start, goal=goal, max_waypoints=12, want_occupancy=True, want_fields=True)
+    same(dev, ref)
+    assert len(ref["field_goal_cell"]) == 4 and np.any(ref["status"] == R.PLANNED) and np.any(ref["status"] == R.UNREACHABLE)
+
+
+def test_g64_serpentine_converges_by_fixed_point_not_by_sweep_count(engine):
+    spec, walls, start, goal = serpentine()
+    ref = grid_plan(spec, walls, None, start, goal, 64)
+    dev = engine.plan_grid(spec, walls, None, start=start, goal=goal, max_waypoints=64, want_occupancy=True, want_fields=True)
+    print("serpentine sweeps:", dev["sweeps"], "cost:", dev["cost"], "count:", dev["count"])
+    same(dev, ref)
+    assert ref["status"][0] == R.PLANNED and ref["cost"][0] > 2 * 64 * R.PLAN_DIAG   # more moves than 2 G, whatever their kind
+    assert 1 <= dev["sweeps"][0] <= 64 * 64
+
+
+def test_truncation_grow_and_reuse_on_the_planner(engine):
+    scene, start, goal = robots33()
+    walls = two_scenes(scene)
+    env = _env("point", 33)
+    planner = GridPlanner(env, walls=walls, cells=32, inflate=INFLATE, max_waypoints=2, engine=engine, extent=EXTENT)
+    spec = planner.spec
+    ref2 = grid_plan(spec, walls, None, start, goal, 2)
+    got = planner.plan(start, goal, want_occupancy=True, want_fields=True)
+    same(got, ref2)
+    assert np.any(got["status"] == R.TRUNCATED) and not got["fields_reused"]
+    grown = planner.plan(start, goal, grow=True)
+    full = grid_plan(spec, walls, None, start, goal, int(ref2["count"].max()))
+    same(grown, full, ("waypoints", "n_waypoints", "count", "status", "cost"))
+    assert grown["waypoints"].shape[1] == ref2["count"].max() > 2 and not np.any(grown["status"] == R.TRUNCATED)
+    # a replanning round: new starts, the same goals -> the resident fields, the path kernel alone
+    moved = start[::-1].copy()
+    again = planner.plan(moved, goal)
+    assert again["fields_reused"]
+    same(again, grid_plan(spec, walls, None, moved, goal, 2), ("waypoints", "n_waypoints", "count", "status", "cost"))
+    # another planner's call replaces the resident fields: this planner notices and computes again
+    other = GridPlanner(env, walls=walls, cells=64, inflate=INFLATE, max_waypoints=2, engine=engine, extent=EXTENT)
+    other.plan(start, goal)
+    stale = dict(planner._kept)
+    back = planner.plan(start, goal)
+    assert not back["fields_reused"]
+    same(back, ref2, ("waypoints", "n_waypoints", "count", "status", "cost"))
+    with pytest.raises(Exception, match="no longer resident"):
+        engine.plan_grid(spec, walls, None, start=start, goal=goal, max_waypoints=2, reuse=stale)
+
+
+def test_engine_refusals_are_named(engine):
+    from mobrob_amd import _lib
+    import ctypes as C
+    scene, start, goal = robots33()
+    walls = two_scenes(scene)
+    spec = GridSpec(EXTENT, 32, INFLATE)
+    with pytest.raises(ValueError, match="max_waypoints"):
+        engine.plan_grid(spec, walls, None, start=start, goal=goal, max_waypoints=0)
+    with pytest.raises(ValueError, match="finite"):
+        engine.plan_grid(spec, walls, None, start=np.where(np.arange(33)[:, None] == 2, np.inf, start), goal=goal)
+    with pytest.raises(ValueError, match="agree on the scene"):
+        engine.plan_grid(spec, walls, three_hazards((scene + 1) % 2), start=start, goal=goal)
+    # the C entry point's own checks, reached with a hand-made spec
+    ok = engine.plan_grid(spec, walls, None, start=start, goal=goal, max_waypoints=4)
+    i32 = C.POINTER(C.c_int32)
+
+    def call(**change):
+        sp = _lib.PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_scenes, sp.n_fields = 33, 2, 32, 4, 2, len(ok["field_goal_cell"])
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(spec.extent), float(spec.h), float(spec.inv_h), INFLATE
+        fof, fcell, fscene = ok["field_of"].copy(), ok["field_goal_cell"].copy(), ok["field_scene"].copy()
+        for k, v in change.items():
+            if k == "field_of":
+                fof[0] = v
+            elif k == "field_goal_cell":
+                fcell[0] = v
+            elif k == "field_scene":
+                fscene[0] = v
+            else:
+                setattr(sp, k, v)
+        wl = _lib.WallsC()
+        wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+        wl.boxes, wl.n_walls = walls.table.ctypes.data_as(C.POINTER(C.c_float)), walls.counts.ctypes.data_as(i32)
+        wl.scene, wl.radius, wl.cost, wl.indicator = walls.scene.ctypes.data_as(i32), walls.radius, walls.cost, 1
+        wp, out = np.zeros((33, 4, 2), np.float32), [np.zeros(33, np.int32) for _ in range(4)]
+        fp = C.POINTER(C.c_float)
+        return _lib.check(engine.lib.mobrob_ppo_plan_grid(
+            engine._h, C.byref(sp), C.byref(wl), None, start.ctypes.data_as(fp), goal.ctypes.data_as(fp), fof.ctypes.data_as(i32),
+            fcell.ctypes.data_as(i32), fscene.ctypes.data_as(i32), wp.ctypes.data_as(fp), *(o.ctypes.data_as(i32) for o in out), None, None,
+            None, None))
+    assert call() == 0
+    for change, word in ((dict(cells=48), "cells must be 32, 64 or 128"), (dict(max_waypoints=0), "max_waypoints"), (dict(pos_dim=1), "pos_dim"),
+                         (dict(n_scenes=3), "n_scenes"), (dict(inv_h=7.0), "h \\* inv_h"), (dict(inflate=-1.0), "inflate"),
+                         (dict(extent=float("nan")), "extent"), (dict(field_of=99), "field_of\\[0\\]"), (dict(field_of=-1), "field_of\\[0\\]"),
+                         (dict(field_scene=2), "field_scene\\[0\\]"), (dict(field_goal_cell=1024), "field_goal_cell\\[0\\]"),
+                         (dict(field_goal_cell=0), "goal of robot"), (dict(n_fields=0), "n_fields"), (dict(n_robots=0), "n_robots")):
+        with pytest.raises(ValueError, match=word):
+            call(**change)
+    same(engine.plan_grid(spec, walls, None, start=start, goal=goal, max_waypoints=4), ok, ("waypoints", "count", "status", "cost"))
+
+
+def test_training_untouched_by_plan_calls():
+    scene, start, goal = robots33()
+    walls = two_scenes(scene)
+    spec = GridSpec(EXTENT, 32, INFLATE)
+    env_a, env_b = _env("point", 16, tl=40), _env("point", 16, tl=40)
+    ea, _ = _engine("point", KW, seed=7)
+    eb, _ = _engine("point", KW, seed=7)
+    kept = None
+    for it in range(2):
+        env_a.collect(ea)
+        env_b.collect(eb)
+        before = _snapshot(eb, stats=False)
+        kept = eb.plan_grid(spec, walls, three_hazards(scene), start=start, goal=goal, max_waypoints=4, want_fields=True, reuse=None)
+        eb.plan_grid(spec, walls, three_hazards(scene), start=start[::-1].copy(), goal=goal, max_waypoints=4, reuse=kept)
+        sa, sb = _snapshot(ea, stats=False), _snapshot(eb, stats=False)
+        for k in sa:
+            assert np.array_equal(sa[k], sb[k]) and np.array_equal(before[k], sb[k]), f"iteration {it}: {k} differs"
+        ea.train()
+        eb.train()
+        assert np.array_equal(ea.get_flat_params(), eb.get_flat_params())
+    assert np.any(kept["status"] == R.PLANNED)
+    ea.close()
+    eb.close()
+
+
+def test_replanning_loop_end_to_end():
+    """plumbing only: the replanned rows are the plan of that round, the wall record is carried; no claim about tracking"""
+    e, _ = _engine("point", KW)
+    e.set_params(golden_params(load_golden("point")))
+    env = _env("point", 32)
+    rng = np.random.default_rng(3)
+    walls = Walls(SCENE0, radius=0.05)
+    start = rng.uniform(-1.4, 1.4, (32, 2)).astype(np.float32)
+    start[:, 0] = -np.abs(start[:, 0]) - 0.15                                    # left of the thin wall, goals right of it
+    goal = np.tile(np.array([[1.2, 1.2], [1.3, -0.2]], np.float32), (16, 1))
+    planner = GridPlanner(env, walls=walls, cells=32, inflate=INFLATE, max_waypoints=8, engine=e, extent=EXTENT)
+    first = planner.plan(start, goal)
+    same(first, grid_plan(planner.spec, walls, None, start, goal, 8), ("waypoints", "n_waypoints", "count", "status", "cost"))
+    inner, rounds = planner.callback(goal), []
+
+    def recording(positions, status, reached):
+        new = inner(positions, status, reached)
+        rounds.append((positions.copy(), status.copy(), new))
+        return new
+    out = follow_with_replanning(e, env, start, first["waypoints"], recording, horizon=20, rounds=3, leg_steps=7,
+                                 n_waypoints=first["n_waypoints"], seed=1, walls=walls)
+    assert len(rounds) == 2 and out["state"].step0 == 60 and out["round_status"].shape == (3, 32)
+    replanned = 0
+    for positions, status, new in rounds:
+        ref = grid_plan(planner.spec, walls, None, positions, goal, 8)
+        stalled = np.flatnonzero(status == STALLED)
+        assert sorted(new) == [i for i in stalled if ref["status"][i] == R.PLANNED]
+        for i, w in new.items():
+            assert w.view(np.uint32).tobytes() == ref["waypoints"][i, :ref["count"][i]].view(np.uint32).tobytes()
+        replanned += len(new)
+    assert replanned > 0, "a leg budget of 7 steps stalls robots: the loop must have replanned some"
+    positions, status, new = rounds[-1]
+    for i, w in new.items():                                                     # the rows in force after the last replanning
+        assert np.array_equal(out["state"].waypoints[i, :len(w)], w) and out["state"].n_waypoints[i] == len(w)
+    ran = first["n_waypoints"] > 0                                                # (a start in a blocked cell has no plan and runs no step)
+    assert ran.sum() >= 16 and out["state"].wall.shape == (32, 7) and np.all(out["steps"][ran] > 0)
+    assert not np.any(np.isnan(out["min_wall_clearance"][ran]))
+    assert np.array_equal(out["contact_steps"], out["state"].wall[:, 1].astype(np.int64))
+    e.close()
