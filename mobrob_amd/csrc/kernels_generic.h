@@ -13,9 +13,12 @@ namespace mobrob {
 // epilogue needs the stored activations only (no pre-activations are kept):
 //   tanh       1 - h^2                        relu        [h > 0]   (torch threshold_backward: 0 at z = 0)
 //   elu        h > 0 ? 1 : h + 1              leaky_relu  h > 0 ? 1 : 0.01   (torch: slope where z <= 0)
-//   sigmoid    h (1 - h)                      softplus    1 - exp(-h)        (= sigmoid(z); torch beta 1, linear above 20)
+//   sigmoid    h (1 - h)                      softplus    -expm1(-h)         (= sigmoid(z); torch beta 1, linear above 20)
 //   softsign   (1 - |h|)^2                    hardtanh    [-1 < h < 1]
 //   relu6      [0 < h < 6]
+// Softplus keeps its relative precision down the left tail through expm1 (1 - exp(-h) cancels: exactly 0 from z = -17 on).  ELU and
+// softsign cannot recover theirs from h alone: h + 1 and 1 - |h| round at 2^-24, so their derivative carries an ABSOLUTE error of up to
+// 2^-24 |g| where it is itself smaller than that (elu z < -17, softsign |z| > 4000) -- the floor torch's own tanh_backward has.
 // SiLU / GELU / Mish are not monotonic: their derivative needs the PRE-activation z.  The training forward leaves z in the layer's
 // dz buffer (GemmArgs.Z; the backward epilogue of that layer reads the element it is about to overwrite):
 //   silu  s (1 + z (1 - s)), s = sigmoid(z)      gelu  Phi(z) + z phi(z)  (torch's default, exact erf form)
@@ -59,7 +62,7 @@ __device__ __forceinline__ float act_bwd(int act, float h, float g) {
     case ACT_ELU: return h > 0.f ? g : g * (h + 1.0f);
     case ACT_LEAKY_RELU: return h > 0.f ? g : 0.01f * g;
     case ACT_SIGMOID: return g * (h * (1.0f - h));
-    case ACT_SOFTPLUS: return g * (1.0f - expf(-h));
+    case ACT_SOFTPLUS: return g * -expm1f(-h);
     case ACT_SOFTSIGN: { const float u = 1.0f - fabsf(h); return g * (u * u); }
     case ACT_HARDTANH: return (h > -1.f && h < 1.f) ? g : 0.f;
     default: return (h > 0.f && h < 6.f) ? g : 0.f;   // ACT_RELU6

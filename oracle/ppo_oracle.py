@@ -225,7 +225,7 @@ def _activation_grad_pre(z, g, activation):
 def _activation_grad(h, g, activation):
     """g * f'(z) with f'(z) written through the OUTPUT h = f(z) (all nine are monotonic) -- what torch's backward formulas give:
     tanh_backward g (1 - h^2); threshold_backward g [z > 0]; elu_backward g (z > 0 ? 1 : exp(z) = h + 1); leaky_relu_backward
-    g (z > 0 ? 1 : 0.01); sigmoid_backward g h (1 - h); softplus_backward g sigmoid(z) = g (1 - exp(-h)); softsign: autograd of
+    g (z > 0 ? 1 : 0.01); sigmoid_backward g h (1 - h); softplus_backward g sigmoid(z) = -g expm1(-h) (1 - exp(-h) cancels in the left tail); softsign: autograd of
     z / (1 + |z|) = g / (1 + |z|)^2 = g (1 - |h|)^2; hardtanh_backward g [-1 < z < 1]; relu6 = hardtanh(0, 6): g [0 < z < 6]."""
     h, g = np.asarray(h, F32), np.asarray(g, F32)
     one = F32(1.0)
@@ -240,7 +240,7 @@ def _activation_grad(h, g, activation):
     if activation == "sigmoid":
         return (g * (h * (one - h))).astype(F32)
     if activation == "softplus":
-        return (g * (one - np.exp(-h))).astype(F32)
+        return (g * -np.expm1(-h)).astype(F32)
     if activation == "softsign":
         u = one - np.abs(h)
         return (g * (u * u)).astype(F32)
