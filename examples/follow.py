@@ -41,7 +41,9 @@ report the contact rate, the crossing rate (robots with such a step) and the min
 cells a side over the arena, blocked where --walls / --arena / --hazards are (mobrob_amd.planning.GridPlanner), one path per robot
 from its start to the goal.  It excludes --waypoints.  A first line reports the rate of robots with a plan; the others count a
 robot without one as not successful.  With --horizon and --leg-steps a stalled robot is planned again from where it stands between
-the calls (the planner's callback).  Moving hazards are reported, not planned around.
+the calls (the planner's callback).  Moving hazards are reported, not planned around.  `--plan-smooth` smooths every plan by line
+of sight (fewer waypoints: only the cells a straight leg cannot skip), `--plan-los-margin` (0 or 1, default 1) is the clearance of
+that test in cells; a second line then reports the waypoints and the moves per planned robot.
 """
 import argparse
 import os
@@ -69,7 +71,8 @@ def check_chain(max_steps, horizon, leg_steps):
 
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
-           release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64):
+           release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
+           plan_smooth=False, plan_los_margin=1):
     calls = check_chain(max_steps, horizon, leg_steps)
     if (goal is None) == (waypoints is None):
         raise ValueError("give --waypoints or --goal, not both")
@@ -105,11 +108,15 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         if goal.shape != (p,) or p < 2:
             raise ValueError(f"--goal must hold {p} coordinates of a robot that moves in x and y, got {goal.size}")
         goals = np.tile(goal, (int(robots), 1))
-        planner = GridPlanner(env, walls=wl, hazards=hz if isinstance(hz, Hazards) else None, cells=int(plan_cells), engine=policy)
+        planner = GridPlanner(env, walls=wl, hazards=hz if isinstance(hz, Hazards) else None, cells=int(plan_cells), engine=policy,
+                              smooth=bool(plan_smooth), los_margin=int(plan_los_margin))
         plan = planner.plan(start, goals, grow=True)
         waypoints, n_waypoints = plan["waypoints"], plan["n_waypoints"]
         replan = planner.callback(goals) if int(leg_steps) > 0 else None
         print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
+        if plan["smoothed"] and np.any(plan["status"] == 0):
+            ok = plan["status"] == 0
+            print(f"smoothed plan: {float(np.mean(plan['count'][ok]))} waypoints for {float(np.mean(plan['moves'][ok]))} moves per planned robot")
     schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
     r = follow_waypoints(policy, env, start, waypoints, n_waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
                          leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
@@ -174,13 +181,15 @@ def report_teams(r):
     print(f"minimum team clearance: {float(np.nanmin(clear)) if np.any(~np.isnan(clear)) else float('nan')}")
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env-name", type=str, default="point")
     ap.add_argument("--policy-name", type=str, default="ppo")
     ap.add_argument("--waypoints", type=str, default=None, help="[K][P] or [n][K][P] positions (.npy)")
     ap.add_argument("--goal", type=str, default=None, help="x,y (x,y,z): plan the waypoints to this goal instead of --waypoints")
     ap.add_argument("--plan-cells", type=int, default=64, help="grid cells a side of the planner (32, 64, 128)")
+    ap.add_argument("--plan-smooth", action="store_true", default=False, help="smooth the planned paths by line of sight")
+    ap.add_argument("--plan-los-margin", type=int, default=1, choices=(0, 1), help="cells a smoothed leg keeps clear on either side")
     ap.add_argument("--robots", type=int, default=1)
     ap.add_argument("--max-steps", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
@@ -199,6 +208,11 @@ if __name__ == "__main__":
     ap.add_argument("--arena", action="store_true", default=False, help="add the reference's turtlebot3 enclosure to the walls")
     ap.add_argument("--robot-radius", type=float, default=0.1, help="the robot's footprint for wall contact")
     ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
+    return ap
+
+
+if __name__ == "__main__":
+    ap = build_parser()
     args = ap.parse_args()
     if (args.waypoints is None) == (args.goal is None):
         ap.error("give --waypoints or --goal, not both")
@@ -212,4 +226,5 @@ if __name__ == "__main__":
            frame_steps=args.frame_steps, hazard_loop=args.hazard_loop, team_size=args.team_size, separation=args.separation,
            release=None if args.release is None else np.load(args.release), stagger=args.stagger,
            walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius,
-           goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells)
+           goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells,
+           plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin)

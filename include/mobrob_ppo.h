@@ -815,6 +815,43 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
                          int32_t* field_out /* [F][G][G] or NULL */, int32_t* sweeps_out /* [F] or NULL */,
                          int64_t* fields_id_out /* or NULL */);
 
+/* ---- grid planner: line-of-sight smoothing of the paths, on resident fields ---------------------------------------------------------
+ * mobrob_ppo_plan_grid's waypoints are cell centres at every change of direction of an eight-connected walk: a staircase.  This call
+ * takes k_plan_path's place on the occupancy and the fields a mobrob_ppo_plan_grid call left resident (spec->reuse_id = its
+ * fields_id_out; cells, n_scenes, n_fields as then; 0 or a stale id: MOBROB_ERR_STATE) and keeps of the walk's cells c_0 .. c_L only
+ * those a straight leg cannot skip.  The rule, all integers, is stated once in mobrob_amd/envs/goal_rules.py (grid_los, grid_smooth,
+ * grid_path_smooth) and reproduced bit for bit:
+ *   visible   los(a, b): the supercover of the segment between the centres of cells a and b.  dx = |x1 - x0|, dy = |y1 - y0|, signs sx,
+ *             sy, counters ix = iy = 0; false if a is not clear; while ix < dx or iy < dy: t = (1 + 2 ix) dy - (1 + 2 iy) dx; t < 0
+ *             steps in x, t > 0 in y, t == 0 (exactly through a cell corner) needs both cells sharing the corner clear and steps in
+ *             both; false if the cell stepped into is not clear.  At most dx + dy steps, symmetric in a and b.
+ *   clear     margin 0: the cell is not blocked.  margin 1: no in-grid cell of its 3 x 3 neighbourhood is blocked.
+ *   smooth    anchor i = 0, j = 1; while j < L: if los(c_i, c_{j+1}) then j += 1, else emit j, i = j, j += 1.  Adjacent cells are never
+ *             tested.  Waypoints: the centres of the emitted cells, then the goal itself (z: the goal's).
+ *   clearance margin 0: every point of a leg between cell centres lies in a free cell, so it keeps inflate - h / sqrt 2 from walls and
+ *             hazards as the unsmoothed path does; the first leg starts at the true start, up to h / sqrt 2 off its cell's centre, and
+ *             is covered only to inflate - sqrt 2 h.  margin 1: every point within one cell of a leg of two or more moves lies in a free
+ *             cell, which restores inflate - h / sqrt 2 for the first leg.  At margin 0 count is never larger than
+ *             mobrob_ppo_plan_grid's; at margin 1 a walk along blocked cells has no clear cell to see from and keeps every cell.
+ *   inputs    start, goal, field_of as a reuse call of mobrob_ppo_plan_grid takes them, scene [n] the scene of every robot (NULL: scene
+ *             0, one scene only).  spec->inflate is not used.
+ *   outputs   waypoints_out, n_waypoints_out, count_out, status_out, cost_out as mobrob_ppo_plan_grid's (status 3: a loop ran into its
+ *             bound of cells * cells; count 0, waypoints zeroed, moves 0) and moves_out [n] = L, the moves of the walk (0: none made).
+ *   kernels   k_plan_smooth: one wave per robot; the walk (k_plan_path's own step) fills a ring of 128 packed cells in LDS, the 64 lanes
+ *             test 64 candidates against the anchor at once, a ballot and a count of trailing zeros find the first that is hidden.
+ *             k_plan_dilate: the cells that are not clear at margin 1, once per set of resident fields, kept beside them.  Runs on the
+ *             engine's stream in the planner's own buffers; nothing a training step reads or writes is touched.
+ * Still out of scope: moving hazards, team-mates as obstacles, walls as solid bodies of the simulation.
+ * MOBROB_ERR_INVALID before any launch or copy for: a NULL argument (scene aside), margin not 0 or 1, n_robots < 1, pos_dim not 2 or 3,
+ * cells not 32 / 64 / 128, max_waypoints < 1, n_fields outside 1 .. n_robots, n_scenes < 1, extent, h, inv_h not finite and > 0 or
+ * h * inv_h not 1 within 1e-5, cells / n_scenes / n_fields not the resident fields', a missing scene index with several scenes, a
+ * non-finite start or goal, scene or field_of out of range, a robot whose scene or goal cell is not its field's. */
+int mobrob_ppo_plan_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, int32_t margin /* 0 or 1 */,
+                           const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */,
+                           const int32_t* field_of /* [n] */, const int32_t* scene /* [n] or NULL */,
+                           float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */,
+                           int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */, int32_t* moves_out /* [n] */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

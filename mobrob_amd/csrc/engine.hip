@@ -280,6 +280,11 @@ struct mobrob_ppo_engine {
   int plan_G = 0, plan_S = 0, plan_F = 0;
   std::vector<int32_t> plan_field_scene, plan_field_goal;   // the resident fields' (scene, goal cell)
   bool plan_lds_set = false;          // k_plan_field's dynamic-LDS attribute is raised once
+  // line-of-sight smoothing (mobrob_ppo_plan_smooth): the cells that are not clear at margin 1 of the resident occupancy, computed
+  // by the first margin-1 call on the fields of id plan_dil_id
+  char* plan_dil = nullptr;
+  size_t plan_dil_bytes = 0;
+  int64_t plan_dil_id = 0;
 };
 
 namespace {
@@ -1353,6 +1358,7 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   if (e->eval_buf) (void)hipFree(e->eval_buf);
   if (e->plan_fields) (void)hipFree(e->plan_fields);
   if (e->plan_buf) (void)hipFree(e->plan_buf);
+  if (e->plan_dil) (void)hipFree(e->plan_dil);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3937,6 +3943,17 @@ static int grow_plan_buf(mobrob_ppo_engine_t* e, char*& buf, size_t& bytes, size
   return MOBROB_OK;
 }
 
+// the resident part of a plan: occupancy | field | field_goal | field_scene | sweeps
+struct PlanKeep {
+  size_t occ, field, fgoal, fscene, sweeps, total;
+  PlanKeep(int S, int F, int cells) {
+    EvalCarve keep;
+    occ = keep.add((size_t)S * cells); field = keep.add((size_t)F * cells * 4); fgoal = keep.add((size_t)F * 4);
+    fscene = keep.add((size_t)F * 4); sweeps = keep.add((size_t)F * 4);
+    total = keep.total;
+  }
+};
+
 int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
                          const float* start, const float* goal, const int32_t* field_of, const int32_t* field_goal_cell,
                          const int32_t* field_scene, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
@@ -4041,10 +4058,8 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
     if (field_lds > (size_t)limit)
       return fail(MOBROB_ERR_INVALID, "plan: k_plan_field needs %zu bytes of LDS at %d cells, the device allows %d per workgroup", field_lds, G, limit);
   }
-  // the resident part: occupancy | field | field_goal | field_scene | sweeps
-  EvalCarve keep;
-  const size_t o_occ = keep.add((size_t)S * cells), o_field = keep.add((size_t)F * cells * 4), o_fgoal = keep.add((size_t)F * 4),
-               o_fscene = keep.add((size_t)F * 4), o_sweeps = keep.add((size_t)F * 4);
+  const PlanKeep keep(S, F, cells);
+  const size_t o_occ = keep.occ, o_field = keep.field, o_fgoal = keep.fgoal, o_fscene = keep.fscene, o_sweeps = keep.sweeps;
   // the call's part
   EvalCarve call;
   const size_t o_start = call.add((size_t)N * P * 4), o_goal = call.add((size_t)N * P * 4), o_fof = call.add((size_t)N * 4),
@@ -4127,6 +4142,105 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
     e->plan_field_scene.assign(field_scene, field_scene + F);
   }
   if (fields_id_out) *fields_id_out = e->plan_id;
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_plan_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, int32_t margin, const float* start, const float* goal,
+                           const int32_t* field_of, const int32_t* scene, float* waypoints_out, int32_t* n_waypoints_out,
+                           int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* moves_out) {
+  if (!e || !spec || !start || !goal || !field_of || !waypoints_out || !n_waypoints_out || !count_out || !status_out || !cost_out ||
+      !moves_out)
+    return fail(MOBROB_ERR_INVALID, "plan_smooth: null argument");
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
+  if (margin != 0 && margin != 1) return fail(MOBROB_ERR_INVALID, "plan_smooth: margin must be 0 or 1, got %d", margin);
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "plan_smooth: n_robots must be >= 1");
+  if (P != 2 && P != 3) return fail(MOBROB_ERR_INVALID, "plan_smooth: pos_dim must be 2 or 3 (the grid is x and y)");
+  if (G != 32 && G != 64 && G != 128) return fail(MOBROB_ERR_INVALID, "plan_smooth: cells must be 32, 64 or 128, got %d", G);
+  if (K < 1) return fail(MOBROB_ERR_INVALID, "plan_smooth: max_waypoints must be >= 1");
+  if (F < 1 || F > N) return fail(MOBROB_ERR_INVALID, "plan_smooth: n_fields = %d outside 1 .. n_robots = %d", F, N);
+  if (S < 1) return fail(MOBROB_ERR_INVALID, "plan_smooth: n_scenes must be >= 1");
+  if (!(std::isfinite(spec->extent) && spec->extent > 0.f && std::isfinite(spec->h) && spec->h > 0.f && std::isfinite(spec->inv_h) &&
+        spec->inv_h > 0.f && std::fabs((double)spec->h * (double)spec->inv_h - 1.0) <= 1e-5))
+    return fail(MOBROB_ERR_INVALID, "plan_smooth: extent, h and inv_h must be finite and > 0 with h * inv_h = 1");
+  if ((int64_t)N * K * P > INT_MAX) return fail(MOBROB_ERR_INVALID, "plan_smooth: n_robots * max_waypoints * pos_dim must fit an int32");
+  if (spec->reuse_id == 0 || spec->reuse_id != e->plan_id)
+    return fail(MOBROB_ERR_STATE, "plan_smooth: the fields of id %lld are no longer resident (resident: %lld)", (long long)spec->reuse_id,
+                (long long)e->plan_id);
+  if (G != e->plan_G || S != e->plan_S || F != e->plan_F)
+    return fail(MOBROB_ERR_INVALID, "plan_smooth: cells, n_scenes, n_fields = %d, %d, %d are not the resident fields' %d, %d, %d", G, S, F,
+                e->plan_G, e->plan_S, e->plan_F);
+  if (!scene && S > 1) return fail(MOBROB_ERR_INVALID, "plan_smooth: %d scenes need a scene index per robot", S);
+  const int cells = G * G;
+  const auto cell_of = [&](float x) {   // plan_cell's arithmetic (kernels_plan.h); volatile: the sum is rounded to float before the product
+    volatile float sum = x + spec->extent;
+    volatile float c = sum * spec->inv_h;
+    return (int)std::fmin(std::fmax(std::floor((float)c), 0.f), (float)(G - 1));
+  };
+  for (int i = 0; i < N; ++i) {
+    for (int j = 0; j < P; ++j)
+      if (!std::isfinite(start[(size_t)i * P + j]) || !std::isfinite(goal[(size_t)i * P + j]))
+        return fail(MOBROB_ERR_INVALID, "plan_smooth: start or goal of robot %d is not finite", i);
+    const int sc = scene ? scene[i] : 0;
+    if (sc < 0 || sc >= S) return fail(MOBROB_ERR_INVALID, "plan_smooth: scene[%d] = %d outside 0 .. %d", i, sc, S - 1);
+    const int f = field_of[i];
+    if (f < 0 || f >= F) return fail(MOBROB_ERR_INVALID, "plan_smooth: field_of[%d] = %d outside 0 .. %d", i, f, F - 1);
+    if (e->plan_field_scene[f] != sc)
+      return fail(MOBROB_ERR_INVALID, "plan_smooth: robot %d is in scene %d, its field %d in scene %d", i, sc, f, e->plan_field_scene[f]);
+    const int gc = cell_of(goal[(size_t)i * P + 1]) * G + cell_of(goal[(size_t)i * P]);
+    if (gc != e->plan_field_goal[f])
+      return fail(MOBROB_ERR_INVALID, "plan_smooth: the goal of robot %d lies in cell %d, its field %d has goal cell %d", i, gc, f,
+                  e->plan_field_goal[f]);
+  }
+  const PlanKeep keep(S, F, cells);
+  EvalCarve call;
+  const size_t o_start = call.add((size_t)N * P * 4), o_goal = call.add((size_t)N * P * 4), o_fof = call.add((size_t)N * 4),
+               o_wp = call.add((size_t)N * K * P * 4), o_nwp = call.add((size_t)N * 4), o_count = call.add((size_t)N * 4),
+               o_status = call.add((size_t)N * 4), o_cost = call.add((size_t)N * 4), o_moves = call.add((size_t)N * 4);
+  if (const int rc = grow_plan_buf(e, e->plan_buf, e->plan_bytes, call.total)) return rc;
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(e->plan_fields + keep.occ);
+  const unsigned char* blk_dev = occ_dev;
+  if (margin == 1) {
+    if (e->plan_dil_id != e->plan_id) {   // once per set of resident fields
+      e->plan_dil_id = 0;
+      if (const int rc = grow_plan_buf(e, e->plan_dil, e->plan_dil_bytes, (size_t)S * cells)) return rc;
+      const PlanDilateArgs da{G, occ_dev, reinterpret_cast<unsigned char*>(e->plan_dil)};
+      hipLaunchKernelGGL(k_plan_dilate, dim3(cdiv(cells, 256), S), dim3(256), 0, e->stream, da);
+      HIPC(hipGetLastError());
+      e->plan_dil_id = e->plan_id;
+    }
+    blk_dev = reinterpret_cast<const unsigned char*>(e->plan_dil);
+  }
+  const auto mine = [&](size_t off) { return e->plan_buf + off; };
+  PlanSmoothArgs sa{};
+  PlanPathArgs& pa = sa.p;
+  pa.g = PlanGrid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  pa.N = N; pa.K = K; pa.P = P;
+  float* start_dev = reinterpret_cast<float*>(mine(o_start));
+  float* goal_dev = reinterpret_cast<float*>(mine(o_goal));
+  int* fof_dev = reinterpret_cast<int*>(mine(o_fof));
+  pa.start = start_dev; pa.goal = goal_dev; pa.field_of = fof_dev;
+  pa.field_scene = reinterpret_cast<int*>(e->plan_fields + keep.fscene);
+  pa.sweeps = reinterpret_cast<int*>(e->plan_fields + keep.sweeps);
+  pa.occ = occ_dev;
+  pa.field = reinterpret_cast<int*>(e->plan_fields + keep.field);
+  pa.wp = reinterpret_cast<float*>(mine(o_wp));
+  pa.nwp = reinterpret_cast<int*>(mine(o_nwp)); pa.count = reinterpret_cast<int*>(mine(o_count));
+  pa.status = reinterpret_cast<int*>(mine(o_status)); pa.cost = reinterpret_cast<int*>(mine(o_cost));
+  sa.blk = blk_dev;
+  sa.moves = reinterpret_cast<int*>(mine(o_moves));
+  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(goal_dev, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(fof_dev, field_of, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
+  hipLaunchKernelGGL(k_plan_smooth, dim3(N), dim3(64), 0, e->stream, sa);   // a wave per robot
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(moves_out, sa.moves, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
 }
 

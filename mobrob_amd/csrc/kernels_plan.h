@@ -14,6 +14,7 @@
 // Three kernels: k_plan_occupancy (a thread per scene and cell), k_plan_field (a workgroup per distinct (scene, goal cell), the
 // field in LDS, sweeps of in-place relaxations until a workgroup-wide "nothing changed", at most G * G of them), k_plan_path (a
 // thread per robot, at most G * G steps).  A loop that runs into its bound reports status 3; nothing here can spin.
+// Line-of-sight smoothing of the path (k_plan_dilate, k_plan_smooth, in k_plan_path's place on resident fields): further down.
 #pragma once
 #include "kernels_wall.h"
 
@@ -224,6 +225,172 @@ __global__ __launch_bounds__(256) void k_plan_path(PlanPathArgs a) {
   a.count[n] = count;
   a.status[n] = status;
   a.cost[n] = cost;
+}
+
+// the move the walk of goal_rules.grid_walk makes from the free cell (ix, iy) of the field d: to a neighbour with d[nb] + w == d[c],
+// the previous direction first, else the lowest index; -1: none (d is not the cost-to-go of occ).  k_plan_path's own step, line for
+// line; that kernel keeps its copy in place because calling this from it reordered instructions of its compiled loop, and existing
+// kernels stay as they are.
+__device__ __forceinline__ int plan_walk_dir(const unsigned char* occ, const int* d, int G, int ix, int iy, int prev) {
+  const unsigned m = plan_moves(occ, G, ix, iy);
+  const int dc = d[iy * G + ix];
+  int dir = -1;
+  for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
+    if (!(m & (1u << k))) continue;
+    const int dn = d[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
+    if (dn >= 0 && dn + (k < 4 ? 5 : 7) == dc) dir = k;
+  }
+  if (prev >= 0 && (m & (1u << prev))) {   // the previous direction first
+    const int dn = d[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
+    if (dn >= 0 && dn + (prev < 4 ? 5 : 7) == dc) dir = prev;
+  }
+  return dir;
+}
+
+// ---- line-of-sight smoothing (mobrob_ppo_plan_smooth; the rule: goal_rules.grid_los / grid_smooth / grid_path_smooth) ----------
+// "clear" at margin 1: no in-grid cell of the 3 x 3 neighbourhood blocked.  k_plan_dilate writes the cells that are NOT clear
+// once per set of resident fields; at margin 0 the occupancy itself is that map.
+struct PlanDilateArgs {
+  int G;
+  const unsigned char* occ;   // [S][G][G]
+  unsigned char* dil;         // [S][G][G] out
+};
+
+// grid (cdiv(G * G, 256), S), 256 threads
+__global__ __launch_bounds__(256) void k_plan_dilate(PlanDilateArgs a) {
+  const int G = a.G, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= G * G) return;
+  const unsigned char* occ = a.occ + (size_t)blockIdx.y * G * G;
+  const int ix = c % G, iy = c / G;
+  unsigned char any = 0;
+  for (int y = max(iy - 1, 0); y <= min(iy + 1, G - 1); ++y)
+    for (int x = max(ix - 1, 0); x <= min(ix + 1, G - 1); ++x) any |= occ[y * G + x];
+  a.dil[(size_t)blockIdx.y * G * G + c] = any ? 1 : 0;
+}
+
+// goal_rules.grid_los on the map blk of cells that are not clear: the supercover of the segment between the centres of (x, y) and
+// (x1, y1), both in the grid (every cell visited lies in their bounding box).  At most dx + dy <= 2 G - 2 steps; the loop is
+// bounded by 2 G on its own.
+__device__ __forceinline__ bool plan_los(const unsigned char* blk, int G, int x, int y, int x1, int y1) {
+  if (blk[y * G + x]) return false;
+  const int dx = abs(x1 - x), dy = abs(y1 - y), sx = x1 > x ? 1 : -1, sy = y1 > y ? 1 : -1;
+  int ix = 0, iy = 0;
+  for (int it = 0; it < 2 * G && (ix < dx || iy < dy); ++it) {
+    const int t = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx;
+    if (t < 0) {
+      x += sx; ++ix;
+    } else if (t > 0) {
+      y += sy; ++iy;
+    } else {   // exactly through a cell corner: both cells that share it must be clear (plan_moves' no corner cutting)
+      if (blk[y * G + x + sx] || blk[(y + sy) * G + x]) return false;
+      x += sx; y += sy; ++ix; ++iy;
+    }
+    if (blk[y * G + x]) return false;
+  }
+  return ix == dx && iy == dy;
+}
+
+constexpr int kPlanRing = 128;   // cells of the walk kept per wave: the window of 64 candidates and the cell before it fit twice
+
+struct PlanSmoothArgs {
+  PlanPathArgs p;             // k_plan_path's own inputs and outputs
+  const unsigned char* blk;   // [S][G][G] cells that are not clear: occ (margin 0) or k_plan_dilate's map (margin 1)
+  int* moves;                 // [N] out: moves of the walk, 0 where none was made
+};
+
+// One wave per robot (grid N, 64 threads: the workgroup IS the wave, so nothing here waits for another wave and the trip counts of
+// different robots never meet).  The walk is k_plan_path's (plan_walk_dir), wave-uniform -- the robot is blockIdx.x, so its state
+// lives in scalar registers -- and lane 0 stores its cells, packed iy * 128 + ix, in a ring of kPlanRing entries in LDS (256 B).  With
+// the anchor c_i and the first untested index `base` (= i + 2: the adjacent cell is never tested), lane l tests
+// plan_los(c_i, c_{base + l}); the first lane that fails, z = ctz(ballot), is the rule's "first cell that is not visible": the cell
+// before it is emitted and becomes the anchor, base = base + z + 2.  No failure: base += 64, same anchor.  The walk runs ahead of
+// base by at most 64 cells; the ring holds indices base - 1 .. base + 63 at any time.  Bounds: the walk G * G moves (k_plan_path's),
+// the window loop G * G rounds (base grows by at least 1 a round and ends beyond L <= G * G), plan_los 2 G steps: status 3.
+__global__ __launch_bounds__(64) void k_plan_smooth(PlanSmoothArgs s) {
+  __shared__ unsigned short ring[kPlanRing];
+  const PlanPathArgs& a = s.p;
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int G = a.g.G, cells = G * G, P = a.P, K = a.K;
+  const int f = a.field_of[n];
+  const size_t scene_off = (size_t)a.field_scene[f] * cells;
+  const unsigned char* occ = a.occ + scene_off;
+  const unsigned char* blk = s.blk + scene_off;
+  const int* d = a.field + (size_t)f * cells;
+  const float* st = a.start + (size_t)n * P;
+  const float* gl = a.goal + (size_t)n * P;
+  float* wp = a.wp + (size_t)n * K * P;
+  int wx = plan_cell(a.g, st[0]), wy = plan_cell(a.g, st[1]);   // the walker
+  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
+  int count = 0, status = kPlanned, cost = -1, walked = 1;     // walked: cells c_0 .. c_{walked - 1} are known
+  if (a.sweeps[f] < 0) {
+    status = kPlanUnconverged;
+  } else if (occ[wy * G + wx] || occ[gy * G + gx] || d[wy * G + wx] < 0) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d[wy * G + wx];
+    int ax = wx, ay = wy, base = 2, prev = -1;
+    bool done = wx == gx && wy == gy;
+    if (lane == 0) ring[0] = (unsigned short)(wy * 128 + wx);
+    for (int round = 0;; ++round) {
+      if (round > cells) { status = kPlanUnconverged; break; }
+      while (!done && walked <= base + 63) {   // the walk, up to the end of the window
+        if (walked > cells) { status = kPlanUnconverged; break; }
+        const int dir = plan_walk_dir(occ, d, G, wx, wy, prev);
+        if (dir < 0) { status = kPlanUnconverged; break; }
+        wx += plan_dx(dir); wy += plan_dy(dir);
+        prev = dir;
+        if (lane == 0) ring[walked & (kPlanRing - 1)] = (unsigned short)(wy * 128 + wx);
+        ++walked;
+        done = wx == gx && wy == gy;
+      }
+      if (status != kPlanned) break;
+      if (done && base >= walked) break;   // no candidate left: L = walked - 1
+      // lane 0's stores to the ring before every lane's loads from it: one wave, so a wave-level fence and no barrier
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const int idx = base + lane;
+      bool hidden = false;
+      if (idx < walked) {
+        const int c = ring[idx & (kPlanRing - 1)];
+        hidden = !plan_los(blk, G, ax, ay, c & 127, c >> 7);
+      }
+      const unsigned long long fails = __ballot(hidden);
+      if (fails == 0) { base += 64; continue; }
+      const int j = base + __builtin_ctzll(fails) - 1;   // the last visible cell: emitted, the next anchor
+      const int c = __builtin_amdgcn_readfirstlane((int)ring[j & (kPlanRing - 1)]);
+      ax = c & 127; ay = c >> 7;
+      if (count < K && lane == 0) {
+        wp[count * P] = plan_centre(a.g, ax);
+        wp[count * P + 1] = plan_centre(a.g, ay);
+        if (P == 3) wp[count * P + 2] = gl[2];
+      }
+      ++count;
+      base = j + 2;
+      // the loads above before the walk's next stores to the ring
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (status == kPlanned) {
+      if (count < K && lane == 0)
+        for (int q = 0; q < P; ++q) wp[count * P + q] = gl[q];
+      ++count;
+      if (count > K) status = kPlanTruncated;
+    }
+  }
+  if (lane != 0) return;
+  int moves = walked - 1;
+  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
+    for (int q = 0; q < min(count, K) * P; ++q) wp[q] = 0.f;
+    count = 0;
+    cost = -1;
+    moves = 0;
+  }
+  a.nwp[n] = min(count, K);
+  a.count[n] = count;
+  a.status[n] = status;
+  a.cost[n] = cost;
+  s.moves[n] = moves;
 }
 
 }  // namespace mobrob

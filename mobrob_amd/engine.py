@@ -692,12 +692,56 @@ class PPOEngine:
             None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), None if fields is None else fields.ctypes.data_as(i32),
             None if sweeps is None else sweeps.ctypes.data_as(i32), C.byref(fid)))
         out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "field_of": field_of,
-               "field_goal_cell": fcell, "field_scene": fscene, "sweeps": sweeps, "fields_id": int(fid.value)}
+               "field_goal_cell": fcell, "field_scene": fscene, "sweeps": sweeps, "fields_id": int(fid.value), "n_scenes": int(S)}
         if occ is not None:
             out["occupancy"] = occ.astype(bool)
         if fields is not None:
             out["fields"] = fields
         return out
+
+    def plan_smooth(self, spec, *, reuse, start, goal, scene=None, max_waypoints=16, margin=1):
+        """Line-of-sight smoothed waypoints on the fields a plan_grid call left on the device (mobrob_ppo_plan_smooth; the rule:
+        goal_rules.grid_los / grid_smooth / grid_path_smooth, reproduced bit for bit).  reuse: the dict that plan_grid call
+        returned (the same scenes and goal cells: ValueError otherwise; fields no longer resident: EngineError); scene [n] or
+        None: the scene index per robot (the walls' / hazards' own); margin: 0 or 1, the clearance of the line-of-sight test in
+        cells.  Returns waypoints [n][K][P] float32, n_waypoints, count, status, cost as plan_grid does, moves [n] int32 (the
+        moves of each walk) and field_of, field_goal_cell, field_scene, fields_id."""
+        from ._lib import PlanSpec
+        from .envs.goal_rules import GridSpec, plan_fields
+        if not isinstance(spec, GridSpec):
+            raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.GridSpec, not {type(spec).__name__}")
+        start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
+        if goal.ndim != 2 or goal.shape[0] < 1 or goal.shape[1] not in (2, 3) or start.shape != goal.shape:
+            raise ValueError(f"plan_smooth: start and goal must both be [n_robots, 2 or 3], got shapes {start.shape} and {goal.shape}")
+        if not (np.all(np.isfinite(start)) and np.all(np.isfinite(goal))):
+            raise ValueError("plan_smooth: start and goal must be finite")
+        n, P = goal.shape
+        K = int(max_waypoints)
+        if K < 1:
+            raise ValueError("plan_smooth: max_waypoints must be >= 1")
+        if scene is not None:
+            scene = np.ascontiguousarray(scene, np.int32)
+            if scene.shape != (n,):
+                raise ValueError(f"plan_smooth: scene must be [n_robots = {n}], got shape {scene.shape}")
+        start, goal = np.ascontiguousarray(start, F32), np.ascontiguousarray(goal, F32)
+        field_of, fcell, fscene = plan_fields(spec, None, scene, goal)
+        if not (np.array_equal(reuse["field_goal_cell"], fcell) and np.array_equal(reuse["field_scene"], fscene)):
+            raise ValueError("plan_smooth: the goal cells or scenes are not those of the resident fields")
+        i32 = C.POINTER(C.c_int32)
+        sp = PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_fields = n, P, spec.cells, K, len(fcell)
+        sp.n_scenes = int(reuse.get("n_scenes", int(fscene.max()) + 1))
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(spec.extent), float(spec.h), float(spec.inv_h), 0.0
+        sp.reuse_id = int(reuse["fields_id"])
+        wp = np.zeros((n, K, P), F32)
+        nwp, count, status, cost, moves = (np.zeros(n, np.int32) for _ in range(5))
+        check(self.lib.mobrob_ppo_plan_smooth(
+            self._h, C.byref(sp), int(margin), _fp(start), _fp(goal), field_of.ctypes.data_as(i32),
+            None if scene is None else scene.ctypes.data_as(i32), _fp(wp), nwp.ctypes.data_as(i32), count.ctypes.data_as(i32),
+            status.ctypes.data_as(i32), cost.ctypes.data_as(i32), moves.ctypes.data_as(i32)))
+        return {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "moves": moves,
+                "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene, "fields_id": int(reuse["fields_id"]),
+                "n_scenes": int(sp.n_scenes)}
 
     def episode_stats(self, reset=True):
         """Episodes finished by the goal environment since the counters were last reset."""

@@ -828,10 +828,104 @@ def plan_fields(spec, occupancy, scene, goal):
     return inv.reshape(n).astype(np.int32), (uniq % (G * G)).astype(np.int32), (uniq // (G * G)).astype(np.int32)
 
 
-def grid_plan(spec, walls, hazards, start, goal, K, occupancy=None, fields=None):
+def grid_dilate(occ_scene):
+    """bool [G][G]: a cell is True when a cell of its 3 x 3 neighbourhood that lies in the grid is blocked (cells outside the grid
+    count as free): the cells that are not "clear" at margin 1."""
+    occ = np.asarray(occ_scene, bool)
+    G = occ.shape[0]
+    pad = np.zeros((G + 2, G + 2), bool)
+    pad[1:-1, 1:-1] = occ
+    out = np.zeros((G, G), bool)
+    for dy in range(3):
+        for dx in range(3):
+            out |= pad[dy:dy + G, dx:dx + G]
+    return out
+
+
+def los_blocked(occ_scene, margin):
+    """The map grid_los tests a cell against: the occupancy itself at margin 0, grid_dilate of it at margin 1."""
+    if isinstance(margin, bool) or margin not in (0, 1):
+        raise ValueError(f"line-of-sight margin must be 0 or 1, got {margin!r}")
+    return np.asarray(occ_scene, bool) if margin == 0 else grid_dilate(occ_scene)
+
+
+def los_walk(blk, a, b):
+    """grid_los on the map `blk` of cells that are not clear -> (visible, steps taken, corners met)."""
+    (x, y), (x1, y1) = (int(a[0]), int(a[1])), (int(b[0]), int(b[1]))
+    dx, dy = abs(x1 - x), abs(y1 - y)
+    sx, sy = (1 if x1 > x else -1), (1 if y1 > y else -1)
+    ix = iy = steps = corners = 0
+    if blk[y, x]:
+        return False, 0, 0
+    while ix < dx or iy < dy:
+        t = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx
+        steps += 1
+        if t < 0:
+            x, ix = x + sx, ix + 1
+        elif t > 0:
+            y, iy = y + sy, iy + 1
+        else:                                   # exactly through a cell corner: no corner cutting, as plan_move_ok
+            corners += 1
+            if blk[y, x + sx] or blk[y + sy, x]:
+                return False, steps, corners
+            x, y, ix, iy = x + sx, y + sy, ix + 1, iy + 1
+        if blk[y, x]:
+            return False, steps, corners
+    return True, steps, corners
+
+
+def grid_los(occ, a, b, margin=0):
+    """Is cell b = (x1, y1) visible from cell a = (x0, y0) on occ [G][G]?  Integers only: the supercover of the segment between the
+    two centres.  With dx = |x1 - x0|, dy = |y1 - y0|, signs sx, sy and counters ix = iy = 0: false if a is not clear; while ix < dx
+    or iy < dy, t = (1 + 2 ix) dy - (1 + 2 iy) dx; t < 0 steps in x, t > 0 steps in y, t == 0 (the segment passes exactly through a
+    cell corner) needs both cells that share the corner, (x + sx, y) and (x, y + sy), clear and then steps in both; false if the
+    cell stepped into is not clear.  At most dx + dy steps; symmetric in a and b.  A cell is clear at margin 0 when it is not
+    blocked, at margin 1 when no in-grid cell of its 3 x 3 neighbourhood is blocked."""
+    return los_walk(los_blocked(occ, margin), a, b)[0]
+
+
+def grid_smooth(cells, occ, margin=1, blocked=None):
+    """Line-of-sight smoothing of grid_walk's cells c_0 .. c_L -> the ascending indices of the cells kept as waypoints.  Anchor
+    i = 0, j = 1; while j < L: if grid_los(occ, c_i, c_{j+1}, margin) then j += 1, else emit j, i = j, j += 1.  Adjacent cells are
+    never tested (they are a move of the walk), so every margin makes progress.  blocked: los_blocked(occ, margin), computed
+    once by a caller with many walks."""
+    blk = los_blocked(occ, margin) if blocked is None else blocked
+    L, out, i, j = len(cells) - 1, [], 0, 1
+    while j < L:
+        if not los_walk(blk, cells[i], cells[j + 1])[0]:
+            out.append(j)
+            i = j
+        j += 1
+    return out
+
+
+def grid_path_smooth(field, occ_scene, spec, start_xy, goal_xy, K, margin=1, blocked=None):
+    """grid_path with line-of-sight smoothing -> (waypoints [K][2] float32, count, status, cost, moves): the waypoints are the
+    centres of the cells grid_smooth keeps of the walk, then goal_xy itself; count, status, cost and the zeroed slots mean what
+    they mean in grid_path; moves = L, the moves of the walk (0 where none was made)."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("max_waypoints must be >= 1")
+    wp = np.zeros((K, 2), np.float32)
+    cells, _, status = grid_walk(field, occ_scene, spec, start_xy, goal_xy)
+    if status == UNREACHABLE:
+        return wp, 0, UNREACHABLE, -1, 0
+    keep = grid_smooth(cells, occ_scene, margin, blocked)
+    for count, j in enumerate(keep[:K]):
+        wp[count] = spec.centre(cells[j][0]), spec.centre(cells[j][1])
+    count = len(keep)
+    if count < K:
+        wp[count] = np.asarray(goal_xy, np.float32)[:2]
+    count += 1
+    sx, sy = cells[0]
+    return wp, count, TRUNCATED if count > K else PLANNED, int(np.asarray(field)[sy, sx]), len(cells) - 1
+
+
+def grid_plan(spec, walls, hazards, start, goal, K, occupancy=None, fields=None, smooth=False, margin=1):
     """The whole plan of n robots by the rule: start, goal [n][P] (P = 2 or 3) -> dict of waypoints [n][K][P] float32 (z of every
     waypoint: the goal's), n_waypoints, count, status, cost [n] int32, occupancy bool [S][G][G], fields int32 [F][G][G], field_of,
-    field_goal_cell, field_scene.  `occupancy` / `fields`: a previous call's, reused (the same scene and goals)."""
+    field_goal_cell, field_scene.  `occupancy` / `fields`: a previous call's, reused (the same scene and goals).  smooth: the
+    paths by grid_path_smooth with the line-of-sight `margin` (0 or 1), and `moves` [n] int32 beside them."""
     start, goal = np.asarray(start, np.float32), np.asarray(goal, np.float32)
     n, P = goal.shape
     _, scene = plan_scene(walls, hazards)
@@ -840,11 +934,20 @@ def grid_plan(spec, walls, hazards, start, goal, K, occupancy=None, fields=None)
     if fields is None:
         fields = np.stack([grid_field(occ[fscene[f]], fcell[f]) for f in range(len(fcell))])
     wp, count, status, cost = np.zeros((n, K, P), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    moves = np.zeros(n, np.int32)
+    blocked = [los_blocked(occ[s], margin) for s in range(len(occ))] if smooth else None
     for i in range(n):
         f = field_of[i]
-        w, count[i], status[i], cost[i] = grid_path(fields[f], occ[fscene[f]], spec, start[i], goal[i], K)
+        if smooth:
+            w, count[i], status[i], cost[i], moves[i] = grid_path_smooth(fields[f], occ[fscene[f]], spec, start[i], goal[i], K, margin,
+                                                                         blocked[fscene[f]])
+        else:
+            w, count[i], status[i], cost[i] = grid_path(fields[f], occ[fscene[f]], spec, start[i], goal[i], K)
         m = min(int(count[i]), K)
         wp[i, :m, :2] = w[:m]
         wp[i, :m, 2:] = goal[i, 2:]
-    return {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
-            "occupancy": occ, "fields": fields, "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene}
+    out = {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
+           "occupancy": occ, "fields": fields, "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene}
+    if smooth:
+        out["moves"] = moves
+    return out

@@ -9,7 +9,9 @@ The rule -- grid, blocked cells, cost-to-go field, path, waypoints -- is stated 
 grid_field, grid_path).  Two paths, one meaning, bit for bit:
   * device: `env` is a `DeviceGoalVecEnv` and `engine` a PPOEngine (or a PPO that has one): mobrob_ppo_plan_grid, three kernels.
   * host: `env` is an `EnvWrapper` or an env name: the NumPy rule itself (as `_host_follow` serves following).
-Static scenes only: moving hazards, team-mates and any-angle smoothing are not planned for."""
+Line-of-sight smoothing (`smooth=True`): of the walk's cells only those a straight leg cannot skip become waypoints
+(goal_rules.grid_los, grid_smooth; device: mobrob_ppo_plan_smooth on the resident fields, k_plan_smooth in k_plan_path's place).
+Static scenes only: moving hazards, team-mates and walls as solid bodies are not planned for."""
 from __future__ import annotations
 
 import numpy as np
@@ -21,14 +23,21 @@ class GridPlanner:
     """A planner over one scene.  env: a DeviceGoalVecEnv (device path; `engine`: the PPOEngine or PPO to run on), or an env name
     / EnvWrapper (host path, the NumPy rule).  walls / hazards: goal_rules.Walls / Hazards or None; cells: 32, 64 or 128 per side
     over the env's [-extent, extent]^2; inflate: clearance of a blocked cell's centre (None: the walls' radius + one cell);
-    max_waypoints: the K slots of a plan."""
+    max_waypoints: the K slots of a plan.  smooth: line-of-sight smoothing of every plan (plan(..., smooth=) overrides it per
+    call); los_margin: 0 or 1, the cells a smoothed leg keeps clear on either side (1: a leg of two or more moves is as far from
+    walls as the unsmoothed path, also on the first leg from an off-centre start; but a walk ALONG blocked cells has no clear
+    cell to see from and keeps every cell as a waypoint -- in cluttered scenes or with a small inflate use 0)."""
 
-    def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None):
+    def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
+                 smooth=False, los_margin=1):
         from .envs.vec_env import DeviceGoalVecEnv
         rules.plan_scene(walls, hazards)
         self.walls, self.hazards, self.K = walls, hazards, int(max_waypoints)
         if self.K < 1:
             raise ValueError("max_waypoints must be >= 1")
+        if isinstance(los_margin, bool) or los_margin not in (0, 1):
+            raise ValueError(f"los_margin must be 0 or 1, got {los_margin!r}")
+        self.smooth, self.los_margin = bool(smooth), int(los_margin)
         self.device = isinstance(env, DeviceGoalVecEnv)
         if self.device:
             self.engine = getattr(engine, "engine", engine)
@@ -65,40 +74,54 @@ class GridPlanner:
                 sc.check_robots(goal.shape[0])
         return start.astype(np.float32), goal.astype(np.float32)
 
-    def _plan(self, start, goal, K, want_occupancy, want_fields):
-        """One call.  The fields of the previous call are reused when this call's (scene, goal cell) list is the same."""
+    def _plan(self, start, goal, K, want_occupancy, want_fields, smooth=False):
+        """One call.  The fields of the previous call are reused when this call's (scene, goal cell) list is the same.  smooth:
+        the paths by line of sight -- on the device a first plan computes the fields with plan_grid and smooths on them, a round
+        on unchanged goals runs k_plan_smooth alone."""
         _, scene = rules.plan_scene(self.walls, self.hazards)
         _, fcell, fscene = rules.plan_fields(self.spec, None, scene, goal)
         kept = self._kept
         same = kept is not None and np.array_equal(kept["field_goal_cell"], fcell) and np.array_equal(kept["field_scene"], fscene)
         if self.device:
             reuse = kept if same and not (want_occupancy or want_fields) and kept["fields_id"] == getattr(self.engine, "_plan_resident", None) else None
-            out = self.engine.plan_grid(self.spec, self.walls, self.hazards, start=start, goal=goal, max_waypoints=K,
-                                        want_occupancy=want_occupancy, want_fields=want_fields, reuse=reuse)
-            self.engine._plan_resident = out["fields_id"]
+            if smooth and reuse is not None:
+                out = dict(kept)
+            else:
+                out = self.engine.plan_grid(self.spec, self.walls, self.hazards, start=start, goal=goal, max_waypoints=K,
+                                            want_occupancy=want_occupancy, want_fields=want_fields, reuse=reuse)
+                self.engine._plan_resident = out["fields_id"]
+                if reuse is not None:
+                    out["sweeps"] = kept["sweeps"]
+            if smooth:
+                out.update(self.engine.plan_smooth(self.spec, reuse=out, start=start, goal=goal, scene=scene, max_waypoints=K,
+                                                   margin=self.los_margin))
             out["fields_reused"] = reuse is not None
-            if reuse is not None:
-                out["sweeps"] = kept["sweeps"]
         else:
             out = rules.grid_plan(self.spec, self.walls, self.hazards, start, goal, K, kept["occupancy"] if same else None,
-                                  kept["fields"] if same else None)
+                                  kept["fields"] if same else None, smooth=smooth, margin=self.los_margin)
             out["fields_reused"] = bool(same)
+        if not smooth:
+            out.pop("moves", None)
         self._kept = out
         return out
 
-    def plan(self, start, goal, *, grow=False, want_occupancy=False, want_fields=False):
+    def plan(self, start, goal, *, grow=False, want_occupancy=False, want_fields=False, smooth=None):
         """start, goal [n][P] -> dict: waypoints [n][K][P] float32 (z: the goal's), n_waypoints [n] (= min(count, K)), count [n]
         waypoints of the full path, status [n] (goal_rules.PLANNED 0, UNREACHABLE 1, TRUNCATED 2; UNCONVERGED 3: a device loop hit
         its bound), cost [n] int32 (-1: unreachable), cost_distance [n] float64 = cost * h / 5 (NaN: unreachable), field_of [n],
         field_goal_cell [F], field_scene [F]; with want_occupancy / want_fields also occupancy bool [S][G][G] / fields int32
-        [F][G][G].  grow: when a robot's path was truncated, plan again with K = count.max() (this call only)."""
+        [F][G][G].  grow: when a robot's path was truncated, plan again with K = count.max() (this call only).  smooth: None (the
+        planner's setting), True or False: line-of-sight smoothing with the planner's los_margin; `smoothed` tells which, `moves`
+        [n] int32 is the number of moves of each robot's walk (None on an unsmoothed plan); `grow` then uses the smoothed count."""
         start, goal = self._check(start, goal)
-        out = self._plan(start, goal, self.K, want_occupancy, want_fields)
+        smooth = self.smooth if smooth is None else bool(smooth)
+        out = self._plan(start, goal, self.K, want_occupancy, want_fields, smooth)
         if grow and np.any(out["status"] == rules.TRUNCATED):
-            out = self._plan(start, goal, int(out["count"].max()), want_occupancy, want_fields)
+            out = self._plan(start, goal, int(out["count"].max()), want_occupancy, want_fields, smooth)
         res = {k: out[k] for k in ("waypoints", "n_waypoints", "count", "status", "cost", "field_of", "field_goal_cell", "field_scene",
                                    "fields_reused")}
         res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
+        res["smoothed"], res["moves"] = smooth, out.get("moves")
         if want_occupancy:
             res["occupancy"] = out["occupancy"]
         if want_fields:
@@ -111,7 +134,8 @@ class GridPlanner:
         """The `planner(positions, status, reached)` of waypoints.follow_with_replanning for the goals `goal` [n][P]: every
         STALLED robot is planned again from where it stands -- all robots in one call, so the fields of the unchanged goals are
         reused and only the paths are walked -- and gets {robot: waypoints[:count]}; robots whose plan is not PLANNED (unreachable
-        from there, or longer than max_waypoints) are left alone.  `callback.last` holds the latest plan (None before the first)."""
+        from there, or longer than max_waypoints) are left alone.  The plans are smoothed when the planner is (`smooth=`).
+        `callback.last` holds the latest plan (None before the first)."""
         from .waypoints import STALLED
         goal = np.asarray(goal, np.float64)
 
