@@ -41,7 +41,10 @@ report the contact rate, the crossing rate (robots with such a step) and the min
 cells a side over the arena, blocked where --walls / --arena / --hazards are (mobrob_amd.planning.GridPlanner), one path per robot
 from its start to the goal.  It excludes --waypoints.  A first line reports the rate of robots with a plan; the others count a
 robot without one as not successful.  With --horizon and --leg-steps a stalled robot is planned again from where it stands between
-the calls (the planner's callback).  Moving hazards are reported, not planned around.  `--plan-smooth` smooths every plan by line
+the calls (the planner's callback).  With `--hazard-frames` the plan is made over TIME: a robot is given `--plan-layer-steps` steps
+(default 10) for one move or wait, `--plan-layers` (default 64) of them are planned against the frames in force, and where the
+cheapest plan waits for a hazard to pass the run gets the release steps as its schedule (so --release / --stagger and
+--plan-smooth are excluded).  `--plan-smooth` smooths every plan by line
 of sight (fewer waypoints: only the cells a straight leg cannot skip), `--plan-los-margin` (0 or 1, default 1) is the clearance of
 that test in cells; a second line then reports the waypoints and the moves per planned robot.
 """
@@ -72,7 +75,7 @@ def check_chain(max_steps, horizon, leg_steps):
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
-           plan_smooth=False, plan_los_margin=1):
+           plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64):
     calls = check_chain(max_steps, horizon, leg_steps)
     if (goal is None) == (waypoints is None):
         raise ValueError("give --waypoints or --goal, not both")
@@ -108,22 +111,30 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         if goal.shape != (p,) or p < 2:
             raise ValueError(f"--goal must hold {p} coordinates of a robot that moves in x and y, got {goal.size}")
         goals = np.tile(goal, (int(robots), 1))
-        planner = GridPlanner(env, walls=wl, hazards=hz if isinstance(hz, Hazards) else None, cells=int(plan_cells), engine=policy,
-                              smooth=bool(plan_smooth), los_margin=int(plan_los_margin))
+        timed = isinstance(hz, MovingHazards)
+        if timed and (release is not None or stagger):
+            raise ValueError("--release / --stagger exclude --goal with --hazard-frames: the time plan makes the schedule")
+        planner = GridPlanner(env, walls=wl, hazards=hz, cells=int(plan_cells), engine=policy, smooth=bool(plan_smooth),
+                              los_margin=int(plan_los_margin), **(dict(layer_steps=int(plan_layer_steps), layers=int(plan_layers)) if timed else {}))
         plan = planner.plan(start, goals, grow=True)
-        waypoints, n_waypoints = plan["waypoints"], plan["n_waypoints"]
-        replan = planner.callback(goals) if int(leg_steps) > 0 else None
+        waypoints, n_waypoints, plan_schedule = plan["waypoints"], plan["n_waypoints"], plan.get("schedule")
+        replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 else None
         print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
         if plan["smoothed"] and np.any(plan["status"] == 0):
             ok = plan["status"] == 0
             print(f"smoothed plan: {float(np.mean(plan['count'][ok]))} waypoints for {float(np.mean(plan['moves'][ok]))} moves per planned robot")
     schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
+    if goal is not None and plan_schedule is not None:
+        schedule = plan_schedule
     r = follow_waypoints(policy, env, start, waypoints, n_waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
                          leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
     for steps in calls[1:]:                                # the run, continued call after call
         if replan is not None:                             # a stalled robot is planned again from where it stands
             for robot, w in replan(np.array(r["state"].positions), r["status"], r["reached"]).items():
-                r["state"].replan([robot], np.asarray(w, np.float64)[None])
+                if isinstance(w, tuple):                   # a time plan: the waypoints and their release steps
+                    r["state"].replan([robot], np.asarray(w[0], np.float64)[None], release=w[1][None])
+                else:
+                    r["state"].replan([robot], np.asarray(w, np.float64)[None])
         r = follow_waypoints(policy, env, max_steps=steps, deterministic=True, seed=seed, hazards=hz, state=r["state"],
                              leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
     K = r["arrival"].shape[1]
@@ -190,6 +201,8 @@ def build_parser():
     ap.add_argument("--plan-cells", type=int, default=64, help="grid cells a side of the planner (32, 64, 128)")
     ap.add_argument("--plan-smooth", action="store_true", default=False, help="smooth the planned paths by line of sight")
     ap.add_argument("--plan-los-margin", type=int, default=1, choices=(0, 1), help="cells a smoothed leg keeps clear on either side")
+    ap.add_argument("--plan-layer-steps", type=int, default=10, help="with --hazard-frames: steps a robot is given for one move or wait")
+    ap.add_argument("--plan-layers", type=int, default=64, help="with --hazard-frames: actions planned in time before the tail (1 .. 256)")
     ap.add_argument("--robots", type=int, default=1)
     ap.add_argument("--max-steps", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
@@ -227,4 +240,5 @@ if __name__ == "__main__":
            release=None if args.release is None else np.load(args.release), stagger=args.stagger,
            walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius,
            goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells,
-           plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin)
+           plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin, plan_layer_steps=args.plan_layer_steps,
+           plan_layers=args.plan_layers)

@@ -841,7 +841,8 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
  *             test 64 candidates against the anchor at once, a ballot and a count of trailing zeros find the first that is hidden.
  *             k_plan_dilate: the cells that are not clear at margin 1, once per set of resident fields, kept beside them.  Runs on the
  *             engine's stream in the planner's own buffers; nothing a training step reads or writes is touched.
- * Still out of scope: moving hazards, team-mates as obstacles, walls as solid bodies of the simulation.
+ * Still out of scope: smoothing of a time plan (mobrob_ppo_plan_grid_time), team-mates as obstacles, walls as solid bodies of the
+ * simulation.
  * MOBROB_ERR_INVALID before any launch or copy for: a NULL argument (scene aside), margin not 0 or 1, n_robots < 1, pos_dim not 2 or 3,
  * cells not 32 / 64 / 128, max_waypoints < 1, n_fields outside 1 .. n_robots, n_scenes < 1, extent, h, inv_h not finite and > 0 or
  * h * inv_h not 1 within 1e-5, cells / n_scenes / n_fields not the resident fields', a missing scene index with several scenes, a
@@ -851,6 +852,54 @@ int mobrob_ppo_plan_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
                            const int32_t* field_of /* [n] */, const int32_t* scene /* [n] or NULL */,
                            float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */,
                            int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */, int32_t* moves_out /* [n] */);
+
+/* ---- grid planner over time: moving hazards as layers of occupancy, waits as release steps -----------------------------------------
+ * mobrob_ppo_plan_grid for hazards that move (mobrob_hazard_frames_t).  The rule is stated once in mobrob_amd/envs/goal_rules.py
+ * (grid_layer_frames, grid_occupancy_time, grid_time_field, grid_walk_time, grid_path_time) and reproduced bit for bit.  A robot is
+ * given layer_steps steps for one ACTION, a move or a wait.
+ *   layers    layer t < T = `layers` covers the global steps step0 + t layer_steps .. step0 + (t + 1) layer_steps - 1, the tail layer T
+ *             every step from step0 + T layer_steps on.  A layer's frames are the distinct f(g) of its steps, a cyclically contiguous
+ *             run; the tail's are all frames with loop, else f(step0 + T layer_steps) .. n_frames - 1.  They are computed here.
+ *   blocked   layer t's map blocks a cell that mobrob_ppo_plan_grid's test blocks for the walls or for the rows of ANY frame of the layer.
+ *   field     d[T + 1][G][G] per field: d_T is mobrob_ppo_plan_grid's field on the tail's map.  For t < T: d_t[c] = -1 if layer t blocks
+ *             c; 0 in the goal cell; else the minimum of d_{t+1}[nb] + w over the moves layer t allows with d_{t+1}[nb] >= 0 (w = 5, 7)
+ *             and of the wait d_{t+1}[c] + 4 where d_{t+1}[c] >= 0; -1 if nothing qualifies.
+ *   walk      from the start's cell at t = 0; unreachable (count 0, cost -1) iff d_0[start cell] < 0.  While not in the goal's cell and
+ *             t < T: the previous move if it qualifies (allowed by layer t, d_{t+1}[nb] >= 0, d_{t+1}[nb] + w == d_t[c]), else the lowest
+ *             such move of E, N, W, S, NE, NW, SW, SE, else the wait (d_{t+1}[c] + 4 == d_t[c]); every action advances t.  From t = T on
+ *             the walk is mobrob_ppo_plan_grid's on (d_T, the tail's map).  A cell entered by a move is a waypoint when the move leaving
+ *             it differs from the move entering it or when the walk waited there; the last waypoint is the goal itself.
+ *   outputs   waypoints_out .. cost_out as mobrob_ppo_plan_grid's (cost: d_0 at the start cell; status 3: the tail's relaxation or a walk
+ *             of more than T + cells * cells actions ran into its bound).  waits_out [n][K]: the waits made at waypoint k's anchor (the
+ *             previous waypoint's cell; the start cell for k = 0); leave_out [n][K]: the actions made before the move that leaves that
+ *             anchor -- a hold there until step0 + leave * layer_steps is mobrob_follow_schedule_t's release step of waypoint k;
+ *             arrive_out [n]: the actions of the whole walk.  Slots from min(count, K) on are 0.  Optional copies: occ_time_out
+ *             [S][T + 1][G][G], fields_time_out [F][T + 1][G][G], sweeps_out [F] (the tail's relaxation sweeps, -1: bound hit).
+ *   kernels   k_plan_occupancy_time (a thread per scene, layer and cell; the walls staged in LDS once, then each frame of the layer),
+ *             k_plan_field_time (a workgroup per field: the tail relaxed in place in LDS, then T Jacobi steps between two LDS layers,
+ *             one barrier each; 9 bytes a cell, 144 KB at 128 cells), k_plan_path_time (a thread per robot).  Every call computes and
+ *             keeps nothing resident: the buffers are this call's own, so fields left resident by mobrob_ppo_plan_grid stay valid.
+ *             Runs on the engine's stream; nothing a training step reads or writes is touched.
+ * MOBROB_ERR_INVALID before any launch or copy for everything mobrob_ppo_plan_grid refuses (spec->reuse_id must be 0) and everything the
+ * *_hazard_frames calls refuse of the frames, and for: layers outside 1 .. MOBROB_PLAN_LAYERS_MAX, layer_steps < 1, step0 < 0, step0 +
+ * (layers + 1) * layer_steps above INT32_MAX, time fields of n_fields * (layers + 1) * cells * cells * 4 bytes above
+ * MOBROB_PLAN_TIME_MAX_BYTES, a field too large for the device's LDS per workgroup. */
+#define MOBROB_PLAN_LAYERS_MAX 256
+#define MOBROB_PLAN_TIME_MAX_BYTES (256u << 20)
+typedef struct mobrob_plan_time {
+  int32_t step0;        /* g0 >= 0: the global step at which the plan starts */
+  int32_t layer_steps;  /* steps a robot is given for one action, >= 1      */
+  int32_t layers;       /* T: 1 .. MOBROB_PLAN_LAYERS_MAX                    */
+} mobrob_plan_time_t;
+int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                              const mobrob_hazard_frames_t* hazards, const mobrob_plan_time_t* time,
+                              const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */,
+                              const int32_t* field_of /* [n] */, const int32_t* field_goal_cell /* [F] */,
+                              const int32_t* field_scene /* [F] */, float* waypoints_out /* [n][K][pos_dim] */,
+                              int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */, int32_t* status_out /* [n] */,
+                              int32_t* cost_out /* [n] */, int32_t* waits_out /* [n][K] */, int32_t* leave_out /* [n][K] */,
+                              int32_t* arrive_out /* [n] */, uint8_t* occ_time_out /* [S][T + 1][G][G] or NULL */,
+                              int32_t* fields_time_out /* [F][T + 1][G][G] or NULL */, int32_t* sweeps_out /* [F] or NULL */);
 
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment

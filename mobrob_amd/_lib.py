@@ -106,6 +106,10 @@ class PlanSpec(C.Structure):  # mobrob_plan_spec_t
                 ("inflate", C.c_float), ("reuse_id", C.c_int64)]
 
 
+class PlanTime(C.Structure):  # mobrob_plan_time_t
+    _fields_ = [("step0", C.c_int32), ("layer_steps", C.c_int32), ("layers", C.c_int32)]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -205,6 +209,10 @@ SYMBOLS = {
     "mobrob_ppo_plan_smooth": (C.c_int, [_P, C.POINTER(PlanSpec), C.c_int32, _F, _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32)]),
+    "mobrob_ppo_plan_grid_time": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardFramesC), C.POINTER(PlanTime), _F, _F,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), _U8, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

@@ -285,6 +285,11 @@ struct mobrob_ppo_engine {
   char* plan_dil = nullptr;
   size_t plan_dil_bytes = 0;
   int64_t plan_dil_id = 0;
+  // time plans (mobrob_ppo_plan_grid_time): one allocation of their own and nothing resident, so the static fields above stay
+  // valid across time-plan calls
+  char* plan_time_buf = nullptr;
+  size_t plan_time_bytes = 0;
+  bool plan_time_lds_set = false;     // k_plan_field_time's dynamic-LDS attribute is raised once
 };
 
 namespace {
@@ -1359,6 +1364,7 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   if (e->plan_fields) (void)hipFree(e->plan_fields);
   if (e->plan_buf) (void)hipFree(e->plan_buf);
   if (e->plan_dil) (void)hipFree(e->plan_dil);
+  if (e->plan_time_buf) (void)hipFree(e->plan_time_buf);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -3954,6 +3960,95 @@ struct PlanKeep {
   }
 };
 
+// what mobrob_ppo_plan_grid and mobrob_ppo_plan_grid_time check alike of the spec and the scenes (the walls' radius and the costs
+// play no part); hz: the hazards, for a time plan the static view of its frames with their time axis in `frames`
+static int plan_check_scenes(const char* who, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                             const HazardIO* frames, std::vector<int32_t>& wall_counts, std::vector<int32_t>& hz_counts) {
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "%s: n_robots must be >= 1", who);
+  if (P != 2 && P != 3) return fail(MOBROB_ERR_INVALID, "%s: pos_dim must be 2 or 3 (the grid is x and y)", who);
+  if (G != 32 && G != 64 && G != 128) return fail(MOBROB_ERR_INVALID, "%s: cells must be 32, 64 or 128, got %d", who, G);
+  if (K < 1) return fail(MOBROB_ERR_INVALID, "%s: max_waypoints must be >= 1", who);
+  if (F < 1 || F > N) return fail(MOBROB_ERR_INVALID, "%s: n_fields = %d outside 1 .. n_robots = %d", who, F, N);
+  if (!(std::isfinite(spec->extent) && spec->extent > 0.f && std::isfinite(spec->h) && spec->h > 0.f && std::isfinite(spec->inv_h) &&
+        spec->inv_h > 0.f && std::fabs((double)spec->h * (double)spec->inv_h - 1.0) <= 1e-5))
+    return fail(MOBROB_ERR_INVALID, "%s: extent, h and inv_h must be finite and > 0 with h * inv_h = 1", who);
+  if (!(std::isfinite(spec->inflate) && spec->inflate >= 0.f)) return fail(MOBROB_ERR_INVALID, "%s: inflate must be finite and >= 0", who);
+  if ((int64_t)N * K * P > INT_MAX) return fail(MOBROB_ERR_INVALID, "%s: n_robots * max_waypoints * pos_dim must fit an int32", who);
+  if (S != (walls ? walls->n_scenes : hz ? hz->n_scenes : 1) || (walls && hz && walls->n_scenes != hz->n_scenes))
+    return fail(MOBROB_ERR_INVALID, "%s: n_scenes = %d is not the scenes' own (walls %d, hazards %d)", who, S, walls ? walls->n_scenes : -1,
+                hz ? hz->n_scenes : -1);
+  // the scenes, by the checks of the calls that take them (the walls' radius and the costs play no part here)
+  if (walls) {
+    const int M = walls->max_walls;
+    if (S < 1) return fail(MOBROB_ERR_INVALID, "%s: walls: n_scenes must be >= 1", who);
+    if (M < 0 || M > kWallMax) return fail(MOBROB_ERR_INVALID, "%s: walls: max_walls must lie in 0 .. %d", who, kWallMax);
+    if (M > 0 && !walls->boxes) return fail(MOBROB_ERR_INVALID, "%s: walls: null box table", who);
+    if (!walls->scene && S > 1) return fail(MOBROB_ERR_INVALID, "%s: walls: %d scenes need a scene index per robot", who, S);
+    wall_counts.assign(S, M);
+    for (int s = 0; s < S; ++s) {
+      if (walls->n_walls) wall_counts[s] = walls->n_walls[s];
+      if (wall_counts[s] < 0 || wall_counts[s] > M)
+        return fail(MOBROB_ERR_INVALID, "%s: walls: n_walls[%d] = %d outside 0 .. %d", who, s, wall_counts[s], M);
+      for (int i = 0; i < wall_counts[s]; ++i) {
+        const float* b = walls->boxes + ((size_t)s * M + i) * 4;
+        if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]) && b[2] >= 0.f && b[3] >= 0.f))
+          return fail(MOBROB_ERR_INVALID, "%s: walls: box %d of scene %d is not finite or has a negative half extent", who, i, s);
+      }
+    }
+    if (walls->scene)
+      for (int i = 0; i < N; ++i)
+        if (walls->scene[i] < 0 || walls->scene[i] >= S)
+          return fail(MOBROB_ERR_INVALID, "%s: walls: scene[%d] = %d outside 0 .. %d", who, i, walls->scene[i], S - 1);
+  }
+  if (hz) {
+    mobrob_hazards_t view = *hz;
+    view.cost = 0.f;   // (unused here: not refused)
+    HazardIO hio = frames ? *frames : HazardIO{};
+    hio.hz = &view; hio.hazard_out = nullptr; hio.episode_cost_out = nullptr;
+    if (const int rc = hazard_check(hio, N, who, hz_counts)) return rc;
+  }
+  if (walls && hz) {
+    if ((walls->scene != nullptr) != (hz->scene != nullptr))
+      return fail(MOBROB_ERR_INVALID, "%s: walls and hazards must agree on the scene index per robot", who);
+    for (int i = 0; walls->scene && i < N; ++i)
+      if (walls->scene[i] != hz->scene[i])
+        return fail(MOBROB_ERR_INVALID, "%s: walls and hazards disagree on the scene of robot %d (%d and %d)", who, i, walls->scene[i], hz->scene[i]);
+  }
+  return MOBROB_OK;
+}
+
+// ... and of the fields (check_fields: the caller's lists, not resident ones) and the robots
+static int plan_check_robots(const char* who, const mobrob_plan_spec_t* spec, const int32_t* scene, const float* start, const float* goal,
+                             const int32_t* field_of, const int32_t* field_goal_cell, const int32_t* field_scene, bool check_fields) {
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, S = spec->n_scenes, F = spec->n_fields, cells = G * G;
+  if (check_fields)
+    for (int f = 0; f < F; ++f) {
+      if (field_scene[f] < 0 || field_scene[f] >= S)
+        return fail(MOBROB_ERR_INVALID, "%s: field_scene[%d] = %d outside 0 .. %d", who, f, field_scene[f], S - 1);
+      if (field_goal_cell[f] < 0 || field_goal_cell[f] >= cells)
+        return fail(MOBROB_ERR_INVALID, "%s: field_goal_cell[%d] = %d outside 0 .. %d", who, f, field_goal_cell[f], cells - 1);
+    }
+  const auto cell_of = [&](float x) {   // plan_cell's arithmetic (kernels_plan.h); volatile: the sum is rounded to float before the product
+    volatile float sum = x + spec->extent;
+    volatile float c = sum * spec->inv_h;
+    return (int)std::fmin(std::fmax(std::floor((float)c), 0.f), (float)(G - 1));
+  };
+  for (int i = 0; i < N; ++i) {
+    for (int j = 0; j < P; ++j)
+      if (!std::isfinite(start[(size_t)i * P + j]) || !std::isfinite(goal[(size_t)i * P + j]))
+        return fail(MOBROB_ERR_INVALID, "%s: start or goal of robot %d is not finite", who, i);
+    const int f = field_of[i];
+    if (f < 0 || f >= F) return fail(MOBROB_ERR_INVALID, "%s: field_of[%d] = %d outside 0 .. %d", who, i, f, F - 1);
+    if (field_scene[f] != (scene ? scene[i] : 0))
+      return fail(MOBROB_ERR_INVALID, "%s: robot %d is in scene %d, its field %d in scene %d", who, i, scene ? scene[i] : 0, f, field_scene[f]);
+    const int gc = cell_of(goal[(size_t)i * P + 1]) * G + cell_of(goal[(size_t)i * P]);
+    if (gc != field_goal_cell[f])
+      return fail(MOBROB_ERR_INVALID, "%s: the goal of robot %d lies in cell %d, its field %d has goal cell %d", who, i, gc, f, field_goal_cell[f]);
+  }
+  return MOBROB_OK;
+}
+
 int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
                          const float* start, const float* goal, const int32_t* field_of, const int32_t* field_goal_cell,
                          const int32_t* field_scene, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
@@ -3964,57 +4059,9 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   const bool reuse = spec->reuse_id != 0;
   if (!reuse && (!field_goal_cell || !field_scene)) return fail(MOBROB_ERR_INVALID, "plan: null argument");
   const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
-  if (N < 1) return fail(MOBROB_ERR_INVALID, "plan: n_robots must be >= 1");
-  if (P != 2 && P != 3) return fail(MOBROB_ERR_INVALID, "plan: pos_dim must be 2 or 3 (the grid is x and y)");
-  if (G != 32 && G != 64 && G != 128) return fail(MOBROB_ERR_INVALID, "plan: cells must be 32, 64 or 128, got %d", G);
-  if (K < 1) return fail(MOBROB_ERR_INVALID, "plan: max_waypoints must be >= 1");
-  if (F < 1 || F > N) return fail(MOBROB_ERR_INVALID, "plan: n_fields = %d outside 1 .. n_robots = %d", F, N);
-  if (!(std::isfinite(spec->extent) && spec->extent > 0.f && std::isfinite(spec->h) && spec->h > 0.f && std::isfinite(spec->inv_h) &&
-        spec->inv_h > 0.f && std::fabs((double)spec->h * (double)spec->inv_h - 1.0) <= 1e-5))
-    return fail(MOBROB_ERR_INVALID, "plan: extent, h and inv_h must be finite and > 0 with h * inv_h = 1");
-  if (!(std::isfinite(spec->inflate) && spec->inflate >= 0.f)) return fail(MOBROB_ERR_INVALID, "plan: inflate must be finite and >= 0");
-  if ((int64_t)N * K * P > INT_MAX) return fail(MOBROB_ERR_INVALID, "plan: n_robots * max_waypoints * pos_dim must fit an int32");
   const int cells = G * G;
-  if (S != (walls ? walls->n_scenes : hz ? hz->n_scenes : 1) || (walls && hz && walls->n_scenes != hz->n_scenes))
-    return fail(MOBROB_ERR_INVALID, "plan: n_scenes = %d is not the scenes' own (walls %d, hazards %d)", S, walls ? walls->n_scenes : -1,
-                hz ? hz->n_scenes : -1);
-  // the scenes, by the checks of the calls that take them (the walls' radius and the costs play no part here)
   std::vector<int32_t> wall_counts, hz_counts;
-  if (walls) {
-    const int M = walls->max_walls;
-    if (S < 1) return fail(MOBROB_ERR_INVALID, "plan: walls: n_scenes must be >= 1");
-    if (M < 0 || M > kWallMax) return fail(MOBROB_ERR_INVALID, "plan: walls: max_walls must lie in 0 .. %d", kWallMax);
-    if (M > 0 && !walls->boxes) return fail(MOBROB_ERR_INVALID, "plan: walls: null box table");
-    if (!walls->scene && S > 1) return fail(MOBROB_ERR_INVALID, "plan: walls: %d scenes need a scene index per robot", S);
-    wall_counts.assign(S, M);
-    for (int s = 0; s < S; ++s) {
-      if (walls->n_walls) wall_counts[s] = walls->n_walls[s];
-      if (wall_counts[s] < 0 || wall_counts[s] > M)
-        return fail(MOBROB_ERR_INVALID, "plan: walls: n_walls[%d] = %d outside 0 .. %d", s, wall_counts[s], M);
-      for (int i = 0; i < wall_counts[s]; ++i) {
-        const float* b = walls->boxes + ((size_t)s * M + i) * 4;
-        if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]) && b[2] >= 0.f && b[3] >= 0.f))
-          return fail(MOBROB_ERR_INVALID, "plan: walls: box %d of scene %d is not finite or has a negative half extent", i, s);
-      }
-    }
-    if (walls->scene)
-      for (int i = 0; i < N; ++i)
-        if (walls->scene[i] < 0 || walls->scene[i] >= S)
-          return fail(MOBROB_ERR_INVALID, "plan: walls: scene[%d] = %d outside 0 .. %d", i, walls->scene[i], S - 1);
-  }
-  if (hz) {
-    mobrob_hazards_t view = *hz;
-    view.cost = 0.f;   // (unused here: not refused)
-    const HazardIO hio{&view, nullptr, nullptr};
-    if (const int rc = hazard_check(hio, N, "plan", hz_counts)) return rc;
-  }
-  if (walls && hz) {
-    if ((walls->scene != nullptr) != (hz->scene != nullptr))
-      return fail(MOBROB_ERR_INVALID, "plan: walls and hazards must agree on the scene index per robot");
-    for (int i = 0; walls->scene && i < N; ++i)
-      if (walls->scene[i] != hz->scene[i])
-        return fail(MOBROB_ERR_INVALID, "plan: walls and hazards disagree on the scene of robot %d (%d and %d)", i, walls->scene[i], hz->scene[i]);
-  }
+  if (const int rc = plan_check_scenes("plan", spec, walls, hz, nullptr, wall_counts, hz_counts)) return rc;
   const int32_t* scene = walls ? walls->scene : hz ? hz->scene : nullptr;
   if (reuse) {
     if (spec->reuse_id != e->plan_id || e->plan_id == 0)
@@ -4025,31 +4072,8 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
                   e->plan_G, e->plan_S, e->plan_F);
     field_goal_cell = e->plan_field_goal.data();
     field_scene = e->plan_field_scene.data();
-  } else {
-    for (int f = 0; f < F; ++f) {
-      if (field_scene[f] < 0 || field_scene[f] >= S)
-        return fail(MOBROB_ERR_INVALID, "plan: field_scene[%d] = %d outside 0 .. %d", f, field_scene[f], S - 1);
-      if (field_goal_cell[f] < 0 || field_goal_cell[f] >= cells)
-        return fail(MOBROB_ERR_INVALID, "plan: field_goal_cell[%d] = %d outside 0 .. %d", f, field_goal_cell[f], cells - 1);
-    }
   }
-  const auto cell_of = [&](float x) {   // plan_cell's arithmetic (kernels_plan.h); volatile: the sum is rounded to float before the product
-    volatile float sum = x + spec->extent;
-    volatile float c = sum * spec->inv_h;
-    return (int)std::fmin(std::fmax(std::floor((float)c), 0.f), (float)(G - 1));
-  };
-  for (int i = 0; i < N; ++i) {
-    for (int j = 0; j < P; ++j)
-      if (!std::isfinite(start[(size_t)i * P + j]) || !std::isfinite(goal[(size_t)i * P + j]))
-        return fail(MOBROB_ERR_INVALID, "plan: start or goal of robot %d is not finite", i);
-    const int f = field_of[i];
-    if (f < 0 || f >= F) return fail(MOBROB_ERR_INVALID, "plan: field_of[%d] = %d outside 0 .. %d", i, f, F - 1);
-    if (field_scene[f] != (scene ? scene[i] : 0))
-      return fail(MOBROB_ERR_INVALID, "plan: robot %d is in scene %d, its field %d in scene %d", i, scene ? scene[i] : 0, f, field_scene[f]);
-    const int gc = cell_of(goal[(size_t)i * P + 1]) * G + cell_of(goal[(size_t)i * P]);
-    if (gc != field_goal_cell[f])
-      return fail(MOBROB_ERR_INVALID, "plan: the goal of robot %d lies in cell %d, its field %d has goal cell %d", i, gc, f, field_goal_cell[f]);
-  }
+  if (const int rc = plan_check_robots("plan", spec, scene, start, goal, field_of, field_goal_cell, field_scene, !reuse)) return rc;
   const size_t field_lds = plan_field_lds_bytes(G);
   const int Mw = walls ? walls->max_walls : 0, Mh = hz ? hz->max_hazards : 0;
   if (!reuse) {   // the per-workgroup LDS limit, as the tile kernels' scenes are checked
@@ -4240,6 +4264,150 @@ int mobrob_ppo_plan_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
   HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(moves_out, sa.moves, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
+}
+
+// ---- grid planner over time (mobrob_ppo_plan_grid_time): moving hazards as layers, waits as release steps --------------------
+// the frames of every layer, as goal_rules.grid_layer_frames states them (64-bit: step0 + (T + 1) * layer_steps fits an int32)
+static void plan_layer_frames(const mobrob_hazard_frames_t* hz, const mobrob_plan_time_t* tm, std::vector<int32_t>& first,
+                              std::vector<int32_t>& number) {
+  const int64_t F = hz->n_frames, fs = hz->frame_steps, g0 = tm->step0, dl = tm->layer_steps;
+  const int T = tm->layers;
+  first.assign(T + 1, 0);
+  number.assign(T + 1, 0);
+  for (int t = 0; t < T; ++t) {
+    const int64_t k_lo = (g0 + t * dl) / fs, k_hi = (g0 + (t + 1) * dl - 1) / fs;
+    if (hz->loop) {
+      first[t] = (int32_t)(k_lo % F);
+      number[t] = (int32_t)std::min<int64_t>(k_hi - k_lo + 1, F);
+    } else {
+      first[t] = (int32_t)std::min<int64_t>(k_lo, F - 1);
+      number[t] = (int32_t)(std::min<int64_t>(k_hi, F - 1) - first[t] + 1);
+    }
+  }
+  first[T] = hz->loop ? 0 : (int32_t)std::min<int64_t>((g0 + T * dl) / fs, F - 1);
+  number[T] = (int32_t)(F - first[T]);
+}
+
+int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                              const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, const float* start, const float* goal,
+                              const int32_t* field_of, const int32_t* field_goal_cell, const int32_t* field_scene, float* waypoints_out,
+                              int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* waits_out,
+                              int32_t* leave_out, int32_t* arrive_out, uint8_t* occ_time_out, int32_t* fields_time_out,
+                              int32_t* sweeps_out) {
+  if (!e || !spec || !hzf || !tm || !start || !goal || !field_of || !field_goal_cell || !field_scene || !waypoints_out ||
+      !n_waypoints_out || !count_out || !status_out || !cost_out || !waits_out || !leave_out || !arrive_out)
+    return fail(MOBROB_ERR_INVALID, "plan_time: null argument");
+  if (spec->reuse_id != 0) return fail(MOBROB_ERR_INVALID, "plan_time: reuse_id must be 0 (a time plan keeps nothing resident)");
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
+  const int cells = G * G, T = tm->layers;
+  mobrob_hazards_t view;
+  const HazardIO frames = hazard_frames_io(hzf, view, nullptr, nullptr);
+  std::vector<int32_t> wall_counts, hz_counts;
+  if (const int rc = plan_check_scenes("plan_time", spec, walls, &view, &frames, wall_counts, hz_counts)) return rc;
+  if (S > 65535) return fail(MOBROB_ERR_INVALID, "plan_time: n_scenes = %d above 65535", S);
+  if (const int rc = plan_check_robots("plan_time", spec, hzf->scene, start, goal, field_of, field_goal_cell, field_scene, true)) return rc;
+  if (T < 1 || T > kPlanLayersMax) return fail(MOBROB_ERR_INVALID, "plan_time: layers must lie in 1 .. %d, got %d", kPlanLayersMax, T);
+  if (tm->layer_steps < 1) return fail(MOBROB_ERR_INVALID, "plan_time: layer_steps must be >= 1, got %d", tm->layer_steps);
+  if (tm->step0 < 0) return fail(MOBROB_ERR_INVALID, "plan_time: step0 must be >= 0, got %d", tm->step0);
+  if ((int64_t)tm->step0 + (int64_t)(T + 1) * tm->layer_steps > INT_MAX)
+    return fail(MOBROB_ERR_INVALID, "plan_time: step0 + (layers + 1) * layer_steps must fit an int32");
+  if ((uint64_t)F * (uint64_t)(T + 1) * (uint64_t)cells * 4u > MOBROB_PLAN_TIME_MAX_BYTES)
+    return fail(MOBROB_ERR_INVALID, "plan_time: time fields of %d x %d x %d x %d x 4 bytes exceed the cap of %u bytes (256 MiB)", F, T + 1, G, G,
+                (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
+  const size_t field_lds = plan_field_time_lds_bytes(G);
+  {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid checks k_plan_field's
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+    if (field_lds > (size_t)limit)
+      return fail(MOBROB_ERR_INVALID, "plan_time: k_plan_field_time needs %zu bytes of LDS at %d cells, the device allows %d per workgroup",
+                  field_lds, G, limit);
+  }
+  std::vector<int32_t> lfirst, lnumber;
+  plan_layer_frames(hzf, tm, lfirst, lnumber);
+  const int Mw = walls ? walls->max_walls : 0, Mh = hzf->max_hazards, NF = hzf->n_frames;
+  const size_t hz_floats = (size_t)S * NF * Mh * 3;
+  EvalCarve call;
+  const size_t o_occ = call.add((size_t)S * (T + 1) * cells), o_field = call.add((size_t)F * (T + 1) * cells * 4),
+               o_fgoal = call.add((size_t)F * 4), o_fscene = call.add((size_t)F * 4), o_sweeps = call.add((size_t)F * 4),
+               o_lfirst = call.add((size_t)(T + 1) * 4), o_lnumber = call.add((size_t)(T + 1) * 4),
+               o_start = call.add((size_t)N * P * 4), o_goal = call.add((size_t)N * P * 4), o_fof = call.add((size_t)N * 4),
+               o_wp = call.add((size_t)N * K * P * 4), o_nwp = call.add((size_t)N * 4), o_count = call.add((size_t)N * 4),
+               o_status = call.add((size_t)N * 4), o_cost = call.add((size_t)N * 4), o_waits = call.add((size_t)N * K * 4),
+               o_leave = call.add((size_t)N * K * 4), o_arrive = call.add((size_t)N * 4),
+               o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
+               o_hz = call.add(std::max<size_t>(hz_floats, 1) * 4), o_nhz = call.add((size_t)S * 4);
+  if (const int rc = grow_plan_buf(e, e->plan_time_buf, e->plan_time_bytes, call.total)) return rc;
+  const auto mine = [&](size_t off) { return e->plan_time_buf + off; };
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(mine(o_occ));
+  int* field_dev = reinterpret_cast<int*>(mine(o_field));
+  int* fgoal_dev = reinterpret_cast<int*>(mine(o_fgoal));
+  int* fscene_dev = reinterpret_cast<int*>(mine(o_fscene));
+  int* sweeps_dev = reinterpret_cast<int*>(mine(o_sweeps));
+  int* lfirst_dev = reinterpret_cast<int*>(mine(o_lfirst));
+  int* lnumber_dev = reinterpret_cast<int*>(mine(o_lnumber));
+  PlanOccTimeArgs oa{};
+  oa.g = PlanGrid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  oa.Mw = Mw; oa.Mh = Mh; oa.F = NF; oa.T = T; oa.layer_first = lfirst_dev; oa.layer_number = lnumber_dev; oa.occ = occ_dev;
+  if (walls) {
+    float* box_dev = reinterpret_cast<float*>(mine(o_box));
+    int* cnt_dev = reinterpret_cast<int*>(mine(o_nwall));
+    if ((size_t)S * Mw) HIPC(hipMemcpyAsync(box_dev, walls->boxes, (size_t)S * Mw * 16, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(cnt_dev, wall_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+    oa.boxes = box_dev; oa.nwall = cnt_dev;
+  }
+  float* hz_dev = reinterpret_cast<float*>(mine(o_hz));
+  int* nhz_dev = reinterpret_cast<int*>(mine(o_nhz));
+  if (hz_floats) HIPC(hipMemcpyAsync(hz_dev, hzf->hazards, hz_floats * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(nhz_dev, hz_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  oa.hz = hz_dev; oa.nhz = nhz_dev;
+  HIPC(hipMemcpyAsync(lfirst_dev, lfirst.data(), (size_t)(T + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(lnumber_dev, lnumber.data(), (size_t)(T + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(fgoal_dev, field_goal_cell, (size_t)F * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(fscene_dev, field_scene, (size_t)F * 4, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_plan_occupancy_time, dim3(cells / 256, T + 1, S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
+  if (!e->plan_time_lds_set) {   // 144 KB at 128 cells: above the 64 KB a kernel gets without asking
+    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_field_time), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)plan_field_time_lds_bytes(128)));
+    e->plan_time_lds_set = true;
+  }
+  const PlanFieldTimeArgs fa{G, T, occ_dev, fgoal_dev, fscene_dev, field_dev, sweeps_dev};
+  hipLaunchKernelGGL(k_plan_field_time, dim3(F), dim3(kPlanFieldThreads), field_lds, e->stream, fa);
+  HIPC(hipGetLastError());
+  PlanPathTimeArgs ta{};
+  PlanPathArgs& pa = ta.p;
+  pa.g = oa.g; pa.N = N; pa.K = K; pa.P = P;
+  float* start_dev = reinterpret_cast<float*>(mine(o_start));
+  float* goal_dev = reinterpret_cast<float*>(mine(o_goal));
+  int* fof_dev = reinterpret_cast<int*>(mine(o_fof));
+  pa.start = start_dev; pa.goal = goal_dev; pa.field_of = fof_dev;
+  pa.field_scene = fscene_dev; pa.sweeps = sweeps_dev; pa.occ = occ_dev; pa.field = field_dev;
+  pa.wp = reinterpret_cast<float*>(mine(o_wp));
+  pa.nwp = reinterpret_cast<int*>(mine(o_nwp)); pa.count = reinterpret_cast<int*>(mine(o_count));
+  pa.status = reinterpret_cast<int*>(mine(o_status)); pa.cost = reinterpret_cast<int*>(mine(o_cost));
+  ta.T = T;
+  ta.waits = reinterpret_cast<int*>(mine(o_waits)); ta.leave = reinterpret_cast<int*>(mine(o_leave));
+  ta.arrive = reinterpret_cast<int*>(mine(o_arrive));
+  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(goal_dev, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(fof_dev, field_of, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
+  HIPC(hipMemsetAsync(ta.waits, 0, (size_t)N * K * 4, e->stream));
+  HIPC(hipMemsetAsync(ta.leave, 0, (size_t)N * K * 4, e->stream));
+  hipLaunchKernelGGL(k_plan_path_time, dim3(cdiv(N, 64)), dim3(64), 0, e->stream, ta);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(waits_out, ta.waits, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(leave_out, ta.leave, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(arrive_out, ta.arrive, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  if (occ_time_out) HIPC(hipMemcpyAsync(occ_time_out, occ_dev, (size_t)S * (T + 1) * cells, hipMemcpyDeviceToHost, e->stream));
+  if (fields_time_out) HIPC(hipMemcpyAsync(fields_time_out, field_dev, (size_t)F * (T + 1) * cells * 4, hipMemcpyDeviceToHost, e->stream));
+  if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, sweeps_dev, (size_t)F * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
 }

@@ -393,4 +393,236 @@ __global__ __launch_bounds__(64) void k_plan_smooth(PlanSmoothArgs s) {
   s.moves[n] = moves;
 }
 
+// ---- planning over time (mobrob_ppo_plan_grid_time; the rule: goal_rules.grid_layer_frames / grid_occupancy_time / grid_time_field /
+// grid_walk_time / grid_path_time) ------------------------------------------------------------------------------------------------
+// Moving hazards as T + 1 LAYERS of occupancy: layer t < T blocks what any hazard frame in force during the robot's t-th action
+// blocks, the tail layer T what any frame from then on blocks.  A layer's frames are a cyclically contiguous run, `number` frames
+// from `first` (computed on the host).  The time field d[T + 1][G][G]: d_T is k_plan_field's fixed point on the tail's map; d_t
+// for t < T is one Jacobi step from d_{t+1} over the moves of layer t's map and the wait (kPlanWait).
+constexpr int kPlanWait = 4;      // a wait: cheaper than a move
+constexpr int kPlanLayersMax = 256;
+
+struct PlanOccTimeArgs {
+  PlanGrid g;
+  const float* boxes;       // [S][Mw][4]
+  const int* nwall;         // [S]
+  int Mw;
+  const float* hz;          // [S][F][Mh][3]
+  const int* nhz;           // [S]
+  int Mh, F, T;
+  const int* layer_first;   // [T + 1]
+  const int* layer_number;  // [T + 1], 1 .. F
+  unsigned char* occ;       // [S][T + 1][G][G] out: 1 blocked
+};
+
+// grid (G * G / 256, T + 1, S), 256 threads (G * G is a multiple of 256), LDS 4 Mw + 3 Mh floats: the scene's walls staged once,
+// then every frame of the layer's set in turn, behind barriers.  The tests are k_plan_occupancy's own.
+__global__ __launch_bounds__(256) void k_plan_occupancy_time(PlanOccTimeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float plan_scene_time_lds[];
+  const int s = blockIdx.z, t = blockIdx.y, G = a.g.G;
+  const int mw = a.nwall ? a.nwall[s] : 0, mh = a.nhz[s];
+  float* wl = plan_scene_time_lds;
+  float* hl = plan_scene_time_lds + 4 * a.Mw;
+  for (int i = threadIdx.x; i < 4 * mw; i += 256) wl[i] = a.boxes[(size_t)s * a.Mw * 4 + i];
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const float px = plan_centre(a.g, c % G), py = plan_centre(a.g, c / G);
+  const int first = a.layer_first[t], number = a.layer_number[t];
+  bool blocked = false;
+  for (int j = 0; j < number; ++j) {
+    int fr = first + j;
+    if (fr >= a.F) fr -= a.F;
+    if (j > 0) __syncthreads();   // the previous frame's loads before this frame's stores
+    const float* rows = a.hz + ((size_t)s * a.F + fr) * a.Mh * 3;
+    for (int i = threadIdx.x; i < 3 * mh; i += 256) hl[i] = rows[i];
+    __syncthreads();
+    if (j == 0)
+      for (int i = 0; i < mw; ++i)
+        if (wall_sdf(px, py, wl[4 * i], wl[4 * i + 1], wl[4 * i + 2], wl[4 * i + 3]) <= a.g.inflate) blocked = true;
+    for (int i = 0; i < mh; ++i) {
+      const float dx = __fsub_rn(px, hl[3 * i]), dy = __fsub_rn(py, hl[3 * i + 1]);
+      const float d = sqrtf(__fadd_rn(rounded(__fmul_rn(dx, dx)), rounded(__fmul_rn(dy, dy))));   // sqrtf: correctly rounded
+      if (d <= __fadd_rn(hl[3 * i + 2], a.g.inflate)) blocked = true;
+    }
+  }
+  a.occ[((size_t)s * (a.T + 1) + t) * G * G + c] = blocked ? 1 : 0;
+}
+
+struct PlanFieldTimeArgs {
+  int G, T;
+  const unsigned char* occ;   // [S][T + 1][G][G]
+  const int* field_goal;      // [F] goal cell
+  const int* field_scene;     // [F]
+  int* field;                 // [F][T + 1][G][G] out: cost-to-go, -1 blocked or unreachable
+  int* sweeps;                // [F] out: sweeps of the tail's relaxation, -1: the bound of G * G was hit
+};
+
+// LDS bytes of k_plan_field_time: two layers of the field, then one byte of moves per cell (144 KB at 128 cells)
+inline size_t plan_field_time_lds_bytes(int G) { return (size_t)G * G * (2 * sizeof(int) + 1); }
+
+// One workgroup per field, 1024 threads.  The tail is k_plan_field's in-place relaxation on the tail's map, to a tested fixed
+// point.  Then T backward layers between two LDS layers, ping-pong: layer t is written from layer t + 1 alone, a pure function of
+// it, so there is no order to argue about; the one barrier per layer puts a layer's stores before the next layer's loads, and the
+// buffer a layer overwrites was last read before that barrier.  A layer's moves come from its own map in global memory, each cell
+// once.
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_field_time(PlanFieldTimeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int plan_field_time_lds[];
+  const int f = blockIdx.x, G = a.G, T = a.T, cells = G * G, tid = threadIdx.x;
+  int* d = plan_field_time_lds;
+  int* e = plan_field_time_lds + cells;
+  unsigned char* moves = reinterpret_cast<unsigned char*>(plan_field_time_lds + 2 * cells);
+  const unsigned char* occ_scene = a.occ + (size_t)a.field_scene[f] * (T + 1) * cells;
+  const unsigned char* occ = occ_scene + (size_t)T * cells;
+  const int goal = a.field_goal[f];
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    const bool blocked = occ[c] != 0;
+    moves[c] = blocked ? 0 : (unsigned char)plan_moves(occ, G, c % G, c / G);
+    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
+  }
+  __syncthreads();
+  int sweeps = -1;
+  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
+    int changed = 0;
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      const unsigned m = moves[c];
+      if (m == 0 || c == goal) continue;
+      const int cur = d[c];
+      int best = cur;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (m & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
+      if (best < cur) { d[c] = best; changed = 1; }
+    }
+    __syncthreads();   // this sweep's stores before the next sweep's loads
+    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
+  }
+  int* out = a.field + (size_t)f * (T + 1) * cells;
+  for (int c = tid; c < cells; c += kPlanFieldThreads) out[(size_t)T * cells + c] = d[c] >= kPlanInf ? -1 : d[c];
+  if (tid == 0) a.sweeps[f] = sweeps;
+  int* nxt = d;   // layer t + 1
+  int* cur = e;   // layer t
+  for (int t = T - 1; t >= 0; --t) {
+    const unsigned char* occ_t = occ_scene + (size_t)t * cells;
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      int best = kPlanInf;
+      if (!occ_t[c]) {
+        if (c == goal) {
+          best = 0;
+        } else {
+          const unsigned m = plan_moves(occ_t, G, c % G, c / G);
+          best = nxt[c] + kPlanWait;
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            if (m & (1u << k)) best = min(best, nxt[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
+          best = min(best, kPlanInf);   // kPlanInf + a cost: still "none"
+        }
+      }
+      cur[c] = best;
+      out[(size_t)t * cells + c] = best >= kPlanInf ? -1 : best;
+    }
+    __syncthreads();
+    int* const swap = nxt; nxt = cur; cur = swap;
+  }
+}
+
+struct PlanPathTimeArgs {
+  PlanPathArgs p;   // k_plan_path's inputs and outputs; occ [S][T + 1][G][G], field [F][T + 1][G][G]
+  int T;
+  int* waits;       // [N][K] out (zeroed by the host): waits at waypoint k's anchor
+  int* leave;       // [N][K] out (zeroed by the host): actions before the move that leaves that anchor
+  int* arrive;      // [N] out: actions of the whole walk
+};
+
+// One thread per robot, 64 to a workgroup: the walk of goal_rules.grid_walk_time with grid_path_time's waypoints.  While t < T an
+// action is the previous move, else the lowest move, else the wait, that descends from d_t to d_{t+1} over layer t's map; from
+// t = T on it is plan_walk_dir on the tail.  At most T + G * G actions: status 3 beyond, as k_plan_path.
+__global__ __launch_bounds__(64) void k_plan_path_time(PlanPathTimeArgs s) {
+  const PlanPathArgs& a = s.p;
+  const int n = blockIdx.x * 64 + threadIdx.x;
+  if (n >= a.N) return;
+  const int G = a.g.G, cells = G * G, P = a.P, K = a.K, T = s.T;
+  const int f = a.field_of[n];
+  const unsigned char* occ = a.occ + (size_t)a.field_scene[f] * (T + 1) * cells;
+  const int* d = a.field + (size_t)f * (T + 1) * cells;
+  const float* st = a.start + (size_t)n * P;
+  const float* gl = a.goal + (size_t)n * P;
+  float* wp = a.wp + (size_t)n * K * P;
+  int* waits = s.waits + (size_t)n * K;
+  int* leave = s.leave + (size_t)n * K;
+  int ix = plan_cell(a.g, st[0]), iy = plan_cell(a.g, st[1]);
+  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
+  int count = 0, status = kPlanned, cost = -1, acts = 0;
+  if (a.sweeps[f] < 0) {
+    status = kPlanUnconverged;
+  } else if (d[iy * G + ix] < 0) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d[iy * G + ix];
+    int prev = -1, waited = 0, t = 0;
+    while (ix != gx || iy != gy) {
+      if (acts >= T + cells) { status = kPlanUnconverged; break; }
+      int dir;
+      if (t < T) {
+        const unsigned char* occ_t = occ + (size_t)t * cells;
+        const int* dn = d + (size_t)(t + 1) * cells;
+        const unsigned m = plan_moves(occ_t, G, ix, iy);
+        const int dc = d[(size_t)t * cells + iy * G + ix];
+        dir = -1;
+        for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
+          if (!(m & (1u << k))) continue;
+          const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
+          if (v >= 0 && v + (k < 4 ? 5 : 7) == dc) dir = k;
+        }
+        if (prev >= 0 && (m & (1u << prev))) {   // the previous move first
+          const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
+          if (v >= 0 && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
+        }
+        if (dir < 0) {   // the wait last
+          const int v = dn[iy * G + ix];
+          if (v >= 0 && v + kPlanWait == dc) dir = 8;
+        }
+        ++t;
+      } else {
+        dir = plan_walk_dir(occ + (size_t)T * cells, d + (size_t)T * cells, G, ix, iy, prev);
+      }
+      if (dir < 0) { status = kPlanUnconverged; break; }   // not a time field of these layers: cannot happen after k_plan_field_time
+      ++acts;
+      if (dir == 8) { ++waited; continue; }
+      const bool turned = prev >= 0 && (dir != prev || waited > 0);
+      if (turned) {
+        if (count < K) {
+          wp[count * P] = plan_centre(a.g, ix);
+          wp[count * P + 1] = plan_centre(a.g, iy);
+          if (P == 3) wp[count * P + 2] = gl[2];
+        }
+        ++count;
+      }
+      if ((prev < 0 || turned) && count < K) {   // this move leaves the anchor of waypoint `count`
+        waits[count] = waited;
+        leave[count] = acts - 1;
+      }
+      ix += plan_dx(dir); iy += plan_dy(dir);
+      prev = dir;
+      waited = 0;
+    }
+    if (status == kPlanned) {
+      if (count < K)
+        for (int j = 0; j < P; ++j) wp[count * P + j] = gl[j];
+      ++count;
+      if (count > K) status = kPlanTruncated;
+    }
+  }
+  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
+    for (int j = 0; j < min(count, K) * P; ++j) wp[j] = 0.f;
+    for (int j = 0; j < K; ++j) { waits[j] = 0; leave[j] = 0; }
+    count = 0;
+    cost = -1;
+    acts = 0;
+  }
+  a.nwp[n] = min(count, K);
+  a.count[n] = count;
+  a.status[n] = status;
+  a.cost[n] = cost;
+  s.arrive[n] = acts;
+}
+
 }  // namespace mobrob

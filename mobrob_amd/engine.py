@@ -743,6 +743,73 @@ class PPOEngine:
                 "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene, "fields_id": int(reuse["fields_id"]),
                 "n_scenes": int(sp.n_scenes)}
 
+    def plan_grid_time(self, spec, walls=None, hazards=None, *, start, goal, step0=0, layer_steps, layers=64, max_waypoints=16,
+                       want_occupancy=False, want_fields=False):
+        """Waypoints and release steps for every robot among hazards that move (mobrob_ppo_plan_grid_time; the rule:
+        goal_rules.grid_plan_time, reproduced bit for bit).  hazards: a goal_rules.MovingHazards; step0: the global step at
+        which the plan starts; layer_steps: the steps a robot is given for one move or wait; layers: T, the actions planned in
+        time before the conservative tail.  Returns plan_grid's dict (sweeps: the tail's; no fields_id -- every call computes
+        and keeps nothing resident, fields a plan_grid call left resident stay valid) plus waits, leave [n][K] int32, arrive
+        [n] int32 and release [n][K] int32 (goal_rules.grid_release: Schedule's release steps), and on request occupancy bool
+        [S][T + 1][G][G] and fields int32 [F][T + 1][G][G]."""
+        from ._lib import PlanSpec, PlanTime, WallsC
+        from .envs import goal_rules as R
+        if not isinstance(spec, R.GridSpec):
+            raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.GridSpec, not {type(spec).__name__}")
+        start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
+        if goal.ndim != 2 or goal.shape[0] < 1 or goal.shape[1] not in (2, 3) or start.shape != goal.shape:
+            raise ValueError(f"plan_time: start and goal must both be [n_robots, 2 or 3], got shapes {start.shape} and {goal.shape}")
+        if not (np.all(np.isfinite(start)) and np.all(np.isfinite(goal))):
+            raise ValueError("plan_time: start and goal must be finite")
+        n, P = goal.shape
+        K = int(max_waypoints)
+        if K < 1:
+            raise ValueError("plan_time: max_waypoints must be >= 1")
+        S, scene = R.plan_scene_time(walls, hazards)
+        step0, layer_steps, T = R.plan_time_check(step0, layer_steps, layers)
+        for sc in (walls, hazards):
+            if sc is not None:
+                sc.check_robots(n)
+        start, goal = np.ascontiguousarray(start, F32), np.ascontiguousarray(goal, F32)
+        field_of, fcell, fscene = R.plan_fields(spec, None, scene, goal)
+        Fn, G = len(fcell), spec.cells
+        i32 = C.POINTER(C.c_int32)
+        sp = PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_scenes, sp.n_fields = n, P, G, K, S, Fn
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(spec.extent), float(spec.h), float(spec.inv_h), float(spec.inflate_for(walls))
+        sp.reuse_id = 0
+        tm = PlanTime()
+        tm.step0, tm.layer_steps, tm.layers = step0, layer_steps, T
+        wl = None
+        if walls is not None:
+            wl = WallsC()
+            wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+            wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
+            wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
+            wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
+        h, _keep = self._hazards_struct(hazards, n)
+        big = Fn * (T + 1) * G * G * 4 > R.PLAN_TIME_MAX_BYTES            # refused by name below; nothing that large is allocated here
+        wp = np.zeros((n, K, P), F32)
+        waits, leave = np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
+        nwp, count, status, cost, arrive = (np.zeros(n, np.int32) for _ in range(5))
+        occ = np.zeros((S, T + 1, G, G), np.uint8) if want_occupancy and not big else None
+        fields = np.zeros((Fn, T + 1, G, G), np.int32) if want_fields and not big else None
+        sweeps = np.zeros(Fn, np.int32)
+        check(self.lib.mobrob_ppo_plan_grid_time(
+            self._h, C.byref(sp), None if wl is None else C.byref(wl), C.byref(h), C.byref(tm), _fp(start), _fp(goal),
+            field_of.ctypes.data_as(i32), fcell.ctypes.data_as(i32), fscene.ctypes.data_as(i32), _fp(wp), nwp.ctypes.data_as(i32),
+            count.ctypes.data_as(i32), status.ctypes.data_as(i32), cost.ctypes.data_as(i32), waits.ctypes.data_as(i32),
+            leave.ctypes.data_as(i32), arrive.ctypes.data_as(i32), None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)),
+            None if fields is None else fields.ctypes.data_as(i32), sweeps.ctypes.data_as(i32)))
+        out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "waits": waits, "leave": leave,
+               "arrive": arrive, "release": R.grid_release(waits, leave, step0, layer_steps), "field_of": field_of,
+               "field_goal_cell": fcell, "field_scene": fscene, "sweeps": sweeps, "n_scenes": int(S)}
+        if occ is not None:
+            out["occupancy"] = occ.astype(bool)
+        if fields is not None:
+            out["fields"] = fields
+        return out
+
     def episode_stats(self, reset=True):
         """Episodes finished by the goal environment since the counters were last reset."""
         st = EpisodeStats()

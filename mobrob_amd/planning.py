@@ -11,7 +11,10 @@ grid_field, grid_path).  Two paths, one meaning, bit for bit:
   * host: `env` is an `EnvWrapper` or an env name: the NumPy rule itself (as `_host_follow` serves following).
 Line-of-sight smoothing (`smooth=True`): of the walk's cells only those a straight leg cannot skip become waypoints
 (goal_rules.grid_los, grid_smooth; device: mobrob_ppo_plan_smooth on the resident fields, k_plan_smooth in k_plan_path's place).
-Static scenes only: moving hazards, team-mates and walls as solid bodies are not planned for."""
+Moving hazards (`hazards=MovingHazards(...)`, `layer_steps=`): the plan is made over time -- layers of occupancy, one
+per action of `layer_steps` steps, a wait where waiting for a hazard to pass is cheapest -- and carries `release` steps and a
+`schedule` for the tracker (goal_rules.grid_plan_time; device: mobrob_ppo_plan_grid_time).  Team-mates, walls as solid bodies and
+smoothing of a time plan are not planned for."""
 from __future__ import annotations
 
 import numpy as np
@@ -26,12 +29,26 @@ class GridPlanner:
     max_waypoints: the K slots of a plan.  smooth: line-of-sight smoothing of every plan (plan(..., smooth=) overrides it per
     call); los_margin: 0 or 1, the cells a smoothed leg keeps clear on either side (1: a leg of two or more moves is as far from
     walls as the unsmoothed path, also on the first leg from an off-centre start; but a walk ALONG blocked cells has no clear
-    cell to see from and keeps every cell as a waypoint -- in cluttered scenes or with a small inflate use 0)."""
+    cell to see from and keeps every cell as a waypoint -- in cluttered scenes or with a small inflate use 0).
+    hazards may be a goal_rules.MovingHazards: every plan is then a time plan.  layer_steps (required then): the steps a robot is
+    given for one move or wait; layers: the actions planned in time before the conservative tail.  A time plan is not smoothed
+    (smooth=True: ValueError) and nothing of it stays resident, so every call computes."""
 
     def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
-                 smooth=False, los_margin=1):
+                 smooth=False, los_margin=1, layer_steps=None, layers=None):
         from .envs.vec_env import DeviceGoalVecEnv
-        rules.plan_scene(walls, hazards)
+        self.timed = isinstance(hazards, rules.MovingHazards)
+        if self.timed:
+            rules.plan_scene_time(walls, hazards)
+            if layer_steps is None:
+                raise ValueError("GridPlanner: moving hazards need layer_steps= (the steps a robot is given for one move)")
+            if smooth:
+                raise ValueError("GridPlanner: smooth=True with moving hazards: smoothing over time is not supported")
+            _, self.layer_steps, self.layers = rules.plan_time_check(0, layer_steps, 64 if layers is None else layers)
+        else:
+            rules.plan_scene(walls, hazards)
+            if layer_steps is not None or layers is not None:
+                raise ValueError("GridPlanner: layer_steps= and layers= belong to moving hazards (a goal_rules.MovingHazards)")
         self.walls, self.hazards, self.K = walls, hazards, int(max_waypoints)
         if self.K < 1:
             raise ValueError("max_waypoints must be >= 1")
@@ -105,21 +122,46 @@ class GridPlanner:
         self._kept = out
         return out
 
-    def plan(self, start, goal, *, grow=False, want_occupancy=False, want_fields=False, smooth=None):
+    def _plan_time(self, start, goal, K, step0, want_occupancy, want_fields):
+        """One time plan: the device call, or the NumPy rule on the host path"""
+        if self.device:
+            return self.engine.plan_grid_time(self.spec, self.walls, self.hazards, start=start, goal=goal, step0=step0,
+                                              layer_steps=self.layer_steps, layers=self.layers, max_waypoints=K,
+                                              want_occupancy=want_occupancy, want_fields=want_fields)
+        return rules.grid_plan_time(self.spec, self.walls, self.hazards, start, goal, K, step0, self.layer_steps, self.layers)
+
+    def plan(self, start, goal, step0=0, *, grow=False, want_occupancy=False, want_fields=False, smooth=None):
         """start, goal [n][P] -> dict: waypoints [n][K][P] float32 (z: the goal's), n_waypoints [n] (= min(count, K)), count [n]
         waypoints of the full path, status [n] (goal_rules.PLANNED 0, UNREACHABLE 1, TRUNCATED 2; UNCONVERGED 3: a device loop hit
         its bound), cost [n] int32 (-1: unreachable), cost_distance [n] float64 = cost * h / 5 (NaN: unreachable), field_of [n],
         field_goal_cell [F], field_scene [F]; with want_occupancy / want_fields also occupancy bool [S][G][G] / fields int32
         [F][G][G].  grow: when a robot's path was truncated, plan again with K = count.max() (this call only).  smooth: None (the
         planner's setting), True or False: line-of-sight smoothing with the planner's los_margin; `smoothed` tells which, `moves`
-        [n] int32 is the number of moves of each robot's walk (None on an unsmoothed plan); `grow` then uses the smoothed count."""
+        [n] int32 is the number of moves of each robot's walk (None on an unsmoothed plan); `grow` then uses the smoothed count.
+        With moving hazards the plan starts at the global step `step0` and the dict gains waits, leave [n][K], arrive [n] (waits at
+        each waypoint's anchor, actions before the move that leaves it, actions of the walk), release [n][K] (the global step until
+        which the robot holds at the anchor, 0: no hold) and `schedule`, a Schedule(release, home=start) for follow_waypoints;
+        occupancy and fields then carry the layer axis, [S][T + 1][G][G] and [F][T + 1][G][G]."""
         start, goal = self._check(start, goal)
         smooth = self.smooth if smooth is None else bool(smooth)
-        out = self._plan(start, goal, self.K, want_occupancy, want_fields, smooth)
-        if grow and np.any(out["status"] == rules.TRUNCATED):
-            out = self._plan(start, goal, int(out["count"].max()), want_occupancy, want_fields, smooth)
+        if self.timed:
+            if smooth:
+                raise ValueError("plan: smooth=True with moving hazards: smoothing over time is not supported")
+            out = self._plan_time(start, goal, self.K, step0, want_occupancy, want_fields)
+            if grow and np.any(out["status"] == rules.TRUNCATED):
+                out = self._plan_time(start, goal, int(out["count"].max()), step0, want_occupancy, want_fields)
+            out["fields_reused"] = False
+        else:
+            if step0 != 0:
+                raise ValueError("plan: step0 belongs to moving hazards; a static plan has no clock")
+            out = self._plan(start, goal, self.K, want_occupancy, want_fields, smooth)
+            if grow and np.any(out["status"] == rules.TRUNCATED):
+                out = self._plan(start, goal, int(out["count"].max()), want_occupancy, want_fields, smooth)
         res = {k: out[k] for k in ("waypoints", "n_waypoints", "count", "status", "cost", "field_of", "field_goal_cell", "field_scene",
                                    "fields_reused")}
+        if self.timed:
+            res.update({k: out[k] for k in ("waits", "leave", "arrive", "release")})
+            res["schedule"] = rules.Schedule(out["release"], home=start)
         res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
         res["smoothed"], res["moves"] = smooth, out.get("moves")
         if want_occupancy:
@@ -130,21 +172,33 @@ class GridPlanner:
             res["sweeps"] = out["sweeps"]
         return res
 
-    def callback(self, goal):
+    def callback(self, goal, horizon=None):
         """The `planner(positions, status, reached)` of waypoints.follow_with_replanning for the goals `goal` [n][P]: every
         STALLED robot is planned again from where it stands -- all robots in one call, so the fields of the unchanged goals are
         reused and only the paths are walked -- and gets {robot: waypoints[:count]}; robots whose plan is not PLANNED (unreachable
         from there, or longer than max_waypoints) are left alone.  The plans are smoothed when the planner is (`smooth=`).
-        `callback.last` holds the latest plan (None before the first)."""
+        `callback.last` holds the latest plan (None before the first).
+        With moving hazards `horizon` is required, the `horizon` of that follow_with_replanning loop: the loop makes call r of the
+        callback after r * horizon steps, so the callback counts its own calls (`callback.calls`) and plans with step0 = r * horizon;
+        a robot then gets (waypoints[:count], release[:count]), which the loop hands to FollowState.replan(..., release=)."""
         from .waypoints import STALLED
         goal = np.asarray(goal, np.float64)
+        if self.timed:
+            if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < 1:
+                raise ValueError(f"callback: moving hazards need horizon= (the replanning loop's, an integer >= 1), got {horizon!r}")
+        elif horizon is not None:
+            raise ValueError("callback: horizon= belongs to moving hazards; a static plan has no clock")
 
         def planner(positions, status, reached):
+            planner.calls += 1
             stalled = np.nonzero(np.asarray(status) == STALLED)[0]
             if stalled.size == 0:
                 return {}
-            plan = self.plan(positions, goal)
+            plan = self.plan(positions, goal, planner.calls * int(horizon)) if self.timed else self.plan(positions, goal)
             planner.last = plan
-            return {int(i): plan["waypoints"][i, :plan["n_waypoints"][i]].copy() for i in stalled if plan["status"][i] == rules.PLANNED}
-        planner.last = None
+            rows = {int(i): plan["waypoints"][i, :plan["n_waypoints"][i]].copy() for i in stalled if plan["status"][i] == rules.PLANNED}
+            if self.timed:
+                rows = {i: (w, plan["release"][i, :len(w)].copy()) for i, w in rows.items()}
+            return rows
+        planner.last, planner.calls = None, 0
         return planner

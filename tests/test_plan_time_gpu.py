@@ -1,0 +1,217 @@
+"""GPU: planning over time on the device (mobrob_ppo_plan_grid_time: k_plan_occupancy_time, k_plan_field_time, k_plan_path_time)
+against the NumPy rule (goal_rules.grid_plan_time), BIT FOR BIT: layer maps, int32 time fields, float32 waypoints compared as
+uint32, counts, statuses, costs, waits, leave, arrive and release.  Nothing here has a tolerance."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from mobrob_amd.envs import goal_rules as R
+from mobrob_amd.envs.goal_rules import GridSpec, MovingHazards, Walls, grid_plan, grid_plan_time
+from mobrob_amd.planning import GridPlanner
+from mobrob_amd.waypoints import follow_with_replanning
+from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots33, serpentine, three_hazards, two_scenes
+from tests.plan_time_scenes import FAR, circling33, gap_case, same_time
+from tests.util import _engine, _env, _snapshot, golden_params, load_golden
+
+pytestmark = pytest.mark.gpu
+KW = dict(pi=(64, 64), vf=(64, 64))
+PLAN = ("waypoints", "n_waypoints", "count", "status", "cost")
+
+
+@pytest.fixture(scope="module")
+def engine():
+    e, _ = _engine("point", KW)
+    yield e
+    e.close()
+
+
+def both(engine, spec, walls, hz, start, goal, K, step0, layer_steps, layers):
+    ref = grid_plan_time(spec, walls, hz, start, goal, K, step0, layer_steps, layers)
+    dev = engine.plan_grid_time(spec, walls, hz, start=start, goal=goal, step0=step0, layer_steps=layer_steps, layers=layers, max_waypoints=K,
+                                want_occupancy=True, want_fields=True)
+    same_time(dev, ref)
+    assert not np.any(dev["status"] == R.UNCONVERGED) and np.all(dev["sweeps"] >= 1)
+    return dev, ref
+
+
+def test_g32_two_scenes_33_robots_circling_hazards_and_a_hold_table(engine):
+    spec, walls, hz, scene, start, goal = circling33()
+    dev, ref = both(engine, spec, walls, hz, start, goal, 4, 0, 10, 8)
+    assert len(ref["field_goal_cell"]) == 14 and {R.PLANNED, R.UNREACHABLE} <= set(ref["status"].tolist())
+    assert np.any(ref["occupancy"][:, 0] != ref["occupancy"][:, 3]) and np.all(ref["layer_number"][:8] == 4) and ref["layer_number"][8] == 24
+    held = circling33(n_frames=7, frame_steps=4, loop=False)[2]
+    dev, ref = both(engine, spec, walls, held, start, goal, 4, 9, 5, 8)                 # step0 > 0; the tail holds the last frame
+    assert ref["layer_first"].tolist() == [2, 3, 4, 6, 6, 6, 6, 6, 6] and ref["layer_number"].tolist() == [2, 2, 2, 1, 1, 1, 1, 1, 1]
+
+
+def test_g128_two_layers_use_the_144_kb_path_and_one_layer_is_enough(engine):
+    rng = np.random.default_rng(5)
+    walls = Walls(SCENE0, radius=0.05)
+    goals = np.array([(1.2, 1.2), (-1.2, -1.2), (1.2, -1.3), (-0.3, 1.3)], np.float32)     # the third lies in the sealed pocket
+    start = rng.uniform(-1.5, 1.5, (9, 2)).astype(np.float32)
+    goal = goals[np.arange(9) % 4]
+    hz = MovingHazards.circling(np.array([[0.0, 0.45], [0.6, 0.6]]), travel=0.3, size=0.1, n_frames=12, dt=2 * np.pi / 12, frame_steps=5, loop=True)
+    dev, ref = both(engine, GridSpec(EXTENT, 128), walls, hz, start, goal, 12, 3, 20, 2)
+    assert np.any(ref["status"] == R.PLANNED) and np.any(ref["status"] == R.UNREACHABLE)
+    both(engine, GridSpec(EXTENT, 32, INFLATE), walls, hz, start, goal, 12, 3, 20, 1)     # T = 1
+
+
+def test_g64_serpentine_with_one_frame_relaxes_the_tail_and_walks_far_past_the_layers(engine):
+    spec, walls, start, goal = serpentine()
+    hz = MovingHazards(np.array([[FAR]]), size=0.1)
+    dev, ref = both(engine, spec, walls, hz, start, goal, 64, 0, 10, 4)
+    static = grid_plan(spec, walls, None, start, goal, 64)
+    print("serpentine sweeps:", dev["sweeps"], "arrive:", dev["arrive"], "count:", dev["count"])
+    same_time(dev, static, PLAN)
+    assert ref["status"][0] == R.PLANNED and dev["arrive"][0] > 2 * 64 > 4 and dev["sweeps"][0] > 2 * 64 and not dev["waits"].any()
+
+
+def test_the_gap_scenario_waits_on_the_device(engine):
+    spec, walls, hz, start, goal = gap_case()
+    dev, _ = both(engine, spec, walls, hz, start, goal, 4, 0, 10, 8)
+    assert dev["cost"][0] == 43 and dev["waits"].tolist() == [[0, 2, 0, 0]] and dev["release"].tolist() == [[0, 40, 0, 0]] and dev["arrive"][0] == 9
+
+
+def test_truncation_and_grow_on_the_planner(engine):
+    spec, walls, hz, scene, start, goal = circling33()
+    env = _env("point", 33)
+    planner = GridPlanner(env, walls=walls, hazards=hz, cells=32, inflate=INFLATE, max_waypoints=2, engine=engine, extent=EXTENT, layer_steps=10, layers=8)
+    ref2 = grid_plan_time(spec, walls, hz, start, goal, 2, 0, 10, 8)
+    got = planner.plan(start, goal, want_occupancy=True, want_fields=True)
+    same_time(got, ref2)
+    assert np.any(got["status"] == R.TRUNCATED) and not got["fields_reused"]
+    grown = planner.plan(start, goal, grow=True)
+    full = grid_plan_time(spec, walls, hz, start, goal, int(ref2["count"].max()), 0, 10, 8)
+    same_time(grown, full, PLAN + ("waits", "leave", "arrive", "release"))
+    assert grown["waypoints"].shape[1] == ref2["count"].max() > 2 and np.array_equal(grown["schedule"].release, full["release"])
+
+
+def test_one_frame_equals_plan_grid_and_resident_static_fields_survive_time_plans(engine):
+    scene, start, goal = robots33()
+    spec, walls, h3 = GridSpec(EXTENT, 32, INFLATE), two_scenes(scene), three_hazards(scene)
+    one = MovingHazards(h3.table[:, None, :, :2].astype(np.float64), size=h3.table[:, :, 2].astype(np.float64), counts=h3.counts, scene=scene)
+    static = engine.plan_grid(spec, walls, h3, start=start, goal=goal, max_waypoints=4, want_occupancy=True, want_fields=True)
+    timed = engine.plan_grid_time(spec, walls, one, start=start, goal=goal, step0=5, layer_steps=3, layers=5, max_waypoints=4,
+                                  want_occupancy=True, want_fields=True)
+    same_time(timed, static, PLAN + ("field_of", "field_goal_cell", "field_scene"))
+    for t in range(6):
+        assert np.array_equal(timed["fields"][:, t], static["fields"]) and np.array_equal(timed["occupancy"][:, t], static["occupancy"])
+    assert not timed["waits"].any()             # (sweep counts are no part of the rule: the in-place relaxation's order is free)
+    moved = start[::-1].copy()                                                   # a reuse round on the static fields, after the time plan
+    again = engine.plan_grid(spec, walls, h3, start=moved, goal=goal, max_waypoints=4, reuse=static)
+    same_time(again, grid_plan(spec, walls, h3, moved, goal, 4), PLAN)
+    assert again["fields_id"] == static["fields_id"]
+
+
+def test_engine_refusals_are_named(engine):
+    from mobrob_amd import _lib
+    spec, walls, hz, scene, start, goal = circling33()
+    kw = dict(start=start, goal=goal, step0=0, layer_steps=10, layers=8, max_waypoints=4)
+    for change, word in ((dict(layers=0), "layers"), (dict(layers=257), "layers"), (dict(layer_steps=0), "layer_steps"), (dict(step0=-1), "step0"),
+                         (dict(step0=2 ** 31 - 90), "fit an int32"), (dict(max_waypoints=0), "max_waypoints")):
+        with pytest.raises(ValueError, match=word):
+            engine.plan_grid_time(spec, walls, hz, **dict(kw, **change))
+    with pytest.raises(TypeError, match="MovingHazards"):
+        engine.plan_grid_time(spec, walls, three_hazards(scene), **kw)
+    with pytest.raises(ValueError, match="agree on the scene"):
+        engine.plan_grid_time(spec, two_scenes((scene + 1) % 2), hz, **kw)
+    n = 64                                                                       # 64 fields x 257 layers x 128 x 128 x 4 bytes
+    far_goals = np.column_stack([np.linspace(-1.5, 1.5, n), np.zeros(n)]).astype(np.float32)
+    with pytest.raises(ValueError, match="exceed the cap"):
+        engine.plan_grid_time(GridSpec(EXTENT, 128), None, gap_case()[2], start=np.zeros((n, 2), np.float32), goal=far_goals, layer_steps=1, layers=256)
+    # the C entry point's own checks, reached with hand-made structs
+    ok = engine.plan_grid_time(spec, walls, hz, **kw)
+    i32, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+
+    def call(time=(0, 10, 8), frames=None, null_hazards=False, **change):
+        sp = _lib.PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_scenes, sp.n_fields = 33, 2, 32, 4, 2, len(ok["field_goal_cell"])
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(spec.extent), float(spec.h), float(spec.inv_h), INFLATE
+        for k, v in change.items():
+            setattr(sp, k, v)
+        tm = _lib.PlanTime()
+        tm.step0, tm.layer_steps, tm.layers = time
+        h, keep = engine._hazards_struct(hz, 33)
+        for k, v in (frames or {}).items():
+            setattr(h, k, v)
+        wl = _lib.WallsC()
+        wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+        wl.boxes, wl.n_walls = walls.table.ctypes.data_as(fp), walls.counts.ctypes.data_as(i32)
+        wl.scene, wl.radius, wl.cost, wl.indicator = walls.scene.ctypes.data_as(i32), walls.radius, walls.cost, 1
+        wp, rows, out = np.zeros((33, 4, 2), np.float32), [np.zeros((33, 4), np.int32) for _ in range(2)], [np.zeros(33, np.int32) for _ in range(5)]
+        return _lib.check(engine.lib.mobrob_ppo_plan_grid_time(
+            engine._h, C.byref(sp), C.byref(wl), None if null_hazards else C.byref(h), C.byref(tm), start.ctypes.data_as(fp), goal.ctypes.data_as(fp),
+            ok["field_of"].ctypes.data_as(i32), ok["field_goal_cell"].ctypes.data_as(i32), ok["field_scene"].ctypes.data_as(i32),
+            wp.ctypes.data_as(fp), *(o.ctypes.data_as(i32) for o in out[:4]), *(o.ctypes.data_as(i32) for o in rows), out[4].ctypes.data_as(i32),
+            None, None, None))
+    assert call() == 0
+    for args, word in ((dict(time=(0, 10, 0)), "layers must lie in 1 .. 256"), (dict(time=(0, 10, 257)), "layers must lie in 1 .. 256"),
+                       (dict(time=(0, 0, 8)), "layer_steps"), (dict(time=(-1, 10, 8)), "step0"), (dict(time=(2 ** 31 - 90, 10, 8)), "fit an int32"),
+                       (dict(null_hazards=True), "null argument"), (dict(reuse_id=7), "reuse_id"), (dict(cells=48), "cells must be 32, 64 or 128"),
+                       (dict(max_waypoints=0), "max_waypoints"), (dict(n_scenes=3), "n_scenes"), (dict(inflate=-1.0), "inflate"),
+                       (dict(frames=dict(n_frames=0)), "n_frames"), (dict(frames=dict(frame_steps=0)), "frame_steps"),
+                       (dict(frames=dict(max_hazards=2000)), "max_hazards")):
+        with pytest.raises(ValueError, match=word):
+            call(**args)
+    same_time(engine.plan_grid_time(spec, walls, hz, **kw), ok, PLAN + ("waits", "leave", "arrive"))
+
+
+def test_replanning_loop_with_a_schedule_equals_the_loop_driven_by_the_host_rule():
+    e, _ = _engine("point", KW)
+    e.set_params(golden_params(load_golden("point")))
+    rng = np.random.default_rng(3)
+    spec, walls, hz, _, _ = gap_case(stay=30)
+    start = rng.uniform(-1.4, 1.4, (32, 2)).astype(np.float32)
+    start[:, 0] = -np.abs(start[:, 0]) - 0.15                                    # left of the thin wall, goals right of it
+    goal = np.tile(np.array([[1.2, 1.2], [1.3, -0.2]], np.float32), (16, 1))
+    kw = dict(walls=walls, hazards=hz, cells=32, inflate=INFLATE, max_waypoints=8, extent=EXTENT, layer_steps=5, layers=16)
+    runs = []
+    for device in (True, False):
+        env = _env("point", 32)
+        planner = GridPlanner(env, engine=e, **kw) if device else GridPlanner("point", **kw)
+        assert planner.device == device
+        first = planner.plan(start, goal)
+        inner, calls = planner.callback(goal, horizon=20), []
+
+        def recording(positions, status, reached, inner=inner, calls=calls):
+            new = inner(positions, status, reached)
+            calls.append(new)
+            return new
+        out = follow_with_replanning(e, env, start, first["waypoints"], recording, horizon=20, rounds=3, leg_steps=7, n_waypoints=first["n_waypoints"],
+                                     seed=1, hazards=hz, walls=walls, schedule=first["schedule"])
+        assert len(calls) == 2 and inner.calls == 2 and out["state"].step0 == 60
+        runs.append((first, calls, out))
+    (fa, ca, oa), (fb, cb, ob) = runs
+    same_time(fa, fb, PLAN + ("waits", "leave", "arrive", "release"))
+    assert fa["waits"].sum() > 0, "robots that reach the gap before step 30 wait for the hazard"
+    assert sum(len(c) for c in ca) > 0, "a leg budget of 7 steps stalls robots: the loop must have replanned some"
+    for new_a, new_b in zip(ca, cb):
+        assert sorted(new_a) == sorted(new_b)
+        for i in new_a:
+            assert new_a[i][0].view(np.uint32).tobytes() == new_b[i][0].view(np.uint32).tobytes() and np.array_equal(new_a[i][1], new_b[i][1])
+    for k in ("arrival", "reached", "status", "steps", "hold_steps", "cost_sum", "round_status"):
+        assert np.array_equal(oa[k], ob[k], equal_nan=oa[k].dtype.kind == "f"), k
+    assert np.array_equal(oa["state"].release, ob["state"].release) and np.array_equal(oa["state"].waypoints, ob["state"].waypoints)
+    e.close()
+
+
+def test_training_untouched_by_time_plan_calls():
+    spec, walls, hz, scene, start, goal = circling33()
+    env_a, env_b = _env("point", 16, tl=40), _env("point", 16, tl=40)
+    ea, _ = _engine("point", KW, seed=7)
+    eb, _ = _engine("point", KW, seed=7)
+    for it in range(2):
+        env_a.collect(ea)
+        env_b.collect(eb)
+        before = _snapshot(eb, stats=False)
+        got = eb.plan_grid_time(spec, walls, hz, start=start, goal=goal, step0=it, layer_steps=10, layers=8, max_waypoints=4, want_fields=True)
+        sa, sb = _snapshot(ea, stats=False), _snapshot(eb, stats=False)
+        for k in sa:
+            assert np.array_equal(sa[k], sb[k]) and np.array_equal(before[k], sb[k]), f"iteration {it}: {k} differs"
+        ea.train()
+        eb.train()
+        assert np.array_equal(ea.get_flat_params(), eb.get_flat_params())
+    assert np.any(got["status"] == R.PLANNED)
+    ea.close()
+    eb.close()
