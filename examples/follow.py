@@ -44,7 +44,9 @@ robot without one as not successful.  With --horizon and --leg-steps a stalled r
 the calls (the planner's callback).  With `--hazard-frames` the plan is made over TIME: a robot is given `--plan-layer-steps` steps
 (default 10) for one move or wait, `--plan-layers` (default 64) of them are planned against the frames in force, and where the
 cheapest plan waits for a hazard to pass the run gets the release steps as its schedule (so --release / --stagger and
---plan-smooth are excluded).  `--plan-smooth` smooths every plan by line
+--plan-smooth are excluded).  With `--team-size` the mates of a team are planned around each other the same way (a time plan, also
+in a static scene): `--plan-reserve` cells are kept around every planned walk, and a line reports the smallest planned team
+clearance beside the run's measured conflicts.  `--plan-smooth` smooths every plan by line
 of sight (fewer waypoints: only the cells a straight leg cannot skip), `--plan-los-margin` (0 or 1, default 1) is the clearance of
 that test in cells; a second line then reports the waypoints and the moves per planned robot.
 """
@@ -75,7 +77,7 @@ def check_chain(max_steps, horizon, leg_steps):
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
-           plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64):
+           plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None):
     calls = check_chain(max_steps, horizon, leg_steps)
     if (goal is None) == (waypoints is None):
         raise ValueError("give --waypoints or --goal, not both")
@@ -111,15 +113,19 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         if goal.shape != (p,) or p < 2:
             raise ValueError(f"--goal must hold {p} coordinates of a robot that moves in x and y, got {goal.size}")
         goals = np.tile(goal, (int(robots), 1))
-        timed = isinstance(hz, MovingHazards)
+        timed = isinstance(hz, MovingHazards) or teams is not None     # with teams the mates are planned around each other, over time
         if timed and (release is not None or stagger):
-            raise ValueError("--release / --stagger exclude --goal with --hazard-frames: the time plan makes the schedule")
+            raise ValueError("--release / --stagger exclude --goal with --hazard-frames or --team-size: the time plan makes the schedule")
         planner = GridPlanner(env, walls=wl, hazards=hz, cells=int(plan_cells), engine=policy, smooth=bool(plan_smooth),
-                              los_margin=int(plan_los_margin), **(dict(layer_steps=int(plan_layer_steps), layers=int(plan_layers)) if timed else {}))
+                              los_margin=int(plan_los_margin), **(dict(layer_steps=int(plan_layer_steps), layers=int(plan_layers)) if timed else {}),
+                              **(dict(teams=teams, reserve=None if plan_reserve is None else int(plan_reserve)) if teams is not None else {}))
         plan = planner.plan(start, goals, grow=True)
         waypoints, n_waypoints, plan_schedule = plan["waypoints"], plan["n_waypoints"], plan.get("schedule")
         replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 else None
         print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
+        if teams is not None:                              # beside the run's measured team conflict steps, further down
+            print(f"planned team clearance: {int(plan['team_clearance'].min())} cells at the least (reserve {planner.reserve}), "
+                  f"{int(plan['team_crossings'].sum())} crossings")
         if plan["smoothed"] and np.any(plan["status"] == 0):
             ok = plan["status"] == 0
             print(f"smoothed plan: {float(np.mean(plan['count'][ok]))} waypoints for {float(np.mean(plan['moves'][ok]))} moves per planned robot")
@@ -201,8 +207,10 @@ def build_parser():
     ap.add_argument("--plan-cells", type=int, default=64, help="grid cells a side of the planner (32, 64, 128)")
     ap.add_argument("--plan-smooth", action="store_true", default=False, help="smooth the planned paths by line of sight")
     ap.add_argument("--plan-los-margin", type=int, default=1, choices=(0, 1), help="cells a smoothed leg keeps clear on either side")
-    ap.add_argument("--plan-layer-steps", type=int, default=10, help="with --hazard-frames: steps a robot is given for one move or wait")
-    ap.add_argument("--plan-layers", type=int, default=64, help="with --hazard-frames: actions planned in time before the tail (1 .. 256)")
+    ap.add_argument("--plan-layer-steps", type=int, default=10, help="with --hazard-frames or --team-size: steps a robot is given for one move or wait")
+    ap.add_argument("--plan-reserve", type=int, default=None,
+                    help="with --goal and --team-size: cells a mate's planned walk reserves around itself, 0 .. 4 (default: ceil(separation / cell))")
+    ap.add_argument("--plan-layers", type=int, default=64, help="with --hazard-frames or --team-size: actions planned in time before the tail (1 .. 256)")
     ap.add_argument("--robots", type=int, default=1)
     ap.add_argument("--max-steps", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
@@ -241,4 +249,4 @@ if __name__ == "__main__":
            walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius,
            goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells,
            plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin, plan_layer_steps=args.plan_layer_steps,
-           plan_layers=args.plan_layers)
+           plan_layers=args.plan_layers, plan_reserve=args.plan_reserve)

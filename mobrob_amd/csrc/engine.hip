@@ -290,6 +290,10 @@ struct mobrob_ppo_engine {
   char* plan_time_buf = nullptr;
   size_t plan_time_bytes = 0;
   bool plan_time_lds_set = false;     // k_plan_field_time's dynamic-LDS attribute is raised once
+  // team plans (mobrob_ppo_plan_grid_team): likewise one allocation of their own and nothing resident
+  char* plan_team_buf = nullptr;
+  size_t plan_team_bytes = 0;
+  bool plan_team_lds_set = false;     // k_plan_team's dynamic-LDS attribute is raised once
 };
 
 namespace {
@@ -1365,6 +1369,7 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   if (e->plan_buf) (void)hipFree(e->plan_buf);
   if (e->plan_dil) (void)hipFree(e->plan_dil);
   if (e->plan_time_buf) (void)hipFree(e->plan_time_buf);
+  if (e->plan_team_buf) (void)hipFree(e->plan_team_buf);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -4409,6 +4414,147 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   if (fields_time_out) HIPC(hipMemcpyAsync(fields_time_out, field_dev, (size_t)F * (T + 1) * cells * 4, hipMemcpyDeviceToHost, e->stream));
   if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, sweeps_dev, (size_t)F * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
+}
+
+// ---- prioritised planning inside a team (mobrob_ppo_plan_grid_team): a mate's planned walk as one more moving obstacle ---------
+int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                              const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t reserve,
+                              const float* start, const float* goal, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
+                              int32_t* status_out, int32_t* cost_out, int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out,
+                              int32_t* sweeps_out, uint16_t* walk_out, int32_t walk_cap, uint8_t* occ_time_out, int32_t* fields_team_out,
+                              int32_t* workgroups_out) {
+  if (!e || !spec || !tm || !start || !goal || !waypoints_out || !n_waypoints_out || !count_out || !status_out || !cost_out || !waits_out ||
+      !leave_out || !arrive_out)
+    return fail(MOBROB_ERR_INVALID, "plan_team: null argument");
+  if (spec->reuse_id != 0) return fail(MOBROB_ERR_INVALID, "plan_team: reuse_id must be 0 (a team plan keeps nothing resident)");
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes;
+  const int cells = G * G, T = tm->layers;
+  mobrob_hazards_t view;
+  HazardIO frames{};
+  if (hzf) frames = hazard_frames_io(hzf, view, nullptr, nullptr);
+  std::vector<int32_t> wall_counts, hz_counts;
+  if (const int rc = plan_check_scenes("plan_team", spec, walls, hzf ? &view : nullptr, hzf ? &frames : nullptr, wall_counts, hz_counts)) return rc;
+  if (S > 65535) return fail(MOBROB_ERR_INVALID, "plan_team: n_scenes = %d above 65535", S);
+  if (spec->n_fields != N) return fail(MOBROB_ERR_INVALID, "plan_team: n_fields = %d must be n_robots = %d (every robot has its own field)", spec->n_fields, N);
+  if (team_size != 1 && team_size != 2 && team_size != 4 && team_size != 8 && team_size != 16)
+    return fail(MOBROB_ERR_INVALID, "plan_team: team_size must be 1, 2, 4, 8 or 16, got %d", team_size);
+  if (N % team_size != 0) return fail(MOBROB_ERR_INVALID, "plan_team: %d robots do not split into teams of %d", N, team_size);
+  if (reserve < 0 || reserve > kPlanReserveMax) return fail(MOBROB_ERR_INVALID, "plan_team: reserve must lie in 0 .. %d, got %d", kPlanReserveMax, reserve);
+  if (walk_out && walk_cap < 1) return fail(MOBROB_ERR_INVALID, "plan_team: walk_cap must be >= 1 with walk_out");
+  if (walk_out && (int64_t)N * walk_cap > INT_MAX) return fail(MOBROB_ERR_INVALID, "plan_team: n_robots * walk_cap must fit an int32");
+  const int32_t* scene = hzf ? hzf->scene : walls ? walls->scene : nullptr;
+  for (int i = 0; i < N; ++i) {
+    for (int j = 0; j < P; ++j)
+      if (!std::isfinite(start[(size_t)i * P + j]) || !std::isfinite(goal[(size_t)i * P + j]))
+        return fail(MOBROB_ERR_INVALID, "plan_team: start or goal of robot %d is not finite", i);
+    if (scene && scene[i] != scene[i - i % team_size])
+      return fail(MOBROB_ERR_INVALID, "plan_team: all members of a team must be in one scene (robot %d is in scene %d, its team's first member in %d)", i,
+                  scene[i], scene[i - i % team_size]);
+  }
+  if (T < 1 || T > kPlanLayersMax) return fail(MOBROB_ERR_INVALID, "plan_team: layers must lie in 1 .. %d, got %d", kPlanLayersMax, T);
+  if (tm->layer_steps < 1) return fail(MOBROB_ERR_INVALID, "plan_team: layer_steps must be >= 1, got %d", tm->layer_steps);
+  if (tm->step0 < 0) return fail(MOBROB_ERR_INVALID, "plan_team: step0 must be >= 0, got %d", tm->step0);
+  if ((int64_t)tm->step0 + (int64_t)(T + 1) * tm->layer_steps > INT_MAX)
+    return fail(MOBROB_ERR_INVALID, "plan_team: step0 + (layers + 1) * layer_steps must fit an int32");
+  const uint64_t field_bytes = (uint64_t)(T + 1) * (uint64_t)cells * 4u;
+  if (field_bytes > MOBROB_PLAN_TIME_MAX_BYTES || (fields_team_out && (uint64_t)N * field_bytes > MOBROB_PLAN_TIME_MAX_BYTES))
+    return fail(MOBROB_ERR_INVALID, "plan_team: time fields of %d x %d x %d x %d x 4 bytes exceed the cap of %u bytes (256 MiB)",
+                fields_team_out ? N : 1, T + 1, G, G, (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
+  const size_t team_lds = plan_team_lds_bytes(G, T);
+  int cus = 0;
+  {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid_time checks k_plan_field_time's
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+    if (team_lds > (size_t)limit)
+      return fail(MOBROB_ERR_INVALID, "plan_team: k_plan_team needs %zu bytes of LDS at %d cells and %d layers, the device allows %d per workgroup",
+                  team_lds, G, T, limit);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device_id) != hipSuccess || cus < 1) cus = 1;
+  }
+  // the workgroups in flight: at most the teams, the compute units, and what the cap on scratch fields allows
+  const int n_teams = N / team_size;
+  const int W = (int)std::min<uint64_t>(std::min(n_teams, cus), MOBROB_PLAN_TIME_MAX_BYTES / field_bytes);
+  std::vector<int32_t> lfirst(T + 1, 0), lnumber(T + 1, 1);   // without frames: a static scene, its own single frame in every layer
+  if (hzf) plan_layer_frames(hzf, tm, lfirst, lnumber);
+  const int Mw = walls ? walls->max_walls : 0, Mh = hzf ? hzf->max_hazards : 0, NF = hzf ? hzf->n_frames : 1;
+  if (!hzf) hz_counts.assign(S, 0);
+  const size_t hz_floats = (size_t)S * NF * Mh * 3;
+  if ((int64_t)N * (6 + 2 * (int64_t)K + (int64_t)K * P) > INT_MAX)
+    return fail(MOBROB_ERR_INVALID, "plan_team: n_robots * (6 + 2 * max_waypoints + max_waypoints * pos_dim) must fit an int32");
+  const size_t wg_ints = plan_team_wg_ints(G, T), n_in = (size_t)2 * N * P + N, n_out = (size_t)N * (6 + 2 * K + K * P);
+  EvalCarve call;
+  const size_t o_occ = call.add((size_t)S * (T + 1) * cells), o_args = call.add(sizeof(PlanTeamArgs)), o_wg = call.add((size_t)W * wg_ints * 4),
+               o_in = call.add(n_in * 4), o_out = call.add(n_out * 4), o_field = call.add(fields_team_out ? (size_t)N * field_bytes : 0),
+               o_walk = call.add(walk_out ? (size_t)N * walk_cap * 2 : 0), o_lfirst = call.add((size_t)(T + 1) * 4),
+               o_lnumber = call.add((size_t)(T + 1) * 4), o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4),
+               o_nwall = call.add((size_t)S * 4), o_hz = call.add(std::max<size_t>(hz_floats, 1) * 4), o_nhz = call.add((size_t)S * 4);
+  if (const int rc = grow_plan_buf(e, e->plan_team_buf, e->plan_team_bytes, call.total)) return rc;
+  const auto mine = [&](size_t off) { return e->plan_team_buf + off; };
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(mine(o_occ));
+  int* lfirst_dev = reinterpret_cast<int*>(mine(o_lfirst));
+  int* lnumber_dev = reinterpret_cast<int*>(mine(o_lnumber));
+  PlanOccTimeArgs oa{};
+  oa.g = PlanGrid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  oa.Mw = Mw; oa.Mh = Mh; oa.F = NF; oa.T = T; oa.layer_first = lfirst_dev; oa.layer_number = lnumber_dev; oa.occ = occ_dev;
+  if (walls) {
+    float* box_dev = reinterpret_cast<float*>(mine(o_box));
+    int* cnt_dev = reinterpret_cast<int*>(mine(o_nwall));
+    if ((size_t)S * Mw) HIPC(hipMemcpyAsync(box_dev, walls->boxes, (size_t)S * Mw * 16, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(cnt_dev, wall_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+    oa.boxes = box_dev; oa.nwall = cnt_dev;
+  }
+  float* hz_dev = reinterpret_cast<float*>(mine(o_hz));
+  int* nhz_dev = reinterpret_cast<int*>(mine(o_nhz));
+  if (hz_floats) HIPC(hipMemcpyAsync(hz_dev, hzf->hazards, hz_floats * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(nhz_dev, hz_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  oa.hz = hz_dev; oa.nhz = nhz_dev;
+  HIPC(hipMemcpyAsync(lfirst_dev, lfirst.data(), (size_t)(T + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(lnumber_dev, lnumber.data(), (size_t)(T + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  // the base layers: the time plan's own kernel, launched as it is (a static scene: one frame)
+  hipLaunchKernelGGL(k_plan_occupancy_time, dim3(cells / 256, T + 1, S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
+  HIPC(hipGetLastError());
+  if (!e->plan_team_lds_set) {   // up to 152 KB at 128 cells and 256 layers: above the 64 KB a kernel gets without asking
+    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_team), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)plan_team_lds_bytes(128, kPlanLayersMax)));
+    e->plan_team_lds_set = true;
+  }
+  // k_plan_team reads its arguments from device memory (kernels_plan.h says why), one block each for inputs, outputs and scratch
+  PlanTeamArgs ta{};
+  ta.g = oa.g; ta.N = N; ta.K = K; ta.P = P; ta.T = T; ta.size = team_size; ta.reserve = reserve; ta.n_teams = n_teams;
+  ta.has_scene = scene ? 1 : 0;
+  ta.walk_cap = walk_out ? walk_cap : 0;
+  float* in_dev = reinterpret_cast<float*>(mine(o_in));
+  int* out_dev = reinterpret_cast<int*>(mine(o_out));
+  ta.in = in_dev; ta.occ = occ_dev; ta.wg = reinterpret_cast<int*>(mine(o_wg)); ta.out = out_dev;
+  ta.fields = fields_team_out ? reinterpret_cast<int*>(mine(o_field)) : nullptr;
+  ta.walk = walk_out ? reinterpret_cast<unsigned short*>(mine(o_walk)) : nullptr;
+  PlanTeamArgs* args_dev = reinterpret_cast<PlanTeamArgs*>(mine(o_args));
+  HIPC(hipMemcpyAsync(args_dev, &ta, sizeof(ta), hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(in_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(in_dev + (size_t)N * P, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  if (scene) HIPC(hipMemcpyAsync(in_dev + (size_t)2 * N * P, scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemsetAsync(out_dev + (size_t)6 * N, 0, (n_out - (size_t)6 * N) * 4, e->stream));   // waits, leave, waypoints
+  if (ta.walk) HIPC(hipMemsetAsync(ta.walk, 0, (size_t)N * walk_cap * 2, e->stream));
+  hipLaunchKernelGGL(k_plan_team, dim3(W), dim3(kPlanFieldThreads), team_lds, e->stream, static_cast<const PlanTeamArgs*>(args_dev));
+  HIPC(hipGetLastError());
+  const auto back = [&](void* dst, size_t off_ints, size_t n_ints) {
+    return hipMemcpyAsync(dst, out_dev + off_ints, n_ints * 4, hipMemcpyDeviceToHost, e->stream);
+  };
+  const size_t n1 = (size_t)N;
+  HIPC(back(n_waypoints_out, 0, n1));
+  HIPC(back(count_out, n1, n1));
+  HIPC(back(status_out, 2 * n1, n1));
+  HIPC(back(cost_out, 3 * n1, n1));
+  HIPC(back(arrive_out, 4 * n1, n1));
+  if (sweeps_out) HIPC(back(sweeps_out, 5 * n1, n1));
+  HIPC(back(waits_out, 6 * n1, n1 * K));
+  HIPC(back(leave_out, 6 * n1 + n1 * K, n1 * K));
+  HIPC(back(waypoints_out, 6 * n1 + 2 * n1 * K, n1 * K * P));
+  if (walk_out) HIPC(hipMemcpyAsync(walk_out, ta.walk, (size_t)N * walk_cap * 2, hipMemcpyDeviceToHost, e->stream));
+  if (occ_time_out) HIPC(hipMemcpyAsync(occ_time_out, occ_dev, (size_t)S * (T + 1) * cells, hipMemcpyDeviceToHost, e->stream));
+  if (fields_team_out) HIPC(hipMemcpyAsync(fields_team_out, ta.fields, (size_t)N * field_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  if (workgroups_out) *workgroups_out = W;
   return MOBROB_OK;
 }
 

@@ -625,4 +625,308 @@ __global__ __launch_bounds__(64) void k_plan_path_time(PlanPathTimeArgs s) {
   s.arrive[n] = acts;
 }
 
+// ---- prioritised planning inside a team (mobrob_ppo_plan_grid_team; the rule: goal_rules.grid_reserve / grid_team_field /
+// grid_walk_team / grid_plan_team) ------------------------------------------------------------------------------------------------
+// A mate's planned walk is one more moving obstacle in the layers.  The member with team-local index m plans after the members
+// 0 .. m - 1 on the map occ_t = base_t OR res_t: layer t < T reserves every cell within Chebyshev distance r of an earlier member's
+// c[t] or c[t + 1], the tail layer T every cell within r of its c[a], a >= min(T, A).  A member without a walk (unreachable, or a
+// loop bound hit) reserves its start cell in every layer.  The field is k_plan_field_time's with one change: the goal cell is
+// terminal only where it is free in occ_t and in every later layer; the walk ends where d_t[c] == 0.
+constexpr int kPlanTeamMax = 16;     // members of a team
+constexpr int kPlanReserveMax = 4;   // r
+
+struct PlanTeamArgs {
+  PlanGrid g;
+  int N, K, P, T, size, reserve, n_teams;
+  int has_scene;              // 0: every robot in scene 0 (all members of a team: one scene)
+  int walk_cap;               // cells per robot in `walk`
+  const float* in;            // the robots: start [N][P] | goal [N][P] | scene [N] (int)
+  const unsigned char* occ;   // [S][T + 1][G][G] the base layers
+  int* wg;                    // per workgroup, plan_team_wg_ints(G, T) ints: the member's field [T + 1][G][G] (-1 blocked, kPlanInf free
+                              // without a path) | the tail cells of the member that walked last [G * G + 4], packed iy * 128 + ix | the
+                              // tail reservations of the team's earlier members, stamped, one byte a cell [G * G]
+  int* out;                   // n_waypoints | count | status | cost | arrive | sweeps, [N] each | waits [N][K] | leave [N][K] | waypoints
+                              // [N][K][P] (float); from waits on zeroed by the host
+  int* fields;                // [N][T + 1][G][G] out or null: the fields as the rule states them (-1 blocked or unreachable)
+  unsigned short* walk;       // [N][walk_cap] out or null: the cells c[0 .. min(A, walk_cap - 1)] of the walk, packed
+};
+// one block of arguments, outputs and scratch each, addressed by offset: a pointer per array would not fit the scalar registers
+__host__ __device__ inline size_t plan_team_wg_ints(int G, int T) { return (size_t)(T + 1) * G * G + (size_t)G * G + 4 + (size_t)G * G / 4; }
+
+// LDS bytes of k_plan_team: k_plan_field_time's two layers and one byte per cell, then the walk cells c[0 .. T] of the team's
+// members (2 bytes a cell) and two words the walking thread hands over
+inline size_t plan_team_lds_bytes(int G, int T) {
+  return (size_t)G * G * (2 * sizeof(int) + 1) + (size_t)kPlanTeamMax * (T + 1) * sizeof(unsigned short) + 16;
+}
+
+// plan_moves on a field of k_plan_team's scratch: a cell is blocked where d < 0
+__device__ __forceinline__ unsigned plan_moves_field(const int* d, int G, int ix, int iy) {
+  unsigned free4 = 0;   // E, N, W, S
+  if (ix + 1 < G && d[iy * G + ix + 1] >= 0) free4 |= 1u;
+  if (iy + 1 < G && d[(iy + 1) * G + ix] >= 0) free4 |= 2u;
+  if (ix > 0 && d[iy * G + ix - 1] >= 0) free4 |= 4u;
+  if (iy > 0 && d[(iy - 1) * G + ix] >= 0) free4 |= 8u;
+  unsigned m = free4;
+  if ((free4 & 3u) == 3u && d[(iy + 1) * G + ix + 1] >= 0) m |= 16u;     // NE: E and N free
+  if ((free4 & 6u) == 6u && d[(iy + 1) * G + ix - 1] >= 0) m |= 32u;     // NW: N and W
+  if ((free4 & 12u) == 12u && d[(iy - 1) * G + ix - 1] >= 0) m |= 64u;   // SW: W and S
+  if ((free4 & 9u) == 9u && d[(iy - 1) * G + ix + 1] >= 0) m |= 128u;    // SE: S and E
+  return m;
+}
+
+// the per-workgroup block of PlanTeamArgs::wg
+__device__ __forceinline__ int* plan_team_wg(const PlanTeamArgs& a) { return a.wg + blockIdx.x * (int)plan_team_wg_ints(a.g.G, a.T); }
+
+// One member's field, by the whole workgroup -> the sweeps of the tail's relaxation (-1: bound hit).  A function of its own, not
+// inlined, and so is plan_team_walk: the wave-uniform values of a phase then live in scalar registers only while the phase runs
+// (inlined, the three phases' loop-invariant values overflowed the scalar file).  Both read the arguments from memory.
+__device__ __noinline__ int plan_team_field(const PlanTeamArgs* __restrict__ ap, int n, int m, int* lds) {
+  const PlanTeamArgs& a = *ap;
+  const int G = a.g.G, T = a.T, r = a.reserve, cells = G * G, tid = threadIdx.x;
+  const int gs = 31 - __clz(G), gm = G - 1;   // G is a power of two: cell c is (c & gm, c >> gs)
+  struct { int* lds; } f{lds};
+  const int scene = a.has_scene ? reinterpret_cast<const int*>(a.in + 2 * a.N * a.P)[n] : 0;
+  const float* gl = a.in + (a.N + n) * a.P;
+  const int goal = plan_cell(a.g, gl[1]) * G + plan_cell(a.g, gl[0]);
+  int* d = f.lds;
+  int* e = f.lds + cells;
+  unsigned char* moves = reinterpret_cast<unsigned char*>(f.lds + 2 * cells);
+  const unsigned short* wcell = reinterpret_cast<const unsigned short*>(moves + cells);
+  const unsigned char* occ_scene = a.occ + (size_t)scene * (T + 1) * cells;
+  int* field = plan_team_wg(a);   // (the host's checks: every offset but the base layers' fits an int)
+  const unsigned char* tres = reinterpret_cast<const unsigned char*>(field + (T + 1) * cells + cells + 4);
+  int* out = a.fields ? a.fields + n * (T + 1) * cells : nullptr;
+  // the tail: its map into e (a thread reads the stamps of its own cells' bytes only after the fence and barrier that follow
+  // the stamping), the moves, the in-place relaxation
+  const unsigned char* occ_T = occ_scene + (size_t)T * cells;
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) e[c] = (occ_T[c] | tres[c]) ? 1 : 0;
+  __syncthreads();
+  bool terminal = e[goal] == 0;
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    const bool blocked = e[c] != 0;
+    moves[c] = blocked ? 0 : (unsigned char)plan_moves(e, G, c & gm, c >> gs);
+    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
+  }
+  __syncthreads();
+  int sweeps = -1;
+  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
+    int changed = 0;
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      const unsigned mv = moves[c];
+      if (mv == 0 || c == goal) continue;
+      const int cur = d[c];
+      int best = cur;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (mv & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
+      if (best < cur) { d[c] = best; changed = 1; }
+    }
+    __syncthreads();   // this sweep's stores before the next sweep's loads
+    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
+  }
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    field[T * cells + c] = e[c] ? -1 : d[c];
+    if (out) out[T * cells + c] = d[c] >= kPlanInf ? -1 : d[c];
+  }
+  int* nxt = d;   // layer t + 1
+  int* cur = e;   // layer t
+  for (int t = T - 1; t >= 0; --t) {
+    const unsigned char* occ_t = occ_scene + (size_t)t * cells;
+    // layer t's map into `moves` (the tail's moves are done with): the base layer, or within r of an earlier member's c[t], c[t + 1]
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      bool blocked = occ_t[c] != 0;
+      const int cx = c & gm, cy = c >> gs;
+      for (int j = 0; j < m && !blocked; ++j) {
+        const int w0 = wcell[j * (T + 1) + t], w1 = wcell[j * (T + 1) + t + 1];
+        blocked = (abs(cx - (w0 & 127)) <= r && abs(cy - (w0 >> 7)) <= r) || (abs(cx - (w1 & 127)) <= r && abs(cy - (w1 >> 7)) <= r);
+      }
+      moves[c] = blocked ? 1 : 0;
+    }
+    __syncthreads();   // the map before its readers; also e's last readers (the tail's write-out) before the first layer's stores
+    terminal = terminal && moves[goal] == 0;
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      int best = kPlanInf;
+      const bool blocked = moves[c] != 0;
+      if (!blocked) {
+        if (c == goal && terminal) {
+          best = 0;
+        } else {
+          const unsigned mv = plan_moves(moves, G, c & gm, c >> gs);
+          best = nxt[c] + kPlanWait;
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            if (mv & (1u << k)) best = min(best, nxt[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
+          best = min(best, kPlanInf);   // kPlanInf + a cost: still "none"
+        }
+      }
+      cur[c] = best;
+      field[t * cells + c] = blocked ? -1 : best;
+      if (out) out[t * cells + c] = best >= kPlanInf ? -1 : best;
+    }
+    __syncthreads();
+    int* const swap = nxt; nxt = cur; cur = swap;
+  }
+  return sweeps;
+}
+
+// The walk of one member, by one thread: k_plan_path_time's loop on this workgroup's scratch field, ending where d_t[c] == 0.  It leaves
+// the member's outputs, c[0 .. T] in `mine` (LDS), the tail cells in `tail` and their number in hand[0].  A function of its own, not
+// inlined: its wave-uniform state would otherwise share the scalar registers with the loop-invariant values of the field loops.
+__device__ __noinline__ void plan_team_walk(const PlanTeamArgs* __restrict__ ap, int n, int m, int sweeps, int* lds) {
+  const PlanTeamArgs& a = *ap;
+  const int G = a.g.G, T = a.T, cells = G * G, P = a.P, K = a.K;
+  const int* field = plan_team_wg(a);
+  int* tail = plan_team_wg(a) + (T + 1) * cells;
+  unsigned short* mine = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(lds + 2 * cells) + cells) + m * (T + 1);
+  int* hand = reinterpret_cast<int*>(mine + (kPlanTeamMax - m) * (T + 1));
+  const float* st = a.in + n * P;
+  const float* gl = a.in + (a.N + n) * P;
+    int* waits = a.out + 6 * a.N + n * K;
+    int* leave = waits + a.N * K;
+    float* wp = reinterpret_cast<float*>(a.out + 6 * a.N + 2 * a.N * K) + n * K * P;
+    unsigned short* wout = a.walk ? a.walk + n * a.walk_cap : nullptr;
+    const int sx = plan_cell(a.g, st[0]), sy = plan_cell(a.g, st[1]);
+    int ix = sx, iy = sy;
+    int count = 0, status = kPlanned, cost = -1, acts = 0, ntail = 0;
+    const int d0 = field[iy * G + ix];
+    if (sweeps < 0) {
+      status = kPlanUnconverged;
+    } else if (d0 < 0 || d0 >= kPlanInf) {
+      status = kPlanUnreachable;
+    } else {
+      cost = d0;
+      int prev = -1, waited = 0;
+      mine[0] = (unsigned short)(iy * 128 + ix);
+      if (wout) wout[0] = mine[0];
+      for (;;) {
+        const int t = min(acts, T);
+        const int* dt = field + t * cells;
+        const int dc = dt[iy * G + ix];
+        if (dc == 0) break;
+        if (acts >= T + cells) { status = kPlanUnconverged; break; }
+        const int* dn = field + min(t + 1, T) * cells;
+        const unsigned mv = plan_moves_field(dt, G, ix, iy);
+        int dir = -1;
+        for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
+          if (!(mv & (1u << k))) continue;
+          const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
+          if (v >= 0 && v < kPlanInf && v + (k < 4 ? 5 : 7) == dc) dir = k;
+        }
+        if (prev >= 0 && (mv & (1u << prev))) {   // the previous move first
+          const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
+          if (v >= 0 && v < kPlanInf && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
+        }
+        if (dir < 0 && t < T) {   // the wait last
+          const int v = dn[iy * G + ix];
+          if (v >= 0 && v < kPlanInf && v + kPlanWait == dc) dir = 8;
+        }
+        if (dir < 0) { status = kPlanUnconverged; break; }   // not a team field of these layers: cannot happen after a converged tail
+        ++acts;
+        if (dir == 8) {
+          ++waited;
+        } else {
+          const bool turned = prev >= 0 && (dir != prev || waited > 0);
+          if (turned) {
+            if (count < K) {
+              wp[count * P] = plan_centre(a.g, ix);
+              wp[count * P + 1] = plan_centre(a.g, iy);
+              if (P == 3) wp[count * P + 2] = gl[2];
+            }
+            ++count;
+          }
+          if ((prev < 0 || turned) && count < K) {   // this move leaves the anchor of waypoint `count`
+            waits[count] = waited;
+            leave[count] = acts - 1;
+          }
+          ix += plan_dx(dir); iy += plan_dy(dir);
+          prev = dir;
+          waited = 0;
+        }
+        const unsigned short cell = (unsigned short)(iy * 128 + ix);   // c[acts]
+        if (acts <= T) mine[acts] = cell;
+        if (acts >= T) tail[ntail++] = cell;                             // at most cells + 1 of them (room for cells + 4): acts <= T + cells
+        if (wout && acts < a.walk_cap) wout[acts] = cell;
+      }
+      if (status == kPlanned) {
+        if (count < K)
+          for (int j = 0; j < P; ++j) wp[count * P + j] = gl[j];
+        ++count;
+        if (count > K) status = kPlanTruncated;
+      }
+    }
+    if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
+      for (int j = 0; j < min(count, K) * P; ++j) wp[j] = 0.f;
+      for (int j = 0; j < K; ++j) { waits[j] = 0; leave[j] = 0; }
+      count = 0;
+      cost = -1;
+      acts = 0;
+    }
+    if (status == kPlanUnreachable || status == kPlanUnconverged) {   // parked: the start cell, in every layer
+      ix = sx; iy = sy;
+      mine[0] = (unsigned short)(iy * 128 + ix);
+      if (wout) wout[0] = mine[0];
+      ntail = 0;
+    }
+    const unsigned short last = (unsigned short)(iy * 128 + ix);
+    for (int t = acts + 1; t <= T; ++t) mine[t] = last;   // c[a] = c[A] beyond the walk
+    if (acts < T) { tail[0] = last; ntail = 1; }
+    hand[0] = ntail;
+    int* o = a.out + n;
+    o[0] = min(count, K);
+    o[a.N] = count;
+    o[2 * a.N] = status;
+    o[3 * a.N] = cost;
+    o[4 * a.N] = acts;
+    o[5 * a.N] = sweeps;
+}
+
+// A team is sequential inside and parallel outside: one workgroup of 1024 threads takes one team at a time, a fixed number of
+// workgroups loops over the teams.  Per member: the tail's map (base OR stamped reservations) and k_plan_field_time's in-place
+// relaxation on it; T Jacobi steps, each on a layer map built in LDS from the base layer and a Chebyshev test against the earlier
+// members' c[t] and c[t + 1]; every layer is written to this workgroup's scratch field.  Thread 0 then walks that field
+// (k_plan_path_time's walk, ending where d_t[c] == 0) and leaves the member's c[0 .. T] in LDS and its tail cells in global memory;
+// all threads stamp the tail cells.  Every hand-off through global memory -- the field to the walking thread, the tail cells
+// and the stamped map to the whole workgroup -- is a workgroup-scope fence and then the barrier.  Bounds: G * G sweeps, T + G * G
+// actions: status 3 and zeroed outputs beyond, the member then reserves its start cell.
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team(const PlanTeamArgs* __restrict__ ap) {
+  extern __shared__ __attribute__((aligned(16))) int plan_team_lds[];
+  const int G = ap->g.G, T = ap->T, cells = G * G, tid = threadIdx.x, r = ap->reserve, size = ap->size, n_teams = ap->n_teams;
+  // LDS: d | e | moves (a byte a cell) | wcell [kPlanTeamMax][T + 1] (2 bytes a cell) | hand (32 (T + 1) bytes on: a word boundary)
+  const int* hand = reinterpret_cast<const int*>(reinterpret_cast<unsigned char*>(plan_team_lds + 2 * cells) + cells + kPlanTeamMax * (T + 1) * 2);
+  int* tail = plan_team_wg(*ap) + (T + 1) * cells;
+  unsigned char* tres = reinterpret_cast<unsigned char*>(tail + cells + 4);
+  for (int team = blockIdx.x; team < n_teams; team += gridDim.x) {
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) tres[c] = 0;   // (its last readers and writers: behind the barrier below)
+    for (int m = 0; m < size; ++m) {
+      const int n = team * size + m;
+      const int sweeps = plan_team_field(ap, n, m, plan_team_lds);
+      // the field, written by every thread to global memory, to the one thread that walks it: a fence, then the barrier
+      __threadfence_block();
+      __syncthreads();
+      if (tid == 0) plan_team_walk(ap, n, m, sweeps, plan_team_lds);
+      // the tail cells, written by thread 0 to global memory, to every thread: a fence, then the barrier (c[0 .. T] and the count
+      // are in LDS, which the barrier orders)
+      __threadfence_block();
+      __syncthreads();
+      const int ntail = hand[0];
+#pragma unroll 1
+      for (int i = tid; i < ntail; i += kPlanFieldThreads) {
+        const int cx = tail[i] & 127, cy = tail[i] >> 7;
+        for (int y = max(cy - r, 0); y <= min(cy + r, G - 1); ++y)
+          for (int x = max(cx - r, 0); x <= min(cx + r, G - 1); ++x) tres[y * G + x] = 1;
+      }
+      // the stamps, bytes in global memory written by any thread, before the next member's tail map (and the next team's zeroes)
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace mobrob

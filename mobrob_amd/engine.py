@@ -810,6 +810,94 @@ class PPOEngine:
             out["fields"] = fields
         return out
 
+    def plan_grid_team(self, spec, walls=None, hazards=None, *, teams, reserve, start, goal, step0=0, layer_steps, layers, max_waypoints=16,
+                       want_occupancy=False, want_fields=False, want_walks=False, clearance=True):
+        """Waypoints and release steps for robots in teams, planned around each other (mobrob_ppo_plan_grid_team; the rule:
+        goal_rules.grid_plan_team, reproduced bit for bit): inside a team the members plan in index order and every member's walk is
+        reserved, `reserve` cells wide, in the layers of the members after it.  hazards: None, a goal_rules.Hazards (a static scene
+        is handed down as one frame) or a MovingHazards; teams: a goal_rules.Teams (its size is used).  Returns plan_grid_time's
+        dict per robot (field_of is the identity, sweeps [n]; nothing stays resident) plus team_clearance and team_crossings
+        [n_teams] int32 (goal_rules.grid_team_clearance_cells of the walks the device reports, all pairs and teams at once;
+        clearance=False leaves both out, and the call is then the device call alone), workgroups (the workgroups k_plan_team was
+        launched with), and on request walks (per robot the cells of its walk, as lists), occupancy bool [S][T + 1][G][G] (the base
+        layers) and fields int32 [n][T + 1][G][G].  The walks come back in T + 1 + 2 G cells a robot; only where a walk is longer
+        (a maze) is the call made a second time with room for the longest."""
+        from ._lib import PlanSpec, PlanTime, WallsC
+        from .envs import goal_rules as R
+        if not isinstance(spec, R.GridSpec):
+            raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.GridSpec, not {type(spec).__name__}")
+        start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
+        if goal.ndim != 2 or goal.shape[0] < 1 or goal.shape[1] not in (2, 3) or start.shape != goal.shape:
+            raise ValueError(f"plan_team: start and goal must both be [n_robots, 2 or 3], got shapes {start.shape} and {goal.shape}")
+        if not (np.all(np.isfinite(start)) and np.all(np.isfinite(goal))):
+            raise ValueError("plan_team: start and goal must be finite")
+        n, P = goal.shape
+        K = int(max_waypoints)
+        if K < 1:
+            raise ValueError("plan_team: max_waypoints must be >= 1")
+        moving = isinstance(hazards, R.MovingHazards)
+        S, scene = R.plan_scene_time(walls, hazards) if moving else R.plan_scene(walls, hazards)
+        step0, layer_steps, T = R.plan_time_check(step0, layer_steps, layers)
+        for sc in (walls, hazards):
+            if sc is not None:
+                sc.check_robots(n)
+        size, r = R.plan_team_check(teams, reserve, n, scene)
+        if hazards is not None and not moving:                             # a static scene: its own single frame
+            hazards = R.MovingHazards(hazards.table[:, None, :, :2].astype(np.float64), size=hazards.table[:, :, 2].astype(np.float64),
+                                      cost=hazards.cost, indicator=hazards.indicator, counts=hazards.counts, scene=hazards.scene)
+        start, goal = np.ascontiguousarray(start, F32), np.ascontiguousarray(goal, F32)
+        G = spec.cells
+        i32 = C.POINTER(C.c_int32)
+        sp = PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_scenes, sp.n_fields = n, P, G, K, S, n
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(spec.extent), float(spec.h), float(spec.inv_h), float(spec.inflate_for(walls))
+        sp.reuse_id = 0
+        tm = PlanTime()
+        tm.step0, tm.layer_steps, tm.layers = step0, layer_steps, T
+        wl = None
+        if walls is not None:
+            wl = WallsC()
+            wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+            wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
+            wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
+            wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
+        h, _keep = self._hazards_struct(hazards, n) if hazards is not None else (None, None)
+        one = (T + 1) * G * G * 4
+        big = one > R.PLAN_TIME_MAX_BYTES or n * one > R.PLAN_TIME_MAX_BYTES     # refused by name below; nothing that large is allocated here
+        fields = np.zeros((n, T + 1, G, G) if not big else (1,), np.int32) if want_fields else None
+        occ = np.zeros((S, T + 1, G, G), np.uint8) if want_occupancy else None
+        walk_cap = T + 1 + 2 * G
+        while True:                                                        # a second call only where a walk is longer than walk_cap
+            wp = np.zeros((n, K, P), F32)
+            waits, leave = np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
+            nwp, count, status, cost, arrive, sweeps = (np.zeros(n, np.int32) for _ in range(6))
+            walk = np.zeros((n, walk_cap), np.uint16)
+            wgs = C.c_int32(0)
+            check(self.lib.mobrob_ppo_plan_grid_team(
+                self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None else C.byref(h), C.byref(tm), size, r, _fp(start),
+                _fp(goal), _fp(wp), nwp.ctypes.data_as(i32), count.ctypes.data_as(i32), status.ctypes.data_as(i32), cost.ctypes.data_as(i32),
+                waits.ctypes.data_as(i32), leave.ctypes.data_as(i32), arrive.ctypes.data_as(i32), sweeps.ctypes.data_as(i32),
+                walk.ctypes.data_as(C.POINTER(C.c_uint16)), walk_cap, None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)),
+                None if fields is None else fields.ctypes.data_as(i32), C.byref(wgs)))
+            if int(arrive.max()) + 1 <= walk_cap:
+                break
+            walk_cap = int(arrive.max()) + 1
+        cells = np.stack([walk & 127, walk >> 7], axis=-1)
+        out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "waits": waits, "leave": leave,
+               "arrive": arrive, "release": R.grid_release(waits, leave, step0, layer_steps), "field_of": np.arange(n, dtype=np.int32),
+               "field_goal_cell": (lambda gx, gy: (gy * G + gx).astype(np.int32))(*spec.cell_of(goal[:, :2])),
+               "field_scene": np.zeros(n, np.int32) if scene is None else np.asarray(scene, np.int32).copy(), "sweeps": sweeps,
+               "n_scenes": int(S), "workgroups": int(wgs.value)}
+        if clearance:
+            out["team_clearance"], out["team_crossings"] = R.grid_team_clearance_cells(cells, arrive.astype(np.int64) + 1, size, T)
+        if want_walks:
+            out["walks"] = [[(int(x), int(y)) for x, y in cells[i, :int(arrive[i]) + 1]] for i in range(n)]
+        if occ is not None:
+            out["occupancy"] = occ.astype(bool)
+        if fields is not None:
+            out["fields"] = fields
+        return out
+
     def episode_stats(self, reset=True):
         """Episodes finished by the goal environment since the counters were last reset."""
         st = EpisodeStats()

@@ -1192,3 +1192,258 @@ def grid_plan_time(spec, walls, hazards, start, goal, K, step0=0, layer_steps=1,
             "waits": waits, "leave": leave, "arrive": arrive, "release": grid_release(waits, leave, step0, layer_steps),
             "occupancy": occ, "fields": fields, "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene,
             "layer_first": first, "layer_number": number}
+
+
+# ---- prioritised planning inside a team: a mate's planned walk is one more moving obstacle in the layers.  This
+# project's own rule, integers but for the occupancy's floats; the device (csrc/kernels_plan.h: k_plan_team) is held to it bit for
+# bit.  The member with team-local index m plans after the members 0 .. m - 1 on occ_t = base_t OR res_t, res the union of their
+# reservations; teams never see each other.  Prioritised planning is INCOMPLETE: a member never yields to a later one.
+PLAN_RESERVE_MAX = 4
+PLAN_NO_PAIR = 2 ** 31 - 1        # the clearance of a team without a pair of mates (size 1)
+
+
+def plan_team_check(teams, reserve, n, scene=None):
+    """-> (size, reserve) as ints, or ValueError: teams a Teams whose size divides n, reserve an integer in 0 .. PLAN_RESERVE_MAX,
+    all members of a team in one scene"""
+    if not isinstance(teams, Teams):
+        raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
+    teams.check_robots(n)
+    if isinstance(reserve, bool) or not isinstance(reserve, (int, np.integer)) or not 0 <= int(reserve) <= PLAN_RESERVE_MAX:
+        raise ValueError(f"plan_team: reserve must be an integer in 0 .. {PLAN_RESERVE_MAX}, got {reserve!r}")
+    if scene is not None:
+        sc = np.asarray(scene).reshape(-1, teams.size)
+        if np.any(sc != sc[:, :1]):
+            raise ValueError(f"plan_team: all members of a team must be in one scene (team {int(np.nonzero(np.any(sc != sc[:, :1], axis=1))[0][0])} is not)")
+    return teams.size, int(reserve)
+
+
+def plan_team_reserve(teams, spec):
+    """The default reserve of a planner: ceil(separation / h), the smallest r for which centres more than r cells apart are at least
+    separation + h apart along an axis; ValueError above PLAN_RESERVE_MAX"""
+    r = int(np.ceil(float(teams.separation) / float(spec.h)))
+    if r > PLAN_RESERVE_MAX:
+        raise ValueError(f"plan_team: a separation of {teams.separation} needs reserve = {r} cells of {float(spec.h)}, at most {PLAN_RESERVE_MAX}: use a coarser grid")
+    return r
+
+
+def plan_team_base(spec, walls, hazards, step0, layer_steps, layers):
+    """The base layers of a team plan, bool [S][T + 1][G][G] -> (occupancy, S, scene): grid_occupancy's map in every layer for None and
+    Hazards (a team plan is a time plan even in a static scene), grid_occupancy_time's for MovingHazards"""
+    if isinstance(hazards, MovingHazards):
+        S, scene = plan_scene_time(walls, hazards)
+        return grid_occupancy_time(spec, walls, hazards, step0, layer_steps, layers), S, scene
+    S, scene = plan_scene(walls, hazards)
+    occ = grid_occupancy(spec, walls, hazards)
+    return np.ascontiguousarray(np.broadcast_to(occ[:, None], (S, layers + 1) + occ.shape[1:])), S, scene
+
+
+def grid_reserve(walk, layers, G, reserve):
+    """The reservation of a walk with cells c[0 .. A] (c[a] = c[A] beyond), bool [T + 1][G][G]: layer t < T reserves every cell within
+    Chebyshev distance `reserve` of c[t] or c[t + 1], the tail layer T every cell within it of any c[a], a >= min(T, A)."""
+    T, r, A = int(layers), int(reserve), len(walk) - 1
+    res = np.zeros((T + 1, G, G), bool)
+
+    def stamp(t, c):
+        res[t, max(c[1] - r, 0):c[1] + r + 1, max(c[0] - r, 0):c[0] + r + 1] = True
+    for t in range(T):
+        stamp(t, walk[min(t, A)])
+        stamp(t, walk[min(t + 1, A)])
+    for a in range(min(T, A), A + 1):
+        stamp(T, walk[a])
+    return res
+
+
+def grid_team_field(occ_layers, goal_cell):
+    """grid_time_field with one change: the goal cell is terminal (d_t = 0) only where it is free in occ_t AND in every later layer up
+    to T; otherwise it is an ordinary cell, so a robot may wait on it or step off and come back."""
+    occ = np.asarray(occ_layers, bool)
+    T, G = occ.shape[0] - 1, occ.shape[1]
+    d = np.full((T + 1, G, G), -1, np.int32)
+    d[T] = grid_field(occ[T], goal_cell)
+    gx, gy = int(goal_cell) % G, int(goal_cell) // G
+    big = np.int32(2 ** 30)
+    terminal = not occ[T, gy, gx]
+    for t in range(T - 1, -1, -1):
+        terminal = terminal and not occ[t, gy, gx]
+        nxt = np.full((G + 2, G + 2), -1, np.int32)
+        nxt[1:-1, 1:-1] = d[t + 1]
+        ok = plan_moves_ok(occ[t])
+        best = np.where(d[t + 1] >= 0, d[t + 1] + np.int32(PLAN_WAIT), big)
+        for k, (dx, dy) in enumerate(PLAN_DIRS):
+            nb = nxt[1 + dy:1 + dy + G, 1 + dx:1 + dx + G]
+            best = np.minimum(best, np.where(ok[k] & (nb >= 0), nb + np.int32(PLAN_STEP if k < 4 else PLAN_DIAG), big))
+        best = np.where(best >= big, np.int32(-1), best)
+        if terminal:
+            best[gy, gx] = 0
+        d[t] = np.where(occ[t], np.int32(-1), best)
+    return d
+
+
+def grid_walk_team(field, occ_layers, spec, start_xy):
+    """grid_walk_time with one change: the walk ends when d_t[c] == 0 (a terminal goal cell), not on entering the goal's cell."""
+    occ, d = np.asarray(occ_layers, bool), np.asarray(field)
+    T, G = d.shape[0] - 1, spec.cells
+    ix, iy = (int(v) for v in spec.cell_of(np.asarray(start_xy, np.float32)[:2]))
+    if d[0, iy, ix] < 0:
+        return [], [], UNREACHABLE
+    cells, acts, prev = [(ix, iy)], [], -1
+    while d[min(len(acts), T), iy, ix] != 0:
+        t = min(len(acts), T)
+        nxt = d[min(t + 1, T)]
+
+        def descends(k):
+            jx, jy = ix + PLAN_DIRS[k][0], iy + PLAN_DIRS[k][1]
+            return plan_move_ok(occ[t], ix, iy, k) and nxt[jy, jx] >= 0 and nxt[jy, jx] + (PLAN_STEP if k < 4 else PLAN_DIAG) == d[t, iy, ix]
+        k = prev if prev >= 0 and descends(prev) else next((j for j in range(8) if descends(j)), -1)
+        if k < 0 and t < T and nxt[iy, ix] >= 0 and nxt[iy, ix] + PLAN_WAIT == d[t, iy, ix]:
+            k = PLAN_WAIT_ACTION
+        if k < 0 or len(acts) >= T + G * G:
+            raise ValueError("grid_walk_team: the field is not the team field of these layers and this goal")
+        if k != PLAN_WAIT_ACTION:
+            ix, iy, prev = ix + PLAN_DIRS[k][0], iy + PLAN_DIRS[k][1], k
+        cells.append((ix, iy))
+        acts.append(k)
+    return cells, acts, PLANNED
+
+
+def grid_path_team(field, occ_layers, spec, start_xy, goal_xy, K):
+    """grid_path_time on grid_walk_team's walk -> (grid_path_time's tuple, cells of the walk ([] when UNREACHABLE))"""
+    K = int(K)
+    if K < 1:
+        raise ValueError("max_waypoints must be >= 1")
+    wp, waits, leave = np.zeros((K, 2), np.float32), np.zeros(K, np.int32), np.zeros(K, np.int32)
+    cells, acts, status = grid_walk_team(field, occ_layers, spec, start_xy)
+    if status == UNREACHABLE:
+        return (wp, 0, UNREACHABLE, -1, waits, leave, 0), []
+    count, prev, waited = 0, -1, 0
+    for a, k in enumerate(acts):
+        if k == PLAN_WAIT_ACTION:
+            waited += 1
+            continue
+        turned = prev >= 0 and (k != prev or waited > 0)
+        if turned:
+            if count < K:
+                wp[count] = spec.centre(cells[a][0]), spec.centre(cells[a][1])
+            count += 1
+        if (prev < 0 or turned) and count < K:      # this move leaves the anchor of waypoint `count`
+            waits[count], leave[count] = waited, a
+        prev, waited = k, 0
+    if count < K:
+        wp[count] = np.asarray(goal_xy, np.float32)[:2]
+    count += 1
+    sx, sy = cells[0]
+    return (wp, count, TRUNCATED if count > K else PLANNED, int(np.asarray(field)[0, sy, sx]), waits, leave, len(acts)), cells
+
+
+def grid_team_clearance(walks, size, layers=None):
+    """The checker of a team plan, independent of the planner: it sees walks only, never occupancy or fields.  walks: per robot the
+    cells [(ix, iy), ...] c[0 .. A] of its walk (c[a] = c[A] beyond; a parked robot: its start cell alone), robots i and j mates when
+    i // size == j // size -> (clearance [n_teams] int32, crossings [n_teams] int32).  clearance: the smallest Chebyshev cell distance
+    of two mates over, for every action t < T, the four pairs {c_i[t], c_i[t + 1]} x {c_j[t], c_j[t + 1]}, and over every pair c_i[a],
+    c_j[b] of the tails, a >= min(T, A_i), b >= min(T, A_j); PLAN_NO_PAIR for a team of one.  crossings: the actions t in which two
+    mates both move diagonally inside one 2 x 2 block, across each other.  layers = T, the layers of the plan: pass it to check what
+    the rule guarantees.  None takes T beyond every walk: every action is then checked in step and the tails are the last cells
+    alone, which is less than the guarantee for walks that run on into the tail layer."""
+    n = len(walks)
+    lengths = np.array([len(w) for w in walks], np.int64)
+    if n and lengths.min() < 1:
+        raise ValueError("grid_team_clearance: every walk has at least its start cell")
+    cells = np.zeros((n, max(int(lengths.max()), 1) if n else 1, 2), np.int64)
+    for i, w in enumerate(walks):
+        cells[i, :lengths[i]] = np.asarray(w, np.int64).reshape(-1, 2)
+    return grid_team_clearance_cells(cells, lengths, size, layers)
+
+
+def grid_team_clearance_cells(cells, lengths, size, layers=None):
+    """grid_team_clearance on arrays: cells [n][L][2] (ix, iy), robot i's walk in its first lengths[i] >= 1 entries.  All pairs of
+    mates and all teams at once; the tails pair by pair only where a walk runs on into the tail layer."""
+    cells, lengths, size = np.asarray(cells, np.int64), np.asarray(lengths, np.int64), int(size)
+    n = cells.shape[0]
+    if size < 1 or n % size != 0:
+        raise ValueError(f"{n} walks do not split into teams of {size}")
+    if n and (lengths.min() < 1 or lengths.max() > cells.shape[1]):
+        raise ValueError("grid_team_clearance: every walk has at least its start cell")
+    g = n // size
+    T = int(lengths.max()) if layers is None else int(layers)
+    clear, cross = np.full(g, PLAN_NO_PAIR, np.int64), np.zeros(g, np.int64)
+    if size == 1 or n == 0:
+        return clear.astype(np.int32), cross.astype(np.int32)
+    idx = np.minimum(np.arange(T + 2)[None, :], lengths[:, None] - 1)                # c[0 .. T + 1], padded with c[A]
+    c = cells[np.arange(n)[:, None], idx].reshape(g, size, T + 2, 2)
+    pair = np.triu(np.ones((size, size), bool), 1)[None, :, :, None]                 # i < j
+    big = np.int64(PLAN_NO_PAIR)
+    if T > 0:
+        for p in (c[:, :, None, :T], c[:, :, None, 1:T + 1]):
+            for q in (c[:, None, :, :T], c[:, None, :, 1:T + 1]):
+                dist = np.where(pair, np.abs(p - q).max(axis=-1), big)               # [g][size][size][T]
+                clear = np.minimum(clear, dist.min(axis=(1, 2, 3)))
+        move = c[:, :, 1:T + 1] - c[:, :, :T]
+        diag = np.abs(move).sum(axis=-1) == 2                                         # [g][size][T]
+        low = np.minimum(c[:, :, :T], c[:, :, 1:T + 1])                              # the block's lower-left corner
+        # both diagonals of one block: the two moves share the corner and neither start is the other's start or end
+        hit = (diag[:, :, None] & diag[:, None, :] & np.all(low[:, :, None] == low[:, None, :], axis=-1)
+               & np.any(c[:, :, None, :T] != c[:, None, :, :T], axis=-1) & np.any(c[:, :, None, :T] != c[:, None, :, 1:T + 1], axis=-1))
+        cross = (hit & pair).sum(axis=(1, 2, 3))
+    # the tails: c[min(T, A) .. A]; one cell for a walk that ends before the tail layer
+    first = np.minimum(T, lengths - 1)
+    one = cells[np.arange(n), first].reshape(g, size, 2)
+    short = (lengths - first == 1).reshape(g, size)
+    dist = np.where(pair[..., 0] & short[:, :, None] & short[:, None, :], np.abs(one[:, :, None] - one[:, None, :]).max(axis=-1), big)
+    clear = np.minimum(clear, dist.min(axis=(1, 2)))
+    for i in np.flatnonzero(~short.ravel()):                                          # a long tail against each mate's tail
+        ti = cells[i, first[i]:lengths[i]]
+        for j in range(i // size * size, (i // size + 1) * size):
+            if j != i and (j > i or short.ravel()[j]):
+                tj = cells[j, first[j]:lengths[j]]
+                clear[i // size] = min(clear[i // size], int(np.abs(ti[:, None, :] - tj[None, :, :]).max(axis=2).min()))
+    return clear.astype(np.int32), cross.astype(np.int32)
+
+
+def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0, layer_steps=None, layers=None, want_fields=True):
+    """The whole team plan of n robots by the rule: grid_plan_time's dict per robot -- there are no shared fields: field_of is the
+    identity and fields is int32 [n][T + 1][G][G] (None without want_fields), each robot's own on ITS map -- with occupancy the
+    BASE layers bool [S][T + 1][G][G], plus walks (per robot the cells of its walk; a robot without one: its start cell),
+    team_clearance and team_crossings [n_teams] int32 (grid_team_clearance).  A member that is UNREACHABLE reserves its start cell
+    in every layer: a parked robot is an obstacle, as in team_cost."""
+    start, goal = np.asarray(start, np.float32), np.asarray(goal, np.float32)
+    n, P = goal.shape
+    if layer_steps is None or layers is None:
+        raise ValueError("plan_team: layer_steps and layers are required (a team plan is a time plan even in a static scene)")
+    step0, layer_steps, T = plan_time_check(step0, layer_steps, layers)
+    occ, S, scene = plan_team_base(spec, walls, hazards, step0, layer_steps, T)
+    for sc in (walls, hazards):
+        if sc is not None:
+            sc.check_robots(n)
+    size, r = plan_team_check(teams, reserve, n, scene)
+    G = spec.cells
+    one = (T + 1) * G * G * 4
+    if one > PLAN_TIME_MAX_BYTES or (want_fields and n * one > PLAN_TIME_MAX_BYTES):
+        raise ValueError(f"plan_team: time fields of {n if want_fields else 1} x {T + 1} x {G} x {G} x 4 bytes exceed the cap of "
+                         f"{PLAN_TIME_MAX_BYTES} bytes ({PLAN_TIME_MAX_BYTES >> 20} MiB)")
+    gx, gy = spec.cell_of(goal[:, :2])
+    sx, sy = spec.cell_of(start[:, :2])
+    sc = np.zeros(n, np.int32) if scene is None else np.asarray(scene, np.int32)
+    fields = np.zeros((n, T + 1, G, G), np.int32) if want_fields else None
+    wp, waits, leave = np.zeros((n, K, P), np.float32), np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
+    count, status, cost, arrive = (np.zeros(n, np.int32) for _ in range(4))
+    walks = []
+    for i in range(n):
+        if i % size == 0:
+            res = np.zeros((T + 1, G, G), bool)
+        layers_i = occ[sc[i]] | res
+        field = grid_team_field(layers_i, int(gy[i]) * G + int(gx[i]))
+        if want_fields:
+            fields[i] = field
+        (w, count[i], status[i], cost[i], waits[i], leave[i], arrive[i]), cells = grid_path_team(field, layers_i, spec, start[i], goal[i], K)
+        m = min(int(count[i]), K)
+        wp[i, :m, :2] = w[:m]
+        wp[i, :m, 2:] = goal[i, 2:]
+        walks.append(cells if cells else [(int(sx[i]), int(sy[i]))])
+        res |= grid_reserve(walks[-1], T, G, r)
+    first, number = grid_layer_frames(hazards, step0, layer_steps, T) if isinstance(hazards, MovingHazards) else (None, None)
+    clear, cross = grid_team_clearance(walks, size, T)
+    return {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
+            "waits": waits, "leave": leave, "arrive": arrive, "release": grid_release(waits, leave, step0, layer_steps),
+            "occupancy": occ, "fields": fields, "field_of": np.arange(n, dtype=np.int32),
+            "field_goal_cell": (gy * G + gx).astype(np.int32), "field_scene": sc.copy(), "layer_first": first, "layer_number": number,
+            "walks": walks, "team_clearance": clear, "team_crossings": cross}

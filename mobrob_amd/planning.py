@@ -13,7 +13,9 @@ Line-of-sight smoothing (`smooth=True`): of the walk's cells only
 (goal_rules.grid_los, grid_smooth; device: mobrob_ppo_plan_smooth on the resident fields, k_plan_smooth in k_plan_path's place).
 Moving hazards (`hazards=MovingHazards(...)`, `layer_steps=`): the plan is made over time -- layers of occupancy, one
 per action of `layer_steps` steps, a wait where waiting for a hazard to pass is cheapest -- and carries `release` steps and a
-`schedule` for the tracker (goal_rules.grid_plan_time; device: mobrob_ppo_plan_grid_time).  Team-mates, walls as solid bodies and
+`schedule` for the tracker (goal_rules.grid_plan_time; device: mobrob_ppo_plan_grid_time).  Teams (`teams=Teams(...)`, DESIGN
+4.12.3): inside a team the members plan in index order and every member's walk is reserved in the layers of the members after it,
+so mates are planned around each other (goal_rules.grid_plan_team; device: mobrob_ppo_plan_grid_team).  Walls as solid bodies and
 smoothing of a time plan are not planned for."""
 from __future__ import annotations
 
@@ -32,18 +34,30 @@ class GridPlanner:
     cell to see from and keeps every cell as a waypoint -- in cluttered scenes or with a small inflate use 0).
     hazards may be a goal_rules.MovingHazards: every plan is then a time plan.  layer_steps (required then): the steps a robot is
     given for one move or wait; layers: the actions planned in time before the conservative tail.  A time plan is not smoothed
-    (smooth=True: ValueError) and nothing of it stays resident, so every call computes."""
+    (smooth=True: ValueError) and nothing of it stays resident, so every call computes.
+    teams: a goal_rules.Teams: every plan is a TEAM plan, a time plan (layer_steps required, also in a static scene) in which the
+    members of a team plan in index order around the walks of the members before them; reserve: the cells (Chebyshev) a walk
+    reserves around itself, 0 .. 4 (None: ceil(separation / h), ValueError above 4).  Prioritised planning is incomplete: a
+    member never yields to a later one, and a later member boxed in by reservations comes back UNREACHABLE."""
 
     def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
-                 smooth=False, los_margin=1, layer_steps=None, layers=None):
+                 smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None):
         from .envs.vec_env import DeviceGoalVecEnv
-        self.timed = isinstance(hazards, rules.MovingHazards)
+        if teams is not None and not isinstance(teams, rules.Teams):
+            raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
+        if teams is None and reserve is not None:
+            raise ValueError("GridPlanner: reserve= belongs to teams=")
+        self.teams = teams
+        self.timed = isinstance(hazards, rules.MovingHazards) or teams is not None
         if self.timed:
-            rules.plan_scene_time(walls, hazards)
+            if isinstance(hazards, rules.MovingHazards):
+                rules.plan_scene_time(walls, hazards)
+            else:
+                rules.plan_scene(walls, hazards)
             if layer_steps is None:
-                raise ValueError("GridPlanner: moving hazards need layer_steps= (the steps a robot is given for one move)")
+                raise ValueError("GridPlanner: moving hazards and teams need layer_steps= (the steps a robot is given for one move)")
             if smooth:
-                raise ValueError("GridPlanner: smooth=True with moving hazards: smoothing over time is not supported")
+                raise ValueError("GridPlanner: smooth=True with moving hazards or teams: smoothing over time is not supported")
             _, self.layer_steps, self.layers = rules.plan_time_check(0, layer_steps, 64 if layers is None else layers)
         else:
             rules.plan_scene(walls, hazards)
@@ -78,6 +92,8 @@ class GridPlanner:
         if self.pos_dim not in (2, 3):
             raise ValueError(f"GridPlanner: the grid is x and y; the environment has {self.pos_dim} position dimension(s)")
         self.spec = rules.GridSpec(extent, cells, inflate)
+        if teams is not None:
+            self.reserve = rules.plan_team_reserve(teams, self.spec) if reserve is None else rules.plan_team_check(teams, reserve, teams.size)[1]
         self._kept = None        # the latest full plan: its goal cells, scenes and (device: resident, host: arrays) fields
 
     def _check(self, start, goal):
@@ -124,6 +140,12 @@ class GridPlanner:
 
     def _plan_time(self, start, goal, K, step0, want_occupancy, want_fields):
         """One time plan: the device call, or the NumPy rule on the host path"""
+        if self.teams is not None:
+            kw = dict(step0=step0, layer_steps=self.layer_steps, layers=self.layers)
+            if self.device:
+                return self.engine.plan_grid_team(self.spec, self.walls, self.hazards, teams=self.teams, reserve=self.reserve, start=start,
+                                                  goal=goal, max_waypoints=K, want_occupancy=want_occupancy, want_fields=want_fields, **kw)
+            return rules.grid_plan_team(self.spec, self.walls, self.hazards, start, goal, K, self.teams, self.reserve, want_fields=want_fields, **kw)
         if self.device:
             return self.engine.plan_grid_time(self.spec, self.walls, self.hazards, start=start, goal=goal, step0=step0,
                                               layer_steps=self.layer_steps, layers=self.layers, max_waypoints=K,
@@ -141,12 +163,14 @@ class GridPlanner:
         With moving hazards the plan starts at the global step `step0` and the dict gains waits, leave [n][K], arrive [n] (waits at
         each waypoint's anchor, actions before the move that leaves it, actions of the walk), release [n][K] (the global step until
         which the robot holds at the anchor, 0: no hold) and `schedule`, a Schedule(release, home=start) for follow_waypoints;
-        occupancy and fields then carry the layer axis, [S][T + 1][G][G] and [F][T + 1][G][G]."""
+        occupancy and fields then carry the layer axis, [S][T + 1][G][G] and [F][T + 1][G][G].  With teams the plan is such a time
+        plan too (every robot has its own field; occupancy: the base layers) and gains team_clearance and team_crossings [n_teams]
+        (goal_rules.grid_team_clearance of the planned walks: more than `reserve` cells and no crossing between planned mates)."""
         start, goal = self._check(start, goal)
         smooth = self.smooth if smooth is None else bool(smooth)
         if self.timed:
             if smooth:
-                raise ValueError("plan: smooth=True with moving hazards: smoothing over time is not supported")
+                raise ValueError("plan: smooth=True with moving hazards or teams: smoothing over time is not supported")
             out = self._plan_time(start, goal, self.K, step0, want_occupancy, want_fields)
             if grow and np.any(out["status"] == rules.TRUNCATED):
                 out = self._plan_time(start, goal, int(out["count"].max()), step0, want_occupancy, want_fields)
@@ -162,6 +186,8 @@ class GridPlanner:
         if self.timed:
             res.update({k: out[k] for k in ("waits", "leave", "arrive", "release")})
             res["schedule"] = rules.Schedule(out["release"], home=start)
+        if self.teams is not None:
+            res.update({k: out[k] for k in ("team_clearance", "team_crossings")})
         res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
         res["smoothed"], res["moves"] = smooth, out.get("moves")
         if want_occupancy:
@@ -180,12 +206,15 @@ class GridPlanner:
         `callback.last` holds the latest plan (None before the first).
         With moving hazards `horizon` is required, the `horizon` of that follow_with_replanning loop: the loop makes call r of the
         callback after r * horizon steps, so the callback counts its own calls (`callback.calls`) and plans with step0 = r * horizon;
-        a robot then gets (waypoints[:count], release[:count]), which the loop hands to FollowState.replan(..., release=)."""
-        from .waypoints import STALLED
+        a robot then gets (waypoints[:count], release[:count]), which the loop hands to FollowState.replan(..., release=).
+        With teams (horizon required as well) a team with any STALLED member is planned again as a whole from where its members
+        stand: every member that is not FINISHED and whose new plan is PLANNED gets (waypoints, release); finished members are
+        planned too, so that they reserve their cell, and are not returned."""
+        from .waypoints import FINISHED, STALLED
         goal = np.asarray(goal, np.float64)
         if self.timed:
             if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < 1:
-                raise ValueError(f"callback: moving hazards need horizon= (the replanning loop's, an integer >= 1), got {horizon!r}")
+                raise ValueError(f"callback: moving hazards and teams need horizon= (the replanning loop's, an integer >= 1), got {horizon!r}")
         elif horizon is not None:
             raise ValueError("callback: horizon= belongs to moving hazards; a static plan has no clock")
 
@@ -196,6 +225,9 @@ class GridPlanner:
                 return {}
             plan = self.plan(positions, goal, planner.calls * int(horizon)) if self.timed else self.plan(positions, goal)
             planner.last = plan
+            if self.teams is not None:                     # the whole team of a stalled robot, its finished members aside
+                mates = np.unique(stalled // self.teams.size)[:, None] * self.teams.size + np.arange(self.teams.size)
+                stalled = np.array([i for i in mates.ravel() if np.asarray(status)[i] != FINISHED], np.int64)
             rows = {int(i): plan["waypoints"][i, :plan["n_waypoints"][i]].copy() for i in stalled if plan["status"][i] == rules.PLANNED}
             if self.timed:
                 rows = {i: (w, plan["release"][i, :len(w)].copy()) for i, w in rows.items()}
