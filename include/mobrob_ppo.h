@@ -841,8 +841,8 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
  *             test 64 candidates against the anchor at once, a ballot and a count of trailing zeros find the first that is hidden.
  *             k_plan_dilate: the cells that are not clear at margin 1, once per set of resident fields, kept beside them.  Runs on the
  *             engine's stream in the planner's own buffers; nothing a training step reads or writes is touched.
- * Still out of scope: smoothing of a time plan (mobrob_ppo_plan_grid_time, mobrob_ppo_plan_grid_team), walls as solid bodies of the
- * simulation.  Team-mates as obstacles: mobrob_ppo_plan_grid_team.
+ * Still out of scope: smoothing of a team plan (mobrob_ppo_plan_grid_team), walls as solid bodies of the simulation.  Smoothing of a
+ * time plan: mobrob_ppo_plan_grid_time_smooth.  Team-mates as obstacles: mobrob_ppo_plan_grid_team.
  * MOBROB_ERR_INVALID before any launch or copy for: a NULL argument (scene aside), margin not 0 or 1, n_robots < 1, pos_dim not 2 or 3,
  * cells not 32 / 64 / 128, max_waypoints < 1, n_fields outside 1 .. n_robots, n_scenes < 1, extent, h, inv_h not finite and > 0 or
  * h * inv_h not 1 within 1e-5, cells / n_scenes / n_fields not the resident fields', a missing scene index with several scenes, a
@@ -900,6 +900,49 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
                               int32_t* cost_out /* [n] */, int32_t* waits_out /* [n][K] */, int32_t* leave_out /* [n][K] */,
                               int32_t* arrive_out /* [n] */, uint8_t* occ_time_out /* [S][T + 1][G][G] or NULL */,
                               int32_t* fields_time_out /* [F][T + 1][G][G] or NULL */, int32_t* sweeps_out /* [F] or NULL */);
+
+/* ---- line-of-sight smoothing of a time plan: a straight leg is tested against every layer it spans ------------------------------
+ * mobrob_ppo_plan_grid_time with mobrob_ppo_plan_smooth's waypoints.  The rule, all integers, is stated once in
+ * mobrob_amd/envs/goal_rules.py (grid_next_blocked, grid_los_time, grid_smooth_time, grid_path_smooth_time) and reproduced bit for bit.
+ *   clear     as mobrob_ppo_plan_smooth's, per layer: blk_t is layer t's map at margin 0, its 3 x 3 dilation at margin 1.
+ *   table     nb[T + 1][G][G] int16 per scene: nb[T][c] = T if blk_T[c] else 32767; for t = T - 1 .. 0, nb[t][c] = t if blk_t[c] else
+ *             nb[t + 1][c].  Cell c is clear in all of the layers lo .. hi (lo <= hi <= T) exactly when nb[lo][c] > hi.
+ *   visible   los_time(a, b, lo, hi): mobrob_ppo_plan_smooth's los on the map nb[lo] <= hi.
+ *   smooth    the walk's cells c[0 .. A], one per action boundary (a wait repeats its cell).  Anchor i = 0, j = 1; while j < A: if
+ *             los_time(c[i], c[j + 1], min(i, T), min(j + 1, T)) then j += 1, else emit j, i = j, j += 1.  A leg of one action is never
+ *             tested.  Waypoints: the centres of the emitted cells, then the goal itself (z: the goal's).
+ *   guarantee a kept leg from action index a to b with b - a >= 2: every cell of the supercover between c[a] and c[b], both ends
+ *             included, is clear at the margin in each of the layers min(a, T) .. min(b, T) -- whatever the robot's speed along the
+ *             leg, as long as it leaves c[a] no earlier and reaches c[b] no later than the walk does.  A leg of one action carries
+ *             mobrob_ppo_plan_grid_time's promise only.  Not promised: fewer waypoints than the unsmoothed plan.
+ *   outputs   waypoints_out .. cost_out, arrive_out and the optional copies as mobrob_ppo_plan_grid_time's.  leave_out [n][K]: the
+ *             action index of waypoint k's anchor, 0 for k = 0, the emitted index of waypoint k - 1 otherwise -- a hold at EVERY anchor
+ *             but the start until step0 + leave * layer_steps is the release step of waypoint k (a straight leg is shorter than the
+ *             walk it replaces; the robot must not enter the next leg before the first layer that leg was tested in).  waits_out
+ *             [n][K] or NULL: zeroed.  moves_out [n]: the actions of the walk that are moves.  next_blocked_out [S][T + 1][G][G] or
+ *             NULL: the table.  Status 3: the tail's relaxation, a walk of more than T + cells * cells actions or as many rounds of
+ *             the window ran into the bound; count 0, cost -1, arrive 0, moves 0, waypoints and leave zeroed.
+ *   kernels   k_plan_occupancy_time and k_plan_field_time as they are; at margin 1 k_plan_dilate as it is over the S * (T + 1) layer
+ *             maps; k_plan_next_blocked (a thread per scene and cell scans the layers from the tail down); k_plan_smooth_time in
+ *             k_plan_path_time's place: one wave per robot, the walk's cells in a ring of 128 packed cells in LDS indexed by action,
+ *             lane l tests c[i] against c[base + l] on nb[min(i, T)] with the threshold min(base + l, T) (base = i + 2 at first,
+ *             + 64 after a window without a hidden cell), a ballot and a count of trailing zeros find the first hidden index.  Every call computes in the time plans' own buffer and keeps nothing
+ *             resident; runs on the engine's stream; nothing a training step reads or writes is touched.
+ * Still out of scope: smoothing of a team plan (a smoothed leg would have to be reserved as a swept region), walls as solid bodies.
+ * MOBROB_ERR_INVALID before any launch or copy for everything mobrob_ppo_plan_grid_time refuses (waits_out aside, moves_out included
+ * in "a NULL argument"), and for: margin not 0 or 1, time fields plus the table of n_scenes * (layers + 1) * cells * cells * 2 bytes
+ * above MOBROB_PLAN_TIME_MAX_BYTES. */
+int mobrob_ppo_plan_grid_time_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                                     const mobrob_hazard_frames_t* hazards, const mobrob_plan_time_t* time, int32_t margin /* 0 or 1 */,
+                                     const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */,
+                                     const int32_t* field_of /* [n] */, const int32_t* field_goal_cell /* [F] */,
+                                     const int32_t* field_scene /* [F] */, float* waypoints_out /* [n][K][pos_dim] */,
+                                     int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */, int32_t* status_out /* [n] */,
+                                     int32_t* cost_out /* [n] */, int32_t* waits_out /* [n][K] or NULL */, int32_t* leave_out /* [n][K] */,
+                                     int32_t* arrive_out /* [n] */, int32_t* moves_out /* [n] */,
+                                     uint8_t* occ_time_out /* [S][T + 1][G][G] or NULL */,
+                                     int32_t* fields_time_out /* [F][T + 1][G][G] or NULL */, int32_t* sweeps_out /* [F] or NULL */,
+                                     int16_t* next_blocked_out /* [S][T + 1][G][G] or NULL */);
 
 /* ---- prioritised planning inside a team: a mate's planned walk as one more moving obstacle ---------------------------------------
  * mobrob_ppo_plan_grid_time for robots in teams of team_size consecutive robots (mobrob_teams_t's partition).  The rule is stated

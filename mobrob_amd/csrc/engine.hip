@@ -4295,16 +4295,27 @@ static void plan_layer_frames(const mobrob_hazard_frames_t* hz, const mobrob_pla
   number[T] = (int32_t)(F - first[T]);
 }
 
-int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
-                              const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, const float* start, const float* goal,
-                              const int32_t* field_of, const int32_t* field_goal_cell, const int32_t* field_scene, float* waypoints_out,
-                              int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* waits_out,
-                              int32_t* leave_out, int32_t* arrive_out, uint8_t* occ_time_out, int32_t* fields_time_out,
-                              int32_t* sweeps_out) {
+// what mobrob_ppo_plan_grid_time_smooth adds to a time plan; null: mobrob_ppo_plan_grid_time itself
+struct PlanTimeSmooth {
+  int32_t margin;
+  int32_t* moves_out;
+  int16_t* next_blocked_out;   // or null
+};
+
+// a time plan: the checks, the layers and the fields of both entry points, then k_plan_path_time, or with `sm` the table of
+// k_plan_next_blocked and k_plan_smooth_time in its place (waits_out may then be null; it is zeroed)
+static int plan_time_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                         const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, const float* start, const float* goal,
+                         const int32_t* field_of, const int32_t* field_goal_cell, const int32_t* field_scene, float* waypoints_out,
+                         int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* waits_out,
+                         int32_t* leave_out, int32_t* arrive_out, uint8_t* occ_time_out, int32_t* fields_time_out, int32_t* sweeps_out,
+                         const PlanTimeSmooth* sm) {
   if (!e || !spec || !hzf || !tm || !start || !goal || !field_of || !field_goal_cell || !field_scene || !waypoints_out ||
-      !n_waypoints_out || !count_out || !status_out || !cost_out || !waits_out || !leave_out || !arrive_out)
+      !n_waypoints_out || !count_out || !status_out || !cost_out || (!sm && !waits_out) || !leave_out || !arrive_out ||
+      (sm && !sm->moves_out))
     return fail(MOBROB_ERR_INVALID, "plan_time: null argument");
   if (spec->reuse_id != 0) return fail(MOBROB_ERR_INVALID, "plan_time: reuse_id must be 0 (a time plan keeps nothing resident)");
+  if (sm && sm->margin != 0 && sm->margin != 1) return fail(MOBROB_ERR_INVALID, "plan_time: margin must be 0 or 1, got %d", sm->margin);
   const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
   const int cells = G * G, T = tm->layers;
   mobrob_hazards_t view;
@@ -4321,6 +4332,9 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   if ((uint64_t)F * (uint64_t)(T + 1) * (uint64_t)cells * 4u > MOBROB_PLAN_TIME_MAX_BYTES)
     return fail(MOBROB_ERR_INVALID, "plan_time: time fields of %d x %d x %d x %d x 4 bytes exceed the cap of %u bytes (256 MiB)", F, T + 1, G, G,
                 (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
+  if (sm && ((uint64_t)F * 4u + (uint64_t)S * 2u) * (uint64_t)(T + 1) * (uint64_t)cells > MOBROB_PLAN_TIME_MAX_BYTES)
+    return fail(MOBROB_ERR_INVALID, "plan_time: time fields of %d x %d x %d x %d x 4 bytes and the next-blocked table of %d x %d x %d x %d x 2 "
+                "bytes exceed the cap of %u bytes (256 MiB)", F, T + 1, G, G, S, T + 1, G, G, (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
   const size_t field_lds = plan_field_time_lds_bytes(G);
   {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid checks k_plan_field's
     int limit = 0;
@@ -4343,6 +4357,9 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
                o_leave = call.add((size_t)N * K * 4), o_arrive = call.add((size_t)N * 4),
                o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
                o_hz = call.add(std::max<size_t>(hz_floats, 1) * 4), o_nhz = call.add((size_t)S * 4);
+  const size_t maps = (size_t)S * (T + 1);   // smoothing: the dilated layers (margin 1), the next-blocked table, the moves
+  const size_t o_dil = sm && sm->margin == 1 ? call.add(maps * cells) : 0, o_nb = sm ? call.add(maps * cells * 2) : 0,
+               o_moves = sm ? call.add((size_t)N * 4) : 0;
   if (const int rc = grow_plan_buf(e, e->plan_time_buf, e->plan_time_bytes, call.total)) return rc;
   const auto mine = [&](size_t off) { return e->plan_time_buf + off; };
   unsigned char* occ_dev = reinterpret_cast<unsigned char*>(mine(o_occ));
@@ -4380,6 +4397,25 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   const PlanFieldTimeArgs fa{G, T, occ_dev, fgoal_dev, fscene_dev, field_dev, sweeps_dev};
   hipLaunchKernelGGL(k_plan_field_time, dim3(F), dim3(kPlanFieldThreads), field_lds, e->stream, fa);
   HIPC(hipGetLastError());
+  PlanSmoothTimeArgs sa{};
+  if (sm) {   // the cells that are not clear in every layer, then the first layer from t on in which a cell is not clear
+    const unsigned char* blk_dev = occ_dev;
+    if (sm->margin == 1) {   // k_plan_dilate as it is, a layer a map: at most 65535 maps a launch (the grid's y)
+      unsigned char* dil_dev = reinterpret_cast<unsigned char*>(mine(o_dil));
+      for (size_t m0 = 0; m0 < maps; m0 += 65535) {
+        const PlanDilateArgs da{G, occ_dev + m0 * cells, dil_dev + m0 * cells};
+        hipLaunchKernelGGL(k_plan_dilate, dim3(cells / 256, (unsigned)std::min<size_t>(maps - m0, 65535)), dim3(256), 0, e->stream, da);
+        HIPC(hipGetLastError());
+      }
+      blk_dev = dil_dev;
+    }
+    const PlanNextBlockedArgs na{G, T, blk_dev, reinterpret_cast<short*>(mine(o_nb))};
+    hipLaunchKernelGGL(k_plan_next_blocked, dim3(cells / 256, S), dim3(256), 0, e->stream, na);
+    HIPC(hipGetLastError());
+    sa.T = T; sa.nb = na.nb;
+    sa.leave = reinterpret_cast<int*>(mine(o_leave)); sa.arrive = reinterpret_cast<int*>(mine(o_arrive));
+    sa.moves = reinterpret_cast<int*>(mine(o_moves));
+  }
   PlanPathTimeArgs ta{};
   PlanPathArgs& pa = ta.p;
   pa.g = oa.g; pa.N = N; pa.K = K; pa.P = P;
@@ -4400,21 +4436,52 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
   HIPC(hipMemsetAsync(ta.waits, 0, (size_t)N * K * 4, e->stream));
   HIPC(hipMemsetAsync(ta.leave, 0, (size_t)N * K * 4, e->stream));
-  hipLaunchKernelGGL(k_plan_path_time, dim3(cdiv(N, 64)), dim3(64), 0, e->stream, ta);
+  if (sm) {
+    sa.p = pa;
+    hipLaunchKernelGGL(k_plan_smooth_time, dim3(N), dim3(64), 0, e->stream, sa);   // a wave per robot
+  } else {
+    hipLaunchKernelGGL(k_plan_path_time, dim3(cdiv(N, 64)), dim3(64), 0, e->stream, ta);
+  }
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
-  HIPC(hipMemcpyAsync(waits_out, ta.waits, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
+  if (waits_out) HIPC(hipMemcpyAsync(waits_out, ta.waits, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));   // (smoothed: the zeroes)
   HIPC(hipMemcpyAsync(leave_out, ta.leave, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(arrive_out, ta.arrive, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  if (sm) {
+    HIPC(hipMemcpyAsync(sm->moves_out, sa.moves, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+    if (sm->next_blocked_out) HIPC(hipMemcpyAsync(sm->next_blocked_out, sa.nb, maps * cells * 2, hipMemcpyDeviceToHost, e->stream));
+  }
   if (occ_time_out) HIPC(hipMemcpyAsync(occ_time_out, occ_dev, (size_t)S * (T + 1) * cells, hipMemcpyDeviceToHost, e->stream));
   if (fields_time_out) HIPC(hipMemcpyAsync(fields_time_out, field_dev, (size_t)F * (T + 1) * cells * 4, hipMemcpyDeviceToHost, e->stream));
   if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, sweeps_dev, (size_t)F * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
+}
+
+int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                              const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, const float* start, const float* goal,
+                              const int32_t* field_of, const int32_t* field_goal_cell, const int32_t* field_scene, float* waypoints_out,
+                              int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* waits_out,
+                              int32_t* leave_out, int32_t* arrive_out, uint8_t* occ_time_out, int32_t* fields_time_out,
+                              int32_t* sweeps_out) {
+  return plan_time_run(e, spec, walls, hzf, tm, start, goal, field_of, field_goal_cell, field_scene, waypoints_out, n_waypoints_out, count_out,
+                       status_out, cost_out, waits_out, leave_out, arrive_out, occ_time_out, fields_time_out, sweeps_out, nullptr);
+}
+
+// ---- line-of-sight smoothing of a time plan (mobrob_ppo_plan_grid_time_smooth): a leg is tested against every layer it spans --
+int mobrob_ppo_plan_grid_time_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                                     const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t margin, const float* start,
+                                     const float* goal, const int32_t* field_of, const int32_t* field_goal_cell, const int32_t* field_scene,
+                                     float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out,
+                                     int32_t* cost_out, int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out, int32_t* moves_out,
+                                     uint8_t* occ_time_out, int32_t* fields_time_out, int32_t* sweeps_out, int16_t* next_blocked_out) {
+  const PlanTimeSmooth sm{margin, moves_out, next_blocked_out};
+  return plan_time_run(e, spec, walls, hzf, tm, start, goal, field_of, field_goal_cell, field_scene, waypoints_out, n_waypoints_out, count_out,
+                       status_out, cost_out, waits_out, leave_out, arrive_out, occ_time_out, fields_time_out, sweeps_out, &sm);
 }
 
 // ---- prioritised planning inside a team (mobrob_ppo_plan_grid_team): a mate's planned walk as one more moving obstacle ---------

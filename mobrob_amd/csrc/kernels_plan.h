@@ -929,4 +929,184 @@ __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team(const PlanTeamA
   }
 }
 
+// ---- line-of-sight smoothing of a time plan (mobrob_ppo_plan_grid_time_smooth; the rule: goal_rules.grid_next_blocked /
+// grid_los_time / grid_smooth_time / grid_path_smooth_time) -------------------------------------------------------------------------
+// A straight leg is tested against EVERY layer it spans.  nb[t][c]: the first layer from t on in which cell c is not clear
+// (kPlanNeverBlocked: none), so "c is clear in the layers lo .. hi" is nb[lo][c] > hi, one load whatever the span.
+constexpr short kPlanNeverBlocked = 32767;   // kPlanLayersMax is 256: a short holds every layer
+
+struct PlanNextBlockedArgs {
+  int G, T;
+  const unsigned char* blk;   // [S][T + 1][G][G] cells that are not clear: k_plan_occupancy_time's maps (margin 0) or k_plan_dilate's of them
+  short* nb;                  // [S][T + 1][G][G] out
+};
+
+// grid (G * G / 256, S), 256 threads (G * G is a multiple of 256): a thread scans its cell's T + 1 layers from the tail down
+__global__ __launch_bounds__(256) void k_plan_next_blocked(PlanNextBlockedArgs a) {
+  const int cells = a.G * a.G, c = blockIdx.x * 256 + threadIdx.x;
+  const size_t scene_off = (size_t)blockIdx.y * (a.T + 1) * cells;
+  short first = kPlanNeverBlocked;
+  for (int t = a.T; t >= 0; --t) {
+    if (a.blk[scene_off + (size_t)t * cells + c]) first = (short)t;
+    a.nb[scene_off + (size_t)t * cells + c] = first;
+  }
+}
+
+// goal_rules.grid_los_time on the layer nbl = nb[lo] with the threshold hi: plan_los on the map nbl <= hi, line for line
+__device__ __forceinline__ bool plan_los_time(const short* nbl, int hi, int G, int x, int y, int x1, int y1) {
+  if (nbl[y * G + x] <= hi) return false;
+  const int dx = abs(x1 - x), dy = abs(y1 - y), sx = x1 > x ? 1 : -1, sy = y1 > y ? 1 : -1;
+  int ix = 0, iy = 0;
+  for (int it = 0; it < 2 * G && (ix < dx || iy < dy); ++it) {
+    const int t = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx;
+    if (t < 0) {
+      x += sx; ++ix;
+    } else if (t > 0) {
+      y += sy; ++iy;
+    } else {   // exactly through a cell corner: both cells that share it must be clear
+      if (nbl[y * G + x + sx] <= hi || nbl[(y + sy) * G + x] <= hi) return false;
+      x += sx; y += sy; ++ix; ++iy;
+    }
+    if (nbl[y * G + x] <= hi) return false;
+  }
+  return ix == dx && iy == dy;
+}
+
+// the action the walk of goal_rules.grid_walk_time makes as its action number t from the cell (ix, iy): 0 .. 7 a move, 8 the wait,
+// -1 none (d is not the time field of occ).  k_plan_path_time's own step, line for line; that kernel keeps its copy in place, as
+// k_plan_path keeps its copy beside plan_walk_dir.
+__device__ __forceinline__ int plan_walk_time_dir(const unsigned char* occ, const int* d, int G, int T, int t, int ix, int iy, int prev) {
+  const int cells = G * G;
+  if (t >= T) return plan_walk_dir(occ + (size_t)T * cells, d + (size_t)T * cells, G, ix, iy, prev);
+  const unsigned char* occ_t = occ + (size_t)t * cells;
+  const int* dn = d + (size_t)(t + 1) * cells;
+  const unsigned m = plan_moves(occ_t, G, ix, iy);
+  const int dc = d[(size_t)t * cells + iy * G + ix];
+  int dir = -1;
+  for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
+    if (!(m & (1u << k))) continue;
+    const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
+    if (v >= 0 && v + (k < 4 ? 5 : 7) == dc) dir = k;
+  }
+  if (prev >= 0 && (m & (1u << prev))) {   // the previous move first
+    const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
+    if (v >= 0 && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
+  }
+  if (dir < 0) {   // the wait last
+    const int v = dn[iy * G + ix];
+    if (v >= 0 && v + kPlanWait == dc) dir = 8;
+  }
+  return dir;
+}
+
+struct PlanSmoothTimeArgs {
+  PlanPathArgs p;    // k_plan_path's inputs and outputs; occ [S][T + 1][G][G], field [F][T + 1][G][G]
+  int T;
+  const short* nb;   // [S][T + 1][G][G] k_plan_next_blocked's
+  int* leave;        // [N][K] out (zeroed by the host): the action index of waypoint k's anchor
+  int* arrive;       // [N] out: actions of the whole walk
+  int* moves;        // [N] out: those of them that are moves
+};
+
+// k_plan_smooth over time: one wave per robot (grid N, 64 threads), no barrier in any loop, the ring of kPlanRing packed cells in
+// LDS.  The ring is indexed by ACTION: c[a] is the cell after a actions, a wait repeats its cell, so `walked` counts actions + 1.
+// With the anchor c[i] and base = i + 2, lane l tests plan_los_time(c[i], c[base + l]) on nb[min(i, T)] with the threshold
+// min(base + l, T): every layer the leg spans.  The first lane that fails, z = ctz(ballot), is the rule's first hidden index: c[base + z
+// - 1] is emitted and becomes the anchor.  Bounds: the walk T + G * G actions (k_plan_path_time's), the window loop T + G * G
+// rounds (base grows by at least 1 a round and ends beyond A <= T + G * G), plan_los_time 2 G steps: status 3, outputs zeroed.
+__global__ __launch_bounds__(64) void k_plan_smooth_time(PlanSmoothTimeArgs s) {
+  __shared__ unsigned short ring[kPlanRing];
+  const PlanPathArgs& a = s.p;
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int G = a.g.G, cells = G * G, P = a.P, K = a.K, T = s.T;
+  const int f = a.field_of[n];
+  const size_t scene_off = (size_t)a.field_scene[f] * (T + 1) * cells;
+  const unsigned char* occ = a.occ + scene_off;
+  const short* nb = s.nb + scene_off;
+  const int* d = a.field + (size_t)f * (T + 1) * cells;
+  const float* st = a.start + (size_t)n * P;
+  const float* gl = a.goal + (size_t)n * P;
+  float* wp = a.wp + (size_t)n * K * P;
+  int* leave = s.leave + (size_t)n * K;
+  int wx = plan_cell(a.g, st[0]), wy = plan_cell(a.g, st[1]);   // the walker
+  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
+  int count = 0, status = kPlanned, cost = -1, walked = 1, moves = 0;   // walked: cells c[0 .. walked - 1] are known
+  if (a.sweeps[f] < 0) {
+    status = kPlanUnconverged;
+  } else if (d[wy * G + wx] < 0) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d[wy * G + wx];
+    int ax = wx, ay = wy, ai = 0, base = 2, prev = -1;   // the anchor's cell and action index
+    bool done = wx == gx && wy == gy;
+    if (lane == 0) ring[0] = (unsigned short)(wy * 128 + wx);
+    for (int round = 0;; ++round) {
+      if (round > T + cells) { status = kPlanUnconverged; break; }
+      while (!done && walked <= base + 63) {   // the walk, up to the end of the window
+        if (walked > T + cells) { status = kPlanUnconverged; break; }
+        const int dir = plan_walk_time_dir(occ, d, G, T, walked - 1, wx, wy, prev);
+        if (dir < 0) { status = kPlanUnconverged; break; }
+        if (dir != 8) {
+          wx += plan_dx(dir); wy += plan_dy(dir);
+          prev = dir;
+          ++moves;
+        }
+        if (lane == 0) ring[walked & (kPlanRing - 1)] = (unsigned short)(wy * 128 + wx);
+        ++walked;
+        done = wx == gx && wy == gy;
+      }
+      if (status != kPlanned) break;
+      if (done && base >= walked) break;   // no candidate left: A = walked - 1
+      // lane 0's stores to the ring before every lane's loads from it: one wave, so a wave-level fence and no barrier
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const int idx = base + lane;
+      bool hidden = false;
+      if (idx < walked) {
+        const int c = ring[idx & (kPlanRing - 1)];
+        hidden = !plan_los_time(nb + (size_t)min(ai, T) * cells, min(idx, T), G, ax, ay, c & 127, c >> 7);
+      }
+      const unsigned long long fails = __ballot(hidden);
+      if (fails == 0) { base += 64; continue; }
+      const int j = base + __builtin_ctzll(fails) - 1;   // the last visible index: emitted, the next anchor
+      const int c = __builtin_amdgcn_readfirstlane((int)ring[j & (kPlanRing - 1)]);
+      ax = c & 127; ay = c >> 7; ai = j;
+      if (count < K && lane == 0) {
+        wp[count * P] = plan_centre(a.g, ax);
+        wp[count * P + 1] = plan_centre(a.g, ay);
+        if (P == 3) wp[count * P + 2] = gl[2];
+      }
+      ++count;
+      if (count < K && lane == 0) leave[count] = j;   // the anchor of the waypoint that follows
+      base = j + 2;
+      // the loads above before the walk's next stores to the ring
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (status == kPlanned) {
+      if (count < K && lane == 0)
+        for (int q = 0; q < P; ++q) wp[count * P + q] = gl[q];
+      ++count;
+      if (count > K) status = kPlanTruncated;
+    }
+  }
+  if (lane != 0) return;
+  int acts = walked - 1;
+  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
+    for (int q = 0; q < min(count, K) * P; ++q) wp[q] = 0.f;
+    for (int q = 0; q < K; ++q) leave[q] = 0;
+    count = 0;
+    cost = -1;
+    acts = 0;
+    moves = 0;
+  }
+  a.nwp[n] = min(count, K);
+  a.count[n] = count;
+  a.status[n] = status;
+  a.cost[n] = cost;
+  s.arrive[n] = acts;
+  s.moves[n] = moves;
+}
+
 }  // namespace mobrob

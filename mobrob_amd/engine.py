@@ -752,6 +752,11 @@ class PPOEngine:
         and keeps nothing resident, fields a plan_grid call left resident stay valid) plus waits, leave [n][K] int32, arrive
         [n] int32 and release [n][K] int32 (goal_rules.grid_release: Schedule's release steps), and on request occupancy bool
         [S][T + 1][G][G] and fields int32 [F][T + 1][G][G]."""
+        return self._plan_time(spec, walls, hazards, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy, want_fields)
+
+    def _plan_time(self, spec, walls, hazards, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy, want_fields,
+                   smooth=None, want_next_blocked=False):
+        """plan_grid_time's call (smooth None) or plan_smooth_time's (smooth: the margin): the checks and the arrays of both"""
         from ._lib import PlanSpec, PlanTime, WallsC
         from .envs import goal_rules as R
         if not isinstance(spec, R.GridSpec):
@@ -788,6 +793,8 @@ class PPOEngine:
             wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
             wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
         h, _keep = self._hazards_struct(hazards, n)
+        if smooth is not None:
+            R.plan_time_smooth_check(Fn, S, T, G, smooth)
         big = Fn * (T + 1) * G * G * 4 > R.PLAN_TIME_MAX_BYTES            # refused by name below; nothing that large is allocated here
         wp = np.zeros((n, K, P), F32)
         waits, leave = np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
@@ -795,20 +802,46 @@ class PPOEngine:
         occ = np.zeros((S, T + 1, G, G), np.uint8) if want_occupancy and not big else None
         fields = np.zeros((Fn, T + 1, G, G), np.int32) if want_fields and not big else None
         sweeps = np.zeros(Fn, np.int32)
-        check(self.lib.mobrob_ppo_plan_grid_time(
-            self._h, C.byref(sp), None if wl is None else C.byref(wl), C.byref(h), C.byref(tm), _fp(start), _fp(goal),
-            field_of.ctypes.data_as(i32), fcell.ctypes.data_as(i32), fscene.ctypes.data_as(i32), _fp(wp), nwp.ctypes.data_as(i32),
-            count.ctypes.data_as(i32), status.ctypes.data_as(i32), cost.ctypes.data_as(i32), waits.ctypes.data_as(i32),
-            leave.ctypes.data_as(i32), arrive.ctypes.data_as(i32), None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)),
-            None if fields is None else fields.ctypes.data_as(i32), sweeps.ctypes.data_as(i32)))
+        head = (self._h, C.byref(sp), None if wl is None else C.byref(wl), C.byref(h), C.byref(tm))
+        robots = (_fp(start), _fp(goal), field_of.ctypes.data_as(i32), fcell.ctypes.data_as(i32), fscene.ctypes.data_as(i32), _fp(wp),
+                  nwp.ctypes.data_as(i32), count.ctypes.data_as(i32), status.ctypes.data_as(i32), cost.ctypes.data_as(i32),
+                  waits.ctypes.data_as(i32), leave.ctypes.data_as(i32), arrive.ctypes.data_as(i32))
+        copies = (None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), None if fields is None else fields.ctypes.data_as(i32),
+                  sweeps.ctypes.data_as(i32))
+        if smooth is None:
+            check(self.lib.mobrob_ppo_plan_grid_time(*head, *robots, *copies))
+            release = R.grid_release(waits, leave, step0, layer_steps)
+        else:
+            moves = np.zeros(n, np.int32)
+            nb = np.zeros((S, T + 1, G, G), np.int16) if want_next_blocked else None
+            check(self.lib.mobrob_ppo_plan_grid_time_smooth(*head, int(smooth), *robots, moves.ctypes.data_as(i32), *copies,
+                                                            None if nb is None else nb.ctypes.data_as(C.POINTER(C.c_int16))))
+            release = R.grid_release_smooth(leave, step0, layer_steps)
         out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "waits": waits, "leave": leave,
-               "arrive": arrive, "release": R.grid_release(waits, leave, step0, layer_steps), "field_of": field_of,
+               "arrive": arrive, "release": release, "field_of": field_of,
                "field_goal_cell": fcell, "field_scene": fscene, "sweeps": sweeps, "n_scenes": int(S)}
+        if smooth is not None:
+            out["moves"] = moves
+            if nb is not None:
+                out["next_blocked"] = nb
         if occ is not None:
             out["occupancy"] = occ.astype(bool)
         if fields is not None:
             out["fields"] = fields
         return out
+
+    def plan_smooth_time(self, spec, walls=None, hazards=None, *, start, goal, step0=0, layer_steps, layers=64, max_waypoints=16, margin=1,
+                         want_occupancy=False, want_fields=False, want_next_blocked=False):
+        """plan_grid_time with line-of-sight smoothing over time (mobrob_ppo_plan_grid_time_smooth; the rule:
+        goal_rules.grid_plan_time(smooth=True), reproduced bit for bit): a straight leg is kept only where it is clear, at
+        `margin` (0 or 1) cells, in every layer it spans.  Returns plan_grid_time's dict with the smoothed waypoints,
+        n_waypoints, count and status; leave [n][K]: the action index of each waypoint's anchor; release [n][K]
+        (goal_rules.grid_release_smooth: a hold at every anchor but the start); waits all zero; moves [n] int32, the moves of
+        each walk; and on request next_blocked int16 [S][T + 1][G][G] (goal_rules.grid_next_blocked)."""
+        if isinstance(margin, bool) or margin not in (0, 1):
+            raise ValueError(f"line-of-sight margin must be 0 or 1, got {margin!r}")
+        return self._plan_time(spec, walls, hazards, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy, want_fields,
+                               smooth=int(margin), want_next_blocked=want_next_blocked)
 
     def plan_grid_team(self, spec, walls=None, hazards=None, *, teams, reserve, start, goal, step0=0, layer_steps, layers, max_waypoints=16,
                        want_occupancy=False, want_fields=False, want_walks=False, clearance=True):

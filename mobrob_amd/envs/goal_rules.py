@@ -1165,15 +1165,32 @@ def grid_release(waits, leave, step0, layer_steps):
     return np.where(waits > 0, int(step0) + leave * int(layer_steps), 0).astype(np.int32)
 
 
-def grid_plan_time(spec, walls, hazards, start, goal, K, step0=0, layer_steps=1, layers=64):
+def plan_time_smooth_check(n_fields, n_scenes, layers, cells, margin):
+    """ValueError unless margin is 0 or 1 and the time fields plus the next-blocked table (n_scenes * (layers + 1) * cells^2 * 2
+    bytes) stay within PLAN_TIME_MAX_BYTES; the engine refuses the same"""
+    if isinstance(margin, bool) or margin not in (0, 1):
+        raise ValueError(f"line-of-sight margin must be 0 or 1, got {margin!r}")
+    if (n_fields * 4 + n_scenes * 2) * (layers + 1) * cells ** 2 > PLAN_TIME_MAX_BYTES:
+        raise ValueError(f"plan_time: time fields of {n_fields} x {layers + 1} x {cells} x {cells} x 4 bytes and the next-blocked table of "
+                         f"{n_scenes} x {layers + 1} x {cells} x {cells} x 2 bytes exceed the cap of {PLAN_TIME_MAX_BYTES} bytes "
+                         f"({PLAN_TIME_MAX_BYTES >> 20} MiB)")
+
+
+def grid_plan_time(spec, walls, hazards, start, goal, K, step0=0, layer_steps=1, layers=64, smooth=False, margin=1,
+                   want_next_blocked=False):
     """The whole time plan of n robots by the rule: grid_plan's dict with occupancy bool [S][T + 1][G][G] and fields int32 [F][T +
     1][G][G] (fields numbered as plan_fields numbers them), plus waits, leave [n][K] int32, arrive [n] int32, release [n][K] int32
-    (grid_release) and layer_first, layer_number [T + 1] (grid_layer_frames)."""
+    (grid_release) and layer_first, layer_number [T + 1] (grid_layer_frames).  smooth: the paths by grid_path_smooth_time with the
+    line-of-sight `margin` (0 or 1): waypoints, n_waypoints, count, status and leave are the smoothed plan's, release is
+    grid_release_smooth's (a hold at every anchor but the start), waits is all zero, `moves` [n] int32 joins them, and with
+    want_next_blocked `next_blocked` int16 [S][T + 1][G][G] (grid_next_blocked of every scene)."""
     start, goal = np.asarray(start, np.float32), np.asarray(goal, np.float32)
     n, P = goal.shape
-    _, scene = plan_scene_time(walls, hazards)
+    S, scene = plan_scene_time(walls, hazards)
     step0, layer_steps, layers = plan_time_check(step0, layer_steps, layers)
     field_of, fcell, fscene = plan_fields(spec, None, scene, goal)
+    if smooth:
+        plan_time_smooth_check(len(fcell), S, layers, spec.cells, margin)
     if len(fcell) * (layers + 1) * spec.cells ** 2 * 4 > PLAN_TIME_MAX_BYTES:
         raise ValueError(f"plan_time: time fields of {len(fcell)} x {layers + 1} x {spec.cells} x {spec.cells} x 4 bytes exceed the cap of "
                          f"{PLAN_TIME_MAX_BYTES} bytes ({PLAN_TIME_MAX_BYTES >> 20} MiB)")
@@ -1181,17 +1198,122 @@ def grid_plan_time(spec, walls, hazards, start, goal, K, step0=0, layer_steps=1,
     occ = grid_occupancy_time(spec, walls, hazards, step0, layer_steps, layers)
     fields = np.stack([grid_time_field(occ[fscene[f]], fcell[f]) for f in range(len(fcell))])
     wp, waits, leave = np.zeros((n, K, P), np.float32), np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
-    count, status, cost, arrive = (np.zeros(n, np.int32) for _ in range(4))
+    count, status, cost, arrive, moves = (np.zeros(n, np.int32) for _ in range(5))
+    nb = np.stack([grid_next_blocked([los_blocked(o, margin) for o in occ[s]]) for s in range(S)]) if smooth else None
     for i in range(n):
         f = field_of[i]
-        w, count[i], status[i], cost[i], waits[i], leave[i], arrive[i] = grid_path_time(fields[f], occ[fscene[f]], spec, start[i], goal[i], K)
+        if smooth:
+            w, count[i], status[i], cost[i], leave[i], arrive[i], moves[i] = grid_path_smooth_time(
+                fields[f], occ[fscene[f]], spec, start[i], goal[i], K, margin, nb[fscene[f]])
+        else:
+            w, count[i], status[i], cost[i], waits[i], leave[i], arrive[i] = grid_path_time(fields[f], occ[fscene[f]], spec, start[i], goal[i], K)
         m = min(int(count[i]), K)
         wp[i, :m, :2] = w[:m]
         wp[i, :m, 2:] = goal[i, 2:]
-    return {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
-            "waits": waits, "leave": leave, "arrive": arrive, "release": grid_release(waits, leave, step0, layer_steps),
-            "occupancy": occ, "fields": fields, "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene,
-            "layer_first": first, "layer_number": number}
+    out = {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
+           "waits": waits, "leave": leave, "arrive": arrive,
+           "release": grid_release_smooth(leave, step0, layer_steps) if smooth else grid_release(waits, leave, step0, layer_steps),
+           "occupancy": occ, "fields": fields, "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene,
+           "layer_first": first, "layer_number": number}
+    if smooth:
+        out["moves"] = moves
+        if want_next_blocked:
+            out["next_blocked"] = nb
+    return out
+
+
+# ---- line-of-sight smoothing of a time plan: a straight leg is tested against EVERY layer it spans.  All integers;
+# the device (csrc/kernels_plan.h: k_plan_next_blocked, k_plan_smooth_time) is held to it bit for bit.  A kept leg from action index
+# a to b with b - a >= 2: every cell of the supercover between c[a] and c[b], both ends included, is clear at the margin in each of
+# the layers min(a, T) .. min(b, T) -- whatever the robot's speed along the leg, as long as it leaves c[a] no earlier and reaches c[b]
+# no later than the walk does.  A leg of one action is the walk's own action and carries grid_walk_time's promise only.
+PLAN_NEVER_BLOCKED = 32767   # grid_next_blocked's "in no layer from here on" (PLAN_LAYERS_MAX is 256: int16 holds every layer)
+
+
+def grid_next_blocked(blk_layers):
+    """int16 [T + 1][G][G] of the maps blk_layers [T + 1][G][G] (los_blocked of every layer): nb[t][c] is the first layer from t on
+    in which c is not clear, PLAN_NEVER_BLOCKED where there is none.  nb[T][c] = T if blk_T[c] else PLAN_NEVER_BLOCKED; for t = T -
+    1 .. 0, nb[t][c] = t if blk_t[c] else nb[t + 1][c].  So c is clear in all of the layers lo .. hi (lo <= hi <= T) exactly when
+    nb[lo][c] > hi: one load per cell per test, whatever the span."""
+    blk = np.asarray(blk_layers, bool)
+    T = blk.shape[0] - 1
+    nb = np.empty(blk.shape, np.int16)
+    nb[T] = np.where(blk[T], np.int16(T), np.int16(PLAN_NEVER_BLOCKED))
+    for t in range(T - 1, -1, -1):
+        nb[t] = np.where(blk[t], np.int16(t), nb[t + 1])
+    return nb
+
+
+class _SpanBlocked:
+    """the map `nb[lo] <= hi` of grid_los_time, a cell at a time (los_walk reads blk[y, x])"""
+
+    def __init__(self, nb, lo, hi):
+        self.row, self.hi = nb[lo], hi
+
+    def __getitem__(self, yx):
+        return self.row[yx] <= self.hi
+
+
+def grid_los_time(nb, a, b, lo, hi):
+    """Is cell b visible from cell a in every layer lo .. hi (lo <= hi <= T)?  los_walk on the map nb[lo] <= hi: the same
+    supercover, the same t == 0 corner rule, false if a is not clear; symmetric in a and b."""
+    return los_walk(_SpanBlocked(nb, int(lo), int(hi)), a, b)[0]
+
+
+def grid_smooth_time(cells, nb):
+    """Line-of-sight smoothing of grid_walk_time's cells c[0 .. A] (one per action boundary, a wait repeats its cell) -> the ascending
+    action indices kept as waypoints.  T = nb.shape[0] - 1.  Anchor i = 0, j = 1; while j < A: if grid_los_time(nb, c[i], c[j + 1],
+    min(i, T), min(j + 1, T)) then j += 1, else emit j, i = j, j += 1.  A leg of one action is never tested.  Waits are not special:
+    a leg that is clear through all its layers may skip a cell where the walk waited (the robot holds at the leg's anchor instead:
+    grid_release_smooth)."""
+    A, T, out, i, j = len(cells) - 1, nb.shape[0] - 1, [], 0, 1
+    while j < A:
+        if not grid_los_time(nb, cells[i], cells[j + 1], min(i, T), min(j + 1, T)):
+            out.append(j)
+            i = j
+        j += 1
+    return out
+
+
+def grid_path_smooth_time(field, occ_layers, spec, start_xy, goal_xy, K, margin=1, nb=None):
+    """grid_path_time with line-of-sight smoothing -> (waypoints [K][2] float32, count, status, cost, leave [K] int32, arrive, moves):
+    the waypoints are the centres of the cells grid_smooth_time keeps of the walk, then goal_xy itself; count, the first min(count,
+    K) slots, the zeroed slots, TRUNCATED, UNREACHABLE and cost = field[0][start cell] mean what they mean in grid_path_time.
+    leave[k]: the action index of waypoint k's anchor, 0 for k = 0 and the kept index of waypoint k - 1 otherwise; arrive = A, the
+    actions of the walk; moves: those of them that are moves.  nb: grid_next_blocked of the scene's layers at this margin,
+    computed once by a caller with many walks."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("max_waypoints must be >= 1")
+    wp, leave = np.zeros((K, 2), np.float32), np.zeros(K, np.int32)
+    cells, acts, status = grid_walk_time(field, occ_layers, spec, start_xy, goal_xy)
+    if status == UNREACHABLE:
+        return wp, 0, UNREACHABLE, -1, leave, 0, 0
+    if nb is None:
+        nb = grid_next_blocked([los_blocked(o, margin) for o in np.asarray(occ_layers, bool)])
+    keep = grid_smooth_time(cells, nb)
+    for count, j in enumerate(keep[:K]):
+        wp[count] = spec.centre(cells[j][0]), spec.centre(cells[j][1])
+    count = len(keep)
+    if count < K:
+        wp[count] = np.asarray(goal_xy, np.float32)[:2]
+    count += 1
+    leave[1:min(count, K)] = keep[:min(count, K) - 1]
+    sx, sy = cells[0]
+    return (wp, count, TRUNCATED if count > K else PLANNED, int(np.asarray(field)[0, sy, sx]), leave, len(acts),
+            sum(k != PLAN_WAIT_ACTION for k in acts))
+
+
+def grid_release_smooth(leave, step0, layer_steps):
+    """Schedule's release steps of a smoothed time plan, int32: step0 + leave * layer_steps where leave > 0, else 0 -- a hold at
+    EVERY anchor but the start, not only where the walk waited: a straight leg is shorter than the walk it replaces, so the robot
+    arrives early and must not enter the next leg before the first layer that leg was tested in.  ValueError where a release step
+    does not fit an int32."""
+    leave = np.asarray(leave, np.int64)
+    release = np.where(leave > 0, int(step0) + leave * int(layer_steps), 0)
+    if release.size and release.max() > 2 ** 31 - 1:
+        raise ValueError(f"plan_time: a release step of {int(release.max())} must fit an int32")
+    return release.astype(np.int32)
 
 
 # ---- prioritised planning inside a team (DESIGN 4.12.3): a mate's planned walk is one more moving obstacle in the layers.  This

@@ -15,8 +15,11 @@ Moving hazards (`hazards=MovingHazards(...)`, `layer_steps=`): th
 per action of `layer_steps` steps, a wait where waiting for a hazard to pass is cheapest -- and carries `release` steps and a
 `schedule` for the tracker (goal_rules.grid_plan_time; device: mobrob_ppo_plan_grid_time).  Teams (`teams=Teams(...)`, DESIGN
 4.12.3): inside a team the members plan in index order and every member's walk is reserved in the layers of the members after it,
-so mates are planned around each other (goal_rules.grid_plan_team; device: mobrob_ppo_plan_grid_team).  Walls as solid bodies and
-smoothing of a time plan are not planned for."""
+so mates are planned around each other (goal_rules.grid_plan_team; device: mobrob_ppo_plan_grid_team).  Smoothing over time
+(`time_smooth=True`, moving hazards without teams): a straight leg is kept only where it is clear in EVERY layer it
+spans, so a leg of two or more actions is clear whatever the robot's speed along it, and the plan holds the robot at every anchor
+until the leg's first layer (goal_rules.grid_plan_time(smooth=True); device: mobrob_ppo_plan_grid_time_smooth).  Walls as solid
+bodies and smoothing of a team plan are not planned for."""
 from __future__ import annotations
 
 import numpy as np
@@ -33,15 +36,17 @@ class GridPlanner:
     walls as the unsmoothed path, also on the first leg from an off-centre start; but a walk ALONG blocked cells has no clear
     cell to see from and keeps every cell as a waypoint -- in cluttered scenes or with a small inflate use 0).
     hazards may be a goal_rules.MovingHazards: every plan is then a time plan.  layer_steps (required then): the steps a robot is
-    given for one move or wait; layers: the actions planned in time before the conservative tail.  A time plan is not smoothed
-    (smooth=True: ValueError) and nothing of it stays resident, so every call computes.
+    given for one move or wait; layers: the actions planned in time before the conservative tail.  Nothing of a time plan stays
+    resident, so every call computes.  time_smooth: line-of-sight smoothing of every time plan, with los_margin, each leg tested
+    against every layer it spans (plan(..., time_smooth=) overrides it per call); it belongs to moving hazards without teams
+    (ValueError otherwise).  smooth= is the static smoother and stays a ValueError on a time plan.
     teams: a goal_rules.Teams: every plan is a TEAM plan, a time plan (layer_steps required, also in a static scene) in which the
     members of a team plan in index order around the walks of the members before them; reserve: the cells (Chebyshev) a walk
     reserves around itself, 0 .. 4 (None: ceil(separation / h), ValueError above 4).  Prioritised planning is incomplete: a
     member never yields to a later one, and a later member boxed in by reservations comes back UNREACHABLE."""
 
     def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
-                 smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None):
+                 smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None, time_smooth=False):
         from .envs.vec_env import DeviceGoalVecEnv
         if teams is not None and not isinstance(teams, rules.Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
@@ -57,7 +62,8 @@ class GridPlanner:
             if layer_steps is None:
                 raise ValueError("GridPlanner: moving hazards and teams need layer_steps= (the steps a robot is given for one move)")
             if smooth:
-                raise ValueError("GridPlanner: smooth=True with moving hazards or teams: smoothing over time is not supported")
+                raise ValueError("GridPlanner: smooth=True with moving hazards or teams: smoothing over time is not supported by smooth= "
+                                 "(moving hazards without teams: time_smooth=True)")
             _, self.layer_steps, self.layers = rules.plan_time_check(0, layer_steps, 64 if layers is None else layers)
         else:
             rules.plan_scene(walls, hazards)
@@ -69,6 +75,7 @@ class GridPlanner:
         if isinstance(los_margin, bool) or los_margin not in (0, 1):
             raise ValueError(f"los_margin must be 0 or 1, got {los_margin!r}")
         self.smooth, self.los_margin = bool(smooth), int(los_margin)
+        self.time_smooth = self._time_smooth_ok(time_smooth)
         self.device = isinstance(env, DeviceGoalVecEnv)
         if self.device:
             self.engine = getattr(engine, "engine", engine)
@@ -95,6 +102,13 @@ class GridPlanner:
         if teams is not None:
             self.reserve = rules.plan_team_reserve(teams, self.spec) if reserve is None else rules.plan_team_check(teams, reserve, teams.size)[1]
         self._kept = None        # the latest full plan: its goal cells, scenes and (device: resident, host: arrays) fields
+
+    def _time_smooth_ok(self, time_smooth):
+        """-> bool(time_smooth), or ValueError where it is asked for without moving hazards or with teams"""
+        if time_smooth and (self.teams is not None or not isinstance(self.hazards, rules.MovingHazards)):
+            raise ValueError("GridPlanner: time_smooth=True needs hazards that are a MovingHazards and no teams (a team plan is not smoothed; "
+                             "a static plan takes smooth=True)")
+        return bool(time_smooth)
 
     def _check(self, start, goal):
         start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
@@ -138,8 +152,8 @@ class GridPlanner:
         self._kept = out
         return out
 
-    def _plan_time(self, start, goal, K, step0, want_occupancy, want_fields):
-        """One time plan: the device call, or the NumPy rule on the host path"""
+    def _plan_time(self, start, goal, K, step0, want_occupancy, want_fields, smooth=False):
+        """One time plan: the device call, or the NumPy rule on the host path.  smooth: over time (never with teams)"""
         if self.teams is not None:
             kw = dict(step0=step0, layer_steps=self.layer_steps, layers=self.layers)
             if self.device:
@@ -147,12 +161,15 @@ class GridPlanner:
                                                   goal=goal, max_waypoints=K, want_occupancy=want_occupancy, want_fields=want_fields, **kw)
             return rules.grid_plan_team(self.spec, self.walls, self.hazards, start, goal, K, self.teams, self.reserve, want_fields=want_fields, **kw)
         if self.device:
-            return self.engine.plan_grid_time(self.spec, self.walls, self.hazards, start=start, goal=goal, step0=step0,
-                                              layer_steps=self.layer_steps, layers=self.layers, max_waypoints=K,
-                                              want_occupancy=want_occupancy, want_fields=want_fields)
-        return rules.grid_plan_time(self.spec, self.walls, self.hazards, start, goal, K, step0, self.layer_steps, self.layers)
+            kw = dict(start=start, goal=goal, step0=step0, layer_steps=self.layer_steps, layers=self.layers, max_waypoints=K,
+                      want_occupancy=want_occupancy, want_fields=want_fields)
+            if smooth:
+                return self.engine.plan_smooth_time(self.spec, self.walls, self.hazards, margin=self.los_margin, **kw)
+            return self.engine.plan_grid_time(self.spec, self.walls, self.hazards, **kw)
+        return rules.grid_plan_time(self.spec, self.walls, self.hazards, start, goal, K, step0, self.layer_steps, self.layers,
+                                    smooth=smooth, margin=self.los_margin)
 
-    def plan(self, start, goal, step0=0, *, grow=False, want_occupancy=False, want_fields=False, smooth=None):
+    def plan(self, start, goal, step0=0, *, grow=False, want_occupancy=False, want_fields=False, smooth=None, time_smooth=None):
         """start, goal [n][P] -> dict: waypoints [n][K][P] float32 (z: the goal's), n_waypoints [n] (= min(count, K)), count [n]
         waypoints of the full path, status [n] (goal_rules.PLANNED 0, UNREACHABLE 1, TRUNCATED 2; UNCONVERGED 3: a device loop hit
         its bound), cost [n] int32 (-1: unreachable), cost_distance [n] float64 = cost * h / 5 (NaN: unreachable), field_of [n],
@@ -165,16 +182,24 @@ class GridPlanner:
         which the robot holds at the anchor, 0: no hold) and `schedule`, a Schedule(release, home=start) for follow_waypoints;
         occupancy and fields then carry the layer axis, [S][T + 1][G][G] and [F][T + 1][G][G].  With teams the plan is such a time
         plan too (every robot has its own field; occupancy: the base layers) and gains team_clearance and team_crossings [n_teams]
-        (goal_rules.grid_team_clearance of the planned walks: more than `reserve` cells and no crossing between planned mates)."""
+        (goal_rules.grid_team_clearance of the planned walks: more than `reserve` cells and no crossing between planned mates).
+        time_smooth: None (the planner's setting), True or False: smoothing over time with the planner's los_margin (moving hazards
+        without teams only).  `smoothed` is then True, `moves` [n] the moves of each walk, leave[k] the action index of waypoint k's
+        anchor, release a hold at EVERY anchor but the start (goal_rules.grid_release_smooth), waits all zero; `grow` uses the
+        smoothed count.  A kept leg of two or more actions is clear in every layer it spans; the count may exceed the unsmoothed
+        plan's."""
         start, goal = self._check(start, goal)
         smooth = self.smooth if smooth is None else bool(smooth)
+        time_smooth = self.time_smooth if time_smooth is None else self._time_smooth_ok(time_smooth)
         if self.timed:
             if smooth:
-                raise ValueError("plan: smooth=True with moving hazards or teams: smoothing over time is not supported")
-            out = self._plan_time(start, goal, self.K, step0, want_occupancy, want_fields)
+                raise ValueError("plan: smooth=True with moving hazards or teams: smoothing over time is not supported by smooth= "
+                                 "(moving hazards without teams: time_smooth=True)")
+            out = self._plan_time(start, goal, self.K, step0, want_occupancy, want_fields, time_smooth)
             if grow and np.any(out["status"] == rules.TRUNCATED):
-                out = self._plan_time(start, goal, int(out["count"].max()), step0, want_occupancy, want_fields)
+                out = self._plan_time(start, goal, int(out["count"].max()), step0, want_occupancy, want_fields, time_smooth)
             out["fields_reused"] = False
+            smooth = time_smooth
         else:
             if step0 != 0:
                 raise ValueError("plan: step0 belongs to moving hazards; a static plan has no clock")
@@ -206,7 +231,8 @@ class GridPlanner:
         `callback.last` holds the latest plan (None before the first).
         With moving hazards `horizon` is required, the `horizon` of that follow_with_replanning loop: the loop makes call r of the
         callback after r * horizon steps, so the callback counts its own calls (`callback.calls`) and plans with step0 = r * horizon;
-        a robot then gets (waypoints[:count], release[:count]), which the loop hands to FollowState.replan(..., release=).
+        a robot then gets (waypoints[:count], release[:count]), which the loop hands to FollowState.replan(..., release=).  The
+        plans are smoothed over time when the planner is (`time_smooth=`); the tuples are the same.
         With teams (horizon required as well) a team with any STALLED member is planned again as a whole from where its members
         stand: every member that is not FINISHED and whose new plan is PLANNED gets (waypoints, release); finished members are
         planned too, so that they reserve their cell, and are not returned."""
