@@ -44,11 +44,12 @@ robot without one as not successful.  With --horizon and --leg-steps a stalled r
 the calls (the planner's callback).  With `--hazard-frames` the plan is made over TIME: a robot is given `--plan-layer-steps` steps
 (default 10) for one move or wait, `--plan-layers` (default 64) of them are planned against the frames in force, and where the
 cheapest plan waits for a hazard to pass the run gets the release steps as its schedule (so --release / --stagger and
---plan-smooth are excluded).  `--plan-time-smooth` (with --hazard-frames, without --team-size) smooths such a plan over time: a
+--plan-smooth are excluded).  `--plan-time-smooth` (with --hazard-frames or --team-size) smooths such a plan over time: a
 straight leg is kept only where it is clear, at --plan-los-margin, in every layer it spans, and the schedule holds the robot at
 every anchor until the leg's first layer.  With `--team-size` the mates of a team are planned around each other the same way (a time plan, also
 in a static scene): `--plan-reserve` cells are kept around every planned walk, and a line reports the smallest planned team
-clearance beside the run's measured conflicts.  `--plan-smooth` smooths every plan by line
+clearance beside the run's measured conflicts; with `--plan-time-smooth` a team plan's legs are at most `--plan-max-leg` actions long
+(default 8, 0: no cap) and every leg is reserved whole for the mates that plan later.  `--plan-smooth` smooths every plan by line
 of sight (fewer waypoints: only the cells a straight leg cannot skip), `--plan-los-margin` (0 or 1, default 1) is the clearance of
 that test in cells; a second line then reports the waypoints and the moves per planned robot.
 """
@@ -79,7 +80,7 @@ def check_chain(max_steps, horizon, leg_steps):
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
-           plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False):
+           plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None):
     calls = check_chain(max_steps, horizon, leg_steps)
     if (goal is None) == (waypoints is None):
         raise ValueError("give --waypoints or --goal, not both")
@@ -120,6 +121,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             raise ValueError("--release / --stagger exclude --goal with --hazard-frames or --team-size: the time plan makes the schedule")
         planner = GridPlanner(env, walls=wl, hazards=hz, cells=int(plan_cells), engine=policy, smooth=bool(plan_smooth),
                               los_margin=int(plan_los_margin), time_smooth=bool(plan_time_smooth),
+                              **(dict(max_leg=None if int(plan_max_leg) == 0 else int(plan_max_leg)) if plan_max_leg is not None else {}),
                               **(dict(layer_steps=int(plan_layer_steps), layers=int(plan_layers)) if timed else {}),
                               **(dict(teams=teams, reserve=None if plan_reserve is None else int(plan_reserve)) if teams is not None else {}))
         plan = planner.plan(start, goals, grow=True)
@@ -210,7 +212,9 @@ def build_parser():
     ap.add_argument("--plan-cells", type=int, default=64, help="grid cells a side of the planner (32, 64, 128)")
     ap.add_argument("--plan-smooth", action="store_true", default=False, help="smooth the planned paths by line of sight")
     ap.add_argument("--plan-time-smooth", action="store_true", default=False,
-                    help="with --goal and --hazard-frames (no --team-size): smooth the time plan, every leg tested in every layer it spans")
+                    help="with --goal and --hazard-frames or --team-size: smooth the time plan, every leg tested in every layer it spans")
+    ap.add_argument("--plan-max-leg", type=int, default=None,
+                    help="with --plan-time-smooth and --team-size: the actions of a smoothed leg at most (default 8; 0: no cap)")
     ap.add_argument("--plan-los-margin", type=int, default=1, choices=(0, 1), help="cells a smoothed leg keeps clear on either side")
     ap.add_argument("--plan-layer-steps", type=int, default=10, help="with --hazard-frames or --team-size: steps a robot is given for one move or wait")
     ap.add_argument("--plan-reserve", type=int, default=None,
@@ -254,4 +258,4 @@ if __name__ == "__main__":
            walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius,
            goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells,
            plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin, plan_layer_steps=args.plan_layer_steps,
-           plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth)
+           plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg)

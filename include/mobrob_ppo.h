@@ -841,8 +841,8 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
  *             test 64 candidates against the anchor at once, a ballot and a count of trailing zeros find the first that is hidden.
  *             k_plan_dilate: the cells that are not clear at margin 1, once per set of resident fields, kept beside them.  Runs on the
  *             engine's stream in the planner's own buffers; nothing a training step reads or writes is touched.
- * Still out of scope: smoothing of a team plan (mobrob_ppo_plan_grid_team), walls as solid bodies of the simulation.  Smoothing of a
- * time plan: mobrob_ppo_plan_grid_time_smooth.  Team-mates as obstacles: mobrob_ppo_plan_grid_team.
+ * Still out of scope: walls as solid bodies of the simulation.  Smoothing of a time plan: mobrob_ppo_plan_grid_time_smooth.
+ * Team-mates as obstacles: mobrob_ppo_plan_grid_team; smoothed: mobrob_ppo_plan_grid_team_smooth.
  * MOBROB_ERR_INVALID before any launch or copy for: a NULL argument (scene aside), margin not 0 or 1, n_robots < 1, pos_dim not 2 or 3,
  * cells not 32 / 64 / 128, max_waypoints < 1, n_fields outside 1 .. n_robots, n_scenes < 1, extent, h, inv_h not finite and > 0 or
  * h * inv_h not 1 within 1e-5, cells / n_scenes / n_fields not the resident fields', a missing scene index with several scenes, a
@@ -928,7 +928,7 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
  *             lane l tests c[i] against c[base + l] on nb[min(i, T)] with the threshold min(base + l, T) (base = i + 2 at first,
  *             + 64 after a window without a hidden cell), a ballot and a count of trailing zeros find the first hidden index.  Every call computes in the time plans' own buffer and keeps nothing
  *             resident; runs on the engine's stream; nothing a training step reads or writes is touched.
- * Still out of scope: smoothing of a team plan (a smoothed leg would have to be reserved as a swept region), walls as solid bodies.
+ * Smoothing of a team plan: mobrob_ppo_plan_grid_team_smooth.  Still out of scope: walls as solid bodies.
  * MOBROB_ERR_INVALID before any launch or copy for everything mobrob_ppo_plan_grid_time refuses (waits_out aside, moves_out included
  * in "a NULL argument"), and for: margin not 0 or 1, time fields plus the table of n_scenes * (layers + 1) * cells * cells * 2 bytes
  * above MOBROB_PLAN_TIME_MAX_BYTES. */
@@ -978,6 +978,52 @@ int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
                               int32_t* leave_out /* [n][K] */, int32_t* arrive_out /* [n] */, int32_t* sweeps_out /* [n] or NULL */,
                               uint16_t* walk_out /* [n][walk_cap] or NULL */, int32_t walk_cap, uint8_t* occ_time_out /* or NULL */,
                               int32_t* fields_team_out /* [n][T + 1][G][G] or NULL */, int32_t* workgroups_out /* or NULL */);
+
+/* ---- smoothing of a team plan: capped line-of-sight legs, reserved as swept regions ------------------------------------------------
+ * mobrob_ppo_plan_grid_team with mobrob_ppo_plan_grid_time_smooth's waypoints.  The rule is stated once in
+ * mobrob_amd/envs/goal_rules.py (grid_leg_cells, grid_smooth_time(max_leg), grid_reserve_legs, grid_team_clearance_legs,
+ * grid_plan_team(smooth=True)) and reproduced bit for bit.
+ *   map       member m plans on occ_t = base_t OR the swept reservations of the members 0 .. m - 1.  Field and walk are
+ *             mobrob_ppo_plan_grid_team's, unchanged, on that map; the table nb is mobrob_ppo_plan_grid_time_smooth's built on that
+ *             same map at `margin`, so it is the member's own.
+ *   smooth    mobrob_ppo_plan_grid_time_smooth's loop with one more condition: the leg from anchor i to j + 1 is kept only if it is
+ *             visible AND j + 1 - i <= max_leg.  max_leg = 1 keeps every cell of the walk (the reservation is then
+ *             mobrob_ppo_plan_grid_team's); INT32_MAX: no cap.
+ *   legs      the anchors are 0, the kept indices, A.  A leg (a, b) of one action has the cells {c[a], c[b]}; a longer one every cell
+ *             the sight line visits: both ends, every cell stepped into, both cells that share a corner the line passes through.
+ *   reserve   P_t, where the member can be during action t: the cells of the leg with a <= t < b for t < A, {c[A]} from A on.  Layer
+ *             t < T holds every cell within Chebyshev distance `reserve` of P_t, the tail layer T of any P_t, t >= min(T, A).  A member
+ *             without a walk reserves its start cell in every layer.
+ *   guarantee two mates that keep to their legs -- leaving no anchor before its release step (leave, as
+ *             mobrob_ppo_plan_grid_time_smooth's) and reaching the next no later than the walk does -- are in cells more than
+ *             `reserve` apart whatever their speeds.  Not promised: more planned robots than mobrob_ppo_plan_grid_team plans (a long leg
+ *             reserves all of itself for all of its span: hence max_leg), fewer waypoints, anything about a later member whose start
+ *             cell an earlier member's leg covers (status 1).
+ *   outputs   mobrob_ppo_plan_grid_team's, with leave_out and moves_out as mobrob_ppo_plan_grid_time_smooth's, waits_out zeroed, and
+ *             keep_out [n][keep_cap] or NULL: the first min(count - 1, keep_cap) kept indices of every robot, the other slots 0 (count - 1
+ *             of them exist: ask again with more room where that is above keep_cap).  Status 3: a loop bound (cells * cells sweeps,
+ *             T + cells * cells actions or window rounds): count 0, cost -1, arrive 0, moves 0, waypoints, leave and kept indices zeroed,
+ *             and the member reserves its start cell.
+ *   kernels   k_plan_occupancy_time for the base layers, as it is; k_plan_team_smooth: a workgroup of 1024 threads per team at a time,
+ *             per member four phases: field and table (the layer's blocked bytes in LDS: the byte at margin 0, the OR of its 3 x 3
+ *             neighbours at margin 1), the walk by one thread, the smoothing by one wave (64 candidates at once, ballot and count of
+ *             trailing zeros), the stamps by all threads (a wave per leg, a lane per layer of its span).  Scratch per workgroup: 7 bytes
+ *             a cell and layer (field 4, table 2, reservation 1) plus the walk; the workgroups are min(teams, compute units,
+ *             MOBROB_PLAN_TIME_MAX_BYTES / that).  LDS: 9 bytes a cell + 64.
+ * MOBROB_ERR_INVALID before any launch or copy for everything mobrob_ppo_plan_grid_team refuses (moves_out included in "a NULL
+ * argument"), and for: margin not 0 or 1, max_leg < 1, keep_cap < 1 with keep_out, one workgroup's scratch above
+ * MOBROB_PLAN_TIME_MAX_BYTES, a workgroup's LDS above the device's limit. */
+int mobrob_ppo_plan_grid_team_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                                     const mobrob_hazard_frames_t* hazards /* or NULL */, const mobrob_plan_time_t* time,
+                                     int32_t team_size, int32_t reserve, int32_t margin /* 0 or 1 */, int32_t max_leg /* >= 1 */,
+                                     const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */,
+                                     float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */,
+                                     int32_t* count_out /* [n] */, int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */,
+                                     int32_t* waits_out /* [n][K] */, int32_t* leave_out /* [n][K] */, int32_t* arrive_out /* [n] */,
+                                     int32_t* moves_out /* [n] */, int32_t* sweeps_out /* [n] or NULL */,
+                                     uint16_t* walk_out /* [n][walk_cap] or NULL */, int32_t walk_cap,
+                                     int32_t* keep_out /* [n][keep_cap] or NULL */, int32_t keep_cap, uint8_t* occ_time_out /* or NULL */,
+                                     int32_t* fields_team_out /* [n][T + 1][G][G] or NULL */, int32_t* workgroups_out /* or NULL */);
 
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment

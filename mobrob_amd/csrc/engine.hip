@@ -294,6 +294,7 @@ struct mobrob_ppo_engine {
   char* plan_team_buf = nullptr;
   size_t plan_team_bytes = 0;
   bool plan_team_lds_set = false;     // k_plan_team's dynamic-LDS attribute is raised once
+  bool plan_team_smooth_lds_set = false;   // and k_plan_team_smooth's
 };
 
 namespace {
@@ -4485,15 +4486,31 @@ int mobrob_ppo_plan_grid_time_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_s
 }
 
 // ---- prioritised planning inside a team (mobrob_ppo_plan_grid_team): a mate's planned walk as one more moving obstacle ---------
-int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
-                              const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t reserve,
-                              const float* start, const float* goal, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
-                              int32_t* status_out, int32_t* cost_out, int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out,
-                              int32_t* sweeps_out, uint16_t* walk_out, int32_t walk_cap, uint8_t* occ_time_out, int32_t* fields_team_out,
-                              int32_t* workgroups_out) {
+// what mobrob_ppo_plan_grid_team_smooth adds to a team plan
+struct PlanTeamSmooth {
+  int32_t margin, max_leg;
+  int32_t* moves_out;
+  int32_t* keep_out;   // [N][keep_cap] or null
+  int32_t keep_cap;
+};
+
+// mobrob_ppo_plan_grid_team (sm null: k_plan_team) and mobrob_ppo_plan_grid_team_smooth (k_plan_team_smooth): one set of checks
+static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                         const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t reserve,
+                         const float* start, const float* goal, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
+                         int32_t* status_out, int32_t* cost_out, int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out,
+                         int32_t* sweeps_out, uint16_t* walk_out, int32_t walk_cap, uint8_t* occ_time_out, int32_t* fields_team_out,
+                         int32_t* workgroups_out, const PlanTeamSmooth* sm) {
   if (!e || !spec || !tm || !start || !goal || !waypoints_out || !n_waypoints_out || !count_out || !status_out || !cost_out || !waits_out ||
       !leave_out || !arrive_out)
     return fail(MOBROB_ERR_INVALID, "plan_team: null argument");
+  if (sm) {
+    if (!sm->moves_out) return fail(MOBROB_ERR_INVALID, "plan_team: null argument");
+    if (sm->margin != 0 && sm->margin != 1) return fail(MOBROB_ERR_INVALID, "plan_team: line-of-sight margin must be 0 or 1, got %d", sm->margin);
+    if (sm->max_leg < 1) return fail(MOBROB_ERR_INVALID, "plan_team: max_leg must be >= 1, got %d", sm->max_leg);
+    if (sm->keep_out && sm->keep_cap < 1) return fail(MOBROB_ERR_INVALID, "plan_team: keep_cap must be >= 1 with keep_out");
+    if (sm->keep_out && (int64_t)spec->n_robots * sm->keep_cap > INT_MAX) return fail(MOBROB_ERR_INVALID, "plan_team: n_robots * keep_cap must fit an int32");
+  }
   if (spec->reuse_id != 0) return fail(MOBROB_ERR_INVALID, "plan_team: reuse_id must be 0 (a team plan keeps nothing resident)");
   const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes;
   const int cells = G * G, T = tm->layers;
@@ -4528,33 +4545,40 @@ int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   if (field_bytes > MOBROB_PLAN_TIME_MAX_BYTES || (fields_team_out && (uint64_t)N * field_bytes > MOBROB_PLAN_TIME_MAX_BYTES))
     return fail(MOBROB_ERR_INVALID, "plan_team: time fields of %d x %d x %d x %d x 4 bytes exceed the cap of %u bytes (256 MiB)",
                 fields_team_out ? N : 1, T + 1, G, G, (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
-  const size_t team_lds = plan_team_lds_bytes(G, T);
+  // one workgroup's scratch: the field alone, or with smoothing the field, the next-blocked table and the reservation (7 bytes a cell and layer)
+  const uint64_t wg_bytes = sm ? (uint64_t)plan_team_smooth_wg_bytes(G, T) : (uint64_t)plan_team_wg_ints(G, T) * 4u;
+  if (sm && wg_bytes > MOBROB_PLAN_TIME_MAX_BYTES)
+    return fail(MOBROB_ERR_INVALID, "plan_team: one team's field, next-blocked table and reservation of %d x %d x %d x 7 bytes exceed the cap of %u bytes (256 MiB)",
+                T + 1, G, G, (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
+  const size_t team_lds = sm ? plan_team_smooth_lds_bytes(G) : plan_team_lds_bytes(G, T);
   int cus = 0;
   {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid_time checks k_plan_field_time's
     int limit = 0;
     if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
     if (team_lds > (size_t)limit)
-      return fail(MOBROB_ERR_INVALID, "plan_team: k_plan_team needs %zu bytes of LDS at %d cells and %d layers, the device allows %d per workgroup",
-                  team_lds, G, T, limit);
+      return fail(MOBROB_ERR_INVALID, "plan_team: %s needs %zu bytes of LDS at %d cells and %d layers, the device allows %d per workgroup",
+                  sm ? "k_plan_team_smooth" : "k_plan_team", team_lds, G, T, limit);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device_id) != hipSuccess || cus < 1) cus = 1;
   }
   // the workgroups in flight: at most the teams, the compute units, and what the cap on scratch fields allows
   const int n_teams = N / team_size;
-  const int W = (int)std::min<uint64_t>(std::min(n_teams, cus), MOBROB_PLAN_TIME_MAX_BYTES / field_bytes);
+  const int W = (int)std::min<uint64_t>(std::min(n_teams, cus), MOBROB_PLAN_TIME_MAX_BYTES / (sm ? wg_bytes : field_bytes));
   std::vector<int32_t> lfirst(T + 1, 0), lnumber(T + 1, 1);   // without frames: a static scene, its own single frame in every layer
   if (hzf) plan_layer_frames(hzf, tm, lfirst, lnumber);
   const int Mw = walls ? walls->max_walls : 0, Mh = hzf ? hzf->max_hazards : 0, NF = hzf ? hzf->n_frames : 1;
   if (!hzf) hz_counts.assign(S, 0);
   const size_t hz_floats = (size_t)S * NF * Mh * 3;
-  if ((int64_t)N * (6 + 2 * (int64_t)K + (int64_t)K * P) > INT_MAX)
-    return fail(MOBROB_ERR_INVALID, "plan_team: n_robots * (6 + 2 * max_waypoints + max_waypoints * pos_dim) must fit an int32");
-  const size_t wg_ints = plan_team_wg_ints(G, T), n_in = (size_t)2 * N * P + N, n_out = (size_t)N * (6 + 2 * K + K * P);
+  const int heads = sm ? 7 : 6;   // the [N] arrays at the front of the outputs: smoothing adds `moves`
+  if ((int64_t)N * (heads + 2 * (int64_t)K + (int64_t)K * P) > INT_MAX)
+    return fail(MOBROB_ERR_INVALID, "plan_team: n_robots * (%d + 2 * max_waypoints + max_waypoints * pos_dim) must fit an int32", heads);
+  const size_t n_in = (size_t)2 * N * P + N, n_out = (size_t)N * (heads + 2 * K + K * P);
   EvalCarve call;
-  const size_t o_occ = call.add((size_t)S * (T + 1) * cells), o_args = call.add(sizeof(PlanTeamArgs)), o_wg = call.add((size_t)W * wg_ints * 4),
+  const size_t o_occ = call.add((size_t)S * (T + 1) * cells), o_args = call.add(sizeof(PlanTeamArgs)), o_wg = call.add((size_t)W * wg_bytes),
                o_in = call.add(n_in * 4), o_out = call.add(n_out * 4), o_field = call.add(fields_team_out ? (size_t)N * field_bytes : 0),
                o_walk = call.add(walk_out ? (size_t)N * walk_cap * 2 : 0), o_lfirst = call.add((size_t)(T + 1) * 4),
                o_lnumber = call.add((size_t)(T + 1) * 4), o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4),
-               o_nwall = call.add((size_t)S * 4), o_hz = call.add(std::max<size_t>(hz_floats, 1) * 4), o_nhz = call.add((size_t)S * 4);
+               o_nwall = call.add((size_t)S * 4), o_hz = call.add(std::max<size_t>(hz_floats, 1) * 4), o_nhz = call.add((size_t)S * 4),
+               o_smargs = call.add(sm ? sizeof(PlanTeamSmoothArgs) : 0), o_keep = call.add(sm && sm->keep_out ? (size_t)N * sm->keep_cap * 4 : 0);
   if (const int rc = grow_plan_buf(e, e->plan_team_buf, e->plan_team_bytes, call.total)) return rc;
   const auto mine = [&](size_t off) { return e->plan_team_buf + off; };
   unsigned char* occ_dev = reinterpret_cast<unsigned char*>(mine(o_occ));
@@ -4580,7 +4604,7 @@ int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   // the base layers: the time plan's own kernel, launched as it is (a static scene: one frame)
   hipLaunchKernelGGL(k_plan_occupancy_time, dim3(cells / 256, T + 1, S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
   HIPC(hipGetLastError());
-  if (!e->plan_team_lds_set) {   // up to 152 KB at 128 cells and 256 layers: above the 64 KB a kernel gets without asking
+  if (!sm && !e->plan_team_lds_set) {   // up to 152 KB at 128 cells and 256 layers: above the 64 KB a kernel gets without asking
     HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_team), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)plan_team_lds_bytes(128, kPlanLayersMax)));
     e->plan_team_lds_set = true;
@@ -4596,13 +4620,30 @@ int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   ta.fields = fields_team_out ? reinterpret_cast<int*>(mine(o_field)) : nullptr;
   ta.walk = walk_out ? reinterpret_cast<unsigned short*>(mine(o_walk)) : nullptr;
   PlanTeamArgs* args_dev = reinterpret_cast<PlanTeamArgs*>(mine(o_args));
-  HIPC(hipMemcpyAsync(args_dev, &ta, sizeof(ta), hipMemcpyHostToDevice, e->stream));
+  PlanTeamSmoothArgs* smargs_dev = reinterpret_cast<PlanTeamSmoothArgs*>(mine(o_smargs));
+  PlanTeamSmoothArgs sa{};
+  if (sm) {
+    if (!e->plan_team_smooth_lds_set) {   // 144 KB at 128 cells: above the 64 KB a kernel gets without asking
+      HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_team_smooth), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)plan_team_smooth_lds_bytes(128)));
+      e->plan_team_smooth_lds_set = true;
+    }
+    sa.t = ta; sa.margin = sm->margin; sa.max_leg = sm->max_leg; sa.keep_cap = sm->keep_out ? sm->keep_cap : 0;
+    sa.keep = sm->keep_out ? reinterpret_cast<int*>(mine(o_keep)) : nullptr;
+    HIPC(hipMemcpyAsync(smargs_dev, &sa, sizeof(sa), hipMemcpyHostToDevice, e->stream));
+    if (sa.keep) HIPC(hipMemsetAsync(sa.keep, 0, (size_t)N * sm->keep_cap * 4, e->stream));
+  } else {
+    HIPC(hipMemcpyAsync(args_dev, &ta, sizeof(ta), hipMemcpyHostToDevice, e->stream));
+  }
   HIPC(hipMemcpyAsync(in_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(in_dev + (size_t)N * P, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
   if (scene) HIPC(hipMemcpyAsync(in_dev + (size_t)2 * N * P, scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
-  HIPC(hipMemsetAsync(out_dev + (size_t)6 * N, 0, (n_out - (size_t)6 * N) * 4, e->stream));   // waits, leave, waypoints
+  HIPC(hipMemsetAsync(out_dev + (size_t)heads * N, 0, (n_out - (size_t)heads * N) * 4, e->stream));   // waits, leave, waypoints
   if (ta.walk) HIPC(hipMemsetAsync(ta.walk, 0, (size_t)N * walk_cap * 2, e->stream));
-  hipLaunchKernelGGL(k_plan_team, dim3(W), dim3(kPlanFieldThreads), team_lds, e->stream, static_cast<const PlanTeamArgs*>(args_dev));
+  if (sm)
+    hipLaunchKernelGGL(k_plan_team_smooth, dim3(W), dim3(kPlanFieldThreads), team_lds, e->stream, static_cast<const PlanTeamSmoothArgs*>(smargs_dev));
+  else
+    hipLaunchKernelGGL(k_plan_team, dim3(W), dim3(kPlanFieldThreads), team_lds, e->stream, static_cast<const PlanTeamArgs*>(args_dev));
   HIPC(hipGetLastError());
   const auto back = [&](void* dst, size_t off_ints, size_t n_ints) {
     return hipMemcpyAsync(dst, out_dev + off_ints, n_ints * 4, hipMemcpyDeviceToHost, e->stream);
@@ -4614,15 +4655,41 @@ int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
   HIPC(back(cost_out, 3 * n1, n1));
   HIPC(back(arrive_out, 4 * n1, n1));
   if (sweeps_out) HIPC(back(sweeps_out, 5 * n1, n1));
-  HIPC(back(waits_out, 6 * n1, n1 * K));
-  HIPC(back(leave_out, 6 * n1 + n1 * K, n1 * K));
-  HIPC(back(waypoints_out, 6 * n1 + 2 * n1 * K, n1 * K * P));
+  const size_t h1 = (size_t)heads * n1;
+  if (sm) HIPC(back(sm->moves_out, 6 * n1, n1));
+  HIPC(back(waits_out, h1, n1 * K));
+  HIPC(back(leave_out, h1 + n1 * K, n1 * K));
+  HIPC(back(waypoints_out, h1 + 2 * n1 * K, n1 * K * P));
+  if (sm && sm->keep_out) HIPC(hipMemcpyAsync(sm->keep_out, sa.keep, (size_t)N * sm->keep_cap * 4, hipMemcpyDeviceToHost, e->stream));
   if (walk_out) HIPC(hipMemcpyAsync(walk_out, ta.walk, (size_t)N * walk_cap * 2, hipMemcpyDeviceToHost, e->stream));
   if (occ_time_out) HIPC(hipMemcpyAsync(occ_time_out, occ_dev, (size_t)S * (T + 1) * cells, hipMemcpyDeviceToHost, e->stream));
   if (fields_team_out) HIPC(hipMemcpyAsync(fields_team_out, ta.fields, (size_t)N * field_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   if (workgroups_out) *workgroups_out = W;
   return MOBROB_OK;
+}
+
+int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                              const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t reserve,
+                              const float* start, const float* goal, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
+                              int32_t* status_out, int32_t* cost_out, int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out,
+                              int32_t* sweeps_out, uint16_t* walk_out, int32_t walk_cap, uint8_t* occ_time_out, int32_t* fields_team_out,
+                              int32_t* workgroups_out) {
+  return plan_team_run(e, spec, walls, hzf, tm, team_size, reserve, start, goal, waypoints_out, n_waypoints_out, count_out, status_out, cost_out,
+                       waits_out, leave_out, arrive_out, sweeps_out, walk_out, walk_cap, occ_time_out, fields_team_out, workgroups_out, nullptr);
+}
+
+// ---- smoothing of a team plan (mobrob_ppo_plan_grid_team_smooth): capped line-of-sight legs, reserved as swept regions --------
+int mobrob_ppo_plan_grid_team_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                                     const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t reserve,
+                                     int32_t margin, int32_t max_leg, const float* start, const float* goal, float* waypoints_out,
+                                     int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out, int32_t* cost_out,
+                                     int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out, int32_t* moves_out, int32_t* sweeps_out,
+                                     uint16_t* walk_out, int32_t walk_cap, int32_t* keep_out, int32_t keep_cap, uint8_t* occ_time_out,
+                                     int32_t* fields_team_out, int32_t* workgroups_out) {
+  const PlanTeamSmooth sm{margin, max_leg, moves_out, keep_out, keep_cap};
+  return plan_team_run(e, spec, walls, hzf, tm, team_size, reserve, start, goal, waypoints_out, n_waypoints_out, count_out, status_out, cost_out,
+                       waits_out, leave_out, arrive_out, sweeps_out, walk_out, walk_cap, occ_time_out, fields_team_out, workgroups_out, &sm);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

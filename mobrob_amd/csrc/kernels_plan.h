@@ -1109,4 +1109,376 @@ __global__ __launch_bounds__(64) void k_plan_smooth_time(PlanSmoothTimeArgs s) {
   s.moves[n] = moves;
 }
 
+// ---- smoothing of a team plan (mobrob_ppo_plan_grid_team_smooth; the rule: goal_rules.grid_leg_cells / grid_reserve_legs /
+// grid_plan_team(smooth=True)) ------------------------------------------------------------------------------------------------------
+// k_plan_team with line-of-sight legs, here because it needs plan_los_time.  A smoothed leg is reserved as a SWEPT region: every
+// cell of its supercover (both ends, every cell stepped into, both cells at a corner), dilated by r, in EVERY layer of its span, so
+// the member may be anywhere on the leg at any time of the span.  The earlier members' reservations are a byte map of this workgroup
+// in global scratch, res [T + 1][G][G]; it replaces k_plan_team's Chebyshev test against c[t], c[t + 1] and its tail stamps.  The
+// member's map occ_t = base_t OR res_t gives its field, its walk and ITS next-blocked table nb (k_plan_next_blocked's meaning, at the
+// margin), all in this workgroup's scratch.  Legs are capped at max_leg actions: a long leg reserves all of itself for all of its span.
+struct PlanTeamSmoothArgs {
+  PlanTeamArgs t;     // k_plan_team's, with t.wg: per workgroup plan_team_smooth_wg_bytes(G, T) bytes: field int [T + 1][G][G] | nb short
+                      // [T + 1][G][G] | res byte [T + 1][G][G] | wk: the walk's cells c[0 .. A], packed iy * 128 + ix, 2 bytes each | kp:
+                      // the kept indices, 2 bytes each;  t.out: n_waypoints | count | status | cost | arrive | sweeps | moves, [N] each |
+                      // waits [N][K] (left zero) | leave [N][K] | waypoints [N][K][P] (float); from waits on zeroed by the host
+  int margin;         // 0 or 1: the cells a leg keeps clear on either side
+  int max_leg;        // >= 1: the actions of a leg at most
+  int keep_cap;       // entries per robot in `keep`
+  int* keep;          // [N][keep_cap] out or null (zeroed by the host): the first min(count - 1, keep_cap) kept indices
+};
+// entries of wk and of kp: a walk has at most T + G * G actions
+__host__ __device__ inline size_t plan_team_smooth_walk_cap(int G, int T) { return ((size_t)T + (size_t)G * G + 8) & ~(size_t)7; }
+__host__ __device__ inline size_t plan_team_smooth_wg_bytes(int G, int T) {
+  return (size_t)(T + 1) * G * G * 7 + plan_team_smooth_walk_cap(G, T) * 4;
+}
+// LDS bytes of k_plan_team_smooth: k_plan_field_time's two layers and one byte per cell, then 16 words handed from phase to phase
+inline size_t plan_team_smooth_lds_bytes(int G) { return (size_t)G * G * (2 * sizeof(int) + 1) + 64; }
+
+struct PlanTeamSmoothWg {
+  int* field;
+  short* nb;
+  unsigned char* res;
+  unsigned short* wk;
+  unsigned short* kp;
+};
+__device__ __forceinline__ PlanTeamSmoothWg plan_team_smooth_wg(const PlanTeamSmoothArgs& s) {
+  const int G = s.t.g.G, T = s.t.T;
+  const size_t lc = (size_t)(T + 1) * G * G;
+  char* base = reinterpret_cast<char*>(s.t.wg) + blockIdx.x * plan_team_smooth_wg_bytes(G, T);
+  PlanTeamSmoothWg w;
+  w.field = reinterpret_cast<int*>(base);
+  w.nb = reinterpret_cast<short*>(base + lc * 4);
+  w.res = reinterpret_cast<unsigned char*>(base + lc * 6);
+  w.wk = reinterpret_cast<unsigned short*>(base + lc * 7);
+  w.kp = w.wk + plan_team_smooth_walk_cap(G, T);
+  return w;
+}
+
+// is a cell within `margin` (0 or 1) of (x, y) that lies in the grid blocked?  (goal_rules.los_blocked, a cell at a time.)  Nine loads
+// without a branch: the neighbours are clamped into the grid, where a clamped one repeats a cell of the neighbourhood; at margin 0
+// all nine are the cell itself.
+template <class Occ>
+__device__ __forceinline__ bool plan_near_blocked(const Occ* occ, int G, int x, int y, int margin) {
+  const int x0 = max(x - margin, 0), x1 = min(x + margin, G - 1), r0 = max(y - margin, 0) * G, r1 = y * G, r2 = min(y + margin, G - 1) * G;
+  return (occ[r0 + x0] | occ[r0 + x] | occ[r0 + x1] | occ[r1 + x0] | occ[r1 + x] | occ[r1 + x1] | occ[r2 + x0] | occ[r2 + x] | occ[r2 + x1]) != 0;
+}
+
+// One member's field AND next-blocked table, by the whole workgroup -> the sweeps of the tail's relaxation (-1: bound hit).
+// plan_team_field's recurrence; the layer map is the base layer OR the reservation byte.  The same pass over the layers, tail first,
+// writes nb from the layer's blocked bytes in LDS: the byte itself at margin 0, the OR over the 3 x 3 neighbours at margin 1; nb[t +
+// 1][c] is read back by the thread that wrote it.
+__device__ __noinline__ int plan_team_smooth_field(const PlanTeamSmoothArgs* __restrict__ sp, int n, int* lds) {
+  const PlanTeamArgs& a = sp->t;
+  const int G = a.g.G, T = a.T, cells = G * G, tid = threadIdx.x, margin = sp->margin;
+  const int gs = 31 - __clz(G), gm = G - 1;   // G is a power of two: cell c is (c & gm, c >> gs)
+  struct { int* lds; } f{lds};
+  const int scene = a.has_scene ? reinterpret_cast<const int*>(a.in + 2 * a.N * a.P)[n] : 0;
+  const float* gl = a.in + (a.N + n) * a.P;
+  const int goal = plan_cell(a.g, gl[1]) * G + plan_cell(a.g, gl[0]);
+  int* d = f.lds;
+  int* e = f.lds + cells;
+  unsigned char* moves = reinterpret_cast<unsigned char*>(f.lds + 2 * cells);
+  const unsigned char* occ_scene = a.occ + (size_t)scene * (T + 1) * cells;
+  const PlanTeamSmoothWg wg = plan_team_smooth_wg(*sp);
+  int* field = wg.field;
+  short* nb = wg.nb;
+  const unsigned char* res = wg.res;
+  int* out = a.fields ? a.fields + n * (T + 1) * cells : nullptr;
+  const unsigned char* occ_T = occ_scene + (size_t)T * cells;
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) e[c] = (occ_T[c] | res[T * cells + c]) ? 1 : 0;
+  __syncthreads();
+  bool terminal = e[goal] == 0;
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    const bool blocked = e[c] != 0;
+    moves[c] = blocked ? 0 : (unsigned char)plan_moves(e, G, c & gm, c >> gs);
+    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
+  }
+  __syncthreads();
+  int sweeps = -1;
+  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
+    int changed = 0;
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      const unsigned mv = moves[c];
+      if (mv == 0 || c == goal) continue;
+      const int cur = d[c];
+      int best = cur;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (mv & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
+      if (best < cur) { d[c] = best; changed = 1; }
+    }
+    __syncthreads();   // this sweep's stores before the next sweep's loads
+    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
+  }
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    field[T * cells + c] = e[c] ? -1 : d[c];
+    if (out) out[T * cells + c] = d[c] >= kPlanInf ? -1 : d[c];
+    const bool hid = plan_near_blocked(e, G, c & gm, c >> gs, margin);
+    nb[T * cells + c] = hid ? (short)T : kPlanNeverBlocked;
+  }
+  int* nxt = d;   // layer t + 1
+  int* cur = e;   // layer t
+  for (int t = T - 1; t >= 0; --t) {
+    const unsigned char* occ_t = occ_scene + (size_t)t * cells;
+    // layer t's map into `moves` (the tail's moves are done with): the base layer, or reserved by an earlier member in this layer
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) moves[c] = (occ_t[c] | res[t * cells + c]) ? 1 : 0;
+    __syncthreads();   // the map before its readers; also e's last readers (the tail's write-out) before the first layer's stores
+    terminal = terminal && moves[goal] == 0;
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      int best = kPlanInf;
+      const bool blocked = moves[c] != 0;
+      if (!blocked) {
+        if (c == goal && terminal) {
+          best = 0;
+        } else {
+          const unsigned mv = plan_moves(moves, G, c & gm, c >> gs);
+          best = nxt[c] + kPlanWait;
+#pragma unroll
+          for (int k = 0; k < 8; ++k)
+            if (mv & (1u << k)) best = min(best, nxt[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
+          best = min(best, kPlanInf);   // kPlanInf + a cost: still "none"
+        }
+      }
+      cur[c] = best;
+      field[t * cells + c] = blocked ? -1 : best;
+      if (out) out[t * cells + c] = best >= kPlanInf ? -1 : best;
+      const bool hid = plan_near_blocked(moves, G, c & gm, c >> gs, margin);
+      nb[t * cells + c] = hid ? (short)t : nb[(t + 1) * cells + c];
+    }
+    __syncthreads();
+    int* const swap = nxt; nxt = cur; cur = swap;
+  }
+  return sweeps;
+}
+
+// The walk of one member, by one thread: plan_team_walk's loop on this workgroup's scratch field, ending where d_t[c] == 0.  It leaves
+// ALL of c[0 .. A] in wk (global scratch: the smoothing reads any of them) and hands over hand[0] = A, [1] = status, [2] = cost,
+// [3] = moves.  A member without a walk: c[0] = its start cell, A = 0.
+__device__ __noinline__ void plan_team_smooth_walk(const PlanTeamSmoothArgs* __restrict__ sp, int n, int sweeps, int* hand) {
+  const PlanTeamArgs& a = sp->t;
+  const int G = a.g.G, T = a.T, cells = G * G, P = a.P;
+  const PlanTeamSmoothWg wg = plan_team_smooth_wg(*sp);
+  const int* field = wg.field;
+  unsigned short* wk = wg.wk;
+  unsigned short* wout = a.walk ? a.walk + n * a.walk_cap : nullptr;
+  const float* st = a.in + n * P;
+  int ix = plan_cell(a.g, st[0]), iy = plan_cell(a.g, st[1]);
+  int status = kPlanned, cost = -1, acts = 0, moves = 0;
+  wk[0] = (unsigned short)(iy * 128 + ix);
+  if (wout) wout[0] = wk[0];
+  const int d0 = field[iy * G + ix];
+  if (sweeps < 0) {
+    status = kPlanUnconverged;
+  } else if (d0 < 0 || d0 >= kPlanInf) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d0;
+    int prev = -1;
+    for (;;) {
+      const int t = min(acts, T);
+      const int* dt = field + t * cells;
+      const int dc = dt[iy * G + ix];
+      if (dc == 0) break;
+      if (acts >= T + cells) { status = kPlanUnconverged; break; }
+      const int* dn = field + min(t + 1, T) * cells;
+      const unsigned mv = plan_moves_field(dt, G, ix, iy);
+      int dir = -1;
+      for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
+        if (!(mv & (1u << k))) continue;
+        const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
+        if (v >= 0 && v < kPlanInf && v + (k < 4 ? 5 : 7) == dc) dir = k;
+      }
+      if (prev >= 0 && (mv & (1u << prev))) {   // the previous move first
+        const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
+        if (v >= 0 && v < kPlanInf && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
+      }
+      if (dir < 0 && t < T) {   // the wait last
+        const int v = dn[iy * G + ix];
+        if (v >= 0 && v < kPlanInf && v + kPlanWait == dc) dir = 8;
+      }
+      if (dir < 0) { status = kPlanUnconverged; break; }   // not a team field of these layers: cannot happen after a converged tail
+      ++acts;
+      if (dir != 8) {
+        ix += plan_dx(dir); iy += plan_dy(dir);
+        prev = dir;
+        ++moves;
+      }
+      const unsigned short cell = (unsigned short)(iy * 128 + ix);   // c[acts]; acts <= T + cells < plan_team_smooth_walk_cap
+      wk[acts] = cell;
+      if (wout && acts < a.walk_cap) wout[acts] = cell;
+    }
+  }
+  if (status != kPlanned) {   // parked: the start cell alone; nothing of a walk that was given up is handed out
+    if (wout)
+      for (int j = 1; j < min(acts + 1, a.walk_cap); ++j) wout[j] = 0;
+    acts = 0; moves = 0; cost = -1;
+  }
+  hand[0] = acts; hand[1] = status; hand[2] = cost; hand[3] = moves;
+}
+
+// The smoothing of one member, by the workgroup's first wave: k_plan_smooth_time's window on the finished walk.  With the anchor c[i]
+// and base = i + 2, lane l tests the leg to c[base + l] on nb[min(i, T)] against the threshold min(base + l, T), and its length base +
+// l - i against max_leg.  The first lane that fails, z = ctz(ballot), is the rule's first hidden or over-cap index: c[base + z - 1] is
+// kept and becomes the anchor.  Lane 0 writes the member's outputs and hands over hand[0] = A, hand[4] = the number of kept indices.
+__device__ __noinline__ void plan_team_smooth_legs(const PlanTeamSmoothArgs* __restrict__ sp, int n, int sweeps, int* hand) {
+  const PlanTeamArgs& a = sp->t;
+  const int G = a.g.G, T = a.T, cells = G * G, P = a.P, K = a.K, N = a.N, lane = threadIdx.x;
+  const int max_leg = sp->max_leg, keep_cap = sp->keep_cap;
+  const PlanTeamSmoothWg wg = plan_team_smooth_wg(*sp);
+  const short* nb = wg.nb;
+  const unsigned short* wk = wg.wk;
+  unsigned short* kp = wg.kp;
+  const float* gl = a.in + (N + n) * P;
+  int* leave = a.out + 7 * N + N * K + n * K;
+  float* wp = reinterpret_cast<float*>(a.out + 7 * N + 2 * N * K) + n * K * P;
+  int* keep = sp->keep ? sp->keep + n * keep_cap : nullptr;
+  int A = hand[0], status = hand[1], cost = hand[2], moves = hand[3];
+  int count = 0;
+  if (status == kPlanned) {
+    int ai = 0, base = 2;                              // the anchor's action index
+    int ax = wk[0] & 127, ay = wk[0] >> 7;             // and its cell
+    for (int round = 0; base <= A; ++round) {
+      if (round > T + cells) { status = kPlanUnconverged; break; }
+      const int idx = base + lane;
+      bool hidden = false;
+      if (idx <= A) {
+        const int c = wk[idx];
+        hidden = idx - ai > max_leg || !plan_los_time(nb + min(ai, T) * cells, min(idx, T), G, ax, ay, c & 127, c >> 7);
+      }
+      const unsigned long long fails = __ballot(hidden);
+      if (fails == 0) { base += 64; continue; }
+      const int j = base + __builtin_ctzll(fails) - 1;   // the last index within the cap and in sight: kept, the next anchor
+      const int c = __builtin_amdgcn_readfirstlane((int)wk[j]);
+      ax = c & 127; ay = c >> 7; ai = j;
+      if (lane == 0) {
+        kp[count] = (unsigned short)j;                   // count <= A - 1 < plan_team_smooth_walk_cap
+        if (keep && count < keep_cap) keep[count] = j;
+        if (count < K) {
+          wp[count * P] = plan_centre(a.g, ax);
+          wp[count * P + 1] = plan_centre(a.g, ay);
+          if (P == 3) wp[count * P + 2] = gl[2];
+        }
+      }
+      ++count;
+      if (count < K && lane == 0) leave[count] = j;      // the anchor of the waypoint that follows
+      base = j + 2;
+    }
+    if (status == kPlanned) {
+      if (count < K && lane == 0)
+        for (int q = 0; q < P; ++q) wp[count * P + q] = gl[q];
+      ++count;
+      if (count > K) status = kPlanTruncated;
+    }
+  }
+  if (lane != 0) return;
+  int kept = count > 0 ? count - 1 : 0;
+  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out; the member parks
+    for (int q = 0; q < min(count, K) * P; ++q) wp[q] = 0.f;
+    for (int q = 0; q < K; ++q) leave[q] = 0;
+    if (keep)
+      for (int q = 0; q < min(count, keep_cap); ++q) keep[q] = 0;
+    if (a.walk)
+      for (int q = 1; q < min(A + 1, a.walk_cap); ++q) a.walk[n * a.walk_cap + q] = 0;
+    count = 0; cost = -1; A = 0; moves = 0; kept = 0;
+  }
+  hand[0] = A;
+  hand[4] = kept;
+  int* o = a.out + n;
+  o[0] = min(count, K);
+  o[N] = count;
+  o[2 * N] = status;
+  o[3 * N] = cost;
+  o[4 * N] = A;
+  o[5 * N] = sweeps;
+  o[6 * N] = moves;
+}
+
+// The reservation of one member, by all threads: a wave per leg, a lane per layer of the leg's span.  The leg (a, b) goes into the layers
+// min(a, T) .. min(b - 1, T): a leg of one action as its two cells, a longer one as plan_los_time's supercover of c[a] .. c[b], cell by
+// cell, both cells at a corner.  One more "leg" is the end cell c[A] in the layers min(A, T) .. T; for a parked member (A = 0) that is
+// its start cell in every layer.  A round of the walk leaves one cell to stamp, or three at a corner; every cell goes through the one
+// loop over the (2 r + 1)^2 cells around it, which writes only those in the grid (the ends are cells of the walk and the supercover
+// stays inside their bounding box, so the centres are in the grid themselves).
+__device__ __noinline__ void plan_team_smooth_stamp(const PlanTeamSmoothArgs* __restrict__ sp, const int* hand) {
+  const PlanTeamArgs& a = sp->t;
+  const int G = a.g.G, T = a.T, cells = G * G, r = a.reserve, w = 2 * r + 1, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const PlanTeamSmoothWg wg = plan_team_smooth_wg(*sp);
+  const int A = hand[0], kept = hand[4], legs = A > 0 ? kept + 1 : 0;
+#pragma unroll 1
+  for (int leg = wave; leg <= legs; leg += kPlanFieldThreads / 64) {
+    const int la = leg == legs ? A : (leg == 0 ? 0 : (int)wg.kp[leg - 1]);
+    const int lb = leg == legs ? A : (leg == kept ? A : (int)wg.kp[leg]);
+    const int hi = leg == legs ? T : min(lb - 1, T);
+    const int ca = wg.wk[la], cb = wg.wk[lb];
+    const int x1 = cb & 127, y1 = cb >> 7;
+    const bool line = lb - la > 1;
+    const int dx = abs(x1 - (ca & 127)), dy = abs(y1 - (ca >> 7)), sx = x1 > (ca & 127) ? 1 : -1, sy = y1 > (ca >> 7) ? 1 : -1;
+#pragma unroll 1
+    for (int t = min(la, T) + lane; t <= hi; t += 64) {
+      unsigned char* layer = wg.res + t * cells;
+      int x = ca & 127, y = ca >> 7, ix = 0, iy = 0;
+      int qx1 = x1, qy1 = y1, qx2 = x, qy2 = y, nq = line ? 1 : 2;   // the first round: c[a], and c[b] of a leg of one action
+#pragma unroll 1
+      for (int it = 0; it <= 2 * G; ++it) {
+#pragma unroll 1
+        for (int q = 0; q < nq; ++q) {
+          const int qx = q == 0 ? x : (q == 1 ? qx1 : qx2), qy = q == 0 ? y : (q == 1 ? qy1 : qy2);
+#pragma unroll 1
+          for (int k = 0; k < w * w; ++k) {
+            const int xx = qx - r + k % w, yy = qy - r + k / w;
+            if (xx >= 0 && xx < G && yy >= 0 && yy < G) layer[yy * G + xx] = 1;
+          }
+        }
+        if (!line || !(ix < dx || iy < dy)) break;
+        const int s = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx;
+        qx1 = x + sx; qy1 = y; qx2 = x; qy2 = y + sy;   // the two cells that share the corner, where s == 0
+        nq = s == 0 ? 3 : 1;
+        if (s <= 0) { x += sx; ++ix; }
+        if (s >= 0) { y += sy; ++iy; }
+      }
+    }
+  }
+}
+
+// One workgroup of 1024 threads takes one team at a time, as k_plan_team does.  Per member four phases, each a function that is not
+// inlined and reads the arguments from memory (k_plan_team says why): the field and nb by all threads; the walk by thread 0; the
+// smoothing by the first wave; the stamps by all threads.  Every hand-off through global memory -- the zeroed and the stamped
+// reservation, the field and nb, the walk's cells, the kept indices -- is a workgroup-scope fence and then the barrier; the handed
+// words are in LDS, which the barrier orders.  Bounds: G * G sweeps, T + G * G actions, T + G * G window rounds, 2 G steps a sight
+// line: status 3 and zeroed outputs beyond, and the member parks.
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team_smooth(const PlanTeamSmoothArgs* __restrict__ sp) {
+  extern __shared__ __attribute__((aligned(16))) int plan_team_smooth_lds[];
+  const int G = sp->t.g.G, T = sp->t.T, cells = G * G, tid = threadIdx.x, size = sp->t.size, n_teams = sp->t.n_teams;
+  int* hand = plan_team_smooth_lds + 2 * cells + cells / 4;   // behind d, e and the byte map
+  for (int team = blockIdx.x; team < n_teams; team += gridDim.x) {
+    int* res4 = reinterpret_cast<int*>(plan_team_smooth_wg(*sp).res);   // (T + 1) * cells bytes, a multiple of 4096, 16-aligned
+#pragma unroll 1
+    for (int i = tid; i < (T + 1) * (cells / 4); i += kPlanFieldThreads) res4[i] = 0;
+    __threadfence_block();
+    __syncthreads();
+    for (int m = 0; m < size; ++m) {
+      const int n = team * size + m;
+      const int sweeps = plan_team_smooth_field(sp, n, plan_team_smooth_lds);
+      __threadfence_block();
+      __syncthreads();
+      if (tid == 0) plan_team_smooth_walk(sp, n, sweeps, hand);
+      __threadfence_block();
+      __syncthreads();
+      if (tid < 64) plan_team_smooth_legs(sp, n, sweeps, hand);
+      __threadfence_block();
+      __syncthreads();
+      plan_team_smooth_stamp(sp, hand);
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace mobrob

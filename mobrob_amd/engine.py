@@ -855,6 +855,28 @@ class PPOEngine:
         launched with), and on request walks (per robot the cells of its walk, as lists), occupancy bool [S][T + 1][G][G] (the base
         layers) and fields int32 [n][T + 1][G][G].  The walks come back in T + 1 + 2 G cells a robot; only where a walk is longer
         (a maze) is the call made a second time with room for the longest."""
+        return self._plan_team(spec, walls, hazards, teams, reserve, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy,
+                               want_fields, want_walks, clearance)
+
+    def plan_smooth_team(self, spec, walls=None, hazards=None, *, teams, reserve, start, goal, step0=0, layer_steps, layers, max_waypoints=16,
+                         margin=1, max_leg=8, want_occupancy=False, want_fields=False, want_walks=False, clearance=True):
+        """plan_grid_team with line-of-sight smoothing (mobrob_ppo_plan_grid_team_smooth; the rule:
+        goal_rules.grid_plan_team(smooth=True), reproduced bit for bit): a leg is kept where it is clear at `margin` (0 or 1) cells in
+        every layer it spans on the member's own map and at most `max_leg` actions long (None: no cap), and it is reserved for the
+        later members as a swept region -- all of its cells in every layer of its span.  Returns plan_grid_team's dict with the
+        smoothed waypoints, n_waypoints, count and status; leave, release and waits as plan_smooth_time's; moves [n] int32; keeps
+        (per robot the kept indices in full; a call is repeated with more room where a robot keeps more than T + 1 + 2 G);
+        team_clearance is goal_rules.grid_team_clearance_legs's (the guarantee: > reserve), team_crossings the walks' count."""
+        from .envs import goal_rules as R
+        if isinstance(margin, bool) or margin not in (0, 1):
+            raise ValueError(f"line-of-sight margin must be 0 or 1, got {margin!r}")
+        cap = 2 ** 31 - 1 if max_leg is None else R.plan_max_leg_check(max_leg)
+        return self._plan_team(spec, walls, hazards, teams, reserve, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy,
+                               want_fields, want_walks, clearance, smooth=(int(margin), cap))
+
+    def _plan_team(self, spec, walls, hazards, teams, reserve, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy,
+                   want_fields, want_walks, clearance, smooth=None):
+        """plan_grid_team's call (smooth None) or plan_smooth_team's (smooth: (margin, max_leg)): the checks and the arrays of both"""
         from ._lib import PlanSpec, PlanTime, WallsC
         from .envs import goal_rules as R
         if not isinstance(spec, R.GridSpec):
@@ -899,32 +921,51 @@ class PPOEngine:
         big = one > R.PLAN_TIME_MAX_BYTES or n * one > R.PLAN_TIME_MAX_BYTES     # refused by name below; nothing that large is allocated here
         fields = np.zeros((n, T + 1, G, G) if not big else (1,), np.int32) if want_fields else None
         occ = np.zeros((S, T + 1, G, G), np.uint8) if want_occupancy else None
-        walk_cap = T + 1 + 2 * G
+        walk_cap = keep_cap = T + 1 + 2 * G
+        if smooth is not None and R.plan_team_smooth_bytes(G, T) > R.PLAN_TIME_MAX_BYTES:
+            raise ValueError(f"plan_team: one team's field, next-blocked table and reservation of {T + 1} x {G} x {G} x 7 bytes exceed the cap "
+                             f"of {R.PLAN_TIME_MAX_BYTES} bytes ({R.PLAN_TIME_MAX_BYTES >> 20} MiB)")
+        u16 = C.POINTER(C.c_uint16)
         while True:                                                        # a second call only where a walk is longer than walk_cap
             wp = np.zeros((n, K, P), F32)
             waits, leave = np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
-            nwp, count, status, cost, arrive, sweeps = (np.zeros(n, np.int32) for _ in range(6))
+            nwp, count, status, cost, arrive, sweeps, moves = (np.zeros(n, np.int32) for _ in range(7))
             walk = np.zeros((n, walk_cap), np.uint16)
             wgs = C.c_int32(0)
-            check(self.lib.mobrob_ppo_plan_grid_team(
-                self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None else C.byref(h), C.byref(tm), size, r, _fp(start),
-                _fp(goal), _fp(wp), nwp.ctypes.data_as(i32), count.ctypes.data_as(i32), status.ctypes.data_as(i32), cost.ctypes.data_as(i32),
-                waits.ctypes.data_as(i32), leave.ctypes.data_as(i32), arrive.ctypes.data_as(i32), sweeps.ctypes.data_as(i32),
-                walk.ctypes.data_as(C.POINTER(C.c_uint16)), walk_cap, None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)),
-                None if fields is None else fields.ctypes.data_as(i32), C.byref(wgs)))
-            if int(arrive.max()) + 1 <= walk_cap:
-                break
-            walk_cap = int(arrive.max()) + 1
+            head = (self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None else C.byref(h), C.byref(tm), size, r)
+            robots = (_fp(start), _fp(goal), _fp(wp), nwp.ctypes.data_as(i32), count.ctypes.data_as(i32), status.ctypes.data_as(i32),
+                      cost.ctypes.data_as(i32), waits.ctypes.data_as(i32), leave.ctypes.data_as(i32), arrive.ctypes.data_as(i32))
+            copies = (None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), None if fields is None else fields.ctypes.data_as(i32),
+                      C.byref(wgs))
+            if smooth is None:
+                check(self.lib.mobrob_ppo_plan_grid_team(*head, *robots, sweeps.ctypes.data_as(i32), walk.ctypes.data_as(u16), walk_cap, *copies))
+                if int(arrive.max()) + 1 <= walk_cap:
+                    break
+            else:
+                keep = np.zeros((n, keep_cap), np.int32)
+                check(self.lib.mobrob_ppo_plan_grid_team_smooth(*head, smooth[0], smooth[1], *robots, moves.ctypes.data_as(i32),
+                                                                sweeps.ctypes.data_as(i32), walk.ctypes.data_as(u16), walk_cap,
+                                                                keep.ctypes.data_as(i32), keep_cap, *copies))
+                if int(arrive.max()) + 1 <= walk_cap and int(count.max()) - 1 <= keep_cap:
+                    break
+                keep_cap = max(keep_cap, int(count.max()) - 1)
+            walk_cap = max(walk_cap, int(arrive.max()) + 1)
         cells = np.stack([walk & 127, walk >> 7], axis=-1)
         out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "waits": waits, "leave": leave,
                "arrive": arrive, "release": R.grid_release(waits, leave, step0, layer_steps), "field_of": np.arange(n, dtype=np.int32),
                "field_goal_cell": (lambda gx, gy: (gy * G + gx).astype(np.int32))(*spec.cell_of(goal[:, :2])),
                "field_scene": np.zeros(n, np.int32) if scene is None else np.asarray(scene, np.int32).copy(), "sweeps": sweeps,
                "n_scenes": int(S), "workgroups": int(wgs.value)}
+        walks = [[(int(x), int(y)) for x, y in cells[i, :int(arrive[i]) + 1]] for i in range(n)] if want_walks or (smooth is not None and clearance) else None
+        if smooth is not None:
+            out["release"], out["moves"] = R.grid_release_smooth(leave, step0, layer_steps), moves
+            out["keeps"] = [keep[i, :max(int(count[i]) - 1, 0)].tolist() for i in range(n)]
         if clearance:
             out["team_clearance"], out["team_crossings"] = R.grid_team_clearance_cells(cells, arrive.astype(np.int64) + 1, size, T)
+            if smooth is not None:
+                out["team_clearance"] = R.grid_team_clearance_legs(walks, R.plan_team_keeps_with_walks(out["keeps"], status), size, T)
         if want_walks:
-            out["walks"] = [[(int(x), int(y)) for x, y in cells[i, :int(arrive[i]) + 1]] for i in range(n)]
+            out["walks"] = walks
         if occ is not None:
             out["occupancy"] = occ.astype(bool)
         if fields is not None:

@@ -1244,6 +1244,13 @@ def grid_next_blocked(blk_layers):
     return nb
 
 
+def plan_max_leg_check(max_leg):
+    """-> max_leg as an int, or ValueError: the cap on a smoothed leg's length in actions, an integer >= 1"""
+    if isinstance(max_leg, bool) or not isinstance(max_leg, (int, np.integer)) or int(max_leg) < 1:
+        raise ValueError(f"plan_team: max_leg must be an integer >= 1 (None: no cap), got {max_leg!r}")
+    return int(max_leg)
+
+
 class _SpanBlocked:
     """the map `nb[lo] <= hi` of grid_los_time, a cell at a time (los_walk reads blk[y, x])"""
 
@@ -1260,15 +1267,18 @@ def grid_los_time(nb, a, b, lo, hi):
     return los_walk(_SpanBlocked(nb, int(lo), int(hi)), a, b)[0]
 
 
-def grid_smooth_time(cells, nb):
+def grid_smooth_time(cells, nb, max_leg=None):
     """Line-of-sight smoothing of grid_walk_time's cells c[0 .. A] (one per action boundary, a wait repeats its cell) -> the ascending
     action indices kept as waypoints.  T = nb.shape[0] - 1.  Anchor i = 0, j = 1; while j < A: if grid_los_time(nb, c[i], c[j + 1],
     min(i, T), min(j + 1, T)) then j += 1, else emit j, i = j, j += 1.  A leg of one action is never tested.  Waits are not special:
     a leg that is clear through all its layers may skip a cell where the walk waited (the robot holds at the leg's anchor instead:
-    grid_release_smooth)."""
+    grid_release_smooth).  max_leg (None: no cap, an integer >= 1 otherwise): the leg from c[i] to c[j + 1] is kept only if it is
+    clear AND j + 1 - i <= max_leg actions long; max_leg = 1 keeps every cell of the walk."""
+    if max_leg is not None:
+        max_leg = plan_max_leg_check(max_leg)
     A, T, out, i, j = len(cells) - 1, nb.shape[0] - 1, [], 0, 1
     while j < A:
-        if not grid_los_time(nb, cells[i], cells[j + 1], min(i, T), min(j + 1, T)):
+        if (max_leg is not None and j + 1 - i > max_leg) or not grid_los_time(nb, cells[i], cells[j + 1], min(i, T), min(j + 1, T)):
             out.append(j)
             i = j
         j += 1
@@ -1521,17 +1531,122 @@ def grid_team_clearance_cells(cells, lengths, size, layers=None):
     return clear.astype(np.int32), cross.astype(np.int32)
 
 
-def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0, layer_steps=None, layers=None, want_fields=True):
+def grid_leg_cells(a, b):
+    """The cells los_walk visits between cell a and cell b, [(ix, iy), ...] in the order of the walk: both ends, every cell stepped
+    into, and at a t == 0 corner both cells that share the corner.  Symmetric in a and b as a set; a == b gives [a]."""
+    (x, y), (x1, y1) = (int(a[0]), int(a[1])), (int(b[0]), int(b[1]))
+    dx, dy = abs(x1 - x), abs(y1 - y)
+    sx, sy = (1 if x1 > x else -1), (1 if y1 > y else -1)
+    ix = iy = 0
+    out = [(x, y)]
+    while ix < dx or iy < dy:
+        t = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx
+        if t < 0:
+            x, ix = x + sx, ix + 1
+        elif t > 0:
+            y, iy = y + sy, iy + 1
+        else:
+            out += [(x + sx, y), (x, y + sy)]
+            x, y, ix, iy = x + sx, y + sy, ix + 1, iy + 1
+        out.append((x, y))
+    return out
+
+
+def grid_team_legs(walk, keep):
+    """The legs of a member with the walk c[0 .. A] and the kept indices `keep` -> [(a, b, cells [k][2] int64), ...]: its anchors
+    are 0, keep..., A; a leg (a, b) of one action has the cells {c[a], c[b]}, a longer one grid_leg_cells(c[a], c[b])."""
+    A = len(walk) - 1
+    anchors = [0] + [int(k) for k in keep] + [A]
+    legs = []
+    for a, b in zip(anchors[:-1], anchors[1:]):
+        if b > a:
+            legs.append((a, b, np.asarray([walk[a], walk[b]] if b - a == 1 else grid_leg_cells(walk[a], walk[b]), np.int64).reshape(-1, 2)))
+    return legs
+
+
+def grid_leg_layers(walk, keep, layers):
+    """Where a member can be, a layer at a time -> a list of T + 1 arrays [k][2] (ix, iy).  With P_t the cells of the leg that
+    contains action t (a <= t < b) for t < A and {c[A]} for t >= A: entry t < T is P_t, the tail entry T the union of the P_t with
+    t >= min(T, A).  A member without a walk (its start cell alone, keep empty) is in c[0] in every layer."""
+    T, A = int(layers), len(walk) - 1
+    end = np.asarray([walk[A]], np.int64).reshape(1, 2)
+    out = [end] * (T + 1)
+    tail = [end]
+    for a, b, cells in grid_team_legs(walk, keep):
+        for t in range(a, min(b, T)):
+            out[t] = cells
+        if b > T:
+            tail.append(cells)
+    out[T] = np.concatenate(tail)
+    return out
+
+
+def grid_reserve_legs(walk, keep, layers, G, reserve):
+    """The swept reservation of a smoothed walk, bool [T + 1][G][G]: layer t holds every in-grid cell within Chebyshev distance
+    `reserve` of grid_leg_layers(walk, keep, layers)[t] -- a straight leg reserves ALL of itself in EVERY layer of its span, so
+    the member may be anywhere on the leg at any time of the span.  When every leg is one action this is grid_reserve(walk, ...)."""
+    T, r = int(layers), int(reserve)
+    res = np.zeros((T + 1, G, G), bool)
+    for t, cells in enumerate(grid_leg_layers(walk, keep, T)):
+        for x, y in cells:
+            res[t, max(y - r, 0):y + r + 1, max(x - r, 0):x + r + 1] = True
+    return res
+
+
+def grid_team_clearance_legs(walks, keeps, size, layers):
+    """The checker of a smoothed team plan, independent of the planner: it sees walks and kept indices only, never maps or fields.
+    walks: per robot the cells of its walk; keeps: per robot the kept indices in full, None for a robot WITHOUT a walk (parked:
+    UNREACHABLE or UNCONVERGED) -> clearance [n_teams] int32: over every pair of mates that both have a walk, the minimum over all
+    layers t <= T of the Chebyshev distance between their sets of grid_leg_layers (the tail layer: the unions); PLAN_NO_PAIR where
+    a team has no such pair (size 1).  The guarantee of grid_plan_team(smooth=True) is clearance > reserve: two mates that keep
+    to their legs -- leaving no anchor before its release and reaching the next no later than the walk does -- are in cells more
+    than `reserve` apart whatever their speeds along the legs."""
+    n, size, T = len(walks), int(size), int(layers)
+    if size < 1 or n % size != 0 or len(keeps) != n:
+        raise ValueError(f"{n} walks and {len(keeps)} lists of kept indices do not split into teams of {size}")
+    clear = np.full(n // size, PLAN_NO_PAIR, np.int64)
+    sets = [None if keeps[i] is None else grid_leg_layers(walks[i], keeps[i], T) for i in range(n)]
+    for i in range(n):
+        for j in range(i + 1, (i // size + 1) * size):
+            if sets[i] is None or sets[j] is None:
+                continue
+            for t in range(T + 1):
+                p, q = sets[i][t], sets[j][t]
+                if t and p is sets[i][t - 1] and q is sets[j][t - 1]:
+                    continue                                                  # the same two legs as in the layer before
+                clear[i // size] = min(clear[i // size], int(np.abs(p[:, None, :] - q[None, :, :]).max(axis=2).min()))
+    return clear.astype(np.int32)
+
+
+def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0, layer_steps=None, layers=None, want_fields=True,
+                   smooth=False, margin=1, max_leg=8):
     """The whole team plan of n robots by the rule: grid_plan_time's dict per robot -- there are no shared fields: field_of is the
     identity and fields is int32 [n][T + 1][G][G] (None without want_fields), each robot's own on ITS map -- with occupancy the
     BASE layers bool [S][T + 1][G][G], plus walks (per robot the cells of its walk; a robot without one: its start cell),
     team_clearance and team_crossings [n_teams] int32 (grid_team_clearance).  A member that is UNREACHABLE reserves its start cell
-    in every layer: a parked robot is an obstacle, as in team_cost."""
+    in every layer: a parked robot is an obstacle, as in team_cost.
+    smooth: member m's map is occ_t = base_t OR the earlier members' grid_reserve_legs; grid_team_field and
+    grid_walk_team run unchanged on it; nb = grid_next_blocked(los_blocked(occ_t, margin) of every t) is built on that same map, so
+    it is the member's own; keep = grid_smooth_time(cells, nb, max_leg) (max_leg None: no cap).  The outputs mean what
+    grid_path_smooth_time gives: the waypoints are the centres of the kept cells, then the goal itself; waits all zero; leave[k]
+    the action index of waypoint k's anchor; arrive, cost and `moves` as there; release = grid_release_smooth.  The dict gains
+    `keeps`, per robot the kept indices in full (not cut at K; [] without a walk).  team_clearance is then
+    grid_team_clearance_legs's and the guarantee is team_clearance > reserve: two mates that keep to their legs, leaving no anchor
+    before its release and reaching the next no later than the walk does, are in cells more than `reserve` apart whatever their
+    speeds; team_crossings stays grid_team_clearance's count on the walks; a later member that has a walk keeps > reserve from an
+    earlier parked mate's start cell.  NOT promised: more PLANNED robots than the unsmoothed plan (a long leg reserves all of itself
+    for all of its span, hence the cap max_leg); fewer waypoints; anything about a later member's start cell that an earlier
+    member's leg covers -- that member comes back UNREACHABLE and is reported as such."""
     start, goal = np.asarray(start, np.float32), np.asarray(goal, np.float32)
     n, P = goal.shape
     if layer_steps is None or layers is None:
         raise ValueError("plan_team: layer_steps and layers are required (a team plan is a time plan even in a static scene)")
     step0, layer_steps, T = plan_time_check(step0, layer_steps, layers)
+    if smooth:
+        if isinstance(margin, bool) or margin not in (0, 1):
+            raise ValueError(f"line-of-sight margin must be 0 or 1, got {margin!r}")
+        if max_leg is not None:
+            max_leg = plan_max_leg_check(max_leg)
     occ, S, scene = plan_team_base(spec, walls, hazards, step0, layer_steps, T)
     for sc in (walls, hazards):
         if sc is not None:
@@ -1542,13 +1657,16 @@ def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0
     if one > PLAN_TIME_MAX_BYTES or (want_fields and n * one > PLAN_TIME_MAX_BYTES):
         raise ValueError(f"plan_team: time fields of {n if want_fields else 1} x {T + 1} x {G} x {G} x 4 bytes exceed the cap of "
                          f"{PLAN_TIME_MAX_BYTES} bytes ({PLAN_TIME_MAX_BYTES >> 20} MiB)")
+    if smooth and plan_team_smooth_bytes(G, T) > PLAN_TIME_MAX_BYTES:
+        raise ValueError(f"plan_team: one team's field, next-blocked table and reservation of {T + 1} x {G} x {G} x 7 bytes exceed the cap "
+                         f"of {PLAN_TIME_MAX_BYTES} bytes ({PLAN_TIME_MAX_BYTES >> 20} MiB)")
     gx, gy = spec.cell_of(goal[:, :2])
     sx, sy = spec.cell_of(start[:, :2])
     sc = np.zeros(n, np.int32) if scene is None else np.asarray(scene, np.int32)
     fields = np.zeros((n, T + 1, G, G), np.int32) if want_fields else None
     wp, waits, leave = np.zeros((n, K, P), np.float32), np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
-    count, status, cost, arrive = (np.zeros(n, np.int32) for _ in range(4))
-    walks = []
+    count, status, cost, arrive, moves = (np.zeros(n, np.int32) for _ in range(5))
+    walks, keeps = [], []
     for i in range(n):
         if i % size == 0:
             res = np.zeros((T + 1, G, G), bool)
@@ -1556,16 +1674,63 @@ def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0
         field = grid_team_field(layers_i, int(gy[i]) * G + int(gx[i]))
         if want_fields:
             fields[i] = field
-        (w, count[i], status[i], cost[i], waits[i], leave[i], arrive[i]), cells = grid_path_team(field, layers_i, spec, start[i], goal[i], K)
+        if smooth:
+            (w, count[i], status[i], cost[i], leave[i], arrive[i], moves[i]), cells, keep = grid_path_smooth_team(
+                field, layers_i, spec, start[i], goal[i], K, margin, max_leg)
+        else:
+            (w, count[i], status[i], cost[i], waits[i], leave[i], arrive[i]), cells = grid_path_team(field, layers_i, spec, start[i], goal[i], K)
+            keep = list(range(1, len(cells) - 1))
         m = min(int(count[i]), K)
         wp[i, :m, :2] = w[:m]
         wp[i, :m, 2:] = goal[i, 2:]
         walks.append(cells if cells else [(int(sx[i]), int(sy[i]))])
-        res |= grid_reserve(walks[-1], T, G, r)
+        keeps.append(keep)
+        res |= grid_reserve_legs(walks[-1], keep, T, G, r) if smooth else grid_reserve(walks[-1], T, G, r)
     first, number = grid_layer_frames(hazards, step0, layer_steps, T) if isinstance(hazards, MovingHazards) else (None, None)
     clear, cross = grid_team_clearance(walks, size, T)
-    return {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
-            "waits": waits, "leave": leave, "arrive": arrive, "release": grid_release(waits, leave, step0, layer_steps),
-            "occupancy": occ, "fields": fields, "field_of": np.arange(n, dtype=np.int32),
-            "field_goal_cell": (gy * G + gx).astype(np.int32), "field_scene": sc.copy(), "layer_first": first, "layer_number": number,
-            "walks": walks, "team_clearance": clear, "team_crossings": cross}
+    out = {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
+           "waits": waits, "leave": leave, "arrive": arrive,
+           "release": grid_release_smooth(leave, step0, layer_steps) if smooth else grid_release(waits, leave, step0, layer_steps),
+           "occupancy": occ, "fields": fields, "field_of": np.arange(n, dtype=np.int32),
+           "field_goal_cell": (gy * G + gx).astype(np.int32), "field_scene": sc.copy(), "layer_first": first, "layer_number": number,
+           "walks": walks, "team_clearance": clear, "team_crossings": cross}
+    if smooth:
+        out["moves"], out["keeps"] = moves, keeps
+        out["team_clearance"] = grid_team_clearance_legs(walks, plan_team_keeps_with_walks(keeps, status), size, T)
+    return out
+
+
+def plan_team_smooth_bytes(G, T):
+    """bytes of one team's scratch in a smoothed team plan: the field (4), the next-blocked table (2) and the reservation (1) per
+    cell and layer; the engine holds the sum over its workgroups under PLAN_TIME_MAX_BYTES and refuses one that exceeds it"""
+    return (int(T) + 1) * int(G) ** 2 * 7
+
+
+def plan_team_keeps_with_walks(keeps, status):
+    """keeps as grid_team_clearance_legs takes them: None for the robots without a walk (UNREACHABLE, UNCONVERGED)"""
+    return [None if int(s) in (UNREACHABLE, UNCONVERGED) else list(k) for k, s in zip(keeps, status)]
+
+
+def grid_path_smooth_team(field, occ_layers, spec, start_xy, goal_xy, K, margin=1, max_leg=8, nb=None):
+    """grid_path_smooth_time on grid_walk_team's walk, the legs capped at max_leg actions -> (grid_path_smooth_time's tuple, cells of
+    the walk ([] when UNREACHABLE), kept indices in full)"""
+    K = int(K)
+    if K < 1:
+        raise ValueError("max_waypoints must be >= 1")
+    wp, leave = np.zeros((K, 2), np.float32), np.zeros(K, np.int32)
+    cells, acts, status = grid_walk_team(field, occ_layers, spec, start_xy)
+    if status == UNREACHABLE:
+        return (wp, 0, UNREACHABLE, -1, leave, 0, 0), [], []
+    if nb is None:
+        nb = grid_next_blocked([los_blocked(o, margin) for o in np.asarray(occ_layers, bool)])
+    keep = grid_smooth_time(cells, nb, max_leg)
+    for count, j in enumerate(keep[:K]):
+        wp[count] = spec.centre(cells[j][0]), spec.centre(cells[j][1])
+    count = len(keep)
+    if count < K:
+        wp[count] = np.asarray(goal_xy, np.float32)[:2]
+    count += 1
+    leave[1:min(count, K)] = keep[:min(count, K) - 1]
+    sx, sy = cells[0]
+    return ((wp, count, TRUNCATED if count > K else PLANNED, int(np.asarray(field)[0, sy, sx]), leave, len(acts),
+             sum(k != PLAN_WAIT_ACTION for k in acts)), cells, keep)

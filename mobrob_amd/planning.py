@@ -16,15 +16,20 @@ per action of `layer_steps` steps, a wait where waiting for a hazard to pass is 
 `schedule` for the tracker (goal_rules.grid_plan_time; device: mobrob_ppo_plan_grid_time).  Teams (`teams=Teams(...)`, DESIGN
 4.12.3): inside a team the members plan in index order and every member's walk is reserved in the layers of the members after it,
 so mates are planned around each other (goal_rules.grid_plan_team; device: mobrob_ppo_plan_grid_team).  Smoothing over time
-(`time_smooth=True`, moving hazards without teams): a straight leg is kept only where it is clear in EVERY layer it
-spans, so a leg of two or more actions is clear whatever the robot's speed along it, and the plan holds the robot at every anchor
-until the leg's first layer (goal_rules.grid_plan_time(smooth=True); device: mobrob_ppo_plan_grid_time_smooth).  Walls as solid
-bodies and smoothing of a team plan are not planned for."""
+(`time_smooth=True`): a straight leg is kept only where it is clear in EVERY layer it spans, so a leg of two or more
+actions is clear whatever the robot's speed along it, and the plan holds the robot at every anchor until the leg's first layer
+(goal_rules.grid_plan_time(smooth=True); device: mobrob_ppo_plan_grid_time_smooth).  With teams a kept leg is at
+most `max_leg` actions long and is reserved for the later members as a swept region, all of its cells in every layer of its span
+(goal_rules.grid_plan_team(smooth=True); device: mobrob_ppo_plan_grid_team_smooth).  Walls as solid bodies are not planned for
+(DESIGN 4.12)."""
 from __future__ import annotations
 
 import numpy as np
 
 from .envs import goal_rules as rules
+
+
+_UNSET = object()   # max_leg= not given
 
 
 class GridPlanner:
@@ -38,20 +43,26 @@ class GridPlanner:
     hazards may be a goal_rules.MovingHazards: every plan is then a time plan.  layer_steps (required then): the steps a robot is
     given for one move or wait; layers: the actions planned in time before the conservative tail.  Nothing of a time plan stays
     resident, so every call computes.  time_smooth: line-of-sight smoothing of every time plan, with los_margin, each leg tested
-    against every layer it spans (plan(..., time_smooth=) overrides it per call); it belongs to moving hazards without teams
-    (ValueError otherwise).  smooth= is the static smoother and stays a ValueError on a time plan.
+    against every layer it spans (plan(..., time_smooth=) overrides it per call); it belongs to moving hazards or teams of two or
+    more (ValueError otherwise; teams of one are refused as they always were: they have no mates, plan them without teams=).  smooth= is the static smoother and stays a ValueError on a time plan.
     teams: a goal_rules.Teams: every plan is a TEAM plan, a time plan (layer_steps required, also in a static scene) in which the
     members of a team plan in index order around the walks of the members before them; reserve: the cells (Chebyshev) a walk
     reserves around itself, 0 .. 4 (None: ceil(separation / h), ValueError above 4).  Prioritised planning is incomplete: a
-    member never yields to a later one, and a later member boxed in by reservations comes back UNREACHABLE."""
+    member never yields to a later one, and a later member boxed in by reservations comes back UNREACHABLE.  With time_smooth a
+    team plan is smoothed too (a team plan is a time plan: no MovingHazards needed): max_leg, the actions of a leg at most (8; None:
+    no cap; it belongs to teams, ValueError otherwise) -- a leg reserves all of its cells in every layer of its span, so long legs
+    shut later members out, and a member whose start cell an earlier member's leg covers comes back UNREACHABLE."""
 
     def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
-                 smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None, time_smooth=False):
+                 smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None, time_smooth=False, max_leg=_UNSET):
         from .envs.vec_env import DeviceGoalVecEnv
         if teams is not None and not isinstance(teams, rules.Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
         if teams is None and reserve is not None:
             raise ValueError("GridPlanner: reserve= belongs to teams=")
+        if max_leg is not _UNSET and teams is None:
+            raise ValueError("GridPlanner: max_leg= belongs to teams= with time_smooth (the cap on a smoothed team plan's legs)")
+        self.max_leg = 8 if max_leg is _UNSET else (None if max_leg is None else rules.plan_max_leg_check(max_leg))
         self.teams = teams
         self.timed = isinstance(hazards, rules.MovingHazards) or teams is not None
         if self.timed:
@@ -63,7 +74,7 @@ class GridPlanner:
                 raise ValueError("GridPlanner: moving hazards and teams need layer_steps= (the steps a robot is given for one move)")
             if smooth:
                 raise ValueError("GridPlanner: smooth=True with moving hazards or teams: smoothing over time is not supported by smooth= "
-                                 "(moving hazards without teams: time_smooth=True)")
+                                 "(a time plan takes time_smooth=True)")
             _, self.layer_steps, self.layers = rules.plan_time_check(0, layer_steps, 64 if layers is None else layers)
         else:
             rules.plan_scene(walls, hazards)
@@ -104,10 +115,11 @@ class GridPlanner:
         self._kept = None        # the latest full plan: its goal cells, scenes and (device: resident, host: arrays) fields
 
     def _time_smooth_ok(self, time_smooth):
-        """-> bool(time_smooth), or ValueError where it is asked for without moving hazards or with teams"""
-        if time_smooth and (self.teams is not None or not isinstance(self.hazards, rules.MovingHazards)):
-            raise ValueError("GridPlanner: time_smooth=True needs hazards that are a MovingHazards and no teams (a team plan is not smoothed; "
-                             "a static plan takes smooth=True)")
+        """-> bool(time_smooth), or ValueError where it is asked for on a plan that is not a time plan (no moving hazards, no teams) or
+        with teams of one: a team of one has no mate to plan around, so it stays refused as before (plan it without teams=)"""
+        if time_smooth and (self.teams.size < 2 if self.teams is not None else not isinstance(self.hazards, rules.MovingHazards)):
+            raise ValueError("GridPlanner: time_smooth=True needs hazards that are a MovingHazards and no teams, or teams of two or more (a team "
+                             "of one has no mates: plan it without teams=; a static plan takes smooth=True)")
         return bool(time_smooth)
 
     def _check(self, start, goal):
@@ -153,9 +165,16 @@ class GridPlanner:
         return out
 
     def _plan_time(self, start, goal, K, step0, want_occupancy, want_fields, smooth=False):
-        """One time plan: the device call, or the NumPy rule on the host path.  smooth: over time (never with teams)"""
+        """One time plan: the device call, or the NumPy rule on the host path.  smooth: over time"""
         if self.teams is not None:
             kw = dict(step0=step0, layer_steps=self.layer_steps, layers=self.layers)
+            if smooth and self.device:
+                return self.engine.plan_smooth_team(self.spec, self.walls, self.hazards, teams=self.teams, reserve=self.reserve, start=start,
+                                                    goal=goal, max_waypoints=K, margin=self.los_margin, max_leg=self.max_leg,
+                                                    want_occupancy=want_occupancy, want_fields=want_fields, **kw)
+            if smooth:
+                return rules.grid_plan_team(self.spec, self.walls, self.hazards, start, goal, K, self.teams, self.reserve, want_fields=want_fields,
+                                            smooth=True, margin=self.los_margin, max_leg=self.max_leg, **kw)
             if self.device:
                 return self.engine.plan_grid_team(self.spec, self.walls, self.hazards, teams=self.teams, reserve=self.reserve, start=start,
                                                   goal=goal, max_waypoints=K, want_occupancy=want_occupancy, want_fields=want_fields, **kw)
@@ -183,8 +202,10 @@ class GridPlanner:
         occupancy and fields then carry the layer axis, [S][T + 1][G][G] and [F][T + 1][G][G].  With teams the plan is such a time
         plan too (every robot has its own field; occupancy: the base layers) and gains team_clearance and team_crossings [n_teams]
         (goal_rules.grid_team_clearance of the planned walks: more than `reserve` cells and no crossing between planned mates).
-        time_smooth: None (the planner's setting), True or False: smoothing over time with the planner's los_margin (moving hazards
-        without teams only).  `smoothed` is then True, `moves` [n] the moves of each walk, leave[k] the action index of waypoint k's
+        time_smooth: None (the planner's setting), True or False: smoothing over time with the planner's los_margin (and, with
+        teams, max_leg; the dict then gains `keeps`, per robot the kept action indices in full, and team_clearance is
+        goal_rules.grid_team_clearance_legs's: mates that keep to their legs stay more than `reserve` cells apart whatever their
+        speeds).  `smoothed` is then True, `moves` [n] the moves of each walk, leave[k] the action index of waypoint k's
         anchor, release a hold at EVERY anchor but the start (goal_rules.grid_release_smooth), waits all zero; `grow` uses the
         smoothed count.  A kept leg of two or more actions is clear in every layer it spans; the count may exceed the unsmoothed
         plan's."""
@@ -194,7 +215,7 @@ class GridPlanner:
         if self.timed:
             if smooth:
                 raise ValueError("plan: smooth=True with moving hazards or teams: smoothing over time is not supported by smooth= "
-                                 "(moving hazards without teams: time_smooth=True)")
+                                 "(a time plan takes time_smooth=True)")
             out = self._plan_time(start, goal, self.K, step0, want_occupancy, want_fields, time_smooth)
             if grow and np.any(out["status"] == rules.TRUNCATED):
                 out = self._plan_time(start, goal, int(out["count"].max()), step0, want_occupancy, want_fields, time_smooth)
@@ -213,6 +234,8 @@ class GridPlanner:
             res["schedule"] = rules.Schedule(out["release"], home=start)
         if self.teams is not None:
             res.update({k: out[k] for k in ("team_clearance", "team_crossings")})
+            if "keeps" in out:
+                res["keeps"] = out["keeps"]
         res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
         res["smoothed"], res["moves"] = smooth, out.get("moves")
         if want_occupancy:
