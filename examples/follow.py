@@ -49,7 +49,9 @@ straight leg is kept only where it is clear, at --plan-los-margin, in every laye
 every anchor until the leg's first layer.  With `--team-size` the mates of a team are planned around each other the same way (a time plan, also
 in a static scene): `--plan-reserve` cells are kept around every planned walk, and a line reports the smallest planned team
 clearance beside the run's measured conflicts; with `--plan-time-smooth` a team plan's legs are at most `--plan-max-leg` actions long
-(default 8, 0: no cap) and every leg is reserved whole for the mates that plan later.  `--plan-smooth` smooths every plan by line
+(default 8, 0: no cap) and every leg is reserved whole for the mates that plan later; `--plan-retries R` (0 .. 8, default 0) plans
+a team whose members stayed parked again, up to R times, with those members first, and a line reports the parked members before
+and after.  `--plan-smooth` smooths every plan by line
 of sight (fewer waypoints: only the cells a straight leg cannot skip), `--plan-los-margin` (0 or 1, default 1) is the clearance of
 that test in cells; a second line then reports the waypoints and the moves per planned robot.
 """
@@ -80,7 +82,8 @@ def check_chain(max_steps, horizon, leg_steps):
 def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False, seed=0, policy=None, hazards=None,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
-           plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None):
+           plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
+           plan_retries=0):
     calls = check_chain(max_steps, horizon, leg_steps)
     if (goal is None) == (waypoints is None):
         raise ValueError("give --waypoints or --goal, not both")
@@ -123,7 +126,8 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
                               los_margin=int(plan_los_margin), time_smooth=bool(plan_time_smooth),
                               **(dict(max_leg=None if int(plan_max_leg) == 0 else int(plan_max_leg)) if plan_max_leg is not None else {}),
                               **(dict(layer_steps=int(plan_layer_steps), layers=int(plan_layers)) if timed else {}),
-                              **(dict(teams=teams, reserve=None if plan_reserve is None else int(plan_reserve)) if teams is not None else {}))
+                              **(dict(teams=teams, reserve=None if plan_reserve is None else int(plan_reserve)) if teams is not None else {}),
+                              **(dict(retries=int(plan_retries)) if int(plan_retries) != 0 else {}))
         plan = planner.plan(start, goals, grow=True)
         waypoints, n_waypoints, plan_schedule = plan["waypoints"], plan["n_waypoints"], plan.get("schedule")
         replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 else None
@@ -131,6 +135,9 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         if teams is not None:                              # beside the run's measured team conflict steps, further down
             print(f"planned team clearance: {int(plan['team_clearance'].min())} cells at the least (reserve {planner.reserve}), "
                   f"{int(plan['team_crossings'].sum())} crossings")
+        if "team_parked" in plan:
+            print(f"planned with retries: {int(plan['team_parked_first'].sum())} parked members in index order, {int(plan['team_parked'].sum())} "
+                  f"after at most {int(plan['team_rounds'].max())} rounds a team")
         if plan["smoothed"] and np.any(plan["status"] == 0):
             ok = plan["status"] == 0
             print(f"smoothed plan: {float(np.mean(plan['count'][ok]))} waypoints for {float(np.mean(plan['moves'][ok]))} moves per planned robot")
@@ -219,6 +226,8 @@ def build_parser():
     ap.add_argument("--plan-layer-steps", type=int, default=10, help="with --hazard-frames or --team-size: steps a robot is given for one move or wait")
     ap.add_argument("--plan-reserve", type=int, default=None,
                     help="with --goal and --team-size: cells a mate's planned walk reserves around itself, 0 .. 4 (default: ceil(separation / cell))")
+    ap.add_argument("--plan-retries", type=int, default=0,
+                    help="with --goal and --team-size: reordering rounds of a team plan, 0 .. 8: a team with parked members plans again, those first")
     ap.add_argument("--plan-layers", type=int, default=64, help="with --hazard-frames or --team-size: actions planned in time before the tail (1 .. 256)")
     ap.add_argument("--robots", type=int, default=1)
     ap.add_argument("--max-steps", type=int, default=1000)
@@ -258,4 +267,5 @@ if __name__ == "__main__":
            walls=None if args.walls is None else np.load(args.walls), arena=args.arena, robot_radius=args.robot_radius,
            goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells,
            plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin, plan_layer_steps=args.plan_layer_steps,
-           plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg)
+           plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg,
+           plan_retries=args.plan_retries)

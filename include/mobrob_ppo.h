@@ -965,7 +965,8 @@ int mobrob_ppo_plan_grid_time_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_s
  *             in place, T Jacobi steps, the field in the workgroup's scratch, one thread walks it.  LDS: 9 bytes a cell + 32 (T + 1) + 16.
  *             Runs on the engine's stream in buffers of its own; nothing resident changes, nothing a training step reads is touched.
  * guarantee: two PLANNED (or truncated) mates are more than `reserve` cells apart (Chebyshev, between cell centres, over both cells
- * of each action) and never cross diagonally inside a 2 x 2 block.  Prioritised planning is incomplete: a member never yields.
+ * of each action) and never cross diagonally inside a 2 x 2 block.  Prioritised planning is incomplete: in this call a member never
+ * yields; mobrob_ppo_plan_grid_team_rounds plans a team again with its failed members first.
  * MOBROB_ERR_INVALID before any launch or copy for everything mobrob_ppo_plan_grid_time refuses of the spec, the scenes, the frames and
  * the time (spec->n_fields must be n_robots), and for: team_size not 1, 2, 4, 8 or 16, n_robots % team_size != 0, reserve outside 0 .. 4,
  * mates in different scenes, walk_cap < 1 with walk_out, one field above MOBROB_PLAN_TIME_MAX_BYTES or n_robots fields above it with
@@ -978,6 +979,44 @@ int mobrob_ppo_plan_grid_team(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
                               int32_t* leave_out /* [n][K] */, int32_t* arrive_out /* [n] */, int32_t* sweeps_out /* [n] or NULL */,
                               uint16_t* walk_out /* [n][walk_cap] or NULL */, int32_t walk_cap, uint8_t* occ_time_out /* or NULL */,
                               int32_t* fields_team_out /* [n][T + 1][G][G] or NULL */, int32_t* workgroups_out /* or NULL */);
+
+/* ---- priority reordering rounds of a team plan: the members that stayed parked plan first ------------------------------------------
+ * mobrob_ppo_plan_grid_team, planned again inside the call with the failed members in front.  The rule is stated once in
+ * mobrob_amd/envs/goal_rules.py (grid_plan_team(order=), plan_team_next_order, grid_plan_team_rounds) and reproduced bit for bit.
+ *   rounds    every team on its own.  Round 0 plans in index order.  After a round the team's parked members are those without a walk
+ *             (status 1 or 3; 2, truncated, has one).  Nobody parked: stop.  Otherwise the next order is the parked members, then the
+ *             others, each in the relative order of this round; stop without planning it after `retries` (0 .. 8) reorderings or if that
+ *             order was already planned for this team (which includes: the parked members are in front already).
+ *   result    the round with the fewest parked members, the earliest on a tie: every output of mobrob_ppo_plan_grid_team is that
+ *             round's, indexed by robot.  In a round, position p of the order plans member order[p] on the base layers OR the
+ *             reservations of the members at the positions before p.  retries = 0: mobrob_ppo_plan_grid_team's outputs.
+ *   outputs   mobrob_ppo_plan_grid_team's (the cells of walk_out beyond arrive are unspecified), and team_order_out [n_teams][team_size]
+ *             (the result's order), team_rounds_out [n_teams] (rounds planned, >= 1), team_parked_out and team_parked_first_out
+ *             [n_teams] (parked members of the result and of round 0).
+ *   kernels   k_plan_occupancy_time as it is; k_plan_team_rounds: k_plan_team's workgroup, field and walk with the loop of rounds
+ *             around the member loop.  Between two rounds one thread counts the parked, builds the next order and looks it up among
+ *             the orders planned; a member's waits, leave and waypoints are zeroed before it walks again; where the last round planned
+ *             is not the best, the team is planned once more in the best order (the plan is a function of the order), which
+ *             team_rounds_out does not count: a call costs between 1 and retries + 2 team plans.  LDS: k_plan_team's + 16 +
+ *             20 (retries + 1) bytes.  Workgroups: min(teams, compute units, MOBROB_PLAN_TIME_MAX_BYTES / bytes of one field); an
+ *             environment variable MOBROB_PLAN_TIME_MAX_BYTES (decimal) lowers that cap on the scratch fields for this call, never
+ *             below one field, and nothing else.
+ * Not repaired: two mates whose start cells, or whose goal cells, are within `reserve` of each other fail in every order; an earlier
+ * member still does not know a later member's start cell; the orders tried are one chain, not all of them.
+ * MOBROB_ERR_INVALID before any launch or copy for everything mobrob_ppo_plan_grid_team refuses (the four team outputs included in "a
+ * NULL argument"), and for retries outside 0 .. 8. */
+int mobrob_ppo_plan_grid_team_rounds(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                                     const mobrob_hazard_frames_t* hazards /* or NULL */, const mobrob_plan_time_t* time,
+                                     int32_t team_size, int32_t reserve, int32_t retries /* 0 .. 8 */,
+                                     const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */,
+                                     float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */,
+                                     int32_t* count_out /* [n] */, int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */,
+                                     int32_t* waits_out /* [n][K] */, int32_t* leave_out /* [n][K] */, int32_t* arrive_out /* [n] */,
+                                     int32_t* sweeps_out /* [n] or NULL */, uint16_t* walk_out /* [n][walk_cap] or NULL */,
+                                     int32_t walk_cap, uint8_t* occ_time_out /* or NULL */,
+                                     int32_t* fields_team_out /* [n][T + 1][G][G] or NULL */, int32_t* workgroups_out /* or NULL */,
+                                     int32_t* team_order_out /* [n_teams][team_size] */, int32_t* team_rounds_out /* [n_teams] */,
+                                     int32_t* team_parked_out /* [n_teams] */, int32_t* team_parked_first_out /* [n_teams] */);
 
 /* ---- smoothing of a team plan: capped line-of-sight legs, reserved as swept regions ------------------------------------------------
  * mobrob_ppo_plan_grid_team with mobrob_ppo_plan_grid_time_smooth's waypoints.  The rule is stated once in

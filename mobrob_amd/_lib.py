@@ -223,6 +223,12 @@ SYMBOLS = {
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.c_int32, _U8, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32)]),
+    "mobrob_ppo_plan_grid_team_rounds": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardFramesC), C.POINTER(PlanTime),
+                                                   C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.c_int32, _U8,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mobrob_ppo_plan_grid_team_smooth": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardFramesC), C.POINTER(PlanTime),
                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, C.POINTER(C.c_int32),
                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -295,6 +295,7 @@ struct mobrob_ppo_engine {
   size_t plan_team_bytes = 0;
   bool plan_team_lds_set = false;     // k_plan_team's dynamic-LDS attribute is raised once
   bool plan_team_smooth_lds_set = false;   // and k_plan_team_smooth's
+  bool plan_team_rounds_lds_set = false;   // and k_plan_team_rounds's
 };
 
 namespace {
@@ -4494,13 +4495,23 @@ struct PlanTeamSmooth {
   int32_t keep_cap;
 };
 
-// mobrob_ppo_plan_grid_team (sm null: k_plan_team) and mobrob_ppo_plan_grid_team_smooth (k_plan_team_smooth): one set of checks
+// what mobrob_ppo_plan_grid_team_rounds adds to a team plan
+struct PlanTeamRounds {
+  int32_t retries;
+  int32_t* order_out;          // [n_teams][team_size]
+  int32_t* rounds_out;         // [n_teams]
+  int32_t* parked_out;         // [n_teams]
+  int32_t* parked_first_out;   // [n_teams]
+};
+
+// mobrob_ppo_plan_grid_team (sm and rr null: k_plan_team), mobrob_ppo_plan_grid_team_smooth (sm: k_plan_team_smooth) and
+// mobrob_ppo_plan_grid_team_rounds (rr: k_plan_team_rounds): one set of checks
 static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
                          const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t reserve,
                          const float* start, const float* goal, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out,
                          int32_t* status_out, int32_t* cost_out, int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out,
                          int32_t* sweeps_out, uint16_t* walk_out, int32_t walk_cap, uint8_t* occ_time_out, int32_t* fields_team_out,
-                         int32_t* workgroups_out, const PlanTeamSmooth* sm) {
+                         int32_t* workgroups_out, const PlanTeamSmooth* sm, const PlanTeamRounds* rr = nullptr) {
   if (!e || !spec || !tm || !start || !goal || !waypoints_out || !n_waypoints_out || !count_out || !status_out || !cost_out || !waits_out ||
       !leave_out || !arrive_out)
     return fail(MOBROB_ERR_INVALID, "plan_team: null argument");
@@ -4510,6 +4521,11 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
     if (sm->max_leg < 1) return fail(MOBROB_ERR_INVALID, "plan_team: max_leg must be >= 1, got %d", sm->max_leg);
     if (sm->keep_out && sm->keep_cap < 1) return fail(MOBROB_ERR_INVALID, "plan_team: keep_cap must be >= 1 with keep_out");
     if (sm->keep_out && (int64_t)spec->n_robots * sm->keep_cap > INT_MAX) return fail(MOBROB_ERR_INVALID, "plan_team: n_robots * keep_cap must fit an int32");
+  }
+  if (rr) {
+    if (!rr->order_out || !rr->rounds_out || !rr->parked_out || !rr->parked_first_out) return fail(MOBROB_ERR_INVALID, "plan_team: null argument");
+    if (rr->retries < 0 || rr->retries > kPlanRetriesMax)
+      return fail(MOBROB_ERR_INVALID, "plan_team: retries must lie in 0 .. %d, got %d", kPlanRetriesMax, rr->retries);
   }
   if (spec->reuse_id != 0) return fail(MOBROB_ERR_INVALID, "plan_team: reuse_id must be 0 (a team plan keeps nothing resident)");
   const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes;
@@ -4550,19 +4566,25 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   if (sm && wg_bytes > MOBROB_PLAN_TIME_MAX_BYTES)
     return fail(MOBROB_ERR_INVALID, "plan_team: one team's field, next-blocked table and reservation of %d x %d x %d x 7 bytes exceed the cap of %u bytes (256 MiB)",
                 T + 1, G, G, (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
-  const size_t team_lds = sm ? plan_team_smooth_lds_bytes(G) : plan_team_lds_bytes(G, T);
+  const size_t team_lds = sm ? plan_team_smooth_lds_bytes(G) : rr ? plan_team_rounds_lds_bytes(G, T, rr->retries) : plan_team_lds_bytes(G, T);
   int cus = 0;
   {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid_time checks k_plan_field_time's
     int limit = 0;
     if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
     if (team_lds > (size_t)limit)
       return fail(MOBROB_ERR_INVALID, "plan_team: %s needs %zu bytes of LDS at %d cells and %d layers, the device allows %d per workgroup",
-                  sm ? "k_plan_team_smooth" : "k_plan_team", team_lds, G, T, limit);
+                  sm ? "k_plan_team_smooth" : rr ? "k_plan_team_rounds" : "k_plan_team", team_lds, G, T, limit);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device_id) != hipSuccess || cus < 1) cus = 1;
   }
   // the workgroups in flight: at most the teams, the compute units, and what the cap on scratch fields allows
   const int n_teams = N / team_size;
-  const int W = (int)std::min<uint64_t>(std::min(n_teams, cus), MOBROB_PLAN_TIME_MAX_BYTES / (sm ? wg_bytes : field_bytes));
+  uint64_t scratch_cap = MOBROB_PLAN_TIME_MAX_BYTES;
+  if (rr) {   // the rounds' call takes a smaller cap on the scratch fields from the environment (never a larger one, at least one field's)
+    const char* v = getenv("MOBROB_PLAN_TIME_MAX_BYTES");
+    const unsigned long long asked = v ? strtoull(v, nullptr, 10) : 0;
+    if (asked) scratch_cap = std::max<uint64_t>(std::min<uint64_t>(asked, scratch_cap), field_bytes);
+  }
+  const int W = (int)std::min<uint64_t>(std::min(n_teams, cus), scratch_cap / (sm ? wg_bytes : field_bytes));
   std::vector<int32_t> lfirst(T + 1, 0), lnumber(T + 1, 1);   // without frames: a static scene, its own single frame in every layer
   if (hzf) plan_layer_frames(hzf, tm, lfirst, lnumber);
   const int Mw = walls ? walls->max_walls : 0, Mh = hzf ? hzf->max_hazards : 0, NF = hzf ? hzf->n_frames : 1;
@@ -4578,7 +4600,8 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
                o_walk = call.add(walk_out ? (size_t)N * walk_cap * 2 : 0), o_lfirst = call.add((size_t)(T + 1) * 4),
                o_lnumber = call.add((size_t)(T + 1) * 4), o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4),
                o_nwall = call.add((size_t)S * 4), o_hz = call.add(std::max<size_t>(hz_floats, 1) * 4), o_nhz = call.add((size_t)S * 4),
-               o_smargs = call.add(sm ? sizeof(PlanTeamSmoothArgs) : 0), o_keep = call.add(sm && sm->keep_out ? (size_t)N * sm->keep_cap * 4 : 0);
+               o_smargs = call.add(sm ? sizeof(PlanTeamSmoothArgs) : 0), o_keep = call.add(sm && sm->keep_out ? (size_t)N * sm->keep_cap * 4 : 0),
+               o_rargs = call.add(rr ? sizeof(PlanTeamRoundsArgs) : 0), o_team = call.add(rr ? ((size_t)N + 3 * (size_t)n_teams) * 4 : 0);
   if (const int rc = grow_plan_buf(e, e->plan_team_buf, e->plan_team_bytes, call.total)) return rc;
   const auto mine = [&](size_t off) { return e->plan_team_buf + off; };
   unsigned char* occ_dev = reinterpret_cast<unsigned char*>(mine(o_occ));
@@ -4604,7 +4627,7 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   // the base layers: the time plan's own kernel, launched as it is (a static scene: one frame)
   hipLaunchKernelGGL(k_plan_occupancy_time, dim3(cells / 256, T + 1, S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
   HIPC(hipGetLastError());
-  if (!sm && !e->plan_team_lds_set) {   // up to 152 KB at 128 cells and 256 layers: above the 64 KB a kernel gets without asking
+  if (!sm && !rr && !e->plan_team_lds_set) {   // up to 152 KB at 128 cells and 256 layers: above the 64 KB a kernel gets without asking
     HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_team), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)plan_team_lds_bytes(128, kPlanLayersMax)));
     e->plan_team_lds_set = true;
@@ -4622,6 +4645,8 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   PlanTeamArgs* args_dev = reinterpret_cast<PlanTeamArgs*>(mine(o_args));
   PlanTeamSmoothArgs* smargs_dev = reinterpret_cast<PlanTeamSmoothArgs*>(mine(o_smargs));
   PlanTeamSmoothArgs sa{};
+  PlanTeamRoundsArgs* rargs_dev = reinterpret_cast<PlanTeamRoundsArgs*>(mine(o_rargs));
+  PlanTeamRoundsArgs ra{};
   if (sm) {
     if (!e->plan_team_smooth_lds_set) {   // 144 KB at 128 cells: above the 64 KB a kernel gets without asking
       HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_team_smooth), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -4632,6 +4657,14 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
     sa.keep = sm->keep_out ? reinterpret_cast<int*>(mine(o_keep)) : nullptr;
     HIPC(hipMemcpyAsync(smargs_dev, &sa, sizeof(sa), hipMemcpyHostToDevice, e->stream));
     if (sa.keep) HIPC(hipMemsetAsync(sa.keep, 0, (size_t)N * sm->keep_cap * 4, e->stream));
+  } else if (rr) {
+    if (!e->plan_team_rounds_lds_set) {   // k_plan_team's and 180 bytes at 8 retries
+      HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_team_rounds), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)plan_team_rounds_lds_bytes(128, kPlanLayersMax, kPlanRetriesMax)));
+      e->plan_team_rounds_lds_set = true;
+    }
+    ra.t = ta; ra.retries = rr->retries; ra.team = reinterpret_cast<int*>(mine(o_team));
+    HIPC(hipMemcpyAsync(rargs_dev, &ra, sizeof(ra), hipMemcpyHostToDevice, e->stream));
   } else {
     HIPC(hipMemcpyAsync(args_dev, &ta, sizeof(ta), hipMemcpyHostToDevice, e->stream));
   }
@@ -4642,6 +4675,8 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   if (ta.walk) HIPC(hipMemsetAsync(ta.walk, 0, (size_t)N * walk_cap * 2, e->stream));
   if (sm)
     hipLaunchKernelGGL(k_plan_team_smooth, dim3(W), dim3(kPlanFieldThreads), team_lds, e->stream, static_cast<const PlanTeamSmoothArgs*>(smargs_dev));
+  else if (rr)
+    hipLaunchKernelGGL(k_plan_team_rounds, dim3(W), dim3(kPlanFieldThreads), team_lds, e->stream, static_cast<const PlanTeamRoundsArgs*>(rargs_dev));
   else
     hipLaunchKernelGGL(k_plan_team, dim3(W), dim3(kPlanFieldThreads), team_lds, e->stream, static_cast<const PlanTeamArgs*>(args_dev));
   HIPC(hipGetLastError());
@@ -4661,6 +4696,16 @@ static int plan_team_run(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   HIPC(back(leave_out, h1 + n1 * K, n1 * K));
   HIPC(back(waypoints_out, h1 + 2 * n1 * K, n1 * K * P));
   if (sm && sm->keep_out) HIPC(hipMemcpyAsync(sm->keep_out, sa.keep, (size_t)N * sm->keep_cap * 4, hipMemcpyDeviceToHost, e->stream));
+  if (rr) {
+    const auto team_back = [&](void* dst, size_t off_ints, size_t n_ints) {
+      return hipMemcpyAsync(dst, ra.team + off_ints, n_ints * 4, hipMemcpyDeviceToHost, e->stream);
+    };
+    const size_t g1 = (size_t)n_teams;
+    HIPC(team_back(rr->order_out, 0, n1));
+    HIPC(team_back(rr->rounds_out, n1, g1));
+    HIPC(team_back(rr->parked_out, n1 + g1, g1));
+    HIPC(team_back(rr->parked_first_out, n1 + 2 * g1, g1));
+  }
   if (walk_out) HIPC(hipMemcpyAsync(walk_out, ta.walk, (size_t)N * walk_cap * 2, hipMemcpyDeviceToHost, e->stream));
   if (occ_time_out) HIPC(hipMemcpyAsync(occ_time_out, occ_dev, (size_t)S * (T + 1) * cells, hipMemcpyDeviceToHost, e->stream));
   if (fields_team_out) HIPC(hipMemcpyAsync(fields_team_out, ta.fields, (size_t)N * field_bytes, hipMemcpyDeviceToHost, e->stream));
@@ -4690,6 +4735,21 @@ int mobrob_ppo_plan_grid_team_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_s
   const PlanTeamSmooth sm{margin, max_leg, moves_out, keep_out, keep_cap};
   return plan_team_run(e, spec, walls, hzf, tm, team_size, reserve, start, goal, waypoints_out, n_waypoints_out, count_out, status_out, cost_out,
                        waits_out, leave_out, arrive_out, sweeps_out, walk_out, walk_cap, occ_time_out, fields_team_out, workgroups_out, &sm);
+}
+
+// ---- priority reordering rounds of a team plan (mobrob_ppo_plan_grid_team_rounds): the parked members first, on the device ------
+int mobrob_ppo_plan_grid_team_rounds(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls,
+                                     const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t reserve,
+                                     int32_t retries, const float* start, const float* goal, float* waypoints_out,
+                                     int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out, int32_t* cost_out,
+                                     int32_t* waits_out, int32_t* leave_out, int32_t* arrive_out, int32_t* sweeps_out, uint16_t* walk_out,
+                                     int32_t walk_cap, uint8_t* occ_time_out, int32_t* fields_team_out, int32_t* workgroups_out,
+                                     int32_t* team_order_out, int32_t* team_rounds_out, int32_t* team_parked_out,
+                                     int32_t* team_parked_first_out) {
+  const PlanTeamRounds rr{retries, team_order_out, team_rounds_out, team_parked_out, team_parked_first_out};
+  return plan_team_run(e, spec, walls, hzf, tm, team_size, reserve, start, goal, waypoints_out, n_waypoints_out, count_out, status_out, cost_out,
+                       waits_out, leave_out, arrive_out, sweeps_out, walk_out, walk_cap, occ_time_out, fields_team_out, workgroups_out, nullptr,
+                       &rr);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -929,6 +929,127 @@ __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team(const PlanTeamA
   }
 }
 
+// ---- priority reordering rounds of a team plan (mobrob_ppo_plan_grid_team_rounds; the rule: goal_rules.grid_plan_team_rounds) ---
+// k_plan_team with a loop of rounds around the member loop.  Round 0 plans in the identity order; after a round the members without
+// a walk (status 1 or 3) are "parked", and the next order is the parked members, then the others, each in this round's relative
+// order.  The rounds stop when nobody is parked, after `retries` reorderings, or when the next order was already planned.  The result
+// is the round with the fewest parked members, the earliest on a tie: if that is not the round planned last, the team is planned
+// once more in its order -- the plan is a function of the order alone, so this replay leaves the best round's bits in the outputs.
+// Position p of the order plans robot team * size + order[p] in slot p: plan_team_field and plan_team_walk take both.
+constexpr int kPlanRetriesMax = 8;
+
+struct PlanTeamRoundsArgs {
+  PlanTeamArgs t;   // k_plan_team's
+  int retries;      // R, 0 .. kPlanRetriesMax
+  int* team;        // out: order [n_teams][size] | rounds [n_teams] | parked [n_teams] | parked_first [n_teams]
+};
+
+// LDS bytes of k_plan_team_rounds: k_plan_team's, then 4 control words, the parked count of every round and the orders planned so
+// far (16 bytes a round)
+inline size_t plan_team_rounds_lds_bytes(int G, int T, int retries) {
+  return plan_team_lds_bytes(G, T) + 16 + (size_t)(retries + 1) * (sizeof(int) + kPlanTeamMax);
+}
+
+// The bookkeeping between two rounds, by one thread between two barriers.  ctl: [0] the row of `hist` to plan next (-1: the team
+// is done), [1] the rounds planned, [2] the best round, [3] 1 while the replay runs.  Not inlined (k_plan_team says why).
+__device__ __noinline__ void plan_team_round_next(const PlanTeamRoundsArgs* __restrict__ rp, int team, int* ctl) {
+  const int size = rp->t.size, R = rp->retries, N = rp->t.N, n_teams = rp->t.n_teams;
+  if (ctl[3]) { ctl[0] = -1; return; }   // that was the replay of the best round
+  int* parked = ctl + 4;
+  unsigned char* hist = reinterpret_cast<unsigned char*>(parked + R + 1);
+  const int k = ctl[1];
+  const unsigned char* ord = hist + k * kPlanTeamMax;
+  const int* status = rp->t.out + 2 * N + team * size;
+  unsigned is_parked = 0;   // bit m: member m has no walk
+  for (int m = 0; m < size; ++m)
+    if (status[m] == kPlanUnreachable || status[m] == kPlanUnconverged) is_parked |= 1u << m;
+  const int np = __popc(is_parked);
+  parked[k] = np;
+  ctl[1] = k + 1;
+  int best = ctl[2];
+  if (k == 0 || np < parked[best]) best = k;
+  ctl[2] = best;
+  bool stop = np == 0 || k == R;
+  if (!stop) {   // k < R: row k + 1 of hist exists
+    unsigned char* nxt = hist + (k + 1) * kPlanTeamMax;
+    int q = 0;
+    for (int p = 0; p < size; ++p)
+      if (is_parked & (1u << ord[p])) nxt[q++] = ord[p];
+    for (int p = 0; p < size; ++p)
+      if (!(is_parked & (1u << ord[p]))) nxt[q++] = ord[p];
+    for (int j = 0; j <= k && !stop; ++j) {   // planned before (also: the parked members are in front already)
+      bool same = true;
+      for (int p = 0; p < size; ++p) same = same && hist[j * kPlanTeamMax + p] == nxt[p];
+      stop = same;
+    }
+  }
+  if (!stop) { ctl[0] = k + 1; return; }
+  int* o = rp->team;
+  for (int p = 0; p < size; ++p) o[team * size + p] = hist[best * kPlanTeamMax + p];
+  o += n_teams * size;
+  o[team] = k + 1;
+  o[n_teams + team] = parked[best];
+  o[2 * n_teams + team] = parked[0];
+  if (best != k) { ctl[0] = best; ctl[3] = 1; } else { ctl[0] = -1; }
+}
+
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team_rounds(const PlanTeamRoundsArgs* __restrict__ rp) {
+  extern __shared__ __attribute__((aligned(16))) int plan_team_rounds_lds[];
+  const PlanTeamArgs* ap = &rp->t;
+  const int G = ap->g.G, T = ap->T, cells = G * G, tid = threadIdx.x, r = ap->reserve, size = ap->size, n_teams = ap->n_teams;
+  const int K = ap->K, P = ap->P, N = ap->N;
+  // LDS: k_plan_team's (d | e | moves | wcell | hand, 16 bytes) | ctl [4] | parked [R + 1] | hist [R + 1][16] (bytes)
+  int* hand = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(plan_team_rounds_lds + 2 * cells) + cells + kPlanTeamMax * (T + 1) * 2);
+  int* ctl = hand + 4;
+  const unsigned char* hist = reinterpret_cast<const unsigned char*>(ctl + 4 + rp->retries + 1);
+  int* tail = plan_team_wg(*ap) + (T + 1) * cells;
+  unsigned char* tres = reinterpret_cast<unsigned char*>(tail + cells + 4);
+  for (int team = blockIdx.x; team < n_teams; team += gridDim.x) {
+    if (tid == 0) {   // round 0: the identity order (the last team's readers of ctl and hist: behind the barrier that ended its rounds)
+      ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; ctl[3] = 0;
+      unsigned char* first = reinterpret_cast<unsigned char*>(ctl + 4 + rp->retries + 1);
+      for (int p = 0; p < kPlanTeamMax; ++p) first[p] = (unsigned char)p;
+    }
+    __syncthreads();
+    for (int pass = 0;; ++pass) {   // at most retries + 1 rounds and the replay
+      const unsigned char* ord = hist + ctl[0] * kPlanTeamMax;
+#pragma unroll 1
+      for (int c = tid; c < cells; c += kPlanFieldThreads) tres[c] = 0;   // per round (its last readers and writers: behind a barrier)
+      for (int m = 0; m < size; ++m) {
+        const int n = team * size + ord[m];
+        if (pass > 0) {   // plan_team_walk writes only the slots its walk touches: what the member's last walk left goes first
+          int* waits = ap->out + 6 * N + n * K;
+          float* wp = reinterpret_cast<float*>(ap->out + 6 * N + 2 * N * K) + n * K * P;
+#pragma unroll 1
+          for (int j = tid; j < K; j += kPlanFieldThreads) { waits[j] = 0; waits[N * K + j] = 0; }
+#pragma unroll 1
+          for (int j = tid; j < K * P; j += kPlanFieldThreads) wp[j] = 0.f;
+        }
+        const int sweeps = plan_team_field(ap, n, m, plan_team_rounds_lds);
+        // the field and the zeroes, written by every thread to global memory, to the one thread that walks: a fence, then the barrier
+        __threadfence_block();
+        __syncthreads();
+        if (tid == 0) plan_team_walk(ap, n, m, sweeps, plan_team_rounds_lds);
+        __threadfence_block();
+        __syncthreads();
+        const int ntail = hand[0];
+#pragma unroll 1
+        for (int i = tid; i < ntail; i += kPlanFieldThreads) {
+          const int cx = tail[i] & 127, cy = tail[i] >> 7;
+          for (int y = max(cy - r, 0); y <= min(cy + r, G - 1); ++y)
+            for (int x = max(cx - r, 0); x <= min(cx + r, G - 1); ++x) tres[y * G + x] = 1;
+        }
+        __threadfence_block();
+        __syncthreads();
+      }
+      if (tid == 0) plan_team_round_next(rp, team, ctl);   // thread 0 wrote the statuses it reads
+      __syncthreads();
+      if (ctl[0] < 0) break;
+    }
+    __syncthreads();   // every thread has read ctl[0] before the next team's thread 0 resets it
+  }
+}
+
 // ---- line-of-sight smoothing of a time plan (mobrob_ppo_plan_grid_time_smooth; the rule: goal_rules.grid_next_blocked /
 // grid_los_time / grid_smooth_time / grid_path_smooth_time) -------------------------------------------------------------------------
 // A straight leg is tested against EVERY layer it spans.  nb[t][c]: the first layer from t on in which cell c is not clear

@@ -858,6 +858,22 @@ class PPOEngine:
         return self._plan_team(spec, walls, hazards, teams, reserve, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy,
                                want_fields, want_walks, clearance)
 
+    def plan_grid_team_rounds(self, spec, walls=None, hazards=None, *, teams, reserve, retries, start, goal, step0=0, layer_steps, layers,
+                              max_waypoints=16, want_occupancy=False, want_fields=False, want_walks=False, clearance=True, smooth=False):
+        """plan_grid_team with up to `retries` (0 .. 8) reordering rounds inside the device call (mobrob_ppo_plan_grid_team_rounds:
+        k_plan_team_rounds; the rule: goal_rules.grid_plan_team_rounds, reproduced bit for bit): a team whose plan leaves members
+        parked (UNREACHABLE or UNCONVERGED) is planned again with those members first, and the result is the round with the fewest
+        parked members.  Returns plan_grid_team's dict of that round, indexed by robot, plus team_order int32 [n_teams][size] (the
+        result's order), team_rounds [n_teams] (rounds planned, >= 1), team_parked and team_parked_first [n_teams] (parked members
+        of the result and of round 0).  What rounds do not repair: goal_rules.grid_plan_team_rounds.  smooth=True is
+        refused by name: rounds of smoothed team plans are not built."""
+        from .envs import goal_rules as R
+        retries = R.plan_retries_check(retries)
+        if smooth:
+            raise ValueError("plan_team: retries with smooth=True is not supported (reordering rounds plan unsmoothed team plans only)")
+        return self._plan_team(spec, walls, hazards, teams, reserve, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy,
+                               want_fields, want_walks, clearance, retries=retries)
+
     def plan_smooth_team(self, spec, walls=None, hazards=None, *, teams, reserve, start, goal, step0=0, layer_steps, layers, max_waypoints=16,
                          margin=1, max_leg=8, want_occupancy=False, want_fields=False, want_walks=False, clearance=True):
         """plan_grid_team with line-of-sight smoothing (mobrob_ppo_plan_grid_team_smooth; the rule:
@@ -875,8 +891,9 @@ class PPOEngine:
                                want_fields, want_walks, clearance, smooth=(int(margin), cap))
 
     def _plan_team(self, spec, walls, hazards, teams, reserve, start, goal, step0, layer_steps, layers, max_waypoints, want_occupancy,
-                   want_fields, want_walks, clearance, smooth=None):
-        """plan_grid_team's call (smooth None) or plan_smooth_team's (smooth: (margin, max_leg)): the checks and the arrays of both"""
+                   want_fields, want_walks, clearance, smooth=None, retries=None):
+        """plan_grid_team's call (smooth and retries None), plan_smooth_team's (smooth: (margin, max_leg)) or plan_grid_team_rounds's
+        (retries: an int): the checks and the arrays of all three"""
         from ._lib import PlanSpec, PlanTime, WallsC
         from .envs import goal_rules as R
         if not isinstance(spec, R.GridSpec):
@@ -937,7 +954,15 @@ class PPOEngine:
                       cost.ctypes.data_as(i32), waits.ctypes.data_as(i32), leave.ctypes.data_as(i32), arrive.ctypes.data_as(i32))
             copies = (None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), None if fields is None else fields.ctypes.data_as(i32),
                       C.byref(wgs))
-            if smooth is None:
+            if retries is not None:
+                order = np.zeros((n // size, size), np.int32)
+                rounds, parked, parked_first = (np.zeros(n // size, np.int32) for _ in range(3))
+                check(self.lib.mobrob_ppo_plan_grid_team_rounds(*head, retries, *robots, sweeps.ctypes.data_as(i32), walk.ctypes.data_as(u16),
+                                                                walk_cap, *copies, order.ctypes.data_as(i32), rounds.ctypes.data_as(i32),
+                                                                parked.ctypes.data_as(i32), parked_first.ctypes.data_as(i32)))
+                if int(arrive.max()) + 1 <= walk_cap:
+                    break
+            elif smooth is None:
                 check(self.lib.mobrob_ppo_plan_grid_team(*head, *robots, sweeps.ctypes.data_as(i32), walk.ctypes.data_as(u16), walk_cap, *copies))
                 if int(arrive.max()) + 1 <= walk_cap:
                     break
@@ -957,6 +982,8 @@ class PPOEngine:
                "field_scene": np.zeros(n, np.int32) if scene is None else np.asarray(scene, np.int32).copy(), "sweeps": sweeps,
                "n_scenes": int(S), "workgroups": int(wgs.value)}
         walks = [[(int(x), int(y)) for x, y in cells[i, :int(arrive[i]) + 1]] for i in range(n)] if want_walks or (smooth is not None and clearance) else None
+        if retries is not None:
+            out.update(team_order=order, team_rounds=rounds, team_parked=parked, team_parked_first=parked_first)
         if smooth is not None:
             out["release"], out["moves"] = R.grid_release_smooth(leave, step0, layer_steps), moves
             out["keeps"] = [keep[i, :max(int(count[i]) - 1, 0)].tolist() for i in range(n)]

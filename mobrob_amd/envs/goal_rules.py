@@ -1329,7 +1329,8 @@ def grid_release_smooth(leave, step0, layer_steps):
 # ---- prioritised planning inside a team: a mate's planned walk is one more moving obstacle in the layers.  This
 # project's own rule, integers but for the occupancy's floats; the device (csrc/kernels_plan.h: k_plan_team) is held to it bit for
 # bit.  The member with team-local index m plans after the members 0 .. m - 1 on occ_t = base_t OR res_t, res the union of their
-# reservations; teams never see each other.  Prioritised planning is INCOMPLETE: a member never yields to a later one.
+# reservations; teams never see each other.  Prioritised planning is INCOMPLETE: inside one plan a member never yields to a later
+# one (grid_plan_team_rounds, further down, plans a team again with the members that stayed parked first).
 PLAN_RESERVE_MAX = 4
 PLAN_NO_PAIR = 2 ** 31 - 1        # the clearance of a team without a pair of mates (size 1)
 
@@ -1619,7 +1620,7 @@ def grid_team_clearance_legs(walks, keeps, size, layers):
 
 
 def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0, layer_steps=None, layers=None, want_fields=True,
-                   smooth=False, margin=1, max_leg=8):
+                   smooth=False, margin=1, max_leg=8, order=None):
     """The whole team plan of n robots by the rule: grid_plan_time's dict per robot -- there are no shared fields: field_of is the
     identity and fields is int32 [n][T + 1][G][G] (None without want_fields), each robot's own on ITS map -- with occupancy the
     BASE layers bool [S][T + 1][G][G], plus walks (per robot the cells of its walk; a robot without one: its start cell),
@@ -1636,7 +1637,10 @@ def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0
     speeds; team_crossings stays grid_team_clearance's count on the walks; a later member that has a walk keeps > reserve from an
     earlier parked mate's start cell.  NOT promised: more PLANNED robots than the unsmoothed plan (a long leg reserves all of itself
     for all of its span, hence the cap max_leg); fewer waypoints; anything about a later member's start cell that an earlier
-    member's leg covers -- that member comes back UNREACHABLE and is reported as such."""
+    member's leg covers -- that member comes back UNREACHABLE and is reported as such.
+    order: None (the identity) or int [n_teams][size], one permutation of 0 .. size - 1 per team (plan_team_order):
+    in team g, position p plans member order[g][p], on the base layers OR the reservations of the members at the positions
+    0 .. p - 1.  Every output stays indexed by robot; the plan is grid_plan_team's on the permuted inputs, un-permuted."""
     start, goal = np.asarray(start, np.float32), np.asarray(goal, np.float32)
     n, P = goal.shape
     if layer_steps is None or layers is None:
@@ -1666,9 +1670,10 @@ def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0
     fields = np.zeros((n, T + 1, G, G), np.int32) if want_fields else None
     wp, waits, leave = np.zeros((n, K, P), np.float32), np.zeros((n, K), np.int32), np.zeros((n, K), np.int32)
     count, status, cost, arrive, moves = (np.zeros(n, np.int32) for _ in range(5))
-    walks, keeps = [], []
-    for i in range(n):
-        if i % size == 0:
+    rows = np.arange(n) if order is None else (np.arange(n) // size * size + plan_team_order(order, n // size, size).ravel())
+    walks, keeps = [None] * n, [None] * n
+    for j, i in enumerate(rows):
+        if j % size == 0:
             res = np.zeros((T + 1, G, G), bool)
         layers_i = occ[sc[i]] | res
         field = grid_team_field(layers_i, int(gy[i]) * G + int(gx[i]))
@@ -1683,9 +1688,9 @@ def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0
         m = min(int(count[i]), K)
         wp[i, :m, :2] = w[:m]
         wp[i, :m, 2:] = goal[i, 2:]
-        walks.append(cells if cells else [(int(sx[i]), int(sy[i]))])
-        keeps.append(keep)
-        res |= grid_reserve_legs(walks[-1], keep, T, G, r) if smooth else grid_reserve(walks[-1], T, G, r)
+        walks[i] = cells if cells else [(int(sx[i]), int(sy[i]))]
+        keeps[i] = keep
+        res |= grid_reserve_legs(walks[i], keep, T, G, r) if smooth else grid_reserve(walks[i], T, G, r)
     first, number = grid_layer_frames(hazards, step0, layer_steps, T) if isinstance(hazards, MovingHazards) else (None, None)
     clear, cross = grid_team_clearance(walks, size, T)
     out = {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status, "cost": cost,
@@ -1697,6 +1702,100 @@ def grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, step0=0
     if smooth:
         out["moves"], out["keeps"] = moves, keeps
         out["team_clearance"] = grid_team_clearance_legs(walks, plan_team_keeps_with_walks(keeps, status), size, T)
+    return out
+
+
+# ---- priority reordering rounds: a team whose plan leaves members parked is planned again with those members first
+PLAN_RETRIES_MAX = 8
+TEAM_ROUND_KEYS = ("team_order", "team_rounds", "team_parked", "team_parked_first")
+
+
+def plan_team_order(order, n_teams, size):
+    """-> order as int64 [n_teams][size], or ValueError: every row a permutation of 0 .. size - 1"""
+    o = np.asarray(order)
+    if o.dtype == bool or not np.issubdtype(o.dtype, np.integer) or o.shape != (int(n_teams), int(size)):
+        raise ValueError(f"plan_team: order must be integers [n_teams = {int(n_teams)}][size = {int(size)}], got {o.dtype} {o.shape}")
+    bad = np.nonzero(np.any(np.sort(o, axis=1) != np.arange(int(size)), axis=1))[0]
+    if bad.size:
+        raise ValueError(f"plan_team: order of team {int(bad[0])} is not a permutation of 0 .. {int(size) - 1}: {o[bad[0]].tolist()}")
+    return o.astype(np.int64)
+
+
+def plan_retries_check(retries):
+    """-> retries as an int, or ValueError: an integer in 0 .. PLAN_RETRIES_MAX (a bool is refused)"""
+    if isinstance(retries, bool) or not isinstance(retries, (int, np.integer)) or not 0 <= int(retries) <= PLAN_RETRIES_MAX:
+        raise ValueError(f"plan_team: retries must be an integer in 0 .. {PLAN_RETRIES_MAX}, got {retries!r}")
+    return int(retries)
+
+
+def plan_team_parked(status):
+    """The members without a walk, bool like status: UNREACHABLE or UNCONVERGED (TRUNCATED has a walk)"""
+    status = np.asarray(status)
+    return (status == UNREACHABLE) | (status == UNCONVERGED)
+
+
+def plan_team_next_order(order, parked):
+    """The order of the next round, a list: the parked members in their relative order of this round, then the others in theirs.
+    order: this round's, [size]; parked: bool [size] indexed by MEMBER"""
+    order = [int(m) for m in order]
+    return [m for m in order if parked[m]] + [m for m in order if not parked[m]]
+
+
+def grid_plan_team_rounds(spec, walls, hazards, start, goal, K, teams, reserve, step0=0, layer_steps=None, layers=None, want_fields=True,
+                          smooth=False, margin=1, max_leg=8, retries=0):
+    """grid_plan_team with up to `retries` (0 .. PLAN_RETRIES_MAX) reordering rounds, every team on its own.  Round 0 plans in the
+    identity order.  After round k the team's parked members are those without a walk (plan_team_parked).  Nobody parked: stop.
+    Otherwise the next order is plan_team_next_order's -- the parked members first; stop without planning it if k == retries or
+    if that order was already planned for this team (which includes: the parked members are in front already).  The result is the
+    round with the fewest parked members, the earliest on a tie: the dict is grid_plan_team(order=that round's), bit for bit, plus
+    team_order int32 [n_teams][size] (the result's order), team_rounds int32 [n_teams] (rounds planned, >= 1), team_parked and
+    team_parked_first int32 [n_teams] (parked members of the result and of round 0).  retries = 0: grid_plan_team's plan.
+    What rounds do NOT repair: two mates whose start cells, or whose goal cells, are within `reserve` of each other fail in every
+    order (whoever plans second finds its start reserved, or its goal never free); an earlier member still does not know a later
+    member's start cell and may plan through it, which parks the later one; and the orders tried are one chain of at most
+    retries + 1, not all size! of them -- a team that some order would plan in full may still come back with members parked.
+    smooth=True with retries > 0 is refused (ValueError): rounds of smoothed team plans are not built."""
+    R_ = plan_retries_check(retries)
+    if smooth and R_ > 0:
+        raise ValueError("plan_team: retries > 0 with smooth=True is not supported (reordering rounds plan unsmoothed team plans only)")
+    kw = dict(step0=step0, layer_steps=layer_steps, layers=layers, want_fields=want_fields, smooth=smooth, margin=margin, max_leg=max_leg)
+    out = grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, **kw)
+    size = teams.size
+    g = len(out["status"]) // size
+    ident = list(range(size))
+    order = np.tile(np.arange(size, dtype=np.int32), (g, 1))                 # the result's
+    now = [ident] * g                                                        # the latest round's
+    tried = [[ident] for _ in range(g)]
+    parked = plan_team_parked(out["status"]).reshape(g, size)
+    best = parked.sum(axis=1).astype(np.int32)
+    first, rounds = best.copy(), np.ones(g, np.int32)
+    live = np.ones(g, bool)
+    for k in range(R_ + 1):
+        nxt = np.tile(np.arange(size), (g, 1))                               # a team that has stopped: any order, its rows are not used
+        for t in np.flatnonzero(live):
+            cand = plan_team_next_order(now[t], parked[t])
+            if not parked[t].any() or k == R_ or cand in tried[t]:
+                live[t] = False
+            else:
+                nxt[t], now[t] = cand, cand
+                tried[t].append(cand)
+        if not live.any():
+            break
+        new = grid_plan_team(spec, walls, hazards, start, goal, K, teams, reserve, order=nxt, **kw)
+        status = plan_team_parked(new["status"]).reshape(g, size)
+        for t in np.flatnonzero(live):
+            rounds[t] += 1
+            parked[t] = status[t]
+            if status[t].sum() < best[t]:
+                best[t], order[t] = status[t].sum(), nxt[t]
+                rows = slice(t * size, (t + 1) * size)
+                for key in ("waypoints", "n_waypoints", "count", "status", "cost", "waits", "leave", "arrive", "release", "fields"):
+                    if out[key] is not None:
+                        out[key][rows] = new[key][rows]
+                out["walks"][rows] = new["walks"][rows]
+                for key in ("team_clearance", "team_crossings"):
+                    out[key][t] = new[key][t]
+    out.update(team_order=order, team_rounds=rounds, team_parked=best, team_parked_first=first)
     return out
 
 

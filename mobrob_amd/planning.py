@@ -20,8 +20,10 @@ so mates are planned around each other (goal_rules.grid_plan_team; device: mobro
 actions is clear whatever the robot's speed along it, and the plan holds the robot at every anchor until the leg's first layer
 (goal_rules.grid_plan_time(smooth=True); device: mobrob_ppo_plan_grid_time_smooth).  With teams a kept leg is at
 most `max_leg` actions long and is reserved for the later members as a swept region, all of its cells in every layer of its span
-(goal_rules.grid_plan_team(smooth=True); device: mobrob_ppo_plan_grid_team_smooth).  Walls as solid bodies are not planned for
-(DESIGN 4.12)."""
+(goal_rules.grid_plan_team(smooth=True); device: mobrob_ppo_plan_grid_team_smooth).  Reordering rounds (`retries=R`, DESIGN
+4.12.6): a team whose plan leaves members parked is planned again, inside the same call, with those members first, and the plan
+with the fewest parked members is the result (goal_rules.grid_plan_team_rounds; device: mobrob_ppo_plan_grid_team_rounds).  Walls
+as solid bodies are not planned for."""
 from __future__ import annotations
 
 import numpy as np
@@ -48,13 +50,19 @@ class GridPlanner:
     teams: a goal_rules.Teams: every plan is a TEAM plan, a time plan (layer_steps required, also in a static scene) in which the
     members of a team plan in index order around the walks of the members before them; reserve: the cells (Chebyshev) a walk
     reserves around itself, 0 .. 4 (None: ceil(separation / h), ValueError above 4).  Prioritised planning is incomplete: a
-    member never yields to a later one, and a later member boxed in by reservations comes back UNREACHABLE.  With time_smooth a
+    later member boxed in by reservations comes back UNREACHABLE.  retries (0 .. 8; it belongs to teams, ValueError otherwise):
+    up to that many reordering rounds -- a team with parked members (UNREACHABLE or UNCONVERGED) is planned again with those
+    members first, and the round with the fewest parked members is the plan; 0 plans once, in index order.  Rounds repair a
+    member that an earlier one boxed in.  They do not repair two mates whose start cells, or whose goal cells, are within
+    `reserve` of each other (they fail in every order), an earlier member still does not know a later member's start cell, and
+    only a chain of at most retries + 1 orders is tried, not every order.  retries > 0 with time_smooth is refused.  With time_smooth a
     team plan is smoothed too (a team plan is a time plan: no MovingHazards needed): max_leg, the actions of a leg at most (8; None:
     no cap; it belongs to teams, ValueError otherwise) -- a leg reserves all of its cells in every layer of its span, so long legs
     shut later members out, and a member whose start cell an earlier member's leg covers comes back UNREACHABLE."""
 
     def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
-                 smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None, time_smooth=False, max_leg=_UNSET):
+                 smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None, time_smooth=False, max_leg=_UNSET,
+                 retries=0):
         from .envs.vec_env import DeviceGoalVecEnv
         if teams is not None and not isinstance(teams, rules.Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
@@ -62,6 +70,9 @@ class GridPlanner:
             raise ValueError("GridPlanner: reserve= belongs to teams=")
         if max_leg is not _UNSET and teams is None:
             raise ValueError("GridPlanner: max_leg= belongs to teams= with time_smooth (the cap on a smoothed team plan's legs)")
+        if teams is None and not (isinstance(retries, (int, np.integer)) and not isinstance(retries, bool) and retries == 0):
+            raise ValueError("GridPlanner: retries= belongs to teams= (reordering rounds of a team plan)")
+        self.retries = rules.plan_retries_check(retries)
         self.max_leg = 8 if max_leg is _UNSET else (None if max_leg is None else rules.plan_max_leg_check(max_leg))
         self.teams = teams
         self.timed = isinstance(hazards, rules.MovingHazards) or teams is not None
@@ -117,6 +128,8 @@ class GridPlanner:
     def _time_smooth_ok(self, time_smooth):
         """-> bool(time_smooth), or ValueError where it is asked for on a plan that is not a time plan (no moving hazards, no teams) or
         with teams of one: a team of one has no mate to plan around, so it stays refused as before (plan it without teams=)"""
+        if time_smooth and self.retries > 0:
+            raise ValueError("GridPlanner: retries > 0 with time_smooth=True is not supported (reordering rounds plan unsmoothed team plans only)")
         if time_smooth and (self.teams.size < 2 if self.teams is not None else not isinstance(self.hazards, rules.MovingHazards)):
             raise ValueError("GridPlanner: time_smooth=True needs hazards that are a MovingHazards and no teams, or teams of two or more (a team "
                              "of one has no mates: plan it without teams=; a static plan takes smooth=True)")
@@ -175,6 +188,13 @@ class GridPlanner:
             if smooth:
                 return rules.grid_plan_team(self.spec, self.walls, self.hazards, start, goal, K, self.teams, self.reserve, want_fields=want_fields,
                                             smooth=True, margin=self.los_margin, max_leg=self.max_leg, **kw)
+            if self.retries > 0 and self.device:
+                return self.engine.plan_grid_team_rounds(self.spec, self.walls, self.hazards, teams=self.teams, reserve=self.reserve,
+                                                         retries=self.retries, start=start, goal=goal, max_waypoints=K,
+                                                         want_occupancy=want_occupancy, want_fields=want_fields, **kw)
+            if self.retries > 0:
+                return rules.grid_plan_team_rounds(self.spec, self.walls, self.hazards, start, goal, K, self.teams, self.reserve,
+                                                   want_fields=want_fields, retries=self.retries, **kw)
             if self.device:
                 return self.engine.plan_grid_team(self.spec, self.walls, self.hazards, teams=self.teams, reserve=self.reserve, start=start,
                                                   goal=goal, max_waypoints=K, want_occupancy=want_occupancy, want_fields=want_fields, **kw)
@@ -208,7 +228,9 @@ class GridPlanner:
         speeds).  `smoothed` is then True, `moves` [n] the moves of each walk, leave[k] the action index of waypoint k's
         anchor, release a hold at EVERY anchor but the start (goal_rules.grid_release_smooth), waits all zero; `grow` uses the
         smoothed count.  A kept leg of two or more actions is clear in every layer it spans; the count may exceed the unsmoothed
-        plan's."""
+        plan's.  With the planner's retries > 0 a team plan is the best of its reordering rounds and the dict gains team_order
+        [n_teams][size] (the order that plan was made in), team_rounds (rounds planned), team_parked and team_parked_first
+        [n_teams] (members without a walk in that plan and in index order) (goal_rules.grid_plan_team_rounds)."""
         start, goal = self._check(start, goal)
         smooth = self.smooth if smooth is None else bool(smooth)
         time_smooth = self.time_smooth if time_smooth is None else self._time_smooth_ok(time_smooth)
@@ -236,6 +258,8 @@ class GridPlanner:
             res.update({k: out[k] for k in ("team_clearance", "team_crossings")})
             if "keeps" in out:
                 res["keeps"] = out["keeps"]
+            if self.retries > 0:
+                res.update({k: out[k] for k in rules.TEAM_ROUND_KEYS})
         res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
         res["smoothed"], res["moves"] = smooth, out.get("moves")
         if want_occupancy:

@@ -1,0 +1,137 @@
+"""GPU: priority reordering rounds on the device (mobrob_ppo_plan_grid_team_rounds: k_plan_occupancy_time, k_plan_team_rounds)
+against the NumPy rule (goal_rules.grid_plan_team_rounds), BIT FOR BIT: every key of a team plan -- base layers, every robot's int32
+time field, float32 waypoints compared as uint32, all K slots of waits, leave and release -- plus team_order, team_rounds,
+team_parked and team_parked_first, and the walks.  Nothing here has a tolerance."""
+import numpy as np
+import pytest
+
+from mobrob_amd.envs import goal_rules as R
+from mobrob_amd.envs.goal_rules import grid_plan_team_rounds
+from mobrob_amd.planning import GridPlanner
+from tests.plan_scenes import EXTENT, INFLATE
+from tests.plan_team_rounds_scenes import CORRIDOR_K, CORRIDOR_TABLE, CORRIDOR_TIME, ROUNDS_KEYS, corridor_case, hopeless_pair
+from tests.plan_team_scenes import TEAM_KEYS, circling32, same_team, sealed_case, teams
+from tests.util import _engine, _env
+
+pytestmark = pytest.mark.gpu
+KW = dict(pi=(64, 64), vf=(64, 64))
+WANT = dict(want_occupancy=True, want_fields=True, want_walks=True)
+
+
+@pytest.fixture(scope="module")
+def engine():
+    e, _ = _engine("point", KW)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def corridor_ref():
+    """the corridor by the rule, computed once: {(reserve, retries): dict}"""
+    spec, walls, start, goal = corridor_case()
+    return {(r, n): grid_plan_team_rounds(spec, walls, None, start, goal, CORRIDOR_K, teams(4), r, retries=n, **CORRIDOR_TIME)
+            for r in (0, 1) for n in (0, 1, 2, 3)}
+
+
+def both(engine, spec, walls, hz, start, goal, K, size, r, retries, step0, layer_steps, layers, ref=None):
+    if ref is None:
+        ref = grid_plan_team_rounds(spec, walls, hz, start, goal, K, teams(size), r, step0, layer_steps, layers, retries=retries)
+    dev = engine.plan_grid_team_rounds(spec, walls, hz, teams=teams(size), reserve=r, retries=retries, start=start, goal=goal, step0=step0,
+                                       layer_steps=layer_steps, layers=layers, max_waypoints=K, **WANT)
+    same_team(dev, ref, ROUNDS_KEYS)
+    assert dev["walks"] == ref["walks"]
+    assert not np.any(dev["status"] == R.UNCONVERGED) and np.all(dev["sweeps"] >= 1)
+    return dev, ref
+
+
+@pytest.mark.parametrize("retries", [0, 1, 2, 3])
+@pytest.mark.parametrize("r", [0, 1])
+def test_corridor(engine, corridor_ref, r, retries):
+    spec, walls, start, goal = corridor_case()
+    dev, _ = both(engine, spec, walls, None, start, goal, CORRIDOR_K, 4, r, retries, 0, CORRIDOR_TIME["layer_steps"], CORRIDOR_TIME["layers"],
+                  ref=corridor_ref[r, retries])
+    order = ((0, 1, 2, 3), (1, 2, 0, 3), (2, 1, 0, 3), (2, 1, 0, 3))[retries]
+    status, cost0, cost1 = CORRIDOR_TABLE[order]
+    assert dev["team_order"].tolist() == [list(order)] and dev["team_rounds"].tolist() == [min(retries, 2) + 1]
+    assert dev["status"].tolist() == status and dev["cost"].tolist() == (cost0, cost1)[r]
+    assert dev["team_parked"].tolist() == [max(2 - retries, 0)] and dev["team_parked_first"].tolist() == [2]
+    assert dev["team_clearance"][0] > r and dev["team_crossings"][0] == 0
+
+
+@pytest.mark.parametrize("size", [2, 4, 16])
+def test_g32_two_scenes_teams_among_circling_hazards(engine, size):
+    spec, walls, hz, start, goal = circling32()
+    dev, ref = both(engine, spec, walls, hz, start, goal, 4, size, 1, 3, 0, 10, 8)
+    assert np.all(dev["team_parked"] <= dev["team_parked_first"]) and dev["workgroups"] == 32 // size
+    print("size", size, "rounds", dev["team_rounds"].tolist(), "parked first", dev["team_parked_first"].tolist(), "parked", dev["team_parked"].tolist())
+
+
+def test_hopeless_pair_keeps_round_0(engine):
+    spec, start, goal = hopeless_pair()
+    dev, _ = both(engine, spec, None, None, start, goal, 8, 2, 1, 3, 0, 10, 48)
+    assert dev["team_rounds"].tolist() == [2] and dev["team_order"].tolist() == [[0, 1]] and dev["team_parked"].tolist() == [1]
+    assert dev["status"].tolist() == [R.PLANNED, R.UNREACHABLE]                # round 1 parked the other one: round 0 was planned again
+
+
+def test_sealed_member_already_first(engine):
+    spec, walls, start, goal = sealed_case()
+    dev, _ = both(engine, spec, walls, None, start, goal, 8, 2, 1, 3, 0, 10, 48)
+    assert dev["team_rounds"].tolist() == [1] and dev["team_parked"].tolist() == [1]
+
+
+def test_more_teams_than_workgroups(engine, corridor_ref, monkeypatch):
+    """16 copies of the corridor team and a cap on the scratch fields of 4 fields: 4 workgroups, each takes 4 teams one after the
+    other on the scratch, the stamps, the walk cells, the orders and the counts the team before left behind.  Teams do not see each
+    other, so the rule's plan of one team, 16 times, is what the device must give."""
+    spec, walls, start, goal = corridor_case(16)
+    T, G = CORRIDOR_TIME["layers"], spec.cells
+    monkeypatch.setenv("MOBROB_PLAN_TIME_MAX_BYTES", str(4 * (T + 1) * G * G * 4))
+    dev = engine.plan_grid_team_rounds(spec, walls, None, teams=teams(4), reserve=1, retries=3, start=start, goal=goal, max_waypoints=CORRIDOR_K,
+                                       **CORRIDOR_TIME, **WANT)
+    assert dev["workgroups"] == 4 < 16 == len(dev["team_rounds"])
+    one = corridor_ref[1, 3]
+    ref = {k: np.tile(one[k], (16,) + (1,) * (np.ndim(one[k]) - 1)) for k in ROUNDS_KEYS if k not in ("occupancy", "field_of")}
+    ref.update(occupancy=one["occupancy"], field_of=np.arange(64, dtype=np.int32))
+    same_team(dev, ref, ROUNDS_KEYS)
+    assert dev["walks"] == one["walks"] * 16
+
+
+@pytest.mark.parametrize("case", ["corridor", "circling"])
+def test_no_retries_is_plan_grid_team(engine, case):
+    if case == "corridor":
+        spec, walls, start, goal = corridor_case()
+        args, kw = (spec, walls, None), dict(teams=teams(4), reserve=1, start=start, goal=goal, max_waypoints=CORRIDOR_K, **CORRIDOR_TIME, **WANT)
+    else:
+        spec, walls, hz, start, goal = circling32()
+        args, kw = (spec, walls, hz), dict(teams=teams(4), reserve=1, start=start, goal=goal, max_waypoints=4, layer_steps=10, layers=8, **WANT)
+    plain = engine.plan_grid_team(*args, **kw)
+    dev = engine.plan_grid_team_rounds(*args, retries=0, **kw)
+    same_team(dev, plain, TEAM_KEYS)       # (not `sweeps`: the tail is relaxed in place, so the sweeps a field took depend on the waves' timing)
+    assert dev["walks"] == plain["walks"] and np.all(dev["team_rounds"] == 1)
+    assert np.array_equal(dev["team_order"], np.tile(np.arange(4, dtype=np.int32), (len(dev["team_rounds"]), 1)))
+    assert np.array_equal(dev["team_parked"], dev["team_parked_first"])
+    assert np.array_equal(dev["team_parked"], R.plan_team_parked(plain["status"]).reshape(-1, 4).sum(axis=1))
+
+
+def test_planner_on_the_device_against_the_host_planner(engine):
+    spec, walls, start, goal = corridor_case()
+    kw = dict(walls=walls, teams=teams(4), reserve=1, retries=2, cells=32, inflate=INFLATE, max_waypoints=CORRIDOR_K, extent=EXTENT, **CORRIDOR_TIME)
+    dev_planner, host_planner = GridPlanner(_env("point", 4), engine=engine, **kw), GridPlanner("point", **kw)
+    assert dev_planner.device and not host_planner.device
+    dev, host = dev_planner.plan(start, goal), host_planner.plan(start, goal)
+    same_team(dev, host, ("waypoints", "n_waypoints", "count", "status", "cost", "waits", "leave", "arrive", "release", "team_clearance",
+                          "team_crossings", "cost_distance") + R.TEAM_ROUND_KEYS)
+    assert dev["team_order"].tolist() == [[2, 1, 0, 3]] and dev["status"].tolist() == [0, 0, 0, 0]
+    assert np.array_equal(dev["schedule"].release, host["schedule"].release)
+
+
+def test_engine_refusals_are_named(engine):
+    spec, walls, start, goal = corridor_case()
+    kw = dict(teams=teams(4), reserve=1, start=start, goal=goal, max_waypoints=CORRIDOR_K, **CORRIDOR_TIME)
+    for bad in (-1, 9, True, 1.5):
+        with pytest.raises(ValueError, match="retries"):
+            engine.plan_grid_team_rounds(spec, walls, None, retries=bad, **kw)
+    with pytest.raises(ValueError, match="smooth"):
+        engine.plan_grid_team_rounds(spec, walls, None, retries=1, smooth=True, **kw)
+    with pytest.raises(ValueError, match="reserve"):
+        engine.plan_grid_team_rounds(spec, walls, None, retries=1, **dict(kw, reserve=5))
