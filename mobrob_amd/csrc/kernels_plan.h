@@ -1,4 +1,4 @@
-// Grid planner (mobrob_ppo_plan_grid): walls and hazards to waypoints, for all robots in one call.
+// Grid planner (mobrob_ppo_plan_grid and the six entry points built on it): walls and hazards to waypoints, for all robots in one call.
 //
 // The rule, stated once in array form in mobrob_amd/envs/goal_rules.py (GridSpec, grid_occupancy, grid_field, grid_path): a grid of
 // G x G cells (G = 32, 64, 128) over [-extent, extent]^2, x and y only.  The host hands down extent, h = 2 extent / G and inv_h =
@@ -11,22 +11,33 @@
 //                d[c] = min(d[nb] + w), d[goal] = 0, so the order of the relaxations does not show in it.
 //   path:        from the start's cell to a neighbour with d[nb] + w == d[c], the previous direction first, else the lowest of E, N,
 //                W, S, NE, NW, SW, SE; a cell's centre is a waypoint where the direction changes; the last waypoint is the goal.
-// Three kernels: k_plan_occupancy (a thread per scene and cell), k_plan_field (a workgroup per distinct (scene, goal cell), the
-// field in LDS, sweeps of in-place relaxations until a workgroup-wide "nothing changed", at most G * G of them), k_plan_path (a
-// thread per robot, at most G * G steps).  A loop that runs into its bound reports status 3; nothing here can spin.
-// Line-of-sight smoothing of the path (k_plan_dilate, k_plan_smooth, in k_plan_path's place on resident fields): further down.
+// A loop that runs into its bound reports status 3; nothing here can spin.
+//
+// Every rule is one device function, and every kernel calls it:
+//   plan_centre_blocked   the wall and hazard test of a cell centre          (k_plan_occupancy, k_plan_occupancy_time)
+//   plan_moves            the move mask over a "cell is free" predicate      (every field and every walk)
+//   plan_tail             the in-place relaxation to a tested fixed point    (k_plan_field, k_plan_field_time, plan_team_field)
+//   plan_jacobi           a cell of layer t from layer t + 1                 (k_plan_field_time, plan_team_field)
+//   plan_step             the descent step                                   (plan_walk_step: plan_path, plan_smooth; the team walks)
+//   plan_los              the supercover sight line over a "cell is hidden" predicate   (plan_smooth, plan_team_smooth_legs)
+//   plan_emit, plan_close, plan_give_up, plan_result   a robot's waypoints and outputs  (every walk and window body)
+//   plan_path<Time>, plan_smooth<Time>   the bodies of k_plan_path / k_plan_path_time and k_plan_smooth / k_plan_smooth_time
+//   plan_team_field<Reserved>   a member's field, over where "reserved" comes from      (k_plan_team, k_plan_team_rounds, k_plan_team_smooth)
+//   plan_team_member      field, walk and stamps of one member               (k_plan_team, k_plan_team_rounds)
 #pragma once
 #include "kernels_wall.h"
 
 namespace mobrob {
 
-constexpr int kPlanInf = 0x3FFFFFFF;   // "no path yet" inside k_plan_field (any sum of a path's costs stays far below it)
+constexpr int kPlanInf = 0x3FFFFFFF;   // "no path yet" inside a field kernel (any sum of a path's costs stays far below it)
+constexpr int kPlanWait = 4;           // cost of a wait in a time field: cheaper than a move
+constexpr short kPlanNeverBlocked = 32767;   // in a next-blocked table: "in no layer" (kPlanLayersMax is 256: a short holds every layer)
 constexpr int kPlanFieldThreads = 1024;
 // status of a robot's plan
 constexpr int kPlanned = 0, kPlanUnreachable = 1, kPlanTruncated = 2, kPlanUnconverged = 3;
 
 struct PlanGrid {
-  int G;                   // cells per side
+  int G;                   // cells per side, a power of two: cell c is (c & (G - 1), c >> log2 G)
   float extent, h, inv_h;  // the host's floats
   float inflate;
 };
@@ -38,27 +49,165 @@ __device__ __forceinline__ int plan_cell(const PlanGrid& g, float x) {
 __device__ __forceinline__ float plan_centre(const PlanGrid& g, int i) {
   return __fadd_rn(-g.extent, rounded(__fmul_rn(__fadd_rn((float)i, 0.5f), g.h)));
 }
-// move k of E, N, W, S, NE, NW, SW, SE
+// move k of E, N, W, S, NE, NW, SW, SE, and its cost
 __device__ __forceinline__ int plan_dx(int k) { return k == 0 || k == 4 || k == 7 ? 1 : (k == 1 || k == 3 ? 0 : -1); }
 __device__ __forceinline__ int plan_dy(int k) { return k == 1 || k == 4 || k == 5 ? 1 : (k == 0 || k == 2 ? 0 : -1); }
+__device__ __forceinline__ int plan_w(int k) { return k < 4 ? 5 : 7; }
+
+// "cell c is free" on a map that is nonzero where a cell is blocked: occupancy bytes, or a layer's map in LDS
+template <class Occ>
+__device__ __forceinline__ auto plan_unblocked(const Occ* occ) {
+  return [occ](int c) { return !occ[c]; };
+}
+template <class Occ>
+__device__ __forceinline__ auto plan_blocked(const Occ* occ) {
+  return [occ](int c) { return occ[c] != 0; };
+}
 
 // the moves a robot in the free cell (ix, iy) may make, bit k for move k: target in the grid and free, a diagonal only with both
 // orthogonal cells at the corner free
-template <class Occ>
-__device__ __forceinline__ unsigned plan_moves(const Occ* occ, int G, int ix, int iy) {
+template <class Free>
+__device__ __forceinline__ unsigned plan_moves(Free free, int G, int ix, int iy) {
+  const int c = iy * G + ix;
   unsigned free4 = 0;   // E, N, W, S
-  if (ix + 1 < G && !occ[iy * G + ix + 1]) free4 |= 1u;
-  if (iy + 1 < G && !occ[(iy + 1) * G + ix]) free4 |= 2u;
-  if (ix > 0 && !occ[iy * G + ix - 1]) free4 |= 4u;
-  if (iy > 0 && !occ[(iy - 1) * G + ix]) free4 |= 8u;
+  if (ix + 1 < G && free(c + 1)) free4 |= 1u;
+  if (iy + 1 < G && free(c + G)) free4 |= 2u;
+  if (ix > 0 && free(c - 1)) free4 |= 4u;
+  if (iy > 0 && free(c - G)) free4 |= 8u;
   unsigned m = free4;
-  if ((free4 & 3u) == 3u && !occ[(iy + 1) * G + ix + 1]) m |= 16u;     // NE: E and N free
-  if ((free4 & 6u) == 6u && !occ[(iy + 1) * G + ix - 1]) m |= 32u;     // NW: N and W
-  if ((free4 & 12u) == 12u && !occ[(iy - 1) * G + ix - 1]) m |= 64u;   // SW: W and S
-  if ((free4 & 9u) == 9u && !occ[(iy - 1) * G + ix + 1]) m |= 128u;    // SE: S and E
+  if ((free4 & 3u) == 3u && free(c + G + 1)) m |= 16u;     // NE: E and N free
+  if ((free4 & 6u) == 6u && free(c + G - 1)) m |= 32u;     // NW: N and W
+  if ((free4 & 12u) == 12u && free(c - G - 1)) m |= 64u;   // SW: W and S
+  if ((free4 & 9u) == 9u && free(c - G + 1)) m |= 128u;    // SE: S and E
   return m;
 }
 
+// The descent step of every walk, from the cell c whose value is dc into the layer dn (the same layer on a static field or a tail,
+// the next layer in time) over the moves m: to a neighbour with dn[nb] + w == dc, the previous direction first, else the lowest
+// index, else -- where `wait` allows it -- the wait (8); -1: none (dn is not a cost-to-go field of these moves).  A neighbour
+// qualifies with 0 <= v < kPlanInf: a team's scratch field holds kPlanInf in free cells without a path; on a field that holds only -1
+// or finite costs the upper test is vacuous.
+__device__ __forceinline__ int plan_step(unsigned m, int dc, const int* dn, int G, int c, int prev, bool wait) {
+  const auto fits = [dc](int v, int w) { return v >= 0 && v < kPlanInf && v + w == dc; };
+  int dir = -1;
+  for (int k = 7; k >= 0; --k)   // descending: the lowest qualifying index is kept
+    if ((m & (1u << k)) && fits(dn[c + plan_dy(k) * G + plan_dx(k)], plan_w(k))) dir = k;
+  if (prev >= 0 && (m & (1u << prev)) && fits(dn[c + plan_dy(prev) * G + plan_dx(prev)], plan_w(prev))) dir = prev;   // the previous direction first
+  if (dir < 0 && wait && fits(dn[c], kPlanWait)) dir = 8;   // the wait last
+  return dir;
+}
+
+// Action number t of the walk of goal_rules.grid_walk_time from the cell (ix, iy), on the layer maps occ [T + 1][G][G] and their time
+// field d: while t < T it descends from d_t to d_{t + 1} over layer t's map and may wait; from t = T on it is goal_rules.grid_walk on
+// the tail.  Without Time the map and the field are static ones: goal_rules.grid_walk, and neither T nor t is looked at.
+template <bool Time>
+__device__ __forceinline__ int plan_walk_step(const unsigned char* occ, const int* d, int G, int T, int t, int ix, int iy, int prev) {
+  const int cells = G * G, c = iy * G + ix;
+  size_t lo = 0, hi = 0;   // the layer the cell is in, the layer the step descends into
+  if constexpr (Time) { lo = (size_t)min(t, T) * cells; hi = (size_t)min(t + 1, T) * cells; }
+  return plan_step(plan_moves(plan_unblocked(occ + lo), G, ix, iy), d[lo + c], d + hi, G, c, prev, Time && t < T);
+}
+
+// The tail of a field, by a whole workgroup of kPlanFieldThreads threads, cell c on thread c % 1024: the moves of every cell of the
+// map `free` into `moves`, d = 0 on a free goal and kPlanInf elsewhere, then sweeps of relaxations until a workgroup-wide "nothing
+// changed" -> the sweeps run (the last one changed nothing), -1: the bound of G * G was hit.  The relaxations are IN PLACE: every
+// value ever stored in d is the cost of a real path to the goal and values only decrease, so a neighbour's value read while its owner
+// replaces it is an upper bound either way, and a sweep that changes nothing has found the fixed point.  A cell is read and written
+// as one aligned 32-bit LDS word.  Blocked cells have no moves and stay at kPlanInf.  Whatever `free` reads is in place before the
+// call; the last barrier here orders the final d before the caller's loads.
+template <class Free>
+__device__ __forceinline__ int plan_tail(int* d, unsigned char* moves, Free free, int goal, int G) {
+  const int cells = G * G, tid = threadIdx.x, gs = 31 - __clz(G), gm = G - 1;
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    const bool blocked = !free(c);
+    moves[c] = blocked ? 0 : (unsigned char)plan_moves(free, G, c & gm, c >> gs);
+    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
+  }
+  __syncthreads();
+  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
+    int changed = 0;
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      const unsigned m = moves[c];
+      if (m == 0 || c == goal) continue;
+      const int cur = d[c];
+      int best = cur;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (m & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + plan_w(k));
+      if (best < cur) { d[c] = best; changed = 1; }
+    }
+    __syncthreads();   // this sweep's stores before the next sweep's loads
+    if (!__syncthreads_or(changed)) return sweep;
+  }
+  return -1;
+}
+
+// One Jacobi step in time: the value of the free cell c in layer t from layer t + 1 (`nxt`) over the moves m of layer t's map and
+// the wait.  A pure function of the layer behind it, so there is no order to argue about.
+__device__ __forceinline__ int plan_jacobi(const int* nxt, unsigned m, int c, int G) {
+  int best = nxt[c] + kPlanWait;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (m & (1u << k)) best = min(best, nxt[c + plan_dy(k) * G + plan_dx(k)] + plan_w(k));
+  return min(best, kPlanInf);   // kPlanInf + a cost: still "none"
+}
+
+// goal_rules.grid_los over the predicate "cell c is hidden" (not clear): the supercover of the segment between the centres of (x, y)
+// and (x1, y1), both in the grid (every cell visited lies in their bounding box).  At most dx + dy <= 2 G - 2 steps; the loop is
+// bounded by 2 G on its own.
+template <class Hidden>
+__device__ __forceinline__ bool plan_los(Hidden hidden, int G, int x, int y, int x1, int y1) {
+  if (hidden(y * G + x)) return false;
+  const int dx = abs(x1 - x), dy = abs(y1 - y), sx = x1 > x ? 1 : -1, sy = y1 > y ? 1 : -1;
+  int ix = 0, iy = 0;
+  for (int it = 0; it < 2 * G && (ix < dx || iy < dy); ++it) {
+    const int t = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx;
+    if (t < 0) {
+      x += sx; ++ix;
+    } else if (t > 0) {
+      y += sy; ++iy;
+    } else {   // exactly through a cell corner: both cells that share it must be clear (plan_moves' no corner cutting)
+      if (hidden(y * G + x + sx) || hidden((y + sy) * G + x)) return false;
+      x += sx; y += sy; ++ix; ++iy;
+    }
+    if (hidden(y * G + x)) return false;
+  }
+  return ix == dx && iy == dy;
+}
+
+// A robot's waypoints [K][P] and outputs.  `writer`: this thread stores (a wave that plans one robot counts in every lane and stores
+// in lane 0).  The z of every waypoint is the goal's.
+__device__ __forceinline__ void plan_emit(float* wp, int count, int K, int P, const PlanGrid& g, int ix, int iy, const float* gl, bool writer) {
+  if (count < K && writer) {
+    wp[count * P] = plan_centre(g, ix);
+    wp[count * P + 1] = plan_centre(g, iy);
+    if (P == 3) wp[count * P + 2] = gl[2];
+  }
+}
+// the goal itself closes the path -> the status
+__device__ __forceinline__ int plan_close(float* wp, int& count, int K, int P, const float* gl, bool writer) {
+  if (count < K && writer)
+    for (int j = 0; j < P; ++j) wp[count * P + j] = gl[j];
+  ++count;
+  return count > K ? kPlanTruncated : kPlanned;
+}
+// nothing of a walk that was given up (status 3) is handed out
+__device__ __forceinline__ void plan_give_up(float* wp, int& count, int& cost, int K, int P) {
+  for (int j = 0; j < min(count, K) * P; ++j) wp[j] = 0.f;
+  count = 0;
+  cost = -1;
+}
+__device__ __forceinline__ void plan_result(int* nwp, int* full, int* stat, int* cst, int count, int K, int status, int cost) {
+  *nwp = min(count, K);
+  *full = count;
+  *stat = status;
+  *cst = cost;
+}
+
+// ---- the static plan (mobrob_ppo_plan_grid): k_plan_occupancy (a thread per scene and cell), k_plan_field (a workgroup per distinct
+// (scene, goal cell), the field in LDS), k_plan_path (a thread per robot, at most G * G steps) ---------------------------------------
 struct PlanOccArgs {
   PlanGrid g;
   const float* boxes;   // [S][Mw][4]
@@ -69,6 +218,19 @@ struct PlanOccArgs {
   int Mh;
   unsigned char* occ;   // [S][G][G] out: 1 blocked
 };
+
+// is the cell centre (px, py) blocked by one of the mw walls wl [mw][4] or the mh hazards hl [mh][3], both staged in LDS?
+__device__ __forceinline__ bool plan_centre_blocked(const PlanGrid& g, float px, float py, const float* wl, int mw, const float* hl, int mh) {
+  bool blocked = false;
+  for (int i = 0; i < mw; ++i)
+    if (wall_sdf(px, py, wl[4 * i], wl[4 * i + 1], wl[4 * i + 2], wl[4 * i + 3]) <= g.inflate) blocked = true;
+  for (int i = 0; i < mh; ++i) {
+    const float dx = __fsub_rn(px, hl[3 * i]), dy = __fsub_rn(py, hl[3 * i + 1]);
+    const float d = sqrtf(__fadd_rn(rounded(__fmul_rn(dx, dx)), rounded(__fmul_rn(dy, dy))));   // sqrtf: correctly rounded
+    if (d <= __fadd_rn(hl[3 * i + 2], g.inflate)) blocked = true;
+  }
+  return blocked;
+}
 
 // grid (cdiv(G * G, 256), S), 256 threads, LDS 4 Mw + 3 Mh floats: the scene's walls and hazards, staged once per workgroup (at
 // the caps of 1024 rows each that is 28 KB: a scene always fits)
@@ -83,16 +245,7 @@ __global__ __launch_bounds__(256) void k_plan_occupancy(PlanOccArgs a) {
   __syncthreads();
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= G * G) return;
-  const float px = plan_centre(a.g, c % G), py = plan_centre(a.g, c / G);
-  bool blocked = false;
-  for (int i = 0; i < mw; ++i)
-    if (wall_sdf(px, py, wl[4 * i], wl[4 * i + 1], wl[4 * i + 2], wl[4 * i + 3]) <= a.g.inflate) blocked = true;
-  for (int i = 0; i < mh; ++i) {
-    const float dx = __fsub_rn(px, hl[3 * i]), dy = __fsub_rn(py, hl[3 * i + 1]);
-    const float d = sqrtf(__fadd_rn(rounded(__fmul_rn(dx, dx)), rounded(__fmul_rn(dy, dy))));   // sqrtf: correctly rounded
-    if (d <= __fadd_rn(hl[3 * i + 2], a.g.inflate)) blocked = true;
-  }
-  a.occ[(size_t)s * G * G + c] = blocked ? 1 : 0;
+  a.occ[(size_t)s * G * G + c] = plan_centre_blocked(a.g, plan_centre(a.g, c % G), plan_centre(a.g, c / G), wl, mw, hl, mh) ? 1 : 0;
 }
 
 struct PlanFieldArgs {
@@ -107,39 +260,13 @@ struct PlanFieldArgs {
 // LDS bytes of k_plan_field: the field, then one byte of moves per cell
 inline size_t plan_field_lds_bytes(int G) { return (size_t)G * G * (sizeof(int) + 1); }
 
-// One workgroup per field, 1024 threads, cell c on thread c % 1024.  The relaxations are IN PLACE: every value ever stored in d is
-// the cost of a real path to the goal and values only decrease, so a neighbour's value read while its owner replaces it is an upper
-// bound either way, and a sweep that changes nothing has found the fixed point.  A cell is read and written as one aligned 32-bit
-// LDS word.  Blocked cells have no moves and stay at kPlanInf.
+// One workgroup per field, 1024 threads: plan_tail on the scene's map.
 __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_field(PlanFieldArgs a) {
   extern __shared__ __attribute__((aligned(16))) int plan_field_lds[];
   const int f = blockIdx.x, G = a.G, cells = G * G, tid = threadIdx.x;
   int* d = plan_field_lds;
   unsigned char* moves = reinterpret_cast<unsigned char*>(plan_field_lds + cells);
-  const unsigned char* occ = a.occ + (size_t)a.field_scene[f] * cells;
-  const int goal = a.field_goal[f];
-  for (int c = tid; c < cells; c += kPlanFieldThreads) {
-    const bool blocked = occ[c] != 0;
-    moves[c] = blocked ? 0 : (unsigned char)plan_moves(occ, G, c % G, c / G);
-    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
-  }
-  __syncthreads();
-  int sweeps = -1;
-  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
-    int changed = 0;
-    for (int c = tid; c < cells; c += kPlanFieldThreads) {
-      const unsigned m = moves[c];
-      if (m == 0 || c == goal) continue;
-      const int cur = d[c];
-      int best = cur;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (m & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
-      if (best < cur) { d[c] = best; changed = 1; }
-    }
-    __syncthreads();   // this sweep's stores before the next sweep's loads
-    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
-  }
+  const int sweeps = plan_tail(d, moves, plan_unblocked(a.occ + (size_t)a.field_scene[f] * cells), a.field_goal[f], G);
   int* out = a.field + (size_t)f * cells;
   for (int c = tid; c < cells; c += kPlanFieldThreads) out[c] = d[c] >= kPlanInf ? -1 : d[c];
   if (tid == 0) a.sweeps[f] = sweeps;
@@ -161,90 +288,72 @@ struct PlanPathArgs {
   int* status;                // [N] out
   int* cost;                  // [N] out: d[start cell], -1 unreachable
 };
+// the time and the smoothing kernels take k_plan_path's arguments as their member p
+__device__ __forceinline__ const PlanPathArgs& plan_path_args(const PlanPathArgs& a) { return a; }
+template <class Args>
+__device__ __forceinline__ const PlanPathArgs& plan_path_args(const Args& s) { return s.p; }
 
-// one thread per robot: the walk of goal_rules.grid_path on its field in global memory
-__global__ __launch_bounds__(256) void k_plan_path(PlanPathArgs a) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= a.N) return;
+// Robot n's walk, by one thread: goal_rules.grid_path on a static field, or with Time goal_rules.grid_walk_time with grid_path_time's
+// waypoints on a time field (Args: PlanPathArgs, PlanPathTimeArgs).  A centre is a waypoint where the direction changes or a wait
+// ended; with Time the waits at a waypoint's anchor and the actions before the move that leaves it are recorded.  At most T + G * G
+// actions (T = 0 without Time): status 3 beyond.  A blocked start or goal cell has d < 0 in its field.
+template <bool Time, class Args>
+__device__ __forceinline__ void plan_path(const Args& s, int n) {
+  const PlanPathArgs& a = plan_path_args(s);
+  const int T = [&s] { if constexpr (Time) return s.T; else return 0; }();
   const int G = a.g.G, cells = G * G, P = a.P, K = a.K;
   const int f = a.field_of[n];
-  const unsigned char* occ = a.occ + (size_t)a.field_scene[f] * cells;
-  const int* d = a.field + (size_t)f * cells;
-  const float* s = a.start + (size_t)n * P;
+  const unsigned char* occ = a.occ + (size_t)a.field_scene[f] * (T + 1) * cells;
+  const int* d = a.field + (size_t)f * (T + 1) * cells;
+  const float* st = a.start + (size_t)n * P;
   const float* gl = a.goal + (size_t)n * P;
   float* wp = a.wp + (size_t)n * K * P;
-  int ix = plan_cell(a.g, s[0]), iy = plan_cell(a.g, s[1]);
+  int ix = plan_cell(a.g, st[0]), iy = plan_cell(a.g, st[1]);
   const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
-  int count = 0, status = kPlanned, cost = -1;
+  int count = 0, status = kPlanned, cost = -1, acts = 0;
   if (a.sweeps[f] < 0) {
     status = kPlanUnconverged;
-  } else if (occ[iy * G + ix] || occ[gy * G + gx] || d[iy * G + ix] < 0) {
+  } else if (d[iy * G + ix] < 0) {
     status = kPlanUnreachable;
   } else {
     cost = d[iy * G + ix];
-    int prev = -1, steps = 0;
+    int prev = -1, waited = 0;
     while (ix != gx || iy != gy) {
-      if (++steps > cells) { status = kPlanUnconverged; break; }
-      const unsigned m = plan_moves(occ, G, ix, iy);
-      const int dc = d[iy * G + ix];
-      int dir = -1;
-      for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
-        if (!(m & (1u << k))) continue;
-        const int dn = d[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
-        if (dn >= 0 && dn + (k < 4 ? 5 : 7) == dc) dir = k;
-      }
-      if (prev >= 0 && (m & (1u << prev))) {   // the previous direction first
-        const int dn = d[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
-        if (dn >= 0 && dn + (prev < 4 ? 5 : 7) == dc) dir = prev;
-      }
-      if (dir < 0) { status = kPlanUnconverged; break; }   // not a cost-to-go field: cannot happen after a converged k_plan_field
-      if (prev >= 0 && dir != prev) {
-        if (count < K) {
-          wp[count * P] = plan_centre(a.g, ix);
-          wp[count * P + 1] = plan_centre(a.g, iy);
-          if (P == 3) wp[count * P + 2] = gl[2];
-        }
+      if (acts >= T + cells) { status = kPlanUnconverged; break; }
+      const int dir = plan_walk_step<Time>(occ, d, G, T, acts, ix, iy, prev);
+      if (dir < 0) { status = kPlanUnconverged; break; }   // not a field of these maps: cannot happen after a converged field kernel
+      ++acts;
+      if (dir == 8) { ++waited; continue; }
+      const bool turned = prev >= 0 && (dir != prev || waited > 0);
+      if (turned) {
+        plan_emit(wp, count, K, P, a.g, ix, iy, gl, true);
         ++count;
       }
+      if constexpr (Time)
+        if ((prev < 0 || turned) && count < K) {   // this move leaves the anchor of waypoint `count`
+          s.waits[(size_t)n * K + count] = waited;
+          s.leave[(size_t)n * K + count] = acts - 1;
+        }
       ix += plan_dx(dir); iy += plan_dy(dir);
       prev = dir;
+      waited = 0;
     }
-    if (status == kPlanned) {
-      if (count < K)
-        for (int j = 0; j < P; ++j) wp[count * P + j] = gl[j];
-      ++count;
-      if (count > K) status = kPlanTruncated;
-    }
+    if (status == kPlanned) status = plan_close(wp, count, K, P, gl, true);
   }
-  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
-    for (int j = 0; j < min(count, K) * P; ++j) wp[j] = 0.f;
-    count = 0;
-    cost = -1;
+  if (status == kPlanUnconverged) {
+    plan_give_up(wp, count, cost, K, P);
+    if constexpr (Time)
+      for (int j = 0; j < K; ++j) { s.waits[(size_t)n * K + j] = 0; s.leave[(size_t)n * K + j] = 0; }
+    acts = 0;
   }
-  a.nwp[n] = min(count, K);
-  a.count[n] = count;
-  a.status[n] = status;
-  a.cost[n] = cost;
+  plan_result(a.nwp + n, a.count + n, a.status + n, a.cost + n, count, K, status, cost);
+  if constexpr (Time) s.arrive[n] = acts;
 }
 
-// the move the walk of goal_rules.grid_walk makes from the free cell (ix, iy) of the field d: to a neighbour with d[nb] + w == d[c],
-// the previous direction first, else the lowest index; -1: none (d is not the cost-to-go of occ).  k_plan_path's own step, line for
-// line; that kernel keeps its copy in place because calling this from it reordered instructions of its compiled loop, and existing
-// kernels stay as they are.
-__device__ __forceinline__ int plan_walk_dir(const unsigned char* occ, const int* d, int G, int ix, int iy, int prev) {
-  const unsigned m = plan_moves(occ, G, ix, iy);
-  const int dc = d[iy * G + ix];
-  int dir = -1;
-  for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
-    if (!(m & (1u << k))) continue;
-    const int dn = d[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
-    if (dn >= 0 && dn + (k < 4 ? 5 : 7) == dc) dir = k;
-  }
-  if (prev >= 0 && (m & (1u << prev))) {   // the previous direction first
-    const int dn = d[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
-    if (dn >= 0 && dn + (prev < 4 ? 5 : 7) == dc) dir = prev;
-  }
-  return dir;
+// one thread per robot, 256 to a workgroup
+__global__ __launch_bounds__(256) void k_plan_path(PlanPathArgs a) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n < a.N) plan_path<false>(a, n);
 }
 
 // ---- line-of-sight smoothing (mobrob_ppo_plan_smooth; the rule: goal_rules.grid_los / grid_smooth / grid_path_smooth) ----------
@@ -268,26 +377,10 @@ __global__ __launch_bounds__(256) void k_plan_dilate(PlanDilateArgs a) {
   a.dil[(size_t)blockIdx.y * G * G + c] = any ? 1 : 0;
 }
 
-// goal_rules.grid_los on the map blk of cells that are not clear: the supercover of the segment between the centres of (x, y) and
-// (x1, y1), both in the grid (every cell visited lies in their bounding box).  At most dx + dy <= 2 G - 2 steps; the loop is
-// bounded by 2 G on its own.
-__device__ __forceinline__ bool plan_los(const unsigned char* blk, int G, int x, int y, int x1, int y1) {
-  if (blk[y * G + x]) return false;
-  const int dx = abs(x1 - x), dy = abs(y1 - y), sx = x1 > x ? 1 : -1, sy = y1 > y ? 1 : -1;
-  int ix = 0, iy = 0;
-  for (int it = 0; it < 2 * G && (ix < dx || iy < dy); ++it) {
-    const int t = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx;
-    if (t < 0) {
-      x += sx; ++ix;
-    } else if (t > 0) {
-      y += sy; ++iy;
-    } else {   // exactly through a cell corner: both cells that share it must be clear (plan_moves' no corner cutting)
-      if (blk[y * G + x + sx] || blk[(y + sy) * G + x]) return false;
-      x += sx; y += sy; ++ix; ++iy;
-    }
-    if (blk[y * G + x]) return false;
-  }
-  return ix == dx && iy == dy;
+// goal_rules.grid_los_time on the layer nbl = nb[lo] of a next-blocked table (k_plan_next_blocked) with the threshold hi: a cell is
+// hidden where it is not clear in some layer lo .. hi
+__device__ __forceinline__ bool plan_los_time(const short* nbl, int hi, int G, int x, int y, int x1, int y1) {
+  return plan_los([nbl, hi](int c) { return nbl[c] <= hi; }, G, x, y, x1, y1);
 }
 
 constexpr int kPlanRing = 128;   // cells of the walk kept per wave: the window of 64 candidates and the cell before it fit twice
@@ -298,54 +391,61 @@ struct PlanSmoothArgs {
   int* moves;                 // [N] out: moves of the walk, 0 where none was made
 };
 
-// One wave per robot (grid N, 64 threads: the workgroup IS the wave, so nothing here waits for another wave and the trip counts of
-// different robots never meet).  The walk is k_plan_path's (plan_walk_dir), wave-uniform -- the robot is blockIdx.x, so its state
-// lives in scalar registers -- and lane 0 stores its cells, packed iy * 128 + ix, in a ring of kPlanRing entries in LDS (256 B).  With
-// the anchor c_i and the first untested index `base` (= i + 2: the adjacent cell is never tested), lane l tests
-// plan_los(c_i, c_{base + l}); the first lane that fails, z = ctz(ballot), is the rule's "first cell that is not visible": the cell
-// before it is emitted and becomes the anchor, base = base + z + 2.  No failure: base += 64, same anchor.  The walk runs ahead of
-// base by at most 64 cells; the ring holds indices base - 1 .. base + 63 at any time.  Bounds: the walk G * G moves (k_plan_path's),
-// the window loop G * G rounds (base grows by at least 1 a round and ends beyond L <= G * G), plan_los 2 G steps: status 3.
-__global__ __launch_bounds__(64) void k_plan_smooth(PlanSmoothArgs s) {
-  __shared__ unsigned short ring[kPlanRing];
+// Robot blockIdx.x's smoothed plan, by one wave (grid N, 64 threads: the workgroup IS the wave, so nothing here waits for another wave
+// and the trip counts of different robots never meet).  Args: PlanSmoothArgs, or with Time PlanSmoothTimeArgs.  The walk is
+// plan_path's (plan_walk_step), wave-uniform -- the robot is blockIdx.x, so its state lives in scalar registers -- and lane 0 stores
+// its cells, packed iy * 128 + ix, in `ring`, kPlanRing entries in LDS (256 B).  The ring is indexed by ACTION: c[a] is the cell after
+// a actions, a wait repeats its cell, so `walked` counts actions + 1.  With the anchor c[i] and the first untested index `base` (= i +
+// 2: the adjacent cell is never tested), lane l tests the leg c[i] .. c[base + l]: plan_los on blk, or with Time plan_los_time on
+// nb[min(i, T)] with the threshold min(base + l, T), every layer the leg spans.  The first lane that fails, z = ctz(ballot), is the
+// rule's first hidden index: c[base + z - 1] is emitted and becomes the anchor, base = base + z + 1.  No failure: base += 64, same
+// anchor.  The walk runs ahead of base by at most 64 cells; the ring holds indices base - 1 .. base + 63 at any time.  Lane 0's
+// stores to the ring and the other lanes' loads from it are ordered by wave-level fences: one wave, so no barrier.  Bounds: the walk
+// T + G * G actions (plan_path's; T = 0 without Time), the window loop as many rounds (base grows by at least 1 a round and ends beyond
+// A <= T + G * G), plan_los 2 G steps: status 3, outputs zeroed.
+template <bool Time, class Args>
+__device__ __forceinline__ void plan_smooth(const Args& s, unsigned short* ring) {
   const PlanPathArgs& a = s.p;
+  const int T = [&s] { if constexpr (Time) return s.T; else return 0; }();
   const int n = blockIdx.x, lane = threadIdx.x;
   const int G = a.g.G, cells = G * G, P = a.P, K = a.K;
   const int f = a.field_of[n];
-  const size_t scene_off = (size_t)a.field_scene[f] * cells;
+  const size_t scene_off = (size_t)a.field_scene[f] * (T + 1) * cells;
   const unsigned char* occ = a.occ + scene_off;
-  const unsigned char* blk = s.blk + scene_off;
-  const int* d = a.field + (size_t)f * cells;
+  const int* d = a.field + (size_t)f * (T + 1) * cells;
   const float* st = a.start + (size_t)n * P;
   const float* gl = a.goal + (size_t)n * P;
   float* wp = a.wp + (size_t)n * K * P;
   int wx = plan_cell(a.g, st[0]), wy = plan_cell(a.g, st[1]);   // the walker
   const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
-  int count = 0, status = kPlanned, cost = -1, walked = 1;     // walked: cells c_0 .. c_{walked - 1} are known
+  int count = 0, status = kPlanned, cost = -1, walked = 1, moves = 0;   // walked: cells c[0 .. walked - 1] are known
   if (a.sweeps[f] < 0) {
     status = kPlanUnconverged;
-  } else if (occ[wy * G + wx] || occ[gy * G + gx] || d[wy * G + wx] < 0) {
+  } else if (d[wy * G + wx] < 0) {
     status = kPlanUnreachable;
   } else {
     cost = d[wy * G + wx];
-    int ax = wx, ay = wy, base = 2, prev = -1;
+    int ax = wx, ay = wy, ai = 0, base = 2, prev = -1;   // the anchor's cell and action index
     bool done = wx == gx && wy == gy;
     if (lane == 0) ring[0] = (unsigned short)(wy * 128 + wx);
     for (int round = 0;; ++round) {
-      if (round > cells) { status = kPlanUnconverged; break; }
+      if (round > T + cells) { status = kPlanUnconverged; break; }
       while (!done && walked <= base + 63) {   // the walk, up to the end of the window
-        if (walked > cells) { status = kPlanUnconverged; break; }
-        const int dir = plan_walk_dir(occ, d, G, wx, wy, prev);
+        if (walked > T + cells) { status = kPlanUnconverged; break; }
+        const int dir = plan_walk_step<Time>(occ, d, G, T, walked - 1, wx, wy, prev);
         if (dir < 0) { status = kPlanUnconverged; break; }
-        wx += plan_dx(dir); wy += plan_dy(dir);
-        prev = dir;
+        if (dir != 8) {
+          wx += plan_dx(dir); wy += plan_dy(dir);
+          prev = dir;
+          ++moves;
+        }
         if (lane == 0) ring[walked & (kPlanRing - 1)] = (unsigned short)(wy * 128 + wx);
         ++walked;
         done = wx == gx && wy == gy;
       }
       if (status != kPlanned) break;
-      if (done && base >= walked) break;   // no candidate left: L = walked - 1
-      // lane 0's stores to the ring before every lane's loads from it: one wave, so a wave-level fence and no barrier
+      if (done && base >= walked) break;   // no candidate left: A = walked - 1
+      // lane 0's stores to the ring before every lane's loads from it
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -353,44 +453,45 @@ __global__ __launch_bounds__(64) void k_plan_smooth(PlanSmoothArgs s) {
       bool hidden = false;
       if (idx < walked) {
         const int c = ring[idx & (kPlanRing - 1)];
-        hidden = !plan_los(blk, G, ax, ay, c & 127, c >> 7);
+        if constexpr (Time) {
+          hidden = !plan_los_time(s.nb + scene_off + (size_t)min(ai, T) * cells, min(idx, T), G, ax, ay, c & 127, c >> 7);
+        } else {
+          hidden = !plan_los(plan_blocked(s.blk + scene_off), G, ax, ay, c & 127, c >> 7);
+        }
       }
       const unsigned long long fails = __ballot(hidden);
       if (fails == 0) { base += 64; continue; }
-      const int j = base + __builtin_ctzll(fails) - 1;   // the last visible cell: emitted, the next anchor
+      const int j = base + __builtin_ctzll(fails) - 1;   // the last visible index: emitted, the next anchor
       const int c = __builtin_amdgcn_readfirstlane((int)ring[j & (kPlanRing - 1)]);
-      ax = c & 127; ay = c >> 7;
-      if (count < K && lane == 0) {
-        wp[count * P] = plan_centre(a.g, ax);
-        wp[count * P + 1] = plan_centre(a.g, ay);
-        if (P == 3) wp[count * P + 2] = gl[2];
-      }
+      ax = c & 127; ay = c >> 7; ai = j;
+      plan_emit(wp, count, K, P, a.g, ax, ay, gl, lane == 0);
       ++count;
+      if constexpr (Time)
+        if (count < K && lane == 0) s.leave[(size_t)n * K + count] = j;   // the anchor of the waypoint that follows
       base = j + 2;
       // the loads above before the walk's next stores to the ring
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
-    if (status == kPlanned) {
-      if (count < K && lane == 0)
-        for (int q = 0; q < P; ++q) wp[count * P + q] = gl[q];
-      ++count;
-      if (count > K) status = kPlanTruncated;
-    }
+    if (status == kPlanned) status = plan_close(wp, count, K, P, gl, lane == 0);
   }
   if (lane != 0) return;
-  int moves = walked - 1;
-  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
-    for (int q = 0; q < min(count, K) * P; ++q) wp[q] = 0.f;
-    count = 0;
-    cost = -1;
+  int acts = walked - 1;
+  if (status == kPlanUnconverged) {
+    plan_give_up(wp, count, cost, K, P);
+    if constexpr (Time)
+      for (int q = 0; q < K; ++q) s.leave[(size_t)n * K + q] = 0;
+    acts = 0;
     moves = 0;
   }
-  a.nwp[n] = min(count, K);
-  a.count[n] = count;
-  a.status[n] = status;
-  a.cost[n] = cost;
+  plan_result(a.nwp + n, a.count + n, a.status + n, a.cost + n, count, K, status, cost);
+  if constexpr (Time) s.arrive[n] = acts;
   s.moves[n] = moves;
+}
+
+__global__ __launch_bounds__(64) void k_plan_smooth(PlanSmoothArgs s) {
+  __shared__ unsigned short ring[kPlanRing];
+  plan_smooth<false>(s, ring);
 }
 
 // ---- planning over time (mobrob_ppo_plan_grid_time; the rule: goal_rules.grid_layer_frames / grid_occupancy_time / grid_time_field /
@@ -399,7 +500,6 @@ __global__ __launch_bounds__(64) void k_plan_smooth(PlanSmoothArgs s) {
 // blocks, the tail layer T what any frame from then on blocks.  A layer's frames are a cyclically contiguous run, `number` frames
 // from `first` (computed on the host).  The time field d[T + 1][G][G]: d_T is k_plan_field's fixed point on the tail's map; d_t
 // for t < T is one Jacobi step from d_{t+1} over the moves of layer t's map and the wait (kPlanWait).
-constexpr int kPlanWait = 4;      // a wait: cheaper than a move
 constexpr int kPlanLayersMax = 256;
 
 struct PlanOccTimeArgs {
@@ -416,7 +516,7 @@ struct PlanOccTimeArgs {
 };
 
 // grid (G * G / 256, T + 1, S), 256 threads (G * G is a multiple of 256), LDS 4 Mw + 3 Mh floats: the scene's walls staged once,
-// then every frame of the layer's set in turn, behind barriers.  The tests are k_plan_occupancy's own.
+// then every frame of the layer's set in turn, behind barriers; the walls are tested with the first frame.
 __global__ __launch_bounds__(256) void k_plan_occupancy_time(PlanOccTimeArgs a) {
   extern __shared__ __attribute__((aligned(16))) float plan_scene_time_lds[];
   const int s = blockIdx.z, t = blockIdx.y, G = a.g.G;
@@ -435,14 +535,7 @@ __global__ __launch_bounds__(256) void k_plan_occupancy_time(PlanOccTimeArgs a) 
     const float* rows = a.hz + ((size_t)s * a.F + fr) * a.Mh * 3;
     for (int i = threadIdx.x; i < 3 * mh; i += 256) hl[i] = rows[i];
     __syncthreads();
-    if (j == 0)
-      for (int i = 0; i < mw; ++i)
-        if (wall_sdf(px, py, wl[4 * i], wl[4 * i + 1], wl[4 * i + 2], wl[4 * i + 3]) <= a.g.inflate) blocked = true;
-    for (int i = 0; i < mh; ++i) {
-      const float dx = __fsub_rn(px, hl[3 * i]), dy = __fsub_rn(py, hl[3 * i + 1]);
-      const float d = sqrtf(__fadd_rn(rounded(__fmul_rn(dx, dx)), rounded(__fmul_rn(dy, dy))));   // sqrtf: correctly rounded
-      if (d <= __fadd_rn(hl[3 * i + 2], a.g.inflate)) blocked = true;
-    }
+    if (plan_centre_blocked(a.g, px, py, wl, j == 0 ? mw : 0, hl, mh)) blocked = true;
   }
   a.occ[((size_t)s * (a.T + 1) + t) * G * G + c] = blocked ? 1 : 0;
 }
@@ -459,63 +552,27 @@ struct PlanFieldTimeArgs {
 // LDS bytes of k_plan_field_time: two layers of the field, then one byte of moves per cell (144 KB at 128 cells)
 inline size_t plan_field_time_lds_bytes(int G) { return (size_t)G * G * (2 * sizeof(int) + 1); }
 
-// One workgroup per field, 1024 threads.  The tail is k_plan_field's in-place relaxation on the tail's map, to a tested fixed
-// point.  Then T backward layers between two LDS layers, ping-pong: layer t is written from layer t + 1 alone, a pure function of
-// it, so there is no order to argue about; the one barrier per layer puts a layer's stores before the next layer's loads, and the
-// buffer a layer overwrites was last read before that barrier.  A layer's moves come from its own map in global memory, each cell
-// once.
+// One workgroup per field, 1024 threads.  The tail is plan_tail on the tail's map.  Then T backward layers between two LDS layers,
+// ping-pong: layer t is written from layer t + 1 alone (plan_jacobi); the one barrier per layer puts a layer's stores before the
+// next layer's loads, and the buffer a layer overwrites was last read before that barrier.  A layer's moves come from its own map in
+// global memory, each cell once.
 __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_field_time(PlanFieldTimeArgs a) {
   extern __shared__ __attribute__((aligned(16))) int plan_field_time_lds[];
-  const int f = blockIdx.x, G = a.G, T = a.T, cells = G * G, tid = threadIdx.x;
-  int* d = plan_field_time_lds;
-  int* e = plan_field_time_lds + cells;
+  const int f = blockIdx.x, G = a.G, T = a.T, cells = G * G, tid = threadIdx.x, gs = 31 - __clz(G), gm = G - 1;
+  int* nxt = plan_field_time_lds;           // layer t + 1
+  int* cur = plan_field_time_lds + cells;   // layer t
   unsigned char* moves = reinterpret_cast<unsigned char*>(plan_field_time_lds + 2 * cells);
   const unsigned char* occ_scene = a.occ + (size_t)a.field_scene[f] * (T + 1) * cells;
-  const unsigned char* occ = occ_scene + (size_t)T * cells;
   const int goal = a.field_goal[f];
-  for (int c = tid; c < cells; c += kPlanFieldThreads) {
-    const bool blocked = occ[c] != 0;
-    moves[c] = blocked ? 0 : (unsigned char)plan_moves(occ, G, c % G, c / G);
-    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
-  }
-  __syncthreads();
-  int sweeps = -1;
-  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
-    int changed = 0;
-    for (int c = tid; c < cells; c += kPlanFieldThreads) {
-      const unsigned m = moves[c];
-      if (m == 0 || c == goal) continue;
-      const int cur = d[c];
-      int best = cur;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (m & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
-      if (best < cur) { d[c] = best; changed = 1; }
-    }
-    __syncthreads();   // this sweep's stores before the next sweep's loads
-    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
-  }
+  const int sweeps = plan_tail(nxt, moves, plan_unblocked(occ_scene + (size_t)T * cells), goal, G);
   int* out = a.field + (size_t)f * (T + 1) * cells;
-  for (int c = tid; c < cells; c += kPlanFieldThreads) out[(size_t)T * cells + c] = d[c] >= kPlanInf ? -1 : d[c];
+  for (int c = tid; c < cells; c += kPlanFieldThreads) out[(size_t)T * cells + c] = nxt[c] >= kPlanInf ? -1 : nxt[c];
   if (tid == 0) a.sweeps[f] = sweeps;
-  int* nxt = d;   // layer t + 1
-  int* cur = e;   // layer t
   for (int t = T - 1; t >= 0; --t) {
     const unsigned char* occ_t = occ_scene + (size_t)t * cells;
     for (int c = tid; c < cells; c += kPlanFieldThreads) {
       int best = kPlanInf;
-      if (!occ_t[c]) {
-        if (c == goal) {
-          best = 0;
-        } else {
-          const unsigned m = plan_moves(occ_t, G, c % G, c / G);
-          best = nxt[c] + kPlanWait;
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            if (m & (1u << k)) best = min(best, nxt[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
-          best = min(best, kPlanInf);   // kPlanInf + a cost: still "none"
-        }
-      }
+      if (!occ_t[c]) best = c == goal ? 0 : plan_jacobi(nxt, plan_moves(plan_unblocked(occ_t), G, c & gm, c >> gs), c, G);
       cur[c] = best;
       out[(size_t)t * cells + c] = best >= kPlanInf ? -1 : best;
     }
@@ -532,97 +589,10 @@ struct PlanPathTimeArgs {
   int* arrive;      // [N] out: actions of the whole walk
 };
 
-// One thread per robot, 64 to a workgroup: the walk of goal_rules.grid_walk_time with grid_path_time's waypoints.  While t < T an
-// action is the previous move, else the lowest move, else the wait, that descends from d_t to d_{t+1} over layer t's map; from
-// t = T on it is plan_walk_dir on the tail.  At most T + G * G actions: status 3 beyond, as k_plan_path.
+// one thread per robot, 64 to a workgroup
 __global__ __launch_bounds__(64) void k_plan_path_time(PlanPathTimeArgs s) {
-  const PlanPathArgs& a = s.p;
   const int n = blockIdx.x * 64 + threadIdx.x;
-  if (n >= a.N) return;
-  const int G = a.g.G, cells = G * G, P = a.P, K = a.K, T = s.T;
-  const int f = a.field_of[n];
-  const unsigned char* occ = a.occ + (size_t)a.field_scene[f] * (T + 1) * cells;
-  const int* d = a.field + (size_t)f * (T + 1) * cells;
-  const float* st = a.start + (size_t)n * P;
-  const float* gl = a.goal + (size_t)n * P;
-  float* wp = a.wp + (size_t)n * K * P;
-  int* waits = s.waits + (size_t)n * K;
-  int* leave = s.leave + (size_t)n * K;
-  int ix = plan_cell(a.g, st[0]), iy = plan_cell(a.g, st[1]);
-  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
-  int count = 0, status = kPlanned, cost = -1, acts = 0;
-  if (a.sweeps[f] < 0) {
-    status = kPlanUnconverged;
-  } else if (d[iy * G + ix] < 0) {
-    status = kPlanUnreachable;
-  } else {
-    cost = d[iy * G + ix];
-    int prev = -1, waited = 0, t = 0;
-    while (ix != gx || iy != gy) {
-      if (acts >= T + cells) { status = kPlanUnconverged; break; }
-      int dir;
-      if (t < T) {
-        const unsigned char* occ_t = occ + (size_t)t * cells;
-        const int* dn = d + (size_t)(t + 1) * cells;
-        const unsigned m = plan_moves(occ_t, G, ix, iy);
-        const int dc = d[(size_t)t * cells + iy * G + ix];
-        dir = -1;
-        for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
-          if (!(m & (1u << k))) continue;
-          const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
-          if (v >= 0 && v + (k < 4 ? 5 : 7) == dc) dir = k;
-        }
-        if (prev >= 0 && (m & (1u << prev))) {   // the previous move first
-          const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
-          if (v >= 0 && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
-        }
-        if (dir < 0) {   // the wait last
-          const int v = dn[iy * G + ix];
-          if (v >= 0 && v + kPlanWait == dc) dir = 8;
-        }
-        ++t;
-      } else {
-        dir = plan_walk_dir(occ + (size_t)T * cells, d + (size_t)T * cells, G, ix, iy, prev);
-      }
-      if (dir < 0) { status = kPlanUnconverged; break; }   // not a time field of these layers: cannot happen after k_plan_field_time
-      ++acts;
-      if (dir == 8) { ++waited; continue; }
-      const bool turned = prev >= 0 && (dir != prev || waited > 0);
-      if (turned) {
-        if (count < K) {
-          wp[count * P] = plan_centre(a.g, ix);
-          wp[count * P + 1] = plan_centre(a.g, iy);
-          if (P == 3) wp[count * P + 2] = gl[2];
-        }
-        ++count;
-      }
-      if ((prev < 0 || turned) && count < K) {   // this move leaves the anchor of waypoint `count`
-        waits[count] = waited;
-        leave[count] = acts - 1;
-      }
-      ix += plan_dx(dir); iy += plan_dy(dir);
-      prev = dir;
-      waited = 0;
-    }
-    if (status == kPlanned) {
-      if (count < K)
-        for (int j = 0; j < P; ++j) wp[count * P + j] = gl[j];
-      ++count;
-      if (count > K) status = kPlanTruncated;
-    }
-  }
-  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
-    for (int j = 0; j < min(count, K) * P; ++j) wp[j] = 0.f;
-    for (int j = 0; j < K; ++j) { waits[j] = 0; leave[j] = 0; }
-    count = 0;
-    cost = -1;
-    acts = 0;
-  }
-  a.nwp[n] = min(count, K);
-  a.count[n] = count;
-  a.status[n] = status;
-  a.cost[n] = cost;
-  s.arrive[n] = acts;
+  if (n < s.p.N) plan_path<true>(s, n);
 }
 
 // ---- prioritised planning inside a team (mobrob_ppo_plan_grid_team; the rule: goal_rules.grid_reserve / grid_team_field /
@@ -659,115 +629,121 @@ inline size_t plan_team_lds_bytes(int G, int T) {
   return (size_t)G * G * (2 * sizeof(int) + 1) + (size_t)kPlanTeamMax * (T + 1) * sizeof(unsigned short) + 16;
 }
 
-// plan_moves on a field of k_plan_team's scratch: a cell is blocked where d < 0
-__device__ __forceinline__ unsigned plan_moves_field(const int* d, int G, int ix, int iy) {
-  unsigned free4 = 0;   // E, N, W, S
-  if (ix + 1 < G && d[iy * G + ix + 1] >= 0) free4 |= 1u;
-  if (iy + 1 < G && d[(iy + 1) * G + ix] >= 0) free4 |= 2u;
-  if (ix > 0 && d[iy * G + ix - 1] >= 0) free4 |= 4u;
-  if (iy > 0 && d[(iy - 1) * G + ix] >= 0) free4 |= 8u;
-  unsigned m = free4;
-  if ((free4 & 3u) == 3u && d[(iy + 1) * G + ix + 1] >= 0) m |= 16u;     // NE: E and N free
-  if ((free4 & 6u) == 6u && d[(iy + 1) * G + ix - 1] >= 0) m |= 32u;     // NW: N and W
-  if ((free4 & 12u) == 12u && d[(iy - 1) * G + ix - 1] >= 0) m |= 64u;   // SW: W and S
-  if ((free4 & 9u) == 9u && d[(iy - 1) * G + ix + 1] >= 0) m |= 128u;    // SE: S and E
-  return m;
+// the per-workgroup block of PlanTeamArgs::wg, and where a workgroup of k_plan_team keeps what one phase hands to the next
+__device__ __forceinline__ int* plan_team_wg(const PlanTeamArgs& a) { return a.wg + blockIdx.x * (int)plan_team_wg_ints(a.g.G, a.T); }
+struct PlanTeamHand {
+  unsigned short* wcell;   // LDS [kPlanTeamMax][T + 1]: the members' c[0 .. T], behind d, e and the byte map
+  int* hand;               // LDS, behind wcell (32 (T + 1) bytes on: a word boundary): [0] the number of tail cells
+  int* tail;               // scratch: the tail cells of the member that walked last
+  unsigned char* tres;     // scratch: the stamped tail reservations
+};
+__device__ __forceinline__ PlanTeamHand plan_team_hand(const PlanTeamArgs& a, int* lds) {
+  const int cells = a.g.G * a.g.G, T = a.T;
+  PlanTeamHand h;
+  h.wcell = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(lds + 2 * cells) + cells);
+  h.hand = reinterpret_cast<int*>(h.wcell + kPlanTeamMax * (T + 1));
+  h.tail = plan_team_wg(a) + (T + 1) * cells;
+  h.tres = reinterpret_cast<unsigned char*>(h.tail + cells + 4);
+  return h;
 }
 
-// the per-workgroup block of PlanTeamArgs::wg
-__device__ __forceinline__ int* plan_team_wg(const PlanTeamArgs& a) { return a.wg + blockIdx.x * (int)plan_team_wg_ints(a.g.G, a.T); }
+// Where "reserved" comes from in the field of k_plan_team's member m: in layer t < T, within r of the c[t] or c[t + 1] of a member 0 ..
+// m - 1 (LDS); in the tail, the stamped bytes.  No next-blocked table.
+struct PlanReservedNear {
+  using Args = PlanTeamArgs;
+  static constexpr bool kNextBlocked = false;
+  int* field;
+  const unsigned short* wcell;
+  const unsigned char* tres;
+  int m, T, r, gs, gm;
+  __device__ __forceinline__ PlanReservedNear(const Args& a, int m_, int* lds)
+      : field(plan_team_wg(a)), m(m_), T(a.T), r(a.reserve), gs(31 - __clz(a.g.G)), gm(a.g.G - 1) {
+    const PlanTeamHand h = plan_team_hand(a, lds);
+    wcell = h.wcell;
+    tres = h.tres;
+  }
+  __device__ __forceinline__ static const PlanTeamArgs& team(const Args& a) { return a; }
+  // is cell c blocked in the tail's map, in layer t's: `base` (the base layer blocks it) OR reserved
+  __device__ __forceinline__ bool tail(int c, bool base) const { return base | (tres[c] != 0); }
+  __device__ __forceinline__ bool layer(int t, int c, bool base) const {
+    const int cx = c & gm, cy = c >> gs;
+    bool near = base;
+    for (int j = 0; j < m && !near; ++j) {
+      const int w0 = wcell[j * (T + 1) + t], w1 = wcell[j * (T + 1) + t + 1];
+      near = (abs(cx - (w0 & 127)) <= r && abs(cy - (w0 >> 7)) <= r) || (abs(cx - (w1 & 127)) <= r && abs(cy - (w1 >> 7)) <= r);
+    }
+    return near;
+  }
+};
 
-// One member's field, by the whole workgroup -> the sweeps of the tail's relaxation (-1: bound hit).  A function of its own, not
-// inlined, and so is plan_team_walk: the wave-uniform values of a phase then live in scalar registers only while the phase runs
-// (inlined, the three phases' loop-invariant values overflowed the scalar file).  Both read the arguments from memory.
-__device__ __noinline__ int plan_team_field(const PlanTeamArgs* __restrict__ ap, int n, int m, int* lds) {
-  const PlanTeamArgs& a = *ap;
-  const int G = a.g.G, T = a.T, r = a.reserve, cells = G * G, tid = threadIdx.x;
-  const int gs = 31 - __clz(G), gm = G - 1;   // G is a power of two: cell c is (c & gm, c >> gs)
-  struct { int* lds; } f{lds};
+// is a cell within `margin` (0 or 1) of (x, y) that lies in the grid blocked?  (goal_rules.los_blocked, a cell at a time.)  Nine loads
+// without a branch: the neighbours are clamped into the grid, where a clamped one repeats a cell of the neighbourhood; at margin 0
+// all nine are the cell itself.
+template <class Occ>
+__device__ __forceinline__ bool plan_near_blocked(const Occ* occ, int G, int x, int y, int margin) {
+  const int x0 = max(x - margin, 0), x1 = min(x + margin, G - 1), r0 = max(y - margin, 0) * G, r1 = y * G, r2 = min(y + margin, G - 1) * G;
+  return (occ[r0 + x0] | occ[r0 + x] | occ[r0 + x1] | occ[r1 + x0] | occ[r1 + x] | occ[r1 + x1] | occ[r2 + x0] | occ[r2 + x] | occ[r2 + x1]) != 0;
+}
+
+// One member's field, by the whole workgroup -> the sweeps of the tail's relaxation (-1: bound hit): the tail's map (base OR reserved)
+// into e and plan_tail on it; then T Jacobi layers as k_plan_field_time's, each on a layer map (base OR reserved) built in LDS in
+// `moves`, with the goal terminal only while it stays free.  Every layer goes to the workgroup's scratch field (-1 blocked, kPlanInf
+// free without a path: the walking thread reads occupancy and cost from one array) and, where asked for, to `fields` as the rule
+// states it.  With Reserved::kNextBlocked the same pass over the layers, tail first, writes the member's next-blocked table nb
+// (k_plan_next_blocked's meaning) from the layer's blocked bytes in LDS: the byte itself at margin 0, the OR over the 3 x 3
+// neighbours at margin 1; nb[t + 1][c] is read back by the thread that wrote it.
+// A function of its own, not inlined, and so are the walks: the wave-uniform values of a phase then live in scalar registers only
+// while the phase runs (inlined, the phases' loop-invariant values overflowed the scalar file).  For the same reason the cell loops
+// are not unrolled, and every phase reads the arguments from memory.
+template <class Reserved>
+__device__ __noinline__ int plan_team_field(const typename Reserved::Args* __restrict__ ap, int n, int m, int* lds) {
+  const PlanTeamArgs& a = Reserved::team(*ap);
+  const Reserved rsv(*ap, m, lds);
+  const int G = a.g.G, T = a.T, cells = G * G, tid = threadIdx.x;
+  const int gs = 31 - __clz(G), gm = G - 1;
   const int scene = a.has_scene ? reinterpret_cast<const int*>(a.in + 2 * a.N * a.P)[n] : 0;
   const float* gl = a.in + (a.N + n) * a.P;
   const int goal = plan_cell(a.g, gl[1]) * G + plan_cell(a.g, gl[0]);
-  int* d = f.lds;
-  int* e = f.lds + cells;
-  unsigned char* moves = reinterpret_cast<unsigned char*>(f.lds + 2 * cells);
-  const unsigned short* wcell = reinterpret_cast<const unsigned short*>(moves + cells);
+  int* d = lds;
+  int* e = lds + cells;
+  unsigned char* moves = reinterpret_cast<unsigned char*>(lds + 2 * cells);
   const unsigned char* occ_scene = a.occ + (size_t)scene * (T + 1) * cells;
-  int* field = plan_team_wg(a);   // (the host's checks: every offset but the base layers' fits an int)
-  const unsigned char* tres = reinterpret_cast<const unsigned char*>(field + (T + 1) * cells + cells + 4);
+  int* field = rsv.field;   // (the host's checks: every offset but the base layers' fits an int)
   int* out = a.fields ? a.fields + n * (T + 1) * cells : nullptr;
-  // the tail: its map into e (a thread reads the stamps of its own cells' bytes only after the fence and barrier that follow
-  // the stamping), the moves, the in-place relaxation
+  // the tail: its map into e (a thread reads the reservations of its own cells only after the fence and barrier that follow their
+  // writing), then the moves and the in-place relaxation
   const unsigned char* occ_T = occ_scene + (size_t)T * cells;
 #pragma unroll 1
-  for (int c = tid; c < cells; c += kPlanFieldThreads) e[c] = (occ_T[c] | tres[c]) ? 1 : 0;
+  for (int c = tid; c < cells; c += kPlanFieldThreads) e[c] = rsv.tail(c, occ_T[c] != 0) ? 1 : 0;
   __syncthreads();
   bool terminal = e[goal] == 0;
-#pragma unroll 1
-  for (int c = tid; c < cells; c += kPlanFieldThreads) {
-    const bool blocked = e[c] != 0;
-    moves[c] = blocked ? 0 : (unsigned char)plan_moves(e, G, c & gm, c >> gs);
-    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
-  }
-  __syncthreads();
-  int sweeps = -1;
-  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
-    int changed = 0;
-#pragma unroll 1
-    for (int c = tid; c < cells; c += kPlanFieldThreads) {
-      const unsigned mv = moves[c];
-      if (mv == 0 || c == goal) continue;
-      const int cur = d[c];
-      int best = cur;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (mv & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
-      if (best < cur) { d[c] = best; changed = 1; }
-    }
-    __syncthreads();   // this sweep's stores before the next sweep's loads
-    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
-  }
+  const int sweeps = plan_tail(d, moves, plan_unblocked(e), goal, G);
 #pragma unroll 1
   for (int c = tid; c < cells; c += kPlanFieldThreads) {
     field[T * cells + c] = e[c] ? -1 : d[c];
     if (out) out[T * cells + c] = d[c] >= kPlanInf ? -1 : d[c];
+    if constexpr (Reserved::kNextBlocked)
+      rsv.nb[T * cells + c] = plan_near_blocked(e, G, c & gm, c >> gs, rsv.margin) ? (short)T : kPlanNeverBlocked;
   }
   int* nxt = d;   // layer t + 1
   int* cur = e;   // layer t
   for (int t = T - 1; t >= 0; --t) {
     const unsigned char* occ_t = occ_scene + (size_t)t * cells;
-    // layer t's map into `moves` (the tail's moves are done with): the base layer, or within r of an earlier member's c[t], c[t + 1]
+    // layer t's map into `moves` (the tail's moves are done with)
 #pragma unroll 1
-    for (int c = tid; c < cells; c += kPlanFieldThreads) {
-      bool blocked = occ_t[c] != 0;
-      const int cx = c & gm, cy = c >> gs;
-      for (int j = 0; j < m && !blocked; ++j) {
-        const int w0 = wcell[j * (T + 1) + t], w1 = wcell[j * (T + 1) + t + 1];
-        blocked = (abs(cx - (w0 & 127)) <= r && abs(cy - (w0 >> 7)) <= r) || (abs(cx - (w1 & 127)) <= r && abs(cy - (w1 >> 7)) <= r);
-      }
-      moves[c] = blocked ? 1 : 0;
-    }
+    for (int c = tid; c < cells; c += kPlanFieldThreads) moves[c] = rsv.layer(t, c, occ_t[c] != 0) ? 1 : 0;
     __syncthreads();   // the map before its readers; also e's last readers (the tail's write-out) before the first layer's stores
     terminal = terminal && moves[goal] == 0;
 #pragma unroll 1
     for (int c = tid; c < cells; c += kPlanFieldThreads) {
-      int best = kPlanInf;
       const bool blocked = moves[c] != 0;
-      if (!blocked) {
-        if (c == goal && terminal) {
-          best = 0;
-        } else {
-          const unsigned mv = plan_moves(moves, G, c & gm, c >> gs);
-          best = nxt[c] + kPlanWait;
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            if (mv & (1u << k)) best = min(best, nxt[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
-          best = min(best, kPlanInf);   // kPlanInf + a cost: still "none"
-        }
-      }
+      int best = kPlanInf;
+      if (!blocked) best = (c == goal && terminal) ? 0 : plan_jacobi(nxt, plan_moves(plan_unblocked(moves), G, c & gm, c >> gs), c, G);
       cur[c] = best;
       field[t * cells + c] = blocked ? -1 : best;
       if (out) out[t * cells + c] = best >= kPlanInf ? -1 : best;
+      if constexpr (Reserved::kNextBlocked)
+        rsv.nb[t * cells + c] = plan_near_blocked(moves, G, c & gm, c >> gs, rsv.margin) ? (short)t : rsv.nb[(t + 1) * cells + c];
     }
     __syncthreads();
     int* const swap = nxt; nxt = cur; cur = swap;
@@ -775,157 +751,128 @@ __device__ __noinline__ int plan_team_field(const PlanTeamArgs* __restrict__ ap,
   return sweeps;
 }
 
-// The walk of one member, by one thread: k_plan_path_time's loop on this workgroup's scratch field, ending where d_t[c] == 0.  It leaves
-// the member's outputs, c[0 .. T] in `mine` (LDS), the tail cells in `tail` and their number in hand[0].  A function of its own, not
-// inlined: its wave-uniform state would otherwise share the scalar registers with the loop-invariant values of the field loops.
+// action number `acts` of a member's walk from (ix, iy) on its scratch field [T + 1][G][G], whose value at the cell in layer min(acts,
+// T) is dc: plan_walk_step with the field itself as the map (a cell is blocked where d < 0)
+__device__ __forceinline__ int plan_team_step(const int* field, int G, int T, int acts, int dc, int ix, int iy, int prev) {
+  const int cells = G * G, t = min(acts, T);
+  const int* dt = field + t * cells;
+  return plan_step(plan_moves([dt](int c) { return dt[c] >= 0; }, G, ix, iy), dc, field + min(t + 1, T) * cells, G, iy * G + ix, prev, t < T);
+}
+
+// The walk of one member, by one thread: plan_path<true>'s loop on this workgroup's scratch field, ending where d_t[c] == 0.  It leaves
+// the member's outputs, c[0 .. T] in its row of wcell (LDS), the tail cells in `tail` and their number in hand[0].
 __device__ __noinline__ void plan_team_walk(const PlanTeamArgs* __restrict__ ap, int n, int m, int sweeps, int* lds) {
   const PlanTeamArgs& a = *ap;
   const int G = a.g.G, T = a.T, cells = G * G, P = a.P, K = a.K;
+  const PlanTeamHand h = plan_team_hand(a, lds);
   const int* field = plan_team_wg(a);
-  int* tail = plan_team_wg(a) + (T + 1) * cells;
-  unsigned short* mine = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(lds + 2 * cells) + cells) + m * (T + 1);
-  int* hand = reinterpret_cast<int*>(mine + (kPlanTeamMax - m) * (T + 1));
+  unsigned short* mine = h.wcell + m * (T + 1);
   const float* st = a.in + n * P;
   const float* gl = a.in + (a.N + n) * P;
-    int* waits = a.out + 6 * a.N + n * K;
-    int* leave = waits + a.N * K;
-    float* wp = reinterpret_cast<float*>(a.out + 6 * a.N + 2 * a.N * K) + n * K * P;
-    unsigned short* wout = a.walk ? a.walk + n * a.walk_cap : nullptr;
-    const int sx = plan_cell(a.g, st[0]), sy = plan_cell(a.g, st[1]);
-    int ix = sx, iy = sy;
-    int count = 0, status = kPlanned, cost = -1, acts = 0, ntail = 0;
-    const int d0 = field[iy * G + ix];
-    if (sweeps < 0) {
-      status = kPlanUnconverged;
-    } else if (d0 < 0 || d0 >= kPlanInf) {
-      status = kPlanUnreachable;
-    } else {
-      cost = d0;
-      int prev = -1, waited = 0;
-      mine[0] = (unsigned short)(iy * 128 + ix);
-      if (wout) wout[0] = mine[0];
-      for (;;) {
-        const int t = min(acts, T);
-        const int* dt = field + t * cells;
-        const int dc = dt[iy * G + ix];
-        if (dc == 0) break;
-        if (acts >= T + cells) { status = kPlanUnconverged; break; }
-        const int* dn = field + min(t + 1, T) * cells;
-        const unsigned mv = plan_moves_field(dt, G, ix, iy);
-        int dir = -1;
-        for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
-          if (!(mv & (1u << k))) continue;
-          const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
-          if (v >= 0 && v < kPlanInf && v + (k < 4 ? 5 : 7) == dc) dir = k;
+  int* waits = a.out + 6 * a.N + n * K;
+  int* leave = waits + a.N * K;
+  float* wp = reinterpret_cast<float*>(a.out + 6 * a.N + 2 * a.N * K) + n * K * P;
+  unsigned short* wout = a.walk ? a.walk + n * a.walk_cap : nullptr;
+  const int sx = plan_cell(a.g, st[0]), sy = plan_cell(a.g, st[1]);
+  int ix = sx, iy = sy;
+  int count = 0, status = kPlanned, cost = -1, acts = 0, ntail = 0;
+  const int d0 = field[iy * G + ix];
+  if (sweeps < 0) {
+    status = kPlanUnconverged;
+  } else if (d0 < 0 || d0 >= kPlanInf) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d0;
+    int prev = -1, waited = 0;
+    mine[0] = (unsigned short)(iy * 128 + ix);
+    if (wout) wout[0] = mine[0];
+    for (;;) {
+      const int dc = field[min(acts, T) * cells + iy * G + ix];
+      if (dc == 0) break;
+      if (acts >= T + cells) { status = kPlanUnconverged; break; }
+      const int dir = plan_team_step(field, G, T, acts, dc, ix, iy, prev);
+      if (dir < 0) { status = kPlanUnconverged; break; }   // not a team field of these layers: cannot happen after a converged tail
+      ++acts;
+      if (dir == 8) {
+        ++waited;
+      } else {
+        const bool turned = prev >= 0 && (dir != prev || waited > 0);
+        if (turned) {
+          plan_emit(wp, count, K, P, a.g, ix, iy, gl, true);
+          ++count;
         }
-        if (prev >= 0 && (mv & (1u << prev))) {   // the previous move first
-          const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
-          if (v >= 0 && v < kPlanInf && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
+        if ((prev < 0 || turned) && count < K) {   // this move leaves the anchor of waypoint `count`
+          waits[count] = waited;
+          leave[count] = acts - 1;
         }
-        if (dir < 0 && t < T) {   // the wait last
-          const int v = dn[iy * G + ix];
-          if (v >= 0 && v < kPlanInf && v + kPlanWait == dc) dir = 8;
-        }
-        if (dir < 0) { status = kPlanUnconverged; break; }   // not a team field of these layers: cannot happen after a converged tail
-        ++acts;
-        if (dir == 8) {
-          ++waited;
-        } else {
-          const bool turned = prev >= 0 && (dir != prev || waited > 0);
-          if (turned) {
-            if (count < K) {
-              wp[count * P] = plan_centre(a.g, ix);
-              wp[count * P + 1] = plan_centre(a.g, iy);
-              if (P == 3) wp[count * P + 2] = gl[2];
-            }
-            ++count;
-          }
-          if ((prev < 0 || turned) && count < K) {   // this move leaves the anchor of waypoint `count`
-            waits[count] = waited;
-            leave[count] = acts - 1;
-          }
-          ix += plan_dx(dir); iy += plan_dy(dir);
-          prev = dir;
-          waited = 0;
-        }
-        const unsigned short cell = (unsigned short)(iy * 128 + ix);   // c[acts]
-        if (acts <= T) mine[acts] = cell;
-        if (acts >= T) tail[ntail++] = cell;                             // at most cells + 1 of them (room for cells + 4): acts <= T + cells
-        if (wout && acts < a.walk_cap) wout[acts] = cell;
+        ix += plan_dx(dir); iy += plan_dy(dir);
+        prev = dir;
+        waited = 0;
       }
-      if (status == kPlanned) {
-        if (count < K)
-          for (int j = 0; j < P; ++j) wp[count * P + j] = gl[j];
-        ++count;
-        if (count > K) status = kPlanTruncated;
-      }
+      const unsigned short cell = (unsigned short)(iy * 128 + ix);   // c[acts]
+      if (acts <= T) mine[acts] = cell;
+      if (acts >= T) h.tail[ntail++] = cell;                           // at most cells + 1 of them (room for cells + 4): acts <= T + cells
+      if (wout && acts < a.walk_cap) wout[acts] = cell;
     }
-    if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
-      for (int j = 0; j < min(count, K) * P; ++j) wp[j] = 0.f;
-      for (int j = 0; j < K; ++j) { waits[j] = 0; leave[j] = 0; }
-      count = 0;
-      cost = -1;
-      acts = 0;
-    }
-    if (status == kPlanUnreachable || status == kPlanUnconverged) {   // parked: the start cell, in every layer
-      ix = sx; iy = sy;
-      mine[0] = (unsigned short)(iy * 128 + ix);
-      if (wout) wout[0] = mine[0];
-      ntail = 0;
-    }
-    const unsigned short last = (unsigned short)(iy * 128 + ix);
-    for (int t = acts + 1; t <= T; ++t) mine[t] = last;   // c[a] = c[A] beyond the walk
-    if (acts < T) { tail[0] = last; ntail = 1; }
-    hand[0] = ntail;
-    int* o = a.out + n;
-    o[0] = min(count, K);
-    o[a.N] = count;
-    o[2 * a.N] = status;
-    o[3 * a.N] = cost;
-    o[4 * a.N] = acts;
-    o[5 * a.N] = sweeps;
+    if (status == kPlanned) status = plan_close(wp, count, K, P, gl, true);
+  }
+  if (status == kPlanUnconverged) {
+    plan_give_up(wp, count, cost, K, P);
+    for (int j = 0; j < K; ++j) { waits[j] = 0; leave[j] = 0; }
+    acts = 0;
+  }
+  if (status == kPlanUnreachable || status == kPlanUnconverged) {   // parked: the start cell, in every layer
+    ix = sx; iy = sy;
+    mine[0] = (unsigned short)(iy * 128 + ix);
+    if (wout) wout[0] = mine[0];
+    ntail = 0;
+  }
+  const unsigned short last = (unsigned short)(iy * 128 + ix);
+  for (int t = acts + 1; t <= T; ++t) mine[t] = last;   // c[a] = c[A] beyond the walk
+  if (acts < T) { h.tail[0] = last; ntail = 1; }
+  h.hand[0] = ntail;
+  int* o = a.out + n;
+  plan_result(o, o + a.N, o + 2 * a.N, o + 3 * a.N, count, K, status, cost);
+  o[4 * a.N] = acts;
+  o[5 * a.N] = sweeps;
+}
+
+// One member of a team, robot n planned in slot m, by the whole workgroup: its field by all threads; thread 0 walks that field and
+// leaves the member's c[0 .. T] in LDS and its tail cells in global memory; all threads stamp the tail cells.  Every hand-off through
+// global memory -- the field (and what the caller zeroed) to the walking thread, the tail cells and the stamped map to the whole
+// workgroup -- is a workgroup-scope fence and then the barrier; c[0 .. T] and the count are in LDS, which the barrier orders.
+__device__ __forceinline__ void plan_team_member(const PlanTeamArgs* __restrict__ ap, int n, int m, int* lds) {
+  const int G = ap->g.G, r = ap->reserve, tid = threadIdx.x;
+  const PlanTeamHand h = plan_team_hand(*ap, lds);
+  const int sweeps = plan_team_field<PlanReservedNear>(ap, n, m, lds);
+  __threadfence_block();
+  __syncthreads();
+  if (tid == 0) plan_team_walk(ap, n, m, sweeps, lds);
+  __threadfence_block();
+  __syncthreads();
+  const int ntail = h.hand[0];
+#pragma unroll 1
+  for (int i = tid; i < ntail; i += kPlanFieldThreads) {
+    const int cx = h.tail[i] & 127, cy = h.tail[i] >> 7;
+    for (int y = max(cy - r, 0); y <= min(cy + r, G - 1); ++y)
+      for (int x = max(cx - r, 0); x <= min(cx + r, G - 1); ++x) h.tres[y * G + x] = 1;
+  }
+  // the stamps, bytes in global memory written by any thread, before the next member's tail map (and the next team's zeroes)
+  __threadfence_block();
+  __syncthreads();
 }
 
 // A team is sequential inside and parallel outside: one workgroup of 1024 threads takes one team at a time, a fixed number of
-// workgroups loops over the teams.  Per member: the tail's map (base OR stamped reservations) and k_plan_field_time's in-place
-// relaxation on it; T Jacobi steps, each on a layer map built in LDS from the base layer and a Chebyshev test against the earlier
-// members' c[t] and c[t + 1]; every layer is written to this workgroup's scratch field.  Thread 0 then walks that field
-// (k_plan_path_time's walk, ending where d_t[c] == 0) and leaves the member's c[0 .. T] in LDS and its tail cells in global memory;
-// all threads stamp the tail cells.  Every hand-off through global memory -- the field to the walking thread, the tail cells
-// and the stamped map to the whole workgroup -- is a workgroup-scope fence and then the barrier.  Bounds: G * G sweeps, T + G * G
-// actions: status 3 and zeroed outputs beyond, the member then reserves its start cell.
+// workgroups loops over the teams, member after member (plan_team_member).  Bounds: G * G sweeps, T + G * G actions: status 3 and
+// zeroed outputs beyond, the member then reserves its start cell.
 __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team(const PlanTeamArgs* __restrict__ ap) {
   extern __shared__ __attribute__((aligned(16))) int plan_team_lds[];
-  const int G = ap->g.G, T = ap->T, cells = G * G, tid = threadIdx.x, r = ap->reserve, size = ap->size, n_teams = ap->n_teams;
-  // LDS: d | e | moves (a byte a cell) | wcell [kPlanTeamMax][T + 1] (2 bytes a cell) | hand (32 (T + 1) bytes on: a word boundary)
-  const int* hand = reinterpret_cast<const int*>(reinterpret_cast<unsigned char*>(plan_team_lds + 2 * cells) + cells + kPlanTeamMax * (T + 1) * 2);
-  int* tail = plan_team_wg(*ap) + (T + 1) * cells;
-  unsigned char* tres = reinterpret_cast<unsigned char*>(tail + cells + 4);
+  const int cells = ap->g.G * ap->g.G, tid = threadIdx.x, size = ap->size, n_teams = ap->n_teams;
+  const PlanTeamHand h = plan_team_hand(*ap, plan_team_lds);
   for (int team = blockIdx.x; team < n_teams; team += gridDim.x) {
 #pragma unroll 1
-    for (int c = tid; c < cells; c += kPlanFieldThreads) tres[c] = 0;   // (its last readers and writers: behind the barrier below)
-    for (int m = 0; m < size; ++m) {
-      const int n = team * size + m;
-      const int sweeps = plan_team_field(ap, n, m, plan_team_lds);
-      // the field, written by every thread to global memory, to the one thread that walks it: a fence, then the barrier
-      __threadfence_block();
-      __syncthreads();
-      if (tid == 0) plan_team_walk(ap, n, m, sweeps, plan_team_lds);
-      // the tail cells, written by thread 0 to global memory, to every thread: a fence, then the barrier (c[0 .. T] and the count
-      // are in LDS, which the barrier orders)
-      __threadfence_block();
-      __syncthreads();
-      const int ntail = hand[0];
-#pragma unroll 1
-      for (int i = tid; i < ntail; i += kPlanFieldThreads) {
-        const int cx = tail[i] & 127, cy = tail[i] >> 7;
-        for (int y = max(cy - r, 0); y <= min(cy + r, G - 1); ++y)
-          for (int x = max(cx - r, 0); x <= min(cx + r, G - 1); ++x) tres[y * G + x] = 1;
-      }
-      // the stamps, bytes in global memory written by any thread, before the next member's tail map (and the next team's zeroes)
-      __threadfence_block();
-      __syncthreads();
-    }
+    for (int c = tid; c < cells; c += kPlanFieldThreads) h.tres[c] = 0;   // (its last readers and writers: behind the member's last barrier)
+    for (int m = 0; m < size; ++m) plan_team_member(ap, team * size + m, m, plan_team_lds);
   }
 }
 
@@ -935,7 +882,7 @@ __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team(const PlanTeamA
 // order.  The rounds stop when nobody is parked, after `retries` reorderings, or when the next order was already planned.  The result
 // is the round with the fewest parked members, the earliest on a tie: if that is not the round planned last, the team is planned
 // once more in its order -- the plan is a function of the order alone, so this replay leaves the best round's bits in the outputs.
-// Position p of the order plans robot team * size + order[p] in slot p: plan_team_field and plan_team_walk take both.
+// Position p of the order plans robot team * size + order[p] in slot p: plan_team_member takes both.
 constexpr int kPlanRetriesMax = 8;
 
 struct PlanTeamRoundsArgs {
@@ -951,7 +898,7 @@ inline size_t plan_team_rounds_lds_bytes(int G, int T, int retries) {
 }
 
 // The bookkeeping between two rounds, by one thread between two barriers.  ctl: [0] the row of `hist` to plan next (-1: the team
-// is done), [1] the rounds planned, [2] the best round, [3] 1 while the replay runs.  Not inlined (k_plan_team says why).
+// is done), [1] the rounds planned, [2] the best round, [3] 1 while the replay runs.  Not inlined (plan_team_field says why).
 __device__ __noinline__ void plan_team_round_next(const PlanTeamRoundsArgs* __restrict__ rp, int team, int* ctl) {
   const int size = rp->t.size, R = rp->retries, N = rp->t.N, n_teams = rp->t.n_teams;
   if (ctl[3]) { ctl[0] = -1; return; }   // that was the replay of the best round
@@ -996,28 +943,25 @@ __device__ __noinline__ void plan_team_round_next(const PlanTeamRoundsArgs* __re
 __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team_rounds(const PlanTeamRoundsArgs* __restrict__ rp) {
   extern __shared__ __attribute__((aligned(16))) int plan_team_rounds_lds[];
   const PlanTeamArgs* ap = &rp->t;
-  const int G = ap->g.G, T = ap->T, cells = G * G, tid = threadIdx.x, r = ap->reserve, size = ap->size, n_teams = ap->n_teams;
-  const int K = ap->K, P = ap->P, N = ap->N;
+  const int cells = ap->g.G * ap->g.G, tid = threadIdx.x, size = ap->size, n_teams = ap->n_teams;
   // LDS: k_plan_team's (d | e | moves | wcell | hand, 16 bytes) | ctl [4] | parked [R + 1] | hist [R + 1][16] (bytes)
-  int* hand = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(plan_team_rounds_lds + 2 * cells) + cells + kPlanTeamMax * (T + 1) * 2);
-  int* ctl = hand + 4;
-  const unsigned char* hist = reinterpret_cast<const unsigned char*>(ctl + 4 + rp->retries + 1);
-  int* tail = plan_team_wg(*ap) + (T + 1) * cells;
-  unsigned char* tres = reinterpret_cast<unsigned char*>(tail + cells + 4);
+  const PlanTeamHand h = plan_team_hand(*ap, plan_team_rounds_lds);
+  int* ctl = h.hand + 4;
+  unsigned char* hist = reinterpret_cast<unsigned char*>(ctl + 4 + rp->retries + 1);
   for (int team = blockIdx.x; team < n_teams; team += gridDim.x) {
     if (tid == 0) {   // round 0: the identity order (the last team's readers of ctl and hist: behind the barrier that ended its rounds)
       ctl[0] = 0; ctl[1] = 0; ctl[2] = 0; ctl[3] = 0;
-      unsigned char* first = reinterpret_cast<unsigned char*>(ctl + 4 + rp->retries + 1);
-      for (int p = 0; p < kPlanTeamMax; ++p) first[p] = (unsigned char)p;
+      for (int p = 0; p < kPlanTeamMax; ++p) hist[p] = (unsigned char)p;
     }
     __syncthreads();
     for (int pass = 0;; ++pass) {   // at most retries + 1 rounds and the replay
       const unsigned char* ord = hist + ctl[0] * kPlanTeamMax;
 #pragma unroll 1
-      for (int c = tid; c < cells; c += kPlanFieldThreads) tres[c] = 0;   // per round (its last readers and writers: behind a barrier)
+      for (int c = tid; c < cells; c += kPlanFieldThreads) h.tres[c] = 0;   // per round (its last readers and writers: behind a barrier)
       for (int m = 0; m < size; ++m) {
         const int n = team * size + ord[m];
         if (pass > 0) {   // plan_team_walk writes only the slots its walk touches: what the member's last walk left goes first
+          const int K = ap->K, P = ap->P, N = ap->N;   // (read here: live across the member's phases they would take scalar registers)
           int* waits = ap->out + 6 * N + n * K;
           float* wp = reinterpret_cast<float*>(ap->out + 6 * N + 2 * N * K) + n * K * P;
 #pragma unroll 1
@@ -1025,22 +969,7 @@ __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team_rounds(const Pl
 #pragma unroll 1
           for (int j = tid; j < K * P; j += kPlanFieldThreads) wp[j] = 0.f;
         }
-        const int sweeps = plan_team_field(ap, n, m, plan_team_rounds_lds);
-        // the field and the zeroes, written by every thread to global memory, to the one thread that walks: a fence, then the barrier
-        __threadfence_block();
-        __syncthreads();
-        if (tid == 0) plan_team_walk(ap, n, m, sweeps, plan_team_rounds_lds);
-        __threadfence_block();
-        __syncthreads();
-        const int ntail = hand[0];
-#pragma unroll 1
-        for (int i = tid; i < ntail; i += kPlanFieldThreads) {
-          const int cx = tail[i] & 127, cy = tail[i] >> 7;
-          for (int y = max(cy - r, 0); y <= min(cy + r, G - 1); ++y)
-            for (int x = max(cx - r, 0); x <= min(cx + r, G - 1); ++x) tres[y * G + x] = 1;
-        }
-        __threadfence_block();
-        __syncthreads();
+        plan_team_member(ap, n, m, plan_team_rounds_lds);
       }
       if (tid == 0) plan_team_round_next(rp, team, ctl);   // thread 0 wrote the statuses it reads
       __syncthreads();
@@ -1054,8 +983,6 @@ __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team_rounds(const Pl
 // grid_los_time / grid_smooth_time / grid_path_smooth_time) -------------------------------------------------------------------------
 // A straight leg is tested against EVERY layer it spans.  nb[t][c]: the first layer from t on in which cell c is not clear
 // (kPlanNeverBlocked: none), so "c is clear in the layers lo .. hi" is nb[lo][c] > hi, one load whatever the span.
-constexpr short kPlanNeverBlocked = 32767;   // kPlanLayersMax is 256: a short holds every layer
-
 struct PlanNextBlockedArgs {
   int G, T;
   const unsigned char* blk;   // [S][T + 1][G][G] cells that are not clear: k_plan_occupancy_time's maps (margin 0) or k_plan_dilate's of them
@@ -1073,53 +1000,6 @@ __global__ __launch_bounds__(256) void k_plan_next_blocked(PlanNextBlockedArgs a
   }
 }
 
-// goal_rules.grid_los_time on the layer nbl = nb[lo] with the threshold hi: plan_los on the map nbl <= hi, line for line
-__device__ __forceinline__ bool plan_los_time(const short* nbl, int hi, int G, int x, int y, int x1, int y1) {
-  if (nbl[y * G + x] <= hi) return false;
-  const int dx = abs(x1 - x), dy = abs(y1 - y), sx = x1 > x ? 1 : -1, sy = y1 > y ? 1 : -1;
-  int ix = 0, iy = 0;
-  for (int it = 0; it < 2 * G && (ix < dx || iy < dy); ++it) {
-    const int t = (1 + 2 * ix) * dy - (1 + 2 * iy) * dx;
-    if (t < 0) {
-      x += sx; ++ix;
-    } else if (t > 0) {
-      y += sy; ++iy;
-    } else {   // exactly through a cell corner: both cells that share it must be clear
-      if (nbl[y * G + x + sx] <= hi || nbl[(y + sy) * G + x] <= hi) return false;
-      x += sx; y += sy; ++ix; ++iy;
-    }
-    if (nbl[y * G + x] <= hi) return false;
-  }
-  return ix == dx && iy == dy;
-}
-
-// the action the walk of goal_rules.grid_walk_time makes as its action number t from the cell (ix, iy): 0 .. 7 a move, 8 the wait,
-// -1 none (d is not the time field of occ).  k_plan_path_time's own step, line for line; that kernel keeps its copy in place, as
-// k_plan_path keeps its copy beside plan_walk_dir.
-__device__ __forceinline__ int plan_walk_time_dir(const unsigned char* occ, const int* d, int G, int T, int t, int ix, int iy, int prev) {
-  const int cells = G * G;
-  if (t >= T) return plan_walk_dir(occ + (size_t)T * cells, d + (size_t)T * cells, G, ix, iy, prev);
-  const unsigned char* occ_t = occ + (size_t)t * cells;
-  const int* dn = d + (size_t)(t + 1) * cells;
-  const unsigned m = plan_moves(occ_t, G, ix, iy);
-  const int dc = d[(size_t)t * cells + iy * G + ix];
-  int dir = -1;
-  for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
-    if (!(m & (1u << k))) continue;
-    const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
-    if (v >= 0 && v + (k < 4 ? 5 : 7) == dc) dir = k;
-  }
-  if (prev >= 0 && (m & (1u << prev))) {   // the previous move first
-    const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
-    if (v >= 0 && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
-  }
-  if (dir < 0) {   // the wait last
-    const int v = dn[iy * G + ix];
-    if (v >= 0 && v + kPlanWait == dc) dir = 8;
-  }
-  return dir;
-}
-
 struct PlanSmoothTimeArgs {
   PlanPathArgs p;    // k_plan_path's inputs and outputs; occ [S][T + 1][G][G], field [F][T + 1][G][G]
   int T;
@@ -1129,115 +1009,19 @@ struct PlanSmoothTimeArgs {
   int* moves;        // [N] out: those of them that are moves
 };
 
-// k_plan_smooth over time: one wave per robot (grid N, 64 threads), no barrier in any loop, the ring of kPlanRing packed cells in
-// LDS.  The ring is indexed by ACTION: c[a] is the cell after a actions, a wait repeats its cell, so `walked` counts actions + 1.
-// With the anchor c[i] and base = i + 2, lane l tests plan_los_time(c[i], c[base + l]) on nb[min(i, T)] with the threshold
-// min(base + l, T): every layer the leg spans.  The first lane that fails, z = ctz(ballot), is the rule's first hidden index: c[base + z
-// - 1] is emitted and becomes the anchor.  Bounds: the walk T + G * G actions (k_plan_path_time's), the window loop T + G * G
-// rounds (base grows by at least 1 a round and ends beyond A <= T + G * G), plan_los_time 2 G steps: status 3, outputs zeroed.
 __global__ __launch_bounds__(64) void k_plan_smooth_time(PlanSmoothTimeArgs s) {
   __shared__ unsigned short ring[kPlanRing];
-  const PlanPathArgs& a = s.p;
-  const int n = blockIdx.x, lane = threadIdx.x;
-  const int G = a.g.G, cells = G * G, P = a.P, K = a.K, T = s.T;
-  const int f = a.field_of[n];
-  const size_t scene_off = (size_t)a.field_scene[f] * (T + 1) * cells;
-  const unsigned char* occ = a.occ + scene_off;
-  const short* nb = s.nb + scene_off;
-  const int* d = a.field + (size_t)f * (T + 1) * cells;
-  const float* st = a.start + (size_t)n * P;
-  const float* gl = a.goal + (size_t)n * P;
-  float* wp = a.wp + (size_t)n * K * P;
-  int* leave = s.leave + (size_t)n * K;
-  int wx = plan_cell(a.g, st[0]), wy = plan_cell(a.g, st[1]);   // the walker
-  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
-  int count = 0, status = kPlanned, cost = -1, walked = 1, moves = 0;   // walked: cells c[0 .. walked - 1] are known
-  if (a.sweeps[f] < 0) {
-    status = kPlanUnconverged;
-  } else if (d[wy * G + wx] < 0) {
-    status = kPlanUnreachable;
-  } else {
-    cost = d[wy * G + wx];
-    int ax = wx, ay = wy, ai = 0, base = 2, prev = -1;   // the anchor's cell and action index
-    bool done = wx == gx && wy == gy;
-    if (lane == 0) ring[0] = (unsigned short)(wy * 128 + wx);
-    for (int round = 0;; ++round) {
-      if (round > T + cells) { status = kPlanUnconverged; break; }
-      while (!done && walked <= base + 63) {   // the walk, up to the end of the window
-        if (walked > T + cells) { status = kPlanUnconverged; break; }
-        const int dir = plan_walk_time_dir(occ, d, G, T, walked - 1, wx, wy, prev);
-        if (dir < 0) { status = kPlanUnconverged; break; }
-        if (dir != 8) {
-          wx += plan_dx(dir); wy += plan_dy(dir);
-          prev = dir;
-          ++moves;
-        }
-        if (lane == 0) ring[walked & (kPlanRing - 1)] = (unsigned short)(wy * 128 + wx);
-        ++walked;
-        done = wx == gx && wy == gy;
-      }
-      if (status != kPlanned) break;
-      if (done && base >= walked) break;   // no candidate left: A = walked - 1
-      // lane 0's stores to the ring before every lane's loads from it: one wave, so a wave-level fence and no barrier
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const int idx = base + lane;
-      bool hidden = false;
-      if (idx < walked) {
-        const int c = ring[idx & (kPlanRing - 1)];
-        hidden = !plan_los_time(nb + (size_t)min(ai, T) * cells, min(idx, T), G, ax, ay, c & 127, c >> 7);
-      }
-      const unsigned long long fails = __ballot(hidden);
-      if (fails == 0) { base += 64; continue; }
-      const int j = base + __builtin_ctzll(fails) - 1;   // the last visible index: emitted, the next anchor
-      const int c = __builtin_amdgcn_readfirstlane((int)ring[j & (kPlanRing - 1)]);
-      ax = c & 127; ay = c >> 7; ai = j;
-      if (count < K && lane == 0) {
-        wp[count * P] = plan_centre(a.g, ax);
-        wp[count * P + 1] = plan_centre(a.g, ay);
-        if (P == 3) wp[count * P + 2] = gl[2];
-      }
-      ++count;
-      if (count < K && lane == 0) leave[count] = j;   // the anchor of the waypoint that follows
-      base = j + 2;
-      // the loads above before the walk's next stores to the ring
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-    if (status == kPlanned) {
-      if (count < K && lane == 0)
-        for (int q = 0; q < P; ++q) wp[count * P + q] = gl[q];
-      ++count;
-      if (count > K) status = kPlanTruncated;
-    }
-  }
-  if (lane != 0) return;
-  int acts = walked - 1;
-  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out
-    for (int q = 0; q < min(count, K) * P; ++q) wp[q] = 0.f;
-    for (int q = 0; q < K; ++q) leave[q] = 0;
-    count = 0;
-    cost = -1;
-    acts = 0;
-    moves = 0;
-  }
-  a.nwp[n] = min(count, K);
-  a.count[n] = count;
-  a.status[n] = status;
-  a.cost[n] = cost;
-  s.arrive[n] = acts;
-  s.moves[n] = moves;
+  plan_smooth<true>(s, ring);
 }
 
 // ---- smoothing of a team plan (mobrob_ppo_plan_grid_team_smooth; the rule: goal_rules.grid_leg_cells / grid_reserve_legs /
 // grid_plan_team(smooth=True)) ------------------------------------------------------------------------------------------------------
-// k_plan_team with line-of-sight legs, here because it needs plan_los_time.  A smoothed leg is reserved as a SWEPT region: every
-// cell of its supercover (both ends, every cell stepped into, both cells at a corner), dilated by r, in EVERY layer of its span, so
-// the member may be anywhere on the leg at any time of the span.  The earlier members' reservations are a byte map of this workgroup
-// in global scratch, res [T + 1][G][G]; it replaces k_plan_team's Chebyshev test against c[t], c[t + 1] and its tail stamps.  The
-// member's map occ_t = base_t OR res_t gives its field, its walk and ITS next-blocked table nb (k_plan_next_blocked's meaning, at the
-// margin), all in this workgroup's scratch.  Legs are capped at max_leg actions: a long leg reserves all of itself for all of its span.
+// k_plan_team with line-of-sight legs.  A smoothed leg is reserved as a SWEPT region: every cell of its supercover (both ends, every
+// cell stepped into, both cells at a corner), dilated by r, in EVERY layer of its span, so the member may be anywhere on the leg at
+// any time of the span.  The earlier members' reservations are a byte map of this workgroup in global scratch, res [T + 1][G][G]; it
+// replaces k_plan_team's Chebyshev test against c[t], c[t + 1] and its tail stamps.  The member's map occ_t = base_t OR res_t gives
+// its field, its walk and ITS next-blocked table nb (k_plan_next_blocked's meaning, at the margin), all in this workgroup's scratch.
+// Legs are capped at max_leg actions: a long leg reserves all of itself for all of its span.
 struct PlanTeamSmoothArgs {
   PlanTeamArgs t;     // k_plan_team's, with t.wg: per workgroup plan_team_smooth_wg_bytes(G, T) bytes: field int [T + 1][G][G] | nb short
                       // [T + 1][G][G] | res byte [T + 1][G][G] | wk: the walk's cells c[0 .. A], packed iy * 128 + ix, 2 bytes each | kp:
@@ -1276,108 +1060,26 @@ __device__ __forceinline__ PlanTeamSmoothWg plan_team_smooth_wg(const PlanTeamSm
   return w;
 }
 
-// is a cell within `margin` (0 or 1) of (x, y) that lies in the grid blocked?  (goal_rules.los_blocked, a cell at a time.)  Nine loads
-// without a branch: the neighbours are clamped into the grid, where a clamped one repeats a cell of the neighbourhood; at margin 0
-// all nine are the cell itself.
-template <class Occ>
-__device__ __forceinline__ bool plan_near_blocked(const Occ* occ, int G, int x, int y, int margin) {
-  const int x0 = max(x - margin, 0), x1 = min(x + margin, G - 1), r0 = max(y - margin, 0) * G, r1 = y * G, r2 = min(y + margin, G - 1) * G;
-  return (occ[r0 + x0] | occ[r0 + x] | occ[r0 + x1] | occ[r1 + x0] | occ[r1 + x] | occ[r1 + x1] | occ[r2 + x0] | occ[r2 + x] | occ[r2 + x1]) != 0;
-}
-
-// One member's field AND next-blocked table, by the whole workgroup -> the sweeps of the tail's relaxation (-1: bound hit).
-// plan_team_field's recurrence; the layer map is the base layer OR the reservation byte.  The same pass over the layers, tail first,
-// writes nb from the layer's blocked bytes in LDS: the byte itself at margin 0, the OR over the 3 x 3 neighbours at margin 1; nb[t +
-// 1][c] is read back by the thread that wrote it.
-__device__ __noinline__ int plan_team_smooth_field(const PlanTeamSmoothArgs* __restrict__ sp, int n, int* lds) {
-  const PlanTeamArgs& a = sp->t;
-  const int G = a.g.G, T = a.T, cells = G * G, tid = threadIdx.x, margin = sp->margin;
-  const int gs = 31 - __clz(G), gm = G - 1;   // G is a power of two: cell c is (c & gm, c >> gs)
-  struct { int* lds; } f{lds};
-  const int scene = a.has_scene ? reinterpret_cast<const int*>(a.in + 2 * a.N * a.P)[n] : 0;
-  const float* gl = a.in + (a.N + n) * a.P;
-  const int goal = plan_cell(a.g, gl[1]) * G + plan_cell(a.g, gl[0]);
-  int* d = f.lds;
-  int* e = f.lds + cells;
-  unsigned char* moves = reinterpret_cast<unsigned char*>(f.lds + 2 * cells);
-  const unsigned char* occ_scene = a.occ + (size_t)scene * (T + 1) * cells;
-  const PlanTeamSmoothWg wg = plan_team_smooth_wg(*sp);
-  int* field = wg.field;
-  short* nb = wg.nb;
-  const unsigned char* res = wg.res;
-  int* out = a.fields ? a.fields + n * (T + 1) * cells : nullptr;
-  const unsigned char* occ_T = occ_scene + (size_t)T * cells;
-#pragma unroll 1
-  for (int c = tid; c < cells; c += kPlanFieldThreads) e[c] = (occ_T[c] | res[T * cells + c]) ? 1 : 0;
-  __syncthreads();
-  bool terminal = e[goal] == 0;
-#pragma unroll 1
-  for (int c = tid; c < cells; c += kPlanFieldThreads) {
-    const bool blocked = e[c] != 0;
-    moves[c] = blocked ? 0 : (unsigned char)plan_moves(e, G, c & gm, c >> gs);
-    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
+// Where "reserved" comes from in the field of a member of k_plan_team_smooth: the workgroup's byte map res, tail and layers alike.  The
+// field pass also writes the member's next-blocked table.
+struct PlanReservedSwept {
+  using Args = PlanTeamSmoothArgs;
+  static constexpr bool kNextBlocked = true;
+  int* field;
+  short* nb;
+  const unsigned char* res;
+  int cells, T, margin;
+  __device__ __forceinline__ PlanReservedSwept(const Args& s, int, int*) : cells(s.t.g.G * s.t.g.G), T(s.t.T), margin(s.margin) {
+    const PlanTeamSmoothWg wg = plan_team_smooth_wg(s);
+    field = wg.field;
+    nb = wg.nb;
+    res = wg.res;
   }
-  __syncthreads();
-  int sweeps = -1;
-  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
-    int changed = 0;
-#pragma unroll 1
-    for (int c = tid; c < cells; c += kPlanFieldThreads) {
-      const unsigned mv = moves[c];
-      if (mv == 0 || c == goal) continue;
-      const int cur = d[c];
-      int best = cur;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (mv & (1u << k)) best = min(best, d[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
-      if (best < cur) { d[c] = best; changed = 1; }
-    }
-    __syncthreads();   // this sweep's stores before the next sweep's loads
-    if (!__syncthreads_or(changed)) { sweeps = sweep; break; }
-  }
-#pragma unroll 1
-  for (int c = tid; c < cells; c += kPlanFieldThreads) {
-    field[T * cells + c] = e[c] ? -1 : d[c];
-    if (out) out[T * cells + c] = d[c] >= kPlanInf ? -1 : d[c];
-    const bool hid = plan_near_blocked(e, G, c & gm, c >> gs, margin);
-    nb[T * cells + c] = hid ? (short)T : kPlanNeverBlocked;
-  }
-  int* nxt = d;   // layer t + 1
-  int* cur = e;   // layer t
-  for (int t = T - 1; t >= 0; --t) {
-    const unsigned char* occ_t = occ_scene + (size_t)t * cells;
-    // layer t's map into `moves` (the tail's moves are done with): the base layer, or reserved by an earlier member in this layer
-#pragma unroll 1
-    for (int c = tid; c < cells; c += kPlanFieldThreads) moves[c] = (occ_t[c] | res[t * cells + c]) ? 1 : 0;
-    __syncthreads();   // the map before its readers; also e's last readers (the tail's write-out) before the first layer's stores
-    terminal = terminal && moves[goal] == 0;
-#pragma unroll 1
-    for (int c = tid; c < cells; c += kPlanFieldThreads) {
-      int best = kPlanInf;
-      const bool blocked = moves[c] != 0;
-      if (!blocked) {
-        if (c == goal && terminal) {
-          best = 0;
-        } else {
-          const unsigned mv = plan_moves(moves, G, c & gm, c >> gs);
-          best = nxt[c] + kPlanWait;
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            if (mv & (1u << k)) best = min(best, nxt[c + plan_dy(k) * G + plan_dx(k)] + (k < 4 ? 5 : 7));
-          best = min(best, kPlanInf);   // kPlanInf + a cost: still "none"
-        }
-      }
-      cur[c] = best;
-      field[t * cells + c] = blocked ? -1 : best;
-      if (out) out[t * cells + c] = best >= kPlanInf ? -1 : best;
-      const bool hid = plan_near_blocked(moves, G, c & gm, c >> gs, margin);
-      nb[t * cells + c] = hid ? (short)t : nb[(t + 1) * cells + c];
-    }
-    __syncthreads();
-    int* const swap = nxt; nxt = cur; cur = swap;
-  }
-  return sweeps;
-}
+  __device__ __forceinline__ static const PlanTeamArgs& team(const Args& s) { return s.t; }
+  // both bytes are loaded whatever the first holds: two loads in flight, no branch between them
+  __device__ __forceinline__ bool tail(int c, bool base) const { return base | (res[T * cells + c] != 0); }
+  __device__ __forceinline__ bool layer(int t, int c, bool base) const { return base | (res[t * cells + c] != 0); }
+};
 
 // The walk of one member, by one thread: plan_team_walk's loop on this workgroup's scratch field, ending where d_t[c] == 0.  It leaves
 // ALL of c[0 .. A] in wk (global scratch: the smoothing reads any of them) and hands over hand[0] = A, [1] = status, [2] = cost,
@@ -1403,27 +1105,10 @@ __device__ __noinline__ void plan_team_smooth_walk(const PlanTeamSmoothArgs* __r
     cost = d0;
     int prev = -1;
     for (;;) {
-      const int t = min(acts, T);
-      const int* dt = field + t * cells;
-      const int dc = dt[iy * G + ix];
+      const int dc = field[min(acts, T) * cells + iy * G + ix];
       if (dc == 0) break;
       if (acts >= T + cells) { status = kPlanUnconverged; break; }
-      const int* dn = field + min(t + 1, T) * cells;
-      const unsigned mv = plan_moves_field(dt, G, ix, iy);
-      int dir = -1;
-      for (int k = 7; k >= 0; --k) {   // descending: the lowest qualifying index is kept
-        if (!(mv & (1u << k))) continue;
-        const int v = dn[(iy + plan_dy(k)) * G + ix + plan_dx(k)];
-        if (v >= 0 && v < kPlanInf && v + (k < 4 ? 5 : 7) == dc) dir = k;
-      }
-      if (prev >= 0 && (mv & (1u << prev))) {   // the previous move first
-        const int v = dn[(iy + plan_dy(prev)) * G + ix + plan_dx(prev)];
-        if (v >= 0 && v < kPlanInf && v + (prev < 4 ? 5 : 7) == dc) dir = prev;
-      }
-      if (dir < 0 && t < T) {   // the wait last
-        const int v = dn[iy * G + ix];
-        if (v >= 0 && v < kPlanInf && v + kPlanWait == dc) dir = 8;
-      }
+      const int dir = plan_team_step(field, G, T, acts, dc, ix, iy, prev);
       if (dir < 0) { status = kPlanUnconverged; break; }   // not a team field of these layers: cannot happen after a converged tail
       ++acts;
       if (dir != 8) {
@@ -1444,7 +1129,7 @@ __device__ __noinline__ void plan_team_smooth_walk(const PlanTeamSmoothArgs* __r
   hand[0] = acts; hand[1] = status; hand[2] = cost; hand[3] = moves;
 }
 
-// The smoothing of one member, by the workgroup's first wave: k_plan_smooth_time's window on the finished walk.  With the anchor c[i]
+// The smoothing of one member, by the workgroup's first wave: plan_smooth<true>'s window on the finished walk.  With the anchor c[i]
 // and base = i + 2, lane l tests the leg to c[base + l] on nb[min(i, T)] against the threshold min(base + l, T), and its length base +
 // l - i against max_leg.  The first lane that fails, z = ctz(ballot), is the rule's first hidden or over-cap index: c[base + z - 1] is
 // kept and becomes the anchor.  Lane 0 writes the member's outputs and hands over hand[0] = A, hand[4] = the number of kept indices.
@@ -1481,52 +1166,42 @@ __device__ __noinline__ void plan_team_smooth_legs(const PlanTeamSmoothArgs* __r
       if (lane == 0) {
         kp[count] = (unsigned short)j;                   // count <= A - 1 < plan_team_smooth_walk_cap
         if (keep && count < keep_cap) keep[count] = j;
-        if (count < K) {
-          wp[count * P] = plan_centre(a.g, ax);
-          wp[count * P + 1] = plan_centre(a.g, ay);
-          if (P == 3) wp[count * P + 2] = gl[2];
-        }
       }
+      plan_emit(wp, count, K, P, a.g, ax, ay, gl, lane == 0);
       ++count;
       if (count < K && lane == 0) leave[count] = j;      // the anchor of the waypoint that follows
       base = j + 2;
     }
-    if (status == kPlanned) {
-      if (count < K && lane == 0)
-        for (int q = 0; q < P; ++q) wp[count * P + q] = gl[q];
-      ++count;
-      if (count > K) status = kPlanTruncated;
-    }
+    if (status == kPlanned) status = plan_close(wp, count, K, P, gl, lane == 0);
   }
   if (lane != 0) return;
   int kept = count > 0 ? count - 1 : 0;
-  if (status == kPlanUnconverged) {   // nothing of a walk that was given up is handed out; the member parks
-    for (int q = 0; q < min(count, K) * P; ++q) wp[q] = 0.f;
-    for (int q = 0; q < K; ++q) leave[q] = 0;
+  if (status == kPlanUnconverged) {   // the member parks
     if (keep)
       for (int q = 0; q < min(count, keep_cap); ++q) keep[q] = 0;
+    plan_give_up(wp, count, cost, K, P);
+    for (int q = 0; q < K; ++q) leave[q] = 0;
     if (a.walk)
       for (int q = 1; q < min(A + 1, a.walk_cap); ++q) a.walk[n * a.walk_cap + q] = 0;
-    count = 0; cost = -1; A = 0; moves = 0; kept = 0;
+    A = 0; moves = 0; kept = 0;
   }
   hand[0] = A;
   hand[4] = kept;
   int* o = a.out + n;
-  o[0] = min(count, K);
-  o[N] = count;
-  o[2 * N] = status;
-  o[3 * N] = cost;
+  plan_result(o, o + N, o + 2 * N, o + 3 * N, count, K, status, cost);
   o[4 * N] = A;
   o[5 * N] = sweeps;
   o[6 * N] = moves;
 }
 
 // The reservation of one member, by all threads: a wave per leg, a lane per layer of the leg's span.  The leg (a, b) goes into the layers
-// min(a, T) .. min(b - 1, T): a leg of one action as its two cells, a longer one as plan_los_time's supercover of c[a] .. c[b], cell by
+// min(a, T) .. min(b - 1, T): a leg of one action as its two cells, a longer one as plan_los's supercover of c[a] .. c[b], cell by
 // cell, both cells at a corner.  One more "leg" is the end cell c[A] in the layers min(A, T) .. T; for a parked member (A = 0) that is
 // its start cell in every layer.  A round of the walk leaves one cell to stamp, or three at a corner; every cell goes through the one
 // loop over the (2 r + 1)^2 cells around it, which writes only those in the grid (the ends are cells of the walk and the supercover
 // stays inside their bounding box, so the centres are in the grid themselves).
+// The traversal is plan_los's, written out: the stamp funnels the one or three cells of a round through ONE copy of the stamping
+// loop, where plan_los's shape (a predicate called at four places) would inline that loop four times.
 __device__ __noinline__ void plan_team_smooth_stamp(const PlanTeamSmoothArgs* __restrict__ sp, const int* hand) {
   const PlanTeamArgs& a = sp->t;
   const int G = a.g.G, T = a.T, cells = G * G, r = a.reserve, w = 2 * r + 1, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1569,7 +1244,7 @@ __device__ __noinline__ void plan_team_smooth_stamp(const PlanTeamSmoothArgs* __
 }
 
 // One workgroup of 1024 threads takes one team at a time, as k_plan_team does.  Per member four phases, each a function that is not
-// inlined and reads the arguments from memory (k_plan_team says why): the field and nb by all threads; the walk by thread 0; the
+// inlined and reads the arguments from memory (plan_team_field says why): the field and nb by all threads; the walk by thread 0; the
 // smoothing by the first wave; the stamps by all threads.  Every hand-off through global memory -- the zeroed and the stamped
 // reservation, the field and nb, the walk's cells, the kept indices -- is a workgroup-scope fence and then the barrier; the handed
 // words are in LDS, which the barrier orders.  Bounds: G * G sweeps, T + G * G actions, T + G * G window rounds, 2 G steps a sight
@@ -1586,7 +1261,7 @@ __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team_smooth(const Pl
     __syncthreads();
     for (int m = 0; m < size; ++m) {
       const int n = team * size + m;
-      const int sweeps = plan_team_smooth_field(sp, n, plan_team_smooth_lds);
+      const int sweeps = plan_team_field<PlanReservedSwept>(sp, n, m, plan_team_smooth_lds);
       __threadfence_block();
       __syncthreads();
       if (tid == 0) plan_team_smooth_walk(sp, n, sweeps, hand);

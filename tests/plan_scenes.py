@@ -1,7 +1,7 @@
 """Scenes shared by tests/test_plan_cpu.py and tests/test_plan_gpu.py (no tests here)."""
 import numpy as np
 
-from mobrob_amd.envs.goal_rules import GridSpec, Hazards, Walls
+from mobrob_amd.envs.goal_rules import GridSpec, Hazards, MovingHazards, Walls
 
 EXTENT = 2.0
 
@@ -44,6 +44,25 @@ def robots33():
     start[5], start[6] = POCKET, (1.3, -1.35)                      # out of the sealed pocket (scene 1 has none: robot 5 is free there)
     start[4] = (1.25, -1.25)                                       # robot 4 (scene 0) starts inside the pocket and has the pocket as goal
     return scene, start.astype(np.float32), goals[which].astype(np.float32)
+
+
+def robots8_xyz():
+    """8 robots with THREE-column starts and goals in scene 0 at 32 cells: starts left of the thin wall, goals right of it, so every
+    path turns at the gap; a plan's waypoints all carry the goal's z.  With K = 4 some plans truncate.  As teams of 2, mates cross on the way to the gap;
+    two hazards circle in the lower left and the right half, clear of the gap -> (spec, walls, moving hazards, start [8][3], goal [8][3])"""
+    rng = np.random.default_rng(29)
+    start = np.concatenate([rng.uniform(-1.5, -0.2, (8, 1)), rng.uniform(-1.5, 1.5, (8, 1)), rng.uniform(0.1, 0.9, (8, 1))], axis=1)
+    goal = np.array([OPEN_RIGHT + (0.25,), (1.3, -0.2, 0.5), (0.5, 0.25, 0.75), (-0.3, 1.3, 1.0)])[np.arange(8) % 4]
+    hz = MovingHazards.circling(np.array([[-0.9, -0.8], [0.9, -0.3]]), travel=0.3, size=0.1, n_frames=12, dt=2 * np.pi / 12, frame_steps=5, loop=True)
+    return GridSpec(EXTENT, 32, INFLATE), Walls(SCENE0, radius=0.05), hz, start.astype(np.float32), goal.astype(np.float32)
+
+
+def xyz_checked(plan, goal, K):
+    """a three-column plan: some robot truncates at K, and every waypoint handed out carries its robot's goal z"""
+    assert plan["waypoints"].shape == (len(goal), K, 3) and np.any(plan["status"] == 2) and np.any(plan["status"] == 0)
+    for i, nw in enumerate(plan["n_waypoints"]):
+        assert np.all(plan["waypoints"][i, :nw, 2] == goal[i, 2]) and not plan["waypoints"][i, nw:].any()
+    return plan
 
 
 def serpentine(cells=64, lanes=15):

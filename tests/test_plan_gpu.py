@@ -8,7 +8,7 @@ from mobrob_amd.envs import goal_rules as R
 from mobrob_amd.envs.goal_rules import GridSpec, Hazards, Walls, grid_plan
 from mobrob_amd.planning import GridPlanner
 from mobrob_amd.waypoints import STALLED, follow_with_replanning
-from tests.plan_scenes import EXTENT, INFLATE, SCENE0, arena, robots33, serpentine, three_hazards, two_scenes
+from tests.plan_scenes import EXTENT, INFLATE, SCENE0, arena, robots8_xyz, robots33, serpentine, three_hazards, two_scenes, xyz_checked
 from tests.util import _engine, _env, _snapshot, golden_params, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +50,12 @@ def test_g32_two_scenes_33_robots_7_goals(engine, scene_kind):
         assert not dev["occupancy"].any() and np.all(dev["status"] == R.PLANNED)
         none = engine.plan_grid(spec, None, None, start=start, goal=goal, max_waypoints=4, want_occupancy=True, want_fields=True)
         same(none, ref)
+
+
+def test_g32_three_column_starts_and_goals(engine):
+    spec, walls, _, start, goal = robots8_xyz()
+    ref = xyz_checked(grid_plan(spec, walls, None, start, goal, 4), goal, 4)
+    same(engine.plan_grid(spec, walls, None, start=start, goal=goal, max_waypoints=4, want_occupancy=True, want_fields=True), ref)
 
 
 def test_g128_four_fields_uses_the_large_lds_path(engine):

@@ -8,7 +8,7 @@ from mobrob_amd.envs import goal_rules as R
 from mobrob_amd.envs.goal_rules import GridSpec, Hazards, Walls, grid_plan
 from mobrob_amd.planning import GridPlanner
 from mobrob_amd.waypoints import STALLED, follow_with_replanning
-from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots33, serpentine, three_hazards, two_scenes
+from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots8_xyz, robots33, serpentine, three_hazards, two_scenes, xyz_checked
 from tests.plan_smooth_cases import KEYS, corners_met, same_plan, window_edges
 from tests.util import _engine, _env, _snapshot, golden_params, load_golden
 
@@ -48,6 +48,12 @@ def test_g32_two_scenes_33_robots(engine, scene_kind, margin):
         assert np.all(dev["count"] == 1)
     if margin == 0:
         assert np.all(dev["count"] <= full["count"])
+
+
+def test_g32_three_column_starts_and_goals(engine):
+    spec, walls, _, start, goal = robots8_xyz()
+    dev, ref, _ = smooth_both(engine, spec, walls, None, start, goal, 2, 0)
+    same_plan(dev, xyz_checked(ref, goal, 2))
 
 
 def test_g128_walks_longer_than_one_window(engine):

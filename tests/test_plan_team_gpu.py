@@ -10,7 +10,7 @@ from mobrob_amd.envs import goal_rules as R
 from mobrob_amd.envs.goal_rules import GridSpec, Teams, Walls, grid_plan, grid_plan_team
 from mobrob_amd.planning import GridPlanner
 from mobrob_amd.waypoints import follow_with_replanning
-from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots33, serpentine, three_hazards, two_scenes
+from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots8_xyz, robots33, serpentine, three_hazards, two_scenes, xyz_checked
 from tests.plan_team_scenes import centres, circling32, lattice_case, same_team, swap_case, teams
 from tests.plan_time_scenes import same_time
 from tests.util import _engine, _env, _snapshot, golden_params, load_golden
@@ -43,6 +43,12 @@ def test_g32_two_scenes_teams_among_circling_hazards(engine, size, r):
     spec, walls, hz, start, goal = circling32()
     dev, ref = both(engine, spec, walls, hz, start, goal, 4, size, r, 0, 10, 8)
     assert {R.PLANNED, R.UNREACHABLE, R.TRUNCATED} <= set(ref["status"].tolist()) and dev["workgroups"] == 32 // size
+
+
+def test_g32_three_column_starts_and_goals_as_teams_of_two(engine):
+    spec, walls, hz, start, goal = robots8_xyz()
+    _, ref = both(engine, spec, walls, hz, start, goal, 4, 2, 1, 0, 10, 8)
+    xyz_checked(ref, goal, 4)
 
 
 def test_g32_step0_on_a_hold_table(engine):

@@ -8,7 +8,7 @@ import pytest
 from mobrob_amd.envs import goal_rules as R
 from mobrob_amd.envs.goal_rules import grid_plan_team_rounds
 from mobrob_amd.planning import GridPlanner
-from tests.plan_scenes import EXTENT, INFLATE
+from tests.plan_scenes import EXTENT, INFLATE, robots8_xyz, xyz_checked
 from tests.plan_team_rounds_scenes import CORRIDOR_K, CORRIDOR_TABLE, CORRIDOR_TIME, ROUNDS_KEYS, corridor_case, hopeless_pair
 from tests.plan_team_scenes import TEAM_KEYS, circling32, same_team, sealed_case, teams
 from tests.util import _engine, _env
@@ -64,6 +64,13 @@ def test_g32_two_scenes_teams_among_circling_hazards(engine, size):
     dev, ref = both(engine, spec, walls, hz, start, goal, 4, size, 1, 3, 0, 10, 8)
     assert np.all(dev["team_parked"] <= dev["team_parked_first"]) and dev["workgroups"] == 32 // size
     print("size", size, "rounds", dev["team_rounds"].tolist(), "parked first", dev["team_parked_first"].tolist(), "parked", dev["team_parked"].tolist())
+
+
+def test_g32_three_column_starts_and_goals_as_teams_of_two(engine):
+    spec, walls, hz, start, goal = robots8_xyz()
+    dev, ref = both(engine, spec, walls, hz, start, goal, 4, 2, 1, 2, 0, 10, 8)
+    xyz_checked(ref, goal, 4)
+    assert dev["team_rounds"].max() > 1                                          # a parked mate: the zeroing before a replanned round runs
 
 
 def test_hopeless_pair_keeps_round_0(engine):

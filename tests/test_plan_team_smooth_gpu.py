@@ -11,7 +11,7 @@ from mobrob_amd.envs import goal_rules as R
 from mobrob_amd.envs.goal_rules import GridSpec, Teams, Walls, grid_plan, grid_plan_team
 from mobrob_amd.planning import GridPlanner
 from mobrob_amd.waypoints import follow_with_replanning
-from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots33, serpentine, three_hazards, two_scenes
+from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots8_xyz, robots33, serpentine, three_hazards, two_scenes, xyz_checked
 from tests.plan_team_scenes import centres, circling32, lattice_case, teams
 from tests.plan_team_smooth_cases import rule_scenes, smooth_both
 from tests.plan_time_scenes import same_time
@@ -39,6 +39,12 @@ def test_g32_two_scenes_teams_among_circling_hazards(engine, size, r, margin):
     assert {R.PLANNED, R.UNREACHABLE, R.TRUNCATED} <= set(ref["status"].tolist()) and dev["workgroups"] == 32 // size
     both = dev["team_clearance"][dev["team_clearance"] != R.PLAN_NO_PAIR]
     assert both.size and np.all(both > r)
+
+
+def test_g32_three_column_starts_and_goals_as_teams_of_two(engine):
+    spec, walls, hz, start, goal = robots8_xyz()
+    _, ref = smooth_both(engine, (spec, walls, hz, start, goal, 2, 10, 8), 4, 1, 0, 8)
+    xyz_checked(ref, goal, 4)
 
 
 def test_g32_without_a_cap_and_with_step0_on_a_hold_table(engine):

@@ -10,7 +10,7 @@ from mobrob_amd.envs import goal_rules as R
 from mobrob_amd.envs.goal_rules import GridSpec, MovingHazards, Walls, grid_plan, grid_plan_time
 from mobrob_amd.planning import GridPlanner
 from mobrob_amd.waypoints import follow_with_replanning
-from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots33, serpentine, three_hazards, two_scenes
+from tests.plan_scenes import EXTENT, INFLATE, SCENE0, robots8_xyz, robots33, serpentine, three_hazards, two_scenes, xyz_checked
 from tests.plan_time_scenes import FAR, circling33, gap_case, same_time
 from tests.util import _engine, _env, _snapshot, golden_params, load_golden
 
@@ -43,6 +43,12 @@ def test_g32_two_scenes_33_robots_circling_hazards_and_a_hold_table(engine):
     held = circling33(n_frames=7, frame_steps=4, loop=False)[2]
     dev, ref = both(engine, spec, walls, held, start, goal, 4, 9, 5, 8)                 # step0 > 0; the tail holds the last frame
     assert ref["layer_first"].tolist() == [2, 3, 4, 6, 6, 6, 6, 6, 6] and ref["layer_number"].tolist() == [2, 2, 2, 1, 1, 1, 1, 1, 1]
+
+
+def test_g32_three_column_starts_and_goals(engine):
+    spec, walls, hz, start, goal = robots8_xyz()
+    _, ref = both(engine, spec, walls, hz, start, goal, 4, 0, 10, 8)
+    xyz_checked(ref, goal, 4)
 
 
 def test_g128_two_layers_use_the_144_kb_path_and_one_layer_is_enough(engine):

@@ -11,7 +11,7 @@ from mobrob_amd.envs import goal_rules as R
 from mobrob_amd.envs.goal_rules import GridSpec, MovingHazards, grid_plan_time
 from mobrob_amd.planning import GridPlanner
 from mobrob_amd.waypoints import follow_with_replanning
-from tests.plan_scenes import EXTENT, INFLATE, serpentine
+from tests.plan_scenes import EXTENT, INFLATE, robots8_xyz, serpentine, xyz_checked
 from tests.plan_smooth_cases import same_plan
 from tests.plan_time_scenes import FAR, circling33, gap_case, goal_sitter, same_time
 from tests.plan_time_smooth_cases import EDGE_ACTIONS, EDGE_MOVES, SMOOTH_KEYS, cap_boundary, static_twin, window_edges_waiting
@@ -49,6 +49,12 @@ def test_g32_two_scenes_33_robots_loop_and_hold(engine, layer_steps, layers, mar
     assert layer_steps == 3 or np.any(ref["arrive"] > ref["moves"]), "at 10 steps a layer some walks wait"
     held = circling33(n_frames=7, frame_steps=4, loop=False)[2]
     both(engine, spec, walls, held, start, goal, 64, 9, layer_steps, layers, margin)      # step0 > 0; the tail holds the last frame
+
+
+def test_g32_three_column_starts_and_goals(engine):
+    spec, walls, hz, start, goal = robots8_xyz()
+    _, ref = both(engine, spec, walls, hz, start, goal, 4, 0, 10, 8, 0)
+    xyz_checked(ref, goal, 4)
 
 
 @pytest.mark.parametrize("margin", [0, 1])
