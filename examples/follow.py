@@ -54,6 +54,12 @@ a team whose members stayed parked again, up to R times, with those members firs
 and after.  `--plan-smooth` smooths every plan by line
 of sight (fewer waypoints: only the cells a straight leg cannot skip), `--plan-los-margin` (0 or 1, default 1) is the clearance of
 that test in cells; a second line then reports the waypoints and the moves per planned robot.
+
+`--goals FILE.npy` plans to a SET of places instead of one goal: `[size][P]` (the places of one team, the same for every team;
+size = --team-size) or `[n][P]` (one per robot).  It excludes --goal and --waypoints.  As given, robot i is planned to goals[i];
+`--assign sum` or `--assign makespan` (it needs --team-size) first assigns the places inside every team -- the pairing of least
+total path cost, or the one whose longest path is shortest -- and a line reports the teams whose pairing changed and the total
+before and after (mobrob_amd.planning.GridPlanner(assign=)).  A run is never reassigned: replanning keeps the assigned goals.
 """
 import argparse
 import os
@@ -83,9 +89,13 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
-           plan_retries=0):
+           plan_retries=0, goals=None, assign=None):
     calls = check_chain(max_steps, horizon, leg_steps)
-    if (goal is None) == (waypoints is None):
+    if goals is not None and (goal is not None or waypoints is not None):
+        raise ValueError("--goals excludes --goal and --waypoints")
+    if assign is not None and (goals is None or team_size is None):
+        raise ValueError("--assign needs --goals and --team-size (places are assigned inside a team)")
+    if goals is None and (goal is None) == (waypoints is None):
         raise ValueError("give --waypoints or --goal, not both")
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
@@ -113,12 +123,20 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             raise ValueError(f"--walls must hold [M][4] (cx, cy, hx, hy), got shape {boxes.shape}")
         wl = Walls(np.concatenate([boxes, Walls.enclosure()]) if arena else boxes, radius=float(robot_radius), indicator=False)
     n_waypoints = replan = None
+    if goals is not None:
+        goals = np.asarray(goals, np.float64)
+        rows = (int(robots),) if team_size is None else (int(team_size), int(robots))
+        if goals.ndim != 2 or goals.shape[1] != p or p < 2 or goals.shape[0] not in rows or int(robots) % goals.shape[0]:
+            raise ValueError(f"--goals must hold [team size][{p}] or [{int(robots)}][{p}] positions of robots that move in x and y, got shape {goals.shape}")
+        goals = np.tile(goals, (int(robots) // goals.shape[0], 1))
+        goal = goals[0]                                    # (from here on: "the waypoints are planned")
     if goal is not None:
         from mobrob_amd.planning import GridPlanner
         goal = np.asarray(goal, np.float64).reshape(-1)
         if goal.shape != (p,) or p < 2:
             raise ValueError(f"--goal must hold {p} coordinates of a robot that moves in x and y, got {goal.size}")
-        goals = np.tile(goal, (int(robots), 1))
+        if goals is None:
+            goals = np.tile(goal, (int(robots), 1))
         timed = isinstance(hz, MovingHazards) or teams is not None     # with teams the mates are planned around each other, over time
         if timed and (release is not None or stagger):
             raise ValueError("--release / --stagger exclude --goal with --hazard-frames or --team-size: the time plan makes the schedule")
@@ -127,8 +145,13 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
                               **(dict(max_leg=None if int(plan_max_leg) == 0 else int(plan_max_leg)) if plan_max_leg is not None else {}),
                               **(dict(layer_steps=int(plan_layer_steps), layers=int(plan_layers)) if timed else {}),
                               **(dict(teams=teams, reserve=None if plan_reserve is None else int(plan_reserve)) if teams is not None else {}),
-                              **(dict(retries=int(plan_retries)) if int(plan_retries) != 0 else {}))
+                              **(dict(retries=int(plan_retries)) if int(plan_retries) != 0 else {}),
+                              **(dict(assign=assign) if assign is not None else {}))
         plan = planner.plan(start, goals, grow=True)
+        if assign is not None:
+            goals = plan["goal"]                           # the callback plans to the goals it is given and never reassigns
+            print(f"assigned ({assign}): {int(plan['assign_changed'].sum())} of {len(plan['assign_changed'])} teams changed, total path cost "
+                  f"{int(plan['assign_identity_total'].sum())} -> {int(plan['assign_total'].sum())}")
         waypoints, n_waypoints, plan_schedule = plan["waypoints"], plan["n_waypoints"], plan.get("schedule")
         replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 else None
         print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
@@ -216,6 +239,9 @@ def build_parser():
     ap.add_argument("--policy-name", type=str, default="ppo")
     ap.add_argument("--waypoints", type=str, default=None, help="[K][P] or [n][K][P] positions (.npy)")
     ap.add_argument("--goal", type=str, default=None, help="x,y (x,y,z): plan the waypoints to this goal instead of --waypoints")
+    ap.add_argument("--goals", type=str, default=None, help="[team size][P] or [n][P] places (.npy): plan robot i to goals[i] instead of --goal")
+    ap.add_argument("--assign", type=str, default=None, choices=("sum", "makespan"),
+                    help="with --goals and --team-size: assign the places inside every team at least total (or least largest) path cost")
     ap.add_argument("--plan-cells", type=int, default=64, help="grid cells a side of the planner (32, 64, 128)")
     ap.add_argument("--plan-smooth", action="store_true", default=False, help="smooth the planned paths by line of sight")
     ap.add_argument("--plan-time-smooth", action="store_true", default=False,
@@ -253,7 +279,11 @@ def build_parser():
 if __name__ == "__main__":
     ap = build_parser()
     args = ap.parse_args()
-    if (args.waypoints is None) == (args.goal is None):
+    if args.goals is not None and (args.goal is not None or args.waypoints is not None):
+        ap.error("--goals excludes --goal and --waypoints")
+    if args.assign is not None and (args.goals is None or args.team_size is None):
+        ap.error("--assign needs --goals and --team-size")
+    if args.goals is None and (args.waypoints is None) == (args.goal is None):
         ap.error("give --waypoints or --goal, not both")
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
@@ -268,4 +298,4 @@ if __name__ == "__main__":
            goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells,
            plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin, plan_layer_steps=args.plan_layer_steps,
            plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg,
-           plan_retries=args.plan_retries)
+           plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign)

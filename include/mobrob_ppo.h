@@ -1064,6 +1064,42 @@ int mobrob_ppo_plan_grid_team_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_s
                                      int32_t* keep_out /* [n][keep_cap] or NULL */, int32_t keep_cap, uint8_t* occ_time_out /* or NULL */,
                                      int32_t* fields_team_out /* [n][T + 1][G][G] or NULL */, int32_t* workgroups_out /* or NULL */);
 
+/* ---- goal assignment inside a team: who takes which goal, a minimum-cost matching ---------------------------------------------------
+ * In front of the team planners, a call of its own: it changes their INPUT (goal[n]) and nothing of theirs.  The rule is stated once in
+ * mobrob_amd/envs/goal_rules.py (grid_assign, plan_assign_match, plan_assign_team) and reproduced bit for bit, the potentials included.
+ *   map       a static scene (hazards, or neither): mobrob_ppo_plan_grid's occupancy; hazard frames (with `time`): the tail layer T of
+ *             mobrob_ppo_plan_grid_time's layers.  Reservations play no part: the matching is a function of (scene, starts, goals).
+ *   matrix    per team C[i][j] = the cost-to-go of member i's start cell to member j's goal cell on that map (mobrob_ppo_plan_grid's
+ *             field), MOBROB_PLAN_ASSIGN_NONE where there is no path: above any total of real costs, so a minimum-sum matching first
+ *             minimises the pairs without a path.
+ *   matching  objective 0 (sum): the minimum-total perfect matching by the shortest-augmenting-path Hungarian method, rows in index
+ *             order, the unused column of least slack with the lowest index on a tie.  Objective 1 (makespan): L, the least value with a
+ *             perfect matching among the entries <= L, then that method on C with the entries above L as MOBROB_PLAN_ASSIGN_FORBID: the
+ *             largest member cost first, then the total.  Identity first: where the identity's total (makespan: its largest entry and
+ *             total) equals the matching's, the identity is the result.
+ *   outputs   assign_out [n]: the robot, a mate or itself, whose goal robot i is given; goal_out [n][pos_dim] = goal[assign];
+ *             assign_cost_out [n] (-1: no path); total_out [2][n_teams] int64: the result's total, the identity's (NONE counted as NONE);
+ *             team_out [4][n_teams]: the result's largest entry, the identity's, changed (0 / 1), status (0; 3: a field hit its sweep
+ *             bound or a loop its bound -- the team keeps the identity, potentials 0); u_out, v_out [n] int64: the row and column
+ *             potentials of the last matching run, u[i] + v[j] <= C'[i][j] with equality on the matched pairs; matrix_out
+ *             [n_teams][team_size][team_size] or NULL: C with -1 for NONE; sweeps_out [n] or NULL: the relaxation sweeps of each field.
+ *   kernels   k_plan_occupancy or k_plan_occupancy_time as they are; k_plan_assign_cost: a workgroup of 1024 threads per robot, its
+ *             goal's field in LDS (5 bytes a cell, as k_plan_field's), of which only the team_size words at the mates' start cells are
+ *             written out; k_plan_assign: a wave per team, lanes as columns.  It works in the team plans' buffer; nothing stays resident.
+ * MOBROB_ERR_INVALID before any launch or copy for: a NULL argument, hazards and frames both, `time` without frames or frames without
+ * it, an objective other than 0 or 1, reuse_id != 0, n_fields != n_robots, a team_size other than 1, 2, 4, 8, 16 or one that does not
+ * divide n_robots, mates in different scenes, non-finite starts or goals, everything mobrob_ppo_plan_grid refuses of the spec and the
+ * scenes and mobrob_ppo_plan_grid_time of the frames and the time, a field too large for the device's LDS per workgroup. */
+#define MOBROB_PLAN_ASSIGN_NONE (1 << 21)
+#define MOBROB_PLAN_ASSIGN_FORBID (1 << 26)
+int mobrob_ppo_plan_assign(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                           const mobrob_hazards_t* hazards /* or NULL */, const mobrob_hazard_frames_t* frames /* or NULL */,
+                           const mobrob_plan_time_t* time /* with frames, else NULL */, int32_t team_size, int32_t objective /* 0 sum, 1 makespan */,
+                           const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */, int32_t* assign_out /* [n] */,
+                           float* goal_out /* [n][pos_dim] */, int32_t* assign_cost_out /* [n] */, int64_t* total_out /* [2][n_teams] */,
+                           int32_t* team_out /* [4][n_teams] */, int64_t* u_out /* [n] */, int64_t* v_out /* [n] */,
+                           int32_t* matrix_out /* [n_teams][team_size][team_size] or NULL */, int32_t* sweeps_out /* [n] or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

@@ -296,6 +296,7 @@ struct mobrob_ppo_engine {
   bool plan_team_lds_set = false;     // k_plan_team's dynamic-LDS attribute is raised once
   bool plan_team_smooth_lds_set = false;   // and k_plan_team_smooth's
   bool plan_team_rounds_lds_set = false;   // and k_plan_team_rounds's
+  bool plan_assign_lds_set = false;        // and k_plan_assign_cost's (mobrob_ppo_plan_assign works in plan_team_buf)
 };
 
 namespace {
@@ -4750,6 +4751,139 @@ int mobrob_ppo_plan_grid_team_rounds(mobrob_ppo_engine_t* e, const mobrob_plan_s
   return plan_team_run(e, spec, walls, hzf, tm, team_size, reserve, start, goal, waypoints_out, n_waypoints_out, count_out, status_out, cost_out,
                        waits_out, leave_out, arrive_out, sweeps_out, walk_out, walk_cap, occ_time_out, fields_team_out, workgroups_out, nullptr,
                        &rr);
+}
+
+// ---- goal assignment inside a team (mobrob_ppo_plan_assign): minimum-cost matching on the device ------------------------------
+// The base map as the planners launch it (k_plan_occupancy for a static scene, k_plan_occupancy_time for frames, of which layer T is
+// read), k_plan_assign_cost, k_plan_assign.  It works in the team plans' buffer and keeps nothing resident.
+int mobrob_ppo_plan_assign(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                           const mobrob_hazard_frames_t* hzf, const mobrob_plan_time_t* tm, int32_t team_size, int32_t objective,
+                           const float* start, const float* goal, int32_t* assign_out, float* goal_out, int32_t* assign_cost_out,
+                           int64_t* total_out, int32_t* team_out, int64_t* u_out, int64_t* v_out, int32_t* matrix_out, int32_t* sweeps_out) {
+  if (!e || !spec || !start || !goal || !assign_out || !goal_out || !assign_cost_out || !total_out || !team_out || !u_out || !v_out)
+    return fail(MOBROB_ERR_INVALID, "plan_assign: null argument");
+  if (hz && hzf) return fail(MOBROB_ERR_INVALID, "plan_assign: static hazards or hazard frames, not both");
+  if ((hzf != nullptr) != (tm != nullptr)) return fail(MOBROB_ERR_INVALID, "plan_assign: time (step0, layer_steps, layers) is needed with hazard frames, and only then");
+  if (objective != 0 && objective != 1) return fail(MOBROB_ERR_INVALID, "plan_assign: objective must be 0 (sum) or 1 (makespan), got %d", objective);
+  if (spec->reuse_id != 0) return fail(MOBROB_ERR_INVALID, "plan_assign: reuse_id must be 0 (an assignment keeps nothing resident)");
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, S = spec->n_scenes;
+  const int cells = G * G, T = tm ? tm->layers : 0;
+  mobrob_hazards_t view;
+  HazardIO frames{};
+  if (hzf) frames = hazard_frames_io(hzf, view, nullptr, nullptr);
+  std::vector<int32_t> wall_counts, hz_counts;
+  if (const int rc = plan_check_scenes("plan_assign", spec, walls, hzf ? &view : hz, hzf ? &frames : nullptr, wall_counts, hz_counts)) return rc;
+  if (S > 65535) return fail(MOBROB_ERR_INVALID, "plan_assign: n_scenes = %d above 65535", S);
+  if (spec->n_fields != N) return fail(MOBROB_ERR_INVALID, "plan_assign: n_fields = %d must be n_robots = %d (every robot's goal has its own field)", spec->n_fields, N);
+  if (team_size != 1 && team_size != 2 && team_size != 4 && team_size != 8 && team_size != 16)
+    return fail(MOBROB_ERR_INVALID, "plan_assign: team_size must be 1, 2, 4, 8 or 16, got %d", team_size);
+  if (N % team_size != 0) return fail(MOBROB_ERR_INVALID, "plan_assign: %d robots do not split into teams of %d", N, team_size);
+  if ((int64_t)N * team_size > INT_MAX) return fail(MOBROB_ERR_INVALID, "plan_assign: n_robots * team_size must fit an int32");
+  const int32_t* scene = hzf ? hzf->scene : walls ? walls->scene : hz ? hz->scene : nullptr;
+  for (int i = 0; i < N; ++i) {
+    for (int j = 0; j < P; ++j)
+      if (!std::isfinite(start[(size_t)i * P + j]) || !std::isfinite(goal[(size_t)i * P + j]))
+        return fail(MOBROB_ERR_INVALID, "plan_assign: start or goal of robot %d is not finite", i);
+    if (scene && scene[i] != scene[i - i % team_size])
+      return fail(MOBROB_ERR_INVALID, "plan_assign: all members of a team must be in one scene (robot %d is in scene %d, its team's first member in %d)", i,
+                  scene[i], scene[i - i % team_size]);
+  }
+  std::vector<int32_t> lfirst, lnumber;
+  if (hzf) {
+    if (T < 1 || T > kPlanLayersMax) return fail(MOBROB_ERR_INVALID, "plan_assign: layers must lie in 1 .. %d, got %d", kPlanLayersMax, T);
+    if (tm->layer_steps < 1) return fail(MOBROB_ERR_INVALID, "plan_assign: layer_steps must be >= 1, got %d", tm->layer_steps);
+    if (tm->step0 < 0) return fail(MOBROB_ERR_INVALID, "plan_assign: step0 must be >= 0, got %d", tm->step0);
+    if ((int64_t)tm->step0 + (int64_t)(T + 1) * tm->layer_steps > INT_MAX)
+      return fail(MOBROB_ERR_INVALID, "plan_assign: step0 + (layers + 1) * layer_steps must fit an int32");
+    plan_layer_frames(hzf, tm, lfirst, lnumber);
+  }
+  const size_t field_lds = plan_field_lds_bytes(G);
+  {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid checks k_plan_field's
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+    if (field_lds > (size_t)limit)
+      return fail(MOBROB_ERR_INVALID, "plan_assign: k_plan_assign_cost needs %zu bytes of LDS at %d cells, the device allows %d per workgroup", field_lds, G, limit);
+  }
+  const int n_teams = N / team_size;
+  const int Mw = walls ? walls->max_walls : 0, Mh = hzf ? hzf->max_hazards : hz ? hz->max_hazards : 0, NF = hzf ? hzf->n_frames : 1;
+  const size_t hz_floats = (size_t)S * NF * Mh * 3;
+  EvalCarve call;
+  const size_t o_occ = call.add((size_t)S * (T + 1) * cells), o_start = call.add((size_t)N * P * 4), o_goal = call.add((size_t)N * P * 4),
+               o_scene = call.add((size_t)N * 4), o_cost = call.add((size_t)N * team_size * 4), o_sweeps = call.add((size_t)N * 4),
+               o_assign = call.add((size_t)N * 4), o_gout = call.add((size_t)N * P * 4), o_acost = call.add((size_t)N * 4),
+               o_total = call.add((size_t)2 * n_teams * 8), o_team = call.add((size_t)4 * n_teams * 4), o_u = call.add((size_t)N * 8),
+               o_v = call.add((size_t)N * 8), o_lfirst = call.add((size_t)(T + 1) * 4), o_lnumber = call.add((size_t)(T + 1) * 4),
+               o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
+               o_hz = call.add(std::max<size_t>(hz_floats, 1) * 4), o_nhz = call.add((size_t)S * 4);
+  if (const int rc = grow_plan_buf(e, e->plan_team_buf, e->plan_team_bytes, call.total)) return rc;
+  const auto mine = [&](size_t off) { return e->plan_team_buf + off; };
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(mine(o_occ));
+  const PlanGrid grid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  float* box_dev = nullptr;
+  int* nwall_dev = nullptr;
+  if (walls) {
+    box_dev = reinterpret_cast<float*>(mine(o_box));
+    nwall_dev = reinterpret_cast<int*>(mine(o_nwall));
+    if ((size_t)S * Mw) HIPC(hipMemcpyAsync(box_dev, walls->boxes, (size_t)S * Mw * 16, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(nwall_dev, wall_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  float* hz_dev = reinterpret_cast<float*>(mine(o_hz));
+  int* nhz_dev = reinterpret_cast<int*>(mine(o_nhz));
+  if (hz || hzf) {
+    if (hz_floats) HIPC(hipMemcpyAsync(hz_dev, hzf ? hzf->hazards : hz->hazards, hz_floats * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(nhz_dev, hz_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  if (hzf) {
+    int* lfirst_dev = reinterpret_cast<int*>(mine(o_lfirst));
+    int* lnumber_dev = reinterpret_cast<int*>(mine(o_lnumber));
+    HIPC(hipMemcpyAsync(lfirst_dev, lfirst.data(), (size_t)(T + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(lnumber_dev, lnumber.data(), (size_t)(T + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    PlanOccTimeArgs oa{};
+    oa.g = grid; oa.boxes = box_dev; oa.nwall = nwall_dev; oa.Mw = Mw; oa.hz = hz_dev; oa.nhz = nhz_dev; oa.Mh = Mh; oa.F = NF; oa.T = T;
+    oa.layer_first = lfirst_dev; oa.layer_number = lnumber_dev; oa.occ = occ_dev;
+    hipLaunchKernelGGL(k_plan_occupancy_time, dim3(cells / 256, T + 1, S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
+  } else {
+    PlanOccArgs oa{};
+    oa.g = grid; oa.boxes = box_dev; oa.nwall = nwall_dev; oa.Mw = Mw; oa.Mh = Mh; oa.occ = occ_dev;
+    if (hz) { oa.hz = hz_dev; oa.nhz = nhz_dev; }
+    hipLaunchKernelGGL(k_plan_occupancy, dim3(cdiv(cells, 256), S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
+  }
+  HIPC(hipGetLastError());
+  if (!e->plan_assign_lds_set) {   // 80 KB at 128 cells: above the 64 KB a kernel gets without asking
+    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_assign_cost), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)plan_field_lds_bytes(128)));
+    e->plan_assign_lds_set = true;
+  }
+  float* start_dev = reinterpret_cast<float*>(mine(o_start));
+  float* goal_dev = reinterpret_cast<float*>(mine(o_goal));
+  int* scene_dev = reinterpret_cast<int*>(mine(o_scene));
+  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(goal_dev, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  if (scene) HIPC(hipMemcpyAsync(scene_dev, scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  PlanAssignCostArgs ca{};
+  ca.g = grid; ca.N = N; ca.P = P; ca.size = team_size; ca.start = start_dev; ca.goal = goal_dev; ca.scene = scene ? scene_dev : nullptr;
+  ca.occ = occ_dev; ca.scene_stride = (size_t)(T + 1) * cells; ca.map_off = (size_t)T * cells;
+  ca.cost = reinterpret_cast<int*>(mine(o_cost)); ca.sweeps = reinterpret_cast<int*>(mine(o_sweeps));
+  hipLaunchKernelGGL(k_plan_assign_cost, dim3(N), dim3(kPlanFieldThreads), field_lds, e->stream, ca);
+  HIPC(hipGetLastError());
+  PlanAssignArgs aa{};
+  aa.N = N; aa.P = P; aa.size = team_size; aa.objective = objective; aa.goal = goal_dev; aa.sweeps = ca.sweeps; aa.cost = ca.cost;
+  aa.assign = reinterpret_cast<int*>(mine(o_assign)); aa.goal_out = reinterpret_cast<float*>(mine(o_gout));
+  aa.assign_cost = reinterpret_cast<int*>(mine(o_acost)); aa.total = reinterpret_cast<long long*>(mine(o_total));
+  aa.team = reinterpret_cast<int*>(mine(o_team)); aa.u = reinterpret_cast<long long*>(mine(o_u)); aa.v = reinterpret_cast<long long*>(mine(o_v));
+  hipLaunchKernelGGL(k_plan_assign, dim3(n_teams), dim3(64), 0, e->stream, aa);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(assign_out, aa.assign, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(goal_out, aa.goal_out, (size_t)N * P * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(assign_cost_out, aa.assign_cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(total_out, aa.total, (size_t)2 * n_teams * 8, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(team_out, aa.team, (size_t)4 * n_teams * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(u_out, aa.u, (size_t)N * 8, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(v_out, aa.v, (size_t)N * 8, hipMemcpyDeviceToHost, e->stream));
+  if (matrix_out) HIPC(hipMemcpyAsync(matrix_out, aa.cost, (size_t)N * team_size * 4, hipMemcpyDeviceToHost, e->stream));
+  if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, ca.sweeps, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

@@ -1277,4 +1277,221 @@ __global__ __launch_bounds__(kPlanFieldThreads) void k_plan_team_smooth(const Pl
   }
 }
 
+// ---- goal assignment inside a team (mobrob_ppo_plan_assign; the rule: goal_rules.grid_assign / plan_assign_match / plan_assign_team) --
+// Who takes which goal: per team the minimum-cost perfect matching on C[i][j] = the static cost-to-go of member i's start cell to
+// member j's goal cell, a pair without a path as kPlanAssignNone.  Two kernels behind the base map: k_plan_assign_cost (a workgroup per
+// robot: its goal's field in LDS, of which only the mates' start cells leave the workgroup) and k_plan_assign (a wave per team).
+constexpr int kPlanAssignNone = 1 << 21;     // above 16 * 7 * 128 * 128, the largest total of real costs
+constexpr int kPlanAssignForbid = 1 << 26;   // in a makespan matching: a pair above the bottleneck
+constexpr long long kPlanAssignBig = 1ll << 62;   // "no slack yet" in a scan
+constexpr int kPlanAssignBisect = 32;        // steps of the bisection for the bottleneck at most: the values lie below 2^27
+
+struct PlanAssignCostArgs {
+  PlanGrid g;
+  int N, P, size;
+  const float* start;         // [N][P]
+  const float* goal;          // [N][P]
+  const int* scene;           // [N] or null: every robot in scene 0
+  const unsigned char* occ;   // the cost map of scene s: occ + s * scene_stride + map_off, [G][G]
+  size_t scene_stride, map_off;
+  int* cost;                  // [N / size][size][size] out
+  int* sweeps;                // [N] out: plan_tail's
+};
+
+// Grid N, 1024 threads, LDS plan_field_lds_bytes(G): plan_tail on the map of robot n's scene for robot n's goal cell, k_plan_field's
+// field, which stays in LDS.  Out go the `size` words C[team][i][n % size], the field at the start cells of n's team (a blocked
+// start cell holds kPlanInf in the field: no path), and the sweeps.  A tail that hit its bound leaves kPlanAssignNone in its column;
+// k_plan_assign reads the sweeps and reports the team.
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_assign_cost(PlanAssignCostArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int plan_assign_lds[];
+  const int n = blockIdx.x, G = a.g.G, cells = G * G, tid = threadIdx.x, m = n % a.size;
+  int* d = plan_assign_lds;
+  unsigned char* moves = reinterpret_cast<unsigned char*>(plan_assign_lds + cells);
+  const float* gl = a.goal + (size_t)n * a.P;
+  const int goal = plan_cell(a.g, gl[1]) * G + plan_cell(a.g, gl[0]);
+  const unsigned char* occ = a.occ + (size_t)(a.scene ? a.scene[n] : 0) * a.scene_stride + a.map_off;
+  const int sweeps = plan_tail(d, moves, plan_unblocked(occ), goal, G);
+  if (tid < a.size) {
+    const int i = n - m + tid;   // a mate, or n itself
+    const float* st = a.start + (size_t)i * a.P;
+    const int v = d[plan_cell(a.g, st[1]) * G + plan_cell(a.g, st[0])];
+    a.cost[(size_t)i * a.size + m] = (sweeps < 0 || v >= kPlanInf) ? kPlanAssignNone : v;
+  }
+  if (tid == 0) a.sweeps[n] = sweeps;
+}
+
+struct PlanAssignArgs {
+  int N, P, size, objective;   // objective 0: sum, 1: makespan
+  const float* goal;           // [N][P]
+  const int* sweeps;           // [N] k_plan_assign_cost's
+  int* cost;                   // [N / size][size][size] in; out: kPlanAssignNone as -1
+  int* assign;                 // [N] out
+  float* goal_out;             // [N][P] out
+  int* assign_cost;            // [N] out
+  long long* total;            // [n_teams] out, then the identity's [n_teams]
+  int* team;                   // max | identity max | changed | status, [n_teams] each, out
+  long long* u;                // [N] out
+  long long* v;                // [N] out
+};
+
+// the least (value, lane) over the 16 lanes of a team, the lower lane on equal values, in every one of the 16 lanes
+__device__ __forceinline__ void plan_assign_argmin(long long& best, int& at) {
+#pragma unroll
+  for (int s = 1; s < kPlanTeamMax; s <<= 1) {
+    const long long ob = __shfl_xor(best, s);
+    const int oa = __shfl_xor(at, s);
+    if (ob < best || (ob == best && oa < at)) { best = ob; at = oa; }
+  }
+}
+__device__ __forceinline__ long long plan_assign_sum(long long x) {
+#pragma unroll
+  for (int s = 1; s < kPlanTeamMax; s <<= 1) x += __shfl_xor(x, s);
+  return x;
+}
+__device__ __forceinline__ int plan_assign_max(int x) {
+#pragma unroll
+  for (int s = 1; s < kPlanTeamMax; s <<= 1) x = max(x, __shfl_xor(x, s));
+  return x;
+}
+
+// goal_rules.plan_assign_match by one wave, lane l < size being column l AND row l: u the potential of row l, v of column l, p the row
+// matched to column l (-1: none); per inserted row minv, way and used of column l and rowin of row l.  cost(i, l): the entry of row i
+// in this lane's column.  The row that is scanned, the column that is taken and delta are the same in every lane (broadcast from lane
+// 0), so the loops are wave-uniform.  Bounds, constants of the rule: size rows, size + 1 scans a row (row i reaches at most i + 1
+// columns), size + 1 steps back along the way -> false beyond (cannot happen).
+template <class Cost>
+__device__ __forceinline__ bool plan_assign_match(Cost cost, int size, int lane, long long& u, long long& v, int& p) {
+  u = 0; v = 0; p = -1;
+  for (int i = 0; i < size; ++i) {
+    long long minv = kPlanAssignBig;
+    int way = -1, j0 = -1, i0 = i;
+    bool used = false, rowin = false;
+    for (int scan = 0;; ++scan) {
+      if (scan > size) return false;
+      if (lane == i0) rowin = true;
+      const long long ui0 = __shfl(u, i0);
+      const bool open = lane < size && !used;
+      if (open) {
+        const long long cur = cost(i0, lane) - ui0 - v;
+        if (cur < minv) { minv = cur; way = j0; }
+      }
+      long long delta = open ? minv : kPlanAssignBig;
+      int j1 = lane;
+      plan_assign_argmin(delta, j1);
+      delta = __shfl(delta, 0);
+      j1 = __shfl(j1, 0);
+      if (rowin) u += delta;
+      if (lane < size) {
+        if (used) v -= delta; else minv -= delta;
+      }
+      j0 = j1;
+      if (lane == j0) used = true;
+      i0 = __shfl(p, j0);
+      if (i0 < 0) break;
+    }
+    for (int step = 0; j0 >= 0; ++step) {   // augment along the way back to the root
+      if (step > size) return false;
+      const int j1 = __shfl(way, j0);
+      const int row = j1 >= 0 ? __shfl(p, j1) : i;
+      if (lane == j0) p = row;
+      j0 = j1;
+    }
+  }
+  return true;
+}
+
+// Grid n_teams, 64 threads: the workgroup IS the wave (as k_plan_smooth's), so nothing here waits for another wave; lane l < size is
+// column l and row l of the team's matrix, the other lanes idle along.  The matrix sits in LDS, [16][16] ints, written and read by
+// this one wave around wave-level fences.  goal_rules.plan_assign_team: the matching of the sum, or for the makespan first the
+// bottleneck L -- a bisection on the VALUE between the largest row minimum (no matching does better) and the identity's largest entry
+// (the identity is a matching), a value being feasible where the 0 / 1 matrix C > value has a matching of total 0; the least feasible
+// value is an entry, so it is the rule's L -- and then the matching on C with the entries above L as kPlanAssignForbid.  Identity
+// first, the totals, the outputs.  A field that did not converge, or a loop beyond its bound: status 3, the identity, potentials 0.
+__global__ __launch_bounds__(64) void k_plan_assign(PlanAssignArgs a) {
+  __shared__ int cm[kPlanTeamMax * kPlanTeamMax];
+  __shared__ int colof[kPlanTeamMax];
+  const int team = blockIdx.x, lane = threadIdx.x, size = a.size, base = team * size, n_teams = a.N / size;
+  const bool mine = lane < size;
+  int* cg = a.cost + (size_t)base * size;
+  bool ok = true;
+  if (mine) {
+    for (int i = 0; i < size; ++i) cm[i * kPlanTeamMax + lane] = cg[i * size + lane];
+    ok = a.sweeps[base + lane] >= 0;
+  }
+  ok = __all(ok);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int* const c16 = cm;   // the matrix, row i at c16 + 16 i
+  const auto raw = [c16](int i, int j) { return (long long)c16[i * kPlanTeamMax + j]; };
+  const int diag = mine ? cm[lane * kPlanTeamMax + lane] : 0;
+  const long long id_total = plan_assign_sum(diag);
+  const int id_max = plan_assign_max(diag);
+  long long u = 0, v = 0;
+  int p = -1;
+  if (ok) {
+    if (a.objective == 0) {
+      ok = plan_assign_match(raw, size, lane, u, v, p);
+    } else {
+      int rowmin = 0;
+      if (mine) {
+        rowmin = cm[lane * kPlanTeamMax];
+        for (int j = 1; j < size; ++j) rowmin = min(rowmin, cm[lane * kPlanTeamMax + j]);
+      }
+      int lo = plan_assign_max(rowmin), hi = id_max;
+      lo = __shfl(lo, 0); hi = __shfl(hi, 0);
+      for (int step = 0; ok && lo < hi; ++step) {
+        if (step >= kPlanAssignBisect) { ok = false; break; }
+        const int mid = lo + (hi - lo) / 2;
+        const auto above = [c16, mid](int i, int j) { return (long long)(c16[i * kPlanTeamMax + j] > mid ? 1 : 0); };
+        ok = plan_assign_match(above, size, lane, u, v, p);
+        long long over = mine && p >= 0 ? above(p, lane) : 0;
+        over = __shfl(plan_assign_sum(over), 0);
+        if (over == 0) hi = mid; else lo = mid + 1;
+      }
+      if (ok) {
+        const int L = lo;
+        const auto capped = [c16, L](int i, int j) {
+          const int c = c16[i * kPlanTeamMax + j];
+          return (long long)(c > L ? kPlanAssignForbid : c);
+        };
+        ok = plan_assign_match(capped, size, lane, u, v, p);
+      }
+    }
+  }
+  ok = __all(ok);
+  if (!ok) { u = 0; v = 0; p = lane; }
+  // the row of column `lane` -> the column of row `lane`
+  if (mine) colof[p] = lane;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  int col = mine ? colof[lane] : 0;
+  int picked = mine ? cm[lane * kPlanTeamMax + col] : 0;
+  long long total = plan_assign_sum(picked);
+  int most = plan_assign_max(picked);
+  if (total == id_total && (a.objective == 0 || most == id_max)) {   // identity first
+    col = lane; picked = diag; most = id_max;
+  }
+  const bool changed = __any(mine && col != lane);
+  if (mine) {
+    const int n = base + lane;
+    a.assign[n] = base + col;
+    for (int j = 0; j < a.P; ++j) a.goal_out[(size_t)n * a.P + j] = a.goal[(size_t)(base + col) * a.P + j];
+    a.assign_cost[n] = picked >= kPlanAssignNone ? -1 : picked;
+    a.u[n] = u;
+    a.v[n] = v;
+    for (int i = 0; i < size; ++i)
+      if (cm[i * kPlanTeamMax + lane] >= kPlanAssignNone) cg[i * size + lane] = -1;
+  }
+  if (lane == 0) {
+    a.total[team] = total;
+    a.total[n_teams + team] = id_total;
+    a.team[team] = most;
+    a.team[n_teams + team] = id_max;
+    a.team[2 * n_teams + team] = changed ? 1 : 0;
+    a.team[3 * n_teams + team] = ok ? kPlanned : kPlanUnconverged;
+  }
+}
+
 }  // namespace mobrob

@@ -999,6 +999,60 @@ class PPOEngine:
             out["fields"] = fields
         return out
 
+    def plan_assign(self, spec, walls=None, hazards=None, *, teams, start, goal, objective="sum", step0=0, layer_steps=None, layers=None,
+                    want_matrix=False):
+        """Who takes which goal inside every team: a minimum-cost perfect matching per team on the device (mobrob_ppo_plan_assign:
+        the base map, k_plan_assign_cost, k_plan_assign; the rule: goal_rules.grid_assign, reproduced bit for bit, the potentials
+        included).  The costs are each robot's own static cost-to-go on the scene's map (with a goal_rules.MovingHazards the
+        conservative tail of its layers: layer_steps and layers are required then, and only then); objective "sum" or "makespan".
+        Returns grid_assign's dict: assign [n] (whose input goal robot i is given), goal [n][P] = goal[assign], assign_cost [n],
+        assign_total, assign_max, assign_identity_total, assign_identity_max, assign_changed, assign_status [n_teams] (UNCONVERGED:
+        a field hit its sweep bound; that team keeps the identity), assign_potentials (u, v), sweeps [n], and with want_matrix
+        assign_matrix int32 [n_teams][size][size].  Nothing stays resident and nothing of a plan or of training is touched."""
+        from ._lib import PlanSpec, PlanTime, WallsC
+        from .envs import goal_rules as R
+        start, goal, size, obj, step0, layer_steps, T = R.plan_assign_check(spec, walls, hazards, start, goal, teams, objective, step0,
+                                                                           layer_steps, layers)
+        moving = isinstance(hazards, R.MovingHazards)
+        S, _ = R.plan_scene_time(walls, hazards) if moving else R.plan_scene(walls, hazards)
+        start, goal = np.ascontiguousarray(start, F32), np.ascontiguousarray(goal, F32)
+        n, P = goal.shape
+        g = n // size
+        i32 = C.POINTER(C.c_int32)
+        i64 = C.POINTER(C.c_int64)
+        sp = PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_scenes, sp.n_fields = n, P, spec.cells, 1, S, n
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(spec.extent), float(spec.h), float(spec.inv_h), float(spec.inflate_for(walls))
+        sp.reuse_id = 0
+        tm = None
+        if moving:
+            tm = PlanTime()
+            tm.step0, tm.layer_steps, tm.layers = step0, layer_steps, T
+        wl = None
+        if walls is not None:
+            wl = WallsC()
+            wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+            wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
+            wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
+            wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
+        h, _keep = self._hazards_struct(hazards, n) if hazards is not None else (None, None)
+        assign, cost, sweeps = (np.zeros(n, np.int32) for _ in range(3))
+        goal_out = np.zeros((n, P), F32)
+        total, team = np.zeros((2, g), np.int64), np.zeros((4, g), np.int32)
+        u, v = np.zeros((g, size), np.int64), np.zeros((g, size), np.int64)
+        matrix = np.zeros((g, size, size), np.int32) if want_matrix else None
+        check(self.lib.mobrob_ppo_plan_assign(
+            self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None or moving else C.byref(h),
+            C.byref(h) if moving else None, None if tm is None else C.byref(tm), size, obj, _fp(start), _fp(goal), assign.ctypes.data_as(i32),
+            _fp(goal_out), cost.ctypes.data_as(i32), total.ctypes.data_as(i64), team.ctypes.data_as(i32), u.ctypes.data_as(i64),
+            v.ctypes.data_as(i64), None if matrix is None else matrix.ctypes.data_as(i32), sweeps.ctypes.data_as(i32)))
+        out = {"assign": assign, "goal": goal_out, "assign_cost": cost, "assign_total": total[0].copy(), "assign_max": team[0].copy(),
+               "assign_identity_total": total[1].copy(), "assign_identity_max": team[1].copy(), "assign_changed": team[2] != 0,
+               "assign_status": team[3].copy(), "assign_potentials": (u, v), "sweeps": sweeps}
+        if matrix is not None:
+            out["assign_matrix"] = matrix
+        return out
+
     def episode_stats(self, reset=True):
         """Episodes finished by the goal environment since the counters were last reset."""
         st = EpisodeStats()

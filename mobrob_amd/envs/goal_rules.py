@@ -1833,3 +1833,196 @@ def grid_path_smooth_team(field, occ_layers, spec, start_xy, goal_xy, K, margin=
     sx, sy = cells[0]
     return ((wp, count, TRUNCATED if count > K else PLANNED, int(np.asarray(field)[0, sy, sx]), leave, len(acts),
              sum(k != PLAN_WAIT_ACTION for k in acts)), cells, keep)
+
+
+# ---- goal assignment inside a team: who takes which goal, a minimum-cost perfect matching per team on each robot's
+# own static cost-to-go.  This project's own rule, integers throughout; the device (csrc/kernels_plan.h: k_plan_assign_cost,
+# k_plan_assign) is held to it bit for bit, the potentials included.  It runs in front of a team plan and changes the plan's INPUT
+# (goal[n]), never the planner; reservations play no part, so the matching is a function of (scene, starts, goals) alone.
+PLAN_ASSIGN_NONE = 1 << 21      # the cost of a pair without a path: above 16 * 7 * 128 * 128, the largest total of real costs
+PLAN_ASSIGN_FORBID = 1 << 26    # in a makespan matching: the cost of a pair above the bottleneck L
+PLAN_ASSIGN_OBJECTIVES = ("sum", "makespan")
+ASSIGN_KEYS = ("assign", "goal", "assign_cost", "assign_total", "assign_max", "assign_identity_total", "assign_identity_max",
+               "assign_changed", "assign_status")
+
+
+def plan_assign_objective(objective):
+    """-> the index of `objective` in PLAN_ASSIGN_OBJECTIVES, or ValueError"""
+    if not isinstance(objective, str) or objective not in PLAN_ASSIGN_OBJECTIVES:
+        raise ValueError(f"plan_assign: objective must be one of {PLAN_ASSIGN_OBJECTIVES}, got {objective!r}")
+    return PLAN_ASSIGN_OBJECTIVES.index(objective)
+
+
+def plan_assign_match(C):
+    """The minimum-total perfect matching of the square int64 matrix C (row i takes column col_of_row[i]) by the shortest-augmenting-
+    path Hungarian method with row and column potentials -> (col_of_row [n] int64, u [n] int64, v [n] int64).  THIS TEXT IS THE
+    DEFINITION, ties included: rows are inserted in index order; every scan relaxes the unused columns from the row i0 that was
+    reached last (minv[j] = min(minv[j], C[i0][j] - u[i0] - v[j]), strict <, so the earlier way is kept on a tie) and takes the unused
+    column of least minv, the lowest index on a tie (strict <); delta goes onto u of the rows in the tree and off v of the used
+    columns and off minv of the others.  On return u[i] + v[j] <= C[i][j] everywhere, with equality on the matched pairs -- the
+    certificate that the total is the least one (any matching's total is >= sum(u) + sum(v))."""
+    C = np.asarray(C, np.int64)
+    n = C.shape[0]
+    if C.ndim != 2 or C.shape[1] != n:
+        raise ValueError(f"plan_assign: the cost matrix must be square, got shape {C.shape}")
+    big = np.int64(1) << 62
+    u, v = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    p = np.full(n, -1, np.int64)                       # p[j]: the row matched to column j
+    for i in range(n):
+        minv, way = np.full(n, big, np.int64), np.full(n, -1, np.int64)   # way[j]: the column before j on its path, -1: the root
+        used, rowin = np.zeros(n, bool), np.zeros(n, bool)
+        j0, i0 = -1, i
+        while True:
+            rowin[i0] = True
+            open_ = ~used
+            cur = C[i0] - u[i0] - v
+            better = open_ & (cur < minv)
+            minv[better], way[better] = cur[better], j0
+            j1 = int(np.argmin(np.where(open_, minv, big)))                # argmin: the first of equal values
+            delta = minv[j1]
+            u[rowin] += delta
+            v[used] -= delta
+            minv[open_] -= delta
+            j0 = j1
+            used[j0] = True
+            i0 = int(p[j0])
+            if i0 < 0:
+                break
+        while j0 >= 0:                                                     # augment along the way back to the root
+            j1 = int(way[j0])
+            p[j0] = p[j1] if j1 >= 0 else i
+            j0 = j1
+    col = np.zeros(n, np.int64)
+    col[p] = np.arange(n)
+    return col, u, v
+
+
+def plan_assign_bottleneck(C):
+    """L: the least value such that a perfect matching exists among the entries of C that are <= L (unique, so any method serves):
+    a bisection over the sorted distinct entries; a value is feasible where the 0 / 1 matrix C > L has a matching of total 0"""
+    C = np.asarray(C, np.int64)
+    cand = np.unique(C)
+    lo, hi = 0, len(cand) - 1                                              # the largest entry is feasible
+    while lo < hi:
+        mid = (lo + hi) // 2
+        B = (C > cand[mid]).astype(np.int64)
+        col, _, _ = plan_assign_match(B)
+        if int(B[np.arange(len(col)), col].sum()) == 0:
+            hi = mid
+        else:
+            lo = mid + 1
+    return int(cand[lo])
+
+
+def plan_assign_team(C, objective="sum"):
+    """One team's assignment on its int64 cost matrix C (NONE entries as PLAN_ASSIGN_NONE) -> (col_of_row, u, v, changed).
+    "sum": plan_assign_match(C).  "makespan": plan_assign_match on where(C > L, PLAN_ASSIGN_FORBID, C), L = plan_assign_bottleneck(C):
+    the largest member cost first, then the total.  Identity first: where the identity's total (makespan: its (max, total)) on C
+    equals the matching's, the identity is the result -- a team that is well paired already is never renumbered.  u, v: the
+    potentials of the (last) plan_assign_match run, whichever matching is returned (the identity is then optimal too, hence tight)."""
+    C = np.asarray(C, np.int64)
+    n = C.shape[0]
+    rows = np.arange(n)
+    if plan_assign_objective(objective) == 1:
+        L = plan_assign_bottleneck(C)
+        col, u, v = plan_assign_match(np.where(C > L, np.int64(PLAN_ASSIGN_FORBID), C))
+        same = int(C[rows, rows].max()) == int(C[rows, col].max()) and int(C[rows, rows].sum()) == int(C[rows, col].sum())
+    else:
+        col, u, v = plan_assign_match(C)
+        same = int(C[rows, rows].sum()) == int(C[rows, col].sum())
+    if same:
+        col = rows.astype(np.int64)
+    return col, u, v, bool(np.any(col != rows))
+
+
+def plan_assign_cells(spec, start, goal):
+    """-> (start cell [n], goal cell [n]) int64 flat indices of float32 starts and goals [n][>= 2]"""
+    sx, sy = spec.cell_of(np.asarray(start, np.float32)[:, :2])
+    gx, gy = spec.cell_of(np.asarray(goal, np.float32)[:, :2])
+    return sy * spec.cells + sx, gy * spec.cells + gx
+
+
+def plan_assign_check(spec, walls, hazards, start, goal, teams, objective, step0, layer_steps, layers):
+    """grid_assign's refusals, by name -> (start, goal float32 [n][P], size, objective index, step0, layer_steps, T); T = 0 (and
+    layer_steps = 1) in a static scene, where neither is looked at"""
+    if not isinstance(spec, GridSpec):
+        raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.GridSpec, not {type(spec).__name__}")
+    if not isinstance(teams, Teams):
+        raise TypeError(f"plan_assign: teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
+    obj = plan_assign_objective(objective)
+    start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
+    if goal.ndim != 2 or goal.shape[0] < 1 or goal.shape[1] not in (2, 3) or start.shape != goal.shape:
+        raise ValueError(f"plan_assign: start and goal must both be [n_robots, 2 or 3], got shapes {start.shape} and {goal.shape}")
+    if not (np.all(np.isfinite(start)) and np.all(np.isfinite(goal))):
+        raise ValueError("plan_assign: start and goal must be finite")
+    if isinstance(hazards, MovingHazards):
+        if layer_steps is None or layers is None:
+            raise ValueError("plan_assign: layer_steps and layers are required with a MovingHazards (the cost map is the tail of its layers)")
+        step0, layer_steps, T = plan_time_check(step0, layer_steps, layers)
+        _, scene = plan_scene_time(walls, hazards)
+    else:
+        step0, layer_steps, T = 0, 1, 0
+        _, scene = plan_scene(walls, hazards)
+    n = goal.shape[0]
+    for sc in (walls, hazards):
+        if sc is not None:
+            sc.check_robots(n)
+    size, _ = plan_team_check(teams, 0, n, scene)
+    return start.astype(np.float32), goal.astype(np.float32), size, obj, step0, layer_steps, T
+
+
+def plan_assign_outputs(C, col, changed, goal, status=None):
+    """The outputs of an assignment from the cost matrices C int64 [n_teams][size][size] (NONE as PLAN_ASSIGN_NONE), the matchings
+    col [n_teams][size] and goal float32 [n][P] -> grid_assign's dict without the matrix and the potentials"""
+    g, size = C.shape[:2]
+    rows = np.arange(size)
+    base = (np.arange(g) * size)[:, None]
+    assign = (base + col).reshape(-1).astype(np.int32)
+    picked, ident = C[np.arange(g)[:, None], rows[None, :], col], C[:, rows, rows]
+    return {"assign": assign, "goal": np.asarray(goal, np.float32)[assign],
+            "assign_cost": np.where(picked >= PLAN_ASSIGN_NONE, -1, picked).reshape(-1).astype(np.int32),
+            "assign_total": picked.sum(axis=1).astype(np.int64), "assign_max": picked.max(axis=1).astype(np.int32),
+            "assign_identity_total": ident.sum(axis=1).astype(np.int64), "assign_identity_max": ident.max(axis=1).astype(np.int32),
+            "assign_changed": np.asarray(changed, bool),
+            "assign_status": np.full(g, PLANNED, np.int32) if status is None else np.asarray(status, np.int32)}
+
+
+def grid_assign(spec, walls, hazards, start, goal, teams, objective="sum", step0=0, layer_steps=None, layers=None, want_matrix=True):
+    """Who takes which goal inside every team -> dict.  The cost map is layer T of the team plan's base layers
+    (plan_team_base): grid_occupancy's map in a static scene, the conservative tail of grid_occupancy_time with a MovingHazards
+    (layer_steps and layers are required only then).  Per team g the int64 matrix C[g][i][j] = grid_field(map of the team's scene,
+    goal cell of member j)[start cell of member i], -1 (blocked or unreachable) as PLAN_ASSIGN_NONE -- so a minimum-sum matching
+    first minimises the number of pairs without a path -- and plan_assign_team(C[g], objective) is the team's matching; a team of
+    one keeps the identity.  The dict: assign int32 [n] (the robot, a mate or itself, whose INPUT goal robot i is given), goal
+    float32 [n][P] = goal[assign], assign_cost int32 [n] (-1: no path), assign_total int64 and assign_max int32 [n_teams] (on C, NONE
+    counted as NONE), assign_identity_total and assign_identity_max (the same of the pairing as given), assign_changed bool
+    [n_teams], assign_status int32 [n_teams] (PLANNED; the device reports UNCONVERGED where a field hit its sweep bound, and that
+    team keeps the identity), assign_potentials (u, v) int64 [n_teams][size] each (plan_assign_match's certificate, of the last
+    run), and with want_matrix assign_matrix int32 [n_teams][size][size], -1 for NONE."""
+    start, goal, size, _, step0, layer_steps, T = plan_assign_check(spec, walls, hazards, start, goal, teams, objective, step0,
+                                                                     layer_steps, layers)
+    occ, _, scene = plan_team_base(spec, walls, hazards, step0, layer_steps, T)
+    cost_map = occ[:, T]
+    n = goal.shape[0]
+    g = n // size
+    sc = np.zeros(n, np.int64) if scene is None else np.asarray(scene, np.int64)
+    scell, gcell = plan_assign_cells(spec, start, goal)
+    fields = {}
+    C = np.zeros((g, size, size), np.int64)
+    for t in range(g):
+        for j in range(size):
+            nj = t * size + j
+            key = (int(sc[nj]), int(gcell[nj]))
+            if key not in fields:
+                fields[key] = grid_field(cost_map[key[0]], key[1]).reshape(-1)
+            d = fields[key][scell[t * size:(t + 1) * size]].astype(np.int64)
+            C[t, :, j] = np.where(d < 0, PLAN_ASSIGN_NONE, d)
+    col, u, v = np.zeros((g, size), np.int64), np.zeros((g, size), np.int64), np.zeros((g, size), np.int64)
+    changed = np.zeros(g, bool)
+    for t in range(g):
+        col[t], u[t], v[t], changed[t] = plan_assign_team(C[t], objective)
+    out = plan_assign_outputs(C, col, changed, goal)
+    out["assign_potentials"] = (u, v)
+    if want_matrix:
+        out["assign_matrix"] = np.where(C >= PLAN_ASSIGN_NONE, -1, C).astype(np.int32)
+    return out

@@ -22,8 +22,11 @@ actions is clear whatever the robot's speed along it, and the plan holds the rob
 most `max_leg` actions long and is reserved for the later members as a swept region, all of its cells in every layer of its span
 (goal_rules.grid_plan_team(smooth=True); device: mobrob_ppo_plan_grid_team_smooth).  Reordering rounds (`retries=R`, DESIGN
 4.12.6): a team whose plan leaves members parked is planned again, inside the same call, with those members first, and the plan
-with the fewest parked members is the result (goal_rules.grid_plan_team_rounds; device: mobrob_ppo_plan_grid_team_rounds).  Walls
-as solid bodies are not planned for."""
+with the fewest parked members is the result (goal_rules.grid_plan_team_rounds; device: mobrob_ppo_plan_grid_team_rounds).  Goal
+assignment (`assign="sum"` or `"makespan"`): a team is given places to occupy, not a pairing -- in front of the
+team plan, every team's members and goals are matched at minimum cost on each robot's own static cost-to-go, and the plan is made
+for the assigned goals, through whichever team path the planner is configured for; `planner.assign(start, goal)` is that step on
+its own (goal_rules.grid_assign; device: mobrob_ppo_plan_assign).  Walls as solid bodies are not planned for."""
 from __future__ import annotations
 
 import numpy as np
@@ -58,11 +61,16 @@ class GridPlanner:
     only a chain of at most retries + 1 orders is tried, not every order.  retries > 0 with time_smooth is refused.  With time_smooth a
     team plan is smoothed too (a team plan is a time plan: no MovingHazards needed): max_leg, the actions of a leg at most (8; None:
     no cap; it belongs to teams, ValueError otherwise) -- a leg reserves all of its cells in every layer of its span, so long legs
-    shut later members out, and a member whose start cell an earlier member's leg covers comes back UNREACHABLE."""
+    shut later members out, and a member whose start cell an earlier member's leg covers comes back UNREACHABLE.
+    assign: None (robot i goes to goal i, as given), "sum" or "makespan" (it belongs to teams, ValueError otherwise): every plan first
+    assigns the goals inside each team -- the minimum-total matching of members and goals, or the one that minimises the largest
+    member cost first and then the total -- on each robot's own static cost-to-go (goal_rules.grid_assign), and plans the assigned
+    goals.  A team that is already paired as well as any matching keeps its pairing.  The matching does not see reservations or
+    the hazards' layers before the tail, teams are matched on their own, and a run is never reassigned."""
 
     def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
                  smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None, time_smooth=False, max_leg=_UNSET,
-                 retries=0):
+                 retries=0, assign=None):
         from .envs.vec_env import DeviceGoalVecEnv
         if teams is not None and not isinstance(teams, rules.Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
@@ -73,6 +81,11 @@ class GridPlanner:
         if teams is None and not (isinstance(retries, (int, np.integer)) and not isinstance(retries, bool) and retries == 0):
             raise ValueError("GridPlanner: retries= belongs to teams= (reordering rounds of a team plan)")
         self.retries = rules.plan_retries_check(retries)
+        if assign is not None:
+            if teams is None:
+                raise ValueError("GridPlanner: assign= belongs to teams= (goals are assigned inside a team)")
+            rules.plan_assign_objective(assign)
+        self.assign_objective = assign
         self.max_leg = 8 if max_leg is _UNSET else (None if max_leg is None else rules.plan_max_leg_check(max_leg))
         self.teams = teams
         self.timed = isinstance(hazards, rules.MovingHazards) or teams is not None
@@ -208,6 +221,21 @@ class GridPlanner:
         return rules.grid_plan_time(self.spec, self.walls, self.hazards, start, goal, K, step0, self.layer_steps, self.layers,
                                     smooth=smooth, margin=self.los_margin)
 
+    def assign(self, start, goal, step0=0, want_matrix=False):
+        """The assignment on its own: start, goal [n][P] -> goal_rules.grid_assign's dict (assign, goal = goal[assign], assign_cost,
+        assign_total, assign_max, assign_identity_total, assign_identity_max, assign_changed, assign_status, assign_potentials, and
+        with want_matrix assign_matrix), by the device call on a DeviceGoalVecEnv and by the NumPy rule on the host path, as `plan`
+        chooses.  The planner needs teams=; the objective is the planner's assign= ("sum" where that is None)."""
+        if self.teams is None:
+            raise ValueError("GridPlanner.assign: the planner has no teams= (goals are assigned inside a team)")
+        start, goal = self._check(start, goal)
+        kw = dict(objective=self.assign_objective or "sum", step0=step0, want_matrix=want_matrix)
+        if isinstance(self.hazards, rules.MovingHazards):
+            kw.update(layer_steps=self.layer_steps, layers=self.layers)
+        if self.device:
+            return self.engine.plan_assign(self.spec, self.walls, self.hazards, teams=self.teams, start=start, goal=goal, **kw)
+        return rules.grid_assign(self.spec, self.walls, self.hazards, start, goal, self.teams, **kw)
+
     def plan(self, start, goal, step0=0, *, grow=False, want_occupancy=False, want_fields=False, smooth=None, time_smooth=None):
         """start, goal [n][P] -> dict: waypoints [n][K][P] float32 (z: the goal's), n_waypoints [n] (= min(count, K)), count [n]
         waypoints of the full path, status [n] (goal_rules.PLANNED 0, UNREACHABLE 1, TRUNCATED 2; UNCONVERGED 3: a device loop hit
@@ -230,8 +258,16 @@ class GridPlanner:
         smoothed count.  A kept leg of two or more actions is clear in every layer it spans; the count may exceed the unsmoothed
         plan's.  With the planner's retries > 0 a team plan is the best of its reordering rounds and the dict gains team_order
         [n_teams][size] (the order that plan was made in), team_rounds (rounds planned), team_parked and team_parked_first
-        [n_teams] (members without a walk in that plan and in index order) (goal_rules.grid_plan_team_rounds)."""
+        [n_teams] (members without a walk in that plan and in index order) (goal_rules.grid_plan_team_rounds).
+        With the planner's assign= the goals are first assigned inside every team (`assign`), the plan is made for the assigned
+        goals -- `grow` plans the same assignment again -- and the dict gains goal_rules.ASSIGN_KEYS: assign [n], goal [n][P] (the
+        goals the plan was made for: hand THESE to `callback` and to the tracker), assign_cost [n], assign_total, assign_max,
+        assign_identity_total, assign_identity_max, assign_changed and assign_status [n_teams]."""
         start, goal = self._check(start, goal)
+        assigned = None
+        if self.assign_objective is not None:
+            assigned = self.assign(start, goal, step0)
+            goal = np.ascontiguousarray(assigned["goal"], np.float32)
         smooth = self.smooth if smooth is None else bool(smooth)
         time_smooth = self.time_smooth if time_smooth is None else self._time_smooth_ok(time_smooth)
         if self.timed:
@@ -260,6 +296,8 @@ class GridPlanner:
                 res["keeps"] = out["keeps"]
             if self.retries > 0:
                 res.update({k: out[k] for k in rules.TEAM_ROUND_KEYS})
+        if assigned is not None:
+            res.update({k: assigned[k] for k in rules.ASSIGN_KEYS})
         res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
         res["smoothed"], res["moves"] = smooth, out.get("moves")
         if want_occupancy:
@@ -282,7 +320,9 @@ class GridPlanner:
         plans are smoothed over time when the planner is (`time_smooth=`); the tuples are the same.
         With teams (horizon required as well) a team with any STALLED member is planned again as a whole from where its members
         stand: every member that is not FINISHED and whose new plan is PLANNED gets (waypoints, release); finished members are
-        planned too, so that they reserve their cell, and are not returned."""
+        planned too, so that they reserve their cell, and are not returned.
+        The callback NEVER reassigns: with the planner's assign= hand it plan["goal"], the goals the first plan was made for; it
+        plans to the goals as given, robot i to goal[i]."""
         from .waypoints import FINISHED, STALLED
         goal = np.asarray(goal, np.float64)
         if self.timed:
@@ -296,7 +336,11 @@ class GridPlanner:
             stalled = np.nonzero(np.asarray(status) == STALLED)[0]
             if stalled.size == 0:
                 return {}
-            plan = self.plan(positions, goal, planner.calls * int(horizon)) if self.timed else self.plan(positions, goal)
+            objective, self.assign_objective = self.assign_objective, None     # the goals as given: a run is never reassigned
+            try:
+                plan = self.plan(positions, goal, planner.calls * int(horizon)) if self.timed else self.plan(positions, goal)
+            finally:
+                self.assign_objective = objective
             planner.last = plan
             if self.teams is not None:                     # the whole team of a stalled robot, its finished members aside
                 mates = np.unique(stalled // self.teams.size)[:, None] * self.teams.size + np.arange(self.teams.size)
