@@ -53,7 +53,10 @@ clearance beside the run's measured conflicts; with `--plan-time-smooth` a team 
 a team whose members stayed parked again, up to R times, with those members first, and a line reports the parked members before
 and after.  `--plan-smooth` smooths every plan by line
 of sight (fewer waypoints: only the cells a straight leg cannot skip), `--plan-los-margin` (0 or 1, default 1) is the clearance of
-that test in cells; a second line then reports the waypoints and the moves per planned robot.
+that test in cells; a second line then reports the waypoints and the moves per planned robot.  `--plan-clearance REACH,WEIGHT`
+(a static plan only: it excludes --hazard-frames, --team-size and --plan-time-smooth) makes the plan pay WEIGHT * (REACH + 1 - c) for
+entering a cell c <= REACH cells from a blocked one, so it keeps away from obstacles where room exists; a line reports the
+waypoints per planned robot and the least clearance of the walks beside those of the plan without it.
 
 `--goals FILE.npy` plans to a SET of places instead of one goal: `[size][P]` (the places of one team, the same for every team;
 size = --team-size) or `[n][P]` (one per robot).  It excludes --goal and --waypoints.  As given, robot i is planned to goals[i];
@@ -89,7 +92,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
-           plan_retries=0, goals=None, assign=None):
+           plan_retries=0, goals=None, assign=None, plan_clearance=None):
     calls = check_chain(max_steps, horizon, leg_steps)
     if goals is not None and (goal is not None or waypoints is not None):
         raise ValueError("--goals excludes --goal and --waypoints")
@@ -146,8 +149,19 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
                               **(dict(layer_steps=int(plan_layer_steps), layers=int(plan_layers)) if timed else {}),
                               **(dict(teams=teams, reserve=None if plan_reserve is None else int(plan_reserve)) if teams is not None else {}),
                               **(dict(retries=int(plan_retries)) if int(plan_retries) != 0 else {}),
-                              **(dict(assign=assign) if assign is not None else {}))
+                              **(dict(assign=assign) if assign is not None else {}),
+                              **(dict(clearance=tuple(plan_clearance)) if plan_clearance is not None else {}))
+        if plan_clearance is not None:                     # the plan without it, made first: the run's plan stays the planner's latest
+            from mobrob_amd.envs.goal_rules import grid_plan_clearance_min
+            plain = planner.plan(start, goals, grow=True, clearance=None, want_occupancy=True, want_fields=True)
+            plain_min = grid_plan_clearance_min(planner.spec, plain, start, goals, planner.clearance[0])
         plan = planner.plan(start, goals, grow=True)
+        if plan_clearance is not None:
+            ok, pk = plan["status"] == 0, plain["status"] == 0
+            if np.any(ok) and np.any(pk):
+                print(f"clearance plan {planner.clearance}: {float(np.mean(plan['count'][ok]))} waypoints per planned robot, least clearance "
+                      f"{int(plan['clearance_min'][ok].min())} cells; without it: {float(np.mean(plain['count'][pk]))} waypoints, least "
+                      f"clearance {int(plain_min[pk].min())} cells")
         if assign is not None:
             goals = plan["goal"]                           # the callback plans to the goals it is given and never reassigns
             print(f"assigned ({assign}): {int(plan['assign_changed'].sum())} of {len(plan['assign_changed'])} teams changed, total path cost "
@@ -249,6 +263,8 @@ def build_parser():
     ap.add_argument("--plan-max-leg", type=int, default=None,
                     help="with --plan-time-smooth and --team-size: the actions of a smoothed leg at most (default 8; 0: no cap)")
     ap.add_argument("--plan-los-margin", type=int, default=1, choices=(0, 1), help="cells a smoothed leg keeps clear on either side")
+    ap.add_argument("--plan-clearance", type=str, default=None,
+                    help="REACH,WEIGHT (1 .. 8, 1 .. 16): a static plan that pays WEIGHT a cell of missing clearance within REACH cells of obstacles")
     ap.add_argument("--plan-layer-steps", type=int, default=10, help="with --hazard-frames or --team-size: steps a robot is given for one move or wait")
     ap.add_argument("--plan-reserve", type=int, default=None,
                     help="with --goal and --team-size: cells a mate's planned walk reserves around itself, 0 .. 4 (default: ceil(separation / cell))")
@@ -298,4 +314,5 @@ if __name__ == "__main__":
            goal=None if args.goal is None else [float(v) for v in args.goal.split(",")], plan_cells=args.plan_cells,
            plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin, plan_layer_steps=args.plan_layer_steps,
            plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg,
-           plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign)
+           plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
+           plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")])

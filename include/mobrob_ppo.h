@@ -853,6 +853,51 @@ int mobrob_ppo_plan_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
                            float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */,
                            int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */, int32_t* moves_out /* [n] */);
 
+/* ---- grid planner: clearance-aware static plans, a per-cell surcharge near blocked cells ----------------------------------------------
+ * mobrob_ppo_plan_grid minimises chamfer length, so its paths hug every obstacle they round.  This call plans on the same grid and the
+ * same blocked cells with a SURCHARGE on entering a cell near a blocked one, so a path takes the middle of a corridor where that costs
+ * little.  The rule, all integers, is stated once in mobrob_amd/envs/goal_rules.py (grid_clearance, grid_surcharge, grid_field_cost,
+ * grid_walk_cost, grid_walk_clearance) and reproduced bit for bit:
+ *   clearance the Chebyshev distance in cells of a cell to the nearest blocked cell of the grid, capped at reach + 1; blocked cells 0;
+ *             cells outside the grid count as free.
+ *   surcharge pen[c] = weight * max(0, reach + 1 - clearance[c]) on free cells, 0 on blocked ones; at most 16 * 8 = 128, a byte.
+ *   field     the fixed point of d[c] = min_k(w(k) + pen[c'] + d[c']) over mobrob_ppo_plan_grid's moves from c into c', d[goal] = 0: the
+ *             goal cell's own surcharge is paid on entry like any cell's, the start cell's never.  -1 blocked or unreachable.
+ *   path      mobrob_ppo_plan_grid's walk with the step to a neighbour with w + pen[c'] + d[c'] == d[c], the same tie order; waypoints,
+ *             count and status as there.  cost_out: d at the start cell, the moves plus the surcharges paid.
+ *   outputs   mobrob_ppo_plan_grid's, and clearance_min_out [n]: the least clearance over the cells the walk enters (reach + 1 for a
+ *             start in the goal's cell, -1 without a walk); on request surcharge_out [S][G][G].
+ *   reuse     as mobrob_ppo_plan_grid's, in resident buffers of this family's own (occupancy, surcharges, cost fields): a plain plan and
+ *             a clearance plan stay resident side by side.  fields_id_out is an id of this family; spec->reuse_id naming fields of the
+ *             other family (either way round), or stale ones, is MOBROB_ERR_STATE.  A reuse call gives the resident reach and weight.
+ *   kernels   k_plan_occupancy as it is; k_plan_surcharge (a workgroup per scene: `reach` rounds of 3 x 3 dilation between two byte maps
+ *             in LDS, a barrier a round, every cell records the round that reached it); k_plan_field_cost (k_plan_field's shape with a
+ *             byte of surcharge per cell beside the field and the moves: 6 bytes a cell, 96 KB at 128 cells); k_plan_path_cost.
+ * NOT promised: the plan is no longer the shortest; a doorway narrower than 2 reach cells is still used, its surcharge is paid.
+ * MOBROB_ERR_INVALID before any launch or copy for reach outside 1 .. 8, weight outside 1 .. 16, a reuse call whose reach or weight is
+ * not the resident fields', and everything mobrob_ppo_plan_grid refuses. */
+int mobrob_ppo_plan_grid_clear(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                               const mobrob_hazards_t* hazards /* or NULL */, int32_t reach /* 1 .. 8 */, int32_t weight /* 1 .. 16 */,
+                               const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */,
+                               const int32_t* field_of /* [n] */, const int32_t* field_goal_cell /* [F] */,
+                               const int32_t* field_scene /* [F] */, float* waypoints_out /* [n][K][pos_dim] */,
+                               int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */, int32_t* status_out /* [n] */,
+                               int32_t* cost_out /* [n] */, int32_t* clearance_min_out /* [n] */,
+                               uint8_t* occupancy_out /* [S][G][G] or NULL */, int32_t* field_out /* [F][G][G] or NULL */,
+                               int32_t* sweeps_out /* [F] or NULL */, uint8_t* surcharge_out /* [S][G][G] or NULL */,
+                               int64_t* fields_id_out /* or NULL */);
+
+/* mobrob_ppo_plan_smooth on the fields a mobrob_ppo_plan_grid_clear call left resident (spec->reuse_id = its fields_id_out; any other
+ * id: MOBROB_ERR_STATE): the walk is the clearance-aware one, the line-of-sight rule is mobrob_ppo_plan_smooth's own and never reads
+ * costs.  k_plan_smooth_cost: k_plan_smooth's wave per robot, ring, ballot window and bounds with the surcharge-aware step.  Outputs
+ * and refusals as mobrob_ppo_plan_smooth's, and clearance_min_out [n] as mobrob_ppo_plan_grid_clear's. */
+int mobrob_ppo_plan_smooth_clear(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, int32_t margin /* 0 or 1 */,
+                                 const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] */,
+                                 const int32_t* field_of /* [n] */, const int32_t* scene /* [n] or NULL */,
+                                 float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */,
+                                 int32_t* count_out /* [n] */, int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */,
+                                 int32_t* moves_out /* [n] */, int32_t* clearance_min_out /* [n] */);
+
 /* ---- grid planner over time: moving hazards as layers of occupancy, waits as release steps -----------------------------------------
  * mobrob_ppo_plan_grid for hazards that move (mobrob_hazard_frames_t).  The rule is stated once in mobrob_amd/envs/goal_rules.py
  * (grid_layer_frames, grid_occupancy_time, grid_time_field, grid_walk_time, grid_path_time) and reproduced bit for bit.  A robot is

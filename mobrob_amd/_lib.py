@@ -209,6 +209,13 @@ SYMBOLS = {
     "mobrob_ppo_plan_smooth": (C.c_int, [_P, C.POINTER(PlanSpec), C.c_int32, _F, _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32)]),
+    "mobrob_ppo_plan_grid_clear": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardsC), C.c_int32, C.c_int32, _F, _F,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _U8,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), _U8, _I64]),
+    "mobrob_ppo_plan_smooth_clear": (C.c_int, [_P, C.POINTER(PlanSpec), C.c_int32, _F, _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mobrob_ppo_plan_grid_time": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardFramesC), C.POINTER(PlanTime), _F, _F,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -285,6 +285,15 @@ struct mobrob_ppo_engine {
   char* plan_dil = nullptr;
   size_t plan_dil_bytes = 0;
   int64_t plan_dil_id = 0;
+  // clearance-aware plans (mobrob_ppo_plan_grid_clear): resident fields of their own -- occupancy, surcharges, the margin-1 map,
+  // cost fields -- beside the plain ones, so neither family evicts the other.  Their ids carry kPlanClearIdBit: an id of one family
+  // never equals a resident id of the other, which is how a reuse_id of the wrong family is refused
+  char* plan_clear_fields = nullptr;
+  size_t plan_clear_fields_bytes = 0;
+  int64_t plan_clear_id = 0, plan_clear_dil_id = 0;
+  int plan_clear_G = 0, plan_clear_S = 0, plan_clear_F = 0, plan_clear_reach = 0, plan_clear_weight = 0;
+  std::vector<int32_t> plan_clear_field_scene, plan_clear_field_goal;
+  bool plan_clear_lds_set = false;    // k_plan_field_cost's dynamic-LDS attribute is raised once
   // time plans (mobrob_ppo_plan_grid_time): one allocation of their own and nothing resident, so the static fields above stay
   // valid across time-plan calls
   char* plan_time_buf = nullptr;
@@ -1371,6 +1380,7 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   if (e->plan_fields) (void)hipFree(e->plan_fields);
   if (e->plan_buf) (void)hipFree(e->plan_buf);
   if (e->plan_dil) (void)hipFree(e->plan_dil);
+  if (e->plan_clear_fields) (void)hipFree(e->plan_clear_fields);
   if (e->plan_time_buf) (void)hipFree(e->plan_time_buf);
   if (e->plan_team_buf) (void)hipFree(e->plan_team_buf);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -4272,6 +4282,253 @@ int mobrob_ppo_plan_smooth(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
   HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(moves_out, sa.moves, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
+}
+
+// ---- clearance-aware static plans (mobrob_ppo_plan_grid_clear, mobrob_ppo_plan_smooth_clear) ------------------------------------
+constexpr int64_t kPlanClearIdBit = (int64_t)1 << 62;   // set in every id of this family, in none of mobrob_ppo_plan_grid's
+
+// the resident part of a clearance-aware plan: occupancy | surcharge | margin-1 map | field | field_goal | field_scene | sweeps
+struct PlanClearKeep {
+  size_t occ, pen, dil, field, fgoal, fscene, sweeps, total;
+  PlanClearKeep(int S, int F, int cells) {
+    EvalCarve keep;
+    occ = keep.add((size_t)S * cells); pen = keep.add((size_t)S * cells); dil = keep.add((size_t)S * cells);
+    field = keep.add((size_t)F * cells * 4); fgoal = keep.add((size_t)F * 4); fscene = keep.add((size_t)F * 4);
+    sweeps = keep.add((size_t)F * 4);
+    total = keep.total;
+  }
+};
+
+static int plan_clear_check_costs(const char* who, int reach, int weight) {
+  if (reach < 1 || reach > kPlanClearReachMax)
+    return fail(MOBROB_ERR_INVALID, "%s: reach must lie in 1 .. %d, got %d", who, kPlanClearReachMax, reach);
+  if (weight < 1 || weight > kPlanClearWeightMax)
+    return fail(MOBROB_ERR_INVALID, "%s: weight must lie in 1 .. %d, got %d", who, kPlanClearWeightMax, weight);
+  return MOBROB_OK;
+}
+
+// is spec->reuse_id the resident clearance fields' own, with their shape?
+static int plan_clear_check_resident(const char* who, const mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec) {
+  if (spec->reuse_id == 0 || spec->reuse_id != e->plan_clear_id)
+    return fail(MOBROB_ERR_STATE, "%s: the clearance fields of id %lld are not resident (resident: %lld; an id of mobrob_ppo_plan_grid's "
+                "names fields of the other family)", who, (long long)spec->reuse_id, (long long)e->plan_clear_id);
+  if (spec->cells != e->plan_clear_G || spec->n_scenes != e->plan_clear_S || spec->n_fields != e->plan_clear_F)
+    return fail(MOBROB_ERR_INVALID, "%s: reuse: cells, n_scenes, n_fields = %d, %d, %d are not the resident fields' %d, %d, %d", who, spec->cells,
+                spec->n_scenes, spec->n_fields, e->plan_clear_G, e->plan_clear_S, e->plan_clear_F);
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_plan_grid_clear(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                               int32_t reach, int32_t weight, const float* start, const float* goal, const int32_t* field_of,
+                               const int32_t* field_goal_cell, const int32_t* field_scene, float* waypoints_out, int32_t* n_waypoints_out,
+                               int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* clearance_min_out, uint8_t* occupancy_out,
+                               int32_t* field_out, int32_t* sweeps_out, uint8_t* surcharge_out, int64_t* fields_id_out) {
+  const char* who = "plan_grid_clear";
+  if (!e || !spec || !start || !goal || !field_of || !waypoints_out || !n_waypoints_out || !count_out || !status_out || !cost_out ||
+      !clearance_min_out)
+    return fail(MOBROB_ERR_INVALID, "%s: null argument", who);
+  const bool reuse = spec->reuse_id != 0;
+  if (!reuse && (!field_goal_cell || !field_scene)) return fail(MOBROB_ERR_INVALID, "%s: null argument", who);
+  if (const int rc = plan_clear_check_costs(who, reach, weight)) return rc;
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
+  const int cells = G * G;
+  std::vector<int32_t> wall_counts, hz_counts;
+  if (const int rc = plan_check_scenes(who, spec, walls, hz, nullptr, wall_counts, hz_counts)) return rc;
+  const int32_t* scene = walls ? walls->scene : hz ? hz->scene : nullptr;
+  if (reuse) {
+    if (const int rc = plan_clear_check_resident(who, e, spec)) return rc;
+    if (reach != e->plan_clear_reach || weight != e->plan_clear_weight)
+      return fail(MOBROB_ERR_INVALID, "%s: reuse: reach, weight = %d, %d are not the resident fields' %d, %d", who, reach, weight,
+                  e->plan_clear_reach, e->plan_clear_weight);
+    field_goal_cell = e->plan_clear_field_goal.data();
+    field_scene = e->plan_clear_field_scene.data();
+  }
+  if (const int rc = plan_check_robots(who, spec, scene, start, goal, field_of, field_goal_cell, field_scene, !reuse)) return rc;
+  const size_t field_lds = plan_field_cost_lds_bytes(G);
+  const int Mw = walls ? walls->max_walls : 0, Mh = hz ? hz->max_hazards : 0;
+  if (!reuse) {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid checks k_plan_field's
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+    if (field_lds > (size_t)limit)
+      return fail(MOBROB_ERR_INVALID, "%s: k_plan_field_cost needs %zu bytes of LDS at %d cells, the device allows %d per workgroup", who,
+                  field_lds, G, limit);
+  }
+  const PlanClearKeep keep(S, F, cells);
+  EvalCarve call;
+  const size_t o_start = call.add((size_t)N * P * 4), o_goal = call.add((size_t)N * P * 4), o_fof = call.add((size_t)N * 4),
+               o_wp = call.add((size_t)N * K * P * 4), o_nwp = call.add((size_t)N * 4), o_count = call.add((size_t)N * 4),
+               o_status = call.add((size_t)N * 4), o_cost = call.add((size_t)N * 4), o_cmin = call.add((size_t)N * 4),
+               o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
+               o_hz = call.add(std::max<size_t>((size_t)S * Mh * 3, 1) * 4), o_nhz = call.add((size_t)S * 4);
+  if (!reuse) {
+    e->plan_clear_id = 0;   // whatever was resident in this family is gone from here on
+    if (const int rc = grow_plan_buf(e, e->plan_clear_fields, e->plan_clear_fields_bytes, keep.total)) return rc;
+  }
+  if (const int rc = grow_plan_buf(e, e->plan_buf, e->plan_bytes, call.total)) return rc;
+  const auto kept = [&](size_t off) { return e->plan_clear_fields + off; };
+  const auto mine = [&](size_t off) { return e->plan_buf + off; };
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(kept(keep.occ));
+  unsigned char* pen_dev = reinterpret_cast<unsigned char*>(kept(keep.pen));
+  int* field_dev = reinterpret_cast<int*>(kept(keep.field));
+  int* fgoal_dev = reinterpret_cast<int*>(kept(keep.fgoal));
+  int* fscene_dev = reinterpret_cast<int*>(kept(keep.fscene));
+  int* sweeps_dev = reinterpret_cast<int*>(kept(keep.sweeps));
+  const PlanGrid grid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  if (!reuse) {
+    PlanOccArgs oa{};
+    oa.g = grid; oa.Mw = Mw; oa.Mh = Mh; oa.occ = occ_dev;
+    if (walls) {
+      float* box_dev = reinterpret_cast<float*>(mine(o_box));
+      int* cnt_dev = reinterpret_cast<int*>(mine(o_nwall));
+      if ((size_t)S * Mw) HIPC(hipMemcpyAsync(box_dev, walls->boxes, (size_t)S * Mw * 16, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(cnt_dev, wall_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+      oa.boxes = box_dev; oa.nwall = cnt_dev;
+    }
+    if (hz) {
+      float* hz_dev = reinterpret_cast<float*>(mine(o_hz));
+      int* cnt_dev = reinterpret_cast<int*>(mine(o_nhz));
+      if ((size_t)S * Mh) HIPC(hipMemcpyAsync(hz_dev, hz->hazards, (size_t)S * Mh * 12, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(cnt_dev, hz_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+      oa.hz = hz_dev; oa.nhz = cnt_dev;
+    }
+    HIPC(hipMemcpyAsync(fgoal_dev, field_goal_cell, (size_t)F * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(fscene_dev, field_scene, (size_t)F * 4, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_plan_occupancy, dim3(cdiv(cells, 256), S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
+    const PlanSurchargeArgs ca{G, reach, weight, occ_dev, pen_dev};
+    hipLaunchKernelGGL(k_plan_surcharge, dim3(S), dim3(kPlanFieldThreads), 0, e->stream, ca);   // a workgroup per scene
+    if (!e->plan_clear_lds_set) {   // 96 KB at 128 cells: above the 64 KB a kernel gets without asking
+      HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_field_cost), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)plan_field_cost_lds_bytes(128)));
+      e->plan_clear_lds_set = true;
+    }
+    const PlanFieldCostArgs fa{G, occ_dev, pen_dev, fgoal_dev, fscene_dev, field_dev, sweeps_dev};
+    hipLaunchKernelGGL(k_plan_field_cost, dim3(F), dim3(kPlanFieldThreads), field_lds, e->stream, fa);
+    HIPC(hipGetLastError());
+  }
+  PlanPathCostArgs ps{};
+  PlanPathArgs& pa = ps.p;
+  pa.g = grid; pa.N = N; pa.K = K; pa.P = P;
+  float* start_dev = reinterpret_cast<float*>(mine(o_start));
+  float* goal_dev = reinterpret_cast<float*>(mine(o_goal));
+  int* fof_dev = reinterpret_cast<int*>(mine(o_fof));
+  pa.start = start_dev; pa.goal = goal_dev; pa.field_of = fof_dev;
+  pa.field_scene = fscene_dev; pa.sweeps = sweeps_dev; pa.occ = occ_dev; pa.field = field_dev;
+  pa.wp = reinterpret_cast<float*>(mine(o_wp));
+  pa.nwp = reinterpret_cast<int*>(mine(o_nwp)); pa.count = reinterpret_cast<int*>(mine(o_count));
+  pa.status = reinterpret_cast<int*>(mine(o_status)); pa.cost = reinterpret_cast<int*>(mine(o_cost));
+  ps.pen = pen_dev; ps.reach = reach; ps.weight = weight;
+  ps.clearance_min = reinterpret_cast<int*>(mine(o_cmin));
+  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(goal_dev, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(fof_dev, field_of, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
+  hipLaunchKernelGGL(k_plan_path_cost, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, ps);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(clearance_min_out, ps.clearance_min, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  if (occupancy_out) HIPC(hipMemcpyAsync(occupancy_out, occ_dev, (size_t)S * cells, hipMemcpyDeviceToHost, e->stream));
+  if (surcharge_out) HIPC(hipMemcpyAsync(surcharge_out, pen_dev, (size_t)S * cells, hipMemcpyDeviceToHost, e->stream));
+  if (field_out) HIPC(hipMemcpyAsync(field_out, field_dev, (size_t)F * cells * 4, hipMemcpyDeviceToHost, e->stream));
+  if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, sweeps_dev, (size_t)F * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  if (!reuse) {   // resident from here on
+    static int64_t next_id = 0;
+    e->plan_clear_id = kPlanClearIdBit | ++next_id;
+    e->plan_clear_G = G; e->plan_clear_S = S; e->plan_clear_F = F;
+    e->plan_clear_reach = reach; e->plan_clear_weight = weight;
+    e->plan_clear_field_goal.assign(field_goal_cell, field_goal_cell + F);
+    e->plan_clear_field_scene.assign(field_scene, field_scene + F);
+  }
+  if (fields_id_out) *fields_id_out = e->plan_clear_id;
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_plan_smooth_clear(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, int32_t margin, const float* start, const float* goal,
+                                 const int32_t* field_of, const int32_t* scene, float* waypoints_out, int32_t* n_waypoints_out,
+                                 int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* moves_out, int32_t* clearance_min_out) {
+  const char* who = "plan_smooth_clear";
+  if (!e || !spec || !start || !goal || !field_of || !waypoints_out || !n_waypoints_out || !count_out || !status_out || !cost_out ||
+      !moves_out || !clearance_min_out)
+    return fail(MOBROB_ERR_INVALID, "%s: null argument", who);
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, F = spec->n_fields;
+  if (margin != 0 && margin != 1) return fail(MOBROB_ERR_INVALID, "%s: margin must be 0 or 1, got %d", who, margin);
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "%s: n_robots must be >= 1", who);
+  if (P != 2 && P != 3) return fail(MOBROB_ERR_INVALID, "%s: pos_dim must be 2 or 3 (the grid is x and y)", who);
+  if (G != 32 && G != 64 && G != 128) return fail(MOBROB_ERR_INVALID, "%s: cells must be 32, 64 or 128, got %d", who, G);
+  if (K < 1) return fail(MOBROB_ERR_INVALID, "%s: max_waypoints must be >= 1", who);
+  if (F < 1 || F > N) return fail(MOBROB_ERR_INVALID, "%s: n_fields = %d outside 1 .. n_robots = %d", who, F, N);
+  if (S < 1) return fail(MOBROB_ERR_INVALID, "%s: n_scenes must be >= 1", who);
+  if (!(std::isfinite(spec->extent) && spec->extent > 0.f && std::isfinite(spec->h) && spec->h > 0.f && std::isfinite(spec->inv_h) &&
+        spec->inv_h > 0.f && std::fabs((double)spec->h * (double)spec->inv_h - 1.0) <= 1e-5))
+    return fail(MOBROB_ERR_INVALID, "%s: extent, h and inv_h must be finite and > 0 with h * inv_h = 1", who);
+  if ((int64_t)N * K * P > INT_MAX) return fail(MOBROB_ERR_INVALID, "%s: n_robots * max_waypoints * pos_dim must fit an int32", who);
+  if (const int rc = plan_clear_check_resident(who, e, spec)) return rc;
+  if (!scene && S > 1) return fail(MOBROB_ERR_INVALID, "%s: %d scenes need a scene index per robot", who, S);
+  for (int i = 0; scene && i < N; ++i)
+    if (scene[i] < 0 || scene[i] >= S) return fail(MOBROB_ERR_INVALID, "%s: scene[%d] = %d outside 0 .. %d", who, i, scene[i], S - 1);
+  if (const int rc = plan_check_robots(who, spec, scene, start, goal, field_of, e->plan_clear_field_goal.data(),
+                                       e->plan_clear_field_scene.data(), false))
+    return rc;
+  const int cells = G * G;
+  const PlanClearKeep keep(S, F, cells);
+  EvalCarve call;
+  const size_t o_start = call.add((size_t)N * P * 4), o_goal = call.add((size_t)N * P * 4), o_fof = call.add((size_t)N * 4),
+               o_wp = call.add((size_t)N * K * P * 4), o_nwp = call.add((size_t)N * 4), o_count = call.add((size_t)N * 4),
+               o_status = call.add((size_t)N * 4), o_cost = call.add((size_t)N * 4), o_moves = call.add((size_t)N * 4),
+               o_cmin = call.add((size_t)N * 4);
+  if (const int rc = grow_plan_buf(e, e->plan_buf, e->plan_bytes, call.total)) return rc;
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(e->plan_clear_fields + keep.occ);
+  const unsigned char* blk_dev = occ_dev;
+  if (margin == 1) {
+    unsigned char* dil_dev = reinterpret_cast<unsigned char*>(e->plan_clear_fields + keep.dil);
+    if (e->plan_clear_dil_id != e->plan_clear_id) {   // once per set of resident fields
+      const PlanDilateArgs da{G, occ_dev, dil_dev};
+      hipLaunchKernelGGL(k_plan_dilate, dim3(cdiv(cells, 256), S), dim3(256), 0, e->stream, da);
+      HIPC(hipGetLastError());
+      e->plan_clear_dil_id = e->plan_clear_id;
+    }
+    blk_dev = dil_dev;
+  }
+  const auto mine = [&](size_t off) { return e->plan_buf + off; };
+  PlanSmoothCostArgs sa{};
+  PlanPathArgs& pa = sa.c.p;
+  pa.g = PlanGrid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  pa.N = N; pa.K = K; pa.P = P;
+  float* start_dev = reinterpret_cast<float*>(mine(o_start));
+  float* goal_dev = reinterpret_cast<float*>(mine(o_goal));
+  int* fof_dev = reinterpret_cast<int*>(mine(o_fof));
+  pa.start = start_dev; pa.goal = goal_dev; pa.field_of = fof_dev;
+  pa.field_scene = reinterpret_cast<int*>(e->plan_clear_fields + keep.fscene);
+  pa.sweeps = reinterpret_cast<int*>(e->plan_clear_fields + keep.sweeps);
+  pa.occ = occ_dev;
+  pa.field = reinterpret_cast<int*>(e->plan_clear_fields + keep.field);
+  pa.wp = reinterpret_cast<float*>(mine(o_wp));
+  pa.nwp = reinterpret_cast<int*>(mine(o_nwp)); pa.count = reinterpret_cast<int*>(mine(o_count));
+  pa.status = reinterpret_cast<int*>(mine(o_status)); pa.cost = reinterpret_cast<int*>(mine(o_cost));
+  sa.c.pen = reinterpret_cast<unsigned char*>(e->plan_clear_fields + keep.pen);
+  sa.c.reach = e->plan_clear_reach; sa.c.weight = e->plan_clear_weight;
+  sa.c.clearance_min = reinterpret_cast<int*>(mine(o_cmin));
+  sa.blk = blk_dev;
+  sa.moves = reinterpret_cast<int*>(mine(o_moves));
+  HIPC(hipMemcpyAsync(start_dev, start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(goal_dev, goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(fof_dev, field_of, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
+  hipLaunchKernelGGL(k_plan_smooth_cost, dim3(N), dim3(64), 0, e->stream, sa);   // a wave per robot
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(moves_out, sa.moves, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(clearance_min_out, sa.c.clearance_min, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
 }

@@ -1494,4 +1494,294 @@ __global__ __launch_bounds__(64) void k_plan_assign(PlanAssignArgs a) {
   }
 }
 
+// ---- clearance-aware static plans (mobrob_ppo_plan_grid_clear, mobrob_ppo_plan_smooth_clear; the rule: goal_rules.grid_clearance /
+// grid_surcharge / grid_field_cost / grid_walk_cost / grid_walk_clearance) ---------------------------------------------------------
+// Entering the free cell c' costs the move plus pen[c'] = weight * max(0, reach + 1 - clearance[c']), clearance the Chebyshev distance
+// in cells to the nearest blocked cell of the grid.  The kernels above are not touched: plan_tail and plan_step have their cost
+// inside their loops, so the relaxation, the step and the two walk bodies are restated here with the surcharge in them (as
+// follow_env_step and k_plan_team_rounds restate theirs), and the move mask with them (plan_moves_bytes: why, there); plan_los, plan_emit,
+// plan_close, plan_give_up and plan_result are the ones above.
+constexpr int kPlanClearReachMax = 8;
+constexpr int kPlanClearWeightMax = 16;     // the largest surcharge, 16 * 8 = 128, fits a byte
+constexpr unsigned char kPlanClearNone = 255;   // in a clearance map: no round has reached the cell yet
+
+struct PlanSurchargeArgs {
+  int G, reach, weight;
+  const unsigned char* occ;   // [S][G][G]
+  unsigned char* pen;         // [S][G][G] out: the surcharge of entering the cell, 0 on blocked cells
+};
+
+// One workgroup per scene, 1024 threads, two byte maps of the scene in LDS (32 KB at 128 cells).  A map holds per cell the round that
+// reached it: 0 blocked, kPlanClearNone not yet.  Round r = 1 .. reach writes `nxt` from `cur` alone: a cell not yet reached with a
+// reached cell in its 3 x 3 neighbourhood (cells outside the grid count as free) records r -- its Chebyshev distance to the nearest
+// blocked cell.  One barrier a round puts nxt's stores before the next round's loads, and the map the next round overwrites was last
+// read before that barrier.
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_surcharge(PlanSurchargeArgs a) {
+  __shared__ unsigned char plan_clear_lds[2 * 128 * 128];
+  const int G = a.G, cells = G * G, tid = threadIdx.x, gs = 31 - __clz(G), gm = G - 1;
+  const unsigned char* occ = a.occ + (size_t)blockIdx.x * cells;
+  unsigned char* cur = plan_clear_lds;
+  unsigned char* nxt = plan_clear_lds + cells;
+  for (int c = tid; c < cells; c += kPlanFieldThreads) cur[c] = occ[c] ? 0 : kPlanClearNone;
+  __syncthreads();
+  for (int r = 1; r <= a.reach; ++r) {
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      unsigned char v = cur[c];
+      if (v == kPlanClearNone) {
+        const int ix = c & gm, iy = c >> gs;
+        bool reached = false;
+        for (int y = max(iy - 1, 0); y <= min(iy + 1, G - 1); ++y)
+          for (int x = max(ix - 1, 0); x <= min(ix + 1, G - 1); ++x) reached |= cur[y * G + x] != kPlanClearNone;
+        if (reached) v = (unsigned char)r;
+      }
+      nxt[c] = v;
+    }
+    __syncthreads();
+    unsigned char* const swap = cur; cur = nxt; nxt = swap;
+  }
+  unsigned char* pen = a.pen + (size_t)blockIdx.x * cells;
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    const int v = cur[c];   // 0 blocked, 1 .. reach, kPlanClearNone: beyond reach, no surcharge
+    pen[c] = (v == 0 || v == kPlanClearNone) ? 0 : (unsigned char)(a.weight * (a.reach + 1 - v));
+  }
+}
+
+struct PlanFieldCostArgs {
+  int G;
+  const unsigned char* occ;   // [S][G][G]
+  const unsigned char* pen;   // [S][G][G] k_plan_surcharge's
+  const int* field_goal;      // [F] goal cell
+  const int* field_scene;     // [F]
+  int* field;                 // [F][G][G] out: cost-to-go with surcharges, -1 blocked or unreachable
+  int* sweeps;                // [F] out: sweeps run (the last one changed nothing), -1: the bound of G * G was hit
+};
+
+// plan_moves on occupancy bytes, restated without the predicate: instantiating plan_moves and plan_tail once more over plan_unblocked's
+// lambda changed the compiled code of k_plan_field_time and of the team kernels' fields and walks (the register allocation, an
+// instruction here and there), and the kernels above stay instruction for instruction what they were
+__device__ __forceinline__ unsigned plan_moves_bytes(const unsigned char* occ, int G, int ix, int iy) {
+  const int c = iy * G + ix;
+  unsigned free4 = 0;   // E, N, W, S
+  if (ix + 1 < G && !occ[c + 1]) free4 |= 1u;
+  if (iy + 1 < G && !occ[c + G]) free4 |= 2u;
+  if (ix > 0 && !occ[c - 1]) free4 |= 4u;
+  if (iy > 0 && !occ[c - G]) free4 |= 8u;
+  unsigned m = free4;
+  if ((free4 & 3u) == 3u && !occ[c + G + 1]) m |= 16u;     // NE: E and N free
+  if ((free4 & 6u) == 6u && !occ[c + G - 1]) m |= 32u;     // NW: N and W
+  if ((free4 & 12u) == 12u && !occ[c - G - 1]) m |= 64u;   // SW: W and S
+  if ((free4 & 9u) == 9u && !occ[c - G + 1]) m |= 128u;    // SE: S and E
+  return m;
+}
+
+// LDS bytes of k_plan_field_cost: the field, one byte of moves and one byte of surcharge per cell (96 KB at 128 cells)
+inline size_t plan_field_cost_lds_bytes(int G) { return (size_t)G * G * (sizeof(int) + 2); }
+
+// plan_tail with the surcharge of the cell moved into: d[c] = min(d[nb] + w + pen[nb]).  plan_tail's argument holds as it stands: every
+// value ever stored in d is the cost of a real path to the goal under these costs and values only decrease, so the in-place sweeps end
+// in the fixed point, whatever the order; the bound of G * G sweeps stays.  `pen_scene` is the scene's map in global memory, staged
+// into `pen` here, each cell by the thread that owns it, before the first barrier.
+__device__ __forceinline__ int plan_tail_cost(int* d, unsigned char* moves, unsigned char* pen, const unsigned char* pen_scene,
+                                              const unsigned char* occ, int goal, int G) {
+  const int cells = G * G, tid = threadIdx.x, gs = 31 - __clz(G), gm = G - 1;
+#pragma unroll 1
+  for (int c = tid; c < cells; c += kPlanFieldThreads) {
+    const bool blocked = occ[c] != 0;
+    moves[c] = blocked ? 0 : (unsigned char)plan_moves_bytes(occ, G, c & gm, c >> gs);
+    pen[c] = pen_scene[c];
+    d[c] = (c == goal && !blocked) ? 0 : kPlanInf;
+  }
+  __syncthreads();
+  for (int sweep = 1; sweep <= cells; ++sweep) {   // the hard bound: a field that needs more is reported, not waited for
+    int changed = 0;
+#pragma unroll 1
+    for (int c = tid; c < cells; c += kPlanFieldThreads) {
+      const unsigned m = moves[c];
+      if (m == 0 || c == goal) continue;
+      const int cur = d[c];
+      int best = cur;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (m & (1u << k)) {
+          const int nb = c + plan_dy(k) * G + plan_dx(k);
+          best = min(best, d[nb] + plan_w(k) + (int)pen[nb]);   // kPlanInf + 7 + 128 stays an int
+        }
+      if (best < cur) { d[c] = best; changed = 1; }
+    }
+    __syncthreads();   // this sweep's stores before the next sweep's loads
+    if (!__syncthreads_or(changed)) return sweep;
+  }
+  return -1;
+}
+
+// One workgroup per field, 1024 threads: plan_tail_cost on the scene's map and surcharges.
+__global__ __launch_bounds__(kPlanFieldThreads) void k_plan_field_cost(PlanFieldCostArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int plan_field_cost_lds[];
+  const int f = blockIdx.x, G = a.G, cells = G * G, tid = threadIdx.x;
+  int* d = plan_field_cost_lds;
+  unsigned char* moves = reinterpret_cast<unsigned char*>(plan_field_cost_lds + cells);
+  unsigned char* pen = moves + cells;
+  const size_t scene_off = (size_t)a.field_scene[f] * cells;
+  const int sweeps = plan_tail_cost(d, moves, pen, a.pen + scene_off, a.occ + scene_off, a.field_goal[f], G);
+  int* out = a.field + (size_t)f * cells;
+  for (int c = tid; c < cells; c += kPlanFieldThreads) out[c] = d[c] >= kPlanInf ? -1 : d[c];
+  if (tid == 0) a.sweeps[f] = sweeps;
+}
+
+// plan_step on a cost field: to a neighbour with d[nb] + w + pen[nb] == dc, the previous direction first, else the lowest index; -1:
+// none (d is not the cost field of these moves and surcharges).  The field holds only -1 or finite costs.
+__device__ __forceinline__ int plan_step_cost(unsigned m, int dc, const int* d, const unsigned char* pen, int G, int c, int prev) {
+  const auto fits = [dc, d, pen](int nb, int w) { const int v = d[nb]; return v >= 0 && v + w + (int)pen[nb] == dc; };
+  int dir = -1;
+  for (int k = 7; k >= 0; --k)   // descending: the lowest qualifying index is kept
+    if ((m & (1u << k)) && fits(c + plan_dy(k) * G + plan_dx(k), plan_w(k))) dir = k;
+  if (prev >= 0 && (m & (1u << prev)) && fits(c + plan_dy(prev) * G + plan_dx(prev), plan_w(prev))) dir = prev;
+  return dir;
+}
+
+struct PlanPathCostArgs {
+  PlanPathArgs p;             // k_plan_path's inputs and outputs; field: k_plan_field_cost's
+  const unsigned char* pen;   // [S][G][G]
+  int reach, weight;
+  int* clearance_min;         // [N] out: the least clearance (capped at reach + 1) over the cells entered, -1 without a walk
+};
+
+// the clearance of the walk's worst cell from its surcharge (a walk enters free cells only: pen = weight * (reach + 1 - clearance))
+__device__ __forceinline__ int plan_clearance_of(int worst_pen, int reach, int weight) { return reach + 1 - worst_pen / weight; }
+
+// Robot n's walk on a cost field, by one thread: plan_path<false> with plan_step_cost, and the largest surcharge met on the way
+__device__ __forceinline__ void plan_path_cost(const PlanPathCostArgs& s, int n) {
+  const PlanPathArgs& a = s.p;
+  const int G = a.g.G, cells = G * G, P = a.P, K = a.K;
+  const int f = a.field_of[n];
+  const size_t scene_off = (size_t)a.field_scene[f] * cells;
+  const unsigned char* occ = a.occ + scene_off;
+  const unsigned char* pen = s.pen + scene_off;
+  const int* d = a.field + (size_t)f * cells;
+  const float* st = a.start + (size_t)n * P;
+  const float* gl = a.goal + (size_t)n * P;
+  float* wp = a.wp + (size_t)n * K * P;
+  int ix = plan_cell(a.g, st[0]), iy = plan_cell(a.g, st[1]);
+  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
+  int count = 0, status = kPlanned, cost = -1, acts = 0, worst = 0;
+  if (a.sweeps[f] < 0) {
+    status = kPlanUnconverged;
+  } else if (d[iy * G + ix] < 0) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d[iy * G + ix];
+    int prev = -1;
+    while (ix != gx || iy != gy) {
+      if (acts >= cells) { status = kPlanUnconverged; break; }
+      const int c = iy * G + ix;
+      const int dir = plan_step_cost(plan_moves_bytes(occ, G, ix, iy), d[c], d, pen, G, c, prev);
+      if (dir < 0) { status = kPlanUnconverged; break; }   // not a field of these maps: cannot happen after a converged field kernel
+      ++acts;
+      if (prev >= 0 && dir != prev) {
+        plan_emit(wp, count, K, P, a.g, ix, iy, gl, true);
+        ++count;
+      }
+      ix += plan_dx(dir); iy += plan_dy(dir);
+      worst = max(worst, (int)pen[iy * G + ix]);
+      prev = dir;
+    }
+    if (status == kPlanned) status = plan_close(wp, count, K, P, gl, true);
+  }
+  if (status == kPlanUnconverged) plan_give_up(wp, count, cost, K, P);
+  plan_result(a.nwp + n, a.count + n, a.status + n, a.cost + n, count, K, status, cost);
+  s.clearance_min[n] = (status == kPlanned || status == kPlanTruncated) ? plan_clearance_of(worst, s.reach, s.weight) : -1;
+}
+
+// one thread per robot, 256 to a workgroup
+__global__ __launch_bounds__(256) void k_plan_path_cost(PlanPathCostArgs s) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n < s.p.N) plan_path_cost(s, n);
+}
+
+struct PlanSmoothCostArgs {
+  PlanPathCostArgs c;
+  const unsigned char* blk;   // [S][G][G] cells that are not clear: occ (margin 0) or k_plan_dilate's map (margin 1)
+  int* moves;                 // [N] out: moves of the walk, 0 where none was made
+};
+
+// Robot blockIdx.x's smoothed plan on a cost field, by one wave: plan_smooth<false> -- the ring of kPlanRing cells indexed by action,
+// the window of 64 candidates tested against the anchor at once, the ballot, the wave-level fences and every bound as stated there --
+// with plan_step_cost for the walk and the largest surcharge met on the way.  The sight lines never read costs.
+__global__ __launch_bounds__(64) void k_plan_smooth_cost(PlanSmoothCostArgs s) {
+  __shared__ unsigned short ring[kPlanRing];
+  const PlanPathArgs& a = s.c.p;
+  const int n = blockIdx.x, lane = threadIdx.x;
+  const int G = a.g.G, cells = G * G, P = a.P, K = a.K;
+  const int f = a.field_of[n];
+  const size_t scene_off = (size_t)a.field_scene[f] * cells;
+  const unsigned char* occ = a.occ + scene_off;
+  const unsigned char* pen = s.c.pen + scene_off;
+  const int* d = a.field + (size_t)f * cells;
+  const float* st = a.start + (size_t)n * P;
+  const float* gl = a.goal + (size_t)n * P;
+  float* wp = a.wp + (size_t)n * K * P;
+  int wx = plan_cell(a.g, st[0]), wy = plan_cell(a.g, st[1]);   // the walker
+  const int gx = plan_cell(a.g, gl[0]), gy = plan_cell(a.g, gl[1]);
+  int count = 0, status = kPlanned, cost = -1, walked = 1, moves = 0, worst = 0;   // walked: cells c[0 .. walked - 1] are known
+  if (a.sweeps[f] < 0) {
+    status = kPlanUnconverged;
+  } else if (d[wy * G + wx] < 0) {
+    status = kPlanUnreachable;
+  } else {
+    cost = d[wy * G + wx];
+    int ax = wx, ay = wy, base = 2, prev = -1;   // the anchor's cell
+    bool done = wx == gx && wy == gy;
+    if (lane == 0) ring[0] = (unsigned short)(wy * 128 + wx);
+    for (int round = 0;; ++round) {
+      if (round > cells) { status = kPlanUnconverged; break; }
+      while (!done && walked <= base + 63) {   // the walk, up to the end of the window
+        if (walked > cells) { status = kPlanUnconverged; break; }
+        const int c = wy * G + wx;
+        const int dir = plan_step_cost(plan_moves_bytes(occ, G, wx, wy), d[c], d, pen, G, c, prev);
+        if (dir < 0) { status = kPlanUnconverged; break; }
+        wx += plan_dx(dir); wy += plan_dy(dir);
+        worst = max(worst, (int)pen[wy * G + wx]);
+        prev = dir;
+        ++moves;
+        if (lane == 0) ring[walked & (kPlanRing - 1)] = (unsigned short)(wy * 128 + wx);
+        ++walked;
+        done = wx == gx && wy == gy;
+      }
+      if (status != kPlanned) break;
+      if (done && base >= walked) break;   // no candidate left
+      // lane 0's stores to the ring before every lane's loads from it
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const int idx = base + lane;
+      bool hidden = false;
+      if (idx < walked) {
+        const int c = ring[idx & (kPlanRing - 1)];
+        hidden = !plan_los(plan_blocked(s.blk + scene_off), G, ax, ay, c & 127, c >> 7);
+      }
+      const unsigned long long fails = __ballot(hidden);
+      if (fails == 0) { base += 64; continue; }
+      const int j = base + __builtin_ctzll(fails) - 1;   // the last visible index: emitted, the next anchor
+      const int c = __builtin_amdgcn_readfirstlane((int)ring[j & (kPlanRing - 1)]);
+      ax = c & 127; ay = c >> 7;
+      plan_emit(wp, count, K, P, a.g, ax, ay, gl, lane == 0);
+      ++count;
+      base = j + 2;
+      // the loads above before the walk's next stores to the ring
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (status == kPlanned) status = plan_close(wp, count, K, P, gl, lane == 0);
+  }
+  if (lane != 0) return;
+  if (status == kPlanUnconverged) {
+    plan_give_up(wp, count, cost, K, P);
+    moves = 0;
+  }
+  plan_result(a.nwp + n, a.count + n, a.status + n, a.cost + n, count, K, status, cost);
+  s.moves[n] = moves;
+  s.c.clearance_min[n] = (status == kPlanned || status == kPlanTruncated) ? plan_clearance_of(worst, s.c.reach, s.c.weight) : -1;
+}
+
 }  // namespace mobrob

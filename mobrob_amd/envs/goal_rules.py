@@ -803,18 +803,19 @@ def grid_walk(field, occ_scene, spec, start_xy, goal_xy):
     return cells, dirs, PLANNED
 
 
-def grid_path(field, occ_scene, spec, start_xy, goal_xy, K):
+def grid_path(field, occ_scene, spec, start_xy, goal_xy, K, walk=None):
     """One robot's waypoints -> (waypoints [K][2] float32, count, status, cost).  The walk starts in the start's cell and steps to
     a neighbour nb with field[nb] + w == field[c] under plan_move_ok: the previous direction if it qualifies, else the lowest index
     of PLAN_DIRS.  A cell's centre is a waypoint when the direction leaving it differs from the direction entering it (the start
     cell emits nothing); the last waypoint is goal_xy itself.  count: the waypoints of the full path; the first min(count, K)
     are written, the other slots are zero.  status PLANNED, UNREACHABLE (start or goal cell blocked, or no path: count 0, cost
-    -1) or TRUNCATED (count > K).  cost = field[start cell].  A start in the goal's cell gives the single waypoint goal_xy."""
+    -1) or TRUNCATED (count > K).  cost = field[start cell].  A start in the goal's cell gives the single waypoint goal_xy.
+    walk: the (cells, directions, status) to take the waypoints from, None: grid_walk's."""
     K = int(K)
     if K < 1:
         raise ValueError("max_waypoints must be >= 1")
     wp = np.zeros((K, 2), np.float32)
-    cells, dirs, status = grid_walk(field, occ_scene, spec, start_xy, goal_xy)
+    cells, dirs, status = grid_walk(field, occ_scene, spec, start_xy, goal_xy) if walk is None else walk
     if status == UNREACHABLE:
         return wp, 0, UNREACHABLE, -1
     count = 0
@@ -913,15 +914,15 @@ def grid_smooth(cells, occ, margin=1, blocked=None):
     return out
 
 
-def grid_path_smooth(field, occ_scene, spec, start_xy, goal_xy, K, margin=1, blocked=None):
+def grid_path_smooth(field, occ_scene, spec, start_xy, goal_xy, K, margin=1, blocked=None, walk=None):
     """grid_path with line-of-sight smoothing -> (waypoints [K][2] float32, count, status, cost, moves): the waypoints are the
     centres of the cells grid_smooth keeps of the walk, then goal_xy itself; count, status, cost and the zeroed slots mean what
-    they mean in grid_path; moves = L, the moves of the walk (0 where none was made)."""
+    they mean in grid_path; moves = L, the moves of the walk (0 where none was made).  walk: as grid_path's."""
     K = int(K)
     if K < 1:
         raise ValueError("max_waypoints must be >= 1")
     wp = np.zeros((K, 2), np.float32)
-    cells, _, status = grid_walk(field, occ_scene, spec, start_xy, goal_xy)
+    cells, _, status = grid_walk(field, occ_scene, spec, start_xy, goal_xy) if walk is None else walk
     if status == UNREACHABLE:
         return wp, 0, UNREACHABLE, -1, 0
     keep = grid_smooth(cells, occ_scene, margin, blocked)
@@ -935,28 +936,43 @@ def grid_path_smooth(field, occ_scene, spec, start_xy, goal_xy, K, margin=1, blo
     return wp, count, TRUNCATED if count > K else PLANNED, int(np.asarray(field)[sy, sx]), len(cells) - 1
 
 
-def grid_plan(spec, walls, hazards, start, goal, K, occupancy=None, fields=None, smooth=False, margin=1):
+def grid_plan(spec, walls, hazards, start, goal, K, occupancy=None, fields=None, smooth=False, margin=1, clearance=None):
     """The whole plan of n robots by the rule: start, goal [n][P] (P = 2 or 3) -> dict of waypoints [n][K][P] float32 (z of every
     waypoint: the goal's), n_waypoints, count, status, cost [n] int32, occupancy bool [S][G][G], fields int32 [F][G][G], field_of,
     field_goal_cell, field_scene.  `occupancy` / `fields`: a previous call's, reused (the same scene and goals).  smooth: the
-    paths by grid_path_smooth with the line-of-sight `margin` (0 or 1), and `moves` [n] int32 beside them."""
+    paths by grid_path_smooth with the line-of-sight `margin` (0 or 1), and `moves` [n] int32 beside them.
+    clearance: None, or (reach, weight): the clearance-aware plan (grid_surcharge, grid_field_cost, grid_walk_cost below) --
+    `fields` are then cost fields with the surcharges in them (reuse only such a call's), `cost` includes the surcharges paid, and
+    the dict gains surcharge uint8 [S][G][G] and clearance_min [n] int32 (grid_walk_clearance)."""
     start, goal = np.asarray(start, np.float32), np.asarray(goal, np.float32)
     n, P = goal.shape
     _, scene = plan_scene(walls, hazards)
+    if clearance is not None:
+        reach, weight = plan_clearance_check(clearance)
     occ = grid_occupancy(spec, walls, hazards) if occupancy is None else occupancy
     field_of, fcell, fscene = plan_fields(spec, occ, scene, goal)
-    if fields is None:
+    if clearance is not None:
+        clear = np.stack([grid_clearance(occ[s], reach) for s in range(len(occ))])
+        pen = np.stack([grid_surcharge(occ[s], reach, weight) for s in range(len(occ))])
+        clearance_min = np.full(n, -1, np.int32)
+    if fields is None and clearance is None:
         fields = np.stack([grid_field(occ[fscene[f]], fcell[f]) for f in range(len(fcell))])
+    elif fields is None:
+        fields = np.stack([grid_field_cost(occ[fscene[f]], pen[fscene[f]], fcell[f]) for f in range(len(fcell))])
     wp, count, status, cost = np.zeros((n, K, P), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
     moves = np.zeros(n, np.int32)
     blocked = [los_blocked(occ[s], margin) for s in range(len(occ))] if smooth else None
     for i in range(n):
         f = field_of[i]
+        walk = None
+        if clearance is not None:
+            walk = grid_walk_cost(fields[f], occ[fscene[f]], pen[fscene[f]], spec, start[i], goal[i])
+            clearance_min[i] = grid_walk_clearance(walk, clear[fscene[f]], reach)
         if smooth:
             w, count[i], status[i], cost[i], moves[i] = grid_path_smooth(fields[f], occ[fscene[f]], spec, start[i], goal[i], K, margin,
-                                                                         blocked[fscene[f]])
+                                                                         blocked[fscene[f]], walk)
         else:
-            w, count[i], status[i], cost[i] = grid_path(fields[f], occ[fscene[f]], spec, start[i], goal[i], K)
+            w, count[i], status[i], cost[i] = grid_path(fields[f], occ[fscene[f]], spec, start[i], goal[i], K, walk)
         m = min(int(count[i]), K)
         wp[i, :m, :2] = w[:m]
         wp[i, :m, 2:] = goal[i, 2:]
@@ -964,6 +980,135 @@ def grid_plan(spec, walls, hazards, start, goal, K, occupancy=None, fields=None,
            "occupancy": occ, "fields": fields, "field_of": field_of, "field_goal_cell": fcell, "field_scene": fscene}
     if smooth:
         out["moves"] = moves
+    if clearance is not None:
+        out["surcharge"], out["clearance_min"] = pen, clearance_min
+    return out
+
+
+# ---- clearance-aware plans: a per-cell surcharge near blocked cells.  This project's own rule, all integers; the
+# device (csrc/kernels_plan.h: k_plan_surcharge, k_plan_field_cost, k_plan_path_cost, k_plan_smooth_cost) is held to it bit for bit.
+# Entering a free cell c' costs the move plus pen[c'] = weight * max(0, reach + 1 - clearance[c']), where clearance is the Chebyshev
+# distance in cells to the nearest blocked cell of the grid.  NOT promised: the plan is no longer the shortest; a doorway narrower
+# than 2 * reach cells is still used (its surcharge is simply paid); `cost` includes the surcharges paid, `moves` stays the walk's
+# length.  Only the static plan takes surcharges.
+PLAN_CLEAR_REACH_MAX = 8
+PLAN_CLEAR_WEIGHT_MAX = 16    # the largest surcharge is 16 * 8 = 128: a byte; a path costs at most G * G * (7 + 128), far below 2^30
+
+
+def plan_clearance_check(clearance):
+    """(reach, weight) -> the two as ints: reach 1 .. PLAN_CLEAR_REACH_MAX, weight 1 .. PLAN_CLEAR_WEIGHT_MAX, integers and not bools
+    (ValueError naming `clearance` otherwise)"""
+    try:
+        reach, weight = clearance
+    except (TypeError, ValueError):
+        raise ValueError(f"clearance must be None or (reach, weight), got {clearance!r}") from None
+    for name, v, top in (("reach", reach, PLAN_CLEAR_REACH_MAX), ("weight", weight, PLAN_CLEAR_WEIGHT_MAX)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
+            raise ValueError(f"clearance {name} must be an integer in 1 .. {top}, got {v!r}")
+    return int(reach), int(weight)
+
+
+def grid_clearance(occ_scene, reach):
+    """uint8 [G][G]: the Chebyshev distance in cells to the nearest blocked cell of the grid, capped at reach + 1; blocked cells are 0;
+    cells outside the grid count as free, as in grid_dilate.  `reach` rounds of grid_dilate: a cell's clearance is the first round
+    that reaches it."""
+    reach = plan_clearance_check((reach, 1))[0]
+    grown = np.asarray(occ_scene, bool)
+    out = np.where(grown, 0, reach + 1).astype(np.uint8)
+    for r in range(1, reach + 1):
+        nxt = grid_dilate(grown)
+        out[nxt & ~grown] = r
+        grown = nxt
+    return out
+
+
+def grid_surcharge(occ_scene, reach, weight):
+    """uint8 [G][G]: weight * max(0, reach + 1 - grid_clearance) on free cells, 0 on blocked ones"""
+    reach, weight = plan_clearance_check((reach, weight))
+    clear = grid_clearance(occ_scene, reach).astype(np.int64)
+    return np.where(np.asarray(occ_scene, bool), 0, weight * np.maximum(0, reach + 1 - clear)).astype(np.uint8)
+
+
+def grid_field_cost(occ_scene, pen, goal_cell):
+    """grid_field with the cost of a move k from c into c' being PLAN_STEP | PLAN_DIAG plus pen[c'] (pen uint8 [G][G]): int32 [G][G],
+    the unique fixed point of d[c] = min_k(w(k) + pen[c'] + d[c']) under plan_move_ok with d[goal] = 0; -1 for blocked and
+    unreachable cells, all -1 for a blocked goal cell.  The goal cell's own surcharge is paid on entry like any cell's; the cell a
+    path starts in is never paid for.  Dijkstra from the goal: a cell c popped with d[c] offers d[c] + w + pen[c] to its neighbours
+    (plan_move_ok is symmetric in the two cells)."""
+    import heapq
+    occ, pen = np.asarray(occ_scene, bool), np.asarray(pen).astype(np.int64)
+    G = occ.shape[0]
+    d = np.full((G, G), -1, np.int32)
+    gx, gy = int(goal_cell) % G, int(goal_cell) // G
+    if not 0 <= int(goal_cell) < G * G:
+        raise ValueError(f"goal cell must lie in 0 .. {G * G - 1}, got {goal_cell}")
+    if occ[gy, gx]:
+        return d
+    d[gy, gx] = 0
+    heap = [(0, gy, gx)]
+    while heap:
+        dc, iy, ix = heapq.heappop(heap)
+        if dc != d[iy, ix]:
+            continue
+        for k, (dx, dy) in enumerate(PLAN_DIRS):
+            if plan_move_ok(occ, ix, iy, k):
+                nd = dc + (PLAN_STEP if k < 4 else PLAN_DIAG) + int(pen[iy, ix])
+                if d[iy + dy, ix + dx] < 0 or nd < d[iy + dy, ix + dx]:
+                    d[iy + dy, ix + dx] = nd
+                    heapq.heappush(heap, (nd, iy + dy, ix + dx))
+    return d
+
+
+def grid_walk_cost(field, occ_scene, pen, spec, start_xy, goal_xy):
+    """grid_walk on a grid_field_cost field: the step goes to the allowed neighbour c' that minimises w(k) + pen[c'] + field[c'] --
+    on such a field that minimum is field[c] -- under grid_walk's tie order: the previous direction if it attains it, else the
+    lowest index of PLAN_DIRS -> (cells, directions, status) as grid_walk's."""
+    occ, d, pen = np.asarray(occ_scene, bool), np.asarray(field), np.asarray(pen).astype(np.int64)
+    G = spec.cells
+    sx, sy = (int(v) for v in spec.cell_of(np.asarray(start_xy, np.float32)[:2]))
+    gx, gy = (int(v) for v in spec.cell_of(np.asarray(goal_xy, np.float32)[:2]))
+    if occ[sy, sx] or occ[gy, gx] or d[sy, sx] < 0:
+        return [], [], UNREACHABLE
+    cells, dirs, prev = [(sx, sy)], [], -1
+    ix, iy = sx, sy
+    while (ix, iy) != (gx, gy):
+        def descends(k):
+            jx, jy = ix + PLAN_DIRS[k][0], iy + PLAN_DIRS[k][1]
+            return plan_move_ok(occ, ix, iy, k) and d[jy, jx] >= 0 and \
+                d[jy, jx] + (PLAN_STEP if k < 4 else PLAN_DIAG) + pen[jy, jx] == d[iy, ix]
+        k = prev if prev >= 0 and descends(prev) else next((j for j in range(8) if descends(j)), -1)
+        if k < 0 or len(cells) > G * G:
+            raise ValueError("grid_path_cost: the field is not the cost-to-go of this occupancy, surcharge and goal")
+        ix, iy, prev = ix + PLAN_DIRS[k][0], iy + PLAN_DIRS[k][1], k
+        cells.append((ix, iy))
+        dirs.append(k)
+    return cells, dirs, PLANNED
+
+
+def grid_path_cost(field, occ_scene, pen, spec, start_xy, goal_xy, K):
+    """grid_path on grid_walk_cost's walk: count, TRUNCATED, UNREACHABLE, the zeroed slots mean what they mean there; cost =
+    field[start cell], the moves of the walk plus the surcharges of the cells it enters."""
+    return grid_path(field, occ_scene, spec, start_xy, goal_xy, K, grid_walk_cost(field, occ_scene, pen, spec, start_xy, goal_xy))
+
+
+def grid_walk_clearance(walk, clear, reach):
+    """The least clearance (grid_clearance's map `clear`, capped at reach + 1) over the cells of a walk after its start cell; reach +
+    1, the cap, for a walk of no moves (the start lies in the goal's cell); -1 without a walk (UNREACHABLE)."""
+    cells, _, status = walk
+    if status == UNREACHABLE:
+        return -1
+    return min([int(reach) + 1] + [int(clear[y, x]) for x, y in cells[1:]])
+
+
+def grid_plan_clearance_min(spec, plan, start, goal, reach):
+    """clearance_min [n] int32 of a PLAIN plan (grid_plan's or the planner's dict with occupancy and fields in it), recomputed from
+    its walks with grid_walk_clearance: what a clearance-aware plan's clearance_min is compared with."""
+    start, goal = np.asarray(start, np.float32), np.asarray(goal, np.float32)
+    occ, out = np.asarray(plan["occupancy"], bool), np.zeros(len(goal), np.int32)
+    clear = [grid_clearance(o, reach) for o in occ]
+    for i, f in enumerate(plan["field_of"]):
+        s = plan["field_scene"][f]
+        out[i] = grid_walk_clearance(grid_walk(plan["fields"][f], occ[s], spec, start[i], goal[i]), clear[s], reach)
     return out
 
 

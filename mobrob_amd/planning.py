@@ -26,7 +26,10 @@ with the fewest parked members is the result (goal_rules.grid_plan_team_rounds; 
 assignment (`assign="sum"` or `"makespan"`): a team is given places to occupy, not a pairing -- in front of the
 team plan, every team's members and goals are matched at minimum cost on each robot's own static cost-to-go, and the plan is made
 for the assigned goals, through whichever team path the planner is configured for; `planner.assign(start, goal)` is that step on
-its own (goal_rules.grid_assign; device: mobrob_ppo_plan_assign).  Walls as solid bodies are not planned for."""
+its own (goal_rules.grid_assign; device: mobrob_ppo_plan_assign).  Clearance (`clearance=(reach, weight)`): a static
+plan that pays a surcharge for entering a cell within `reach` cells of a blocked one, so it takes the middle of a corridor where
+that costs little (goal_rules.grid_plan(..., clearance=); device: mobrob_ppo_plan_grid_clear, mobrob_ppo_plan_smooth_clear).
+Walls as solid bodies are not planned for."""
 from __future__ import annotations
 
 import numpy as np
@@ -66,11 +69,16 @@ class GridPlanner:
     assigns the goals inside each team -- the minimum-total matching of members and goals, or the one that minimises the largest
     member cost first and then the total -- on each robot's own static cost-to-go (goal_rules.grid_assign), and plans the assigned
     goals.  A team that is already paired as well as any matching keeps its pairing.  The matching does not see reservations or
-    the hazards' layers before the tail, teams are matched on their own, and a run is never reassigned."""
+    the hazards' layers before the tail, teams are matched on their own, and a run is never reassigned.
+    clearance: None, or (reach 1 .. 8, weight 1 .. 16): every plan pays weight * (reach + 1 - c) for entering a free cell whose
+    Chebyshev distance c to the nearest blocked cell is at most reach, so paths keep away from obstacles where room exists
+    (plan(..., clearance=) overrides it per call).  It belongs to static plans, plain or with smooth=: with moving hazards, teams=,
+    time_smooth= or assign= it is a ValueError.  The plan is then no longer the shortest, a doorway narrower than 2 reach cells is
+    still used (its surcharge is paid), `cost` includes the surcharges and `moves` stays the walk's length."""
 
     def __init__(self, env, walls=None, hazards=None, cells=64, inflate=None, max_waypoints=16, engine=None, extent=None,
                  smooth=False, los_margin=1, layer_steps=None, layers=None, teams=None, reserve=None, time_smooth=False, max_leg=_UNSET,
-                 retries=0, assign=None):
+                 retries=0, assign=None, clearance=None):
         from .envs.vec_env import DeviceGoalVecEnv
         if teams is not None and not isinstance(teams, rules.Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
@@ -111,6 +119,7 @@ class GridPlanner:
             raise ValueError(f"los_margin must be 0 or 1, got {los_margin!r}")
         self.smooth, self.los_margin = bool(smooth), int(los_margin)
         self.time_smooth = self._time_smooth_ok(time_smooth)
+        self.clearance = self._clearance_ok(clearance)
         self.device = isinstance(env, DeviceGoalVecEnv)
         if self.device:
             self.engine = getattr(engine, "engine", engine)
@@ -148,6 +157,16 @@ class GridPlanner:
                              "of one has no mates: plan it without teams=; a static plan takes smooth=True)")
         return bool(time_smooth)
 
+    def _clearance_ok(self, clearance):
+        """-> None or the checked (reach, weight); ValueError naming `clearance` where it is asked for on a plan that is not static"""
+        if clearance is None:
+            return None
+        for what, on in (("hazards=MovingHazards", isinstance(self.hazards, rules.MovingHazards)), ("teams=", self.teams is not None),
+                         ("time_smooth=", self.time_smooth), ("assign=", self.assign_objective is not None)):
+            if on:
+                raise ValueError(f"GridPlanner: clearance= with {what} is not supported (surcharges belong to static plans, plain or smooth=)")
+        return rules.plan_clearance_check(clearance)
+
     def _check(self, start, goal):
         start, goal = np.asarray(start, np.float64), np.asarray(goal, np.float64)
         if goal.ndim != 2 or goal.shape[1] != self.pos_dim or start.shape != goal.shape:
@@ -159,15 +178,32 @@ class GridPlanner:
                 sc.check_robots(goal.shape[0])
         return start.astype(np.float32), goal.astype(np.float32)
 
-    def _plan(self, start, goal, K, want_occupancy, want_fields, smooth=False):
+    def _plan(self, start, goal, K, want_occupancy, want_fields, smooth=False, clearance=None):
         """One call.  The fields of the previous call are reused when this call's (scene, goal cell) list is the same.  smooth:
         the paths by line of sight -- on the device a first plan computes the fields with plan_grid and smooths on them, a round
-        on unchanged goals runs k_plan_smooth alone."""
+        on unchanged goals runs k_plan_smooth alone.  clearance: (reach, weight) or None; the kept fields are reused only by a call
+        with the same clearance (the engine keeps the two families resident side by side)."""
         _, scene = rules.plan_scene(self.walls, self.hazards)
         _, fcell, fscene = rules.plan_fields(self.spec, None, scene, goal)
         kept = self._kept
-        same = kept is not None and np.array_equal(kept["field_goal_cell"], fcell) and np.array_equal(kept["field_scene"], fscene)
-        if self.device:
+        same = kept is not None and np.array_equal(kept["field_goal_cell"], fcell) and np.array_equal(kept["field_scene"], fscene) and \
+            kept.get("clearance") == clearance
+        if self.device and clearance is not None:
+            reuse = kept if same and not (want_occupancy or want_fields) and \
+                kept["fields_id"] == getattr(self.engine, "_plan_clear_resident", None) else None
+            if smooth and reuse is not None:
+                out = dict(kept)
+            else:
+                out = self.engine.plan_grid_clear(self.spec, self.walls, self.hazards, clearance=clearance, start=start, goal=goal,
+                                                  max_waypoints=K, want_occupancy=want_occupancy, want_fields=want_fields, reuse=reuse)
+                self.engine._plan_clear_resident = out["fields_id"]
+                if reuse is not None:
+                    out["sweeps"] = kept["sweeps"]
+            if smooth:
+                out.update(self.engine.plan_smooth_clear(self.spec, reuse=out, start=start, goal=goal, scene=scene, max_waypoints=K,
+                                                         margin=self.los_margin))
+            out["fields_reused"] = reuse is not None
+        elif self.device:
             reuse = kept if same and not (want_occupancy or want_fields) and kept["fields_id"] == getattr(self.engine, "_plan_resident", None) else None
             if smooth and reuse is not None:
                 out = dict(kept)
@@ -183,8 +219,10 @@ class GridPlanner:
             out["fields_reused"] = reuse is not None
         else:
             out = rules.grid_plan(self.spec, self.walls, self.hazards, start, goal, K, kept["occupancy"] if same else None,
-                                  kept["fields"] if same else None, smooth=smooth, margin=self.los_margin)
+                                  kept["fields"] if same else None, smooth=smooth, margin=self.los_margin, clearance=clearance)
             out["fields_reused"] = bool(same)
+            if clearance is not None:
+                out["clearance"] = clearance
         if not smooth:
             out.pop("moves", None)
         self._kept = out
@@ -236,7 +274,8 @@ class GridPlanner:
             return self.engine.plan_assign(self.spec, self.walls, self.hazards, teams=self.teams, start=start, goal=goal, **kw)
         return rules.grid_assign(self.spec, self.walls, self.hazards, start, goal, self.teams, **kw)
 
-    def plan(self, start, goal, step0=0, *, grow=False, want_occupancy=False, want_fields=False, smooth=None, time_smooth=None):
+    def plan(self, start, goal, step0=0, *, grow=False, want_occupancy=False, want_fields=False, smooth=None, time_smooth=None,
+             clearance=_UNSET):
         """start, goal [n][P] -> dict: waypoints [n][K][P] float32 (z: the goal's), n_waypoints [n] (= min(count, K)), count [n]
         waypoints of the full path, status [n] (goal_rules.PLANNED 0, UNREACHABLE 1, TRUNCATED 2; UNCONVERGED 3: a device loop hit
         its bound), cost [n] int32 (-1: unreachable), cost_distance [n] float64 = cost * h / 5 (NaN: unreachable), field_of [n],
@@ -262,7 +301,11 @@ class GridPlanner:
         With the planner's assign= the goals are first assigned inside every team (`assign`), the plan is made for the assigned
         goals -- `grow` plans the same assignment again -- and the dict gains goal_rules.ASSIGN_KEYS: assign [n], goal [n][P] (the
         goals the plan was made for: hand THESE to `callback` and to the tracker), assign_cost [n], assign_total, assign_max,
-        assign_identity_total, assign_identity_max, assign_changed and assign_status [n_teams]."""
+        assign_identity_total, assign_identity_max, assign_changed and assign_status [n_teams].
+        clearance: not given (the planner's setting), None or (reach, weight): the clearance-aware static plan, plain or smoothed;
+        the dict then gains `clearance` and clearance_min [n] int32, the least clearance in cells (capped at reach + 1) over the
+        cells each walk enters (-1: no walk); `cost` includes the surcharges paid, `fields` are the cost fields."""
+        clearance = self.clearance if clearance is _UNSET else self._clearance_ok(clearance)
         start, goal = self._check(start, goal)
         assigned = None
         if self.assign_objective is not None:
@@ -270,6 +313,8 @@ class GridPlanner:
             goal = np.ascontiguousarray(assigned["goal"], np.float32)
         smooth = self.smooth if smooth is None else bool(smooth)
         time_smooth = self.time_smooth if time_smooth is None else self._time_smooth_ok(time_smooth)
+        if clearance is not None and time_smooth:
+            raise ValueError("plan: clearance= with time_smooth= is not supported (surcharges belong to static plans, plain or smooth=)")
         if self.timed:
             if smooth:
                 raise ValueError("plan: smooth=True with moving hazards or teams: smoothing over time is not supported by smooth= "
@@ -282,9 +327,9 @@ class GridPlanner:
         else:
             if step0 != 0:
                 raise ValueError("plan: step0 belongs to moving hazards; a static plan has no clock")
-            out = self._plan(start, goal, self.K, want_occupancy, want_fields, smooth)
+            out = self._plan(start, goal, self.K, want_occupancy, want_fields, smooth, clearance)
             if grow and np.any(out["status"] == rules.TRUNCATED):
-                out = self._plan(start, goal, int(out["count"].max()), want_occupancy, want_fields, smooth)
+                out = self._plan(start, goal, int(out["count"].max()), want_occupancy, want_fields, smooth, clearance)
         res = {k: out[k] for k in ("waypoints", "n_waypoints", "count", "status", "cost", "field_of", "field_goal_cell", "field_scene",
                                    "fields_reused")}
         if self.timed:
@@ -298,6 +343,8 @@ class GridPlanner:
                 res.update({k: out[k] for k in rules.TEAM_ROUND_KEYS})
         if assigned is not None:
             res.update({k: assigned[k] for k in rules.ASSIGN_KEYS})
+        if clearance is not None:
+            res["clearance"], res["clearance_min"] = clearance, out["clearance_min"]
         res["cost_distance"] = np.where(out["cost"] >= 0, out["cost"].astype(np.float64) * float(self.spec.h) / rules.PLAN_STEP, np.nan)
         res["smoothed"], res["moves"] = smooth, out.get("moves")
         if want_occupancy:
