@@ -35,7 +35,8 @@ time a robot needs to clear a crossing is the one-line demonstration that delays
 `--walls FILE.npy` ([M][4]: centre x, y and half extents hx, hy of M axis-aligned boxes) checks every step against walls:
 contact of the robot's footprint (`--robot-radius R`, default 0.1) and crossing of the step's segment, which also sees a step that
 jumps a thin wall.  `--arena` adds the reference's turtlebot3 enclosure (four boxes, 2.98 m outside, 0.265 m thick).  Three lines
-report the contact rate, the crossing rate (robots with such a step) and the minimum clearance to a wall.  Walls block nothing.
+report the contact rate, the crossing rate (robots with such a step) and the minimum clearance to a wall.  Walls block nothing unless `--solid` is given: robots then stop and slide at them
+(goal_rules.wall_block), and two more lines report the share of robots blocked at least once and the fully stopped steps.
 
 `--goal X,Y` (X,Y,Z for a drone) PLANS the waypoints instead of reading them: a grid of `--plan-cells` (32, 64, 128; default 64)
 cells a side over the arena, blocked where --walls / --arena / --hazards are (mobrob_amd.planning.GridPlanner), one path per robot
@@ -92,7 +93,9 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
-           plan_retries=0, goals=None, assign=None, plan_clearance=None):
+           plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False):
+    if solid and walls is None and not arena:
+        raise ValueError("--solid needs --walls or --arena")
     calls = check_chain(max_steps, horizon, leg_steps)
     if goals is not None and (goal is not None or waypoints is not None):
         raise ValueError("--goals excludes --goal and --waypoints")
@@ -124,7 +127,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         boxes = np.zeros((0, 4)) if walls is None else np.asarray(walls, np.float64)
         if boxes.ndim != 2 or boxes.shape[1] != 4:
             raise ValueError(f"--walls must hold [M][4] (cx, cy, hx, hy), got shape {boxes.shape}")
-        wl = Walls(np.concatenate([boxes, Walls.enclosure()]) if arena else boxes, radius=float(robot_radius), indicator=False)
+        wl = Walls(np.concatenate([boxes, Walls.enclosure()]) if arena else boxes, radius=float(robot_radius), indicator=False, solid=bool(solid))
     n_waypoints = replan = None
     if goals is not None:
         goals = np.asarray(goals, np.float64)
@@ -211,6 +214,9 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         clear = r["min_wall_clearance"]
         print(f"wall contact rate: {float(np.mean(r['contact_steps'] > 0))}")
         print(f"wall crossing rate: {float(np.mean(r['crossing_steps'] > 0))}")
+        if solid:
+            print(f"wall blocked rate: {float(np.mean(r['wall_blocked_steps'] > 0))}")
+            print(f"wall stopped steps: {int(np.sum(r['wall_stopped_steps']))}")
         print(f"minimum wall clearance: {float(np.nanmin(clear)) if np.any(~np.isnan(clear)) else float('nan')}")
     return r
 
@@ -286,6 +292,7 @@ def build_parser():
     ap.add_argument("--separation", type=float, default=0.3, help="distance team-mates must keep")
     ap.add_argument("--release", type=str, default=None, help="[K] or [n][K] release steps of the waypoints (.npy, integers)")
     ap.add_argument("--walls", type=str, default=None, help="[M][4] boxes cx, cy, hx, hy (.npy): report wall contacts and crossings")
+    ap.add_argument("--solid", action="store_true", default=False, help="with --walls / --arena: the walls block (robots stop and slide)")
     ap.add_argument("--arena", action="store_true", default=False, help="add the reference's turtlebot3 enclosure to the walls")
     ap.add_argument("--robot-radius", type=float, default=0.1, help="the robot's footprint for wall contact")
     ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
@@ -315,4 +322,4 @@ if __name__ == "__main__":
            plan_smooth=args.plan_smooth, plan_los_margin=args.plan_los_margin, plan_layer_steps=args.plan_layer_steps,
            plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg,
            plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
-           plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")])
+           plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid)

@@ -40,7 +40,10 @@ extern "C" {
 
 /* 2: config slot `persistent_train` became `activation`, `forward_x3` added, MOBROB_K_COUNT 6 -> 7 (profile_read arrays),
  *    MOBROB_BUF_COUNT / reserved[] resized -- a binding built against 1 must not load this library
- * 3: pi_hidden_ext / vf_hidden_ext (net_arch depths 4 .. 8), use_sde, sde_sample_freq appended to the config, activation codes 2 .. 11 */
+ * 3: pi_hidden_ext / vf_hidden_ext (net_arch depths 4 .. 8), use_sde, sde_sample_freq appended to the config, activation codes 2 .. 11
+ * (entry points added since -- the latest: mobrob_ppo_follow_waypoints_solid -- change no struct and no existing entry point: a binding
+ *  built against an earlier 3 loads this library, so the number stays; a binding finds out whether a library has such an entry point by
+ *  looking the symbol up) */
 #define MOBROB_PPO_ABI_VERSION 3
 /* policy_kwargs.activation_fn (SB3 ActorCriticPolicy; the reference splats ppo_kwargs into PPO verbatim, ppo.py:58): the
  * parameter-free element-wise torch.nn modules with torch's default arguments (ELU alpha 1, LeakyReLU slope 0.01, Softplus beta 1 /
@@ -718,7 +721,7 @@ int mobrob_ppo_follow_waypoints_scheduled(mobrob_ppo_engine_t* e, const mobrob_g
 /* ---- walls: box contact and crossing checks in waypoint-following runs -----------------------------------------------------------
  * One call of a run (mobrob_ppo_follow_waypoints_scheduled, with `teams` and `schedule` optional: NULL = none, and team_out /
  * sched_out are then NULL) whose robots are checked against WALLS: axis-aligned boxes (cx, cy, hx, hy), hx, hy >= 0 half extents,
- * up to 1024 per scene, shared or per robot by a scene index exactly as mobrob_hazards_t.  The check is observational: dynamics,
+ * up to 1024 per scene, shared or per robot by a scene index exactly as mobrob_hazards_t.  The check is observational (solid walls: mobrob_ppo_follow_waypoints_solid below): dynamics,
  * rewards, arrivals, status, hazard_out, team_out, sched_out, path and trace are the bits of the call without walls.  The rule
  * (mobrob_amd/envs/goal_rules.py: wall_check): after the step with 0-based global number g a robot that stepped has pre-step xy a
  * and post-step xy p (x and y only, for drones too; a is where the previous step ended, or the carried position).  In float32,
@@ -763,6 +766,40 @@ int mobrob_ppo_follow_waypoints_walls(mobrob_ppo_engine_t* e, const mobrob_goal_
                                       double* sched_out /* [n][2] in / out, NULL iff no schedule */,
                                       double* wall_out /* [n][7] in / out */, float* path_out /* or NULL */,
                                       float* trace_out /* or NULL */);
+
+/* ---- solid walls: robots stop and slide at the boxes ---------------------------------------------------------------------------
+ * mobrob_ppo_follow_waypoints_walls with the walls SOLID: the same arguments plus blocked_out.  Inside every environment step,
+ * between the dynamics and the goal test, the proposed position is resolved against the robot's scene (mobrob_amd/envs/
+ * goal_rules.py: wall_block).  With a the pre-step xy and p the xy the velocity update and the clamp to +-extent propose, in
+ * float32, every operation rounded on its own, Hx = hx + radius, Hy = hy + radius per wall:
+ *     a wall with |ax - cx| <= Hx and |ay - cy| <= Hy does not hold in this step (a robot that starts inside an inflated box can
+ *     leave it; such a step counts as `inside`);
+ *     seg_hit(a, c) = OR over the other walls of the crossing test above on the segment a c, with Hx, Hy for hx, hy;
+ *     candidates c0 = (px, py), c1 = (px, ay), c2 = (ax, py), c3 = (ax, ay): the first without a hit is taken (c3 untested), its
+ *     number is the step's code; the velocity component of every dropped axis becomes +0.0 (the robot pushes and slides).
+ * The reach test, reward, arrival, next waypoint, path, trace and the next observation use the resolved position; wall_out is then
+ * accounted on (a, resolved) as in the call above.  z is untouched.  Exact: a robot that never had a step `inside` has 0 crossing
+ * steps.  Up to rounding: its minimum clearance is > -1e-6 (contacts are not promised to be exactly 0).  Not promised: the robot is
+ * not placed on the wall's surface (a gap of up to one step remains); no friction, no rotation; robots do not block each other;
+ * evaluation takes no walls.
+ *   blocked_out [n][4] int32, in / out, carried like wall_out: blocked steps (code != 0), first blocked step (global, 1-based, -1 =
+ *             none), fully stopped steps (code 3), steps in which a wall did not hold.  A run starts from 0, -1, 0, 0.
+ *   kernels   k_goal64_tile / k_goal_task_step<WallTask<[HazardTask<]SolidFollowTask<ResumeFollowTask | ScheduledFollowTask>[>]>>,
+ *             with or without TeamTask around them: the resolution runs on the robot's own lane / thread inside the env step,
+ *             serially over the scene (one pass when c0 is clean, at most three), on the scene WallTask staged in LDS when shared.
+ * MOBROB_ERR_INVALID, besides every check of mobrob_ppo_follow_waypoints_walls, for: a NULL blocked_out, hazard frames (static
+ * hazards, teams and schedules compose; moving hazards do not yet), a carried blocked record no call returns. */
+int mobrob_ppo_follow_waypoints_solid(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                      const mobrob_hazards_t* hz /* or NULL */, const mobrob_hazard_frames_t* hzf /* must be NULL */,
+                                      const mobrob_follow_resume_t* resume, const mobrob_teams_t* teams /* or NULL */,
+                                      const mobrob_follow_schedule_t* schedule /* or NULL */, const mobrob_walls_t* walls,
+                                      const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                      int32_t* arrival /* [n][K] in / out */, double* robot_out /* [n][4] in / out */,
+                                      double* hazard_out /* [n][4] in / out, NULL iff no hazards */,
+                                      double* team_out /* [n][5] in / out, NULL iff no teams */,
+                                      double* sched_out /* [n][2] in / out, NULL iff no schedule */,
+                                      double* wall_out /* [n][7] in / out */, int32_t* blocked_out /* [n][4] in / out */,
+                                      float* path_out /* or NULL */, float* trace_out /* or NULL */);
 
 /* ---- grid planner: walls and hazards to waypoints ---------------------------------------------------------------------------
  * Plans waypoints for n_robots robots at once on a grid of cells x cells (32, 64 or 128) over [-extent, extent]^2, x and y only, from
@@ -841,7 +878,7 @@ int mobrob_ppo_plan_grid(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
  *             test 64 candidates against the anchor at once, a ballot and a count of trailing zeros find the first that is hidden.
  *             k_plan_dilate: the cells that are not clear at margin 1, once per set of resident fields, kept beside them.  Runs on the
  *             engine's stream in the planner's own buffers; nothing a training step reads or writes is touched.
- * Still out of scope: walls as solid bodies of the simulation.  Smoothing of a time plan: mobrob_ppo_plan_grid_time_smooth.
+ * Walls as solid bodies of the run: mobrob_ppo_follow_waypoints_solid (the planner itself is unchanged by it).  Smoothing of a time plan: mobrob_ppo_plan_grid_time_smooth.
  * Team-mates as obstacles: mobrob_ppo_plan_grid_team; smoothed: mobrob_ppo_plan_grid_team_smooth.
  * MOBROB_ERR_INVALID before any launch or copy for: a NULL argument (scene aside), margin not 0 or 1, n_robots < 1, pos_dim not 2 or 3,
  * cells not 32 / 64 / 128, max_waypoints < 1, n_fields outside 1 .. n_robots, n_scenes < 1, extent, h, inv_h not finite and > 0 or
@@ -973,7 +1010,7 @@ int mobrob_ppo_plan_grid_time(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* 
  *             lane l tests c[i] against c[base + l] on nb[min(i, T)] with the threshold min(base + l, T) (base = i + 2 at first,
  *             + 64 after a window without a hidden cell), a ballot and a count of trailing zeros find the first hidden index.  Every call computes in the time plans' own buffer and keeps nothing
  *             resident; runs on the engine's stream; nothing a training step reads or writes is touched.
- * Smoothing of a team plan: mobrob_ppo_plan_grid_team_smooth.  Still out of scope: walls as solid bodies.
+ * Smoothing of a team plan: mobrob_ppo_plan_grid_team_smooth.  Solid walls: mobrob_ppo_follow_waypoints_solid.
  * MOBROB_ERR_INVALID before any launch or copy for everything mobrob_ppo_plan_grid_time refuses (waits_out aside, moves_out included
  * in "a NULL argument"), and for: margin not 0 or 1, time fields plus the table of n_scenes * (layers + 1) * cells * cells * 2 bytes
  * above MOBROB_PLAN_TIME_MAX_BYTES. */

@@ -3317,6 +3317,13 @@ static int eval_prepare(mobrob_ppo_engine_t* e, const EvalCall& c, const GoalEnv
   return MOBROB_OK;
 }
 
+// The DP instance of k_goal64_tile a task runs at observation width Dp -- the one rule for the launch (eval_run) and for the LDS
+// check made before it (follow_waypoints).  Tasks with solid walls never run the 16-wide tile: the 32-wide one serves 16-wide
+// observations too (features beyond D are zero in the observation tile and in W1's fragment: the same sums).  Their 16-wide instance
+// came out of the compiler with a 20-byte private segment that no instruction touches -- not understood --, which the build's
+// audit refuses, so it is not instantiated.
+static int eval_tile_width(int Dp, bool solid) { return solid ? std::max(Dp, 32) : Dp; }
+
 // Runs the task for a.max_steps steps: k_goal64_tile on 2x64 tanh engines of the fused family (returns 1), else the per-step path
 // (returns 0): the engine's forward() in rows_max chunks + the step kernel per step, then the task's `fin` kernel if it has one.
 template <class Task>
@@ -3327,9 +3334,17 @@ static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, voi
   const bool persistent = e->fused.enabled && e->fused.H == 64 && env_int("MOBROB_EVAL_PERSISTENT", 1) != 0;
   if (persistent) {
     Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
-    size_t lds_bytes = eval64_lds_bytes(a.Dp);
-    if constexpr (Task::kWide) lds_bytes += Task::tile_lds_bytes(args);
-    FUSED_DISPATCH_DP(a.Dp, hipLaunchKernelGGL((k_goal64_tile<DPc, Task>), dim3(cdiv(N, 16)), dim3(64), lds_bytes, e->stream, args, W));
+    if constexpr (task_solid<Task>) {
+      const int Dt = eval_tile_width(a.Dp, true);   // never 16
+      const size_t lds_bytes = eval64_lds_bytes(Dt) + Task::tile_lds_bytes(args);
+      if (Dt == 32) hipLaunchKernelGGL((k_goal64_tile<32, Task>), dim3(cdiv(N, 16)), dim3(64), lds_bytes, e->stream, args, W);
+      else if (Dt == 48) hipLaunchKernelGGL((k_goal64_tile<48, Task>), dim3(cdiv(N, 16)), dim3(64), lds_bytes, e->stream, args, W);
+      else hipLaunchKernelGGL((k_goal64_tile<64, Task>), dim3(cdiv(N, 16)), dim3(64), lds_bytes, e->stream, args, W);
+    } else {
+      size_t lds_bytes = eval64_lds_bytes(a.Dp);
+      if constexpr (Task::kWide) lds_bytes += Task::tile_lds_bytes(args);
+      FUSED_DISPATCH_DP(a.Dp, hipLaunchKernelGGL((k_goal64_tile<DPc, Task>), dim3(cdiv(N, 16)), dim3(64), lds_bytes, e->stream, args, W));
+    }
   } else {
     hipLaunchKernelGGL(k_goal_task_init<Task>, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, args);
     for (int t = 0; t < a.max_steps; ++t) {
@@ -3507,8 +3522,9 @@ static int sched_check(const SchedIO& sio, int N, int K, int P, const std::vecto
 struct WallIO {
   const mobrob_walls_t* wl;
   double* wall_out;           // [N][7] in / out
+  int32_t* blocked_out = nullptr;   // [N][4] in / out: solid walls (mobrob_ppo_follow_waypoints_solid) when not null
 };
-struct WallFill {             // the wall fields of WallArgs (after eval_prepare grew eval_buf)
+struct WallFill {           // the wall fields of WallArgs (after eval_prepare grew eval_buf)
   const float* boxes;
   const int* nwall;
   const int* scene;
@@ -3587,6 +3603,45 @@ static int resume_run(mobrob_ppo_engine_t* e, int N, const HazardIO* hio, const 
   const int ran = !hio ? run_with_walls<Base>(e, h.b, wio, wf, tio, tf)
                   : hio->frames ? run_with_walls<FrameHazardTask<Base>>(e, hf, wio, wf, tio, tf)
                                 : run_with_walls<HazardTask<Base>>(e, h, wio, wf, tio, tf);
+  if (tio && ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
+  return ran;
+}
+
+// run_with_walls for a task that always has them (no instance of the task outside WallTask)
+template <class Task>
+static int run_in_walls(mobrob_ppo_engine_t* e, const typename Task::Args& a, const WallFill& wf, const TeamIO* tio, const TeamFill& tf) {
+  const WallArgs<typename Task::Args> w{a, wf.boxes, wf.nwall, wf.scene, wf.M, wf.radius, wf.coef, wf.indicator,
+                                        (int)WallTask<Task>::base_lds_floats(a), wf.out};
+  return run_with_teams<WallTask<Task>>(e, w, tio, tf);
+}
+
+// the carried blocked record of a run with solid walls: refused before any launch or copy
+static int solid_check(const WallIO& wio, int N, int step0, const double* robot_out) {
+  for (int i = 0; i < N; ++i) {
+    const int32_t* o = wio.blocked_out + (size_t)i * 4;
+    const double steps = robot_out[(size_t)i * 4 + 1];
+    const auto count = [&](int32_t v) { return v >= 0 && (double)v <= steps; };
+    if (!(count(o[0]) && count(o[2]) && count(o[3]) && o[2] <= o[0] && o[1] >= -1 && o[1] <= step0 && (o[1] < 0) == (o[0] == 0)))
+      return fail(MOBROB_ERR_INVALID, "follow: solid: carried blocked record of robot %d is not one a call returns", i);
+  }
+  return MOBROB_OK;
+}
+
+// resume_run with solid walls: Base (filled in `b`) restated as SolidFollowTask<Base>, alone or under static hazards, always in
+// WallTask, with teams when `tio`.  blocked_dev: the uploaded blocked record (downloaded by the caller).
+template <class Base>
+static int solid_run(mobrob_ppo_engine_t* e, int N, const HazardIO* hio, const HazardCarve& hc, const TeamIO* tio, const TeamFill& tf,
+                     const typename Base::Args& b, double*& hazard_dev, const WallIO* wio, const WallFill& wf, int* blocked_dev) {
+  using Solid = SolidFollowTask<Base>;
+  HazardArgs<typename Solid::Args> h{};
+  h.b = typename Solid::Args{b, wf.radius, blocked_dev};
+  if (hio) {
+    if (const int rc = hazard_fill(e, *hio, N, hc, h)) return rc;
+    HIPC(hipMemcpyAsync(h.hazard_out, hio->hazard_out, (size_t)N * 4 * 8, hipMemcpyHostToDevice, e->stream));
+  }
+  hazard_dev = h.hazard_out;
+  if (tio) HIPC(hipMemcpyAsync(tf.out, tio->team_out, (size_t)N * 5 * 8, hipMemcpyHostToDevice, e->stream));
+  const int ran = !hio ? run_in_walls<Solid>(e, h.b, wf, tio, tf) : run_in_walls<HazardTask<Solid>>(e, h, wf, tio, tf);
   if (tio && ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
   return ran;
 }
@@ -3755,9 +3810,14 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
   std::vector<int32_t> wall_counts;
   if (wio) {   // (only with rs, likewise)
     if (const int rc = wall_check(*wio, N, rs->step0, robot_out, wall_counts)) return rc;
+    if (wio->blocked_out) {
+      if (hio && hio->frames)
+        return fail(MOBROB_ERR_INVALID, "follow: solid: solid walls do not run with hazard frames yet (static hazards, teams and schedules do)");
+      if (const int rc = solid_check(*wio, N, rs->step0, robot_out)) return rc;
+    }
     if (e->fused.enabled && e->fused.H == 64) {   // the tile kernel's LDS: actor, the hazards' blocks, the walls' blocks
       const size_t hz_floats = hio ? 32 + (hio->hz->scene ? 0 : 3 * (size_t)hio->hz->max_hazards) : 32;
-      const size_t tile = eval64_lds_bytes(e->Dp) + (hz_floats + 32 + (wio->wl->scene ? 0 : 4 * (size_t)wio->wl->max_walls)) * sizeof(float);
+      const size_t tile = eval64_lds_bytes(eval_tile_width(e->Dp, wio->blocked_out != nullptr)) + (hz_floats + 32 + (wio->wl->scene ? 0 : 4 * (size_t)wio->wl->max_walls)) * sizeof(float);
       int limit = 0;
       if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
       if (tile > (size_t)limit)
@@ -3778,7 +3838,7 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
                o_sched = carve.add(sio ? (size_t)N * 2 * 8 : 0),
                o_wbox = carve.add(wio ? std::max<size_t>((size_t)wio->wl->n_scenes * wio->wl->max_walls * 4, 1) * 4 : 0),
                o_wcnt = carve.add(wio ? (size_t)wio->wl->n_scenes * 4 : 0), o_wscene = carve.add(wio ? (size_t)N * 4 : 0),
-               o_wout = carve.add(wio ? (size_t)N * 7 * 8 : 0);
+               o_wout = carve.add(wio ? (size_t)N * 7 * 8 : 0), o_wblk = carve.add(wio && wio->blocked_out ? (size_t)N * 4 * 4 : 0);
   FrameHazardArgs<FollowArgs> hf{};    // the frames tasks' arguments hold the static tasks'
   FrameHazardArgs<ResumeArgs> hrf{};
   FrameHazardArgs<ScheduledArgs> hsf{};
@@ -3837,6 +3897,9 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
       if (wl->scene) HIPC(hipMemcpyAsync(scene_dev, wl->scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
       HIPC(hipMemcpyAsync(wf.out, wio->wall_out, (size_t)N * 7 * 8, hipMemcpyHostToDevice, e->stream));
     }
+    const bool solid = wio && wio->blocked_out;
+    int* blocked_dev = solid ? eval_at<int>(e, o_wblk) : nullptr;
+    if (solid) HIPC(hipMemcpyAsync(blocked_dev, wio->blocked_out, (size_t)N * 4 * 4, hipMemcpyHostToDevice, e->stream));
     if (sio) {
       ScheduledArgs& sa = hsf.h.b;
       int* rel_dev = eval_at<int>(e, o_rel);
@@ -3845,16 +3908,19 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
       HIPC(hipMemcpyAsync(rel_dev, sio->sc->release, (size_t)N * K * 4, hipMemcpyHostToDevice, e->stream));
       HIPC(hipMemcpyAsync(home_dev, sio->sc->home, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
       HIPC(hipMemcpyAsync(sa.sched_out, sio->sched_out, (size_t)N * 2 * 8, hipMemcpyHostToDevice, e->stream));
-      ran = resume_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, hsf, hazard_dev, wio, wf);
+      ran = solid ? solid_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, sa, hazard_dev, wio, wf, blocked_dev)
+                  : resume_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, hsf, hazard_dev, wio, wf);
       if (ran >= 0) HIPC(hipMemcpyAsync(sio->sched_out, sa.sched_out, (size_t)N * 2 * 8, hipMemcpyDeviceToHost, e->stream));
     } else {
-      ran = resume_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, hrf, hazard_dev, wio, wf);
+      ran = solid ? solid_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, r, hazard_dev, wio, wf, blocked_dev)
+                  : resume_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, hrf, hazard_dev, wio, wf);
     }
     if (ran >= 0) {
       HIPC(hipMemcpyAsync(rs->state, r.state, (size_t)N * 6 * 4, hipMemcpyDeviceToHost, e->stream));
       HIPC(hipMemcpyAsync(rs->leg_used, r.leg_used, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
       HIPC(hipMemcpyAsync(rs->status, r.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
       if (wio) HIPC(hipMemcpyAsync(wio->wall_out, wf.out, (size_t)N * 7 * 8, hipMemcpyDeviceToHost, e->stream));
+      if (solid) HIPC(hipMemcpyAsync(wio->blocked_out, blocked_dev, (size_t)N * 4 * 4, hipMemcpyDeviceToHost, e->stream));
     }
   }
   if (ran < 0) return ran;
@@ -3947,6 +4013,28 @@ int mobrob_ppo_follow_waypoints_walls(mobrob_ppo_engine_t* e, const mobrob_goal_
   const TeamIO tio{teams, team_out};
   const SchedIO sio{schedule, sched_out};
   const WallIO wio{walls, wall_out};
+  mobrob_hazards_t view;
+  const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
+  return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
+                          (hz || hzf) ? &hio : nullptr, resume, teams ? &tio : nullptr, schedule ? &sio : nullptr, &wio);
+}
+
+int mobrob_ppo_follow_waypoints_solid(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                      const mobrob_hazards_t* hz, const mobrob_hazard_frames_t* hzf, const mobrob_follow_resume_t* resume,
+                                      const mobrob_teams_t* teams, const mobrob_follow_schedule_t* schedule, const mobrob_walls_t* walls,
+                                      const float* waypoints, const int32_t* n_waypoints, int32_t* arrival, double* robot_out,
+                                      double* hazard_out, double* team_out, double* sched_out, double* wall_out, int32_t* blocked_out,
+                                      float* path_out, float* trace_out) {
+  if (!resume || !walls || !wall_out || !blocked_out)
+    return fail(MOBROB_ERR_INVALID, "follow: solid: null argument (a call with walls is a call of a run)");
+  if ((teams != nullptr) != (team_out != nullptr)) return fail(MOBROB_ERR_INVALID, "follow: solid: team_out is needed with teams, and only then");
+  if ((schedule != nullptr) != (sched_out != nullptr))
+    return fail(MOBROB_ERR_INVALID, "follow: solid: sched_out is needed with a schedule, and only then");
+  if (hz && hzf) return fail(MOBROB_ERR_INVALID, "follow: solid: static hazards or hazard frames, not both");
+  if ((hz || hzf) != (hazard_out != nullptr)) return fail(MOBROB_ERR_INVALID, "follow: solid: hazard_out is needed with hazards, and only then");
+  const TeamIO tio{teams, team_out};
+  const SchedIO sio{schedule, sched_out};
+  const WallIO wio{walls, wall_out, blocked_out};
   mobrob_hazards_t view;
   const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
   return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,

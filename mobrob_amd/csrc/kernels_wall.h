@@ -17,6 +17,7 @@
 // first contact step (global, 1-based, -1: none), minimum clearance (NaN: no step run, +inf: no walls), the wall at that minimum
 // (first attainment, -1: none), crossing steps, first crossing step), read at entry and continued like hazard_out.
 #pragma once
+#include <type_traits>
 #include "kernels_team.h"
 
 namespace mobrob {
@@ -102,6 +103,251 @@ __device__ __forceinline__ void wall_store(double* o, const WallAcc& W, int step
   o[4] = (double)W.wall; o[5] = (double)W.crossings; o[6] = (double)W.first_cross;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Solid walls (mobrob_ppo_follow_waypoints_solid): the step's proposed position is resolved against the scene INSIDE the env step,
+// between the dynamics and the goal test.  The rule, stated once in goal_rules.py (wall_block): with a the pre-step xy, p the xy
+// goal_advance's update proposes (after the clamp), Hx = hx + radius, Hy = hy + radius per wall,
+//   a wall with |ax - cx| <= Hx and |ay - cy| <= Hy does not hold in this step (`inside`: a robot that starts in an inflated box
+//   can leave it);  seg_hit(a, c): OR over the other walls of wall_partial's separating test with Hx, Hy for hx, hy;
+//   candidates c0 = (px, py), c1 = (px, ay), c2 = (ax, py), c3 = (ax, ay): the first without a hit is taken, c3 untested;
+//   a dropped axis has its velocity component set to +0.0.
+// The reach test, reward, arrival, next waypoint, path, trace and the next observation use the resolved position; WallTask's check
+// then runs on (a, q) as it does on any step.  z is untouched.
+//
+// The resolution runs serially on the robot's own thread over its scene (the tile kernel's env phase has one lane per robot): one
+// pass over the walls when c0 is clean, at most three; every pass visits every wall (the first also decides `inside`).  No barrier, no hook of k_goal64_tile is added: a shared scene is the one WallTask::stage put in LDS.
+//
+// SolidFollowTask<B> restates B = ResumeFollowTask / ScheduledFollowTask with that step (goal_advance, follow_env_step and
+// sched_env_step keep their instructions: they are not touched) and carries blocked_out [N][4] int32: blocked steps (code != 0),
+// first blocked step (global, 1-based, -1: none), fully stopped steps (code 3), steps with a wall that did not hold.  It is always
+// wrapped in WallTask (directly or under HazardTask), which names the robot's scene to it before every step.
+// ------------------------------------------------------------------------------------------------
+struct WallResolved {
+  float qx, qy;
+  int code;
+  bool inside;
+};
+
+// the rule: pre-step (ax, ay), proposed (px, py) -> the resolved position, the code and `inside`.  One loop, run once per
+// candidate c0, c1, c2 until one is clean; every pass visits every wall (the first decides `inside` over the whole scene).
+__device__ __forceinline__ WallResolved wall_resolve(const float* w, int m, float radius, float ax, float ay, float px, float py) {
+  WallResolved r{px, py, 0, false};
+  for (; r.code < 3; ++r.code) {
+    r.qx = r.code == 2 ? ax : px;
+    r.qy = r.code == 1 ? ay : py;
+    const float ex = rounded(__fmul_rn(0.5f, __fsub_rn(r.qx, ax))), ey = rounded(__fmul_rn(0.5f, __fsub_rn(r.qy, ay)));
+    const float sx = rounded(__fmul_rn(0.5f, __fadd_rn(ax, r.qx))), sy = rounded(__fmul_rn(0.5f, __fadd_rn(ay, r.qy)));
+    const float aex = fabsf(ex), aey = fabsf(ey);
+    bool hit = false;
+    for (int i = 0; i < m; ++i) {   // no branch in the body: a lane-private loop inside the tile's step loop
+      const float cx = w[4 * i], cy = w[4 * i + 1];
+      const float Hx = __fadd_rn(w[4 * i + 2], radius), Hy = __fadd_rn(w[4 * i + 3], radius);
+      const bool within = fabsf(__fsub_rn(ax, cx)) <= Hx && fabsf(__fsub_rn(ay, cy)) <= Hy;   // the wall does not hold in this step
+      const float mx = __fsub_rn(sx, cx), my = __fsub_rn(sy, cy);
+      const float cross = fabsf(__fsub_rn(rounded(__fmul_rn(mx, ey)), rounded(__fmul_rn(my, ex))));
+      const float reach = __fadd_rn(rounded(__fmul_rn(Hx, aey)), rounded(__fmul_rn(Hy, aex)));
+      const bool apart = fabsf(mx) > __fadd_rn(Hx, aex) || fabsf(my) > __fadd_rn(Hy, aey) || cross > reach;
+      r.inside = r.inside || within;
+      hit = hit || (!within && !apart);
+    }
+    if (!hit) return r;
+  }
+  r.qx = ax; r.qy = ay;   // c3, untested
+  return r;
+}
+
+struct SolidOutcome {
+  GoalOutcome o;
+  int code;
+  bool inside;
+};
+
+// goal_advance (kernels_env.h) with the resolution between the position update and d1: the same operations in the same order
+// around it.  A function of its own, as sched_env_step is: the existing tasks keep their instructions.
+template <class GP>
+__device__ __forceinline__ SolidOutcome solid_goal_advance(GoalState& g, const GP& p, const float* act, int A, const float* ws, int m,
+                                                           float radius) {
+  float cmd[3] = {0.f, 0.f, 0.f};
+  for (int k = 0; k < A; ++k) {
+    const float a = act[k];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) cmd[j] = __fmaf_rn(p.mix[j][k], a, cmd[j]);
+  }
+  const float d0 = goal_dist(g.goal, g.pos, p.P);
+  const float ax = g.pos[0], ay = g.pos[1];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    if (j < p.P) {
+      g.vel[j] = __fmaf_rn(0.8f, g.vel[j], __fmul_rn(0.2f, cmd[j]));
+      g.pos[j] = fminf(fmaxf(__fmaf_rn(p.dt, g.vel[j], g.pos[j]), -p.extent), p.extent);
+    }
+  }
+  const WallResolved r = wall_resolve(ws, m, radius, ax, ay, g.pos[0], g.pos[1]);
+  g.pos[0] = r.qx; g.pos[1] = r.qy;
+  if (r.code & 2) g.vel[0] = 0.f;   // x dropped (2, 3)
+  if (r.code & 1) g.vel[1] = 0.f;   // y dropped (1, 3)
+  const float d1 = goal_dist(g.goal, g.pos, p.P);
+  SolidOutcome s;
+  GoalOutcome& o = s.o;
+  o.reached = d1 < p.reach;
+  o.reward = __fadd_rn(__fsub_rn(d0, d1), o.reached ? __fadd_rn(p.bonus, p.extra_bonus) : 0.f);
+  o.term = p.terminate_on_goal && o.reached;
+  g.ep_len += 1;
+  g.ep_ret = __fadd_rn(g.ep_ret, o.reward);
+  o.tr = g.ep_len >= p.time_limit && !o.term;
+  o.done = o.term || o.tr;
+  s.code = r.code;
+  s.inside = r.inside;
+  return s;
+}
+
+struct SolidAcc {
+  int blocked, first, stopped, inside;
+};
+
+template <class BaseArgs>
+struct SolidArgs {
+  BaseArgs b;              // ResumeArgs / ScheduledArgs
+  float radius;            // the scene itself is WallArgs' (named to the robot by WallTask before every step)
+  int* blocked_out;        // [N][4] in / out; per-step path: live state between the launches
+};
+
+template <class BaseRobot>
+struct SolidRobot {
+  BaseRobot b;
+  SolidAcc acc;
+  const float* ws;         // the robot's scene for the step at hand (LDS for a shared scene on the tile) and its wall count
+  int m;
+};
+
+// sched_env_step (kernels_follow.h) with solid_goal_advance: with hold = false and follow_set_goal after an arrival it is
+// follow_env_step.  g1 of the blocked record: g0 + t + 1.
+template <int XT = 0>
+__device__ __forceinline__ float solid_env_step(GoalState& g, FollowRobot& R, SolidAcc& S, const FollowArgs& f, int n, int t,
+                                               const float* act, const float* obs_row, float* post, int g0, bool hold, float held_in,
+                                               const float* ws, int m, float radius) {
+  const EvalArgs& a = f.e;
+  float* fl = eval_trace_row<XT>(g, a, n, t, act, obs_row);
+  const int k_before = R.k;
+  const SolidOutcome so = solid_goal_advance(g, a.p, act, a.A, ws, m, radius);
+  const GoalOutcome o = so.o;
+  if (so.code != 0) {
+    S.blocked += 1;
+    if (S.first < 0) S.first = g0 + t + 1;
+    if (so.code == 3) S.stopped += 1;
+  }
+  if (so.inside) S.inside += 1;
+  if (post) { post[0] = g.pos[0]; post[1] = g.pos[1]; }
+  R.steps += 1;
+  const bool arrived = o.reached && !hold;
+  const float held_at = hold ? fmaxf(held_in, goal_dist(g.goal, g.pos, a.p.P)) : held_in;
+  if (!hold) R.ret_sum += (double)o.reward;
+  if (arrived) {
+    f.arrival[(size_t)n * f.K + R.k] = g0 + t + 1;
+    R.k += 1;
+  }
+  const bool going = R.k < R.nwp;
+  if (fl) {
+    fl[0] = hold ? 0.f : o.reward; fl[1] = arrived ? 1.f : 0.f; fl[2] = (float)k_before; fl[3] = going ? 0.f : 1.f;
+  }
+  if (f.path && (t + 1) % f.path_stride == 0) follow_path_store(f, (t + 1) / f.path_stride, n, g);
+  return held_at;
+}
+
+template <class B>
+struct SolidFollowTask {
+  static constexpr bool kScheduled = std::is_same_v<B, ScheduledFollowTask>;
+  static_assert(kScheduled || std::is_same_v<B, ResumeFollowTask>, "solid walls restate the two run tasks");
+  using Args = SolidArgs<typename B::Args>;
+  using Robot = SolidRobot<typename B::Robot>;
+  static constexpr bool kWide = false;
+  static constexpr bool kResume = true;
+  static constexpr bool kFrames = false;
+  static __host__ __device__ __forceinline__ const EvalArgs& eval(const Args& a) { return B::eval(a.b); }
+  static __device__ __forceinline__ int step0(const Args& a) { return B::step0(a.b); }
+  static __device__ __forceinline__ const ResumeArgs& resume(const Args& a) {
+    if constexpr (kScheduled) return a.b.r;
+    else return a.b;
+  }
+  static __device__ __forceinline__ SolidAcc acc_load(const Args& a, int n) {
+    const int* o = a.blocked_out + (size_t)n * 4;
+    return SolidAcc{o[0], o[1], o[2], o[3]};
+  }
+  static __device__ __forceinline__ void acc_store(const Args& a, int n, const SolidAcc& S) {
+    int* o = a.blocked_out + (size_t)n * 4;
+    o[0] = S.blocked; o[1] = S.first; o[2] = S.stopped; o[3] = S.inside;
+  }
+  static __device__ __forceinline__ void start(GoalState& g, Robot& R, const Args& a, int n) {
+    B::start(g, R.b, a.b, n);
+    R.acc = acc_load(a, n);
+    R.ws = nullptr; R.m = 0;
+  }
+  static __device__ __forceinline__ bool active(const Args& a, const Robot& R) { return B::active(a.b, R.b); }
+  // ResumeFollowTask::step / ScheduledFollowTask::step with solid_env_step
+  template <int XT = 0>
+  static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
+                                              const float* obs_row, float* post = nullptr) {
+    const ResumeArgs& r = resume(a);
+    const int k0 = R.b.b.k;
+    if constexpr (kScheduled) {
+      const int gs = r.step0 + t;
+      const bool hold = gs < a.b.release[(size_t)n * r.f.K + k0];
+      R.b.drift = solid_env_step<XT>(g, R.b.b, R.acc, r.f, n, t, act, obs_row, post, r.step0, hold, R.b.drift, R.ws, R.m, a.radius);
+      if (hold) {
+        R.b.holds += 1;
+      } else {
+        R.b.leg_used = (R.b.b.k != k0 || r.leg_steps == 0) ? 0 : R.b.leg_used + 1;
+      }
+      if (hold || R.b.b.k != k0) sched_set_goal(g, a.b, n, R.b.b.k, R.b.b.nwp, gs + 1);
+    } else {
+      (void)solid_env_step<XT>(g, R.b.b, R.acc, r.f, n, t, act, obs_row, post, r.step0, false, 0.f, R.ws, R.m, a.radius);
+      if (R.b.b.k != k0 && R.b.b.k < R.b.b.nwp) follow_set_goal(g, r.f, n, R.b.b.k);
+      R.b.leg_used = (R.b.b.k != k0 || r.leg_steps == 0) ? 0 : R.b.leg_used + 1;
+    }
+    return active(a, R);
+  }
+  static __device__ __forceinline__ int episodes(const Robot&) { return 0; }
+  static __device__ __forceinline__ int steps(const Robot& R) { return B::steps(R.b); }
+  static __device__ __forceinline__ bool recorded(const Robot&, int) { return false; }
+  static __device__ __forceinline__ void finish(const Args& a, int n, const Robot& R, const GoalState& g) {
+    B::finish(a.b, n, R.b, g);
+    acc_store(a, n, R.acc);
+  }
+  static __device__ __forceinline__ Robot load(const Args& a, int n) { return Robot{B::load(a.b, n), acc_load(a, n), nullptr, 0}; }
+  static __device__ __forceinline__ void store(const Args& a, int n, const Robot& R) {
+    B::store(a.b, n, R.b);
+    acc_store(a, n, R.acc);
+  }
+};
+
+// the solid task inside a wrapped task (itself, or under HazardTask), and its robot inside the wrapped robot
+template <class T>
+struct wall_solid_inner : std::false_type {};
+template <class B>
+struct wall_solid_inner<SolidFollowTask<B>> : std::true_type {};
+template <class B>
+struct wall_solid_inner<HazardTask<B>> : wall_solid_inner<B> {};
+template <class B>
+__device__ __forceinline__ typename SolidFollowTask<B>::Robot& wall_solid_robot(SolidFollowTask<B>*, typename SolidFollowTask<B>::Robot& R) {
+  return R;
+}
+template <class B>
+__device__ __forceinline__ auto& wall_solid_robot(HazardTask<B>*, typename HazardTask<B>::Robot& R) {
+  return wall_solid_robot(static_cast<B*>(nullptr), R.b);
+}
+
+// a task that holds the solid task anywhere inside (TeamTask<WallTask<...>> included): the host's choice of tile width
+template <class T>
+struct wall_solid_any : wall_solid_inner<T> {};
+template <class B>
+struct wall_solid_any<TeamTask<B>> : wall_solid_any<B> {};
+template <class Base>
+struct WallTask;
+template <class B>
+struct wall_solid_any<WallTask<B>> : wall_solid_inner<B> {};
+template <class T>
+constexpr bool task_solid = wall_solid_any<T>::value;
+
 template <class Base>
 struct WallTask {
   static_assert(Base::kResume, "walls are a property of a run: the wrapped task must be resumable");
@@ -142,6 +388,10 @@ struct WallTask {
   static __device__ __forceinline__ bool step(GoalState& g, Robot& R, const Args& a, int n, int t, const float* act,
                                               const float* obs_row) {
     const float ax = g.pos[0], ay = g.pos[1];
+    if constexpr (wall_solid_inner<Base>::value) {   // solid walls: the scene the base's env step resolves against
+      auto& S = wall_solid_robot(static_cast<Base*>(nullptr), R.b);
+      S.ws = scene_of(a, n, S.m);
+    }
     bool going;
     if constexpr (Base::kWide) going = Base::step(g, R.b, a.b, n, t, act, obs_row);
     else going = Base::template step<0>(g, R.b, a.b, n, t, act, obs_row);
@@ -176,6 +426,11 @@ struct WallTask {
                                                    const float* obs_row, float* xy, int& e0) {
     float* pre = xy + a.pre_off;   // the robot's row of the pre-step block
     pre[0] = g.pos[0]; pre[1] = g.pos[1];
+    if constexpr (wall_solid_inner<Base>::value) {   // solid walls: a shared scene is the staged one, 32 floats after the pre-step block
+      auto& S = wall_solid_robot(static_cast<Base*>(nullptr), R.b);
+      const float* ws = scene_of(a, n, S.m);
+      S.ws = a.scene ? ws : pre - 2 * (n & 15) + 32;
+    }
     if constexpr (Base::kWide) return Base::step_lane(g, R.b, a.b, n, t, act, obs_row, xy, e0);
     else return Base::template step<0>(g, R.b, a.b, n, t, act, obs_row, xy);
   }

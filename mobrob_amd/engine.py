@@ -472,12 +472,15 @@ class PPOEngine:
         hold_drift, lateness and `state.sched`; trace rows of hold steps carry the flags 0, 0.
         walls: a goal_rules.Walls -> mobrob_ppo_follow_waypoints_walls (always a call of a run; without `resume` its first),
         adding the keys of waypoints.wall_result (wall_cost_sum, contact_steps, first_contact, min_wall_clearance, closest_wall,
-        crossing_steps, first_crossing) and `state.wall`; nothing else the call returns changes."""
+        crossing_steps, first_crossing) and `state.wall`; nothing else the call returns changes.  With walls.solid the walls
+        block (mobrob_ppo_follow_waypoints_solid; goal_rules.wall_block states the rule): robots stop and slide at them, the
+        dict gains the keys of waypoints.blocked_result (wall_blocked_steps, wall_first_blocked, wall_stopped_steps,
+        wall_inside_steps) and `state.blocked`.  Solid walls with a MovingHazards are refused (ValueError naming `solid`)."""
         from .waypoints import FollowState, follow_inputs
         if resume is not None or int(leg_steps) != 0 or teams is not None or schedule is not None or walls is not None:
             if resume is None:
                 resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule,
-                                     walls is not None)
+                                     walls if walls is not None else False)
             elif not (start is None and waypoints is None and n_waypoints is None):
                 raise ValueError("follow_waypoints: a resumed call takes its robots and waypoints from `resume`")
             return self._follow_resume(pos_dim, mix, dt, extent, reach_radius, goal_bonus, extra_bonus, obs_noise, resume,
@@ -523,7 +526,8 @@ class PPOEngine:
         mobrob_ppo_follow_waypoints_walls) on a copy of `state`."""
         from ._lib import FollowResume, FollowScheduleC, TeamsC, WallsC
         from .envs.goal_rules import Schedule, Teams, Walls
-        from .waypoints import FollowState, schedule_result, team_result, wall_result
+        from .envs.goal_rules import MovingHazards
+        from .waypoints import FollowState, blocked_result, schedule_result, team_result, wall_result
         if not isinstance(state, FollowState):
             raise TypeError(f"follow_waypoints: resume must be a FollowState, not {type(state).__name__}")
         if (state.hazard is None) != (hazards is None):
@@ -544,6 +548,11 @@ class PPOEngine:
             if not isinstance(walls, Walls):
                 raise TypeError(f"walls must be a mobrob_amd.envs.goal_rules.Walls, not {type(walls).__name__}")
             walls.check_robots(state.n_robots)
+        solid = walls is not None and bool(getattr(walls, "solid", False))
+        if (getattr(state, "blocked", None) is None) == solid:
+            raise ValueError("follow_waypoints: a run has solid walls in every call or in none (FollowState(..., walls=Walls(..., solid=True)))")
+        if solid and isinstance(hazards, MovingHazards):
+            raise ValueError("follow_waypoints: solid=True does not run with MovingHazards yet (static hazards, teams and schedules do)")
         st = state.copy()
         n, K, P = st.waypoints.shape
         if P != int(pos_dim):
@@ -566,6 +575,10 @@ class PPOEngine:
         if walls is not None:
             st.wall = np.ascontiguousarray(st.wall, np.float64)
             if st.wall.shape != (n, 7):
+                raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
+        if solid:
+            st.blocked = np.ascontiguousarray(st.blocked, np.int32)
+            if st.blocked.shape != (n, 4):
                 raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
         if st.state.shape != (n, 6) or st.robot.shape != (n, 4) or st.arrival.shape != (n, K) or st.leg_used.shape != (n,):
             raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
@@ -598,11 +611,14 @@ class PPOEngine:
             wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
             wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
             wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
-            r = check(self.lib.mobrob_ppo_follow_waypoints_walls(
-                self._h, C.byref(g), C.byref(sp), None if h is None or frames else C.byref(h), C.byref(h) if frames else None,
-                C.byref(rs), None if tm is None else C.byref(tm), None if sc is None else C.byref(sc), C.byref(wl), *tail[:5],
-                None if tm is None else st.team.ctypes.data_as(dp), None if sc is None else st.sched.ctypes.data_as(dp),
-                st.wall.ctypes.data_as(dp), *tail[5:]))
+            head = (self._h, C.byref(g), C.byref(sp), None if h is None or frames else C.byref(h), C.byref(h) if frames else None,
+                    C.byref(rs), None if tm is None else C.byref(tm), None if sc is None else C.byref(sc), C.byref(wl), *tail[:5],
+                    None if tm is None else st.team.ctypes.data_as(dp), None if sc is None else st.sched.ctypes.data_as(dp),
+                    st.wall.ctypes.data_as(dp))
+            if solid:
+                r = check(self.lib.mobrob_ppo_follow_waypoints_solid(*head, st.blocked.ctypes.data_as(i32), *tail[5:]))
+            else:
+                r = check(self.lib.mobrob_ppo_follow_waypoints_walls(*head, *tail[5:]))
         elif schedule is not None:
             r = check(self.lib.mobrob_ppo_follow_waypoints_scheduled(
                 self._h, C.byref(g), C.byref(sp), None if h is None or frames else C.byref(h), C.byref(h) if frames else None,
@@ -630,6 +646,8 @@ class PPOEngine:
             out.update(schedule_result(st))
         if walls is not None:
             out.update(wall_result(st))
+        if solid:
+            out.update(blocked_result(st))
         if path is not None:
             out["path"] = path
         return out

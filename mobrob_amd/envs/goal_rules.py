@@ -473,9 +473,10 @@ class Walls:
     """A wall layout: `boxes` [M, 4] (one scene) or [S, M, 4] (scenes) rows (cx, cy, hx, hy) -- centre and half extents, hx, hy
     >= 0 --, `counts` [S] walls in use per scene (None: all M), `scene` [n] scene of each robot (None: S must be 1), `radius` the
     robot's footprint, `cost` per unit of intrusion and `indicator` (a step's cost is 1 if there is any).  Only x and y count,
-    for every robot.  Checked on construction (ValueError)."""
+    for every robot.  Checked on construction (ValueError).  `solid`: False -- the walls are observed (wall_check) and block
+    nothing; True -- a waypoint-following run also resolves every step against them (wall_block): robots stop and slide."""
 
-    def __init__(self, boxes, counts=None, scene=None, radius=0.0, cost=1.0, indicator=True):
+    def __init__(self, boxes, counts=None, scene=None, radius=0.0, cost=1.0, indicator=True, solid=False):
         bx = np.asarray(boxes, np.float64)
         if bx.size == 0 and bx.ndim < 2:
             bx = bx.reshape(0, 4)
@@ -516,6 +517,7 @@ class Walls:
         self.table = np.ascontiguousarray(bx, np.float32)   # [S, M, 4]
         self.counts, self.scene, self.indicator = cnt, sc, bool(indicator)
         self.radius, self.cost = float(np.float32(radius)), float(np.float32(cost))   # the float32 values every path uses
+        self.solid = bool(solid)
 
     @property
     def n_scenes(self):
@@ -535,8 +537,9 @@ class Walls:
             raise ValueError(f"wall scene must have {n} entries, one per robot, got {self.scene.shape[0]}")
 
     @staticmethod
-    def enclosure(length=ARENA_LENGTH, thick=ARENA_THICK, centre=(0.0, 0.0)):
-        """[4, 4] float64 boxes of a square enclosure of outer side `length` and wall thickness `thick` around `centre`, laid out
+    def enclosure(length=ARENA_LENGTH, thick=ARENA_THICK, centre=(0.0, 0.0), solid=None, **kwargs):
+        """With `solid` given (True or False): the Walls of the enclosure below, Walls(boxes, solid=solid, **kwargs).  Otherwise the
+        [4, 4] float64 boxes of a square enclosure of outer side `length` and wall thickness `thick` around `centre`, laid out
         as the reference's arena is (pinned by tests/golden/wall_cases.npz): four equal bars in a pinwheel, each reaching from one
         outer corner to the inner face of the next bar.  With r = (length - thick) / 2 and h = thick / 2 the bars sit at (-h, r),
         (r, h), (h, -r), (-r, -h) with half extents (r, h), (h, r), (r, h), (h, r)."""
@@ -545,7 +548,12 @@ class Walls:
             raise ValueError(f"an enclosure needs 0 <= thick <= length, got length {length}, thick {thick}")
         cx, cy = (float(c) for c in centre)
         r, h = (length - thick) / 2, thick / 2
-        return np.array([[cx - h, cy + r, r, h], [cx + r, cy + h, h, r], [cx + h, cy - r, r, h], [cx - r, cy - h, h, r]], np.float64)
+        boxes = np.array([[cx - h, cy + r, r, h], [cx + r, cy + h, h, r], [cx + h, cy - r, r, h], [cx - r, cy - h, h, r]], np.float64)
+        if solid is None:
+            if kwargs:
+                raise TypeError(f"enclosure: {sorted(kwargs)} need solid= (the call then returns a Walls, not the boxes)")
+            return boxes
+        return Walls(boxes, solid=bool(solid), **kwargs)
 
 
 def wall_check(pre_xy, post_xy, boxes, radius=0.0, coef=1.0, indicator=True, counts=None):
@@ -632,6 +640,109 @@ def wall_fold(record, pre_xy, post_xy, stepped, walls, step0=0):
         cross = s & hit
         rec[:, 5] += cross
         rec[:, 6] = np.where(cross & (rec[:, 6] < 0), step0 + t + 1, rec[:, 6])
+    return rec
+
+
+# ---- solid walls (Walls(..., solid=True)): the step's proposed position is resolved against the boxes inside the environment
+# step, between the dynamics and the goal test.  Stated here once; the device (csrc/kernels_wall.h: wall_resolve) is held to it
+# bit for bit, the host loop applies it as it stands.
+BLOCKED_START = (0, -1, 0, 0)   # a robot's blocked record before its first step: blocked steps, first blocked step, stopped, inside
+
+
+def goal_propose32(pos, vel, act, mix, dt, extent, P):
+    """The device's velocity and position update (csrc/kernels_env.h: goal_advance) bit for bit: pos, vel [..., >= P] float32,
+    act [..., A], mix [3][>= A] -> (proposed pos [..., P], vel [..., P]) float32.  cmd_j accumulates mix[j][k] act[k] in k order
+    by fused multiply-adds from 0; vel_j = fma(0.8, vel_j, 0.2 cmd_j); pos_j = clamp(fma(dt, vel_j, pos_j), -extent, extent)."""
+    f32 = np.float32
+    pos, vel, act, mix = (np.asarray(x, f32) for x in (pos, vel, act, mix))
+    lead = np.broadcast_shapes(pos.shape[:-1], vel.shape[:-1], act.shape[:-1])
+    new_pos, new_vel = [], []
+    for j in range(int(P)):
+        cmd = np.zeros(lead, f32)
+        for k in range(act.shape[-1]):
+            cmd = _fma32(mix[j, k], act[..., k], cmd).reshape(lead)
+        v = _fma32(f32(0.8), vel[..., j], f32(0.2) * cmd).reshape(lead)
+        p = np.minimum(np.maximum(_fma32(f32(dt), v, pos[..., j]).reshape(lead), -f32(extent)), f32(extent))
+        new_vel.append(v)
+        new_pos.append(p.astype(f32))
+    return np.stack(new_pos, -1), np.stack(new_vel, -1)
+
+
+def wall_block(a_xy, p_xy, boxes, radius=0.0, counts=None):
+    """Solid walls, ONE step: a_xy [..., 2] the x, y before the step, p_xy [..., 2] the x, y the dynamics propose (after the clamp
+    to the extent), boxes [M, 4] or [..., M, 4] rows (cx, cy, hx, hy), counts [...] walls in use (None: all M) -> (q_xy [..., 2]
+    float32 the position the step ends on, code [...] int64, inside [...] bool).  Float32, every operation rounded on its own.
+        Hx = hx + radius,  Hy = hy + radius                       (the robot's centre against the closed square-inflated box)
+        a wall with |ax - cx| <= Hx and |ay - cy| <= Hy does not hold in this step (inside: any such wall) -- a robot that
+        starts within an inflated box can leave it;
+        seg_hit(a, c): the OR over the other walls of wall_check's separating test of the segment a c with Hx, Hy for hx, hy;
+        candidates in order: c0 = (px, py), c1 = (px, ay), c2 = (ax, py), c3 = (ax, ay); the first one without a hit is taken,
+        c3 untested; code = its number.
+    A dropped axis (y for 1, x for 2, both for 3) has its velocity component set to +0.0 by the caller (wall_block_velocity).
+    Float add and the non-negative products are monotone, so a segment that meets a closed un-inflated box meets its inflated
+    one: with inside False, wall_check(a, q) reports no crossing."""
+    f32 = np.float32
+    a, p = np.asarray(a_xy, f32), np.asarray(p_xy, f32)
+    if a.shape != p.shape or p.shape[-1:] != (2,):
+        raise ValueError(f"a_xy and p_xy must both be [..., 2], got {a.shape} and {p.shape}")
+    bx = np.asarray(boxes, f32)
+    bx = bx.reshape(bx.shape[:-1] + (4,)) if bx.size else np.zeros((0, 4), f32)
+    lead, M = p.shape[:-1], bx.shape[-2]
+    used = np.full(lead, M) if counts is None else np.broadcast_to(np.asarray(counts), lead)
+    rad, half = f32(radius), f32(0.5)
+    ax, ay, px, py = a[..., 0], a[..., 1], p[..., 0], p[..., 1]
+    walls = []
+    inside = np.zeros(lead, bool)
+    for w in range(M):
+        cx, cy = bx[..., w, 0], bx[..., w, 1]
+        Hx, Hy = bx[..., w, 2] + rad, bx[..., w, 3] + rad
+        on = w < used
+        within = on & (np.abs(ax - cx) <= Hx) & (np.abs(ay - cy) <= Hy)
+        inside = inside | within
+        walls.append((cx, cy, Hx, Hy, on & ~within))
+
+    def seg_hit(qx, qy):
+        ex, ey = half * (qx - ax), half * (qy - ay)
+        sx, sy = half * (ax + qx), half * (ay + qy)
+        aex, aey = np.abs(ex), np.abs(ey)
+        hit = np.zeros(lead, bool)
+        for cx, cy, Hx, Hy, holds in walls:
+            mx, my = sx - cx, sy - cy
+            apart = (np.abs(mx) > Hx + aex) | (np.abs(my) > Hy + aey) | (np.abs(mx * ey - my * ex) > Hx * aey + Hy * aex)
+            hit = hit | (holds & ~apart)
+        return hit
+    h0, h1, h2 = seg_hit(px, py), seg_hit(px, ay), seg_hit(ax, py)
+    code = np.where(~h0, 0, np.where(~h1, 1, np.where(~h2, 2, 3)))
+    qx = np.where((code == 0) | (code == 1), px, ax)
+    qy = np.where((code == 0) | (code == 2), py, ay)
+    return np.stack([qx, qy], -1).astype(f32), np.asarray(code, np.int64), inside
+
+
+def wall_block_velocity(vel, code):
+    """vel [..., P] after the step's velocity update -> the velocity the step ends with: the component of every dropped axis
+    (y for code 1, x for 2, both for 3) is +0.0; z is untouched."""
+    v = np.array(vel, copy=True)
+    code = np.asarray(code)
+    v[..., 0] = np.where((code == 2) | (code == 3), v.dtype.type(0), v[..., 0])
+    v[..., 1] = np.where((code == 1) | (code == 3), v.dtype.type(0), v[..., 1])
+    return v
+
+
+def wall_blocked_fold(record, code, inside, stepped, step0=0):
+    """The carried blocked record after the steps step0 .. step0 + T - 1: record [n][4] integers (blocked steps: code != 0, the
+    first such step as a global 1-based number or -1, fully stopped steps: code 3, steps in which a wall did not hold: inside),
+    code / inside / stepped [T][n].  Returns a new [n][4] int64; a robot accounts only for the steps in which it stepped."""
+    rec = np.array(record, np.int64)
+    code, inside, stepped = np.asarray(code), np.asarray(inside, bool), np.asarray(stepped, bool)
+    T, n = stepped.shape
+    if rec.shape != (n, 4) or code.shape != (T, n) or inside.shape != (T, n):
+        raise ValueError(f"record must be [{n}][4] and code, inside [{T}][{n}], got {rec.shape}, {code.shape} and {inside.shape}")
+    for t in range(T):
+        blocked = stepped[t] & (code[t] != 0)
+        rec[:, 0] += blocked
+        rec[:, 1] = np.where(blocked & (rec[:, 1] < 0), step0 + t + 1, rec[:, 1])
+        rec[:, 2] += stepped[t] & (code[t] == 3)
+        rec[:, 3] += stepped[t] & inside[t]
     return rec
 
 

@@ -59,6 +59,20 @@ a step that jumps a thin wall or clips a corner.  Walls are observational: nothi
   box;  first_crossing [n] the first such step, -1 = none
 and `state.wall` carries the seven.  A call with walls is always a call of a run; `replan` leaves the wall record alone.
 
+With `Walls(..., solid=True)` the walls also BLOCK (goal_rules.wall_block states the rule): inside every step, between the dynamics
+and the goal test, the proposed x, y is resolved against the robot's scene -- the robot's centre is kept out of every box inflated
+by the radius on each axis; a wall whose inflated box holds the pre-step position does not hold in that step, so a robot that
+starts inside one can leave.  The candidates are tried in a fixed order -- the proposed position, the x move alone, the y move
+alone, no move -- and the first whose swept segment meets no wall is taken; the velocity of every dropped axis becomes +0.0 (the
+robot pushes and slides, it does not bounce).  The reach test, reward, arrival, path and the next observation use the resolved
+position; the check above then runs on it and stays observational.  A robot that never had a wall ignored has 0 crossing steps,
+and its minimum clearance is > -1e-6 (rounding; exact-0 contacts are not promised).  Not promised: the robot is not placed on the
+wall's surface (a gap of up to one step remains), no friction or rotation, robots do not block each other, evaluation takes no
+walls.  Solid walls with MovingHazards are refused.  The dict gains
+  wall_blocked_steps [n] steps not taken as proposed;  wall_first_blocked [n] the first such step (global, 1-based), -1 = none;
+  wall_stopped_steps [n] steps with no move at all;  wall_inside_steps [n] steps in which a wall did not hold
+and `state.blocked` carries the four.  Robots stalled against a wall (leg_steps) are replanned by the rounds as any stalled robot.
+
 Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
 sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
 into the next call) and `status`, and takes the previous call's `state=`.  Call c covers the global steps step0 .. step0 +
@@ -130,6 +144,8 @@ class FollowState:
       release [n][K] int32, home [n][P] float32, sched [n][2] float64 hold steps, hold drift -- or None without a schedule
       wall [n][7]       float64 wall cost sum, contact steps, first contact, min clearance, that wall, crossing steps, first
                         crossing -- or None without walls
+      blocked [n][4]    int32 blocked steps, first blocked step, fully stopped steps, steps with a wall ignored -- or None unless
+                        the walls are solid (`walls` given as the run's Walls, with solid=True)
       waypoints [n][K][P] float32, n_waypoints [n] int32: the rows in force (changed by `replan` only)"""
 
     def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False, schedule=None, walls=False):
@@ -147,6 +163,10 @@ class FollowState:
         if walls:
             from .envs.goal_rules import WALL_START
             self.wall = np.tile(np.array(WALL_START), (n, 1))
+        self.blocked = None
+        if getattr(walls, "solid", False):
+            from .envs.goal_rules import BLOCKED_START
+            self.blocked = np.tile(np.array(BLOCKED_START, np.int32), (n, 1))
         self.release = self.home = self.sched = None
         if schedule is not None:
             from .envs.goal_rules import SCHED_START, Schedule
@@ -179,7 +199,7 @@ class FollowState:
     def replan(self, rows, waypoints, n_waypoints=None, release=None):
         """New waypoints for the robots `rows` ([m] indices): waypoints [m][K'][P] or [K'][P] (the same for each), counts
         n_waypoints [m] (None: K' each).  Those robots start over on their new rows -- reached = 0, arrival = -1, leg_used = 0 --
-        and keep position, velocity, reward sum, steps run, hazard sums, team sums and the wall record.  K grows when K' is larger.
+        and keep position, velocity, reward sum, steps run, hazard sums, team sums and the wall and blocked records.  K grows when K' is larger.
         In a scheduled run the replanned rows get `release` ([m][K'] or [K'] global steps; None: 0, released at once), their
         `home` becomes where they are, and the hold record is carried.  `release` on a run without a schedule is refused."""
         rows = np.atleast_1d(np.asarray(rows))
@@ -244,6 +264,15 @@ def _check_run(state, leg_steps, max_steps, hazards, teams=None, schedule=None, 
         walls.check_robots(state.n_robots)
         if np.shape(state.wall) != (state.n_robots, 7):
             raise ValueError("state.wall must be [n_robots][7]")
+    solid = walls is not None and bool(getattr(walls, "solid", False))
+    if (getattr(state, "blocked", None) is None) == solid:
+        raise ValueError("a run has solid walls in every call or in none (FollowState(..., walls=Walls(..., solid=True)))")
+    if solid:
+        from .envs.goal_rules import MovingHazards
+        if isinstance(hazards, MovingHazards):
+            raise ValueError("solid=True does not run with MovingHazards yet (static hazards, teams and schedules do)")
+        if np.shape(state.blocked) != (state.n_robots, 4):
+            raise ValueError("state.blocked must be [n_robots][4]")
     if (getattr(state, "release", None) is None) != (schedule is None):
         raise ValueError("a run has a schedule in every call or in none (FollowState(..., schedule=Schedule))")
     if schedule is not None:
@@ -269,6 +298,34 @@ def _status(k, nw, leg_used, leg_steps):
     return NO_WAYPOINTS if nw == 0 else FINISHED if k >= nw else STALLED if leg_steps > 0 and leg_used >= leg_steps else GOING
 
 
+def _solid_step(env, action, pre, rows, radius):
+    """EnvWrapper.step with solid walls: the simulator's own step, goal_rules.wall_block on (pre-step xy, proposed xy), the kept
+    axes at the simulator's precision and the dropped ones put back with zero velocity, then EnvWrapper.step's tail (reward
+    against the goal in force, hazard cost) at the resolved position.  Functionally the rule; not bit-matched to the device.
+    -> (reward, info, code, inside)"""
+    from .envs import goal_rules as rules
+    if not (hasattr(env.env, "pos") and hasattr(env.env, "vel")):
+        raise TypeError("solid walls need a simulator whose position and velocity can be set (env.env.pos, env.env.vel)")
+    _, _, _, _, info = env.env.step(action)
+    prop = np.asarray(env.get_pos(), np.float64)
+    _, code, inside = rules.wall_block(pre[:2], prop[:2], rows, radius)
+    code = int(code)
+    if code:
+        vel = np.array(env.env.vel, np.float64)
+        for axis, bit in ((0, 2), (1, 1)):               # x is dropped by codes 2 and 3, y by 1 and 3
+            if code & bit:
+                prop[axis], vel[axis] = pre[axis], 0.0
+        env.set_pos(prop)
+        env.env.vel = vel
+    reward = env.reward_fn()
+    hz = getattr(env, "_hazards", None)
+    if hz is not None:
+        cost, _ = rules.hazard_cost(env.get_pos(), hz.rows(), hz.cost, hz.indicator)
+        info = dict(info)
+        info["cost_hazards"] = info["cost"] = float(cost)
+    return reward, info, code, bool(inside)
+
+
 def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards=None, leg_steps=0, teams=None,
                  schedule=None, walls=None):
     """The semantics, one robot after another on EnvWrapper's public API (make_env(i) -> the robot's env): one call of the run
@@ -281,8 +338,10 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
     is taken, a hold step skips the reward sum, the arrival and the leg count, and goal_rules.schedule_fold folds the hold
     record from the anchors and the float32 positions after the hold steps.
     With `walls` every step's float32 x, y before and after it are kept and goal_rules.wall_fold applies wall_check per step after
-    the last robot."""
-    from .envs.goal_rules import MovingHazards, hazard_cost, schedule_fold, team_fold, wall_fold
+    the last robot.  With walls.solid every step is _solid_step (wall_block inside the step) and the blocked record is folded
+    by goal_rules.wall_blocked_fold."""
+    from .envs.goal_rules import MovingHazards, hazard_cost, schedule_fold, team_fold, wall_blocked_fold, wall_fold
+    solid = walls is not None and bool(getattr(walls, "solid", False))
     st = state.copy()
     st.state = st.state.astype(np.float64)              # the host simulator's own precision, carried exactly
     wp, nw, step0 = st.waypoints, st.n_waypoints, st.step0
@@ -299,6 +358,7 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
     if walls is not None:
         wall_pre, wall_post = np.zeros((max_steps, n, 2), np.float32), np.zeros((max_steps, n, 2), np.float32)
         wall_stepped = np.zeros((max_steps, n), bool)
+        wall_code, wall_inside = np.zeros((max_steps, n), np.int64), np.zeros((max_steps, n), bool)
     if schedule is not None:
         rel, home = st.release, st.home
         held, held_anchor, held_pos = np.zeros((max_steps, n), bool), np.zeros((max_steps, n, P), np.float32), np.zeros((max_steps, n, P), np.float32)
@@ -338,7 +398,10 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
                 a, _ = model.predict(obs, deterministic=deterministic)
                 if walls is not None:
                     wall_pre[t, i, :min(P, 2)] = pos[:2]
-                _, r, _, _, info = env.step(a)
+                if solid:
+                    r, info, wall_code[t, i], wall_inside[t, i] = _solid_step(env, a, pos, walls.rows(i), walls.radius)
+                else:
+                    _, r, _, _, info = env.step(a)
                 if not hold:                           # a hold step's reward is progress towards a place the robot waits at
                     st.robot[i, 0] += float(r)
                 st.robot[i, 1] += 1
@@ -388,6 +451,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
         st.sched = schedule_fold(st.sched, held_anchor, held_pos, held)
     if walls is not None:
         st.wall = wall_fold(st.wall, wall_pre, wall_post, wall_stepped, walls, step0)
+    if solid:
+        st.blocked = wall_blocked_fold(st.blocked, wall_code, wall_inside, wall_stepped, step0).astype(np.int32)
     st.step0 = step0 + max_steps
     out = {"arrival": st.arrival.astype(np.int64), "reached": st.reached, "steps": st.robot[:, 1].astype(np.int64),
            "reward_sum": st.robot[:, 0].copy(), "final_distance": final_distance, "trace": None, "persistent": None,
@@ -401,6 +466,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
         out.update(schedule_result(st))
     if walls is not None:
         out.update(wall_result(st))
+    if solid:
+        out.update(blocked_result(st))
     if path is not None:
         out["path"] = path
     return out
@@ -412,6 +479,13 @@ def wall_result(state):
     return {"wall_cost_sum": w[:, 0].copy(), "contact_steps": w[:, 1].astype(np.int64), "first_contact": w[:, 2].astype(np.int64),
             "min_wall_clearance": w[:, 3].copy(), "closest_wall": w[:, 4].astype(np.int64), "crossing_steps": w[:, 5].astype(np.int64),
             "first_crossing": w[:, 6].astype(np.int64)}
+
+
+def blocked_result(state):
+    """The keys a run with solid walls adds to a call's dict, from the state after the call (state.blocked [n][4])."""
+    b = np.asarray(state.blocked)
+    return {"wall_blocked_steps": b[:, 0].astype(np.int64), "wall_first_blocked": b[:, 1].astype(np.int64),
+            "wall_stopped_steps": b[:, 2].astype(np.int64), "wall_inside_steps": b[:, 3].astype(np.int64)}
 
 
 def schedule_result(state):
@@ -451,7 +525,7 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
     if isinstance(env, DeviceGoalVecEnv):
         if state is None:
             state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams is not None, schedule,
-                                walls is not None)
+                                walls if walls is not None else False)
         _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
         return env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
                           path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps, teams=teams,
@@ -472,7 +546,8 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         def make_env(i):
             return env
     if state is None:
-        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule, walls is not None)
+        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule,
+                            walls if walls is not None else False)
     elif isinstance(state, FollowState) and state.waypoints.shape[2] != pos_dim:
         raise ValueError(f"state has {state.waypoints.shape[2]} position dimensions, the environment {pos_dim}")
     leg_steps = _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
