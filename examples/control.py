@@ -58,11 +58,13 @@ def simulate(env_name, policy_name="ppo", epochs=5, no_gui=True, video_path=None
     return rewards
 
 
-def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None, seed=0, hazards=None):
+def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None, seed=0, hazards=None, tile256=False):
     """The protocol of `simulate` for max(robots, epochs) robots in one device evaluation (PPOEngine.evaluate_goal_env)."""
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
     policy = load_policy(env_name, policy_name) if policy is None else policy
+    if tile256:   # a 2x256 tanh policy: the evaluation (without hazards) as one launch; ValueError on any other policy
+        policy.engine.set_eval_tile256(True)
     n = max(int(robots), int(epochs))
     env = DeviceGoalVecEnv.for_robot(env_name, n, time_limit=0, seed=seed, terminate_on_goal=True)
     from mobrob_amd.envs.goal_rules import Hazards
@@ -79,7 +81,7 @@ def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None
     return rewards
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env-name", type=str, default="point")
     ap.add_argument("--policy-name", type=str, default="ppo")
@@ -89,11 +91,20 @@ if __name__ == "__main__":
     ap.add_argument("--robots", type=int, default=None,
                     help="evaluate max(ROBOTS, epochs) robots at once on the device (one engine call)")
     ap.add_argument("--hazards", type=str, default=None, help="[M][2] hazard centres (.npy), with --robots: report hazard costs")
+    ap.add_argument("--tile256", action="store_true", default=False,
+                    help="with --robots, a 2x256 tanh policy: the evaluation as one launch (PPOEngine.set_eval_tile256)")
+    return ap
+
+
+if __name__ == "__main__":
+    ap = build_parser()
     a = ap.parse_args()
     if a.hazards is not None and a.robots is None:
         ap.error("--hazards needs --robots (the device evaluation)")
+    if a.tile256 and a.robots is None:
+        ap.error("--tile256 needs --robots (the device evaluation)")
     if a.robots is not None:
         simulate_device(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, robots=a.robots,
-                        hazards=None if a.hazards is None else np.load(a.hazards))
+                        hazards=None if a.hazards is None else np.load(a.hazards), tile256=a.tile256)
         sys.exit(0)
     simulate(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, no_gui=a.no_gui, video_path=a.video_path)

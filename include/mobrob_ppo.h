@@ -1244,6 +1244,15 @@ int mobrob_ppo_x3_mode(const mobrob_ppo_engine_t* e);
  * mobrob_ppo_train_enqueue (no snapshot) fails at the next synchronising call instead. */
 int mobrob_ppo_update_mode(const mobrob_ppo_engine_t* e);
 
+/* Switches the one-launch evaluation / waypoint-following kernel of fused 2x256 tanh engines (k_goal256_tile, csrc/kernels_eval256.h)
+ * on or off for this engine.  It is OFF unless told: with it on, mobrob_ppo_evaluate_goal_env, mobrob_ppo_follow_waypoints, _resume and
+ * _scheduled calls without hazards, teams or walls run as one launch and return 1 (persistent); every other call runs the per-step
+ * path as before and returns 0.  The actor of that kernel is f32 MFMA with the fast tanh of the 2x64 tile kernel: results agree with the
+ * per-step path to float32 rounding, not bit for bit; the same call repeated, or a run split into calls, gives the same bits.  An engine
+ * that was never told follows the environment variable MOBROB_EVAL_TILE256 (1: on), read per call; MOBROB_EVAL_PERSISTENT=0 forces the
+ * per-step path whatever is set here.  MOBROB_ERR_INVALID (naming tile256) on an engine that is not fused 2x256 tanh. */
+int mobrob_ppo_set_eval_tile256(mobrob_ppo_engine_t* e, int32_t on);
+
 /* train/explained_variance as SB3's PPO.train logs it (stable_baselines3 2.0.0 ppo.py: explained_variance(rollout_buffer.values.flatten(),
  * rollout_buffer.returns.flatten()) = 1 - Var[returns - values] / Var[returns], NaN when the returns do not vary), over the rollout
  * in the buffer; reached from the reference through PPOCtrl.learn (src/mobrob/rl_control/ppo.py:73-74) with verbose / tensorboard_log

@@ -51,6 +51,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_env.h"
 #include "kernels_eval.h"
 #include "kernels_follow.h"
+#include "kernels_eval256.h"
 #include "kernels_hazard.h"
 #include "kernels_team.h"
 #include "kernels_wall.h"
@@ -271,6 +272,7 @@ struct mobrob_ppo_engine {
   // policy evaluation (mobrob_ppo_evaluate_goal_env): one hipMalloc of its own, outside the arena, grown on demand
   char* eval_buf = nullptr;
   size_t eval_bytes = 0;
+  int eval_tile256 = -1;   // mobrob_ppo_set_eval_tile256: 1 on, 0 off, -1 not told (MOBROB_EVAL_TILE256 decides, read per call)
   // grid planner (mobrob_ppo_plan_grid): two allocations of its own, outside the arena, grown on demand.  plan_fields holds what
   // a replanning round reuses (occupancy, fields, their scenes, goal cells and sweep counts), plan_buf a call's inputs and outputs
   char* plan_fields = nullptr;
@@ -1691,6 +1693,15 @@ int mobrob_ppo_x3_mode(const mobrob_ppo_engine_t* e) {
 }
 
 int mobrob_ppo_update_mode(const mobrob_ppo_engine_t* e) { return e ? e->last_update_mode : 0; }
+
+int mobrob_ppo_set_eval_tile256(mobrob_ppo_engine_t* e, int32_t on) {
+  if (!e) return fail(MOBROB_ERR_INVALID, "set_eval_tile256: null engine");
+  if (!(e->fused.enabled && e->fused.H == FH))
+    return fail(MOBROB_ERR_INVALID, "set_eval_tile256: the tile256 kernel serves fused 2x256 tanh engines only (this one: %s)",
+                e->fused.enabled ? "fused 2x64" : "not of the fused family");
+  e->eval_tile256 = on != 0;
+  return MOBROB_OK;
+}
 
 int mobrob_ppo_explained_variance(mobrob_ppo_engine_t* e, double* out) {
   if (!e || !out) return fail(MOBROB_ERR_INVALID, "explained_variance: null argument");
@@ -3332,7 +3343,24 @@ static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, voi
   const int N = a.N;
   // MOBROB_EVAL_PERSISTENT=0: the per-step path on every engine (A/B, tests); read per call
   const bool persistent = e->fused.enabled && e->fused.H == 64 && env_int("MOBROB_EVAL_PERSISTENT", 1) != 0;
-  if (persistent) {
+  // k_goal256_tile (kernels_eval256.h): fused 2x256 tanh engines, the non-wide tasks, and only when switched on
+  bool tile256 = false;
+  if constexpr (task_tile256<Task>)
+    tile256 = e->fused.enabled && e->fused.H == FH && env_int("MOBROB_EVAL_PERSISTENT", 1) != 0 &&
+              (e->eval_tile256 >= 0 ? e->eval_tile256 != 0 : env_int("MOBROB_EVAL_TILE256", 0) != 0);
+  if (tile256) {
+    if constexpr (task_tile256<Task>) {
+      const size_t lds_bytes = eval256_lds_bytes();
+      int limit = 0;
+      if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+      if (lds_bytes > (size_t)limit)
+        return fail(MOBROB_ERR_INVALID, "eval tile256: k_goal256_tile needs %zu bytes of LDS, the device allows %d per workgroup (switch it off: mobrob_ppo_set_eval_tile256)",
+                    lds_bytes, limit);
+      HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_goal256_tile<Task>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+      const Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
+      hipLaunchKernelGGL(k_goal256_tile<Task>, dim3(cdiv(N, 16)), dim3(256), lds_bytes, e->stream, args, W);
+    }
+  } else if (persistent) {
     Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
     if constexpr (task_solid<Task>) {
       const int Dt = eval_tile_width(a.Dp, true);   // never 16
@@ -3359,7 +3387,7 @@ static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, voi
     if (fin) hipLaunchKernelGGL(fin, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, args);
   }
   HIPC(hipGetLastError());
-  return persistent ? 1 : 0;
+  return persistent || tile256 ? 1 : 0;
 }
 
 // robot_out and the trace back to the caller; returns `ran` (eval_run's) once everything enqueued on the stream is done

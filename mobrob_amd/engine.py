@@ -1233,6 +1233,20 @@ class PPOEngine:
         """Bit 0: the latest train() ran every epoch as one co-operative launch (k_epoch64) instead of three launches per step."""
         return int(self.lib.mobrob_ppo_update_mode(self._h))
 
+    def set_eval_tile256(self, on):
+        """Switch the one-launch evaluation / following kernel of fused 2x256 tanh engines (k_goal256_tile) on or off for this
+        engine: evaluate_goal_env and follow_waypoints calls without hazards, teams or walls then report `persistent` True.  Off
+        unless told (or MOBROB_EVAL_TILE256=1 for engines never told).  ValueError naming tile256 on any other engine."""
+        if not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"eval_tile256 must be a bool, got {type(on).__name__}")
+        check(self.lib.mobrob_ppo_set_eval_tile256(self._h, int(bool(on))))
+        self._eval_tile256 = bool(on)
+
+    @property
+    def eval_tile256(self):
+        """What set_eval_tile256 was told last (False: never told)."""
+        return bool(getattr(self, "_eval_tile256", False))
+
     def explained_variance(self):
         """1 - Var[returns - values] / Var[returns] over the rollout in the buffer (SB3's train/explained_variance)."""
         out = C.c_double()
