@@ -282,6 +282,51 @@ def selector_rows(mag=1e30):
     return obs
 
 
+# ---- tanh: layer 2 of the evaluation tiles (k_goal64_tile, k_goal256_tile) through a bias-saturated layer 1 ----------------
+# The tiles build their own observations, so no selector row reaches them.  Instead W1 = 0 and b1 = +TILE_B1 make every h1[k] the
+# saturated 1, whatever the observation; W2[u, k] = z for ONE k per probed unit u (all else 0, b2 = 0) gives z2[u] = z exactly, through
+# the layer-2 MFMA and, on the 256 tile, the register-resident fragment element (u, k); W3[a, u_a] = 1 (b3 = 0) hands tanh(z2[u_a]) back
+# as action a -- the head, and the 256 tile's fixed-order sum of four partials, add only zeros.  Layer 1 is the saturated selector here
+# and nothing more: this is no per-unit probe of layer 1.
+TILE_B1 = 30.0
+
+
+def tile_points(pts_pos=None):
+    """every probe point in both signs (-0.0 included)"""
+    pos = TANH_POS if pts_pos is None else pts_pos
+    return np.concatenate([pos, -pos]).astype(F32)
+
+
+def _tile_probe(j, H, pts):
+    """probe j -> (unit, k, z): unit j % H, so that any A <= H consecutive probes sit on distinct units; the first H probes show every
+    unit a point with |z| >= 20, the next H one with |z| < 1, the rest walk through all points; k = (5 j + 3) % H walks through every
+    column of W2 (5 is coprime to H = 64 and 256), so through all four k-quarters l >> 4 of every fragment k-step."""
+    big, small = pts[np.abs(pts) >= 20.0], pts[np.abs(pts) < 1.0]
+    z = big[j % len(big)] if j < H else small[j % len(small)] if j < 2 * H else pts[(j - 2 * H) % len(pts)]
+    return j % H, (5 * j + 3) % H, F32(z)
+
+
+def tile_launches(A, H, pts_pos=None):
+    """launches of A probes each that cover tile_points on top of the two per-unit passes"""
+    return -(-(2 * H + len(tile_points(pts_pos))) // A)
+
+
+def tile_probe(D, A, H, launch, pts_pos=None):
+    """-> (params of a 2 x H tanh network over D observation features, units [A], columns k [A], points z [A]) of one launch"""
+    assert A <= H
+    pts = tile_points(pts_pos)
+    p = zero_params(D, A, (H, H), (H, H))
+    p[f"{PI}.0.bias"][:] = TILE_B1
+    units, ks, zs = [], [], []
+    for a in range(A):
+        u, k, z = _tile_probe(launch * A + a, H, pts)
+        p[f"{PI}.2.weight"][u, k] = z
+        p["action_net.weight"][a, u] = 1.0
+        units.append(u), ks.append(k), zs.append(z)
+    assert len(set(units)) == A
+    return p, np.array(units), np.array(ks), np.array(zs, F32)
+
+
 # ---- the backward probe's minibatch and its float64 factor ------------------------------------------
 ADV, RET_GAP = 2.0 ** 22, 1.0
 VF_COEF = 2.0 ** 20      # with HEAD_W = 2^-21 and the gap of 1: the value net's factor is 2 * 2^20 * 2^-21 = 1, the policy net's 2^22 * 0.5 * 2^-21 = 1 per action

@@ -16,6 +16,14 @@ the 1 - h^2 of the backward, to h == +-1 exactly from |z| = 20 on and to finite 
 backward k_split64_train, k_fused64_train, k_pair64_train, k_epoch64: 2.40e-7; k_chain_train, k_fused_train x3 and f32: 2.44e-7, at
 the same point.  The claim holds.  Layer 2 of the generic chain stays inside layer 1's figures (worst mish backward 1.96).
 
+The two one-launch evaluation tiles came later and build their own observations, so no selector row reaches them: their layer 2 is
+probed through a bias-saturated layer 1 (tests/act_probe.py tile_probe) and read back as the traced action of a one-step evaluation.
+Every layer-2 unit, every point of TANH_POS in both signs, every column of W2 (all k-quarters of the fragment; on the 256 tile the
+register-resident slice, a quarter of it in AGPRs).  Measured: k_goal64_tile<16>, <32>, <48>, <64> (point, car, turtlebot3, doggo),
+<16> with two head blocks (drone), k_goal256_tile with one and two head blocks (doggo, drone): 1.42e-7 at z = -0.999 each, exactly
++-1 from |z| = 20 on, finite with 1e30 in W2.  Layer 1 of the tiles is exercised as the saturated selector only: there is no
+per-unit probe of their layer 1 here.
+
 Hidden widths 72 and 40 are no multiples of the 32-wide fragment, so clamped lanes are in play; the probed units sit on both sides of
 every fragment edge and at the last column.
 """
@@ -308,3 +316,55 @@ def test_tanh_family_backward(name, H, x3, env, B, how, monkeypatch):
     assert seen == set(pts.astype(np.float64).tolist())
     print(f"{name}: 1 - h^2 worst absolute error {worst[0]:.3e} at z = {worst[1]:.4g} (bound {P.TANH_BWD_ABS:.3e})")
     assert worst[0] <= P.TANH_BWD_ABS, (name, worst)
+
+
+# ------------------------------------------------------------------------------------------------
+# the one-launch evaluation tiles (k_goal64_tile at its four observation widths, k_goal256_tile): they build their own observations,
+# so layer 2 is reached through a bias-saturated layer 1 (tests/act_probe.py tile_probe) and read back as the traced action of a
+# one-step evaluation of 16 robots
+# ------------------------------------------------------------------------------------------------
+# (kernel, robot: its D picks the tile width and its A the head blocks, hidden width)
+TILE_ACTORS = [("k_goal64_tile<16>", "point", 64), ("k_goal64_tile<32>", "car", 64), ("k_goal64_tile<48>", "turtlebot3", 64),
+               ("k_goal64_tile<64>", "doggo", 64), ("k_goal64_tile<16> two head blocks", "drone", 64),
+               ("k_goal256_tile", "doggo", 256), ("k_goal256_tile two head blocks", "drone", 256)]
+
+
+@pytest.mark.parametrize("name,robot,H", TILE_ACTORS, ids=[f"{c[1]}{c[2]}" for c in TILE_ACTORS])
+def test_tile_actor_forward(name, robot, H, monkeypatch):
+    """fast_tanh of layer 2 in both tile actors, the assertions of test_tanh_family_forward: 2e-7 absolute against float64, exactly
+    +-1 from |z| = 20 on, finite with 1e30 in W2.  Every layer-2 unit is probed, each with a point of |z| >= 20 and one of |z| < 1;
+    every point of TANH_POS is seen in both signs; the chosen column k of W2 walks through every k-step and k-quarter (on the 256
+    tile: through the register-resident fragment; the probed units cover all four waves' head slices).  Layer 1 is exercised as
+    the saturated selector only."""
+    from mobrob_amd.engine import PPOEngine
+    from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
+    from mobrob_amd.envs.wrapper import ROBOT_DIMS
+    monkeypatch.delenv("MOBROB_EVAL_PERSISTENT", raising=False)
+    D, A, _ = ROBOT_DIMS[robot]
+    R = 16
+    e = PPOEngine(obs_dim=D, act_dim=A, n_envs=R, n_steps=16, batch_size=64, n_epochs=1, pi=(H, H), vf=(H, H))   # action bounds +-1
+    if H == 256:
+        e.set_eval_tile256(True)
+    env = DeviceGoalVecEnv.for_robot(robot, R, time_limit=0, seed=1)
+    worst, saturated = (0.0, 0.0), 0
+    big, small, cols, seen = np.zeros(H, bool), np.zeros(H, bool), set(), set()
+    for i in range(P.tile_launches(A, H)):
+        p, units, ks, z = P.tile_probe(D, A, H, i)
+        e.set_params(p)
+        r = env.evaluate(e, n_robots=R, max_steps=1, trace=(R, 1), seed=i)
+        assert r["persistent"] is True
+        act = r["trace"][0, :, 9 + D:9 + D + A]
+        assert np.array_equal(act, np.broadcast_to(act[0], act.shape)), (name, i, "the robots of a tile differ")
+        w = _check_tanh_forward(name, act, np.broadcast_to(z, act.shape))
+        worst, saturated = max(worst, w[:2]), saturated + w[2]
+        big[units[np.abs(z) >= 20.0]] = True
+        small[units[np.abs(z) < 1.0]] = True
+        cols |= set(ks.tolist())
+        seen |= {(float(abs(v)), bool(np.signbit(v))) for v in z}
+    e.close()
+    assert big.all() and small.all(), (name, "units without a tail point or a small one", np.flatnonzero(~(big & small)))
+    assert cols == set(range(H)), (name, "columns of W2 never chosen")
+    assert seen == {(float(v), s) for v in P.TANH_POS for s in (False, True)}
+    assert saturated > 0
+    print(f"{name}: fast_tanh worst absolute error {worst[0]:.3e} at z = {worst[1]:.4g} (claim {P.TANH_FWD_ABS:.1e})")
+    assert worst[0] <= P.TANH_FWD_ABS, (name, worst)
