@@ -58,13 +58,15 @@ def simulate(env_name, policy_name="ppo", epochs=5, no_gui=True, video_path=None
     return rewards
 
 
-def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None, seed=0, hazards=None, tile256=False):
+def simulate_device(env_name, policy_name="ppo", epochs=5, robots=1, policy=None, seed=0, hazards=None, tile256=False, tile256_wide=False):
     """The protocol of `simulate` for max(robots, epochs) robots in one device evaluation (PPOEngine.evaluate_goal_env)."""
     from mobrob_amd import load_policy
     from mobrob_amd.envs.vec_env import DeviceGoalVecEnv
     policy = load_policy(env_name, policy_name) if policy is None else policy
-    if tile256:   # a 2x256 tanh policy: the evaluation (without hazards) as one launch; ValueError on any other policy
+    if tile256 or tile256_wide:   # a 2x256 tanh policy: the evaluation (without hazards) as one launch; ValueError on any other policy
         policy.engine.set_eval_tile256(True)
+    if tile256_wide:   # ... and with --hazards too (implies tile256)
+        policy.engine.set_eval_tile256_wide(True)
     n = max(int(robots), int(epochs))
     env = DeviceGoalVecEnv.for_robot(env_name, n, time_limit=0, seed=seed, terminate_on_goal=True)
     from mobrob_amd.envs.goal_rules import Hazards
@@ -93,6 +95,8 @@ def build_parser():
     ap.add_argument("--hazards", type=str, default=None, help="[M][2] hazard centres (.npy), with --robots: report hazard costs")
     ap.add_argument("--tile256", action="store_true", default=False,
                     help="with --robots, a 2x256 tanh policy: the evaluation as one launch (PPOEngine.set_eval_tile256)")
+    ap.add_argument("--tile256-wide", action="store_true", default=False,
+                    help="... and the evaluation with --hazards as well (PPOEngine.set_eval_tile256_wide); implies --tile256")
     return ap
 
 
@@ -101,10 +105,11 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.hazards is not None and a.robots is None:
         ap.error("--hazards needs --robots (the device evaluation)")
-    if a.tile256 and a.robots is None:
-        ap.error("--tile256 needs --robots (the device evaluation)")
+    if (a.tile256 or a.tile256_wide) and a.robots is None:
+        ap.error("--tile256 / --tile256-wide need --robots (the device evaluation)")
     if a.robots is not None:
         simulate_device(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, robots=a.robots,
-                        hazards=None if a.hazards is None else np.load(a.hazards), tile256=a.tile256)
+                        hazards=None if a.hazards is None else np.load(a.hazards), tile256=a.tile256 or a.tile256_wide,
+                        tile256_wide=a.tile256_wide)
         sys.exit(0)
     simulate(env_name=a.env_name, policy_name=a.policy_name, epochs=a.epochs, no_gui=a.no_gui, video_path=a.video_path)

@@ -93,7 +93,8 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            horizon=None, leg_steps=0, hazard_frames=None, frame_steps=1, hazard_loop=False, team_size=None, separation=0.3,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
-           plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False):
+           plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False,
+           tile256_wide=False):
     if solid and walls is None and not arena:
         raise ValueError("--solid needs --walls or --arena")
     calls = check_chain(max_steps, horizon, leg_steps)
@@ -109,8 +110,10 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     from mobrob_amd.envs.wrapper import ROBOT_DIMS, KinematicSim
     from mobrob_amd.waypoints import follow_waypoints
     policy = load_policy(env_name, policy_name) if policy is None else policy
-    if tile256:   # a 2x256 tanh policy: calls without hazards, teams or walls run as one launch (ValueError on any other policy)
+    if tile256 or tile256_wide:   # a 2x256 tanh policy: calls without hazards, teams or walls run as one launch (ValueError on any other policy)
         getattr(policy, "engine", policy).set_eval_tile256(True)
+    if tile256_wide:   # ... and calls with hazards too (implies tile256); walls and teams stay on the per-step path
+        getattr(policy, "engine", policy).set_eval_tile256_wide(True)
     d, a, p = ROBOT_DIMS[env_name]
     extent = KinematicSim(d, a, p).extent
     start = np.random.default_rng(seed).uniform(-extent / 2, extent / 2, (int(robots), p))   # the env's init_space
@@ -300,6 +303,8 @@ def build_parser():
     ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
     ap.add_argument("--tile256", action="store_true", default=False,
                     help="a 2x256 tanh policy: run calls without hazards, teams or walls as one launch (PPOEngine.set_eval_tile256)")
+    ap.add_argument("--tile256-wide", action="store_true", default=False,
+                    help="... and calls WITH hazards as well (PPOEngine.set_eval_tile256_wide); implies --tile256; walls and teams stay per step")
     return ap
 
 
@@ -327,4 +332,4 @@ if __name__ == "__main__":
            plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg,
            plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
            plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid,
-           tile256=args.tile256)
+           tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide)

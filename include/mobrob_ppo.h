@@ -1253,6 +1253,18 @@ int mobrob_ppo_update_mode(const mobrob_ppo_engine_t* e);
  * per-step path whatever is set here.  MOBROB_ERR_INVALID (naming tile256) on an engine that is not fused 2x256 tanh. */
 int mobrob_ppo_set_eval_tile256(mobrob_ppo_engine_t* e, int32_t on);
 
+/* The same kernel for calls WITH hazards, static or moving (the *_hazards and *_hazard_frames entry points).  A switch of its own,
+ * OFF unless told: such a call runs as one launch and returns 1 only when tile256 is in force (mobrob_ppo_set_eval_tile256 or
+ * MOBROB_EVAL_TILE256) AND this switch is (told here, or MOBROB_EVAL_TILE256_WIDE=1 for engines never told, read per call),
+ * MOBROB_EVAL_PERSISTENT is not 0, and the task's shared scene fits the LDS left beside the actor (13 424 bytes: every shared hazard
+ * scene fits; per-robot scenes are read from global memory).  Served: mobrob_ppo_evaluate_goal_env and mobrob_ppo_follow_waypoints
+ * with static or moving hazards, resumed runs with moving hazards, scheduled runs with static hazards.  NOT served, whatever is set
+ * here: calls with walls (observational or solid) or teams, resumed runs with static hazards, scheduled runs with moving hazards
+ *  -- they run the per-step path as before and return 0; none is refused.  The hazard records are the bits the
+ * per-step path gives for the same positions; positions agree with it to float32 rounding, as for the non-wide tasks.
+ * MOBROB_ERR_INVALID (naming tile256) on a null engine and on an engine that is not fused 2x256 tanh. */
+int mobrob_ppo_set_eval_tile256_wide(mobrob_ppo_engine_t* e, int32_t on);
+
 /* train/explained_variance as SB3's PPO.train logs it (stable_baselines3 2.0.0 ppo.py: explained_variance(rollout_buffer.values.flatten(),
  * rollout_buffer.returns.flatten()) = 1 - Var[returns - values] / Var[returns], NaN when the returns do not vary), over the rollout
  * in the buffer; reached from the reference through PPOCtrl.learn (src/mobrob/rl_control/ppo.py:73-74) with verbose / tensorboard_log

@@ -262,6 +262,7 @@ SYMBOLS = {
     "mobrob_ppo_x3_mode": (C.c_int, [_P]),
     "mobrob_ppo_update_mode": (C.c_int, [_P]),
     "mobrob_ppo_set_eval_tile256": (C.c_int, [_P, C.c_int32]),
+    "mobrob_ppo_set_eval_tile256_wide": (C.c_int, [_P, C.c_int32]),
     "mobrob_ppo_feistel_permutation": (C.c_int, [_P, C.c_int64, C.c_uint64, _I64]),
     "mobrob_ppo_profile_enable": (C.c_int, [_P, C.c_int32]),
     "mobrob_ppo_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), _I64]),

@@ -273,6 +273,7 @@ struct mobrob_ppo_engine {
   char* eval_buf = nullptr;
   size_t eval_bytes = 0;
   int eval_tile256 = -1;   // mobrob_ppo_set_eval_tile256: 1 on, 0 off, -1 not told (MOBROB_EVAL_TILE256 decides, read per call)
+  int eval_tile256_wide = -1;   // mobrob_ppo_set_eval_tile256_wide: likewise (MOBROB_EVAL_TILE256_WIDE); the wide tasks need both
   // grid planner (mobrob_ppo_plan_grid): two allocations of its own, outside the arena, grown on demand.  plan_fields holds what
   // a replanning round reuses (occupancy, fields, their scenes, goal cells and sweep counts), plan_buf a call's inputs and outputs
   char* plan_fields = nullptr;
@@ -1700,6 +1701,15 @@ int mobrob_ppo_set_eval_tile256(mobrob_ppo_engine_t* e, int32_t on) {
     return fail(MOBROB_ERR_INVALID, "set_eval_tile256: the tile256 kernel serves fused 2x256 tanh engines only (this one: %s)",
                 e->fused.enabled ? "fused 2x64" : "not of the fused family");
   e->eval_tile256 = on != 0;
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_set_eval_tile256_wide(mobrob_ppo_engine_t* e, int32_t on) {
+  if (!e) return fail(MOBROB_ERR_INVALID, "set_eval_tile256_wide: null engine");
+  if (!(e->fused.enabled && e->fused.H == FH))
+    return fail(MOBROB_ERR_INVALID, "set_eval_tile256_wide: the tile256 kernel serves fused 2x256 tanh engines only (this one: %s)",
+                e->fused.enabled ? "fused 2x64" : "not of the fused family");
+  e->eval_tile256_wide = on != 0;
   return MOBROB_OK;
 }
 
@@ -3343,12 +3353,29 @@ static int eval_run(mobrob_ppo_engine_t* e, const typename Task::Args& args, voi
   const int N = a.N;
   // MOBROB_EVAL_PERSISTENT=0: the per-step path on every engine (A/B, tests); read per call
   const bool persistent = e->fused.enabled && e->fused.H == 64 && env_int("MOBROB_EVAL_PERSISTENT", 1) != 0;
-  // k_goal256_tile (kernels_eval256.h): fused 2x256 tanh engines, the non-wide tasks, and only when switched on
+  // k_goal256_tile (kernels_eval256.h): fused 2x256 tanh engines, and only when switched on.  The non-wide tasks ...
   bool tile256 = false;
   if constexpr (task_tile256<Task>)
     tile256 = e->fused.enabled && e->fused.H == FH && env_int("MOBROB_EVAL_PERSISTENT", 1) != 0 &&
               (e->eval_tile256 >= 0 ? e->eval_tile256 != 0 : env_int("MOBROB_EVAL_TILE256", 0) != 0);
+  // ... and the wide tasks of task_tile256_wide (hazards), when the wide switch is in force as well and the task's LDS region
+  // fits behind the tile's; a call that does not fit takes the per-step path, as every such call did before
+  if constexpr (task_tile256_wide<Task>) {
+    if (e->fused.enabled && e->fused.H == FH && env_int("MOBROB_EVAL_PERSISTENT", 1) != 0 &&
+        (e->eval_tile256 >= 0 ? e->eval_tile256 != 0 : env_int("MOBROB_EVAL_TILE256", 0) != 0) &&
+        (e->eval_tile256_wide >= 0 ? e->eval_tile256_wide != 0 : env_int("MOBROB_EVAL_TILE256_WIDE", 0) != 0)) {
+      int limit = 0;
+      if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+      tile256 = eval256_lds_bytes() + Task::tile_lds_bytes(args) <= (size_t)limit;
+    }
+  }
   if (tile256) {
+    if constexpr (task_tile256_wide<Task>) {
+      const size_t lds_bytes = eval256_lds_bytes() + Task::tile_lds_bytes(args);
+      HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_goal256_tile<Task>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+      const Eval64Net W{Pp(e, e->tPW[0]), Pp(e, e->tPB[0]), Pp(e, e->tPW[1]), Pp(e, e->tPB[1]), Pp(e, T_AW), Pp(e, T_AB)};
+      hipLaunchKernelGGL(k_goal256_tile<Task>, dim3(cdiv(N, 16)), dim3(256), lds_bytes, e->stream, args, W);
+    }
     if constexpr (task_tile256<Task>) {
       const size_t lds_bytes = eval256_lds_bytes();
       int limit = 0;

@@ -2,7 +2,12 @@
 //
 // The tasks, the environment rules, the observation features, the action rule and the trace row are those of kernels_eval.h /
 // kernels_follow.h, used unchanged; only the actor is new.  Served: the non-wide tasks (EvalTask, FollowTask, ResumeFollowTask,
-// ScheduledFollowTask).  The wide tasks' after_step is written for a workgroup of one wave and stays on the per-step path.
+// ScheduledFollowTask) and, behind a switch of their own, the wide tasks of task_tile256_wide: static and moving hazards over
+// most of those four.  The kernel is written for every wide task (walls, solid walls, teams and their stacks too: the hooks below are all
+// there), but the tiles of WallTask / TeamTask spill vector registers and are not instantiated (tile256_wide_left_out): they stay
+// on the per-step path.  A wide task's hooks are written for one 64-lane wave and take plain LDS pointers: here that
+// wave is wave 0, which owns the tile's 16 robots anyway, and its LDS region starts at LayEval256::END, laid out exactly as behind
+// LayEval64::END ([16][2] post-step xy, at + 32 what Task::stage fills).
 //
 // One workgroup = FOUR waves (one per SIMD: __launch_bounds__(256) gives every lane the whole 512-entry register file) = one tile
 // of 16 robots.  Wave w owns the output columns 64 w .. 64 w + 63 of both hidden layers.
@@ -18,6 +23,7 @@
 // layer 2 (4 x 64, B from registers) | head: wave w multiplies its K-slice 64 w .. 64 w + 63 of H2 into a partial [16][32] in LDS
 // (wave 0's accumulator starts at b3) | env phase on lanes 0 .. 15 of wave 0: the mean is ((p0 + p1) + p2) + p3, a FIXED order, then
 // eval_actions and Task::step exactly as in k_goal64_tile; GoalState and the task's accumulators stay in those lanes' registers.
+// A wide task: Task::step_lane on those 16 lanes, then Task::after_step on all 64 lanes of wave 0, as in k_goal64_tile.
 //
 // Barriers.  Every __syncthreads() below is reached by all four waves the same number of times:
 //   * the five barriers of a step sit in straight-line code of the loop body, outside every lane- or wave-dependent branch;
@@ -31,6 +37,20 @@
 // What each barrier orders: (1) X written -> layer 1 reads it; (2) H1 written -> layer 2 reads all 256 columns; (3) H2 written ->
 // head reads; (4) partials written -> env lanes sum them; (5) state rows, `go` written, X / partial reads of the env phase done ->
 // next step's observation phase.  H1 (H2) of step t + 1 is written behind barrier (1) ((2)) of t + 1, after its readers of step t.
+//
+// The wide tasks' region (from LayEval256::END: post-step block, the base's scene, pre-step block, wall scene; the teams' xy block is
+// the post-step block) is PRIVATE TO WAVE 0: no other wave reads or writes a word of it.  So it needs no workgroup barrier, and none
+// is added: the step still has five.  Wave-scoped ordering is used instead.  A wave's LDS instructions execute in the order they
+// were issued, so a read sees every earlier write of the same wave; what is left is to keep the compiler from moving them, which
+// eval256_wave_sync() does (release fence, wave barrier, acquire fence, all at wavefront scope: no instruction but the ordering).
+//   * scene (Task::stage, wave 0) and the xy rows of Task::place: written before the opening barrier, read in the loop behind it.
+//   * frame (Task::stage_frame, wave 0, top of a step whose frame differs): after wave 0's own reads of the old frame in the
+//     previous step's after_step (program order; barrier (5) lies between), before this step's after_step (barriers (1) - (4) lie
+//     between).  The frame index depends on g0 + t alone: the test is uniform, and only wave 0 acts on it.
+//   * post-step and pre-step blocks: written by step_lane on lanes 0 .. 15, read by after_step on lanes 0 .. 63 of the same wave
+//     behind eval256_wave_sync(); the next step's writes come after these reads in program order (and behind barrier (5)).
+//   * teams: a row of the xy block of a robot that does not step keeps what `place` or its last step wrote, as in k_goal64_tile.
+// No __syncthreads() sits inside `if (wave == 0)`.  `go` is written after after_step, from wave 0's ballot, before barrier (5).
 #pragma once
 #include "kernels_eval.h"
 
@@ -54,10 +74,48 @@ struct LayEval256 {
 };
 inline size_t eval256_lds_bytes() { return LayEval256::END * sizeof(float); }
 
-// the tasks k_goal256_tile is instantiated for (eval_run): every other task runs the per-step path on 256-wide engines
+// the non-wide tasks k_goal256_tile is instantiated for (eval_run), under mobrob_ppo_set_eval_tile256 alone
 template <class Task>
 constexpr bool task_tile256 = std::is_same_v<Task, EvalTask> || std::is_same_v<Task, FollowTask> ||
                               std::is_same_v<Task, ResumeFollowTask> || std::is_same_v<Task, ScheduledFollowTask>;
+
+// the wide tasks it is instantiated for, under mobrob_ppo_set_eval_tile256_wide as well: every wide task eval_run is instantiated
+// with, less those named in tile256_wide_left_out (what was left on the per-step path, and why)
+template <class Task>
+struct tile256_wide_left_out : std::false_type {};
+// Left out: every task under WallTask or TeamTask (kernels_wall.h, kernels_team.h).  Their tiles came out of the compiler with 4 .. 8
+// spilled vector registers (the correctly rounded sqrtf of wall_sdf / team_partial on top of the resident W2 slice), which the
+// build's audit refuses; they stay on the per-step path.  So do HazardTask<ResumeFollowTask> (4 spilled vector registers) and
+// FrameHazardTask<ScheduledFollowTask> (a 20-byte private segment, as eval_tile_width's note in engine.hip describes for another
+// tile).  Served: HazardTask<> and FrameHazardTask<> over EvalTask and FollowTask, FrameHazardTask<ResumeFollowTask>,
+// HazardTask<ScheduledFollowTask>.
+template <class Base>
+struct WallTask;
+template <class Base>
+struct TeamTask;
+template <class B>
+struct tile256_wide_left_out<WallTask<B>> : std::true_type {};
+template <class B>
+struct tile256_wide_left_out<TeamTask<B>> : std::true_type {};
+template <class Base>
+struct HazardTask;
+template <class Base>
+struct FrameHazardTask;
+struct ResumeFollowTask;
+struct ScheduledFollowTask;
+template <>
+struct tile256_wide_left_out<HazardTask<ResumeFollowTask>> : std::true_type {};
+template <>
+struct tile256_wide_left_out<FrameHazardTask<ScheduledFollowTask>> : std::true_type {};
+template <class Task>
+constexpr bool task_tile256_wide = Task::kWide && !tile256_wide_left_out<Task>::value;
+
+// orders the LDS accesses of ONE wave: writes before it are seen by reads after it, on every lane of the wave (see "Barriers")
+__device__ __forceinline__ void eval256_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // W1, W3 -> LDS in fragment order (zero beyond D / A), the biases, a zeroed observation tile
 __device__ __forceinline__ void eval256_load_lds(const Eval64Net& W, int D, int A, int tid) {
@@ -80,7 +138,7 @@ __device__ __forceinline__ void eval256_load_lds(const Eval64Net& W, int D, int 
 
 template <class Task>
 __global__ __launch_bounds__(256) void k_goal256_tile(typename Task::Args args, Eval64Net W) {
-  static_assert(!Task::kWide && !Task::kFrames, "k_goal256_tile serves the non-wide tasks");
+  static_assert(task_tile256<Task> || task_tile256_wide<Task>, "k_goal256_tile: a task outside both traits");
   using L = LayEval256;
   const EvalArgs& a = Task::eval(args);
   const int tid = threadIdx.x;
@@ -88,6 +146,9 @@ __global__ __launch_bounds__(256) void k_goal256_tile(typename Task::Args args, 
   const int r16 = lane & 15, q = lane >> 4;
   const int row0 = blockIdx.x * 16;
   eval256_load_lds(W, a.D, a.A, tid);
+  if constexpr (Task::kWide) {   // the task's region is wave 0's alone: after [16][2] post-step positions at L::END
+    if (wave == 0) Task::stage(args, &lds[L::END + 32], lane);
+  }
   // ---- the wave's slice of W2, resident for the launch ----
   float w2[4][64];
 #pragma unroll
@@ -104,6 +165,7 @@ __global__ __launch_bounds__(256) void k_goal256_tile(typename Task::Args args, 
     Task::start(g, R, args, n);
     active = Task::active(args, R);
     eval64_state_lds(&lds[L::ST + 12 * r16], g);
+    if constexpr (task_teams<Task>) Task::place(g, &lds[L::END + 2 * r16]);
   }
   if (wave == 0) {
     const uint64_t any = __ballot(active);
@@ -114,7 +176,16 @@ __global__ __launch_bounds__(256) void k_goal256_tile(typename Task::Args args, 
   const bool wide_head = a.A > 16;
   const int ks1 = a.Dp / 4, per = a.Dp / 4;
   const int g0 = task_step0<Task>(args);   // t: step of this launch (trace, path); g0 + t: step of the streams
+  [[maybe_unused]] int staged = 0;         // kFrames: the frame of the shared scene resident in LDS (Task::stage: the first used)
+  if constexpr (Task::kFrames) staged = Task::frame(args, g0);
   for (int t = 0; t < a.max_steps && go; ++t) {   // uniform across the four waves: see "Barriers" above
+    if constexpr (Task::kFrames) {
+      const int f = Task::frame(args, g0 + t);   // uniform over the workgroup; wave 0 alone touches the scene
+      if (f != staged) {
+        if (wave == 0) Task::stage_frame(args, &lds[L::END + 32], lane, f);
+        staged = f;
+      }
+    }
     // ---- observation tile: thread (r = tid & 15, c = tid >> 4) builds chunk c of robot r ----
     {
       const int r = tid & 15, c = tid >> 4;
@@ -182,6 +253,22 @@ __global__ __launch_bounds__(256) void k_goal256_tile(typename Task::Args args, 
     __syncthreads();   // (4)
     // ---- env phase: the tile's 16 lanes (wave 0) ----
     if (wave == 0) {
+      if constexpr (Task::kWide) {
+        // the 16 robot lanes, then the task's wide phase on all 64 lanes of this wave (robot lane & 15 stepped: bit of `stepping`)
+        const uint64_t stepping = __ballot(mine && active);
+        int e0 = 0;
+        if (mine && active) {
+          float* act = &lds[L::MU + r16 * L::LDM];
+          const float* p = &lds[L::PT + r16 * L::LDM];
+          for (int k = 0; k < a.A; ++k)
+            act[k] = ((p[k] + p[16 * L::LDM + k]) + p[2 * 16 * L::LDM + k]) + p[3 * 16 * L::LDM + k];
+          eval_actions(a, n, g0 + t, act, act);
+          active = Task::step_lane(g, R, args, n, t, act, &lds[L::X + r16 * L::LDX], &lds[L::END + 2 * r16], e0);
+          eval64_state_lds(&lds[L::ST + 12 * r16], g);
+        }
+        eval256_wave_sync();   // step_lane's xy rows -> after_step's reads on the wave's other lanes
+        Task::after_step(args, R, n, t, lane, (stepping >> r16) & 1ull, e0, &lds[L::END], &lds[L::END + 32]);
+      } else {
       if (mine && active) {
         float* act = &lds[L::MU + r16 * L::LDM];   // the mean row becomes the applied action in place
         const float* p = &lds[L::PT + r16 * L::LDM];
@@ -190,6 +277,7 @@ __global__ __launch_bounds__(256) void k_goal256_tile(typename Task::Args args, 
         eval_actions(a, n, g0 + t, act, act);
         active = Task::step(g, R, args, n, t, act, &lds[L::X + r16 * L::LDX]);
         eval64_state_lds(&lds[L::ST + 12 * r16], g);
+      }
       }
       const uint64_t any = __ballot(active);
       if (tid == 0) lds[L::GO] = any ? 1.f : 0.f;

@@ -1247,6 +1247,21 @@ class PPOEngine:
         """What set_eval_tile256 was told last (False: never told)."""
         return bool(getattr(self, "_eval_tile256", False))
 
+    def set_eval_tile256_wide(self, on):
+        """The same kernel for calls WITH static or moving hazards: a switch of its own, off unless told (or
+        MOBROB_EVAL_TILE256_WIDE=1 for engines never told).  Such a call reports `persistent` True only when tile256 is in force as
+        well (set_eval_tile256); calls with walls or teams, resumed runs with static hazards and scheduled runs with moving hazards
+        are not served and run the per-step path as before.  ValueError naming tile256 on an engine that is not fused 2x256 tanh."""
+        if not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"eval_tile256_wide must be a bool, got {type(on).__name__}")
+        check(self.lib.mobrob_ppo_set_eval_tile256_wide(self._h, int(bool(on))))
+        self._eval_tile256_wide = bool(on)
+
+    @property
+    def eval_tile256_wide(self):
+        """What set_eval_tile256_wide was told last (False: never told)."""
+        return bool(getattr(self, "_eval_tile256_wide", False))
+
     def explained_variance(self):
         """1 - Var[returns - values] / Var[returns] over the rollout in the buffer (SB3's train/explained_variance)."""
         out = C.c_double()

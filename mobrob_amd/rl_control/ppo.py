@@ -269,7 +269,7 @@ class PPO:
                  gamma=0.99, gae_lambda=0.95, clip_range=0.2, clip_range_vf=None, normalize_advantage=True,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, use_sde=False, sde_sample_freq=-1, target_kl=None,
                  stats_window_size=100, tensorboard_log=None, policy_kwargs=None, verbose=0, seed=None, device="auto",
-                 eval_tile256=False, _init_setup_model=True, _dims=None, _engine_kwargs=None):
+                 eval_tile256=False, eval_tile256_wide=False, _init_setup_model=True, _dims=None, _engine_kwargs=None):
         if policy not in ("MlpPolicy",) and getattr(policy, "__name__", "") != "ActorCriticPolicy":
             raise ValueError(f"Policy {policy} unknown")
         # eval_tile256: evaluations and waypoint following of a 2x256 tanh policy as one launch (PPOEngine.set_eval_tile256); it is
@@ -277,6 +277,10 @@ class PPO:
         if not isinstance(eval_tile256, bool):
             raise TypeError(f"eval_tile256 must be a bool, got {type(eval_tile256).__name__}")
         self.eval_tile256 = eval_tile256
+        # eval_tile256_wide: the same for calls with hazards (PPOEngine.set_eval_tile256_wide; needs eval_tile256 too)
+        if not isinstance(eval_tile256_wide, bool):
+            raise TypeError(f"eval_tile256_wide must be a bool, got {type(eval_tile256_wide).__name__}")
+        self.eval_tile256_wide = eval_tile256_wide
         self.policy_class = "MlpPolicy"
         self.env = env
         # learning_rate / clip_range / clip_range_vf may be floats or SB3 schedules: callables of progress_remaining
@@ -397,6 +401,8 @@ class PPO:
         self.engine.set_hyper(clip_range_vf=self.clip_range_vf, target_kl=self.target_kl)
         if self.eval_tile256:   # (ValueError naming tile256 unless the engine is fused 2x256 tanh)
             self.engine.set_eval_tile256(True)
+        if self.eval_tile256_wide:
+            self.engine.set_eval_tile256_wide(True)
         self._backend = None
         self.engine.set_params(policy_init(self.obs_dim, self.act_dim, self.net_arch[0], self.net_arch[1],
                                            seed=0 if self.seed is None else int(self.seed),
