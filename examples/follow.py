@@ -35,7 +35,7 @@ time a robot needs to clear a crossing is the one-line demonstration that delays
 `--walls FILE.npy` ([M][4]: centre x, y and half extents hx, hy of M axis-aligned boxes) checks every step against walls:
 contact of the robot's footprint (`--robot-radius R`, default 0.1) and crossing of the step's segment, which also sees a step that
 jumps a thin wall.  `--arena` adds the reference's turtlebot3 enclosure (four boxes, 2.98 m outside, 0.265 m thick).  Three lines
-report the contact rate, the crossing rate (robots with such a step) and the minimum clearance to a wall.  Walls block nothing unless `--solid` is given: robots then stop and slide at them
+report the contact rate, the crossing rate (robots with such a step) and the minimum clearance to a wall.  Walls block nothing unless `--solid` is given: robots then stop and slide at them.  Team-mates block nothing unless `--team-solid` is given (with --team-size): a robot then stops or slides at the square of half-width --separation around each mate, the lower team index first, and three lines report the blocked rate, the stopped steps and the steps inside a mate's square
 (goal_rules.wall_block), and two more lines report the share of robots blocked at least once and the fully stopped steps.
 
 `--goal X,Y` (X,Y,Z for a drone) PLANS the waypoints instead of reading them: a grid of `--plan-cells` (32, 64, 128; default 64)
@@ -94,7 +94,9 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
            plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False,
-           tile256_wide=False):
+           tile256_wide=False, team_solid=False):
+    if team_solid and team_size is None:
+        raise ValueError("--team-solid needs --team-size")
     if solid and walls is None and not arena:
         raise ValueError("--solid needs --walls or --arena")
     calls = check_chain(max_steps, horizon, leg_steps)
@@ -126,7 +128,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         if fr.ndim != 3 or fr.shape[2] != 3:
             raise ValueError(f"--hazard-frames must hold [F][M][3] (x, y, radius), got shape {fr.shape}")
         hz = MovingHazards(fr[:, :, :2], fr[None, :, :, 2], frame_steps=int(frame_steps), loop=bool(hazard_loop), indicator=False)
-    teams = None if team_size is None else Teams(int(team_size), float(separation))   # (a ValueError names what is wrong)
+    teams = None if team_size is None else Teams(int(team_size), float(separation), solid=bool(team_solid))   # (a ValueError names what is wrong)
     wl = None
     if walls is not None or arena:
         boxes = np.zeros((0, 4)) if walls is None else np.asarray(walls, np.float64)
@@ -223,6 +225,10 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             print(f"wall blocked rate: {float(np.mean(r['wall_blocked_steps'] > 0))}")
             print(f"wall stopped steps: {int(np.sum(r['wall_stopped_steps']))}")
         print(f"minimum wall clearance: {float(np.nanmin(clear)) if np.any(~np.isnan(clear)) else float('nan')}")
+    if teams is not None and team_solid:
+        print(f"team blocked rate: {float(np.mean(r['team_blocked_steps'] > 0))}")
+        print(f"team stopped steps: {int(np.sum(r['team_stopped_steps']))}")
+        print(f"team inside steps: {int(np.sum(r['team_inside_steps']))}")
     return r
 
 
@@ -297,6 +303,9 @@ def build_parser():
     ap.add_argument("--separation", type=float, default=0.3, help="distance team-mates must keep")
     ap.add_argument("--release", type=str, default=None, help="[K] or [n][K] release steps of the waypoints (.npy, integers)")
     ap.add_argument("--walls", type=str, default=None, help="[M][4] boxes cx, cy, hx, hy (.npy): report wall contacts and crossings")
+    ap.add_argument("--team-solid", action="store_true", default=False,
+                    help="with --team-size: team-mates block each other (stop and slide at the square of half-width --separation "
+                         "around a mate); alone or with --solid walls, not with hazards, not with --host")
     ap.add_argument("--solid", action="store_true", default=False, help="with --walls / --arena: the walls block (robots stop and slide)")
     ap.add_argument("--arena", action="store_true", default=False, help="add the reference's turtlebot3 enclosure to the walls")
     ap.add_argument("--robot-radius", type=float, default=0.1, help="the robot's footprint for wall contact")
@@ -332,4 +341,4 @@ if __name__ == "__main__":
            plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg,
            plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
            plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid,
-           tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide)
+           tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide, team_solid=args.team_solid)

@@ -41,7 +41,7 @@ extern "C" {
 /* 2: config slot `persistent_train` became `activation`, `forward_x3` added, MOBROB_K_COUNT 6 -> 7 (profile_read arrays),
  *    MOBROB_BUF_COUNT / reserved[] resized -- a binding built against 1 must not load this library
  * 3: pi_hidden_ext / vf_hidden_ext (net_arch depths 4 .. 8), use_sde, sde_sample_freq appended to the config, activation codes 2 .. 11
- * (entry points added since -- the latest: mobrob_ppo_follow_waypoints_solid -- change no struct and no existing entry point: a binding
+ * (entry points added since -- the latest: mobrob_ppo_follow_waypoints_teams_solid -- change no struct and no existing entry point: a binding
  *  built against an earlier 3 loads this library, so the number stays; a binding finds out whether a library has such an entry point by
  *  looking the symbol up) */
 #define MOBROB_PPO_ABI_VERSION 3
@@ -800,6 +800,48 @@ int mobrob_ppo_follow_waypoints_solid(mobrob_ppo_engine_t* e, const mobrob_goal_
                                       double* sched_out /* [n][2] in / out, NULL iff no schedule */,
                                       double* wall_out /* [n][7] in / out */, int32_t* blocked_out /* [n][4] in / out */,
                                       float* path_out /* or NULL */, float* trace_out /* or NULL */);
+
+/* ---- solid teams: team-mates block each other --------------------------------------------------------------------------------
+ * mobrob_ppo_follow_waypoints_teams with the mates SOLID, alone (walls, wall_out, blocked_out NULL) or together with solid walls
+ * (all three given, as mobrob_ppo_follow_waypoints_solid takes them), over plain and scheduled runs.  Inside every environment
+ * step, between the dynamics and the goal test, the proposed position is resolved against the robot's team-mates (mobrob_amd/envs/
+ * goal_rules.py: team_block, team_block_step).  It is the rule of solid walls over one longer list of inflated boxes:
+ *     mate j: the closed square with centre c_j and Hx = Hy = separation exactly;  wall w: Hx = hx + radius, Hy = hy + radius;
+ *     a box that holds the pre-step position does not hold in this step (mates that start too close can separate);
+ *     candidates c0 .. c3, the segment test and the velocity of a dropped axis (+0.0) as in the call above, against mates and walls
+ *     at once -- one resolve over the union, not two in sequence.
+ * Where mate j stands (c_j): the order is serial inside a team, by team-local index m = 0 .. team_size - 1, within one global step.
+ * Member m resolves against mates with a lower index where they stand AFTER this step's resolve and against mates with a higher
+ * index where they stood BEFORE the step; a mate that does not step (finished, held back by its budget, inactive) counts where it
+ * stands.  The proposals do not depend on the mates.  The reach test, reward, arrival, next waypoint, path, trace and the next
+ * observation use the resolved position; team_out (and wall_out) are then accounted on the resolved positions and stay observational.
+ * For a pair of mates that was never inside each other's square in the run -- exact: no step's segment meets the other's closed
+ * square; up to rounding: their Chebyshev distance after every step is > separation - 1e-6, so the clearance in team_out[n][3] is
+ * > -1e-6.  Not promised: fairness (the lower index goes first), freedom from deadlock (two mates sent to one point: the first to
+ * arrive holds the other out; a leg budget and replanning are the remedy), anything across teams, rotation, friction.
+ *   team_blocked_out [n][4] int32, in / out, carried like blocked_out: steps blocked by a mate (a rejected candidate met a mate's
+ *             square), the first such step (global, 1-based, -1 = none), such steps with no move at all (code 3), steps inside a
+ *             mate's square.  A run starts from 0, -1, 0, 0.  With walls, blocked_out counts in the same way the steps in which a
+ *             rejected candidate met a wall: a step blocked by walls only is counted there alone, one blocked by both in both.
+ *   kernels   k_goal64_tile / k_goal_task_step<TeamTask<[WallTask<]SolidTeamFollowTask<ResumeFollowTask | ScheduledFollowTask,
+ *             walls>[>]>> (csrc/kernels_team_solid.h): the resolve is a loop over the team-local index inside the env step, on the
+ *             tile's [16][2] block of positions in LDS, on the per-step path on the state rows; a team lies in one wave on both.
+ * team_size 1 gives the bits of mobrob_ppo_follow_waypoints_teams / _solid.  MOBROB_ERR_INVALID, besides every check of those two
+ * calls, for: a NULL teams, team_out or team_blocked_out, static hazards or hazard frames (hz, hzf and hazard_out must be NULL),
+ * walls without blocked_out (observational walls), wall_out or blocked_out without walls, a carried team-blocked record no call
+ * returns. */
+int mobrob_ppo_follow_waypoints_teams_solid(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                            const mobrob_hazards_t* hz /* must be NULL */, const mobrob_hazard_frames_t* hzf /* must be NULL */,
+                                            const mobrob_follow_resume_t* resume, const mobrob_teams_t* teams,
+                                            const mobrob_follow_schedule_t* schedule /* or NULL */, const mobrob_walls_t* walls /* or NULL */,
+                                            const float* waypoints /* [n][K][pos_dim] */, const int32_t* n_waypoints /* or NULL */,
+                                            int32_t* arrival /* [n][K] in / out */, double* robot_out /* [n][4] in / out */,
+                                            double* hazard_out /* must be NULL */, double* team_out /* [n][5] in / out */,
+                                            double* sched_out /* [n][2] in / out, NULL iff no schedule */,
+                                            double* wall_out /* [n][7] in / out, NULL iff no walls */,
+                                            int32_t* blocked_out /* [n][4] in / out, NULL iff no walls */,
+                                            int32_t* team_blocked_out /* [n][4] in / out */, float* path_out /* or NULL */,
+                                            float* trace_out /* or NULL */);
 
 /* ---- grid planner: walls and hazards to waypoints ---------------------------------------------------------------------------
  * Plans waypoints for n_robots robots at once on a grid of cells x cells (32, 64 or 128) over [-extent, extent]^2, x and y only, from

@@ -208,6 +208,12 @@ SYMBOLS = {
                                                     C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                     C.POINTER(C.c_int32), _F, _F]),
+    "mobrob_ppo_follow_waypoints_teams_solid": (C.c_int, [_P, C.POINTER(GoalEnv), C.POINTER(FollowSpec), C.POINTER(HazardsC),
+                                                          C.POINTER(HazardFramesC), C.POINTER(FollowResume), C.POINTER(TeamsC),
+                                                          C.POINTER(FollowScheduleC), C.POINTER(WallsC), _F, C.POINTER(C.c_int32),
+                                                          C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, _F]),
     "mobrob_ppo_plan_grid": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardsC), _F, _F, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _U8, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -55,6 +55,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_hazard.h"
 #include "kernels_team.h"
 #include "kernels_wall.h"
+#include "kernels_team_solid.h"
 #include "kernels_plan.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
@@ -3515,6 +3516,7 @@ static void hazard_fill_frames(const HazardIO& hio, FrameHazardArgs<BaseArgs>& h
 struct TeamIO {
   const mobrob_teams_t* tm;
   double* team_out;           // [N][5] in / out
+  int32_t* team_blocked_out = nullptr;   // [N][4] in / out: solid teams (mobrob_ppo_follow_waypoints_teams_solid) when not null
 };
 struct TeamFill {             // the team fields of TeamArgs (after eval_prepare grew eval_buf)
   int team_size;
@@ -3700,6 +3702,40 @@ static int solid_run(mobrob_ppo_engine_t* e, int N, const HazardIO* hio, const H
   if (tio && ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
   return ran;
 }
+
+// the carried team-blocked record of a run with solid teams: refused before any launch or copy
+static int team_solid_check(const TeamIO& tio, int N, int step0, const double* robot_out) {
+  for (int i = 0; i < N; ++i) {
+    const int32_t* o = tio.team_blocked_out + (size_t)i * 4;
+    const double steps = robot_out[(size_t)i * 4 + 1];
+    const auto count = [&](int32_t v) { return v >= 0 && (double)v <= steps; };
+    if (!(count(o[0]) && count(o[2]) && count(o[3]) && o[2] <= o[0] && o[1] >= -1 && o[1] <= step0 && (o[1] < 0) == (o[0] == 0)))
+      return fail(MOBROB_ERR_INVALID, "follow: solid teams: carried team-blocked record of robot %d is not one a call returns", i);
+  }
+  return MOBROB_OK;
+}
+
+// one call of a run with solid teams: Base (filled in `b`) restated as SolidTeamFollowTask<Base, walls>, in TeamTask, with solid
+// walls (`wio`) in WallTask between the two.  tblk_dev / blocked_dev: the uploaded records (downloaded by the caller).
+template <class Base>
+static int team_solid_run(mobrob_ppo_engine_t* e, int N, const TeamIO* tio, const TeamFill& tf, const typename Base::Args& b,
+                          const WallIO* wio, const WallFill& wf, int* blocked_dev, int* tblk_dev) {
+  HIPC(hipMemcpyAsync(tf.out, tio->team_out, (size_t)N * 5 * 8, hipMemcpyHostToDevice, e->stream));
+  int ran;
+  if (wio) {
+    using Solid = SolidTeamFollowTask<Base, true>;
+    const typename Solid::Args a{b, tf.team_size, tf.sep, wf.radius, tblk_dev, blocked_dev};
+    const WallArgs<typename Solid::Args> w{a, wf.boxes, wf.nwall, wf.scene, wf.M, wf.radius, wf.coef, wf.indicator,
+                                           (int)WallTask<Solid>::base_lds_floats(a), wf.out};
+    ran = team_run<WallTask<Solid>>(e, w, tf);   // (never without TeamTask: no such instance is built)
+  } else {
+    using Solid = SolidTeamFollowTask<Base, false>;
+    const typename Solid::Args a{b, tf.team_size, tf.sep, 0.f, tblk_dev, nullptr};
+    ran = team_run<Solid>(e, a, tf);
+  }
+  if (ran >= 0) HIPC(hipMemcpyAsync(tio->team_out, tf.out, (size_t)N * 5 * 8, hipMemcpyDeviceToHost, e->stream));
+  return ran;
+}
 }  // extern "C++"
 
 // evaluate, with hazards when `hio` is not null (mobrob_ppo_evaluate_goal_env_hazards)
@@ -3860,6 +3896,14 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     if (const int rc = follow_resume_check(rs, spec, nw, robot_out, hio ? hio->hazard_out : nullptr)) return rc;
   if (tio)   // (only with rs: the entry point refuses a call without it)
     if (const int rc = team_check(*tio, N, rs->step0, robot_out)) return rc;
+  if (tio && tio->team_blocked_out) {   // solid teams: alone or with solid walls, over both run tasks
+    if (hio)
+      return fail(MOBROB_ERR_INVALID, hio->frames ? "follow: solid teams: solid teams do not run with hazard frames yet (solid walls and schedules do)"
+                                                  : "follow: solid teams: solid teams do not run with static hazards yet (solid walls and schedules do)");
+    if (wio && !wio->blocked_out)
+      return fail(MOBROB_ERR_INVALID, "follow: solid teams: solid teams do not run with observational walls yet (solid walls do)");
+    if (const int rc = team_solid_check(*tio, N, rs->step0, robot_out)) return rc;
+  }
   if (sio)   // (only with rs, likewise)
     if (const int rc = sched_check(*sio, N, K, P, nw, robot_out)) return rc;
   std::vector<int32_t> wall_counts;
@@ -3893,7 +3937,8 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
                o_sched = carve.add(sio ? (size_t)N * 2 * 8 : 0),
                o_wbox = carve.add(wio ? std::max<size_t>((size_t)wio->wl->n_scenes * wio->wl->max_walls * 4, 1) * 4 : 0),
                o_wcnt = carve.add(wio ? (size_t)wio->wl->n_scenes * 4 : 0), o_wscene = carve.add(wio ? (size_t)N * 4 : 0),
-               o_wout = carve.add(wio ? (size_t)N * 7 * 8 : 0), o_wblk = carve.add(wio && wio->blocked_out ? (size_t)N * 4 * 4 : 0);
+               o_wout = carve.add(wio ? (size_t)N * 7 * 8 : 0), o_wblk = carve.add(wio && wio->blocked_out ? (size_t)N * 4 * 4 : 0),
+               o_tblk = carve.add(tio && tio->team_blocked_out ? (size_t)N * 4 * 4 : 0);
   FrameHazardArgs<FollowArgs> hf{};    // the frames tasks' arguments hold the static tasks'
   FrameHazardArgs<ResumeArgs> hrf{};
   FrameHazardArgs<ScheduledArgs> hsf{};
@@ -3955,6 +4000,9 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
     const bool solid = wio && wio->blocked_out;
     int* blocked_dev = solid ? eval_at<int>(e, o_wblk) : nullptr;
     if (solid) HIPC(hipMemcpyAsync(blocked_dev, wio->blocked_out, (size_t)N * 4 * 4, hipMemcpyHostToDevice, e->stream));
+    const bool tsolid = tio && tio->team_blocked_out;
+    int* tblk_dev = tsolid ? eval_at<int>(e, o_tblk) : nullptr;
+    if (tsolid) HIPC(hipMemcpyAsync(tblk_dev, tio->team_blocked_out, (size_t)N * 4 * 4, hipMemcpyHostToDevice, e->stream));
     if (sio) {
       ScheduledArgs& sa = hsf.h.b;
       int* rel_dev = eval_at<int>(e, o_rel);
@@ -3963,11 +4011,13 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
       HIPC(hipMemcpyAsync(rel_dev, sio->sc->release, (size_t)N * K * 4, hipMemcpyHostToDevice, e->stream));
       HIPC(hipMemcpyAsync(home_dev, sio->sc->home, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
       HIPC(hipMemcpyAsync(sa.sched_out, sio->sched_out, (size_t)N * 2 * 8, hipMemcpyHostToDevice, e->stream));
-      ran = solid ? solid_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, sa, hazard_dev, wio, wf, blocked_dev)
+      ran = tsolid ? team_solid_run<ScheduledFollowTask>(e, N, tio, tf, sa, wio, wf, blocked_dev, tblk_dev)
+            : solid ? solid_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, sa, hazard_dev, wio, wf, blocked_dev)
                   : resume_run<ScheduledFollowTask>(e, N, hio, hc, tio, tf, hsf, hazard_dev, wio, wf);
       if (ran >= 0) HIPC(hipMemcpyAsync(sio->sched_out, sa.sched_out, (size_t)N * 2 * 8, hipMemcpyDeviceToHost, e->stream));
     } else {
-      ran = solid ? solid_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, r, hazard_dev, wio, wf, blocked_dev)
+      ran = tsolid ? team_solid_run<ResumeFollowTask>(e, N, tio, tf, r, wio, wf, blocked_dev, tblk_dev)
+            : solid ? solid_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, r, hazard_dev, wio, wf, blocked_dev)
                   : resume_run<ResumeFollowTask>(e, N, hio, hc, tio, tf, hrf, hazard_dev, wio, wf);
     }
     if (ran >= 0) {
@@ -3976,6 +4026,7 @@ static int follow_waypoints(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env
       HIPC(hipMemcpyAsync(rs->status, r.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
       if (wio) HIPC(hipMemcpyAsync(wio->wall_out, wf.out, (size_t)N * 7 * 8, hipMemcpyDeviceToHost, e->stream));
       if (solid) HIPC(hipMemcpyAsync(wio->blocked_out, blocked_dev, (size_t)N * 4 * 4, hipMemcpyDeviceToHost, e->stream));
+      if (tsolid) HIPC(hipMemcpyAsync(tio->team_blocked_out, tblk_dev, (size_t)N * 4 * 4, hipMemcpyDeviceToHost, e->stream));
     }
   }
   if (ran < 0) return ran;
@@ -4094,6 +4145,34 @@ int mobrob_ppo_follow_waypoints_solid(mobrob_ppo_engine_t* e, const mobrob_goal_
   const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
   return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
                           (hz || hzf) ? &hio : nullptr, resume, teams ? &tio : nullptr, schedule ? &sio : nullptr, &wio);
+}
+
+int mobrob_ppo_follow_waypoints_teams_solid(mobrob_ppo_engine_t* e, const mobrob_goal_env_t* env, const mobrob_follow_spec_t* spec,
+                                            const mobrob_hazards_t* hz, const mobrob_hazard_frames_t* hzf,
+                                            const mobrob_follow_resume_t* resume, const mobrob_teams_t* teams,
+                                            const mobrob_follow_schedule_t* schedule, const mobrob_walls_t* walls, const float* waypoints,
+                                            const int32_t* n_waypoints, int32_t* arrival, double* robot_out, double* hazard_out,
+                                            double* team_out, double* sched_out, double* wall_out, int32_t* blocked_out,
+                                            int32_t* team_blocked_out, float* path_out, float* trace_out) {
+  if (!resume || !teams || !team_out || !team_blocked_out)
+    return fail(MOBROB_ERR_INVALID, "follow: solid teams: null argument (a call with teams is a call of a run)");
+  if ((schedule != nullptr) != (sched_out != nullptr))
+    return fail(MOBROB_ERR_INVALID, "follow: solid teams: sched_out is needed with a schedule, and only then");
+  if ((walls != nullptr) != (wall_out != nullptr))
+    return fail(MOBROB_ERR_INVALID, "follow: solid teams: wall_out is needed with walls, and only then");
+  if (walls && !blocked_out)
+    return fail(MOBROB_ERR_INVALID, "follow: solid teams: solid teams do not run with observational walls yet (solid walls do: blocked_out)");
+  if (!walls && blocked_out) return fail(MOBROB_ERR_INVALID, "follow: solid teams: blocked_out is needed with walls, and only then");
+  if (hz && hzf) return fail(MOBROB_ERR_INVALID, "follow: solid teams: static hazards or hazard frames, not both");
+  if ((hz || hzf) != (hazard_out != nullptr))
+    return fail(MOBROB_ERR_INVALID, "follow: solid teams: hazard_out is needed with hazards, and only then");
+  const TeamIO tio{teams, team_out, team_blocked_out};
+  const SchedIO sio{schedule, sched_out};
+  const WallIO wio{walls, wall_out, blocked_out};
+  mobrob_hazards_t view;
+  const HazardIO hio = hzf ? hazard_frames_io(hzf, view, hazard_out, nullptr) : HazardIO{hz, hazard_out, nullptr};
+  return follow_waypoints(e, env, spec, nullptr, waypoints, n_waypoints, arrival, robot_out, path_out, trace_out,
+                          (hz || hzf) ? &hio : nullptr, resume, &tio, schedule ? &sio : nullptr, walls ? &wio : nullptr);
 }
 
 // ---- grid planner (mobrob_ppo_plan_grid): walls and hazards to waypoints ---------------------------------------------------

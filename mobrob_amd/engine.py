@@ -475,11 +475,15 @@ class PPOEngine:
         crossing_steps, first_crossing) and `state.wall`; nothing else the call returns changes.  With walls.solid the walls
         block (mobrob_ppo_follow_waypoints_solid; goal_rules.wall_block states the rule): robots stop and slide at them, the
         dict gains the keys of waypoints.blocked_result (wall_blocked_steps, wall_first_blocked, wall_stopped_steps,
-        wall_inside_steps) and `state.blocked`.  Solid walls with a MovingHazards are refused (ValueError naming `solid`)."""
+        wall_inside_steps) and `state.blocked`.  Solid walls with a MovingHazards are refused (ValueError naming `solid`).
+        With teams.solid the mates block each other (mobrob_ppo_follow_waypoints_teams_solid; goal_rules.team_block_step states
+        the rule), alone or with solid walls, with or without a schedule: the dict gains the keys of waypoints.team_blocked_result
+        (team_blocked_steps, team_first_blocked, team_stopped_steps, team_inside_steps) and `state.team_blocked`.  Solid teams with
+        hazards of either kind or with observational walls are refused (ValueError naming `Teams(solid=True)`)."""
         from .waypoints import FollowState, follow_inputs
         if resume is not None or int(leg_steps) != 0 or teams is not None or schedule is not None or walls is not None:
             if resume is None:
-                resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule,
+                resume = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams if teams is not None else False, schedule,
                                      walls if walls is not None else False)
             elif not (start is None and waypoints is None and n_waypoints is None):
                 raise ValueError("follow_waypoints: a resumed call takes its robots and waypoints from `resume`")
@@ -527,7 +531,8 @@ class PPOEngine:
         from ._lib import FollowResume, FollowScheduleC, TeamsC, WallsC
         from .envs.goal_rules import Schedule, Teams, Walls
         from .envs.goal_rules import MovingHazards
-        from .waypoints import FollowState, blocked_result, schedule_result, team_result, wall_result
+        from .waypoints import (FollowState, blocked_result, schedule_result, team_blocked_result, team_result, team_solid_check,
+                                wall_result)
         if not isinstance(state, FollowState):
             raise TypeError(f"follow_waypoints: resume must be a FollowState, not {type(state).__name__}")
         if (state.hazard is None) != (hazards is None):
@@ -538,6 +543,7 @@ class PPOEngine:
             if not isinstance(teams, Teams):
                 raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
             teams.check_robots(state.n_robots)
+        tsolid = team_solid_check(state, hazards, teams, walls)
         if (getattr(state, "release", None) is None) != (schedule is None):
             raise ValueError("follow_waypoints: a run has a schedule in every call or in none (FollowState(..., schedule=Schedule))")
         if schedule is not None and not isinstance(schedule, Schedule):
@@ -580,6 +586,8 @@ class PPOEngine:
             st.blocked = np.ascontiguousarray(st.blocked, np.int32)
             if st.blocked.shape != (n, 4):
                 raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
+        if tsolid:
+            st.team_blocked = np.ascontiguousarray(st.team_blocked, np.int32)
         if st.state.shape != (n, 6) or st.robot.shape != (n, 4) or st.arrival.shape != (n, K) or st.leg_used.shape != (n,):
             raise ValueError("follow_waypoints: the arrays of `resume` do not fit its waypoints")
         sp = FollowSpec()
@@ -605,7 +613,20 @@ class PPOEngine:
         if schedule is not None:
             sc = FollowScheduleC()
             sc.release, sc.home = st.release.ctypes.data_as(i32), _fp(st.home)
-        if walls is not None:
+        if tsolid:
+            wl = None
+            if walls is not None:
+                wl = WallsC()
+                wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+                wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
+                wl.scene = None if walls.scene is None else walls.scene.ctypes.data_as(i32)
+                wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
+            r = check(self.lib.mobrob_ppo_follow_waypoints_teams_solid(
+                self._h, C.byref(g), C.byref(sp), None, None, C.byref(rs), C.byref(tm), None if sc is None else C.byref(sc),
+                None if wl is None else C.byref(wl), *tail[:5], st.team.ctypes.data_as(dp),
+                None if sc is None else st.sched.ctypes.data_as(dp), None if wl is None else st.wall.ctypes.data_as(dp),
+                None if wl is None else st.blocked.ctypes.data_as(i32), st.team_blocked.ctypes.data_as(i32), *tail[5:]))
+        elif walls is not None:
             wl = WallsC()
             wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
             wl.boxes, wl.n_walls = _fp(walls.table), walls.counts.ctypes.data_as(i32)
@@ -648,6 +669,8 @@ class PPOEngine:
             out.update(wall_result(st))
         if solid:
             out.update(blocked_result(st))
+        if tsolid:
+            out.update(team_blocked_result(st))
         if path is not None:
             out["path"] = path
         return out

@@ -259,9 +259,11 @@ TEAM_START = (0.0, 0.0, -1.0, np.nan, -1.0)   # a robot's team record before its
 class Teams:
     """Robots partitioned into teams of `size` consecutive robots (team of robot n: n // size, team-local index n % size) that
     must keep `separation` apart: `cost` per unit of intrusion, `indicator`: a step's cost is 1 if there is any.  Robots of
-    different teams never see each other.  Checked on construction (ValueError)."""
+    different teams never see each other.  Checked on construction (ValueError).  `solid`: False -- the mates are observed
+    (team_cost) and block nothing; True -- a waypoint-following run also resolves every step against the mates (team_block):
+    a robot stops or slides at the square of half-width `separation` around each mate."""
 
-    def __init__(self, size, separation, cost=1.0, indicator=False):
+    def __init__(self, size, separation, cost=1.0, indicator=False, solid=False):
         if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or int(size) not in TEAM_SIZES:
             raise ValueError(f"team size must be one of {TEAM_SIZES}, got {size!r}")
         separation, cost = float(separation), float(cost)
@@ -271,6 +273,7 @@ class Teams:
             raise ValueError(f"team cost must be finite and >= 0, got {cost}")
         self.size, self.indicator = int(size), bool(indicator)
         self.separation, self.cost = float(np.float32(separation)), float(np.float32(cost))   # the float32 values every path uses
+        self.solid = bool(solid)
 
     def check_robots(self, n):
         if int(n) % self.size != 0:
@@ -744,6 +747,145 @@ def wall_blocked_fold(record, code, inside, stepped, step0=0):
         rec[:, 2] += stepped[t] & (code[t] == 3)
         rec[:, 3] += stepped[t] & inside[t]
     return rec
+
+
+# ---- solid teams (Teams(..., solid=True)): team-mates are obstacles inside the environment step.  A mate is one more box of
+# wall_block's rule, one that moves: the closed square of half-width `separation` around where the mate stands.  Stated here once;
+# the device (csrc/kernels_team_solid.h: team_resolve) is held to it bit for bit.
+TEAM_BLOCKED_START = (0, -1, 0, 0)   # a robot's team-blocked record before its first step: steps blocked by a mate, first, stopped, inside
+
+
+def team_block(a_xy, p_xy, mates_xy, sep, boxes=None, radius=0.0, counts=None):
+    """Solid teams, ONE robot's resolve: a_xy [..., 2] the x, y before the step, p_xy [..., 2] the x, y the dynamics propose,
+    mates_xy [..., J, 2] where each of its J mates stands (team_block_step says which position that is), sep the separation;
+    with solid walls also boxes [M, 4] or [..., M, 4], radius and counts as wall_block takes them -> (q_xy [..., 2] float32,
+    code [...] int64, inside [...] bool, by_mate [...] bool, by_wall [...] bool, wall_inside [...] bool).
+    It is wall_block's rule over one list of inflated boxes, float32, every operation rounded on its own:
+        mate j:  centre c_j, Hx = Hy = sep exactly (no addition)          wall w:  Hx = hx + radius, Hy = hy + radius
+        a box with |ax - cx| <= Hx and |ay - cy| <= Hy does not hold in this step -- `inside`: any such mate, `wall_inside`: any
+        such wall -- so mates that start too close can separate;
+        candidates c0 = (px, py), c1 = (px, ay), c2 = (ax, py), c3 = (ax, ay) in wall_block's order with its three-axis segment
+        test against every box that holds, mates and walls at once; the first candidate without a hit is taken, c3 untested.
+    The split of a blocked step between the two records: by_mate -- a rejected candidate (c0 .. c(code - 1)) met a mate's square;
+    by_wall -- a rejected candidate met a wall.  Both can hold in one step; with code 0 neither does.  A step blocked by walls
+    only has by_mate False and is counted in the walls' blocked record alone (team_block_fold).
+    With boxes None the first three results are wall_block(a, p, [(cx, cy, sep, sep) per mate], radius=0.0) bit for bit."""
+    f32 = np.float32
+    a, p = np.asarray(a_xy, f32), np.asarray(p_xy, f32)
+    if a.shape != p.shape or p.shape[-1:] != (2,):
+        raise ValueError(f"a_xy and p_xy must both be [..., 2], got {a.shape} and {p.shape}")
+    lead = p.shape[:-1]
+    mt = np.asarray(mates_xy, f32)
+    mt = mt.reshape(mt.shape[:-1] + (2,)) if mt.size else np.zeros(lead + (0, 2), f32)
+    if mt.shape[:-2] != lead:
+        raise ValueError(f"mates_xy must be {lead + ('J', 2)}, got {mt.shape}")
+    s, half = f32(sep), f32(0.5)
+    ax, ay, px, py = a[..., 0], a[..., 1], p[..., 0], p[..., 1]
+    held = []                                                     # (cx, cy, Hx, Hy, holds, mate)
+    inside, wall_inside = np.zeros(lead, bool), np.zeros(lead, bool)
+    for j in range(mt.shape[-2]):
+        cx, cy = mt[..., j, 0], mt[..., j, 1]
+        within = (np.abs(ax - cx) <= s) & (np.abs(ay - cy) <= s)
+        inside = inside | within
+        held.append((cx, cy, s, s, ~within, True))
+    if boxes is not None:
+        bx = np.asarray(boxes, f32)
+        bx = bx.reshape(bx.shape[:-1] + (4,)) if bx.size else np.zeros((0, 4), f32)
+        M, rad = bx.shape[-2], f32(radius)
+        used = np.full(lead, M) if counts is None else np.broadcast_to(np.asarray(counts), lead)
+        for w in range(M):
+            cx, cy = bx[..., w, 0], bx[..., w, 1]
+            Hx, Hy = bx[..., w, 2] + rad, bx[..., w, 3] + rad
+            on = w < used
+            within = on & (np.abs(ax - cx) <= Hx) & (np.abs(ay - cy) <= Hy)
+            wall_inside = wall_inside | within
+            held.append((cx, cy, Hx, Hy, on & ~within, False))
+
+    def seg_hit(qx, qy):
+        ex, ey = half * (qx - ax), half * (qy - ay)
+        sx, sy = half * (ax + qx), half * (ay + qy)
+        aex, aey = np.abs(ex), np.abs(ey)
+        hit = [np.zeros(lead, bool), np.zeros(lead, bool)]        # walls, mates
+        for cx, cy, Hx, Hy, holds, mate in held:
+            mx, my = sx - cx, sy - cy
+            apart = (np.abs(mx) > Hx + aex) | (np.abs(my) > Hy + aey) | (np.abs(mx * ey - my * ex) > Hx * aey + Hy * aex)
+            hit[mate] = hit[mate] | (holds & ~apart)
+        return hit
+    (w0, m0), (w1, m1), (w2, m2) = seg_hit(px, py), seg_hit(px, ay), seg_hit(ax, py)
+    h0, h1, h2 = w0 | m0, w1 | m1, w2 | m2
+    code = np.where(~h0, 0, np.where(~h1, 1, np.where(~h2, 2, 3)))
+    by_mate = ((code >= 1) & m0) | ((code >= 2) & m1) | ((code >= 3) & m2)
+    by_wall = ((code >= 1) & w0) | ((code >= 2) & w1) | ((code >= 3) & w2)
+    qx = np.where((code == 0) | (code == 1), px, ax)
+    qy = np.where((code == 0) | (code == 2), py, ay)
+    return np.stack([qx, qy], -1).astype(f32), np.asarray(code, np.int64), inside, by_mate, by_wall, wall_inside
+
+
+def team_block_scalar(a, p, mates, sep):
+    """team_block without walls for ONE robot, restated with Python loops over np.float32 scalars: a, p (x, y), mates a list of
+    (x, y) -> ((qx, qy), code, inside, by_mate).  The array form is held to it by the tests."""
+    f32 = np.float32
+    ax, ay, px, py, s, half = f32(a[0]), f32(a[1]), f32(p[0]), f32(p[1]), f32(sep), f32(0.5)
+    boxes = [(f32(cx), f32(cy)) for cx, cy in mates]
+    within = [bool(abs(ax - cx) <= s and abs(ay - cy) <= s) for cx, cy in boxes]
+    by_mate = False
+    for code, (qx, qy) in enumerate(((px, py), (px, ay), (ax, py))):
+        ex, ey = half * (qx - ax), half * (qy - ay)
+        sx, sy = half * (ax + qx), half * (ay + qy)
+        aex, aey = abs(ex), abs(ey)
+        hit = False
+        for (cx, cy), inside in zip(boxes, within):
+            mx, my = sx - cx, sy - cy
+            apart = abs(mx) > s + aex or abs(my) > s + aey or abs(f32(mx * ey) - f32(my * ex)) > f32(s * aey) + f32(s * aex)
+            hit = hit or (not inside and not apart)
+        if not hit:
+            return (qx, qy), code, any(within), by_mate
+        by_mate = True
+    return (ax, ay), 3, any(within), True
+
+
+def team_block_step(stand_xy, prop_xy, stepped, teams, walls=None):
+    """Solid teams, ONE global step of all n robots: stand_xy [n][2] where every robot stands before the step (for a robot that
+    steps: its pre-step x, y), prop_xy [n][2] the x, y the dynamics propose for the robots that step (ignored for the others),
+    stepped [n], teams a Teams, walls a solid Walls or None -> (q_xy [n][2] where every robot stands after the step, code,
+    inside, by_mate, by_wall, wall_inside [n]; zeros / False for a robot that did not step).
+    The order is serial inside a team, by team-local index m = 0 .. size - 1: member m resolves (team_block) against the mates
+    with a lower index where they stand AFTER their resolve of this step, against the mates with a higher index where they stood
+    BEFORE the step; a mate that does not step (finished, not released, inactive in this call) counts where it stands.  Teams
+    are independent of each other."""
+    f32 = np.float32
+    pos = np.array(stand_xy, f32)
+    prop, stepped = np.asarray(prop_xy, f32), np.asarray(stepped, bool)
+    n = stepped.shape[0]
+    teams.check_robots(n)
+    if pos.shape != (n, 2) or prop.shape != (n, 2):
+        raise ValueError(f"stand_xy and prop_xy must be [{n}][2], got {pos.shape} and {prop.shape}")
+    G = teams.size
+    code, flags = np.zeros(n, np.int64), np.zeros((4, n), bool)
+    boxes = counts = None
+    if walls is not None:
+        walls.check_robots(n)
+        sc = np.zeros(n, np.int64) if walls.scene is None else walls.scene.astype(np.int64)
+        boxes, counts = walls.table[sc], walls.counts[sc]
+    for m in range(G):
+        idx = np.arange(m, n, G)
+        mates = pos.reshape(n // G, G, 2)[:, [j for j in range(G) if j != m]]
+        q, c, *fl = team_block(pos[idx], prop[idx], mates, teams.separation, None if boxes is None else boxes[idx],
+                               0.0 if walls is None else walls.radius, None if counts is None else counts[idx])
+        s = stepped[idx]
+        pos[idx] = np.where(s[:, None], q, pos[idx])
+        code[idx] = np.where(s, c, 0)
+        for k in range(4):
+            flags[k, idx] = s & fl[k]
+    return (pos, code) + tuple(flags)
+
+
+def team_block_fold(record, code, inside, by_mate, stepped, step0=0):
+    """The carried team-blocked record after the steps step0 .. step0 + T - 1: record [n][4] integers (steps blocked by a mate:
+    by_mate, the first such step as a global 1-based number or -1, such steps with no move at all: code 3, steps inside a mate's
+    square), code / inside / by_mate / stepped [T][n].  It is wall_blocked_fold on the code of the steps a mate blocked; with
+    solid walls the walls' own record is wall_blocked_fold(record, where(by_wall, code, 0), wall_inside, stepped, step0)."""
+    return wall_blocked_fold(record, np.where(np.asarray(by_mate, bool), np.asarray(code), 0), inside, stepped, step0)
 
 
 # ---- grid planner: walls and hazards to waypoints.  This project's own rule; it is stated here once and the device

@@ -73,6 +73,20 @@ walls.  Solid walls with MovingHazards are refused.  The dict gains
   wall_stopped_steps [n] steps with no move at all;  wall_inside_steps [n] steps in which a wall did not hold
 and `state.blocked` carries the four.  Robots stalled against a wall (leg_steps) are replanned by the rounds as any stalled robot.
 
+With `Teams(..., solid=True)` the mates also BLOCK each other (goal_rules.team_block / team_block_step state the rule): a mate is
+one more box of the rule above, the closed square of half-width `separation` around where it stands, and with solid walls the
+scene's boxes and the mates are resolved at once.  The order is serial inside a team, by team-local index, within one global step:
+a member resolves against mates with a lower index where they stand after this step's resolve, against mates with a higher index
+where they stood before the step, against a mate that does not step where it stands.  A pair of mates that was never inside each
+other's square keeps a Chebyshev distance > separation - 1e-6, so min_team_clearance is > -1e-6 for them.  Not promised: fairness
+(the lower index goes first), freedom from deadlock (two mates sent to one point: the first to arrive holds the other out -- the
+counters below show it, a leg budget with follow_with_replanning is the remedy, planning with assign= prevents it), anything
+across teams.  Runs on the device engine, alone or with solid walls, with or without a schedule; hazards, observational walls
+and the host loop are refused by name.  The dict gains
+  team_blocked_steps [n] steps blocked by a mate;  team_first_blocked [n] the first such step (global, 1-based), -1 = none;
+  team_stopped_steps [n] such steps with no move at all;  team_inside_steps [n] steps inside a mate's square
+and `state.team_blocked` carries the four; with solid walls wall_blocked_steps and its kin count the steps a wall blocked.
+
 Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
 sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
 into the next call) and `status`, and takes the previous call's `state=`.  Call c covers the global steps step0 .. step0 +
@@ -146,6 +160,8 @@ class FollowState:
                         crossing -- or None without walls
       blocked [n][4]    int32 blocked steps, first blocked step, fully stopped steps, steps with a wall ignored -- or None unless
                         the walls are solid (`walls` given as the run's Walls, with solid=True)
+      team_blocked [n][4] int32 steps blocked by a mate, first such step, fully stopped ones, steps inside a mate's square -- or
+                        None unless the teams are solid (`teams` given as the run's Teams, with solid=True)
       waypoints [n][K][P] float32, n_waypoints [n] int32: the rows in force (changed by `replan` only)"""
 
     def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False, schedule=None, walls=False):
@@ -159,6 +175,10 @@ class FollowState:
         self.leg_used, self.status = np.zeros(n, np.int32), np.zeros(n, np.int32)
         self.hazard = np.tile(np.array([0.0, 0.0, -1.0, np.nan]), (n, 1)) if hazards else None
         self.team = np.tile(np.array([0.0, 0.0, -1.0, np.nan, -1.0]), (n, 1)) if teams else None
+        self.team_blocked = None
+        if getattr(teams, "solid", False):
+            from .envs.goal_rules import TEAM_BLOCKED_START
+            self.team_blocked = np.tile(np.array(TEAM_BLOCKED_START, np.int32), (n, 1))
         self.wall = None
         if walls:
             from .envs.goal_rules import WALL_START
@@ -255,6 +275,7 @@ def _check_run(state, leg_steps, max_steps, hazards, teams=None, schedule=None, 
         if not isinstance(teams, Teams):
             raise TypeError(f"teams must be a mobrob_amd.envs.goal_rules.Teams, not {type(teams).__name__}")
         teams.check_robots(state.n_robots)
+    team_solid_check(state, hazards, teams, walls)
     if (getattr(state, "wall", None) is None) != (walls is None):
         raise ValueError("a run has walls in every call or in none (FollowState(..., walls=True))")
     if walls is not None:
@@ -292,6 +313,24 @@ def _check_run(state, leg_steps, max_steps, hazards, teams=None, schedule=None, 
     if np.any(state.robot[:, 2] < 0) or np.any(state.robot[:, 2] > state.n_waypoints):
         raise ValueError("state: waypoints reached must lie in 0 .. n_waypoints")
     return leg_steps
+
+
+def team_solid_check(state, hazards, teams, walls):
+    """The compositions solid teams run in, and the run's team-blocked record: ValueError by name otherwise.  -> solid or not"""
+    solid = teams is not None and bool(getattr(teams, "solid", False))
+    if (getattr(state, "team_blocked", None) is None) == solid:
+        raise ValueError("a run has solid teams in every call or in none (FollowState(..., teams=Teams(..., solid=True)))")
+    if solid:
+        from .envs.goal_rules import MovingHazards
+        if isinstance(hazards, MovingHazards):
+            raise ValueError("Teams(solid=True) does not run with MovingHazards yet (solid walls and schedules do)")
+        if hazards is not None:
+            raise ValueError("Teams(solid=True) does not run with static hazards yet (solid walls and schedules do)")
+        if walls is not None and not bool(getattr(walls, "solid", False)):
+            raise ValueError("Teams(solid=True) does not run with observational walls yet (Walls(..., solid=True) do)")
+        if np.shape(state.team_blocked) != (state.n_robots, 4):
+            raise ValueError("state.team_blocked must be [n_robots][4]")
+    return solid
 
 
 def _status(k, nw, leg_used, leg_steps):
@@ -342,6 +381,8 @@ def _host_follow(model, make_env, state, max_steps, deterministic, seed, path_st
     by goal_rules.wall_blocked_fold."""
     from .envs.goal_rules import MovingHazards, hazard_cost, schedule_fold, team_fold, wall_blocked_fold, wall_fold
     solid = walls is not None and bool(getattr(walls, "solid", False))
+    if teams is not None and bool(getattr(teams, "solid", False)):
+        raise ValueError("Teams(solid=True) runs on the device engine only: the host loop steps robot after robot, not step after step")
     st = state.copy()
     st.state = st.state.astype(np.float64)              # the host simulator's own precision, carried exactly
     wp, nw, step0 = st.waypoints, st.n_waypoints, st.step0
@@ -495,6 +536,13 @@ def schedule_result(state):
             "lateness": Schedule.lateness(state.release, state.arrival)}
 
 
+def team_blocked_result(state):
+    """The keys a run with solid teams adds to a call's dict, from the state after the call (state.team_blocked [n][4])."""
+    b = np.asarray(state.team_blocked)
+    return {"team_blocked_steps": b[:, 0].astype(np.int64), "team_first_blocked": b[:, 1].astype(np.int64),
+            "team_stopped_steps": b[:, 2].astype(np.int64), "team_inside_steps": b[:, 3].astype(np.int64)}
+
+
 def team_result(team):
     """The keys a team record [n][5] adds to a call's dict."""
     return {"team_cost_sum": team[:, 0].copy(), "conflict_steps": team[:, 1].astype(np.int64), "first_conflict": team[:, 2].astype(np.int64),
@@ -524,7 +572,7 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         raise ValueError("start and waypoints are needed unless `state` continues a run")
     if isinstance(env, DeviceGoalVecEnv):
         if state is None:
-            state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams is not None, schedule,
+            state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams if teams is not None else False, schedule,
                                 walls if walls is not None else False)
         _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
         return env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
@@ -546,7 +594,7 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         def make_env(i):
             return env
     if state is None:
-        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams is not None, schedule,
+        state = FollowState(start, waypoints, n_waypoints, hazards is not None, pos_dim, teams if teams is not None else False, schedule,
                             walls if walls is not None else False)
     elif isinstance(state, FollowState) and state.waypoints.shape[2] != pos_dim:
         raise ValueError(f"state has {state.waypoints.shape[2]} position dimensions, the environment {pos_dim}")
