@@ -94,7 +94,9 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
            plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False,
-           tile256_wide=False, team_solid=False):
+           tile256_wide=False, team_solid=False, check_spec=False):
+    if check_spec and goal is None:
+        raise ValueError("--check-spec needs --goal (the specification is: eventually inside the reach radius around the goal)")
     if team_solid and team_size is None:
         raise ValueError("--team-solid needs --team-size")
     if solid and walls is None and not arena:
@@ -191,8 +193,15 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
     if goal is not None and plan_schedule is not None:
         schedule = plan_schedule
+    monitored = {}
+    if check_spec:   # eventually inside the reach circle around the goal; with walls: always outside every one of them
+        from mobrob_amd.envs.goal_rules import REACH_RADIUS, Regions, Spec, inside, outside
+        boxes = np.zeros((0, 4), np.float32) if wl is None else wl.rows(0)
+        regions = Regions(np.concatenate([[[goal[0], goal[1], REACH_RADIUS, 0.0]], boxes]), [1] + [0] * len(boxes))
+        clauses = [Spec.eventually(inside(0))] + ([Spec.always(outside(1, 1 + len(boxes)))] if len(boxes) else [])
+        monitored = dict(spec=Spec(regions, clauses), path_stride=1)
     r = follow_waypoints(policy, env, start, waypoints, n_waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
-                         leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
+                         leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl, **monitored)
     for steps in calls[1:]:                                # the run, continued call after call
         if replan is not None:                             # a stalled robot is planned again from where it stands
             for robot, w in replan(np.array(r["state"].positions), r["status"], r["reached"]).items():
@@ -201,7 +210,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
                 else:
                     r["state"].replan([robot], np.asarray(w, np.float64)[None])
         r = follow_waypoints(policy, env, max_steps=steps, deterministic=True, seed=seed, hazards=hz, state=r["state"],
-                             leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl)
+                             leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl, **monitored)
     K = r["arrival"].shape[1]
     done = r["reached"] == (K if goal is None else np.where(r["state"].n_waypoints > 0, r["state"].n_waypoints, -1))
     last = r["arrival"][done, (K if goal is None else r["state"].n_waypoints[done]) - 1]
@@ -229,6 +238,10 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         print(f"team blocked rate: {float(np.mean(r['team_blocked_steps'] > 0))}")
         print(f"team stopped steps: {int(np.sum(r['team_stopped_steps']))}")
         print(f"team inside steps: {int(np.sum(r['team_inside_steps']))}")
+    if check_spec:
+        worst = int(np.argmin(r["robustness"]))
+        print(f"specification satisfied: {int(np.sum(r['satisfied']))} of {len(r['satisfied'])} robots")
+        print(f"worst robustness: {float(r['robustness'][worst])} (robot {worst}, clause {int(r['weakest'][worst])})")
     return r
 
 
@@ -310,6 +323,9 @@ def build_parser():
     ap.add_argument("--arena", action="store_true", default=False, help="add the reference's turtlebot3 enclosure to the walls")
     ap.add_argument("--robot-radius", type=float, default=0.1, help="the robot's footprint for wall contact")
     ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
+    ap.add_argument("--check-spec", action="store_true", default=False,
+                    help="with --goal: monitor 'eventually inside the reach radius around the goal' and, with --walls / --arena, "
+                         "'always outside every wall'; report the satisfied robots and the worst robustness")
     ap.add_argument("--tile256", action="store_true", default=False,
                     help="a 2x256 tanh policy: run calls without hazards, teams or walls as one launch (PPOEngine.set_eval_tile256)")
     ap.add_argument("--tile256-wide", action="store_true", default=False,
@@ -326,6 +342,8 @@ if __name__ == "__main__":
         ap.error("--assign needs --goals and --team-size")
     if args.goals is None and (args.waypoints is None) == (args.goal is None):
         ap.error("give --waypoints or --goal, not both")
+    if args.check_spec and args.goal is None:
+        ap.error("--check-spec needs --goal")
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
     except ValueError as ex:
@@ -341,4 +359,5 @@ if __name__ == "__main__":
            plan_layers=args.plan_layers, plan_reserve=args.plan_reserve, plan_time_smooth=args.plan_time_smooth, plan_max_leg=args.plan_max_leg,
            plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
            plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid,
-           tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide, team_solid=args.team_solid)
+           tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide, team_solid=args.team_solid,
+           check_spec=args.check_spec)

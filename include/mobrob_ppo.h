@@ -41,7 +41,7 @@ extern "C" {
 /* 2: config slot `persistent_train` became `activation`, `forward_x3` added, MOBROB_K_COUNT 6 -> 7 (profile_read arrays),
  *    MOBROB_BUF_COUNT / reserved[] resized -- a binding built against 1 must not load this library
  * 3: pi_hidden_ext / vf_hidden_ext (net_arch depths 4 .. 8), use_sde, sde_sample_freq appended to the config, activation codes 2 .. 11
- * (entry points added since -- the latest: mobrob_ppo_follow_waypoints_teams_solid -- change no struct and no existing entry point: a binding
+ * (entry points added since -- the latest: mobrob_ppo_spec_monitor with its own mobrob_spec_t -- change no existing struct and no existing entry point: a binding
  *  built against an earlier 3 loads this library, so the number stays; a binding finds out whether a library has such an entry point by
  *  looking the symbol up) */
 #define MOBROB_PPO_ABI_VERSION 3
@@ -1223,6 +1223,46 @@ int mobrob_ppo_plan_assign(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
                            float* goal_out /* [n][pos_dim] */, int32_t* assign_cost_out /* [n] */, int64_t* total_out /* [2][n_teams] */,
                            int32_t* team_out /* [4][n_teams] */, int64_t* u_out /* [n] */, int64_t* v_out /* [n] */,
                            int32_t* matrix_out /* [n_teams][team_size][team_size] or NULL */, int32_t* sweeps_out /* [n] or NULL */);
+
+/* ---- run specifications: reach / avoid / until robustness per robot, from the positions of a run ----------------------------------
+ * The rule is stated once in mobrob_amd/envs/goal_rules.py (Regions, region_margins, spec_predicate, spec_fold) and k_spec_monitor
+ * (csrc/kernels_spec.h) reproduces it bit for bit.  A scene is up to MOBROB_SPEC_REGIONS_MAX regions: kind 0 a box (cx, cy, hx, hy),
+ * kind 1 a circle (cx, cy, r, 0); only x and y count.  The specification is the conjunction of n_clauses clauses; clause c is
+ * (op[c], window [a[c], b[c]] in sample time tau = global steps completed, predicate 1, and for UNTIL predicate 2); a predicate is
+ * the range of regions [lo, hi) read as their union and `out` (0: inside, 1: outside).  Per robot and clause the call carries
+ * val = (rho, guard) and wit = the witness sample; the state before a robot's first sample is rho = +inf (ALWAYS) or -inf, guard =
+ * +inf, wit = -1 (the caller's to set).
+ *   path      host [T + 1][n][P], time-major, as mobrob_ppo_follow_waypoints* writes it with path_stride 1: record 0 the position at
+ *             entry.  step0 == 0: records 0 .. T are the samples tau = 0 .. T; step0 > 0: record 0 is skipped (the previous call
+ *             folded it) and records 1 .. T are tau = step0 + 1 .. step0 + T.
+ *   val, wit  host [n][n_clauses][2] float and [n][n_clauses] int32, in and out.
+ * The path is uploaded into a buffer of the monitor's own, outside the arena: rollout, training and evaluation buffers are untouched.
+ * MOBROB_ERR_INVALID before any launch or copy, naming the argument, for: a NULL pointer; n < 1, T < 1, P outside 1 .. 3, n_scenes <
+ * 1, max_regions outside 0 .. 64, n_clauses outside 1 .. 16, a scene's count outside 0 .. max_regions, several scenes without a
+ * scene index, a scene index outside 0 .. n_scenes - 1, a kind other than 0 or 1, a region that is not finite or has a negative
+ * extent; a path above MOBROB_SPEC_PATH_MAX_BYTES; step0 < 0 or step0 + T above INT32_MAX; an op outside 0 .. 2; a window with a < 0
+ * or a > b; a region range outside 0 <= lo <= hi <= max_regions; a non-finite position (the robot and the record are named). */
+#define MOBROB_SPEC_REGIONS_MAX 64
+#define MOBROB_SPEC_CLAUSES_MAX 16
+#define MOBROB_SPEC_OPEN 2147483647 /* the right end of an open window */
+#define MOBROB_SPEC_ALWAYS 0
+#define MOBROB_SPEC_EVENTUALLY 1
+#define MOBROB_SPEC_UNTIL 2
+#define MOBROB_SPEC_PATH_MAX_BYTES (256u << 20)
+typedef struct {
+  int32_t n_scenes, max_regions;
+  const float* regions;      /* [n_scenes][max_regions][4]                                 */
+  const int32_t* kinds;      /* [n_scenes][max_regions]: 0 box, 1 circle                   */
+  const int32_t* n_regions;  /* [n_scenes] regions in use                                  */
+  const int32_t* scene;      /* [n] scene of each robot, or NULL (n_scenes must be 1)      */
+  int32_t n_clauses;
+  int32_t op[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t a[MOBROB_SPEC_CLAUSES_MAX], b[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t lo1[MOBROB_SPEC_CLAUSES_MAX], hi1[MOBROB_SPEC_CLAUSES_MAX], out1[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t lo2[MOBROB_SPEC_CLAUSES_MAX], hi2[MOBROB_SPEC_CLAUSES_MAX], out2[MOBROB_SPEC_CLAUSES_MAX];   /* UNTIL only */
+} mobrob_spec_t;
+int mobrob_ppo_spec_monitor(mobrob_ppo_engine_t* e, const mobrob_spec_t* spec, const float* path /* [T + 1][n][P] */, int32_t n,
+                            int32_t T, int32_t P, int32_t step0, float* val /* [n][n_clauses][2] */, int32_t* wit /* [n][n_clauses] */);
 
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment

@@ -110,6 +110,12 @@ class PlanTime(C.Structure):  # mobrob_plan_time_t
     _fields_ = [("step0", C.c_int32), ("layer_steps", C.c_int32), ("layers", C.c_int32)]
 
 
+class SpecC(C.Structure):  # mobrob_spec_t
+    _fields_ = [("n_scenes", C.c_int32), ("max_regions", C.c_int32), ("regions", C.POINTER(C.c_float)),
+                ("kinds", C.POINTER(C.c_int32)), ("n_regions", C.POINTER(C.c_int32)), ("scene", C.POINTER(C.c_int32)),
+                ("n_clauses", C.c_int32)] + [(k, C.c_int32 * 16) for k in ("op", "a", "b", "lo1", "hi1", "out1", "lo2", "hi2", "out2")]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -257,6 +263,7 @@ SYMBOLS = {
     "mobrob_ppo_plan_assign": (C.c_int, [_P, C.POINTER(PlanSpec), C.POINTER(WallsC), C.POINTER(HazardsC), C.POINTER(HazardFramesC),
                                          C.POINTER(PlanTime), C.c_int32, C.c_int32, _F, _F, C.POINTER(C.c_int32), _F, C.POINTER(C.c_int32),
                                          _I64, C.POINTER(C.c_int32), _I64, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mobrob_ppo_spec_monitor": (C.c_int, [_P, C.POINTER(SpecC), _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, C.POINTER(C.c_int32)]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

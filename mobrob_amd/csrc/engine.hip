@@ -57,6 +57,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_wall.h"
 #include "kernels_team_solid.h"
 #include "kernels_plan.h"
+#include "kernels_spec.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -310,6 +311,9 @@ struct mobrob_ppo_engine {
   bool plan_team_smooth_lds_set = false;   // and k_plan_team_smooth's
   bool plan_team_rounds_lds_set = false;   // and k_plan_team_rounds's
   bool plan_assign_lds_set = false;        // and k_plan_assign_cost's (mobrob_ppo_plan_assign works in plan_team_buf)
+  // run specifications (mobrob_ppo_spec_monitor): the uploaded path, the carried state and the tables, one allocation of their own
+  char* spec_buf = nullptr;
+  size_t spec_bytes = 0;
 };
 
 namespace {
@@ -1387,6 +1391,7 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   if (e->plan_clear_fields) (void)hipFree(e->plan_clear_fields);
   if (e->plan_time_buf) (void)hipFree(e->plan_time_buf);
   if (e->plan_team_buf) (void)hipFree(e->plan_team_buf);
+  if (e->spec_buf) (void)hipFree(e->spec_buf);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -5361,6 +5366,116 @@ int mobrob_ppo_plan_assign(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
   HIPC(hipMemcpyAsync(v_out, aa.v, (size_t)N * 8, hipMemcpyDeviceToHost, e->stream));
   if (matrix_out) HIPC(hipMemcpyAsync(matrix_out, aa.cost, (size_t)N * team_size * 4, hipMemcpyDeviceToHost, e->stream));
   if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, ca.sweeps, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
+}
+
+// ---- run specifications (mobrob_ppo_spec_monitor): robustness per robot from the positions of a run -------------------------------
+// everything the call refuses, before any launch or copy; counts: the scenes' region counts
+static int spec_check(const mobrob_spec_t* spec, const float* path, int N, int T, int P, int step0, std::vector<int32_t>& counts) {
+  const char* who = "spec_monitor";
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "%s: n must be >= 1, got %d", who, N);
+  if (T < 1) return fail(MOBROB_ERR_INVALID, "%s: T must be >= 1, got %d", who, T);
+  if (P < 1 || P > 3) return fail(MOBROB_ERR_INVALID, "%s: P must lie in 1 .. 3, got %d", who, P);
+  if (step0 < 0) return fail(MOBROB_ERR_INVALID, "%s: step0 must be >= 0, got %d", who, step0);
+  if ((int64_t)step0 + T > INT_MAX) return fail(MOBROB_ERR_INVALID, "%s: step0 + T must fit an int32", who);
+  const unsigned long long bytes = (unsigned long long)(T + 1ll) * (unsigned long long)N * P * 4ull;
+  if (bytes > (unsigned long long)MOBROB_SPEC_PATH_MAX_BYTES)
+    return fail(MOBROB_ERR_INVALID, "%s: path of %llu bytes is above the limit of %u", who, bytes, (unsigned)MOBROB_SPEC_PATH_MAX_BYTES);
+  const int S = spec->n_scenes, R = spec->max_regions, C = spec->n_clauses;
+  if (S < 1) return fail(MOBROB_ERR_INVALID, "%s: spec: n_scenes must be >= 1", who);
+  if (R < 0 || R > kSpecRegionsMax) return fail(MOBROB_ERR_INVALID, "%s: spec: max_regions must lie in 0 .. %d, got %d", who, kSpecRegionsMax, R);
+  if (C < 1 || C > kSpecClausesMax) return fail(MOBROB_ERR_INVALID, "%s: spec: n_clauses must lie in 1 .. %d, got %d", who, kSpecClausesMax, C);
+  if (!spec->n_regions) return fail(MOBROB_ERR_INVALID, "%s: spec: null n_regions", who);
+  if (R > 0 && (!spec->regions || !spec->kinds)) return fail(MOBROB_ERR_INVALID, "%s: spec: null regions or kinds", who);
+  if (!spec->scene && S > 1) return fail(MOBROB_ERR_INVALID, "%s: spec: %d scenes need a scene index per robot", who, S);
+  counts.assign(spec->n_regions, spec->n_regions + S);
+  for (int s = 0; s < S; ++s) {
+    if (counts[s] < 0 || counts[s] > R) return fail(MOBROB_ERR_INVALID, "%s: spec: n_regions[%d] = %d outside 0 .. %d", who, s, counts[s], R);
+    for (int r = 0; r < counts[s]; ++r) {
+      const float* b = spec->regions + ((size_t)s * R + r) * 4;
+      const int kind = spec->kinds[(size_t)s * R + r];
+      if (kind != 0 && kind != 1) return fail(MOBROB_ERR_INVALID, "%s: spec: kinds: region %d of scene %d has kind %d (0 box, 1 circle)", who, r, s, kind);
+      if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]) && b[2] >= 0.f && (kind == 1 || b[3] >= 0.f)))
+        return fail(MOBROB_ERR_INVALID, "%s: spec: regions: region %d of scene %d is not finite or has a negative extent", who, r, s);
+    }
+  }
+  if (spec->scene)
+    for (int i = 0; i < N; ++i)
+      if (spec->scene[i] < 0 || spec->scene[i] >= S)
+        return fail(MOBROB_ERR_INVALID, "%s: spec: scene[%d] = %d outside 0 .. %d", who, i, spec->scene[i], S - 1);
+  for (int c = 0; c < C; ++c) {
+    if (spec->op[c] < MOBROB_SPEC_ALWAYS || spec->op[c] > MOBROB_SPEC_UNTIL)
+      return fail(MOBROB_ERR_INVALID, "%s: spec: op[%d] = %d outside 0 .. 2", who, c, spec->op[c]);
+    if (spec->a[c] < 0 || spec->a[c] > spec->b[c])
+      return fail(MOBROB_ERR_INVALID, "%s: spec: window of clause %d: a = %d, b = %d do not obey 0 <= a <= b", who, c, spec->a[c], spec->b[c]);
+    if (spec->lo1[c] < 0 || spec->lo1[c] > spec->hi1[c] || spec->hi1[c] > R)
+      return fail(MOBROB_ERR_INVALID, "%s: spec: region range [%d, %d) of clause %d outside 0 .. %d", who, spec->lo1[c], spec->hi1[c], c, R);
+    if (spec->op[c] == MOBROB_SPEC_UNTIL && (spec->lo2[c] < 0 || spec->lo2[c] > spec->hi2[c] || spec->hi2[c] > R))
+      return fail(MOBROB_ERR_INVALID, "%s: spec: second region range [%d, %d) of clause %d outside 0 .. %d", who, spec->lo2[c], spec->hi2[c], c, R);
+  }
+  // positions: one pass over the exponent bits, a second one only to name the offender
+  const size_t total = (size_t)(T + 1) * N * P;
+  uint32_t bad = 0;
+  for (size_t k = 0; k < total; ++k) {
+    uint32_t w;
+    memcpy(&w, path + k, 4);
+    bad |= (uint32_t)((w & 0x7F800000u) == 0x7F800000u);
+  }
+  if (bad)
+    for (size_t k = 0; k < total; ++k)
+      if (!std::isfinite(path[k]))
+        return fail(MOBROB_ERR_INVALID, "%s: path: the position of robot %d in record %d is not finite", who, (int)((k / P) % N), (int)(k / P / N));
+  return MOBROB_OK;
+}
+
+int mobrob_ppo_spec_monitor(mobrob_ppo_engine_t* e, const mobrob_spec_t* spec, const float* path, int32_t n, int32_t T, int32_t P,
+                            int32_t step0, float* val, int32_t* wit) {
+  if (!e) return fail(MOBROB_ERR_INVALID, "spec_monitor: null engine");
+  if (!spec) return fail(MOBROB_ERR_INVALID, "spec_monitor: null spec");
+  if (!path) return fail(MOBROB_ERR_INVALID, "spec_monitor: null path");
+  if (!val) return fail(MOBROB_ERR_INVALID, "spec_monitor: null val");
+  if (!wit) return fail(MOBROB_ERR_INVALID, "spec_monitor: null wit");
+  std::vector<int32_t> counts;
+  if (const int rc = spec_check(spec, path, n, T, P, step0, counts)) return rc;
+  const int S = spec->n_scenes, R = spec->max_regions, C = spec->n_clauses;
+  std::vector<int32_t> clauses((size_t)C * kSpecClauseWords);
+  for (int c = 0; c < C; ++c) {
+    const bool until = spec->op[c] == MOBROB_SPEC_UNTIL;
+    const int32_t row[kSpecClauseWords] = {spec->op[c], spec->a[c], spec->b[c], spec->lo1[c], spec->hi1[c], spec->out1[c] != 0,
+                                           until ? spec->lo2[c] : 0, until ? spec->hi2[c] : 0, until ? spec->out2[c] != 0 : 0};
+    std::copy(row, row + kSpecClauseWords, clauses.begin() + (size_t)c * kSpecClauseWords);
+  }
+  const size_t path_bytes = (size_t)(T + 1) * n * P * 4, val_bytes = (size_t)n * C * 8, wit_bytes = (size_t)n * C * 4;
+  EvalCarve call;
+  const size_t o_path = call.add(path_bytes), o_val = call.add(val_bytes), o_wit = call.add(wit_bytes),
+               o_reg = call.add(std::max<size_t>((size_t)S * R * 16, 4)), o_kind = call.add(std::max<size_t>((size_t)S * R * 4, 4)),
+               o_cnt = call.add((size_t)S * 4), o_scene = call.add((size_t)n * 4), o_cl = call.add(clauses.size() * 4);
+  if (const int rc = grow_plan_buf(e, e->spec_buf, e->spec_bytes, call.total)) return rc;
+  const auto mine = [&](size_t off) { return e->spec_buf + off; };
+  SpecArgs a{};
+  a.path = reinterpret_cast<float*>(mine(o_path));
+  a.regions = reinterpret_cast<float*>(mine(o_reg)); a.kinds = reinterpret_cast<int*>(mine(o_kind));
+  a.nreg = reinterpret_cast<int*>(mine(o_cnt)); a.scene = spec->scene ? reinterpret_cast<int*>(mine(o_scene)) : nullptr;
+  a.clauses = reinterpret_cast<int*>(mine(o_cl));
+  a.val = reinterpret_cast<float*>(mine(o_val)); a.wit = reinterpret_cast<int*>(mine(o_wit));
+  a.N = n; a.T = T; a.P = P; a.R = R; a.C = C;
+  a.r0 = step0 == 0 ? 0 : 1;
+  a.tau0 = step0;
+  HIPC(hipMemcpyAsync(mine(o_path), path, path_bytes, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_val), val, val_bytes, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_wit), wit, wit_bytes, hipMemcpyHostToDevice, e->stream));
+  if ((size_t)S * R) {
+    HIPC(hipMemcpyAsync(mine(o_reg), spec->regions, (size_t)S * R * 16, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(mine(o_kind), spec->kinds, (size_t)S * R * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  HIPC(hipMemcpyAsync(mine(o_cnt), counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  if (spec->scene) HIPC(hipMemcpyAsync(mine(o_scene), spec->scene, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_cl), clauses.data(), clauses.size() * 4, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_spec_monitor, dim3(cdiv(n, 64)), dim3(64), 0, e->stream, a);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(val, a.val, val_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(wit, a.wit, wit_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
 }

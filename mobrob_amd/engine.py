@@ -675,6 +675,41 @@ class PPOEngine:
             out["path"] = path
         return out
 
+    def spec_monitor(self, spec, path, step0=0, state=None):
+        """A specification folded over the positions of one call of a run (mobrob_ppo_spec_monitor; the rule: goal_rules.spec_fold,
+        reproduced bit for bit).  spec: a goal_rules.Spec; path [T + 1][n][P] as follow_waypoints returns it with path_stride=1;
+        step0: the run's global step at the call's entry; state: the goal_rules.SpecState the previous call returned (None:
+        spec_start).  Returns (the new SpecState, goal_rules.spec_result of it)."""
+        from ._lib import SpecC
+        from .envs.goal_rules import SPEC_UNTIL, Spec, SpecState, spec_check_state, spec_result, spec_start
+        if not isinstance(spec, Spec):
+            raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.Spec, not {type(spec).__name__}")
+        path = np.ascontiguousarray(path, F32)
+        if path.ndim != 3:
+            raise ValueError(f"spec_monitor: path must be [T + 1][n][P], got shape {path.shape}")
+        T, n, P = path.shape[0] - 1, path.shape[1], path.shape[2]
+        reg = spec.regions
+        reg.check_robots(n)
+        if state is None:
+            state = spec_start(n, spec)
+        spec_check_state(state, n, spec)
+        if not -2 ** 31 <= int(step0) < 2 ** 31:
+            raise ValueError("spec_monitor: step0 must fit an int32")
+        new = state.copy()
+        i32 = C.POINTER(C.c_int32)
+        sp = SpecC()
+        sp.n_scenes, sp.max_regions, sp.n_clauses = reg.n_scenes, reg.max_regions, spec.n_clauses
+        sp.regions, sp.kinds, sp.n_regions = _fp(reg.table), reg.kinds.ctypes.data_as(i32), reg.counts.ctypes.data_as(i32)
+        sp.scene = None if reg.scene is None else reg.scene.ctypes.data_as(i32)
+        for c, (op, a, b, p1, p2) in enumerate(spec.clauses):
+            sp.op[c], sp.a[c], sp.b[c] = op, a, b
+            sp.lo1[c], sp.hi1[c], sp.out1[c] = p1[0], p1[1], int(p1[2])
+            if op == SPEC_UNTIL:
+                sp.lo2[c], sp.hi2[c], sp.out2[c] = p2[0], p2[1], int(p2[2])
+        check(self.lib.mobrob_ppo_spec_monitor(self._h, C.byref(sp), _fp(path), n, T, P, int(step0), _fp(new.val),
+                                               new.wit.ctypes.data_as(i32)))
+        return new, spec_result(new, spec)
+
     def plan_grid(self, spec, walls=None, hazards=None, *, start, goal, max_waypoints=16, want_occupancy=False, want_fields=False,
                   reuse=None):
         """Waypoints for every robot from a grid over the scene (mobrob_ppo_plan_grid; the rule: goal_rules.grid_occupancy /

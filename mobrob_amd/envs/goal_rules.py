@@ -2424,3 +2424,299 @@ def grid_assign(spec, walls, hazards, start, goal, teams, objective="sum", step0
     if want_matrix:
         out["assign_matrix"] = np.where(C >= PLAN_ASSIGN_NONE, -1, C).astype(np.int32)
     return out
+
+
+# ---- run specifications: reach / avoid / until robustness per robot, from the positions of a run (the device: csrc/kernels_spec.h,
+# k_spec_monitor, held to this bit for bit).  Stated here once; waypoints.monitor, the host loop and PPOEngine.spec_monitor apply it.
+SPEC_REGIONS_MAX = 64           # regions per scene
+SPEC_CLAUSES_MAX = 16           # clauses of a specification
+SPEC_OPEN = 2 ** 31 - 1         # the right end of an open window
+SPEC_ALWAYS, SPEC_EVENTUALLY, SPEC_UNTIL = 0, 1, 2
+SPEC_BOX, SPEC_CIRCLE = 0, 1    # region kinds
+SPEC_RESULT_KEYS = ("spec_rho", "spec_witness", "robustness", "weakest", "satisfied")
+
+
+class Regions:
+    """The regions a specification speaks about: `rows` [R, 4] (one scene) or [S, R, 4] (scenes) float32, `kinds` [R] or [S, R]:
+    kind 0 (SPEC_BOX) an axis-aligned box (cx, cy, hx, hy) with hx, hy >= 0, kind 1 (SPEC_CIRCLE) a circle (cx, cy, r, 0) with
+    r >= 0; `counts` [S] regions in use per scene (None: all R), `scene` [n] scene of each robot (None: S must be 1).  R <=
+    SPEC_REGIONS_MAX.  Only x and y count, as for hazards and walls, for drones too.  Checked on construction (ValueError)."""
+
+    def __init__(self, rows, kinds, counts=None, scene=None):
+        rw = np.asarray(rows, np.float64)
+        if rw.size == 0 and rw.ndim < 2:
+            rw = rw.reshape(0, 4)
+        if rw.ndim == 2:
+            rw = rw[None]
+        if rw.ndim != 3 or rw.shape[2] != 4:
+            raise ValueError(f"region rows must be [R, 4] or [S, R, 4], got shape {np.shape(rows)}")
+        S, R = rw.shape[:2]
+        if S < 1:
+            raise ValueError("regions need at least one scene")
+        if R > SPEC_REGIONS_MAX:
+            raise ValueError(f"at most {SPEC_REGIONS_MAX} regions per scene, got {R}")
+        kd = np.asarray(kinds)
+        if kd.size == 0:
+            kd = np.zeros((S, R), np.int32)
+        if kd.shape == (R,):
+            kd = np.broadcast_to(kd, (S, R))
+        if kd.shape != (S, R) or not np.issubdtype(kd.dtype, np.integer):
+            raise ValueError(f"region kinds must be [{R}] or [{S}, {R}] integers, got {kd.dtype} of shape {kd.shape}")
+        if np.any((kd != SPEC_BOX) & (kd != SPEC_CIRCLE)):
+            raise ValueError("region kinds must be 0 (box) or 1 (circle)")
+        if not np.all(np.isfinite(rw)) or np.any(np.abs(rw) > np.finfo(np.float32).max):
+            raise ValueError("region rows must be finite")
+        if np.any(rw[..., 2] < 0) or np.any((kd == SPEC_BOX) & (rw[..., 3] < 0)):
+            raise ValueError("box half extents and circle radii must be >= 0")
+        if counts is None:
+            cnt = np.full(S, R, np.int32)
+        else:
+            cnt = np.asarray(counts)
+            if cnt.shape != (S,) or not np.issubdtype(cnt.dtype, np.integer) or np.any(cnt < 0) or np.any(cnt > R):
+                raise ValueError(f"region counts must be {S} integers in 0 .. {R}")
+            cnt = cnt.astype(np.int32)
+        if scene is None:
+            if S != 1:
+                raise ValueError(f"{S} region scenes need a scene index per robot")
+            sc = None
+        else:
+            sc = np.asarray(scene)
+            if sc.ndim != 1 or not np.issubdtype(sc.dtype, np.integer) or np.any(sc < 0) or np.any(sc >= S):
+                raise ValueError(f"region scene indices must be integers in 0 .. {S - 1}")
+            sc = np.ascontiguousarray(sc, np.int32)
+        self.table = np.ascontiguousarray(rw, np.float32)     # [S, R, 4]
+        self.kinds = np.ascontiguousarray(kd, np.int32)       # [S, R]
+        self.counts, self.scene = cnt, sc
+
+    @property
+    def n_scenes(self):
+        return self.table.shape[0]
+
+    @property
+    def max_regions(self):
+        return self.table.shape[1]
+
+    def check_robots(self, n):
+        if self.scene is not None and self.scene.shape != (n,):
+            raise ValueError(f"region scene must have {n} entries, one per robot, got {self.scene.shape[0]}")
+
+    @staticmethod
+    def from_walls(walls):
+        """Every wall as a box region: the box itself, not inflated by the robot radius; scenes and counts are the walls' own."""
+        return Regions(walls.table, np.full(walls.table.shape[:2], SPEC_BOX, np.int32), walls.counts, walls.scene)
+
+    @staticmethod
+    def from_hazards(hazards):
+        """Every hazard as a circle region of its radius; scenes and counts are the hazards' own."""
+        t = hazards.table
+        rows = np.concatenate([t, np.zeros(t.shape[:2] + (1,), np.float32)], axis=-1)
+        return Regions(rows, np.full(t.shape[:2], SPEC_CIRCLE, np.int32), hazards.counts, hazards.scene)
+
+
+def region_margins(xy, rows, kinds):
+    """The INSIDE margin of every region at every position: xy [n, 2], rows [n, R, 4], kinds [n, R] -> [n, R] float32.  float32,
+    every operation rounded on its own, no fma.  Box: m = -sdf with sdf exactly as wall_check states it (the device: wall_sdf of
+    csrc/kernels_wall.h).  Circle: m = r - sqrt(dx * dx + dy * dy) with dx = px - cx, each product, the sum and the root rounded
+    (the device: the distance of csrc/kernels_hazard.h).  Positive inside, 0 (-0.0 for a box) on the boundary, negative outside."""
+    f32 = np.float32
+    xy, rows = np.asarray(xy, f32), np.asarray(rows, f32)
+    px, py = xy[:, None, 0], xy[:, None, 1]
+    cx, cy, e2, e3 = (rows[..., j] for j in range(4))
+    zero = f32(0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        dx, dy = px - cx, py - cy
+        qx, qy = np.abs(dx) - e2, np.abs(dy) - e3
+        ox, oy = np.maximum(qx, zero), np.maximum(qy, zero)
+        sdf = np.sqrt(ox * ox + oy * oy) + np.minimum(np.maximum(qx, qy), zero)
+        circle = e2 - np.sqrt(dx * dx + dy * dy)
+    return np.where(np.asarray(kinds) == SPEC_CIRCLE, circle, -sdf).astype(f32)
+
+
+def inside(lo, hi=None):
+    """The predicate "inside the union of the regions lo .. hi - 1" (hi=None: the single region lo): its value is the largest
+    inside margin of the range."""
+    return _predicate(lo, hi, False)
+
+
+def outside(lo, hi=None):
+    """The predicate "outside every region lo .. hi - 1" (hi=None: the single region lo): minus the largest inside margin."""
+    return _predicate(lo, hi, True)
+
+
+def _predicate(lo, hi, out):
+    lo = int(lo)
+    hi = lo + 1 if hi is None else int(hi)
+    if lo < 0 or hi < lo:
+        raise ValueError(f"a predicate's region range must obey 0 <= lo <= hi, got [{lo}, {hi})")
+    return (lo, hi, bool(out))
+
+
+class Spec:
+    """A specification: the conjunction of at most SPEC_CLAUSES_MAX clauses over `regions` (a Regions).  A clause is built by
+    Spec.always(pred, a, b), Spec.eventually(pred, a, b) or Spec.until(pred1, pred2, a, b) with predicates from inside() /
+    outside() and a window [a, b] in sample time tau -- the number of global steps completed, tau = 0 the start of the run --,
+    0 <= a <= b, b=None open (SPEC_OPEN).  See spec_fold for the meaning.
+
+    Not built: nested operators (eventually-always, stay-until-the-end), disjunction of clauses, predicates on velocity or on
+    team-mates, moving regions."""
+
+    def __init__(self, regions, clauses):
+        if not isinstance(regions, Regions):
+            raise TypeError(f"regions must be a mobrob_amd.envs.goal_rules.Regions, not {type(regions).__name__}")
+        clauses = list(clauses)
+        if not 1 <= len(clauses) <= SPEC_CLAUSES_MAX:
+            raise ValueError(f"a specification has 1 .. {SPEC_CLAUSES_MAX} clauses, got {len(clauses)}")
+        R = regions.max_regions
+        for c, cl in enumerate(clauses):
+            if not (isinstance(cl, tuple) and len(cl) == 5 and cl[0] in (SPEC_ALWAYS, SPEC_EVENTUALLY, SPEC_UNTIL)):
+                raise TypeError(f"clause {c} is not one of Spec.always / Spec.eventually / Spec.until")
+            for p in cl[3:]:
+                if p[1] > R:
+                    raise ValueError(f"clause {c}: region range [{p[0]}, {p[1]}) outside 0 .. {R}")
+        self.regions, self.clauses = regions, tuple(clauses)
+
+    @property
+    def n_clauses(self):
+        return len(self.clauses)
+
+    @staticmethod
+    def _clause(op, pred1, pred2, a, b):
+        a = int(a)
+        b = SPEC_OPEN if b is None else int(b)
+        if not 0 <= a <= b <= SPEC_OPEN:
+            raise ValueError(f"a window must obey 0 <= a <= b, got [{a}, {b}]")
+        for p in (pred1, pred2):
+            if not (isinstance(p, tuple) and len(p) == 3):
+                raise TypeError("a predicate comes from inside() or outside()")
+        return (op, a, b, pred1, pred2)
+
+    @staticmethod
+    def always(pred, a=0, b=None):
+        return Spec._clause(SPEC_ALWAYS, pred, pred, a, b)
+
+    @staticmethod
+    def eventually(pred, a=0, b=None):
+        return Spec._clause(SPEC_EVENTUALLY, pred, pred, a, b)
+
+    @staticmethod
+    def until(pred1, pred2, a=0, b=None):
+        return Spec._clause(SPEC_UNTIL, pred1, pred2, a, b)
+
+
+class SpecState:
+    """What a specification carries per robot from call to call of a run: val [n][C][2] float32 (rho, guard) and wit [n][C] int32
+    (the witness sample, -1 = none)."""
+
+    def __init__(self, val, wit):
+        self.val, self.wit = np.ascontiguousarray(val, np.float32), np.ascontiguousarray(wit, np.int32)
+        if self.val.ndim != 3 or self.val.shape[2] != 2 or self.wit.shape != self.val.shape[:2]:
+            raise ValueError(f"a SpecState is val [n][C][2] and wit [n][C], got {self.val.shape} and {self.wit.shape}")
+
+    def copy(self):
+        return SpecState(self.val.copy(), self.wit.copy())
+
+
+def spec_start(n, spec):
+    """The state of n robots before their first sample: rho = +inf for ALWAYS, -inf for EVENTUALLY and UNTIL; guard = +inf;
+    witness = -1."""
+    C = spec.n_clauses
+    val = np.full((int(n), C, 2), np.inf, np.float32)
+    for c, cl in enumerate(spec.clauses):
+        if cl[0] != SPEC_ALWAYS:
+            val[:, c, 0] = -np.inf
+    return SpecState(val, np.full((int(n), C), -1, np.int32))
+
+
+def spec_check_state(state, n, spec):
+    if not isinstance(state, SpecState):
+        raise TypeError(f"a specification's state must be a SpecState (spec_start), not {type(state).__name__}")
+    if state.val.shape != (n, spec.n_clauses, 2):
+        raise ValueError(f"the specification's state is for {state.val.shape[:2]} (robots, clauses), the call has {(n, spec.n_clauses)}")
+
+
+def spec_predicate(margins, counts, pred):
+    """The value of a predicate (lo, hi, outside) at one sample: margins [n, R], counts [n] regions of each robot's scene.  u = the
+    maximum of the margins lo .. min(hi, count) - 1, taken by explicit > in ascending order (-inf for an empty range); the value is
+    u for inside, -u for outside."""
+    lo, hi, out = pred
+    u = np.full(margins.shape[0], -np.inf, np.float32)
+    for r in range(lo, min(hi, margins.shape[1])):
+        m = margins[:, r]
+        take = (r < counts) & (m > u)
+        u = np.where(take, m, u)
+    return -u if out else u
+
+
+def spec_fold(state, path, spec, step0=0):
+    """The state after the samples of one call: `path` [T+1][n][P] as follow_waypoints returns it with path_stride=1 (record 0 the
+    position at entry, record r the position after r steps of the call).  With step0 == 0 the records 0 .. T are the samples tau =
+    0 .. T; with step0 > 0 record 0 is skipped -- the previous call folded it as its last -- and the records 1 .. T are tau = step0
+    + 1 .. step0 + T.  Only x and y are used (a missing y is 0).
+
+    Idle robots.  The device kernels (csrc/kernels_follow.h: follow_start / resume start write record 0 for every robot,
+    follow_env_step writes record t + 1 after each step, follow_finish fills every record after a robot's last step with the
+    position it stands at) and the host loop (`path[ran + 1:, i] = pos`) leave no row unwritten: a robot that is finished, stalled,
+    without waypoints or parked in an earlier call holds its position in every record of the call.  The monitor samples whatever
+    position the row holds: a parked robot is still somewhere, and its clauses go on being folded.
+
+    The sample at tau with predicate values v1 (and v2), folded per robot and clause, comparisons explicit and strict so that the
+    first attainment is kept:
+      ALWAYS      if a <= tau <= b and v1 < rho: rho = v1, witness = tau
+      EVENTUALLY  if a <= tau <= b and v1 > rho: rho = v1, witness = tau
+      UNTIL       at every tau: if v1 < guard: guard = v1;  then if a <= tau <= b: w = v2 if v2 < guard else guard; if w > rho:
+                  rho = w, witness = tau  (so pred1 is held from tau = 0 through tau inclusive)
+    Returns a new SpecState."""
+    path = np.asarray(path)
+    if path.ndim != 3 or path.shape[0] < 2 or not 1 <= path.shape[2] <= 3:
+        raise ValueError(f"path must be [T + 1][n][P] with T >= 1 and P in 1 .. 3, got shape {path.shape}")
+    if not np.all(np.isfinite(path)):
+        raise ValueError("path holds non-finite positions")
+    path = path.astype(np.float32)
+    T, n, P = path.shape[0] - 1, path.shape[1], path.shape[2]
+    step0 = int(step0)
+    if step0 < 0 or step0 + T > SPEC_OPEN:
+        raise ValueError("step0 must be >= 0 and step0 + T fit an int32")
+    reg = spec.regions
+    reg.check_robots(n)
+    spec_check_state(state, n, spec)
+    sc = np.zeros(n, np.int64) if reg.scene is None else reg.scene.astype(np.int64)
+    rows, kinds, counts = reg.table[sc], reg.kinds[sc], reg.counts[sc]
+    val, wit = state.val.copy(), state.wit.copy()
+    xy = np.zeros((n, 2), np.float32)
+    for r in range(0 if step0 == 0 else 1, T + 1):
+        tau = step0 + r
+        xy[:, :min(P, 2)] = path[r, :, :2]
+        m = region_margins(xy, rows, kinds)
+        for c, (op, a, b, p1, p2) in enumerate(spec.clauses):
+            rho, guard = val[:, c, 0], val[:, c, 1]
+            v1 = spec_predicate(m, counts, p1)
+            window = a <= tau <= b
+            if op == SPEC_UNTIL:
+                guard = np.where(v1 < guard, v1, guard)
+                val[:, c, 1] = guard
+                v2 = spec_predicate(m, counts, p2)
+                w = np.where(v2 < guard, v2, guard)
+                take = (w > rho) if window else np.zeros(n, bool)
+                new = w
+            else:
+                take = ((v1 < rho) if op == SPEC_ALWAYS else (v1 > rho)) if window else np.zeros(n, bool)
+                new = v1
+            val[:, c, 0] = np.where(take, new, rho)
+            wit[:, c] = np.where(take, tau, wit[:, c])
+    return SpecState(val, wit)
+
+
+def spec_result(state, spec):
+    """The verdict so far, from the carried state: spec_rho [n][C] float32, spec_witness [n][C] int32, robustness [n] float32 (the
+    minimum over the clauses by strict <, ascending), weakest [n] int32 (the clause at that minimum), satisfied [n] bool
+    (robustness > 0: a margin of exactly 0 is not satisfied).  An EVENTUALLY whose window has not opened reads -inf."""
+    rho = state.val[:, :, 0].copy()
+    n, C = rho.shape
+    if C != spec.n_clauses:
+        raise ValueError(f"the state has {C} clauses, the specification {spec.n_clauses}")
+    rob, weak = rho[:, 0].copy(), np.zeros(n, np.int32)
+    for c in range(1, C):
+        take = rho[:, c] < rob
+        rob, weak = np.where(take, rho[:, c], rob), np.where(take, c, weak).astype(np.int32)
+    return {"spec_rho": rho, "spec_witness": state.wit.copy(), "robustness": rob.astype(np.float32), "weakest": weak,
+            "satisfied": rob > 0}

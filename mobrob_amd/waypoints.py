@@ -87,6 +87,20 @@ and the host loop are refused by name.  The dict gains
   team_stopped_steps [n] such steps with no move at all;  team_inside_steps [n] steps inside a mate's square
 and `state.team_blocked` carries the four; with solid walls wall_blocked_steps and its kin count the steps a wall blocked.
 
+With `spec` (a goal_rules.Spec) the run is MONITORED: a small specification language over regions (goal_rules.Regions: boxes and
+circles; x and y only) is evaluated for every robot from the run's positions -- was the goal region visited inside its window, were
+the forbidden regions avoided throughout, was region A kept until B was reached, and by what margin.  A clause is
+Spec.always(pred, a, b), Spec.eventually(pred, a, b) or Spec.until(pred1, pred2, a, b) with predicates inside(lo, hi) / outside(lo,
+hi) over a range of regions read as their union and a window [a, b] in sample time tau (global steps completed; tau = 0 is the
+start); the specification is the conjunction of its clauses (goal_rules.spec_fold states the fold).  The monitor reads `path`, so
+the call needs path_stride=1; it samples whatever position a row holds, and the rows of idle robots hold where they stand.  The
+dict gains
+  spec_rho [n][C] float32 robustness of each clause so far;  spec_witness [n][C] the sample that decided it (-1: none);
+  robustness [n] the smallest clause value;  weakest [n] that clause;  satisfied [n] robustness > 0 (a margin of 0 is not)
+and `state.spec` (a goal_rules.SpecState) carries the fold, so a split run ends on the same bits.  On the device the fold is one
+kernel over the call's path (PPOEngine.spec_monitor), on the host goal_rules.spec_fold; `monitor(path, spec, ...)` below does either
+for a recorded path.  `replan` leaves the monitor alone.  Every other key is what the call without `spec=` returns.
+
 Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
 sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
 into the next call) and `status`, and takes the previous call's `state=`.  Call c covers the global steps step0 .. step0 +
@@ -162,9 +176,11 @@ class FollowState:
                         the walls are solid (`walls` given as the run's Walls, with solid=True)
       team_blocked [n][4] int32 steps blocked by a mate, first such step, fully stopped ones, steps inside a mate's square -- or
                         None unless the teams are solid (`teams` given as the run's Teams, with solid=True)
+      spec              a goal_rules.SpecState: the monitor's fold so far -- or None without a specification
       waypoints [n][K][P] float32, n_waypoints [n] int32: the rows in force (changed by `replan` only)"""
 
-    def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False, schedule=None, walls=False):
+    def __init__(self, start, waypoints, n_waypoints=None, hazards=False, pos_dim=None, teams=False, schedule=None, walls=False,
+                 spec=None):
         s, wp, nw = follow_inputs(start, waypoints, n_waypoints, pos_dim)
         n, K, P = wp.shape
         self.waypoints, self.n_waypoints, self.step0 = wp, nw, 0
@@ -187,6 +203,10 @@ class FollowState:
         if getattr(walls, "solid", False):
             from .envs.goal_rules import BLOCKED_START
             self.blocked = np.tile(np.array(BLOCKED_START, np.int32), (n, 1))
+        self.spec = None
+        if spec is not None:
+            from .envs.goal_rules import spec_start
+            self.spec = spec_start(n, spec)
         self.release = self.home = self.sched = None
         if schedule is not None:
             from .envs.goal_rules import SCHED_START, Schedule
@@ -200,7 +220,8 @@ class FollowState:
 
     def copy(self):
         c = object.__new__(FollowState)
-        c.__dict__ = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self.__dict__.items()}
+        from .envs.goal_rules import SpecState
+        c.__dict__ = {k: (v.copy() if isinstance(v, (np.ndarray, SpecState)) else v) for k, v in self.__dict__.items()}
         return c
 
     @property
@@ -549,8 +570,48 @@ def team_result(team):
             "min_team_clearance": team[:, 3].copy(), "closest_partner": team[:, 4].astype(np.int64)}
 
 
+def monitor(path, spec, step0=0, state=None, engine=None):
+    """A specification folded over a recorded path: path [T + 1][n][P] at stride 1 (record 0 the position at entry), step0 the
+    global step at the path's entry, state the goal_rules.SpecState of the run so far (None: before the first sample).  With
+    `engine` (a PPOEngine, or anything with `.engine`) the fold runs on the device (PPOEngine.spec_monitor), without it is the
+    NumPy rule (goal_rules.spec_fold); both give the same bits.  Returns (the new SpecState, the five keys of spec_result)."""
+    from .envs.goal_rules import Spec, spec_fold, spec_result, spec_start
+    if not isinstance(spec, Spec):
+        raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.Spec, not {type(spec).__name__}")
+    if engine is not None:
+        return getattr(engine, "engine", engine).spec_monitor(spec, path, step0=step0, state=state)
+    if state is None:
+        state = spec_start(np.shape(path)[1], spec)
+    new = spec_fold(state, path, spec, step0)
+    return new, spec_result(new, spec)
+
+
+def _spec_check_call(spec, path_stride, state):
+    """`spec=` of a call: the type, the stride the monitor needs and the run's state.  -> the SpecState at entry, or None (the
+    call starts the run: spec_start once the robots are counted)"""
+    from .envs.goal_rules import Spec
+    if not isinstance(spec, Spec):
+        raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.Spec, not {type(spec).__name__}")
+    if int(path_stride) != 1:
+        raise ValueError(f"spec= monitors the run from its path: it needs path_stride=1, got path_stride={int(path_stride)}")
+    if state is None:
+        return None
+    carried = getattr(state, "spec", None)
+    if carried is None and getattr(state, "step0", 0) != 0:
+        raise ValueError("a run is monitored in every call or in none (FollowState(..., spec=Spec), or spec= from the first call on)")
+    return carried
+
+
+def _spec_fold_call(out, spec, carried, step0, engine):
+    """Folds the call's own path into the monitor and adds the state and the five keys to the call's dict."""
+    new, res = monitor(out["path"], spec, step0=step0, state=carried, engine=engine)
+    out["state"].spec = new
+    out.update(res)
+    return out
+
+
 def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *, max_steps=1000, deterministic=True, seed=0,
-                     path_stride=0, hazards=None, state=None, leg_steps=0, teams=None, schedule=None, walls=None):
+                     path_stride=0, hazards=None, state=None, leg_steps=0, teams=None, schedule=None, walls=None, spec=None):
     """Every robot i follows waypoints[i][:n_waypoints[i]] from start[i] under `model` (a PPO, or for the host path anything
     with `.predict`).  `env`: a DeviceGoalVecEnv (device path), an EnvWrapper, or an env name for `get_env` (host path; a
     fresh environment per robot for a name, the given one reused robot after robot otherwise).  Returns the dict described in
@@ -560,7 +621,8 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
     teams: a goal_rules.Teams (separation costs between team-mates, see the module docstring).
     schedule: a goal_rules.Schedule (release steps and holds, see the module docstring); with `state`, which holds the release
     steps in force, it only says that the run is scheduled.
-    walls: a goal_rules.Walls (box contact and crossing checks, see the module docstring)."""
+    walls: a goal_rules.Walls (box contact and crossing checks, see the module docstring).
+    spec: a goal_rules.Spec (the run is monitored, see the module docstring); needs path_stride=1."""
     from .envs.vec_env import DeviceGoalVecEnv
     from .envs.wrapper import EnvWrapper, TimeLimit, get_env
     max_steps, path_stride = int(max_steps), int(path_stride)
@@ -570,14 +632,20 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         raise ValueError("a resumed call takes its robots and waypoints from `state` (new waypoints: state.replan)")
     if state is None and (start is None or waypoints is None):
         raise ValueError("start and waypoints are needed unless `state` continues a run")
+    if spec is None and getattr(state, "spec", None) is not None:
+        raise ValueError("a run is monitored in every call or in none: state.spec is set, spec= is missing")
+    carried = None if spec is None else _spec_check_call(spec, path_stride, state)
     if isinstance(env, DeviceGoalVecEnv):
         if state is None:
             state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams if teams is not None else False, schedule,
                                 walls if walls is not None else False)
         _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
-        return env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
-                          path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps, teams=teams,
-                          schedule=schedule, walls=walls)
+        if spec is not None:
+            spec.regions.check_robots(state.n_robots)
+        out = env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
+                         path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps, teams=teams,
+                         schedule=schedule, walls=walls)
+        return out if spec is None else _spec_fold_call(out, spec, carried, state.step0, getattr(model, "engine", model))
     if isinstance(env, str):
         name = env
 
@@ -599,20 +667,26 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
     elif isinstance(state, FollowState) and state.waypoints.shape[2] != pos_dim:
         raise ValueError(f"state has {state.waypoints.shape[2]} position dimensions, the environment {pos_dim}")
     leg_steps = _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
-    return _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps, teams, schedule,
-                        walls)
+    if spec is not None:
+        spec.regions.check_robots(state.n_robots)
+    out = _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps, teams, schedule,
+                       walls)
+    return out if spec is None else _spec_fold_call(out, spec, carried, state.step0, None)   # two paths, one meaning: spec_fold
 
 
 def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, rounds, leg_steps=0, n_waypoints=None,
-                           deterministic=True, seed=0, hazards=None, teams=None, schedule=None, walls=None):
+                           deterministic=True, seed=0, hazards=None, teams=None, schedule=None, walls=None, spec=None, path_stride=0):
     """A planner's loop around the tracker: `rounds` calls of `horizon` steps each, one run (see the module docstring).  After
     every round but the last, `planner(positions [n][P], status [n], reached [n])` returns {robot index: new waypoints [k][P]}
     (or None / {} for no change), applied through FollowState.replan.  The loop ends early once no robot is going or stalled
     and the planner changes nothing.  Returns the last call's dict plus `round_status` [rounds run][n].  teams: a
     goal_rules.Teams; the planner callback is unchanged (the team sums are in the returned dict and in its `state`).  schedule: a
     goal_rules.Schedule; a planner that returns {robot: (waypoints, release)} gives the new waypoints release steps (global).
-    walls: a goal_rules.Walls; replanning leaves the wall record alone."""
+    walls: a goal_rules.Walls; replanning leaves the wall record alone.  spec: a goal_rules.Spec -- the run is monitored round
+    after round (needs path_stride=1; `path` is then the last round's) and replanning leaves the monitor alone."""
     horizon, rounds = int(horizon), int(rounds)
+    if spec is not None:
+        _spec_check_call(spec, path_stride, None)
     if horizon < 1 or rounds < 1:
         raise ValueError("horizon and rounds must be >= 1")
     out, state, statuses = None, None, []
@@ -620,7 +694,7 @@ def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, ro
         first = state is None
         out = follow_waypoints(model, env, start if first else None, waypoints if first else None, n_waypoints if first else None,
                                max_steps=horizon, deterministic=deterministic, seed=seed, hazards=hazards, state=state,
-                               leg_steps=leg_steps, teams=teams, schedule=schedule, walls=walls)
+                               leg_steps=leg_steps, teams=teams, schedule=schedule, walls=walls, spec=spec, path_stride=path_stride)
         state = out["state"]
         statuses.append(out["status"].copy())
         if r + 1 == rounds:
