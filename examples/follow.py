@@ -94,9 +94,11 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
            plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False,
-           tile256_wide=False, team_solid=False, check_spec=False):
+           tile256_wide=False, team_solid=False, check_spec=False, spec_hold=0):
     if check_spec and goal is None:
         raise ValueError("--check-spec needs --goal (the specification is: eventually inside the reach radius around the goal)")
+    if int(spec_hold) != 0 and not check_spec:
+        raise ValueError("--spec-hold needs --check-spec")
     if team_solid and team_size is None:
         raise ValueError("--team-solid needs --team-size")
     if solid and walls is None and not arena:
@@ -194,11 +196,12 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     if goal is not None and plan_schedule is not None:
         schedule = plan_schedule
     monitored = {}
-    if check_spec:   # eventually inside the reach circle around the goal; with walls: always outside every one of them
+    if check_spec:   # eventually inside the reach circle around the goal (--spec-hold H: for H steps in a row); with walls: always outside every one
         from mobrob_amd.envs.goal_rules import REACH_RADIUS, Regions, Spec, inside, outside
         boxes = np.zeros((0, 4), np.float32) if wl is None else wl.rows(0)
         regions = Regions(np.concatenate([[[goal[0], goal[1], REACH_RADIUS, 0.0]], boxes]), [1] + [0] * len(boxes))
-        clauses = [Spec.eventually(inside(0))] + ([Spec.always(outside(1, 1 + len(boxes)))] if len(boxes) else [])
+        reach = Spec.eventually(inside(0)) if int(spec_hold) == 0 else Spec.stay(inside(0), int(spec_hold))   # (ValueError above SPEC_HOLD_MAX)
+        clauses = [reach] + ([Spec.always(outside(1, 1 + len(boxes)))] if len(boxes) else [])
         monitored = dict(spec=Spec(regions, clauses), path_stride=1)
     r = follow_waypoints(policy, env, start, waypoints, n_waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
                          leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl, **monitored)
@@ -326,6 +329,9 @@ def build_parser():
     ap.add_argument("--check-spec", action="store_true", default=False,
                     help="with --goal: monitor 'eventually inside the reach radius around the goal' and, with --walls / --arena, "
                          "'always outside every wall'; report the satisfied robots and the worst robustness")
+    ap.add_argument("--spec-hold", type=int, default=0,
+                    help="with --check-spec: 'inside the reach radius around the goal for H consecutive steps' (0 .. 255) in place of "
+                         "'eventually inside'; 0: eventually inside")
     ap.add_argument("--tile256", action="store_true", default=False,
                     help="a 2x256 tanh policy: run calls without hazards, teams or walls as one launch (PPOEngine.set_eval_tile256)")
     ap.add_argument("--tile256-wide", action="store_true", default=False,
@@ -344,6 +350,8 @@ if __name__ == "__main__":
         ap.error("give --waypoints or --goal, not both")
     if args.check_spec and args.goal is None:
         ap.error("--check-spec needs --goal")
+    if args.spec_hold != 0 and not args.check_spec:
+        ap.error("--spec-hold needs --check-spec")
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
     except ValueError as ex:
@@ -360,4 +368,4 @@ if __name__ == "__main__":
            plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
            plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid,
            tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide, team_solid=args.team_solid,
-           check_spec=args.check_spec)
+           check_spec=args.check_spec, spec_hold=args.spec_hold)

@@ -41,7 +41,7 @@ extern "C" {
 /* 2: config slot `persistent_train` became `activation`, `forward_x3` added, MOBROB_K_COUNT 6 -> 7 (profile_read arrays),
  *    MOBROB_BUF_COUNT / reserved[] resized -- a binding built against 1 must not load this library
  * 3: pi_hidden_ext / vf_hidden_ext (net_arch depths 4 .. 8), use_sde, sde_sample_freq appended to the config, activation codes 2 .. 11
- * (entry points added since -- the latest: mobrob_ppo_spec_monitor with its own mobrob_spec_t -- change no existing struct and no existing entry point: a binding
+ * (entry points added since -- the latest: mobrob_ppo_spec_monitor_nested with its own mobrob_spec_nested_t -- change no existing struct and no existing entry point: a binding
  *  built against an earlier 3 loads this library, so the number stays; a binding finds out whether a library has such an entry point by
  *  looking the symbol up) */
 #define MOBROB_PPO_ABI_VERSION 3
@@ -1263,6 +1263,47 @@ typedef struct {
 } mobrob_spec_t;
 int mobrob_ppo_spec_monitor(mobrob_ppo_engine_t* e, const mobrob_spec_t* spec, const float* path /* [T + 1][n][P] */, int32_t n,
                             int32_t T, int32_t P, int32_t step0, float* val /* [n][n_clauses][2] */, int32_t* wit /* [n][n_clauses] */);
+
+/* ---- nested run specifications: stay-for and recurring visits ----------------------------------------------------------------------
+ * mobrob_ppo_spec_monitor with two more ops, each over the sliding window of the last hold + 1 values of predicate 1 (the rule:
+ * goal_rules.spec_fold; k_spec_monitor_nested, csrc/kernels_spec_nested.h, reproduces it bit for bit):
+ *   MOBROB_SPEC_STAY   eventually_[a,b] always_[0,hold]:  at tau >= hold with a <= tau - hold <= b, s = the window's minimum;
+ *                      s > rho: rho = s, witness = tau - hold.  rho starts at -inf.
+ *   MOBROB_SPEC_RECUR  always_[a,b] eventually_[0,hold]:  s = the window's maximum; s < rho: rho = s, witness = tau - hold.  rho
+ *                      starts at +inf.
+ * [a, b] bounds the START of the inner window.  The window's extremum is taken under the total order on float bits (key = i ^ ((i >>
+ * 31) & 0x7fffffff) on the int32 view: -0.0 < +0.0), the outer comparison is the float comparison.  guard is not used and stays
+ * +inf.  A window the run ends before completing is not folded.  hold = 0 is EVENTUALLY / ALWAYS bit for bit.  The flat ops are
+ * folded exactly as mobrob_ppo_spec_monitor folds them.
+ *   hold      per clause, 0 .. MOBROB_SPEC_HOLD_MAX for STAY / RECUR and 0 for a flat op; the sum of (hold + 1) over the nested
+ *             clauses is at most MOBROB_SPEC_WINDOW_SLOTS.
+ *   tail, W   host [n][W] float, in and out, W the sum of the holds: for each nested clause, in clause order, the last `hold` values
+ *             of its predicate, oldest first.  Before a robot's first sample every entry is +inf (STAY) or -inf (RECUR), the caller's
+ *             to set.  NULL is allowed when W == 0.
+ * The call uses the monitor's own buffer outside the arena, as mobrob_ppo_spec_monitor does.  MOBROB_ERR_INVALID before any launch or
+ * copy, val, wit and tail untouched, for everything mobrob_ppo_spec_monitor refuses (an op outside 0 .. 4 here) and for: a hold
+ * outside 0 .. 255; a hold other than 0 on a flat op; windows above the slot cap; a W that is not the sum of the holds; a NULL tail
+ * with W > 0. */
+#define MOBROB_SPEC_STAY 3
+#define MOBROB_SPEC_RECUR 4
+#define MOBROB_SPEC_HOLD_MAX 255
+#define MOBROB_SPEC_WINDOW_SLOTS 512
+typedef struct {
+  int32_t n_scenes, max_regions;   /* mobrob_spec_t's fields, in its order ...                   */
+  const float* regions;
+  const int32_t* kinds;
+  const int32_t* n_regions;
+  const int32_t* scene;
+  int32_t n_clauses;
+  int32_t op[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t a[MOBROB_SPEC_CLAUSES_MAX], b[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t lo1[MOBROB_SPEC_CLAUSES_MAX], hi1[MOBROB_SPEC_CLAUSES_MAX], out1[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t lo2[MOBROB_SPEC_CLAUSES_MAX], hi2[MOBROB_SPEC_CLAUSES_MAX], out2[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t hold[MOBROB_SPEC_CLAUSES_MAX];   /* ... then the inner window of each clause             */
+} mobrob_spec_nested_t;
+int mobrob_ppo_spec_monitor_nested(mobrob_ppo_engine_t* e, const mobrob_spec_nested_t* spec, const float* path /* [T + 1][n][P] */,
+                                   int32_t n, int32_t T, int32_t P, int32_t step0, float* val /* [n][n_clauses][2] */,
+                                   int32_t* wit /* [n][n_clauses] */, float* tail /* [n][W] or NULL */, int32_t W);
 
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment

@@ -116,6 +116,10 @@ class SpecC(C.Structure):  # mobrob_spec_t
                 ("n_clauses", C.c_int32)] + [(k, C.c_int32 * 16) for k in ("op", "a", "b", "lo1", "hi1", "out1", "lo2", "hi2", "out2")]
 
 
+class SpecNestedC(C.Structure):  # mobrob_spec_nested_t: mobrob_spec_t's fields, then hold
+    _fields_ = SpecC._fields_ + [("hold", C.c_int32 * 16)]
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -264,6 +268,8 @@ SYMBOLS = {
                                          C.POINTER(PlanTime), C.c_int32, C.c_int32, _F, _F, C.POINTER(C.c_int32), _F, C.POINTER(C.c_int32),
                                          _I64, C.POINTER(C.c_int32), _I64, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mobrob_ppo_spec_monitor": (C.c_int, [_P, C.POINTER(SpecC), _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, C.POINTER(C.c_int32)]),
+    "mobrob_ppo_spec_monitor_nested": (C.c_int, [_P, C.POINTER(SpecNestedC), _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F,
+                                                 C.POINTER(C.c_int32), _F, C.c_int32]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),
     "mobrob_ppo_buffer_info": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_size_t)]),

@@ -58,6 +58,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_team_solid.h"
 #include "kernels_plan.h"
 #include "kernels_spec.h"
+#include "kernels_spec_nested.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -314,6 +315,7 @@ struct mobrob_ppo_engine {
   // run specifications (mobrob_ppo_spec_monitor): the uploaded path, the carried state and the tables, one allocation of their own
   char* spec_buf = nullptr;
   size_t spec_bytes = 0;
+  bool spec_nested_lds_set = false;   // k_spec_monitor_nested's dynamic-LDS attribute is raised once
 };
 
 namespace {
@@ -5372,8 +5374,9 @@ int mobrob_ppo_plan_assign(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
 
 // ---- run specifications (mobrob_ppo_spec_monitor): robustness per robot from the positions of a run -------------------------------
 // everything the call refuses, before any launch or copy; counts: the scenes' region counts
-static int spec_check(const mobrob_spec_t* spec, const float* path, int N, int T, int P, int step0, std::vector<int32_t>& counts) {
-  const char* who = "spec_monitor";
+// (who: the entry point's name in the messages; max_op: the last op it takes)
+static int spec_check(const char* who, int max_op, const mobrob_spec_t* spec, const float* path, int N, int T, int P, int step0,
+                      std::vector<int32_t>& counts) {
   if (N < 1) return fail(MOBROB_ERR_INVALID, "%s: n must be >= 1, got %d", who, N);
   if (T < 1) return fail(MOBROB_ERR_INVALID, "%s: T must be >= 1, got %d", who, T);
   if (P < 1 || P > 3) return fail(MOBROB_ERR_INVALID, "%s: P must lie in 1 .. 3, got %d", who, P);
@@ -5405,8 +5408,8 @@ static int spec_check(const mobrob_spec_t* spec, const float* path, int N, int T
       if (spec->scene[i] < 0 || spec->scene[i] >= S)
         return fail(MOBROB_ERR_INVALID, "%s: spec: scene[%d] = %d outside 0 .. %d", who, i, spec->scene[i], S - 1);
   for (int c = 0; c < C; ++c) {
-    if (spec->op[c] < MOBROB_SPEC_ALWAYS || spec->op[c] > MOBROB_SPEC_UNTIL)
-      return fail(MOBROB_ERR_INVALID, "%s: spec: op[%d] = %d outside 0 .. 2", who, c, spec->op[c]);
+    if (spec->op[c] < MOBROB_SPEC_ALWAYS || spec->op[c] > max_op)
+      return fail(MOBROB_ERR_INVALID, "%s: spec: op[%d] = %d outside 0 .. %d", who, c, spec->op[c], max_op);
     if (spec->a[c] < 0 || spec->a[c] > spec->b[c])
       return fail(MOBROB_ERR_INVALID, "%s: spec: window of clause %d: a = %d, b = %d do not obey 0 <= a <= b", who, c, spec->a[c], spec->b[c]);
     if (spec->lo1[c] < 0 || spec->lo1[c] > spec->hi1[c] || spec->hi1[c] > R)
@@ -5437,7 +5440,7 @@ int mobrob_ppo_spec_monitor(mobrob_ppo_engine_t* e, const mobrob_spec_t* spec, c
   if (!val) return fail(MOBROB_ERR_INVALID, "spec_monitor: null val");
   if (!wit) return fail(MOBROB_ERR_INVALID, "spec_monitor: null wit");
   std::vector<int32_t> counts;
-  if (const int rc = spec_check(spec, path, n, T, P, step0, counts)) return rc;
+  if (const int rc = spec_check("spec_monitor", MOBROB_SPEC_UNTIL, spec, path, n, T, P, step0, counts)) return rc;
   const int S = spec->n_scenes, R = spec->max_regions, C = spec->n_clauses;
   std::vector<int32_t> clauses((size_t)C * kSpecClauseWords);
   for (int c = 0; c < C; ++c) {
@@ -5476,6 +5479,91 @@ int mobrob_ppo_spec_monitor(mobrob_ppo_engine_t* e, const mobrob_spec_t* spec, c
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(val, a.val, val_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(wit, a.wit, wit_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
+}
+
+// ---- nested run specifications (mobrob_ppo_spec_monitor_nested): the flat call with stay / recur clauses and their carried tail -----
+int mobrob_ppo_spec_monitor_nested(mobrob_ppo_engine_t* e, const mobrob_spec_nested_t* spec, const float* path, int32_t n, int32_t T,
+                                   int32_t P, int32_t step0, float* val, int32_t* wit, float* tail, int32_t W) {
+  const char* who = "spec_monitor_nested";
+  if (!e) return fail(MOBROB_ERR_INVALID, "%s: null engine", who);
+  if (!spec) return fail(MOBROB_ERR_INVALID, "%s: null spec", who);
+  if (!path) return fail(MOBROB_ERR_INVALID, "%s: null path", who);
+  if (!val) return fail(MOBROB_ERR_INVALID, "%s: null val", who);
+  if (!wit) return fail(MOBROB_ERR_INVALID, "%s: null wit", who);
+  // the flat call's checks on the flat call's fields (mobrob_spec_t is the head of mobrob_spec_nested_t, field by field)
+  mobrob_spec_t head;
+  head.n_scenes = spec->n_scenes; head.max_regions = spec->max_regions;
+  head.regions = spec->regions; head.kinds = spec->kinds; head.n_regions = spec->n_regions; head.scene = spec->scene;
+  head.n_clauses = spec->n_clauses;
+  memcpy(head.op, spec->op, sizeof head.op); memcpy(head.a, spec->a, sizeof head.a); memcpy(head.b, spec->b, sizeof head.b);
+  memcpy(head.lo1, spec->lo1, sizeof head.lo1); memcpy(head.hi1, spec->hi1, sizeof head.hi1); memcpy(head.out1, spec->out1, sizeof head.out1);
+  memcpy(head.lo2, spec->lo2, sizeof head.lo2); memcpy(head.hi2, spec->hi2, sizeof head.hi2); memcpy(head.out2, spec->out2, sizeof head.out2);
+  std::vector<int32_t> counts;
+  if (const int rc = spec_check(who, MOBROB_SPEC_RECUR, &head, path, n, T, P, step0, counts)) return rc;
+  const int S = spec->n_scenes, R = spec->max_regions, C = spec->n_clauses;
+  int slots = 0;
+  long long width = 0;
+  std::vector<int32_t> clauses((size_t)C * kSpecNestedClauseWords);
+  for (int c = 0; c < C; ++c) {
+    const int op = spec->op[c], h = spec->hold[c];
+    const bool until = op == MOBROB_SPEC_UNTIL, nested = op >= MOBROB_SPEC_STAY;
+    if (h < 0 || h > MOBROB_SPEC_HOLD_MAX)
+      return fail(MOBROB_ERR_INVALID, "%s: spec: hold[%d] = %d outside 0 .. %d", who, c, h, MOBROB_SPEC_HOLD_MAX);
+    if (!nested && h != 0) return fail(MOBROB_ERR_INVALID, "%s: spec: hold[%d] = %d on the flat op %d (must be 0)", who, c, h, op);
+    const int32_t row[kSpecNestedClauseWords] = {op, spec->a[c], spec->b[c], spec->lo1[c], spec->hi1[c], spec->out1[c] != 0,
+                                                 until ? spec->lo2[c] : 0, until ? spec->hi2[c] : 0, until ? spec->out2[c] != 0 : 0,
+                                                 h, slots, (int32_t)width};
+    std::copy(row, row + kSpecNestedClauseWords, clauses.begin() + (size_t)c * kSpecNestedClauseWords);
+    if (nested) { slots += h + 1; width += h; }
+  }
+  if (slots > MOBROB_SPEC_WINDOW_SLOTS)
+    return fail(MOBROB_ERR_INVALID, "%s: spec: the nested clauses' windows take %d slots (the sum of hold + 1), above %d", who, slots,
+                MOBROB_SPEC_WINDOW_SLOTS);
+  if (W != width) return fail(MOBROB_ERR_INVALID, "%s: W = %d is not the sum of the holds, %lld", who, W, width);
+  if (W > 0 && !tail) return fail(MOBROB_ERR_INVALID, "%s: null tail with W = %d", who, W);
+  const size_t path_bytes = (size_t)(T + 1) * n * P * 4, val_bytes = (size_t)n * C * 8, wit_bytes = (size_t)n * C * 4,
+               tail_bytes = (size_t)n * W * 4;
+  EvalCarve call;
+  const size_t o_path = call.add(path_bytes), o_val = call.add(val_bytes), o_wit = call.add(wit_bytes),
+               o_reg = call.add(std::max<size_t>((size_t)S * R * 16, 4)), o_kind = call.add(std::max<size_t>((size_t)S * R * 4, 4)),
+               o_cnt = call.add((size_t)S * 4), o_scene = call.add((size_t)n * 4), o_cl = call.add(clauses.size() * 4),
+               o_tail = call.add(std::max<size_t>(tail_bytes, 4));
+  if (const int rc = grow_plan_buf(e, e->spec_buf, e->spec_bytes, call.total)) return rc;
+  if (!e->spec_nested_lds_set) {   // up to 158 KB at the slot cap: above the 64 KB a kernel gets without asking
+    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_spec_monitor_nested), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)spec_nested_lds_bytes(kSpecWindowSlots)));
+    e->spec_nested_lds_set = true;
+  }
+  const auto mine = [&](size_t off) { return e->spec_buf + off; };
+  SpecNestedArgs na{};
+  SpecArgs& a = na.f;
+  a.path = reinterpret_cast<float*>(mine(o_path));
+  a.regions = reinterpret_cast<float*>(mine(o_reg)); a.kinds = reinterpret_cast<int*>(mine(o_kind));
+  a.nreg = reinterpret_cast<int*>(mine(o_cnt)); a.scene = spec->scene ? reinterpret_cast<int*>(mine(o_scene)) : nullptr;
+  a.clauses = reinterpret_cast<int*>(mine(o_cl));
+  a.val = reinterpret_cast<float*>(mine(o_val)); a.wit = reinterpret_cast<int*>(mine(o_wit));
+  a.N = n; a.T = T; a.P = P; a.R = R; a.C = C;
+  a.r0 = step0 == 0 ? 0 : 1;
+  a.tau0 = step0;
+  na.tail = reinterpret_cast<float*>(mine(o_tail)); na.W = W;
+  HIPC(hipMemcpyAsync(mine(o_path), path, path_bytes, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_val), val, val_bytes, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_wit), wit, wit_bytes, hipMemcpyHostToDevice, e->stream));
+  if (tail_bytes) HIPC(hipMemcpyAsync(mine(o_tail), tail, tail_bytes, hipMemcpyHostToDevice, e->stream));
+  if ((size_t)S * R) {
+    HIPC(hipMemcpyAsync(mine(o_reg), spec->regions, (size_t)S * R * 16, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(mine(o_kind), spec->kinds, (size_t)S * R * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  HIPC(hipMemcpyAsync(mine(o_cnt), counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  if (spec->scene) HIPC(hipMemcpyAsync(mine(o_scene), spec->scene, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_cl), clauses.data(), clauses.size() * 4, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_spec_monitor_nested, dim3(cdiv(n, 64)), dim3(64), spec_nested_lds_bytes(slots), e->stream, na);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(val, a.val, val_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(wit, a.wit, wit_bytes, hipMemcpyDeviceToHost, e->stream));
+  if (tail_bytes) HIPC(hipMemcpyAsync(tail, na.tail, tail_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
 }

@@ -679,8 +679,10 @@ class PPOEngine:
         """A specification folded over the positions of one call of a run (mobrob_ppo_spec_monitor; the rule: goal_rules.spec_fold,
         reproduced bit for bit).  spec: a goal_rules.Spec; path [T + 1][n][P] as follow_waypoints returns it with path_stride=1;
         step0: the run's global step at the call's entry; state: the goal_rules.SpecState the previous call returned (None:
-        spec_start).  Returns (the new SpecState, goal_rules.spec_result of it)."""
-        from ._lib import SpecC
+        spec_start).  Returns (the new SpecState, goal_rules.spec_result of it).  A specification with a nested clause (Spec.stay /
+        Spec.recur) goes through mobrob_ppo_spec_monitor_nested, which also carries the state's tail; one without takes
+        mobrob_ppo_spec_monitor as before."""
+        from ._lib import SpecC, SpecNestedC
         from .envs.goal_rules import SPEC_UNTIL, Spec, SpecState, spec_check_state, spec_result, spec_start
         if not isinstance(spec, Spec):
             raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.Spec, not {type(spec).__name__}")
@@ -697,17 +699,24 @@ class PPOEngine:
             raise ValueError("spec_monitor: step0 must fit an int32")
         new = state.copy()
         i32 = C.POINTER(C.c_int32)
-        sp = SpecC()
+        sp = SpecNestedC() if spec.nested else SpecC()
         sp.n_scenes, sp.max_regions, sp.n_clauses = reg.n_scenes, reg.max_regions, spec.n_clauses
         sp.regions, sp.kinds, sp.n_regions = _fp(reg.table), reg.kinds.ctypes.data_as(i32), reg.counts.ctypes.data_as(i32)
         sp.scene = None if reg.scene is None else reg.scene.ctypes.data_as(i32)
-        for c, (op, a, b, p1, p2) in enumerate(spec.clauses):
+        for c, (op, a, b, p1, p2) in enumerate(cl[:5] for cl in spec.clauses):
             sp.op[c], sp.a[c], sp.b[c] = op, a, b
             sp.lo1[c], sp.hi1[c], sp.out1[c] = p1[0], p1[1], int(p1[2])
             if op == SPEC_UNTIL:
                 sp.lo2[c], sp.hi2[c], sp.out2[c] = p2[0], p2[1], int(p2[2])
-        check(self.lib.mobrob_ppo_spec_monitor(self._h, C.byref(sp), _fp(path), n, T, P, int(step0), _fp(new.val),
-                                               new.wit.ctypes.data_as(i32)))
+        if spec.nested:
+            for c, h in enumerate(spec.holds):
+                sp.hold[c] = h
+            W = spec.tail_width
+            check(self.lib.mobrob_ppo_spec_monitor_nested(self._h, C.byref(sp), _fp(path), n, T, P, int(step0), _fp(new.val),
+                                                          new.wit.ctypes.data_as(i32), _fp(new.tail) if W else None, W))
+        else:
+            check(self.lib.mobrob_ppo_spec_monitor(self._h, C.byref(sp), _fp(path), n, T, P, int(step0), _fp(new.val),
+                                                   new.wit.ctypes.data_as(i32)))
         return new, spec_result(new, spec)
 
     def plan_grid(self, spec, walls=None, hazards=None, *, start, goal, max_waypoints=16, want_occupancy=False, want_fields=False,

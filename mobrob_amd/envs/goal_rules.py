@@ -2427,11 +2427,15 @@ def grid_assign(spec, walls, hazards, start, goal, teams, objective="sum", step0
 
 
 # ---- run specifications: reach / avoid / until robustness per robot, from the positions of a run (the device: csrc/kernels_spec.h,
-# k_spec_monitor, held to this bit for bit).  Stated here once; waypoints.monitor, the host loop and PPOEngine.spec_monitor apply it.
+# k_spec_monitor, and csrc/kernels_spec_nested.h, k_spec_monitor_nested, for a specification with a nested clause; both held to this
+# bit for bit).  Stated here once; waypoints.monitor, the host loop and PPOEngine.spec_monitor apply it.
 SPEC_REGIONS_MAX = 64           # regions per scene
 SPEC_CLAUSES_MAX = 16           # clauses of a specification
 SPEC_OPEN = 2 ** 31 - 1         # the right end of an open window
 SPEC_ALWAYS, SPEC_EVENTUALLY, SPEC_UNTIL = 0, 1, 2
+SPEC_STAY, SPEC_RECUR = 3, 4    # the nested clauses: eventually-always and always-eventually over a sliding window (spec_fold)
+SPEC_HOLD_MAX = 255             # the longest inner window [t, t + h] of a nested clause
+SPEC_WINDOW_SLOTS = 512         # the sum of (h + 1) over the nested clauses of a specification (the device's window block)
 SPEC_BOX, SPEC_CIRCLE = 0, 1    # region kinds
 SPEC_RESULT_KEYS = ("spec_rho", "spec_witness", "robustness", "weakest", "satisfied")
 
@@ -2557,8 +2561,18 @@ class Spec:
     outside() and a window [a, b] in sample time tau -- the number of global steps completed, tau = 0 the start of the run --,
     0 <= a <= b, b=None open (SPEC_OPEN).  See spec_fold for the meaning.
 
-    Not built: nested operators (eventually-always, stay-until-the-end), disjunction of clauses, predicates on velocity or on
-    team-mates, moving regions."""
+    The two nested clauses fold a sliding-window extremum of their predicate:
+      Spec.stay(pred, hold, a, b)     eventually_[a,b] always_[0,hold] pred: inside for hold + 1 consecutive samples, somewhere
+      Spec.recur(pred, every, a, b)   always_[a,b] eventually_[0,every] pred: in every window of every + 1 samples at least once
+    with h = hold (or every) an integer in 0 .. SPEC_HOLD_MAX and [a, b] bounding the START t of the inner window [t, t + h].  The
+    sum of (h + 1) over a specification's nested clauses is at most SPEC_WINDOW_SLOTS.  A window that the run ends before
+    completing is not folded: a stay whose hold outlasts the run reads -inf, a recur with no complete window +inf (as an ALWAYS
+    whose window never opened).  h = 0 is eventually / always, bit for bit, witness included.  "Stay until the end of the run" is
+    no operator of its own: on a finite trace of T steps it is the last sample, and stay(pred, hold, a=T - hold, b=T - hold) asks
+    for the last hold + 1 samples.
+
+    Not built: deeper nesting (an until inside a window, a window inside a window), disjunction of clauses, predicates on velocity
+    or on team-mates, moving regions."""
 
     def __init__(self, regions, clauses):
         if not isinstance(regions, Regions):
@@ -2568,12 +2582,25 @@ class Spec:
             raise ValueError(f"a specification has 1 .. {SPEC_CLAUSES_MAX} clauses, got {len(clauses)}")
         R = regions.max_regions
         for c, cl in enumerate(clauses):
-            if not (isinstance(cl, tuple) and len(cl) == 5 and cl[0] in (SPEC_ALWAYS, SPEC_EVENTUALLY, SPEC_UNTIL)):
-                raise TypeError(f"clause {c} is not one of Spec.always / Spec.eventually / Spec.until")
-            for p in cl[3:]:
+            flat = isinstance(cl, tuple) and len(cl) == 5 and cl[0] in (SPEC_ALWAYS, SPEC_EVENTUALLY, SPEC_UNTIL)
+            nested = isinstance(cl, tuple) and len(cl) == 6 and cl[0] in (SPEC_STAY, SPEC_RECUR)
+            if not (flat or nested):
+                raise TypeError(f"clause {c} is not one of Spec.always / Spec.eventually / Spec.until / Spec.stay / Spec.recur")
+            for p in cl[3:5]:
                 if p[1] > R:
                     raise ValueError(f"clause {c}: region range [{p[0]}, {p[1]}) outside 0 .. {R}")
+            if nested:
+                _hold(cl[5], f"clause {c}: hold")
         self.regions, self.clauses = regions, tuple(clauses)
+        # per clause: the inner window's h (0 for a flat clause) and where its h values start in SpecState.tail
+        self.holds = tuple(cl[5] if len(cl) == 6 else 0 for cl in self.clauses)
+        self.nested = any(len(cl) == 6 for cl in self.clauses)
+        self.tail_offsets = tuple(int(v) for v in np.cumsum((0,) + self.holds)[:-1])
+        self.tail_width = sum(self.holds)
+        slots = sum(h + 1 for cl, h in zip(self.clauses, self.holds) if len(cl) == 6)
+        if slots > SPEC_WINDOW_SLOTS:
+            raise ValueError(f"the nested clauses' windows take {slots} slots (the sum of hold + 1), above SPEC_WINDOW_SLOTS = "
+                             f"{SPEC_WINDOW_SLOTS}")
 
     @property
     def n_clauses(self):
@@ -2602,29 +2629,62 @@ class Spec:
     def until(pred1, pred2, a=0, b=None):
         return Spec._clause(SPEC_UNTIL, pred1, pred2, a, b)
 
+    @staticmethod
+    def stay(pred, hold, a=0, b=None):
+        """eventually_[a,b] always_[0,hold] pred: the best, over the window starts t in [a, b], of the worst value in [t, t + hold]"""
+        return Spec._clause(SPEC_STAY, pred, pred, a, b) + (_hold(hold, "stay: hold"),)
+
+    @staticmethod
+    def recur(pred, every, a=0, b=None):
+        """always_[a,b] eventually_[0,every] pred: the worst, over the window starts t in [a, b], of the best value in [t, t + every]"""
+        return Spec._clause(SPEC_RECUR, pred, pred, a, b) + (_hold(every, "recur: every"),)
+
+
+def _hold(h, what):
+    if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or not 0 <= h <= SPEC_HOLD_MAX:
+        raise ValueError(f"{what} must be an integer in 0 .. SPEC_HOLD_MAX = {SPEC_HOLD_MAX}, got {h!r}")
+    return int(h)
+
+
+def spec_key(v):
+    """The total order on float32 bits as an int32 key: key = i ^ ((i >> 31) & 0x7fffffff) on the int32 view, so that -0.0 < +0.0
+    and every bit pattern has its place.  The inner extremum of a nested clause is taken under it: a box margin is -0.0 on the
+    boundary and a circle's +0.0, and under float comparison the bits of a window's minimum would depend on the order in which an
+    implementation visits the window.  With the key a ring rescan, a monotonic queue and a block scan all give the same bits."""
+    i = np.ascontiguousarray(v, np.float32).view(np.int32)
+    return i ^ ((i >> 31) & np.int32(0x7fffffff))
+
 
 class SpecState:
-    """What a specification carries per robot from call to call of a run: val [n][C][2] float32 (rho, guard) and wit [n][C] int32
-    (the witness sample, -1 = none)."""
+    """What a specification carries per robot from call to call of a run: val [n][C][2] float32 (rho, guard), wit [n][C] int32
+    (the witness sample, -1 = none) and tail [n][W] float32, W the sum of h over the nested clauses in clause order: for each
+    nested clause the last h values of its predicate, oldest first (chronological, not a ring position, so that two
+    implementations agree on its bits).  tail=None is [n][0], the tail of a specification without nested clauses."""
 
-    def __init__(self, val, wit):
+    def __init__(self, val, wit, tail=None):
         self.val, self.wit = np.ascontiguousarray(val, np.float32), np.ascontiguousarray(wit, np.int32)
         if self.val.ndim != 3 or self.val.shape[2] != 2 or self.wit.shape != self.val.shape[:2]:
             raise ValueError(f"a SpecState is val [n][C][2] and wit [n][C], got {self.val.shape} and {self.wit.shape}")
+        self.tail = np.zeros((self.val.shape[0], 0), np.float32) if tail is None else np.ascontiguousarray(tail, np.float32)
+        if self.tail.ndim != 2 or self.tail.shape[0] != self.val.shape[0]:
+            raise ValueError(f"a SpecState's tail is [n][W] with n = {self.val.shape[0]}, got {self.tail.shape}")
 
     def copy(self):
-        return SpecState(self.val.copy(), self.wit.copy())
+        return SpecState(self.val.copy(), self.wit.copy(), self.tail.copy())
 
 
 def spec_start(n, spec):
-    """The state of n robots before their first sample: rho = +inf for ALWAYS, -inf for EVENTUALLY and UNTIL; guard = +inf;
-    witness = -1."""
+    """The state of n robots before their first sample: rho = +inf for ALWAYS and RECUR, -inf for EVENTUALLY, UNTIL and STAY; guard
+    = +inf; witness = -1; every tail entry +inf for STAY and -inf for RECUR (what an always / an eventually over nothing reads)."""
     C = spec.n_clauses
     val = np.full((int(n), C, 2), np.inf, np.float32)
+    tail = np.full((int(n), spec.tail_width), np.inf, np.float32)
     for c, cl in enumerate(spec.clauses):
-        if cl[0] != SPEC_ALWAYS:
+        if cl[0] not in (SPEC_ALWAYS, SPEC_RECUR):
             val[:, c, 0] = -np.inf
-    return SpecState(val, np.full((int(n), C), -1, np.int32))
+        if cl[0] == SPEC_RECUR:
+            tail[:, spec.tail_offsets[c]:spec.tail_offsets[c] + spec.holds[c]] = -np.inf
+    return SpecState(val, np.full((int(n), C), -1, np.int32), tail)
 
 
 def spec_check_state(state, n, spec):
@@ -2632,6 +2692,8 @@ def spec_check_state(state, n, spec):
         raise TypeError(f"a specification's state must be a SpecState (spec_start), not {type(state).__name__}")
     if state.val.shape != (n, spec.n_clauses, 2):
         raise ValueError(f"the specification's state is for {state.val.shape[:2]} (robots, clauses), the call has {(n, spec.n_clauses)}")
+    if state.tail.shape != (n, spec.tail_width):
+        raise ValueError(f"the specification's state has a tail of shape {state.tail.shape}, the nested clauses need {(n, spec.tail_width)}")
 
 
 def spec_predicate(margins, counts, pred):
@@ -2665,6 +2727,13 @@ def spec_fold(state, path, spec, step0=0):
       EVENTUALLY  if a <= tau <= b and v1 > rho: rho = v1, witness = tau
       UNTIL       at every tau: if v1 < guard: guard = v1;  then if a <= tau <= b: w = v2 if v2 < guard else guard; if w > rho:
                   rho = w, witness = tau  (so pred1 is held from tau = 0 through tau inclusive)
+    and for the nested clauses, h the clause's hold, the window the last h + 1 values v1(tau - h) .. v1(tau) (the carried tail and
+    this sample's value):
+      STAY        if tau >= h and a <= tau - h <= b: s = the window's minimum; if s > rho: rho = s, witness = tau - h
+      RECUR       if tau >= h and a <= tau - h <= b: s = the window's maximum; if s < rho: rho = s, witness = tau - h
+    The inner extremum is taken under the total order on float32 bits (spec_key: -0.0 < +0.0), the outer comparison is the float
+    comparison of the flat clauses; guard is not used and stays +inf.  A window the run ends before completing is never folded;
+    the tail then carries its values into the next call.  After every sample the tail is the last h values, oldest first.
     Returns a new SpecState."""
     path = np.asarray(path)
     if path.ndim != 3 or path.shape[0] < 2 or not 1 <= path.shape[2] <= 3:
@@ -2681,16 +2750,29 @@ def spec_fold(state, path, spec, step0=0):
     spec_check_state(state, n, spec)
     sc = np.zeros(n, np.int64) if reg.scene is None else reg.scene.astype(np.int64)
     rows, kinds, counts = reg.table[sc], reg.kinds[sc], reg.counts[sc]
-    val, wit = state.val.copy(), state.wit.copy()
+    val, wit, tail = state.val.copy(), state.wit.copy(), state.tail.copy()
     xy = np.zeros((n, 2), np.float32)
+    rows_n = np.arange(n)
     for r in range(0 if step0 == 0 else 1, T + 1):
         tau = step0 + r
         xy[:, :min(P, 2)] = path[r, :, :2]
         m = region_margins(xy, rows, kinds)
-        for c, (op, a, b, p1, p2) in enumerate(spec.clauses):
+        for c, (op, a, b, p1, p2) in enumerate(cl[:5] for cl in spec.clauses):
             rho, guard = val[:, c, 0], val[:, c, 1]
             v1 = spec_predicate(m, counts, p1)
             window = a <= tau <= b
+            if op in (SPEC_STAY, SPEC_RECUR):
+                h, o = spec.holds[c], spec.tail_offsets[c]
+                win = np.concatenate([tail[:, o:o + h], v1[:, None].astype(np.float32)], axis=1)   # v1(tau - h) .. v1(tau)
+                tail[:, o:o + h] = win[:, 1:]
+                if not (tau >= h and a <= tau - h <= b):
+                    continue
+                key = spec_key(win)
+                new = win[rows_n, np.argmin(key, axis=1) if op == SPEC_STAY else np.argmax(key, axis=1)]
+                take = (new > rho) if op == SPEC_STAY else (new < rho)
+                val[:, c, 0] = np.where(take, new, rho)
+                wit[:, c] = np.where(take, tau - h, wit[:, c])
+                continue
             if op == SPEC_UNTIL:
                 guard = np.where(v1 < guard, v1, guard)
                 val[:, c, 1] = guard
@@ -2703,7 +2785,7 @@ def spec_fold(state, path, spec, step0=0):
                 new = v1
             val[:, c, 0] = np.where(take, new, rho)
             wit[:, c] = np.where(take, tau, wit[:, c])
-    return SpecState(val, wit)
+    return SpecState(val, wit, tail)
 
 
 def spec_result(state, spec):

@@ -90,7 +90,8 @@ and `state.team_blocked` carries the four; with solid walls wall_blocked_steps a
 With `spec` (a goal_rules.Spec) the run is MONITORED: a small specification language over regions (goal_rules.Regions: boxes and
 circles; x and y only) is evaluated for every robot from the run's positions -- was the goal region visited inside its window, were
 the forbidden regions avoided throughout, was region A kept until B was reached, and by what margin.  A clause is
-Spec.always(pred, a, b), Spec.eventually(pred, a, b) or Spec.until(pred1, pred2, a, b) with predicates inside(lo, hi) / outside(lo,
+Spec.always(pred, a, b), Spec.eventually(pred, a, b), Spec.until(pred1, pred2, a, b), Spec.stay(pred, hold, a, b) (inside for hold
+consecutive steps) or Spec.recur(pred, every, a, b) (at least once in every window of `every` steps) with predicates inside(lo, hi) / outside(lo,
 hi) over a range of regions read as their union and a window [a, b] in sample time tau (global steps completed; tau = 0 is the
 start); the specification is the conjunction of its clauses (goal_rules.spec_fold states the fold).  The monitor reads `path`, so
 the call needs path_stride=1; it samples whatever position a row holds, and the rows of idle robots hold where they stand.  The
