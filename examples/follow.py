@@ -196,13 +196,22 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     if goal is not None and plan_schedule is not None:
         schedule = plan_schedule
     monitored = {}
-    if check_spec:   # eventually inside the reach circle around the goal (--spec-hold H: for H steps in a row); with walls: always outside every one
+    if check_spec:   # eventually inside the reach circle around the goal (--spec-hold H: for H steps in a row); with walls: always outside every one;
+        # with moving hazards: outside every one from the first step on; with teams: always further than the separation from every mate
         from mobrob_amd.envs.goal_rules import REACH_RADIUS, Regions, Spec, inside, outside
         boxes = np.zeros((0, 4), np.float32) if wl is None else wl.rows(0)
         regions = Regions(np.concatenate([[[goal[0], goal[1], REACH_RADIUS, 0.0]], boxes]), [1] + [0] * len(boxes))
         reach = Spec.eventually(inside(0)) if int(spec_hold) == 0 else Spec.stay(inside(0), int(spec_hold))   # (ValueError above SPEC_HOLD_MAX)
         clauses = [reach] + ([Spec.always(outside(1, 1 + len(boxes)))] if len(boxes) else [])
-        monitored = dict(spec=Spec(regions, clauses), path_stride=1)
+        if isinstance(hz, MovingHazards):   # --hazard-frames: never inside a moving hazard, from the first step on
+            from mobrob_amd.envs.goal_rules import MovingRegions
+            first = regions.max_regions
+            regions = MovingRegions.join(regions, MovingRegions.from_hazards(hz))
+            clauses.append(Spec.always(outside(first, regions.max_regions), a=1))
+        if teams is not None:               # --team-size / --separation: always further than the separation from every mate
+            from mobrob_amd.envs.goal_rules import apart
+            clauses.append(Spec.always(apart(teams.separation)))
+        monitored = dict(spec=Spec(regions, clauses, team_size=1 if teams is None else teams.size), path_stride=1)
     r = follow_waypoints(policy, env, start, waypoints, n_waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
                          leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl, **monitored)
     for steps in calls[1:]:                                # the run, continued call after call
@@ -328,7 +337,9 @@ def build_parser():
     ap.add_argument("--stagger", type=int, default=0, help="release robot m of a team (robot i without teams) m * S steps later")
     ap.add_argument("--check-spec", action="store_true", default=False,
                     help="with --goal: monitor 'eventually inside the reach radius around the goal' and, with --walls / --arena, "
-                         "'always outside every wall'; report the satisfied robots and the worst robustness")
+                         "'always outside every wall'; with --hazard-frames, 'outside every moving hazard from the first step on'; "
+                         "with --team-size / --separation, 'always further than the separation from every team-mate'; report the "
+                         "satisfied robots and the worst robustness")
     ap.add_argument("--spec-hold", type=int, default=0,
                     help="with --check-spec: 'inside the reach radius around the goal for H consecutive steps' (0 .. 255) in place of "
                          "'eventually inside'; 0: eventually inside")

@@ -41,7 +41,7 @@ extern "C" {
 /* 2: config slot `persistent_train` became `activation`, `forward_x3` added, MOBROB_K_COUNT 6 -> 7 (profile_read arrays),
  *    MOBROB_BUF_COUNT / reserved[] resized -- a binding built against 1 must not load this library
  * 3: pi_hidden_ext / vf_hidden_ext (net_arch depths 4 .. 8), use_sde, sde_sample_freq appended to the config, activation codes 2 .. 11
- * (entry points added since -- the latest: mobrob_ppo_spec_monitor_nested with its own mobrob_spec_nested_t -- change no existing struct and no existing entry point: a binding
+ * (entry points added since -- the latest: mobrob_ppo_spec_monitor_moving with its own mobrob_spec_moving_t -- change no existing struct and no existing entry point: a binding
  *  built against an earlier 3 loads this library, so the number stays; a binding finds out whether a library has such an entry point by
  *  looking the symbol up) */
 #define MOBROB_PPO_ABI_VERSION 3
@@ -1302,6 +1302,48 @@ typedef struct {
   int32_t hold[MOBROB_SPEC_CLAUSES_MAX];   /* ... then the inner window of each clause             */
 } mobrob_spec_nested_t;
 int mobrob_ppo_spec_monitor_nested(mobrob_ppo_engine_t* e, const mobrob_spec_nested_t* spec, const float* path /* [T + 1][n][P] */,
+                                   int32_t n, int32_t T, int32_t P, int32_t step0, float* val /* [n][n_clauses][2] */,
+                                   int32_t* wit /* [n][n_clauses] */, float* tail /* [n][W] or NULL */, int32_t W);
+
+/* ---- run specifications over things that move: moving regions and predicates on team-mates -----------------------------------------
+ * mobrob_ppo_spec_monitor_nested with a frame axis on the region table and two more kinds of predicate (the rule: goal_rules.py,
+ * MovingRegions, spec_mate_predicate, spec_fold; k_spec_monitor_moving, csrc/kernels_spec_moving.h, reproduces it bit for bit):
+ *   frames    regions is [n_scenes][n_frames][max_regions][4]; kinds and n_regions have no frame axis.  The sample at tau reads the
+ *             frame f(max(tau - 1, 0)), f(g) = min(g / frame_steps, n_frames - 1), or (g / frame_steps) % n_frames with loop = 1:
+ *             the frame that mobrob_ppo_follow_waypoints_hazard_frames used in the check of the step before the sample.
+ *   kind1, kind2   what predicate 1 / 2 of a clause reads: MOBROB_SPEC_PRED_REGIONS its region range, as before;
+ *             MOBROB_SPEC_PRED_TOGETHER / _APART the robot's team-mates at this sample's record (the region range is ignored and
+ *             must be a legal one, [0, 0) for instance).  Robot i has the mates j = (i / team_size) * team_size + m, m ascending,
+ *             j != i; g_j = rad - sqrt(dx * dx + dy * dy), dx = px_i - px_j, every operation rounded on its own.  TOGETHER is the
+ *             minimum of the g_j by explicit < from +inf, APART minus their maximum by explicit > from -inf; a team of one reads
+ *             +inf for both.  kind2 and rad2 count for UNTIL only.
+ *   rad1, rad2     the distance d of a mate predicate; finite and >= 0 in every clause (0 for a region predicate).
+ * n_frames = 1, team_size = 1 and kinds of 0 give mobrob_ppo_spec_monitor_nested's bits.  The call uses the monitor's own buffer
+ * outside the arena.  MOBROB_ERR_INVALID before any launch or copy, val, wit and tail untouched, for everything
+ * mobrob_ppo_spec_monitor_nested refuses and for: a team_size other than 1, 2, 4, 8, 16; n not a multiple of team_size; a kind
+ * outside 0 .. 2; a radius that is negative or not finite; n_frames < 1; frame_steps < 1; loop other than 0 or 1; a region table
+ * above MOBROB_SPEC_FRAMES_MAX_BYTES; a region that is not finite or has a negative extent in any frame. */
+#define MOBROB_SPEC_PRED_REGIONS 0
+#define MOBROB_SPEC_PRED_TOGETHER 1
+#define MOBROB_SPEC_PRED_APART 2
+#define MOBROB_SPEC_FRAMES_MAX_BYTES (64u << 20)
+typedef struct {
+  int32_t n_scenes, max_regions;   /* mobrob_spec_nested_t's fields, in its order ...            */
+  const float* regions;            /* [n_scenes][n_frames][max_regions][4]                       */
+  const int32_t* kinds;
+  const int32_t* n_regions;
+  const int32_t* scene;
+  int32_t n_clauses;
+  int32_t op[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t a[MOBROB_SPEC_CLAUSES_MAX], b[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t lo1[MOBROB_SPEC_CLAUSES_MAX], hi1[MOBROB_SPEC_CLAUSES_MAX], out1[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t lo2[MOBROB_SPEC_CLAUSES_MAX], hi2[MOBROB_SPEC_CLAUSES_MAX], out2[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t hold[MOBROB_SPEC_CLAUSES_MAX];
+  int32_t kind1[MOBROB_SPEC_CLAUSES_MAX], kind2[MOBROB_SPEC_CLAUSES_MAX];   /* ... then what each predicate reads ... */
+  float rad1[MOBROB_SPEC_CLAUSES_MAX], rad2[MOBROB_SPEC_CLAUSES_MAX];       /* ... a mate predicate's distance ...    */
+  int32_t team_size, n_frames, frame_steps, loop;                           /* ... the teams and the frames           */
+} mobrob_spec_moving_t;
+int mobrob_ppo_spec_monitor_moving(mobrob_ppo_engine_t* e, const mobrob_spec_moving_t* spec, const float* path /* [T + 1][n][P] */,
                                    int32_t n, int32_t T, int32_t P, int32_t step0, float* val /* [n][n_clauses][2] */,
                                    int32_t* wit /* [n][n_clauses] */, float* tail /* [n][W] or NULL */, int32_t W);
 

@@ -120,6 +120,12 @@ class SpecNestedC(C.Structure):  # mobrob_spec_nested_t: mobrob_spec_t's fields,
     _fields_ = SpecC._fields_ + [("hold", C.c_int32 * 16)]
 
 
+class SpecMovingC(C.Structure):  # mobrob_spec_moving_t: mobrob_spec_nested_t's fields, then the predicate kinds, the distances, teams, frames
+    _fields_ = (SpecNestedC._fields_ + [("kind1", C.c_int32 * 16), ("kind2", C.c_int32 * 16), ("rad1", C.c_float * 16),
+                                        ("rad2", C.c_float * 16)]
+                + [(k, C.c_int32) for k in ("team_size", "n_frames", "frame_steps", "loop")])
+
+
 _P, _F, _U8, _I64 = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 SYMBOLS = {
     "mobrob_ppo_default_config": (None, [C.POINTER(Config)]),
@@ -269,6 +275,8 @@ SYMBOLS = {
                                          _I64, C.POINTER(C.c_int32), _I64, _I64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mobrob_ppo_spec_monitor": (C.c_int, [_P, C.POINTER(SpecC), _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, C.POINTER(C.c_int32)]),
     "mobrob_ppo_spec_monitor_nested": (C.c_int, [_P, C.POINTER(SpecNestedC), _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F,
+                                                 C.POINTER(C.c_int32), _F, C.c_int32]),
+    "mobrob_ppo_spec_monitor_moving": (C.c_int, [_P, C.POINTER(SpecMovingC), _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F,
                                                  C.POINTER(C.c_int32), _F, C.c_int32]),
     "mobrob_ppo_sde_reset_noise": (C.c_int, [_P]),
     "mobrob_ppo_sde_set_noise": (C.c_int, [_P, _F]),

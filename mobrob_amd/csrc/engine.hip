@@ -59,6 +59,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_plan.h"
 #include "kernels_spec.h"
 #include "kernels_spec_nested.h"
+#include "kernels_spec_moving.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -316,6 +317,7 @@ struct mobrob_ppo_engine {
   char* spec_buf = nullptr;
   size_t spec_bytes = 0;
   bool spec_nested_lds_set = false;   // k_spec_monitor_nested's dynamic-LDS attribute is raised once
+  bool spec_moving_lds_set = false;   // k_spec_monitor_moving's likewise
 };
 
 namespace {
@@ -5374,9 +5376,9 @@ int mobrob_ppo_plan_assign(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
 
 // ---- run specifications (mobrob_ppo_spec_monitor): robustness per robot from the positions of a run -------------------------------
 // everything the call refuses, before any launch or copy; counts: the scenes' region counts
-// (who: the entry point's name in the messages; max_op: the last op it takes)
+// (who: the entry point's name in the messages; max_op: the last op it takes; F: the frames of a region table [S][F][R][4])
 static int spec_check(const char* who, int max_op, const mobrob_spec_t* spec, const float* path, int N, int T, int P, int step0,
-                      std::vector<int32_t>& counts) {
+                      std::vector<int32_t>& counts, int F = 1) {
   if (N < 1) return fail(MOBROB_ERR_INVALID, "%s: n must be >= 1, got %d", who, N);
   if (T < 1) return fail(MOBROB_ERR_INVALID, "%s: T must be >= 1, got %d", who, T);
   if (P < 1 || P > 3) return fail(MOBROB_ERR_INVALID, "%s: P must lie in 1 .. 3, got %d", who, P);
@@ -5396,11 +5398,15 @@ static int spec_check(const char* who, int max_op, const mobrob_spec_t* spec, co
   for (int s = 0; s < S; ++s) {
     if (counts[s] < 0 || counts[s] > R) return fail(MOBROB_ERR_INVALID, "%s: spec: n_regions[%d] = %d outside 0 .. %d", who, s, counts[s], R);
     for (int r = 0; r < counts[s]; ++r) {
-      const float* b = spec->regions + ((size_t)s * R + r) * 4;
       const int kind = spec->kinds[(size_t)s * R + r];
       if (kind != 0 && kind != 1) return fail(MOBROB_ERR_INVALID, "%s: spec: kinds: region %d of scene %d has kind %d (0 box, 1 circle)", who, r, s, kind);
-      if (!(std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]) && b[2] >= 0.f && (kind == 1 || b[3] >= 0.f)))
-        return fail(MOBROB_ERR_INVALID, "%s: spec: regions: region %d of scene %d is not finite or has a negative extent", who, r, s);
+      for (int f = 0; f < F; ++f) {
+        const float* b = spec->regions + (((size_t)s * F + f) * R + r) * 4;
+        if (std::isfinite(b[0]) && std::isfinite(b[1]) && std::isfinite(b[2]) && std::isfinite(b[3]) && b[2] >= 0.f && (kind == 1 || b[3] >= 0.f))
+          continue;
+        if (F == 1) return fail(MOBROB_ERR_INVALID, "%s: spec: regions: region %d of scene %d is not finite or has a negative extent", who, r, s);
+        return fail(MOBROB_ERR_INVALID, "%s: spec: regions: region %d of scene %d is not finite or has a negative extent in frame %d", who, r, s, f);
+      }
     }
   }
   if (spec->scene)
@@ -5560,6 +5566,118 @@ int mobrob_ppo_spec_monitor_nested(mobrob_ppo_engine_t* e, const mobrob_spec_nes
   if (spec->scene) HIPC(hipMemcpyAsync(mine(o_scene), spec->scene, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
   HIPC(hipMemcpyAsync(mine(o_cl), clauses.data(), clauses.size() * 4, hipMemcpyHostToDevice, e->stream));
   hipLaunchKernelGGL(k_spec_monitor_nested, dim3(cdiv(n, 64)), dim3(64), spec_nested_lds_bytes(slots), e->stream, na);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(val, a.val, val_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(wit, a.wit, wit_bytes, hipMemcpyDeviceToHost, e->stream));
+  if (tail_bytes) HIPC(hipMemcpyAsync(tail, na.tail, tail_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
+}
+
+// ---- run specifications over things that move (mobrob_ppo_spec_monitor_moving): the nested call with region frames and mate predicates
+int mobrob_ppo_spec_monitor_moving(mobrob_ppo_engine_t* e, const mobrob_spec_moving_t* spec, const float* path, int32_t n, int32_t T,
+                                   int32_t P, int32_t step0, float* val, int32_t* wit, float* tail, int32_t W) {
+  const char* who = "spec_monitor_moving";
+  if (!e) return fail(MOBROB_ERR_INVALID, "%s: null engine", who);
+  if (!spec) return fail(MOBROB_ERR_INVALID, "%s: null spec", who);
+  if (!path) return fail(MOBROB_ERR_INVALID, "%s: null path", who);
+  if (!val) return fail(MOBROB_ERR_INVALID, "%s: null val", who);
+  if (!wit) return fail(MOBROB_ERR_INVALID, "%s: null wit", who);
+  // what is new in this call and sizes the table, before the table is read
+  const int F = spec->n_frames, size = spec->team_size;
+  if (size != 1 && size != 2 && size != 4 && size != 8 && size != 16)
+    return fail(MOBROB_ERR_INVALID, "%s: spec: team_size must be 1, 2, 4, 8 or 16, got %d", who, size);
+  if (F < 1) return fail(MOBROB_ERR_INVALID, "%s: spec: n_frames must be >= 1, got %d", who, F);
+  if (spec->frame_steps < 1) return fail(MOBROB_ERR_INVALID, "%s: spec: frame_steps must be >= 1, got %d", who, spec->frame_steps);
+  if (spec->loop != 0 && spec->loop != 1) return fail(MOBROB_ERR_INVALID, "%s: spec: loop must be 0 or 1, got %d", who, spec->loop);
+  if (spec->n_scenes >= 1 && spec->max_regions >= 0 && spec->max_regions <= kSpecRegionsMax) {
+    const unsigned long long table = (unsigned long long)spec->n_scenes * (unsigned long long)F * (unsigned long long)spec->max_regions * 16ull;
+    if (table > (unsigned long long)MOBROB_SPEC_FRAMES_MAX_BYTES)
+      return fail(MOBROB_ERR_INVALID, "%s: spec: region frames of %llu bytes are above the limit of %u", who, table,
+                  (unsigned)MOBROB_SPEC_FRAMES_MAX_BYTES);
+  }
+  // the flat call's checks on the flat call's fields (mobrob_spec_t is the head of mobrob_spec_moving_t, field by field), per frame
+  mobrob_spec_t head;
+  head.n_scenes = spec->n_scenes; head.max_regions = spec->max_regions;
+  head.regions = spec->regions; head.kinds = spec->kinds; head.n_regions = spec->n_regions; head.scene = spec->scene;
+  head.n_clauses = spec->n_clauses;
+  memcpy(head.op, spec->op, sizeof head.op); memcpy(head.a, spec->a, sizeof head.a); memcpy(head.b, spec->b, sizeof head.b);
+  memcpy(head.lo1, spec->lo1, sizeof head.lo1); memcpy(head.hi1, spec->hi1, sizeof head.hi1); memcpy(head.out1, spec->out1, sizeof head.out1);
+  memcpy(head.lo2, spec->lo2, sizeof head.lo2); memcpy(head.hi2, spec->hi2, sizeof head.hi2); memcpy(head.out2, spec->out2, sizeof head.out2);
+  std::vector<int32_t> counts;
+  if (const int rc = spec_check(who, MOBROB_SPEC_RECUR, &head, path, n, T, P, step0, counts, F)) return rc;
+  if (n % size != 0) return fail(MOBROB_ERR_INVALID, "%s: %d robots do not split into teams of %d", who, n, size);
+  const int S = spec->n_scenes, R = spec->max_regions, C = spec->n_clauses;
+  int slots = 0;
+  long long width = 0;
+  std::vector<int32_t> clauses((size_t)C * kSpecMovingClauseWords);
+  for (int c = 0; c < C; ++c) {
+    const int op = spec->op[c], h = spec->hold[c];
+    const bool until = op == MOBROB_SPEC_UNTIL, nested = op >= MOBROB_SPEC_STAY;
+    if (h < 0 || h > MOBROB_SPEC_HOLD_MAX)
+      return fail(MOBROB_ERR_INVALID, "%s: spec: hold[%d] = %d outside 0 .. %d", who, c, h, MOBROB_SPEC_HOLD_MAX);
+    if (!nested && h != 0) return fail(MOBROB_ERR_INVALID, "%s: spec: hold[%d] = %d on the flat op %d (must be 0)", who, c, h, op);
+    if (spec->kind1[c] < MOBROB_SPEC_PRED_REGIONS || spec->kind1[c] > MOBROB_SPEC_PRED_APART)
+      return fail(MOBROB_ERR_INVALID, "%s: spec: kind1[%d] = %d outside 0 .. 2", who, c, spec->kind1[c]);
+    if (until && (spec->kind2[c] < MOBROB_SPEC_PRED_REGIONS || spec->kind2[c] > MOBROB_SPEC_PRED_APART))
+      return fail(MOBROB_ERR_INVALID, "%s: spec: kind2[%d] = %d outside 0 .. 2", who, c, spec->kind2[c]);
+    if (!(std::isfinite(spec->rad1[c]) && spec->rad1[c] >= 0.f))
+      return fail(MOBROB_ERR_INVALID, "%s: spec: rad1[%d] is negative or not finite", who, c);
+    if (until && !(std::isfinite(spec->rad2[c]) && spec->rad2[c] >= 0.f))
+      return fail(MOBROB_ERR_INVALID, "%s: spec: rad2[%d] is negative or not finite", who, c);
+    int32_t d1, d2 = 0;
+    memcpy(&d1, &spec->rad1[c], 4);
+    if (until) memcpy(&d2, &spec->rad2[c], 4);
+    const int32_t row[kSpecMovingClauseWords] = {op, spec->a[c], spec->b[c], spec->lo1[c], spec->hi1[c], spec->out1[c] != 0,
+                                                 until ? spec->lo2[c] : 0, until ? spec->hi2[c] : 0, until ? spec->out2[c] != 0 : 0,
+                                                 h, slots, (int32_t)width, spec->kind1[c], until ? spec->kind2[c] : 0, d1, d2};
+    std::copy(row, row + kSpecMovingClauseWords, clauses.begin() + (size_t)c * kSpecMovingClauseWords);
+    if (nested) { slots += h + 1; width += h; }
+  }
+  if (slots > MOBROB_SPEC_WINDOW_SLOTS)
+    return fail(MOBROB_ERR_INVALID, "%s: spec: the nested clauses' windows take %d slots (the sum of hold + 1), above %d", who, slots,
+                MOBROB_SPEC_WINDOW_SLOTS);
+  if (W != width) return fail(MOBROB_ERR_INVALID, "%s: W = %d is not the sum of the holds, %lld", who, W, width);
+  if (W > 0 && !tail) return fail(MOBROB_ERR_INVALID, "%s: null tail with W = %d", who, W);
+  const size_t path_bytes = (size_t)(T + 1) * n * P * 4, val_bytes = (size_t)n * C * 8, wit_bytes = (size_t)n * C * 4,
+               tail_bytes = (size_t)n * W * 4, reg_bytes = (size_t)S * F * R * 16;
+  EvalCarve call;
+  const size_t o_path = call.add(path_bytes), o_val = call.add(val_bytes), o_wit = call.add(wit_bytes),
+               o_reg = call.add(std::max<size_t>(reg_bytes, 4)), o_kind = call.add(std::max<size_t>((size_t)S * R * 4, 4)),
+               o_cnt = call.add((size_t)S * 4), o_scene = call.add((size_t)n * 4), o_cl = call.add(clauses.size() * 4),
+               o_tail = call.add(std::max<size_t>(tail_bytes, 4));
+  if (const int rc = grow_plan_buf(e, e->spec_buf, e->spec_bytes, call.total)) return rc;
+  if (!e->spec_moving_lds_set) {   // up to 158.3 KB at the slot cap: above the 64 KB a kernel gets without asking
+    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_spec_monitor_moving), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)spec_moving_lds_bytes(kSpecWindowSlots)));
+    e->spec_moving_lds_set = true;
+  }
+  const auto mine = [&](size_t off) { return e->spec_buf + off; };
+  SpecMovingArgs ma{};
+  SpecNestedArgs& na = ma.n;
+  SpecArgs& a = na.f;
+  a.path = reinterpret_cast<float*>(mine(o_path));
+  a.regions = reinterpret_cast<float*>(mine(o_reg)); a.kinds = reinterpret_cast<int*>(mine(o_kind));
+  a.nreg = reinterpret_cast<int*>(mine(o_cnt)); a.scene = spec->scene ? reinterpret_cast<int*>(mine(o_scene)) : nullptr;
+  a.clauses = reinterpret_cast<int*>(mine(o_cl));
+  a.val = reinterpret_cast<float*>(mine(o_val)); a.wit = reinterpret_cast<int*>(mine(o_wit));
+  a.N = n; a.T = T; a.P = P; a.R = R; a.C = C;
+  a.r0 = step0 == 0 ? 0 : 1;
+  a.tau0 = step0;
+  na.tail = reinterpret_cast<float*>(mine(o_tail)); na.W = W;
+  ma.F = F; ma.frame_steps = spec->frame_steps; ma.loop = spec->loop; ma.size = size;
+  HIPC(hipMemcpyAsync(mine(o_path), path, path_bytes, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_val), val, val_bytes, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_wit), wit, wit_bytes, hipMemcpyHostToDevice, e->stream));
+  if (tail_bytes) HIPC(hipMemcpyAsync(mine(o_tail), tail, tail_bytes, hipMemcpyHostToDevice, e->stream));
+  if (reg_bytes) {
+    HIPC(hipMemcpyAsync(mine(o_reg), spec->regions, reg_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(mine(o_kind), spec->kinds, (size_t)S * R * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  HIPC(hipMemcpyAsync(mine(o_cnt), counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  if (spec->scene) HIPC(hipMemcpyAsync(mine(o_scene), spec->scene, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_cl), clauses.data(), clauses.size() * 4, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_spec_monitor_moving, dim3(cdiv(n, 64)), dim3(64), spec_moving_lds_bytes(slots), e->stream, ma);
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(val, a.val, val_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(wit, a.wit, wit_bytes, hipMemcpyDeviceToHost, e->stream));

@@ -2427,8 +2427,9 @@ def grid_assign(spec, walls, hazards, start, goal, teams, objective="sum", step0
 
 
 # ---- run specifications: reach / avoid / until robustness per robot, from the positions of a run (the device: csrc/kernels_spec.h,
-# k_spec_monitor, and csrc/kernels_spec_nested.h, k_spec_monitor_nested, for a specification with a nested clause; both held to this
-# bit for bit).  Stated here once; waypoints.monitor, the host loop and PPOEngine.spec_monitor apply it.
+# k_spec_monitor, csrc/kernels_spec_nested.h, k_spec_monitor_nested, for a specification with a nested clause, and
+# csrc/kernels_spec_moving.h, k_spec_monitor_moving, for one with moving regions or a mate predicate; all held to this bit for bit).
+# Stated here once; waypoints.monitor, the host loop and PPOEngine.spec_monitor apply it.
 SPEC_REGIONS_MAX = 64           # regions per scene
 SPEC_CLAUSES_MAX = 16           # clauses of a specification
 SPEC_OPEN = 2 ** 31 - 1         # the right end of an open window
@@ -2438,6 +2439,8 @@ SPEC_HOLD_MAX = 255             # the longest inner window [t, t + h] of a neste
 SPEC_WINDOW_SLOTS = 512         # the sum of (h + 1) over the nested clauses of a specification (the device's window block)
 SPEC_BOX, SPEC_CIRCLE = 0, 1    # region kinds
 SPEC_RESULT_KEYS = ("spec_rho", "spec_witness", "robustness", "weakest", "satisfied")
+SPEC_FRAMES_MAX_BYTES = 64 << 20   # cap on a MovingRegions table (S * F * R * 16 bytes); the engine refuses a larger one too
+SPEC_PRED_REGIONS, SPEC_PRED_TOGETHER, SPEC_PRED_APART = 0, 1, 2   # what a predicate reads: a region range, or the team-mates
 
 
 class Regions:
@@ -2517,6 +2520,98 @@ class Regions:
         return Regions(rows, np.full(t.shape[:2], SPEC_CIRCLE, np.int32), hazards.counts, hazards.scene)
 
 
+class MovingRegions:
+    """Regions that move: `Regions` plus a time axis of F piecewise-constant FRAMES, as MovingHazards is to Hazards.  `rows`
+    [F, R, 4] (one scene) or [S, F, R, 4], stored as float32 [S, F, R, 4]; `kinds` [R] or [S, R] -- a region keeps its kind over
+    the frames --; `frame_steps` >= 1 steps per frame; `loop`: wrap around after the last frame instead of holding it; `counts`
+    and `scene` as for `Regions`.  R <= SPEC_REGIONS_MAX, F >= 1, and the table holds at most SPEC_FRAMES_MAX_BYTES.  Every check
+    of `Regions` applies per frame.  Checked on construction (ValueError).
+
+    Time: the sample at tau reads the frame f(max(tau - 1, 0)) with f MovingHazards.frame_index's rule.  A sample at tau >= 1 is
+    the position after the step with 0-based global number tau - 1, whose hazard check uses f(tau - 1): a clause over hazards
+    sees the frame the run's own hazard check saw.  Nothing is interpolated."""
+
+    def __init__(self, rows, kinds, frame_steps=1, loop=False, counts=None, scene=None):
+        rw = np.asarray(rows, np.float64)
+        if rw.ndim == 3:
+            rw = rw[None]
+        if rw.ndim != 4 or rw.shape[3] != 4:
+            raise ValueError(f"moving region rows must be [F, R, 4] or [S, F, R, 4], got shape {np.shape(rows)}")
+        S, F, R = rw.shape[:3]
+        if S < 1:
+            raise ValueError("regions need at least one scene")
+        if F < 1:
+            raise ValueError("moving regions need at least one frame")
+        if R > SPEC_REGIONS_MAX:
+            raise ValueError(f"at most {SPEC_REGIONS_MAX} regions per scene, got {R}")
+        if S * F * R * 16 > SPEC_FRAMES_MAX_BYTES:
+            raise ValueError(f"region frames of {S} x {F} x {R} x 16 bytes exceed the cap of {SPEC_FRAMES_MAX_BYTES} bytes "
+                             f"({SPEC_FRAMES_MAX_BYTES >> 20} MiB)")
+        if isinstance(frame_steps, bool) or not isinstance(frame_steps, (int, np.integer)) or frame_steps < 1:
+            raise ValueError(f"frame_steps must be an integer >= 1, got {frame_steps!r}")
+        if frame_steps > 2 ** 31 - 1:
+            raise ValueError("frame_steps must fit an int32")
+        first = Regions(rw[:, 0], kinds, counts, scene)   # kinds, counts, scene and frame 0: Regions' checks
+        kd = first.kinds
+        if not np.all(np.isfinite(rw)) or np.any(np.abs(rw) > np.finfo(np.float32).max):
+            raise ValueError("region rows must be finite")
+        if np.any(rw[..., 2] < 0) or np.any((kd[:, None, :] == SPEC_BOX) & (rw[..., 3] < 0)):
+            raise ValueError("box half extents and circle radii must be >= 0")
+        self.table = np.ascontiguousarray(rw, np.float32)     # [S, F, R, 4]
+        self.kinds, self.counts, self.scene = kd, first.counts, first.scene
+        self.frame_steps, self.loop = int(frame_steps), bool(loop)
+
+    @property
+    def n_scenes(self):
+        return self.table.shape[0]
+
+    @property
+    def n_frames(self):
+        return self.table.shape[1]
+
+    @property
+    def max_regions(self):
+        return self.table.shape[2]
+
+    check_robots = Regions.check_robots
+    frame_index = MovingHazards.frame_index
+
+    def frame_at(self, tau):
+        """The frame in force at the sample tau: frame_index(max(tau - 1, 0))."""
+        return self.frame_index(max(int(tau) - 1, 0))
+
+    @staticmethod
+    def from_hazards(moving_hazards):
+        """Every hazard as a circle region of its per-frame radius; scenes, counts, frame_steps and loop are the hazards' own."""
+        if not isinstance(moving_hazards, MovingHazards):
+            raise TypeError(f"MovingRegions.from_hazards takes a MovingHazards, not {type(moving_hazards).__name__}")
+        t = moving_hazards.table
+        rows = np.concatenate([t, np.zeros(t.shape[:3] + (1,), np.float32)], axis=-1)
+        return MovingRegions(rows, np.full((t.shape[0], t.shape[2]), SPEC_CIRCLE, np.int32), moving_hazards.frame_steps,
+                             moving_hazards.loop, moving_hazards.counts, moving_hazards.scene)
+
+    @staticmethod
+    def join(static_regions, moving):
+        """The static regions first (indices 0 .. Rs - 1, equal in every frame), then the moving ones (Rs .. Rs + Rm - 1); frames,
+        frame_steps and loop are `moving`'s.  The scenes and scene indices of both must agree, and every static count must equal
+        Rs: `counts` names a prefix of a scene's regions, and a static scene that uses fewer than Rs would put unused rows before
+        the moving ones."""
+        if not isinstance(static_regions, Regions) or not isinstance(moving, MovingRegions):
+            raise TypeError("MovingRegions.join takes (a Regions, a MovingRegions)")
+        Rs, F = static_regions.max_regions, moving.n_frames
+        if static_regions.n_scenes != moving.n_scenes:
+            raise ValueError(f"join: the static regions have {static_regions.n_scenes} scenes, the moving ones {moving.n_scenes}")
+        if (static_regions.scene is None) != (moving.scene is None) or (
+                moving.scene is not None and not np.array_equal(static_regions.scene, moving.scene)):
+            raise ValueError("join: the static and the moving regions must have the same scene index per robot")
+        if np.any(static_regions.counts != Rs):
+            raise ValueError(f"join: static counts must all equal the {Rs} static regions (counts name a prefix of a scene's regions), "
+                             f"got {static_regions.counts.tolist()}")
+        rows = np.concatenate([np.broadcast_to(static_regions.table[:, None], (moving.n_scenes, F, Rs, 4)), moving.table], axis=2)
+        return MovingRegions(rows, np.concatenate([static_regions.kinds, moving.kinds], axis=1), moving.frame_steps, moving.loop,
+                             moving.counts + Rs, moving.scene)
+
+
 def region_margins(xy, rows, kinds):
     """The INSIDE margin of every region at every position: xy [n, 2], rows [n, R, 4], kinds [n, R] -> [n, R] float32.  float32,
     every operation rounded on its own, no fma.  Box: m = -sdf with sdf exactly as wall_check states it (the device: wall_sdf of
@@ -2555,10 +2650,43 @@ def _predicate(lo, hi, out):
     return (lo, hi, bool(out))
 
 
+def together(d):
+    """The mate predicate "every team-mate is within d": the minimum over the mates of d - distance (+inf in a team of one)."""
+    return _mate_predicate(SPEC_PRED_TOGETHER, d)
+
+
+def apart(d):
+    """The mate predicate "every team-mate is further than d": minus the maximum over the mates of d - distance (+inf in a team
+    of one)."""
+    return _mate_predicate(SPEC_PRED_APART, d)
+
+
+def _mate_predicate(kind, d):
+    d = float(d)
+    if not np.isfinite(d) or d < 0 or d > float(np.finfo(np.float32).max):
+        raise ValueError(f"a mate predicate's distance must be finite and >= 0, got {d}")
+    return ("mates", kind, float(np.float32(d)))   # the float32 value every path uses
+
+
+def _is_region_predicate(p):
+    return isinstance(p, tuple) and len(p) == 3 and p[0] != "mates"
+
+
+def _is_mate_predicate(p):
+    return isinstance(p, tuple) and len(p) == 3 and p[0] == "mates" and p[1] in (SPEC_PRED_TOGETHER, SPEC_PRED_APART)
+
+
+def spec_predicate_words(pred):
+    """A predicate as the C ABI takes it: (lo, hi, out, kind, radius); a mate predicate has the empty range [0, 0)."""
+    if _is_mate_predicate(pred):
+        return 0, 0, 0, pred[1], pred[2]
+    return pred[0], pred[1], int(pred[2]), SPEC_PRED_REGIONS, 0.0
+
+
 class Spec:
-    """A specification: the conjunction of at most SPEC_CLAUSES_MAX clauses over `regions` (a Regions).  A clause is built by
-    Spec.always(pred, a, b), Spec.eventually(pred, a, b) or Spec.until(pred1, pred2, a, b) with predicates from inside() /
-    outside() and a window [a, b] in sample time tau -- the number of global steps completed, tau = 0 the start of the run --,
+    """A specification: the conjunction of at most SPEC_CLAUSES_MAX clauses over `regions` (a Regions or a MovingRegions).  A
+    clause is built by Spec.always(pred, a, b), Spec.eventually(pred, a, b) or Spec.until(pred1, pred2, a, b) with predicates from
+    inside() / outside() / together() / apart() and a window [a, b] in sample time tau -- the number of global steps completed, tau = 0 the start of the run --,
     0 <= a <= b, b=None open (SPEC_OPEN).  See spec_fold for the meaning.
 
     The two nested clauses fold a sliding-window extremum of their predicate:
@@ -2571,12 +2699,23 @@ class Spec:
     no operator of its own: on a finite trace of T steps it is the last sample, and stay(pred, hold, a=T - hold, b=T - hold) asks
     for the last hold + 1 samples.
 
-    Not built: deeper nesting (an until inside a window, a window inside a window), disjunction of clauses, predicates on velocity
-    or on team-mates, moving regions."""
+    Things that move.  `regions` may be a MovingRegions: the sample at tau reads the frame MovingRegions.frame_at(tau), the one
+    the run's own hazard check saw.  The mate predicates together(d) / apart(d) speak about the robot's team: `team_size` (one of
+    TEAM_SIZES) consecutive robots, robot i with the mates j = (i // size) * size + m, m ascending, j != i, each at the position
+    this sample's record holds for it (an idle mate stands where its row says).  g_j = d - dist_ij with the circle margin's
+    arithmetic, the mate as the centre; together(d) is the minimum of the g_j by explicit <, from +inf; apart(d) minus their
+    maximum by explicit >, from -inf; a team of one reads +inf for both.  They stand wherever inside / outside do, in all five
+    clause kinds.  `dynamic` is True for a specification with moving regions or a mate predicate (the device folds it with
+    k_spec_monitor_moving); one without either is the object it was and takes the call it took.
 
-    def __init__(self, regions, clauses):
-        if not isinstance(regions, Regions):
+    Not built: deeper nesting (an until inside a window, a window inside a window), disjunction of clauses, predicates on
+    velocity, interpolation between frames."""
+
+    def __init__(self, regions, clauses, team_size=1):
+        if not isinstance(regions, (Regions, MovingRegions)):
             raise TypeError(f"regions must be a mobrob_amd.envs.goal_rules.Regions, not {type(regions).__name__}")
+        if isinstance(team_size, bool) or not isinstance(team_size, (int, np.integer)) or int(team_size) not in TEAM_SIZES:
+            raise ValueError(f"a specification's team_size must be one of {TEAM_SIZES}, got {team_size!r}")
         clauses = list(clauses)
         if not 1 <= len(clauses) <= SPEC_CLAUSES_MAX:
             raise ValueError(f"a specification has 1 .. {SPEC_CLAUSES_MAX} clauses, got {len(clauses)}")
@@ -2587,11 +2726,16 @@ class Spec:
             if not (flat or nested):
                 raise TypeError(f"clause {c} is not one of Spec.always / Spec.eventually / Spec.until / Spec.stay / Spec.recur")
             for p in cl[3:5]:
-                if p[1] > R:
+                if not (_is_region_predicate(p) or _is_mate_predicate(p)):
+                    raise TypeError(f"clause {c}: a predicate comes from inside() / outside() / together() / apart()")
+                if _is_region_predicate(p) and p[1] > R:
                     raise ValueError(f"clause {c}: region range [{p[0]}, {p[1]}) outside 0 .. {R}")
             if nested:
                 _hold(cl[5], f"clause {c}: hold")
-        self.regions, self.clauses = regions, tuple(clauses)
+        self.regions, self.clauses, self.team_size = regions, tuple(clauses), int(team_size)
+        self.moving = isinstance(regions, MovingRegions)
+        self.mates = any(_is_mate_predicate(p) for cl in self.clauses for p in cl[3:5])
+        self.dynamic = self.moving or self.mates
         # per clause: the inner window's h (0 for a flat clause) and where its h values start in SpecState.tail
         self.holds = tuple(cl[5] if len(cl) == 6 else 0 for cl in self.clauses)
         self.nested = any(len(cl) == 6 for cl in self.clauses)
@@ -2606,6 +2750,12 @@ class Spec:
     def n_clauses(self):
         return len(self.clauses)
 
+    def check_robots(self, n):
+        """The regions' check of the robot count, and the teams': n must split into teams of team_size."""
+        self.regions.check_robots(n)
+        if int(n) % self.team_size != 0:
+            raise ValueError(f"{int(n)} robots do not split into the specification's teams of {self.team_size}")
+
     @staticmethod
     def _clause(op, pred1, pred2, a, b):
         a = int(a)
@@ -2614,7 +2764,7 @@ class Spec:
             raise ValueError(f"a window must obey 0 <= a <= b, got [{a}, {b}]")
         for p in (pred1, pred2):
             if not (isinstance(p, tuple) and len(p) == 3):
-                raise TypeError("a predicate comes from inside() or outside()")
+                raise TypeError("a predicate comes from inside() or outside(), together() or apart()")
         return (op, a, b, pred1, pred2)
 
     @staticmethod
@@ -2709,6 +2859,27 @@ def spec_predicate(margins, counts, pred):
     return -u if out else u
 
 
+def spec_mate_predicate(xy, team_size, pred):
+    """The value of a mate predicate at one sample: xy [n, 2] float32, n a multiple of team_size.  Per robot i and mate j, m
+    ascending: g = d - sqrt(dx * dx + dy * dy), dx = px_i - px_j, every operation float32 and rounded on its own (the circle
+    margin of region_margins with the mate as the centre).  together: the minimum by explicit < from +inf; apart: minus the
+    maximum by explicit > from -inf."""
+    f32 = np.float32
+    _, kind, d = pred
+    xy = np.asarray(xy, f32)
+    n, size = xy.shape[0], int(team_size)
+    mates = xy.reshape(n // size, size, 2)
+    me = np.arange(n) % size
+    u = np.full(n, np.inf if kind == SPEC_PRED_TOGETHER else -np.inf, f32)
+    for m in range(size):
+        other = np.repeat(mates[:, m], size, axis=0)                    # [n, 2]: mate m of every robot's team
+        dx, dy = xy[:, 0] - other[:, 0], xy[:, 1] - other[:, 1]
+        g = (f32(d) - np.sqrt(dx * dx + dy * dy)).astype(f32)
+        take = (me != m) & ((g < u) if kind == SPEC_PRED_TOGETHER else (g > u))
+        u = np.where(take, g, u)
+    return u if kind == SPEC_PRED_TOGETHER else -u
+
+
 def spec_fold(state, path, spec, step0=0):
     """The state after the samples of one call: `path` [T+1][n][P] as follow_waypoints returns it with path_stride=1 (record 0 the
     position at entry, record r the position after r steps of the call).  With step0 == 0 the records 0 .. T are the samples tau =
@@ -2734,6 +2905,11 @@ def spec_fold(state, path, spec, step0=0):
     The inner extremum is taken under the total order on float32 bits (spec_key: -0.0 < +0.0), the outer comparison is the float
     comparison of the flat clauses; guard is not used and stays +inf.  A window the run ends before completing is never folded;
     the tail then carries its values into the next call.  After every sample the tail is the last h values, oldest first.
+
+    Things that move.  With a MovingRegions the margins of the sample at tau are those of the frame regions.frame_at(tau) =
+    f(max(tau - 1, 0)): it depends on the global tau only, so a split run ends on the same bits, and F == 1 is the static Regions
+    bit for bit.  A mate predicate's value is spec_mate_predicate of this sample's record, idle mates included; a robot count
+    that spec.team_size does not divide is refused.
     Returns a new SpecState."""
     path = np.asarray(path)
     if path.ndim != 3 or path.shape[0] < 2 or not 1 <= path.shape[2] <= 3:
@@ -2746,20 +2922,24 @@ def spec_fold(state, path, spec, step0=0):
     if step0 < 0 or step0 + T > SPEC_OPEN:
         raise ValueError("step0 must be >= 0 and step0 + T fit an int32")
     reg = spec.regions
-    reg.check_robots(n)
+    spec.check_robots(n)
     spec_check_state(state, n, spec)
     sc = np.zeros(n, np.int64) if reg.scene is None else reg.scene.astype(np.int64)
-    rows, kinds, counts = reg.table[sc], reg.kinds[sc], reg.counts[sc]
+    kinds, counts = reg.kinds[sc], reg.counts[sc]
+    rows = None if spec.moving else reg.table[sc]
     val, wit, tail = state.val.copy(), state.wit.copy(), state.tail.copy()
     xy = np.zeros((n, 2), np.float32)
     rows_n = np.arange(n)
     for r in range(0 if step0 == 0 else 1, T + 1):
         tau = step0 + r
         xy[:, :min(P, 2)] = path[r, :, :2]
-        m = region_margins(xy, rows, kinds)
+        m = region_margins(xy, reg.table[sc, reg.frame_at(tau)] if spec.moving else rows, kinds)
+
+        def value(pred):
+            return spec_mate_predicate(xy, spec.team_size, pred) if _is_mate_predicate(pred) else spec_predicate(m, counts, pred)
         for c, (op, a, b, p1, p2) in enumerate(cl[:5] for cl in spec.clauses):
             rho, guard = val[:, c, 0], val[:, c, 1]
-            v1 = spec_predicate(m, counts, p1)
+            v1 = value(p1)
             window = a <= tau <= b
             if op in (SPEC_STAY, SPEC_RECUR):
                 h, o = spec.holds[c], spec.tail_offsets[c]
@@ -2776,7 +2956,7 @@ def spec_fold(state, path, spec, step0=0):
             if op == SPEC_UNTIL:
                 guard = np.where(v1 < guard, v1, guard)
                 val[:, c, 1] = guard
-                v2 = spec_predicate(m, counts, p2)
+                v2 = value(p2)
                 w = np.where(v2 < guard, v2, guard)
                 take = (w > rho) if window else np.zeros(n, bool)
                 new = w

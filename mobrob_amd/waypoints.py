@@ -100,7 +100,10 @@ dict gains
   robustness [n] the smallest clause value;  weakest [n] that clause;  satisfied [n] robustness > 0 (a margin of 0 is not)
 and `state.spec` (a goal_rules.SpecState) carries the fold, so a split run ends on the same bits.  On the device the fold is one
 kernel over the call's path (PPOEngine.spec_monitor), on the host goal_rules.spec_fold; `monitor(path, spec, ...)` below does either
-for a recorded path.  `replan` leaves the monitor alone.  Every other key is what the call without `spec=` returns.
+for a recorded path.  `replan` leaves the monitor alone.  Every other key is what the call without `spec=` returns.  The regions may
+move (goal_rules.MovingRegions, from MovingHazards by MovingRegions.from_hazards: the sample at tau reads the frame the run's own
+hazard check saw) and a predicate may speak about the team-mates (together(d) / apart(d) with Spec(..., team_size=)): the same
+funnel, the same keys.  With `teams=` a spec.team_size above 1 must be teams.size.
 
 Runs.  A planner works in rounds: track for a horizon, look where the robots are, replan the stuck ones, continue.  A RUN is a
 sequence of calls over the same robots with the same seed; every call returns `state` (a FollowState: what the robots carry
@@ -636,13 +639,15 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
     if spec is None and getattr(state, "spec", None) is not None:
         raise ValueError("a run is monitored in every call or in none: state.spec is set, spec= is missing")
     carried = None if spec is None else _spec_check_call(spec, path_stride, state)
+    if spec is not None and teams is not None and spec.team_size > 1 and teams.size != spec.team_size:
+        raise ValueError(f"teams.size = {teams.size} differs from spec.team_size = {spec.team_size}: a mate predicate speaks about the run's teams")
     if isinstance(env, DeviceGoalVecEnv):
         if state is None:
             state = FollowState(start, waypoints, n_waypoints, hazards is not None, env.pos_dim, teams if teams is not None else False, schedule,
                                 walls if walls is not None else False)
         _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
         if spec is not None:
-            spec.regions.check_robots(state.n_robots)
+            spec.check_robots(state.n_robots)
         out = env.follow(getattr(model, "engine", model), max_steps=max_steps, deterministic=deterministic, seed=seed,
                          path_stride=path_stride, hazards=hazards, resume=state, leg_steps=leg_steps, teams=teams,
                          schedule=schedule, walls=walls)
@@ -669,7 +674,7 @@ def follow_waypoints(model, env, start=None, waypoints=None, n_waypoints=None, *
         raise ValueError(f"state has {state.waypoints.shape[2]} position dimensions, the environment {pos_dim}")
     leg_steps = _check_run(state, leg_steps, max_steps, hazards, teams, schedule, walls)
     if spec is not None:
-        spec.regions.check_robots(state.n_robots)
+        spec.check_robots(state.n_robots)
     out = _host_follow(model, make_env, state, max_steps, deterministic, seed, path_stride, hazards, leg_steps, teams, schedule,
                        walls)
     return out if spec is None else _spec_fold_call(out, spec, carried, state.step0, None)   # two paths, one meaning: spec_fold
