@@ -64,6 +64,11 @@ size = --team-size) or `[n][P]` (one per robot).  It excludes --goal and --waypo
 `--assign sum` or `--assign makespan` (it needs --team-size) first assigns the places inside every team -- the pairing of least
 total path cost, or the one whose longest path is shortest -- and a line reports the teams whose pairing changed and the total
 before and after (mobrob_amd.planning.GridPlanner(assign=)).  A run is never reassigned: replanning keeps the assigned goals.
+
+`--check-spec --plan-spec [--pace N]` lets the specification that --check-spec monitors drive the plan: its stations (here the reach
+circle around --goal; with --spec-hold H a stay of H steps, which needs --pace, the steps a robot is given for one orthogonal move)
+are planned with GridPlanner.plan_spec in place of the plan to --goal, the walls once more as keep-out regions; the run follows the
+plan's schedule, the monitor then judges it.  It excludes --hazard-frames, --team-size, --plan-smooth and --plan-clearance.
 """
 import argparse
 import os
@@ -94,11 +99,15 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
            plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False,
-           tile256_wide=False, team_solid=False, check_spec=False, spec_hold=0):
+           tile256_wide=False, team_solid=False, check_spec=False, spec_hold=0, plan_spec=False, pace=None):
     if check_spec and goal is None:
         raise ValueError("--check-spec needs --goal (the specification is: eventually inside the reach radius around the goal)")
     if int(spec_hold) != 0 and not check_spec:
         raise ValueError("--spec-hold needs --check-spec")
+    if plan_spec and not check_spec:
+        raise ValueError("--plan-spec needs --check-spec (the specification whose stations are planned)")
+    if pace is not None and not plan_spec:
+        raise ValueError("--pace needs --plan-spec")
     if team_solid and team_size is None:
         raise ValueError("--team-solid needs --team-size")
     if solid and walls is None and not arena:
@@ -147,6 +156,22 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             raise ValueError(f"--goals must hold [team size][{p}] or [{int(robots)}][{p}] positions of robots that move in x and y, got shape {goals.shape}")
         goals = np.tile(goals, (int(robots) // goals.shape[0], 1))
         goal = goals[0]                                    # (from here on: "the waypoints are planned")
+    def monitored_spec():   # eventually inside the reach circle around the goal (--spec-hold H: for H steps in a row); with walls: always outside every one;
+        # with moving hazards: outside every one from the first step on; with teams: always further than the separation from every mate
+        from mobrob_amd.envs.goal_rules import REACH_RADIUS, Regions, Spec, inside, outside
+        boxes = np.zeros((0, 4), np.float32) if wl is None else wl.rows(0)
+        regions = Regions(np.concatenate([[[goal[0], goal[1], REACH_RADIUS, 0.0]], boxes]), [1] + [0] * len(boxes))
+        reach = Spec.eventually(inside(0)) if int(spec_hold) == 0 else Spec.stay(inside(0), int(spec_hold))   # (ValueError above SPEC_HOLD_MAX)
+        clauses = [reach] + ([Spec.always(outside(1, 1 + len(boxes)))] if len(boxes) else [])
+        if isinstance(hz, MovingHazards):   # --hazard-frames: never inside a moving hazard, from the first step on
+            from mobrob_amd.envs.goal_rules import MovingRegions
+            first = regions.max_regions
+            regions = MovingRegions.join(regions, MovingRegions.from_hazards(hz))
+            clauses.append(Spec.always(outside(first, regions.max_regions), a=1))
+        if teams is not None:               # --team-size / --separation: always further than the separation from every mate
+            from mobrob_amd.envs.goal_rules import apart
+            clauses.append(Spec.always(apart(teams.separation)))
+        return dict(spec=Spec(regions, clauses, team_size=1 if teams is None else teams.size), path_stride=1)
     if goal is not None:
         from mobrob_amd.planning import GridPlanner
         goal = np.asarray(goal, np.float64).reshape(-1)
@@ -169,7 +194,13 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             from mobrob_amd.envs.goal_rules import grid_plan_clearance_min
             plain = planner.plan(start, goals, grow=True, clearance=None, want_occupancy=True, want_fields=True)
             plain_min = grid_plan_clearance_min(planner.spec, plain, start, goals, planner.clearance[0])
-        plan = planner.plan(start, goals, grow=True)
+        if plan_spec:                                      # the specification's stations in --goal's place, in the order the plan chooses
+            plan = planner.plan_spec(start, monitored_spec()["spec"], pace=pace)
+            plan.update(smoothed=False, moves=None)
+            print(f"planned from the specification: tour cost {float(np.mean(plan['cost'][plan['status'] == 0])) if np.any(plan['status'] == 0) else float('nan')} "
+                  f"ticks, {int(np.sum(plan['release'] != 0))} holds, stations covered: {bool(np.all(plan['covered']))}")
+        else:
+            plan = planner.plan(start, goals, grow=True)
         if plan_clearance is not None:
             ok, pk = plan["status"] == 0, plain["status"] == 0
             if np.any(ok) and np.any(pk):
@@ -181,7 +212,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             print(f"assigned ({assign}): {int(plan['assign_changed'].sum())} of {len(plan['assign_changed'])} teams changed, total path cost "
                   f"{int(plan['assign_identity_total'].sum())} -> {int(plan['assign_total'].sum())}")
         waypoints, n_waypoints, plan_schedule = plan["waypoints"], plan["n_waypoints"], plan.get("schedule")
-        replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 else None
+        replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 and not plan_spec else None
         print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
         if teams is not None:                              # beside the run's measured team conflict steps, further down
             print(f"planned team clearance: {int(plan['team_clearance'].min())} cells at the least (reserve {planner.reserve}), "
@@ -195,23 +226,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
     schedule = make_schedule(release, stagger, int(robots), np.shape(waypoints)[-2], team_size)
     if goal is not None and plan_schedule is not None:
         schedule = plan_schedule
-    monitored = {}
-    if check_spec:   # eventually inside the reach circle around the goal (--spec-hold H: for H steps in a row); with walls: always outside every one;
-        # with moving hazards: outside every one from the first step on; with teams: always further than the separation from every mate
-        from mobrob_amd.envs.goal_rules import REACH_RADIUS, Regions, Spec, inside, outside
-        boxes = np.zeros((0, 4), np.float32) if wl is None else wl.rows(0)
-        regions = Regions(np.concatenate([[[goal[0], goal[1], REACH_RADIUS, 0.0]], boxes]), [1] + [0] * len(boxes))
-        reach = Spec.eventually(inside(0)) if int(spec_hold) == 0 else Spec.stay(inside(0), int(spec_hold))   # (ValueError above SPEC_HOLD_MAX)
-        clauses = [reach] + ([Spec.always(outside(1, 1 + len(boxes)))] if len(boxes) else [])
-        if isinstance(hz, MovingHazards):   # --hazard-frames: never inside a moving hazard, from the first step on
-            from mobrob_amd.envs.goal_rules import MovingRegions
-            first = regions.max_regions
-            regions = MovingRegions.join(regions, MovingRegions.from_hazards(hz))
-            clauses.append(Spec.always(outside(first, regions.max_regions), a=1))
-        if teams is not None:               # --team-size / --separation: always further than the separation from every mate
-            from mobrob_amd.envs.goal_rules import apart
-            clauses.append(Spec.always(apart(teams.separation)))
-        monitored = dict(spec=Spec(regions, clauses, team_size=1 if teams is None else teams.size), path_stride=1)
+    monitored = monitored_spec() if check_spec else {}
     r = follow_waypoints(policy, env, start, waypoints, n_waypoints, max_steps=calls[0], deterministic=True, seed=seed, hazards=hz,
                          leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl, **monitored)
     for steps in calls[1:]:                                # the run, continued call after call
@@ -343,6 +358,11 @@ def build_parser():
     ap.add_argument("--spec-hold", type=int, default=0,
                     help="with --check-spec: 'inside the reach radius around the goal for H consecutive steps' (0 .. 255) in place of "
                          "'eventually inside'; 0: eventually inside")
+    ap.add_argument("--plan-spec", action="store_true", default=False,
+                    help="with --check-spec: plan the specification's stations (here: the reach circle around --goal, the walls as keep-out "
+                         "regions) with GridPlanner.plan_spec instead of planning to --goal, follow with the plan's schedule, then monitor")
+    ap.add_argument("--pace", type=int, default=None,
+                    help="with --plan-spec: the steps a robot is given for one orthogonal move (required with --spec-hold)")
     ap.add_argument("--tile256", action="store_true", default=False,
                     help="a 2x256 tanh policy: run calls without hazards, teams or walls as one launch (PPOEngine.set_eval_tile256)")
     ap.add_argument("--tile256-wide", action="store_true", default=False,
@@ -363,6 +383,10 @@ if __name__ == "__main__":
         ap.error("--check-spec needs --goal")
     if args.spec_hold != 0 and not args.check_spec:
         ap.error("--spec-hold needs --check-spec")
+    if args.plan_spec and not args.check_spec:
+        ap.error("--plan-spec needs --check-spec")
+    if args.pace is not None and not args.plan_spec:
+        ap.error("--pace needs --plan-spec")
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
     except ValueError as ex:
@@ -379,4 +403,4 @@ if __name__ == "__main__":
            plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
            plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid,
            tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide, team_solid=args.team_solid,
-           check_spec=args.check_spec, spec_hold=args.spec_hold)
+           check_spec=args.check_spec, spec_hold=args.spec_hold, plan_spec=args.plan_spec, pace=args.pace)

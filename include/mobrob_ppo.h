@@ -1347,6 +1347,58 @@ int mobrob_ppo_spec_monitor_moving(mobrob_ppo_engine_t* e, const mobrob_spec_mov
                                    int32_t n, int32_t T, int32_t P, int32_t step0, float* val /* [n][n_clauses][2] */,
                                    int32_t* wit /* [n][n_clauses] */, float* tail /* [n][W] or NULL */, int32_t W);
 
+/* ---- a plan from a specification: the order of the stations and the stitched waypoints ----------------------------------------------
+ * The planner and the specifications meet here: the avoid clauses of a specification become obstacles, its reach clauses stations, and
+ * per robot the device chooses the order of the stations and stitches the waypoints, for all robots in one call.  The rule is stated once
+ * in mobrob_amd/envs/goal_rules.py (spec_plan_parse, spec_plan_occupancy, spec_plan_stations, spec_plan_tour, spec_plan) and reproduced bit
+ * for bit.  The caller has sorted the clauses: here a station is a range of regions [lo, hi) read as their union, an avoid clause likewise.
+ *   spec      mobrob_ppo_plan_grid's, with n_scenes the REGIONS' scenes (which the walls' and hazards' must equal where those exist),
+ *             n_fields the distinct (scene, goal cell) pairs of `goal` (0 without a goal) and reuse_id 0.
+ *   regions   the region table as mobrob_ppo_spec_monitor takes it: n_scenes, max_regions, regions, kinds, n_regions, scene are read, the
+ *             clauses are not.
+ *   map       mobrob_ppo_plan_grid's occupancy (zeros without walls and hazards), OR-ed per scene with the avoid regions: a cell is
+ *             blocked when a region r of an avoid range, r below the scene's count, has an inside margin >= -inflate at the cell's centre.
+ *   anchors   per scene and station, over the unblocked cells, the cell of the largest inside margin m of the station's range (the total
+ *             order on float bits, the lowest cell on a tie): station_margin_out [S][M] is that m (-inf without an unblocked cell) and
+ *             station_cell_out [S][M] the cell where m > 0, else -1 -- every robot of such a scene has status 1.
+ *   costs     one mobrob_ppo_plan_grid field per (scene, anchor) and per goal field, all in ONE launch; matrix_out [S][M][M]: the field
+ *             of station j at the anchor of station i, -1 none.
+ *   order     in ticks (5 an orthogonal move, 7 a diagonal): open_c, close_c, dwell_c [M] are the stations' windows and dwells in ticks.
+ *             dep(j, arr) = max(arr, open_c[j]) + dwell_c[j], feasible iff max(arr, open_c[j]) <= close_c[j]; Held-Karp over the subsets
+ *             of stations, every minimum that of the pair (value, predecessor), the end station minimising (ticks + the goal leg, j).
+ *   outputs   mobrob_ppo_plan_grid's waypoints, n_waypoints, count, status (0 planned, 1 no feasible tour, 2 truncated to the first K,
+ *             3 a loop hit its bound) and cost (the ticks at the end, waits included; -1); tour_order_out [n][M]: the station at each
+ *             position; tour_eta_out [n][M]: ticks on arrival, before the wait for the opening; station_waypoint_out [n][M]: the index
+ *             in the full path of each position's anchor waypoint; release_out [n][K]: at the slot of the waypoint after a station whose
+ *             departure exceeds its arrival, min(ceil(departure * pace / 5), INT32_MAX), else 0 (a mobrob_follow_schedule_t's release);
+ *             the -1 of a robot without a tour fills its tour_order, tour_eta and station_waypoint.  z of every waypoint: the goal's,
+ *             else the start's.  occupancy_out [S][G][G] and sweeps_out [S * M + n_fields] or NULL.
+ *   kernels   k_plan_occupancy and k_plan_field as they are; csrc/kernels_plan_spec.h: k_plan_region_occupancy (a thread per scene and
+ *             cell), k_plan_station (a workgroup per scene and station, which writes the anchor into the field list), k_plan_tour_matrix,
+ *             k_plan_tour (a wave per robot, the table of 256 x 8 values in LDS), k_plan_tour_path (a thread per robot).  The call works
+ *             in a buffer of its own, outside the arena; mobrob_ppo_plan_grid's resident fields stay valid across it.
+ * MOBROB_ERR_INVALID before any launch or copy, outputs untouched, for: a NULL argument; a goal without its field lists; reuse_id != 0;
+ * n_fields != 0 without a goal; n_stations outside 1 .. MOBROB_PLAN_TOUR_STATIONS_MAX; n_avoid outside 0 .. MOBROB_SPEC_CLAUSES_MAX; pace
+ * outside 1 .. 2^20; everything mobrob_ppo_plan_grid refuses of the spec, the scenes, the robots and the goal fields, and
+ * mobrob_ppo_spec_monitor of the region table; n_scenes not the regions'; regions that disagree with the walls / hazards on a robot's
+ * scene; a station's or an avoid clause's range outside 0 <= lo <= hi <= max_regions; ticks negative or above
+ * MOBROB_PLAN_TOUR_TICKS_MAX; open_c > close_c; fields above MOBROB_PLAN_TIME_MAX_BYTES in total; a field too large for the device's LDS. */
+#define MOBROB_PLAN_TOUR_STATIONS_MAX 8
+#define MOBROB_PLAN_TOUR_TICKS_MAX (1 << 24)
+int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                         const mobrob_hazards_t* hazards /* or NULL */, const mobrob_spec_t* regions, int32_t n_stations,
+                         const int32_t* station_lo /* [M] */, const int32_t* station_hi /* [M] */, int32_t n_avoid,
+                         const int32_t* avoid_lo /* [n_avoid] or NULL */, const int32_t* avoid_hi /* [n_avoid] or NULL */,
+                         const int32_t* open_c /* [M] */, const int32_t* close_c /* [M] */, const int32_t* dwell_c /* [M] */, int32_t pace,
+                         const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] or NULL */,
+                         const int32_t* field_of /* [n], with a goal */, const int32_t* field_goal_cell /* [n_fields], with a goal */,
+                         const int32_t* field_scene /* [n_fields], with a goal */, float* waypoints_out /* [n][K][pos_dim] */,
+                         int32_t* n_waypoints_out /* [n] */, int32_t* count_out /* [n] */, int32_t* status_out /* [n] */,
+                         int32_t* cost_out /* [n] */, int32_t* tour_order_out /* [n][M] */, int32_t* tour_eta_out /* [n][M] */,
+                         int32_t* station_waypoint_out /* [n][M] */, int32_t* release_out /* [n][K] */,
+                         int32_t* station_cell_out /* [S][M] */, float* station_margin_out /* [S][M] */, int32_t* matrix_out /* [S][M][M] */,
+                         uint8_t* occupancy_out /* [S][G][G] or NULL */, int32_t* sweeps_out /* [S * M + n_fields] or NULL */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

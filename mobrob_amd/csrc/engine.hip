@@ -60,6 +60,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_spec.h"
 #include "kernels_spec_nested.h"
 #include "kernels_spec_moving.h"
+#include "kernels_plan_spec.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -318,6 +319,9 @@ struct mobrob_ppo_engine {
   size_t spec_bytes = 0;
   bool spec_nested_lds_set = false;   // k_spec_monitor_nested's dynamic-LDS attribute is raised once
   bool spec_moving_lds_set = false;   // k_spec_monitor_moving's likewise
+  // plans from a specification (mobrob_ppo_spec_plan): one allocation of their own and nothing resident
+  char* plan_spec_buf = nullptr;
+  size_t plan_spec_bytes = 0;
 };
 
 namespace {
@@ -1396,6 +1400,7 @@ void mobrob_ppo_destroy(mobrob_ppo_engine_t* e) {
   if (e->plan_time_buf) (void)hipFree(e->plan_time_buf);
   if (e->plan_team_buf) (void)hipFree(e->plan_team_buf);
   if (e->spec_buf) (void)hipFree(e->spec_buf);
+  if (e->plan_spec_buf) (void)hipFree(e->plan_spec_buf);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -5377,20 +5382,13 @@ int mobrob_ppo_plan_assign(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
 // ---- run specifications (mobrob_ppo_spec_monitor): robustness per robot from the positions of a run -------------------------------
 // everything the call refuses, before any launch or copy; counts: the scenes' region counts
 // (who: the entry point's name in the messages; max_op: the last op it takes; F: the frames of a region table [S][F][R][4])
-static int spec_check(const char* who, int max_op, const mobrob_spec_t* spec, const float* path, int N, int T, int P, int step0,
-                      std::vector<int32_t>& counts, int F = 1) {
-  if (N < 1) return fail(MOBROB_ERR_INVALID, "%s: n must be >= 1, got %d", who, N);
-  if (T < 1) return fail(MOBROB_ERR_INVALID, "%s: T must be >= 1, got %d", who, T);
-  if (P < 1 || P > 3) return fail(MOBROB_ERR_INVALID, "%s: P must lie in 1 .. 3, got %d", who, P);
-  if (step0 < 0) return fail(MOBROB_ERR_INVALID, "%s: step0 must be >= 0, got %d", who, step0);
-  if ((int64_t)step0 + T > INT_MAX) return fail(MOBROB_ERR_INVALID, "%s: step0 + T must fit an int32", who);
-  const unsigned long long bytes = (unsigned long long)(T + 1ll) * (unsigned long long)N * P * 4ull;
-  if (bytes > (unsigned long long)MOBROB_SPEC_PATH_MAX_BYTES)
-    return fail(MOBROB_ERR_INVALID, "%s: path of %llu bytes is above the limit of %u", who, bytes, (unsigned)MOBROB_SPEC_PATH_MAX_BYTES);
+// the region table of a specification (its scenes, counts, kinds, rows and scene indices); check_clauses: n_clauses is looked at too
+static int spec_check_regions(const char* who, const mobrob_spec_t* spec, int N, std::vector<int32_t>& counts, int F, bool check_clauses) {
   const int S = spec->n_scenes, R = spec->max_regions, C = spec->n_clauses;
   if (S < 1) return fail(MOBROB_ERR_INVALID, "%s: spec: n_scenes must be >= 1", who);
   if (R < 0 || R > kSpecRegionsMax) return fail(MOBROB_ERR_INVALID, "%s: spec: max_regions must lie in 0 .. %d, got %d", who, kSpecRegionsMax, R);
-  if (C < 1 || C > kSpecClausesMax) return fail(MOBROB_ERR_INVALID, "%s: spec: n_clauses must lie in 1 .. %d, got %d", who, kSpecClausesMax, C);
+  if (check_clauses && (C < 1 || C > kSpecClausesMax))
+    return fail(MOBROB_ERR_INVALID, "%s: spec: n_clauses must lie in 1 .. %d, got %d", who, kSpecClausesMax, C);
   if (!spec->n_regions) return fail(MOBROB_ERR_INVALID, "%s: spec: null n_regions", who);
   if (R > 0 && (!spec->regions || !spec->kinds)) return fail(MOBROB_ERR_INVALID, "%s: spec: null regions or kinds", who);
   if (!spec->scene && S > 1) return fail(MOBROB_ERR_INVALID, "%s: spec: %d scenes need a scene index per robot", who, S);
@@ -5413,6 +5411,21 @@ static int spec_check(const char* who, int max_op, const mobrob_spec_t* spec, co
     for (int i = 0; i < N; ++i)
       if (spec->scene[i] < 0 || spec->scene[i] >= S)
         return fail(MOBROB_ERR_INVALID, "%s: spec: scene[%d] = %d outside 0 .. %d", who, i, spec->scene[i], S - 1);
+  return MOBROB_OK;
+}
+
+static int spec_check(const char* who, int max_op, const mobrob_spec_t* spec, const float* path, int N, int T, int P, int step0,
+                      std::vector<int32_t>& counts, int F = 1) {
+  if (N < 1) return fail(MOBROB_ERR_INVALID, "%s: n must be >= 1, got %d", who, N);
+  if (T < 1) return fail(MOBROB_ERR_INVALID, "%s: T must be >= 1, got %d", who, T);
+  if (P < 1 || P > 3) return fail(MOBROB_ERR_INVALID, "%s: P must lie in 1 .. 3, got %d", who, P);
+  if (step0 < 0) return fail(MOBROB_ERR_INVALID, "%s: step0 must be >= 0, got %d", who, step0);
+  if ((int64_t)step0 + T > INT_MAX) return fail(MOBROB_ERR_INVALID, "%s: step0 + T must fit an int32", who);
+  const unsigned long long bytes = (unsigned long long)(T + 1ll) * (unsigned long long)N * P * 4ull;
+  if (bytes > (unsigned long long)MOBROB_SPEC_PATH_MAX_BYTES)
+    return fail(MOBROB_ERR_INVALID, "%s: path of %llu bytes is above the limit of %u", who, bytes, (unsigned)MOBROB_SPEC_PATH_MAX_BYTES);
+  if (const int rc = spec_check_regions(who, spec, N, counts, F, true)) return rc;
+  const int R = spec->max_regions, C = spec->n_clauses;
   for (int c = 0; c < C; ++c) {
     if (spec->op[c] < MOBROB_SPEC_ALWAYS || spec->op[c] > max_op)
       return fail(MOBROB_ERR_INVALID, "%s: spec: op[%d] = %d outside 0 .. %d", who, c, spec->op[c], max_op);
@@ -5682,6 +5695,192 @@ int mobrob_ppo_spec_monitor_moving(mobrob_ppo_engine_t* e, const mobrob_spec_mov
   HIPC(hipMemcpyAsync(val, a.val, val_bytes, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(wit, a.wit, wit_bytes, hipMemcpyDeviceToHost, e->stream));
   if (tail_bytes) HIPC(hipMemcpyAsync(tail, na.tail, tail_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipStreamSynchronize(e->stream));
+  return MOBROB_OK;
+}
+
+// ---- a plan from a specification (mobrob_ppo_spec_plan): the order of the stations and the stitched waypoints on the device -------
+// k_plan_occupancy as it is (or a zeroed map), k_plan_region_occupancy, k_plan_station (which writes the anchors into the field list),
+// ONE k_plan_field launch for the S * M station fields and the goal fields, k_plan_tour_matrix, k_plan_tour, k_plan_tour_path.  It
+// works in a buffer of its own and keeps nothing resident: mobrob_ppo_plan_grid's resident fields stay valid across it.
+int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                         const mobrob_spec_t* regions, int32_t n_stations, const int32_t* station_lo, const int32_t* station_hi,
+                         int32_t n_avoid, const int32_t* avoid_lo, const int32_t* avoid_hi, const int32_t* open_c, const int32_t* close_c,
+                         const int32_t* dwell_c, int32_t pace, const float* start, const float* goal, const int32_t* field_of,
+                         const int32_t* field_goal_cell, const int32_t* field_scene, float* waypoints_out, int32_t* n_waypoints_out,
+                         int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* tour_order_out, int32_t* tour_eta_out,
+                         int32_t* station_waypoint_out, int32_t* release_out, int32_t* station_cell_out, float* station_margin_out,
+                         int32_t* matrix_out, uint8_t* occupancy_out, int32_t* sweeps_out) {
+  const char* who = "spec_plan";
+  if (!e || !spec || !regions || !station_lo || !station_hi || !open_c || !close_c || !dwell_c || !start || !waypoints_out ||
+      !n_waypoints_out || !count_out || !status_out || !cost_out || !tour_order_out || !tour_eta_out || !station_waypoint_out ||
+      !release_out || !station_cell_out || !station_margin_out || !matrix_out)
+    return fail(MOBROB_ERR_INVALID, "%s: null argument", who);
+  if (goal && (!field_of || !field_goal_cell || !field_scene)) return fail(MOBROB_ERR_INVALID, "%s: null argument (a goal needs its field lists)", who);
+  if (spec->reuse_id != 0) return fail(MOBROB_ERR_INVALID, "%s: reuse_id must be 0 (a plan from a specification keeps nothing resident)", who);
+  const int N = spec->n_robots, P = spec->pos_dim, G = spec->cells, K = spec->max_waypoints, S = spec->n_scenes, M = n_stations;
+  const int Fg = goal ? spec->n_fields : 0;
+  if (!goal && spec->n_fields != 0) return fail(MOBROB_ERR_INVALID, "%s: n_fields = %d must be 0 without a goal", who, spec->n_fields);
+  if (M < 1 || M > kPlanTourMax) return fail(MOBROB_ERR_INVALID, "%s: n_stations must lie in 1 .. %d, got %d", who, kPlanTourMax, M);
+  if (n_avoid < 0 || n_avoid > kSpecClausesMax) return fail(MOBROB_ERR_INVALID, "%s: n_avoid must lie in 0 .. %d, got %d", who, kSpecClausesMax, n_avoid);
+  if (n_avoid > 0 && (!avoid_lo || !avoid_hi)) return fail(MOBROB_ERR_INVALID, "%s: null avoid ranges", who);
+  if (pace < 1 || pace > (1 << 20)) return fail(MOBROB_ERR_INVALID, "%s: pace must lie in 1 .. 2^20, got %d", who, pace);
+  std::vector<int32_t> wall_counts, hz_counts, region_counts;
+  {   // the spec and the scenes, by mobrob_ppo_plan_grid's checks (which count the scenes of walls and hazards, and at least one field)
+    mobrob_plan_spec_t chk = *spec;
+    if (!walls && !hz) chk.n_scenes = 1;
+    if (!goal) chk.n_fields = 1;
+    if (const int rc = plan_check_scenes(who, &chk, walls, hz, nullptr, wall_counts, hz_counts)) return rc;
+  }
+  if (const int rc = spec_check_regions(who, regions, N, region_counts, 1, false)) return rc;
+  if (S != regions->n_scenes) return fail(MOBROB_ERR_INVALID, "%s: n_scenes = %d is not the regions' %d", who, S, regions->n_scenes);
+  if (S > 65535) return fail(MOBROB_ERR_INVALID, "%s: n_scenes = %d above 65535", who, S);
+  if (walls || hz) {   // walls and hazards agree with each other (plan_check_scenes); the regions must agree with them
+    const int32_t* other = walls ? walls->scene : hz->scene;
+    if ((other != nullptr) != (regions->scene != nullptr))
+      return fail(MOBROB_ERR_INVALID, "%s: the regions and the walls / hazards must agree on the scene index per robot", who);
+    for (int i = 0; other && i < N; ++i)
+      if (other[i] != regions->scene[i])
+        return fail(MOBROB_ERR_INVALID, "%s: the regions and the walls / hazards disagree on the scene of robot %d (%d and %d)", who, i,
+                    regions->scene[i], other[i]);
+  }
+  const int R = regions->max_regions;
+  for (int j = 0; j < M; ++j) {
+    if (station_lo[j] < 0 || station_lo[j] > station_hi[j] || station_hi[j] > R)
+      return fail(MOBROB_ERR_INVALID, "%s: region range [%d, %d) of station %d outside 0 .. %d", who, station_lo[j], station_hi[j], j, R);
+    for (const int32_t* ticks : {open_c, close_c, dwell_c})
+      if (ticks[j] < 0 || ticks[j] > kPlanTourTicksMax)
+        return fail(MOBROB_ERR_INVALID, "%s: open, close and dwell ticks of station %d must lie in 0 .. %d", who, j, kPlanTourTicksMax);
+    if (open_c[j] > close_c[j])
+      return fail(MOBROB_ERR_INVALID, "%s: station %d opens at tick %d, after it closes at tick %d", who, j, open_c[j], close_c[j]);
+  }
+  for (int v = 0; v < n_avoid; ++v)
+    if (avoid_lo[v] < 0 || avoid_lo[v] > avoid_hi[v] || avoid_hi[v] > R)
+      return fail(MOBROB_ERR_INVALID, "%s: region range [%d, %d) of avoid clause %d outside 0 .. %d", who, avoid_lo[v], avoid_hi[v], v, R);
+  const int32_t* scene = regions->scene;
+  if (goal) {
+    if (const int rc = plan_check_robots(who, spec, scene, start, goal, field_of, field_goal_cell, field_scene, true)) return rc;
+  } else {
+    for (size_t k = 0; k < (size_t)N * P; ++k)
+      if (!std::isfinite(start[k])) return fail(MOBROB_ERR_INVALID, "%s: start of robot %d is not finite", who, (int)(k / P));
+  }
+  if ((int64_t)N * K > INT_MAX || (int64_t)S * M * M > INT_MAX) return fail(MOBROB_ERR_INVALID, "%s: n_robots * max_waypoints must fit an int32", who);
+  const int cells = G * G, F = S * M + Fg;
+  if ((uint64_t)((uint64_t)S * M + Fg) * (uint64_t)cells * 4u > MOBROB_PLAN_TIME_MAX_BYTES)
+    return fail(MOBROB_ERR_INVALID, "%s: fields of (%d x %d + %d) x %d x %d x 4 bytes exceed the cap of %u bytes (256 MiB)", who, S, M, Fg, G, G,
+                (unsigned)MOBROB_PLAN_TIME_MAX_BYTES);
+  const size_t field_lds = plan_field_lds_bytes(G);
+  {   // the per-workgroup LDS limit, as mobrob_ppo_plan_grid checks k_plan_field's
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device_id) != hipSuccess) limit = 64 * 1024;
+    if (field_lds > (size_t)limit)
+      return fail(MOBROB_ERR_INVALID, "%s: k_plan_field needs %zu bytes of LDS at %d cells, the device allows %d per workgroup", who, field_lds, G, limit);
+  }
+  const int Mw = walls ? walls->max_walls : 0, Mh = hz ? hz->max_hazards : 0;
+  EvalCarve call;
+  const size_t o_occ = call.add((size_t)S * cells), o_field = call.add((size_t)F * cells * 4), o_fgoal = call.add((size_t)F * 4),
+               o_fscene = call.add((size_t)F * 4), o_sweeps = call.add((size_t)F * 4), o_start = call.add((size_t)N * P * 4),
+               o_goal = call.add((size_t)N * P * 4), o_fof = call.add((size_t)N * 4), o_scene = call.add((size_t)N * 4),
+               o_wp = call.add((size_t)N * K * P * 4), o_nwp = call.add((size_t)N * 4), o_count = call.add((size_t)N * 4),
+               o_status = call.add((size_t)N * 4), o_cost = call.add((size_t)N * 4), o_order = call.add((size_t)N * M * 4),
+               o_eta = call.add((size_t)N * M * 4), o_depart = call.add((size_t)N * M * 4), o_swp = call.add((size_t)N * M * 4),
+               o_release = call.add((size_t)N * K * 4), o_cell = call.add((size_t)S * M * 4), o_margin = call.add((size_t)S * M * 4),
+               o_matrix = call.add((size_t)S * M * M * 4), o_reg = call.add(std::max<size_t>((size_t)S * R * 16, 4)),
+               o_kind = call.add(std::max<size_t>((size_t)S * R * 4, 4)), o_cnt = call.add((size_t)S * 4),
+               o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
+               o_hz = call.add(std::max<size_t>((size_t)S * Mh * 3, 1) * 4), o_nhz = call.add((size_t)S * 4);
+  if (const int rc = grow_plan_buf(e, e->plan_spec_buf, e->plan_spec_bytes, call.total)) return rc;
+  const auto mine = [&](size_t off) { return e->plan_spec_buf + off; };
+  const auto ints = [&](size_t off) { return reinterpret_cast<int*>(mine(off)); };
+  const auto floats = [&](size_t off) { return reinterpret_cast<float*>(mine(off)); };
+  unsigned char* occ_dev = reinterpret_cast<unsigned char*>(mine(o_occ));
+  const PlanGrid grid{G, spec->extent, spec->h, spec->inv_h, spec->inflate};
+  // the field list: the stations' fields of scene s at s * M + j (their goal cells are k_plan_station's to write), then the goals'
+  std::vector<int32_t> fscene(F);
+  for (int f = 0; f < S * M; ++f) fscene[f] = f / M;
+  for (int f = 0; f < Fg; ++f) fscene[S * M + f] = field_scene[f];
+  HIPC(hipMemcpyAsync(ints(o_fscene), fscene.data(), (size_t)F * 4, hipMemcpyHostToDevice, e->stream));
+  if (Fg) HIPC(hipMemcpyAsync(ints(o_fgoal) + S * M, field_goal_cell, (size_t)Fg * 4, hipMemcpyHostToDevice, e->stream));
+  if ((size_t)S * R) {
+    HIPC(hipMemcpyAsync(mine(o_reg), regions->regions, (size_t)S * R * 16, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(mine(o_kind), regions->kinds, (size_t)S * R * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  HIPC(hipMemcpyAsync(mine(o_cnt), region_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+  HIPC(hipMemcpyAsync(mine(o_start), start, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+  if (goal) {
+    HIPC(hipMemcpyAsync(mine(o_goal), goal, (size_t)N * P * 4, hipMemcpyHostToDevice, e->stream));
+    HIPC(hipMemcpyAsync(mine(o_fof), field_of, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  if (scene) HIPC(hipMemcpyAsync(mine(o_scene), scene, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+  if (walls || hz) {
+    PlanOccArgs oa{};
+    oa.g = grid; oa.Mw = Mw; oa.Mh = Mh; oa.occ = occ_dev;
+    if (walls) {
+      if ((size_t)S * Mw) HIPC(hipMemcpyAsync(mine(o_box), walls->boxes, (size_t)S * Mw * 16, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(mine(o_nwall), wall_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+      oa.boxes = floats(o_box); oa.nwall = ints(o_nwall);
+    }
+    if (hz) {
+      if ((size_t)S * Mh) HIPC(hipMemcpyAsync(mine(o_hz), hz->hazards, (size_t)S * Mh * 12, hipMemcpyHostToDevice, e->stream));
+      HIPC(hipMemcpyAsync(mine(o_nhz), hz_counts.data(), (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+      oa.hz = floats(o_hz); oa.nhz = ints(o_nhz);
+    }
+    hipLaunchKernelGGL(k_plan_occupancy, dim3(cdiv(cells, 256), S), dim3(256), ((size_t)4 * Mw + 3 * Mh) * sizeof(float), e->stream, oa);
+  } else {
+    HIPC(hipMemsetAsync(occ_dev, 0, (size_t)S * cells, e->stream));
+  }
+  if (n_avoid > 0) {
+    PlanRegionOccArgs ra{};
+    ra.g = grid; ra.regions = floats(o_reg); ra.kinds = ints(o_kind); ra.nreg = ints(o_cnt); ra.R = R; ra.n_avoid = n_avoid; ra.occ = occ_dev;
+    for (int v = 0; v < n_avoid; ++v) { ra.lo[v] = avoid_lo[v]; ra.hi[v] = avoid_hi[v]; }
+    hipLaunchKernelGGL(k_plan_region_occupancy, dim3(cdiv(cells, 256), S), dim3(256), 0, e->stream, ra);
+  }
+  PlanStationArgs sa{};
+  sa.g = grid; sa.regions = floats(o_reg); sa.kinds = ints(o_kind); sa.nreg = ints(o_cnt); sa.R = R; sa.M = M; sa.occ = occ_dev;
+  sa.cell = ints(o_cell); sa.margin = floats(o_margin); sa.field_goal = ints(o_fgoal);
+  for (int j = 0; j < M; ++j) { sa.lo[j] = station_lo[j]; sa.hi[j] = station_hi[j]; }
+  hipLaunchKernelGGL(k_plan_station, dim3(M, S), dim3(256), 0, e->stream, sa);
+  if (!e->plan_lds_set) {   // 80 KB at 128 cells: above the 64 KB a kernel gets without asking
+    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(k_plan_field), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)plan_field_lds_bytes(128)));
+    e->plan_lds_set = true;
+  }
+  const PlanFieldArgs fa{G, occ_dev, ints(o_fgoal), ints(o_fscene), ints(o_field), ints(o_sweeps)};
+  hipLaunchKernelGGL(k_plan_field, dim3(F), dim3(kPlanFieldThreads), field_lds, e->stream, fa);
+  const PlanTourMatrixArgs ma{S, M, cells, ints(o_cell), ints(o_field), ints(o_matrix)};
+  hipLaunchKernelGGL(k_plan_tour_matrix, dim3(cdiv(S * M * M, 256)), dim3(256), 0, e->stream, ma);
+  PlanTourArgs ta{};
+  ta.g = grid; ta.N = N; ta.P = P; ta.M = M; ta.S = S; ta.has_goal = goal ? 1 : 0;
+  ta.start = floats(o_start); ta.scene = scene ? ints(o_scene) : nullptr; ta.field_of = goal ? ints(o_fof) : nullptr;
+  ta.cell = ints(o_cell); ta.matrix = ints(o_matrix); ta.field = ints(o_field); ta.sweeps = ints(o_sweeps);
+  for (int j = 0; j < M; ++j) { ta.open_c[j] = open_c[j]; ta.close_c[j] = close_c[j]; ta.dwell_c[j] = dwell_c[j]; }
+  ta.status = ints(o_status); ta.cost = ints(o_cost); ta.order = ints(o_order); ta.eta = ints(o_eta); ta.depart = ints(o_depart);
+  hipLaunchKernelGGL(k_plan_tour, dim3(N), dim3(64), 0, e->stream, ta);   // a wave per robot
+  PlanTourPathArgs pa{};
+  pa.g = grid; pa.N = N; pa.K = K; pa.P = P; pa.M = M; pa.S = S; pa.has_goal = ta.has_goal; pa.pace = pace;
+  pa.start = ta.start; pa.goal = goal ? floats(o_goal) : nullptr; pa.scene = ta.scene; pa.field_of = ta.field_of;
+  pa.cell = ta.cell; pa.occ = occ_dev; pa.field = ta.field; pa.depart = ta.depart; pa.order = ta.order; pa.eta = ta.eta;
+  pa.wp = floats(o_wp); pa.nwp = ints(o_nwp); pa.count = ints(o_count); pa.status = ta.status; pa.cost = ta.cost;
+  pa.swp = ints(o_swp); pa.release = ints(o_release);
+  HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
+  HIPC(hipMemsetAsync(pa.release, 0, (size_t)N * K * 4, e->stream));
+  HIPC(hipMemsetAsync(pa.swp, 0xFF, (size_t)N * M * 4, e->stream));   // -1: no anchor waypoint
+  hipLaunchKernelGGL(k_plan_tour_path, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, pa);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(status_out, pa.status, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(cost_out, pa.cost, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(tour_order_out, pa.order, (size_t)N * M * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(tour_eta_out, pa.eta, (size_t)N * M * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(station_waypoint_out, pa.swp, (size_t)N * M * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(release_out, pa.release, (size_t)N * K * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(station_cell_out, sa.cell, (size_t)S * M * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(station_margin_out, sa.margin, (size_t)S * M * 4, hipMemcpyDeviceToHost, e->stream));
+  HIPC(hipMemcpyAsync(matrix_out, ma.matrix, (size_t)S * M * M * 4, hipMemcpyDeviceToHost, e->stream));
+  if (occupancy_out) HIPC(hipMemcpyAsync(occupancy_out, occ_dev, (size_t)S * cells, hipMemcpyDeviceToHost, e->stream));
+  if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, ints(o_sweeps), (size_t)F * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
 }

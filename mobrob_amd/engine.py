@@ -1262,6 +1262,66 @@ class PPOEngine:
             out["assign_matrix"] = matrix
         return out
 
+    def plan_spec(self, grid, walls=None, hazards=None, *, spec, start, goal=None, pace=None, max_waypoints=16, want_occupancy=False):
+        """A plan from a specification on the device (mobrob_ppo_spec_plan; the rule: goal_rules.spec_plan, reproduced bit for bit):
+        the avoid clauses of `spec` become obstacles, its reach clauses stations, and per robot the order of the stations and the
+        stitched waypoints are computed in one call.  grid: a goal_rules.GridSpec; walls / hazards: static, or None; spec: a
+        goal_rules.Spec of the plannable fragment (spec_plan_parse); start [n][P]; goal [n][P] or None; pace: spec_plan_pace's.
+        Returns spec_plan's dict (occupancy only with want_occupancy) and `sweeps`, the relaxation sweeps of each field.  Nothing
+        stays resident and plan_grid's resident fields stay valid."""
+        from ._lib import PlanSpec, SpecC, WallsC
+        from .envs import goal_rules as R
+        avoid, stations, (open_c, close_c, dwell_c), S, scene, start, goal, K, pace = R.spec_plan_check(grid, walls, hazards, spec, start,
+                                                                                                     goal, max_waypoints, pace)
+        reg = spec.regions
+        n, P = start.shape
+        G, M = grid.cells, len(stations)
+        start = np.ascontiguousarray(start, F32)
+        i32 = C.POINTER(C.c_int32)
+        ip = lambda a: a.ctypes.data_as(i32)   # noqa: E731
+        if goal is not None:
+            goal = np.ascontiguousarray(goal, F32)
+            field_of, fcell, fscene = R.plan_fields(grid, None, scene, goal)
+        Fg = 0 if goal is None else len(fcell)
+        sp = PlanSpec()
+        sp.n_robots, sp.pos_dim, sp.cells, sp.max_waypoints, sp.n_scenes, sp.n_fields = n, P, G, K, S, Fg
+        sp.extent, sp.h, sp.inv_h, sp.inflate = float(grid.extent), float(grid.h), float(grid.inv_h), float(grid.inflate_for(walls))
+        sp.reuse_id = 0
+        wl = None
+        if walls is not None:
+            wl = WallsC()
+            wl.n_scenes, wl.max_walls = walls.n_scenes, walls.max_walls
+            wl.boxes, wl.n_walls = _fp(walls.table), ip(walls.counts)
+            wl.scene = None if walls.scene is None else ip(walls.scene)
+            wl.radius, wl.cost, wl.indicator = walls.radius, walls.cost, int(walls.indicator)
+        h, _keep = (None, None) if hazards is None else self._hazards_struct(hazards, n)
+        rg = SpecC()
+        rg.n_scenes, rg.max_regions, rg.n_clauses = reg.n_scenes, reg.max_regions, 0
+        rg.regions, rg.kinds, rg.n_regions = _fp(reg.table), ip(reg.kinds), ip(reg.counts)
+        rg.scene = None if reg.scene is None else ip(reg.scene)
+        st_lo, st_hi = (np.array([s[k] for s in stations], np.int32) for k in (0, 1))
+        av_lo, av_hi = (np.array([a[k] for a in avoid], np.int32) for k in (0, 1))
+        wp = np.zeros((n, K, P), F32)
+        nwp, count, status, cost = (np.zeros(n, np.int32) for _ in range(4))
+        order, eta, swp = (np.zeros((n, M), np.int32) for _ in range(3))
+        release = np.zeros((n, K), np.int32)
+        cell, margin, matrix = np.zeros((S, M), np.int32), np.zeros((S, M), F32), np.zeros((S, M, M), np.int32)
+        occ = np.zeros((S, G, G), np.uint8) if want_occupancy else None
+        sweeps = np.zeros(S * M + Fg, np.int32)
+        check(self.lib.mobrob_ppo_spec_plan(
+            self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None else C.byref(h), C.byref(rg), M, ip(st_lo),
+            ip(st_hi), len(avoid), ip(av_lo) if avoid else None, ip(av_hi) if avoid else None, ip(open_c), ip(close_c), ip(dwell_c), pace,
+            _fp(start), None if goal is None else _fp(goal), None if goal is None else ip(field_of), None if goal is None else ip(fcell),
+            None if goal is None else ip(fscene), _fp(wp), ip(nwp), ip(count), ip(status), ip(cost), ip(order), ip(eta), ip(swp),
+            ip(release), ip(cell), _fp(margin), ip(matrix), None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), ip(sweeps)))
+        out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "tour_order": order, "tour_eta": eta,
+               "station_waypoint": swp, "release": release, "station_cell": cell, "station_margin": margin,
+               "covered": margin >= np.float32(R.REACH_RADIUS), "matrix": matrix, "open_c": open_c, "close_c": close_c, "dwell_c": dwell_c,
+               "pace": pace, "sweeps": sweeps}
+        if occ is not None:
+            out["occupancy"] = occ.astype(bool)
+        return out
+
     def episode_stats(self, reset=True):
         """Episodes finished by the goal environment since the counters were last reset."""
         st = EpisodeStats()

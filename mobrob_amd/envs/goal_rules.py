@@ -1035,10 +1035,16 @@ def grid_field(occ_scene, goal_cell):
 def grid_walk(field, occ_scene, spec, start_xy, goal_xy):
     """The cells of grid_path's walk -> (cells [(ix, iy), ...] from the start's cell to the goal's, directions taken, status):
     status UNREACHABLE (empty lists) if the start cell or the goal cell is blocked or field[start] < 0."""
-    occ, d = np.asarray(occ_scene, bool), np.asarray(field)
-    G = spec.cells
     sx, sy = (int(v) for v in spec.cell_of(np.asarray(start_xy, np.float32)[:2]))
     gx, gy = (int(v) for v in spec.cell_of(np.asarray(goal_xy, np.float32)[:2]))
+    return grid_walk_cells(field, occ_scene, (sx, sy), (gx, gy))
+
+
+def grid_walk_cells(field, occ_scene, start_cell, goal_cell):
+    """grid_walk between two cells (ix, iy): the descent rule itself, stated here once (grid_walk, and every leg of spec_plan)"""
+    occ, d = np.asarray(occ_scene, bool), np.asarray(field)
+    G = occ.shape[0]
+    (sx, sy), (gx, gy) = start_cell, goal_cell
     if occ[sy, sx] or occ[gy, gx] or d[sy, sx] < 0:
         return [], [], UNREACHABLE
     cells, dirs, prev = [(sx, sy)], [], -1
@@ -2708,8 +2714,11 @@ class Spec:
     clause kinds.  `dynamic` is True for a specification with moving regions or a mate predicate (the device folds it with
     k_spec_monitor_moving); one without either is the object it was and takes the call it took.
 
+    A specification can also drive the plan: spec_plan (GridPlanner.plan_spec) turns the always(outside) clauses over the whole run
+    into obstacles and the eventually / stay clauses over inside() into stations, and chooses their order per robot.
+
     Not built: deeper nesting (an until inside a window, a window inside a window), disjunction of clauses, predicates on
-    velocity, interpolation between frames."""
+    velocity, interpolation between frames; in a plan from a specification: until, recur, mate predicates and moving regions."""
 
     def __init__(self, regions, clauses, team_size=1):
         if not isinstance(regions, (Regions, MovingRegions)):
@@ -2982,3 +2991,318 @@ def spec_result(state, spec):
         rob, weak = np.where(take, rho[:, c], rob), np.where(take, c, weak).astype(np.int32)
     return {"spec_rho": rho, "spec_witness": state.wit.copy(), "robustness": rob.astype(np.float32), "weakest": weak,
             "satisfied": rob > 0}
+
+
+# ---- a plan from a specification: avoid clauses become obstacles, reach clauses stations; per robot the order of
+# the stations (Held-Karp over the stations' own cost-to-go fields, with windows and dwell) and the stitched waypoints.  This
+# project's own rule, all integers except the two margin tests; the device (csrc/kernels_plan_spec.h: k_plan_region_occupancy,
+# k_plan_station, k_plan_tour_matrix, k_plan_tour, k_plan_tour_path, with k_plan_occupancy and k_plan_field as they are) is held to
+# it bit for bit.  NOT planned: smoothing of the legs, teams, moving hazards or regions, precedence (until), recurring visits,
+# re-ordering during a run, more than PLAN_TOUR_STATIONS_MAX stations.
+PLAN_TOUR_STATIONS_MAX = 8          # 256 subsets of stations: the tour table of one robot fits a wave's LDS
+PLAN_TOUR_TICKS_MAX = 1 << 24       # every open, close and dwell in ticks is clamped here: 8 legs of them stay below 2^30
+PLAN_TOUR_INF = 0x3FFFFFFF          # "no feasible way" in the tour table
+SPEC_PLAN_KEYS = ("waypoints", "n_waypoints", "count", "status", "cost", "tour_order", "tour_eta", "station_waypoint", "release",
+                  "station_cell", "station_margin", "matrix")
+
+
+def spec_plan_parse(spec):
+    """The plannable fragment of a Spec -> (avoid [(lo, hi)], stations [(lo, hi, a, b, hold)]), stations in clause order.
+    Avoid: Spec.always(outside(lo, hi)) with the window exactly [0, open].  Station: Spec.eventually(inside(lo, hi), a, b) (hold 0)
+    or Spec.stay(inside(lo, hi), hold, a, b).  Everything else is a ValueError naming the clause and the reason: until, recur, an
+    always with another window or over inside, an eventually / stay over outside, mate predicates, team_size != 1, MovingRegions,
+    no station at all, more than PLAN_TOUR_STATIONS_MAX stations."""
+    if not isinstance(spec, Spec):
+        raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.Spec, not {type(spec).__name__}")
+    if spec.moving:
+        raise ValueError("spec_plan: MovingRegions are not planned for (a plan needs static regions)")
+    if spec.team_size != 1:
+        raise ValueError(f"spec_plan: team_size must be 1, got {spec.team_size} (teams are not planned from a specification)")
+    avoid, stations = [], []
+    for c, cl in enumerate(spec.clauses):
+        op, a, b, p1 = cl[:4]
+        if op == SPEC_UNTIL:
+            raise ValueError(f"spec_plan: clause {c}: until is not plannable (precedence between stations is not built)")
+        if op == SPEC_RECUR:
+            raise ValueError(f"spec_plan: clause {c}: recur is not plannable (a station is visited once)")
+        if _is_mate_predicate(p1):
+            raise ValueError(f"spec_plan: clause {c}: a mate predicate (together / apart) is not plannable")
+        lo, hi, out = p1
+        if op == SPEC_ALWAYS:
+            if not out:
+                raise ValueError(f"spec_plan: clause {c}: always over inside() is not plannable (only always(outside(...)) is: an obstacle)")
+            if (a, b) != (0, SPEC_OPEN):
+                raise ValueError(f"spec_plan: clause {c}: always(outside(...)) must have the window [0, open], got [{a}, {b}] "
+                                 "(an obstacle holds for the whole plan)")
+            avoid.append((lo, hi))
+        else:
+            if out:
+                raise ValueError(f"spec_plan: clause {c}: {'stay' if op == SPEC_STAY else 'eventually'} over outside() is not plannable "
+                                 "(a station is inside(...))")
+            stations.append((lo, hi, a, b, cl[5] if op == SPEC_STAY else 0))
+    if not stations:
+        raise ValueError("spec_plan: the specification has no visit clause (eventually / stay over inside(...)): nothing to plan")
+    if len(stations) > PLAN_TOUR_STATIONS_MAX:
+        raise ValueError(f"spec_plan: {len(stations)} stations, at most PLAN_TOUR_STATIONS_MAX = {PLAN_TOUR_STATIONS_MAX}")
+    return avoid, stations
+
+
+def spec_plan_pace(pace, stations):
+    """-> the checked pace: an integer >= 1 (at most 2^20); None is 1 where no station has a window or a dwell and a ValueError
+    naming `pace` where one has (the plan cannot turn steps into moves without it)"""
+    if pace is None:
+        if any((a, b, hold) != (0, SPEC_OPEN, 0) for _, _, a, b, hold in stations):
+            raise ValueError("spec_plan: pace= is required when a station has a window or a dwell (the steps a robot is given for one "
+                             "orthogonal move)")
+        return 1
+    if isinstance(pace, bool) or not isinstance(pace, (int, np.integer)) or not 1 <= pace <= 1 << 20:
+        raise ValueError(f"spec_plan: pace must be an integer in 1 .. 2^20, got {pace!r}")
+    return int(pace)
+
+
+def spec_plan_ticks(stations, pace):
+    """The stations' windows and dwells in ticks (PLAN_STEP a pace) -> (open_c, close_c, dwell_c) int32 [M]: ceil(5 a / pace),
+    floor(5 b / pace) (an open b: the clamp), ceil(5 hold / pace), each clamped to PLAN_TOUR_TICKS_MAX.  ValueError where a window
+    holds no tick at this pace (open_c > close_c)."""
+    cap = PLAN_TOUR_TICKS_MAX
+    open_c = [min(-((-PLAN_STEP * a) // pace), cap) for _, _, a, _, _ in stations]
+    close_c = [cap if b == SPEC_OPEN else min((PLAN_STEP * b) // pace, cap) for _, _, _, b, _ in stations]
+    dwell_c = [min(-((-PLAN_STEP * h) // pace), cap) for _, _, _, _, h in stations]
+    for j, (o, c) in enumerate(zip(open_c, close_c)):
+        if o > c:
+            raise ValueError(f"spec_plan: station {j}: the window [{stations[j][2]}, {stations[j][3]}] holds no move boundary at pace {pace} "
+                             f"(opens at tick {o}, closes at tick {c})")
+    return np.array(open_c, np.int32), np.array(close_c, np.int32), np.array(dwell_c, np.int32)
+
+
+def spec_plan_scene(regions, walls=None, hazards=None):
+    """-> (S, scene [n] int32 or None): the regions' scenes, which the walls' and the hazards' must equal where those exist"""
+    plan_scene(walls, hazards)
+    for what, sc in (("walls", walls), ("hazards", hazards)):
+        if sc is None:
+            continue
+        if sc.n_scenes != regions.n_scenes:
+            raise ValueError(f"spec_plan: the regions have {regions.n_scenes} scenes, the {what} {sc.n_scenes}")
+        if (sc.scene is None) != (regions.scene is None) or (sc.scene is not None and not np.array_equal(sc.scene, regions.scene)):
+            raise ValueError(f"spec_plan: the regions and the {what} must agree on the scene index per robot")
+    return regions.n_scenes, regions.scene
+
+
+def spec_plan_check(grid, walls, hazards, spec, start, goal, K, pace):
+    """spec_plan's refusals, by name -> (avoid, stations, ticks, S, scene, start, goal or None (float32), K, pace)"""
+    if not isinstance(grid, GridSpec):
+        raise TypeError(f"grid must be a mobrob_amd.envs.goal_rules.GridSpec, not {type(grid).__name__}")
+    avoid, stations = spec_plan_parse(spec)
+    pace = spec_plan_pace(pace, stations)
+    ticks = spec_plan_ticks(stations, pace)
+    S, scene = spec_plan_scene(spec.regions, walls, hazards)
+    start = np.asarray(start, np.float64)
+    if start.ndim != 2 or start.shape[0] < 1 or start.shape[1] not in (2, 3):
+        raise ValueError(f"spec_plan: start must be [n_robots, 2 or 3], got shape {start.shape}")
+    if goal is not None:
+        goal = np.asarray(goal, np.float64)
+        if goal.shape != start.shape:
+            raise ValueError(f"spec_plan: goal must have start's shape {start.shape}, got {goal.shape}")
+    if not np.all(np.isfinite(start)) or (goal is not None and not np.all(np.isfinite(goal))):
+        raise ValueError("spec_plan: start and goal must be finite")
+    for sc in (walls, hazards, spec.regions):
+        if sc is not None:
+            sc.check_robots(start.shape[0])
+    K = int(K)
+    if K < 1:
+        raise ValueError("spec_plan: max_waypoints must be >= 1")
+    return avoid, stations, ticks, S, scene, start.astype(np.float32), None if goal is None else goal.astype(np.float32), K, pace
+
+
+def _spec_plan_margins(grid, regions, s):
+    """region_margins of scene s at every cell centre -> float32 [G * G][R], cell c = iy * G + ix"""
+    G = grid.cells
+    c = grid.centre(np.arange(G))
+    xy = np.stack([np.broadcast_to(c[None, :], (G, G)).reshape(-1), np.broadcast_to(c[:, None], (G, G)).reshape(-1)], axis=1)
+    R = regions.max_regions
+    return region_margins(xy, np.broadcast_to(regions.table[s], (G * G, R, 4)), np.broadcast_to(regions.kinds[s], (G * G, R)))
+
+
+def spec_plan_occupancy(grid, walls, hazards, regions, avoid):
+    """The blocked map of a plan from a specification, bool [S][G][G]: grid_occupancy of the walls and hazards, OR-ed per scene with
+    the avoid regions -- a cell is blocked when a region r of an avoid range, r < counts[scene], has region_margins(centre)[r] >=
+    float32(-inflate).  Equality blocks, as for walls."""
+    S = regions.n_scenes
+    G = grid.cells
+    occ = grid_occupancy(grid, walls, hazards) if (walls is not None or hazards is not None) else np.zeros((S, G, G), bool)
+    occ = occ.copy()
+    edge = np.float32(-grid.inflate_for(walls))
+    for s in range(S):
+        if not avoid:
+            break
+        m = _spec_plan_margins(grid, regions, s)
+        for lo, hi in avoid:
+            for r in range(lo, min(hi, int(regions.counts[s]))):
+                occ[s] |= (m[:, r] >= edge).reshape(G, G)
+    return occ
+
+
+def spec_plan_stations(grid, regions, stations, occ):
+    """The anchors -> (station_cell int32 [S][M], station_margin float32 [S][M]).  Per scene and station the candidates are the
+    unblocked cells, m(c) = spec_predicate(inside(lo, hi)) at the cell's centre; the best cell is the one of the largest spec_key(m),
+    the lowest cell index on a tie, and station_margin is its m (-inf without an unblocked cell); it is the anchor when m > 0, else
+    the anchor is -1."""
+    S, M, G = regions.n_scenes, len(stations), grid.cells
+    cell, margin = np.full((S, M), -1, np.int32), np.full((S, M), -np.inf, np.float32)
+    for s in range(S):
+        mg = _spec_plan_margins(grid, regions, s)
+        free = np.nonzero(~occ[s].reshape(-1))[0]
+        if free.size == 0:
+            continue
+        counts = np.full(G * G, regions.counts[s])
+        for j, (lo, hi, _, _, _) in enumerate(stations):
+            m = spec_predicate(mg, counts, (lo, hi, False))[free]
+            best = int(np.argmax(spec_key(m)))                      # argmax: the first, hence the lowest cell, of equal keys
+            margin[s, j] = m[best]
+            if m[best] > 0:
+                cell[s, j] = free[best]
+    return cell, margin
+
+
+def spec_plan_tour(d0, D, E, open_c, close_c, dwell_c):
+    """The order of the stations for n robots at once (Held-Karp).  d0 int64 [n][M]: start to station j; D int64 [n][M][M]: station
+    i to station j (the robot's scene's); E int64 [n][M]: station i to the goal (zeros without a goal); PLAN_ASSIGN_NONE reads "no
+    path".  dep(j, arr) = max(arr, open_c[j]) + dwell_c[j], feasible iff arr is a real cost and max(arr, open_c[j]) <= close_c[j].
+    t[{j}][j] = dep(j, d0[j]); t[mask + j][j] = the minimum over the feasible i in mask of dep(j, t[mask][i] + D[i][j]), taken of the
+    pair (value, i), so the lowest i wins a tie; the tour ends at the j minimising (t[full][j] + E[j], j).
+    -> (feasible bool [n], cost int64 [n], order int32 [n][M], eta int64 [n][M] (ticks on arrival, before max with open_c), depart
+    int64 [n][M]); order, eta, depart are -1 and cost -1 where no feasible tour exists."""
+    n, M = d0.shape
+    INF, NONE = PLAN_TOUR_INF, PLAN_ASSIGN_NONE
+    full = (1 << M) - 1
+    t = np.full((n, 1 << M, M), INF, np.int64)
+    pred = np.full((n, 1 << M, M), -1, np.int8)
+
+    def dep(j, arr, ok):
+        begin = np.maximum(arr, open_c[j])
+        return np.where(ok & (begin <= close_c[j]), begin + dwell_c[j], INF)
+    for mask in range(1, full + 1):
+        for j in range(M):
+            if not mask >> j & 1:
+                continue
+            rest = mask ^ (1 << j)
+            if rest == 0:
+                t[:, mask, j] = dep(j, d0[:, j], d0[:, j] < NONE)
+                continue
+            best, via = np.full(n, INF, np.int64), np.full(n, -1, np.int8)
+            for i in range(M):                                   # ascending: strict < keeps the lowest i of equal values
+                if not rest >> i & 1:
+                    continue
+                val = dep(j, t[:, rest, i] + D[:, i, j], (t[:, rest, i] < INF) & (D[:, i, j] < NONE))
+                take = val < best
+                best, via = np.where(take, val, best), np.where(take, i, via).astype(np.int8)
+            t[:, mask, j], pred[:, mask, j] = best, via
+    cost, last = np.full(n, INF, np.int64), np.full(n, -1, np.int64)
+    for j in range(M):
+        tot = np.where((t[:, full, j] < INF) & (E[:, j] < NONE), t[:, full, j] + E[:, j], INF)
+        take = tot < cost
+        cost, last = np.where(take, tot, cost), np.where(take, j, last)
+    ok = cost < INF
+    order, eta, depart = np.full((n, M), -1, np.int32), np.full((n, M), -1, np.int64), np.full((n, M), -1, np.int64)
+    for r in np.nonzero(ok)[0]:
+        mask, j = full, int(last[r])
+        for k in range(M - 1, -1, -1):
+            order[r, k] = j
+            depart[r, k] = t[r, mask, j]
+            i = int(pred[r, mask, j])
+            eta[r, k] = d0[r, j] if i < 0 else t[r, mask ^ (1 << j), i] + D[r, i, j]
+            mask, j = mask ^ (1 << j), i
+    return ok, np.where(ok, cost, -1), order, eta, depart
+
+
+def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None):
+    """The plan of n robots from a specification (DESIGN 4.12.9) -> dict.  grid: a GridSpec; walls / hazards: static, or None;
+    spec: a Spec of the plannable fragment (spec_plan_parse); start [n][P]; goal [n][P] or None: where every robot ends after its
+    last station; K waypoint slots; pace: the steps a robot is given for one orthogonal move (spec_plan_pace).
+
+    Blocked map: spec_plan_occupancy.  Anchors: spec_plan_stations -> station_cell, station_margin [S][M]; covered [S][M] =
+    station_margin >= REACH_RADIUS (the tracker calls a waypoint reached within REACH_RADIUS of it: only a covered station is
+    certainly entered on arrival).  A scene with an anchor of -1 gives every robot of it status UNREACHABLE.
+    Costs: one grid_field per (scene, anchor) and per distinct (scene, goal cell); matrix int32 [S][M][M], matrix[s][i][j] = the field
+    of station j at the anchor of station i (-1: none).  Time is in ticks, PLAN_STEP for an orthogonal move and PLAN_DIAG for a
+    diagonal one (the fields' units): spec_plan_ticks.  Order: spec_plan_tour.
+    Waypoints: the legs in tour order, then the goal leg; each leg descends its target's field by grid_walk_cells' rule (the previous
+    direction forgotten at the start of a leg) and emits what grid_path emits: the centres of the cells where the direction
+    changes, then the leg's end -- a station's anchor centre, or the goal itself.  z of every waypoint: the goal's, else the start's.
+    The dict: waypoints float32 [n][K][P], n_waypoints, count (the waypoints of the full path), status [n] int32 (PLANNED,
+    UNREACHABLE: no feasible tour, count 0, TRUNCATED: the first K are written; the device reports UNCONVERGED where a loop hit its
+    bound), cost [n] int32 (the ticks at the end, waits included; -1), tour_order int32 [n][M] (the station at each position),
+    tour_eta int32 [n][M] (ticks on arrival at each position, before the wait for its opening), station_waypoint int32 [n][M] (the
+    index in the full path of each position's anchor waypoint), release int32 [n][K]: at the slot of the waypoint AFTER a station
+    whose departure exceeds its arrival, min(ceil(departure ticks * pace / PLAN_STEP), 2^31 - 1), else 0 -- ready for
+    Schedule(release), which holds the robot at the station until then --, and station_cell, station_margin, covered, matrix,
+    occupancy, open_c, close_c, dwell_c, pace.
+
+    Limitations: pace is an estimate of the policy's speed; a robot that arrives later than planned dwells for less time (the
+    release is a global step, not a duration); the monitor after the run remains the judge."""
+    avoid, stations, (open_c, close_c, dwell_c), S, scene, start, goal, K, pace = spec_plan_check(grid, walls, hazards, spec, start,
+                                                                                                 goal, K, pace)
+    reg = spec.regions
+    n, P = start.shape
+    G, M = grid.cells, len(stations)
+    occ = spec_plan_occupancy(grid, walls, hazards, reg, avoid)
+    cell, margin = spec_plan_stations(grid, reg, stations, occ)
+    NONE = PLAN_ASSIGN_NONE
+    fields = [[grid_field(occ[s], cell[s, j]).reshape(-1) if cell[s, j] >= 0 else np.full(G * G, -1, np.int32) for j in range(M)]
+              for s in range(S)]
+    matrix = np.full((S, M, M), -1, np.int32)
+    for s in range(S):
+        for i in range(M):
+            if cell[s, i] >= 0:
+                matrix[s, i] = [fields[s][j][cell[s, i]] for j in range(M)]
+    sc = np.zeros(n, np.int64) if scene is None else np.asarray(scene, np.int64)
+    scell, _ = plan_assign_cells(grid, start, start)
+    real = lambda v: np.where(np.asarray(v, np.int64) < 0, NONE, np.asarray(v, np.int64))   # noqa: E731
+    d0 = real(np.array([[fields[sc[r]][j][scell[r]] for j in range(M)] for r in range(n)]))
+    D = real(matrix)[sc]
+    if goal is not None:
+        field_of, fcell, fscene = plan_fields(grid, None, scene, goal)
+        gfields = [grid_field(occ[fscene[f]], fcell[f]).reshape(-1) for f in range(len(fcell))]
+        E = real(np.array([[gfields[field_of[r]][cell[sc[r], i]] if cell[sc[r], i] >= 0 else -1 for i in range(M)] for r in range(n)]))
+    else:
+        E = np.zeros((n, M), np.int64)
+    anchored = np.all(cell[sc] >= 0, axis=1)
+    d0[~anchored] = NONE
+    ok, cost, order, eta, depart = spec_plan_tour(d0, D, E, open_c.astype(np.int64), close_c.astype(np.int64), dwell_c.astype(np.int64))
+    wp, release = np.zeros((n, K, P), np.float32), np.zeros((n, K), np.int32)
+    count, status = np.zeros(n, np.int32), np.full(n, UNREACHABLE, np.int32)
+    swp = np.full((n, M), -1, np.int32)
+    z = (start if goal is None else goal)[:, 2:]
+
+    def centre(c):
+        return grid.centre(c % G), grid.centre(c // G)
+    for r in np.nonzero(ok)[0]:
+        s, cur, cnt = int(sc[r]), int(scell[r]), 0
+
+        def emit(xy, cnt=None):
+            if cnt < K:
+                wp[r, cnt, :2], wp[r, cnt, 2:] = xy, z[r]
+        legs = [(int(cell[s, j]), fields[s][j]) for j in order[r]] + ([] if goal is None else [(None, gfields[field_of[r]])])
+        for k, (target, field) in enumerate(legs):
+            to = int(fcell[field_of[r]]) if target is None else target
+            cells, dirs, st = grid_walk_cells(field.reshape(G, G), occ[s], (cur % G, cur // G), (to % G, to // G))
+            if st != PLANNED:
+                raise ValueError("spec_plan: a leg of a feasible tour has no walk (the fields are not those of this map)")
+            for q in range(1, len(cells) - 1):
+                if dirs[q] != dirs[q - 1]:
+                    emit(centre(cells[q][1] * G + cells[q][0]), cnt)
+                    cnt += 1
+            if target is None:
+                emit(goal[r, :2], cnt)
+            else:
+                emit(centre(to), cnt)
+                swp[r, k] = cnt
+                if depart[r, k] > eta[r, k] and k + 1 < len(legs) and cnt + 1 < K:
+                    release[r, cnt + 1] = min(-((-int(depart[r, k]) * pace) // PLAN_STEP), SPEC_OPEN)
+            cnt += 1
+            cur = to
+        count[r], status[r] = cnt, TRUNCATED if cnt > K else PLANNED
+    return {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status,
+            "cost": cost.astype(np.int32), "tour_order": order, "tour_eta": eta.astype(np.int32), "station_waypoint": swp,
+            "release": release, "station_cell": cell, "station_margin": margin, "covered": margin >= np.float32(REACH_RADIUS),
+            "matrix": matrix, "occupancy": occ, "open_c": open_c, "close_c": close_c, "dwell_c": dwell_c, "pace": pace}

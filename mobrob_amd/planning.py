@@ -29,6 +29,9 @@ for the assigned goals, through whichever team path the planner is configured fo
 its own (goal_rules.grid_assign; device: mobrob_ppo_plan_assign).  Clearance (`clearance=(reach, weight)`): a static
 plan that pays a surcharge for entering a cell within `reach` cells of a blocked one, so it takes the middle of a corridor where
 that costs little (goal_rules.grid_plan(..., clearance=); device: mobrob_ppo_plan_grid_clear, mobrob_ppo_plan_smooth_clear).
+A plan from a specification (`planner.plan_spec(start, spec, goal=None, pace=None)`): the avoid clauses of a
+goal_rules.Spec become obstacles, its reach clauses stations, and per robot the visit order and the stitched waypoints are chosen
+(goal_rules.spec_plan; device: mobrob_ppo_spec_plan).
 Walls as solid bodies are not planned for."""
 from __future__ import annotations
 
@@ -354,6 +357,37 @@ class GridPlanner:
         if out.get("sweeps") is not None:
             res["sweeps"] = out["sweeps"]
         return res
+
+    def plan_spec(self, start, spec, goal=None, pace=None, max_waypoints=None):
+        """A plan from a specification: the avoid clauses of `spec` (Spec.always(outside(...)) over the whole run)
+        become obstacles beside the planner's walls and hazards, its reach clauses (Spec.eventually / Spec.stay over inside(...),
+        at most 8) stations, and per robot the order of the stations is chosen -- the shortest tour that keeps every window and
+        dwell -- and the waypoints stitched, all robots in one call: the device call on a DeviceGoalVecEnv, the NumPy rule on the
+        host path (goal_rules.spec_plan; device: mobrob_ppo_spec_plan), bit for bit.  start [n][P]; goal [n][P] or None: where
+        the robots end after the last station; pace: the steps a robot is given for one orthogonal move (an integer >= 1; None: 1
+        where no station has a window or a dwell, a ValueError naming pace= where one has); max_waypoints: the K slots (None: the
+        planner's).  Returns goal_rules.spec_plan's dict (waypoints, n_waypoints, count, status, cost in ticks, tour_order, tour_eta,
+        station_waypoint, release, station_cell, station_margin, covered, matrix, ...) and `schedule`: a
+        Schedule(release, home=start) for follow_waypoints where any release is nonzero, else None.
+        Refused by name: a planner with teams=, moving hazards, clearance= or smooth= (legs are not smoothed, teams and moving
+        hazards are not planned from a specification), and everything goal_rules.spec_plan_parse refuses of the specification.
+        pace is an estimate of the policy's speed: a robot that arrives later than planned dwells for less time, and the monitor
+        after the run remains the judge."""
+        for what, on in (("teams=", self.teams is not None), ("hazards=MovingHazards", isinstance(self.hazards, rules.MovingHazards)),
+                         ("clearance=", self.clearance is not None), ("smooth=", self.smooth), ("time_smooth=", self.time_smooth)):
+            if on:
+                raise ValueError(f"GridPlanner.plan_spec: a planner with {what} is not supported (a plan from a specification is the "
+                                 "static, unsmoothed plan of single robots)")
+        K = self.K if max_waypoints is None else int(max_waypoints)
+        start = np.asarray(start, np.float64)
+        if start.ndim != 2 or start.shape[1] != self.pos_dim:
+            raise ValueError(f"plan_spec: start must be [n_robots, {self.pos_dim}], got shape {start.shape}")
+        if self.device:
+            out = self.engine.plan_spec(self.spec, self.walls, self.hazards, spec=spec, start=start, goal=goal, pace=pace, max_waypoints=K)
+        else:
+            out = rules.spec_plan(self.spec, self.walls, self.hazards, spec, start, goal, K, pace)
+        out["schedule"] = rules.Schedule(out["release"], home=start) if np.any(out["release"] != 0) else None
+        return out
 
     def callback(self, goal, horizon=None):
         """The `planner(positions, status, reached)` of waypoints.follow_with_replanning for the goals `goal` [n][P]: every
