@@ -69,6 +69,9 @@ before and after (mobrob_amd.planning.GridPlanner(assign=)).  A run is never rea
 circle around --goal; with --spec-hold H a stay of H steps, which needs --pace, the steps a robot is given for one orthogonal move)
 are planned with GridPlanner.plan_spec in place of the plan to --goal, the walls once more as keep-out regions; the run follows the
 plan's schedule, the monitor then judges it.  It excludes --hazard-frames, --team-size, --plan-smooth and --plan-clearance.
+`--replan-spec` (with --plan-spec, --horizon and --leg-steps) plans a stalled robot again between the calls of the run, from where it
+stands and at the run's step, for the stations the monitor has not seen satisfied yet (GridPlanner.spec_callback); `--partial` lets
+a robot that cannot keep every window keep the stations it still can, in the first plan and in every later one.
 """
 import argparse
 import os
@@ -99,7 +102,8 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            release=None, stagger=0, walls=None, arena=False, robot_radius=0.1, goal=None, plan_cells=64,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
            plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False,
-           tile256_wide=False, team_solid=False, check_spec=False, spec_hold=0, plan_spec=False, pace=None):
+           tile256_wide=False, team_solid=False, check_spec=False, spec_hold=0, plan_spec=False, pace=None,
+           replan_spec=False, partial=False):
     if check_spec and goal is None:
         raise ValueError("--check-spec needs --goal (the specification is: eventually inside the reach radius around the goal)")
     if int(spec_hold) != 0 and not check_spec:
@@ -108,6 +112,10 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         raise ValueError("--plan-spec needs --check-spec (the specification whose stations are planned)")
     if pace is not None and not plan_spec:
         raise ValueError("--pace needs --plan-spec")
+    if replan_spec and not plan_spec:
+        raise ValueError("--replan-spec needs --plan-spec (the plan that is made again during the run)")
+    if partial and not plan_spec:
+        raise ValueError("--partial needs --plan-spec")
     if team_solid and team_size is None:
         raise ValueError("--team-solid needs --team-size")
     if solid and walls is None and not arena:
@@ -195,8 +203,10 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             plain = planner.plan(start, goals, grow=True, clearance=None, want_occupancy=True, want_fields=True)
             plain_min = grid_plan_clearance_min(planner.spec, plain, start, goals, planner.clearance[0])
         if plan_spec:                                      # the specification's stations in --goal's place, in the order the plan chooses
-            plan = planner.plan_spec(start, monitored_spec()["spec"], pace=pace)
+            plan = planner.plan_spec(start, monitored_spec()["spec"], pace=pace, partial=bool(partial))
             plan.update(smoothed=False, moves=None)
+            if replan_spec and plan["schedule"] is None:   # the replanned rows may bring release steps: the run has a schedule from its first call
+                plan["schedule"] = Schedule(plan["release"], home=start)
             print(f"planned from the specification: tour cost {float(np.mean(plan['cost'][plan['status'] == 0])) if np.any(plan['status'] == 0) else float('nan')} "
                   f"ticks, {int(np.sum(plan['release'] != 0))} holds, stations covered: {bool(np.all(plan['covered']))}")
         else:
@@ -213,6 +223,8 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
                   f"{int(plan['assign_identity_total'].sum())} -> {int(plan['assign_total'].sum())}")
         waypoints, n_waypoints, plan_schedule = plan["waypoints"], plan["n_waypoints"], plan.get("schedule")
         replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 and not plan_spec else None
+        if replan_spec:                                    # a stalled robot gets the stations it has not visited yet, from where it stands
+            replan = planner.spec_callback(monitored_spec()["spec"], pace=pace, partial=bool(partial))
         print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
         if teams is not None:                              # beside the run's measured team conflict steps, further down
             print(f"planned team clearance: {int(plan['team_clearance'].min())} cells at the least (reserve {planner.reserve}), "
@@ -231,7 +243,8 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
                          leg_steps=leg_steps, teams=teams, schedule=schedule, walls=wl, **monitored)
     for steps in calls[1:]:                                # the run, continued call after call
         if replan is not None:                             # a stalled robot is planned again from where it stands
-            for robot, w in replan(np.array(r["state"].positions), r["status"], r["reached"]).items():
+            more = dict(state=r["state"]) if getattr(replan, "wants_state", False) else {}
+            for robot, w in replan(np.array(r["state"].positions), r["status"], r["reached"], **more).items():
                 if isinstance(w, tuple):                   # a time plan: the waypoints and their release steps
                     r["state"].replan([robot], np.asarray(w[0], np.float64)[None], release=w[1][None])
                 else:
@@ -363,6 +376,11 @@ def build_parser():
                          "regions) with GridPlanner.plan_spec instead of planning to --goal, follow with the plan's schedule, then monitor")
     ap.add_argument("--pace", type=int, default=None,
                     help="with --plan-spec: the steps a robot is given for one orthogonal move (required with --spec-hold)")
+    ap.add_argument("--replan-spec", action="store_true", default=False,
+                    help="with --plan-spec: between the calls of the run (--horizon, --leg-steps) plan a stalled robot again from where it "
+                         "stands, for the stations not yet visited (GridPlanner.spec_callback)")
+    ap.add_argument("--partial", action="store_true", default=False,
+                    help="with --plan-spec: a robot that cannot keep every window keeps the stations it still can (plan_spec(partial=True))")
     ap.add_argument("--tile256", action="store_true", default=False,
                     help="a 2x256 tanh policy: run calls without hazards, teams or walls as one launch (PPOEngine.set_eval_tile256)")
     ap.add_argument("--tile256-wide", action="store_true", default=False,
@@ -387,6 +405,8 @@ if __name__ == "__main__":
         ap.error("--plan-spec needs --check-spec")
     if args.pace is not None and not args.plan_spec:
         ap.error("--pace needs --plan-spec")
+    if (args.replan_spec or args.partial) and not args.plan_spec:
+        ap.error("--replan-spec and --partial need --plan-spec")
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
     except ValueError as ex:
@@ -403,4 +423,5 @@ if __name__ == "__main__":
            plan_retries=args.plan_retries, goals=None if args.goals is None else np.load(args.goals), assign=args.assign,
            plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid,
            tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide, team_solid=args.team_solid,
-           check_spec=args.check_spec, spec_hold=args.spec_hold, plan_spec=args.plan_spec, pace=args.pace)
+           check_spec=args.check_spec, spec_hold=args.spec_hold, plan_spec=args.plan_spec, pace=args.pace,
+           replan_spec=args.replan_spec, partial=args.partial)

@@ -1399,6 +1399,40 @@ int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
                          int32_t* station_cell_out /* [S][M] */, float* station_margin_out /* [S][M] */, int32_t* matrix_out /* [S][M][M] */,
                          uint8_t* occupancy_out /* [S][G][G] or NULL */, int32_t* sweeps_out /* [S * M + n_fields] or NULL */);
 
+/* The same plan from the middle of a run (goal_rules.spec_plan with state=, step0=, partial=; csrc/kernels_plan_spec_resume.h).  Every
+ * argument of mobrob_ppo_spec_plan means what it means there, and the same checks are made; in addition
+ *   todo         [n]: bit j set = robot r still has to visit station j (the caller reads the monitor's carried state: a station is done
+ *                when the rho of its clause is > 0).  The tour table is filled for the subsets of todo[r] only -- enumerated, not filtered.
+ *   step0_ticks  t0 = ceil(5 * step0 / pace), the tick the plan starts at: t[{j}][j] = dep(j, t0 + d0[j]).  Windows, cost, tour_eta and
+ *                release stay absolute.
+ *   partial      0: the tour visits all of todo[r], or the status is 1 (with todo[r] == 0 the plan is the goal leg alone, cost t0 + its
+ *                ticks, and without a goal planned with count 0).  1: the visited set V, a subset of todo[r], and its last station j
+ *                are the lexicographic minimum of (popcount(todo) - popcount(V), t[V][j] + E[j], V, j) over the feasible entries, V = 0
+ *                an entry with the total t0 + the goal leg from the start and j = -1; status 1 only without any feasible entry.
+ *   outputs      tour_len_out [n] = |V| and dropped_out [n] = todo & ~V (0 and todo without a feasible entry); tour_order, tour_eta and
+ *                station_waypoint are -1 at the positions >= tour_len.
+ *   kernels      k_plan_tour_resume (a wave per robot; the submasks of todo sorted by level in LDS, the selection a wave-wide minimum)
+ *                and k_plan_tour_path_legs (16 lanes a robot, a lane a leg: count, prefix sum across the lanes, emit) in place of
+ *                k_plan_tour and k_plan_tour_path; everything before them as mobrob_ppo_spec_plan runs it.
+ * MOBROB_ERR_INVALID, outputs untouched, for everything mobrob_ppo_spec_plan refuses and for: todo, tour_len_out or dropped_out NULL;
+ * step0_ticks outside 0 .. MOBROB_PLAN_TOUR_TICKS_MAX; a todo with a bit at or above n_stations (or negative); partial not 0 / 1. */
+int mobrob_ppo_spec_replan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                           const mobrob_hazards_t* hazards /* or NULL */, const mobrob_spec_t* regions, int32_t n_stations,
+                           const int32_t* station_lo /* [M] */, const int32_t* station_hi /* [M] */, int32_t n_avoid,
+                           const int32_t* avoid_lo /* [n_avoid] or NULL */, const int32_t* avoid_hi /* [n_avoid] or NULL */,
+                           const int32_t* open_c /* [M] */, const int32_t* close_c /* [M] */, const int32_t* dwell_c /* [M] */, int32_t pace,
+                           const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] or NULL */,
+                           const int32_t* field_of /* [n], with a goal */, const int32_t* field_goal_cell /* [n_fields], with a goal */,
+                           const int32_t* field_scene /* [n_fields], with a goal */, const int32_t* todo /* [n] */, int32_t step0_ticks,
+                           int32_t partial, float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */,
+                           int32_t* count_out /* [n] */, int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */,
+                           int32_t* tour_order_out /* [n][M] */, int32_t* tour_eta_out /* [n][M] */,
+                           int32_t* station_waypoint_out /* [n][M] */, int32_t* release_out /* [n][K] */,
+                           int32_t* station_cell_out /* [S][M] */, float* station_margin_out /* [S][M] */,
+                           int32_t* matrix_out /* [S][M][M] */, uint8_t* occupancy_out /* [S][G][G] or NULL */,
+                           int32_t* sweeps_out /* [S * M + n_fields] or NULL */, int32_t* tour_len_out /* [n] */,
+                           int32_t* dropped_out /* [n] */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

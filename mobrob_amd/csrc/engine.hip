@@ -61,6 +61,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_spec_nested.h"
 #include "kernels_spec_moving.h"
 #include "kernels_plan_spec.h"
+#include "kernels_plan_spec_resume.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -5703,7 +5704,16 @@ int mobrob_ppo_spec_monitor_moving(mobrob_ppo_engine_t* e, const mobrob_spec_mov
 // k_plan_occupancy as it is (or a zeroed map), k_plan_region_occupancy, k_plan_station (which writes the anchors into the field list),
 // ONE k_plan_field launch for the S * M station fields and the goal fields, k_plan_tour_matrix, k_plan_tour, k_plan_tour_path.  It
 // works in a buffer of its own and keeps nothing resident: mobrob_ppo_plan_grid's resident fields stay valid across it.
-int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+// mobrob_ppo_spec_replan is the same call from the middle of a run (csrc/kernels_plan_spec_resume.h): the same checks, buffer, map,
+// stations, fields and matrix, then k_plan_tour_resume and k_plan_tour_path_legs in place of the last two.
+struct SpecReplan {
+  const int32_t* todo;     // [n]
+  int32_t t0, partial;
+  int32_t* tour_len_out;   // [n]
+  int32_t* dropped_out;    // [n]
+};
+
+static int spec_plan_run(const char* who, const SpecReplan* rp, mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
                          const mobrob_spec_t* regions, int32_t n_stations, const int32_t* station_lo, const int32_t* station_hi,
                          int32_t n_avoid, const int32_t* avoid_lo, const int32_t* avoid_hi, const int32_t* open_c, const int32_t* close_c,
                          const int32_t* dwell_c, int32_t pace, const float* start, const float* goal, const int32_t* field_of,
@@ -5711,7 +5721,6 @@ int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
                          int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* tour_order_out, int32_t* tour_eta_out,
                          int32_t* station_waypoint_out, int32_t* release_out, int32_t* station_cell_out, float* station_margin_out,
                          int32_t* matrix_out, uint8_t* occupancy_out, int32_t* sweeps_out) {
-  const char* who = "spec_plan";
   if (!e || !spec || !regions || !station_lo || !station_hi || !open_c || !close_c || !dwell_c || !start || !waypoints_out ||
       !n_waypoints_out || !count_out || !status_out || !cost_out || !tour_order_out || !tour_eta_out || !station_waypoint_out ||
       !release_out || !station_cell_out || !station_margin_out || !matrix_out)
@@ -5765,6 +5774,15 @@ int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
       if (!std::isfinite(start[k])) return fail(MOBROB_ERR_INVALID, "%s: start of robot %d is not finite", who, (int)(k / P));
   }
   if ((int64_t)N * K > INT_MAX || (int64_t)S * M * M > INT_MAX) return fail(MOBROB_ERR_INVALID, "%s: n_robots * max_waypoints must fit an int32", who);
+  if (rp) {
+    if (!rp->todo || !rp->tour_len_out || !rp->dropped_out) return fail(MOBROB_ERR_INVALID, "%s: null argument", who);
+    if (rp->t0 < 0 || rp->t0 > kPlanTourTicksMax)
+      return fail(MOBROB_ERR_INVALID, "%s: step0_ticks must lie in 0 .. %d, got %d", who, kPlanTourTicksMax, rp->t0);
+    if (rp->partial != 0 && rp->partial != 1) return fail(MOBROB_ERR_INVALID, "%s: partial must be 0 or 1, got %d", who, rp->partial);
+    for (int i = 0; i < N; ++i)
+      if (rp->todo[i] < 0 || rp->todo[i] >= (1 << M))
+        return fail(MOBROB_ERR_INVALID, "%s: todo of robot %d is 0x%x, a bit at or above n_stations = %d", who, i, (unsigned)rp->todo[i], M);
+  }
   const int cells = G * G, F = S * M + Fg;
   if ((uint64_t)((uint64_t)S * M + Fg) * (uint64_t)cells * 4u > MOBROB_PLAN_TIME_MAX_BYTES)
     return fail(MOBROB_ERR_INVALID, "%s: fields of (%d x %d + %d) x %d x %d x 4 bytes exceed the cap of %u bytes (256 MiB)", who, S, M, Fg, G, G,
@@ -5788,7 +5806,8 @@ int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
                o_matrix = call.add((size_t)S * M * M * 4), o_reg = call.add(std::max<size_t>((size_t)S * R * 16, 4)),
                o_kind = call.add(std::max<size_t>((size_t)S * R * 4, 4)), o_cnt = call.add((size_t)S * 4),
                o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
-               o_hz = call.add(std::max<size_t>((size_t)S * Mh * 3, 1) * 4), o_nhz = call.add((size_t)S * 4);
+               o_hz = call.add(std::max<size_t>((size_t)S * Mh * 3, 1) * 4), o_nhz = call.add((size_t)S * 4),
+               o_todo = call.add((size_t)N * 4), o_len = call.add((size_t)N * 4), o_drop = call.add((size_t)N * 4);   // a replan's
   if (const int rc = grow_plan_buf(e, e->plan_spec_buf, e->plan_spec_bytes, call.total)) return rc;
   const auto mine = [&](size_t off) { return e->plan_spec_buf + off; };
   const auto ints = [&](size_t off) { return reinterpret_cast<int*>(mine(off)); };
@@ -5855,7 +5874,13 @@ int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   ta.cell = ints(o_cell); ta.matrix = ints(o_matrix); ta.field = ints(o_field); ta.sweeps = ints(o_sweeps);
   for (int j = 0; j < M; ++j) { ta.open_c[j] = open_c[j]; ta.close_c[j] = close_c[j]; ta.dwell_c[j] = dwell_c[j]; }
   ta.status = ints(o_status); ta.cost = ints(o_cost); ta.order = ints(o_order); ta.eta = ints(o_eta); ta.depart = ints(o_depart);
-  hipLaunchKernelGGL(k_plan_tour, dim3(N), dim3(64), 0, e->stream, ta);   // a wave per robot
+  if (rp) {
+    HIPC(hipMemcpyAsync(mine(o_todo), rp->todo, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+    const PlanTourResumeArgs ra{ta, ints(o_todo), rp->t0, rp->partial, ints(o_len), ints(o_drop)};
+    hipLaunchKernelGGL(k_plan_tour_resume, dim3(N), dim3(64), 0, e->stream, ra);   // a wave per robot
+  } else {
+    hipLaunchKernelGGL(k_plan_tour, dim3(N), dim3(64), 0, e->stream, ta);   // a wave per robot
+  }
   PlanTourPathArgs pa{};
   pa.g = grid; pa.N = N; pa.K = K; pa.P = P; pa.M = M; pa.S = S; pa.has_goal = ta.has_goal; pa.pace = pace;
   pa.start = ta.start; pa.goal = goal ? floats(o_goal) : nullptr; pa.scene = ta.scene; pa.field_of = ta.field_of;
@@ -5865,8 +5890,17 @@ int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   HIPC(hipMemsetAsync(pa.wp, 0, (size_t)N * K * P * 4, e->stream));
   HIPC(hipMemsetAsync(pa.release, 0, (size_t)N * K * 4, e->stream));
   HIPC(hipMemsetAsync(pa.swp, 0xFF, (size_t)N * M * 4, e->stream));   // -1: no anchor waypoint
-  hipLaunchKernelGGL(k_plan_tour_path, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, pa);
+  if (rp) {
+    const PlanTourPathLegsArgs la{pa, ints(o_len)};
+    hipLaunchKernelGGL(k_plan_tour_path_legs, dim3(cdiv(N, 256 / kPlanLegLanes)), dim3(256), 0, e->stream, la);   // 16 lanes a robot
+  } else {
+    hipLaunchKernelGGL(k_plan_tour_path, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, pa);
+  }
   HIPC(hipGetLastError());
+  if (rp) {
+    HIPC(hipMemcpyAsync(rp->tour_len_out, ints(o_len), (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipMemcpyAsync(rp->dropped_out, ints(o_drop), (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  }
   HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(count_out, pa.count, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
@@ -5883,6 +5917,36 @@ int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec,
   if (sweeps_out) HIPC(hipMemcpyAsync(sweeps_out, ints(o_sweeps), (size_t)F * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipStreamSynchronize(e->stream));
   return MOBROB_OK;
+}
+
+int mobrob_ppo_spec_plan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                         const mobrob_spec_t* regions, int32_t n_stations, const int32_t* station_lo, const int32_t* station_hi,
+                         int32_t n_avoid, const int32_t* avoid_lo, const int32_t* avoid_hi, const int32_t* open_c, const int32_t* close_c,
+                         const int32_t* dwell_c, int32_t pace, const float* start, const float* goal, const int32_t* field_of,
+                         const int32_t* field_goal_cell, const int32_t* field_scene, float* waypoints_out, int32_t* n_waypoints_out,
+                         int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* tour_order_out, int32_t* tour_eta_out,
+                         int32_t* station_waypoint_out, int32_t* release_out, int32_t* station_cell_out, float* station_margin_out,
+                         int32_t* matrix_out, uint8_t* occupancy_out, int32_t* sweeps_out) {
+  return spec_plan_run("spec_plan", nullptr, e, spec, walls, hz, regions, n_stations, station_lo, station_hi, n_avoid, avoid_lo, avoid_hi, open_c,
+                       close_c, dwell_c, pace, start, goal, field_of, field_goal_cell, field_scene, waypoints_out, n_waypoints_out, count_out,
+                       status_out, cost_out, tour_order_out, tour_eta_out, station_waypoint_out, release_out, station_cell_out,
+                       station_margin_out, matrix_out, occupancy_out, sweeps_out);
+}
+
+int mobrob_ppo_spec_replan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                           const mobrob_spec_t* regions, int32_t n_stations, const int32_t* station_lo, const int32_t* station_hi,
+                           int32_t n_avoid, const int32_t* avoid_lo, const int32_t* avoid_hi, const int32_t* open_c, const int32_t* close_c,
+                           const int32_t* dwell_c, int32_t pace, const float* start, const float* goal, const int32_t* field_of,
+                           const int32_t* field_goal_cell, const int32_t* field_scene, const int32_t* todo, int32_t step0_ticks,
+                           int32_t partial, float* waypoints_out, int32_t* n_waypoints_out, int32_t* count_out, int32_t* status_out,
+                           int32_t* cost_out, int32_t* tour_order_out, int32_t* tour_eta_out, int32_t* station_waypoint_out,
+                           int32_t* release_out, int32_t* station_cell_out, float* station_margin_out, int32_t* matrix_out,
+                           uint8_t* occupancy_out, int32_t* sweeps_out, int32_t* tour_len_out, int32_t* dropped_out) {
+  const SpecReplan rp{todo, step0_ticks, partial, tour_len_out, dropped_out};
+  return spec_plan_run("spec_replan", &rp, e, spec, walls, hz, regions, n_stations, station_lo, station_hi, n_avoid, avoid_lo, avoid_hi, open_c,
+                       close_c, dwell_c, pace, start, goal, field_of, field_goal_cell, field_scene, waypoints_out, n_waypoints_out, count_out,
+                       status_out, cost_out, tour_order_out, tour_eta_out, station_waypoint_out, release_out, station_cell_out,
+                       station_margin_out, matrix_out, occupancy_out, sweeps_out);
 }
 
 // ---- buffers ----------------------------------------------------------------------------------------

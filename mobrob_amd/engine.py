@@ -1262,17 +1262,24 @@ class PPOEngine:
             out["assign_matrix"] = matrix
         return out
 
-    def plan_spec(self, grid, walls=None, hazards=None, *, spec, start, goal=None, pace=None, max_waypoints=16, want_occupancy=False):
+    def plan_spec(self, grid, walls=None, hazards=None, *, spec, start, goal=None, pace=None, max_waypoints=16, want_occupancy=False,
+                  state=None, step0=0, partial=False):
         """A plan from a specification on the device (mobrob_ppo_spec_plan; the rule: goal_rules.spec_plan, reproduced bit for bit):
         the avoid clauses of `spec` become obstacles, its reach clauses stations, and per robot the order of the stations and the
         stitched waypoints are computed in one call.  grid: a goal_rules.GridSpec; walls / hazards: static, or None; spec: a
         goal_rules.Spec of the plannable fragment (spec_plan_parse); start [n][P]; goal [n][P] or None; pace: spec_plan_pace's.
         Returns spec_plan's dict (occupancy only with want_occupancy) and `sweeps`, the relaxation sweeps of each field.  Nothing
-        stays resident and plan_grid's resident fields stay valid."""
+        stays resident and plan_grid's resident fields stay valid.
+        state (a goal_rules.SpecState), step0, partial: the plan from the middle of a run, spec_plan's keywords.  With all three at
+        their defaults the call is mobrob_ppo_spec_plan; otherwise mobrob_ppo_spec_replan (k_plan_tour_resume,
+        k_plan_tour_path_legs), with todo made here from the state.  Either way the dict holds SPEC_REPLAN_KEYS and t0."""
         from ._lib import PlanSpec, SpecC, WallsC
         from .envs import goal_rules as R
+        raw_pace = pace
         avoid, stations, (open_c, close_c, dwell_c), S, scene, start, goal, K, pace = R.spec_plan_check(grid, walls, hazards, spec, start,
                                                                                                      goal, max_waypoints, pace)
+        done, todo, t0 = R.spec_plan_resume_check(spec, start.shape[0], None if raw_pace is None else pace, state, step0, partial)
+        resume = state is not None or step0 != 0 or bool(partial)
         reg = spec.regions
         n, P = start.shape
         G, M = grid.cells, len(stations)
@@ -1308,16 +1315,23 @@ class PPOEngine:
         cell, margin, matrix = np.zeros((S, M), np.int32), np.zeros((S, M), F32), np.zeros((S, M, M), np.int32)
         occ = np.zeros((S, G, G), np.uint8) if want_occupancy else None
         sweeps = np.zeros(S * M + Fg, np.int32)
-        check(self.lib.mobrob_ppo_spec_plan(
-            self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None else C.byref(h), C.byref(rg), M, ip(st_lo),
-            ip(st_hi), len(avoid), ip(av_lo) if avoid else None, ip(av_hi) if avoid else None, ip(open_c), ip(close_c), ip(dwell_c), pace,
-            _fp(start), None if goal is None else _fp(goal), None if goal is None else ip(field_of), None if goal is None else ip(fcell),
-            None if goal is None else ip(fscene), _fp(wp), ip(nwp), ip(count), ip(status), ip(cost), ip(order), ip(eta), ip(swp),
-            ip(release), ip(cell), _fp(margin), ip(matrix), None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), ip(sweeps)))
+        ins = (self._h, C.byref(sp), None if wl is None else C.byref(wl), None if h is None else C.byref(h), C.byref(rg), M, ip(st_lo),
+               ip(st_hi), len(avoid), ip(av_lo) if avoid else None, ip(av_hi) if avoid else None, ip(open_c), ip(close_c), ip(dwell_c), pace,
+               _fp(start), None if goal is None else _fp(goal), None if goal is None else ip(field_of), None if goal is None else ip(fcell),
+               None if goal is None else ip(fscene))
+        outs = (_fp(wp), ip(nwp), ip(count), ip(status), ip(cost), ip(order), ip(eta), ip(swp), ip(release), ip(cell), _fp(margin),
+                ip(matrix), None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), ip(sweeps))
+        if resume:
+            todo = np.ascontiguousarray(todo, np.int32)
+            tour_len, dropped = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            check(self.lib.mobrob_ppo_spec_replan(*ins, ip(todo), t0, int(bool(partial)), *outs, ip(tour_len), ip(dropped)))
+        else:
+            check(self.lib.mobrob_ppo_spec_plan(*ins, *outs))
+            tour_len, dropped = np.where(order[:, 0] >= 0, M, 0).astype(np.int32), np.where(order[:, 0] >= 0, 0, todo).astype(np.int32)
         out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "tour_order": order, "tour_eta": eta,
                "station_waypoint": swp, "release": release, "station_cell": cell, "station_margin": margin,
                "covered": margin >= np.float32(R.REACH_RADIUS), "matrix": matrix, "open_c": open_c, "close_c": close_c, "dwell_c": dwell_c,
-               "pace": pace, "sweeps": sweeps}
+               "pace": pace, "sweeps": sweeps, "tour_len": tour_len, "dropped": dropped, "done": done, "t0": t0}
         if occ is not None:
             out["occupancy"] = occ.astype(bool)
         return out

@@ -2996,9 +2996,10 @@ def spec_result(state, spec):
 # ---- a plan from a specification: avoid clauses become obstacles, reach clauses stations; per robot the order of
 # the stations (Held-Karp over the stations' own cost-to-go fields, with windows and dwell) and the stitched waypoints.  This
 # project's own rule, all integers except the two margin tests; the device (csrc/kernels_plan_spec.h: k_plan_region_occupancy,
-# k_plan_station, k_plan_tour_matrix, k_plan_tour, k_plan_tour_path, with k_plan_occupancy and k_plan_field as they are) is held to
-# it bit for bit.  NOT planned: smoothing of the legs, teams, moving hazards or regions, precedence (until), recurring visits,
-# re-ordering during a run, more than PLAN_TOUR_STATIONS_MAX stations.
+# k_plan_station, k_plan_tour_matrix, k_plan_tour, k_plan_tour_path, with k_plan_occupancy and k_plan_field as they are; from the
+# middle of a run csrc/kernels_plan_spec_resume.h: k_plan_tour_resume, k_plan_tour_path_legs) is held to it bit for bit.  NOT planned:
+# smoothing of the legs, teams, moving hazards or regions, precedence (until), recurring visits, credit for a dwell in progress, more
+# than PLAN_TOUR_STATIONS_MAX stations.
 PLAN_TOUR_STATIONS_MAX = 8          # 256 subsets of stations: the tour table of one robot fits a wave's LDS
 PLAN_TOUR_TICKS_MAX = 1 << 24       # every open, close and dwell in ticks is clamped here: 8 legs of them stay below 2^30
 PLAN_TOUR_INF = 0x3FFFFFFF          # "no feasible way" in the tour table
@@ -3173,8 +3174,26 @@ def spec_plan_tour(d0, D, E, open_c, close_c, dwell_c):
     -> (feasible bool [n], cost int64 [n], order int32 [n][M], eta int64 [n][M] (ticks on arrival, before max with open_c), depart
     int64 [n][M]); order, eta, depart are -1 and cost -1 where no feasible tour exists."""
     n, M = d0.shape
+    return spec_plan_tour_resume(d0, D, E, np.zeros(n, np.int64), open_c, close_c, dwell_c, np.full(n, (1 << M) - 1, np.int64), 0, False)[:5]
+
+
+def spec_plan_tour_resume(d0, D, E, e0, open_c, close_c, dwell_c, todo, t0, partial):
+    """spec_plan_tour from the middle of a run: the one statement of the order rule (spec_plan_tour is this with every station to
+    do, t0 = 0 and partial off).  todo int [n]: the bit set of the stations robot r still has to visit; t0: the tick the plan starts
+    at; e0 int64 [n]: the start to the goal (0 without a goal, PLAN_ASSIGN_NONE: no path).  The table is filled for the masks that
+    are subsets of todo[r] only: t[{j}][j] = dep(j, t0 + d0[j]), the recurrence and dep as in spec_plan_tour.
+    partial off: the tour visits all of todo[r] and ends at the j of todo[r] minimising (t[todo][j] + E[j], j); with todo[r] == 0
+    there is no station leg and the total is t0 + e0 (feasible iff e0 is a real cost).
+    partial on: the visited set V, a subset of todo[r], and its last station j are the lexicographic minimum of (popcount(todo) -
+    popcount(V), t[V][j] + E[j], V as an integer, j) over the feasible entries; V = 0 is an entry with the total t0 + e0 and j = -1.
+    -> (feasible bool [n], cost int64 [n], order int32 [n][M], eta int64 [n][M], depart int64 [n][M], tour_len int32 [n] = |V|,
+    dropped int32 [n] = todo & ~V); order, eta and depart are -1 at the positions >= tour_len; without a feasible entry cost is
+    -1, tour_len 0 and dropped is todo."""
+    n, M = d0.shape
     INF, NONE = PLAN_TOUR_INF, PLAN_ASSIGN_NONE
     full = (1 << M) - 1
+    todo = np.asarray(todo, np.int64)
+    t0 = int(t0)
     t = np.full((n, 1 << M, M), INF, np.int64)
     pred = np.full((n, 1 << M, M), -1, np.int8)
 
@@ -3182,40 +3201,108 @@ def spec_plan_tour(d0, D, E, open_c, close_c, dwell_c):
         begin = np.maximum(arr, open_c[j])
         return np.where(ok & (begin <= close_c[j]), begin + dwell_c[j], INF)
     for mask in range(1, full + 1):
+        sub = (mask & ~todo) == 0                                # the robots whose todo holds this mask
+        if not sub.any():
+            continue
         for j in range(M):
             if not mask >> j & 1:
                 continue
             rest = mask ^ (1 << j)
             if rest == 0:
-                t[:, mask, j] = dep(j, d0[:, j], d0[:, j] < NONE)
+                t[:, mask, j] = dep(j, t0 + d0[:, j], sub & (d0[:, j] < NONE))
                 continue
             best, via = np.full(n, INF, np.int64), np.full(n, -1, np.int8)
             for i in range(M):                                   # ascending: strict < keeps the lowest i of equal values
                 if not rest >> i & 1:
                     continue
-                val = dep(j, t[:, rest, i] + D[:, i, j], (t[:, rest, i] < INF) & (D[:, i, j] < NONE))
+                val = dep(j, t[:, rest, i] + D[:, i, j], sub & (t[:, rest, i] < INF) & (D[:, i, j] < NONE))
                 take = val < best
                 best, via = np.where(take, val, best), np.where(take, i, via).astype(np.int8)
             t[:, mask, j], pred[:, mask, j] = best, via
-    cost, last = np.full(n, INF, np.int64), np.full(n, -1, np.int64)
-    for j in range(M):
-        tot = np.where((t[:, full, j] < INF) & (E[:, j] < NONE), t[:, full, j] + E[:, j], INF)
-        take = tot < cost
-        cost, last = np.where(take, tot, cost), np.where(take, j, last)
-    ok = cost < INF
+    # the selection: a strict lexicographic < over ascending (V, j) keeps the lowest (V, j) of equal (left out, total)
+    rows = np.arange(n)
+    left = np.full(n, M + 1, np.int64)                           # stations of todo left out; M + 1: no entry yet
+    cost, visit, last = np.full(n, INF, np.int64), np.zeros(n, np.int64), np.full(n, -1, np.int64)
+    have = np.array([bin(int(v)).count("1") for v in todo], np.int64)
+    empty = (e0 < NONE) & ((todo == 0) | bool(partial))         # V = 0: the goal leg alone (the first entry: V = 0 is the lowest)
+    left, cost = np.where(empty, have, left), np.where(empty, t0 + e0, cost)
+    for mask in range(1, full + 1):
+        cand = ((mask & ~todo) == 0) if partial else (todo == mask)
+        if not cand.any():
+            continue
+        out = have - bin(mask).count("1")
+        for j in range(M):
+            if not mask >> j & 1:
+                continue
+            ok = cand & (t[:, mask, j] < INF) & (E[:, j] < NONE)
+            tot = np.where(ok, t[:, mask, j] + E[:, j], INF)
+            take = ok & ((out < left) | ((out == left) & (tot < cost)))
+            left, cost = np.where(take, out, left), np.where(take, tot, cost)
+            visit, last = np.where(take, mask, visit), np.where(take, j, last)
+    ok = left <= M
     order, eta, depart = np.full((n, M), -1, np.int32), np.full((n, M), -1, np.int64), np.full((n, M), -1, np.int64)
-    for r in np.nonzero(ok)[0]:
-        mask, j = full, int(last[r])
-        for k in range(M - 1, -1, -1):
+    tour_len = np.where(ok, np.array([bin(int(v)).count("1") for v in visit], np.int64), 0).astype(np.int32)
+    for r in rows[ok]:
+        mask, j = int(visit[r]), int(last[r])
+        for k in range(int(tour_len[r]) - 1, -1, -1):
             order[r, k] = j
             depart[r, k] = t[r, mask, j]
             i = int(pred[r, mask, j])
-            eta[r, k] = d0[r, j] if i < 0 else t[r, mask ^ (1 << j), i] + D[r, i, j]
+            eta[r, k] = t0 + d0[r, j] if i < 0 else t[r, mask ^ (1 << j), i] + D[r, i, j]
             mask, j = mask ^ (1 << j), i
-    return ok, np.where(ok, cost, -1), order, eta, depart
+    dropped = (todo & ~np.where(ok, visit, 0)).astype(np.int32)
+    return ok, np.where(ok, cost, -1), order, eta, depart, tour_len, dropped
 
 
-def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None):
+SPEC_REPLAN_KEYS = ("tour_len", "dropped", "done")
+
+
+def spec_plan_clauses(spec):
+    """-> int [M]: the clause index of each station, in the clause order spec_plan_parse numbers the stations in"""
+    spec_plan_parse(spec)
+    return np.array([c for c, cl in enumerate(spec.clauses) if cl[0] != SPEC_ALWAYS], np.int64)
+
+
+def spec_plan_done(spec, state):
+    """-> bool [n][M]: station j is done for robot r iff state.val[r, clause_j, 0] > 0 -- spec_result's strict rule: a margin of
+    exactly 0 (either sign) is not done.  state: a SpecState of this specification (spec_check_state).
+    Limit: the carried tail of a stay clause, a dwell in progress, is deliberately not read: a robot interrupted in a dwell dwells
+    again in full."""
+    clauses = spec_plan_clauses(spec)
+    if not isinstance(state, SpecState):
+        raise TypeError(f"a specification's state must be a SpecState (spec_start), not {type(state).__name__}")
+    spec_check_state(state, state.val.shape[0], spec)
+    # rho > 0 read off the float32 bits (0 < bits <= those of +inf): the smallest denormal is done even in a process whose float
+    # unit has been put into flush-to-zero mode by a library built for fast math
+    b = np.ascontiguousarray(state.val[:, clauses, 0]).view(np.int32)
+    return (b > 0) & (b <= np.int32(0x7F800000))
+
+
+def spec_plan_resume_check(spec, n, pace, state, step0, partial):
+    """The refusals of spec_plan's state=, step0= and partial=, by name -> (done bool [n][M], todo int32 [n], t0).  `pace` is the
+    checked pace with the caller's None kept (spec_plan_pace's 1 is a pace nobody stated).  t0 = ceil(PLAN_STEP * step0 / pace)
+    must not exceed PLAN_TOUR_TICKS_MAX: a time in the table is then at most the larger of t0 and an opening, plus 8 dwells and 9
+    legs below PLAN_ASSIGN_NONE each -- under 2^24 + 8 * 2^24 + 9 * 2^21 < 2^28, far below 2^30 as before."""
+    M = len(spec_plan_clauses(spec))
+    if isinstance(step0, bool) or not isinstance(step0, (int, np.integer)) or step0 < 0:
+        raise ValueError(f"spec_plan: step0 must be an integer >= 0, got {step0!r}")
+    if not isinstance(partial, (bool, np.bool_)):
+        raise ValueError(f"spec_plan: partial must be True or False, got {partial!r}")
+    if step0 != 0 and pace is None:
+        raise ValueError("spec_plan: pace= is required with a nonzero step0 (the start tick is ceil(PLAN_STEP * step0 / pace))")
+    t0 = 0 if step0 == 0 else -((-PLAN_STEP * int(step0)) // int(pace))
+    if t0 > PLAN_TOUR_TICKS_MAX:
+        raise ValueError(f"spec_plan: step0 = {step0} at pace {pace} starts at tick {t0}, above PLAN_TOUR_TICKS_MAX = {PLAN_TOUR_TICKS_MAX}")
+    if state is None:
+        done = np.zeros((n, M), bool)
+    else:
+        spec_check_state(state, n, spec)
+        done = spec_plan_done(spec, state)
+    todo = ((~done).astype(np.int64) << np.arange(M)).sum(axis=1).astype(np.int32)
+    return done, todo, t0
+
+
+def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None, *, state=None, step0=0, partial=False):
     """The plan of n robots from a specification (DESIGN 4.12.9) -> dict.  grid: a GridSpec; walls / hazards: static, or None;
     spec: a Spec of the plannable fragment (spec_plan_parse); start [n][P]; goal [n][P] or None: where every robot ends after its
     last station; K waypoint slots; pace: the steps a robot is given for one orthogonal move (spec_plan_pace).
@@ -3238,10 +3325,24 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None):
     Schedule(release), which holds the robot at the station until then --, and station_cell, station_margin, covered, matrix,
     occupancy, open_c, close_c, dwell_c, pace.
 
+    From the middle of a run (state=, step0=, partial=; the outputs SPEC_REPLAN_KEYS).  state: the monitor's SpecState; done
+    bool [n][M] = spec_plan_done, and todo[r] is the set of stations not done (all of them without a state): the tour of robot r
+    is over todo[r] only, and a missing anchor matters only for a station of todo[r].  step0: the global step the robots stand at;
+    the plan starts at tick t0 = ceil(PLAN_STEP * step0 / pace) (at most PLAN_TOUR_TICKS_MAX; pace is then required), and windows,
+    cost, tour_eta and release stay absolute: ticks and global steps of the run.  partial: off, every station of todo[r] is visited
+    or the robot is UNREACHABLE; on, the largest feasible subset V is (spec_plan_tour_resume) -- a station without an anchor or
+    whose window has closed is dropped -- and only no feasible entry at all, not even the goal leg, is UNREACHABLE.  tour_len int32
+    [n] = |V|, dropped int32 [n] = the bit set todo & ~V; tour_order, tour_eta and station_waypoint are -1 at the positions >=
+    tour_len.  With todo[r] == 0 the plan is the goal leg alone, cost t0 + its ticks; without a goal it is PLANNED with count 0.
+    The waypoints and releases are stitched over the tour_len legs and the goal leg by the one loop below.
+
     Limitations: pace is an estimate of the policy's speed; a robot that arrives later than planned dwells for less time (the
-    release is a global step, not a duration); the monitor after the run remains the judge."""
+    release is a global step, not a duration); a dwell in progress earns no credit (spec_plan_done); the monitor after the run
+    remains the judge."""
+    raw_pace = pace
     avoid, stations, (open_c, close_c, dwell_c), S, scene, start, goal, K, pace = spec_plan_check(grid, walls, hazards, spec, start,
                                                                                                  goal, K, pace)
+    done, todo, t0 = spec_plan_resume_check(spec, start.shape[0], None if raw_pace is None else pace, state, step0, partial)
     reg = spec.regions
     n, P = start.shape
     G, M = grid.cells, len(stations)
@@ -3264,11 +3365,12 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None):
         field_of, fcell, fscene = plan_fields(grid, None, scene, goal)
         gfields = [grid_field(occ[fscene[f]], fcell[f]).reshape(-1) for f in range(len(fcell))]
         E = real(np.array([[gfields[field_of[r]][cell[sc[r], i]] if cell[sc[r], i] >= 0 else -1 for i in range(M)] for r in range(n)]))
+        e0 = real(np.array([gfields[field_of[r]][scell[r]] for r in range(n)]))
     else:
-        E = np.zeros((n, M), np.int64)
-    anchored = np.all(cell[sc] >= 0, axis=1)
-    d0[~anchored] = NONE
-    ok, cost, order, eta, depart = spec_plan_tour(d0, D, E, open_c.astype(np.int64), close_c.astype(np.int64), dwell_c.astype(np.int64))
+        E, e0 = np.zeros((n, M), np.int64), np.zeros(n, np.int64)
+    # a station without an anchor has a field of -1 everywhere: nothing reaches it or leaves it, so a tour that holds it is infeasible
+    ok, cost, order, eta, depart, tour_len, dropped = spec_plan_tour_resume(
+        d0, D, E, e0, open_c.astype(np.int64), close_c.astype(np.int64), dwell_c.astype(np.int64), todo, t0, bool(partial))
     wp, release = np.zeros((n, K, P), np.float32), np.zeros((n, K), np.int32)
     count, status = np.zeros(n, np.int32), np.full(n, UNREACHABLE, np.int32)
     swp = np.full((n, M), -1, np.int32)
@@ -3282,7 +3384,7 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None):
         def emit(xy, cnt=None):
             if cnt < K:
                 wp[r, cnt, :2], wp[r, cnt, 2:] = xy, z[r]
-        legs = [(int(cell[s, j]), fields[s][j]) for j in order[r]] + ([] if goal is None else [(None, gfields[field_of[r]])])
+        legs = [(int(cell[s, j]), fields[s][j]) for j in order[r, :tour_len[r]]] + ([] if goal is None else [(None, gfields[field_of[r]])])
         for k, (target, field) in enumerate(legs):
             to = int(fcell[field_of[r]]) if target is None else target
             cells, dirs, st = grid_walk_cells(field.reshape(G, G), occ[s], (cur % G, cur // G), (to % G, to // G))
@@ -3305,4 +3407,5 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None):
     return {"waypoints": wp, "n_waypoints": np.minimum(count, K).astype(np.int32), "count": count, "status": status,
             "cost": cost.astype(np.int32), "tour_order": order, "tour_eta": eta.astype(np.int32), "station_waypoint": swp,
             "release": release, "station_cell": cell, "station_margin": margin, "covered": margin >= np.float32(REACH_RADIUS),
-            "matrix": matrix, "occupancy": occ, "open_c": open_c, "close_c": close_c, "dwell_c": dwell_c, "pace": pace}
+            "matrix": matrix, "occupancy": occ, "open_c": open_c, "close_c": close_c, "dwell_c": dwell_c, "pace": pace,
+            "tour_len": tour_len, "dropped": dropped, "done": done, "t0": t0}

@@ -358,7 +358,7 @@ class GridPlanner:
             res["sweeps"] = out["sweeps"]
         return res
 
-    def plan_spec(self, start, spec, goal=None, pace=None, max_waypoints=None):
+    def plan_spec(self, start, spec, goal=None, pace=None, max_waypoints=None, *, state=None, step0=0, partial=False):
         """A plan from a specification: the avoid clauses of `spec` (Spec.always(outside(...)) over the whole run)
         become obstacles beside the planner's walls and hazards, its reach clauses (Spec.eventually / Spec.stay over inside(...),
         at most 8) stations, and per robot the order of the stations is chosen -- the shortest tour that keeps every window and
@@ -372,7 +372,19 @@ class GridPlanner:
         Refused by name: a planner with teams=, moving hazards, clearance= or smooth= (legs are not smoothed, teams and moving
         hazards are not planned from a specification), and everything goal_rules.spec_plan_parse refuses of the specification.
         pace is an estimate of the policy's speed: a robot that arrives later than planned dwells for less time, and the monitor
-        after the run remains the judge."""
+        after the run remains the judge.
+        From the middle of a run (goal_rules.spec_plan's state=, step0=, partial=; device: mobrob_ppo_spec_replan): state is the
+        monitor's SpecState, or the run's FollowState, whose .spec and .step0 are then taken (a step0= that disagrees is refused,
+        as is a FollowState of a run without a specification); the stations whose clause is already satisfied are left out, the
+        plan starts at step0, and with partial=True a robot keeps the stations it can still keep.  The dict then also holds
+        tour_len, dropped and done (SPEC_REPLAN_KEYS).  A dwell in progress earns no credit: the robot dwells again in full."""
+        from .waypoints import FollowState
+        if isinstance(state, FollowState):
+            if state.spec is None:
+                raise ValueError("plan_spec: state is a FollowState of a run without a specification (follow_waypoints(..., spec=))")
+            if step0 not in (0, state.step0):
+                raise ValueError(f"plan_spec: step0 = {step0} disagrees with the FollowState's step0 = {state.step0}")
+            state, step0 = state.spec, int(state.step0)
         for what, on in (("teams=", self.teams is not None), ("hazards=MovingHazards", isinstance(self.hazards, rules.MovingHazards)),
                          ("clearance=", self.clearance is not None), ("smooth=", self.smooth), ("time_smooth=", self.time_smooth)):
             if on:
@@ -383,11 +395,42 @@ class GridPlanner:
         if start.ndim != 2 or start.shape[1] != self.pos_dim:
             raise ValueError(f"plan_spec: start must be [n_robots, {self.pos_dim}], got shape {start.shape}")
         if self.device:
-            out = self.engine.plan_spec(self.spec, self.walls, self.hazards, spec=spec, start=start, goal=goal, pace=pace, max_waypoints=K)
+            out = self.engine.plan_spec(self.spec, self.walls, self.hazards, spec=spec, start=start, goal=goal, pace=pace, max_waypoints=K,
+                                        state=state, step0=step0, partial=partial)
         else:
-            out = rules.spec_plan(self.spec, self.walls, self.hazards, spec, start, goal, K, pace)
+            out = rules.spec_plan(self.spec, self.walls, self.hazards, spec, start, goal, K, pace, state=state, step0=step0, partial=partial)
         out["schedule"] = rules.Schedule(out["release"], home=start) if np.any(out["release"] != 0) else None
         return out
+
+    def spec_callback(self, spec, goal=None, pace=None, partial=True, when="stalled"):
+        """The planner of waypoints.follow_with_replanning for a run that follows a plan from a specification: its attribute
+        `wants_state` is True, so the loop calls it as planner(positions, status, reached, state=the run's FollowState), and it
+        plans again with plan_spec(positions, spec, goal, pace, state=state, partial=partial): the stations the monitor has seen
+        satisfied are left out and the plan starts at the run's step.  when="stalled": the STALLED robots are replanned;
+        when="all": every robot that is not FINISHED.  A chosen robot whose new plan is PLANNED with count > 0 gets
+        (waypoints[:count], release[:count]) -- so the run needs a schedule from its first call --; the others are left alone.
+        `callback.last` holds the latest plan (None before the first, and after a call without a robot to replan the plan of the
+        call before), `callback.calls` counts the calls.  The monitor is read, never written."""
+        from .waypoints import FINISHED, STALLED
+        if when not in ("stalled", "all"):
+            raise ValueError(f"spec_callback: when must be 'stalled' or 'all', got {when!r}")
+        rules.spec_plan_parse(spec)
+
+        def planner(positions, status, reached, state=None):
+            planner.calls += 1
+            if state is None:
+                raise ValueError("spec_callback: the planner needs the run's state (follow_with_replanning hands it to a planner "
+                                 "whose wants_state is true)")
+            status = np.asarray(status)
+            chosen = np.nonzero(status == STALLED if when == "stalled" else status != FINISHED)[0]
+            if chosen.size == 0:
+                return {}
+            plan = self.plan_spec(positions, spec, goal=goal, pace=pace, state=state, partial=partial)
+            planner.last = plan
+            return {int(i): (plan["waypoints"][i, :plan["count"][i]].copy(), plan["release"][i, :plan["count"][i]].copy())
+                    for i in chosen if plan["status"][i] == rules.PLANNED and plan["count"][i] > 0}
+        planner.last, planner.calls, planner.wants_state = None, 0, True
+        return planner
 
     def callback(self, goal, horizon=None):
         """The `planner(positions, status, reached)` of waypoints.follow_with_replanning for the goals `goal` [n][P]: every

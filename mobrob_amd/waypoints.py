@@ -689,7 +689,11 @@ def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, ro
     goal_rules.Teams; the planner callback is unchanged (the team sums are in the returned dict and in its `state`).  schedule: a
     goal_rules.Schedule; a planner that returns {robot: (waypoints, release)} gives the new waypoints release steps (global).
     walls: a goal_rules.Walls; replanning leaves the wall record alone.  spec: a goal_rules.Spec -- the run is monitored round
-    after round (needs path_stride=1; `path` is then the last round's) and replanning leaves the monitor alone."""
+    after round (needs path_stride=1; `path` is then the last round's) and replanning leaves the monitor alone: a planner whose
+    attribute `wants_state` is true (GridPlanner.spec_callback) is called as planner(positions, status, reached, state=the run's
+    FollowState) and may READ the monitor's carried state (state.spec, state.step0) to leave out what is already achieved; nothing
+    writes it.  Every other planner is called as before.  When such a planner returns releases the run needs a schedule from its
+    first call (schedule=): a ValueError naming it where there is none."""
     horizon, rounds = int(horizon), int(rounds)
     if spec is not None:
         _spec_check_call(spec, path_stride, None)
@@ -705,8 +709,16 @@ def follow_with_replanning(model, env, start, waypoints, planner, *, horizon, ro
         statuses.append(out["status"].copy())
         if r + 1 == rounds:
             break
-        plan = planner(np.array(state.positions), out["status"].copy(), out["reached"].copy()) or {}
+        if getattr(planner, "wants_state", False):
+            plan = planner(np.array(state.positions), out["status"].copy(), out["reached"].copy(), state=state) or {}
+            if schedule is None and any(isinstance(w, tuple) and np.any(np.asarray(w[1]) != 0) for w in plan.values()):
+                raise ValueError("follow_with_replanning: the planner returned release steps but the run has no schedule; pass "
+                                 "schedule= (a goal_rules.Schedule, e.g. the first plan's or Schedule(zeros)) from the first call")
+        else:
+            plan = planner(np.array(state.positions), out["status"].copy(), out["reached"].copy()) or {}
         for robot, w in plan.items():
+            if schedule is None and isinstance(w, tuple) and getattr(planner, "wants_state", False):
+                w = w[0]                                             # releases all zero: released at once, as without a schedule
             if schedule is not None and isinstance(w, tuple):
                 state.replan([int(robot)], np.asarray(w[0], np.float64)[None], release=np.asarray(w[1])[None])
             else:
