@@ -72,6 +72,9 @@ plan's schedule, the monitor then judges it.  It excludes --hazard-frames, --tea
 `--replan-spec` (with --plan-spec, --horizon and --leg-steps) plans a stalled robot again between the calls of the run, from where it
 stands and at the run's step, for the stations the monitor has not seen satisfied yet (GridPlanner.spec_callback); `--partial` lets
 a robot that cannot keep every window keep the stations it still can, in the first plan and in every later one.
+`--share N [--share-objective sum]` (with --plan-spec; it excludes --team-size) shares the stations within teams of N consecutive
+robots: each station is visited by one member (plan_spec(share=N): the team done as early as possible, or with the least total), the
+others get no tour, and after the run the team's verdict is printed beside the robots' (waypoints.spec_team_result: someone reached).
 """
 import argparse
 import os
@@ -103,7 +106,14 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
            plan_smooth=False, plan_los_margin=1, plan_layer_steps=10, plan_layers=64, plan_reserve=None, plan_time_smooth=False, plan_max_leg=None,
            plan_retries=0, goals=None, assign=None, plan_clearance=None, solid=False, tile256=False,
            tile256_wide=False, team_solid=False, check_spec=False, spec_hold=0, plan_spec=False, pace=None,
-           replan_spec=False, partial=False):
+           replan_spec=False, partial=False, share=None, share_objective=None):
+    if share is not None and not plan_spec:
+        raise ValueError("--share needs --plan-spec (the plan whose stations the team shares)")
+    if share is not None and team_size is not None:
+        raise ValueError("--share excludes --team-size (mates do not plan around each other in a plan from a specification)")
+    if share_objective is not None and share is None:
+        raise ValueError("--share-objective needs --share")
+    shared = {} if share is None else dict(share=int(share), objective=share_objective or "makespan")
     if check_spec and goal is None:
         raise ValueError("--check-spec needs --goal (the specification is: eventually inside the reach radius around the goal)")
     if int(spec_hold) != 0 and not check_spec:
@@ -203,8 +213,13 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
             plain = planner.plan(start, goals, grow=True, clearance=None, want_occupancy=True, want_fields=True)
             plain_min = grid_plan_clearance_min(planner.spec, plain, start, goals, planner.clearance[0])
         if plan_spec:                                      # the specification's stations in --goal's place, in the order the plan chooses
-            plan = planner.plan_spec(start, monitored_spec()["spec"], pace=pace, partial=bool(partial))
+            plan = planner.plan_spec(start, monitored_spec()["spec"], pace=pace, partial=bool(partial), **shared)
             plan.update(smoothed=False, moves=None)
+            if shared:
+                ok = plan["team_feasible"]
+                print(f"shared within teams of {shared['share']} ({shared['objective']}): {int(ok.sum())} of {len(ok)} teams allotted, "
+                      f"{int(np.sum(plan['share'] != 0))} members with stations, mean makespan "
+                      f"{float(np.mean(plan['team_makespan'][ok])) if np.any(ok) else float('nan')} ticks")
             if replan_spec and plan["schedule"] is None:   # the replanned rows may bring release steps: the run has a schedule from its first call
                 plan["schedule"] = Schedule(plan["release"], home=start)
             print(f"planned from the specification: tour cost {float(np.mean(plan['cost'][plan['status'] == 0])) if np.any(plan['status'] == 0) else float('nan')} "
@@ -224,7 +239,7 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         waypoints, n_waypoints, plan_schedule = plan["waypoints"], plan["n_waypoints"], plan.get("schedule")
         replan = planner.callback(goals, **(dict(horizon=calls[0]) if timed else {})) if int(leg_steps) > 0 and not plan_spec else None
         if replan_spec:                                    # a stalled robot gets the stations it has not visited yet, from where it stands
-            replan = planner.spec_callback(monitored_spec()["spec"], pace=pace, partial=bool(partial))
+            replan = planner.spec_callback(monitored_spec()["spec"], pace=pace, partial=bool(partial), **shared)
         print(f"planned rate: {float(np.mean(plan['status'] == 0))}")
         if teams is not None:                              # beside the run's measured team conflict steps, further down
             print(f"planned team clearance: {int(plan['team_clearance'].min())} cells at the least (reserve {planner.reserve}), "
@@ -282,6 +297,14 @@ def follow(env_name, policy_name, waypoints, robots, max_steps=1000, host=False,
         worst = int(np.argmin(r["robustness"]))
         print(f"specification satisfied: {int(np.sum(r['satisfied']))} of {len(r['satisfied'])} robots")
         print(f"worst robustness: {float(r['robustness'][worst])} (robot {worst}, clause {int(r['weakest'][worst])})")
+        if shared:                                         # the team's verdict: a station someone visited is visited
+            from mobrob_amd.waypoints import spec_team_result
+            team = spec_team_result(r, monitored["spec"], shared["share"])
+            worst = int(np.argmin(team["team_robustness"]))
+            print(f"team specification satisfied: {int(np.sum(team['team_satisfied']))} of {len(team['team_satisfied'])} teams")
+            print(f"worst team robustness: {float(team['team_robustness'][worst])} (team {worst}, clause {int(team['team_weakest'][worst])}, "
+                  f"member {int(team['team_member'][worst, team['team_weakest'][worst]])})")
+        r.update(team if shared else {})
     return r
 
 
@@ -381,6 +404,11 @@ def build_parser():
                          "stands, for the stations not yet visited (GridPlanner.spec_callback)")
     ap.add_argument("--partial", action="store_true", default=False,
                     help="with --plan-spec: a robot that cannot keep every window keeps the stations it still can (plan_spec(partial=True))")
+    ap.add_argument("--share", type=int, default=None,
+                    help="with --plan-spec: share the stations within teams of N consecutive robots, each station to one member "
+                         "(plan_spec(share=N)); prints the team verdict (waypoints.spec_team_result)")
+    ap.add_argument("--share-objective", choices=("makespan", "sum"), default=None,
+                    help="with --share: the team done as early as possible (makespan, the default) or with the least total (sum)")
     ap.add_argument("--tile256", action="store_true", default=False,
                     help="a 2x256 tanh policy: run calls without hazards, teams or walls as one launch (PPOEngine.set_eval_tile256)")
     ap.add_argument("--tile256-wide", action="store_true", default=False,
@@ -407,6 +435,10 @@ if __name__ == "__main__":
         ap.error("--pace needs --plan-spec")
     if (args.replan_spec or args.partial) and not args.plan_spec:
         ap.error("--replan-spec and --partial need --plan-spec")
+    if args.share is not None and (not args.plan_spec or args.team_size is not None):
+        ap.error("--share needs --plan-spec and excludes --team-size")
+    if args.share_objective is not None and args.share is None:
+        ap.error("--share-objective needs --share")
     try:
         check_chain(args.max_steps, args.horizon, args.leg_steps)
     except ValueError as ex:
@@ -424,4 +456,4 @@ if __name__ == "__main__":
            plan_clearance=None if args.plan_clearance is None else [int(v) for v in args.plan_clearance.split(",")], solid=args.solid,
            tile256=args.tile256 or args.tile256_wide, tile256_wide=args.tile256_wide, team_solid=args.team_solid,
            check_spec=args.check_spec, spec_hold=args.spec_hold, plan_spec=args.plan_spec, pace=args.pace,
-           replan_spec=args.replan_spec, partial=args.partial)
+           replan_spec=args.replan_spec, partial=args.partial, share=args.share, share_objective=args.share_objective)

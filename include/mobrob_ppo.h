@@ -1433,6 +1433,46 @@ int mobrob_ppo_spec_replan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
                            int32_t* sweeps_out /* [S * M + n_fields] or NULL */, int32_t* tour_len_out /* [n] */,
                            int32_t* dropped_out /* [n] */);
 
+/* The same plan with the stations shared within a team (goal_rules.spec_plan with share=, objective=; csrc/kernels_plan_spec_share.h).
+ * Every argument of mobrob_ppo_spec_replan means what it means there, and the same checks are made; in addition
+ *   team_size    1, 2, 4, 8 or 16 consecutive robots: team r / team_size, member r % team_size; n_robots is a multiple of it.  T, the
+ *                stations the team still has to visit, is the bitwise AND of its members' todo (reduced on the host).
+ *   objective    0 makespan: the smallest largest member cost and under it the smallest sum of the member costs; 1 sum.
+ *   partial      0: the team covers all of T, or every member has status 1 with count 0, cost -1, orders -1 and share 0.  1: the covered
+ *                set C is the lexicographic minimum of (popcount(T) - popcount(U), f[U], U) over the feasible U, f the primary pass.
+ *   outputs      share_out [n]: the stations of member r, a partition of C within the team.  The member's tour, waypoints and releases
+ *                are those of mobrob_ppo_spec_replan with todo = share and partial 0; cost_out is best[r][share[r]]; dropped_out is 0
+ *                for a member of a team with an allotment (with team_size 1 the team's loss) and T without one.  Per team, [n /
+ *                team_size]: team_cover_out = C, team_dropped_out = T & ~C, team_makespan_out the largest member cost,
+ *                team_total_out (int64) their sum; 0, T, -1 and -1 for a team without an allotment.
+ *   kernels      after the tour matrix k_plan_tour_best (a wave per robot, k_plan_tour_resume's table over the subsets of T -> best
+ *                [n][256]) and k_plan_team_share (a wave per team: best in LDS, the partition DP over the members with the lanes on
+ *                the sets U and their submasks enumerated ascending, the covered set a wave-wide minimum, the backtrack by lane 0);
+ *                then k_plan_tour_resume over the shares, k_plan_team_void (a thread per robot: the members of a team without an
+ *                allotment) and k_plan_tour_path_legs.
+ * With team_size 1 every output it shares with mobrob_ppo_spec_replan equals that call's, for both objectives.
+ * MOBROB_ERR_INVALID, outputs untouched, for everything mobrob_ppo_spec_replan refuses and for: a team_size not 1, 2, 4, 8 or 16;
+ * n_robots % team_size != 0; an objective not 0 / 1; share_out or a team output NULL. */
+int mobrob_ppo_spec_plan_share(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls /* or NULL */,
+                               const mobrob_hazards_t* hazards /* or NULL */, const mobrob_spec_t* regions, int32_t n_stations,
+                               const int32_t* station_lo /* [M] */, const int32_t* station_hi /* [M] */, int32_t n_avoid,
+                               const int32_t* avoid_lo /* [n_avoid] or NULL */, const int32_t* avoid_hi /* [n_avoid] or NULL */,
+                               const int32_t* open_c /* [M] */, const int32_t* close_c /* [M] */, const int32_t* dwell_c /* [M] */,
+                               int32_t pace, const float* start /* [n][pos_dim] */, const float* goal /* [n][pos_dim] or NULL */,
+                               const int32_t* field_of /* [n], with a goal */, const int32_t* field_goal_cell /* [n_fields], with a goal */,
+                               const int32_t* field_scene /* [n_fields], with a goal */, const int32_t* todo /* [n] */,
+                               int32_t step0_ticks, int32_t partial, int32_t team_size, int32_t objective,
+                               float* waypoints_out /* [n][K][pos_dim] */, int32_t* n_waypoints_out /* [n] */,
+                               int32_t* count_out /* [n] */, int32_t* status_out /* [n] */, int32_t* cost_out /* [n] */,
+                               int32_t* tour_order_out /* [n][M] */, int32_t* tour_eta_out /* [n][M] */,
+                               int32_t* station_waypoint_out /* [n][M] */, int32_t* release_out /* [n][K] */,
+                               int32_t* station_cell_out /* [S][M] */, float* station_margin_out /* [S][M] */,
+                               int32_t* matrix_out /* [S][M][M] */, uint8_t* occupancy_out /* [S][G][G] or NULL */,
+                               int32_t* sweeps_out /* [S * M + n_fields] or NULL */, int32_t* tour_len_out /* [n] */,
+                               int32_t* dropped_out /* [n] */, int32_t* share_out /* [n] */,
+                               int32_t* team_cover_out /* [n / team_size] */, int32_t* team_dropped_out /* [n / team_size] */,
+                               int32_t* team_makespan_out /* [n / team_size] */, int64_t* team_total_out /* [n / team_size] */);
+
 /* ---- gSDE (use_sde = 1) ------------------------------------------------------------------------
  * policy.reset_noise(n_envs) (SB3 ActorCriticPolicy.reset_noise -> sample_weights): new exploration matrices for every environment
  * and the single matrix predict() uses for batches of another size, from the CURRENT log_std.  The rollout collectors call it

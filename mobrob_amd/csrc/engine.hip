@@ -62,6 +62,7 @@ inline void poison_lds(hipStream_t st) {
 #include "kernels_spec_moving.h"
 #include "kernels_plan_spec.h"
 #include "kernels_plan_spec_resume.h"
+#include "kernels_plan_spec_share.h"
 #include "kernels_rollout.h"
 #include "kernels_epoch64.h"
 #include "robot_ctrl.h"
@@ -5706,11 +5707,23 @@ int mobrob_ppo_spec_monitor_moving(mobrob_ppo_engine_t* e, const mobrob_spec_mov
 // works in a buffer of its own and keeps nothing resident: mobrob_ppo_plan_grid's resident fields stay valid across it.
 // mobrob_ppo_spec_replan is the same call from the middle of a run (csrc/kernels_plan_spec_resume.h): the same checks, buffer, map,
 // stations, fields and matrix, then k_plan_tour_resume and k_plan_tour_path_legs in place of the last two.
+// mobrob_ppo_spec_plan_share is the replan with the team's stations shared among its members (csrc/kernels_plan_spec_share.h): after the
+// matrix k_plan_tour_best and k_plan_team_share, then k_plan_tour_resume over the shares, k_plan_team_void and k_plan_tour_path_legs.
+struct SpecShare {
+  int32_t team_size, objective;
+  int32_t* share_out;           // [n]
+  int32_t* team_cover_out;      // [n / team_size]
+  int32_t* team_dropped_out;    // [n / team_size]
+  int32_t* team_makespan_out;   // [n / team_size]
+  int64_t* team_total_out;      // [n / team_size]
+};
+
 struct SpecReplan {
   const int32_t* todo;     // [n]
   int32_t t0, partial;
   int32_t* tour_len_out;   // [n]
   int32_t* dropped_out;    // [n]
+  const SpecShare* share;  // null: every robot for itself
 };
 
 static int spec_plan_run(const char* who, const SpecReplan* rp, mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
@@ -5783,6 +5796,18 @@ static int spec_plan_run(const char* who, const SpecReplan* rp, mobrob_ppo_engin
       if (rp->todo[i] < 0 || rp->todo[i] >= (1 << M))
         return fail(MOBROB_ERR_INVALID, "%s: todo of robot %d is 0x%x, a bit at or above n_stations = %d", who, i, (unsigned)rp->todo[i], M);
   }
+  const SpecShare* sh = rp ? rp->share : nullptr;
+  if (sh) {
+    const int size = sh->team_size;
+    if (size != 1 && size != 2 && size != 4 && size != 8 && size != 16)
+      return fail(MOBROB_ERR_INVALID, "%s: team_size must be 1, 2, 4, 8 or 16, got %d", who, size);
+    if (N % size != 0) return fail(MOBROB_ERR_INVALID, "%s: %d robots do not split into teams of %d", who, N, size);
+    if (sh->objective != 0 && sh->objective != 1)
+      return fail(MOBROB_ERR_INVALID, "%s: objective must be 0 (makespan) or 1 (sum), got %d", who, sh->objective);
+    if (!sh->share_out || !sh->team_cover_out || !sh->team_dropped_out || !sh->team_makespan_out || !sh->team_total_out)
+      return fail(MOBROB_ERR_INVALID, "%s: null argument", who);
+  }
+  const int tsize = sh ? sh->team_size : 1, NT = N / tsize;
   const int cells = G * G, F = S * M + Fg;
   if ((uint64_t)((uint64_t)S * M + Fg) * (uint64_t)cells * 4u > MOBROB_PLAN_TIME_MAX_BYTES)
     return fail(MOBROB_ERR_INVALID, "%s: fields of (%d x %d + %d) x %d x %d x 4 bytes exceed the cap of %u bytes (256 MiB)", who, S, M, Fg, G, G,
@@ -5808,6 +5833,10 @@ static int spec_plan_run(const char* who, const SpecReplan* rp, mobrob_ppo_engin
                o_box = call.add(std::max<size_t>((size_t)S * Mw * 4, 1) * 4), o_nwall = call.add((size_t)S * 4),
                o_hz = call.add(std::max<size_t>((size_t)S * Mh * 3, 1) * 4), o_nhz = call.add((size_t)S * 4),
                o_todo = call.add((size_t)N * 4), o_len = call.add((size_t)N * 4), o_drop = call.add((size_t)N * 4);   // a replan's
+  const auto shared = [&](size_t bytes) { return sh ? call.add(bytes) : (size_t)0; };   // a shared plan's: the other calls' buffer as it was
+  const size_t o_team = shared((size_t)N * 4), o_best = shared((size_t)N * kPlanTourMasks * 4), o_share = shared((size_t)N * 4),
+               o_unconv = shared((size_t)N * 4), o_tcover = shared((size_t)NT * 4), o_tdrop = shared((size_t)NT * 4),
+               o_tmake = shared((size_t)NT * 4), o_ttotal = shared((size_t)NT * 8);
   if (const int rc = grow_plan_buf(e, e->plan_spec_buf, e->plan_spec_bytes, call.total)) return rc;
   const auto mine = [&](size_t off) { return e->plan_spec_buf + off; };
   const auto ints = [&](size_t off) { return reinterpret_cast<int*>(mine(off)); };
@@ -5874,7 +5903,26 @@ static int spec_plan_run(const char* who, const SpecReplan* rp, mobrob_ppo_engin
   ta.cell = ints(o_cell); ta.matrix = ints(o_matrix); ta.field = ints(o_field); ta.sweeps = ints(o_sweeps);
   for (int j = 0; j < M; ++j) { ta.open_c[j] = open_c[j]; ta.close_c[j] = close_c[j]; ta.dwell_c[j] = dwell_c[j]; }
   ta.status = ints(o_status); ta.cost = ints(o_cost); ta.order = ints(o_order); ta.eta = ints(o_eta); ta.depart = ints(o_depart);
-  if (rp) {
+  std::vector<int32_t> team_todo;   // T: what no member of the team has done yet (alive until the stream is synchronised)
+  if (sh) {
+    team_todo.resize(N);
+    for (int g = 0; g < NT; ++g) {   // the AND over the team's members, then the same T for each of them
+      int32_t T = rp->todo[g * tsize];
+      for (int k = 1; k < tsize; ++k) T &= rp->todo[g * tsize + k];
+      for (int k = 0; k < tsize; ++k) team_todo[g * tsize + k] = T;
+    }
+    HIPC(hipMemcpyAsync(mine(o_team), team_todo.data(), (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
+    const PlanTourBestArgs ba{ta, ints(o_team), rp->t0, ints(o_best), ints(o_unconv)};
+    hipLaunchKernelGGL(k_plan_tour_best, dim3(N), dim3(64), 0, e->stream, ba);   // a wave per robot
+    const PlanTeamShareArgs ha{tsize, M, sh->objective, rp->partial, ints(o_best), ints(o_team), ints(o_share), ints(o_tcover), ints(o_tdrop),
+                               ints(o_tmake), reinterpret_cast<long long*>(mine(o_ttotal))};
+    hipLaunchKernelGGL(k_plan_team_share, dim3(NT), dim3(64), 0, e->stream, ha);   // a wave per team
+    const PlanTourResumeArgs ra{ta, ints(o_share), rp->t0, 0, ints(o_len), ints(o_drop)};
+    hipLaunchKernelGGL(k_plan_tour_resume, dim3(N), dim3(64), 0, e->stream, ra);
+    const PlanTeamVoidArgs va{N, M, tsize, ints(o_team), ints(o_tmake), ints(o_tdrop), ints(o_unconv), ta.status, ta.cost, ta.order, ta.eta,
+                              ta.depart, ints(o_len), ints(o_drop)};
+    hipLaunchKernelGGL(k_plan_team_void, dim3(cdiv(N, 256)), dim3(256), 0, e->stream, va);
+  } else if (rp) {
     HIPC(hipMemcpyAsync(mine(o_todo), rp->todo, (size_t)N * 4, hipMemcpyHostToDevice, e->stream));
     const PlanTourResumeArgs ra{ta, ints(o_todo), rp->t0, rp->partial, ints(o_len), ints(o_drop)};
     hipLaunchKernelGGL(k_plan_tour_resume, dim3(N), dim3(64), 0, e->stream, ra);   // a wave per robot
@@ -5900,6 +5948,13 @@ static int spec_plan_run(const char* who, const SpecReplan* rp, mobrob_ppo_engin
   if (rp) {
     HIPC(hipMemcpyAsync(rp->tour_len_out, ints(o_len), (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
     HIPC(hipMemcpyAsync(rp->dropped_out, ints(o_drop), (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+  }
+  if (sh) {
+    HIPC(hipMemcpyAsync(sh->share_out, ints(o_share), (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipMemcpyAsync(sh->team_cover_out, ints(o_tcover), (size_t)NT * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipMemcpyAsync(sh->team_dropped_out, ints(o_tdrop), (size_t)NT * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipMemcpyAsync(sh->team_makespan_out, ints(o_tmake), (size_t)NT * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipMemcpyAsync(sh->team_total_out, mine(o_ttotal), (size_t)NT * 8, hipMemcpyDeviceToHost, e->stream));
   }
   HIPC(hipMemcpyAsync(waypoints_out, pa.wp, (size_t)N * K * P * 4, hipMemcpyDeviceToHost, e->stream));
   HIPC(hipMemcpyAsync(n_waypoints_out, pa.nwp, (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
@@ -5942,10 +5997,29 @@ int mobrob_ppo_spec_replan(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spe
                            int32_t* cost_out, int32_t* tour_order_out, int32_t* tour_eta_out, int32_t* station_waypoint_out,
                            int32_t* release_out, int32_t* station_cell_out, float* station_margin_out, int32_t* matrix_out,
                            uint8_t* occupancy_out, int32_t* sweeps_out, int32_t* tour_len_out, int32_t* dropped_out) {
-  const SpecReplan rp{todo, step0_ticks, partial, tour_len_out, dropped_out};
+  const SpecReplan rp{todo, step0_ticks, partial, tour_len_out, dropped_out, nullptr};
   return spec_plan_run("spec_replan", &rp, e, spec, walls, hz, regions, n_stations, station_lo, station_hi, n_avoid, avoid_lo, avoid_hi, open_c,
                        close_c, dwell_c, pace, start, goal, field_of, field_goal_cell, field_scene, waypoints_out, n_waypoints_out, count_out,
                        status_out, cost_out, tour_order_out, tour_eta_out, station_waypoint_out, release_out, station_cell_out,
+                       station_margin_out, matrix_out, occupancy_out, sweeps_out);
+}
+
+int mobrob_ppo_spec_plan_share(mobrob_ppo_engine_t* e, const mobrob_plan_spec_t* spec, const mobrob_walls_t* walls, const mobrob_hazards_t* hz,
+                               const mobrob_spec_t* regions, int32_t n_stations, const int32_t* station_lo, const int32_t* station_hi,
+                               int32_t n_avoid, const int32_t* avoid_lo, const int32_t* avoid_hi, const int32_t* open_c, const int32_t* close_c,
+                               const int32_t* dwell_c, int32_t pace, const float* start, const float* goal, const int32_t* field_of,
+                               const int32_t* field_goal_cell, const int32_t* field_scene, const int32_t* todo, int32_t step0_ticks,
+                               int32_t partial, int32_t team_size, int32_t objective, float* waypoints_out, int32_t* n_waypoints_out,
+                               int32_t* count_out, int32_t* status_out, int32_t* cost_out, int32_t* tour_order_out, int32_t* tour_eta_out,
+                               int32_t* station_waypoint_out, int32_t* release_out, int32_t* station_cell_out, float* station_margin_out,
+                               int32_t* matrix_out, uint8_t* occupancy_out, int32_t* sweeps_out, int32_t* tour_len_out, int32_t* dropped_out,
+                               int32_t* share_out, int32_t* team_cover_out, int32_t* team_dropped_out, int32_t* team_makespan_out,
+                               int64_t* team_total_out) {
+  const SpecShare sh{team_size, objective, share_out, team_cover_out, team_dropped_out, team_makespan_out, team_total_out};
+  const SpecReplan rp{todo, step0_ticks, partial, tour_len_out, dropped_out, &sh};
+  return spec_plan_run("spec_plan_share", &rp, e, spec, walls, hz, regions, n_stations, station_lo, station_hi, n_avoid, avoid_lo, avoid_hi,
+                       open_c, close_c, dwell_c, pace, start, goal, field_of, field_goal_cell, field_scene, waypoints_out, n_waypoints_out,
+                       count_out, status_out, cost_out, tour_order_out, tour_eta_out, station_waypoint_out, release_out, station_cell_out,
                        station_margin_out, matrix_out, occupancy_out, sweeps_out);
 }
 

@@ -41,6 +41,106 @@ __device__ __forceinline__ unsigned long long plan_tour_key(int left, int total,
   return ((unsigned long long)left << 42) | ((unsigned long long)total << 12) | ((unsigned long long)V << 4) | (unsigned long long)(j + 1);
 }
 
+// the LDS of one robot's tour table: the kernel that owns the arrays hands them to the two helpers below
+struct PlanTourTable {
+  int* t;                  // [256][8] the table
+  signed char* pred;       // [256][8]
+  unsigned char* list;     // [256] the submasks of todo by (stations visited, value)
+  int* binom;              // [9][9]
+  int* Dm; int* d0; int* E; int* pos;          // [8][8], [8], [8], [8]
+  int* open_c; int* close_c; int* dwell_c;     // [8] each
+  int* bad; int* e0s;                          // one int each
+};
+
+// The staging of a robot's table, stated once (k_plan_tour_resume, k_plan_tour_best): the binomials, the robot's costs and ticks, the
+// unconverged flag, the positions of todo's stations and the list of its submasks.  All 64 lanes call it; it ends on a barrier.
+__device__ __forceinline__ void plan_tour_stage(const PlanTourArgs& a, int n, int lane, int todo, const PlanTourTable& m) {
+  const int M = a.M, G = a.g.G, cells = G * G, W = kPlanTourMax + 1, L = __popc(todo);
+  const int s = a.scene ? a.scene[n] : 0;
+  const int* fields = a.field + (size_t)s * M * cells;
+  if (lane == 0) *m.bad = 0;
+  __syncthreads();
+  for (int idx = lane; idx < W * W; idx += 64) {   // C(p, q), exact at every step
+    const int p = idx / W, q = idx % W;
+    int v = q <= p ? 1 : 0;
+    for (int i = 1; i <= q && q <= p; ++i) v = v * (p - q + i) / i;
+    m.binom[idx] = v;
+  }
+  if (lane < M * M) {
+    const int v = a.matrix[s * M * M + lane];
+    m.Dm[lane] = v < 0 ? kPlanAssignNone : v;
+  }
+  if (lane < M) {
+    const float* st = a.start + (size_t)n * a.P;
+    const int sc = plan_cell(a.g, st[1]) * G + plan_cell(a.g, st[0]);
+    const int v = fields[(size_t)lane * cells + sc];
+    m.d0[lane] = v < 0 ? kPlanAssignNone : v;
+    int e = 0;
+    if (a.has_goal) {
+      const int ci = a.cell[s * M + lane];
+      e = ci >= 0 ? a.field[(size_t)(a.S * M + a.field_of[n]) * cells + ci] : -1;
+    }
+    m.E[lane] = e < 0 ? kPlanAssignNone : e;
+    m.open_c[lane] = a.open_c[lane]; m.close_c[lane] = a.close_c[lane]; m.dwell_c[lane] = a.dwell_c[lane];
+    if (((todo >> lane) & 1) && a.sweeps[s * M + lane] < 0) *m.bad = 1;
+    if (lane == 0) {
+      int e0 = 0;
+      if (a.has_goal) {
+        if (a.sweeps[a.S * M + a.field_of[n]] < 0) *m.bad = 1;
+        e0 = a.field[(size_t)(a.S * M + a.field_of[n]) * cells + sc];
+      }
+      *m.e0s = e0 < 0 ? kPlanAssignNone : e0;
+      int b = 0;
+      for (int j = 0; j < kPlanTourMax; ++j)
+        if ((todo >> j) & 1) m.pos[b++] = j;
+    }
+  }
+  __syncthreads();
+  for (int c = lane; c < (1 << L); c += 64) {   // the compact masks into their places: level offset + rank within the level
+    const int level = __popc(c);
+    int at = 0, i = 0;
+    for (int q = 0; q < level; ++q) at += m.binom[L * W + q];
+    for (int p = 0; p < L; ++p)
+      if ((c >> p) & 1) at += m.binom[p * W + ++i];
+    m.list[at] = (unsigned char)plan_tour_deposit(c, todo);
+  }
+  __syncthreads();
+}
+
+// The table fill, stated once: level by level over the list, the 64 lanes on the (mask, station of todo) pairs of a level.
+__device__ __forceinline__ void plan_tour_levels(const PlanTourTable& m, int lane, int L, int M, int t0) {
+  const int W = kPlanTourMax + 1;
+  const auto dep = [&](int j, int arr) {
+    const int begin = max(arr, m.open_c[j]);
+    return begin <= m.close_c[j] ? begin + m.dwell_c[j] : kPlanInf;
+  };
+  int first = 1;   // list[0] is the empty set
+  for (int level = 1; level <= L; ++level) {
+    const int cnt = m.binom[L * W + level];
+    for (int idx = lane; idx < cnt * L; idx += 64) {
+      const int e = idx / L, j = m.pos[idx - e * L], mask = m.list[first + e];
+      if (!((mask >> j) & 1)) continue;
+      const int rest = mask ^ (1 << j);
+      int best = kPlanInf, via = -1;
+      if (rest == 0) {
+        if (m.d0[j] < kPlanAssignNone) best = dep(j, t0 + m.d0[j]);
+      } else {
+        for (int i = 0; i < M; ++i) {   // ascending, strict <: the lowest i of equal values
+          if (!((rest >> i) & 1)) continue;
+          const int ti = m.t[rest * kPlanTourMax + i], dij = m.Dm[i * M + j];
+          if (ti >= kPlanInf || dij >= kPlanAssignNone) continue;
+          const int v = dep(j, ti + dij);
+          if (v < best) { best = v; via = i; }
+        }
+      }
+      m.t[mask * kPlanTourMax + j] = best;
+      m.pred[mask * kPlanTourMax + j] = (signed char)via;
+    }
+    first += cnt;
+    __syncthreads();
+  }
+}
+
 // A wave per robot, k_plan_tour's shape: t [256][8] and pred in LDS.  The submasks of todo are ENUMERATED: `list` holds them sorted
 // by (stations visited, value) -- the rank of a compact mask among those of its popcount is its combinatorial number -- so a level
 // is a contiguous run of the list and a robot with three stations left touches 8 masks, not 256.  The 64 lanes take the (mask,
@@ -54,86 +154,11 @@ __global__ __launch_bounds__(64) void k_plan_tour_resume(PlanTourResumeArgs r) {
   __shared__ int open_c[kPlanTourMax], close_c[kPlanTourMax], dwell_c[kPlanTourMax];
   __shared__ int bad, e0s;
   const PlanTourArgs& a = r.base;
-  const int n = blockIdx.x, lane = threadIdx.x, M = a.M, G = a.g.G, cells = G * G, W = kPlanTourMax + 1;
-  const int s = a.scene ? a.scene[n] : 0;
+  const int n = blockIdx.x, lane = threadIdx.x, M = a.M;
   const int todo = r.todo[n] & ((1 << M) - 1), L = __popc(todo), t0 = r.t0;
-  const int* fields = a.field + (size_t)s * M * cells;
-  if (lane == 0) bad = 0;
-  __syncthreads();
-  for (int idx = lane; idx < W * W; idx += 64) {   // C(p, q), exact at every step
-    const int p = idx / W, q = idx % W;
-    int v = q <= p ? 1 : 0;
-    for (int i = 1; i <= q && q <= p; ++i) v = v * (p - q + i) / i;
-    binom[idx] = v;
-  }
-  if (lane < M * M) {
-    const int v = a.matrix[s * M * M + lane];
-    Dm[lane] = v < 0 ? kPlanAssignNone : v;
-  }
-  if (lane < M) {
-    const float* st = a.start + (size_t)n * a.P;
-    const int sc = plan_cell(a.g, st[1]) * G + plan_cell(a.g, st[0]);
-    const int v = fields[(size_t)lane * cells + sc];
-    d0[lane] = v < 0 ? kPlanAssignNone : v;
-    int e = 0;
-    if (a.has_goal) {
-      const int ci = a.cell[s * M + lane];
-      e = ci >= 0 ? a.field[(size_t)(a.S * M + a.field_of[n]) * cells + ci] : -1;
-    }
-    E[lane] = e < 0 ? kPlanAssignNone : e;
-    open_c[lane] = a.open_c[lane]; close_c[lane] = a.close_c[lane]; dwell_c[lane] = a.dwell_c[lane];
-    if (((todo >> lane) & 1) && a.sweeps[s * M + lane] < 0) bad = 1;
-    if (lane == 0) {
-      int e0 = 0;
-      if (a.has_goal) {
-        if (a.sweeps[a.S * M + a.field_of[n]] < 0) bad = 1;
-        e0 = a.field[(size_t)(a.S * M + a.field_of[n]) * cells + sc];
-      }
-      e0s = e0 < 0 ? kPlanAssignNone : e0;
-      int b = 0;
-      for (int j = 0; j < kPlanTourMax; ++j)
-        if ((todo >> j) & 1) pos[b++] = j;
-    }
-  }
-  __syncthreads();
-  for (int c = lane; c < (1 << L); c += 64) {   // the compact masks into their places: level offset + rank within the level
-    const int level = __popc(c);
-    int at = 0, i = 0;
-    for (int q = 0; q < level; ++q) at += binom[L * W + q];
-    for (int p = 0; p < L; ++p)
-      if ((c >> p) & 1) at += binom[p * W + ++i];
-    list[at] = (unsigned char)plan_tour_deposit(c, todo);
-  }
-  __syncthreads();
-  const auto dep = [&](int j, int arr) {
-    const int begin = max(arr, open_c[j]);
-    return begin <= close_c[j] ? begin + dwell_c[j] : kPlanInf;
-  };
-  int first = 1;   // list[0] is the empty set
-  for (int level = 1; level <= L; ++level) {
-    const int cnt = binom[L * W + level];
-    for (int idx = lane; idx < cnt * L; idx += 64) {
-      const int e = idx / L, j = pos[idx - e * L], mask = list[first + e];
-      if (!((mask >> j) & 1)) continue;
-      const int rest = mask ^ (1 << j);
-      int best = kPlanInf, via = -1;
-      if (rest == 0) {
-        if (d0[j] < kPlanAssignNone) best = dep(j, t0 + d0[j]);
-      } else {
-        for (int i = 0; i < M; ++i) {   // ascending, strict <: the lowest i of equal values
-          if (!((rest >> i) & 1)) continue;
-          const int ti = t[rest * kPlanTourMax + i], dij = Dm[i * M + j];
-          if (ti >= kPlanInf || dij >= kPlanAssignNone) continue;
-          const int v = dep(j, ti + dij);
-          if (v < best) { best = v; via = i; }
-        }
-      }
-      t[mask * kPlanTourMax + j] = best;
-      pred[mask * kPlanTourMax + j] = (signed char)via;
-    }
-    first += cnt;
-    __syncthreads();
-  }
+  const PlanTourTable tb{t, pred, list, binom, Dm, d0, E, pos, open_c, close_c, dwell_c, &bad, &e0s};
+  plan_tour_stage(a, n, lane, todo, tb);
+  plan_tour_levels(tb, lane, L, M, t0);
   // the selection: every lane the minimum of its candidates, then the wave's
   const unsigned long long none = ~0ull;
   unsigned long long key = none;

@@ -1263,7 +1263,7 @@ class PPOEngine:
         return out
 
     def plan_spec(self, grid, walls=None, hazards=None, *, spec, start, goal=None, pace=None, max_waypoints=16, want_occupancy=False,
-                  state=None, step0=0, partial=False):
+                  state=None, step0=0, partial=False, share=None, objective="makespan"):
         """A plan from a specification on the device (mobrob_ppo_spec_plan; the rule: goal_rules.spec_plan, reproduced bit for bit):
         the avoid clauses of `spec` become obstacles, its reach clauses stations, and per robot the order of the stations and the
         stitched waypoints are computed in one call.  grid: a goal_rules.GridSpec; walls / hazards: static, or None; spec: a
@@ -1272,7 +1272,10 @@ class PPOEngine:
         stays resident and plan_grid's resident fields stay valid.
         state (a goal_rules.SpecState), step0, partial: the plan from the middle of a run, spec_plan's keywords.  With all three at
         their defaults the call is mobrob_ppo_spec_plan; otherwise mobrob_ppo_spec_replan (k_plan_tour_resume,
-        k_plan_tour_path_legs), with todo made here from the state.  Either way the dict holds SPEC_REPLAN_KEYS and t0."""
+        k_plan_tour_path_legs), with todo made here from the state.  Either way the dict holds SPEC_REPLAN_KEYS and t0.
+        share (a team size), objective ("makespan" / "sum"): the team's stations are shared among its members, spec_plan's
+        keywords; the call is then mobrob_ppo_spec_plan_share (k_plan_tour_best, k_plan_team_share, k_plan_team_void) and the dict
+        also holds SPEC_SHARE_KEYS.  share=None takes the path it took."""
         from ._lib import PlanSpec, SpecC, WallsC
         from .envs import goal_rules as R
         raw_pace = pace
@@ -1280,6 +1283,8 @@ class PPOEngine:
                                                                                                      goal, max_waypoints, pace)
         done, todo, t0 = R.spec_plan_resume_check(spec, start.shape[0], None if raw_pace is None else pace, state, step0, partial)
         resume = state is not None or step0 != 0 or bool(partial)
+        if share is not None:
+            share, objective = R.spec_plan_share_check(start.shape[0], share, objective)
         reg = spec.regions
         n, P = start.shape
         G, M = grid.cells, len(stations)
@@ -1321,7 +1326,18 @@ class PPOEngine:
                None if goal is None else ip(fscene))
         outs = (_fp(wp), ip(nwp), ip(count), ip(status), ip(cost), ip(order), ip(eta), ip(swp), ip(release), ip(cell), _fp(margin),
                 ip(matrix), None if occ is None else occ.ctypes.data_as(C.POINTER(C.c_uint8)), ip(sweeps))
-        if resume:
+        shared = {}
+        if share is not None:
+            todo = np.ascontiguousarray(todo, np.int32)
+            tour_len, dropped, mine = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+            cover, lost, makespan = (np.zeros(n // share, np.int32) for _ in range(3))
+            total = np.zeros(n // share, np.int64)
+            check(self.lib.mobrob_ppo_spec_plan_share(*ins, ip(todo), t0, int(bool(partial)), share, R.SPEC_SHARE_OBJECTIVES.index(objective),
+                                                      *outs, ip(tour_len), ip(dropped), ip(mine), ip(cover), ip(lost), ip(makespan),
+                                                      total.ctypes.data_as(C.POINTER(C.c_int64))))
+            shared = {"share": mine, "team_cover": cover, "team_dropped": lost, "team_makespan": makespan, "team_total": total,
+                      "team_done": done.reshape(n // share, share, M).any(axis=1), "team_feasible": makespan >= 0}
+        elif resume:
             todo = np.ascontiguousarray(todo, np.int32)
             tour_len, dropped = np.zeros(n, np.int32), np.zeros(n, np.int32)
             check(self.lib.mobrob_ppo_spec_replan(*ins, ip(todo), t0, int(bool(partial)), *outs, ip(tour_len), ip(dropped)))
@@ -1331,7 +1347,7 @@ class PPOEngine:
         out = {"waypoints": wp, "n_waypoints": nwp, "count": count, "status": status, "cost": cost, "tour_order": order, "tour_eta": eta,
                "station_waypoint": swp, "release": release, "station_cell": cell, "station_margin": margin,
                "covered": margin >= np.float32(R.REACH_RADIUS), "matrix": matrix, "open_c": open_c, "close_c": close_c, "dwell_c": dwell_c,
-               "pace": pace, "sweeps": sweeps, "tour_len": tour_len, "dropped": dropped, "done": done, "t0": t0}
+               "pace": pace, "sweeps": sweeps, "tour_len": tour_len, "dropped": dropped, "done": done, "t0": t0, **shared}
         if occ is not None:
             out["occupancy"] = occ.astype(bool)
         return out

@@ -2998,8 +2998,8 @@ def spec_result(state, spec):
 # project's own rule, all integers except the two margin tests; the device (csrc/kernels_plan_spec.h: k_plan_region_occupancy,
 # k_plan_station, k_plan_tour_matrix, k_plan_tour, k_plan_tour_path, with k_plan_occupancy and k_plan_field as they are; from the
 # middle of a run csrc/kernels_plan_spec_resume.h: k_plan_tour_resume, k_plan_tour_path_legs) is held to it bit for bit.  NOT planned:
-# smoothing of the legs, teams, moving hazards or regions, precedence (until), recurring visits, credit for a dwell in progress, more
-# than PLAN_TOUR_STATIONS_MAX stations.
+# smoothing of the legs, mates planning around each other, moving hazards or regions, precedence (until), recurring visits, credit
+# for a dwell in progress, more than PLAN_TOUR_STATIONS_MAX stations.
 PLAN_TOUR_STATIONS_MAX = 8          # 256 subsets of stations: the tour table of one robot fits a wave's LDS
 PLAN_TOUR_TICKS_MAX = 1 << 24       # every open, close and dwell in ticks is clamped here: 8 legs of them stay below 2^30
 PLAN_TOUR_INF = 0x3FFFFFFF          # "no feasible way" in the tour table
@@ -3177,18 +3177,12 @@ def spec_plan_tour(d0, D, E, open_c, close_c, dwell_c):
     return spec_plan_tour_resume(d0, D, E, np.zeros(n, np.int64), open_c, close_c, dwell_c, np.full(n, (1 << M) - 1, np.int64), 0, False)[:5]
 
 
-def spec_plan_tour_resume(d0, D, E, e0, open_c, close_c, dwell_c, todo, t0, partial):
-    """spec_plan_tour from the middle of a run: the one statement of the order rule (spec_plan_tour is this with every station to
-    do, t0 = 0 and partial off).  todo int [n]: the bit set of the stations robot r still has to visit; t0: the tick the plan starts
-    at; e0 int64 [n]: the start to the goal (0 without a goal, PLAN_ASSIGN_NONE: no path).  The table is filled for the masks that
-    are subsets of todo[r] only: t[{j}][j] = dep(j, t0 + d0[j]), the recurrence and dep as in spec_plan_tour.
-    partial off: the tour visits all of todo[r] and ends at the j of todo[r] minimising (t[todo][j] + E[j], j); with todo[r] == 0
-    there is no station leg and the total is t0 + e0 (feasible iff e0 is a real cost).
-    partial on: the visited set V, a subset of todo[r], and its last station j are the lexicographic minimum of (popcount(todo) -
-    popcount(V), t[V][j] + E[j], V as an integer, j) over the feasible entries; V = 0 is an entry with the total t0 + e0 and j = -1.
-    -> (feasible bool [n], cost int64 [n], order int32 [n][M], eta int64 [n][M], depart int64 [n][M], tour_len int32 [n] = |V|,
-    dropped int32 [n] = todo & ~V); order, eta and depart are -1 at the positions >= tour_len; without a feasible entry cost is
-    -1, tour_len 0 and dropped is todo."""
+def spec_plan_table(d0, D, open_c, close_c, dwell_c, todo, t0):
+    """The tour table, the one statement of its recurrence (spec_plan_tour_resume and spec_plan_best fill it here) -> (t int64
+    [n][1 << M][M], pred int8 [n][1 << M][M]).  t[V][j] is the earliest departure from station j after visiting exactly the
+    stations of V, j last, from the tick t0 on; it is filled for the masks that are subsets of todo[r] only and PLAN_TOUR_INF
+    everywhere else.  t[{j}][j] = dep(j, t0 + d0[j]); t[mask + j][j] = the minimum over the feasible i in mask of dep(j, t[mask][i] +
+    D[i][j]), taken of the pair (value, i): the lowest i wins a tie, and pred holds it (-1 at a single station)."""
     n, M = d0.shape
     INF, NONE = PLAN_TOUR_INF, PLAN_ASSIGN_NONE
     full = (1 << M) - 1
@@ -3219,6 +3213,27 @@ def spec_plan_tour_resume(d0, D, E, e0, open_c, close_c, dwell_c, todo, t0, part
                 take = val < best
                 best, via = np.where(take, val, best), np.where(take, i, via).astype(np.int8)
             t[:, mask, j], pred[:, mask, j] = best, via
+    return t, pred
+
+
+def spec_plan_tour_resume(d0, D, E, e0, open_c, close_c, dwell_c, todo, t0, partial):
+    """spec_plan_tour from the middle of a run: the one statement of the order rule (spec_plan_tour is this with every station to
+    do, t0 = 0 and partial off).  todo int [n]: the bit set of the stations robot r still has to visit; t0: the tick the plan starts
+    at; e0 int64 [n]: the start to the goal (0 without a goal, PLAN_ASSIGN_NONE: no path).  The table is filled for the masks that
+    are subsets of todo[r] only: t[{j}][j] = dep(j, t0 + d0[j]), the recurrence and dep as in spec_plan_tour.
+    partial off: the tour visits all of todo[r] and ends at the j of todo[r] minimising (t[todo][j] + E[j], j); with todo[r] == 0
+    there is no station leg and the total is t0 + e0 (feasible iff e0 is a real cost).
+    partial on: the visited set V, a subset of todo[r], and its last station j are the lexicographic minimum of (popcount(todo) -
+    popcount(V), t[V][j] + E[j], V as an integer, j) over the feasible entries; V = 0 is an entry with the total t0 + e0 and j = -1.
+    -> (feasible bool [n], cost int64 [n], order int32 [n][M], eta int64 [n][M], depart int64 [n][M], tour_len int32 [n] = |V|,
+    dropped int32 [n] = todo & ~V); order, eta and depart are -1 at the positions >= tour_len; without a feasible entry cost is
+    -1, tour_len 0 and dropped is todo."""
+    n, M = d0.shape
+    INF, NONE = PLAN_TOUR_INF, PLAN_ASSIGN_NONE
+    full = (1 << M) - 1
+    todo = np.asarray(todo, np.int64)
+    t0 = int(t0)
+    t, pred = spec_plan_table(d0, D, open_c, close_c, dwell_c, todo, t0)
     # the selection: a strict lexicographic < over ascending (V, j) keeps the lowest (V, j) of equal (left out, total)
     rows = np.arange(n)
     left = np.full(n, M + 1, np.int64)                           # stations of todo left out; M + 1: no entry yet
@@ -3302,7 +3317,166 @@ def spec_plan_resume_check(spec, n, pace, state, step0, partial):
     return done, todo, t0
 
 
-def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None, *, state=None, step0=0, partial=False):
+# ---- a team shares the stations: each station to one member, the team done as early as possible.  best is what a
+# subset costs a member, spec_plan_share the exact partition of the team's stations among its members; the device
+# (csrc/kernels_plan_spec_share.h: k_plan_tour_best, k_plan_team_share, k_plan_team_void) is held to both bit for bit.
+SPEC_SHARE_KEYS = ("share", "team_cover", "team_dropped", "team_makespan", "team_total", "team_done")
+SPEC_SHARE_OBJECTIVES = ("makespan", "sum")
+
+
+def spec_plan_share_size(size, objective):
+    """The refusals of share= and objective= that need no robot count, by name -> (size, objective)"""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or int(size) not in TEAM_SIZES:
+        raise ValueError(f"spec_plan: share must be a team size, one of {TEAM_SIZES}, got {size!r}")
+    if objective not in SPEC_SHARE_OBJECTIVES:
+        raise ValueError(f"spec_plan: objective must be one of {SPEC_SHARE_OBJECTIVES}, got {objective!r}")
+    return int(size), objective
+
+
+def spec_plan_share_check(n, size, objective):
+    """The refusals of spec_plan's share= and objective=, by name -> (size, objective): spec_plan_share_size's, and an n that does
+    not split into teams"""
+    size, objective = spec_plan_share_size(size, objective)
+    if int(n) % size != 0:
+        raise ValueError(f"spec_plan: {int(n)} robots do not split into teams of share = {size}")
+    return size, objective
+
+
+def spec_plan_best(d0, D, E, e0, open_c, close_c, dwell_c, T, t0):
+    """What every subset of the team's stations costs a robot -> best int64 [n][1 << M].  T int [n]: the bit set of the stations
+    the robot's team still has to visit.  With t = spec_plan_table(..., T, t0): best[r][V] = the minimum over the j of V with t[V][j]
+    and E[j] real of t[V][j] + E[j] -- the ticks at the end of the robot's best tour over exactly V, goal leg included --,
+    best[r][0] = t0 + e0[r] where e0[r] is a real cost, and PLAN_TOUR_INF where nothing is feasible and for every V that is not a
+    subset of T[r]."""
+    n, M = d0.shape
+    INF, NONE = PLAN_TOUR_INF, PLAN_ASSIGN_NONE
+    t, _ = spec_plan_table(d0, D, open_c, close_c, dwell_c, T, t0)
+    E = np.asarray(E, np.int64)
+    tot = np.where((t < INF) & (E[:, None, :] < NONE), t + E[:, None, :], INF)
+    best = tot.min(axis=2)
+    best[:, 0] = np.where(np.asarray(e0) < NONE, int(t0) + np.asarray(e0, np.int64), INF)
+    return best
+
+
+_SHARE_NONE = 1 << 40   # "no feasible split" in a row of the partition DP: above every sum of sixteen member costs
+
+
+def _spec_share_pass(best, add, cap):
+    """One pass of the partition DP over the members k = 0 .. size - 1 of every team at once.  best int64 [teams][size][256 or
+    fewer]; add: the terms are combined by + (else by max); cap int64 [teams] or None: a member's own cost above it is no term.
+    row[0][U] = best[0][U]; row[k][U] = the minimum over the V that are subsets of U of combine(row[k - 1][U \\ V], best[k][V]),
+    infeasible terms skipped, V ascending and compared by strict <: the lowest V of equal values.
+    -> (the last row int64 [teams][W], _SHARE_NONE where nothing is feasible -- a sum of sixteen costs may pass PLAN_TOUR_INF --,
+    choice int32 [teams][size][W]: the V taken, 0 where nothing is feasible)"""
+    nt, size, W = best.shape
+    INF, NO = PLAN_TOUR_INF, _SHARE_NONE
+    U = np.arange(W)
+    ok = best < INF if cap is None else (best < INF) & (best <= cap[:, None, None])
+    row = np.where(ok[:, 0], best[:, 0], NO)
+    choice = np.zeros((nt, size, W), np.int32)
+    for k in range(1, size):
+        new = np.full((nt, W), NO, np.int64)
+        for V in range(W):
+            sup = U[(U & V) == V]                                    # the U that hold V
+            prev, own = row[:, sup ^ V], best[:, k, V][:, None]
+            val = prev + own if add else np.maximum(prev, own)
+            take = ok[:, k, V][:, None] & (prev < NO) & (val < new[:, sup])
+            new[:, sup] = np.where(take, val, new[:, sup])
+            choice[:, k, sup] = np.where(take, V, choice[:, k, sup])
+        row = new
+    return row, choice
+
+
+def spec_plan_share(best, T, size, objective="makespan", partial=False):
+    """The stations of every team allotted to its members, exactly.  best int64 [n][1 << M]: spec_plan_best's; T int [n]: the team's
+    stations to visit, the same for every member; size: the team size (TEAM_SIZES; consecutive robots, team r // size, member
+    r % size).  -> (share int32 [n]: the bit set of the stations robot r visits, team): team a dict of team_cover, team_dropped
+    (int32 bit sets), team_makespan (int32), team_total (int64) and team_feasible (bool), each [n / size].
+
+    Primary pass over the members k and the U that are subsets of T.  "makespan": f[0][U] = best[0][U], f[k][U] = the minimum over
+    the subsets V of U of max(f[k - 1][U \\ V], best[k][V]); "sum": the same with +.  Infeasible terms are skipped.
+    Covered set C: without partial C = T, and the team is infeasible where f[size - 1][T] is PLAN_TOUR_INF; with partial C is the
+    lexicographic minimum of (popcount(T) - popcount(U), f[size - 1][U], U) over the feasible U, and the team is infeasible only
+    where no U is feasible.
+    Allotment: a sum pass under a cap, which makes (makespan, sum) exact lexicographically.  cap = f[size - 1][C] for "makespan",
+    none for "sum" (where f is g and one pass is made).  g[0][U] = best[0][U] where it is <= cap; g[k][U] = the minimum of g[k - 1][U
+    \\ V] + best[k][V] over the subsets V of U with best[k][V] <= cap, V ascending and compared by strict <, so that the lowest V
+    wins a tie; choice[k][U] is that V.  The backtrack starts at (size - 1, C), and member 0 gets what remains.
+    team_makespan is the largest member cost best[r][share[r]], team_total their sum (int64: every cost is below 2^28).  An
+    infeasible team: share 0, team_cover 0, team_dropped T, team_makespan and team_total -1."""
+    best = np.asarray(best, np.int64)
+    n, W = best.shape
+    size, objective = spec_plan_share_check(n, size, objective)
+    T = np.asarray(T, np.int64)
+    if T.shape != (n,) or np.any(T < 0) or np.any(T >= W):
+        raise ValueError(f"spec_plan_share: T must be [n] bit sets below {W}")
+    nt = n // size
+    if np.any(T.reshape(nt, size) != T[::size, None]):
+        raise ValueError("spec_plan_share: the members of a team must share one T")
+    if not isinstance(partial, (bool, np.bool_)):
+        raise ValueError(f"spec_plan: partial must be True or False, got {partial!r}")
+    NO = _SHARE_NONE
+    Tt, b = T[::size], best.reshape(nt, size, W)
+    add = objective == "sum"
+    f, choice = _spec_share_pass(b, add, None)
+    teams = np.arange(nt)
+    if partial:
+        pop = np.array([bin(u).count("1") for u in range(W)], np.int64)
+        key = (pop[Tt][:, None] - pop[None, :]) << 50 | f << 10 | np.arange(W)[None, :]      # f < 2^32, U < 2^10
+        key = np.where(f < NO, key, np.int64(1) << 62)
+        C = key.argmin(axis=1)                                                               # the first, hence the lowest, minimum
+    else:
+        C = Tt.copy()
+    feasible = f[teams, C] < NO
+    if not add:
+        _, choice = _spec_share_pass(b, True, np.where(feasible, f[teams, C], -1))
+    share = np.zeros((nt, size), np.int64)
+    U = np.where(feasible, C, 0)
+    for k in range(size - 1, 0, -1):
+        share[:, k] = choice[teams, k, U]
+        U = U ^ share[:, k]
+    share[:, 0] = U
+    cost = np.take_along_axis(b, share[:, :, None], axis=2)[:, :, 0]
+    team = {"team_cover": np.where(feasible, C, 0).astype(np.int32), "team_dropped": np.where(feasible, Tt & ~C, Tt).astype(np.int32),
+            "team_makespan": np.where(feasible, cost.max(axis=1), -1).astype(np.int32),
+            "team_total": np.where(feasible, cost.sum(axis=1), -1).astype(np.int64), "team_feasible": feasible}
+    return share.reshape(n).astype(np.int32), team
+
+
+def spec_team_result(result, spec, size):
+    """The team's verdict from the per-robot one (result: a dict with spec_result's spec_rho [n][C]; size: the team size, TEAM_SIZES,
+    consecutive robots).  Per clause the team's value is the MAXIMUM over the mates for eventually / stay -- someone did it; strict >
+    over ascending members, so the lowest member wins a tie -- and the MINIMUM for always / recur / until -- everyone kept it;
+    strict <.  -> team_rho float32 [n / size][C], team_member int32 [n / size][C] (the member, 0 .. size - 1, whose value it is),
+    team_robustness float32, team_weakest int32 and team_satisfied bool [n / size] by spec_result's rule (the minimum over the
+    clauses by strict <, ascending; satisfied: > 0).  An eventually that no mate's window has opened for reads -inf."""
+    if not isinstance(spec, Spec):
+        raise TypeError(f"spec must be a mobrob_amd.envs.goal_rules.Spec, not {type(spec).__name__}")
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or int(size) not in TEAM_SIZES:
+        raise ValueError(f"spec_team_result: size must be one of {TEAM_SIZES}, got {size!r}")
+    rho = np.asarray(result["spec_rho"], np.float32)
+    if rho.ndim != 2 or rho.shape[1] != spec.n_clauses:
+        raise ValueError(f"spec_team_result: spec_rho must be [n][{spec.n_clauses}], got shape {rho.shape}")
+    n, C = rho.shape
+    size = int(size)
+    if n % size != 0:
+        raise ValueError(f"spec_team_result: {n} robots do not split into teams of {size}")
+    r = rho.reshape(n // size, size, C)
+    some = np.array([cl[0] in (SPEC_EVENTUALLY, SPEC_STAY) for cl in spec.clauses])
+    val, who = r[:, 0].copy(), np.zeros((n // size, C), np.int32)
+    for m in range(1, size):
+        take = np.where(some[None, :], r[:, m] > val, r[:, m] < val)
+        val, who = np.where(take, r[:, m], val), np.where(take, m, who).astype(np.int32)
+    rob, weak = val[:, 0].copy(), np.zeros(n // size, np.int32)
+    for c in range(1, C):
+        take = val[:, c] < rob
+        rob, weak = np.where(take, val[:, c], rob), np.where(take, c, weak).astype(np.int32)
+    return {"team_rho": val.astype(np.float32), "team_member": who, "team_robustness": rob.astype(np.float32), "team_weakest": weak,
+            "team_satisfied": rob > 0}
+
+
+def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None, *, state=None, step0=0, partial=False, share=None,
+              objective="makespan"):
     """The plan of n robots from a specification (DESIGN 4.12.9) -> dict.  grid: a GridSpec; walls / hazards: static, or None;
     spec: a Spec of the plannable fragment (spec_plan_parse); start [n][P]; goal [n][P] or None: where every robot ends after its
     last station; K waypoint slots; pace: the steps a robot is given for one orthogonal move (spec_plan_pace).
@@ -3336,6 +3510,18 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None, *, 
     tour_len.  With todo[r] == 0 the plan is the goal leg alone, cost t0 + its ticks; without a goal it is PLANNED with count 0.
     The waypoints and releases are stitched over the tour_len legs and the goal leg by the one loop below.
 
+    A team shares the stations (share=size, objective="makespan" or "sum"; the outputs SPEC_SHARE_KEYS).  Teams
+    are Teams' teams: `size` consecutive robots, n a multiple of size.  team_done bool [n / size][M]: a station is done for the team
+    once any member's clause reads satisfied; T, the team's stations to visit, is the rest.  spec_plan_best gives what every subset
+    of T costs each member, spec_plan_share allots every station of the covered set team_cover to exactly one member -- the
+    smallest makespan and under it the smallest sum of the members' costs, or the smallest sum --; with partial the team covers
+    the largest set it can and team_dropped is the rest, without it an infeasible team has every member UNREACHABLE with count 0,
+    cost -1, orders -1 and share 0.  share int32 [n]: the member's stations; its tour, waypoints and releases are those of todo =
+    share[r] with partial off, its cost best[r][share[r]] (a member with an empty share plans the goal leg alone), and its
+    dropped is 0 -- the team's loss is team_dropped -- except in a team of one, where it is the team's.  team_makespan int32 and
+    team_total int64 [n / size]: the largest member cost and their sum, -1 for an infeasible team.  share=1 is the plan without
+    share=, bit for bit, for both objectives; share=None is the call it was.  Mates do not plan around each other.
+
     Limitations: pace is an estimate of the policy's speed; a robot that arrives later than planned dwells for less time (the
     release is a global step, not a duration); a dwell in progress earns no credit (spec_plan_done); the monitor after the run
     remains the judge."""
@@ -3343,6 +3529,8 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None, *, 
     avoid, stations, (open_c, close_c, dwell_c), S, scene, start, goal, K, pace = spec_plan_check(grid, walls, hazards, spec, start,
                                                                                                  goal, K, pace)
     done, todo, t0 = spec_plan_resume_check(spec, start.shape[0], None if raw_pace is None else pace, state, step0, partial)
+    if share is not None:
+        share, objective = spec_plan_share_check(start.shape[0], share, objective)
     reg = spec.regions
     n, P = start.shape
     G, M = grid.cells, len(stations)
@@ -3369,8 +3557,25 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None, *, 
     else:
         E, e0 = np.zeros((n, M), np.int64), np.zeros(n, np.int64)
     # a station without an anchor has a field of -1 everywhere: nothing reaches it or leaves it, so a tour that holds it is infeasible
-    ok, cost, order, eta, depart, tour_len, dropped = spec_plan_tour_resume(
-        d0, D, E, e0, open_c.astype(np.int64), close_c.astype(np.int64), dwell_c.astype(np.int64), todo, t0, bool(partial))
+    ticks = (open_c.astype(np.int64), close_c.astype(np.int64), dwell_c.astype(np.int64))
+    shared = {}
+    if share is None:
+        ok, cost, order, eta, depart, tour_len, dropped = spec_plan_tour_resume(d0, D, E, e0, *ticks, todo, t0, bool(partial))
+    else:
+        # a station is done for the team once it is for any member; the members' tours are spec_plan_tour_resume's over their shares
+        size = share
+        team_done = done.reshape(n // size, size, M).any(axis=1)
+        T = np.repeat(((~team_done).astype(np.int64) << np.arange(M)).sum(axis=1), size)
+        best = spec_plan_best(d0, D, E, e0, *ticks, T, t0)
+        mine, team = spec_plan_share(best, T, size, objective, bool(partial))
+        ok, cost, order, eta, depart, tour_len, dropped = spec_plan_tour_resume(d0, D, E, e0, *ticks, mine, t0, False)
+        lost = ~np.repeat(team["team_feasible"], size)             # an infeasible team: every member UNREACHABLE, nothing planned
+        ok, cost, tour_len = ok & ~lost, np.where(lost, -1, cost), np.where(lost, 0, tour_len).astype(np.int32)
+        order[lost], eta[lost], depart[lost] = -1, -1, -1
+        # a member of a feasible team drops nothing (its share is feasible by construction): the team's loss is team_dropped.  A
+        # team of one is the robot, and its loss the robot's -- what spec_plan_tour_resume reports for it without share=
+        dropped = np.where(lost, T, np.repeat(team["team_dropped"], size) if size == 1 else 0).astype(np.int32)
+        shared = {"share": mine, "team_done": team_done, **team}
     wp, release = np.zeros((n, K, P), np.float32), np.zeros((n, K), np.int32)
     count, status = np.zeros(n, np.int32), np.full(n, UNREACHABLE, np.int32)
     swp = np.full((n, M), -1, np.int32)
@@ -3408,4 +3613,4 @@ def spec_plan(grid, walls, hazards, spec, start, goal=None, K=16, pace=None, *, 
             "cost": cost.astype(np.int32), "tour_order": order, "tour_eta": eta.astype(np.int32), "station_waypoint": swp,
             "release": release, "station_cell": cell, "station_margin": margin, "covered": margin >= np.float32(REACH_RADIUS),
             "matrix": matrix, "occupancy": occ, "open_c": open_c, "close_c": close_c, "dwell_c": dwell_c, "pace": pace,
-            "tour_len": tour_len, "dropped": dropped, "done": done, "t0": t0}
+            "tour_len": tour_len, "dropped": dropped, "done": done, "t0": t0, **shared}

@@ -358,7 +358,8 @@ class GridPlanner:
             res["sweeps"] = out["sweeps"]
         return res
 
-    def plan_spec(self, start, spec, goal=None, pace=None, max_waypoints=None, *, state=None, step0=0, partial=False):
+    def plan_spec(self, start, spec, goal=None, pace=None, max_waypoints=None, *, state=None, step0=0, partial=False, share=None,
+                  objective="makespan"):
         """A plan from a specification: the avoid clauses of `spec` (Spec.always(outside(...)) over the whole run)
         become obstacles beside the planner's walls and hazards, its reach clauses (Spec.eventually / Spec.stay over inside(...),
         at most 8) stations, and per robot the order of the stations is chosen -- the shortest tour that keeps every window and
@@ -377,7 +378,12 @@ class GridPlanner:
         monitor's SpecState, or the run's FollowState, whose .spec and .step0 are then taken (a step0= that disagrees is refused,
         as is a FollowState of a run without a specification); the stations whose clause is already satisfied are left out, the
         plan starts at step0, and with partial=True a robot keeps the stations it can still keep.  The dict then also holds
-        tour_len, dropped and done (SPEC_REPLAN_KEYS).  A dwell in progress earns no credit: the robot dwells again in full."""
+        tour_len, dropped and done (SPEC_REPLAN_KEYS).  A dwell in progress earns no credit: the robot dwells again in full.
+        A team shares the stations (goal_rules.spec_plan's share=, objective=; device: mobrob_ppo_spec_plan_share):
+        share is the team size (consecutive robots, as Teams), and each station the team still has to visit goes to one member --
+        the smallest makespan, then the smallest sum of the members' costs, or with objective="sum" the smallest sum.  The dict then
+        also holds share, team_cover, team_dropped, team_makespan, team_total and team_done (SPEC_SHARE_KEYS).  The planner itself
+        still has no teams=: mates do not plan around each other on their tours."""
         from .waypoints import FollowState
         if isinstance(state, FollowState):
             if state.spec is None:
@@ -396,13 +402,14 @@ class GridPlanner:
             raise ValueError(f"plan_spec: start must be [n_robots, {self.pos_dim}], got shape {start.shape}")
         if self.device:
             out = self.engine.plan_spec(self.spec, self.walls, self.hazards, spec=spec, start=start, goal=goal, pace=pace, max_waypoints=K,
-                                        state=state, step0=step0, partial=partial)
+                                        state=state, step0=step0, partial=partial, share=share, objective=objective)
         else:
-            out = rules.spec_plan(self.spec, self.walls, self.hazards, spec, start, goal, K, pace, state=state, step0=step0, partial=partial)
+            out = rules.spec_plan(self.spec, self.walls, self.hazards, spec, start, goal, K, pace, state=state, step0=step0, partial=partial,
+                                  share=share, objective=objective)
         out["schedule"] = rules.Schedule(out["release"], home=start) if np.any(out["release"] != 0) else None
         return out
 
-    def spec_callback(self, spec, goal=None, pace=None, partial=True, when="stalled"):
+    def spec_callback(self, spec, goal=None, pace=None, partial=True, when="stalled", share=None, objective="makespan"):
         """The planner of waypoints.follow_with_replanning for a run that follows a plan from a specification: its attribute
         `wants_state` is True, so the loop calls it as planner(positions, status, reached, state=the run's FollowState), and it
         plans again with plan_spec(positions, spec, goal, pace, state=state, partial=partial): the stations the monitor has seen
@@ -410,11 +417,15 @@ class GridPlanner:
         when="all": every robot that is not FINISHED.  A chosen robot whose new plan is PLANNED with count > 0 gets
         (waypoints[:count], release[:count]) -- so the run needs a schedule from its first call --; the others are left alone.
         `callback.last` holds the latest plan (None before the first, and after a call without a robot to replan the plan of the
-        call before), `callback.calls` counts the calls.  The monitor is read, never written."""
+        call before), `callback.calls` counts the calls.  The monitor is read, never written.
+        share= (a team size) and objective=: the plan is plan_spec(..., share=, objective=), and a team with any chosen member is
+        replanned as a whole: every member that is not FINISHED and whose new plan is PLANNED with count > 0 gets its tuple."""
         from .waypoints import FINISHED, STALLED
         if when not in ("stalled", "all"):
             raise ValueError(f"spec_callback: when must be 'stalled' or 'all', got {when!r}")
         rules.spec_plan_parse(spec)
+        if share is not None:
+            share, objective = rules.spec_plan_share_size(share, objective)     # the robots are counted when the plan is made
 
         def planner(positions, status, reached, state=None):
             planner.calls += 1
@@ -425,8 +436,11 @@ class GridPlanner:
             chosen = np.nonzero(status == STALLED if when == "stalled" else status != FINISHED)[0]
             if chosen.size == 0:
                 return {}
-            plan = self.plan_spec(positions, spec, goal=goal, pace=pace, state=state, partial=partial)
+            plan = self.plan_spec(positions, spec, goal=goal, pace=pace, state=state, partial=partial, share=share, objective=objective)
             planner.last = plan
+            if share is not None:                          # the whole team of a chosen robot, its finished members aside
+                mates = np.unique(chosen // share)[:, None] * share + np.arange(share)
+                chosen = np.array([i for i in mates.ravel() if status[i] != FINISHED], np.int64)
             return {int(i): (plan["waypoints"][i, :plan["count"][i]].copy(), plan["release"][i, :plan["count"][i]].copy())
                     for i in chosen if plan["status"][i] == rules.PLANNED and plan["count"][i] > 0}
         planner.last, planner.calls, planner.wants_state = None, 0, True

@@ -590,6 +590,14 @@ def monitor(path, spec, step0=0, state=None, engine=None):
     return new, spec_result(new, spec)
 
 
+def spec_team_result(result, spec, size):
+    """The team's verdict of a run with a specification, from a call's dict or monitor()'s (its spec_rho [n][C]): per clause the
+    maximum over the `size` mates for eventually / stay -- someone did it -- and the minimum for always / recur / until -- everyone
+    kept it.  goal_rules.spec_team_result: team_rho, team_member, team_robustness, team_weakest, team_satisfied, each per team."""
+    from .envs.goal_rules import spec_team_result as rule
+    return rule(result, spec, size)
+
+
 def _spec_check_call(spec, path_stride, state):
     """`spec=` of a call: the type, the stride the monitor needs and the run's state.  -> the SpecState at entry, or None (the
     call starts the run: spec_start once the robots are counted)"""
